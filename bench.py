@@ -28,6 +28,22 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0            # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: all files of one run together
+
+
+def dump_outputs(directory: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """--dump-outputs: what the last timed step computed, each array as DIR/<name>.npy in float32 (float64 stays float64; RGBA8 bytes
+    convert exactly).  Every array gets an equal share of `limit`; one larger than its share is written as a fixed, seeded sample of its
+    elements (flattened; the same positions on every run), so that two builds can be compared output for output."""
+    os.makedirs(directory, exist_ok=True)
+    share = limit // max(len(arrays), 1) - 4096                         # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _hip():
@@ -345,6 +361,12 @@ def views_workload(args, rank, world, dev, workload=None, steps=None, emit=True)
     if world > 1:
         dist.barrier()
     dt_python = time.perf_counter() - t0
+
+    def last_step():                                               # --dump-outputs: the caller's destination buffers as the last step left them
+        if scope:
+            return {f"{k}_ch{c}": np.array(a) for c, (xyz, col) in enumerate(outs) for k, a in (("xyz", xyz), ("rgba", col))}
+        return {"xyz": np.array(outs[0]), "rgb": np.array(outs[1])}
+    dump = last_step() if args.dump_outputs and emit else None
     # the same loop with the host side in C++ (tools/rt_driver.cpp -> signalizer_amd/librtdriver.so: what a plugin's audio callback and
     # paint would execute; the Python loop above pays 60-100 us of interpreter and ctypes time per frame on top of the library's own)
     dt = dt_python
@@ -380,6 +402,8 @@ def views_workload(args, rank, world, dev, workload=None, steps=None, emit=True)
         if d < 0:
             raise RuntimeError(f"rt_driver: C-ABI call failed ({d})")
         dt, host = float(d), "c++ (tools/rt_driver.cpp)"
+        if dump is not None:
+            dump = last_step()
         refused += busy.value
         assert verts.value == units, (verts.value, units)
         # the same frames with the vertex streams left in HBM (caller-owned DEVICE buffers: a mapped vertex buffer object / exported memory
@@ -398,6 +422,8 @@ def views_workload(args, rank, world, dev, workload=None, steps=None, emit=True)
         refused += busy.value
         assert verts.value == units, (verts.value, units)
         dt_resident = float(d2)
+    if dump is not None:
+        dump_outputs(args.dump_outputs, {(k if world == 1 else f"{k}_rank{rank}"): a for k, a in dump.items()}, DUMP_LIMIT_BYTES // world)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -596,7 +622,13 @@ def main() -> None:
                          "torch.distributed's RCCL backend) and SAYS SO: on stderr and in config.shard_impl of the line (with the error) -- a "
                          "scaling record with a disclosed fall-back instead of none")
     ap.add_argument("--allow-torch-fallback", action="store_true", help="(the default since round 5; kept for old command lines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the arrays its caller receives: the RGBA8 columns; "
+                         "cfg3 / cfg4: the vertex and colour buffers) as DIR/<name>.npy in float32, at most 64 MB in all; the inputs are "
+                         "seeded, so two builds run with the same arguments can be compared output for output.  N ranks: <name>_rank<r>")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from signalizer_amd import api, config, synth
@@ -746,6 +778,9 @@ def main() -> None:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:                                           # (untimed; before the passes below overwrite the step's image)
+        dump_outputs(args.dump_outputs, {"rgba" if world == 1 else f"rgba_rank{rank}": shard.rgba[:frames_per_rank].cpu().numpy()},
+                     DUMP_LIMIT_BYTES // world)
     enq_ms = None
     if graph is not None:                                           # the same K steps enqueued one by one (diagnostic, untimed for `value`)
         torch.cuda.synchronize()

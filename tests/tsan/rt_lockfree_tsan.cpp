@@ -300,6 +300,7 @@ struct SpectrumHandle {
     std::atomic<uint32_t> lines[kLineSlots][kP];         // relaxed atomics: see the file comment
     MockEvent lineEv[kLineSlots];
     std::atomic<uint64_t> dropped{0}, busy{0}, frames{0};
+    uint64_t lineReads = 0, lapped = 0;                  // consumer thread only: line-results reads, and those the seqlock discarded
 
     SpectrumHandle()
     {
@@ -385,8 +386,19 @@ struct SpectrumHandle {
             const uint64_t n = lineSeq.newest(landed, &none);
             if (n == 0) { if (none) return 0; continue; }
             uint32_t out[kP];
-            for (int i = 0; i < kP; ++i) out[i] = lines[lineSeq.slotOf(n)][i].load(std::memory_order_relaxed);
-            if (!lineSeq.stillValid(n)) continue;
+            const int ls = lineSeq.slotOf(n);
+            for (int i = 0; i < kP / 2; ++i) out[i] = lines[ls][i].load(std::memory_order_relaxed);
+            // every 256th read stalls in mid-copy until the producer has lapped it (bounded: the producer may be done): the rewrite of the
+            // slot then lands in the second half of the copy, so the seqlock's discard path is taken on purpose, not only when the
+            // threads happen to collide -- a seqlock that misses the lap returns a torn read and fails the CHECK below.  (The wait polls
+            // with relaxed loads and sleeps: no happens-before edge that could hide a race from ThreadSanitizer.)
+            if (++lineReads % 256 == 0) {
+                const auto until = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
+                while (lines[ls][kP / 2].load(std::memory_order_relaxed) == uint32_t(n) && std::chrono::steady_clock::now() < until)
+                    std::this_thread::sleep_for(std::chrono::microseconds(20));
+            }
+            for (int i = kP / 2; i < kP; ++i) out[i] = lines[ls][i].load(std::memory_order_relaxed);
+            if (!lineSeq.stillValid(n)) { ++lapped; continue; }
             for (int i = 0; i < kP; ++i) CHECK(out[i] == uint32_t(n));
             return n;
         }
@@ -442,9 +454,10 @@ static void scenarioSpectrum(uint64_t blocks)
     h.gpu.synchronize();
     CHECK(h.nextExpected == blocks);                     // every block reached the GPU side, in order, exactly once
     CHECK(h.lineResults() == blocks);                    // the newest copy, whole
-    std::printf("spectrum handle: %llu blocks, %llu waited in the host FIFO, %llu pushes refused, %llu columns dropped by a full queue\n",
+    std::printf("spectrum handle: %llu blocks, %llu waited in the host FIFO, %llu pushes refused, %llu columns dropped by a full queue, "
+                "%llu line-results reads lapped\n",
                 static_cast<unsigned long long>(blocks), static_cast<unsigned long long>(h.bl.deferred), static_cast<unsigned long long>(h.busy.load()),
-                static_cast<unsigned long long>(h.dropped.load()));
+                static_cast<unsigned long long>(h.dropped.load()), static_cast<unsigned long long>(h.lapped));
 }
 
 int main(int argc, char **argv)

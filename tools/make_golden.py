@@ -2,7 +2,7 @@
 
 The reference ships no tests or golden vectors and cannot be built here, so these
 fixtures pin the oracle itself (against silent regressions) and give the GPU tests a data-only target
-that travels to the GPU box.  Exception: hsb_table.npz and colour_tables.npz come from the reference's own
+that travels to the GPU box.  Exception: hsb_table.npz, hsb_rotation_200k.npz and colour_tables.npz come from the reference's own
 juce::Colour::withRotatedHue, compiled from /root/reference (oracle/ref_juce_colour.cpp).  Inputs are re-synthesised from seeds (signalizer_amd.synth), only
 parameters and expected outputs are stored.  Run:  python tools/make_golden.py
 """
@@ -82,6 +82,7 @@ def main():
         tables["base_" + name] = base
         tables["table_" + name] = t
     np.savez_compressed(os.path.join(OUT, "colour_tables.npz"), **tables)
+    hsb_rotation_200k(pyref)
     # zero-crossing triggers (KA11)
     sig = synth.gen(3, 192000, 48000, 2)
     st = po.ZeroCrossingState(state=0.0, threshold=0.05, steady_clock=0, cross_origin=0, count=0, armed=0)
@@ -97,6 +98,27 @@ def main():
     R = np.array([0, 1, 1, -1, 0, 0.25, 0.5, -1e-8], np.float32)
     np.savez_compressed(os.path.join(OUT, "polar_cases.npz"), L=L, R=R, xyz=po.vector_polar(L, R))
     print("golden fixtures written to", OUT, {f: os.path.getsize(os.path.join(OUT, f)) for f in sorted(os.listdir(OUT))})
+
+
+def ka9_inputs(seed: int = 2026, n: int = 200000):
+    """the colours and rotation amounts of tests/test_oracle_math.py::test_KA9_hsb_rotation_equals_the_compiled_reference (the same recipe is restated there)"""
+    rng = np.random.default_rng(seed)
+    cols = rng.integers(0, 256, (n, 3)).astype(np.uint8)
+    amt = rng.random(n).astype(np.float32)
+    amt[: 16 * 17 // 2] = [np.float32(i) / np.float32(p) for p in range(1, 17) for i in range(p)]        # index / size as ColourRotation computes it
+    return cols, amt
+
+
+def hsb_rotation_200k(pyref, seed: int = 2026, n: int = 200000):
+    """KA9's 200 000 rotations through the reference's own withRotatedHue: only the seed and the outputs are stored"""
+    import ctypes as C
+    cols, amt = ka9_inputs(seed, n)
+    L, vp = pyref.lib(), C.c_void_p
+    out = np.zeros((n, 3), np.uint8)
+    for i in range(n):
+        L.sgzref_rotate_hue_rgb8(vp(cols[i].ctypes.data), C.c_float(float(amt[i])), vp(out[i].ctypes.data))
+    np.savez_compressed(os.path.join(OUT, "hsb_rotation_200k.npz"), seed=seed, n=n, rotated=out,
+                        source="juce::Colour::withRotatedHue, compiled reference")
 
 
 if __name__ == "__main__":
