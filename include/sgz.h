@@ -192,9 +192,9 @@ sgz_status sgz_plan_reset_resonator(sgz_plan *plan, void *stream);
 #define SGZ_OPT_RESONATOR_SLAB 5u   /* RSNT: frames per slab of a long render (the per-frame resonator states between the kernels are held for one
                                       slab at a time; 0, the default: as many frames as fit 256 MiB).  A slab continues the state the one
                                       before it left.  It plays no part in the sharded render (SGZ_OPT_RESONATOR_SHARD_BOUND) */
-#define SGZ_OPT_WIDE_GROUPS 6u       /* N = 32768 channel-split plans (pairs): 0 (default): one 512-thread workgroup per (frame, pair, channel), 32 values
-                                      per thread (spectrum_real.hip); 1: 1024 threads of sixteen values (spectrum_real16.hip: 8 waves per SIMD; measured
-                                      7-12 % slower on MI355X -- NOTES.md round 5 -- and kept as a tested alternative) */
+#define SGZ_OPT_WIDE_GROUPS 6u       /* retired: N = 32768 channel-split plans always run the 512-thread form (spectrum_real.hip).  The 1024-thread form
+                                      this selected measured 7-12 % slower; the option is accepted for source compatibility, any
+                                      value returns SGZ_OK and changes nothing */
 #define SGZ_OPT_RESONATOR_SHARD_BOUND 7u /* RSNT, sgz_spectrogram_render_sharded only: that render holds the per-frame resonator states of a rank's WHOLE
                                       chunk between its two halves (from rest ... carry + windows) and cannot cut it, so this is a bound, in frames
                                       (0, the default: 8 GiB worth): a rank's chunk above it is refused with SGZ_EUNSUPPORTED on every rank before

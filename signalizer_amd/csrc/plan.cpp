@@ -991,35 +991,6 @@ sgz_status buildPlan(const sgz_spectrum_config &cfg, Plan &p, std::string &err)
             p.twRealPost[size_t(kc) * 2 + 0] = float(std::cos(ang));
             p.twRealPost[size_t(kc) * 2 + 1] = float(std::sin(ang));
         }
-        // The 1024-thread form of the N = 32768 channel transform (spectrum_real16.hip): M = 16 x 16 x (4 across a lane quad x 16).
-        //   tw16: [16 q2][64 c_lo] W_1024^{c_lo q2} (pass 2), then [4 l][16 r] sign_l W_64^{r m}, m = brev2(l) (pass 3: the quad's
-        //         radix-4 stage leaves lane l with sign_l a_m, signs (+, -, -, -): tools/emulate_real16.py), staged in LDS by every workgroup
-        //   twPost16: [1024] W_N^{kb}, kb = q1 + 16 q2 + 256 m: the recombination twiddle of a thread's first bin
-        p.tw16.clear(); p.twPost16.clear();
-        if (p.N == 32768 && p.realSplit) {
-            p.tw16.resize(size_t(16 * 64 + 4 * 16) * 2);
-            for (uint32_t q = 0; q < 16; ++q)
-                for (uint32_t c = 0; c < 64; ++c) {
-                    const double ang = -kTwoPi * double((q * c) % 1024u) / 1024.0;
-                    p.tw16[(size_t(q) * 64 + c) * 2 + 0] = float(std::cos(ang));
-                    p.tw16[(size_t(q) * 64 + c) * 2 + 1] = float(std::sin(ang));
-                }
-            for (uint32_t l = 0; l < 4; ++l) {
-                const uint32_t m = ((l & 1u) << 1) | (l >> 1);
-                const double sign = l == 0 ? 1.0 : -1.0;
-                for (uint32_t r = 0; r < 16; ++r) {
-                    const double ang = -kTwoPi * double((r * m) % 64u) / 64.0;
-                    p.tw16[(size_t(16 * 64) + size_t(l) * 16 + r) * 2 + 0] = float(sign * std::cos(ang));
-                    p.tw16[(size_t(16 * 64) + size_t(l) * 16 + r) * 2 + 1] = float(sign * std::sin(ang));
-                }
-            }
-            p.twPost16.resize(size_t(1024) * 2);
-            for (uint32_t kb = 0; kb < 1024; ++kb) {
-                const double ang = -kTwoPi * double(kb) / double(p.N);
-                p.twPost16[size_t(kb) * 2 + 0] = float(std::cos(ang));
-                p.twPost16[size_t(kb) * 2 + 1] = float(std::sin(ang));
-            }
-        }
     }
     return SGZ_OK;
 }

@@ -99,7 +99,6 @@ struct Plan {
     std::vector<float> windowHalf;      // channel-split path: window / 2 (those kernels transform x w / 2: real_common.hpp realBinMag)
     std::vector<float> winPhase; float winP0 = 0.f, winP1 = 0.f;   // channel-split path, Hann / Hamming periodic: the window is computed in the kernel
     std::vector<float> twRealPost;      // W_N^{kc}, kc < R1 * 32: the real-FFT recombination twiddle of a thread's bins
-    std::vector<float> tw16, twPost16;  // the 1024-thread form of the N = 32768 channel transform (spectrum_real16.hip): pass-2 / pass-3 twiddles (LDS-staged), W_N^{kb}
     std::vector<float> tw2Full;         // channel-split kernels, N >= 32768: the whole pass-2 table W_1024^{c q} as [c < 32][34] float2 (re, im), q < 32 used, two pad entries per row (a thread's 32 factors are 16 ds_read_b128); staged in LDS
     // Chunk-scan pixel map of the channel-split kernels (chunk_map.hpp, built by buildChunkMap): a side's M magnitudes are cut into
     // T chunks of 32 consecutive entries, one per thread; the arg-max runs of >= 2 entries ("tiles") are segments of a segmented
@@ -122,7 +121,7 @@ struct Plan {
     float resWeights[9] = {0};          // [V]
     DeviceScalars scalars{};
     // sgz_plan_set_option
-    bool optChannelSplit = true, optFusedColour = true, optFetchWindow = false, optWideGroups = false;
+    bool optChannelSplit = true, optFusedColour = true, optFetchWindow = false;
     bool optPipelined = false;          // the plan is a lane of an sgz_render_queue of depth >= 2 (RealParams::pipelined)
     uint32_t optFusedPixels = 4;        // pixels per workgroup of the fused colour K_B (4, 8, 16): SGZ_OPT_FUSED_COLOUR = 1 / 8 / 16
     int optMatrixResonator = 2;        // 0: vector ALUs, 1: bf16 matrix cores (three-part split; opt-in: on MI355X its instruction stream disturbs FFT
@@ -154,7 +153,7 @@ struct Plan {
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;
-    float *d_tw16 = nullptr, *d_twPost16 = nullptr, *d_windowHalf = nullptr;
+    float *d_windowHalf = nullptr;
     float *d_twReal1 = nullptr, *d_twRealPost = nullptr, *d_winPhase = nullptr, *d_winPhaseT = nullptr;
     uint32_t *d_chunkEnds = nullptr, *d_chunkReBase = nullptr, *d_chunkRec = nullptr; float *d_weights12 = nullptr;
     float *d_ny = nullptr, *d_nyBest = nullptr; size_t nyCap = 0;   // channel-split path: what a frame's two channel workgroups leave for realLateKernel

@@ -1,5 +1,4 @@
-// real_common.hpp -- helpers shared by the two forms of the channel-split K_A: spectrum_real.hip (R1 x 32 threads of 32 values) and
-// spectrum_real16.hip (1024 threads of 16 values, N = 32768).  gfx950 only.
+// real_common.hpp -- helpers of the channel-split K_A (spectrum_real.hip: R1 x 32 threads of 32 values).  gfx950 only.
 #pragma once
 #include "chunk_map.hpp"
 #include "fft_scalar.hpp"
@@ -104,15 +103,5 @@ inline hipError_t grantLds(const void *kernel, size_t need, size_t (&granted)[64
     if (e == hipSuccess && dev >= 0 && dev < 64) granted[dev] = need;
     return e;
 }
-
-// LDS bytes of the 1024-thread form (spectrum_real16.hip): |X| / exchange areas, then the LDS-staged twiddle tables ([16][64] + [4][16] float2,
-// 16-byte aligned) and column 0's scratch (128 floats) -- or, later in a workgroup's life, the map's tile and row maxima
-constexpr size_t real16LdsBytes(uint32_t maxSlots)
-{
-    const size_t a = size_t((realXFloats(16384) + 3) & ~3) + (16 * 64 + 4 * 16) * 2 + 128, b = size_t(realXFloats(16384)) + maxSlots + 1 + 512;
-    return (a > b ? a : b) * 4;
-}
-// spectrum_real16.hip: the 1024-thread form (N = 32768, pairs); binsIn: the bins-injection hook on that form's pixel map
-hipError_t launchStftReal16(const RealParams &prm, hipStream_t stream);
 
 }  // namespace sgz

@@ -857,8 +857,6 @@ hipError_t launchStftReal(const RealParams &prm, uint32_t N, hipStream_t stream)
     const bool mono = prm.mode != SGZ_CH_SEPARATE && prm.mode != SGZ_CH_MIDSIDE;
     const long units = prm.frames * long(prm.C) * (mono ? 1 : 2);
     if (units <= 0) return hipSuccess;
-    // N = 32768, pairs: the 1024-thread form (spectrum_real16.hip) unless the plan switched it off or its LDS layout does not fit
-    if (N == 32768 && !mono && prm.tw16 && real16LdsBytes(std::max(prm.chunkSlots[0], prm.chunkSlots[1])) <= 80 * 1024) return launchStftReal16(prm, stream);
     const uint32_t M = N / 2, T = M / 32;
     const uint32_t maxSlots = std::max(prm.chunkSlots[0], prm.chunkSlots[1]);
     // magnitudes, then the map's tile / chunk maxima (the same floats hold column 0's scratch during the recombination), then (mono) the complex entries

@@ -474,21 +474,18 @@ def test_unsupported_and_errors(gpu):
     # MidSide: the same two workgroups on (l + r) / 2 and (l - r) / 2
     (32768, 48000.0, 2, 5, dict(channel_mode=config.CH_MIDSIDE)), (65536, 96000.0, 1, 3, dict(channel_mode=config.CH_MIDSIDE)),
     (16384, 48000.0, 1, 7, dict(channel_mode=config.CH_MIDSIDE)),
-    # the 1024-thread form of the N = 32768 kernel (spectrum_real16.hip; plan option SGZ_OPT_WIDE_GROUPS)
-    (32768, 48000.0, 1, 5, dict(wide=1)), (32768, 48000.0, 3, 4, dict(wide=1)), (32768, 48000.0, 2, 4, dict(view_scaling=0, wide=1)),
-    (32768, 48000.0, 2, 5, dict(channel_mode=config.CH_MIDSIDE, wide=1)), (32768, 44100.0, 1, 4, dict(window_type=config.WIN_BLACKMAN_HARRIS, wide=1))])
+    # a fetched window at 44.1 kHz
+    pytest.param(32768, 44100.0, 1, 4, dict(window_type=config.WIN_BLACKMAN_HARRIS), id="32768-44100.0-1-4-blackman-harris")])
 def test_channel_split_kernel_against_the_oracle(gpu, oracle, monkeypatch, N, sr, pairs, frames, over):
     """spectrum_real.hip (one workgroup per (frame, pair, channel), real-input FFT; the default at N = 16384 and 65536, forced here at
     N = 32768 too) through the parity chain, and bin for bin against the whole-frame kernels: same csf within the FFT tolerance -- including
     csf[0], csf[N], csf[N/2 - 1] (quirk Q3) and csf[N/2], the one entry that needs both channels and is settled by whichever
     workgroup finishes second -- and identical pixels given identical bins."""
     from parity_chain import check_render
-    over = dict(over)
-    wide = over.pop("wide", 0)
     cfg = config.spectrum_config(sample_rate=sr, window_size=N, hop=N // 4, num_pairs=pairs, **over)
     S = N + (frames - 1) * (N // 4)
     x = synth.gen(23, int(sr), S, 2 * pairs)
-    split = api.Plan(cfg).set_option(api.OPT_WIDE_GROUPS, wide).upload()
+    split = api.Plan(cfg).upload()
     whole = api.Plan(cfg).set_option(api.OPT_CHANNEL_SPLIT, 0).upload()
     assert split.path & 8 and not whole.path & 8
     xg = _planar_cuda(x, gpu)
@@ -503,6 +500,13 @@ def test_channel_split_kernel_against_the_oracle(gpu, oracle, monkeypatch, N, sr
     x[0] = 0; x[1] = 0
     m = split.stage_mapped(_planar_cuda(x, gpu)).cpu().numpy()
     assert not m[:, 0].any() and np.isfinite(m).all()
+    if N == 32768:
+        # SGZ_OPT_WIDE_GROUPS is retired: still accepted, and the plan runs exactly as without it
+        retired = api.Plan(cfg)
+        assert api.lib().sgz_plan_set_option(retired.h, api.OPT_WIDE_GROUPS, 1) == api.SGZ_OK
+        retired.upload()
+        assert retired.path == split.path
+        assert np.array_equal(retired.stage_mapped(_planar_cuda(x, gpu)).cpu().numpy().view(np.uint32), m.view(np.uint32))
     if pairs > 1:
         problems, stats = check_render(oracle, split, cfg, x, gpu)
         assert not problems, (problems[:5], stats)
@@ -515,10 +519,9 @@ def test_channel_split_kernel_against_the_oracle(gpu, oracle, monkeypatch, N, sr
     (32768, 48000.0, dict(view_scaling=config.VIEW_LINEAR, view_left=0.0, view_right=0.02, axis_points=777)),
     (16384, 48000.0, dict(bin_interp=config.INTERP_NONE, axis_points=2500)),       # more pixels than two per thread: the map's further rounds
     (65536, 96000.0, dict(axis_points=300, min_log_freq=40.0)),                    # long runs: many chunks per pixel
-    # the 1024-thread form's map (two lanes per row of 32 magnitudes: spectrum_real16.hip ChunkMap16)
-    (32768, 48000.0, dict(wide=1)), (32768, 48000.0, dict(channel_mode=config.CH_MIDSIDE, bin_interp=config.INTERP_LINEAR, wide=1)),
-    (32768, 48000.0, dict(view_scaling=config.VIEW_LINEAR, view_left=0.0, view_right=0.02, axis_points=777, wide=1)),
-    (32768, 48000.0, dict(bin_interp=config.INTERP_NONE, axis_points=2500, wide=1)), (32768, 48000.0, dict(axis_points=300, min_log_freq=40.0, wide=1))])
+    # the same two at N = 32768
+    pytest.param(32768, 48000.0, dict(bin_interp=config.INTERP_NONE, axis_points=2500), id="32768-48000.0-no-interp-2500-px"),
+    pytest.param(32768, 48000.0, dict(axis_points=300, min_log_freq=40.0), id="32768-48000.0-300-px-from-40-hz")])
 def test_channel_split_mapping_bit_exact_given_bins(gpu, oracle, monkeypatch, N, sr, over):
     """Chain link 2 on the kernels the bench runs: sgz_stage_map_from_bins on a channel-split plan feeds the oracle's csf magnitudes to
     realMapFromBinsKernel -- the chunk-scan map, the late-pixel bookkeeping and realLateKernel are the very functions stftRealKernel
@@ -526,15 +529,13 @@ def test_channel_split_mapping_bit_exact_given_bins(gpu, oracle, monkeypatch, N,
     the pixels whose taps reach over bin 0, must equal the oracle's mapToLinearSpace (TransformDSP.inl:871-985) bit for bit."""
     import torch
     po = oracle
-    over = dict(over)
-    wide = over.pop("wide", 0)
     cfg = config.spectrum_config(sample_rate=sr, window_size=N, hop=N // 4, **over)
     p = po.params_from_dict(cfg)
     frames = 3
     x = synth.gen(23, int(sr), N + (frames - 1) * (N // 4), 2)
     x[0, 1::2] -= 0.4                                   # energy at Nyquist in the left channel: csf[N/2] wins the top pixels
     x[0, 0::2] += 0.4
-    plan = api.Plan(cfg).set_option(api.OPT_WIDE_GROUPS, wide).upload()
+    plan = api.Plan(cfg).upload()
     assert plan.path & 8
     csfs = np.zeros((frames, 1, plan.N + 1), np.float32)
     want = np.zeros((frames, 1, 2, plan.P), np.float32)
@@ -734,7 +735,6 @@ def test_launches_in_flight_on_several_streams_are_bit_identical(gpu, size):
 _OVERLAP_CASES = {
     "real-16384-midside": dict(window_size=16384, hop=4096, channel_mode=config.CH_MIDSIDE),
     "real-mono-merge": dict(channel_mode=config.CH_MERGE),
-    "wide-groups": dict(_wide=1),
     "whole-frame-complex": dict(channel_mode=config.CH_COMPLEX),
     "whole-frame-4096-padded": dict(window_size=3000, hop=750),
     "halves-8192": dict(window_size=8192, hop=2048),
@@ -751,23 +751,14 @@ def test_every_kernel_family_is_bit_identical_with_launches_in_flight(gpu, case)
     """the concurrency axis for the other K_A / K_B forms (tools/overlap_stress_cfgs.py is the long version: 15 configurations x 1 800
     renders, 0 differing): whole renders of three fixed buffers over four plans / streams against the quiet run"""
     import torch
-    over = dict(_OVERLAP_CASES[case])
-    wide = over.pop("_wide", 0)
-    cfg = config.spectrum_config(**over)
+    cfg = config.spectrum_config(**_OVERLAP_CASES[case])
     frames = 100 if cfg["window_size"] >= 16384 else 160
     S = cfg["window_size"] + cfg["hop"] * (frames - 1)
     xs = [torch.from_numpy(synth.gen(500 + k, int(cfg["sample_rate"]), S, 2 * cfg["num_pairs"])).to(gpu) for k in range(3)]
-
-    def make():
-        p = api.Plan(cfg)
-        if wide:
-            p.set_option(api.OPT_WIDE_GROUPS, 1)
-        return p.upload()
-
-    ref = make()
+    ref = api.Plan(cfg).upload()
     want = [ref.render(x).clone() for x in xs]
     torch.cuda.synchronize()
-    plans = [make() for _ in range(4)]
+    plans = [api.Plan(cfg).upload() for _ in range(4)]
     streams = [torch.cuda.Stream(device=gpu) for _ in range(4)]
     bad = 0
     for r in range(25 if cfg["algorithm"] else 80):

@@ -12,7 +12,6 @@ AGGRESSORS = {
     "real N=32768 separate (bench)": dict(),
     "real N=16384 midside": dict(window_size=16384, hop=4096, channel_mode=cf.CH_MIDSIDE),
     "real N=65536 two pairs (walking)": dict(window_size=65536, hop=16384, num_pairs=2, sample_rate=96000.0),
-    "wide groups N=32768": dict(_wide=1),
     "whole-frame complex N=32768": dict(channel_mode=cf.CH_COMPLEX),
     "whole-frame N=4096 zero-padded": dict(window_size=3000, hop=750),
     "halves N=8192": dict(window_size=8192, hop=2048),
@@ -33,12 +32,11 @@ torch.cuda.synchronize()
 s1, s2 = torch.cuda.Stream(device=gpu), torch.cuda.Stream(device=gpu)
 for name, over in AGGRESSORS.items():
     over = dict(over)
-    wide, form = over.pop("_wide", 0), over.pop("_form", None)
+    form = over.pop("_form", None)
     cfg = cf.spectrum_config(**over)
     frames = 100 if cfg["window_size"] >= 16384 else 200
     xa = torch.from_numpy(synth.gen(7, int(cfg["sample_rate"]), cfg["window_size"] + cfg["hop"] * (frames - 1), 2 * cfg["num_pairs"])).to(gpu)
     p = api.Plan(cfg)
-    if wide: p.set_option(api.OPT_WIDE_GROUPS, 1)
     if form is not None: p.set_option(api.OPT_MATRIX_RESONATOR, form)
     p.upload()
     out = p.render(xa)

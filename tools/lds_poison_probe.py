@@ -63,7 +63,6 @@ CASES = {
     "real N=16384 midside": dict(window_size=16384, hop=4096, channel_mode=cf.CH_MIDSIDE),
     "real N=65536 two pairs": dict(window_size=65536, hop=16384, num_pairs=2, sample_rate=96000.0),
     "real mono merge N=32768": dict(channel_mode=cf.CH_MERGE),
-    "wide groups N=32768": dict(_wide=1),
     "whole-frame complex N=32768": dict(channel_mode=cf.CH_COMPLEX),
     "whole-frame N=4096 zero-padded": dict(window_size=3000, hop=750),
     "halves N=8192": dict(window_size=8192, hop=2048),
@@ -80,16 +79,11 @@ CASES = {
 }
 total = 0
 for name, over in CASES.items():
-    over = dict(over)
-    wide = over.pop("_wide", 0)
     cfg = cf.spectrum_config(**over)
     frames = 60
     S = cfg["window_size"] + cfg["hop"] * (frames - 1)
     x = torch.from_numpy(synth.gen(500, int(cfg["sample_rate"]), S, 2 * cfg["num_pairs"])).to(gpu)
-    plan = api.Plan(cfg)
-    if wide:
-        plan.set_option(api.OPT_WIDE_GROUPS, 1)
-    plan.upload()
+    plan = api.Plan(cfg).upload()
     F = plan.num_frames(S)
 
     def run():

@@ -13,7 +13,6 @@ CASES = {
     "real N=16384 midside": dict(window_size=16384, hop=4096, channel_mode=cf.CH_MIDSIDE),
     "real N=65536 two pairs": dict(window_size=65536, hop=16384, num_pairs=2, sample_rate=96000.0),
     "real mono merge N=32768": dict(channel_mode=cf.CH_MERGE),
-    "wide groups N=32768": dict(_wide=1),
     "whole-frame complex N=32768": dict(channel_mode=cf.CH_COMPLEX),
     "whole-frame N=4096 zero-padded": dict(window_size=3000, hop=750),
     "halves N=8192": dict(window_size=8192, hop=2048),
@@ -38,7 +37,6 @@ if os.environ.get("CASES"):                                # CASES=substring,sub
 prepared = []
 for name, over in CASES.items():
     over = dict(over)
-    wide = over.pop("_wide", 0)
     fuzz = over.pop("_fuzz", None)
     if fuzz:
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -50,10 +48,8 @@ for name, over in CASES.items():
         frames = 120 if cfg["window_size"] >= 16384 else 200
         S = cfg["window_size"] + cfg["hop"] * (frames - 1)
         xs = [torch.from_numpy(synth.gen(500 + k, int(cfg["sample_rate"]), S, 2 * cfg["num_pairs"])).to(gpu) for k in range(3)]
-    def mk(cfg=cfg, wide=wide):
-        p = api.Plan(cfg)
-        if wide: p.set_option(api.OPT_WIDE_GROUPS, 1)
-        return p.upload()
+    def mk(cfg=cfg):
+        return api.Plan(cfg).upload()
     ref = mk()
     want = [(ref.render(x) if STAGE == "render" else ref.stage_mapped(x).view(torch.int32)).clone() for x in xs]
     torch.cuda.synchronize()

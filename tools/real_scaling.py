@@ -1,4 +1,4 @@
-"""K_A launch time against the number of frames (cfg2 settings), both forms of the N = 32768 channel-split kernel, sustained clock:
+"""K_A launch time against the number of frames (cfg2 settings), the N = 32768 channel-split kernel, sustained clock:
 the staircase shows what a workgroup costs alone on its CU, as one of two, and per dispatch generation"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -7,7 +7,7 @@ import torch
 from signalizer_amd import api, config, synth
 from ka_time import timeit
 cfg = config.cfg2()
-plans = {"wide(1024x16)": api.Plan(cfg).upload(), "narrow(512x32)": api.Plan(cfg).set_option(api.OPT_WIDE_GROUPS, 0).upload()}
+plans = {"K_A(512x32)": api.Plan(cfg).upload()}
 x = torch.from_numpy(synth.gen(2, 48000, 32768 + 8192 * 1100, 2)).cuda()
 stream = torch.cuda.current_stream().cuda_stream
 frames = [int(a) for a in sys.argv[1:]] or [1, 16, 64, 128, 192, 256, 320, 348, 384, 512, 768, 1024]
