@@ -139,6 +139,11 @@ def check_render(po, plan, cfg, x, gpu, want_lines=False, win_abs=WIN_ABS):
             f, c, s, px = [int(v[0]) for v in np.nonzero(bad)]
             problems.append("mapped: %d pixels off, first frame %d pair %d side %d pixel %d: %g vs %g (max %g)" %
                             (int(bad.sum()), f, c, s, px, got_mapped[f, c, s, px], ref[f, c, s, px], scale[f, c, 0]))
+    # the largest |K_A - oracle| / (the frame's largest bin) over the finite pixels (magnitude planes; Phase: its magnitude plane) -- link 1's margin
+    rel = np.where(finite[:, :, 0], dm, 0) / scale if phase else np.where(finite, dm, 0) / scale[:, :, None]
+    worst_rel = float(rel.max()) if rel.size else 0.0
     d = np.abs(got_rgba.astype(int) - r["rgba"].astype(int))
-    return problems, {"ties": ties, "bytes_differing": int((d > 0).sum()), "max_byte_diff": int(d.max()) if d.size else 0,
+    # pixels finite on one side only (link 1 skips them): a caller whose input keeps every pixel finite can require none
+    one_sided = int((np.isfinite(ref) != np.isfinite(got_mapped)).sum())
+    return problems, {"ties": ties, "worst_rel": worst_rel, "one_sided_nonfinite": one_sided, "bytes_differing": int((d > 0).sum()), "max_byte_diff": int(d.max()) if d.size else 0,
                       "frac": float((d > 0).mean()) if d.size else 0.0}

@@ -107,6 +107,42 @@ def test_KA3_two_for_one_equals_two_mono_runs(oracle):
     assert abs(csfS.real[N // 2 - 1] - 0.5 * csfL.real[N // 2 - 1]) <= tol
 
 
+@pytest.mark.parametrize("N", [1024, 16384, 32768, 65536])
+@pytest.mark.parametrize("win", [config.WIN_HANN, config.WIN_BLACKMAN_HARRIS])
+def test_two_for_one_split_vs_numpy_fp64(oracle, N, win):
+    """The oracle's Separate-mode csf[0 .. N] (fp32 transform, split, quirks) against the fp64 restatement of tests/fp64_bins.py, which
+    shares no code with it: the anchor of the GPU bins' bar (tests/test_gpu_full_size.py holds the kernels to the same restatement).
+    Every entry within 2e-7 x the frame's largest bin for the signals the suite renders (synth.gen: tones + sweep + 10 % noise; measured
+    <= 1.5e-7 over 40 seeds), 3e-7 for white noise, whose flat spectrum puts the largest bin closest to the rounding (measured <= 2.6e-7
+    over 40 seeds) -- and csf[0], csf[N/2 - 1], csf[N/2], csf[N] (the signed DC pair, quirk Q3, the unsplit entry) individually."""
+    from fp64_bins import separate_bins, window
+    from signalizer_amd import synth
+    po = oracle
+    p = po.params_from_dict(config.spectrum_config(window_size=N, hop=N, window_type=win))
+    w = window(win, config.WIN_PERIODIC, N)
+    rng = np.random.default_rng(N + win)
+    cases = [(synth.gen(seed, 48000, N, 2), 2e-7) for seed in (3, 17, 40, 91)]
+    cases += [(rng.uniform(-1, 1, (2, N)).astype(np.float32), 3e-7) for _ in range(2)]
+    for x, bar in cases:
+        _, csf, _ = po.frame_bins(p, x[0], x[1])
+        assert not csf.imag.any()
+        ref = separate_bins(x[0], x[1], w, N)
+        top = np.abs(ref).max()
+        err = np.abs(csf.real - ref)
+        assert err.max() <= bar * top, (err.max() / top, int(err.argmax()))
+        for k in (0, N // 2 - 1, N // 2, N):
+            assert err[k] <= bar * top, (k, err[k] / top)
+    # the quirk entries agree where they are large, not only where they are small: a left tone on bin N/2 - 1, a right Nyquist tone
+    # and a right offset put csf[N/2 - 1], csf[N/2] and csf[N] among the largest entries of their frame
+    n = np.arange(N)
+    x = np.stack([np.cos(2 * np.pi * (N // 2 - 1) * n / N), np.cos(np.pi * n) * 0.5 + 0.25]).astype(np.float32)
+    _, csf, _ = po.frame_bins(p, x[0], x[1])
+    ref = separate_bins(x[0], x[1], w, N)
+    top = np.abs(ref).max()
+    assert min(ref[N // 2 - 1], ref[N // 2], ref[N]) > 0.1 * top
+    assert np.abs(csf.real - ref).max() <= 2e-7 * np.abs(ref).max()
+
+
 def test_KA5_log_mapping_endpoints(oracle):
     po = oracle
     p = po.params_from_dict(config.cfg2())
