@@ -260,6 +260,19 @@ __device__ __forceinline__ double trigSample(uint32_t mode, const float *a, cons
     return double(a[i]);
 }
 
+// The detectors' source in a block of n samples: the planes (a, b) trigSample reads and the mode it reads them in (MidSide triggers
+// on the Mid of its pair)
+__device__ __forceinline__ uint32_t triggerPlanes(const IngestParams &prm, const float *blk, uint32_t n, const float *&a, const float *&b)
+{
+    uint32_t mode = prm.oscMode, pair = prm.trigPair;
+    if (mode == SGZ_OSC_MIDSIDE) { mode = SGZ_OSC_MID; pair = prm.trigSeparate & ~1u; }             // :340-352
+    if (mode == SGZ_OSC_RIGHT) a = b = blk + size_t(pair + 1) * n;
+    else if (mode == SGZ_OSC_LEFT) a = b = blk + size_t(pair) * n;
+    else if (mode == SGZ_OSC_SEPARATE) a = b = blk + size_t(prm.trigSeparate) * n;
+    else { a = blk + size_t(pair) * n; b = a + n; }
+    return mode;
+}
+
 __device__ __forceinline__ unsigned long long minU64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 
 #ifdef SGZ_DEBUG
@@ -268,6 +281,588 @@ __device__ unsigned long long g_ingestClk[8];
 #else
 #define ICLK(k) do { } while (0)
 #endif
+
+constexpr unsigned int kStage = 64;             // triggers / swaps of a callback staged in LDS
+constexpr unsigned int kFlat = 1024;            // swaps of a callback the one-pass copy takes (one per thread; more: one after the other)
+
+// The planes that move together through the rings: the audio channels, or (colour_by_frequency) the colour planes
+template <typename T>
+struct Planes {
+    const T *block; uint32_t pitch;             // the callback's samples: plane c at block + c * pitch
+    T *back, *front;                            // [count][backCap], [count][size]
+    uint32_t count;
+};
+
+// sample `abs` (absolute index: the block from written0 on, the back ring before it) of every plane -> slot d of the front ring
+template <typename T>
+__device__ __forceinline__ void copyToFront(const Planes<T> &p, unsigned long long abs, unsigned long long written0, uint32_t d, uint32_t size,
+                                            uint32_t backCap)
+{
+    const bool fromBlock = abs >= written0;
+    const uint32_t bi = uint32_t(abs - written0), ri = uint32_t(abs & (backCap - 1));
+    for (uint32_t c = 0; c < p.count; ++c)
+        p.front[size_t(c) * size + d] = fromBlock ? p.block[size_t(c) * p.pitch + bi] : p.back[size_t(c) * backCap + ri];
+}
+
+// the block (its newest backCap samples) -> the back ring, at absolute index mod backCap
+template <typename T>
+__device__ __forceinline__ void copyToBack(const Planes<T> &p, uint32_t n, unsigned long long written0, uint32_t backCap)
+{
+    const uint32_t keep = n > backCap ? backCap : n, first = n - keep;
+    for (uint32_t e = threadIdx.x; e < keep * p.count; e += blockDim.x) {
+        const uint32_t c = e / keep, i = first + (e - c * keep);
+        p.back[size_t(c) * backCap + uint32_t((written0 + i) & (backCap - 1))] = p.block[size_t(c) * p.pitch + i];
+    }
+}
+
+// What a swap of len samples leaves in the front ring when `later` more samples follow it in the same block: the ring holds `size`
+// samples, so only the last `size` of a longer run are written, and of those the first ones that the later swaps overwrite are dead.
+// Returns the count m of surviving samples; they start at sample `first` of the swap.  (A noisy signal fires a dozen triggers per
+// block, each swap copies a window's worth, and only the last one or two are still there when the block is done -- the others just
+// move the cursor.)
+__device__ __forceinline__ uint32_t survivingRange(uint32_t len, unsigned long long later, uint32_t size, uint32_t &first)
+{
+    const uint32_t skip = len > size ? len - size : 0u;
+    const uint32_t m0 = len - skip;
+    const unsigned long long room = later >= size ? 0ull : size - later;       // newest samples of this swap that stay visible
+    const uint32_t dead = m0 > room ? uint32_t(m0 - room) : 0u;
+    first = skip + dead;
+    return m0 - dead;
+}
+
+// ---- update(), StreamPreprocessing.h:55-76 (thread 0; the queue edits must precede phase A's appends)
+__device__ __forceinline__ void updatePhase(ScopeDev *st, const unsigned long long *peaks, unsigned long long playhead)
+{
+    st->steadyClock = playhead;
+    if (st->windowChanged) {
+        st->windowChanged = 0;
+        if (st->isWorkingOnPeak && st->qCount) { st->qHead = (st->qHead + 1) % kPeakCap; st->qCount--; }
+        while (st->qCount && peaks[st->qHead] < playhead) { st->qHead = (st->qHead + 1) % kPeakCap; st->qCount--; }
+        st->bufferedSamples = st->currentPeak = st->oldPeak = 0;
+        st->frontOrigin = playhead;
+        st->isWorkingOnPeak = 0;
+    }
+}
+
+// ---- A': PeakHoldProcessor over the block (StreamPreprocessing.h:270-313): an envelope follower whose every step depends on the
+// last one's branch -- one lane walks the block (a few microseconds per 512 samples; the triggers it finds are rare)
+__device__ __forceinline__ void peakHoldPhase(const IngestParams &prm, ScopeDev *st, const float *blk, uint32_t n, unsigned long long playhead)
+{
+    const float *a, *b;
+    const uint32_t mode = triggerPlanes(prm, blk, n, a, b);
+    double state = st->state;
+    const double thr2 = st->threshold * st->threshold, hysteresis = st->hysteresis;
+    int holding = st->isPeakHold;
+    unsigned int qc = st->qCount;
+    const unsigned int q0 = st->qHead;
+    unsigned long long dropped = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        double sample = trigSample(mode, a, b, i);
+        sample *= sample;
+        const double delta = sample - state;
+        if (delta < 0) {
+            state *= 0.9999;
+            state = fmax(thr2, state);
+            if (holding) {
+                if (qc < kPeakCap) { prm.peaks[(q0 + qc) % kPeakCap] = playhead + (unsigned long long)i - 1ull; ++qc; }
+                else ++dropped;
+                holding = 0;
+            }
+        } else {
+            if (delta > hysteresis * state) holding = 1;
+            state = sample;
+        }
+    }
+    st->state = state; st->isPeakHold = holding; st->qCount = qc; st->droppedPeaks += dropped;
+}
+
+// ---- A: ZeroCrossingProcessor (executeSamplingWindows, OscilloscopeDSP.inl:311-385) over the n samples of a run of blocks, the
+// whole workgroup: each thread walks a segment three times -- last arm / last threshold crossing (two prefix-max scans give every
+// segment the state in front of it), triggers counted (a prefix sum gives each its slot in the queue), triggers written.
+//   arm_i = (s_i > 0 && s_{i-1} < 0);  fire_i <=> s_i > threshold && lastArm(i) > lastThr(i-1)
+// (virtual indices: an arm inherited from before the run sits at -1, "no arm" at -3, "no threshold crossing yet" at -2).
+// load(i, b) -> double: sample i of the run; b is the accessor's cursor (the block sample i is in), kept per thread as it walks forward.
+// blockFires null: one callback -- triggers beyond the queue's room are not written and count as dropped.  Otherwise the whole
+// batch, all or nothing: per-block counts go to blockFires, and if the queue cannot take every trigger nothing is written and
+// false is returned (the queue's count is then left to the callbacks).  Ends in a barrier-free section: the caller syncs.
+template <typename Load>
+__device__ __forceinline__ bool zeroCrossings(uint32_t n, Load load, ScopeDev *st, unsigned long long *peaks, unsigned long long playhead,
+                                              unsigned int *blockFires, int *sScan2, unsigned int *sSum)
+{
+    const int tid = threadIdx.x, T = blockDim.x;
+    const double threshold = st->threshold, prevState = st->state;
+    const int armedIn = st->isPeakHold;
+    const unsigned long long originIn = st->crossOrigin;
+    const uint32_t seg = (n + T - 1) / T;
+    const uint32_t i0 = min(n, uint32_t(tid) * seg), i1 = min(n, i0 + seg);
+    uint32_t bStart = 0;                                                   // the block of sample i0 - 1 (or of i0)
+    const double before = i0 > 0 ? load(i0 - 1, bStart) : prevState;      // sample i0 - 1
+    auto walk = [&, i0, i1](auto step) {                                   // step(i, s_i, arm_i, b)
+        uint32_t b = bStart;
+        double prev = before;
+        for (uint32_t i = i0; i < i1; ++i) {
+            const double s = load(i, b);
+            step(i, s, s > 0 && prev < 0, b);
+            prev = s;
+        }
+    };
+    int segArm = INT_MIN, segThr = INT_MIN;                               // (sample indices < 2^31; "nothing yet" below every sentinel)
+    walk([&](uint32_t i, double s, bool arm, uint32_t) { if (arm) segArm = int(i); if (s > threshold) segThr = int(i); });
+    int totArm, totThr, inArm, inThr;
+    blockExclusiveMax2(segArm, armedIn ? -1 : -3, segThr, -2, sScan2, inArm, inThr, totArm, totThr);
+    auto triggers = [&](auto fire) {                                       // fire(lastArm, b) for each trigger of the segment
+        int la = inArm, lt = inThr;
+        walk([&](uint32_t i, double s, bool arm, uint32_t b) {
+            if (arm) la = int(i);
+            if (s > threshold) { if (la > lt) fire(la, b); lt = int(i); }
+        });
+    };
+    unsigned int fires = 0;
+    triggers([&](int, uint32_t b) { ++fires; if (blockFires) atomicAdd(&blockFires[b], 1u); });
+    unsigned int totalFires;
+    unsigned int pos = blockExclusiveSum(fires, sSum, &totalFires);
+    const unsigned int q0 = st->qHead, qc0 = st->qCount;
+    if (blockFires && qc0 + totalFires > kPeakCap) return false;          // (uniform)
+    triggers([&](int la, uint32_t) {
+        if (qc0 + pos < kPeakCap) peaks[(q0 + qc0 + pos) % kPeakCap] = (la == -1) ? originIn : playhead + (unsigned long long)la;
+        ++pos;
+    });
+    __syncthreads();
+    if (tid == 0) {
+        if (!blockFires) {
+            const unsigned int room = kPeakCap - qc0;
+            st->qCount = qc0 + (totalFires < room ? totalFires : room);
+            if (totalFires > room) st->droppedPeaks += totalFires - room;
+        }
+        st->isPeakHold = totArm > totThr ? 1 : 0;
+        if (totArm >= 0) st->crossOrigin = playhead + (unsigned long long)totArm;
+        uint32_t b = 0;
+        st->state = n ? load(n - 1, b) : prevState;
+    }
+    return true;
+}
+
+// What phase B hands on to C and E: the callback's swap count and the extent of its last audioProcessing call
+struct SwapPlan { unsigned int numSwaps, lastStart, lastLen; };
+
+// ---- B: processMutating's automaton (StreamPreprocessing.h:79-206) over a callback of n samples -> the swap list: the first kStage
+// swaps in sSwaps, the rest in swapList.  Wave 0, every lane the same scalar walk (lane 0 stores); the 64-trigger rounds use all of
+// them.  The head of the trigger queue is staged in sPeaks: the automaton walks without memory round trips (a block holds a handful
+// of triggers).
+__device__ __forceinline__ void processMutating(const IngestParams &prm, ScopeDev *st, uint32_t n, const unsigned long long *sPeaks,
+                                                Swap *sSwaps, SwapPlan &plan)
+{
+    const unsigned int lane = threadIdx.x;
+    const bool lane0 = lane == 0;
+    const unsigned int qHeadIn = st->qHead;
+    auto peakAt = [&](unsigned int q) {
+        const unsigned int k = (q + kPeakCap - qHeadIn) % kPeakCap;
+        return k < kStage ? sPeaks[k] : prm.peaks[q];
+    };
+    auto storeSwap = [&](unsigned int k, unsigned long long src, unsigned int len) {     // swap k of the callback, if the list has room
+        if (k < kMaxSwaps) {
+            const Swap sw{src, len};
+            if (k < kStage) sSwaps[k] = sw; else prm.swapList[k] = sw;   // (two stores: a selected reference is a flat one)
+        }
+    };
+    unsigned int numSwaps = 0, lastStart = 0, lastLen = n;
+    const unsigned long long written0 = st->written;
+    unsigned long long bufferedSamples = st->bufferedSamples, frontOrigin = st->frontOrigin, steadyClock = st->steadyClock;
+    unsigned long long oldPeak = st->oldPeak, currentPeak = st->currentPeak;
+    unsigned int qHead = st->qHead, qCount = st->qCount;
+    int isWorkingOnPeak = st->isWorkingOnPeak;
+    unsigned int swapsDone = 0;
+    unsigned long long numSamples = n, consumed = 0;
+    if (frontOrigin + bufferedSamples < steadyClock) { frontOrigin = steadyClock; bufferedSamples = 0; }   // :81-85
+    const double ceilingSize = ceil(st->windowSize);
+    const double halfSize = ceilingSize / 2;
+    const unsigned long long bufferedCap = (unsigned long long)(ceilingSize + 1);                      // :101
+    // (for an integer d >= 0:  double(d) < halfSize  <=>  d < ceil(halfSize))
+    const unsigned long long halfCeil = (unsigned long long)ceil(halfSize);
+    auto processIntoBackBuffer = [&](unsigned long long samples) {                                     // :90-105
+        lastStart = (unsigned int)consumed; lastLen = (unsigned int)samples;
+        consumed += samples;
+        numSamples -= samples;
+        const unsigned long long oldSamples = bufferedSamples;
+        steadyClock += samples;
+        bufferedSamples += samples;
+        bufferedSamples = minU64(bufferedSamples, bufferedCap);
+        frontOrigin += (oldSamples + samples) - bufferedSamples;
+    };
+    auto pickUpNextPeak = [&]() {                                                                      // :120-141
+        const unsigned long long nextPeak = peakAt(qHead);
+        isWorkingOnPeak = 1;
+        if (nextPeak >= steadyClock) {
+            const unsigned long long deltaToPeak = nextPeak - steadyClock;
+            processIntoBackBuffer(minU64(numSamples, (unsigned long long)(double(deltaToPeak) + halfSize)));
+        }
+        currentPeak = nextPeak;
+    };
+    // swapBuffers(cappedSize, -bufferedSamples): source = the oldest buffered sample onwards; the trigger is done (:191-205).  Both
+    // callers hold a queued trigger and cappedSize <= bufferedSamples.
+    auto swapBuffers = [&](unsigned long long cappedSize) {
+        if (lane0) storeSwap(numSwaps, (written0 + consumed) - bufferedSamples, (unsigned int)cappedSize);
+        if (numSwaps < kMaxSwaps) ++numSwaps;
+        bufferedSamples -= cappedSize;
+        frontOrigin += cappedSize;
+        oldPeak = currentPeak;
+        isWorkingOnPeak = 0;
+        qHead = (qHead + 1) % kPeakCap; qCount--;
+        ++swapsDone;
+    };
+    if (ceilingSize == 0 && qCount) qCount = 0;                                                        // :107-110
+    // The walk below is the reference's, branch for branch.  In front of it, the same walk for the case a running stream is
+    // in at almost every trigger -- the next trigger lies inside the current window (less than half a window after the last
+    // one): what the general body computes then is  missing = peak - oldPeak, neededPreSamples = 0, take what is missing
+    // from the callback, swap min(buffered, missing + 1) samples  (every
+    // double in :147-190 is an integer plus, at most, the half of an odd window: the casts truncate it away on both sides of
+    // the one subtraction that matters).  Some forty triggers per callback at cfg3: 8.9 us of a 16 us callback in the general body, 6.3 us here (a lone lane issues an
+    // instruction every ~8 cycles; the same in 32-bit arithmetic relative to the callback's start, or with the queue's head read
+    // one trigger ahead, measured no faster).  Anything else -- a trigger outside the window -- leaves the state exactly as
+    // the general body expects it at that point and falls through to it.
+    while (numSamples != 0) {
+        // ---- a ROUND: up to 64 queued triggers at once, one per lane.  For a trigger that is fetched with the running clock
+        // already past it (no samples swallowed at the fetch, :128), inside the window and in order, the walk does
+        //     taken = max(missing - buffered, 0) samples from the callback;  swap min(max(buffered, missing), missing + 1);
+        //     buffered <- max(buffered - (missing + 1), 0)
+        // -- maps that compose by addition: buffered in front of trigger l is max(buffered_0 - sum_{i<l}(missing_i + 1), 0),
+        // so every trigger's numbers are prefix sums.  The round takes the longest run of such triggers that the callback's
+        // samples cover (the first one fetched at or after the running clock, out of order, outside the window, or short of
+        // samples ends it) and leaves the walk's state behind it; the scalar iteration below handles whatever comes next.
+        if (!isWorkingOnPeak && qCount >= 4u && halfCeil <= (1ull << 24) && bufferedSamples <= bufferedCap && bufferedSamples < (1ull << 30) &&
+            numSamples < (1ull << 30) && steadyClock < (1ull << 51)) {
+            const unsigned long long base = steadyClock;
+            auto fits = [&](unsigned long long v) { const long long r = (long long)(v - base); return r > -(1ll << 30) && r < (1ll << 30); };
+            if (fits(oldPeak)) {
+                const unsigned int cnt = qCount < 64u ? qCount : 64u;
+                const unsigned int buf0 = (unsigned int)bufferedSamples, ns0 = (unsigned int)numSamples, hc = (unsigned int)halfCeil;
+                auto scan = [&](unsigned int v) {                         // inclusive prefix sum over the wave
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) { const unsigned int u = __shfl_up(v, o); if (lane >= (unsigned int)o) v += u; }
+                    return v;
+                };
+                const unsigned long long pk = lane < cnt ? peakAt((qHead + lane) % kPeakCap) : 0ull;
+                bool ok = lane < cnt && fits(pk);
+                const int p = ok ? int((long long)(pk - base)) : 0;
+                int prev = __shfl_up(p, 1);
+                if (lane == 0) prev = int((long long)(oldPeak - base));
+                ok = ok && p >= prev;
+                const unsigned int d = ok ? (unsigned int)(p - prev) : 0u;
+                ok = ok && d < hc;
+                const unsigned int a = ok ? d + 1u : 0u;
+                const unsigned int S = scan(a), Sprev = S - a;
+                const unsigned int bufL = buf0 > Sprev ? buf0 - Sprev : 0u;
+                const unsigned int tp = ok && d > bufL ? d - bufL : 0u;
+                const unsigned int Cc = scan(tp), Cprev = Cc - tp;
+                const bool swallow = ok && p >= 0 && (unsigned int)p >= Cprev;       // fetched at or after the running clock (base + Cprev)
+                const bool stop = !ok || swallow || Cc > ns0 || Cprev >= ns0;
+                const unsigned long long stops = __ballot(stop);
+                const unsigned int m = stops ? (unsigned int)__builtin_ctzll(stops) : 64u;   // triggers 0 .. m-1 complete
+                if (m > 0) {
+                    const unsigned int bufTake = bufL > d ? bufL : d, capped = bufTake < d + 1u ? bufTake : d + 1u;
+                    const unsigned int capSum = scan(lane < m ? capped : 0u);
+                    if (lane < m) storeSwap(numSwaps + lane, written0 + consumed + Cc - bufTake, capped);
+                    const unsigned long long took = __ballot(lane < m && tp > 0u);
+                    if (took) {
+                        const int hl = 63 - __builtin_clzll(took);
+                        lastStart = (unsigned int)consumed + __shfl(Cprev, hl);
+                        lastLen = __shfl(tp, hl);
+                    }
+                    const unsigned int Sm = __shfl(S, int(m) - 1), Cm = __shfl(Cc, int(m) - 1), capM = __shfl(capSum, int(m) - 1);
+                    const int pm = __shfl(p, int(m) - 1);
+                    bufferedSamples = buf0 > Sm ? buf0 - Sm : 0u;
+                    numSamples -= Cm; consumed += Cm; steadyClock += Cm;
+                    frontOrigin += capM;
+                    oldPeak = currentPeak = base + (unsigned long long)(long long)pm;
+                    qHead = (qHead + m) % kPeakCap; qCount -= m;
+                    swapsDone += m;
+                    numSwaps = numSwaps + m < kMaxSwaps ? numSwaps + m : kMaxSwaps;
+                    continue;
+                }
+            }
+        }
+        bool fastDone = false;
+        if (qCount) do {
+            if (!isWorkingOnPeak) pickUpNextPeak();
+            if (currentPeak < oldPeak) break;                                // (the general body: the difference wraps, "outside the window")
+            const unsigned long long d = currentPeak - oldPeak;
+            if (d >= halfCeil || oldPeak >= (1ull << 51)) break;
+            // inside the window: windowEnd = oldPeak + (u64)halfSize, peakWindowEnd = currentPeak + (u64)halfSize,
+            // missingBufferSamples = d, neededPreSamples = 0
+            if (bufferedSamples < d) {                                       // :176-182: the samples still missing come out of this callback
+                const unsigned long long numRemaining = d - bufferedSamples;
+                const unsigned long long toProcess = minU64(numSamples, numRemaining);
+                if (toProcess > 0) processIntoBackBuffer(toProcess);
+                if (numRemaining != toProcess) { fastDone = true; break; }   // not ready: the callback is used up, the trigger stays open
+            }
+            swapBuffers(minU64(bufferedSamples, d + 1ull));
+            fastDone = true;
+        } while (false);
+        if (fastDone) continue;
+        if (!qCount) { processIntoBackBuffer(numSamples); break; }
+        else if (!isWorkingOnPeak) pickUpNextPeak();
+        unsigned long long windowEnd;
+        bool isPeakOutsideOfWindow = false, readyForBufferSwap = false;
+        if (double(currentPeak - oldPeak) < halfSize) windowEnd = (unsigned long long)(double(oldPeak) + halfSize);   // :147-150
+        else { isPeakOutsideOfWindow = true; windowEnd = frontOrigin + bufferedSamples; }
+        const unsigned long long peakWindowEnd =
+            (unsigned long long)(double((isPeakOutsideOfWindow ? 1ull : 0ull) + currentPeak) + halfSize);       // :158
+        unsigned long long toProcess = 0;
+        const unsigned long long missingBufferSamples = peakWindowEnd - minU64(peakWindowEnd, windowEnd);
+        const unsigned long long neededPreSamples =
+            minU64((unsigned long long)halfSize, (unsigned long long)(fmax(double(currentPeak - oldPeak), halfSize) - halfSize));
+        if (isPeakOutsideOfWindow) {
+            toProcess = minU64(numSamples, missingBufferSamples);
+            if (toProcess > 0) processIntoBackBuffer(toProcess);
+            readyForBufferSwap = missingBufferSamples == toProcess;
+        } else if (bufferedSamples >= missingBufferSamples) readyForBufferSwap = true;
+        else {
+            const unsigned long long numRemaining = missingBufferSamples - bufferedSamples;
+            toProcess = minU64(numSamples, numRemaining);
+            if (toProcess > 0) processIntoBackBuffer(toProcess);
+            readyForBufferSwap = numRemaining == toProcess;
+        }
+        if (readyForBufferSwap) {
+            const double amount = (isPeakOutsideOfWindow ? halfSize : double(missingBufferSamples)) + double(neededPreSamples);
+            swapBuffers(minU64(bufferedSamples, (unsigned long long)ceil(amount + 1)));
+        }
+    }
+    if (lane0) {
+        st->swaps += swapsDone;                            // (once: a read-modify-write of global memory inside the walk is a round trip per trigger)
+        st->bufferedSamples = bufferedSamples; st->frontOrigin = frontOrigin; st->steadyClock = steadyClock;
+        st->oldPeak = oldPeak; st->currentPeak = currentPeak; st->qHead = qHead; st->qCount = qCount;
+        st->isWorkingOnPeak = isWorkingOnPeak;
+        plan.numSwaps = numSwaps; plan.lastStart = lastStart; plan.lastLen = lastLen;
+    }
+}
+
+// ---- F: per-sample colours of the block (audioProcessing :445-517, :588-647) -> col.block.  Every sample passes through
+// audioProcessing exactly once and in order, whatever the split into calls, so the filters run over the block as a whole.
+__device__ __forceinline__ void colourPhase(const ColourParams &col, const float *blk, uint32_t n, uint32_t C)
+{
+    const int tid = threadIdx.x, T = blockDim.x;
+    // The three filter stages hand their per-sample outputs on through LDS, a tile of the callback at a time (samples in, band
+    // signals, smoothed energies: 11 floats per channel and sample; a stereo tile is 416 samples).  Through the HBM scratch every
+    // sixteen samples of every stage waited for a memory round trip of its own: 64 us per stage, 193 us of a 206 us callback.
+    constexpr uint32_t kFFloats = 9216;
+    __shared__ float sF[kFFloats];
+    const uint32_t MB = col.maxBlock;
+    ColourDev *cs = col.st;
+    uint32_t tile = kFFloats / (11u * C);
+    tile = tile >= 16u ? (tile & ~15u) : (tile ? tile : 1u);
+    if (tile > 512u) tile = 512u;
+    float *sX = sF, *sB = sX + size_t(C) * tile, *sS = sB + size_t(4 * C) * tile;       // [C][tile], [4 C][tile], [6 C][tile]
+    // the lanes' filter states stay in registers from tile to tile
+    const bool r12 = uint32_t(tid) < 2 * C, r3 = uint32_t(tid) < 6 * C;
+    const uint32_t fc = uint32_t(tid) >> 1, fhp = uint32_t(tid) & 1u;
+    float k1[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, k2[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f, c0 = 0.f, c1 = 0.f, d0 = 0.f, d1 = 0.f, y = 0.f;
+    float *stp = nullptr;
+    const uint32_t pair3 = uint32_t(tid) / 12u, r = uint32_t(tid) % 12u, sig3 = r / 3u, band3 = r % 3u;
+    if (r12) {
+        const float *ka = fhp ? col.hp1 : col.lp1, *kb = fhp ? col.hp2 : col.lp2;
+        for (int j = 0; j < 5; ++j) { k1[j] = ka[j]; k2[j] = kb[j]; }
+        float (*z1)[2] = cs->z[fc] + (fhp ? 2 : 0), (*z2)[2] = cs->z[fc] + (fhp ? 6 : 4);
+        a0 = z1[0][0]; a1 = z1[0][1]; b0 = z1[1][0]; b1 = z1[1][1];
+        c0 = z2[0][0]; c1 = z2[0][1]; d0 = z2[1][0]; d1 = z2[1][1];
+    }
+    if (r3) {
+        stp = sig3 == 0 ? &cs->smooth[2 * pair3][band3] : sig3 == 1 ? &cs->smooth[2 * pair3 + 1][band3]
+            : sig3 == 2 ? &cs->aux[2 * pair3][band3] : &cs->aux[2 * pair3 + 1][band3];
+        y = *stp;
+    }
+    const float pole = col.pole;
+    for (uint32_t t0 = 0; t0 < n; t0 += tile) {
+        const uint32_t m = min(tile, n - t0);
+        for (uint32_t e = tid; e < C * m; e += T) { const uint32_t c = e / m, i = e - c * m; sX[size_t(c) * tile + i] = blk[size_t(c) * n + t0 + i]; }
+        __syncthreads();
+        if (r12) {                                                     // F1: low = LP4_f1(x), rest = HP4_f1(x)
+            const float *x = sX + size_t(fc) * tile;
+            float *out = sB + (size_t(fc) * 4 + (fhp ? 3 : 0)) * tile;
+            walkSequential(m, [&](uint32_t i) { return x[i]; },
+                           [&](uint32_t i, float v) { out[i] = biquadStep(k1, b0, b1, biquadStep(k1, a0, a1, v)); });
+        }
+        __syncthreads();
+        if (r12) {                                                     // F2: mid = LP4_f2(rest), high = HP4_f2(rest)
+            const float *x = sB + (size_t(fc) * 4 + 3) * tile;
+            float *out = sB + (size_t(fc) * 4 + (fhp ? 2 : 1)) * tile;
+            walkSequential(m, [&](uint32_t i) { return x[i]; },
+                           [&](uint32_t i, float v) { out[i] = biquadStep(k2, d0, d1, biquadStep(k2, c0, c1, v)); });
+        }
+        __syncthreads();
+        if (r3) {                                                      // F3: filterStates (:460-468) of left, right, mid, side
+            const float *l = sB + (size_t(2 * pair3) * 4 + band3) * tile, *rr = sB + (size_t(2 * pair3 + 1) * 4 + band3) * tile;
+            float *out = sS + size_t(tid) * tile;
+            // (which signal a lane smooths is a lane constant: both inputs are read and the lane's one picked by selects -- as a
+            // branch inside the batched loads the four cases ran one after the other: 90 us of a 150 us callback)
+            const bool isL = sig3 == 0, isR = sig3 == 1, isMid = sig3 == 2;
+            walkSequential(m, [&](uint32_t i) { return l[i]; },
+                           [&](uint32_t i, float lv) {
+                               const float rv = rr[i];
+                               const float sum = lv + rv, dif = lv - rv;
+                               const float v = isL ? lv : (isR ? rv : (isMid ? sum : dif));
+                               const float input = v * v;
+                               y = input + pole * (y - input);
+                               out[i] = y;
+                           });
+        }
+        __syncthreads();
+        for (uint32_t e = tid; e < 2 * C * m; e += T) {                // F4: accumulateColour per (signal, sample)
+            const uint32_t q = e / m, i = e - q * m, pair = q >> 2, sig = q & 3u;
+            const float *sp = sS + size_t(pair * 12 + sig * 3) * tile + i;
+            const float stv[3] = {sp[0], sp[tile], sp[2 * size_t(tile)]};
+            const uint32_t keyCh = 2 * pair + (sig & 1u);              // left / mid: the left key, right / side: the right key
+            const uint32_t plane = (sig < 2 ? 0u : C) + keyCh;         // cwLeft, cwRight -> colourData; cwMid, cwSide -> auxColourData
+            col.block[size_t(plane) * MB + t0 + i] = accumulateColour(stv, col.band, col.keys[keyCh], col.blend);
+        }
+        __syncthreads();
+    }
+    if (r12) {
+        float (*z1)[2] = cs->z[fc] + (fhp ? 2 : 0), (*z2)[2] = cs->z[fc] + (fhp ? 6 : 4);
+        z1[0][0] = a0; z1[0][1] = a1; z1[1][0] = b0; z1[1][1] = b1;
+        z2[0][0] = c0; z2[0][1] = c1; z2[1][0] = d0; z2[1][1] = d1;
+    }
+    if (r3) *stp = y;
+}
+
+// ---- C: the ns swaps of phase B (hold: ZeroCrossing, EnvelopeHold) or the block itself (None / Spectral: audioProcessing straight
+// into the front buffer), in order, into the front rings from ring slot cursor0 on; returns the cursor behind them.
+// written0: the absolute index of the block's first sample.
+__device__ __forceinline__ uint32_t frontPhase(const IngestParams &prm, const Planes<float> &audio, const Planes<uint32_t> &colour,
+                                               bool hold, const Swap *swaps, uint32_t ns, uint32_t n, uint32_t cursor0, unsigned long long written0,
+                                               unsigned int *sSum)
+{
+    const uint32_t size = prm.size, backCap = prm.backCap;
+    const int tid = threadIdx.x, T = blockDim.x;
+    auto copy = [&](unsigned long long abs, uint32_t d) {
+        copyToFront(audio, abs, written0, d, size, backCap);
+        if (prm.colours) copyToFront(colour, abs, written0, d, size, backCap);
+    };
+    auto swapAt = [&](uint32_t k) { return k < kStage ? swaps[k] : prm.swapList[k]; };
+    if (hold && ns <= kFlat) {
+        // The usual case -- a handful of swaps, all in LDS -- as ONE pass: no two swaps of a block write the same ring slot (what a later
+        // swap would overwrite is dead and never written), and their sources are read-only here, so they need no order among
+        // themselves.  Swap k's surviving range comes from prefix sums of the lengths (lane k of wave 0; one thread each past 64);
+        // then every thread copies its share of the concatenation.  (One swap after the other with a barrier each cost a memory
+        // round trip per swap: 8.9 us of a 25 us block at a dozen swaps, tools/ingest_clocks.py; now 1.9 us.)
+        __shared__ unsigned long long sFlatSrc[kFlat];
+        __shared__ uint32_t sFlatDst[kFlat], sFlatEnd[kFlat], sFlatTotal, sCursorEnd;
+        // swap k's row of the tables; scan(v, total) -> inclusive prefix sum of v over the swaps
+        auto tableRow = [&](uint32_t k, bool live, const Swap &sw, auto scanLen, auto scanM) {
+            unsigned long long total;
+            const unsigned long long inc = scanLen((unsigned long long)sw.len, total);
+            uint32_t first, totalM;
+            const uint32_t incM = scanM(survivingRange(sw.len, total - inc, size, first), totalM);
+            if (live) {
+                sFlatSrc[k] = sw.src + first;
+                sFlatDst[k] = uint32_t((cursor0 + (inc - sw.len) + first) % size);
+                sFlatEnd[k] = incM;
+            }
+            if (k == 0) { sFlatTotal = totalM; sCursorEnd = uint32_t((cursor0 + total) % size); }
+        };
+        const uint32_t k = uint32_t(tid);
+        const bool live = k < ns;
+        if (ns > kStage) {
+            // more swaps than a wave has lanes (a 10 kHz tone at 48 kHz crosses zero 107 times per 512-sample callback): workgroup-wide
+            // prefix sums, one swap per thread (the swaps beyond the staged ones are read back from HBM).  One after the other they cost
+            // 0.65 us each: 74 us per callback at 107, 143 us at 213.
+            __shared__ unsigned long long sScan64[16];
+            // (read at a loop-variant index: at k alone the selected LDS-or-HBM address is hoisted out of the block loop, a flat
+            // pointer per thread that the colour phase has no registers for)
+            Swap sw = swapAt(live ? k : 0u);
+            if (!live) sw = Swap{0ull, 0u, 0u};
+            tableRow(k, live, sw,
+                     [&](unsigned long long v, unsigned long long &t) { return blockInclusiveSum(v, sScan64, &t); },
+                     [&](uint32_t v, uint32_t &t) { return blockInclusiveSum(v, sSum, &t); });
+        } else if (tid < 64) {
+            auto waveScan = [&](auto v, auto &total) {
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const auto u = __shfl_up(v, o); if (tid >= o) v += u; }
+                total = __shfl(v, 63);
+                return v;
+            };
+            tableRow(k, live, live ? swaps[k] : Swap{0ull, 0u, 0u}, waveScan, waveScan);
+        }
+        __syncthreads();
+        const uint32_t M = sFlatTotal;
+        for (uint32_t e = tid; e < M; e += T) {
+            uint32_t lo = 0, hi = ns;                                    // the swap of element e: smallest k with sFlatEnd[k] > e
+            while (lo + 1 < hi) { const uint32_t mid = (lo + hi) >> 1; if (sFlatEnd[mid - 1] > e) hi = mid; else lo = mid; }
+            const uint32_t i = e - (lo ? sFlatEnd[lo - 1] : 0u);
+            copy(sFlatSrc[lo] + i, (sFlatDst[lo] + i) % size);
+        }
+        const uint32_t cursor = sCursorEnd;
+        __syncthreads();
+        return cursor;
+    }
+    // one run after the other, each behind a barrier; `later`: the samples the runs after it append
+    uint32_t cursor = cursor0;
+    auto append = [&](unsigned long long src, uint32_t len, unsigned long long later) {
+        uint32_t first;
+        const uint32_t m = survivingRange(len, later, size, first);
+        const uint32_t d0 = uint32_t((cursor + first) % size);
+        for (uint32_t i = tid; i < m; i += T) copy(src + first + i, (d0 + i) % size);
+        cursor = uint32_t((cursor + len) % size);
+        __syncthreads();
+    };
+    if (!hold) { append(written0, n, 0ull); return cursor; }
+    unsigned long long later = 0;                                        // suffix sums of the swap lengths: a thread-private walk from the back
+    for (uint32_t k = 0; k < ns; ++k) later += swapAt(k).len;
+    for (uint32_t k = 0; k < ns; ++k) {
+        const Swap sw = swapAt(k);
+        later -= sw.len;
+        append(sw.src, sw.len, later);
+    }
+    return cursor;
+}
+
+// ---- E: RMS envelope (audioProcessing, OscilloscopeDSP.inl:520-585, :676-693); wave 0, lane c = recurrence c.  The callback's last
+// audioProcessing call covers samples [lastStart, lastStart + lastLen).
+// (the reference runs the recurrence in PeakDecay mode too and throws the result away, :506-585 against :676: only RMS stores it)
+__device__ __forceinline__ void envelopePhase(const IngestParams &prm, ScopeDev *st, const float *blk, uint32_t n, uint32_t lastStart, uint32_t lastLen)
+{
+    const int tid = threadIdx.x;
+    const uint32_t C = prm.channels;
+    const bool active = tid < int(C);
+    const float k = prm.envelopeCoeff;
+    const uint32_t mode = prm.oscMode;
+    // channels 0 / 1 are stored back (:690-691) and so run through every audioProcessing call of the block; the others restart
+    // from their stored envelope in every call, so only the last call's samples matter for them
+    const uint32_t from = tid < 2 ? 0u : lastStart, to = lastStart + lastLen;
+    float y = active ? st->envelope[tid] : 0.f;
+    const float *b0 = blk, *b1 = blk + n, *bc = blk + size_t(active ? tid : 0) * n;
+    bool own = false;
+    if (mode == SGZ_OSC_SEPARATE) {
+        own = true;
+        if (active) walkSequential(to - from, [&](uint32_t i) { return bc[from + i]; }, [&](uint32_t, float v) { const float s = v * v; y = s + k * (y - s); });
+    } else if (mode == SGZ_OSC_MIDSIDE) {
+        if (tid < 2) {
+            own = true;
+            // the mix itself is exact in either order of evaluation: (l +- r) once, squared, halved
+            walkSequential(to, [&](uint32_t i) { return tid == 0 ? b0[i] + b1[i] : b0[i] - b1[i]; },
+                           [&](uint32_t, float v) { const float s = 0.5f * (v * v); y = s + k * (y - s); });
+        }
+    } else if (tid == 0) {
+        own = true;
+        const float *src = mode == SGZ_OSC_RIGHT ? b1 : b0;
+        // (one walk per mode: a branch inside the load would keep the batch of loads from being issued together)
+        auto rms = [&](uint32_t, float v) { const float s = v * v; y = s + k * (y - s); };
+        if (mode == SGZ_OSC_MID) walkSequential(to, [&](uint32_t i) { return 0.5f * (b0[i] + b1[i]); }, rms);
+        else if (mode == SGZ_OSC_SIDE) walkSequential(to, [&](uint32_t i) { return 0.5f * (b0[i] - b1[i]); }, rms);
+        else walkSequential(to, [&](uint32_t i) { return src[i]; }, rms);
+    }
+    // filterEnv[c] of the last call: copies of channel 0 (mono modes) / channel 1 (MidSide) where the channel has no recurrence
+    const float y0 = __shfl(y, 0), y1 = __shfl(y, 1);
+    const float fe = own ? y : (mode == SGZ_OSC_MIDSIDE ? y1 : y0);
+    float start = active ? __builtin_sqrtf(fe) : 0.f;                  // RMS: gain and stored envelopes
+    for (int o = 32; o > 0; o >>= 1) start = fmaxf(start, __shfl_xor(start, o));
+    if (tid == 0) {
+        st->envelopeGain = 1.0 / double(start);
+        st->envelope[0] = y0;
+        st->envelope[1] = (mode == SGZ_OSC_SEPARATE || mode == SGZ_OSC_MIDSIDE) ? y1 : y0;
+    }
+}
+
 // (the colour parameters -- ~100 words with the per-channel keys -- come through a pointer: as a by-value argument they stayed live in
 // scalar registers across the loop over the batch's blocks and pushed four vector registers into scratch)
 __device__ void scopePeakBody(const PeakParams &prm);
@@ -277,8 +872,6 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
     const ColourParams &col = *colp;
     __shared__ int sScan2[32];
     __shared__ unsigned int sSum[16];
-    __shared__ unsigned int sNumSwaps, sLastStart, sLastLen, sCursor0;
-    __shared__ unsigned long long sWritten0;
     // The stream state lives in LDS for the length of the kernel (one coalesced read, one write-back): the phases below touch its fields
     // some thirty times, mostly from one lane and each time behind the last (the kernels of the render thread read the copy in HBM,
     // between launches)
@@ -289,13 +882,9 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
     for (uint32_t w = tid; w < sizeof(ScopeDev) / 4; w += T) reinterpret_cast<uint32_t *>(&sState)[w] = reinterpret_cast<const uint32_t *>(prm.st)[w];
     __syncthreads();
     ScopeDev *st = &sState;
-    constexpr unsigned int kStage = 64;             // triggers / swaps staged in LDS
-    constexpr unsigned int kFlat = 1024;            // swaps of a callback the one-pass copy takes (one per thread; more: one after the other)
     __shared__ unsigned long long sPeaks[kStage];
     __shared__ Swap sSwaps[kStage];
-    __shared__ unsigned long long sFlatSrc[kFlat];
-    __shared__ uint32_t sFlatDst[kFlat], sFlatEnd[kFlat], sFlatTotal, sCursorEnd;
-    __shared__ unsigned long long sScan64[16];
+    __shared__ SwapPlan sPlan;
     // One launch ingests every block that was waiting (sgz_scope_push only stages; whoever needs the state -- the render thread's calls, a
     // full batch, sgz_scope_flush -- submits): the blocks go through the reference's per-callback state machine ONE AFTER THE OTHER, with
     // their boundaries where the host put them (audioEntryPoint runs once per onStreamAudio: update(), the detector, processMutating's
@@ -307,13 +896,13 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
         if (tid == int(b)) { sBlockOff[b] = prm.blockOff[b]; sBlockLen[b] = prm.blockLen[b]; }
     __syncthreads();
     batchFetch(prm.batchHost, const_cast<float *>(prm.batch), prm.batchFloats, tid, T);
-    // ---- A for the WHOLE batch.  The zero-crossing detector (phase A below) is a scan over the samples whose state (armed, last
-    // threshold crossing, previous sample) does not depend on what processMutating does with the triggers, and a trigger's slot in the
-    // queue's ring is head + count + (triggers before it) whatever has been popped meanwhile: so the detector runs ONCE over the
+    // ---- A for the WHOLE batch.  The zero-crossing detector (phase A) is a scan over the samples whose state (armed, last threshold
+    // crossing, previous sample) does not depend on what processMutating does with the triggers, and a trigger's slot in the queue's
+    // ring is head + count + (triggers before it) whatever has been popped meanwhile: so the detector runs ONCE over the
     // concatenation of the batch's blocks (three passes and two block-wide scans instead of that per block: 4 us per block saved),
     // writes every trigger where the per-callback walk would, and each block's processMutating then sees the queue grow by its own
     // block's triggers only (sFires).  Taken when no trigger can be dropped (count + all fires <= capacity: then no callback of the
-    // sequential walk drops one either) and no window change is pending (update() edits the queue); otherwise block by block as before.
+    // sequential walk drops one either) and no window change is pending (update() edits the queue); otherwise block by block.
     __shared__ uint32_t sBlockStart[BatchRing::kMaxBlocks + 1];
     __shared__ unsigned int sFires[BatchRing::kMaxBlocks];
     __shared__ int sBatchedA;
@@ -326,700 +915,71 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
     if (tid < int(BatchRing::kMaxBlocks)) sFires[tid] = 0;
     __syncthreads();
     if (prm.triggerMode == 4u && C >= 2 && prm.numBlocks > 1 && !st->windowChanged) {       // (uniform)
-        uint32_t localMode = prm.oscMode, pair = prm.trigPair;
-        if (localMode == SGZ_OSC_MIDSIDE) { localMode = SGZ_OSC_MID; pair = prm.trigSeparate & ~1u; }     // :340-352
-        const uint32_t N = sBlockStart[prm.numBlocks];
-        // sample i of the concatenation; b: the block it is in (kept by the caller: a thread walks forward)
-        auto sampleAt = [&](uint32_t i, uint32_t &b) -> double {
+        auto sampleAt = [&](uint32_t i, uint32_t &b) -> double {           // sample i of the concatenation
             while (sBlockStart[b + 1] <= i) ++b;
-            const uint32_t nb = sBlockLen[b], j = i - sBlockStart[b];
-            const float *base = prm.batch + sBlockOff[b];
-            const float *pa, *pb;
-            if (localMode == SGZ_OSC_RIGHT) pa = pb = base + size_t(pair + 1) * nb;
-            else if (localMode == SGZ_OSC_LEFT) pa = pb = base + size_t(pair) * nb;
-            else if (localMode == SGZ_OSC_SEPARATE) pa = pb = base + size_t(prm.trigSeparate) * nb;
-            else { pa = base + size_t(pair) * nb; pb = pa + nb; }
-            return trigSample(localMode, pa, pb, j);
+            const float *a, *c;
+            const uint32_t mode = triggerPlanes(prm, prm.batch + sBlockOff[b], sBlockLen[b], a, c);
+            return trigSample(mode, a, c, i - sBlockStart[b]);
         };
-        const double threshold = st->threshold, prevState = st->state;
-        const int armedIn = st->isPeakHold;
-        const unsigned long long originIn = st->crossOrigin, playhead0 = st->playhead;
-        const uint32_t seg = (N + T - 1) / T;
-        const uint32_t i0 = min(N, uint32_t(tid) * seg), i1 = min(N, i0 + seg);
-        uint32_t bStart = 0;                                               // the block of sample i0 - 1 (or of i0)
-        double before = prevState;                                         // sample i0 - 1
-        if (i0 > 0 && i0 <= N) before = sampleAt(i0 - 1, bStart);
-        int segArm = INT_MIN, segThr = INT_MIN;
-        {
-            uint32_t b = bStart; double prev = before;
-            for (uint32_t i = i0; i < i1; ++i) {
-                const double s = sampleAt(i, b);
-                if (s > 0 && prev < 0) segArm = int(i);
-                if (s > threshold) segThr = int(i);
-                prev = s;
-            }
-        }
-        int totArm, totThr, inArm, inThr;
-        blockExclusiveMax2(segArm, armedIn ? -1 : -3, segThr, -2, sScan2, inArm, inThr, totArm, totThr);
-        unsigned int fires = 0;
-        {
-            uint32_t b = bStart; double prev = before;
-            int la = inArm, lt = inThr;
-            for (uint32_t i = i0; i < i1; ++i) {
-                const double s = sampleAt(i, b);
-                if (s > 0 && prev < 0) la = int(i);
-                if (s > threshold) { if (la > lt) { ++fires; atomicAdd(&sFires[b], 1u); } lt = int(i); }
-                prev = s;
-            }
-        }
-        unsigned int totalFires;
-        unsigned int pos = blockExclusiveSum(fires, sSum, &totalFires);
-        const unsigned int q0 = st->qHead, qc0 = st->qCount;
-        if (qc0 + totalFires <= kPeakCap) {                                // (uniform) nothing can be dropped
-            uint32_t b = bStart; double prev = before;
-            int la = inArm, lt = inThr;
-            for (uint32_t i = i0; i < i1; ++i) {
-                const double s = sampleAt(i, b);
-                if (s > 0 && prev < 0) la = int(i);
-                if (s > threshold) {
-                    if (la > lt) {
-                        prm.peaks[(q0 + qc0 + pos) % kPeakCap] = (la == -1) ? originIn : playhead0 + (unsigned long long)la;
-                        ++pos;
-                    }
-                    lt = int(i);
-                }
-                prev = s;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                st->isPeakHold = totArm > totThr ? 1 : 0;
-                if (totArm >= 0) st->crossOrigin = playhead0 + (unsigned long long)totArm;
-                uint32_t bl = prm.numBlocks - 1;
-                st->state = sampleAt(N - 1, bl);
-                sBatchedA = 1;
-            }
-        }
+        if (zeroCrossings(sBlockStart[prm.numBlocks], sampleAt, st, prm.peaks, st->playhead, sFires, sScan2, sSum) && tid == 0) sBatchedA = 1;
         __syncthreads();
     }
     const bool batchedA = sBatchedA != 0;
-    for (uint32_t blockIndex = 0; blockIndex < prm.numBlocks; ++blockIndex) {
-    const float *const blk = prm.batch + sBlockOff[blockIndex];
-    const uint32_t n = sBlockLen[blockIndex];
-    const unsigned long long playhead = st->playhead;
-    ICLK(0);
-
-    // ---- update(), StreamPreprocessing.h:55-76 (thread 0; the queue edits must precede phase A's appends)
-    if (tid == 0) {
-        st->steadyClock = playhead;
-        if (st->windowChanged) {
-            st->windowChanged = 0;
-            if (st->isWorkingOnPeak && st->qCount) { st->qHead = (st->qHead + 1) % kPeakCap; st->qCount--; }
-            while (st->qCount && prm.peaks[st->qHead] < playhead) { st->qHead = (st->qHead + 1) % kPeakCap; st->qCount--; }
-            st->bufferedSamples = st->currentPeak = st->oldPeak = 0;
-            st->frontOrigin = playhead;
-            st->isWorkingOnPeak = 0;
-        }
-    }
-    __syncthreads();
-
     const bool hold = prm.triggerMode == 4u || prm.triggerMode == 3u;      // ZeroCrossing, EnvelopeHold: detector -> processMutating
-    // ---- A': PeakHoldProcessor over the block (StreamPreprocessing.h:270-313): an envelope follower whose every step depends on the
-    // last one's branch -- one lane walks the block (a few microseconds per 512 samples; the triggers it finds are rare)
-    if (prm.triggerMode == 3u && C >= 2) {
-        if (tid == 0) {
-            uint32_t localMode = prm.oscMode, pair = prm.trigPair;
-            if (localMode == SGZ_OSC_MIDSIDE) { localMode = SGZ_OSC_MID; pair = prm.trigSeparate & ~1u; }     // :340-352
+    for (uint32_t blockIndex = 0; blockIndex < prm.numBlocks; ++blockIndex) {
+        const float *const blk = prm.batch + sBlockOff[blockIndex];
+        const uint32_t n = sBlockLen[blockIndex];
+        const unsigned long long playhead = st->playhead;
+        ICLK(0);
+        if (tid == 0) updatePhase(st, prm.peaks, playhead);
+        __syncthreads();
+        if (prm.triggerMode == 3u && C >= 2) {
+            if (tid == 0) peakHoldPhase(prm, st, blk, n, playhead);
+            __syncthreads();
+        }
+        if (batchedA) {                                                    // (found for the whole batch above: this callback's triggers become visible)
+            if (tid == 0) st->qCount += sFires[blockIndex];
+            __syncthreads();
+        } else if (prm.triggerMode == 4u && C >= 2) {
             const float *a, *b;
-            if (localMode == SGZ_OSC_RIGHT) a = b = blk + size_t(pair + 1) * n;
-            else if (localMode == SGZ_OSC_LEFT) a = b = blk + size_t(pair) * n;
-            else if (localMode == SGZ_OSC_SEPARATE) a = b = blk + size_t(prm.trigSeparate) * n;
-            else { a = blk + size_t(pair) * n; b = a + n; }
-            double state = st->state;
-            const double thr2 = st->threshold * st->threshold, hysteresis = st->hysteresis;
-            int holding = st->isPeakHold;
-            unsigned int qc = st->qCount;
-            const unsigned int q0 = st->qHead;
-            unsigned long long dropped = 0;
-            for (uint32_t i = 0; i < n; ++i) {
-                double sample = trigSample(localMode, a, b, i);
-                sample *= sample;
-                const double delta = sample - state;
-                if (delta < 0) {
-                    state *= 0.9999;
-                    state = fmax(thr2, state);
-                    if (holding) {
-                        if (qc < kPeakCap) { prm.peaks[(q0 + qc) % kPeakCap] = playhead + (unsigned long long)i - 1ull; ++qc; }
-                        else ++dropped;
-                        holding = 0;
-                    }
-                } else {
-                    if (delta > hysteresis * state) holding = 1;
-                    state = sample;
-                }
-            }
-            st->state = state; st->isPeakHold = holding; st->qCount = qc; st->droppedPeaks += dropped;
+            const uint32_t mode = triggerPlanes(prm, blk, n, a, b);
+            zeroCrossings(n, [&](uint32_t i, uint32_t &) { return trigSample(mode, a, b, i); }, st, prm.peaks, playhead, nullptr, sScan2, sSum);
+            __syncthreads();
         }
+        ICLK(1);
+        if (hold && tid < int(kStage) && uint32_t(tid) < st->qCount) sPeaks[tid] = prm.peaks[(st->qHead + uint32_t(tid)) % kPeakCap];
         __syncthreads();
-    }
-    // ---- A: ZeroCrossingProcessor over the block (executeSamplingWindows, OscilloscopeDSP.inl:311-385)
-    if (batchedA) {                                                        // (found for the whole batch above: this callback's triggers become visible)
-        if (tid == 0) st->qCount += sFires[blockIndex];
+        if (hold && tid < 64) processMutating(prm, st, n, sPeaks, sSwaps, sPlan);
+        else if (tid == 0) sPlan = SwapPlan{0u, 0u, n};
         __syncthreads();
-    } else if (prm.triggerMode == 4u && C >= 2) {
-        uint32_t localMode = prm.oscMode, pair = prm.trigPair;
-        if (localMode == SGZ_OSC_MIDSIDE) { localMode = SGZ_OSC_MID; pair = prm.trigSeparate & ~1u; }     // :340-352
-        const float *a, *b;
-        if (localMode == SGZ_OSC_RIGHT) a = b = blk + size_t(pair + 1) * n;
-        else if (localMode == SGZ_OSC_LEFT) a = b = blk + size_t(pair) * n;
-        else if (localMode == SGZ_OSC_SEPARATE) a = b = blk + size_t(prm.trigSeparate) * n;
-        else { a = blk + size_t(pair) * n; b = a + n; }
-        const double threshold = st->threshold, prevState = st->state;
-        const int armedIn = st->isPeakHold;
-        const unsigned long long originIn = st->crossOrigin;
-        const uint32_t seg = (n + T - 1) / T;
-        const uint32_t i0 = min(n, uint32_t(tid) * seg), i1 = min(n, i0 + seg);
-        // arm_i = (s_i > 0 && s_{i-1} < 0); fire_i <=> s_i > threshold && lastArm(i) > lastThr(i-1)  (virtual indices: an arm
-        // inherited from the previous block sits at -1, "no arm" at -3, "no threshold crossing yet" at -2)
-        int segArm = INT_MIN, segThr = INT_MIN;                           // (sample indices of this block, < 2^31; "nothing yet" below every sentinel)
-        for (uint32_t i = i0; i < i1; ++i) {
-            const double s = trigSample(localMode, a, b, i);
-            const double prev = i ? trigSample(localMode, a, b, i - 1) : prevState;
-            if (s > 0 && prev < 0) segArm = int(i);
-            if (s > threshold) segThr = int(i);
+        ICLK(2);
+        if (prm.colours) {
+            colourPhase(col, blk, n, C);
+            __syncthreads();
         }
-        int totArm, totThr, inArm, inThr;
-        blockExclusiveMax2(segArm, armedIn ? -1 : -3, segThr, -2, sScan2, inArm, inThr, totArm, totThr);
-        int la = inArm, lt = inThr;
-        unsigned int fires = 0;
-        for (uint32_t i = i0; i < i1; ++i) {
-            const double s = trigSample(localMode, a, b, i);
-            const double prev = i ? trigSample(localMode, a, b, i - 1) : prevState;
-            if (s > 0 && prev < 0) la = int(i);
-            if (s > threshold) { if (la > lt) ++fires; lt = int(i); }
-        }
-        unsigned int totalFires;
-        unsigned int pos = blockExclusiveSum(fires, sSum, &totalFires);
-        const unsigned int q0 = st->qHead, qc0 = st->qCount;
-        la = inArm; lt = inThr;
-        for (uint32_t i = i0; i < i1; ++i) {
-            const double s = trigSample(localMode, a, b, i);
-            const double prev = i ? trigSample(localMode, a, b, i - 1) : prevState;
-            if (s > 0 && prev < 0) la = int(i);
-            if (s > threshold) {
-                if (la > lt) {
-                    if (qc0 + pos < kPeakCap) prm.peaks[(q0 + qc0 + pos) % kPeakCap] = (la == -1) ? originIn : playhead + (unsigned long long)la;
-                    ++pos;
-                }
-                lt = int(i);
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned int room = kPeakCap - qc0;
-            st->qCount = qc0 + (totalFires < room ? totalFires : room);
-            if (totalFires > room) st->droppedPeaks += totalFires - room;
-            st->isPeakHold = totArm > totThr ? 1 : 0;
-            if (totArm >= 0) st->crossOrigin = playhead + (unsigned long long)totArm;
-            st->state = n ? trigSample(localMode, a, b, n - 1) : prevState;
-        }
-        __syncthreads();
-    }
-
-    ICLK(1);
-    // ---- B: processMutating's automaton (thread 0) -> swap list.  The head of the trigger queue is fetched by 64 lanes at once and the
-    // swap list starts in LDS: the automaton then walks without memory round trips (a block holds a handful of triggers)
-    if (hold && tid < int(kStage) && uint32_t(tid) < st->qCount) sPeaks[tid] = prm.peaks[(st->qHead + uint32_t(tid)) % kPeakCap];
-    const unsigned int qHeadIn = st->qHead;
-    __syncthreads();
-    auto peakAt = [&](unsigned int q) {
-        const unsigned int k = (q + kPeakCap - qHeadIn) % kPeakCap;
-        return k < kStage ? sPeaks[k] : prm.peaks[q];
-    };
-    if (tid < 64) {                                                  // wave 0, every lane the same scalar walk (lane 0 stores); the rounds below use all of them
-        const bool lane0 = tid == 0;
-        unsigned int numSwaps = 0, lastStart = 0, lastLen = n;
+        // (phase B has not touched the ring fields of the state: the block's rings start where the last block left them)
+        const uint32_t cursor0 = st->frontCursor;
         const unsigned long long written0 = st->written;
-        if (lane0) { sCursor0 = st->frontCursor; sWritten0 = written0; }
-        if (hold) {
-            unsigned long long bufferedSamples = st->bufferedSamples, frontOrigin = st->frontOrigin, steadyClock = st->steadyClock;
-            unsigned long long oldPeak = st->oldPeak, currentPeak = st->currentPeak;
-            unsigned int qHead = st->qHead, qCount = st->qCount;
-            int isWorkingOnPeak = st->isWorkingOnPeak;
-            unsigned int swapsDone = 0;
-            unsigned long long numSamples = n, consumed = 0;
-            if (frontOrigin + bufferedSamples < steadyClock) { frontOrigin = steadyClock; bufferedSamples = 0; }   // :81-85
-            const double ceilingSize = ceil(st->windowSize);
-            const double halfSize = ceilingSize / 2;
-            const unsigned long long bufferedCap = (unsigned long long)(ceilingSize + 1);                      // :101
-            // (for an integer d >= 0:  double(d) < halfSize  <=>  d < ceil(halfSize))
-            const unsigned long long halfCeil = (unsigned long long)ceil(halfSize);
-            auto processIntoBackBuffer = [&](unsigned long long samples) {                                     // :90-105
-                lastStart = (unsigned int)consumed; lastLen = (unsigned int)samples;
-                consumed += samples;
-                numSamples -= samples;
-                const unsigned long long oldSamples = bufferedSamples;
-                steadyClock += samples;
-                bufferedSamples += samples;
-                bufferedSamples = minU64(bufferedSamples, bufferedCap);
-                frontOrigin += (oldSamples + samples) - bufferedSamples;
-            };
-            if (ceilingSize == 0 && qCount) qCount = 0;                                                        // :107-110
-            // The walk below is the reference's, branch for branch.  In front of it, the same walk for the case a running stream is
-            // in at almost every trigger -- the next trigger lies inside the current window (less than half a window after the last
-            // one): what the general body computes then is  missing = peak - oldPeak, neededPreSamples = 0, take what is missing
-            // from the callback, swap min(buffered, missing + 1) samples  (every
-            // double in :147-190 is an integer plus, at most, the half of an odd window: the casts truncate it away on both sides of
-            // the one subtraction that matters).  Some forty triggers per callback at cfg3: 8.9 us of a 16 us callback in the general body, 6.3 us here (a lone lane issues an
-            // instruction every ~8 cycles; the same in 32-bit arithmetic relative to the callback's start, or with the queue's head read
-            // one trigger ahead, measured no faster).  Anything else -- a trigger outside the window -- leaves the state exactly as
-            // the general body expects it at that point and falls through to it.
-            while (numSamples != 0) {
-                // ---- a ROUND: up to 64 queued triggers at once, one per lane.  For a trigger that is fetched with the running clock
-                // already past it (no samples swallowed at the fetch, :128), inside the window and in order, the walk does
-                //     taken = max(missing - buffered, 0) samples from the callback;  swap min(max(buffered, missing), missing + 1);
-                //     buffered <- max(buffered - (missing + 1), 0)
-                // -- maps that compose by addition: buffered in front of trigger l is max(buffered_0 - sum_{i<l}(missing_i + 1), 0),
-                // so every trigger's numbers are prefix sums.  The round takes the longest run of such triggers that the callback's
-                // samples cover (the first one fetched at or after the running clock, out of order, outside the window, or short of
-                // samples ends it) and leaves the walk's state behind it; the scalar iteration below handles whatever comes next.
-                if (!isWorkingOnPeak && qCount >= 4u && halfCeil <= (1ull << 24) && bufferedSamples <= bufferedCap && bufferedSamples < (1ull << 30) &&
-                    numSamples < (1ull << 30) && steadyClock < (1ull << 51)) {
-                    const unsigned long long base = steadyClock;
-                    auto fits = [&](unsigned long long v) { const long long r = (long long)(v - base); return r > -(1ll << 30) && r < (1ll << 30); };
-                    if (fits(oldPeak)) {
-                        const unsigned int lane = (unsigned int)tid, cnt = qCount < 64u ? qCount : 64u;
-                        const unsigned int buf0 = (unsigned int)bufferedSamples, ns0 = (unsigned int)numSamples, hc = (unsigned int)halfCeil;
-                        auto scan = [&](unsigned int v) {                         // inclusive prefix sum over the wave
-#pragma unroll
-                            for (int o = 1; o < 64; o <<= 1) { const unsigned int u = __shfl_up(v, o); if (lane >= (unsigned int)o) v += u; }
-                            return v;
-                        };
-                        const unsigned long long pk = lane < cnt ? peakAt((qHead + lane) % kPeakCap) : 0ull;
-                        bool ok = lane < cnt && fits(pk);
-                        const int p = ok ? int((long long)(pk - base)) : 0;
-                        int prev = __shfl_up(p, 1);
-                        if (lane == 0) prev = int((long long)(oldPeak - base));
-                        ok = ok && p >= prev;
-                        const unsigned int d = ok ? (unsigned int)(p - prev) : 0u;
-                        ok = ok && d < hc;
-                        const unsigned int a = ok ? d + 1u : 0u;
-                        const unsigned int S = scan(a), Sprev = S - a;
-                        const unsigned int bufL = buf0 > Sprev ? buf0 - Sprev : 0u;
-                        const unsigned int tp = ok && d > bufL ? d - bufL : 0u;
-                        const unsigned int Cc = scan(tp), Cprev = Cc - tp;
-                        const bool swallow = ok && p >= 0 && (unsigned int)p >= Cprev;       // fetched at or after the running clock (base + Cprev)
-                        const bool stop = !ok || swallow || Cc > ns0 || Cprev >= ns0;
-                        const unsigned long long stops = __ballot(stop);
-                        const unsigned int m = stops ? (unsigned int)__builtin_ctzll(stops) : 64u;   // triggers 0 .. m-1 complete
-                        if (m > 0) {
-                            const unsigned int bufTake = bufL > d ? bufL : d, capped = bufTake < d + 1u ? bufTake : d + 1u;
-                            const unsigned int capSum = scan(lane < m ? capped : 0u);
-                            if (lane < m && numSwaps + lane < kMaxSwaps) {
-                                const Swap sw{written0 + consumed + Cc - bufTake, capped};
-                                if (numSwaps + lane < kStage) sSwaps[numSwaps + lane] = sw; else prm.swapList[numSwaps + lane] = sw;
-                            }
-                            const unsigned long long took = __ballot(lane < m && tp > 0u);
-                            if (took) {
-                                const int hl = 63 - __builtin_clzll(took);
-                                lastStart = (unsigned int)consumed + __shfl(Cprev, hl);
-                                lastLen = __shfl(tp, hl);
-                            }
-                            const unsigned int Sm = __shfl(S, int(m) - 1), Cm = __shfl(Cc, int(m) - 1), capM = __shfl(capSum, int(m) - 1);
-                            const int pm = __shfl(p, int(m) - 1);
-                            bufferedSamples = buf0 > Sm ? buf0 - Sm : 0u;
-                            numSamples -= Cm; consumed += Cm; steadyClock += Cm;
-                            frontOrigin += capM;
-                            oldPeak = currentPeak = base + (unsigned long long)(long long)pm;
-                            qHead = (qHead + m) % kPeakCap; qCount -= m;
-                            swapsDone += m;
-                            numSwaps = numSwaps + m < kMaxSwaps ? numSwaps + m : kMaxSwaps;
-                            continue;
-                        }
-                    }
-                }
-                bool fastDone = false;
-                if (qCount) do {
-                    if (!isWorkingOnPeak) {                                          // :120-141
-                        const unsigned long long nextPeak = peakAt(qHead);
-                        isWorkingOnPeak = 1;
-                        if (nextPeak >= steadyClock) {
-                            const unsigned long long deltaToPeak = nextPeak - steadyClock;
-                            const unsigned long long toProcess = minU64(numSamples, (unsigned long long)(double(deltaToPeak) + halfSize));
-                            processIntoBackBuffer(toProcess);
-                        }
-                        currentPeak = nextPeak;
-                    }
-                    if (currentPeak < oldPeak) break;                                // (the general body: the difference wraps, "outside the window")
-                    const unsigned long long d = currentPeak - oldPeak;
-                    if (d >= halfCeil || oldPeak >= (1ull << 51)) break;
-                    // inside the window: windowEnd = oldPeak + (u64)halfSize, peakWindowEnd = currentPeak + (u64)halfSize,
-                    // missingBufferSamples = d, neededPreSamples = 0
-                    if (bufferedSamples < d) {                                       // :176-182: the samples still missing come out of this callback
-                        const unsigned long long numRemaining = d - bufferedSamples;
-                        const unsigned long long toProcess = minU64(numSamples, numRemaining);
-                        if (toProcess > 0) processIntoBackBuffer(toProcess);
-                        if (numRemaining != toProcess) { fastDone = true; break; }   // not ready: the callback is used up, the trigger stays open
-                    }
-                    const unsigned long long cappedSize = minU64(bufferedSamples, d + 1ull);
-                    if (numSwaps < kMaxSwaps) {
-                        const Swap sw{(written0 + consumed) - bufferedSamples, (unsigned int)cappedSize};
-                        if (lane0) { if (numSwaps < kStage) sSwaps[numSwaps] = sw; else prm.swapList[numSwaps] = sw; }     // (two stores: a selected reference is a flat one)
-                        ++numSwaps;
-                    }
-                    bufferedSamples -= cappedSize;
-                    frontOrigin += cappedSize;
-                    oldPeak = currentPeak;
-                    isWorkingOnPeak = 0;
-                    qHead = (qHead + 1) % kPeakCap; qCount--;
-                    ++swapsDone;
-                    fastDone = true;
-                } while (false);
-                if (fastDone) continue;
-                if (!qCount) { processIntoBackBuffer(numSamples); break; }
-                else if (!isWorkingOnPeak) {
-                    isWorkingOnPeak = 1;
-                    const unsigned long long nextPeak = peakAt(qHead);
-                    if (nextPeak >= steadyClock) {
-                        const unsigned long long deltaToPeak = nextPeak - steadyClock;
-                        const unsigned long long toProcess = minU64(numSamples, (unsigned long long)(double(deltaToPeak) + halfSize));
-                        processIntoBackBuffer(toProcess);
-                        currentPeak = nextPeak;
-                    } else currentPeak = nextPeak;
-                }
-                unsigned long long windowEnd;
-                bool isPeakOutsideOfWindow = false, readyForBufferSwap = false;
-                if (double(currentPeak - oldPeak) < halfSize) windowEnd = (unsigned long long)(double(oldPeak) + halfSize);   // :147-150
-                else { isPeakOutsideOfWindow = true; windowEnd = frontOrigin + bufferedSamples; }
-                const unsigned long long peakWindowEnd =
-                    (unsigned long long)(double((isPeakOutsideOfWindow ? 1ull : 0ull) + currentPeak) + halfSize);       // :158
-                unsigned long long toProcess = 0;
-                const unsigned long long missingBufferSamples = peakWindowEnd - minU64(peakWindowEnd, windowEnd);
-                const unsigned long long neededPreSamples =
-                    minU64((unsigned long long)halfSize, (unsigned long long)(fmax(double(currentPeak - oldPeak), halfSize) - halfSize));
-                if (isPeakOutsideOfWindow) {
-                    toProcess = minU64(numSamples, missingBufferSamples);
-                    if (toProcess > 0) processIntoBackBuffer(toProcess);
-                    readyForBufferSwap = missingBufferSamples == toProcess;
-                } else if (bufferedSamples >= missingBufferSamples) readyForBufferSwap = true;
-                else {
-                    const unsigned long long numRemaining = missingBufferSamples - bufferedSamples;
-                    toProcess = minU64(numSamples, numRemaining);
-                    if (toProcess > 0) processIntoBackBuffer(toProcess);
-                    readyForBufferSwap = numRemaining == toProcess;
-                }
-                if (readyForBufferSwap) {
-                    const double amount = (isPeakOutsideOfWindow ? halfSize : double(missingBufferSamples)) + double(neededPreSamples);
-                    const unsigned long long cappedSize = minU64(bufferedSamples, (unsigned long long)ceil(amount + 1));
-                    // swapBuffers(cappedSize, -bufferedSamples): source = the oldest buffered sample onwards
-                    if (numSwaps < kMaxSwaps) {
-                        const Swap sw{(written0 + consumed) - bufferedSamples, (unsigned int)cappedSize};
-                        if (lane0) { if (numSwaps < kStage) sSwaps[numSwaps] = sw; else prm.swapList[numSwaps] = sw; }
-                        ++numSwaps;
-                    }
-                    bufferedSamples -= minU64(bufferedSamples, cappedSize);
-                    frontOrigin += cappedSize;
-                    oldPeak = currentPeak;
-                    isWorkingOnPeak = 0;
-                    if (qCount) { qHead = (qHead + 1) % kPeakCap; qCount--; }
-                    ++swapsDone;
-                }
-            }
-            if (lane0) {
-                st->swaps += swapsDone;                            // (once: a read-modify-write of global memory inside the walk is a round trip per trigger)
-                st->bufferedSamples = bufferedSamples; st->frontOrigin = frontOrigin; st->steadyClock = steadyClock;
-                st->oldPeak = oldPeak; st->currentPeak = currentPeak; st->qHead = qHead; st->qCount = qCount;
-                st->isWorkingOnPeak = isWorkingOnPeak;
-            }
+        ICLK(3);
+        const Planes<float> audio{blk, n, prm.back, prm.front, C};
+        const Planes<uint32_t> colour{col.block, col.maxBlock, col.back, col.front, 2 * C};
+        const uint32_t cursor = frontPhase(prm, audio, colour, hold, sSwaps, sPlan.numSwaps, n, cursor0, written0, sSum);
+        ICLK(4);
+        if (hold) {                                                        // ---- D: the block goes into the back rings
+            copyToBack(audio, n, written0, prm.backCap);
+            if (prm.colours) copyToBack(colour, n, written0, prm.backCap);
         }
-        if (lane0) { sNumSwaps = numSwaps; sLastStart = lastStart; sLastLen = lastLen; }
-    }
-    __syncthreads();
-
-    ICLK(2);
-    // ---- F: per-sample colours of the block (audioProcessing :445-517, :588-647).  Every sample passes through audioProcessing exactly
-    // once and in order, whatever the split into calls, so the filters run over the block as a whole.
-    if (prm.colours) {
-        // The three filter stages hand their per-sample outputs on through LDS, a tile of the callback at a time (samples in, band
-        // signals, smoothed energies: 11 floats per channel and sample; a stereo tile is 416 samples).  Through the HBM scratch every
-        // sixteen samples of every stage waited for a memory round trip of its own: 64 us per stage, 193 us of a 206 us callback.
-        constexpr uint32_t kFFloats = 9216;
-        __shared__ float sF[kFFloats];
-        const uint32_t MB = col.maxBlock;
-        ColourDev *cs = col.st;
-        uint32_t tile = kFFloats / (11u * C);
-        tile = tile >= 16u ? (tile & ~15u) : (tile ? tile : 1u);
-        if (tile > 512u) tile = 512u;
-        float *sX = sF, *sB = sX + size_t(C) * tile, *sS = sB + size_t(4 * C) * tile;       // [C][tile], [4 C][tile], [6 C][tile]
-        // the lanes' filter states stay in registers from tile to tile
-        const bool r12 = uint32_t(tid) < 2 * C, r3 = uint32_t(tid) < 6 * C;
-        const uint32_t fc = uint32_t(tid) >> 1, fhp = uint32_t(tid) & 1u;
-        float k1[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, k2[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f, c0 = 0.f, c1 = 0.f, d0 = 0.f, d1 = 0.f, y = 0.f;
-        float *stp = nullptr;
-        const uint32_t pair3 = uint32_t(tid) / 12u, r = uint32_t(tid) % 12u, sig3 = r / 3u, band3 = r % 3u;
-        if (r12) {
-            const float *ka = fhp ? col.hp1 : col.lp1, *kb = fhp ? col.hp2 : col.lp2;
-            for (int j = 0; j < 5; ++j) { k1[j] = ka[j]; k2[j] = kb[j]; }
-            float (*z1)[2] = cs->z[fc] + (fhp ? 2 : 0), (*z2)[2] = cs->z[fc] + (fhp ? 6 : 4);
-            a0 = z1[0][0]; a1 = z1[0][1]; b0 = z1[1][0]; b1 = z1[1][1];
-            c0 = z2[0][0]; c1 = z2[0][1]; d0 = z2[1][0]; d1 = z2[1][1];
+        ICLK(5);
+        if (prm.envMode == 1u && tid < 64) envelopePhase(prm, st, blk, n, sPlan.lastStart, sPlan.lastLen);
+        __syncthreads();
+        ICLK(6);
+        if (tid == 0) {
+            st->frontCursor = cursor;
+            if (hold) st->written = written0 + n;
+            st->playhead = playhead + n;
         }
-        if (r3) {
-            stp = sig3 == 0 ? &cs->smooth[2 * pair3][band3] : sig3 == 1 ? &cs->smooth[2 * pair3 + 1][band3]
-                : sig3 == 2 ? &cs->aux[2 * pair3][band3] : &cs->aux[2 * pair3 + 1][band3];
-            y = *stp;
-        }
-        const float pole = col.pole;
-        for (uint32_t t0 = 0; t0 < n; t0 += tile) {
-            const uint32_t m = min(tile, n - t0);
-            for (uint32_t e = tid; e < C * m; e += T) { const uint32_t c = e / m, i = e - c * m; sX[size_t(c) * tile + i] = blk[size_t(c) * n + t0 + i]; }
-            __syncthreads();
-            if (r12) {                                                     // F1: low = LP4_f1(x), rest = HP4_f1(x)
-                const float *x = sX + size_t(fc) * tile;
-                float *out = sB + (size_t(fc) * 4 + (fhp ? 3 : 0)) * tile;
-                walkSequential(m, [&](uint32_t i) { return x[i]; },
-                               [&](uint32_t i, float v) { out[i] = biquadStep(k1, b0, b1, biquadStep(k1, a0, a1, v)); });
-            }
-            __syncthreads();
-            if (r12) {                                                     // F2: mid = LP4_f2(rest), high = HP4_f2(rest)
-                const float *x = sB + (size_t(fc) * 4 + 3) * tile;
-                float *out = sB + (size_t(fc) * 4 + (fhp ? 2 : 1)) * tile;
-                walkSequential(m, [&](uint32_t i) { return x[i]; },
-                               [&](uint32_t i, float v) { out[i] = biquadStep(k2, d0, d1, biquadStep(k2, c0, c1, v)); });
-            }
-            __syncthreads();
-            if (r3) {                                                      // F3: filterStates (:460-468) of left, right, mid, side
-                const float *l = sB + (size_t(2 * pair3) * 4 + band3) * tile, *rr = sB + (size_t(2 * pair3 + 1) * 4 + band3) * tile;
-                float *out = sS + size_t(tid) * tile;
-                // (which signal a lane smooths is a lane constant: both inputs are read and the lane's one picked by selects -- as a
-                // branch inside the batched loads the four cases ran one after the other: 90 us of a 150 us callback)
-                const bool isL = sig3 == 0, isR = sig3 == 1, isMid = sig3 == 2;
-                walkSequential(m, [&](uint32_t i) { return l[i]; },
-                               [&](uint32_t i, float lv) {
-                                   const float rv = rr[i];
-                                   const float sum = lv + rv, dif = lv - rv;
-                                   const float v = isL ? lv : (isR ? rv : (isMid ? sum : dif));
-                                   const float input = v * v;
-                                   y = input + pole * (y - input);
-                                   out[i] = y;
-                               });
-            }
-            __syncthreads();
-            for (uint32_t e = tid; e < 2 * C * m; e += T) {                // F4: accumulateColour per (signal, sample)
-                const uint32_t q = e / m, i = e - q * m, pair = q >> 2, sig = q & 3u;
-                const float *sp = sS + size_t(pair * 12 + sig * 3) * tile + i;
-                const float stv[3] = {sp[0], sp[tile], sp[2 * size_t(tile)]};
-                const uint32_t keyCh = 2 * pair + (sig & 1u);              // left / mid: the left key, right / side: the right key
-                const uint32_t plane = (sig < 2 ? 0u : C) + keyCh;         // cwLeft, cwRight -> colourData; cwMid, cwSide -> auxColourData
-                col.block[size_t(plane) * MB + t0 + i] = accumulateColour(stv, col.band, col.keys[keyCh], col.blend);
-            }
-            __syncthreads();
-        }
-        if (r12) {
-            float (*z1)[2] = cs->z[fc] + (fhp ? 2 : 0), (*z2)[2] = cs->z[fc] + (fhp ? 6 : 4);
-            z1[0][0] = a0; z1[0][1] = a1; z1[1][0] = b0; z1[1][1] = b1;
-            z2[0][0] = c0; z2[0][1] = c1; z2[1][0] = d0; z2[1][1] = d1;
-        }
-        if (r3) *stp = y;
         __syncthreads();
     }
-
-    // ---- C: swaps (ZeroCrossing) or the block itself (None / Spectral: audioProcessing straight into the front buffer), in order
-    const uint32_t size = prm.size;
-    uint32_t cursor = sCursor0;
-    ICLK(3);
-    const unsigned long long written0 = sWritten0;
-    // `later`: samples that swaps after this one (same block) will append.  The ring holds `size` samples, so whatever this swap writes
-    // survives only where fewer than `size` samples follow: a noisy signal fires a dozen triggers per block, each swap copies a
-    // window's worth, and only the last one or two are still there when the block is done -- the others just move the cursor.
-    auto appendFront = [&](unsigned long long src, uint32_t len, unsigned long long later) {
-        // only the last `size` samples of a longer run survive in the ring
-        uint32_t skip = len > size ? len - size : 0;
-        const uint32_t cur0 = uint32_t((cursor + skip) % size);
-        // of the remaining m samples the first `dead` are overwritten by the later swaps
-        const uint32_t m0 = len - skip;
-        const unsigned long long room = later >= size ? 0ull : size - later;          // newest samples of this swap that stay visible
-        const uint32_t dead = m0 > room ? uint32_t(m0 - room) : 0u;
-        const uint32_t m = m0 - dead;
-        for (uint32_t c = 0; c < C; ++c)
-            for (uint32_t i = tid; i < m; i += T) {
-                const unsigned long long abs = src + skip + dead + i;
-                const float v = abs >= written0 ? blk[size_t(c) * n + uint32_t(abs - written0)]
-                                                : prm.back[size_t(c) * prm.backCap + uint32_t(abs & (prm.backCap - 1))];
-                uint32_t d = (cur0 + dead + i) % size;
-                prm.front[size_t(c) * size + d] = v;
-            }
-        if (prm.colours)
-            for (uint32_t c = 0; c < 2 * C; ++c)
-                for (uint32_t i = tid; i < m; i += T) {
-                    const unsigned long long abs = src + skip + dead + i;
-                    const uint32_t v = abs >= written0 ? col.block[size_t(c) * col.maxBlock + uint32_t(abs - written0)]
-                                                       : col.back[size_t(c) * prm.backCap + uint32_t(abs & (prm.backCap - 1))];
-                    uint32_t d = (cur0 + dead + i) % size;
-                    col.front[size_t(c) * size + d] = v;
-                }
-        cursor = uint32_t((cursor + len) % size);
-        __syncthreads();
-    };
-    if (hold && sNumSwaps <= kFlat) {
-        // The usual case -- a handful of swaps, all in LDS -- as ONE pass: no two swaps of a block write the same ring slot (what a later
-        // swap would overwrite is `dead` and never written), and their sources are read-only here, so they need no order among
-        // themselves.  Lane k of wave 0 works out swap k's surviving range from prefix sums of the lengths; then every thread
-        // copies its share of the concatenation.  (One swap after the other with a barrier each cost a memory round trip per swap:
-        // 8.9 us of a 25 us block at a dozen swaps, tools/ingest_clocks.py; now 1.9 us.)
-        const uint32_t ns = sNumSwaps;
-        if (ns > kStage) {
-            // more swaps than a wave has lanes (a 10 kHz tone at 48 kHz crosses zero 107 times per 512-sample callback): the same
-            // tables from workgroup-wide prefix sums, one swap per thread (the swaps beyond the staged ones are read back from HBM).
-            // One after the other they cost 0.65 us each: 74 us per callback at 107, 143 us at 213.
-            const uint32_t k = uint32_t(tid);
-            const bool live = k < ns;
-            Swap sw{0ull, 0u, 0u};
-            if (live) sw = k < kStage ? sSwaps[k] : prm.swapList[k];
-            const uint32_t len = sw.len;
-            unsigned long long total;
-            const unsigned long long inc = blockInclusiveSum<unsigned long long>(len, sScan64, &total);
-            const unsigned long long before = inc - len, later = total - inc;
-            const uint32_t skip = len > size ? len - size : 0u;
-            const uint32_t m0 = len - skip;
-            const unsigned long long room = later >= size ? 0ull : size - later;
-            const uint32_t dead = m0 > room ? uint32_t(m0 - room) : 0u;
-            const uint32_t m = m0 - dead;
-            uint32_t totalM;
-            const uint32_t incM = blockInclusiveSum<uint32_t>(m, sSum, &totalM);
-            if (live) {
-                sFlatSrc[k] = sw.src + skip + dead;
-                sFlatDst[k] = uint32_t((sCursor0 + before + skip + dead) % size);
-                sFlatEnd[k] = incM;
-            }
-            if (tid == 0) { sFlatTotal = totalM; sCursorEnd = uint32_t((sCursor0 + total) % size); }
-        } else if (tid < 64) {
-            const uint32_t k = uint32_t(tid);
-            const bool live = k < ns;
-            const uint32_t len = live ? sSwaps[live ? k : 0].len : 0u;
-            const unsigned long long src0 = live ? sSwaps[k].src : 0ull;
-            unsigned long long inc = len;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const unsigned long long u = __shfl_up(inc, o); if (tid >= o) inc += u; }
-            const unsigned long long total = __shfl(inc, 63), before = inc - len, later = total - inc;
-            const uint32_t skip = len > size ? len - size : 0u;
-            const uint32_t m0 = len - skip;
-            const unsigned long long room = later >= size ? 0ull : size - later;
-            const uint32_t dead = m0 > room ? uint32_t(m0 - room) : 0u;
-            const uint32_t m = m0 - dead;
-            uint32_t incM = m;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incM, o); if (tid >= o) incM += u; }
-            sFlatSrc[k] = src0 + skip + dead;
-            sFlatDst[k] = uint32_t((sCursor0 + before + skip + dead) % size);
-            sFlatEnd[k] = incM;
-            if (tid == 63) { sFlatTotal = incM; sCursorEnd = uint32_t((sCursor0 + total) % size); }
-        }
-        __syncthreads();
-        const uint32_t M = sFlatTotal;
-        auto locate = [&](uint32_t e, unsigned long long &abs, uint32_t &d) {
-            uint32_t lo = 0, hi = ns;                                    // smallest k with sFlatEnd[k] > e
-            while (lo + 1 < hi) { const uint32_t mid = (lo + hi) >> 1; if (sFlatEnd[mid - 1] > e) hi = mid; else lo = mid; }
-            const uint32_t i = e - (lo ? sFlatEnd[lo - 1] : 0u);
-            abs = sFlatSrc[lo] + i;
-            d = (sFlatDst[lo] + i) % size;
-        };
-        for (uint32_t e = tid; e < M; e += T) {
-            unsigned long long abs; uint32_t d;
-            locate(e, abs, d);
-            const bool fromBlock = abs >= written0;
-            const uint32_t bi = uint32_t(abs - written0), ri = uint32_t(abs & (prm.backCap - 1));
-            for (uint32_t c = 0; c < C; ++c)
-                prm.front[size_t(c) * size + d] = fromBlock ? blk[size_t(c) * n + bi] : prm.back[size_t(c) * prm.backCap + ri];
-            if (prm.colours)
-                for (uint32_t c = 0; c < 2 * C; ++c)
-                    col.front[size_t(c) * size + d] = fromBlock ? col.block[size_t(c) * col.maxBlock + bi] : col.back[size_t(c) * prm.backCap + ri];
-        }
-        cursor = sCursorEnd;
-        __syncthreads();
-    } else if (hold) {
-        const uint32_t ns = sNumSwaps;
-        // suffix sums of the swap lengths: thread-private walk from the back (the list is short)
-        unsigned long long later = 0;
-        auto swapAt = [&](uint32_t k) { return k < kStage ? sSwaps[k] : prm.swapList[k]; };
-        for (uint32_t k = 0; k < ns; ++k) later += swapAt(k).len;
-        for (uint32_t k = 0; k < ns; ++k) {
-            const Swap sw = swapAt(k);
-            later -= sw.len;
-            appendFront(sw.src, sw.len, later);
-        }
-    } else appendFront(written0, n, 0ull);
-
-    ICLK(4);
-    // ---- D: the block goes into the back rings (ZeroCrossing / EnvelopeHold only; absolute index mod backCap)
-    if (hold) {
-        const uint32_t keep = n > prm.backCap ? prm.backCap : n, first = n - keep;
-        for (uint32_t e = tid; e < keep * C; e += T) {
-            const uint32_t c = e / keep, i = first + (e - c * keep);
-            prm.back[size_t(c) * prm.backCap + uint32_t((written0 + i) & (prm.backCap - 1))] = blk[size_t(c) * n + i];
-        }
-        if (prm.colours)
-            for (uint32_t e = tid; e < keep * 2 * C; e += T) {
-                const uint32_t c = e / keep, i = first + (e - c * keep);
-                col.back[size_t(c) * prm.backCap + uint32_t((written0 + i) & (prm.backCap - 1))] = col.block[size_t(c) * col.maxBlock + i];
-            }
-    }
-
-    ICLK(5);
-    // ---- E: RMS envelope (audioProcessing, OscilloscopeDSP.inl:520-585, :676-693); wave 0, lane c = recurrence c
-    // (the reference runs the recurrence in PeakDecay mode too and throws the result away, :506-585 against :676: only RMS stores it)
-    if (prm.envMode == 1u && tid < 64) {
-        const bool active = tid < int(C);
-        const float k = prm.envelopeCoeff;
-        const uint32_t mode = prm.oscMode;
-        const uint32_t lastStart = sLastStart, lastLen = sLastLen;
-        // channels 0 / 1 are stored back (:690-691) and so run through every audioProcessing call of the block; the others restart
-        // from their stored envelope in every call, so only the last call's samples matter for them
-        const uint32_t from = tid < 2 ? 0u : lastStart, to = lastStart + lastLen;
-        float y = active ? st->envelope[tid] : 0.f;
-        const float *b0 = blk, *b1 = blk + n, *bc = blk + size_t(active ? tid : 0) * n;
-        bool own = false;
-        if (mode == SGZ_OSC_SEPARATE) {
-            own = true;
-            if (active) walkSequential(to - from, [&](uint32_t i) { return bc[from + i]; }, [&](uint32_t, float v) { const float s = v * v; y = s + k * (y - s); });
-        } else if (mode == SGZ_OSC_MIDSIDE) {
-            if (tid < 2) {
-                own = true;
-                // the mix itself is exact in either order of evaluation: (l +- r) once, squared, halved
-                walkSequential(to, [&](uint32_t i) { return tid == 0 ? b0[i] + b1[i] : b0[i] - b1[i]; },
-                               [&](uint32_t, float v) { const float s = 0.5f * (v * v); y = s + k * (y - s); });
-            }
-        } else if (tid == 0) {
-            own = true;
-            const float *src = mode == SGZ_OSC_RIGHT ? b1 : b0;
-            // (one walk per mode: a branch inside the load would keep the batch of loads from being issued together)
-            auto rms = [&](uint32_t, float v) { const float s = v * v; y = s + k * (y - s); };
-            if (mode == SGZ_OSC_MID) walkSequential(to, [&](uint32_t i) { return 0.5f * (b0[i] + b1[i]); }, rms);
-            else if (mode == SGZ_OSC_SIDE) walkSequential(to, [&](uint32_t i) { return 0.5f * (b0[i] - b1[i]); }, rms);
-            else walkSequential(to, [&](uint32_t i) { return src[i]; }, rms);
-        }
-        // filterEnv[c] of the last call: copies of channel 0 (mono modes) / channel 1 (MidSide) where the channel has no recurrence
-        const float y0 = __shfl(y, 0), y1 = __shfl(y, 1);
-        const float fe = own ? y : (mode == SGZ_OSC_MIDSIDE ? y1 : y0);
-        if (prm.envMode == 1u) {                           // RMS: gain and stored envelopes
-            float start = active ? __builtin_sqrtf(fe) : 0.f;
-            for (int o = 32; o > 0; o >>= 1) start = fmaxf(start, __shfl_xor(start, o));
-            if (tid == 0) {
-                st->envelopeGain = 1.0 / double(start);
-                st->envelope[0] = y0;
-                st->envelope[1] = (mode == SGZ_OSC_SEPARATE || mode == SGZ_OSC_MIDSIDE) ? y1 : y0;
-            }
-        }
-    }
-    __syncthreads();
-    ICLK(6);
-    if (tid == 0) {
-        st->frontCursor = cursor;
-        if (hold) st->written = written0 + n;
-        st->playhead = playhead + n;
-    }
-    __syncthreads();
-    }   // next block of the batch
     for (uint32_t w = tid; w < sizeof(ScopeDev) / 4; w += T) reinterpret_cast<uint32_t *>(prm.st)[w] = reinterpret_cast<const uint32_t *>(&sState)[w];
     ICLK(7);
     if (prm.doPeak) {                                            // (uniform) the rings and the state this launch wrote, as every lane sees them
