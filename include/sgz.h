@@ -659,12 +659,18 @@ sgz_status sgz_scope_front_colours(sgz_scope *s, uint32_t channel, uint32_t aux,
 sgz_status sgz_scope_debug_state(sgz_scope *s, uint64_t out[8]);
 
 /* ------------------------------------------------------------------------------------------------
- * Vectorscope: polar transform (drawPolarPlot, VectorscopeRendering.cpp:500-746) and the audio-thread
- * one-pole filters (Processor::audioProcessing, Vectorscope.cpp:268-377).
+ * Vectorscope: polar transform (drawPolarPlot, VectorscopeRendering.cpp:500-746), Lissajous plot (drawRectPlot, :444-497) and
+ * the audio-thread one-pole filters (Processor::audioProcessing, Vectorscope.cpp:268-377).
  */
 /* d_xyz: DEVICE float3 [pairs][n]; pair p uses channels 2p, 2p+1 of d_planar */
 sgz_status sgz_vector_polar_device(const float *d_planar, size_t stride, uint32_t pairs, size_t n,
                                    uint32_t lanes, float *d_xyz, void *stream);
+/* The Lissajous plot (drawRectPlot, VectorscopeRendering.cpp:444-497) of `pairs` pairs of d_planar (DEVICE, oldest sample first;
+ * pair p = channels 2p, 2p+1 at d_planar + c * stride, stride >= n, n <= 2^31): vertex v of pair p = (right, left, v * sampleFade - 1)
+ * with sampleFade = 1 / max(1, n - 1); d_xyz: DEVICE float3 [pairs][n].  d_rgb (DEVICE float3 [pairs][n], or NULL): colours[p] * fade
+ * (fade = v * sampleFade) when `fade` is set, colours[p] otherwise; colours: HOST float [pairs][3], needed only when d_rgb != NULL. */
+sgz_status sgz_vector_lissajous_device(const float *d_planar, size_t stride, uint32_t pairs, size_t n, uint32_t fade,
+                                       const float *colours, float *d_xyz, float *d_rgb, void *stream);
 typedef struct sgz_vector_filters { float env[2]; float balance[2][2]; float phase[2]; } sgz_vector_filters;
 sgz_status sgz_vector_audio_processing_device(sgz_vector_filters *f, const float *d_left, const float *d_right,
                                               size_t n, uint32_t lanes, float envelope_coeff, float stereo_coeff,
@@ -672,8 +678,8 @@ sgz_status sgz_vector_audio_processing_device(sgz_vector_filters *f, const float
 
 /* Vectorscope real-time handle: replaces VectorScope::Processor::onStreamAudio -> audioProcessing (Source/Vectorscope/Vectorscope.h:141,
  * Vectorscope.cpp:268-392) and the cpl::AudioStream history the renderer reads, and on the render thread VectorScope::runPeakFilter
- * (VectorscopeRendering.cpp:826-889) and drawPolarPlot (:500-746) for every channel pair -> the (x, y, z) + (r, g, b) stream
- * PrimitiveDrawer::addVertex / addColour receive.  History ring, filter states and gain live in HBM; push = (batched, as sgz_scope_push) one staged copy + one
+ * (VectorscopeRendering.cpp:826-889), drawPolarPlot (:500-746) or drawRectPlot (:444-497) for every channel pair and drawStereoMeters
+ * (:748-823) -> the (x, y, z) + (r, g, b) stream PrimitiveDrawer::addVertex / addColour receive.  History ring, filter states and gain live in HBM; push = (batched, as sgz_scope_push) one staged copy + one
  * launch and never waits for the GPU (SGZ_BUSY instead).  One producer thread (push), one consumer thread (everything else). */
 typedef struct sgz_vector_config {
     double   sample_rate;
@@ -707,6 +713,24 @@ sgz_status sgz_vector_vertices_all(sgz_vector *s, float *xyz, float *rgb, uint32
 void      *sgz_vector_stream(sgz_vector *s);       /* as sgz_scope_stream */
 /* parity hook: history ring memory of one channel + the write cursor */
 sgz_status sgz_vector_history(sgz_vector *s, uint32_t channel, float *out /*window_size*/, uint32_t *size, uint32_t *cursor);
+/* The Lissajous plot (state.isPolar off: drawRectPlot, VectorscopeRendering.cpp:444-497), the polar calls' twins: same buffers, same
+ * count and wait rules, same vertex order (the older section of the ring first).  Vertex v of pair p = (right, left, fade - 1) with
+ * fade = (float) v * sampleFade, sampleFade = 1 / max(1, window_size - 1) -- x, y are the samples as stored (NaN, inf, -0 included).
+ * rgb = colours[p] * fade with fade_history, colours[p] without.  The strip's alpha is not in the stream (it is constant per strip):
+ * with fade_history the reference draws it as getFloatGreen() -- colours[p][1] (quirk Q9) --, without it the colour's own alpha,
+ * which the host's adapter supplies.  Gain, rotation and the primitive type (fillPath) are GL state, as for the polar stream.
+ * These reads leave the polar stream's fade-ramp work alone. */
+sgz_status sgz_vector_lissajous_vertices(sgz_vector *s, uint32_t pair, float *xyz, float *rgb, uint32_t *count);
+sgz_status sgz_vector_lissajous_vertices_all(sgz_vector *s, float *xyz, float *rgb, uint32_t *count);   /* one launch, one wait; host or DEVICE */
+sgz_status sgz_vector_lissajous_vertices_device(sgz_vector *s, uint32_t pair, float *d_xyz, float *d_rgb, uint32_t *count);   /* DEVICE buffers */
+/* drawStereoMeters (VectorscopeRendering.cpp:748-823): the four indicator positions along their meters (0 .. 1 for the non-negative balance states push produces), by filter index k:
+ * balance[k] = atanf(balance[k][1] / balance[k][0]) / (pi_f * 0.5f), 0.5f where that is not normal; stereo[k] = phase[k] * 0.5f + 0.5f.
+ * Reference quirk: drawStereoMeters draws index 0 as the thin full-brightness "quick" indicator, while FilterStates (Vectorscope.h:99-105)
+ * names index 0 Slow -- the fields keep the index, the host draws [0] as the quick and [1] as the slow indicator to match the plugin.
+ * (A struct tag without a typedef, as struct stat beside stat(): the reading function has the same name.) */
+struct sgz_vector_meters { float balance[2]; float stereo[2]; };
+sgz_status sgz_vector_meters_from_filters(const sgz_vector_filters *f, struct sgz_vector_meters *out);   /* host arithmetic only, no GPU */
+sgz_status sgz_vector_meters(sgz_vector *s, struct sgz_vector_meters *out);      /* = sgz_vector_filters_get + the above (flushes, waits) */
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,10 @@ class VectorFilters(C.Structure):
     _fields_ = [("env", C.c_float * 2), ("balance", (C.c_float * 2) * 2), ("phase", C.c_float * 2)]
 
 
+class VectorMeters(C.Structure):
+    _fields_ = [("balance", C.c_float * 2), ("stereo", C.c_float * 2)]
+
+
 class VectorConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_double), ("num_channels", C.c_uint32), ("window_size", C.c_uint32), ("envelope_mode", C.c_uint32),
                 ("lanes", C.c_uint32), ("fade_history", C.c_uint32), ("max_block", C.c_uint32), ("envelope_window", C.c_double),
@@ -138,6 +142,8 @@ EXPORTS = [
     "sgz_vector_filters_get", "sgz_vector_vertices", "sgz_vector_vertices_all", "sgz_spectrum_backlog", "sgz_spectrum_stream", "sgz_spectrum_flush", "sgz_scope_flush", "sgz_scope_set_transport", "sgz_vector_flush", "sgz_vector_history",
     "sgz_scope_num_points", "sgz_scope_lanczos_device", "sgz_scope_zero_crossing_device",
     "sgz_peak_filter_device", "sgz_vector_polar_device", "sgz_vector_audio_processing_device",
+    "sgz_vector_lissajous_vertices", "sgz_vector_lissajous_vertices_all", "sgz_vector_lissajous_vertices_device", "sgz_vector_lissajous_device",
+    "sgz_vector_meters_from_filters", "sgz_vector_meters",
 ]
 
 
@@ -271,6 +277,12 @@ def lib() -> C.CDLL:
     L.sgz_vector_vertices.argtypes = [vp, u32, vp, vp, C.POINTER(u32)]
     L.sgz_vector_vertices_all.argtypes = [vp, vp, vp, C.POINTER(u32)]
     L.sgz_vector_history.argtypes = [vp, u32, vp, C.POINTER(u32), C.POINTER(u32)]
+    L.sgz_vector_lissajous_vertices.argtypes = [vp, u32, vp, vp, C.POINTER(u32)]
+    L.sgz_vector_lissajous_vertices_all.argtypes = [vp, vp, vp, C.POINTER(u32)]
+    L.sgz_vector_lissajous_vertices_device.argtypes = [vp, u32, vp, vp, C.POINTER(u32)]
+    L.sgz_vector_lissajous_device.argtypes = [vp, sz, u32, sz, u32, vp, vp, vp, vp]
+    L.sgz_vector_meters_from_filters.argtypes = [C.POINTER(VectorFilters), C.POINTER(VectorMeters)]
+    L.sgz_vector_meters.argtypes = [vp, C.POINTER(VectorMeters)]
     L.sgz_scope_num_points.argtypes = [C.POINTER(ScopeView)]
     L.sgz_scope_num_points.restype = sz
     L.sgz_scope_lanczos_device.argtypes = [C.POINTER(ScopeView), vp, sz, sz, u32, vp, vp]
@@ -292,6 +304,18 @@ def check(status: int) -> int:
 
 def _np_ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _buf_ptr(a):
+    """a numpy array's or a torch tensor's (host or device) data pointer"""
+    return C.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else _np_ptr(a)
+
+
+def vector_meters_from_filters(filters: VectorFilters) -> VectorMeters:
+    """drawStereoMeters' indicator positions from the filter states (sgz_vector_meters_from_filters; host arithmetic, no GPU)"""
+    m = VectorMeters()
+    check(lib().sgz_vector_meters_from_filters(C.byref(filters), C.byref(m)))
+    return m
 
 
 RT_OPT_STRICT_REFERENCE_QUIRKS, RT_OPT_AUDIO_HISTORY, RT_OPT_DEFER_SUBMIT, RT_OPT_PARK_PUSHES = 1, 2, 3, 4
@@ -765,3 +789,32 @@ class Vector:
         cnt = C.c_uint32(n)
         check(lib().sgz_vector_vertices(self.h, pair, _np_ptr(xyz), _np_ptr(rgb) if want_colours else None, C.byref(cnt)))
         return xyz, rgb
+
+    def lissajous(self, pair: int = 0, want_colours: bool = True):
+        """drawRectPlot's stream of one pair (sgz_vector_lissajous_vertices): xyz float32 [n][3], rgb float32 [n][3] or None"""
+        self.flush()
+        n = self.cfg.window_size
+        xyz = np.zeros((n, 3), np.float32)
+        rgb = np.zeros((n, 3), np.float32) if want_colours else None
+        cnt = C.c_uint32(n)
+        check(lib().sgz_vector_lissajous_vertices(self.h, pair, _np_ptr(xyz), _np_ptr(rgb) if want_colours else None, C.byref(cnt)))
+        return xyz, rgb
+
+    def lissajous_all(self, xyz=None, rgb=None):
+        """every pair's Lissajous stream with one wait (sgz_vector_lissajous_vertices_all).  xyz / rgb: [pairs][n][3] float32 buffers
+        the caller keeps -- numpy arrays or torch tensors, host (pinned or not) or device --; xyz None: fresh numpy arrays for both"""
+        self.flush()
+        n, pairs = self.cfg.window_size, self.cfg.num_channels // 2
+        if xyz is None:
+            xyz, rgb = np.empty((pairs, n, 3), np.float32), np.empty((pairs, n, 3), np.float32)
+        assert tuple(xyz.shape) == (pairs, n, 3) and (rgb is None or tuple(rgb.shape) == (pairs, n, 3))
+        cnt = C.c_uint32(n)
+        check(lib().sgz_vector_lissajous_vertices_all(self.h, _buf_ptr(xyz), _buf_ptr(rgb) if rgb is not None else None, C.byref(cnt)))
+        return xyz, rgb
+
+    def meters(self) -> VectorMeters:
+        """drawStereoMeters' indicator positions from the handle's filter states (sgz_vector_meters; waits)"""
+        self.flush()
+        m = VectorMeters()
+        check(lib().sgz_vector_meters(self.h, C.byref(m)))
+        return m

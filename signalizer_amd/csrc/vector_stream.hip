@@ -1,9 +1,10 @@
 // vector_stream.hip -- the Vectorscope's real-time handle (sgz_vector_*): audio history ring, the audio thread's one-pole
-// filters and the polar plot's vertex / colour stream, all resident in HBM.  gfx950 only.
+// filters and the polar and Lissajous plots' vertex / colour streams, all resident in HBM.  gfx950 only.
 //
 // Replaces VectorScope::Processor::onStreamAudio -> audioProcessing (Source/Vectorscope/Vectorscope.cpp:268-392) on the audio
 // thread -- plus the cpl::AudioStream history the renderer reads (a CLIFOStream per channel) -- and on the render thread
-// VectorScope::runPeakFilter (VectorscopeRendering.cpp:826-889) and drawPolarPlot (:500-746) for every channel pair.
+// VectorScope::runPeakFilter (VectorscopeRendering.cpp:826-889), drawPolarPlot (:500-746) or drawRectPlot (:444-497) for every
+// channel pair, and drawStereoMeters' indicator arithmetic (:748-823, host only).
 //
 // Layout: ring [channels][size], size = the audio history window in samples, one write cursor.  A render sees the ring as the
 // reference's AudioBufferView does: section 0 = memory [cursor, size), section 1 = [0, cursor) (getItIndex / getItRange).
@@ -315,6 +316,40 @@ __global__ void __launch_bounds__(256) vectorPolarViewKernel(const PolarParams p
     if (prm.rgb) prm.rgb[at] = prm.fade ? make_float3(col[0] * cf, col[1] * cf, col[2] * cf) : make_float3(col[0], col[1], col[2]);
 }
 
+// VectorScope::drawRectPlot (VectorscopeRendering.cpp:444-497), the Lissajous plot: vertex v = (right, left, v * sampleFade - 1),
+// sampleFade = 1 / max(1, n - 1) (:453); with fadeHistory the colour is colour * fade (:488), without it the strip's one colour (:459).
+// The lambda's sampleFrame is taken to run 0 .. n - 1 over the same two sections the polar plot reads (audio.iterate<2, true>: cpl's
+// AudioStream, not in the reference tree -- UNVERIFIED vs cpl).  fade is a product, not a running sum: no ramp tables.
+struct LissajousParams {
+    const VecDev *st;                                          // the handle's state (the cursor is read here), or null: cursor 0
+    const float *ring; size_t stride; uint32_t size;           // channel c at ring + c * stride, `size` samples each
+    float sampleFade; uint32_t fade;
+    float3 *xyz, *rgb; size_t pairStride;                      // pair firstPair + p's streams at xyz + p * pairStride (vertices)
+    float colour[32][3];                                       // [p]: subscript blockIdx.y only (uniform)
+    uint32_t firstPair;
+};
+// grid (vertices / 256, pairs of this call)
+__global__ void __launch_bounds__(256) vectorLissajousKernel(const LissajousParams prm)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;            // vertex index = sampleFrame (size <= 2^31)
+    const uint32_t size = prm.size;
+    if (v >= size) return;
+    const uint32_t cursor = prm.st ? prm.st->cursor : 0u;
+    const uint32_t older = size - cursor;                                 // section 0 = memory [cursor, size), then [0, cursor)
+    const size_t mem = v < older ? size_t(cursor) + v : size_t(v - older);
+    const uint32_t pair = prm.firstPair + blockIdx.y;
+    const float left = prm.ring[size_t(2 * pair) * prm.stride + mem];
+    const float right = prm.ring[size_t(2 * pair + 1) * prm.stride + mem];
+    const float fade = float(v) * prm.sampleFade;                         // size_t -> float rounds to nearest (:466, :487)
+    const size_t at = size_t(blockIdx.y) * prm.pairStride + v;
+    prm.xyz[at] = make_float3(right, left, fade - 1.0f);
+    if (!prm.rgb) return;
+    const float *col = prm.colour[blockIdx.y];
+    prm.rgb[at] = prm.fade ? make_float3(fade * col[0], fade * col[1], fade * col[2]) : make_float3(col[0], col[1], col[2]);
+}
+
+inline float lissajousSampleFade(size_t n) { return 1.0f / float(std::max<int>(1, int(n - 1))); }   // :453
+
 }  // namespace
 
 struct sgz_vector {
@@ -592,13 +627,34 @@ static sgz_status vectorVerticesInto(sgz_vector *s, uint32_t firstPair, uint32_t
     return SGZ_OK;
 }
 
-sgz_status sgz_vector_vertices(sgz_vector *s, uint32_t pair, float *xyz, float *rgb, uint32_t *count)
+// the kernels of `pairs` consecutive pairs' Lissajous streams (drawRectPlot) into DEVICE buffers, laid out as vectorVerticesInto's; no
+// ramp work and no ramp state touched: the polar reads around it find their tables as they left them
+static sgz_status vectorLissajousInto(sgz_vector *s, uint32_t firstPair, uint32_t pairs, float *d_xyz, float *d_rgb)
+{
+    if (sgz_status sy = vectorSync(s); sy != SGZ_OK) return sy;           // (flush on read: the blocks that wait in the open batch come first)
+    const uint32_t size = s->size;
+    LissajousParams prm{};
+    prm.st = s->d_state; prm.ring = s->d_ring; prm.stride = size; prm.size = size;
+    prm.sampleFade = lissajousSampleFade(size); prm.fade = s->cfg.fade_history ? 1u : 0u;
+    prm.xyz = reinterpret_cast<float3 *>(d_xyz); prm.rgb = reinterpret_cast<float3 *>(d_rgb); prm.pairStride = size;
+    for (uint32_t p = 0; p < pairs; ++p)
+        for (int k = 0; k < 3; ++k) prm.colour[p][k] = s->cfg.colours[firstPair + p][k];
+    prm.firstPair = firstPair;
+    hipLaunchKernelGGL(vectorLissajousKernel, dim3((size + 255) / 256, pairs), dim3(256), 0, s->stream, prm);
+    SGZ_HIP(hipGetLastError());
+    return SGZ_OK;
+}
+
+// The three buffer forms, shared by the polar and the Lissajous stream (`into` = vectorVerticesInto / vectorLissajousInto).
+using VerticesInto = sgz_status (*)(sgz_vector *, uint32_t, uint32_t, float *, float *);
+
+static sgz_status vectorReadPair(sgz_vector *s, VerticesInto into, uint32_t pair, float *xyz, float *rgb, uint32_t *count)
 {
     if (!s || !xyz || !count) return fail(SGZ_EINVAL, "null argument");
     if (pair >= s->cfg.num_channels / 2) return fail(SGZ_EINVAL, "pair out of range");
     const uint32_t size = s->size;
     if (*count < size) { *count = size; return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
-    const sgz_status st = vectorVerticesInto(s, pair, 1, s->d_xyz, rgb ? s->d_rgb : nullptr);
+    const sgz_status st = into(s, pair, 1, s->d_xyz, rgb ? s->d_rgb : nullptr);
     if (st != SGZ_OK) return st;
     const size_t bytes = size_t(size) * 3 * sizeof(float);
     if (sgz_status rb = readBack(xyz, s->d_xyz, bytes, rgb, s->d_rgb, bytes, s->h_out, s->stream); rb != SGZ_OK) return rb;
@@ -606,38 +662,114 @@ sgz_status sgz_vector_vertices(sgz_vector *s, uint32_t pair, float *xyz, float *
     return SGZ_OK;
 }
 
-sgz_status sgz_vector_vertices_all(sgz_vector *s, float *xyz, float *rgb, uint32_t *count)
+static sgz_status vectorReadAll(sgz_vector *s, VerticesInto into, float *xyz, float *rgb, uint32_t *count)
 {
     if (!s || !xyz || !count) return fail(SGZ_EINVAL, "null argument");
     const uint32_t size = s->size, pairs = s->cfg.num_channels / 2;
     if (*count < size) { *count = size; return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size per pair)"); }
     const size_t per = size_t(size) * 3;
-    // pinned, device-mapped destinations: the polar kernels write them themselves (no staging, no DMA copy behind the kernels)
+    // pinned, device-mapped destinations: the vertex kernels write them themselves (no staging, no DMA copy behind the kernels)
     float *mx = static_cast<float *>(mappedDevicePointer(xyz, s->stream)), *mc = rgb ? static_cast<float *>(mappedDevicePointer(rgb, s->stream)) : nullptr;
     if (mx && (!rgb || mc)) {
-        const sgz_status st = vectorVerticesInto(s, 0, pairs, mx, rgb ? mc : nullptr);       // every pair in one launch
+        const sgz_status st = into(s, 0, pairs, mx, rgb ? mc : nullptr);       // every pair in one launch
         if (st != SGZ_OK) return st;
         SGZ_HIP(hipStreamSynchronize(s->stream));
         *count = size;
         return SGZ_OK;
     }
-    if (const sgz_status st = vectorVerticesInto(s, 0, pairs, s->d_xyz, rgb ? s->d_rgb : nullptr); st != SGZ_OK) return st;
+    if (const sgz_status st = into(s, 0, pairs, s->d_xyz, rgb ? s->d_rgb : nullptr); st != SGZ_OK) return st;
     const size_t bytes = pairs * per * sizeof(float);
     if (sgz_status rb = readBack(xyz, s->d_xyz, bytes, rgb, s->d_rgb, bytes, s->h_out, s->stream); rb != SGZ_OK) return rb;
     *count = size;
     return SGZ_OK;
 }
 
-sgz_status sgz_vector_vertices_device(sgz_vector *s, uint32_t pair, float *d_xyz, float *d_rgb, uint32_t *count)
+static sgz_status vectorReadDevice(sgz_vector *s, VerticesInto into, uint32_t pair, float *d_xyz, float *d_rgb, uint32_t *count)
 {
     if (!s || !d_xyz || !count) return fail(SGZ_EINVAL, "null argument");
     if (pair >= s->cfg.num_channels / 2) return fail(SGZ_EINVAL, "pair out of range");
     if (*count < s->size) { *count = s->size; return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
-    const sgz_status st = vectorVerticesInto(s, pair, 1, d_xyz, d_rgb);
+    const sgz_status st = into(s, pair, 1, d_xyz, d_rgb);
     if (st != SGZ_OK) return st;
     SGZ_HIP(hipStreamSynchronize(s->stream));                 // the vertices are in place when the call returns
     *count = s->size;
     return SGZ_OK;
+}
+
+sgz_status sgz_vector_vertices(sgz_vector *s, uint32_t pair, float *xyz, float *rgb, uint32_t *count)
+{
+    return vectorReadPair(s, vectorVerticesInto, pair, xyz, rgb, count);
+}
+
+sgz_status sgz_vector_vertices_all(sgz_vector *s, float *xyz, float *rgb, uint32_t *count)
+{
+    return vectorReadAll(s, vectorVerticesInto, xyz, rgb, count);
+}
+
+sgz_status sgz_vector_vertices_device(sgz_vector *s, uint32_t pair, float *d_xyz, float *d_rgb, uint32_t *count)
+{
+    return vectorReadDevice(s, vectorVerticesInto, pair, d_xyz, d_rgb, count);
+}
+
+sgz_status sgz_vector_lissajous_vertices(sgz_vector *s, uint32_t pair, float *xyz, float *rgb, uint32_t *count)
+{
+    return vectorReadPair(s, vectorLissajousInto, pair, xyz, rgb, count);
+}
+
+sgz_status sgz_vector_lissajous_vertices_all(sgz_vector *s, float *xyz, float *rgb, uint32_t *count)
+{
+    return vectorReadAll(s, vectorLissajousInto, xyz, rgb, count);
+}
+
+sgz_status sgz_vector_lissajous_vertices_device(sgz_vector *s, uint32_t pair, float *d_xyz, float *d_rgb, uint32_t *count)
+{
+    return vectorReadDevice(s, vectorLissajousInto, pair, d_xyz, d_rgb, count);
+}
+
+sgz_status sgz_vector_lissajous_device(const float *d_planar, size_t stride, uint32_t pairs, size_t n, uint32_t fade,
+                                       const float *colours, float *d_xyz, float *d_rgb, void *stream)
+{
+    if (!d_planar || !d_xyz || pairs == 0 || (d_rgb && !colours)) return fail(SGZ_EINVAL, "bad argument");
+    if (n == 0) return SGZ_OK;
+    if (n > (size_t(1) << 31) || stride < n) return fail(SGZ_EINVAL, "n above 2^31 or stride below n");
+    hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+    LissajousParams prm{};
+    prm.st = nullptr; prm.ring = d_planar; prm.stride = stride; prm.size = uint32_t(n);
+    prm.sampleFade = lissajousSampleFade(n); prm.fade = fade ? 1u : 0u;
+    prm.pairStride = n;
+    for (uint32_t first = 0; first < pairs; first += 32) {                 // (32 pairs' colours per launch: the parameter struct's table)
+        const uint32_t count = std::min<uint32_t>(32, pairs - first);
+        prm.firstPair = first;
+        prm.xyz = reinterpret_cast<float3 *>(d_xyz + size_t(first) * n * 3);
+        prm.rgb = d_rgb ? reinterpret_cast<float3 *>(d_rgb + size_t(first) * n * 3) : nullptr;
+        for (uint32_t p = 0; p < count; ++p)
+            for (int k = 0; k < 3; ++k) prm.colour[p][k] = d_rgb ? colours[size_t(first + p) * 3 + k] : 0.f;
+        hipLaunchKernelGGL(vectorLissajousKernel, dim3(unsigned((n + 255) / 256), count), dim3(256), 0, hs, prm);
+        SGZ_HIP(hipGetLastError());
+    }
+    return SGZ_OK;
+}
+
+// drawStereoMeters (VectorscopeRendering.cpp:766-776): host arithmetic on the filter states, by filter index (see sgz.h)
+sgz_status sgz_vector_meters_from_filters(const sgz_vector_filters *f, struct sgz_vector_meters *out)
+{
+    if (!f || !out) return fail(SGZ_EINVAL, "null argument");
+    const float pi = 3.14159265358979323846f;                  // simd::consts<float>::pi
+    for (int k = 0; k < 2; ++k) {
+        float balance = std::atan(f->balance[k][1] / f->balance[k][0]) / (pi * 0.5f);   // :768, :771 (remember, y / x)
+        if (!std::isnormal(balance)) balance = 0.5f;                                   // :769-770, :772-773
+        out->balance[k] = balance;
+        out->stereo[k] = f->phase[k] * 0.5f + 0.5f;                                    // :775-776
+    }
+    return SGZ_OK;
+}
+
+sgz_status sgz_vector_meters(sgz_vector *s, struct sgz_vector_meters *out)
+{
+    if (!s || !out) return fail(SGZ_EINVAL, "null argument");
+    sgz_vector_filters f;
+    if (sgz_status st = sgz_vector_filters_get(s, &f, nullptr); st != SGZ_OK) return st;
+    return sgz_vector_meters_from_filters(&f, out);
 }
 
 }  // extern "C"
