@@ -509,6 +509,63 @@ sgz_status sgz_spectrum_track_peak_lines(sgz_spectrum *s, uint32_t pair, uint32_
 sgz_status sgz_spectrum_history(sgz_spectrum *s, uint32_t channel, float *out /*W*/);
 
 /* ------------------------------------------------------------------------------------------------
+ * The line graph's vertex stream: Spectrum::renderTransformAsGraph (SpectrumRendering.cpp:794-897), what its PrimitiveDrawers receive
+ * for every pair, built on the device from the line results (float2 [pairs][SGZ_NUM_GRAPHS][P], .first = left / magnitude, .second =
+ * right / phase, exactly what sgz_spectrum_render_lines returns).  S = 2 sides for SGZ_CH_SEPARATE, SGZ_CH_MIDSIDE and SGZ_CH_PHASE (the
+ * fall-throughs at :831, :877), 1 for the other modes.  Per pair p in ascending order (one renderTransformAsGraph call each, :639-652):
+ *   1. flood fill, when alphaFloodFill != 0 (:807): for k = 1, 0, then side = right (S == 2 only), then left: 2P vertices, GL_LINES,
+ *      (i, y, z), (i, endPoint, z) for i = 0 .. P-1
+ *   2. strips: for k = 1, 0, then right (S == 2 only), then left: P vertices, GL_LINE_STRIP, (i, y, z)
+ * y = results[p][k][i].second on the right side (z = -0.5), .first on the left side (z = 0): the stored float as it is (NaN, inf, -0 bit
+ * for bit; in Phase mode the right side is the phase, drawn anyway as the reference does).  x = (float) i.  endPoint = (dbs.high > dbs.low
+ * ? 0 : 1) is always 0: the plan refuses high_db <= low_db and getDBs() only widens the range.  Vertices per pair:
+ * SGZ_NUM_GRAPHS * S * P * (flood ? 3 : 1); float3 packed, 12 bytes a vertex, pair p's at p * that.
+ * GL state is the host's, per draw: the model matrix translate(-1, -1, 0) then scale(1 / ((P - 1) * 0.5), 2, 1) (:801-802) -- it is not
+ * applied to the vertices: x_clip = model[0] x + model[2], y_clip = model[1] y + model[3] --; fills blend SRC_ALPHA, ONE_MINUS_SRC_ALPHA
+ * with multisampling off, strips blend ONE, ONE_MINUS_SRC_COLOR with multisampling as state.antialias.
+ */
+#define SGZ_PRIM_LINES      0x0001u   /* GL_LINES      (the flood fill) */
+#define SGZ_PRIM_LINE_STRIP 0x0003u   /* GL_LINE_STRIP (the graph)      */
+#define SGZ_SIDE_LEFT  0u             /* results .first,  z = 0    */
+#define SGZ_SIDE_RIGHT 1u             /* results .second, z = -0.5 */
+/* Colours are RGBA8, the bytes juce::Colour holds: colour_one[k] / colour_two[k] = content->lines[k].colourOne / colourTwo.  Pair p draws
+ * ColourRotation(colour, pairs, false)[p] (Spectrum.cpp:384-385, :646) = withRotatedHue((float) p / (float) pairs), alpha kept (the RGB part
+ * is sgz_rotate_hue_rgb8); a fill draws it withAlpha(flood_alpha): alpha byte = a <= 0 ? 0 : a >= 1 ? 255 : (uint8_t) (a * 255.996f)
+ * (juce_Colour.cpp:27-30).  Line widths: fills rendering_scale (:797), strips max(0.001f, (float) (rendering_scale * primitive_size)) (:852). */
+typedef struct sgz_line_graph_style {
+    uint8_t colour_one[SGZ_NUM_GRAPHS][4];   /* left side (and the only side of a one-sided mode) */
+    uint8_t colour_two[SGZ_NUM_GRAPHS][4];   /* right side                                        */
+    float   flood_alpha;                     /* state.alphaFloodFill: 0 = no flood fill            */
+    float   primitive_size;                  /* state.primitiveSize                               */
+    double  rendering_scale;                 /* oglc->getRenderingScale()                         */
+} sgz_line_graph_style;
+typedef struct sgz_line_graph_draw {
+    uint32_t first, count;      /* vertices [first, first + count) of the stream      */
+    uint32_t primitive;         /* SGZ_PRIM_LINES (fill) / SGZ_PRIM_LINE_STRIP (graph) */
+    uint32_t pair, graph, side; /* side: SGZ_SIDE_*                                    */
+    uint8_t  rgba[4];
+    float    line_width;
+} sgz_line_graph_draw;
+/* the stream's length for `pairs` pairs (0 for an unknown channel mode); host only */
+size_t     sgz_line_graph_vertex_count(uint32_t channel_mode, uint32_t pairs, uint32_t axis_points, uint32_t flood);
+/* The draw list in the order above (host only, no GPU): flood = style->flood_alpha != 0.  *count: capacity in records on entry, records
+ * written on return; too small (or out NULL) -> SGZ_EINVAL with *count = the size needed.  model (or NULL): the four coefficients. */
+sgz_status sgz_line_graph_draws(const sgz_line_graph_style *style, uint32_t channel_mode, uint32_t pairs, uint32_t axis_points,
+                                sgz_line_graph_draw *out, uint32_t *count, float model[4]);
+/* Stage call, stateless: d_lines DEVICE float2 [pairs][SGZ_NUM_GRAPHS][axis_points] -> d_xyz DEVICE float3 [sgz_line_graph_vertex_count].
+ * One launch; asynchronous on `stream`.  axis_points <= 2^24. */
+sgz_status sgz_line_graph_vertices_device(const float *d_lines, uint32_t pairs, uint32_t axis_points, uint32_t channel_mode,
+                                          uint32_t flood, float *d_xyz, void *stream);
+/* The handle's line graph straight into a vertex buffer: exactly sgz_spectrum_render_lines (the newest window -- RSNT: the resonator state --,
+ * both filters advanced ONCE with this call's poles), then the vertex kernel on the same stream, then one wait.  xyz: pageable host,
+ * pinned host or DEVICE memory (a mapped VBO) -- device memory and pinned, device-mapped host memory are written by the kernel itself,
+ * anything else through a staging buffer the first such call allocates.  *count: capacity in vertices on entry, vertices written on return;
+ * too small -> SGZ_EINVAL with *count = the size needed, nothing written and the filters untouched.  Afterwards sgz_spectrum_line_results and
+ * sgz_spectrum_track_peak_lines see this call's results.  SGZ_EINVAL on a COLOUR_SPECTRUM handle; never delays push. */
+sgz_status sgz_spectrum_render_line_vertices(sgz_spectrum *s, const float *poles /*[SGZ_NUM_GRAPHS] or NULL*/, uint32_t flood, float *xyz,
+                                             uint32_t *count);
+
+/* ------------------------------------------------------------------------------------------------
  * Oscilloscope: Lanczos-10 per-point resampler (drawWavePlot, OscilloscopeRendering.cpp:790-891),
  * zero-crossing trigger (ZeroCrossingProcessor::process, StreamPreprocessing.h:315-349) and the peak
  * envelope (runPeakFilter, OscilloscopeDSP.inl:713-886).

@@ -93,6 +93,23 @@ class VectorMeters(C.Structure):
     _fields_ = [("balance", C.c_float * 2), ("stereo", C.c_float * 2)]
 
 
+class LineGraphStyle(C.Structure):
+    _fields_ = [("colour_one", (C.c_uint8 * 4) * NUM_GRAPHS), ("colour_two", (C.c_uint8 * 4) * NUM_GRAPHS), ("flood_alpha", C.c_float),
+                ("primitive_size", C.c_float), ("rendering_scale", C.c_double)]
+
+
+class LineGraphDraw(C.Structure):
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("primitive", C.c_uint32), ("pair", C.c_uint32), ("graph", C.c_uint32),
+                ("side", C.c_uint32), ("rgba", C.c_uint8 * 4), ("line_width", C.c_float)]
+
+
+# sgz_line_graph_draw as a numpy record (line_graph_draws' result)
+LINE_GRAPH_DRAW_DTYPE = np.dtype([("first", np.uint32), ("count", np.uint32), ("primitive", np.uint32), ("pair", np.uint32),
+                                  ("graph", np.uint32), ("side", np.uint32), ("rgba", np.uint8, (4,)), ("line_width", np.float32)])
+PRIM_LINES, PRIM_LINE_STRIP = 0x0001, 0x0003
+SIDE_LEFT, SIDE_RIGHT = 0, 1
+
+
 class VectorConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_double), ("num_channels", C.c_uint32), ("window_size", C.c_uint32), ("envelope_mode", C.c_uint32),
                 ("lanes", C.c_uint32), ("fade_history", C.c_uint32), ("max_block", C.c_uint32), ("envelope_window", C.c_double),
@@ -144,6 +161,7 @@ EXPORTS = [
     "sgz_peak_filter_device", "sgz_vector_polar_device", "sgz_vector_audio_processing_device",
     "sgz_vector_lissajous_vertices", "sgz_vector_lissajous_vertices_all", "sgz_vector_lissajous_vertices_device", "sgz_vector_lissajous_device",
     "sgz_vector_meters_from_filters", "sgz_vector_meters",
+    "sgz_line_graph_vertex_count", "sgz_line_graph_draws", "sgz_line_graph_vertices_device", "sgz_spectrum_render_line_vertices",
 ]
 
 
@@ -283,6 +301,11 @@ def lib() -> C.CDLL:
     L.sgz_vector_lissajous_device.argtypes = [vp, sz, u32, sz, u32, vp, vp, vp, vp]
     L.sgz_vector_meters_from_filters.argtypes = [C.POINTER(VectorFilters), C.POINTER(VectorMeters)]
     L.sgz_vector_meters.argtypes = [vp, C.POINTER(VectorMeters)]
+    L.sgz_line_graph_vertex_count.argtypes = [u32, u32, u32, u32]
+    L.sgz_line_graph_vertex_count.restype = sz
+    L.sgz_line_graph_draws.argtypes = [C.POINTER(LineGraphStyle), u32, u32, u32, vp, C.POINTER(u32), vp]
+    L.sgz_line_graph_vertices_device.argtypes = [vp, u32, u32, u32, u32, vp, vp]
+    L.sgz_spectrum_render_line_vertices.argtypes = [vp, vp, u32, vp, C.POINTER(u32)]
     L.sgz_scope_num_points.argtypes = [C.POINTER(ScopeView)]
     L.sgz_scope_num_points.restype = sz
     L.sgz_scope_lanczos_device.argtypes = [C.POINTER(ScopeView), vp, sz, sz, u32, vp, vp]
@@ -316,6 +339,50 @@ def vector_meters_from_filters(filters: VectorFilters) -> VectorMeters:
     m = VectorMeters()
     check(lib().sgz_vector_meters_from_filters(C.byref(filters), C.byref(m)))
     return m
+
+
+def line_graph_style(colour_one, colour_two, flood_alpha: float, primitive_size: float = 1.0, rendering_scale: float = 1.0) -> LineGraphStyle:
+    """sgz_line_graph_style from RGBA8 colours per graph (colour_one / colour_two: [SGZ_NUM_GRAPHS][4])"""
+    st = LineGraphStyle()
+    for k in range(NUM_GRAPHS):
+        for j in range(4):
+            st.colour_one[k][j] = int(colour_one[k][j])
+            st.colour_two[k][j] = int(colour_two[k][j])
+    st.flood_alpha, st.primitive_size, st.rendering_scale = flood_alpha, primitive_size, rendering_scale
+    return st
+
+
+def line_graph_vertex_count(channel_mode: int, pairs: int, axis_points: int, flood: bool) -> int:
+    """renderTransformAsGraph's vertex count for `pairs` pairs (sgz_line_graph_vertex_count; host only)"""
+    return int(lib().sgz_line_graph_vertex_count(channel_mode, pairs, axis_points, int(bool(flood))))
+
+
+def line_graph_draws(style: LineGraphStyle, channel_mode: int, pairs: int, axis_points: int):
+    """renderTransformAsGraph's draw list (sgz_line_graph_draws; host only): (records as a LINE_GRAPH_DRAW_DTYPE array, model float32 [4])"""
+    cnt = C.c_uint32(0)
+    st = lib().sgz_line_graph_draws(C.byref(style), channel_mode, pairs, axis_points, None, C.byref(cnt), None)
+    if st != SGZ_EINVAL or cnt.value == 0:                     # (the size query: a refusal that reports the count)
+        check(st)
+    out = np.zeros(cnt.value, LINE_GRAPH_DRAW_DTYPE)
+    model = np.zeros(4, np.float32)
+    check(lib().sgz_line_graph_draws(C.byref(style), channel_mode, pairs, axis_points, _np_ptr(out), C.byref(cnt), _np_ptr(model)))
+    return out[:cnt.value], model
+
+
+def spectrum_render_line_vertices(handle, poles, flood: bool, out):
+    """sgz_spectrum_render_line_vertices on a LINE_GRAPH spectrum handle: render_lines' work, then the vertex stream into `out` -- float32
+    [vertices][3] (or any shape of that size), a numpy array or a torch tensor, host (pinned or not) or device.  poles: [SGZ_NUM_GRAPHS]
+    or None.  Returns the vertex count."""
+    if hasattr(out, "numel"):
+        assert str(out.dtype) == "torch.float32" and out.is_contiguous()
+        n = out.numel() // 3
+    else:
+        assert out.dtype == np.float32 and out.flags.c_contiguous
+        n = out.size // 3
+    cnt = C.c_uint32(n)
+    pl = (C.c_float * NUM_GRAPHS)(*poles) if poles is not None else None
+    check(lib().sgz_spectrum_render_line_vertices(handle, pl, int(bool(flood)), _buf_ptr(out), C.byref(cnt)))
+    return cnt.value
 
 
 RT_OPT_STRICT_REFERENCE_QUIRKS, RT_OPT_AUDIO_HISTORY, RT_OPT_DEFER_SUBMIT, RT_OPT_PARK_PUSHES = 1, 2, 3, 4

@@ -28,6 +28,8 @@
 // (`trackPlan`: per-launch scratch is per Plan) and reads the ring without a lock: the producer publishes how far it is ABOUT to
 // write before it enqueues an ingest kernel, the consumer checks that figure after it has enqueued its transform, and repeats the
 // (idempotent) transform in the one-in-a-million case where its window could have been overtaken.
+// sgz_spectrum_render_line_vertices does the same and then writes renderTransformAsGraph's vertex stream from the results
+// (line_graph.hip) into the caller's buffer on the same stream.
 //
 // Threading: one producer thread (push) and one consumer thread (pop_column / line_results / configure / clear_state).
 // push never waits for the GPU: staging slots and column slots are checked with hipEventQuery / atomics, allocations and LDS
@@ -125,6 +127,10 @@ struct sgz_spectrum {
     // line graph (consumer thread): K_A's output for the ring's newest window, the results on the host
     float *d_lineMapped = nullptr;    // [C][sides][P]
     float *h_lineOut = nullptr;       // pinned [C][graphs][P][2]
+    // the line graph's vertex stream for destinations its kernel cannot write (sgz_spectrum_render_line_vertices: pageable memory, another
+    // device's): grown by the first such call, kept across configure
+    float *d_verts = nullptr; size_t vertsCap = 0;      // device [vertices][3] floats
+    float *h_verts = nullptr; size_t hVertsCap = 0;     // pinned bounce buffer, floats
     // colour spectrum: lineGraphs[k].results of the newest frame, copied to the host behind every batch (triple buffer, seqlock)
     static constexpr int kLineSlots = 3;
     float *h_lines = nullptr;         // pinned [kLineSlots][C][graphs][P][2]
@@ -170,6 +176,8 @@ static void freeHandle(sgz_spectrum *s)
     for (float *p : {s->d_ring, s->d_mapped, s->d_state, s->d_lines, s->d_linesBatch, s->d_trackBins, s->d_strict, s->d_lineMapped}) if (p) (void)hipFree(p);
     if (s->h_lineOut) (void)hipHostFree(s->h_lineOut);
     if (s->h_lines) (void)hipHostFree(s->h_lines);
+    if (s->d_verts) (void)hipFree(s->d_verts);
+    if (s->h_verts) (void)hipHostFree(s->h_verts);
     for (auto &e : s->lineEvents) if (e) (void)hipEventDestroy(e);
     if (s->d_peak) (void)hipFree(s->d_peak);
     unbindImage(s);
@@ -655,13 +663,11 @@ sgz_status sgz_spectrum_line_results(sgz_spectrum *s, uint32_t pair, uint32_t gr
     return SGZ_OK;
 }
 
-sgz_status sgz_spectrum_render_lines(sgz_spectrum *s, const float *poles, float *out)
+// sgz_spectrum_render_lines' device work: the newest window's transform (RSNT: the resonators' windowed state) and both filters advanced
+// once with this call's poles, into d_lines -- enqueued on the handle's stream, not waited for
+static sgz_status renderLinesOnDevice(sgz_spectrum *s, const float *poles)
 {
-    if (!s || !out) return fail(SGZ_EINVAL, "null argument");
     Plan &p = *s->trackPlan;                                  // the consumer's plan (per-launch scratch is per plan)
-    TraceRange range("sgz::spectrum render_lines");
-    if (p.cfg.display_mode != SGZ_DISPLAY_LINE_GRAPH) return fail(SGZ_EINVAL, "sgz_spectrum_render_lines: the handle is configured for SGZ_DISPLAY_COLOUR_SPECTRUM");
-    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
     const float *mapped = s->d_lineMapped;
     sgz_status st = SGZ_OK;
     if (isResonator(p)) {
@@ -678,10 +684,55 @@ sgz_status sgz_spectrum_render_lines(sgz_spectrum *s, const float *poles, float 
         for (int k = 0; k < SGZ_NUM_GRAPHS; ++k) { p.scalars.pole[k] = poles[k]; p.scalars.phasePole[k] = std::pow(poles[k], 0.3f); }
     st = runDecayColour(p, mapped, 1, nullptr, s->d_lines, s->d_state, s->stream);
     p.scalars = keep;
-    if (st != SGZ_OK) return st;
+    return st;
+}
+
+sgz_status sgz_spectrum_render_lines(sgz_spectrum *s, const float *poles, float *out)
+{
+    if (!s || !out) return fail(SGZ_EINVAL, "null argument");
+    Plan &p = *s->trackPlan;
+    TraceRange range("sgz::spectrum render_lines");
+    if (p.cfg.display_mode != SGZ_DISPLAY_LINE_GRAPH) return fail(SGZ_EINVAL, "sgz_spectrum_render_lines: the handle is configured for SGZ_DISPLAY_COLOUR_SPECTRUM");
+    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
+    if (sgz_status st = renderLinesOnDevice(s, poles); st != SGZ_OK) return st;
     SGZ_HIP(hipMemcpyAsync(s->h_lineOut, s->d_lines, stateN * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     SGZ_HIP(hipStreamSynchronize(s->stream));
     std::memcpy(out, s->h_lineOut, stateN * sizeof(float));
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrum_render_line_vertices(sgz_spectrum *s, const float *poles, uint32_t flood, float *xyz, uint32_t *count)
+{
+    if (!s || !xyz || !count) return fail(SGZ_EINVAL, "null argument");
+    Plan &p = *s->trackPlan;
+    TraceRange range("sgz::spectrum render_line_vertices");
+    if (p.cfg.display_mode != SGZ_DISPLAY_LINE_GRAPH) return fail(SGZ_EINVAL, "sgz_spectrum_render_line_vertices: the handle is configured for SGZ_DISPLAY_COLOUR_SPECTRUM");
+    const size_t verts = sgz_line_graph_vertex_count(p.cfg.channel_mode, p.C, p.P, flood);
+    if (verts > 0xffffffffu) return fail(SGZ_EINVAL, "line graph: more than 2^32 vertices");
+    if (*count < verts) { *count = uint32_t(verts); return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
+    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2, vfloats = verts * 3;
+    // device memory, and pinned host memory mapped into the device's address space: the vertex kernel writes it itself (rt_common.hpp)
+    float *direct = static_cast<float *>(mappedDevicePointer(xyz, s->stream));
+    if (!direct) {                                            // (staging first: a failed allocation leaves the filters where they were)
+        if (sgz_status st = ensureCap(&s->d_verts, &s->vertsCap, vfloats); st != SGZ_OK) return st;
+        if (!isCopyTarget(xyz) && s->hVertsCap < vfloats) {
+            if (s->h_verts) { (void)hipHostFree(s->h_verts); s->h_verts = nullptr; s->hVertsCap = 0; }
+            SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_verts), vfloats * sizeof(float), hipHostMallocDefault));
+            s->hVertsCap = vfloats;
+        }
+    }
+    if (sgz_status st = renderLinesOnDevice(s, poles); st != SGZ_OK) return st;
+    if (sgz_status st = launchLineGraphVertices(s->d_lines, p.C, p.P, p.cfg.channel_mode, flood, direct ? direct : s->d_verts, s->stream); st != SGZ_OK)
+        return st;
+    // h_lineOut stays the last render's results (sgz_spectrum_line_results, track_peak_lines): the small copy rides along
+    if (direct) {
+        SGZ_HIP(hipMemcpyAsync(s->h_lineOut, s->d_lines, stateN * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        SGZ_HIP(hipStreamSynchronize(s->stream));
+    } else if (sgz_status rb = readBack(xyz, s->d_verts, vfloats * sizeof(float), s->h_lineOut, s->d_lines, stateN * sizeof(float), s->h_verts, s->stream);
+               rb != SGZ_OK) {
+        return rb;
+    }
+    *count = uint32_t(verts);
     return SGZ_OK;
 }
 

@@ -19,6 +19,9 @@ sgz_status hipFail(hipError_t e, const char *what);
 
 constexpr size_t kExportGranule = size_t(2) << 20;      // allocations that are exported as dma-buf fds: whole 2 MiB blocks (sgz_export_alloc)
 sgz_status ensureCap(float **buf, size_t *cap, size_t need);
+// line_graph.hip: the line graph's vertex kernel (sgz_line_graph_vertices_device; the spectrum handle's render_line_vertices)
+sgz_status launchLineGraphVertices(const float *d_lines, uint32_t pairs, uint32_t P, uint32_t mode, uint32_t flood, float *d_xyz,
+                                   hipStream_t stream);
 int numCUs();
 // K_A over `frames` frames (ideal STFT framing from d_planar); any of mapped/binsOut may be null
 // deferLate: the caller's next call is runDecayColour on the same d_mapped with only an image wanted -- a channel-split launch may then
