@@ -421,7 +421,7 @@ void       sgz_peer_transport_release(void *ctx_storage);
  * frameQueue.popElement (SpectrumRendering.cpp:696-721) -- plus the two steps before the path: the additive
  * channel routing of MixGraphListener::deliver (Source/Common/MixGraphListener.cpp:247-334, sgz_spectrum_set_mix) and the audio
  * history ring, which lives in HBM (mirrored: the transform reads its window in place).  One producer thread (push) and one
- * consumer thread (pop_column, line_results, configure, set_mix, clear_state) may run concurrently.  push never waits for the GPU
+ * consumer thread (pop_column, line_results, configure, set_view, set_mix, clear_state) may run concurrently.  push never waits for the GPU
  * and allocates nothing: when the GPU is several blocks behind, or a configure is in progress, it returns SGZ_BUSY and the block
  * is not taken.  At most 131072 samples per push.
  */
@@ -449,11 +449,42 @@ sgz_status sgz_spectrum_pop_column(sgz_spectrum *s, uint8_t *rgba /*4*P*/, uint3
  *                               EGL surfaceless context can be made current; on the MI355X boxes this library is developed on it cannot (no
  *                               display engine; the image has libGL / GLX, which needs an X server, but neither libEGL nor libgbm) and the
  *                               test skips with the loader's error: there the call is only known to fail with a status
- * A configure drops the binding (the image height is the axis size). */
+ * A configure drops the binding (the image height is the axis size); sgz_spectrum_set_view keeps it. */
 sgz_status sgz_spectrum_bind_image(sgz_spectrum *s, void *d_image, uint32_t columns, size_t pitch_bytes);
 sgz_status sgz_spectrum_create_image(sgz_spectrum *s, uint32_t columns, void **d_image, size_t *pitch_bytes, int *dmabuf_fd);
 sgz_status sgz_spectrum_bind_gl_buffer(sgz_spectrum *s, unsigned int gl_buffer, uint32_t columns, size_t pitch_bytes);
 sgz_status sgz_spectrum_flush_columns(sgz_spectrum *s, uint32_t *first_column, uint32_t *count);
+/* Zoom / pan (consumer thread): Spectrum::handleFlagUpdates' viewChanged branch (Spectrum.cpp:532-575) for a change of viewLeft /
+ * viewRight only -- what mouseWheelMove / mouseDrag (:172-290) cause.  The view is checked as sgz_spectrum_configure checks it (finite,
+ * 0 <= left < right <= 1); SGZ_EINVAL leaves the handle exactly as it was.  Every other field stays as configured (a change of scaling,
+ * min_log_freq, size or mode is a sgz_spectrum_configure).
+ *   kept:     the audio history in HBM and the frame cadence (a frame fires where it would have; strict-quirks framing included), the mix
+ *             matrix, the handle options, the column queue, the image binding and framePixelPosition
+ *   replaced: remapFrequencies and what hangs on it (map tables, slope map, tracker tables, resonator tuning), built before push is held
+ *             off: push returns SGZ_BUSY only while the new tables are swapped in and warmed up
+ *   zeroed:   pair.clearLineGraphStates() (TransformPair.h:169-175): both graphs' decay states and results -- sgz_spectrum_line_results
+ *             reads zeros until a frame computed after this call arrives.  RSNT: the resonators restart at rest under their new tuning
+ *             (UNVERIFIED vs cpl: cpl's mapSystemHz is not in the tree)
+ *   COLOUR_SPECTRUM with an image bound and a rect that changed: oglImage.freeLinearVerticalTranslation(oldViewRect, viewRect)
+ *             (:560-561) on the bound image (sgz_view_translate_device's rule), waited for before the call returns.  Columns still in
+ *             the queue keep the mapping they were computed with and land untranslated at the next flush_columns.
+ * Waits for the GPU: not for the audio thread. */
+sgz_status sgz_spectrum_set_view(sgz_spectrum *s, double view_left, double view_right);
+/* freeLinearVerticalTranslation of a spectrogram image (UNVERIFIED vs cpl: cpl's resampling is not in the tree; this is the library's
+ * rule).  Image row i is axis point i, at view fraction left + (right - left) * i / (P - 1) in every scaling and channel mode, so the
+ * old image is resampled along rows.  In fp64, S0 = old_right - old_left, S1 = new_right - new_left, for every new row i:
+ *     u = new_left + S1 * (i / (P - 1.0));  r = (u - old_left) / S0 * (P - 1.0)
+ *     r outside [-0.5, P - 0.5]: src[i] = -1 (no source: texel 0x00000000, what sgz_spectrum_create_image holds)
+ *     else r = clamp(r, 0, P - 1); j = floor(r); w = floor((r - j) * 256 + 0.5); w == 256 -> j += 1, w = 0;  src[i] = j, weight[i] = w
+ *     every byte c of texel (x, i) = (a_c * (256 - w) + b_c * w + 128) >> 8 with a = old (x, j), b = old (x, min(j + 1, P - 1))
+ * (w = 0 copies the row).  Every column of the image is translated; texels beyond `columns` in a wider pitch are not touched.
+ * sgz_view_translation_rows: the table (host only, no GPU); SGZ_EINVAL for P < 2 or an invalid view.
+ * sgz_view_translate_device: the stage call, stateless: d_image DEVICE [P][pitch_bytes], translated in place; allocates its scratch,
+ * and waits for the result on `stream` before it returns.  P <= 2^20. */
+sgz_status sgz_view_translation_rows(uint32_t axis_points, double old_left, double old_right, double new_left, double new_right,
+                                     int32_t *src /*[P]*/, uint16_t *weight /*[P]*/);
+sgz_status sgz_view_translate_device(void *d_image, uint32_t columns, size_t pitch_bytes, uint32_t axis_points, double old_left,
+                                     double old_right, double new_left, double new_right, void *stream);
 /* lineGraphs[graph].getResults(P) for pair `pair`: float2 [P] (TransformPair.h:72-76).  COLOUR_SPECTRUM: the results of the newest
  * frame whose copy has reached the host (a pinned triple buffer the producer's stream fills: this call waits for nothing and never
  * touches the producer's stream); LINE_GRAPH: the results of the last sgz_spectrum_render_lines. */

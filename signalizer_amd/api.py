@@ -162,6 +162,7 @@ EXPORTS = [
     "sgz_vector_lissajous_vertices", "sgz_vector_lissajous_vertices_all", "sgz_vector_lissajous_vertices_device", "sgz_vector_lissajous_device",
     "sgz_vector_meters_from_filters", "sgz_vector_meters",
     "sgz_line_graph_vertex_count", "sgz_line_graph_draws", "sgz_line_graph_vertices_device", "sgz_spectrum_render_line_vertices",
+    "sgz_spectrum_set_view", "sgz_view_translation_rows", "sgz_view_translate_device",
 ]
 
 
@@ -306,6 +307,10 @@ def lib() -> C.CDLL:
     L.sgz_line_graph_draws.argtypes = [C.POINTER(LineGraphStyle), u32, u32, u32, vp, C.POINTER(u32), vp]
     L.sgz_line_graph_vertices_device.argtypes = [vp, u32, u32, u32, u32, vp, vp]
     L.sgz_spectrum_render_line_vertices.argtypes = [vp, vp, u32, vp, C.POINTER(u32)]
+    dbl = C.c_double
+    L.sgz_spectrum_set_view.argtypes = [vp, dbl, dbl]
+    L.sgz_view_translation_rows.argtypes = [u32, dbl, dbl, dbl, dbl, vp, vp]
+    L.sgz_view_translate_device.argtypes = [vp, u32, sz, u32, dbl, dbl, dbl, dbl, vp]
     L.sgz_scope_num_points.argtypes = [C.POINTER(ScopeView)]
     L.sgz_scope_num_points.restype = sz
     L.sgz_scope_lanczos_device.argtypes = [C.POINTER(ScopeView), vp, sz, sz, u32, vp, vp]
@@ -383,6 +388,29 @@ def spectrum_render_line_vertices(handle, poles, flood: bool, out):
     pl = (C.c_float * NUM_GRAPHS)(*poles) if poles is not None else None
     check(lib().sgz_spectrum_render_line_vertices(handle, pl, int(bool(flood)), _buf_ptr(out), C.byref(cnt)))
     return cnt.value
+
+
+def spectrum_set_view(handle, left: float, right: float) -> None:
+    """sgz_spectrum_set_view: zoom / pan a spectrum handle (viewLeft / viewRight) keeping its audio history, queue and image binding;
+    the bound image of a colour-spectrum handle follows the view (freeLinearVerticalTranslation)"""
+    check(lib().sgz_spectrum_set_view(handle, float(left), float(right)))
+
+
+def view_translation_rows(axis_points: int, old_left: float, old_right: float, new_left: float, new_right: float):
+    """the translation's row table (sgz_view_translation_rows; host only): (src int32 [P], -1 = no source; weight uint16 [P])"""
+    src = np.zeros(axis_points, np.int32)
+    weight = np.zeros(axis_points, np.uint16)
+    check(lib().sgz_view_translation_rows(axis_points, old_left, old_right, new_left, new_right, _np_ptr(src), _np_ptr(weight)))
+    return src, weight
+
+
+def view_translate_device(image, columns: int, pitch_bytes: int, axis_points: int, old_left: float, old_right: float, new_left: float,
+                          new_right: float, stream=None) -> None:
+    """sgz_view_translate_device: translate a DEVICE image [P][pitch_bytes] of RGBA8 texels in place (a torch tensor or a device
+    pointer); waits for the result"""
+    ptr = C.c_void_p(image.data_ptr()) if hasattr(image, "data_ptr") else C.c_void_p(int(image))
+    check(lib().sgz_view_translate_device(ptr, columns, pitch_bytes, axis_points, old_left, old_right, new_left, new_right,
+                                          C.c_void_p(stream) if stream else None))
 
 
 RT_OPT_STRICT_REFERENCE_QUIRKS, RT_OPT_AUDIO_HISTORY, RT_OPT_DEFER_SUBMIT, RT_OPT_PARK_PUSHES = 1, 2, 3, 4

@@ -44,6 +44,10 @@
 // GL / Vulkan context lives on the display GPU and imports the fd with EXT_memory_object_fd / EGL_EXT_image_dma_buf_import), or
 // (c) an OpenGL buffer object of a context on the same device, registered and mapped through HIP's GL interop
 // (sgz_spectrum_bind_gl_buffer).
+//
+// Zoom / pan (sgz_spectrum_set_view, consumer thread; handleFlagUpdates' viewChanged branch, Spectrum.cpp:532-575): the new view's plans
+// are built outside cfgMu; under it the producer's stream is drained, the plans are swapped and warmed up, and the line graphs cleared.
+// The ring, the cadence, the column queue and the image binding stay; the bound image is translated afterwards (view_translate.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -154,6 +158,7 @@ struct sgz_spectrum {
     uint8_t *d_image = nullptr; size_t imgPitch = 0; uint32_t imgColumns = 0, imgX = 0;
     bool imgOwned = false;
     hipGraphicsResource *glResource = nullptr;
+    float *d_viewScratch = nullptr; size_t viewScratchCap = 0;    // sgz_spectrum_set_view: the row table and the image copy it gathers from (floats)
 };
 
 static void unbindImage(sgz_spectrum *s)
@@ -164,6 +169,7 @@ static void unbindImage(sgz_spectrum *s)
         s->glResource = nullptr;
     }
     if (s->imgOwned && s->d_image) (void)hipFree(s->d_image);
+    if (s->d_viewScratch) { (void)hipFree(s->d_viewScratch); s->d_viewScratch = nullptr; s->viewScratchCap = 0; }
     s->d_image = nullptr; s->imgOwned = false; s->imgColumns = 0; s->imgPitch = 0; s->imgX = 0;
 }
 
@@ -208,8 +214,8 @@ static sgz_status uploadMix(sgz_spectrum *s, uint32_t numSources, const uint8_t 
     return s->stage.init(numSources, kPiece);
 }
 
-// builds everything for a configuration into the handle (the caller holds cfgMu, or the handle is not shared yet)
-static sgz_status setup(sgz_spectrum *s, const sgz_spectrum_config *cfg)
+// both plans of a configuration, built and uploaded (touches nothing of the handle)
+static sgz_status makePlans(const sgz_spectrum_config *cfg, Plan **plan, Plan **trackPlan)
 {
     Plan *pl = new (std::nothrow) Plan();
     if (!pl) return fail(SGZ_ENOMEM, "out of memory");
@@ -225,6 +231,42 @@ static sgz_status setup(sgz_spectrum *s, const sgz_spectrum_config *cfg)
     catch (const std::bad_alloc &) { st = SGZ_ENOMEM; err = "out of memory building the plan tables"; }
     if (st == SGZ_OK) st = uploadPlan(*tp, err);
     if (st != SGZ_OK) { delete pl; delete tp; return fail(st, err); }
+    *plan = pl;
+    *trackPlan = tp;
+    return SGZ_OK;
+}
+
+// warm-up of the handle's plans: the largest batch a push can produce and the consumer's line-graph step, on the ring as it stands (read,
+// never written) -- every lazy allocation and LDS grant of the kernels happens here, not on the audio thread.  The state it leaves is
+// cleared again: decay states, line results and the resonators start at rest (the caller holds cfgMu, or the handle is not shared yet)
+static sgz_status warmUp(sgz_spectrum *s)
+{
+    Plan &p = *s->plan, &tp = *s->trackPlan;
+    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
+    sgz_status st = runStft(p, s->d_ring, size_t(2) * s->cap, long(s->maxFrames), s->d_mapped, nullptr, nullptr, s->stream, nullptr, /*deferLate=*/true);
+    if (st == SGZ_OK) st = runDecayColour(p, s->d_mapped, long(s->maxFrames), s->d_colsBatch, s->d_linesBatch, s->d_state, s->stream);
+    if (st == SGZ_OK && s->maxFrames > 1) {
+        st = runStft(p, s->d_ring, size_t(2) * s->cap, 1, s->d_mapped, nullptr, nullptr, s->stream, nullptr, /*deferLate=*/true);
+        if (st == SGZ_OK) st = runDecayColour(p, s->d_mapped, 1, s->d_colsBatch, s->d_linesBatch, s->d_state, s->stream);
+    }
+    // ... and the consumer thread's line-graph step on its own plan (one frame with line results and state)
+    if (st == SGZ_OK && !isResonator(p)) st = runStft(tp, s->d_ring, size_t(2) * s->cap, 1, s->d_lineMapped, nullptr, nullptr, s->stream);
+    if (st == SGZ_OK) st = runDecayColour(tp, isResonator(p) ? s->d_mapped : s->d_lineMapped, 1, nullptr, s->d_lines, s->d_state, s->stream);
+    if (st != SGZ_OK) return st;
+    if ((st = resetResonator(p, s->stream)) != SGZ_OK) return st;
+    SGZ_HIP(hipMemsetAsync(s->d_state, 0, stateN * sizeof(float), s->stream));
+    SGZ_HIP(hipMemsetAsync(s->d_lines, 0, stateN * sizeof(float), s->stream));
+    SGZ_HIP(hipMemsetAsync(s->d_mapped, 0, size_t(s->maxFrames) * p.C * p.sides * p.P * sizeof(float), s->stream));   // (RSNT line graph: the windowed state of resonators at rest)
+    SGZ_HIP(hipStreamSynchronize(s->stream));
+    return SGZ_OK;
+}
+
+// builds everything for a configuration into the handle (the caller holds cfgMu, or the handle is not shared yet)
+static sgz_status setup(sgz_spectrum *s, const sgz_spectrum_config *cfg)
+{
+    Plan *pl = nullptr, *tp = nullptr;
+    sgz_status st = makePlans(cfg, &pl, &tp);
+    if (st != SGZ_OK) return st;
     if (!s->stream) SGZ_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     (void)hipStreamSynchronize(s->stream);
     delete s->plan;
@@ -271,24 +313,7 @@ static sgz_status setup(sgz_spectrum *s, const sgz_spectrum_config *cfg)
     for (auto &e : s->colEvents) if (!e) SGZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     s->colQ.reset();
     if ((st = uploadMix(s, uint32_t(nch), nullptr)) != SGZ_OK) return st;
-    // warm-up: the largest batch a push can produce, on the silent ring -- every lazy allocation and LDS grant of the kernels
-    // happens here, not on the audio thread.  The state it leaves is cleared again.
-    st = runStft(p, s->d_ring, size_t(2) * s->cap, long(s->maxFrames), s->d_mapped, nullptr, nullptr, s->stream, nullptr, /*deferLate=*/true);
-    if (st == SGZ_OK) st = runDecayColour(p, s->d_mapped, long(s->maxFrames), s->d_colsBatch, s->d_linesBatch, s->d_state, s->stream);
-    if (st == SGZ_OK && s->maxFrames > 1) {
-        st = runStft(p, s->d_ring, size_t(2) * s->cap, 1, s->d_mapped, nullptr, nullptr, s->stream, nullptr, /*deferLate=*/true);
-        if (st == SGZ_OK) st = runDecayColour(p, s->d_mapped, 1, s->d_colsBatch, s->d_linesBatch, s->d_state, s->stream);
-    }
-    // ... and the consumer thread's line-graph step on its own plan (one frame with line results and state)
-    if (st == SGZ_OK && !isResonator(p)) st = runStft(*tp, s->d_ring, size_t(2) * s->cap, 1, s->d_lineMapped, nullptr, nullptr, s->stream);
-    if (st == SGZ_OK) st = runDecayColour(*tp, isResonator(p) ? s->d_mapped : s->d_lineMapped, 1, nullptr, s->d_lines, s->d_state, s->stream);
-    if (st != SGZ_OK) return st;
-    if ((st = resetResonator(p, s->stream)) != SGZ_OK) return st;
-    SGZ_HIP(hipMemsetAsync(s->d_state, 0, stateN * sizeof(float), s->stream));
-    SGZ_HIP(hipMemsetAsync(s->d_lines, 0, stateN * sizeof(float), s->stream));
-    SGZ_HIP(hipMemsetAsync(s->d_mapped, 0, size_t(s->maxFrames) * p.C * p.sides * p.P * sizeof(float), s->stream));   // (RSNT line graph: the windowed state of resonators at rest)
-    SGZ_HIP(hipStreamSynchronize(s->stream));
-    return SGZ_OK;
+    return warmUp(s);
 }
 
 // ring position of the first of the `span` samples that end `back` samples before absolute sample count `at`
@@ -632,6 +657,67 @@ sgz_status sgz_spectrum_flush_columns(sgz_spectrum *s, uint32_t *first_column, u
     if (first_column) *first_column = first;
     if (count) *count = n;
     return n ? SGZ_OK : SGZ_EMPTY;
+}
+
+// freeLinearVerticalTranslation(oldViewRect, viewRect) of the bound image (view_translate.hip), a GL buffer mapped around it as in
+// flush_columns; waits for the texels
+static sgz_status translateBoundImage(sgz_spectrum *s, const double oldView[2], const double newView[2])
+{
+    const uint32_t P = s->plan->P;
+    hipGraphicsResource *gl = s->glResource;
+    uint8_t *image = s->d_image;
+    if (gl) {
+        void *ptr = nullptr; size_t size = 0;
+        SGZ_HIP(hipGraphicsMapResources(1, &gl, s->outStream));
+        const hipError_t e = hipGraphicsResourceGetMappedPointer(&ptr, &size, gl);
+        if (e != hipSuccess) { (void)hipGraphicsUnmapResources(1, &gl, s->outStream); return hipFail(e, "hipGraphicsResourceGetMappedPointer"); }
+        image = static_cast<uint8_t *>(ptr);
+    }
+    const sgz_status st = translateViewImage(image, s->imgColumns, s->imgPitch, P, oldView, newView, &s->d_viewScratch, &s->viewScratchCap, s->outStream);
+    if (gl) {
+        if (st != SGZ_OK) (void)hipStreamSynchronize(s->outStream);
+        const hipError_t eu = hipGraphicsUnmapResources(1, &gl, s->outStream);
+        if (st == SGZ_OK && eu != hipSuccess) return hipFail(eu, "hipGraphicsUnmapResources");
+    }
+    return st;
+}
+
+sgz_status sgz_spectrum_set_view(sgz_spectrum *s, double view_left, double view_right)
+{
+    if (!s) return fail(SGZ_EINVAL, "null handle");
+    if (!validViewRect(view_left, view_right)) return fail(SGZ_EINVAL, "view must satisfy 0 <= view_left < view_right <= 1");
+    sgz_spectrum_config cfg = s->plan->cfg;                   // (only this thread replaces the plans)
+    const double oldView[2] = {cfg.view_left, cfg.view_right}, newView[2] = {view_left, view_right};
+    cfg.view_left = view_left;
+    cfg.view_right = view_right;
+    // remapFrequencies with everything that hangs on it (map tables, slope map, tracker tables, resonator tuning): new plans, built and
+    // uploaded before the handle is held, so that push is refused only while they are swapped in
+    Plan *pl = nullptr, *tp = nullptr;
+    sgz_status st = makePlans(&cfg, &pl, &tp);
+    if (st != SGZ_OK) return st;
+    {
+        std::lock_guard<std::mutex> lk(s->cfgMu);
+        const hipError_t e = hipStreamSynchronize(s->stream);   // the old plans' launches are done; the ring, written / planned and the
+        if (e != hipSuccess) { delete pl; delete tp; return hipFail(e, "hipStreamSynchronize"); }   // frame cadence stay as they are
+        delete s->plan;
+        s->plan = pl;
+        delete s->trackPlan;
+        s->trackPlan = tp;
+        // the new plans' warm-up (their paths may differ from the old ones': realSplit / sideMapOk depend on the mapping), which leaves the
+        // decay states, the line results and the resonators at rest: pair.clearLineGraphStates() (TransformPair.h:169-175) -- and the host's
+        // copies of the results with them
+        if ((st = warmUp(s)) != SGZ_OK) return st;
+        const Plan &p = *s->plan;
+        const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
+        std::memset(s->h_lineOut, 0, stateN * sizeof(float));
+        std::memset(s->h_lines, 0, size_t(sgz_spectrum::kLineSlots) * stateN * sizeof(float));
+        s->lineSeq.reset();
+    }
+    // Spectrum.cpp:560-561: the columns on screen follow the view -- only when the rect changed; queued columns keep the mapping they were
+    // computed with and land after this, as the frameQueue's do
+    if (cfg.display_mode == SGZ_DISPLAY_COLOUR_SPECTRUM && (oldView[0] != view_left || oldView[1] != view_right) && (s->d_image || s->glResource))
+        return translateBoundImage(s, oldView, newView);
+    return SGZ_OK;
 }
 
 sgz_status sgz_spectrum_line_results(sgz_spectrum *s, uint32_t pair, uint32_t graph, float *out)

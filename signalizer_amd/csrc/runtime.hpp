@@ -22,6 +22,11 @@ sgz_status ensureCap(float **buf, size_t *cap, size_t need);
 // line_graph.hip: the line graph's vertex kernel (sgz_line_graph_vertices_device; the spectrum handle's render_line_vertices)
 sgz_status launchLineGraphVertices(const float *d_lines, uint32_t pairs, uint32_t P, uint32_t mode, uint32_t flood, float *d_xyz,
                                    hipStream_t stream);
+// view_translate.hip: the spectrogram image following a change of view (sgz_view_translate_device; the spectrum handle's set_view).
+// translateViewImage waits for its result; scratch / scratchCap (floats) are grown as needed and stay the caller's
+bool validViewRect(double left, double right);
+sgz_status translateViewImage(uint8_t *image, uint32_t columns, size_t pitch, uint32_t P, const double oldView[2], const double newView[2],
+                              float **scratch, size_t *scratchCap, hipStream_t stream);
 int numCUs();
 // K_A over `frames` frames (ideal STFT framing from d_planar); any of mapped/binsOut may be null
 // deferLate: the caller's next call is runDecayColour on the same d_mapped with only an image wanted -- a channel-split launch may then
