@@ -24,6 +24,8 @@ extern "C" {
  *    sgz_spectrum_set_option (round 4);
  * 5: sgz_scope_set_option / sgz_vector_set_option (SGZ_RT_OPT_DEFER_SUBMIT, SGZ_RT_OPT_PARK_PUSHES), sgz_spectrum_track_peak_lines, plan option
  *    SGZ_OPT_WIDE_GROUPS; the Oscilloscope / Vectorscope readers flush the host FIFO as well; SGZ_OPT_RESONATOR_SLAB bounds the sharded RSNT render (round 5; its own option SGZ_OPT_RESONATOR_SHARD_BOUND from round 6);
+ * (5, later: sgz_scope_set_mix / sgz_vector_set_mix were added without a version change: no existing entry point or struct changed;
+ *  a binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -690,6 +692,15 @@ sgz_status sgz_scope_configure(sgz_scope *s, const sgz_scope_config *cfg);
 /* onStreamAudio(ctx, float** buffer, numChannels, numSamples); the steady clock is the running count of pushed samples */
 sgz_status sgz_scope_push(sgz_scope *s, const float *const *planar, uint32_t num_channels, uint32_t nsamples);
 sgz_status sgz_scope_flush(sgz_scope *s);      /* as sgz_spectrum_flush */
+/* MixGraphListener::deliver's routing (Source/Common/MixGraphListener.cpp:247-334), as sgz_spectrum_set_mix: destination channel d (of
+ * num_channels) = the sum of the source channels c with matrix[d * num_sources + c] != 0, added in ascending c onto a row of 0.0f
+ * (copyFromHead<true> into a cleared row: -0.0 becomes +0.0, NaN propagates); a destination with no source is silence.  push then takes
+ * num_sources channels (1..64; fewer, as many or more than num_channels) and refuses any other count with SGZ_EINVAL.  The ingest
+ * launch routes the staged sources itself: no extra launch, push still allocates nothing.  Consumer thread, like configure: every
+ * block pushed before the call (staged, batched, parked or deferred) goes through the old routing; a concurrent push is refused with
+ * SGZ_BUSY while the switch holds the handle, it never waits.  A NULL matrix, 0 or more than 64 sources: SGZ_EINVAL, the handle
+ * unchanged.  configure returns the routing to the identity over num_channels. */
+sgz_status sgz_scope_set_mix(sgz_scope *s, uint32_t num_sources, const uint8_t *matrix /*[num_channels][num_sources]*/);
 /* Handle switch (consumer thread, between create / configure and the first push; the library reads no environment variable):
  *   SGZ_RT_OPT_DEFER_SUBMIT  0 (default): a pushed block goes to the GPU at once when nothing of the handle is in flight, otherwise it
  *       joins the open batch, which the next submission takes in ONE launch.  1: every block waits for a full batch or a reader
@@ -787,6 +798,8 @@ void       sgz_vector_destroy(sgz_vector *s);
 sgz_status sgz_vector_configure(sgz_vector *s, const sgz_vector_config *cfg);
 sgz_status sgz_vector_push(sgz_vector *s, const float *const *planar, uint32_t num_channels, uint32_t nsamples);
 sgz_status sgz_vector_flush(sgz_vector *s);    /* as sgz_spectrum_flush */
+/* the host graph's routing, exactly as sgz_scope_set_mix (Vectorscope.h:141's onStreamAudio receives the routed stream) */
+sgz_status sgz_vector_set_mix(sgz_vector *s, uint32_t num_sources, const uint8_t *matrix /*[num_channels][num_sources]*/);
 sgz_status sgz_vector_set_option(sgz_vector *s, uint32_t option, uint64_t value);   /* SGZ_RT_OPT_DEFER_SUBMIT / SGZ_RT_OPT_PARK_PUSHES, as sgz_scope_set_option */
 sgz_status sgz_vector_peak_filter(sgz_vector *s, double delta_time, double *envelope_gain /*optional: reading it waits*/);
 sgz_status sgz_vector_filters_get(sgz_vector *s, sgz_vector_filters *filters, double *envelope_gain);

@@ -163,6 +163,7 @@ EXPORTS = [
     "sgz_vector_meters_from_filters", "sgz_vector_meters",
     "sgz_line_graph_vertex_count", "sgz_line_graph_draws", "sgz_line_graph_vertices_device", "sgz_spectrum_render_line_vertices",
     "sgz_spectrum_set_view", "sgz_view_translation_rows", "sgz_view_translate_device",
+    "sgz_scope_set_mix", "sgz_vector_set_mix",
 ]
 
 
@@ -271,6 +272,7 @@ def lib() -> C.CDLL:
     L.sgz_scope_destroy.restype = None
     L.sgz_scope_configure.argtypes = [vp, C.POINTER(ScopeConfig)]
     L.sgz_scope_push.argtypes = [vp, vp, u32, u32]
+    L.sgz_scope_set_mix.argtypes = [vp, u32, vp]
     L.sgz_scope_peak_filter.argtypes = [vp, C.c_double, u32, C.POINTER(C.c_double)]
     L.sgz_scope_gains.argtypes = [vp, C.POINTER(C.c_double), vp]
     L.sgz_scope_vertex_count.argtypes = [vp, C.POINTER(ScopeView)]
@@ -291,6 +293,7 @@ def lib() -> C.CDLL:
     L.sgz_vector_destroy.restype = None
     L.sgz_vector_configure.argtypes = [vp, C.POINTER(VectorConfig)]
     L.sgz_vector_push.argtypes = [vp, vp, u32, u32]
+    L.sgz_vector_set_mix.argtypes = [vp, u32, vp]
     L.sgz_vector_peak_filter.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.sgz_vector_filters_get.argtypes = [vp, C.POINTER(VectorFilters), C.POINTER(C.c_double)]
     L.sgz_vector_vertices.argtypes = [vp, u32, vp, vp, C.POINTER(u32)]
@@ -719,6 +722,14 @@ class Scope:
         ptrs = (C.c_void_p * b.shape[0])(*[b[c].ctypes.data for c in range(b.shape[0])])
         return check(lib().sgz_scope_push(self.h, ptrs, b.shape[0], b.shape[1]))
 
+    def set_mix(self, matrix: np.ndarray):
+        """sgz_scope_set_mix: matrix uint8 [num_channels, num_sources]; push then takes num_sources channels"""
+        m = np.ascontiguousarray(matrix, np.uint8)
+        if m.ndim != 2 or m.shape[0] != self.cfg.num_channels:
+            raise ValueError(f"mix matrix must be [num_channels = {self.cfg.num_channels}, num_sources], got {m.shape}")
+        check(lib().sgz_scope_set_mix(self.h, m.shape[1], _np_ptr(m)))
+        return self
+
     def flush(self):
         """blocks that waited for a staging slot are enqueued now (sgz_scope_flush): readers of results call it first"""
         check(lib().sgz_scope_flush(self.h))
@@ -837,6 +848,14 @@ class Vector:
         b = np.ascontiguousarray(block, np.float32)
         ptrs = (C.c_void_p * b.shape[0])(*[b[c].ctypes.data for c in range(b.shape[0])])
         return check(lib().sgz_vector_push(self.h, ptrs, b.shape[0], b.shape[1]))
+
+    def set_mix(self, matrix: np.ndarray):
+        """sgz_vector_set_mix: matrix uint8 [num_channels, num_sources]; push then takes num_sources channels"""
+        m = np.ascontiguousarray(matrix, np.uint8)
+        if m.ndim != 2 or m.shape[0] != self.cfg.num_channels:
+            raise ValueError(f"mix matrix must be [num_channels = {self.cfg.num_channels}, num_sources], got {m.shape}")
+        check(lib().sgz_vector_set_mix(self.h, m.shape[1], _np_ptr(m)))
+        return self
 
     def flush(self):
         """blocks that waited for a staging slot are enqueued now (sgz_vector_flush): readers of results call it first"""

@@ -276,4 +276,109 @@ __device__ __forceinline__ void batchFetch(const float *from, float *to, uint32_
 }
 #endif
 
+// MixGraphListener::deliver's routing for the batched handles (sgz_scope_set_mix / sgz_vector_set_mix, Source/Common/MixGraphListener.cpp:
+// 247-334): destination d = the sources listed in src[d][0 .. count[d]), ascending, added onto 0.0f -- what copyFromHead<true> into a
+// cleared row does (-0.0 becomes +0.0, NaN propagates).  Built from the [destinations][sources] matrix on the host; the ingest kernel
+// keeps a copy in LDS.
+struct MixRoute {
+    static constexpr uint32_t kMax = 64;
+    uint32_t count[kMax];
+    uint8_t src[kMax][kMax];
+};
+
+// A handle's routing: with none set, or the identity, `active` is false and the staged batch IS the destination rows (the ingest kernels'
+// default path, untouched); otherwise the batch holds numSources rows per block and the ingest kernel writes the destination rows to `d_rows`
+// before its phases read them.
+struct BatchMix {
+    MixRoute *d_route = nullptr;
+    float *d_rows = nullptr;       // device [destinations x slotSamples]: one batch's destination rows, every block at its own addresses
+    size_t rowsFloats = 0;
+    uint32_t numSources = 0;       // what push takes
+    bool active = false;
+
+    void release()
+    {
+        if (d_route) (void)hipFree(d_route);
+        if (d_rows) (void)hipFree(d_rows);
+        d_route = nullptr; d_rows = nullptr; rowsFloats = 0;
+        active = false;
+    }
+    void reset(uint32_t numChannels) { release(); numSources = numChannels; }          // configure: the identity over num_channels
+    // (caller: the arguments are valid, the handle's stream is idle, the staging holds numSources rows per block of up to slotSamples)
+    sgz_status set(uint32_t numSrc, uint32_t numDst, const uint8_t *matrix, uint32_t slotSamples)
+    {
+        MixRoute r{};
+        bool identity = numSrc == numDst;
+        for (uint32_t d = 0; d < numDst; ++d)
+            for (uint32_t c = 0; c < numSrc; ++c) {
+                const bool on = matrix[size_t(d) * numSrc + c] != 0;
+                if (on) r.src[d][r.count[d]++] = uint8_t(c);
+                identity = identity && on == (c == d);
+            }
+        if (identity) { reset(numSrc); return SGZ_OK; }
+        if (!d_route) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&d_route), sizeof(MixRoute)));
+        SGZ_HIP(hipMemcpy(d_route, &r, sizeof(MixRoute), hipMemcpyHostToDevice));
+        const size_t need = size_t(numDst) * slotSamples;
+        if (rowsFloats < need) {
+            if (d_rows) (void)hipFree(d_rows);
+            d_rows = nullptr; rowsFloats = 0;
+            SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&d_rows), need * sizeof(float)));
+            rowsFloats = need;
+        }
+        numSources = numSrc;
+        active = true;
+        return SGZ_OK;
+    }
+};
+
+#ifdef __HIPCC__
+// The routing step of a batched ingest kernel (ONE workgroup), behind batchFetch: block b of the staged batch ([numSrc][len] at
+// numSrc x start) -> its destination rows ([numDst][len] at numDst x start of `rows`), and sBlockOff[b] to match, so that the phases
+// behind it read the destination rows as they read an unrouted batch.  The whole batch is routed here, not block by block, because the
+// Oscilloscope's zero-crossing detector scans the concatenation of the batch's blocks before the per-block walk; every block has its own
+// addresses in `rows`, so no line a wave reads can have been left in the CU's L1 by an earlier block of the launch (the L1 starts the
+// launch cold).  Every thread takes four (destination, sample) elements at a time, so that four loads are in flight per source step.
+__device__ __forceinline__ void batchMix(const MixRoute *route, MixRoute &sRoute, const float *src, float *rows, uint32_t numSrc, uint32_t numDst,
+                                         uint32_t numBlocks, uint32_t *sBlockOff, const uint32_t *sBlockLen, int tid, int threads)
+{
+    static_assert(sizeof(MixRoute) % 4 == 0, "copied as words");
+    for (uint32_t w = uint32_t(tid); w < sizeof(MixRoute) / 4; w += uint32_t(threads))
+        reinterpret_cast<uint32_t *>(&sRoute)[w] = reinterpret_cast<const uint32_t *>(route)[w];
+    __syncthreads();
+    const uint32_t T = uint32_t(threads);
+    uint32_t start = 0;
+    for (uint32_t b = 0; b < numBlocks; ++b) {                                // (uniform)
+        const uint32_t n = sBlockLen[b], total = numDst * n;
+        const float *in = src + size_t(numSrc) * start;
+        float *out = rows + size_t(numDst) * start;
+        for (uint32_t e0 = uint32_t(tid); e0 < total; e0 += 4u * T) {
+            uint32_t d[4], i[4], cnt[4];
+            float v[4];
+            uint32_t kmax = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t e = e0 + uint32_t(j) * T;
+                d[j] = e < total ? e / n : 0u;
+                i[j] = e < total ? e - d[j] * n : 0u;
+                cnt[j] = e < total ? sRoute.count[d[j]] : 0u;
+                kmax = cnt[j] > kmax ? cnt[j] : kmax;
+                v[j] = 0.f;
+            }
+            for (uint32_t k = 0; k < kmax; ++k) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (k < cnt[j]) v[j] = v[j] + in[size_t(sRoute.src[d[j]][k]) * n + i[j]];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (e0 + uint32_t(j) * T < total) out[size_t(d[j]) * n + i[j]] = v[j];
+        }
+        if (tid == int(b)) sBlockOff[b] = numDst * start;                    // (nobody reads the table before the barrier below)
+        start += n;
+    }
+    __threadfence_block();
+    __syncthreads();
+}
+#endif
+
 }  // namespace sgz

@@ -122,6 +122,8 @@ struct IngestParams {
     Swap *swapList;                           // [kMaxSwaps]
     const float *batch;                       // the staged blocks, back to back: block b = [channels][blockLen[b]] at batch + blockOff[b]
     const float *batchHost; uint32_t batchFloats;   // the pinned slot they are fetched from first (rt_common.hpp batchFetch), or null
+    const MixRoute *route; float *mixRows;    // sgz_scope_set_mix: the batch holds numSources rows per block, routed into mixRows first (rt_common.hpp batchMix); route null: none
+    uint32_t numSources;
     uint32_t numBlocks, channels;
     uint32_t blockOff[BatchRing::kMaxBlocks], blockLen[BatchRing::kMaxBlocks];
     float *front; uint32_t size;              // [channels][size]
@@ -896,6 +898,13 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
         if (tid == int(b)) { sBlockOff[b] = prm.blockOff[b]; sBlockLen[b] = prm.blockLen[b]; }
     __syncthreads();
     batchFetch(prm.batchHost, const_cast<float *>(prm.batch), prm.batchFloats, tid, T);
+    // sgz_scope_set_mix: the staged source rows -> the destination rows every phase below reads (and sBlockOff into them)
+    __shared__ MixRoute sRoute;
+    const float *batch = prm.batch;
+    if (prm.route) {                                                       // (uniform)
+        batchMix(prm.route, sRoute, prm.batch, prm.mixRows, prm.numSources, C, prm.numBlocks, sBlockOff, sBlockLen, tid, T);
+        batch = prm.mixRows;
+    }
     // ---- A for the WHOLE batch.  The zero-crossing detector (phase A) is a scan over the samples whose state (armed, last threshold
     // crossing, previous sample) does not depend on what processMutating does with the triggers, and a trigger's slot in the queue's
     // ring is head + count + (triggers before it) whatever has been popped meanwhile: so the detector runs ONCE over the
@@ -918,7 +927,7 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
         auto sampleAt = [&](uint32_t i, uint32_t &b) -> double {           // sample i of the concatenation
             while (sBlockStart[b + 1] <= i) ++b;
             const float *a, *c;
-            const uint32_t mode = triggerPlanes(prm, prm.batch + sBlockOff[b], sBlockLen[b], a, c);
+            const uint32_t mode = triggerPlanes(prm, batch + sBlockOff[b], sBlockLen[b], a, c);
             return trigSample(mode, a, c, i - sBlockStart[b]);
         };
         if (zeroCrossings(sBlockStart[prm.numBlocks], sampleAt, st, prm.peaks, st->playhead, sFires, sScan2, sSum) && tid == 0) sBatchedA = 1;
@@ -927,7 +936,7 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
     const bool batchedA = sBatchedA != 0;
     const bool hold = prm.triggerMode == 4u || prm.triggerMode == 3u;      // ZeroCrossing, EnvelopeHold: detector -> processMutating
     for (uint32_t blockIndex = 0; blockIndex < prm.numBlocks; ++blockIndex) {
-        const float *const blk = prm.batch + sBlockOff[blockIndex];
+        const float *const blk = batch + sBlockOff[blockIndex];
         const uint32_t n = sBlockLen[blockIndex];
         const unsigned long long playhead = st->playhead;
         ICLK(0);
@@ -1322,6 +1331,7 @@ struct sgz_scope {
     BatchRing batch;                           // staged blocks waiting for their (one) ingest launch (rt_common.hpp)
     uint32_t maxBlock = 0;
     Backlog backlog;                           // blocks waiting for a staging slot (rt_common.hpp)
+    BatchMix mix;                              // sgz_scope_set_mix's routing (rt_common.hpp): the staging holds mix.numSources rows per block
     ScopeDev *d_state = nullptr;
     unsigned long long *d_peaks = nullptr;
     Swap *d_swaps = nullptr;
@@ -1349,6 +1359,7 @@ static void scopeFree(sgz_scope *s)
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     s->batch.release();
     s->backlog.release();
+    s->mix.release();
     for (void *p : {(void *)s->d_state, (void *)s->d_peaks, (void *)s->d_swaps, (void *)s->d_front, (void *)s->d_back, (void *)s->d_xyz,
                     (void *)s->d_rgba, (void *)s->col.st, (void *)s->col.bands, (void *)s->col.sm, (void *)s->col.block, (void *)s->col.front,
                     (void *)s->col.back, (void *)s->d_spectral, (void *)s->d_tw, (void *)s->d_col})
@@ -1442,6 +1453,11 @@ static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fre
         }
         s->col.maxBlock = maxBlock;
     }
+    if (s->batch.channels != C) {             // a configure after sgz_scope_set_mix: the staging takes num_channels rows again
+        if ((st = s->batch.init(C, std::max<uint32_t>(s->maxBlock, 8192u))) != SGZ_OK) return st;
+        if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+    }
+    s->mix.reset(C);                          // the routing returns to the identity over num_channels
     if (colours) {
         // tuneCrossOver(300, 3000, sampleRate), tuneColourSmoothing(ms, sampleRate) (ChannelData.h:163-171).  cpl's designs are not in the
         // reference tree: the 3-band Linkwitz-Riley tree and the one-pole design are the published ones (oracle/scope_spectral.c)
@@ -1556,6 +1572,7 @@ static sgz_status scopeSubmit(sgz_scope *s, const PeakParams *peak = nullptr)
     prm.st = s->d_state; prm.peaks = s->d_peaks; prm.swapList = s->d_swaps;
     prm.batch = d_batch; prm.numBlocks = s->batch.count; prm.channels = s->cfg.num_channels;
     for (uint32_t b = 0; b < s->batch.count; ++b) { prm.blockOff[b] = s->batch.off[b]; prm.blockLen[b] = s->batch.len[b]; }
+    if (s->mix.active) { prm.route = s->mix.d_route; prm.mixRows = s->mix.d_rows; prm.numSources = s->batch.channels; }
     prm.front = s->d_front; prm.size = s->size; prm.back = s->d_back; prm.backCap = s->backCap;
     prm.triggerMode = s->cfg.trigger_mode; prm.oscMode = s->cfg.channel_mode; prm.envMode = s->cfg.envelope_mode;
     prm.trigSeparate = s->trigSeparate; prm.trigPair = s->trigPair; prm.envelopeCoeff = s->envelopeCoeff;
@@ -1593,7 +1610,8 @@ sgz_status sgz_scope_push(sgz_scope *s, const float *const *planar, uint32_t num
     if (!s || !planar) return fail(SGZ_EINVAL, "null argument");
     std::unique_lock<std::mutex> lk(s->mu, std::try_to_lock);      // never waits: a reconfiguration in progress drops the block
     if (!lk.owns_lock()) { s->busy++; return SGZ_BUSY; }
-    if (num_channels != s->cfg.num_channels) return fail(SGZ_EINVAL, "num_channels differs from the configuration");
+    if (num_channels != s->mix.numSources)
+        return fail(SGZ_EINVAL, "num_channels differs from the configuration (or from the source count of sgz_scope_set_mix)");
     if (nsamples == 0) return SGZ_OK;                              // audioEntryPoint returns at once (:403-404)
     if (nsamples > s->maxBlock) return fail(SGZ_EINVAL, "block longer than sgz_scope_config::max_block");
     // never waits: the render thread is submitting the open batch right now -> the block waits its turn in the host FIFO, like one
@@ -1603,6 +1621,19 @@ sgz_status sgz_scope_push(sgz_scope *s, const float *const *planar, uint32_t num
     const sgz_status st = batchPush(side, planar, num_channels, nsamples, s->parkPushes.load(std::memory_order_relaxed));
     if (st == SGZ_BUSY) s->busy++;
     return st;
+}
+
+sgz_status sgz_scope_set_mix(sgz_scope *s, uint32_t num_sources, const uint8_t *matrix)
+{
+    if (!s || !matrix || num_sources == 0 || num_sources > MixRoute::kMax) return fail(SGZ_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lk(s->mu);                                // (a push meanwhile is refused with SGZ_BUSY: it never waits)
+    if (sgz_status sy = scopeSync(s); sy != SGZ_OK) return sy;            // the audio already taken goes through the old routing
+    SGZ_HIP(hipStreamSynchronize(s->stream));
+    if (s->batch.channels != num_sources) {                               // staging, pinned slot and FIFO for num_sources rows per block
+        if (sgz_status st = s->batch.init(num_sources, std::max<uint32_t>(s->maxBlock, 8192u)); st != SGZ_OK) return st;
+        if (!s->backlog.init(backlogFloats(num_sources, s->cfg.sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+    }
+    return s->mix.set(num_sources, s->cfg.num_channels, matrix, s->batch.slotSamples);
 }
 
 void *sgz_scope_stream(sgz_scope *s) { return s ? s->stream : nullptr; }

@@ -39,6 +39,7 @@ struct VecIngest {
     VecDev *st;
     const float *batchHost; uint32_t batchFloats;             // the pinned slot the blocks are fetched from first (rt_common.hpp batchFetch), or null
     const float *batch; uint32_t numBlocks, channels;         // the staged blocks back to back: block b = [channels][blockLen[b]] at batch + blockOff[b]
+    const MixRoute *route; float *mixRows; uint32_t numSources;   // sgz_vector_set_mix: numSources rows per staged block, routed into mixRows first; route null: none
     uint32_t blockOff[BatchRing::kMaxBlocks], blockLen[BatchRing::kMaxBlocks];
     float *ring; uint32_t size;
     uint32_t lanes, envMode;
@@ -61,8 +62,15 @@ __global__ void __launch_bounds__(256) vectorIngestKernel(const VecIngest prm)
         if (tid == int(b)) { sBlockOff[b] = prm.blockOff[b]; sBlockLen[b] = prm.blockLen[b]; }
     __syncthreads();
     batchFetch(prm.batchHost, const_cast<float *>(prm.batch), prm.batchFloats, tid, 256);
+    // sgz_vector_set_mix: the staged source rows -> the destination rows the blocks below read (rt_common.hpp batchMix)
+    __shared__ MixRoute sRoute;
+    const float *batch = prm.batch;
+    if (prm.route) {                                                      // (uniform)
+        batchMix(prm.route, sRoute, prm.batch, prm.mixRows, prm.numSources, C, prm.numBlocks, sBlockOff, sBlockLen, tid, 256);
+        batch = prm.mixRows;
+    }
     for (uint32_t blockIndex = 0; blockIndex < prm.numBlocks; ++blockIndex) {
-    const float *const blk = prm.batch + sBlockOff[blockIndex];
+    const float *const blk = batch + sBlockOff[blockIndex];
     const uint32_t n = sBlockLen[blockIndex];
     const uint32_t cursor0 = st->cursor;
     // ring append (only the newest `size` samples of a longer block survive)
@@ -361,6 +369,7 @@ struct sgz_vector {
     BatchRing batch;                           // staged blocks waiting for their (one) ingest launch (rt_common.hpp)
     uint32_t maxBlock = 0;
     Backlog backlog;                           // blocks waiting for a staging slot (rt_common.hpp)
+    BatchMix mix;                              // sgz_vector_set_mix's routing (rt_common.hpp): the staging holds mix.numSources rows per block
     VecDev *d_state = nullptr;
     float *d_ring = nullptr;
     uint32_t size = 0;
@@ -382,6 +391,7 @@ static void vectorFree(sgz_vector *s)
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     s->batch.release();
     s->backlog.release();
+    s->mix.release();
     for (void *p : {(void *)s->d_state, (void *)s->d_ring, (void *)s->d_ramp, (void *)s->d_tail, (void *)s->d_rampTable, (void *)s->d_rampCount, (void *)s->d_xyz, (void *)s->d_rgb})
         if (p) (void)hipFree(p);
     if (s->h_out) (void)hipHostFree(s->h_out);
@@ -434,6 +444,11 @@ static sgz_status vectorSetup(sgz_vector *s, const sgz_vector_config *cfg, bool 
             SGZ_HIP(hipMemcpy(s->d_state, &h, sizeof(h), hipMemcpyHostToDevice));
         }
     }
+    if (s->batch.channels != C) {             // a configure after sgz_vector_set_mix: the staging takes num_channels rows again
+        if (sgz_status st = s->batch.init(C, std::max<uint32_t>(s->maxBlock, 8192u)); st != SGZ_OK) return st;
+        if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+    }
+    s->mix.reset(C);                          // the routing returns to the identity over num_channels
     s->size = size;
     // handleFlagUpdates, Vectorscope.cpp:201-202: relaxed_atomic<float> coefficients
     s->envelopeCoeff = float(std::exp(-1.0 / (cfg->envelope_window * cfg->sample_rate)));
@@ -481,6 +496,7 @@ static sgz_status vectorSubmit(sgz_vector *s)
     prm.batchHost = fetchFrom; prm.batchFloats = floats;
     prm.st = s->d_state; prm.batch = d_batch; prm.numBlocks = s->batch.count; prm.channels = s->cfg.num_channels;
     for (uint32_t b = 0; b < s->batch.count; ++b) { prm.blockOff[b] = s->batch.off[b]; prm.blockLen[b] = s->batch.len[b]; }
+    if (s->mix.active) { prm.route = s->mix.d_route; prm.mixRows = s->mix.d_rows; prm.numSources = s->batch.channels; }
     prm.ring = s->d_ring; prm.size = s->size; prm.lanes = s->cfg.lanes; prm.envMode = s->cfg.envelope_mode;
     prm.envelope = s->envelopeCoeff; prm.pole0 = s->stereoCoeff; prm.pole1 = s->pole1;
     hipLaunchKernelGGL(vectorIngestKernel, dim3(1), dim3(256), 0, s->stream, prm);
@@ -516,7 +532,8 @@ sgz_status sgz_vector_push(sgz_vector *s, const float *const *planar, uint32_t n
     if (!s || !planar) return fail(SGZ_EINVAL, "null argument");
     std::unique_lock<std::mutex> lk(s->mu, std::try_to_lock);
     if (!lk.owns_lock()) { s->busy++; return SGZ_BUSY; }
-    if (num_channels != s->cfg.num_channels) return fail(SGZ_EINVAL, "num_channels differs from the configuration");
+    if (num_channels != s->mix.numSources)
+        return fail(SGZ_EINVAL, "num_channels differs from the configuration (or from the source count of sgz_vector_set_mix)");
     if (nsamples == 0) return SGZ_OK;
     if (nsamples > s->maxBlock) return fail(SGZ_EINVAL, "block longer than sgz_vector_config::max_block");
     // never waits: the render thread is submitting the open batch right now -> the block waits its turn in the host FIFO, like one the
@@ -526,6 +543,19 @@ sgz_status sgz_vector_push(sgz_vector *s, const float *const *planar, uint32_t n
     const sgz_status st = batchPush(side, planar, num_channels, nsamples, s->parkPushes.load(std::memory_order_relaxed));
     if (st == SGZ_BUSY) s->busy++;
     return st;
+}
+
+sgz_status sgz_vector_set_mix(sgz_vector *s, uint32_t num_sources, const uint8_t *matrix)
+{
+    if (!s || !matrix || num_sources == 0 || num_sources > MixRoute::kMax) return fail(SGZ_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lk(s->mu);                                // (a push meanwhile is refused with SGZ_BUSY: it never waits)
+    if (sgz_status sy = vectorSync(s); sy != SGZ_OK) return sy;           // the audio already taken goes through the old routing
+    SGZ_HIP(hipStreamSynchronize(s->stream));
+    if (s->batch.channels != num_sources) {                               // staging, pinned slot and FIFO for num_sources rows per block
+        if (sgz_status st = s->batch.init(num_sources, std::max<uint32_t>(s->maxBlock, 8192u)); st != SGZ_OK) return st;
+        if (!s->backlog.init(backlogFloats(num_sources, s->cfg.sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+    }
+    return s->mix.set(num_sources, s->cfg.num_channels, matrix, s->batch.slotSamples);
 }
 
 void *sgz_vector_stream(sgz_vector *s) { return s ? s->stream : nullptr; }
