@@ -26,6 +26,9 @@ extern "C" {
  *    SGZ_OPT_WIDE_GROUPS; the Oscilloscope / Vectorscope readers flush the host FIFO as well; SGZ_OPT_RESONATOR_SLAB bounds the sharded RSNT render (round 5; its own option SGZ_OPT_RESONATOR_SHARD_BOUND from round 6);
  * (5, later: sgz_scope_set_mix / sgz_vector_set_mix were added without a version change: no existing entry point or struct changed;
  *  a binding that needs them looks the symbols up.)
+ * (5, later: the Oscilloscope's time modes -- sgz_scope_config grew time_mode at its end (SGZ_TIME_*; 0 = the behaviour before), and
+ *  sgz_scope_set_tempo, sgz_scope_effective_window and sgz_scope_time_window were added.  The version number stays 5, which the
+ *  suite pins; a binding built against an older header passes the shorter sgz_scope_config and must not be mixed with this library.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -76,6 +79,8 @@ enum { SGZ_OSC_LEFT = 0, SGZ_OSC_RIGHT, SGZ_OSC_MID, SGZ_OSC_SIDE, SGZ_OSC_SEPAR
 
 /* OscilloscopeContent::TriggeringMode, Source/Oscilloscope/OscilloscopeParameters.h:50-58 */
 enum { SGZ_TRIG_NONE = 0, SGZ_TRIG_SPECTRAL, SGZ_TRIG_WINDOW, SGZ_TRIG_ENVELOPE_HOLD, SGZ_TRIG_ZERO_CROSSING };
+/* OscilloscopeContent::TimeMode, Source/Oscilloscope/OscilloscopeParameters.h:60: what sgz_scope_config::window_size counts */
+enum { SGZ_TIME_TIME = 0, SGZ_TIME_CYCLES, SGZ_TIME_BEATS };
 /* EnvelopeModes / SubSampleInterpolation, Source/Common/CommonSignalizer.h:72-85 */
 enum { SGZ_ENV_NONE = 0, SGZ_ENV_RMS, SGZ_ENV_PEAK_DECAY };
 enum { SGZ_SUBSAMPLE_NONE = 0, SGZ_SUBSAMPLE_RECTANGULAR, SGZ_SUBSAMPLE_LINEAR, SGZ_SUBSAMPLE_LANCZOS };
@@ -650,7 +655,8 @@ sgz_status sgz_peak_filter_device(const float *d_ch, size_t stride, uint32_t cha
  * (sgz_scope_set_transport), customTrigger, and the None / Rectangular interpolations of drawWavePlot. */
 typedef struct sgz_scope_config {
     double   sample_rate;
-    double   window_size;        /* state.effectiveWindowSize in samples (fractions allowed)                     */
+    double   window_size;        /* the window value (windowSize's transformed value): samples in SGZ_TIME_TIME (= state.effectiveWindowSize,
+                                    fractions allowed), periods of the fundamental in SGZ_TIME_CYCLES, beat division in SGZ_TIME_BEATS */
     uint32_t num_channels;       /* even, 2..64                                                                  */
     uint32_t trigger_mode;       /* SGZ_TRIG_* (Window: see sgz_scope_set_transport)                             */
     uint32_t channel_mode;       /* SGZ_OSC_* (OscChannels): trigger mix, envelope mix                           */
@@ -673,6 +679,21 @@ typedef struct sgz_scope_config {
     /* Spectral triggering on a frequency the user names (state.customTrigger / customTriggerFrequency, OscilloscopeDSP.inl:71-81) */
     uint32_t custom_trigger;
     double   custom_trigger_frequency;    /* Hz, in (0, sample_rate / 2)                                          */
+    /* state.timeMode (Oscilloscope.cpp:258): SGZ_TIME_*.  handleFlagUpdates' window step (Oscilloscope.cpp:291-307) runs at the top of
+     * every sgz_scope_analyse, which then works with that frame's effectiveWindowSize (sgz_scope_effective_window):
+     *   TIME    window_size samples.
+     *   CYCLES  window_size * cycleSamples + 1, cycleSamples of the PREVIOUS analyse (0 before the first: a window of 1 sample) --
+     *           computed on the device from the state the Spectral kernel keeps.  Spectral trigger only (checkAndInformInvalidCombinations,
+     *           OscilloscopeRendering.cpp:244-259); any other: SGZ_EINVAL.
+     *   BEATS   max(128, sample_rate * (60 / (max(10, bpm) * window_size))), bpm from sgz_scope_set_tempo (0 until the first call).
+     * CYCLES / BEATS: window_size > 0 and finite; the largest window the mode can reach (window_size * sample_rate / 5 + 1 -- the
+     * fundamental's 5 Hz floor, or the custom trigger frequency if lower --, resp. the 10 BPM floor's) must respect the 2^26 ring bound.
+     * With the Spectral trigger the ring is allocated once for that largest window, and a new window only moves the frame's ring_size
+     * (nothing is cleared).  BEATS with another trigger: a frame whose window differs from the last one's does what
+     * sgz_scope_configure with window_size = the new window does (setSettings' windowChanged; a changed ceil resizes and clears the
+     * rings), from inside sgz_scope_analyse.  (The reference's resize -- cpl's setStorageRequirements -- is not in its tree: UNVERIFIED
+     * vs cpl that it clears like this.) */
+    uint32_t time_mode;
 } sgz_scope_config;
 /* Oscilloscope::triggerState after analyseAndSetupState's first two steps (Oscilloscope.h:176-196) */
 typedef struct sgz_trigger_state {
@@ -687,7 +708,9 @@ typedef struct sgz_trigger_state {
 typedef struct sgz_scope sgz_scope;
 sgz_status sgz_scope_create(const sgz_scope_config *cfg, sgz_scope **out);
 void       sgz_scope_destroy(sgz_scope *s);
-/* handleFlagUpdates -> TriggeringProcessor::setSettings (Oscilloscope.cpp:310).  A changed ceil(window) resizes (and clears) the rings. */
+/* handleFlagUpdates -> TriggeringProcessor::setSettings (Oscilloscope.cpp:310).  A changed ceil(window) resizes (and clears) the rings;
+ * whenever the rings are reallocated, the trigger's buffered samples start over at the next block, even if another configure with the
+ * same ceil comes first. */
 sgz_status sgz_scope_configure(sgz_scope *s, const sgz_scope_config *cfg);
 /* onStreamAudio(ctx, float** buffer, numChannels, numSamples); the steady clock is the running count of pushed samples */
 sgz_status sgz_scope_push(sgz_scope *s, const float *const *planar, uint32_t num_channels, uint32_t nsamples);
@@ -715,6 +738,15 @@ sgz_status sgz_scope_set_option(sgz_scope *s, uint32_t option, uint64_t value);
  * playhead.getPositionInSamples() + numSamples of the newest block (OscilloscopeDSP.inl:706; OscilloscopeRendering.cpp:588-592,
  * :798-801).  Any thread, any time (one atomic store); ignored by the other modes. */
 sgz_status sgz_scope_set_transport(sgz_scope *s, int64_t position_in_samples);
+/* cs.bpm = playhead.getBPM() of the newest block (OscilloscopeDSP.inl:707), read by SGZ_TIME_BEATS at the next sgz_scope_analyse.
+ * Any thread, any time (one atomic store); 0 before the first call (the reference's `double bpm {}`), which the formula floors to 10. */
+sgz_status sgz_scope_set_tempo(sgz_scope *s, double bpm);
+/* state.effectiveWindowSize of the current frame (the window the vertex calls draw: time divisions and cursor readouts need it);
+ * before the first sgz_scope_analyse the mode's window with cycleSamples 0 and the tempo of the moment */
+double     sgz_scope_effective_window(const sgz_scope *s);
+/* handleFlagUpdates' window step on the host (Oscilloscope.cpp:293-307), no GPU: time_mode SGZ_TIME_*, value = window_size,
+ * cycle_samples read by CYCLES, bpm by BEATS.  (Time: value; an unknown mode: value.) */
+double     sgz_scope_time_window(uint32_t time_mode, double value, double sample_rate, double bpm, double cycle_samples);
 /* runPeakFilter once per rendered frame: delta_time = openGLDeltaTime(), lanes = the SIMD width whose tail the reference drops
  * (8 = AVX); *auto_gain = state.autoGain (optional; reading it waits for the kernel) */
 sgz_status sgz_scope_peak_filter(sgz_scope *s, double delta_time, uint32_t lanes, double *auto_gain);
@@ -726,7 +758,9 @@ sgz_status sgz_scope_gains(sgz_scope *s, double *envelope_gain, float *envelopes
  * phase) on the device ring; the state is read back (this call waits) and kept for the vertex calls.  Other modes: cycle_samples = 0
  * and the mode's fixed sample_offset, no GPU work.  The Spectral ring keeps the most the reference can ask for
  * ((size_t)(0.5 + sampleRate / 5 + ceil(window)) samples, the 5 Hz floor) and every read wraps in `ring_size`, the size
- * resizeAudioStorage gives the reference's ring for this frame (ChannelData.h:107-128), counted back from the newest sample. */
+ * resizeAudioStorage gives the reference's ring for this frame (ChannelData.h:107-128), counted back from the newest sample.
+ * SGZ_TIME_CYCLES / BEATS: the frame's window is set first (see sgz_scope_config::time_mode); vertex calls and
+ * sgz_scope_vertex_count use it until the next analyse. */
 sgz_status sgz_scope_analyse(sgz_scope *s, uint32_t evaluator, uint32_t channel, sgz_trigger_state *out);
 size_t     sgz_scope_vertex_count(const sgz_scope *s, const sgz_scope_view *view);
 /* One evaluator's line strip.  evaluator: SGZ_OSC_LEFT / RIGHT (channel `channel` / `channel` + 1) or SGZ_OSC_MID / SIDE (0.5 (l +- r)

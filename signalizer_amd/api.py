@@ -77,7 +77,11 @@ class ScopeConfig(C.Structure):
                 ("colours", (C.c_uint8 * 4) * 64),
                 ("trigger_hysteresis", C.c_double), ("trigger_phase_offset", C.c_double), ("colour_by_frequency", C.c_uint32),
                 ("frequency_colouring_blend", C.c_float), ("colour_smoothing_ms", C.c_double), ("band_colours", (C.c_float * 3) * 3),
-                ("custom_trigger", C.c_uint32), ("custom_trigger_frequency", C.c_double)]
+                ("custom_trigger", C.c_uint32), ("custom_trigger_frequency", C.c_double), ("time_mode", C.c_uint32)]
+
+
+# OscilloscopeContent::TimeMode (sgz_scope_config::time_mode): what window_size counts -- samples, periods, beat division
+TIME_TIME, TIME_CYCLES, TIME_BEATS = 0, 1, 2
 
 
 class TriggerState(C.Structure):
@@ -164,6 +168,7 @@ EXPORTS = [
     "sgz_line_graph_vertex_count", "sgz_line_graph_draws", "sgz_line_graph_vertices_device", "sgz_spectrum_render_line_vertices",
     "sgz_spectrum_set_view", "sgz_view_translation_rows", "sgz_view_translate_device",
     "sgz_scope_set_mix", "sgz_vector_set_mix",
+    "sgz_scope_set_tempo", "sgz_scope_effective_window", "sgz_scope_time_window",
 ]
 
 
@@ -220,6 +225,11 @@ def lib() -> C.CDLL:
     L.sgz_plan_get_resonator.argtypes = [vp, vp, vp, vp, vp]
     L.sgz_plan_reset_resonator.argtypes = [vp, vp]
     L.sgz_scope_set_transport.argtypes = [vp, C.c_int64]
+    L.sgz_scope_set_tempo.argtypes = [vp, C.c_double]
+    L.sgz_scope_effective_window.argtypes = [vp]
+    L.sgz_scope_effective_window.restype = C.c_double
+    L.sgz_scope_time_window.argtypes = [u32, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.sgz_scope_time_window.restype = C.c_double
     L.sgz_spectrogram_render_device.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
     L.sgz_spectrogram_render.argtypes = [C.POINTER(SpectrumConfig), vp, u32, sz, vp, vp, C.POINTER(Timing)]
     L.sgz_spectrogram_render_host.argtypes = [vp, vp, u32, sz, vp, vp, C.POINTER(Timing)]
@@ -676,6 +686,11 @@ def rotate_hue(rgb, amount: float) -> np.ndarray:
     return out
 
 
+def time_window(time_mode: int, value: float, sample_rate: float, bpm: float = 0.0, cycle_samples: float = 0.0) -> float:
+    """sgz_scope_time_window: handleFlagUpdates' effectiveWindowSize for a time mode, on the host"""
+    return lib().sgz_scope_time_window(int(time_mode), float(value), float(sample_rate), float(bpm), float(cycle_samples))
+
+
 class Scope:
     """sgz_scope_* handle: the Oscilloscope's audio-thread state machine in HBM + drawWavePlot vertices."""
 
@@ -737,6 +752,14 @@ class Scope:
     def set_transport(self, position_in_samples: int):
         """cs.transportPosition (TriggeringMode::Window)"""
         check(lib().sgz_scope_set_transport(self.h, C.c_int64(int(position_in_samples))))
+
+    def set_tempo(self, bpm: float):
+        """cs.bpm, the host playhead's tempo (TIME_BEATS reads it at the next analyse); any thread"""
+        check(lib().sgz_scope_set_tempo(self.h, float(bpm)))
+
+    def effective_window(self) -> float:
+        """state.effectiveWindowSize of the current frame (set by analyse in TIME_CYCLES / TIME_BEATS)"""
+        return lib().sgz_scope_effective_window(self.h)
 
     def front(self, channel: int):
         self.flush()

@@ -1083,6 +1083,7 @@ struct SpectralDev {
     BinRec record;                           // triggerState.record
     double fundamental, cycleSamples, sampleOffset, phase;
     unsigned long long ringSize;             // resizeAudioStorage's size (ChannelData.h:107-128): in = of the previous frame, out = of this one
+    double effectiveWindow;                  // state.effectiveWindowSize of the frame (out)
 };
 struct SpectralParams {
     SpectralDev *st;
@@ -1091,6 +1092,9 @@ struct SpectralParams {
     double windowSize, sampleRate, threshold, hysteresis, phaseOffsetDeg, quarterSemitone;
     double customFrequency;                  // state.customTrigger ? state.customTriggerFrequency : 0
     const double2 *tw;                       // [4096] exp(-2 pi i k / 8192)
+    double cycles;                           // SGZ_TIME_CYCLES: the window value (windowSize = cycles * the last frame's cycleSamples + 1); else 0
+    unsigned long long firstRing;            // the ring of the frame before the first one, if not st->ringSize (SGZ_TIME_BEATS); else 0
+    ScopeDev *trig;                          // Cycles / Beats: the TriggeringProcessor that setSettings gives the frame's window; else null
 };
 
 __device__ __forceinline__ double recOmega(const BinRec &r) { return double(r.index) + r.offset; }
@@ -1172,9 +1176,22 @@ __global__ void __launch_bounds__(1024) scopeSpectralKernel(const SpectralParams
     __shared__ double sRadians, sSampleDifference;
     __shared__ long sOffset2;
     const int tid = threadIdx.x;
+    __shared__ double sWindow;
     SpectralDev *st = prm.st;
-    const uint32_t cursor = *prm.d_cursor, cap = prm.cap, len = uint32_t(st->ringSize);
+    const uint32_t cursor = *prm.d_cursor, cap = prm.cap, len = uint32_t(prm.firstRing ? prm.firstRing : st->ringSize);
     constexpr uint32_t N = 8192;
+    // handleFlagUpdates' window step (Oscilloscope.cpp:293-307) for this frame -- Cycles: from the cycleSamples the last frame left,
+    // read before anything below overwrites it (every thread takes the same fp64 value: no host round trip)
+    if (tid == 0) {
+        const double w = prm.cycles > 0 ? prm.cycles * st->cycleSamples + 1 : prm.windowSize;
+        sWindow = w;
+        if (prm.trig) {                                    // setSettings (StreamPreprocessing.h:46-53; a change still pending stays so)
+            if (ceil(w) != ceil(prm.trig->windowSize)) prm.trig->windowChanged = 1;
+            prm.trig->windowSize = w;
+        }
+    }
+    __syncthreads();
+    const double windowSize = sWindow;
 
     // what calculateFundamentalPeriod leaves behind and what calculateTriggeringOffset derives from it first (:256-270)
     auto settle = [&](const BinRec &rec, double fundamental) {
@@ -1184,10 +1201,10 @@ __global__ void __launch_bounds__(1024) scopeSpectralKernel(const SpectralParams
         st->cycleSamples = cycleSamples;
         const double tau = 6.283185307179586476925286766559;
         const double radians = tau * recOmega(rec) / double(N);
-        const double offsetReal = fmax(double(N), prm.windowSize + cycleSamples);
+        const double offsetReal = fmax(double(N), windowSize + cycleSamples);
         const unsigned long long offset = (unsigned long long)ceil(offsetReal);
         sRadians = radians;
-        sSampleDifference = double(offset) - (prm.windowSize + cycleSamples);
+        sSampleDifference = double(offset) - (windowSize + cycleSamples);
         sOffset2 = long(offset);
     };
     if (prm.customFrequency > 0) {
@@ -1198,7 +1215,7 @@ __global__ void __launch_bounds__(1024) scopeSpectralKernel(const SpectralParams
         }
     } else {
     {   // transformBuffer[i] = eval.evaluateSampleInc() from -max(ceil(effectiveWindowSize), LookaheadSize) (:92-99)
-        const long offset = long(fmax(ceil(prm.windowSize), double(N)));
+        const long offset = long(fmax(ceil(windowSize), double(N)));
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const uint32_t i = uint32_t(tid) + 1024u * j;
@@ -1315,8 +1332,9 @@ __global__ void __launch_bounds__(1024) scopeSpectralKernel(const SpectralParams
         const double cycles = phase / tau;
         st->sampleOffset = cycles * prm.sampleRate / st->fundamental - 1;
         // resizeAudioStorage(Spectral) for this frame (ChannelData.h:113-117)
-        const unsigned long long need = (unsigned long long)(0.5 + st->cycleSamples + ceil(prm.windowSize));
+        const unsigned long long need = (unsigned long long)(0.5 + st->cycleSamples + ceil(windowSize));
         st->ringSize = need > N ? need : N;
+        st->effectiveWindow = windowSize;
     }
 }
 
@@ -1346,7 +1364,10 @@ struct sgz_scope {
     SpectralDev *d_spectral = nullptr;
     double2 *d_tw = nullptr;
     std::atomic<long long> transport{0};                 // cs.transportPosition (OscilloscopeDSP.inl:706): TriggeringMode::Window places the window by it
+    std::atomic<double> tempo{0.0};                       // cs.bpm (OscilloscopeDSP.inl:707): SGZ_TIME_BEATS reads it at the frame boundary
+    bool spectralFresh = false;                           // the Spectral state was reset and no frame has been analysed since
     sgz_trigger_state trig{};                             // triggerState as of the last sgz_scope_analyse (consumer thread)
+    double effWindow = 0;                                 // state.effectiveWindowSize of the current frame (consumer thread)
     // vertex output (consumer side)
     float *d_xyz = nullptr; uint32_t *d_rgba = nullptr; size_t vertexCap = 0;
     void *h_out = nullptr; size_t hOutBytes = 0;          // pinned
@@ -1367,6 +1388,28 @@ static void scopeFree(sgz_scope *s)
     if (s->h_out) (void)hipHostFree(s->h_out);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
+}
+
+// handleFlagUpdates' window step, Oscilloscope.cpp:293-307 (the Cycles branch also runs in scopeSpectralKernel, the same fp64 expression)
+static double timeWindow(uint32_t mode, double value, double sampleRate, double bpm, double cycleSamples)
+{
+    if (mode == SGZ_TIME_BEATS) return std::max(sampleRate * (60 / (std::max(10.0, bpm) * value)), 128.0);
+    if (mode == SGZ_TIME_CYCLES) return value * cycleSamples + 1;
+    return value;
+}
+
+// The largest effectiveWindowSize a configuration can reach, and (Spectral) the largest cycleSamples: what the rings are allocated for.
+// Cycles: cycleSamples <= sampleRate / 5 (the fundamental's floor, calculateFundamentalPeriod) or sampleRate / custom frequency;
+// Beats: the 10 BPM floor.  (The same operations as the per-frame values: a correctly rounded division and product are monotone.)
+static double scopeMaxCycleSamples(const sgz_scope_config *c)
+{
+    return c->sample_rate / (c->custom_trigger ? std::min(5.0, c->custom_trigger_frequency) : 5.0);
+}
+static double scopeMaxWindow(const sgz_scope_config *c)
+{
+    if (c->time_mode == SGZ_TIME_CYCLES) return timeWindow(SGZ_TIME_CYCLES, c->window_size, c->sample_rate, 0.0, scopeMaxCycleSamples(c));
+    if (c->time_mode == SGZ_TIME_BEATS) return timeWindow(SGZ_TIME_BEATS, c->window_size, c->sample_rate, 0.0, 0.0);
+    return c->window_size;
 }
 
 static sgz_status scopeValidate(const sgz_scope_config *c)
@@ -1396,23 +1439,45 @@ static sgz_status scopeValidate(const sgz_scope_config *c)
     if (!std::isfinite(c->trigger_threshold) || !std::isfinite(c->trigger_channel) || !(c->trigger_channel >= 1)) return fail(SGZ_EINVAL, "trigger");
     if (!std::isfinite(c->envelope_window) || c->envelope_window < 0) return fail(SGZ_EINVAL, "envelope_window");
     if (c->max_block > (1u << 17)) return fail(SGZ_EINVAL, "max_block above 131072 samples");
+    if (c->time_mode > SGZ_TIME_BEATS) return fail(SGZ_EINVAL, "time_mode");
+    if (c->time_mode != SGZ_TIME_TIME) {
+        // checkAndInformInvalidCombinations (OscilloscopeRendering.cpp:244-259) draws nothing but its message for these
+        if (c->time_mode == SGZ_TIME_CYCLES && c->trigger_mode != SGZ_TRIG_SPECTRAL)
+            return fail(SGZ_EINVAL, "Invalid combination of time and triggering modes (Cycles needs the Spectral trigger)");
+        if (!(c->window_size > 0)) return fail(SGZ_EINVAL, "window_size must be > 0 in the Cycles and Beats time modes");
+        const double maxWindow = scopeMaxWindow(c);
+        const double ring = c->trigger_mode == SGZ_TRIG_SPECTRAL ? scopeMaxCycleSamples(c) + maxWindow : maxWindow;
+        if (!(ring <= double(1u << 26))) return fail(SGZ_EINVAL, "ring too long for the largest window of the time mode");
+    }
     return SGZ_OK;
 }
 
 // (re)allocates everything for a configuration; the device state starts as make_unique<TriggeringProcessor>() leaves it (zeroes)
-// followed by setSettings(mode, window, threshold, hysteresis) (Oscilloscope.cpp:310)
-static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fresh)
+// followed by setSettings(mode, window, threshold, hysteresis) (Oscilloscope.cpp:310).
+// retime (SGZ_TIME_BEATS, another trigger than Spectral: sgz_scope_analyse found the frame's window changed): the same with
+// effectiveWindowSize = *retime and the rest of the configuration as it is -- the routing of sgz_scope_set_mix and the staging stay.
+static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fresh, const double *retime = nullptr)
 {
     sgz_status st = scopeValidate(cfg);
     if (st != SGZ_OK) return st;
     if (!s->stream) SGZ_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     SGZ_HIP(hipStreamSynchronize(s->stream));
     const uint32_t C = cfg->num_channels;
+    const bool spectral = cfg->trigger_mode == SGZ_TRIG_SPECTRAL;
+    // state.effectiveWindowSize (handleFlagUpdates' window step; Cycles: with the cycleSamples the Spectral state keeps, set below).
+    // A configure that leaves the time mode and its value as they are keeps the frame's window: the next analyse moves it.
+    const bool keepFrame = !fresh && !retime && cfg->time_mode != SGZ_TIME_TIME && cfg->time_mode == s->cfg.time_mode &&
+                           cfg->window_size == s->cfg.window_size && cfg->sample_rate == s->cfg.sample_rate;
+    double window = retime ? *retime : keepFrame ? s->effWindow
+                  : timeWindow(cfg->time_mode, cfg->window_size, cfg->sample_rate, s->tempo.load(std::memory_order_relaxed), 0.0);
     // ChannelData::resizeAudioStorage (ChannelData.h:107-128).  Spectral: the largest ring the reference can ask for (5 Hz floor of the
-    // fundamental); the reference's ring of the frame is cut out of it by the readers (sgz_trigger_state::ring_size)
-    uint32_t size = uint32_t(std::ceil(cfg->window_size + 1));                       // :121
-    if (cfg->trigger_mode == SGZ_TRIG_SPECTRAL)
+    // fundamental); the reference's ring of the frame is cut out of it by the readers (sgz_trigger_state::ring_size).  Cycles / Beats:
+    // for the largest window the time mode can reach, so that a new window never reallocates
+    uint32_t size = uint32_t(std::ceil(window + 1));                                  // :121
+    if (spectral && cfg->time_mode == SGZ_TIME_TIME)
         size = uint32_t(std::max<size_t>(size_t(0.5 + cfg->sample_rate / 5.0 + std::ceil(cfg->window_size)), 8192));
+    else if (spectral)
+        size = uint32_t(std::max<size_t>(size_t(0.5 + scopeMaxCycleSamples(cfg) + std::ceil(scopeMaxWindow(cfg))), 8192));
     uint32_t backCap = 1; while (backCap < size) backCap <<= 1;
     const uint32_t maxBlock = cfg->max_block ? cfg->max_block : 8192u;
     const bool colours = cfg->colour_by_frequency != 0;
@@ -1426,11 +1491,13 @@ static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fre
         SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_back), size_t(C) * backCap * sizeof(float)));
         SGZ_HIP(hipMemset(s->d_front, 0, size_t(C) * size * sizeof(float)));
         SGZ_HIP(hipMemset(s->d_back, 0, size_t(C) * backCap * sizeof(float)));
-        // a slot takes a whole batch: the blocks of one rendered frame and more (at least 8192 samples)
-        if ((st = s->batch.init(C, std::max<uint32_t>(maxBlock, 8192u))) != SGZ_OK) return st;
-        s->maxBlock = maxBlock;
-        // one second of audio may wait for the GPU (at least 32 blocks)
-        if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+        if (!retime) {
+            // a slot takes a whole batch: the blocks of one rendered frame and more (at least 8192 samples)
+            if ((st = s->batch.init(C, std::max<uint32_t>(maxBlock, 8192u))) != SGZ_OK) return st;
+            s->maxBlock = maxBlock;
+            // one second of audio may wait for the GPU (at least 32 blocks)
+            if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+        }
         if (!s->d_state) {
             SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_state), sizeof(ScopeDev)));
             SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_peaks), size_t(kPeakCap) * sizeof(unsigned long long)));
@@ -1453,11 +1520,13 @@ static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fre
         }
         s->col.maxBlock = maxBlock;
     }
-    if (s->batch.channels != C) {             // a configure after sgz_scope_set_mix: the staging takes num_channels rows again
-        if ((st = s->batch.init(C, std::max<uint32_t>(s->maxBlock, 8192u))) != SGZ_OK) return st;
-        if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+    if (!retime) {
+        if (s->batch.channels != C) {         // a configure after sgz_scope_set_mix: the staging takes num_channels rows again
+            if ((st = s->batch.init(C, std::max<uint32_t>(s->maxBlock, 8192u))) != SGZ_OK) return st;
+            if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+        }
+        s->mix.reset(C);                      // the routing returns to the identity over num_channels
     }
-    s->mix.reset(C);                          // the routing returns to the identity over num_channels
     if (colours) {
         // tuneCrossOver(300, 3000, sampleRate), tuneColourSmoothing(ms, sampleRate) (ChannelData.h:163-171).  cpl's designs are not in the
         // reference tree: the 3-band Linkwitz-Riley tree and the one-pole design are the published ones (oracle/scope_spectral.c)
@@ -1493,21 +1562,29 @@ static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fre
                                         2 * 8192 * int(sizeof(double))));
         }
         if (realloc || s->cfg.trigger_mode != SGZ_TRIG_SPECTRAL) {
+            if (cfg->time_mode == SGZ_TIME_CYCLES) window = timeWindow(SGZ_TIME_CYCLES, cfg->window_size, cfg->sample_rate, 0.0, 0.0);
             SpectralDev sd{};                                                             // Oscilloscope(): medianPos(), value-initialised filter
-            sd.ringSize = std::max<size_t>(size_t(0.5 + 0.0 + std::ceil(cfg->window_size)), 8192);
+            sd.ringSize = std::max<size_t>(size_t(0.5 + 0.0 + std::ceil(window)), 8192);
+            sd.effectiveWindow = window;
             SGZ_HIP(hipMemcpy(s->d_spectral, &sd, sizeof(sd), hipMemcpyHostToDevice));
             s->trig = sgz_trigger_state{};
             s->trig.ring_size = sd.ringSize;
+            s->spectralFresh = true;
+        } else if (cfg->time_mode == SGZ_TIME_CYCLES && !keepFrame) {
+            window = timeWindow(SGZ_TIME_CYCLES, cfg->window_size, cfg->sample_rate, 0.0, s->trig.cycle_samples);   // (the state kept)
         }
     } else {
         s->trig = sgz_trigger_state{};
         s->trig.ring_size = size;
         if (cfg->trigger_mode == SGZ_TRIG_ZERO_CROSSING || cfg->trigger_mode == SGZ_TRIG_ENVELOPE_HOLD)   // calculateTriggeringOffset :233-240
-            s->trig.sample_offset = (cfg->window_size * 0.5 - double(int(cfg->window_size * 0.5))) - 1.5;
+            s->trig.sample_offset = (window * 0.5 - double(int(window * 0.5))) - 1.5;
     }
-    // TriggeringProcessor::setSettings, StreamPreprocessing.h:46-53
-    h.windowChanged = std::ceil(cfg->window_size) != std::ceil(h.windowSize) ? 1 : 0;
-    h.windowSize = cfg->window_size;
+    // TriggeringProcessor::setSettings, StreamPreprocessing.h:46-53.  Rings reallocated here (or by an earlier call that no block has
+    // seen yet: the flag still pending) start over at written = 0, so update() must reset what processMutating has buffered -- the
+    // reference's assignment would drop a pending flag on a second call with the same ceil, and the next swap would then address
+    // bufferedSamples behind a ring that no longer holds them
+    h.windowChanged = (std::ceil(window) != std::ceil(h.windowSize) || (!fresh && (realloc || h.windowChanged))) ? 1 : 0;
+    h.windowSize = window;
     h.threshold = cfg->trigger_threshold;
     h.hysteresis = cfg->trigger_hysteresis;
     SGZ_HIP(hipMemcpy(s->d_state, &h, sizeof(h), hipMemcpyHostToDevice));
@@ -1521,6 +1598,7 @@ static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fre
     SGZ_HIP(hipStreamSynchronize(s->stream));                                               // (no ingest launch is reading the old copy)
     SGZ_HIP(hipMemcpy(s->d_col, &s->col, sizeof(ColourParams), hipMemcpyHostToDevice));
     s->cfg = *cfg;
+    s->effWindow = window;
     return SGZ_OK;
 }
 
@@ -1753,19 +1831,44 @@ sgz_status sgz_scope_set_transport(sgz_scope *s, int64_t position_in_samples)
     return SGZ_OK;
 }
 
+sgz_status sgz_scope_set_tempo(sgz_scope *s, double bpm)
+{
+    if (!s) return fail(SGZ_EINVAL, "null handle");
+    s->tempo.store(bpm, std::memory_order_relaxed);
+    return SGZ_OK;
+}
+
+double sgz_scope_effective_window(const sgz_scope *s) { return s ? s->effWindow : 0.0; }
+
+double sgz_scope_time_window(uint32_t time_mode, double value, double sample_rate, double bpm, double cycle_samples)
+{
+    return timeWindow(time_mode, value, sample_rate, bpm, cycle_samples);
+}
+
 size_t sgz_scope_vertex_count(const sgz_scope *s, const sgz_scope_view *view)
 {
     if (!s || !view || view->width < 2 || !(view->right > view->left)) return 0;
     sgz_scope_view v = *view;
-    v.window_size = s->cfg.window_size;
+    v.window_size = s->effWindow;
     return scopeVertexCount(v, s->cfg.interpolation, s->cfg.trigger_mode, s->trig.cycle_samples);
 }
 
 sgz_status sgz_scope_analyse(sgz_scope *s, uint32_t evaluator, uint32_t channel, sgz_trigger_state *out)
 {
     if (!s) return fail(SGZ_EINVAL, "null handle");
+    const bool spectral = s->cfg.trigger_mode == SGZ_TRIG_SPECTRAL;
+    if (s->cfg.time_mode == SGZ_TIME_BEATS && !spectral) {
+        // handleFlagUpdates at the frame boundary: a new tempo's window goes through setSettings and resizeAudioStorage as a
+        // configure with that window would (the blocks taken so far through the old one; a push meanwhile is refused with SGZ_BUSY)
+        const double window = timeWindow(SGZ_TIME_BEATS, s->cfg.window_size, s->cfg.sample_rate, s->tempo.load(std::memory_order_relaxed), 0.0);
+        if (window != s->effWindow) {
+            std::lock_guard<std::mutex> lk(s->mu);
+            if (sgz_status sy = scopeSync(s); sy != SGZ_OK) return sy;
+            if (sgz_status st = scopeSetup(s, &s->cfg, false, &window); st != SGZ_OK) return st;
+        }
+    }
     if (sgz_status sy = scopeSync(s); sy != SGZ_OK) return sy;            // (flush on read: the blocks that wait in the open batch come first)
-    if (s->cfg.trigger_mode == SGZ_TRIG_SPECTRAL) {
+    if (spectral) {
         const uint32_t C = s->cfg.num_channels;
         uint32_t chA, chB, evalMode;
         switch (evaluator) {
@@ -1781,7 +1884,15 @@ sgz_status sgz_scope_analyse(sgz_scope *s, uint32_t evaluator, uint32_t channel,
         prm.ringA = s->d_front + size_t(chA) * s->size; prm.ringB = s->d_front + size_t(chB) * s->size;
         prm.evalMode = evalMode; prm.cap = s->size;
         prm.d_cursor = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s->d_state) + offsetof(ScopeDev, frontCursor));
-        prm.windowSize = s->cfg.window_size; prm.sampleRate = s->cfg.sample_rate;
+        // the frame's window: Cycles computes it inside the kernel from the cycleSamples it keeps, Beats from the tempo of the moment
+        prm.windowSize = timeWindow(s->cfg.time_mode, s->cfg.window_size, s->cfg.sample_rate, s->tempo.load(std::memory_order_relaxed), 0.0);
+        prm.cycles = s->cfg.time_mode == SGZ_TIME_CYCLES ? s->cfg.window_size : 0.0;
+        // Beats: before the first frame the reference's ring is the one the first frame's window asks for (as a Time handle created
+        // with that window has it), whatever the tempo was when the state was set up
+        if (s->cfg.time_mode != SGZ_TIME_TIME) prm.trig = s->d_state;
+        if (s->cfg.time_mode == SGZ_TIME_BEATS && s->spectralFresh)
+            prm.firstRing = std::max<size_t>(size_t(0.5 + 0.0 + std::ceil(prm.windowSize)), 8192);
+        prm.sampleRate = s->cfg.sample_rate;
         prm.threshold = s->cfg.trigger_threshold; prm.hysteresis = s->cfg.trigger_hysteresis;
         prm.customFrequency = s->cfg.custom_trigger ? s->cfg.custom_trigger_frequency : 0.0;
         prm.phaseOffsetDeg = s->cfg.trigger_phase_offset;
@@ -1795,6 +1906,8 @@ sgz_status sgz_scope_analyse(sgz_scope *s, uint32_t evaluator, uint32_t channel,
         s->trig.record_index = h.record.index; s->trig.record_value = h.record.value; s->trig.record_offset = h.record.offset;
         s->trig.fundamental = h.fundamental; s->trig.cycle_samples = h.cycleSamples; s->trig.sample_offset = h.sampleOffset;
         s->trig.phase = h.phase; s->trig.ring_size = h.ringSize;
+        s->effWindow = h.effectiveWindow;
+        s->spectralFresh = false;
     }
     if (out) *out = s->trig;
     return SGZ_OK;
@@ -1832,7 +1945,7 @@ static sgz_status scopeVerticesInto(sgz_scope *s, const sgz_scope_view *view, ui
     StripSource src;
     if (sgz_status st = scopeStripSource(s, evaluator, channel, d_rgba != nullptr, &src); st != SGZ_OK) return st;
     sgz_scope_view v = *view;
-    v.window_size = s->cfg.window_size;                               // state.effectiveWindowSize is the stream's
+    v.window_size = s->effWindow;                                     // state.effectiveWindowSize is the stream's (this frame's)
     SGZ_HIP(launchScopeVertices(v, s->cfg.trigger_mode, s->cfg.interpolation, src.ringA, src.ringB, src.evalMode, uint32_t(s->trig.ring_size), s->size,
                                 reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s->d_state) + offsetof(ScopeDev, frontCursor)),
                                 s->trig.cycle_samples, s->trig.sample_offset, s->transport.load(std::memory_order_relaxed), src.key, src.colRing, d_xyz,
@@ -1850,7 +1963,7 @@ static sgz_status scopeVerticesPairInto(sgz_scope *s, const sgz_scope_view *view
     if (sgz_status st = scopeStripSource(s, evaluators[0], channels[0], d_rgba[0] != nullptr, &a); st != SGZ_OK) return st;
     if (sgz_status st = scopeStripSource(s, evaluators[1], channels[1], d_rgba[1] != nullptr, &b); st != SGZ_OK) return st;
     sgz_scope_view v = *view;
-    v.window_size = s->cfg.window_size;
+    v.window_size = s->effWindow;
     const float *ra[2] = {a.ringA, b.ringA}, *rb[2] = {a.ringB, b.ringB};
     const uint32_t em[2] = {a.evalMode, b.evalMode}, key[2] = {a.key, b.key};
     const uint32_t *cr[2] = {a.colRing, b.colRing};
@@ -1869,7 +1982,7 @@ sgz_status sgz_scope_vertices(sgz_scope *s, const sgz_scope_view *view, uint32_t
     if (!s || !view || !xyz || !count) return fail(SGZ_EINVAL, "null argument");
     if (view->width < 2 || !(view->right > view->left)) return fail(SGZ_EINVAL, "bad view");
     sgz_scope_view v = *view;
-    v.window_size = s->cfg.window_size;
+    v.window_size = s->effWindow;
     const size_t need = scopeVertexCount(v, s->cfg.interpolation, s->cfg.trigger_mode, s->trig.cycle_samples);
     if (need > *count) { *count = uint32_t(need); return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
     if (s->vertexCap < need) {
@@ -1907,7 +2020,7 @@ sgz_status sgz_scope_vertices_all(sgz_scope *s, const sgz_scope_view *view, uint
     if (!s || !view || !evaluators || !channels || !xyz || !counts) return fail(SGZ_EINVAL, "null argument");
     if (view->width < 2 || !(view->right > view->left)) return fail(SGZ_EINVAL, "bad view");
     sgz_scope_view v = *view;
-    v.window_size = s->cfg.window_size;
+    v.window_size = s->effWindow;
     const size_t need = scopeVertexCount(v, s->cfg.interpolation, s->cfg.trigger_mode, s->trig.cycle_samples);
     bool small = false, direct = true;
     for (uint32_t k = 0; k < items; ++k) {
@@ -1950,7 +2063,7 @@ sgz_status sgz_scope_vertices_device(sgz_scope *s, const sgz_scope_view *view, u
     if (view->width < 2 || !(view->right > view->left)) return fail(SGZ_EINVAL, "bad view");
     if ((reinterpret_cast<uintptr_t>(d_xyz) & 3) || (reinterpret_cast<uintptr_t>(d_rgba) & 3)) return fail(SGZ_EINVAL, "4-byte aligned buffers");
     sgz_scope_view v = *view;
-    v.window_size = s->cfg.window_size;
+    v.window_size = s->effWindow;
     const size_t need = scopeVertexCount(v, s->cfg.interpolation, s->cfg.trigger_mode, s->trig.cycle_samples);
     if (need > *count) { *count = uint32_t(need); return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
     size_t points = 0;
