@@ -290,6 +290,11 @@ void       sgz_export_free(void *d_ptr);
 /* Stage entry points (parity tests call these through the ABI; all DEVICE pointers, async on stream):
  *  bins:   per (frame,pair) the post-split magnitude array csf[0..N] of mapToLinearSpace
  *          (TransformDSP.inl:858-869 for Separate/MidSide; :553-560 mono modes) as float [N+1];
+ *          Separate / MidSide: csf[0] and csf[N] signed (Re Z[0] / 2, Im Z[0] / 2), the rest magnitudes.  The entries the reference
+ *          leaves complex are reported as magnitudes: Complex csf[0] = |Z[0]| / 2; Left / Right / Merge / Side csf[N/2] = |X[N/2]| / 2,
+ *          csf[N/2 + 1 .. N - 1] = |X[k]|, csf[N] = 0 -- except on the channel-split kernel's mono form (SGZ_PATH_CHANNEL_SPLIT in
+ *          those modes), which writes csf[0 .. N/2] only, with csf[N/2] = X[N/2] / 2 signed (real for a real signal, the value the
+ *          reference holds), and leaves csf[N/2 + 1 .. N] untouched (its pixels take conj X[k] from held entries instead);
  *  mapped: csp magnitudes after pixel mapping (TransformDSP.inl:871-985), float [frames][pairs][2][P];
  *  decay+colour from given mapped magnitudes (TransformDSP.inl:1299-1435 + SpectrumDSP.cpp:111-206).
  * SGZ_CH_PHASE (TransformDSP.inl:643-853, :1393-1432): the bins stay complex -- `bins` is float2 [N+1] (re, im) after

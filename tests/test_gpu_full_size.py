@@ -122,11 +122,14 @@ def _setup(gpu, name):
 
 def _poison_next(gpu, shape):
     """The next allocation of `shape` float32 comes back full of NaN instead of what the caching allocator last kept there: an output
-    entry the launch never writes (a unit the remap skips) is then non-finite, not a stale copy of a right answer."""
+    entry the launch never writes (a unit the remap skips) is then non-finite, not a stale copy of a right answer.  Returns the poisoned
+    block's address: a caller that allocates nothing else before the output can check that the output landed on it."""
     import torch
     torch.cuda.empty_cache()
     t = torch.full(shape, float("nan"), dtype=torch.float32, device=gpu)
+    ptr = t.data_ptr()
     del t
+    return ptr
 
 
 def _chain(oracle, plan, cfg, x, gpu, want_lines=False):

@@ -52,7 +52,8 @@ def _oracle_bins(po, p, x, frames, hop, W):
 
 
 @pytest.mark.parametrize("cfgname", ["cfg1", "cfg2small", "midside", "left", "w3000", "n32", "n1024", "n8192", "n65536", "w100",
-                                     "n65536pad", "n8192sep", "n65536midside", "n8192pad_left", "n65536complex"])
+                                     "n65536pad", "n8192sep", "n65536midside", "n8192pad_left", "n65536complex", "right", "side",
+                                     "n32768side"])
 def test_bins_tolerance(gpu, oracle, cfgname):
     po = oracle
     cfg = {
@@ -75,6 +76,10 @@ def test_bins_tolerance(gpu, oracle, cfgname):
                                                 window_type=config.WIN_BLACKMAN_HARRIS),
         "n8192pad_left": config.spectrum_config(window_size=5000, hop=1000, channel_mode=config.CH_LEFT),
         "n65536complex": config.spectrum_config(window_size=65536, hop=16384, channel_mode=config.CH_COMPLEX),
+        # the other two mono mixes: Right on the channel-split kernel (N = 16384), Side on the halves path and the channel-split kernel
+        "right": config.spectrum_config(channel_mode=config.CH_RIGHT, window_size=16384, hop=4096),
+        "side": config.spectrum_config(channel_mode=config.CH_SIDE, window_size=8192, hop=2048, window_type=config.WIN_BLACKMAN_HARRIS),
+        "n32768side": config.spectrum_config(channel_mode=config.CH_SIDE),
     }[cfgname]
     W, hop = cfg["window_size"], cfg["hop"]
     frames = 3
