@@ -433,7 +433,7 @@ void       sgz_peer_transport_release(void *ctx_storage);
  * frameQueue.popElement (SpectrumRendering.cpp:696-721) -- plus the two steps before the path: the additive
  * channel routing of MixGraphListener::deliver (Source/Common/MixGraphListener.cpp:247-334, sgz_spectrum_set_mix) and the audio
  * history ring, which lives in HBM (mirrored: the transform reads its window in place).  One producer thread (push) and one
- * consumer thread (pop_column, line_results, configure, set_view, set_mix, clear_state) may run concurrently.  push never waits for the GPU
+ * consumer thread (pop_column, line_results, configure, set_view, resize, set_mix, clear_state) may run concurrently.  push never waits for the GPU
  * and allocates nothing: when the GPU is several blocks behind, or a configure is in progress, it returns SGZ_BUSY and the block
  * is not taken.  At most 131072 samples per push.
  */
@@ -461,7 +461,7 @@ sgz_status sgz_spectrum_pop_column(sgz_spectrum *s, uint8_t *rgba /*4*P*/, uint3
  *                               EGL surfaceless context can be made current; on the MI355X boxes this library is developed on it cannot (no
  *                               display engine; the image has libGL / GLX, which needs an X server, but neither libEGL nor libgbm) and the
  *                               test skips with the loader's error: there the call is only known to fail with a status
- * A configure drops the binding (the image height is the axis size); sgz_spectrum_set_view keeps it. */
+ * A configure drops the binding (the image height is the axis size); sgz_spectrum_set_view keeps it; sgz_spectrum_resize moves it. */
 sgz_status sgz_spectrum_bind_image(sgz_spectrum *s, void *d_image, uint32_t columns, size_t pitch_bytes);
 sgz_status sgz_spectrum_create_image(sgz_spectrum *s, uint32_t columns, void **d_image, size_t *pitch_bytes, int *dmabuf_fd);
 sgz_status sgz_spectrum_bind_gl_buffer(sgz_spectrum *s, unsigned int gl_buffer, uint32_t columns, size_t pitch_bytes);
@@ -497,6 +497,50 @@ sgz_status sgz_view_translation_rows(uint32_t axis_points, double old_left, doub
                                      int32_t *src /*[P]*/, uint16_t *weight /*[P]*/);
 sgz_status sgz_view_translate_device(void *d_image, uint32_t columns, size_t pitch_bytes, uint32_t axis_points, double old_left,
                                      double old_right, double new_left, double new_right, void *stream);
+/* Resize (consumer thread): Spectrum::handleFlagUpdates' resized branch (Spectrum.cpp:503-515) -- what Spectrum::resized() (:156-159) and
+ * the Spectrum stretch knob (:333-336) cause: axis_points is the editor's height in COLOUR_SPECTRUM and its width in LINE_GRAPH (:445-451);
+ * the image is oglImage.resize(width / spectrumStretching, height, true), the columns it keeps.  axis_points is checked as
+ * sgz_spectrum_configure checks it (2 ... 2^20); d_image is NULL or satisfies sgz_spectrum_bind_image's rules (columns > 0,
+ * pitch >= 4 * columns, 4-byte aligned); a LINE_GRAPH handle takes NULL only.  SGZ_EINVAL leaves the handle exactly as it was; a handle
+ * bound to a GL buffer returns SGZ_EUNSUPPORTED, unchanged (the host unbinds it first).  Every other config field stays as configured.
+ *   kept:     the audio history in HBM and the frame cadence (strict-quirks framing included), the mix matrix, the handle options, the push
+ *             backlog, the stats counters and the view
+ *   replaced: both plans for the new size (map tables, slope map, tracker tables, resonator bank) and every buffer of the axis size, made
+ *             before push is held off: push returns SGZ_BUSY only while they are swapped in and warmed up
+ *   zeroed:   the viewChanged the resized branch sets (:532-575, :566) clears both graphs' decay states and results, also at an unchanged
+ *             size -- sgz_spectrum_line_results reads zeros until a frame computed after this call arrives.  RSNT: the resonators restart
+ *             at rest under the new bank (UNVERIFIED vs cpl: cpl's mapSystemHz is not in the tree)
+ *   queue:    at an unchanged axis size the queued columns stay and land in the new image at the next flush_columns or pop_column; at a
+ *             new size they are discarded, as queued frames of another size are skipped at render (SpectrumRendering.cpp:702), and not
+ *             counted in dropped_columns
+ *   image:    an image bound before and d_image given: the old content moves into d_image by sgz_image_resize_device's rule, and the
+ *             binding moves to d_image, caller-owned -- it may be the old image's own memory.  An old image of sgz_spectrum_create_image
+ *             is freed after the move (pass its own pointer to keep it: the new size must then fit its allocation; an exportable new
+ *             image comes from sgz_export_alloc).  No image bound before: d_image is bound as sgz_spectrum_bind_image binds it (content
+ *             untouched, x = 0).  d_image NULL: the binding is dropped, as sgz_spectrum_configure drops it.
+ * Waits for the GPU: not for the audio thread. */
+sgz_status sgz_spectrum_resize(sgz_spectrum *s, uint32_t axis_points, void *d_image, uint32_t columns, size_t pitch_bytes);
+/* oglImage.resize(width, height, true) of a spectrogram image (UNVERIFIED vs cpl: cpl's COpenGLImage::resize is not in the tree; this is
+ * the library's rule).  The old image has P0 rows, C0 columns and next-write column x0 (framePixelPosition); the new one P1 rows and C1
+ * columns.
+ *   rows (axis point i sits at the same view fraction i / (P - 1) at both sizes), for every new row i, in fp64:
+ *     r = (i * (P0 - 1.0)) / (P1 - 1.0);  j = floor(r);  w = floor((r - j) * 256 + 0.5);  w == 256 -> j += 1, w = 0;  src[i] = j, weight[i] = w
+ *     every byte c of a texel = (a_c * (256 - w) + b_c * w + 128) >> 8 with a from old row j, b from old row min(j + 1, P0 - 1)
+ *     (sgz_view_translate_device's blend; P0 == P1 copies the rows)
+ *   columns (time stays 1:1: a column is one frame): x1 = x0 mod C1; new column c has age a = (x1 - 1 - c) mod C1; a < min(C0, C1): its
+ *     source is old column (x0 - 1 - a) mod C0, otherwise src[c] = -1 and the texel is 0x00000000 (what sgz_spectrum_create_image holds).
+ *     The same size is the identity, x unchanged
+ * Texels beyond `columns` in a wider pitch are never written.
+ * sgz_image_resize_rows / sgz_image_resize_columns: the tables (host only, no GPU); SGZ_EINVAL for P outside 2 ... 2^20, no columns,
+ * C >= 2^31 or old_x >= old_columns.
+ * sgz_image_resize_device: the stage call, stateless: d_src [P0][src_pitch_bytes] into d_dst [P1][dst_pitch_bytes], both DEVICE; SGZ_EINVAL
+ * when their byte ranges overlap; *new_x (may be NULL) = x1.  Allocates its scratch and waits for the result on `stream` before it
+ * returns. */
+sgz_status sgz_image_resize_rows(uint32_t old_axis_points, uint32_t new_axis_points, int32_t *src /*[P1]*/, uint16_t *weight /*[P1]*/);
+sgz_status sgz_image_resize_columns(uint32_t old_columns, uint32_t old_x, uint32_t new_columns, int32_t *src /*[C1]*/, uint32_t *new_x);
+sgz_status sgz_image_resize_device(const void *d_src, uint32_t old_columns, size_t src_pitch_bytes, uint32_t old_axis_points, uint32_t old_x,
+                                   void *d_dst, uint32_t new_columns, size_t dst_pitch_bytes, uint32_t new_axis_points, uint32_t *new_x,
+                                   void *stream);
 /* lineGraphs[graph].getResults(P) for pair `pair`: float2 [P] (TransformPair.h:72-76).  COLOUR_SPECTRUM: the results of the newest
  * frame whose copy has reached the host (a pinned triple buffer the producer's stream fills: this call waits for nothing and never
  * touches the producer's stream); LINE_GRAPH: the results of the last sgz_spectrum_render_lines. */

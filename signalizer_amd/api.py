@@ -167,6 +167,7 @@ EXPORTS = [
     "sgz_vector_meters_from_filters", "sgz_vector_meters",
     "sgz_line_graph_vertex_count", "sgz_line_graph_draws", "sgz_line_graph_vertices_device", "sgz_spectrum_render_line_vertices",
     "sgz_spectrum_set_view", "sgz_view_translation_rows", "sgz_view_translate_device",
+    "sgz_spectrum_resize", "sgz_image_resize_rows", "sgz_image_resize_columns", "sgz_image_resize_device",
     "sgz_scope_set_mix", "sgz_vector_set_mix",
     "sgz_scope_set_tempo", "sgz_scope_effective_window", "sgz_scope_time_window",
 ]
@@ -324,6 +325,10 @@ def lib() -> C.CDLL:
     L.sgz_spectrum_set_view.argtypes = [vp, dbl, dbl]
     L.sgz_view_translation_rows.argtypes = [u32, dbl, dbl, dbl, dbl, vp, vp]
     L.sgz_view_translate_device.argtypes = [vp, u32, sz, u32, dbl, dbl, dbl, dbl, vp]
+    L.sgz_spectrum_resize.argtypes = [vp, u32, vp, u32, sz]
+    L.sgz_image_resize_rows.argtypes = [u32, u32, vp, vp]
+    L.sgz_image_resize_columns.argtypes = [u32, u32, u32, vp, C.POINTER(u32)]
+    L.sgz_image_resize_device.argtypes = [vp, u32, sz, u32, u32, vp, u32, sz, u32, C.POINTER(u32), vp]
     L.sgz_scope_num_points.argtypes = [C.POINTER(ScopeView)]
     L.sgz_scope_num_points.restype = sz
     L.sgz_scope_lanczos_device.argtypes = [C.POINTER(ScopeView), vp, sz, sz, u32, vp, vp]
@@ -424,6 +429,42 @@ def view_translate_device(image, columns: int, pitch_bytes: int, axis_points: in
     ptr = C.c_void_p(image.data_ptr()) if hasattr(image, "data_ptr") else C.c_void_p(int(image))
     check(lib().sgz_view_translate_device(ptr, columns, pitch_bytes, axis_points, old_left, old_right, new_left, new_right,
                                           C.c_void_p(stream) if stream else None))
+
+
+def _dev_ptr(image):
+    return C.c_void_p(image.data_ptr()) if hasattr(image, "data_ptr") else C.c_void_p(int(image)) if image else None
+
+
+def spectrum_resize(handle, axis_points: int, image=None, columns: int = 0, pitch_bytes: int = 0) -> None:
+    """sgz_spectrum_resize: a new axis size (the editor resized, or Spectrum stretch changed) keeping the audio history and cadence; the
+    bound image's content moves into `image` (a torch tensor or a device pointer, caller-owned), or the binding is dropped (None)"""
+    check(lib().sgz_spectrum_resize(handle, axis_points, _dev_ptr(image), columns, pitch_bytes))
+
+
+def image_resize_rows(old_axis_points: int, new_axis_points: int):
+    """the resize's row table (sgz_image_resize_rows; host only): (src int32 [P1], weight uint16 [P1])"""
+    src = np.zeros(new_axis_points, np.int32)
+    weight = np.zeros(new_axis_points, np.uint16)
+    check(lib().sgz_image_resize_rows(old_axis_points, new_axis_points, _np_ptr(src), _np_ptr(weight)))
+    return src, weight
+
+
+def image_resize_columns(old_columns: int, old_x: int, new_columns: int):
+    """the resize's column table (sgz_image_resize_columns; host only): (src int32 [C1], -1 = no source; the new write column x1)"""
+    src = np.zeros(new_columns, np.int32)
+    x1 = C.c_uint32(0)
+    check(lib().sgz_image_resize_columns(old_columns, old_x, new_columns, _np_ptr(src), C.byref(x1)))
+    return src, x1.value
+
+
+def image_resize_device(src, old_columns: int, src_pitch_bytes: int, old_axis_points: int, old_x: int, dst, new_columns: int,
+                        dst_pitch_bytes: int, new_axis_points: int, stream=None) -> int:
+    """sgz_image_resize_device: resample a DEVICE image [P0][src_pitch_bytes] of RGBA8 texels into another, [P1][dst_pitch_bytes] (torch
+    tensors or device pointers; their memory must not overlap); waits for the result.  Returns the new write column x1."""
+    x1 = C.c_uint32(0)
+    check(lib().sgz_image_resize_device(_dev_ptr(src), old_columns, src_pitch_bytes, old_axis_points, old_x, _dev_ptr(dst), new_columns,
+                                        dst_pitch_bytes, new_axis_points, C.byref(x1), C.c_void_p(stream) if stream else None))
+    return x1.value
 
 
 RT_OPT_STRICT_REFERENCE_QUIRKS, RT_OPT_AUDIO_HISTORY, RT_OPT_DEFER_SUBMIT, RT_OPT_PARK_PUSHES = 1, 2, 3, 4

@@ -48,6 +48,10 @@
 // Zoom / pan (sgz_spectrum_set_view, consumer thread; handleFlagUpdates' viewChanged branch, Spectrum.cpp:532-575): the new view's plans
 // are built outside cfgMu; under it the producer's stream is drained, the plans are swapped and warmed up, and the line graphs cleared.
 // The ring, the cadence, the column queue and the image binding stay; the bound image is translated afterwards (view_translate.hip).
+//
+// Resize (sgz_spectrum_resize, consumer thread; handleFlagUpdates' resized branch, Spectrum.cpp:503-515): as set_view, with a new axis size:
+// the plans and every buffer whose size is the axis size (AxisBuffers) are made outside cfgMu and swapped in under it.  The ring and the
+// cadence stay; the queued columns stay when the size does; the bound image is resampled into the new one afterwards (image_resize.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -156,10 +160,57 @@ struct sgz_spectrum {
     uint8_t *d_colsQ = nullptr;       // [kQueueDepth][P][4]
     hipStream_t outStream = nullptr;
     uint8_t *d_image = nullptr; size_t imgPitch = 0; uint32_t imgColumns = 0, imgX = 0;
-    bool imgOwned = false;
+    bool imgOwned = false; size_t imgOwnedBytes = 0;           // (create_image: the allocation's size)
     hipGraphicsResource *glResource = nullptr;
     float *d_viewScratch = nullptr; size_t viewScratchCap = 0;    // sgz_spectrum_set_view: the row table and the image copy it gathers from (floats)
 };
+
+// the buffers whose size is the axis size P: setup() allocates them with the rest, sgz_spectrum_resize replaces them.  h_cols / d_colsQ
+// are the column queue's slots (a resize to the same size keeps them, and the columns in them)
+struct AxisBuffers {
+    float *d_mapped = nullptr, *d_state = nullptr, *d_lines = nullptr, *d_linesBatch = nullptr, *d_lineMapped = nullptr;
+    uint8_t *d_colsBatch = nullptr;
+    float *h_lineOut = nullptr, *h_lines = nullptr;
+    uint8_t *h_cols = nullptr, *d_colsQ = nullptr;
+};
+
+static void freeAxisBuffers(AxisBuffers &b)
+{
+    for (float *q : {b.d_mapped, b.d_state, b.d_lines, b.d_linesBatch, b.d_lineMapped}) if (q) (void)hipFree(q);
+    for (uint8_t *q : {b.d_colsBatch, b.d_colsQ}) if (q) (void)hipFree(q);
+    for (void *q : {static_cast<void *>(b.h_lineOut), static_cast<void *>(b.h_lines), static_cast<void *>(b.h_cols)}) if (q) (void)hipHostFree(q);
+    b = AxisBuffers();
+}
+
+// allocates the buffers of a plan (`queue`: the column queue's slots too); on failure `b` holds what was allocated (freeAxisBuffers)
+static sgz_status allocAxisBuffers(const Plan &p, uint32_t maxFrames, bool queue, AxisBuffers &b)
+{
+    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_mapped), size_t(maxFrames) * p.C * p.sides * p.P * sizeof(float)));
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_state), stateN * sizeof(float)));
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_lines), stateN * sizeof(float)));
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_linesBatch), size_t(maxFrames) * stateN * sizeof(float)));
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_colsBatch), size_t(maxFrames) * p.P * 4));
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_lineMapped), size_t(p.C) * p.sides * p.P * sizeof(float)));
+    SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&b.h_lineOut), stateN * sizeof(float), hipHostMallocDefault));
+    SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&b.h_lines), size_t(sgz_spectrum::kLineSlots) * stateN * sizeof(float), hipHostMallocDefault));
+    std::memset(b.h_lineOut, 0, stateN * sizeof(float));
+    std::memset(b.h_lines, 0, size_t(sgz_spectrum::kLineSlots) * stateN * sizeof(float));
+    if (queue) {
+        SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&b.h_cols), size_t(kQueueDepth) * p.P * 4, hipHostMallocDefault));
+        SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_colsQ), size_t(kQueueDepth) * p.P * 4));
+    }
+    return SGZ_OK;
+}
+
+// the handle's axis buffers and `b` change places (`queue`: the column queue's slots too)
+static void exchangeAxisBuffers(sgz_spectrum *s, AxisBuffers &b, bool queue)
+{
+    std::swap(s->d_mapped, b.d_mapped); std::swap(s->d_state, b.d_state); std::swap(s->d_lines, b.d_lines);
+    std::swap(s->d_linesBatch, b.d_linesBatch); std::swap(s->d_lineMapped, b.d_lineMapped); std::swap(s->d_colsBatch, b.d_colsBatch);
+    std::swap(s->h_lineOut, b.h_lineOut); std::swap(s->h_lines, b.h_lines);
+    if (queue) { std::swap(s->h_cols, b.h_cols); std::swap(s->d_colsQ, b.d_colsQ); }
+}
 
 static void unbindImage(sgz_spectrum *s)
 {
@@ -170,7 +221,7 @@ static void unbindImage(sgz_spectrum *s)
     }
     if (s->imgOwned && s->d_image) (void)hipFree(s->d_image);
     if (s->d_viewScratch) { (void)hipFree(s->d_viewScratch); s->d_viewScratch = nullptr; s->viewScratchCap = 0; }
-    s->d_image = nullptr; s->imgOwned = false; s->imgColumns = 0; s->imgPitch = 0; s->imgX = 0;
+    s->d_image = nullptr; s->imgOwned = false; s->imgOwnedBytes = 0; s->imgColumns = 0; s->imgPitch = 0; s->imgX = 0;
 }
 
 static void freeHandle(sgz_spectrum *s)
@@ -179,19 +230,17 @@ static void freeHandle(sgz_spectrum *s)
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     s->stage.release();
     s->backlog.release();
-    for (float *p : {s->d_ring, s->d_mapped, s->d_state, s->d_lines, s->d_linesBatch, s->d_trackBins, s->d_strict, s->d_lineMapped}) if (p) (void)hipFree(p);
-    if (s->h_lineOut) (void)hipHostFree(s->h_lineOut);
-    if (s->h_lines) (void)hipHostFree(s->h_lines);
+    for (float *p : {s->d_ring, s->d_trackBins, s->d_strict}) if (p) (void)hipFree(p);
     if (s->d_verts) (void)hipFree(s->d_verts);
     if (s->h_verts) (void)hipHostFree(s->h_verts);
     for (auto &e : s->lineEvents) if (e) (void)hipEventDestroy(e);
     if (s->d_peak) (void)hipFree(s->d_peak);
     unbindImage(s);
+    AxisBuffers axis;
+    exchangeAxisBuffers(s, axis, true);
+    freeAxisBuffers(axis);
     if (s->outStream) (void)hipStreamDestroy(s->outStream);
-    if (s->d_colsQ) (void)hipFree(s->d_colsQ);
-    if (s->d_colsBatch) (void)hipFree(s->d_colsBatch);
     if (s->d_mix) (void)hipFree(s->d_mix);
-    if (s->h_cols) (void)hipHostFree(s->h_cols);
     for (auto &e : s->colEvents) if (e) (void)hipEventDestroy(e);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s->plan;
@@ -275,12 +324,10 @@ static sgz_status setup(sgz_spectrum *s, const sgz_spectrum_config *cfg)
     s->trackPlan = tp;
     Plan &p = *pl;
     const size_t nch = size_t(2) * p.C;
-    for (float **q : {&s->d_ring, &s->d_mapped, &s->d_state, &s->d_lines, &s->d_linesBatch, &s->d_trackBins, &s->d_strict, &s->d_lineMapped}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-    if (s->h_lineOut) { (void)hipHostFree(s->h_lineOut); s->h_lineOut = nullptr; }
-    if (s->h_lines) { (void)hipHostFree(s->h_lines); s->h_lines = nullptr; }
-    if (s->d_colsBatch) { (void)hipFree(s->d_colsBatch); s->d_colsBatch = nullptr; }
-    if (s->h_cols) { (void)hipHostFree(s->h_cols); s->h_cols = nullptr; }
-    if (s->d_colsQ) { (void)hipFree(s->d_colsQ); s->d_colsQ = nullptr; }
+    for (float **q : {&s->d_ring, &s->d_trackBins, &s->d_strict}) if (*q) { (void)hipFree(*q); *q = nullptr; }
+    AxisBuffers axis;
+    exchangeAxisBuffers(s, axis, true);
+    freeAxisBuffers(axis);
     unbindImage(s);                                        // the image's height is the axis size: a new configuration needs a new binding
     // a piece's frames read windows that end inside the piece: the ring must hold W + one piece (RSNT: a frame consumes the `hop`
     // samples that end with it) -- and a second piece of slack for the consumer thread's transforms of the newest window (see above)
@@ -292,23 +339,13 @@ static sgz_status setup(sgz_spectrum *s, const sgz_spectrum_config *cfg)
     s->sinceLast = 0;
     s->lineSeq.reset();
     s->deferredStat.store(0); s->waitingStat.store(0);
-    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_mapped), size_t(s->maxFrames) * p.C * p.sides * p.P * sizeof(float)));
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_state), stateN * sizeof(float)));
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_lines), stateN * sizeof(float)));
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_linesBatch), size_t(s->maxFrames) * stateN * sizeof(float)));
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_colsBatch), size_t(s->maxFrames) * p.P * 4));
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_lineMapped), size_t(p.C) * p.sides * p.P * sizeof(float)));
+    st = allocAxisBuffers(p, s->maxFrames, true, axis);
+    exchangeAxisBuffers(s, axis, true);                    // (a failure leaves the handle what was allocated: freeHandle takes it)
+    if (st != SGZ_OK) return st;
     SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_strict), nch * p.W * sizeof(float)));
-    SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_lineOut), stateN * sizeof(float), hipHostMallocDefault));
-    SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_lines), size_t(sgz_spectrum::kLineSlots) * stateN * sizeof(float), hipHostMallocDefault));
-    std::memset(s->h_lineOut, 0, stateN * sizeof(float));
-    std::memset(s->h_lines, 0, size_t(sgz_spectrum::kLineSlots) * stateN * sizeof(float));
     for (auto &e : s->lineEvents) if (!e) SGZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (p.cfg.channel_mode != SGZ_CH_PHASE && !isResonator(p)) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_trackBins), size_t(p.C) * (size_t(p.N) + 1) * sizeof(float)));
     if (!s->d_peak) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_peak), sizeof(sgz_peak)));
-    SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_cols), size_t(kQueueDepth) * p.P * 4, hipHostMallocDefault));
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_colsQ), size_t(kQueueDepth) * p.P * 4));
     if (!s->outStream) SGZ_HIP(hipStreamCreateWithFlags(&s->outStream, hipStreamNonBlocking));
     for (auto &e : s->colEvents) if (!e) SGZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     s->colQ.reset();
@@ -578,7 +615,7 @@ sgz_status sgz_spectrum_create_image(sgz_spectrum *s, uint32_t columns, void **d
     int fd = -1;
     if (e == hipSuccess && dmabuf_fd) e = hipMemGetHandleForAddressRange(&fd, img, bytes, hipMemRangeHandleTypeDmaBufFd, 0);
     if (e != hipSuccess) { (void)hipFree(img); return hipFail(e, "image allocation / dma-buf export"); }
-    s->d_image = img; s->imgOwned = true; s->imgColumns = columns; s->imgPitch = pitch; s->imgX = 0;
+    s->d_image = img; s->imgOwned = true; s->imgOwnedBytes = bytes; s->imgColumns = columns; s->imgPitch = pitch; s->imgX = 0;
     if (d_image) *d_image = img;
     *pitch_bytes = pitch;
     if (dmabuf_fd) *dmabuf_fd = fd;
@@ -717,6 +754,73 @@ sgz_status sgz_spectrum_set_view(sgz_spectrum *s, double view_left, double view_
     // computed with and land after this, as the frameQueue's do
     if (cfg.display_mode == SGZ_DISPLAY_COLOUR_SPECTRUM && (oldView[0] != view_left || oldView[1] != view_right) && (s->d_image || s->glResource))
         return translateBoundImage(s, oldView, newView);
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrum_resize(sgz_spectrum *s, uint32_t axis_points, void *d_image, uint32_t columns, size_t pitch_bytes)
+{
+    if (!s) return fail(SGZ_EINVAL, "null handle");
+    if (!validAxisPoints(axis_points)) return fail(SGZ_EINVAL, "2 <= axis_points <= 2^20");
+    if (s->glResource) return fail(SGZ_EUNSUPPORTED, "a GL buffer is bound: unbind it (sgz_spectrum_bind_image(s, NULL, 0, 0)) before a resize");
+    sgz_spectrum_config cfg = s->plan->cfg;                   // (only this thread replaces the plans)
+    const uint32_t P0 = s->plan->P, P1 = axis_points;
+    uint8_t *const newImage = static_cast<uint8_t *>(d_image);
+    const bool move = newImage && s->d_image;              // an image bound before and one given: its content moves over
+    if (newImage) {
+        if (cfg.display_mode == SGZ_DISPLAY_LINE_GRAPH) return fail(SGZ_EINVAL, "a LINE_GRAPH handle has no colour columns: d_image must be NULL");
+        if (!validImageLayout(newImage, columns, pitch_bytes)) return fail(SGZ_EINVAL, "image: columns > 0, pitch >= 4 * columns, 4-byte aligned");
+        if (move && !imageResizeFits(s->imgColumns, columns, P1)) return fail(SGZ_EINVAL, "image resize: more than 2^31 workgroups or columns");
+        if (s->imgOwned) {
+            // the library's own image (create_image) is freed after the move -- unless it is the new image itself, which must then fit it
+            const uintptr_t o = reinterpret_cast<uintptr_t>(s->d_image), n = reinterpret_cast<uintptr_t>(newImage);
+            if (n > o && n < o + s->imgOwnedBytes) return fail(SGZ_EINVAL, "d_image lies inside the library's own image but does not start it");
+            if (n == o && pitch_bytes * (P1 - 1u) + size_t(columns) * 4 > s->imgOwnedBytes)
+                return fail(SGZ_EINVAL, "d_image is the library's own image and too small for the new size");
+        }
+    }
+    cfg.axis_points = P1;
+    // the new size's plans (map tables, slope map, tracker tables, resonator bank) and buffers, made before the handle is held, so that
+    // push is refused only while they are swapped in; a same-size resize keeps the queue's slots and the columns in them
+    const bool sameSize = P1 == P0;
+    Plan *pl = nullptr, *tp = nullptr;
+    sgz_status st = makePlans(&cfg, &pl, &tp);
+    if (st != SGZ_OK) return st;
+    AxisBuffers axis;
+    st = allocAxisBuffers(*pl, s->maxFrames, !sameSize, axis);
+    if (st == SGZ_OK && move) st = ensureCap(&s->d_viewScratch, &s->viewScratchCap, imageResizeScratchFloats(P0, s->imgColumns, P1, columns));
+    if (st != SGZ_OK) { freeAxisBuffers(axis); delete pl; delete tp; return st; }
+    {
+        std::lock_guard<std::mutex> lk(s->cfgMu);
+        const hipError_t e = hipStreamSynchronize(s->stream);   // the old plans' launches are done; the ring, written / planned and the
+        if (e != hipSuccess) { freeAxisBuffers(axis); delete pl; delete tp; return hipFail(e, "hipStreamSynchronize"); }   // cadence stay
+        delete s->plan;
+        s->plan = pl;
+        delete s->trackPlan;
+        s->trackPlan = tp;
+        exchangeAxisBuffers(s, axis, !sameSize);
+        if (!sameSize) s->colQ.reset();         // frames of the old size are skipped at render (SpectrumRendering.cpp:702); not counted as dropped
+        // the warm-up leaves the decay states, the line results and the resonators at rest: the viewChanged the resized branch sets clears
+        // both line graphs (:566) -- the host's copies of the results start zeroed (allocAxisBuffers)
+        s->lineSeq.reset();
+        st = warmUp(s);
+    }
+    freeAxisBuffers(axis);                                     // (the old size's: nothing uses them any more)
+    if (st != SGZ_OK) { unbindImage(s); return st; }          // (an image of the old size must not take columns of the new one)
+    // oglImage.resize(width / spectrumStretching, height, true) (:503-515): the bound image's content moves into the new one
+    if (!newImage) {
+        unbindImage(s);
+        return SGZ_OK;
+    }
+    uint32_t x1 = 0;
+    if (move) {
+        if ((st = resizeImage(s->d_image, s->imgColumns, s->imgPitch, P0, s->imgX, newImage, columns, pitch_bytes, P1, &x1, &s->d_viewScratch,
+                              &s->viewScratchCap, s->outStream)) != SGZ_OK) {
+            unbindImage(s);
+            return st;
+        }
+        if (s->imgOwned && s->d_image != newImage) { (void)hipFree(s->d_image); s->imgOwned = false; s->imgOwnedBytes = 0; }
+    }
+    s->d_image = newImage; s->imgColumns = columns; s->imgPitch = pitch_bytes; s->imgX = x1;
     return SGZ_OK;
 }
 

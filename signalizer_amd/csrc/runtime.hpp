@@ -27,6 +27,15 @@ sgz_status launchLineGraphVertices(const float *d_lines, uint32_t pairs, uint32_
 bool validViewRect(double left, double right);
 sgz_status translateViewImage(uint8_t *image, uint32_t columns, size_t pitch, uint32_t P, const double oldView[2], const double newView[2],
                               float **scratch, size_t *scratchCap, hipStream_t stream);
+// image_resize.hip: the spectrogram image following a resize (sgz_image_resize_device; the spectrum handle's resize).  resizeImage waits for
+// its result; src and dst may share memory; scratch / scratchCap (floats, imageResizeScratchFloats of them) are grown as needed and stay
+// the caller's
+bool validAxisPoints(uint32_t P);
+bool validImageLayout(const void *d_image, uint32_t columns, size_t pitch);
+bool imageResizeFits(uint32_t C0, uint32_t C1, uint32_t P1);         // the kernel's grid and the int32 column table
+size_t imageResizeScratchFloats(uint32_t P0, uint32_t C0, uint32_t P1, uint32_t C1);
+sgz_status resizeImage(const uint8_t *src, uint32_t C0, size_t srcPitch, uint32_t P0, uint32_t x0, uint8_t *dst, uint32_t C1,
+                       size_t dstPitch, uint32_t P1, uint32_t *x1, float **scratch, size_t *scratchCap, hipStream_t stream);
 int numCUs();
 // K_A over `frames` frames (ideal STFT framing from d_planar); any of mapped/binsOut may be null
 // deferLate: the caller's next call is runDecayColour on the same d_mapped with only an image wanted -- a channel-split launch may then
