@@ -29,6 +29,8 @@ extern "C" {
  * (5, later: the Oscilloscope's time modes -- sgz_scope_config grew time_mode at its end (SGZ_TIME_*; 0 = the behaviour before), and
  *  sgz_scope_set_tempo, sgz_scope_effective_window and sgz_scope_time_window were added.  The version number stays 5, which the
  *  suite pins; a binding built against an older header passes the shorter sgz_scope_config and must not be mixed with this library.)
+ * (5, later: plan option SGZ_OPT_IMAGE_ONLY_SPLIT and the test hook sgz_stage_nyquist.  No existing entry point or struct changed and
+ *  the suite pins 5; a binding that sets the option on an older library gets SGZ_EINVAL, "unknown plan option", and looks the hook up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -208,6 +210,14 @@ sgz_status sgz_plan_reset_resonator(sgz_plan *plan, void *stream);
                                       anything is allocated or exchanged (round 6; rounds 4-5 read SGZ_OPT_RESONATOR_SLAB here) */
 #define SGZ_OPT_PIPELINED 8u          /* 1: other launches run beside this plan's (a lane of an sgz_render_queue sets it): K_A without the tunings of a launch
                                       that has the chip to itself (the second generation's delayed start, the wave priorities).  Same results. */
+#define SGZ_OPT_IMAGE_ONLY_SPLIT 9u   /* 1 (default): a render that asks for the image alone (sgz_spectrogram_render_device / sgz_spectrogram_render
+                                      without lines or state, sgz_render_queue) of a one-pair Separate plan at N = 32768 with an evaluated window, no
+                                      low pixels and the fused colour K_B transforms the pair's first channel only, and takes the second channel's
+                                      Nyquist bin -- the one number of it the image reads -- from workgroups that sum it without a transform.  Every
+                                      input sample is still read; the image is byte-identical.  0: both channels' transforms (for A/B and tests);
+                                      2 <= n <= 4096: as 1, with n frames per Nyquist workgroup instead of the automatic size (a render of fewer
+                                      frames uses its frame count); larger values are refused with SGZ_EINVAL.  Other renders, the stage calls
+                                      and the real-time handles are not affected. */
 sgz_status sgz_plan_set_option(sgz_plan *plan, uint32_t option, uint32_t value);
 /* The pixels whose filter taps or arg-max run reach a csf entry the reference leaves complex -- Complex: csf[0] = Z[0]/2
  * (TransformDSP.inl:993); Left / Right / Merge / Side: csf[N/2 .. N-1] (:553-560), reached by windows that wrap below bin 0 or
@@ -312,6 +322,12 @@ sgz_status sgz_stage_map_from_bins(sgz_plan *plan, const float *d_bins, size_t f
  * on every other plan this is sgz_stage_mapped. */
 sgz_status sgz_stage_mapped_dominant(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples,
                                      float *d_mapped /*[frames][pairs][2][P]*/, void *stream);
+/* Test hook of a channel-split pair plan: the two channels' Nyquist bins X_L[M], X_R[M] per (frame, pair) as K_A leaves them for
+ * csf[N/2], from the launch an image-only render runs (image_only != 0; SGZ_OPT_IMAGE_ONLY_SPLIT) or from the two-channel launch.
+ * *ny_frames (may be NULL): frames per Nyquist workgroup of that launch, 0 for the two-channel form; *low_pixels (may be NULL): the
+ * plan's pixels whose taps reach over bin 0 into the other channel (such plans keep the two-channel form). */
+sgz_status sgz_stage_nyquist(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, int image_only,
+                             float *d_ny /*[frames][pairs][2]*/, uint32_t *ny_frames, uint32_t *low_pixels, void *stream);
 /* d_rgba and d_lines may both be NULL: a state-only pass that just advances d_state over `frames` frames (what the
  * multi-GPU carry exchange below needs from every rank before the real pass). */
 sgz_status sgz_stage_decay_colour(sgz_plan *plan, const float *d_mapped, size_t frames,

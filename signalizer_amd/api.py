@@ -149,7 +149,7 @@ EXPORTS = [
     "sgz_plan_get_mapped_frequencies", "sgz_plan_get_slope_map", "sgz_plan_get_colour_ratios",
     "sgz_plan_get_colour_table", "sgz_rotate_hue_rgb8", "sgz_num_frames", "sgz_plan_num_frames", "sgz_plan_get_resonator", "sgz_plan_reset_resonator",
     "sgz_render_queue_create", "sgz_render_queue_destroy", "sgz_render_queue_submit", "sgz_render_queue_wait", "sgz_render_queue_join", "sgz_render_queue_set_option", "sgz_render_queue_distinct_lanes",
-    "sgz_spectrogram_render_device", "sgz_spectrogram_render", "sgz_stage_bins", "sgz_stage_mapped", "sgz_stage_mapped_dominant", "sgz_plan_set_option",
+    "sgz_spectrogram_render_device", "sgz_spectrogram_render", "sgz_stage_bins", "sgz_stage_mapped", "sgz_stage_mapped_dominant", "sgz_stage_nyquist", "sgz_plan_set_option",
     "sgz_stage_map_from_bins", "sgz_stage_track_peak", "sgz_spectrum_track_peak", "sgz_track_peak_lines", "sgz_spectrum_track_peak_lines", "sgz_stage_decay_colour", "sgz_stage_decay_scan", "sgz_stage_decay_emit", "sgz_stage_logf", "sgz_stage_finish_pixel", "sgz_decay_fold_carry", "sgz_comm_unique_id", "sgz_comm_create", "sgz_comm_destroy", "sgz_shard_layout", "sgz_spectrogram_render_sharded_on",
     "sgz_spectrogram_render_sharded", "sgz_peer_group_create", "sgz_peer_group_destroy", "sgz_peer_transport", "sgz_peer_transport_release",
     "sgz_spectrum_create", "sgz_spectrum_destroy", "sgz_spectrum_configure", "sgz_spectrum_push",
@@ -237,6 +237,7 @@ def lib() -> C.CDLL:
     L.sgz_stage_bins.argtypes = [vp, vp, sz, sz, vp, vp]
     L.sgz_stage_mapped.argtypes = [vp, vp, sz, sz, vp, vp]
     L.sgz_stage_mapped_dominant.argtypes = [vp, vp, sz, sz, vp, vp]
+    L.sgz_stage_nyquist.argtypes = [vp, vp, sz, sz, C.c_int, vp, C.POINTER(u32), C.POINTER(u32), vp]
     L.sgz_stage_map_from_bins.argtypes = [vp, vp, sz, vp, vp]
     L.sgz_stage_decay_colour.argtypes = [vp, vp, sz, vp, vp, vp, vp]
     L.sgz_decay_fold_carry.argtypes = [vp, vp, vp, u32, u32, vp, vp]
@@ -471,6 +472,7 @@ RT_OPT_STRICT_REFERENCE_QUIRKS, RT_OPT_AUDIO_HISTORY, RT_OPT_DEFER_SUBMIT, RT_OP
 OPT_CHANNEL_SPLIT, OPT_FUSED_COLOUR, OPT_FETCH_WINDOW, OPT_MATRIX_RESONATOR, OPT_RESONATOR_SLAB, OPT_WIDE_GROUPS = 1, 2, 3, 4, 5, 6   # OPT_WIDE_GROUPS: retired, accepted and ignored (sgz.h)
 OPT_RESONATOR_SHARD_BOUND = 7
 OPT_PIPELINED = 8
+OPT_IMAGE_ONLY_SPLIT = 9
 
 
 class Plan:
@@ -622,6 +624,17 @@ class Plan:
         check(lib().sgz_stage_mapped(self.h, planar.data_ptr(), planar.stride(0), S, out.data_ptr(),
                                      torch.cuda.current_stream().cuda_stream))
         return out
+
+    def stage_nyquist(self, planar, image_only: bool):
+        """sgz_stage_nyquist: (ny [F][C][2] float32 on the device, frames per Nyquist workgroup (0: two-channel launch), low pixels)"""
+        import torch
+        S = planar.shape[1]
+        F = self.num_frames(S)
+        out = torch.empty((F, self.C, 2), dtype=torch.float32, device=planar.device)
+        nyf, low = C.c_uint32(0), C.c_uint32(0)
+        check(lib().sgz_stage_nyquist(self.h, planar.data_ptr(), planar.stride(0), S, 1 if image_only else 0, out.data_ptr(),
+                                      C.byref(nyf), C.byref(low), torch.cuda.current_stream().cuda_stream))
+        return out, nyf.value, low.value
 
     def stage_map_from_bins(self, bins):
         import torch

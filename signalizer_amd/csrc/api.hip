@@ -307,7 +307,8 @@ sgz_status ensureSecondStream(Plan &p)
 }
 
 sgz_status runStft(Plan &p, const float *d_planar, size_t chStride, long frames, float *d_mapped,
-                          float *d_binsOut, const float *d_binsIn, hipStream_t stream, unsigned long long *d_phaseClock, bool deferLate)
+                          float *d_binsOut, const float *d_binsIn, hipStream_t stream, unsigned long long *d_phaseClock, bool deferLate,
+                          bool imageOnly)
 {
     TraceRange range("sgz::runStft (K_A)");
     p.lateDeferred = nullptr; p.lateFrames = 0;
@@ -359,6 +360,16 @@ sgz_status runStft(Plan &p, const float *d_planar, size_t chStride, long frames,
         if (deferLate && !p.realMono && d_mapped && !d_binsOut && p.realLowCount[0] + p.realLowCount[1] == 0) { rp.lateInNext = 1u; p.lateDeferred = d_mapped; p.lateFrames = frames; }
         rp.roundSize = uint32_t(numCUs()) * (p.N == 16384 ? 4u : p.N == 32768 ? 2u : 1u);   // workgroups a CU holds at once
         rp.pipelined = p.optPipelined ? 1u : 0u;
+        // image-only renders (spectrum_real.hip nyquistUnit): side 0's channel workgroups and Nyquist workgroups of F frames each, F such
+        // that both together fill one round of workgroup slots where the channel workgroups leave room (SGZ_OPT_IMAGE_ONLY_SPLIT >= 2: F itself)
+        // (never more than the frame count: the kernel divides by it)
+        if (imageOnly && rp.lateInNext && p.optImageOnlySplit && p.realSplit && p.cfg.channel_mode == SGZ_CH_SEPARATE && p.N == 32768 &&
+            rp.winPhase && p.C == 1) {
+            const long room = long(rp.roundSize) - tasks;
+            const long want = p.optImageOnlySplit >= 2 ? long(p.optImageOnlySplit) : room > 0 ? std::min<long>(8, std::max<long>(1, (tasks + room - 1) / room)) : 4;
+            rp.nyFrames = uint32_t(std::min<long>(want, frames));
+        }
+        p.lastNyFrames = rp.nyFrames;
 #ifdef SGZ_DEBUG
         rp.phaseClock = d_phaseClock; rp.clkUnit = g_ablate >> 16;
 #endif
@@ -625,6 +636,9 @@ sgz_status sgz_plan_set_option(sgz_plan *plan, uint32_t option, uint32_t value)
     case SGZ_OPT_RESONATOR_SLAB: p.optResonatorSlab = value; return SGZ_OK;
     case SGZ_OPT_RESONATOR_SHARD_BOUND: p.optResonatorShardBound = value; return SGZ_OK;
     case SGZ_OPT_PIPELINED: p.optPipelined = value != 0; return SGZ_OK;
+    case SGZ_OPT_IMAGE_ONLY_SPLIT:
+        if (value > kMaxNyFrames) return fail(SGZ_EINVAL, "SGZ_OPT_IMAGE_ONLY_SPLIT: 0, 1 or 2 .. 4096 frames per Nyquist workgroup");
+        p.optImageOnlySplit = value; return SGZ_OK;
     case SGZ_OPT_WIDE_GROUPS: return SGZ_OK;                   // retired (sgz.h): accepted, changes nothing
     default: return fail(SGZ_EINVAL, "unknown plan option");
     }
@@ -740,7 +754,12 @@ sgz_status sgz_spectrogram_render_device(sgz_plan *plan, const float *d_planar, 
     // RSNT: a render without a carried decay state is a job of its own -- the resonators start from rest too (TransformPair.h:183);
     // with d_state the caller continues a stream and the resonators (kept in the plan) continue with it
     if (!d_state && (st = resetResonator(p, s)) != SGZ_OK) return st;
-    if ((st = runStft(p, d_planar, channel_stride, frames, p.d_mapped, nullptr, nullptr, s, nullptr, /*deferLate=*/true)) != SGZ_OK) return st;
+    // an image and nothing else, whose K_B is the fused colour kernel (it reads side 0 of the pair and settles the late pixels itself):
+    // K_A may skip what only side 1 of the pair would feed (runStft, imageOnly)
+    DecayParams colour{};
+    colour.rgba = d_rgba; colour.C = p.C; colour.numChunks = uint32_t((frames + 7) / 8);
+    const bool imageOnly = d_rgba && !d_lines && !d_state && p.optFusedColour && p.cfg.channel_mode != SGZ_CH_PHASE && decayColourFusedApplies(colour);
+    if ((st = runStft(p, d_planar, channel_stride, frames, p.d_mapped, nullptr, nullptr, s, nullptr, /*deferLate=*/true, imageOnly)) != SGZ_OK) return st;
     return runDecayColour(p, p.d_mapped, frames, d_rgba, d_lines, d_state, s);
 }
 
@@ -1006,6 +1025,29 @@ sgz_status sgz_stage_mapped_dominant(sgz_plan *plan, const float *d_planar, size
     st = runStft(p, d_planar, channel_stride, frames, d_mapped, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream), nullptr, /*deferLate=*/true);
     p.lateDeferred = nullptr;                        // (nobody completes them: see sgz.h)
     return st;
+}
+
+sgz_status sgz_stage_nyquist(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, int image_only, float *d_ny,
+                             uint32_t *ny_frames, uint32_t *low_pixels, void *stream)
+{
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    if (!p.optChannelSplit || !p.realSplit) return fail(SGZ_EUNSUPPORTED, "sgz_stage_nyquist: not a channel-split pair plan");
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    if (!d_planar || !d_ny) return fail(SGZ_EINVAL, "null buffer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if ((st = ensureCap(&p.d_mapped, &p.mappedCap, size_t(frames) * p.C * p.sides * p.P)) != SGZ_OK) return st;
+    // the launch of an image-only render (image_only != 0: sgz_spectrogram_render_device's choice for a plan that qualifies) or of the
+    // two-channel form; its late pixels are left to nobody
+    st = runStft(p, d_planar, channel_stride, frames, p.d_mapped, nullptr, nullptr, s, nullptr, /*deferLate=*/true, image_only != 0);
+    p.lateDeferred = nullptr; p.lateFrames = 0;
+    if (st != SGZ_OK) return st;
+    SGZ_HIP(hipMemcpyAsync(d_ny, p.d_ny, size_t(frames) * p.C * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (ny_frames) *ny_frames = p.lastNyFrames;
+    if (low_pixels) *low_pixels = p.realLowCount[0] + p.realLowCount[1];
+    return SGZ_OK;
 }
 
 sgz_status sgz_stage_map_from_bins(sgz_plan *plan, const float *d_bins, size_t frames, float *d_mapped, void *stream)

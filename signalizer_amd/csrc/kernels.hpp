@@ -83,10 +83,15 @@ struct RealParams {
     uint32_t lowCount[2];
     unsigned long long *phaseClock; uint32_t clkUnit;   // -DSGZ_DEBUG builds: shader clocks of workgroup `clkUnit` at the phase boundaries
     uint32_t roundSize;       // workgroups that run concurrently, for the XCD-aware order
+    // image-only render (N = 32768, Separate, window evaluated, C == 1, late pixels left to K_B, no low pixels): 0 -- both channels' workgroups;
+    // n -- side 0's channel workgroups only, and one Nyquist workgroup per n frames of a pair that leaves the right channel's X_R[M] in ny
+    // (spectrum_real.hip nyquistUnit).  Nothing else of side 1 is computed: mapped, nyBest and low of side 1 are not written.
+    uint32_t nyFrames;
     uint32_t pipelined;       // 1: other launches run beside this one (sgz_render_queue): the second generation's delayed start and the wave priorities --
                               // tuned for a launch that has the chip to itself -- are left out (tools/pipeline_depth.py: 25.5 -> 22.0 us per render at depth 3)
 };
 constexpr int kLowBins = 24;
+constexpr uint32_t kMaxNyFrames = 4096;   // SGZ_OPT_IMAGE_ONLY_SPLIT's largest forced size (runStft also caps it at the launch's frame count)
 hipError_t launchStftReal(const RealParams &prm, uint32_t N, hipStream_t stream);
 // the late pixels of a launch that ran with lateInNext = 1 (pairs), as a launch of its own
 hipError_t launchRealLate(const RealParams &prm, uint32_t N, hipStream_t stream);

@@ -123,6 +123,8 @@ struct Plan {
     // sgz_plan_set_option
     bool optChannelSplit = true, optFusedColour = true, optFetchWindow = false;
     bool optPipelined = false;          // the plan is a lane of an sgz_render_queue of depth >= 2 (RealParams::pipelined)
+    uint32_t optImageOnlySplit = 1;     // image-only renders skip side 1's transform (0: never; 1: automatic size; n >= 2: n frames per Nyquist workgroup)
+    uint32_t lastNyFrames = 0;          // RealParams::nyFrames of the last channel-split launch (0: both channels' workgroups) -- sgz_stage_nyquist
     uint32_t optFusedPixels = 4;        // pixels per workgroup of the fused colour K_B (4, 8, 16): SGZ_OPT_FUSED_COLOUR = 1 / 8 / 16
     int optMatrixResonator = 2;        // 0: vector ALUs, 1: bf16 matrix cores (three-part split; opt-in: on MI355X its instruction stream disturbs FFT
                                        //    kernels running beside it -- rocFFT's too --, NOTES.md round 6), 2: fp32 matrix cores (default since round 6)

@@ -40,6 +40,9 @@ int numCUs();
 // K_A over `frames` frames (ideal STFT framing from d_planar); any of mapped/binsOut may be null
 // deferLate: the caller's next call is runDecayColour on the same d_mapped with only an image wanted -- a channel-split launch may then
 // leave its late pixels (late_fix.hpp) to K_B's fused kernel instead of a launch of its own (runDecayColour checks Plan::lateDeferred)
+// imageOnly: nothing but that image is read from d_mapped (side 0 of every pair, and both channels' Nyquist bins through the late pixels):
+// an eligible channel-split launch may skip side 1's transform (RealParams::nyFrames).  Set by the caller, never inferred from deferLate
+// (the real-time handle defers its late pixels too, and keeps both sides).
 // the plan's second stream and the fork / join events that tie it to the caller's (created on first use, destroyed with the plan)
 sgz_status ensureSecondStream(Plan &p);
 sgz_status resetResonator(Plan &p, hipStream_t stream);
@@ -53,7 +56,7 @@ sgz_status runResonatorJoin(Plan &p, long frames, float *d_mapped, const float *
                             float *d_carry, hipStream_t stream);
 sgz_status runStft(Plan &p, const float *d_planar, size_t chStride, long frames, float *d_mapped,
                    float *d_binsOut, const float *d_binsIn, hipStream_t stream, unsigned long long *d_phaseClock = nullptr,
-                   bool deferLate = false);
+                   bool deferLate = false, bool imageOnly = false);
 #ifdef SGZ_DEBUG
 extern uint32_t g_ablate;   // debug only (tools/ablate.py)
 #endif

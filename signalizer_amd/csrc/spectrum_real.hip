@@ -106,6 +106,25 @@ __device__ __forceinline__ float2 rotateTwiddle(const float2 w, const float cm1,
     return float2{r.x, r.y};
 }
 
+// The evaluated window (Hann / Hamming, periodic) on one pair of rows of a column: w = p0 + t on row j, p0 - t on row j + R1 / 2 (half a turn
+// further), t = p1 cos(theta) the column's phase (pc: p1 cos, ps: p1 sin of the (even, odd) samples' angles) turned by a32 32nds of a turn.
+// Shared by the channel workgroups and the Nyquist workgroups of an image-only launch, which must window bit for bit alike.
+__device__ __forceinline__ void windowPairCos(v2 &lo, v2 &hi, const int a32, const v2 pc, const v2 ps, const v2 p0)
+{
+    v2 t = pc;
+    if (a32 != 0) {
+        const v2 k = v2{cos32(a32), sin32(a32)};
+        v2 m;
+        asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(m) : "v"(ps), "s"(k));                   // ps sin
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(t) : "v"(pc), "s"(k), "v"(m));   // pc cos - ps sin
+    }
+    v2 wa, wb;
+    asm("v_pk_add_f32 %0, %1, %2" : "=v"(wa) : "v"(t), "s"(p0));
+    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[1,0] neg_hi:[1,0]" : "=v"(wb) : "v"(t), "s"(p0));
+    lo = lo * wa;
+    hi = hi * wb;
+}
+
 // Everything behind the barrier that completes a side's magnitudes in LDS: the test hook that writes them out, the pair exchange,
 // the pixel map (chunk_map.hpp) and the settlement of the pixels that need both channels.  Shared by the transform kernel and by
 // realMapFromBinsKernel (sgz_stage_map_from_bins: the same code maps injected bins, so "the mapping is bit-exact given the bins"
@@ -151,15 +170,85 @@ __device__ __forceinline__ void realMapSettle(const P &prm, float *lds, const in
     }
 }
 
+// ---- Image-only renders (MIX = 4).  The image reads side 0 of every pair alone (K_B's colour kernel: LineMain); of side 1 it needs one
+// number, the right channel's Nyquist bin X_R[M], which enters csf[N/2] = |X_L[M] + i X_R[M]| / 2 for side 0's top pixels (late_fix.hpp).
+// So such a launch runs the channel workgroups of side 0 only and, behind them, NYQUIST workgroups that each leave X_R[M] = 2 (Re Z[0] -
+// Im Z[0]) of `nyFrames` consecutive frames of one pair without a transform: Z[0], the DC term of the packed x w / 2, summed in exactly
+// the order passes 1 - 3 of a channel workgroup produce it -- pass 1's radix-16 tree per column (its twiddle row q1 = 0 is skipped), pass
+// 2's radix-32 tree over c_hi (TWFUSE: no product in front of exchange 2), pass 3's fused first level with table row 0 and its remaining
+// levels over c_lo -- with the same window code and the same butterflies, whose outputs other than Z[0] the compiler drops.  Every
+// sample of the right channel is still read.  Light: a frame is one pass over its samples, two barriers, 32 lanes' and then one thread's
+// 32-point tree.  Nobody waits for them inside the launch: K_B reads ny behind the launch boundary, as it does for the channel workgroups.
+// Bit-exactness rests on the two roles compiling the shared arithmetic alike: the builds contract floating-point expressions across
+// statements (-ffp-contract=fast), and the window's product meets pass 1's first add as one fma in both -- a change to either role, or to
+// the compiler, may fuse differently.  sgz_stage_nyquist and tests/test_gpu_image_only_split.py compare the ny words of both launch forms.
+template <int LR1>
+__device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, const uint32_t light, const int tid)
+{
+    constexpr int LR = 5, R = 32, R1 = 1 << LR1, RR = R * R;
+    static_assert(LR1 == 4, "the Nyquist workgroups mirror the two-columns-per-thread form (N = 32768)");
+    const uint32_t F = prm.nyFrames, perPair = uint32_t(prm.frames) / F + (uint32_t(prm.frames) % F != 0u);     // (runStft: 1 <= F <= frames)
+    const uint32_t pair = light / perPair, f0 = (light - pair * perPair) * F;
+    const uint32_t f1 = f0 + F < uint32_t(prm.frames) ? f0 + F : uint32_t(prm.frames);
+    const float *X0 = prm.planar + size_t(2 * pair + 1) * prm.chStride;          // the pair's second channel
+    const uint32_t lane16 = uint32_t(tid) * 16u;
+    const float4 ph[2] = {ldg(prm.winPhase, lane16 * 2u), ldg(prm.winPhase + 1, lane16 * 2u)};     // columns 2 tid, 2 tid + 1
+    const v2 p0 = v2{prm.winP0, prm.winP0};
+    v2 *lds2 = reinterpret_cast<v2 *>(lds);                                     // [1024] column sums, then [32] pass-2 sums
+    for (uint32_t f = f0; f < f1; ++f) {
+        const float *X = X0 + size_t(f) * prm.hop;
+        // one column at a time (16 registers of samples, not the channel workgroup's 32: the tail of this role shares the kernel's
+        // register allocation with the channel workgroups, whose form is at the 128-register limit)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            v2 c[R1];
+#pragma unroll
+            for (int j = 0; j < R1; ++j) c[j] = ldgPinned<v2>(X, uint32_t(RR * j) * 8u + 8u * u, lane16);
+            const v2 pc = v2{ph[u].x, ph[u].y}, ps = v2{ph[u].z, ph[u].w};
+#pragma unroll
+            for (int j = 0; j < R1 / 2; ++j) windowPairCos(c[j], c[j + R1 / 2], j * (32 / R1), pc, ps, p0);
+            ditPacked<LR1, 0>(c);                                             // pass 1 (pass1Columns): Z1[column][q1 = 0] at register 0
+            lds2[2 * tid + u] = c[0];
+        }
+        __syncthreads();
+        if (tid < R) {                                                         // pass 2, c_lo = tid: c_hi = 0 .. 31 in natural order
+            v2 s[R];
+#pragma unroll
+            for (int h = 0; h < R; ++h) s[h] = lds2[tid + R * h];
+            ditPacked<LR, 0>(s);
+            lds2[RR + tid] = s[0];
+        }
+        __syncthreads();
+        if (tid == 0) {                                                        // pass 3, q2 = 0: register r is c_lo = r
+            v2 s[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) s[r] = lds2[RR + r];
+            const float4 *tab = prm.tw2Full;                                   // row q2 = 0 (the channel workgroups read its LDS copy)
+#pragma unroll
+            for (int i = 0; i < R / 4; ++i) {
+                const float4 wa = tab[i], wb = tab[i + R / 4];
+                if (i == 0) bflyPackedFusedTw<true>(s[0], s[R / 2], v2{1.f, 0.f}, v2{wb.x, wb.y});
+                else bflyPackedFusedTw<false>(s[2 * i], s[2 * i + R / 2], v2{wa.x, wa.y}, v2{wb.x, wb.y});
+                bflyPackedFusedTw<false>(s[2 * i + 1], s[2 * i + 1 + R / 2], v2{wa.z, wa.w}, v2{wb.z, wb.w});
+            }
+            ditPacked<LR, 0, R, 2>(s);
+            prm.ny[((size_t(f) * prm.C + pair) << 1) | 1u] = 2.f * (s[0].x - s[0].y);   // as the channel workgroup stores it (the transform runs on x w / 2)
+        }
+    }
+}
+
 // MONO: SpectrumChannels Left / Right / Merge / Side -- ONE real signal per (frame, pair) (the reference transforms it as a complex frame
 // with a zero imaginary part, TransformDSP.inl:59-135): one workgroup per task, no pair exchange.  csf[0] = |X[0]| / 2 and
 // csf[N/2] = X[N/2] / 2 (:547-552; the latter stays signed: the reference leaves it complex, and X[N/2] of a real signal is real).
-template <int LR1, bool WCOS, int MIX = 0>                 // MIX: 0 Separate (two channel workgroups), 1 mono Left / Right, 2 MidSide (two workgroups on mid and side), 3 mono Merge / Side
+// MIX: 0 Separate (two channel workgroups), 1 mono Left / Right, 2 MidSide (two workgroups on mid and side), 3 mono Merge / Side,
+// 4 Separate for an image-only render (side 0's channel workgroups, then the Nyquist workgroups: nyquistUnit above)
+template <int LR1, bool WCOS, int MIX = 0>
 __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealParams launchPrm)
 {
     constexpr int LR = 5, R = 32, R1 = 1 << LR1, T = R1 * R, RR = R * R, M = R1 * RR, N = 2 * M, U = R / R1;
     constexpr bool MONO = MIX == 1 || MIX == 3;
-    constexpr bool mixed = MIX >= 2;                    // the signal is (l +- r) / 2: compile-time, the second channel's loads cost registers
+    constexpr bool SIDE0 = MIX == 4;
+    constexpr bool mixed = MIX == 2 || MIX == 3;        // the signal is (l +- r) / 2: compile-time, the second channel's loads cost registers
     constexpr int PADSTRIDE = chunkPos(T);              // padded distance between k and k + T
     constexpr int ROW = R + 2, TILE = R * ROW;            // exchange 2: rows of 32 + 2 floats (8-byte aligned rows: the transposed reads are ds_read_b64, free of bank conflicts)
     constexpr int XFLOATS = realXFloats(M);             // this side's |X| array (padded) -- the map's tile and chunk maxima follow it
@@ -175,16 +264,25 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     // wave requests the first half of the NEXT unit's rows as soon as its own magnitudes are out of the registers those rows land in --
     // the requests are served while the slower waves still transform and the map runs; the second half follows at the top of the loop.
     constexpr bool WALK = LR1 == 5 && MIX == 0 && WCOS;
-    const uint32_t totalUnits = WALK ? uint32_t(launchPrm.frames) * launchPrm.C * 2u : gridDim.x;
+    // channel workgroups of the launch: SIDE0 -- one per (frame, pair), the Nyquist workgroups behind them leave at once
+    const uint32_t heavyUnits = SIDE0 ? uint32_t(launchPrm.frames) * launchPrm.C : gridDim.x;
+    if constexpr (SIDE0) {
+        // (thread index opaque: nothing the role derives from it is shared with -- hoisted into -- the channel workgroups' code)
+        if (blockIdx.x >= heavyUnits) { nyquistUnit<LR1>(launchPrm, lds, blockIdx.x - heavyUnits, opaque(tid0)); return; }
+    }
+    const uint32_t totalUnits = WALK ? uint32_t(launchPrm.frames) * launchPrm.C * 2u : heavyUnits;
     uint32_t walkIndex = blockIdx.x;
-    UnitId uid = unitOfIndex<MONO>(launchPrm, walkIndex, totalUnits);     // (frame, pair, channel) or (frame, pair); real_common.hpp
+    // (frame, pair, channel) or (frame, pair); real_common.hpp.  SIDE0: the (frame, pair) order of the mono modes, side 0, the same `self`
+    UnitId uid = unitOfIndex<MONO || SIDE0>(launchPrm, walkIndex, totalUnits);
     [[maybe_unused]] bool firstUnit = true;
     // Wave priorities for a launch of two full dispatch generations and a partial third (cfg2: 696 workgroups on 256 CUs, two resident
     // per CU).  tools/unit_trace.py: workgroups b and b + #CUs share a CU, the third generation starts in the slots the first frees
     // and the launch ends when IT ends; its workgroups share their CU with second-generation ones that have ~10 us of slack.  Third
     // generation at priority 3, first at 2, second at 1: -0.6 us of a 28.7 us launch at the sustained clock (tools/ab3.sh; every
     // assignment with the last generation on top measures within 0.1 us of this one, 3 / 0 / 3 half the gain, 3 / 0 / 0 a loss).
-    // Longer launches are left alone.  (A speed assumption only.)
+    // Longer launches are left alone.  (A speed assumption only.)  Both rules count the whole grid, an image-only launch's Nyquist workgroups
+    // (SIDE0) included: counting channel workgroups only measured 0.1 - 0.2 us slower at 480 and 500 frames, where the two differ (cfg2's 464
+    // workgroups take neither rule either way).
     if constexpr (LR1 == 4) {
         const uint32_t cus = launchPrm.roundSize >> 1;
         // The two workgroups that share a CU from the first clock of a launch (b and b + #CUs) would run IN PHASE -- both fetching, both in
@@ -368,18 +466,7 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
                         c[i2] = v2{c[i2].x * (prm.winP0 - te), c[i2].y * (prm.winP0 - to)};
                         continue;
                     }
-                    v2 t = pc;
-                    if (a32 != 0) {
-                        const v2 k = v2{cos32(a32), sin32(a32)};
-                        v2 m;
-                        asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(m) : "v"(ps), "s"(k));                   // ps sin
-                        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(t) : "v"(pc), "s"(k), "v"(m));   // pc cos - ps sin
-                    }
-                    v2 wa, wb;
-                    asm("v_pk_add_f32 %0, %1, %2" : "=v"(wa) : "v"(t), "s"(p0));
-                    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[1,0] neg_hi:[1,0]" : "=v"(wb) : "v"(t), "s"(p0));
-                    c[i] = c[i] * wa;
-                    c[i2] = c[i2] * wb;
+                    windowPairCos(c[i], c[i2], a32, pc, ps, p0);
                 }
             }
         } else {
@@ -855,13 +942,18 @@ hipError_t launchFinishPixel(const float *x, float *y, size_t n, hipStream_t str
 hipError_t launchStftReal(const RealParams &prm, uint32_t N, hipStream_t stream)
 {
     const bool mono = prm.mode != SGZ_CH_SEPARATE && prm.mode != SGZ_CH_MIDSIDE;
-    const long units = prm.frames * long(prm.C) * (mono ? 1 : 2);
+    // image-only form (MIX = 4): side 0's channel workgroups, then ceil(frames / nyFrames) Nyquist workgroups per pair.  Only where K_B
+    // settles the late pixels from side 0's magnitudes and both channels' Nyquist bins (lateInNext, no low pixels) and nothing else of side 1 is read.
+    const bool side0 = prm.nyFrames && N == 32768 && prm.mode == SGZ_CH_SEPARATE && prm.winPhase && prm.lateInNext && prm.mapped && !prm.binsOut &&
+                       !prm.binsIn && prm.lowCount[0] + prm.lowCount[1] == 0;
+    const long tasks = prm.frames * long(prm.C);
+    const long units = side0 ? tasks + long(prm.C) * ((prm.frames + prm.nyFrames - 1) / prm.nyFrames) : tasks * (mono ? 1 : 2);
     if (units <= 0) return hipSuccess;
     const uint32_t M = N / 2, T = M / 32;
     const uint32_t maxSlots = std::max(prm.chunkSlots[0], prm.chunkSlots[1]);
     // magnitudes, then the map's tile / chunk maxima (the same floats hold column 0's scratch during the recombination), then (mono) the complex entries
     const size_t ldsBytes = (size_t(realXFloats(int(M))) + realExtraFloats(maxSlots, T, N >= 32768) + 64 + (mono ? 2 * kSpecBins : 0)) * 4;
-    static size_t granted[27][64] = {};
+    static size_t granted[28][64] = {};
     const bool wcos = prm.winPhase != nullptr;
     if (prm.binsIn) {
         if (mono) return hipErrorNotSupported;
@@ -910,7 +1002,8 @@ hipError_t launchStftReal(const RealParams &prm, uint32_t N, hipStream_t stream)
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
-    if (N == 32768) e = wcos ? go(&stftRealKernel<4, true>, 0, 512, 80 * 1024) : go(&stftRealKernel<4, false>, 1, 512, 80 * 1024);
+    if (side0) e = go(&stftRealKernel<4, true, 4>, 27, 512, 80 * 1024);
+    else if (N == 32768) e = wcos ? go(&stftRealKernel<4, true>, 0, 512, 80 * 1024) : go(&stftRealKernel<4, false>, 1, 512, 80 * 1024);
     else if (N == 16384) e = wcos ? go(&stftRealKernel<3, true>, 4, 256, 40 * 1024) : go(&stftRealKernel<3, false>, 5, 256, 40 * 1024);
     else if (N == 65536) e = wcos ? go(&stftRealKernel<5, true>, 2, 1024, 160 * 1024) : go(&stftRealKernel<5, false>, 3, 1024, 160 * 1024);
     else return hipErrorNotSupported;
