@@ -31,6 +31,8 @@ extern "C" {
  *  suite pins; a binding built against an older header passes the shorter sgz_scope_config and must not be mixed with this library.)
  * (5, later: plan option SGZ_OPT_IMAGE_ONLY_SPLIT and the test hook sgz_stage_nyquist.  No existing entry point or struct changed and
  *  the suite pins 5; a binding that sets the option on an older library gets SGZ_EINVAL, "unknown plan option", and looks the hook up.)
+ * (5, later: sgz_spectrum_update, sgz_spectrum_update_effects (SGZ_UPDATE_*) and the stage call sgz_ring_resize_device.  No existing
+ *  entry point or struct changed and the suite pins 5; a binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -449,7 +451,7 @@ void       sgz_peer_transport_release(void *ctx_storage);
  * frameQueue.popElement (SpectrumRendering.cpp:696-721) -- plus the two steps before the path: the additive
  * channel routing of MixGraphListener::deliver (Source/Common/MixGraphListener.cpp:247-334, sgz_spectrum_set_mix) and the audio
  * history ring, which lives in HBM (mirrored: the transform reads its window in place).  One producer thread (push) and one
- * consumer thread (pop_column, line_results, configure, set_view, resize, set_mix, clear_state) may run concurrently.  push never waits for the GPU
+ * consumer thread (pop_column, line_results, configure, set_view, resize, update, set_mix, clear_state) may run concurrently.  push never waits for the GPU
  * and allocates nothing: when the GPU is several blocks behind, or a configure is in progress, it returns SGZ_BUSY and the block
  * is not taken.  At most 131072 samples per push.
  */
@@ -484,8 +486,8 @@ sgz_status sgz_spectrum_bind_gl_buffer(sgz_spectrum *s, unsigned int gl_buffer, 
 sgz_status sgz_spectrum_flush_columns(sgz_spectrum *s, uint32_t *first_column, uint32_t *count);
 /* Zoom / pan (consumer thread): Spectrum::handleFlagUpdates' viewChanged branch (Spectrum.cpp:532-575) for a change of viewLeft /
  * viewRight only -- what mouseWheelMove / mouseDrag (:172-290) cause.  The view is checked as sgz_spectrum_configure checks it (finite,
- * 0 <= left < right <= 1); SGZ_EINVAL leaves the handle exactly as it was.  Every other field stays as configured (a change of scaling,
- * min_log_freq, size or mode is a sgz_spectrum_configure).
+ * 0 <= left < right <= 1); SGZ_EINVAL leaves the handle exactly as it was.  Every other field stays as configured (a change of scaling or
+ * min_log_freq is a sgz_spectrum_update, of size a sgz_spectrum_resize, of display mode a sgz_spectrum_configure).
  *   kept:     the audio history in HBM and the frame cadence (a frame fires where it would have; strict-quirks framing included), the mix
  *             matrix, the handle options, the column queue, the image binding and framePixelPosition
  *   replaced: remapFrequencies and what hangs on it (map tables, slope map, tracker tables, resonator tuning), built before push is held
@@ -557,6 +559,64 @@ sgz_status sgz_image_resize_columns(uint32_t old_columns, uint32_t old_x, uint32
 sgz_status sgz_image_resize_device(const void *d_src, uint32_t old_columns, size_t src_pitch_bytes, uint32_t old_axis_points, uint32_t old_x,
                                    void *d_dst, uint32_t new_columns, size_t dst_pitch_bytes, uint32_t new_axis_points, uint32_t *new_x,
                                    void *stream);
+/* Every other setting change (consumer thread): the rest of Spectrum::handleFlagUpdates (Spectrum.cpp:351-616), where each parameter
+ * raises a flag that rebuilds only what depends on it (parameterChangedRT, :291-343).  cfg is a complete configuration; it is compared
+ * field by field with the handle's current one and the union of what the changed fields' flags do is applied.
+ *   refused, the handle left exactly as it was:
+ *     SGZ_EINVAL        what sgz_spectrum_create refuses; a change of axis_points (that is sgz_spectrum_resize); a window_size above an
+ *                       explicitly set SGZ_RT_OPT_AUDIO_HISTORY
+ *     SGZ_EUNSUPPORTED  a change of sample_rate or num_pairs (a new stream) or of display_mode (a new display): sgz_spectrum_configure
+ *   a configuration equal to the current one: SGZ_OK, nothing touched, no plan built, push never held off.
+ *   kept, always:  the audio history in HBM and the frame cadence (processedSamplesSinceLastFrame), the mix matrix, the handle options, the
+ *                  push backlog, the stats counters, the image binding and framePixelPosition, and the queued columns (the axis size is
+ *                  unchanged: they land later as they were computed)
+ *   replaced:      both plans, and the buffers whose size depends on a changed field (frames per piece = 16384 / hop + 1, the sides of the
+ *                  channel mode, the tracker's [pairs][N + 1] bins, strict mode's [2 pairs][W] frame), made before push is held off: push
+ *                  returns SGZ_BUSY only while they are swapped in and warmed up.  Blocks waiting in the push FIFO are transformed under
+ *                  the new configuration.
+ *   per field (sgz_spectrum_update_effects says which apply):
+ *     low_db, high_db, clip_db, colours, ratios, pole, slope_a / slope_b, bin_interp (assigned every call, :365-413; slopeMapChanged,
+ *         :578-581): nothing zeroed -- the decay states, the line results and the RSNT resonators continue
+ *     window_type, window_symmetry, window_alpha, window_beta, free_q (windowKernelChange -> regenerateWindowKernel, remapResonator,
+ *         :583-595): FFT: nothing zeroed; RSNT: the resonators restart at rest under the new bank (UNVERIFIED vs cpl, as in set_view)
+ *     window_size (audioWindowWasResized -> setStorage, windowKernelChange, :481-494): as the row above; the ring keeps its newest samples
+ *         at the new capacity by sgz_ring_resize_device's rule (UNVERIFIED vs cpl: cpl's AudioStream history resize is not in the tree)
+ *     hop (sampleBufferSize, assigned every call, :365): nothing zeroed.  The cadence follows audioEntryPoint (TransformDSP.inl:1172-1201):
+ *         when the samples since the last frame reach the new hop, the next push fires one frame at the position of the update (over the
+ *         W newest samples as of then), then one every new hop; strict-quirks framing likewise
+ *     view_scaling, min_log_freq, view_left / view_right, channel_mode (viewChanged, :422-431, :532-575): clearLineGraphStates -- both
+ *         graphs' decay states and results are zeroed (sgz_spectrum_line_results reads zeros until a frame computed after this call); RSNT:
+ *         the resonators restart at rest.  COLOUR_SPECTRUM with an image bound and a rect that changed: the image is translated as
+ *         sgz_spectrum_set_view translates it (:560-561), waited for before the call returns
+ *     algorithm (resetStateBuffers -> clearAudioState, :321-324, :608-612): what sgz_spectrum_clear_state zeroes -- decay states, line
+ *         results, resonators
+ * Waits for the GPU: not for the audio thread. */
+sgz_status sgz_spectrum_update(sgz_spectrum *s, const sgz_spectrum_config *cfg);
+/* What sgz_spectrum_update does for a change from `from` to `to` (host only, no GPU; the update decides by this call): SGZ_OK and
+ * *effects = a mask of the flags below (0: the configurations are equal), or the update's refusal -- SGZ_EINVAL for an invalid `to` or an
+ * axis_points change, SGZ_EUNSUPPORTED for a sample_rate, num_pairs or display_mode change (checked in that order: validity, then those
+ * three, then axis_points).  Fields compare by value (_pad and _reserved are ignored).  The audio-history refusal depends on the handle and
+ * is the update's alone.
+ *   SGZ_UPDATE_PLANS                new plans are built and swapped in (every change)
+ *   SGZ_UPDATE_CLEAR_LINES          both graphs' decay states and results are zeroed (a view-class or algorithm change)
+ *   SGZ_UPDATE_CLEAR_STATE          clearAudioState: the above and the resonators (an algorithm change)
+ *   SGZ_UPDATE_RESONATORS_AT_REST   `to` is RSNT and its resonators start at rest (window, window_size, view class or algorithm changed)
+ *   SGZ_UPDATE_TRANSLATE_IMAGE      `to` is COLOUR_SPECTRUM and the rect (view_left / view_right) changed: a bound image is translated
+ *   SGZ_UPDATE_RING_MOVED           the ring's capacity ((RSNT ? hop : window_size) + 32768, rounded up to 64) changes */
+#define SGZ_UPDATE_PLANS 1u
+#define SGZ_UPDATE_CLEAR_LINES 2u
+#define SGZ_UPDATE_CLEAR_STATE 4u
+#define SGZ_UPDATE_RESONATORS_AT_REST 8u
+#define SGZ_UPDATE_TRANSLATE_IMAGE 16u
+#define SGZ_UPDATE_RING_MOVED 32u
+sgz_status sgz_spectrum_update_effects(const sgz_spectrum_config *from, const sgz_spectrum_config *to, uint32_t *effects);
+/* The update's ring move, as a stateless stage call: d_old [channels][2 old_cap] and d_new [channels][2 new_cap] are mirrored rings (sample
+ * t at t mod cap and t mod cap + cap) into which `written` samples have gone.  For every t in [written - new_cap, written), d_new receives
+ * at both mirror positions (non-negative residues, so a t below 0 has its slot too) the old sample when t >= written - old_cap and t >= 0,
+ * otherwise 0.0f (silence, as a ring starts).  DEVICE pointers; enqueued on `stream`, nothing waited for.  SGZ_EINVAL for a null ring, a
+ * zero capacity or one of 2^31 or more, no channels or more than 65535, or byte ranges that overlap. */
+sgz_status sgz_ring_resize_device(const float *d_old, uint32_t old_cap, float *d_new, uint32_t new_cap, uint32_t channels, uint64_t written,
+                                  void *stream);
 /* lineGraphs[graph].getResults(P) for pair `pair`: float2 [P] (TransformPair.h:72-76).  COLOUR_SPECTRUM: the results of the newest
  * frame whose copy has reached the host (a pinned triple buffer the producer's stream fills: this call waits for nothing and never
  * touches the producer's stream); LINE_GRAPH: the results of the last sgz_spectrum_render_lines. */
@@ -571,7 +631,7 @@ sgz_status sgz_spectrum_line_results(sgz_spectrum *s, uint32_t pair, uint32_t gr
  * the configured ones.  Waits for its own result (it is the render thread's call); never delays push.  SGZ_EINVAL on a
  * COLOUR_SPECTRUM handle. */
 sgz_status sgz_spectrum_render_lines(sgz_spectrum *s, const float *poles /*[SGZ_NUM_GRAPHS] or NULL*/, float *out /*[pairs][graphs][P][2]*/);
-/* Handle switches (consumer thread, between create / configure and the first push; a configure keeps them):
+/* Handle switches (consumer thread, between create / configure and the first push; a configure or an update keeps them):
  *   SGZ_RT_OPT_STRICT_REFERENCE_QUIRKS  0 (default): ideal STFT framing -- a frame fires every `hop` samples wherever that falls inside a
  *       host block.  1: audioEntryPoint as written (TransformDSP.inl:1165-1211): every frame of one callback is prepared
  *       from the history BEFORE the callback plus the first min(availableSamples, W) samples of the UN-offset block (Q1: a 512-sample

@@ -168,6 +168,7 @@ EXPORTS = [
     "sgz_line_graph_vertex_count", "sgz_line_graph_draws", "sgz_line_graph_vertices_device", "sgz_spectrum_render_line_vertices",
     "sgz_spectrum_set_view", "sgz_view_translation_rows", "sgz_view_translate_device",
     "sgz_spectrum_resize", "sgz_image_resize_rows", "sgz_image_resize_columns", "sgz_image_resize_device",
+    "sgz_spectrum_update", "sgz_spectrum_update_effects", "sgz_ring_resize_device",
     "sgz_scope_set_mix", "sgz_vector_set_mix",
     "sgz_scope_set_tempo", "sgz_scope_effective_window", "sgz_scope_time_window",
 ]
@@ -330,6 +331,9 @@ def lib() -> C.CDLL:
     L.sgz_image_resize_rows.argtypes = [u32, u32, vp, vp]
     L.sgz_image_resize_columns.argtypes = [u32, u32, u32, vp, C.POINTER(u32)]
     L.sgz_image_resize_device.argtypes = [vp, u32, sz, u32, u32, vp, u32, sz, u32, C.POINTER(u32), vp]
+    L.sgz_spectrum_update.argtypes = [vp, C.POINTER(SpectrumConfig)]
+    L.sgz_spectrum_update_effects.argtypes = [C.POINTER(SpectrumConfig), C.POINTER(SpectrumConfig), C.POINTER(u32)]
+    L.sgz_ring_resize_device.argtypes = [vp, u32, vp, u32, u32, C.c_uint64, vp]
     L.sgz_scope_num_points.argtypes = [C.POINTER(ScopeView)]
     L.sgz_scope_num_points.restype = sz
     L.sgz_scope_lanczos_device.argtypes = [C.POINTER(ScopeView), vp, sz, sz, u32, vp, vp]
@@ -466,6 +470,36 @@ def image_resize_device(src, old_columns: int, src_pitch_bytes: int, old_axis_po
     check(lib().sgz_image_resize_device(_dev_ptr(src), old_columns, src_pitch_bytes, old_axis_points, old_x, _dev_ptr(dst), new_columns,
                                         dst_pitch_bytes, new_axis_points, C.byref(x1), C.c_void_p(stream) if stream else None))
     return x1.value
+
+
+# sgz_spectrum_update_effects' flags
+UPDATE_PLANS, UPDATE_CLEAR_LINES, UPDATE_CLEAR_STATE, UPDATE_RESONATORS_AT_REST, UPDATE_TRANSLATE_IMAGE, UPDATE_RING_MOVED = 1, 2, 4, 8, 16, 32
+
+
+def _as_config(cfg) -> SpectrumConfig:
+    return cfg if isinstance(cfg, SpectrumConfig) else config_from_dict(cfg)
+
+
+def spectrum_update(handle, cfg) -> None:
+    """sgz_spectrum_update: any setting change short of a new stream, display mode or axis size (a config dict or SpectrumConfig), keeping
+    the audio history, the cadence, the mix, the queued columns and the image binding; what it zeroes is spectrum_update_effects'"""
+    c = _as_config(cfg)
+    check(lib().sgz_spectrum_update(handle, C.byref(c)))
+
+
+def spectrum_update_effects(old, new) -> int:
+    """what sgz_spectrum_update does for a change from `old` to `new` (config dicts or SpectrumConfig; host only): the UPDATE_* mask, 0 for
+    equal configurations; raises SgzError with the update's refusal"""
+    a, b, fx = _as_config(old), _as_config(new), C.c_uint32(0)
+    check(lib().sgz_spectrum_update_effects(C.byref(a), C.byref(b), C.byref(fx)))
+    return fx.value
+
+
+def ring_resize_device(old_ring, old_cap: int, new_ring, new_cap: int, channels: int, written: int, stream=None) -> None:
+    """sgz_ring_resize_device: the mirrored ring [channels][2 old_cap] into [channels][2 new_cap] keeping its newest samples (DEVICE float32:
+    torch tensors or device pointers); enqueued on `stream`, not waited for"""
+    check(lib().sgz_ring_resize_device(_dev_ptr(old_ring), old_cap, _dev_ptr(new_ring), new_cap, channels, written,
+                                       C.c_void_p(stream) if stream else None))
 
 
 RT_OPT_STRICT_REFERENCE_QUIRKS, RT_OPT_AUDIO_HISTORY, RT_OPT_DEFER_SUBMIT, RT_OPT_PARK_PUSHES = 1, 2, 3, 4

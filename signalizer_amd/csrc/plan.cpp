@@ -599,7 +599,7 @@ static void buildResonator(Plan &p)
     }
 }
 
-sgz_status buildPlan(const sgz_spectrum_config &cfg, Plan &p, std::string &err)
+sgz_status validateConfig(const sgz_spectrum_config &cfg, std::string &err)
 {
     if (cfg.window_size < 1 || cfg.axis_points < 2 || cfg.num_pairs < 1 || cfg.hop < 1 || !(cfg.sample_rate >= 1)) {
         err = "invalid spectrum config (window_size>=1, axis_points>=2 (TransformConstant.h:127), num_pairs>=1, hop>=1, sample_rate>=1)";
@@ -631,6 +631,12 @@ sgz_status buildPlan(const sgz_spectrum_config &cfg, Plan &p, std::string &err)
     }
     if (!(cfg.high_db > cfg.low_db)) { err = "high_db must exceed low_db"; return SGZ_EINVAL; }
     if (cfg.algorithm > SGZ_ALGO_RSNT) { err = "algorithm must be SGZ_ALGO_FFT or SGZ_ALGO_RSNT"; return SGZ_EINVAL; }
+    return SGZ_OK;
+}
+
+sgz_status buildPlan(const sgz_spectrum_config &cfg, Plan &p, std::string &err)
+{
+    if (sgz_status st = validateConfig(cfg, err); st != SGZ_OK) return st;
     p.cfg = cfg;
     p.W = cfg.window_size;
     p.N = transformSizeFor(p.W);

@@ -178,6 +178,8 @@ inline long planFrames(const Plan &p, size_t nsamples)
     return isResonator(p) ? long(nsamples / p.cfg.hop) : long(sgz_num_frames(nsamples, p.W, p.cfg.hop));
 }
 
+// The checks buildPlan makes before it builds anything (SGZ_OK or SGZ_EINVAL, message in `err`).
+sgz_status validateConfig(const sgz_spectrum_config &cfg, std::string &err);
 // Builds every host table; returns SGZ_OK or an error (message in `err`).
 sgz_status buildPlan(const sgz_spectrum_config &cfg, Plan &plan, std::string &err);
 sgz_status uploadPlan(Plan &plan, std::string &err);

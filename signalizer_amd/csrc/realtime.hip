@@ -52,6 +52,13 @@
 // Resize (sgz_spectrum_resize, consumer thread; handleFlagUpdates' resized branch, Spectrum.cpp:503-515): as set_view, with a new axis size:
 // the plans and every buffer whose size is the axis size (AxisBuffers) are made outside cfgMu and swapped in under it.  The ring and the
 // cadence stay; the queued columns stay when the size does; the bound image is resampled into the new one afterwards (image_resize.hip).
+//
+// Every other setting (sgz_spectrum_update, consumer thread; the rest of handleFlagUpdates, Spectrum.cpp:351-616): sgz_spectrum_update_effects
+// classes the changed fields, and only their flags' work is done.  The plans and the buffers whose size changes (frames per piece, sides,
+// tracker bins, strict frame, the ring) are made outside cfgMu; under it the stream is drained, the ring is moved to its new capacity
+// keeping its newest samples (ring_resize.hip), and the new plans are warmed up on scratch state -- the decay states, line results and
+// RSNT resonator states a class keeps are never touched by the warm-up (the resonators are copied from the old plan).  A changed rect
+// translates the bound image afterwards, as set_view does.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -212,6 +219,24 @@ static void exchangeAxisBuffers(sgz_spectrum *s, AxisBuffers &b, bool queue)
     if (queue) { std::swap(s->h_cols, b.h_cols); std::swap(s->d_colsQ, b.d_colsQ); }
 }
 
+// the buffers whose size is frames per piece x the channel mode's sides, and the line graph's K_A output [C][sides][P]: what an update of
+// the hop or the channel mode replaces (d_state / d_lines and the host copies are [C][graphs][P][2] whatever the configuration)
+static sgz_status allocFrameBuffers(const Plan &p, uint32_t maxFrames, AxisBuffers &b)
+{
+    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_mapped), size_t(maxFrames) * p.C * p.sides * p.P * sizeof(float)));
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_linesBatch), size_t(maxFrames) * stateN * sizeof(float)));
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_colsBatch), size_t(maxFrames) * p.P * 4));
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&b.d_lineMapped), size_t(p.C) * p.sides * p.P * sizeof(float)));
+    return SGZ_OK;
+}
+
+static void exchangeFrameBuffers(sgz_spectrum *s, AxisBuffers &b)
+{
+    std::swap(s->d_mapped, b.d_mapped); std::swap(s->d_linesBatch, b.d_linesBatch); std::swap(s->d_colsBatch, b.d_colsBatch);
+    std::swap(s->d_lineMapped, b.d_lineMapped);
+}
+
 static void unbindImage(sgz_spectrum *s)
 {
     if (s->outStream) (void)hipStreamSynchronize(s->outStream);
@@ -285,22 +310,30 @@ static sgz_status makePlans(const sgz_spectrum_config *cfg, Plan **plan, Plan **
     return SGZ_OK;
 }
 
-// warm-up of the handle's plans: the largest batch a push can produce and the consumer's line-graph step, on the ring as it stands (read,
-// never written) -- every lazy allocation and LDS grant of the kernels happens here, not on the audio thread.  The state it leaves is
-// cleared again: decay states, line results and the resonators start at rest (the caller holds cfgMu, or the handle is not shared yet)
-static sgz_status warmUp(sgz_spectrum *s)
+// the warm-up's launches on the handle's plans: the largest batch a push can produce and the consumer's line-graph step, on the ring as it
+// stands (read, never written), with `mapped` / `state` / `lines` in place of the handle's own buffers of those sizes
+static sgz_status warmUpLaunches(sgz_spectrum *s, float *mapped, float *state, float *lines)
 {
     Plan &p = *s->plan, &tp = *s->trackPlan;
-    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
-    sgz_status st = runStft(p, s->d_ring, size_t(2) * s->cap, long(s->maxFrames), s->d_mapped, nullptr, nullptr, s->stream, nullptr, /*deferLate=*/true);
-    if (st == SGZ_OK) st = runDecayColour(p, s->d_mapped, long(s->maxFrames), s->d_colsBatch, s->d_linesBatch, s->d_state, s->stream);
+    sgz_status st = runStft(p, s->d_ring, size_t(2) * s->cap, long(s->maxFrames), mapped, nullptr, nullptr, s->stream, nullptr, /*deferLate=*/true);
+    if (st == SGZ_OK) st = runDecayColour(p, mapped, long(s->maxFrames), s->d_colsBatch, s->d_linesBatch, state, s->stream);
     if (st == SGZ_OK && s->maxFrames > 1) {
-        st = runStft(p, s->d_ring, size_t(2) * s->cap, 1, s->d_mapped, nullptr, nullptr, s->stream, nullptr, /*deferLate=*/true);
-        if (st == SGZ_OK) st = runDecayColour(p, s->d_mapped, 1, s->d_colsBatch, s->d_linesBatch, s->d_state, s->stream);
+        st = runStft(p, s->d_ring, size_t(2) * s->cap, 1, mapped, nullptr, nullptr, s->stream, nullptr, /*deferLate=*/true);
+        if (st == SGZ_OK) st = runDecayColour(p, mapped, 1, s->d_colsBatch, s->d_linesBatch, state, s->stream);
     }
     // ... and the consumer thread's line-graph step on its own plan (one frame with line results and state)
     if (st == SGZ_OK && !isResonator(p)) st = runStft(tp, s->d_ring, size_t(2) * s->cap, 1, s->d_lineMapped, nullptr, nullptr, s->stream);
-    if (st == SGZ_OK) st = runDecayColour(tp, isResonator(p) ? s->d_mapped : s->d_lineMapped, 1, nullptr, s->d_lines, s->d_state, s->stream);
+    if (st == SGZ_OK) st = runDecayColour(tp, isResonator(p) ? mapped : s->d_lineMapped, 1, nullptr, lines, state, s->stream);
+    return st;
+}
+
+// warm-up of the handle's plans -- every lazy allocation and LDS grant of the kernels happens here, not on the audio thread.  The state it
+// leaves is cleared again: decay states, line results and the resonators start at rest (the caller holds cfgMu, or the handle is not shared yet)
+static sgz_status warmUp(sgz_spectrum *s)
+{
+    Plan &p = *s->plan;
+    const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
+    sgz_status st = warmUpLaunches(s, s->d_mapped, s->d_state, s->d_lines);
     if (st != SGZ_OK) return st;
     if ((st = resetResonator(p, s->stream)) != SGZ_OK) return st;
     SGZ_HIP(hipMemsetAsync(s->d_state, 0, stateN * sizeof(float), s->stream));
@@ -308,6 +341,13 @@ static sgz_status warmUp(sgz_spectrum *s)
     SGZ_HIP(hipMemsetAsync(s->d_mapped, 0, size_t(s->maxFrames) * p.C * p.sides * p.P * sizeof(float), s->stream));   // (RSNT line graph: the windowed state of resonators at rest)
     SGZ_HIP(hipStreamSynchronize(s->stream));
     return SGZ_OK;
+}
+
+// the ring's capacity: a piece's frames read windows that end inside the piece, so the ring must hold W + one piece (RSNT: a frame
+// consumes the `hop` samples that end with it) -- and a second piece of slack for the consumer thread's transforms of the newest window
+static uint32_t ringCapFor(const sgz_spectrum_config &cfg)
+{
+    return ((cfg.algorithm == SGZ_ALGO_RSNT ? cfg.hop : cfg.window_size) + 2 * kPiece + 63u) & ~63u;
 }
 
 // builds everything for a configuration into the handle (the caller holds cfgMu, or the handle is not shared yet)
@@ -329,9 +369,7 @@ static sgz_status setup(sgz_spectrum *s, const sgz_spectrum_config *cfg)
     exchangeAxisBuffers(s, axis, true);
     freeAxisBuffers(axis);
     unbindImage(s);                                        // the image's height is the axis size: a new configuration needs a new binding
-    // a piece's frames read windows that end inside the piece: the ring must hold W + one piece (RSNT: a frame consumes the `hop`
-    // samples that end with it) -- and a second piece of slack for the consumer thread's transforms of the newest window (see above)
-    s->cap = ((isResonator(p) ? p.cfg.hop : p.W) + 2 * kPiece + 63u) & ~63u;
+    s->cap = ringCapFor(p.cfg);                            // (the ring's capacity: see there)
     s->maxFrames = kPiece / p.cfg.hop + 1;
     SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_ring), nch * 2 * s->cap * sizeof(float)));
     SGZ_HIP(hipMemsetAsync(s->d_ring, 0, nch * 2 * s->cap * sizeof(float), s->stream));    // history starts as silence
@@ -821,6 +859,150 @@ sgz_status sgz_spectrum_resize(sgz_spectrum *s, uint32_t axis_points, void *d_im
         if (s->imgOwned && s->d_image != newImage) { (void)hipFree(s->d_image); s->imgOwned = false; s->imgOwnedBytes = 0; }
     }
     s->d_image = newImage; s->imgColumns = columns; s->imgPitch = pitch_bytes; s->imgX = x1;
+    return SGZ_OK;
+}
+
+// what sgz_spectrum_create refuses before it builds a plan
+static sgz_status checkRealtimeConfig(const sgz_spectrum_config &cfg)
+{
+    if (cfg.num_pairs > 16) return fail(SGZ_EINVAL, "real-time handle supports at most 32 channels");
+    if (cfg.display_mode > SGZ_DISPLAY_COLOUR_SPECTRUM) return fail(SGZ_EINVAL, "display_mode: SGZ_DISPLAY_LINE_GRAPH or SGZ_DISPLAY_COLOUR_SPECTRUM");
+    std::string err;
+    if (validateConfig(cfg, err) != SGZ_OK) return fail(SGZ_EINVAL, err);
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrum_update_effects(const sgz_spectrum_config *from, const sgz_spectrum_config *to, uint32_t *effects)
+{
+    if (!from || !to || !effects) return fail(SGZ_EINVAL, "null argument");
+    if (sgz_status st = checkRealtimeConfig(*to); st != SGZ_OK) return st;
+    const sgz_spectrum_config &a = *from, &b = *to;
+    if (a.sample_rate != b.sample_rate || a.num_pairs != b.num_pairs)
+        return fail(SGZ_EUNSUPPORTED, "a new sample_rate or num_pairs is a new stream: sgz_spectrum_configure");
+    if (a.display_mode != b.display_mode) return fail(SGZ_EUNSUPPORTED, "a new display_mode is a new display: sgz_spectrum_configure");
+    if (a.axis_points != b.axis_points) return fail(SGZ_EINVAL, "a new axis_points is sgz_spectrum_resize (it takes the image)");
+    // the field classes of handleFlagUpdates (sgz.h)
+    bool look = a.low_db != b.low_db || a.high_db != b.high_db || a.clip_db != b.clip_db || a.slope_a != b.slope_a || a.slope_b != b.slope_b ||
+                a.bin_interp != b.bin_interp || std::memcmp(a.colours, b.colours, sizeof(a.colours)) != 0;
+    for (int k = 0; k < SGZ_NUM_GRAPHS; ++k) look = look || a.pole[k] != b.pole[k];
+    for (int k = 0; k < SGZ_NUM_SPEC_COLOURS; ++k) look = look || a.ratios[k] != b.ratios[k];
+    const bool window = a.window_type != b.window_type || a.window_symmetry != b.window_symmetry || a.window_alpha != b.window_alpha ||
+                        a.window_beta != b.window_beta || a.free_q != b.free_q;
+    const bool size = a.window_size != b.window_size, hop = a.hop != b.hop;
+    const bool rect = a.view_left != b.view_left || a.view_right != b.view_right;
+    const bool view = rect || a.view_scaling != b.view_scaling || a.min_log_freq != b.min_log_freq || a.channel_mode != b.channel_mode;
+    const bool algo = a.algorithm != b.algorithm;
+    uint32_t fx = 0;
+    if (look || window || size || hop || view || algo) fx |= SGZ_UPDATE_PLANS;
+    if (view || algo) fx |= SGZ_UPDATE_CLEAR_LINES;
+    if (algo) fx |= SGZ_UPDATE_CLEAR_STATE;
+    if (b.algorithm == SGZ_ALGO_RSNT && (window || size || view || algo)) fx |= SGZ_UPDATE_RESONATORS_AT_REST;
+    if (b.display_mode == SGZ_DISPLAY_COLOUR_SPECTRUM && rect) fx |= SGZ_UPDATE_TRANSLATE_IMAGE;
+    if (ringCapFor(a) != ringCapFor(b)) fx |= SGZ_UPDATE_RING_MOVED;
+    *effects = fx;
+    return SGZ_OK;
+}
+
+// what an update allocates before the handle is held, and what it takes out of the handle (freed after the lock is released)
+struct UpdateBuffers {
+    float *ring = nullptr, *strict = nullptr, *trackBins = nullptr;
+    AxisBuffers frames;
+    float *scratch = nullptr;                 // the warm-up's stand-ins for d_mapped, d_state, d_lines (the handle's keep their content)
+    void release()
+    {
+        for (float *q : {ring, strict, trackBins, scratch}) if (q) (void)hipFree(q);
+        freeAxisBuffers(frames);
+        ring = strict = trackBins = scratch = nullptr;
+    }
+};
+
+sgz_status sgz_spectrum_update(sgz_spectrum *s, const sgz_spectrum_config *cfg)
+{
+    if (!s || !cfg) return fail(SGZ_EINVAL, "null argument");
+    const sgz_spectrum_config old = s->plan->cfg;            // (only this thread replaces the plans)
+    uint32_t fx = 0;
+    if (sgz_status st = sgz_spectrum_update_effects(&old, cfg, &fx); st != SGZ_OK) return st;
+    if (!fx) return SGZ_OK;                                   // nothing changed: nothing touched, push never held off
+    if (s->audioHistory != 0 && cfg->window_size > s->audioHistory)
+        return fail(SGZ_EINVAL, "the window exceeds the audio history set with SGZ_RT_OPT_AUDIO_HISTORY (prepareTransform, TransformDSP.inl:241-242)");
+    // the new plans and every buffer whose size changes, made before the handle is held, so that push is refused only while they are swapped in
+    Plan *pl = nullptr, *tp = nullptr;
+    sgz_status st = makePlans(cfg, &pl, &tp);
+    if (st != SGZ_OK) return st;
+    const Plan &np = *pl, &op = *s->plan;
+    const uint32_t nch = 2 * np.C, cap = ringCapFor(*cfg), maxFrames = kPiece / cfg->hop + 1;
+    const bool newFrames = maxFrames != s->maxFrames || np.sides != op.sides;
+    const bool track = np.cfg.channel_mode != SGZ_CH_PHASE && !isResonator(np);
+    const bool newTrack = track && (!s->d_trackBins || np.N != op.N);
+    const size_t stateN = size_t(np.C) * SGZ_NUM_GRAPHS * np.P * 2, mappedN = size_t(maxFrames) * np.C * np.sides * np.P;
+    UpdateBuffers nb;
+    auto alloc = [](float **q, size_t floats) { return hipMalloc(reinterpret_cast<void **>(q), floats * sizeof(float)); };
+    hipError_t e = hipSuccess;
+    if (fx & SGZ_UPDATE_RING_MOVED) e = alloc(&nb.ring, size_t(nch) * 2 * cap);
+    if (e == hipSuccess && np.W != op.W) e = alloc(&nb.strict, size_t(nch) * np.W);
+    if (e == hipSuccess && newTrack) e = alloc(&nb.trackBins, size_t(np.C) * (size_t(np.N) + 1));
+    if (e == hipSuccess) e = alloc(&nb.scratch, mappedN + 2 * stateN);
+    st = e != hipSuccess ? hipFail(e, "hipMalloc (spectrum update)") : newFrames ? allocFrameBuffers(np, maxFrames, nb.frames) : SGZ_OK;
+    if (st != SGZ_OK) { nb.release(); delete pl; delete tp; return st; }
+    {
+        std::lock_guard<std::mutex> lk(s->cfgMu);
+        e = hipStreamSynchronize(s->stream);                  // the old plans' launches are done; written / planned and the cadence stay
+        if (e != hipSuccess) { nb.release(); delete pl; delete tp; return hipFail(e, "hipStreamSynchronize"); }
+        // the ring at its new capacity, its newest samples kept (ring_resize.hip); `written` stays, so ringPos stays valid
+        if (nb.ring) {
+            if ((st = resizeRing(s->d_ring, s->cap, nb.ring, cap, nch, s->written.load(std::memory_order_relaxed), s->stream)) != SGZ_OK) {
+                nb.release(); delete pl; delete tp; return st;
+            }
+            std::swap(s->d_ring, nb.ring);
+            s->cap = cap;
+        }
+        // (from here on the handle is the new configuration's: a failing step is reported, the old plans are freed all the same)
+        auto step = [&](hipError_t r, const char *what) { if (st == SGZ_OK && r != hipSuccess) st = hipFail(r, what); };
+        if (newFrames) {
+            // RSNT line graph: d_mapped holds the resonators' windowed state, which render_lines reads -- it moves along while the sides stay
+            if (np.sides == op.sides)
+                step(hipMemcpyAsync(nb.frames.d_mapped, s->d_mapped, size_t(np.C) * np.sides * np.P * sizeof(float), hipMemcpyDeviceToDevice, s->stream),
+                     "hipMemcpyAsync");
+            exchangeFrameBuffers(s, nb.frames);
+        }
+        s->maxFrames = maxFrames;
+        if (nb.strict) std::swap(s->d_strict, nb.strict);
+        if (newTrack || !track) std::swap(s->d_trackBins, nb.trackBins);   // (!track: the handle's bins go, nb's null comes in)
+        Plan *oldPlan = s->plan, *oldTrack = s->trackPlan;
+        s->plan = pl;
+        s->trackPlan = tp;
+        // the warm-up runs on scratch stand-ins: the states the update keeps are not touched by it
+        if (st == SGZ_OK) st = warmUpLaunches(s, nb.scratch, nb.scratch + mappedN, nb.scratch + mappedN + stateN);
+        if (st == SGZ_OK && (fx & SGZ_UPDATE_CLEAR_LINES)) {
+            // clearLineGraphStates (TransformPair.h:169-175) -- and the host's copies of the results with them
+            step(hipMemsetAsync(s->d_state, 0, stateN * sizeof(float), s->stream), "hipMemsetAsync");
+            step(hipMemsetAsync(s->d_lines, 0, stateN * sizeof(float), s->stream), "hipMemsetAsync");
+            std::memset(s->h_lineOut, 0, stateN * sizeof(float));
+            std::memset(s->h_lines, 0, size_t(sgz_spectrum::kLineSlots) * stateN * sizeof(float));
+            s->lineSeq.reset();
+        }
+        if (st == SGZ_OK && isResonator(np)) {
+            // the warm-up advanced the new bank: it restarts at rest, or continues from the old bank's state (V and P unchanged)
+            const size_t resBytes = size_t(np.C) * 2 * size_t(np.resV) * np.P * 2 * sizeof(float);
+            const bool carry = !(fx & SGZ_UPDATE_RESONATORS_AT_REST) && isResonator(*oldPlan) && oldPlan->d_resState && oldPlan->resV == np.resV;
+            if (carry) {
+                step(hipMemcpyAsync(pl->d_resState, oldPlan->d_resState, resBytes, hipMemcpyDeviceToDevice, s->stream), "hipMemcpyAsync");
+            } else {
+                st = resetResonator(*pl, s->stream);
+                step(hipMemsetAsync(s->d_mapped, 0, mappedN * sizeof(float), s->stream), "hipMemsetAsync");   // (the windowed state at rest)
+            }
+        }
+        step(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        delete oldPlan;
+        delete oldTrack;
+    }
+    nb.release();                                             // (what the handle had before: nothing uses it any more)
+    if (st != SGZ_OK) return st;
+    // Spectrum.cpp:560-561: the columns on screen follow a changed rect; queued columns land as they were computed
+    if ((fx & SGZ_UPDATE_TRANSLATE_IMAGE) && (s->d_image || s->glResource)) {
+        const double oldView[2] = {old.view_left, old.view_right}, newView[2] = {cfg->view_left, cfg->view_right};
+        return translateBoundImage(s, oldView, newView);
+    }
     return SGZ_OK;
 }
 

@@ -36,6 +36,10 @@ bool imageResizeFits(uint32_t C0, uint32_t C1, uint32_t P1);         // the kern
 size_t imageResizeScratchFloats(uint32_t P0, uint32_t C0, uint32_t P1, uint32_t C1);
 sgz_status resizeImage(const uint8_t *src, uint32_t C0, size_t srcPitch, uint32_t P0, uint32_t x0, uint8_t *dst, uint32_t C1,
                        size_t dstPitch, uint32_t P1, uint32_t *x1, float **scratch, size_t *scratchCap, hipStream_t stream);
+// ring_resize.hip: the real-time Spectrum's mirrored ring [channels][2 cap] at a new capacity, its newest samples kept (sgz_ring_resize_device;
+// the spectrum handle's update).  resizeRing enqueues on `stream` and waits for nothing
+bool validRingResize(const float *d_old, uint32_t oldCap, const float *d_new, uint32_t newCap, uint32_t channels);
+sgz_status resizeRing(const float *d_old, uint32_t oldCap, float *d_new, uint32_t newCap, uint32_t channels, uint64_t written, hipStream_t stream);
 int numCUs();
 // K_A over `frames` frames (ideal STFT framing from d_planar); any of mapped/binsOut may be null
 // deferLate: the caller's next call is runDecayColour on the same d_mapped with only an image wanted -- a channel-split launch may then
