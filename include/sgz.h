@@ -484,6 +484,75 @@ sgz_status sgz_spectrum_bind_image(sgz_spectrum *s, void *d_image, uint32_t colu
 sgz_status sgz_spectrum_create_image(sgz_spectrum *s, uint32_t columns, void **d_image, size_t *pitch_bytes, int *dmabuf_fd);
 sgz_status sgz_spectrum_bind_gl_buffer(sgz_spectrum *s, unsigned int gl_buffer, uint32_t columns, size_t pitch_bytes);
 sgz_status sgz_spectrum_flush_columns(sgz_spectrum *s, uint32_t *first_column, uint32_t *count);
+/* The render thread's colour-spectrum frame as the plugin runs it (consumer thread, once per video frame): Spectrum::renderColourSpectrum
+ * (SpectrumRendering.cpp:672-749) = frame pacing + freeze around the pop loop, then the ring image drawn unrolled.  COLOUR_SPECTRUM handles
+ * only (a LINE_GRAPH handle: SGZ_EINVAL).  The handle keeps three values for it: framesPerUpdate (0 from sgz_spectrum_create on: the
+ * constructor zero-initialises it, Spectrum.cpp:59, and nothing but the loop assigns it), frame_update_smoothing (0) and frozen (0).  All
+ * three survive sgz_spectrum_configure, _update, _resize, _set_view and every (re)binding of the image; sgz_spectrum_pop_column and
+ * sgz_spectrum_flush_columns neither read nor write them.
+ *   sgz_spectrum_set_pacing      content->frameUpdateSmoothing ("Upd. smoothing", SpectrumParameters.h:104, :122: the range is
+ *                                [0, 0.996]; here finite in [0, 1), else SGZ_EINVAL)
+ *   sgz_spectrum_set_frozen      Spectrum::freeze / unfreeze (Spectrum.cpp:161-169): state.isFrozen
+ *   sgz_spectrum_render_columns  the pop loop of one video frame (:679-735) into the bound image (none bound: SGZ_EINVAL), a GL buffer
+ *                                mapped and unmapped around the writes as in flush_columns.  With z = framesPerUpdate, s = the smoothing
+ *                                and stored() = the columns in the queue now (getApproximateStoredFrames(), read live):
+ *                                  z1 = stored() + s * (z - stored())            (:686-687; fp64, as written)
+ *                                  s != 0: at most round(z) columns are popped  (:688, :693: round(framesPerUpdate), not round(z1))
+ *                                  s == 0: every column is popped, and z1 = stored() + s * (z - stored()) again behind each pop
+ *                                          (:727-731; processedFrames stays 0 there, its ++ sits behind `!shouldCap ||`)
+ *                                  framesPerUpdate = z1                          (:735)
+ *                                A pop ends the loop when the queue is empty or its first column's copy has not completed (popElement
+ *                                fails), and -- this library's limits -- after 10 columns (the queue's depth: the slots go back to the
+ *                                producer behind the write) or one lap of the image.  All columns taken are written by ONE kernel launch
+ *                                at x = framePixelPosition, wrapping at `columns`, waited for; framePixelPosition advances by the count.
+ *                                *first_column / *count name the texel columns written, *frames_per_update = framesPerUpdate after the
+ *                                call (each may be NULL).  SGZ_EMPTY: none taken (framesPerUpdate is updated all the same).  Frozen
+ *                                (:679): nothing is taken, framesPerUpdate and framePixelPosition stay, SGZ_EMPTY; the producer keeps
+ *                                running and drops the columns a full queue cannot take (SpectrumDSP.cpp:185-186; dropped_columns of
+ *                                sgz_spectrum_stats counts them)
+ *   sgz_spectrum_present         OpenGLImageDrawer::drawCircular(framePixelPosition / (columns - 1)) (:742-744) of the bound image into
+ *                                d_dst, DEVICE memory [P][dst_pitch_bytes] (pitch >= 4 * columns, 4-byte aligned), by
+ *                                sgz_image_unroll_device's rule with x = framePixelPosition; waits for the texels.  Frozen or not.  A
+ *                                d_dst whose bytes overlap the bound image's: SGZ_EINVAL.  A host that draws the ring itself (two quads
+ *                                split at *first_column + *count) does not need it. */
+sgz_status sgz_spectrum_set_pacing(sgz_spectrum *s, double frame_update_smoothing);
+sgz_status sgz_spectrum_set_frozen(sgz_spectrum *s, int frozen);
+sgz_status sgz_spectrum_render_columns(sgz_spectrum *s, uint32_t *first_column, uint32_t *count, double *frames_per_update);
+sgz_status sgz_spectrum_present(sgz_spectrum *s, void *d_dst, size_t dst_pitch_bytes);
+/* One pass of renderColourSpectrum's pop loop as written (:681-735) for a queue of `queued` columns that nobody adds to meanwhile and a
+ * previous framesPerUpdate z (host only, no GPU; sgz_spectrum_render_columns runs the same arithmetic on the live queue).  Line by line,
+ * with Q = queued, s = smoothing:
+ *   :681      localFrameZ1 = framesPerUpdate = z
+ *   :685-687  processedFrames = 0; approximateFrames = 0 + Q; localFrameZ1 = Q + s * (z - Q)
+ *   :688      framesThisTime = round(framesPerUpdate) = round(z)     -- of the OLD value, not of localFrameZ1
+ *   :691      shouldCap = s != 0
+ *   :693      while (!shouldCap || processedFrames++ < framesThisTime): with shouldCap the body runs at most round(z) times and
+ *             processedFrames counts them; without it the `||` short-circuits, processedFrames++ is never evaluated and stays 0
+ *   :696-697  popElement fails -> break: after Q pops
+ *   :727-732  only when !shouldCap: approximateFrames = processedFrames (0) + what is left; localFrameZ1 = left + s * (z - left)
+ *   :735      framesPerUpdate = localFrameZ1
+ * so
+ *   smoothing != 0: *pop = min(queued, round(z));  *z_next = queued + smoothing * (z - queued)
+ *   smoothing == 0: *pop = queued;                 *z_next = left + 0 * (z - left) with left = queued - *pop = 0, i.e. 0 (what :729-731
+ *                                                  leave behind the last pop; with queued = 0 there is no pop and :687 gives the same)
+ * round(v) = (size_t) floor(v + 0.5) (UNVERIFIED vs cpl: cpl::Math::round is not in the tree; this is the library's rule).  smoothing
+ * finite in [0, 1), z finite >= 0: else SGZ_EINVAL. */
+sgz_status sgz_frame_pacing_step(double z, double smoothing, uint32_t queued, uint32_t *pop, double *z_next);
+/* The two kernels behind them as stateless stage calls: asynchronous on `stream`, DEVICE pointers, nothing waited for; a null pointer is
+ * SGZ_EINVAL.  Both only move texels.
+ * sgz_columns_to_image_device: n RGBA8 columns [n][P] into an image [P rows][pitch_bytes] of the bound image's layout (row y = axis point
+ *   y): texel ((x0 + k) % columns, y) = d_columns[k][y] -- what oglImage.updateSingleColumn(framePixelPosition, ...) uploads for n popped
+ *   frames in a row (SpectrumRendering.cpp:721-724), or a whole sgz_spectrogram_render_device result [frames][P] as a texture.  1 <= n <=
+ *   columns < 2^31, x0 < columns, 1 <= P <= 2^20, pitch_bytes >= 4 * columns and a multiple of 4, both pointers 4-byte aligned.  Texels
+ *   of other columns and beyond `columns` in a wider pitch are not touched.
+ * sgz_image_unroll_device: drawCircular(x / (columns - 1)) (:742-744; UNVERIFIED vs cpl: cpl's OpenGLImageDrawer is not in the tree; this
+ *   is the library's rule): dst[y][j] = src[y][(x + j) % columns] for j < columns -- column x (the oldest, the next to be overwritten) at
+ *   the left, x - 1 (the newest) at the right.  x < columns < 2^31, 1 <= P <= 2^20, pitches as above.  d_src and d_dst must not overlap
+ *   (SGZ_EINVAL); texels beyond `columns` in a wider destination pitch are not touched. */
+sgz_status sgz_columns_to_image_device(const uint8_t *d_columns /*[n][P][4]*/, size_t n, uint32_t axis_points, void *d_image,
+                                       uint32_t columns, size_t pitch_bytes, uint32_t x0, void *stream);
+sgz_status sgz_image_unroll_device(const void *d_src, uint32_t columns, size_t src_pitch_bytes, uint32_t axis_points, uint32_t x, void *d_dst,
+                                   size_t dst_pitch_bytes, void *stream);
 /* Zoom / pan (consumer thread): Spectrum::handleFlagUpdates' viewChanged branch (Spectrum.cpp:532-575) for a change of viewLeft /
  * viewRight only -- what mouseWheelMove / mouseDrag (:172-290) cause.  The view is checked as sgz_spectrum_configure checks it (finite,
  * 0 <= left < right <= 1); SGZ_EINVAL leaves the handle exactly as it was.  Every other field stays as configured (a change of scaling or

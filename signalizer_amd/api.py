@@ -171,6 +171,8 @@ EXPORTS = [
     "sgz_spectrum_update", "sgz_spectrum_update_effects", "sgz_ring_resize_device",
     "sgz_scope_set_mix", "sgz_vector_set_mix",
     "sgz_scope_set_tempo", "sgz_scope_effective_window", "sgz_scope_time_window",
+    "sgz_spectrum_set_pacing", "sgz_spectrum_set_frozen", "sgz_spectrum_render_columns", "sgz_spectrum_present", "sgz_frame_pacing_step",
+    "sgz_columns_to_image_device", "sgz_image_unroll_device",
 ]
 
 
@@ -334,6 +336,13 @@ def lib() -> C.CDLL:
     L.sgz_spectrum_update.argtypes = [vp, C.POINTER(SpectrumConfig)]
     L.sgz_spectrum_update_effects.argtypes = [C.POINTER(SpectrumConfig), C.POINTER(SpectrumConfig), C.POINTER(u32)]
     L.sgz_ring_resize_device.argtypes = [vp, u32, vp, u32, u32, C.c_uint64, vp]
+    L.sgz_spectrum_set_pacing.argtypes = [vp, dbl]
+    L.sgz_spectrum_set_frozen.argtypes = [vp, C.c_int]
+    L.sgz_spectrum_render_columns.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(dbl)]
+    L.sgz_spectrum_present.argtypes = [vp, vp, sz]
+    L.sgz_frame_pacing_step.argtypes = [dbl, dbl, u32, C.POINTER(u32), C.POINTER(dbl)]
+    L.sgz_columns_to_image_device.argtypes = [vp, sz, u32, vp, u32, sz, u32, vp]
+    L.sgz_image_unroll_device.argtypes = [vp, u32, sz, u32, u32, vp, sz, vp]
     L.sgz_scope_num_points.argtypes = [C.POINTER(ScopeView)]
     L.sgz_scope_num_points.restype = sz
     L.sgz_scope_lanczos_device.argtypes = [C.POINTER(ScopeView), vp, sz, sz, u32, vp, vp]
@@ -500,6 +509,51 @@ def ring_resize_device(old_ring, old_cap: int, new_ring, new_cap: int, channels:
     torch tensors or device pointers); enqueued on `stream`, not waited for"""
     check(lib().sgz_ring_resize_device(_dev_ptr(old_ring), old_cap, _dev_ptr(new_ring), new_cap, channels, written,
                                        C.c_void_p(stream) if stream else None))
+
+
+def frame_pacing_step(z: float, smoothing: float, queued: int):
+    """one pass of renderColourSpectrum's pop loop (sgz_frame_pacing_step; host only): (columns popped, framesPerUpdate afterwards)"""
+    pop, z_next = C.c_uint32(0), C.c_double(0.0)
+    check(lib().sgz_frame_pacing_step(z, smoothing, queued, C.byref(pop), C.byref(z_next)))
+    return pop.value, z_next.value
+
+
+def spectrum_set_pacing(handle, frame_update_smoothing: float) -> None:
+    """sgz_spectrum_set_pacing: content->frameUpdateSmoothing of a colour-spectrum handle, in [0, 1)"""
+    check(lib().sgz_spectrum_set_pacing(handle, float(frame_update_smoothing)))
+
+
+def spectrum_set_frozen(handle, frozen: bool) -> None:
+    """sgz_spectrum_set_frozen: Spectrum::freeze / unfreeze"""
+    check(lib().sgz_spectrum_set_frozen(handle, int(bool(frozen))))
+
+
+def spectrum_render_columns(handle):
+    """sgz_spectrum_render_columns: one video frame's pop loop into the bound image: (status SGZ_OK / SGZ_EMPTY, first column, count,
+    framesPerUpdate afterwards)"""
+    first, cnt, fpu = C.c_uint32(0), C.c_uint32(0), C.c_double(0.0)
+    st = check(lib().sgz_spectrum_render_columns(handle, C.byref(first), C.byref(cnt), C.byref(fpu)))
+    return st, first.value, cnt.value, fpu.value
+
+
+def spectrum_present(handle, dst, dst_pitch_bytes: int) -> None:
+    """sgz_spectrum_present: the bound ring image unrolled (oldest column at the left) into `dst`, DEVICE [P][dst_pitch_bytes] (a torch
+    tensor or a device pointer); waits for the texels"""
+    check(lib().sgz_spectrum_present(handle, _dev_ptr(dst), dst_pitch_bytes))
+
+
+def columns_to_image_device(columns_rgba, n: int, axis_points: int, image, columns: int, pitch_bytes: int, x0: int = 0, stream=None) -> None:
+    """sgz_columns_to_image_device: DEVICE columns [n][P] RGBA8 into a DEVICE image [P][pitch_bytes] at texel columns (x0 + k) % columns
+    (torch tensors or device pointers); enqueued on `stream`, not waited for"""
+    check(lib().sgz_columns_to_image_device(_dev_ptr(columns_rgba), n, axis_points, _dev_ptr(image), columns, pitch_bytes, x0,
+                                            C.c_void_p(stream) if stream else None))
+
+
+def image_unroll_device(src, columns: int, src_pitch_bytes: int, axis_points: int, x: int, dst, dst_pitch_bytes: int, stream=None) -> None:
+    """sgz_image_unroll_device: dst[y][j] = src[y][(x + j) % columns] (DEVICE images: torch tensors or device pointers, not overlapping);
+    enqueued on `stream`, not waited for"""
+    check(lib().sgz_image_unroll_device(_dev_ptr(src), columns, src_pitch_bytes, axis_points, x, _dev_ptr(dst), dst_pitch_bytes,
+                                        C.c_void_p(stream) if stream else None))
 
 
 RT_OPT_STRICT_REFERENCE_QUIRKS, RT_OPT_AUDIO_HISTORY, RT_OPT_DEFER_SUBMIT, RT_OPT_PARK_PUSHES = 1, 2, 3, 4

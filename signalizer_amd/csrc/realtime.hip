@@ -45,6 +45,11 @@
 // (c) an OpenGL buffer object of a context on the same device, registered and mapped through HIP's GL interop
 // (sgz_spectrum_bind_gl_buffer).
 //
+// The render thread's loop as the plugin runs it (renderColourSpectrum, SpectrumRendering.cpp:672-749): sgz_spectrum_render_columns is
+// flush_columns inside the reference's pop loop -- frame pacing (framesPerUpdate / frameUpdateSmoothing, :681-735) and freeze (:679) -- with
+// all the columns a video frame takes written by ONE launch; sgz_spectrum_present is drawCircular (:742-744), the ring image unrolled into
+// the caller's device memory (spectrum_present.hip has both kernels).
+//
 // Zoom / pan (sgz_spectrum_set_view, consumer thread; handleFlagUpdates' viewChanged branch, Spectrum.cpp:532-575): the new view's plans
 // are built outside cfgMu; under it the producer's stream is drained, the plans are swapped and warmed up, and the line graphs cleared.
 // The ring, the cadence, the column queue and the image binding stay; the bound image is translated afterwards (view_translate.hip).
@@ -170,6 +175,11 @@ struct sgz_spectrum {
     bool imgOwned = false; size_t imgOwnedBytes = 0;           // (create_image: the allocation's size)
     hipGraphicsResource *glResource = nullptr;
     float *d_viewScratch = nullptr; size_t viewScratchCap = 0;    // sgz_spectrum_set_view: the row table and the image copy it gathers from (floats)
+    // renderColourSpectrum's own state (consumer thread, sgz_spectrum_render_columns): framesPerUpdate, content->frameUpdateSmoothing and
+    // state.isFrozen.  Nothing but the pop loop assigns framesPerUpdate after the constructor's zero (Spectrum.cpp:59), so no setup, resize,
+    // update or binding touches the three
+    double framesPerUpdate = 0.0, frameUpdateSmoothing = 0.0;
+    bool frozen = false;
 };
 
 // the buffers whose size is the axis size P: setup() allocates them with the rest, sgz_spectrum_resize replaces them.  h_cols / d_colsQ
@@ -732,6 +742,124 @@ sgz_status sgz_spectrum_flush_columns(sgz_spectrum *s, uint32_t *first_column, u
     if (first_column) *first_column = first;
     if (count) *count = n;
     return n ? SGZ_OK : SGZ_EMPTY;
+}
+
+// the bound image as device memory (a GL buffer is HIP's only between map and unmap: flush_columns), and its release again -- `drain`:
+// behind a failed step, whose launches must not outlive the mapping
+static sgz_status mapBoundImage(sgz_spectrum *s, uint8_t **image)
+{
+    *image = s->d_image;
+    hipGraphicsResource *gl = s->glResource;
+    if (!gl) return SGZ_OK;
+    void *ptr = nullptr; size_t size = 0;
+    SGZ_HIP(hipGraphicsMapResources(1, &gl, s->outStream));
+    const hipError_t e = hipGraphicsResourceGetMappedPointer(&ptr, &size, gl);
+    if (e != hipSuccess) { (void)hipGraphicsUnmapResources(1, &gl, s->outStream); return hipFail(e, "hipGraphicsResourceGetMappedPointer"); }
+    *image = static_cast<uint8_t *>(ptr);
+    return SGZ_OK;
+}
+
+static sgz_status unmapBoundImage(sgz_spectrum *s, bool drain)
+{
+    hipGraphicsResource *gl = s->glResource;
+    if (!gl) return SGZ_OK;
+    if (drain) (void)hipStreamSynchronize(s->outStream);
+    SGZ_HIP(hipGraphicsUnmapResources(1, &gl, s->outStream));
+    return SGZ_OK;
+}
+
+static sgz_status colourHandleWithImage(const sgz_spectrum *s)
+{
+    if (!s) return fail(SGZ_EINVAL, "null handle");
+    if (s->plan->cfg.display_mode == SGZ_DISPLAY_LINE_GRAPH) return fail(SGZ_EINVAL, "a LINE_GRAPH handle has no colour columns (sgz_spectrum_config::display_mode)");
+    if (!s->d_image && !s->glResource) return fail(SGZ_EINVAL, "no image bound");
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrum_set_pacing(sgz_spectrum *s, double frame_update_smoothing)
+{
+    if (!s) return fail(SGZ_EINVAL, "null handle");
+    if (s->plan->cfg.display_mode == SGZ_DISPLAY_LINE_GRAPH) return fail(SGZ_EINVAL, "a LINE_GRAPH handle has no colour columns (sgz_spectrum_config::display_mode)");
+    if (!validSmoothing(frame_update_smoothing)) return fail(SGZ_EINVAL, "frame_update_smoothing: finite, 0 <= smoothing < 1");
+    s->frameUpdateSmoothing = frame_update_smoothing;
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrum_set_frozen(sgz_spectrum *s, int frozen)
+{
+    if (!s) return fail(SGZ_EINVAL, "null handle");
+    if (s->plan->cfg.display_mode == SGZ_DISPLAY_LINE_GRAPH) return fail(SGZ_EINVAL, "a LINE_GRAPH handle has no colour columns (sgz_spectrum_config::display_mode)");
+    s->frozen = frozen != 0;
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrum_render_columns(sgz_spectrum *s, uint32_t *first_column, uint32_t *count, double *frames_per_update)
+{
+    if (sgz_status st = colourHandleWithImage(s); st != SGZ_OK) return st;
+    if (first_column) *first_column = s->imgX;
+    if (count) *count = 0;
+    if (frames_per_update) *frames_per_update = s->framesPerUpdate;
+    if (s->frozen) return SGZ_EMPTY;                           // :679: the queue is left to the producer, which drops what does not fit
+    const Plan &p = *s->plan;
+    const double z = s->framesPerUpdate, smoothing = s->frameUpdateSmoothing;
+    const uint64_t head0 = s->colQ.consumerHead();
+    auto stored = [&](uint64_t head) { return s->colQ.tail.load(std::memory_order_acquire) - head; };   // getApproximateStoredFrames()
+    // :686-691 (processedFrames is 0 here)
+    double z1 = pacedFramesPerUpdate(stored(head0), smoothing, z);
+    const uint64_t framesThisTime = pacedFramesThisTime(z);
+    const bool shouldCap = smoothing != 0.0;
+    // the slots go back to the producer behind the launch, so a call takes at most the queue's depth; and at most one lap of the image,
+    // so that `first` / `count` describe the dirty range unambiguously (flush_columns)
+    const uint32_t most = std::min<uint32_t>(kQueueDepth, s->imgColumns);
+    uint32_t n = 0;
+    uint64_t head = head0;
+    while (n < most && (!shouldCap || n < framesThisTime)) {   // (n is processedFrames where the reference compares it: :693)
+        if (!s->colQ.consumerHas(head)) break;                  // popElement fails: the queue is empty ...
+        const hipError_t q = hipEventQuery(s->colEvents[int(head % kQueueDepth)]);
+        if (q == hipErrorNotReady) break;                       // ... or its first column has not landed yet
+        if (q != hipSuccess) return hipFail(q, "hipEventQuery");
+        ++head; ++n;
+        if (!shouldCap) z1 = pacedFramesPerUpdate(stored(head), smoothing, z);   // :727-731 (processedFrames stays 0 behind `!shouldCap ||`)
+    }
+    if (n) {
+        uint8_t *image = nullptr;
+        if (sgz_status st = mapBoundImage(s, &image); st != SGZ_OK) return st;
+        sgz_status st = launchColumnsToImage(s->d_colsQ, uint32_t(head0 % kQueueDepth), kQueueDepth, n, p.P, image, s->imgColumns, s->imgPitch,
+                                             s->imgX, s->outStream);
+        if (st == SGZ_OK) {
+            const hipError_t e = hipStreamSynchronize(s->outStream);   // the texels are in place before the slots go back to the producer
+            if (e != hipSuccess) st = hipFail(e, "hipStreamSynchronize");
+        }
+        const sgz_status su = unmapBoundImage(s, st != SGZ_OK);
+        if (st != SGZ_OK) return st;
+        if (su != SGZ_OK) return su;
+        s->colQ.consumerRelease(head);
+        s->imgX = uint32_t((uint64_t(s->imgX) + n) % s->imgColumns);   // framePixelPosition (:723-724)
+    }
+    s->framesPerUpdate = z1;                                    // :735
+    if (count) *count = n;
+    if (frames_per_update) *frames_per_update = z1;
+    return n ? SGZ_OK : SGZ_EMPTY;
+}
+
+sgz_status sgz_spectrum_present(sgz_spectrum *s, void *d_dst, size_t dst_pitch_bytes)
+{
+    if (sgz_status st = colourHandleWithImage(s); st != SGZ_OK) return st;
+    if (!d_dst) return fail(SGZ_EINVAL, "null argument");
+    if (!validImageLayout(d_dst, s->imgColumns, dst_pitch_bytes)) return fail(SGZ_EINVAL, "destination: pitch >= 4 * columns, 4-byte aligned");
+    const uint32_t P = s->plan->P;
+    uint8_t *image = nullptr;
+    if (sgz_status st = mapBoundImage(s, &image); st != SGZ_OK) return st;
+    sgz_status st = imagesOverlap(image, s->imgPitch, s->imgColumns, d_dst, dst_pitch_bytes, s->imgColumns, P)
+                        ? fail(SGZ_EINVAL, "the destination overlaps the bound image")
+                        : launchImageUnroll(image, s->imgColumns, s->imgPitch, P, s->imgX % s->imgColumns, static_cast<uint8_t *>(d_dst),
+                                            dst_pitch_bytes, s->outStream);
+    if (st == SGZ_OK) {
+        const hipError_t e = hipStreamSynchronize(s->outStream);
+        if (e != hipSuccess) st = hipFail(e, "hipStreamSynchronize");
+    }
+    const sgz_status su = unmapBoundImage(s, st != SGZ_OK);
+    return st != SGZ_OK ? st : su;
 }
 
 // freeLinearVerticalTranslation(oldViewRect, viewRect) of the bound image (view_translate.hip), a GL buffer mapped around it as in

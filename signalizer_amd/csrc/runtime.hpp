@@ -40,6 +40,18 @@ sgz_status resizeImage(const uint8_t *src, uint32_t C0, size_t srcPitch, uint32_
 // the spectrum handle's update).  resizeRing enqueues on `stream` and waits for nothing
 bool validRingResize(const float *d_old, uint32_t oldCap, const float *d_new, uint32_t newCap, uint32_t channels);
 sgz_status resizeRing(const float *d_old, uint32_t oldCap, float *d_new, uint32_t newCap, uint32_t channels, uint64_t written, hipStream_t stream);
+// spectrum_present.hip: renderColourSpectrum's frame pacing (:687 / :730 and round(framesPerUpdate), :688), the columns of one video frame
+// into the image in one launch (column k = d_columns[(slot0 + k) mod ring], at texel column (x0 + k) mod columns) and drawCircular
+// (sgz_columns_to_image_device / sgz_image_unroll_device; the spectrum handle's render_columns / present).  The launches enqueue on
+// `stream` and wait for nothing; their arguments are the stage calls', checked by the caller
+bool validSmoothing(double smoothing);
+double pacedFramesPerUpdate(uint64_t approximateFrames, double smoothing, double framesPerUpdate);
+uint64_t pacedFramesThisTime(double framesPerUpdate);
+bool imagesOverlap(const void *a, size_t aPitch, uint32_t aColumns, const void *b, size_t bPitch, uint32_t bColumns, uint32_t P);
+sgz_status launchColumnsToImage(const uint8_t *d_columns, uint32_t slot0, uint32_t ring, size_t n, uint32_t P, uint8_t *d_image,
+                                uint32_t columns, size_t pitch, uint32_t x0, hipStream_t stream);
+sgz_status launchImageUnroll(const uint8_t *d_src, uint32_t columns, size_t srcPitch, uint32_t P, uint32_t x, uint8_t *d_dst, size_t dstPitch,
+                             hipStream_t stream);
 int numCUs();
 // K_A over `frames` frames (ideal STFT framing from d_planar); any of mapped/binsOut may be null
 // deferLate: the caller's next call is runDecayColour on the same d_mapped with only an image wanted -- a channel-split launch may then
