@@ -978,6 +978,35 @@ void      *sgz_scope_stream(sgz_scope *s);
  * Vulkan imported -- without the D2H copy.  In place when the call returns. */
 sgz_status sgz_scope_vertices_device(sgz_scope *s, const sgz_scope_view *view, uint32_t evaluator, uint32_t channel, float *d_xyz,
                                      uint8_t *d_rgba, uint32_t *count);
+/* The dense stream: the frame's sample-space Linear strip reduced on the device to a minimum and a maximum vertex per column -- what a
+ * host draws when the window holds many samples per pixel (pixelsPerSample < 1, where drawWavePlot itself falls back to Linear and
+ * sgz_scope_vertices returns one vertex per sample).  The reference has no counterpart.
+ * V[0 .. n) is the Linear strip of the current frame, exactly what sgz_scope_vertices writes for a view below one pixel per sample
+ * (or under SGZ_SUBSAMPLE_LINEAR): V[i] = (i, sample, 0) + RGBA8, n = max(2, ceil(window)) + quantizedCycleSamples; it depends on
+ * neither sgz_scope_config::interpolation nor a view.  cols = min(columns, n); column b holds the indices
+ * ceil(b n / cols) <= i < ceil((b + 1) n / cols).  lo(b): the lowest index whose y equals the minimum of the column's non-NaN y
+ * (IEEE `<`: -0 and +0 tie, ties go to the lowest index); hi(b) likewise for the maximum; both the column's first index when every y is
+ * NaN.  The stream is 2 cols vertices: column b gives V[min(lo, hi)] then V[max(lo, hi)] (twice the same vertex when they are equal),
+ * xyz and RGBA8 copied bit for bit -- a subsequence of V, drawn with V's matrix and primitive (x is the sample index).
+ * 0 for a NULL handle or columns == 0. */
+size_t     sgz_scope_dense_vertex_count(const sgz_scope *s, uint32_t columns);
+/* One evaluator's dense strip; evaluator / channel / xyz / rgba (may be NULL) / *count and the rules for pinned and pageable host
+ * buffers as sgz_scope_vertices.  SGZ_EINVAL (nothing written, the handle untouched): columns == 0, an evaluator or channel out of
+ * range, NULL xyz or count, *count < the need (*count then holds it). */
+sgz_status sgz_scope_dense_vertices(sgz_scope *s, uint32_t columns, uint32_t evaluator, uint32_t channel, float *xyz, uint8_t *rgba,
+                                    uint32_t *count);
+/* Several evaluators' dense strips of one frame, enqueued back to back, ONE wait; host or (all of them) DEVICE buffers, as
+ * sgz_scope_vertices_all. */
+sgz_status sgz_scope_dense_vertices_all(sgz_scope *s, uint32_t columns, uint32_t items, const uint32_t *evaluators, const uint32_t *channels,
+                                        float *const *xyz, uint8_t *const *rgba, uint32_t *counts);
+/* ... into DEVICE buffers, as sgz_scope_vertices_device.  In place when the call returns. */
+sgz_status sgz_scope_dense_vertices_device(sgz_scope *s, uint32_t columns, uint32_t evaluator, uint32_t channel, float *d_xyz,
+                                           uint8_t *d_rgba, uint32_t *count);
+/* The same reduction as a stage call on rings in time order (d_ring / len / stride / channels as sgz_scope_lanczos_device): V is the
+ * newest n samples, V[i] = (i, ring[(len - n + i) mod len]); d_xy: DEVICE float2 [channels][2 min(columns, n)].  Enqueued on
+ * `stream`, no wait; scratch is allocated and freed in stream order.  len, n < 2^31. */
+sgz_status sgz_scope_dense_device(const float *d_ring, size_t len, size_t stride, uint32_t channels, size_t n, uint32_t columns,
+                                  float *d_xy, void *stream);
 /* parity hooks: front buffer memory of one channel (begin()) + its write cursor; TriggeringProcessor counters
  * {frontOrigin, bufferedSamples, oldPeak, currentPeak, steadyClock, peaks.size(), isWorkingOnPeak, swaps} */
 sgz_status sgz_scope_front(sgz_scope *s, uint32_t channel, float *out /*size*/, uint32_t *size, uint32_t *cursor);

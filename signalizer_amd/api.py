@@ -173,6 +173,8 @@ EXPORTS = [
     "sgz_scope_set_tempo", "sgz_scope_effective_window", "sgz_scope_time_window",
     "sgz_spectrum_set_pacing", "sgz_spectrum_set_frozen", "sgz_spectrum_render_columns", "sgz_spectrum_present", "sgz_frame_pacing_step",
     "sgz_columns_to_image_device", "sgz_image_unroll_device",
+    "sgz_scope_dense_vertex_count", "sgz_scope_dense_vertices", "sgz_scope_dense_vertices_all", "sgz_scope_dense_vertices_device",
+    "sgz_scope_dense_device",
 ]
 
 
@@ -300,6 +302,12 @@ def lib() -> C.CDLL:
     L.sgz_scope_vertices_device.argtypes = [vp, C.POINTER(ScopeView), u32, u32, vp, vp, C.POINTER(u32)]
     L.sgz_scope_vertices_all.argtypes = [vp, C.POINTER(ScopeView), u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
     L.sgz_vector_vertices_device.argtypes = [vp, u32, vp, vp, C.POINTER(u32)]
+    L.sgz_scope_dense_vertex_count.argtypes = [vp, u32]
+    L.sgz_scope_dense_vertex_count.restype = sz
+    L.sgz_scope_dense_vertices.argtypes = [vp, u32, u32, u32, vp, vp, C.POINTER(u32)]
+    L.sgz_scope_dense_vertices_device.argtypes = [vp, u32, u32, u32, vp, vp, C.POINTER(u32)]
+    L.sgz_scope_dense_vertices_all.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
+    L.sgz_scope_dense_device.argtypes = [vp, sz, sz, u32, sz, u32, vp, vp]
     L.sgz_export_alloc.argtypes = [sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]
     L.sgz_export_free.argtypes = [vp]
     L.sgz_export_free.restype = None
@@ -833,6 +841,16 @@ def time_window(time_mode: int, value: float, sample_rate: float, bpm: float = 0
     return lib().sgz_scope_time_window(int(time_mode), float(value), float(sample_rate), float(bpm), float(cycle_samples))
 
 
+def scope_dense_device(ring, n: int, columns: int, xy, length: int | None = None, stride: int | None = None, stream=None) -> None:
+    """sgz_scope_dense_device: ring DEVICE float32 [channels][stride] in time order (the first `length` of each row), xy DEVICE float32
+    [channels][2 min(columns, n)][2]; the per-column min / max vertices of the newest n samples.  Enqueued on `stream`, no wait."""
+    channels = int(ring.shape[0])
+    stride = int(ring.shape[1]) if stride is None else int(stride)
+    length = stride if length is None else int(length)
+    check(lib().sgz_scope_dense_device(_buf_ptr(ring), length, stride, channels, int(n), int(columns), _buf_ptr(xy),
+                                       C.c_void_p(stream) if stream else None))
+
+
 class Scope:
     """sgz_scope_* handle: the Oscilloscope's audio-thread state machine in HBM + drawWavePlot vertices."""
 
@@ -975,6 +993,39 @@ class Scope:
         cs = (C.c_void_p * k)(*[o[1].ctypes.data if o[1] is not None else None for o in out])
         cnt = (C.c_uint32 * k)(*[o[0].shape[0] for o in out])
         check(lib().sgz_scope_vertices_all(self.h, C.byref(view), k, ev, ch, xs, cs if want else None, cnt))
+        return [(o[0][:cnt[i]], o[1][:cnt[i]] if o[1] is not None else None) for i, o in enumerate(out)]
+
+    def dense_vertex_count(self, columns: int) -> int:
+        """sgz_scope_dense_vertex_count: 2 min(columns, n) for the current frame"""
+        return lib().sgz_scope_dense_vertex_count(self.h, int(columns))
+
+    def dense_vertices(self, columns: int, evaluator: int, channel: int = 0, want_colours: bool = True, out=None):
+        """sgz_scope_dense_vertices: the Linear strip's minimum and maximum vertex per column.  out: (xyz [>= 2 cols][3], rgba
+        [>= 2 cols][4] or None), numpy arrays or torch tensors (host, pinned or device) the caller keeps; default: fresh arrays"""
+        n = self.dense_vertex_count(columns)
+        if out is not None:
+            xyz, rgba = out
+            want_colours = rgba is not None
+            cap = int(xyz.shape[0])
+        else:
+            xyz = np.empty((n, 3), np.float32)
+            rgba = np.empty((n, 4), np.uint8) if want_colours else None
+            cap = n
+        cnt = C.c_uint32(cap)
+        check(lib().sgz_scope_dense_vertices(self.h, int(columns), evaluator, channel, _buf_ptr(xyz),
+                                             _buf_ptr(rgba) if want_colours else None, C.byref(cnt)))
+        return xyz[:cnt.value], (rgba[:cnt.value] if want_colours else None)
+
+    def dense_vertices_all(self, columns: int, evaluators, channels, out):
+        """sgz_scope_dense_vertices_all: out = [(xyz, rgba or None), ...] one per item (numpy arrays or torch tensors, host or all of
+        them device); the strips are enqueued back to back, one wait"""
+        k = len(evaluators)
+        ev = (C.c_uint32 * k)(*evaluators); ch = (C.c_uint32 * k)(*channels)
+        xs = (C.c_void_p * k)(*[_buf_ptr(o[0]).value for o in out])
+        want = any(o[1] is not None for o in out)
+        cs = (C.c_void_p * k)(*[_buf_ptr(o[1]).value if o[1] is not None else None for o in out])
+        cnt = (C.c_uint32 * k)(*[int(o[0].shape[0]) for o in out])
+        check(lib().sgz_scope_dense_vertices_all(self.h, int(columns), k, ev, ch, xs, cs if want else None, cnt))
         return [(o[0][:cnt[i]], o[1][:cnt[i]] if o[1] is not None else None) for i, o in enumerate(out)]
 
 

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "rt_common.hpp"
+#include "scope_ring.hpp"
 
 #pragma clang fp contract(off)
 
@@ -64,6 +65,11 @@ hipError_t launchScopeVertices(const sgz_scope_view &view, uint32_t triggerMode,
                                double cycleSamples, double sampleOffset, long long transport, uint32_t rgba, const uint32_t *colRing, float *d_xyz,
                                uint32_t *d_rgba, size_t capacity, size_t *points, hipStream_t stream);
 size_t scopeVertexCount(const sgz_scope_view &view, uint32_t interpolation, uint32_t triggerMode, double cycleSamples);
+// scope_dense.hip: the per-column min / max reduction of the Linear strip
+size_t scopeDenseScratchBytes(size_t n, uint32_t columns);
+hipError_t launchScopeDense(const float *ringA, const float *ringB, uint32_t evalMode, uint32_t size, uint32_t cap, const uint32_t *d_cursor,
+                            size_t n, long start0, uint32_t columns, uint32_t key, const uint32_t *colRing, float *d_xyz, uint32_t *d_rgba,
+                            void *scratch, size_t *points, hipStream_t stream);
 }
 
 namespace {
@@ -1371,6 +1377,7 @@ struct sgz_scope {
     // vertex output (consumer side)
     float *d_xyz = nullptr; uint32_t *d_rgba = nullptr; size_t vertexCap = 0;
     void *h_out = nullptr; size_t hOutBytes = 0;          // pinned
+    void *d_dense = nullptr; size_t denseBytes = 0;       // partial records of the dense stream's long columns (scope_dense.hip)
     uint64_t busy = 0;
 };
 
@@ -1383,7 +1390,7 @@ static void scopeFree(sgz_scope *s)
     s->mix.release();
     for (void *p : {(void *)s->d_state, (void *)s->d_peaks, (void *)s->d_swaps, (void *)s->d_front, (void *)s->d_back, (void *)s->d_xyz,
                     (void *)s->d_rgba, (void *)s->col.st, (void *)s->col.bands, (void *)s->col.sm, (void *)s->col.block, (void *)s->col.front,
-                    (void *)s->col.back, (void *)s->d_spectral, (void *)s->d_tw, (void *)s->d_col})
+                    (void *)s->col.back, (void *)s->d_spectral, (void *)s->d_tw, (void *)s->d_col, s->d_dense})
         if (p) (void)hipFree(p);
     if (s->h_out) (void)hipHostFree(s->h_out);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -1976,15 +1983,9 @@ static sgz_status scopeVerticesPairInto(sgz_scope *s, const sgz_scope_view *view
     return SGZ_OK;
 }
 
-sgz_status sgz_scope_vertices(sgz_scope *s, const sgz_scope_view *view, uint32_t evaluator, uint32_t channel, float *xyz, uint8_t *rgba,
-                              uint32_t *count)
+// the handle's own vertex buffers (device + pinned bounce) hold `need` vertices
+static sgz_status scopeReserveVertices(sgz_scope *s, size_t need)
 {
-    if (!s || !view || !xyz || !count) return fail(SGZ_EINVAL, "null argument");
-    if (view->width < 2 || !(view->right > view->left)) return fail(SGZ_EINVAL, "bad view");
-    sgz_scope_view v = *view;
-    v.window_size = s->effWindow;
-    const size_t need = scopeVertexCount(v, s->cfg.interpolation, s->cfg.trigger_mode, s->trig.cycle_samples);
-    if (need > *count) { *count = uint32_t(need); return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
     if (s->vertexCap < need) {
         if (s->d_xyz) (void)hipFree(s->d_xyz);
         if (s->d_rgba) (void)hipFree(s->d_rgba);
@@ -1995,6 +1996,19 @@ sgz_status sgz_scope_vertices(sgz_scope *s, const sgz_scope_view *view, uint32_t
         SGZ_HIP(hipHostMalloc(&s->h_out, need * 16, hipHostMallocDefault));
         s->vertexCap = need;
     }
+    return SGZ_OK;
+}
+
+sgz_status sgz_scope_vertices(sgz_scope *s, const sgz_scope_view *view, uint32_t evaluator, uint32_t channel, float *xyz, uint8_t *rgba,
+                              uint32_t *count)
+{
+    if (!s || !view || !xyz || !count) return fail(SGZ_EINVAL, "null argument");
+    if (view->width < 2 || !(view->right > view->left)) return fail(SGZ_EINVAL, "bad view");
+    sgz_scope_view v = *view;
+    v.window_size = s->effWindow;
+    const size_t need = scopeVertexCount(v, s->cfg.interpolation, s->cfg.trigger_mode, s->trig.cycle_samples);
+    if (need > *count) { *count = uint32_t(need); return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
+    if (sgz_status rs = scopeReserveVertices(s, need); rs != SGZ_OK) return rs;
     size_t points = 0;
     // pinned, device-mapped destinations: the vertex kernel writes them itself (2.4 MB per evaluator at cfg3: the DMA copy behind the
     // kernel was most of a rendered frame's GPU time)
@@ -2069,6 +2083,120 @@ sgz_status sgz_scope_vertices_device(sgz_scope *s, const sgz_scope_view *view, u
     size_t points = 0;
     const sgz_status st = scopeVerticesInto(s, view, evaluator, channel, d_xyz, reinterpret_cast<uint32_t *>(d_rgba), need, &points);
     if (st != SGZ_OK) return st;
+    SGZ_HIP(hipStreamSynchronize(s->stream));                 // the vertices are in place when the call returns
+    *count = uint32_t(points);
+    return SGZ_OK;
+}
+
+// ---- the dense stream (scope_dense.hip): the frame's Linear strip reduced to a min and a max vertex per column
+static LinearExtent scopeDenseExtent(const sgz_scope *s)
+{
+    return scopeLinearExtent(s->effWindow, s->cfg.trigger_mode, s->trig.cycle_samples, s->transport.load(std::memory_order_relaxed));
+}
+
+size_t sgz_scope_dense_vertex_count(const sgz_scope *s, uint32_t columns)
+{
+    if (!s || columns == 0) return 0;
+    return 2 * std::min<size_t>(columns, scopeDenseExtent(s).n);
+}
+
+// what every dense call checks before it touches the handle; *need = 2 min(columns, n)
+static sgz_status scopeDenseCheck(sgz_scope *s, uint32_t columns, uint32_t evaluator, uint32_t channel, size_t *need)
+{
+    if (columns == 0) return fail(SGZ_EINVAL, "columns == 0");
+    StripSource src;
+    if (sgz_status st = scopeStripSource(s, evaluator, channel, false, &src); st != SGZ_OK) return st;
+    *need = sgz_scope_dense_vertex_count(s, columns);
+    return SGZ_OK;
+}
+
+// one evaluator's dense strip into DEVICE buffers, enqueued behind the blocks that wait (flush on read); no wait
+static sgz_status scopeDenseInto(sgz_scope *s, uint32_t columns, uint32_t evaluator, uint32_t channel, float *d_xyz, uint32_t *d_rgba,
+                                 size_t *points)
+{
+    if (sgz_status sy = scopeSync(s); sy != SGZ_OK) return sy;
+    StripSource src;
+    if (sgz_status st = scopeStripSource(s, evaluator, channel, d_rgba != nullptr, &src); st != SGZ_OK) return st;
+    const LinearExtent ext = scopeDenseExtent(s);
+    // the long columns' partial records: the handle's own, in stream order behind the previous strip's
+    if (const size_t bytes = scopeDenseScratchBytes(ext.n, columns); bytes > s->denseBytes) {
+        if (s->d_dense) (void)hipFree(s->d_dense);
+        s->d_dense = nullptr; s->denseBytes = 0;
+        SGZ_HIP(hipMalloc(&s->d_dense, bytes));
+        s->denseBytes = bytes;
+    }
+    SGZ_HIP(launchScopeDense(src.ringA, src.ringB, src.evalMode, uint32_t(s->trig.ring_size), s->size,
+                             reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s->d_state) + offsetof(ScopeDev, frontCursor)),
+                             ext.n, -ext.bufferOffset, columns, src.key, src.colRing, d_xyz, d_rgba, s->d_dense, points, s->stream));
+    return SGZ_OK;
+}
+
+sgz_status sgz_scope_dense_vertices(sgz_scope *s, uint32_t columns, uint32_t evaluator, uint32_t channel, float *xyz, uint8_t *rgba,
+                                    uint32_t *count)
+{
+    if (!s || !xyz || !count) return fail(SGZ_EINVAL, "null argument");
+    size_t need = 0, points = 0;
+    if (sgz_status st = scopeDenseCheck(s, columns, evaluator, channel, &need); st != SGZ_OK) return st;
+    if (need > *count) { *count = uint32_t(need); return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
+    void *mx = mappedDevicePointer(xyz, s->stream), *mc = rgba ? mappedDevicePointer(rgba, s->stream) : nullptr;
+    if (mx && (!rgba || mc)) {                                // pinned, device-mapped (or device) buffers: the kernel writes them itself
+        if (sgz_status sd = scopeDenseInto(s, columns, evaluator, channel, static_cast<float *>(mx), static_cast<uint32_t *>(mc), &points); sd != SGZ_OK)
+            return sd;
+        SGZ_HIP(hipStreamSynchronize(s->stream));
+        *count = uint32_t(points);
+        return SGZ_OK;
+    }
+    if (sgz_status rs = scopeReserveVertices(s, need); rs != SGZ_OK) return rs;
+    if (sgz_status st = scopeDenseInto(s, columns, evaluator, channel, s->d_xyz, rgba ? s->d_rgba : nullptr, &points); st != SGZ_OK) return st;
+    if (sgz_status rb = readBack(xyz, s->d_xyz, points * 3 * sizeof(float), rgba, s->d_rgba, points * sizeof(uint32_t), s->h_out, s->stream);
+        rb != SGZ_OK) return rb;
+    *count = uint32_t(points);
+    return SGZ_OK;
+}
+
+sgz_status sgz_scope_dense_vertices_all(sgz_scope *s, uint32_t columns, uint32_t items, const uint32_t *evaluators, const uint32_t *channels,
+                                        float *const *xyz, uint8_t *const *rgba, uint32_t *counts)
+{
+    if (!s || !evaluators || !channels || !xyz || !counts) return fail(SGZ_EINVAL, "null argument");
+    if (columns == 0) return fail(SGZ_EINVAL, "columns == 0");
+    size_t need = 0;
+    bool small = false, direct = true;
+    for (uint32_t k = 0; k < items; ++k) {
+        if (!xyz[k]) return fail(SGZ_EINVAL, "null argument");
+        if (sgz_status st = scopeDenseCheck(s, columns, evaluators[k], channels[k], &need); st != SGZ_OK) return st;
+    }
+    for (uint32_t k = 0; k < items; ++k) {
+        if (need > counts[k]) { counts[k] = uint32_t(need); small = true; }
+        direct = direct && mappedDevicePointer(xyz[k], s->stream) && (!rgba || !rgba[k] || mappedDevicePointer(rgba[k], s->stream));
+    }
+    if (small) return fail(SGZ_EINVAL, "vertex buffer too small (counts hold the required size)");
+    if (!direct) {                                            // a pageable buffer among them: item by item through the bounce buffer
+        for (uint32_t k = 0; k < items; ++k) {
+            const sgz_status st = sgz_scope_dense_vertices(s, columns, evaluators[k], channels[k], xyz[k], rgba ? rgba[k] : nullptr, &counts[k]);
+            if (st != SGZ_OK) return st;
+        }
+        return SGZ_OK;
+    }
+    for (uint32_t k = 0; k < items; ++k) {
+        size_t points = 0;
+        const sgz_status st = scopeDenseInto(s, columns, evaluators[k], channels[k], static_cast<float *>(mappedDevicePointer(xyz[k], s->stream)),
+                                             rgba && rgba[k] ? static_cast<uint32_t *>(mappedDevicePointer(rgba[k], s->stream)) : nullptr, &points);
+        if (st != SGZ_OK) { (void)hipStreamSynchronize(s->stream); return st; }
+        counts[k] = uint32_t(points);
+    }
+    SGZ_HIP(hipStreamSynchronize(s->stream));
+    return SGZ_OK;
+}
+
+sgz_status sgz_scope_dense_vertices_device(sgz_scope *s, uint32_t columns, uint32_t evaluator, uint32_t channel, float *d_xyz, uint8_t *d_rgba,
+                                           uint32_t *count)
+{
+    if (!s || !d_xyz || !count) return fail(SGZ_EINVAL, "null argument");
+    if ((reinterpret_cast<uintptr_t>(d_xyz) & 3) || (reinterpret_cast<uintptr_t>(d_rgba) & 3)) return fail(SGZ_EINVAL, "4-byte aligned buffers");
+    size_t need = 0, points = 0;
+    if (sgz_status st = scopeDenseCheck(s, columns, evaluator, channel, &need); st != SGZ_OK) return st;
+    if (need > *count) { *count = uint32_t(need); return fail(SGZ_EINVAL, "vertex buffer too small (count holds the required size)"); }
+    if (sgz_status st = scopeDenseInto(s, columns, evaluator, channel, d_xyz, reinterpret_cast<uint32_t *>(d_rgba), &points); st != SGZ_OK) return st;
     SGZ_HIP(hipStreamSynchronize(s->stream));                 // the vertices are in place when the call returns
     *count = uint32_t(points);
     return SGZ_OK;

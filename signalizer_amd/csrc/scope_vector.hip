@@ -15,6 +15,7 @@
 
 #include "runtime.hpp"
 #include "fade_chain.hpp"
+#include "scope_ring.hpp"
 
 #pragma clang fp contract(off)
 
@@ -208,24 +209,7 @@ scopeLanczosKernel(const float *ring, size_t len, size_t stride, uint32_t channe
     }
 }
 
-// ---- drawWavePlot on the handle's front ring (sgz_scope_vertices): the ring's write cursor is read from device memory, the
-// sample comes from an evaluator (SampleColourEvaluators.h: one channel, or 0.5 (l +- r)), and a vertex is (x, y, 0) + RGBA8.
-__device__ __forceinline__ float evalSample(const float *a, const float *b, uint32_t mode, uint32_t idx)
-{
-    if (mode == 1u) return 0.5f * (a[idx] + b[idx]);       // MidSideEvaluatorBase<0, std::plus<>>::evaluateSample
-    if (mode == 2u) return 0.5f * (a[idx] - b[idx]);       // <1, std::minus<>>
-    return a[idx];
-}
-
-// The reference's ring of `len` samples inside a physical ring of `cap` >= len (Spectral mode keeps the largest ring the reference can
-// ask for, see sgz.h): logical position q (counted from the write cursor = the oldest of the newest `len` samples) -> memory index.
-// cap == len (every other mode): (cursor + q) mod len, the ring itself.
-__device__ __forceinline__ uint32_t ringPhys(long rel, uint32_t cursor, uint32_t cap, uint32_t len)
-{
-    long q = rel % long(len);
-    if (q < 0) q += long(len);
-    return uint32_t((long(cursor) + long(cap - len) + q) % long(cap));
-}
+// evalSample, ringPhys: scope_ring.hpp (shared with scope_dense.hip)
 // UPixel::lerp(other, t) with a double t (currentColour.lerp(nextColour, delta), OscilloscopeRendering.cpp:876): per component
 // (uint8)(a + (b - a) t)
 __device__ __forceinline__ uint32_t lerpRgba(uint32_t a, uint32_t b, double t)
@@ -568,18 +552,6 @@ vectorAudioKernel(const float *L, const float *R, size_t n, float envelope, floa
     if (lane < 8) reinterpret_cast<float *>(st)[lane] = y;
 }
 
-// Scratch of the stage calls: stream-ordered allocations (hipMallocAsync / hipFreeAsync on the caller's stream), so the library keeps
-// no process-wide device state -- any number of host threads, streams and devices may use the stage calls at once.
-struct StreamScratch {
-    void *p = nullptr;
-    hipStream_t s;
-    explicit StreamScratch(hipStream_t stream) : s(stream) {}
-    hipError_t get(size_t bytes) { return hipMallocAsync(&p, bytes, s); }
-    ~StreamScratch() { if (p) (void)hipFreeAsync(p, s); }
-    StreamScratch(const StreamScratch &) = delete;
-    StreamScratch &operator=(const StreamScratch &) = delete;
-};
-
 // which branch drawWavePlot takes: Lanczos falls back to Linear below one pixel per sample (:575-578)
 bool waveIsLanczos(const sgz_scope_view &v, uint32_t interpolation)
 {
@@ -646,19 +618,9 @@ hipError_t launchScopeVertices(const sgz_scope_view &view, uint32_t triggerMode,
                            size, cap, d_cursor, s.points, s.samplePos0, s.samplesPerPixel, s.unit0, s.inc, s.cursor0);
         *points = s.points;
     } else {
-        const long roundedWindow = long(std::ceil(view.window_size));
-        long bufferOffset, quantizedCycleSamples = 0;
-        if (triggerMode == SGZ_TRIG_WINDOW) {
-            bufferOffset = long(std::ceil(std::fmod(double(transport), view.window_size)));   // :588-592
-        } else if (triggerMode == SGZ_TRIG_ZERO_CROSSING || triggerMode == SGZ_TRIG_ENVELOPE_HOLD) {
-            const double realOffset = (view.window_size * 0.5 - double(int(view.window_size * 0.5))) - 1.5;
-            bufferOffset = long(std::ceil(realOffset));                                 // :593-594
-        } else {
-            // :598-612; this branch is never Lanczos, so cycleBuffers = 1
-            if (triggerMode == SGZ_TRIG_SPECTRAL) quantizedCycleSamples = long(std::ceil(cycleSamples));
-            bufferOffset = roundedWindow + quantizedCycleSamples;
-        }
-        const size_t n = size_t(std::max<long>(2, roundedWindow) + quantizedCycleSamples);
+        const LinearExtent ext = scopeLinearExtent(view.window_size, triggerMode, cycleSamples, transport);
+        const size_t n = ext.n;
+        const long bufferOffset = ext.bufferOffset;
         if (waveIsRect(view, interpolation)) {
             if (2 * n > capacity) return hipErrorInvalidValue;
             hipLaunchKernelGGL(scopeWaveRectKernel, dim3(unsigned((n + block - 1) / block)), dim3(block), 0, stream, ringA, ringB, evalMode,
