@@ -851,8 +851,39 @@ def scope_dense_device(ring, n: int, columns: int, xy, length: int | None = None
                                        C.c_void_p(stream) if stream else None))
 
 
-class Scope:
+class _BatchedIngest:
+    """What api.Scope and api.Vector take audio with: sgz_scope_* / sgz_vector_* push, set_mix, set_option, flush (_c: the C prefix)."""
+
+    def _call(self, name: str, *args) -> int:
+        return check(getattr(lib(), f"{self._c}_{name}")(self.h, *args))
+
+    def set_option(self, option: int, value: int):
+        """sgz_scope_set_option / sgz_vector_set_option (RT_OPT_DEFER_SUBMIT, RT_OPT_PARK_PUSHES)"""
+        self._call("set_option", option, value)
+        return self
+
+    def push(self, block: np.ndarray) -> int:
+        """sgz_scope_push / sgz_vector_push: block float32 [channels, samples]; returns SGZ_OK or SGZ_BUSY"""
+        b = np.ascontiguousarray(block, np.float32)
+        ptrs = (C.c_void_p * b.shape[0])(*[b[c].ctypes.data for c in range(b.shape[0])])
+        return self._call("push", ptrs, b.shape[0], b.shape[1])
+
+    def set_mix(self, matrix: np.ndarray):
+        """sgz_scope_set_mix / sgz_vector_set_mix: matrix uint8 [num_channels, num_sources]; push then takes num_sources channels"""
+        m = np.ascontiguousarray(matrix, np.uint8)
+        if m.ndim != 2 or m.shape[0] != self.cfg.num_channels:
+            raise ValueError(f"mix matrix must be [num_channels = {self.cfg.num_channels}, num_sources], got {m.shape}")
+        self._call("set_mix", m.shape[1], _np_ptr(m))
+        return self
+
+    def flush(self):
+        """blocks that waited for a staging slot are enqueued now (sgz_scope_flush / sgz_vector_flush): readers of results call it first"""
+        self._call("flush")
+
+
+class Scope(_BatchedIngest):
     """sgz_scope_* handle: the Oscilloscope's audio-thread state machine in HBM + drawWavePlot vertices."""
+    _c = "sgz_scope"
 
     def __init__(self, **kw):
         self.cfg = ScopeConfig()
@@ -871,11 +902,6 @@ class Scope:
         self.h = C.c_void_p()
         check(lib().sgz_scope_create(C.byref(self.cfg), C.byref(self.h)))
 
-    def set_option(self, option: int, value: int):
-        """sgz_scope_set_option (RT_OPT_DEFER_SUBMIT)"""
-        check(lib().sgz_scope_set_option(self.h, option, value))
-        return self
-
     def close(self):
         if getattr(self, "h", None):
             lib().sgz_scope_destroy(self.h)
@@ -891,23 +917,6 @@ class Scope:
         for k, v in kw.items():
             setattr(self.cfg, k, v)
         check(lib().sgz_scope_configure(self.h, C.byref(self.cfg)))
-
-    def push(self, block: np.ndarray) -> int:
-        b = np.ascontiguousarray(block, np.float32)
-        ptrs = (C.c_void_p * b.shape[0])(*[b[c].ctypes.data for c in range(b.shape[0])])
-        return check(lib().sgz_scope_push(self.h, ptrs, b.shape[0], b.shape[1]))
-
-    def set_mix(self, matrix: np.ndarray):
-        """sgz_scope_set_mix: matrix uint8 [num_channels, num_sources]; push then takes num_sources channels"""
-        m = np.ascontiguousarray(matrix, np.uint8)
-        if m.ndim != 2 or m.shape[0] != self.cfg.num_channels:
-            raise ValueError(f"mix matrix must be [num_channels = {self.cfg.num_channels}, num_sources], got {m.shape}")
-        check(lib().sgz_scope_set_mix(self.h, m.shape[1], _np_ptr(m)))
-        return self
-
-    def flush(self):
-        """blocks that waited for a staging slot are enqueued now (sgz_scope_flush): readers of results call it first"""
-        check(lib().sgz_scope_flush(self.h))
 
     def set_transport(self, position_in_samples: int):
         """cs.transportPosition (TriggeringMode::Window)"""
@@ -1029,8 +1038,9 @@ class Scope:
         return [(o[0][:cnt[i]], o[1][:cnt[i]] if o[1] is not None else None) for i, o in enumerate(out)]
 
 
-class Vector:
+class Vector(_BatchedIngest):
     """sgz_vector_* handle: history ring + audio-thread filters + polar vertices in HBM."""
+    _c = "sgz_vector"
 
     def __init__(self, **kw):
         self.cfg = VectorConfig()
@@ -1044,11 +1054,6 @@ class Vector:
         self.h = C.c_void_p()
         check(lib().sgz_vector_create(C.byref(self.cfg), C.byref(self.h)))
 
-    def set_option(self, option: int, value: int):
-        """sgz_vector_set_option (RT_OPT_DEFER_SUBMIT)"""
-        check(lib().sgz_vector_set_option(self.h, option, value))
-        return self
-
     def close(self):
         if getattr(self, "h", None):
             lib().sgz_vector_destroy(self.h)
@@ -1059,23 +1064,6 @@ class Vector:
             self.close()
         except Exception:
             pass
-
-    def push(self, block: np.ndarray) -> int:
-        b = np.ascontiguousarray(block, np.float32)
-        ptrs = (C.c_void_p * b.shape[0])(*[b[c].ctypes.data for c in range(b.shape[0])])
-        return check(lib().sgz_vector_push(self.h, ptrs, b.shape[0], b.shape[1]))
-
-    def set_mix(self, matrix: np.ndarray):
-        """sgz_vector_set_mix: matrix uint8 [num_channels, num_sources]; push then takes num_sources channels"""
-        m = np.ascontiguousarray(matrix, np.uint8)
-        if m.ndim != 2 or m.shape[0] != self.cfg.num_channels:
-            raise ValueError(f"mix matrix must be [num_channels = {self.cfg.num_channels}, num_sources], got {m.shape}")
-        check(lib().sgz_vector_set_mix(self.h, m.shape[1], _np_ptr(m)))
-        return self
-
-    def flush(self):
-        """blocks that waited for a staging slot are enqueued now (sgz_vector_flush): readers of results call it first"""
-        check(lib().sgz_vector_flush(self.h))
 
     def history(self, channel: int):
         self.flush()

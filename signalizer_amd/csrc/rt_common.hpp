@@ -3,6 +3,10 @@
 // block"): a slot whose previous upload has not completed is detected with hipEventQuery, and the block then WAITS ITS TURN in the
 // FIFO (Backlog below) -- the stream the kernels see has no holes, as the reference's cpl::AudioStream FIFO guarantees short of its own
 // overflow (PluginProcessor.cpp:195-198, MixGraphListener.cpp:336-387).  Only a full FIFO refuses a block (SGZ_BUSY).
+//
+// The Spectrum handle stages one block per launch (StageRing).  The Oscilloscope and the Vectorscope take several blocks per launch and
+// share everything that does so: BatchFront is the host side of such a handle (staging, routing, the push lock, the options, the entry
+// points' bodies and the GPU side of rt_lockfree.hpp's hand-over protocol), BatchArgs / batchOpen the head of its ingest kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +14,8 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
+#include <string>
 
 #include "rt_lockfree.hpp"     // Backlog, SpinFlag, BatchCore, the hand-over protocol, ColumnQueue, LineSeqlock: HIP-free (ThreadSanitizer harness)
 #include "runtime.hpp"
@@ -380,5 +386,153 @@ __device__ __forceinline__ void batchMix(const MixRoute *route, MixRoute &sRoute
     __syncthreads();
 }
 #endif
+
+// The head of a batched ingest kernel's parameters (embedded by value; BatchFront::fill writes it): the staged blocks back to back, block
+// b = [channels][blockLen[b]] at batch + blockOff[b] -- or, routed, [numSources][blockLen[b]] there and the destination rows in mixRows.
+struct BatchArgs {
+    const float *batch;
+    const float *batchHost; uint32_t batchFloats;      // the pinned slot the blocks are fetched from first (batchFetch), or null
+    const MixRoute *route; float *mixRows;             // sgz_*_set_mix: routed into mixRows first (batchMix); route null: none
+    uint32_t numSources;
+    uint32_t numBlocks, channels;
+    uint32_t blockOff[BatchCore::kMaxBlocks], blockLen[BatchCore::kMaxBlocks];
+};
+
+#ifdef __HIPCC__
+// The preface of a batched ingest kernel (ONE workgroup; sBlockOff / sBlockLen / sRoute are the kernel's own __shared__ objects): the
+// block table into LDS, the batch out of the pinned slot, the routing.  Returns the rows the phases read, block b at sBlockOff[b].
+// (the block table goes through LDS: a run-time subscript into the by-value argument struct would move the struct to scratch)
+__device__ __forceinline__ const float *batchOpen(const BatchArgs &a, uint32_t *sBlockOff, uint32_t *sBlockLen, MixRoute &sRoute, int tid, int threads)
+{
+#pragma unroll
+    for (uint32_t b = 0; b < BatchCore::kMaxBlocks; ++b)
+        if (tid == int(b)) { sBlockOff[b] = a.blockOff[b]; sBlockLen[b] = a.blockLen[b]; }
+    __syncthreads();
+    batchFetch(a.batchHost, const_cast<float *>(a.batch), a.batchFloats, tid, threads);
+    const float *rows = a.batch;
+    if (a.route) {                                                        // (uniform)
+        batchMix(a.route, sRoute, a.batch, a.mixRows, a.numSources, a.channels, a.numBlocks, sBlockOff, sBlockLen, tid, threads);
+        rows = a.mixRows;
+    }
+    return rows;
+}
+#endif
+
+// The host side of a handle whose ingest kernel takes several blocks per launch (sgz_scope and sgz_vector derive from it): the staging,
+// the routing, the lock between configure and push, the options -- and the bodies of push / set_mix / set_option / flush and of the
+// flush on read, written once.  `submit` is the handle's own "open batch -> GPU" (caller holds the batch flag; count > 0): upload, fill
+// the kernel parameters' head, launch, commit.  `noun` is "scope" / "vector", for the messages that name the handle.
+struct BatchFront {
+    std::atomic<bool> deferSubmit{false};      // sgz_*_set_option(SGZ_RT_OPT_DEFER_SUBMIT); read by whoever holds the batch flag
+    std::atomic<bool> parkPushes{false};       // ... (SGZ_RT_OPT_PARK_PUSHES): every push waits in the host FIFO for the next reader / flush
+    std::mutex mu;                             // configure (consumer thread) against push (producer: try_lock only, never waits)
+    hipStream_t stream = nullptr;
+    BatchRing batch;                           // staged blocks waiting for their (one) ingest launch
+    uint32_t maxBlock = 0;
+    Backlog backlog;                           // blocks waiting for a staging slot
+    BatchMix mix;                              // sgz_*_set_mix's routing: the staging holds mix.numSources rows per block
+    uint64_t busy = 0;
+
+    // Pinned slots and FIFO for `rows` rows per block of up to `block` samples.  A slot takes a whole batch: the blocks of a rendered
+    // frame and more (at least 8192 samples); one second of audio may wait for the GPU in the FIFO.  maxBlock follows as soon as the
+    // slots are there: push appends a block of up to maxBlock samples to an empty slot without looking at the slot's size.
+    sgz_status staging(uint32_t rows, double sampleRate, uint32_t block)
+    {
+        if (sgz_status st = batch.init(rows, std::max<uint32_t>(block, 8192u)); st != SGZ_OK) return st;
+        maxBlock = block;
+        if (!backlog.init(backlogFloats(rows, sampleRate, block))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
+        return SGZ_OK;
+    }
+    // destroy: freeOwn() frees the handle's own buffers, behind the stream's last work and in front of the stream's end
+    template <class FreeOwn>
+    void release(FreeOwn freeOwn)
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        batch.release();
+        backlog.release();
+        mix.release();
+        freeOwn();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+
+    // the handle's GPU side for rt_lockfree.hpp's hand-over protocol (batchPush / batchSync / batchFlushAll: one block behind the ones
+    // already staged, parked blocks behind the open batch's in order, flush on read -- the same code the ThreadSanitizer harness runs on
+    // a mock GPU)
+    template <class Submit>
+    struct Side {
+        BatchFront &f;
+        Submit &submitBatch;
+        BatchCore &batch() { return f.batch; }
+        Backlog &backlog() { return f.backlog; }
+        sgz_status submit() { return submitBatch(); }
+        sgz_status slotReady() { return f.batch.slotReady(); }
+        bool gpuIdle() { return f.batch.idle(); }
+        void waitGpu() { (void)hipStreamSynchronize(f.stream); }
+        bool deferSubmit() { return f.deferSubmit.load(std::memory_order_relaxed); }
+    };
+    template <class Submit>
+    Side<Submit> side(Submit &submit) { return Side<Submit>{*this, submit}; }
+
+    // consumer side (flush on read): what waits in the host FIFO and in the open batch goes to the GPU in front of the caller's own work
+    template <class Submit>
+    sgz_status sync(Submit submit)
+    {
+        auto s = side(submit);
+        return batchSync(s);
+    }
+    template <class Submit>
+    sgz_status flush(Submit submit)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto s = side(submit);
+        return batchFlushAll(s);                                          // (this call may wait: it is not the audio thread's)
+    }
+    template <class Submit>
+    sgz_status push(Submit submit, const float *const *planar, uint32_t num_channels, uint32_t nsamples, const char *noun)
+    {
+        if (!planar) return fail(SGZ_EINVAL, "null argument");
+        std::unique_lock<std::mutex> lk(mu, std::try_to_lock);            // never waits: a reconfiguration in progress drops the block
+        if (!lk.owns_lock()) { busy++; return SGZ_BUSY; }
+        if (num_channels != mix.numSources)
+            return fail(SGZ_EINVAL, std::string("num_channels differs from the configuration (or from the source count of sgz_") + noun + "_set_mix)");
+        if (nsamples == 0) return SGZ_OK;                                 // the Oscilloscope's audioEntryPoint returns at once too (OscilloscopeDSP.inl)
+        if (nsamples > maxBlock) return fail(SGZ_EINVAL, std::string("block longer than sgz_") + noun + "_config::max_block");
+        // never waits: the render thread is submitting the open batch right now -> the block waits its turn in the host FIFO, like one
+        // the GPU is not ready for (Backlog); SGZ_BUSY = that FIFO is full
+        // (SGZ_RT_OPT_PARK_PUSHES: every block takes that way -- the tests' handle on a race that timing alone produces)
+        auto s = side(submit);
+        const sgz_status st = batchPush(s, planar, num_channels, nsamples, parkPushes.load(std::memory_order_relaxed));
+        if (st == SGZ_BUSY) busy++;
+        return st;
+    }
+    // num_channels / sampleRate: the handle's configuration (the destinations; the FIFO's second of audio)
+    template <class Submit>
+    sgz_status setMix(uint32_t num_sources, uint32_t num_channels, double sampleRate, const uint8_t *matrix, Submit submit)
+    {
+        if (!matrix || num_sources == 0 || num_sources > MixRoute::kMax) return fail(SGZ_EINVAL, "bad argument");
+        std::lock_guard<std::mutex> lk(mu);                               // (a push meanwhile is refused with SGZ_BUSY: it never waits)
+        if (sgz_status sy = sync(submit); sy != SGZ_OK) return sy;        // the audio already taken goes through the old routing
+        SGZ_HIP(hipStreamSynchronize(stream));
+        if (batch.channels != num_sources)                                // staging, pinned slot and FIFO for num_sources rows per block
+            if (sgz_status st = staging(num_sources, sampleRate, maxBlock); st != SGZ_OK) return st;
+        return mix.set(num_sources, num_channels, matrix, batch.slotSamples);
+    }
+    sgz_status setOption(uint32_t option, uint64_t value, const char *noun)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (option == SGZ_RT_OPT_PARK_PUSHES) { parkPushes.store(value != 0, std::memory_order_relaxed); return SGZ_OK; }
+        if (option != SGZ_RT_OPT_DEFER_SUBMIT) return fail(SGZ_EINVAL, std::string("unknown ") + noun + " option");
+        deferSubmit.store(value != 0, std::memory_order_relaxed);
+        return SGZ_OK;
+    }
+    // the shared head of the ingest kernel's parameters (value-initialised by the caller), between upload and the handle's own fields
+    void fill(BatchArgs &a, const float *d_batch, const float *fetchFrom, uint32_t floats, uint32_t channels) const
+    {
+        a.batch = d_batch; a.batchHost = fetchFrom; a.batchFloats = floats;
+        a.numBlocks = batch.count; a.channels = channels;
+        for (uint32_t b = 0; b < batch.count; ++b) { a.blockOff[b] = batch.off[b]; a.blockLen[b] = batch.len[b]; }
+        if (mix.active) { a.route = mix.d_route; a.mixRows = mix.d_rows; a.numSources = batch.channels; }
+    }
+};
 
 }  // namespace sgz

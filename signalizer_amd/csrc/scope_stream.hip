@@ -126,12 +126,7 @@ struct IngestParams {
     ScopeDev *st;
     unsigned long long *peaks;                // [kPeakCap]
     Swap *swapList;                           // [kMaxSwaps]
-    const float *batch;                       // the staged blocks, back to back: block b = [channels][blockLen[b]] at batch + blockOff[b]
-    const float *batchHost; uint32_t batchFloats;   // the pinned slot they are fetched from first (rt_common.hpp batchFetch), or null
-    const MixRoute *route; float *mixRows;    // sgz_scope_set_mix: the batch holds numSources rows per block, routed into mixRows first (rt_common.hpp batchMix); route null: none
-    uint32_t numSources;
-    uint32_t numBlocks, channels;
-    uint32_t blockOff[BatchRing::kMaxBlocks], blockLen[BatchRing::kMaxBlocks];
+    BatchArgs in;                             // the staged blocks and sgz_scope_set_mix's routing (rt_common.hpp)
     float *front; uint32_t size;              // [channels][size]
     float *back; uint32_t backCap;            // [channels][backCap], power of two
     uint32_t triggerMode, oscMode, envMode;
@@ -830,7 +825,7 @@ __device__ __forceinline__ uint32_t frontPhase(const IngestParams &prm, const Pl
 __device__ __forceinline__ void envelopePhase(const IngestParams &prm, ScopeDev *st, const float *blk, uint32_t n, uint32_t lastStart, uint32_t lastLen)
 {
     const int tid = threadIdx.x;
-    const uint32_t C = prm.channels;
+    const uint32_t C = prm.in.channels;
     const bool active = tid < int(C);
     const float k = prm.envelopeCoeff;
     const uint32_t mode = prm.oscMode;
@@ -884,7 +879,7 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
     // some thirty times, mostly from one lane and each time behind the last (the kernels of the render thread read the copy in HBM,
     // between launches)
     __shared__ ScopeDev sState;
-    const uint32_t C = prm.channels;
+    const uint32_t C = prm.in.channels;
     const int tid = threadIdx.x, T = blockDim.x;
     static_assert(sizeof(ScopeDev) % 4 == 0, "copied as words");
     for (uint32_t w = tid; w < sizeof(ScopeDev) / 4; w += T) reinterpret_cast<uint32_t *>(&sState)[w] = reinterpret_cast<const uint32_t *>(prm.st)[w];
@@ -897,19 +892,20 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
     // full batch, sgz_scope_flush -- submits): the blocks go through the reference's per-callback state machine ONE AFTER THE OTHER, with
     // their boundaries where the host put them (audioEntryPoint runs once per onStreamAudio: update(), the detector, processMutating's
     // window selection all see callback extents), the stream state staying in LDS in between.
+    // (rt_common.hpp batchOpen's three steps, written out: through the function this kernel spilt 154 scalar registers instead of 142)
     // (the block table goes through LDS: a run-time subscript into the by-value argument struct would move the struct to scratch)
     __shared__ uint32_t sBlockOff[BatchRing::kMaxBlocks], sBlockLen[BatchRing::kMaxBlocks];
 #pragma unroll
     for (uint32_t b = 0; b < BatchRing::kMaxBlocks; ++b)
-        if (tid == int(b)) { sBlockOff[b] = prm.blockOff[b]; sBlockLen[b] = prm.blockLen[b]; }
+        if (tid == int(b)) { sBlockOff[b] = prm.in.blockOff[b]; sBlockLen[b] = prm.in.blockLen[b]; }
     __syncthreads();
-    batchFetch(prm.batchHost, const_cast<float *>(prm.batch), prm.batchFloats, tid, T);
+    batchFetch(prm.in.batchHost, const_cast<float *>(prm.in.batch), prm.in.batchFloats, tid, T);
     // sgz_scope_set_mix: the staged source rows -> the destination rows every phase below reads (and sBlockOff into them)
     __shared__ MixRoute sRoute;
-    const float *batch = prm.batch;
-    if (prm.route) {                                                       // (uniform)
-        batchMix(prm.route, sRoute, prm.batch, prm.mixRows, prm.numSources, C, prm.numBlocks, sBlockOff, sBlockLen, tid, T);
-        batch = prm.mixRows;
+    const float *batch = prm.in.batch;
+    if (prm.in.route) {                                                    // (uniform)
+        batchMix(prm.in.route, sRoute, prm.in.batch, prm.in.mixRows, prm.in.numSources, C, prm.in.numBlocks, sBlockOff, sBlockLen, tid, T);
+        batch = prm.in.mixRows;
     }
     // ---- A for the WHOLE batch.  The zero-crossing detector (phase A) is a scan over the samples whose state (armed, last threshold
     // crossing, previous sample) does not depend on what processMutating does with the triggers, and a trigger's slot in the queue's
@@ -923,25 +919,25 @@ __global__ void __launch_bounds__(1024) scopeIngestKernel(const IngestParams prm
     __shared__ int sBatchedA;
     if (tid == 0) {
         uint32_t acc = 0;
-        for (uint32_t b = 0; b < BatchRing::kMaxBlocks; ++b) { sBlockStart[b] = acc; acc += b < prm.numBlocks ? sBlockLen[b] : 0u; }
+        for (uint32_t b = 0; b < BatchRing::kMaxBlocks; ++b) { sBlockStart[b] = acc; acc += b < prm.in.numBlocks ? sBlockLen[b] : 0u; }
         sBlockStart[BatchRing::kMaxBlocks] = acc;
         sBatchedA = 0;
     }
     if (tid < int(BatchRing::kMaxBlocks)) sFires[tid] = 0;
     __syncthreads();
-    if (prm.triggerMode == 4u && C >= 2 && prm.numBlocks > 1 && !st->windowChanged) {       // (uniform)
+    if (prm.triggerMode == 4u && C >= 2 && prm.in.numBlocks > 1 && !st->windowChanged) {       // (uniform)
         auto sampleAt = [&](uint32_t i, uint32_t &b) -> double {           // sample i of the concatenation
             while (sBlockStart[b + 1] <= i) ++b;
             const float *a, *c;
             const uint32_t mode = triggerPlanes(prm, batch + sBlockOff[b], sBlockLen[b], a, c);
             return trigSample(mode, a, c, i - sBlockStart[b]);
         };
-        if (zeroCrossings(sBlockStart[prm.numBlocks], sampleAt, st, prm.peaks, st->playhead, sFires, sScan2, sSum) && tid == 0) sBatchedA = 1;
+        if (zeroCrossings(sBlockStart[prm.in.numBlocks], sampleAt, st, prm.peaks, st->playhead, sFires, sScan2, sSum) && tid == 0) sBatchedA = 1;
         __syncthreads();
     }
     const bool batchedA = sBatchedA != 0;
     const bool hold = prm.triggerMode == 4u || prm.triggerMode == 3u;      // ZeroCrossing, EnvelopeHold: detector -> processMutating
-    for (uint32_t blockIndex = 0; blockIndex < prm.numBlocks; ++blockIndex) {
+    for (uint32_t blockIndex = 0; blockIndex < prm.in.numBlocks; ++blockIndex) {
         const float *const blk = batch + sBlockOff[blockIndex];
         const uint32_t n = sBlockLen[blockIndex];
         const unsigned long long playhead = st->playhead;
@@ -1346,16 +1342,8 @@ __global__ void __launch_bounds__(1024) scopeSpectralKernel(const SpectralParams
 
 }  // namespace
 
-struct sgz_scope {
+struct sgz_scope : BatchFront {                // (rt_common.hpp: stream, staging, routing, push lock, options)
     sgz_scope_config cfg{};
-    std::atomic<bool> deferSubmit{false};      // sgz_scope_set_option(SGZ_RT_OPT_DEFER_SUBMIT); read by whoever holds the batch flag
-    std::atomic<bool> parkPushes{false};                  // ... (SGZ_RT_OPT_PARK_PUSHES): every push waits in the host FIFO for the next reader / flush
-    std::mutex mu;                    // configure (consumer thread) against push (producer: try_lock only, never waits)
-    hipStream_t stream = nullptr;
-    BatchRing batch;                           // staged blocks waiting for their (one) ingest launch (rt_common.hpp)
-    uint32_t maxBlock = 0;
-    Backlog backlog;                           // blocks waiting for a staging slot (rt_common.hpp)
-    BatchMix mix;                              // sgz_scope_set_mix's routing (rt_common.hpp): the staging holds mix.numSources rows per block
     ScopeDev *d_state = nullptr;
     unsigned long long *d_peaks = nullptr;
     Swap *d_swaps = nullptr;
@@ -1378,22 +1366,18 @@ struct sgz_scope {
     float *d_xyz = nullptr; uint32_t *d_rgba = nullptr; size_t vertexCap = 0;
     void *h_out = nullptr; size_t hOutBytes = 0;          // pinned
     void *d_dense = nullptr; size_t denseBytes = 0;       // partial records of the dense stream's long columns (scope_dense.hip)
-    uint64_t busy = 0;
 };
 
 static void scopeFree(sgz_scope *s)
 {
     if (!s) return;
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    s->batch.release();
-    s->backlog.release();
-    s->mix.release();
-    for (void *p : {(void *)s->d_state, (void *)s->d_peaks, (void *)s->d_swaps, (void *)s->d_front, (void *)s->d_back, (void *)s->d_xyz,
-                    (void *)s->d_rgba, (void *)s->col.st, (void *)s->col.bands, (void *)s->col.sm, (void *)s->col.block, (void *)s->col.front,
-                    (void *)s->col.back, (void *)s->d_spectral, (void *)s->d_tw, (void *)s->d_col, s->d_dense})
-        if (p) (void)hipFree(p);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    s->release([s] {
+        for (void *p : {(void *)s->d_state, (void *)s->d_peaks, (void *)s->d_swaps, (void *)s->d_front, (void *)s->d_back, (void *)s->d_xyz,
+                        (void *)s->d_rgba, (void *)s->col.st, (void *)s->col.bands, (void *)s->col.sm, (void *)s->col.block, (void *)s->col.front,
+                        (void *)s->col.back, (void *)s->d_spectral, (void *)s->d_tw, (void *)s->d_col, s->d_dense})
+            if (p) (void)hipFree(p);
+        if (s->h_out) (void)hipHostFree(s->h_out);
+    });
     delete s;
 }
 
@@ -1498,13 +1482,7 @@ static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fre
         SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_back), size_t(C) * backCap * sizeof(float)));
         SGZ_HIP(hipMemset(s->d_front, 0, size_t(C) * size * sizeof(float)));
         SGZ_HIP(hipMemset(s->d_back, 0, size_t(C) * backCap * sizeof(float)));
-        if (!retime) {
-            // a slot takes a whole batch: the blocks of one rendered frame and more (at least 8192 samples)
-            if ((st = s->batch.init(C, std::max<uint32_t>(maxBlock, 8192u))) != SGZ_OK) return st;
-            s->maxBlock = maxBlock;
-            // one second of audio may wait for the GPU (at least 32 blocks)
-            if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
-        }
+        if (!retime && (st = s->staging(C, cfg->sample_rate, maxBlock)) != SGZ_OK) return st;     // (s->maxBlock = maxBlock once the slots are there)
         if (!s->d_state) {
             SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_state), sizeof(ScopeDev)));
             SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_peaks), size_t(kPeakCap) * sizeof(unsigned long long)));
@@ -1528,10 +1506,8 @@ static sgz_status scopeSetup(sgz_scope *s, const sgz_scope_config *cfg, bool fre
         s->col.maxBlock = maxBlock;
     }
     if (!retime) {
-        if (s->batch.channels != C) {         // a configure after sgz_scope_set_mix: the staging takes num_channels rows again
-            if ((st = s->batch.init(C, std::max<uint32_t>(s->maxBlock, 8192u))) != SGZ_OK) return st;
-            if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
-        }
+        if (s->batch.channels != C)           // a configure after sgz_scope_set_mix: the staging takes num_channels rows again
+            if ((st = s->staging(C, cfg->sample_rate, s->maxBlock)) != SGZ_OK) return st;
         s->mix.reset(C);                      // the routing returns to the identity over num_channels
     }
     if (colours) {
@@ -1653,11 +1629,8 @@ static sgz_status scopeSubmit(sgz_scope *s, const PeakParams *peak = nullptr)
     const float *d_batch = s->batch.upload(s->stream, &st, &fetchFrom, &floats);
     if (!d_batch) return st;
     IngestParams prm{};
-    prm.batchHost = fetchFrom; prm.batchFloats = floats;
+    s->fill(prm.in, d_batch, fetchFrom, floats, s->cfg.num_channels);
     prm.st = s->d_state; prm.peaks = s->d_peaks; prm.swapList = s->d_swaps;
-    prm.batch = d_batch; prm.numBlocks = s->batch.count; prm.channels = s->cfg.num_channels;
-    for (uint32_t b = 0; b < s->batch.count; ++b) { prm.blockOff[b] = s->batch.off[b]; prm.blockLen[b] = s->batch.len[b]; }
-    if (s->mix.active) { prm.route = s->mix.d_route; prm.mixRows = s->mix.d_rows; prm.numSources = s->batch.channels; }
     prm.front = s->d_front; prm.size = s->size; prm.back = s->d_back; prm.backCap = s->backCap;
     prm.triggerMode = s->cfg.trigger_mode; prm.oscMode = s->cfg.channel_mode; prm.envMode = s->cfg.envelope_mode;
     prm.trigSeparate = s->trigSeparate; prm.trigPair = s->trigPair; prm.envelopeCoeff = s->envelopeCoeff;
@@ -1668,78 +1641,29 @@ static sgz_status scopeSubmit(sgz_scope *s, const PeakParams *peak = nullptr)
     return s->batch.commit(s->stream);
 }
 
-// the handle's GPU side for rt_lockfree.hpp's hand-over protocol (batchPush / batchSync / batchFlushAll: one block behind the ones already
-// staged, parked blocks behind the open batch's in order, flush on read -- the same code the ThreadSanitizer harness runs on a mock GPU)
-namespace {
-struct ScopeIngestSide {
-    sgz_scope *s;
-    BatchCore &batch() { return s->batch; }
-    Backlog &backlog() { return s->backlog; }
-    sgz_status submit() { return scopeSubmit(s); }
-    sgz_status slotReady() { return s->batch.slotReady(); }
-    bool gpuIdle() { return s->batch.idle(); }
-    void waitGpu() { (void)hipStreamSynchronize(s->stream); }
-    bool deferSubmit() { return s->deferSubmit.load(std::memory_order_relaxed); }
-};
-}  // namespace
+static auto scopeSubmitter(sgz_scope *s) { return [s] { return scopeSubmit(s); }; }
 
 // consumer side (flush on read): what waits in the host FIFO and in the open batch goes to the GPU in front of the caller's own work
-static sgz_status scopeSync(sgz_scope *s)
-{
-    ScopeIngestSide side{s};
-    return batchSync(side);
-}
+static sgz_status scopeSync(sgz_scope *s) { return s->sync(scopeSubmitter(s)); }
 
 sgz_status sgz_scope_push(sgz_scope *s, const float *const *planar, uint32_t num_channels, uint32_t nsamples)
 {
-    if (!s || !planar) return fail(SGZ_EINVAL, "null argument");
-    std::unique_lock<std::mutex> lk(s->mu, std::try_to_lock);      // never waits: a reconfiguration in progress drops the block
-    if (!lk.owns_lock()) { s->busy++; return SGZ_BUSY; }
-    if (num_channels != s->mix.numSources)
-        return fail(SGZ_EINVAL, "num_channels differs from the configuration (or from the source count of sgz_scope_set_mix)");
-    if (nsamples == 0) return SGZ_OK;                              // audioEntryPoint returns at once (:403-404)
-    if (nsamples > s->maxBlock) return fail(SGZ_EINVAL, "block longer than sgz_scope_config::max_block");
-    // never waits: the render thread is submitting the open batch right now -> the block waits its turn in the host FIFO, like one
-    // the GPU is not ready for (rt_common.hpp Backlog); SGZ_BUSY = that FIFO is full
-    // (SGZ_RT_OPT_PARK_PUSHES: every block takes that way -- the tests' handle on a race that timing alone produces)
-    ScopeIngestSide side{s};
-    const sgz_status st = batchPush(side, planar, num_channels, nsamples, s->parkPushes.load(std::memory_order_relaxed));
-    if (st == SGZ_BUSY) s->busy++;
-    return st;
+    return s ? s->push(scopeSubmitter(s), planar, num_channels, nsamples, "scope") : fail(SGZ_EINVAL, "null argument");
 }
 
 sgz_status sgz_scope_set_mix(sgz_scope *s, uint32_t num_sources, const uint8_t *matrix)
 {
-    if (!s || !matrix || num_sources == 0 || num_sources > MixRoute::kMax) return fail(SGZ_EINVAL, "bad argument");
-    std::lock_guard<std::mutex> lk(s->mu);                                // (a push meanwhile is refused with SGZ_BUSY: it never waits)
-    if (sgz_status sy = scopeSync(s); sy != SGZ_OK) return sy;            // the audio already taken goes through the old routing
-    SGZ_HIP(hipStreamSynchronize(s->stream));
-    if (s->batch.channels != num_sources) {                               // staging, pinned slot and FIFO for num_sources rows per block
-        if (sgz_status st = s->batch.init(num_sources, std::max<uint32_t>(s->maxBlock, 8192u)); st != SGZ_OK) return st;
-        if (!s->backlog.init(backlogFloats(num_sources, s->cfg.sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
-    }
-    return s->mix.set(num_sources, s->cfg.num_channels, matrix, s->batch.slotSamples);
+    return s ? s->setMix(num_sources, s->cfg.num_channels, s->cfg.sample_rate, matrix, scopeSubmitter(s)) : fail(SGZ_EINVAL, "bad argument");
 }
 
 void *sgz_scope_stream(sgz_scope *s) { return s ? s->stream : nullptr; }
 
 sgz_status sgz_scope_set_option(sgz_scope *s, uint32_t option, uint64_t value)
 {
-    if (!s) return fail(SGZ_EINVAL, "null handle");
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (option == SGZ_RT_OPT_PARK_PUSHES) { s->parkPushes.store(value != 0, std::memory_order_relaxed); return SGZ_OK; }
-    if (option != SGZ_RT_OPT_DEFER_SUBMIT) return fail(SGZ_EINVAL, "unknown scope option");
-    s->deferSubmit.store(value != 0, std::memory_order_relaxed);
-    return SGZ_OK;
+    return s ? s->setOption(option, value, "scope") : fail(SGZ_EINVAL, "null handle");
 }
 
-sgz_status sgz_scope_flush(sgz_scope *s)
-{
-    if (!s) return fail(SGZ_EINVAL, "null handle");
-    std::lock_guard<std::mutex> lk(s->mu);
-    ScopeIngestSide side{s};
-    return batchFlushAll(side);                                       // (this call may wait: it is not the audio thread's)
-}
+sgz_status sgz_scope_flush(sgz_scope *s) { return s ? s->flush(scopeSubmitter(s)) : fail(SGZ_EINVAL, "null handle"); }
 
 sgz_status sgz_scope_peak_filter(sgz_scope *s, double delta_time, uint32_t lanes, double *auto_gain)
 {
@@ -1752,7 +1676,8 @@ sgz_status sgz_scope_peak_filter(sgz_scope *s, double delta_time, uint32_t lanes
     PeakParams prm{s->d_state, s->d_front, s->size, s->cfg.num_channels, s->cfg.channel_mode, lanes, coeff, spectral ? numSamples : 0u};
     // flush on read: the blocks that wait in the open batch come first -- and the filter rides on their launch (one workgroup either
     // way: a launch and the gap in front of it less per rendered frame)
-    ScopeIngestSide side{s};
+    auto submit = scopeSubmitter(s);
+    auto side = s->side(submit);
     s->batch.lock();
     const sgz_status tb = batchTakeBacklog(side, false);
     const bool fused = tb == SGZ_OK && s->batch.count != 0;

@@ -37,10 +37,7 @@ struct VecDev {
 
 struct VecIngest {
     VecDev *st;
-    const float *batchHost; uint32_t batchFloats;             // the pinned slot the blocks are fetched from first (rt_common.hpp batchFetch), or null
-    const float *batch; uint32_t numBlocks, channels;         // the staged blocks back to back: block b = [channels][blockLen[b]] at batch + blockOff[b]
-    const MixRoute *route; float *mixRows; uint32_t numSources;   // sgz_vector_set_mix: numSources rows per staged block, routed into mixRows first; route null: none
-    uint32_t blockOff[BatchRing::kMaxBlocks], blockLen[BatchRing::kMaxBlocks];
+    BatchArgs in;                                              // the staged blocks and sgz_vector_set_mix's routing (rt_common.hpp)
     float *ring; uint32_t size;
     uint32_t lanes, envMode;
     float envelope, pole0, pole1;
@@ -52,24 +49,13 @@ __global__ void __launch_bounds__(256) vectorIngestKernel(const VecIngest prm)
     __shared__ float sL[kTile], sR[kTile], sP[kTile];
     VecDev *st = prm.st;
     const int tid = threadIdx.x;
-    const uint32_t size = prm.size, C = prm.channels;
+    const uint32_t size = prm.size, C = prm.in.channels;
     // one launch takes every block that was waiting (rt_common.hpp BatchRing), one after the other with the host's block boundaries:
     // audioProcessing drops the SIMD tail of EVERY callback (Vectorscope.cpp:292)
-    // (the block table goes through LDS: a run-time subscript into the by-value argument struct would move the struct to scratch)
     __shared__ uint32_t sBlockOff[BatchRing::kMaxBlocks], sBlockLen[BatchRing::kMaxBlocks];
-#pragma unroll
-    for (uint32_t b = 0; b < BatchRing::kMaxBlocks; ++b)
-        if (tid == int(b)) { sBlockOff[b] = prm.blockOff[b]; sBlockLen[b] = prm.blockLen[b]; }
-    __syncthreads();
-    batchFetch(prm.batchHost, const_cast<float *>(prm.batch), prm.batchFloats, tid, 256);
-    // sgz_vector_set_mix: the staged source rows -> the destination rows the blocks below read (rt_common.hpp batchMix)
     __shared__ MixRoute sRoute;
-    const float *batch = prm.batch;
-    if (prm.route) {                                                      // (uniform)
-        batchMix(prm.route, sRoute, prm.batch, prm.mixRows, prm.numSources, C, prm.numBlocks, sBlockOff, sBlockLen, tid, 256);
-        batch = prm.mixRows;
-    }
-    for (uint32_t blockIndex = 0; blockIndex < prm.numBlocks; ++blockIndex) {
+    const float *batch = batchOpen(prm.in, sBlockOff, sBlockLen, sRoute, tid, 256);
+    for (uint32_t blockIndex = 0; blockIndex < prm.in.numBlocks; ++blockIndex) {
     const float *const blk = batch + sBlockOff[blockIndex];
     const uint32_t n = sBlockLen[blockIndex];
     const uint32_t cursor0 = st->cursor;
@@ -360,16 +346,8 @@ inline float lissajousSampleFade(size_t n) { return 1.0f / float(std::max<int>(1
 
 }  // namespace
 
-struct sgz_vector {
+struct sgz_vector : BatchFront {               // (rt_common.hpp: stream, staging, routing, push lock, options)
     sgz_vector_config cfg{};
-    std::atomic<bool> deferSubmit{false};      // sgz_vector_set_option(SGZ_RT_OPT_DEFER_SUBMIT); read by whoever holds the batch flag
-    std::atomic<bool> parkPushes{false};                  // ... (SGZ_RT_OPT_PARK_PUSHES): every push waits in the host FIFO for the next reader / flush
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    BatchRing batch;                           // staged blocks waiting for their (one) ingest launch (rt_common.hpp)
-    uint32_t maxBlock = 0;
-    Backlog backlog;                           // blocks waiting for a staging slot (rt_common.hpp)
-    BatchMix mix;                              // sgz_vector_set_mix's routing (rt_common.hpp): the staging holds mix.numSources rows per block
     VecDev *d_state = nullptr;
     float *d_ring = nullptr;
     uint32_t size = 0;
@@ -378,7 +356,6 @@ struct sgz_vector {
     FadeSeg *d_rampTable = nullptr; int *d_rampCount = nullptr;     // the first section's progressions, per (size, lanes); the second's, per frame, behind them
     uint32_t rampTableSize = 0, rampTableLanes = 0;
     void *h_out = nullptr;
-    uint64_t busy = 0;
     // the fade ramp is a function of (size, cursor, lanes): one replay serves every pair of a rendered frame -- it is redone when a block
     // has been accepted since (pushes counts them; ~0 = never computed / reconfigured)
     std::atomic<uint64_t> pushes{0};
@@ -388,14 +365,11 @@ struct sgz_vector {
 static void vectorFree(sgz_vector *s)
 {
     if (!s) return;
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    s->batch.release();
-    s->backlog.release();
-    s->mix.release();
-    for (void *p : {(void *)s->d_state, (void *)s->d_ring, (void *)s->d_ramp, (void *)s->d_tail, (void *)s->d_rampTable, (void *)s->d_rampCount, (void *)s->d_xyz, (void *)s->d_rgb})
-        if (p) (void)hipFree(p);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    s->release([s] {
+        for (void *p : {(void *)s->d_state, (void *)s->d_ring, (void *)s->d_ramp, (void *)s->d_tail, (void *)s->d_rampTable, (void *)s->d_rampCount, (void *)s->d_xyz, (void *)s->d_rgb})
+            if (p) (void)hipFree(p);
+        if (s->h_out) (void)hipHostFree(s->h_out);
+    });
     delete s;
 }
 
@@ -426,11 +400,9 @@ static sgz_status vectorSetup(sgz_vector *s, const sgz_vector_config *cfg, bool 
         SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_xyz), pairsCap * size * 3 * sizeof(float)));
         SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_rgb), pairsCap * size * 3 * sizeof(float)));
         SGZ_HIP(hipHostMalloc(&s->h_out, pairsCap * size * 6 * sizeof(float), hipHostMallocDefault));
-        sgz_status st = s->batch.init(C, std::max<uint32_t>(maxBlock, 8192u));     // a slot takes a whole batch: the blocks of a rendered frame and more
-        s->maxBlock = maxBlock;
+        const sgz_status st = s->staging(C, cfg->sample_rate, maxBlock);
+        s->maxBlock = maxBlock;                   // (also when the slots could not be had)
         if (st != SGZ_OK) return st;
-        // one second of audio may wait for the GPU (at least 32 blocks)
-        if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
         if (!s->d_state) {
             SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_state), sizeof(VecDev)));
             SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_tail), 2 * sizeof(float)));
@@ -444,10 +416,8 @@ static sgz_status vectorSetup(sgz_vector *s, const sgz_vector_config *cfg, bool 
             SGZ_HIP(hipMemcpy(s->d_state, &h, sizeof(h), hipMemcpyHostToDevice));
         }
     }
-    if (s->batch.channels != C) {             // a configure after sgz_vector_set_mix: the staging takes num_channels rows again
-        if (sgz_status st = s->batch.init(C, std::max<uint32_t>(s->maxBlock, 8192u)); st != SGZ_OK) return st;
-        if (!s->backlog.init(backlogFloats(C, cfg->sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
-    }
+    if (s->batch.channels != C)               // a configure after sgz_vector_set_mix: the staging takes num_channels rows again
+        if (sgz_status st = s->staging(C, cfg->sample_rate, s->maxBlock); st != SGZ_OK) return st;
     s->mix.reset(C);                          // the routing returns to the identity over num_channels
     s->size = size;
     // handleFlagUpdates, Vectorscope.cpp:201-202: relaxed_atomic<float> coefficients
@@ -493,10 +463,8 @@ static sgz_status vectorSubmit(sgz_vector *s)
     const float *d_batch = s->batch.upload(s->stream, &st, &fetchFrom, &floats);
     if (!d_batch) return st;
     VecIngest prm{};
-    prm.batchHost = fetchFrom; prm.batchFloats = floats;
-    prm.st = s->d_state; prm.batch = d_batch; prm.numBlocks = s->batch.count; prm.channels = s->cfg.num_channels;
-    for (uint32_t b = 0; b < s->batch.count; ++b) { prm.blockOff[b] = s->batch.off[b]; prm.blockLen[b] = s->batch.len[b]; }
-    if (s->mix.active) { prm.route = s->mix.d_route; prm.mixRows = s->mix.d_rows; prm.numSources = s->batch.channels; }
+    s->fill(prm.in, d_batch, fetchFrom, floats, s->cfg.num_channels);
+    prm.st = s->d_state;
     prm.ring = s->d_ring; prm.size = s->size; prm.lanes = s->cfg.lanes; prm.envMode = s->cfg.envelope_mode;
     prm.envelope = s->envelopeCoeff; prm.pole0 = s->stereoCoeff; prm.pole1 = s->pole1;
     hipLaunchKernelGGL(vectorIngestKernel, dim3(1), dim3(256), 0, s->stream, prm);
@@ -505,78 +473,29 @@ static sgz_status vectorSubmit(sgz_vector *s)
     return s->batch.commit(s->stream);
 }
 
-// the handle's GPU side for rt_lockfree.hpp's hand-over protocol (batchPush / batchSync / batchFlushAll; the ThreadSanitizer harness runs
-// the same protocol code on a mock GPU)
-namespace {
-struct VectorIngestSide {
-    sgz_vector *s;
-    BatchCore &batch() { return s->batch; }
-    Backlog &backlog() { return s->backlog; }
-    sgz_status submit() { return vectorSubmit(s); }
-    sgz_status slotReady() { return s->batch.slotReady(); }
-    bool gpuIdle() { return s->batch.idle(); }
-    void waitGpu() { (void)hipStreamSynchronize(s->stream); }
-    bool deferSubmit() { return s->deferSubmit.load(std::memory_order_relaxed); }
-};
-}  // namespace
+static auto vectorSubmitter(sgz_vector *s) { return [s] { return vectorSubmit(s); }; }
 
 // consumer side (flush on read): what waits in the host FIFO and in the open batch goes to the GPU in front of the caller's own work
-static sgz_status vectorSync(sgz_vector *s)
-{
-    VectorIngestSide side{s};
-    return batchSync(side);
-}
+static sgz_status vectorSync(sgz_vector *s) { return s->sync(vectorSubmitter(s)); }
 
 sgz_status sgz_vector_push(sgz_vector *s, const float *const *planar, uint32_t num_channels, uint32_t nsamples)
 {
-    if (!s || !planar) return fail(SGZ_EINVAL, "null argument");
-    std::unique_lock<std::mutex> lk(s->mu, std::try_to_lock);
-    if (!lk.owns_lock()) { s->busy++; return SGZ_BUSY; }
-    if (num_channels != s->mix.numSources)
-        return fail(SGZ_EINVAL, "num_channels differs from the configuration (or from the source count of sgz_vector_set_mix)");
-    if (nsamples == 0) return SGZ_OK;
-    if (nsamples > s->maxBlock) return fail(SGZ_EINVAL, "block longer than sgz_vector_config::max_block");
-    // never waits: the render thread is submitting the open batch right now -> the block waits its turn in the host FIFO, like one the
-    // GPU is not ready for (rt_common.hpp Backlog); SGZ_BUSY = that FIFO is full
-    // (SGZ_RT_OPT_PARK_PUSHES: every block takes that way -- the tests' handle on a race that timing alone produces)
-    VectorIngestSide side{s};
-    const sgz_status st = batchPush(side, planar, num_channels, nsamples, s->parkPushes.load(std::memory_order_relaxed));
-    if (st == SGZ_BUSY) s->busy++;
-    return st;
+    return s ? s->push(vectorSubmitter(s), planar, num_channels, nsamples, "vector") : fail(SGZ_EINVAL, "null argument");
 }
 
 sgz_status sgz_vector_set_mix(sgz_vector *s, uint32_t num_sources, const uint8_t *matrix)
 {
-    if (!s || !matrix || num_sources == 0 || num_sources > MixRoute::kMax) return fail(SGZ_EINVAL, "bad argument");
-    std::lock_guard<std::mutex> lk(s->mu);                                // (a push meanwhile is refused with SGZ_BUSY: it never waits)
-    if (sgz_status sy = vectorSync(s); sy != SGZ_OK) return sy;           // the audio already taken goes through the old routing
-    SGZ_HIP(hipStreamSynchronize(s->stream));
-    if (s->batch.channels != num_sources) {                               // staging, pinned slot and FIFO for num_sources rows per block
-        if (sgz_status st = s->batch.init(num_sources, std::max<uint32_t>(s->maxBlock, 8192u)); st != SGZ_OK) return st;
-        if (!s->backlog.init(backlogFloats(num_sources, s->cfg.sample_rate, s->maxBlock))) return fail(SGZ_ENOMEM, "out of memory (push backlog)");
-    }
-    return s->mix.set(num_sources, s->cfg.num_channels, matrix, s->batch.slotSamples);
+    return s ? s->setMix(num_sources, s->cfg.num_channels, s->cfg.sample_rate, matrix, vectorSubmitter(s)) : fail(SGZ_EINVAL, "bad argument");
 }
 
 void *sgz_vector_stream(sgz_vector *s) { return s ? s->stream : nullptr; }
 
 sgz_status sgz_vector_set_option(sgz_vector *s, uint32_t option, uint64_t value)
 {
-    if (!s) return fail(SGZ_EINVAL, "null handle");
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (option == SGZ_RT_OPT_PARK_PUSHES) { s->parkPushes.store(value != 0, std::memory_order_relaxed); return SGZ_OK; }
-    if (option != SGZ_RT_OPT_DEFER_SUBMIT) return fail(SGZ_EINVAL, "unknown vector option");
-    s->deferSubmit.store(value != 0, std::memory_order_relaxed);
-    return SGZ_OK;
+    return s ? s->setOption(option, value, "vector") : fail(SGZ_EINVAL, "null handle");
 }
 
-sgz_status sgz_vector_flush(sgz_vector *s)
-{
-    if (!s) return fail(SGZ_EINVAL, "null handle");
-    std::lock_guard<std::mutex> lk(s->mu);
-    VectorIngestSide side{s};
-    return batchFlushAll(side);                                       // (this call may wait: it is not the audio thread's)
-}
+sgz_status sgz_vector_flush(sgz_vector *s) { return s ? s->flush(vectorSubmitter(s)) : fail(SGZ_EINVAL, "null handle"); }
 
 sgz_status sgz_vector_peak_filter(sgz_vector *s, double delta_time, double *envelope_gain)
 {

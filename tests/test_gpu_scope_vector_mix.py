@@ -391,6 +391,36 @@ def test_source_count_refusals_leave_the_stream_unchanged(gpu, kind):
 
 
 @pytest.mark.parametrize("kind", ["scope", "vector"])
+def test_both_handles_answer_misuse_with_the_same_status(gpu, kind):
+    """one walk through the entry points' refusals, the same for both handles: every refused call returns its status and leaves the
+    stream alone, and the handle ends up equal to a twin that only saw the accepted blocks"""
+    L = api.lib()
+    call = lambda name, h, *args: getattr(L, f"sgz_{kind}_{name}")(h.h, *args)      # noqa: E731
+    if kind == "scope":
+        cfg = _scope_cfg(num_channels=2, window_size=64.0, max_block=16, trigger_mode=0)
+    else:
+        cfg = _vector_cfg(num_channels=2, window_size=64, max_block=16)
+    x = _sources(90, 3 * 8, 3, cfg["sample_rate"])
+    a, b = _handles(kind, cfg)
+    assert _raw_push(a, kind, x[:, :8]) == api.SGZ_EINVAL                  # 3 channels into a 2-channel handle
+    assert _raw_push(a, kind, x[:2, :0]) == api.SGZ_OK                     # no samples: accepted, nothing consumed
+    assert _raw_push(a, kind, np.zeros((2, 17), np.float32)) == api.SGZ_EINVAL      # longer than max_block
+    assert call("set_option", a, 99, 1) == api.SGZ_EINVAL                  # no such option
+    assert call("set_mix", a, 0, np.ones((2, 1), np.uint8).ctypes.data) == api.SGZ_EINVAL
+    assert call("set_mix", a, 65, np.ones((2, 65), np.uint8).ctypes.data) == api.SGZ_EINVAL
+    assert call("set_option", a, api.RT_OPT_PARK_PUSHES, 1) == api.SGZ_OK
+    for pos in range(0, 24, 8):
+        assert _raw_push(a, kind, x[:2, pos:pos + 8]) == api.SGZ_OK        # parked in the host FIFO
+        _push(b, x[:2, pos:pos + 8])
+    assert call("flush", a) == api.SGZ_OK
+    for c in range(2):
+        got, gcur = a.front(c) if kind == "scope" else a.history(c)
+        want, wcur = b.front(c) if kind == "scope" else b.history(c)
+        assert gcur == wcur and _same(got, want), f"channel {c}"
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("kind", ["scope", "vector"])
 def test_full_batch_at_the_maximum_shape(gpu, kind):
     """64 sources into 64 channels at max_block 8192, deferred submission: every batch is a full slot"""
     if kind == "scope":
