@@ -33,6 +33,9 @@ extern "C" {
  *  the suite pins 5; a binding that sets the option on an older library gets SGZ_EINVAL, "unknown plan option", and looks the hook up.)
  * (5, later: sgz_spectrum_update, sgz_spectrum_update_effects (SGZ_UPDATE_*) and the stage call sgz_ring_resize_device.  No existing
  *  entry point or struct changed and the suite pins 5; a binding that needs them looks the symbols up.)
+ * (5, later: interleaved PCM in -- SGZ_PCM_*, sgz_pcm_sample_bytes, sgz_pcm_to_planar_device, the sgz_pcm_stream handle, sgz_stream_step and
+ *  sgz_spectrogram_render_pcm.  No existing entry point or struct changed and the suite pins 5; a binding that needs them looks the
+ *  symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -289,6 +292,76 @@ sgz_status sgz_spectrogram_render_host(sgz_plan *plan, const float *const *plana
 sgz_status sgz_spectrogram_render(const sgz_spectrum_config *cfg, const float *const *planar,
                                   uint32_t num_channels, size_t nsamples, uint8_t *rgba_out,
                                   float *lines_out, sgz_timing *timing);
+
+/* ---- interleaved PCM in: the offline render fed as a decoder hands audio out ---------------------------------------------------------
+ * Audio files hold interleaved integer PCM, often with more channels than the plan has; the planar fp32 the entry points above take is
+ * what a caller would otherwise produce on the CPU (and then send 4 bytes per sample where 2 or 3 would do).  The reference has no
+ * counterpart: its host hands planar float blocks to onStreamAudio (Spectrum.h:370).
+ *
+ * Formats: little-endian, sample i of source channel c at byte (i * src_channels + c) * sample_bytes.  The fp32 value is defined exactly:
+ *   SGZ_PCM_U8   (x - 128) * 2^-7                    SGZ_PCM_S16  x * 2^-15                SGZ_PCM_S24  3 packed bytes, sign-extended, x * 2^-23
+ *   SGZ_PCM_S32  (float) x, nearest even, * 2^-31    SGZ_PCM_F32  the 32 bits copied (NaN payloads, -0, denormals kept)
+ *   SGZ_PCM_F64  rounded to nearest even (overflow to +-inf, underflow to a denormal or 0; a NaN stays a NaN, payload unspecified) */
+enum { SGZ_PCM_F32 = 0, SGZ_PCM_U8, SGZ_PCM_S16, SGZ_PCM_S24, SGZ_PCM_S32, SGZ_PCM_F64, SGZ_PCM_END };
+uint32_t   sgz_pcm_sample_bytes(uint32_t format);            /* 4, 1, 2, 3, 4, 8; 0 for an unknown format (host only) */
+/* Convert and de-interleave on the device: row d of d_planar (d < num_channels, at d_planar + d * channel_stride) receives source channel
+ * channel_map[d] (HOST array; NULL = identity).  A source channel may feed several rows or none.  Only d_planar[d * channel_stride + i],
+ * i < nsamples, is written, and only the nsamples * src_channels * sample_bytes bytes at d_pcm are read.  Asynchronous on `stream`.
+ * SGZ_EINVAL, nothing written: a null pointer, an unknown format, src_channels or num_channels of 0 or above 64, a map entry >= src_channels
+ * (identity: src_channels < num_channels), channel_stride < nsamples, d_pcm not aligned to the sample's natural alignment (1 for U8 and
+ * S24).  nsamples == 0: SGZ_OK, nothing is launched. */
+sgz_status sgz_pcm_to_planar_device(const void *d_pcm, uint32_t format, uint32_t src_channels, size_t nsamples,
+                                    const uint32_t *channel_map /*HOST [num_channels] or NULL = identity*/, uint32_t num_channels,
+                                    float *d_planar, size_t channel_stride, void *stream);
+
+/* The arithmetic of a streamed render (host only): `held` samples are waiting, `incoming` arrive; with total = held + incoming,
+ * *frames = total >= window_size ? (total - window_size) / hop + 1 : 0 frames are complete (frame f = samples [f*hop, f*hop + W) of the
+ * stream) and *keep = total - *frames * hop samples stay for the next step (keep < window_size; keep >= window_size - hop once a frame
+ * was made).  SGZ_EINVAL: a zero window or hop, a null result, hop > window_size (samples between frames would have to be skipped:
+ * not a stream this arithmetic describes). */
+sgz_status sgz_stream_step(uint32_t window_size, uint32_t hop, uint64_t held, uint64_t incoming, uint64_t *frames, uint64_t *keep);
+
+typedef struct sgz_pcm_timing {     /* filled by feed / render_pcm when non-NULL.  The four stage times are sums of event intervals on three */
+    double wall_ms;                 /* streams that overlap: together they may exceed wall_ms (the host's clock around the call).  Asking for */
+                                    /* it puts four more event markers per piece on the streams: time a run without it for the wall clock    */
+    double h2d_ms, convert_ms, render_ms, d2h_ms;
+    uint64_t frames, chunks;        /* columns returned; pieces the PCM was cut into */
+} sgz_pcm_timing;
+
+/* The stream handle: interleaved PCM in pieces of any size -> the spectrogram's columns (and line results) as they become complete.
+ * Let the stream be everything fed since create or reset.  What all feeds returned, concatenated, equals what
+ * sgz_spectrogram_render_host returns for the stream's converted planar floats, byte for byte, however the stream is cut into feeds
+ * (empty, one-sample, shorter than the hop or than the held tail) and whatever chunk_samples is.  A feed returns exactly the frames that
+ * became complete (sgz_stream_step; sgz_pcm_stream_frames_for tells how many the next feed of nsamples yields); a stream that never reaches
+ * window_size samples yields none (feeds: SGZ_OK, *frames_out = 0).
+ *   channel_map    HOST [2*num_pairs]: plan channel d is source channel channel_map[d]; NULL = identity
+ *   chunk_samples  a feed is cut into pieces of at most this many samples; every piece is uploaded on a copy stream (from the caller's
+ *                  memory when it is pinned -- hipHostMalloc / hipHostRegister --, else through one of two pinned slots), converted and
+ *                  rendered with carried decay state on a compute stream, and read back on a third (into the caller's memory when pinned):
+ *                  upload k+1, render k and read-back k-1 overlap; the host waits to reuse a slot and at the end of the feed.  Device and
+ *                  pinned memory are bounded by chunk_samples and window_size, never by the stream's length.
+ *                  0 = the default: 2^20 samples, less where a slot of that many frames would pass 256 MiB (64-channel F64: 2^19).  By
+ *                  measurement (tools/bench_pcm_render.py, a kept stream fed cfg2's 60 s of stereo S16 at 2^16 .. 2^22: 5.1 / 2.5 / 1.4 /
+ *                  0.93 / 0.67 / 0.65 / 0.66 ms): a piece costs ~0.1 ms of host and stream work whatever its size.  At most 2^26.
+ *   rgba_out       HOST RGBA8 [capacity_frames][P][4]; lines_out: optional HOST float2 [capacity_frames][pairs][graphs][P]
+ * Refusals consume nothing and leave the stream unchanged.  SGZ_EINVAL: what sgz_plan_create or the converter refuses, a null pcm with
+ * nsamples > 0, capacity_frames below the need (*frames_out then holds the need), chunk_samples above 2^26.  SGZ_EUNSUPPORTED: an RSNT
+ * configuration (its multi-frame launches chain frames from rest within an fp32 bar, not bit for bit: a chunked render would not equal
+ * the single one), hop > window_size.  The FFT algorithm is taken in all eight channel modes.
+ * reset: a new file -- held samples dropped, decay state zero.  One thread at a time per stream; streams are independent. */
+typedef struct sgz_pcm_stream sgz_pcm_stream;
+sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format, uint32_t src_channels,
+                                 const uint32_t *channel_map /*[2*num_pairs] or NULL*/, size_t chunk_samples /*0 = default*/,
+                                 sgz_pcm_stream **out);
+void       sgz_pcm_stream_destroy(sgz_pcm_stream *s);
+uint64_t   sgz_pcm_stream_frames_for(const sgz_pcm_stream *s, size_t nsamples);   /* frames the next feed of nsamples yields */
+sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm /*HOST*/, size_t nsamples, uint8_t *rgba_out, float *lines_out /*or NULL*/,
+                               uint64_t capacity_frames, uint64_t *frames_out, sgz_pcm_timing *timing /*or NULL*/);
+sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s);
+/* One-shot: a stream with the default chunk_samples (the buffer's length if that is less), one feed of the whole buffer (rgba_out / lines_out hold
+ * sgz_num_frames frames), destroyed.  Fewer samples than one window: SGZ_SKIPPED_FRAME, as sgz_spectrogram_render_host. */
+sgz_status sgz_spectrogram_render_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                      const uint32_t *channel_map, size_t nsamples, uint8_t *rgba_out, float *lines_out, sgz_pcm_timing *timing);
 
 /* Device memory for the display hand-off: `bytes` rounded up to whole 2 MiB blocks (*allocated), exported as a dma-buf
  * file descriptor (dmabuf_fd may be NULL: plain allocation) that the GL / Vulkan context of the display GPU -- an MI355X has no graphics

@@ -60,6 +60,19 @@ class Timing(C.Structure):
     _fields_ = [("h2d_ms", C.c_double), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("frames", C.c_uint64)]
 
 
+class PcmTiming(C.Structure):
+    _fields_ = [("wall_ms", C.c_double), ("h2d_ms", C.c_double), ("convert_ms", C.c_double), ("render_ms", C.c_double), ("d2h_ms", C.c_double),
+                ("frames", C.c_uint64), ("chunks", C.c_uint64)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# sgz_pcm_to_planar_device / sgz_pcm_stream: the interleaved sample formats (SGZ_PCM_*) and their bytes per sample
+PCM_F32, PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F64, PCM_END = range(7)
+PCM_SAMPLE_BYTES = {PCM_F32: 4, PCM_U8: 1, PCM_S16: 2, PCM_S24: 3, PCM_S32: 4, PCM_F64: 8}
+
+
 class ScopeView(C.Structure):
     _fields_ = [("window_size", C.c_double), ("left", C.c_double), ("right", C.c_double),
                 ("rendering_scale", C.c_double), ("width", C.c_uint32), ("_pad", C.c_uint32)]
@@ -175,6 +188,8 @@ EXPORTS = [
     "sgz_columns_to_image_device", "sgz_image_unroll_device",
     "sgz_scope_dense_vertex_count", "sgz_scope_dense_vertices", "sgz_scope_dense_vertices_all", "sgz_scope_dense_vertices_device",
     "sgz_scope_dense_device",
+    "sgz_pcm_sample_bytes", "sgz_pcm_to_planar_device", "sgz_stream_step", "sgz_pcm_stream_create", "sgz_pcm_stream_destroy",
+    "sgz_pcm_stream_frames_for", "sgz_pcm_stream_feed", "sgz_pcm_stream_reset", "sgz_spectrogram_render_pcm",
 ]
 
 
@@ -360,6 +375,19 @@ def lib() -> C.CDLL:
     L.sgz_vector_polar_device.argtypes = [vp, sz, u32, sz, u32, vp, vp]
     L.sgz_vector_audio_processing_device.argtypes = [C.POINTER(VectorFilters), vp, vp, sz, u32, C.c_float,
                                                      C.c_float, C.c_float, C.c_int, C.POINTER(C.c_float), vp]
+    u64 = C.c_uint64
+    L.sgz_pcm_sample_bytes.argtypes = [u32]
+    L.sgz_pcm_sample_bytes.restype = u32
+    L.sgz_pcm_to_planar_device.argtypes = [vp, u32, u32, sz, vp, u32, vp, sz, vp]
+    L.sgz_stream_step.argtypes = [u32, u32, u64, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.sgz_pcm_stream_create.argtypes = [C.POINTER(SpectrumConfig), u32, u32, vp, sz, C.POINTER(vp)]
+    L.sgz_pcm_stream_destroy.argtypes = [vp]
+    L.sgz_pcm_stream_destroy.restype = None
+    L.sgz_pcm_stream_frames_for.argtypes = [vp, sz]
+    L.sgz_pcm_stream_frames_for.restype = u64
+    L.sgz_pcm_stream_feed.argtypes = [vp, vp, sz, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
+    L.sgz_pcm_stream_reset.argtypes = [vp]
+    L.sgz_spectrogram_render_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, vp, vp, C.POINTER(PcmTiming)]
     _lib = L
     return L
 
@@ -827,6 +855,99 @@ def render_spectrogram_host(plan, planar: np.ndarray, want_lines: bool = False):
     t = Timing()
     check(lib().sgz_spectrogram_render_host(plan.h, ptrs, nch, S, _np_ptr(rgba), _np_ptr(lines) if want_lines else None, C.byref(t)))
     return rgba, lines, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+
+
+def stream_step(window_size: int, hop: int, held: int, incoming: int):
+    """sgz_stream_step (host arithmetic, no GPU): (frames that become complete, samples kept for the next step)"""
+    f, k = C.c_uint64(0), C.c_uint64(0)
+    check(lib().sgz_stream_step(window_size, hop, held, incoming, C.byref(f), C.byref(k)))
+    return int(f.value), int(k.value)
+
+
+def _channel_map(channel_map):
+    if channel_map is None:
+        return None, None
+    m = np.ascontiguousarray(channel_map, np.uint32)
+    return m, _np_ptr(m)
+
+
+def pcm_to_planar_device(pcm, fmt: int, src_channels: int, nsamples: int, planar, channel_map=None, num_channels: int | None = None,
+                         channel_stride: int | None = None, stream=None) -> None:
+    """sgz_pcm_to_planar_device: pcm -- a cuda tensor of interleaved bytes (any dtype; its data pointer is the first sample), planar -- a cuda
+    float32 tensor [num_channels, >= nsamples] with contiguous rows.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    m, mp = _channel_map(channel_map)
+    nch = num_channels if num_channels is not None else (len(m) if m is not None else planar.shape[0])
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    check(lib().sgz_pcm_to_planar_device(_buf_ptr(pcm), fmt, src_channels, nsamples, mp, nch, _buf_ptr(planar),
+                                         channel_stride if channel_stride is not None else planar.stride(0), s))
+
+
+class PcmStream:
+    """sgz_pcm_stream: interleaved PCM in pieces -> spectrogram columns as they become complete (sgz.h "interleaved PCM in").
+    pcm: a numpy array or a host torch tensor (pinned memory is uploaded from in place) holding nsamples * src_channels samples of the
+    format; the bytes are taken as they lie."""
+
+    def __init__(self, cfg, fmt: int, src_channels: int, channel_map=None, chunk_samples: int = 0):
+        self.cfg = _as_config(cfg)
+        self.format, self.src_channels = fmt, src_channels
+        self.frame_bytes = src_channels * PCM_SAMPLE_BYTES.get(fmt, 0)
+        m, mp = _channel_map(channel_map)
+        self.h = C.c_void_p()
+        check(lib().sgz_pcm_stream_create(C.byref(self.cfg), fmt, src_channels, mp, chunk_samples, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().sgz_pcm_stream_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                           # noqa: BLE001
+            pass
+
+    def frames_for(self, nsamples: int) -> int:
+        return int(lib().sgz_pcm_stream_frames_for(self.h, nsamples))
+
+    def reset(self):
+        check(lib().sgz_pcm_stream_reset(self.h))
+
+    def feed_into(self, pcm, nsamples: int, rgba, lines, capacity_frames: int, timing: bool = True):
+        """the C call as it is: (status, frames_out, PcmTiming or None); rgba / lines: numpy arrays or host torch tensors (lines may be None)"""
+        t, f = PcmTiming() if timing else None, C.c_uint64(0)
+        st = lib().sgz_pcm_stream_feed(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, _buf_ptr(rgba) if rgba is not None else None,
+                                       _buf_ptr(lines) if lines is not None else None, capacity_frames, C.byref(f), C.byref(t) if timing else None)
+        return st, int(f.value), t
+
+    def feed(self, pcm, nsamples: int | None = None, want_lines: bool = False):
+        """Feeds nsamples (default: all of pcm) and returns (rgba uint8 [frames, P, 4], lines float32 [frames, pairs, graphs, P, 2] or None,
+        timing dict)."""
+        nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+        n = nbytes // self.frame_bytes if nsamples is None else nsamples
+        F, P = self.frames_for(n), self.cfg.axis_points
+        rgba = np.zeros((max(F, 1), P, 4), np.uint8)
+        lines = np.zeros((max(F, 1), self.cfg.num_pairs, NUM_GRAPHS, P, 2), np.float32) if want_lines else None
+        st, f, t = self.feed_into(pcm if n else None, n, rgba, lines, F)
+        check(st)
+        assert f == F, (f, F)
+        return rgba[:F], lines[:F] if want_lines else None, t.asdict()
+
+
+def render_spectrogram_pcm(cfg, pcm, fmt: int, src_channels: int, channel_map=None, nsamples: int | None = None, want_lines: bool = False):
+    """One-shot render of an interleaved PCM buffer (sgz_spectrogram_render_pcm): (status, rgba, lines, timing dict); status is
+    SGZ_SKIPPED_FRAME for fewer samples than one window."""
+    c = _as_config(cfg)
+    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
+    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
+    rgba = np.zeros((max(F, 1), c.axis_points, 4), np.uint8)               # (never an empty array: its pointer may be null)
+    lines = np.zeros((max(F, 1), c.num_pairs, NUM_GRAPHS, c.axis_points, 2), np.float32) if want_lines else None
+    m, mp = _channel_map(channel_map)
+    t = PcmTiming()
+    st = check(lib().sgz_spectrogram_render_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, _np_ptr(rgba),
+                                                _np_ptr(lines) if want_lines else None, C.byref(t)))
+    return st, rgba[:F], lines[:F] if want_lines else None, t.asdict()
 
 
 def rotate_hue(rgb, amount: float) -> np.ndarray:

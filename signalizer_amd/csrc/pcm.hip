@@ -1,0 +1,430 @@
+// pcm.hip -- interleaved PCM in (include/sgz.h "interleaved PCM in"): the convert-and-de-interleave kernel, and the stream handle that
+// cuts a feed into pieces and runs upload / convert + render / read-back of neighbouring pieces side by side on three streams.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <new>
+
+#include "rt_common.hpp"       // isPinnedHost
+#include "runtime.hpp"
+
+namespace sgz {
+
+// ---- the converter ---------------------------------------------------------------------------------------------------------------------
+// A transposition whose input rows (one sample of every source channel: a "frame" of frameBytes = src_channels * sample_bytes, 1 .. 512
+// bytes, 3, 9, 15 ... for S24) are much shorter than a wave's access.  One workgroup takes a tile of tileSamples consecutive frames:
+//   load   the tile's bytes as 16-byte chunks at 16-byte-aligned ADDRESSES, whatever the frame size and wherever d_pcm starts, lane after
+//          lane (1 KiB per wave instruction), into LDS at the same offsets -- the tile's first byte sits `lead` = address & 15 bytes in.
+//          A chunk that reaches over either end of the PCM buffer (the first chunk of the first tile, the last of the last) is read byte by
+//          byte instead: nothing outside [d_pcm, d_pcm + nsamples * frameBytes) is touched.  Chunks that reach into a NEIGHBOURING tile are
+//          read whole (those bytes are the buffer's own).
+//   store  a wave takes one (destination row, 64 consecutive samples) unit at a time: lane l reads its sample from LDS -- any byte address:
+//          the word that holds it and, for S24 / F64, the next one -- converts, and the wave stores 64 consecutive floats of that row.
+// All byte offsets are 64-bit (a tile's start: tile * tileSamples * frameBytes).
+constexpr int kPcmThreads = 256;
+constexpr uint32_t kPcmMaxChannels = 64;
+constexpr uint32_t kPcmTileBytes = 16384;       // the tile's target size; one frame group of 64 samples is the least (up to 32 KiB: 64 x F64)
+constexpr uint32_t kPcmMaxTileSamples = 4096;
+
+struct PcmMap { uint32_t src[kPcmMaxChannels]; };
+
+template <uint32_t FORMAT> struct PcmBytes;
+template <> struct PcmBytes<SGZ_PCM_F32> { static constexpr uint32_t value = 4; };
+template <> struct PcmBytes<SGZ_PCM_U8> { static constexpr uint32_t value = 1; };
+template <> struct PcmBytes<SGZ_PCM_S16> { static constexpr uint32_t value = 2; };
+template <> struct PcmBytes<SGZ_PCM_S24> { static constexpr uint32_t value = 3; };
+template <> struct PcmBytes<SGZ_PCM_S32> { static constexpr uint32_t value = 4; };
+template <> struct PcmBytes<SGZ_PCM_F64> { static constexpr uint32_t value = 8; };
+
+// the sample at LDS byte offset `at` (a multiple of the sample's natural alignment) as the fp32 word sgz.h defines
+template <uint32_t FORMAT>
+__device__ __forceinline__ uint32_t pcmSample(const uint32_t *words, uint32_t at)
+{
+    const uint32_t w = at >> 2, sh = (at & 3u) * 8u;
+    if constexpr (FORMAT == SGZ_PCM_F32) {
+        return words[w];                                                   // the bits themselves: no arithmetic touches a NaN
+    } else if constexpr (FORMAT == SGZ_PCM_S32) {
+        return __float_as_uint(float(int32_t(words[w])) * 0x1p-31f);       // v_cvt_f32_i32 rounds to nearest even
+    } else if constexpr (FORMAT == SGZ_PCM_S16) {
+        return __float_as_uint(float(int32_t(int16_t(words[w] >> sh))) * 0x1p-15f);
+    } else if constexpr (FORMAT == SGZ_PCM_U8) {
+        return __float_as_uint(float(int32_t((words[w] >> sh) & 0xffu) - 128) * 0x1p-7f);
+    } else if constexpr (FORMAT == SGZ_PCM_S24) {
+        // three bytes anywhere in two words (the second one is read even where the sample ends in the first: the tile has a pad word)
+        const uint64_t two = uint64_t(words[w]) | uint64_t(words[w + 1]) << 32;
+        const int32_t x = int32_t(uint32_t(two >> sh) << 8) >> 8;
+        return __float_as_uint(float(x) * 0x1p-23f);
+    } else {
+        const double v = __longlong_as_double((long long)(uint64_t(words[w]) | uint64_t(words[w + 1]) << 32));
+        return __float_as_uint(float(v));                                  // v_cvt_f32_f64: nearest even, denormal results kept
+    }
+}
+
+template <uint32_t FORMAT>
+__global__ __launch_bounds__(kPcmThreads) void pcmToPlanarKernel(const uint8_t *__restrict__ pcm, uint64_t nsamples, uint32_t srcChannels,
+                                                                 uint32_t tileSamples, PcmMap map, uint32_t numChannels,
+                                                                 uint32_t *__restrict__ planar, uint64_t channelStride)
+{
+    extern __shared__ uint4 pcmTile[];                                     // [lead + tile bytes, rounded up to chunks] + one pad chunk
+    constexpr uint32_t kBytes = PcmBytes<FORMAT>::value;
+    const uint32_t frameBytes = srcChannels * kBytes;
+    const uint64_t first = uint64_t(blockIdx.x) * tileSamples;             // the tile's first sample
+    const uint32_t count = uint32_t(min(uint64_t(tileSamples), nsamples - first));
+    const uint64_t bufBegin = reinterpret_cast<uint64_t>(pcm), bufEnd = bufBegin + nsamples * frameBytes;
+    const uint64_t tileBegin = bufBegin + first * frameBytes, tileEnd = tileBegin + uint64_t(count) * frameBytes;
+    const uint64_t aligned = tileBegin & ~uint64_t(15);
+    const uint32_t lead = uint32_t(tileBegin - aligned);
+    const uint32_t chunks = uint32_t((tileEnd - aligned + 15) >> 4);
+    for (uint32_t k = threadIdx.x; k < chunks; k += kPcmThreads) {
+        const uint64_t a = aligned + uint64_t(k) * 16;
+        uint4 v;
+        if (a >= bufBegin && a + 16 <= bufEnd) {
+            v = *reinterpret_cast<const uint4 *>(pcm + int64_t(a - bufBegin));
+        } else {                                                           // at most two chunks of a launch: the buffer's own bytes, one by one
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (uint32_t b = 0; b < 16; ++b)
+                if (a + b >= bufBegin && a + b < bufEnd) w[b >> 2] |= uint32_t(pcm[int64_t(a + b - bufBegin)]) << ((b & 3u) * 8u);
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        pcmTile[k] = v;
+    }
+    __syncthreads();
+    const uint32_t *words = reinterpret_cast<const uint32_t *>(pcmTile);
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (uniform: map.src[d] is a scalar load)
+    const uint32_t groups = (count + 63u) >> 6;
+    for (uint32_t u = wave; u < groups * numChannels; u += kPcmThreads / 64) {
+        const uint32_t d = u / groups, i = (u - d * groups) * 64u + lane;  // (d and the group are the same in every lane of the wave)
+        if (i < count) planar[uint64_t(d) * channelStride + first + i] = pcmSample<FORMAT>(words, lead + (i * srcChannels + map.src[d]) * kBytes);
+    }
+}
+
+static uint32_t pcmTileSamples(uint32_t frameBytes)
+{
+    return std::min(kPcmMaxTileSamples, 64u * std::max(1u, kPcmTileBytes / (64u * frameBytes)));
+}
+
+static uint32_t pcmAlignment(uint32_t format)
+{
+    return format == SGZ_PCM_S16 ? 2u : (format == SGZ_PCM_S32 || format == SGZ_PCM_F32) ? 4u : format == SGZ_PCM_F64 ? 8u : 1u;
+}
+
+static uint32_t pcmSampleBytes(uint32_t format)
+{
+    switch (format) {
+    case SGZ_PCM_F32: case SGZ_PCM_S32: return 4;
+    case SGZ_PCM_U8: return 1;
+    case SGZ_PCM_S16: return 2;
+    case SGZ_PCM_S24: return 3;
+    case SGZ_PCM_F64: return 8;
+    default: return 0;
+    }
+}
+
+// everything the converter refuses that does not depend on the buffers (the stream handle checks it at create)
+static sgz_status checkPcmLayout(uint32_t format, uint32_t srcChannels, const uint32_t *channelMap, uint32_t numChannels, PcmMap &map)
+{
+    if (pcmSampleBytes(format) == 0) return fail(SGZ_EINVAL, "unknown PCM format");
+    if (srcChannels == 0 || srcChannels > kPcmMaxChannels || numChannels == 0 || numChannels > kPcmMaxChannels)
+        return fail(SGZ_EINVAL, "PCM: 1 .. 64 source channels and 1 .. 64 destination rows");
+    if (!channelMap && srcChannels < numChannels) return fail(SGZ_EINVAL, "PCM: the identity map needs src_channels >= num_channels");
+    for (uint32_t d = 0; d < numChannels; ++d) {
+        map.src[d] = channelMap ? channelMap[d] : d;
+        if (map.src[d] >= srcChannels) return fail(SGZ_EINVAL, "PCM: channel_map entry >= src_channels");
+    }
+    for (uint32_t d = numChannels; d < kPcmMaxChannels; ++d) map.src[d] = 0;
+    return SGZ_OK;
+}
+
+static sgz_status launchPcmToPlanar(const void *d_pcm, uint32_t format, uint32_t srcChannels, size_t nsamples, const PcmMap &map,
+                                    uint32_t numChannels, float *d_planar, size_t channelStride, hipStream_t stream)
+{
+    if (!d_pcm || !d_planar) return fail(SGZ_EINVAL, "null buffer");
+    if (channelStride < nsamples) return fail(SGZ_EINVAL, "PCM: channel_stride < nsamples");
+    if (reinterpret_cast<uintptr_t>(d_pcm) % pcmAlignment(format)) return fail(SGZ_EINVAL, "PCM: d_pcm is not aligned to its sample type");
+    if (nsamples == 0) return SGZ_OK;
+    const uint32_t frameBytes = srcChannels * pcmSampleBytes(format);
+    const uint32_t tileSamples = pcmTileSamples(frameBytes);
+    const size_t tiles = (nsamples + tileSamples - 1) / tileSamples;
+    if (tiles > 0x7fffffffu) return fail(SGZ_EINVAL, "PCM: too many samples for one launch");
+    // 15 bytes of lead at most, the tile, rounded up to whole chunks; one more chunk so that the word behind the last sample exists
+    const uint32_t lds = ((15u + tileSamples * frameBytes + 15u) & ~15u) + 16u;
+    uint32_t *out = reinterpret_cast<uint32_t *>(d_planar);
+    const uint8_t *in = static_cast<const uint8_t *>(d_pcm);
+    const dim3 grid{uint32_t(tiles)}, block{uint32_t(kPcmThreads)};
+#define SGZ_PCM_LAUNCH(F) hipLaunchKernelGGL(pcmToPlanarKernel<F>, grid, block, lds, stream, in, uint64_t(nsamples), srcChannels, tileSamples, map, numChannels, out, uint64_t(channelStride))
+    switch (format) {
+    case SGZ_PCM_F32: SGZ_PCM_LAUNCH(SGZ_PCM_F32); break;
+    case SGZ_PCM_U8: SGZ_PCM_LAUNCH(SGZ_PCM_U8); break;
+    case SGZ_PCM_S16: SGZ_PCM_LAUNCH(SGZ_PCM_S16); break;
+    case SGZ_PCM_S24: SGZ_PCM_LAUNCH(SGZ_PCM_S24); break;
+    case SGZ_PCM_S32: SGZ_PCM_LAUNCH(SGZ_PCM_S32); break;
+    default: SGZ_PCM_LAUNCH(SGZ_PCM_F64); break;
+    }
+#undef SGZ_PCM_LAUNCH
+    SGZ_HIP(hipGetLastError());
+    return SGZ_OK;
+}
+
+static sgz_status streamStep(uint32_t W, uint32_t hop, uint64_t held, uint64_t incoming, uint64_t *frames, uint64_t *keep)
+{
+    if (W == 0 || hop == 0 || hop > W || !frames || !keep) return fail(SGZ_EINVAL, "sgz_stream_step: window_size >= hop >= 1, results non-null");
+    const uint64_t total = held + incoming;
+    *frames = total >= W ? (total - W) / hop + 1 : 0;
+    *keep = total - *frames * hop;
+    return SGZ_OK;
+}
+
+}  // namespace sgz
+
+using namespace sgz;
+
+// ---- the stream handle -----------------------------------------------------------------------------------------------------------------
+namespace {
+// The default piece: 2^20 samples, less where a slot of that many frames would pass 256 MiB (64-channel F64: 2^19).  A kept stream fed cfg2's
+// 60 s of stereo S16 (tools/bench_pcm_render.py): 5.1 / 2.5 / 1.4 / 0.93 / 0.67 / 0.65 / 0.66 ms at 2^16 .. 2^22 -- a piece costs the host
+// and the streams ~0.1 ms whatever its size, which 2^20 samples (21 frames' worth of upload at cfg2, 128 frames to render) bury.
+constexpr size_t kPcmDefaultChunk = size_t(1) << 20;
+constexpr size_t kPcmDefaultSlotBytes = size_t(256) << 20;
+constexpr size_t kPcmMaxChunk = size_t(1) << 26;
+
+struct PcmSlot {                        // what one piece in flight owns; a slot is reused by the piece after next
+    void *h_pcm = nullptr;              // pinned [chunk][frameBytes], made when the first pageable feed arrives
+    void *d_pcm = nullptr;
+    uint8_t *d_rgba = nullptr, *h_rgba = nullptr;       // [maxFrames][P][4]; the pinned twin when rgba_out is pageable
+    float *d_lines = nullptr, *h_lines = nullptr;       // [maxFrames][C][graphs][P][2], made when lines are first asked for
+    hipEvent_t ev[7] = {};              // upload begin / END (copy stream); convert begin, convert end, render END (compute); read-back begin / END
+                                        // (the capitals order the streams; the others are recorded for a caller that asks for timing only: a
+                                        // marker costs the stream it sits on microseconds, api.hip sgz_render_queue_submit)
+    bool timed = false;
+    bool busy = false, rendered = false;
+    // the host's part of the read-back, done when the slot is drained
+    uint8_t *rgbaDst = nullptr; float *linesDst = nullptr; size_t rgbaBytes = 0, linesBytes = 0;
+};
+}  // namespace
+
+struct sgz_pcm_stream {
+    sgz_spectrum_config cfg{};
+    sgz_plan *plan = nullptr;
+    uint32_t format = 0, srcChannels = 0, frameBytes = 0, numChannels = 0;
+    PcmMap map{};
+    size_t chunk = 0, stride = 0, maxFrames = 0;
+    hipStream_t copy = nullptr, compute = nullptr, back = nullptr;
+    PcmSlot slot[2];
+    float *d_planar[2] = {nullptr, nullptr};            // [numChannels][stride] each: the held tail moves from one to the front of the other
+    float *d_state = nullptr;
+    int cur = 0;
+    uint64_t held = 0, pieces = 0;
+};
+
+static size_t pcmStateBytes(const sgz_pcm_stream &s) { return size_t(s.cfg.num_pairs) * SGZ_NUM_GRAPHS * s.cfg.axis_points * 2 * sizeof(float); }
+static size_t pcmLinesFloats(const sgz_pcm_stream &s, uint64_t frames) { return size_t(frames) * s.cfg.num_pairs * SGZ_NUM_GRAPHS * s.cfg.axis_points * 2; }
+
+// waits for the piece that used the slot, hands its columns to the caller (pageable destinations) and adds its event intervals up
+static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
+{
+    if (!sl.busy) return SGZ_OK;
+    sl.busy = false;
+    SGZ_HIP(hipEventSynchronize(sl.ev[sl.rendered ? 6 : 4]));
+    if (sl.rgbaDst) std::memcpy(sl.rgbaDst, sl.h_rgba, sl.rgbaBytes);
+    if (sl.linesDst) std::memcpy(sl.linesDst, sl.h_lines, sl.linesBytes);
+    sl.rgbaDst = nullptr; sl.linesDst = nullptr;
+    if (timing && sl.timed) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, sl.ev[0], sl.ev[1]) == hipSuccess) timing->h2d_ms += ms;
+        if (hipEventElapsedTime(&ms, sl.ev[2], sl.ev[3]) == hipSuccess) timing->convert_ms += ms;
+        if (hipEventElapsedTime(&ms, sl.ev[3], sl.ev[4]) == hipSuccess) timing->render_ms += ms;
+        if (sl.rendered && hipEventElapsedTime(&ms, sl.ev[5], sl.ev[6]) == hipSuccess) timing->d2h_ms += ms;
+    }
+    return SGZ_OK;
+}
+
+extern "C" {
+
+uint32_t sgz_pcm_sample_bytes(uint32_t format) { return pcmSampleBytes(format); }
+
+sgz_status sgz_stream_step(uint32_t window_size, uint32_t hop, uint64_t held, uint64_t incoming, uint64_t *frames, uint64_t *keep)
+{
+    return streamStep(window_size, hop, held, incoming, frames, keep);
+}
+
+sgz_status sgz_pcm_to_planar_device(const void *d_pcm, uint32_t format, uint32_t src_channels, size_t nsamples, const uint32_t *channel_map,
+                                    uint32_t num_channels, float *d_planar, size_t channel_stride, void *stream)
+{
+    PcmMap map;
+    if (sgz_status st = checkPcmLayout(format, src_channels, channel_map, num_channels, map); st != SGZ_OK) return st;
+    return launchPcmToPlanar(d_pcm, format, src_channels, nsamples, map, num_channels, d_planar, channel_stride, reinterpret_cast<hipStream_t>(stream));
+}
+
+void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
+{
+    if (!s) return;
+    for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamSynchronize(q);
+    for (PcmSlot &sl : s->slot) {
+        for (void *p : {sl.h_pcm, (void *)sl.h_rgba, (void *)sl.h_lines}) if (p) (void)hipHostFree(p);
+        for (void *p : {sl.d_pcm, (void *)sl.d_rgba, (void *)sl.d_lines}) if (p) (void)hipFree(p);
+        for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
+    }
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state}) if (p) (void)hipFree(p);
+    for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
+    if (s->plan) sgz_plan_destroy(s->plan);
+    delete s;
+}
+
+sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format, uint32_t src_channels, const uint32_t *channel_map,
+                                 size_t chunk_samples, sgz_pcm_stream **out)
+{
+    if (!cfg || !out) return fail(SGZ_EINVAL, "null argument");
+    sgz_pcm_stream *s = new (std::nothrow) sgz_pcm_stream();
+    if (!s) return fail(SGZ_ENOMEM, "out of memory");
+    auto bail = [&](sgz_status st) { const std::string keep = g_lastError; sgz_pcm_stream_destroy(s); g_lastError = keep; return st; };
+    if (sgz_status st = sgz_plan_create(cfg, &s->plan); st != SGZ_OK) return bail(st);
+    if (cfg->algorithm == SGZ_ALGO_RSNT)
+        return bail(fail(SGZ_EUNSUPPORTED, "sgz_pcm_stream: RSNT launches chain their frames within an fp32 bar, a chunked render would not equal the single one"));
+    if (cfg->hop > cfg->window_size) return bail(fail(SGZ_EUNSUPPORTED, "sgz_pcm_stream: hop > window_size"));
+    if (cfg->num_pairs > kPcmMaxChannels / 2) return bail(fail(SGZ_EINVAL, "sgz_pcm_stream: at most 32 pairs"));
+    s->cfg = *cfg; s->format = format; s->srcChannels = src_channels; s->numChannels = 2 * cfg->num_pairs;
+    if (sgz_status st = checkPcmLayout(format, src_channels, channel_map, s->numChannels, s->map); st != SGZ_OK) return bail(st);
+    if (chunk_samples > kPcmMaxChunk) return bail(fail(SGZ_EINVAL, "sgz_pcm_stream: chunk_samples above 2^26"));
+    s->frameBytes = src_channels * pcmSampleBytes(format);
+    s->chunk = chunk_samples ? chunk_samples : std::min(kPcmDefaultChunk, kPcmDefaultSlotBytes / s->frameBytes);
+    s->stride = (size_t(cfg->window_size) - 1 + s->chunk + 63) & ~size_t(63);       // the held tail (< W) and a piece behind it; 256-byte rows
+    s->maxFrames = (s->chunk - 1) / cfg->hop + 1;
+    if (sgz_status st = sgz_plan_upload(s->plan); st != SGZ_OK) return bail(st);
+#define SGZ_PCM_TRY(call) do { if (hipError_t e_ = (call); e_ != hipSuccess) return bail(hipFail(e_, #call)); } while (0)
+    for (hipStream_t *q : {&s->copy, &s->compute, &s->back}) SGZ_PCM_TRY(hipStreamCreateWithFlags(q, hipStreamNonBlocking));
+    for (PcmSlot &sl : s->slot) {
+        for (hipEvent_t &e : sl.ev) SGZ_PCM_TRY(hipEventCreate(&e));
+        SGZ_PCM_TRY(hipMalloc(&sl.d_pcm, s->chunk * s->frameBytes));
+        SGZ_PCM_TRY(hipMalloc(reinterpret_cast<void **>(&sl.d_rgba), s->maxFrames * cfg->axis_points * 4));
+    }
+    for (float *&p : s->d_planar) SGZ_PCM_TRY(hipMalloc(reinterpret_cast<void **>(&p), size_t(s->numChannels) * s->stride * sizeof(float)));
+    SGZ_PCM_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_state), pcmStateBytes(*s)));
+    SGZ_PCM_TRY(hipMemset(s->d_state, 0, pcmStateBytes(*s)));
+#undef SGZ_PCM_TRY
+    *out = s;
+    return SGZ_OK;
+}
+
+uint64_t sgz_pcm_stream_frames_for(const sgz_pcm_stream *s, size_t nsamples)
+{
+    uint64_t frames = 0, keep = 0;
+    if (!s || streamStep(s->cfg.window_size, s->cfg.hop, s->held, nsamples, &frames, &keep) != SGZ_OK) return 0;
+    return frames;
+}
+
+sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    SGZ_HIP(hipMemsetAsync(s->d_state, 0, pcmStateBytes(*s), s->compute));          // (in order behind whatever the last feed left there: nothing)
+    SGZ_HIP(hipStreamSynchronize(s->compute));
+    s->held = 0;
+    return SGZ_OK;
+}
+
+sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint8_t *rgba_out, float *lines_out,
+                               uint64_t capacity_frames, uint64_t *frames_out, sgz_pcm_timing *timing)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null pcm");
+    const uint64_t need = sgz_pcm_stream_frames_for(s, nsamples);
+    if (frames_out) *frames_out = need;
+    if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
+    if (need && !rgba_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null rgba_out");
+    if (timing) *timing = sgz_pcm_timing{};
+    const uint32_t W = s->cfg.window_size, hop = s->cfg.hop, P = s->cfg.axis_points;
+    const bool pcmPinned = nsamples && isPinnedHost(pcm);
+    const bool rgbaPinned = need && isPinnedHost(rgba_out), linesPinned = need && lines_out && isPinnedHost(lines_out);
+    // (the pinned slots and the lines buffers are made on first need: a caller with pinned memory of its own never pays for them)
+    for (PcmSlot &sl : s->slot) {
+        if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s->chunk * s->frameBytes, hipHostMallocDefault));
+        if (need && !rgbaPinned && !sl.h_rgba) SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_rgba), s->maxFrames * P * 4, hipHostMallocDefault));
+        if (need && lines_out && !sl.d_lines) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&sl.d_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float)));
+        if (need && lines_out && !linesPinned && !sl.h_lines)
+            SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float), hipHostMallocDefault));
+    }
+    const uint8_t *src = static_cast<const uint8_t *>(pcm);
+    uint64_t framesDone = 0, chunks = 0;
+    for (size_t at = 0; at < nsamples; ) {
+        const size_t n = std::min(s->chunk, nsamples - at);
+        PcmSlot &sl = s->slot[s->pieces & 1];
+        if (sgz_status st = pcmDrain(sl, timing); st != SGZ_OK) return st;          // the one wait inside a feed: the piece before last
+        uint64_t frames = 0, keep = 0;
+        if (sgz_status st = streamStep(W, hop, s->held, n, &frames, &keep); st != SGZ_OK) return st;
+        const size_t bytes = n * s->frameBytes;
+        const void *from = src + at * s->frameBytes;
+        if (!pcmPinned) { std::memcpy(sl.h_pcm, from, bytes); from = sl.h_pcm; }
+        // 1. upload
+        sl.timed = timing != nullptr;
+        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[0], s->copy));
+        SGZ_HIP(hipMemcpyAsync(sl.d_pcm, from, bytes, hipMemcpyHostToDevice, s->copy));
+        SGZ_HIP(hipEventRecord(sl.ev[1], s->copy));
+        // 2. convert behind the held tail, render what became complete, move the new tail to the front of the other planar buffer
+        float *planar = s->d_planar[s->cur];
+        SGZ_HIP(hipStreamWaitEvent(s->compute, sl.ev[1], 0));
+        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[2], s->compute));
+        if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s->format, s->srcChannels, n, s->map, s->numChannels, planar + s->held, s->stride, s->compute); st != SGZ_OK) return st;
+        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s->compute));
+        const uint64_t total = s->held + n;
+        sl.rendered = frames > 0;
+        if (frames) {
+            const sgz_status st = sgz_spectrogram_render_device(s->plan, planar, s->stride, size_t(total), sl.d_rgba, lines_out ? sl.d_lines : nullptr, s->d_state, s->compute);
+            if (st != SGZ_OK) return st;
+            if (keep) SGZ_HIP(hipMemcpy2DAsync(s->d_planar[s->cur ^ 1], s->stride * sizeof(float), planar + (total - keep), s->stride * sizeof(float),
+                                               size_t(keep) * sizeof(float), s->numChannels, hipMemcpyDeviceToDevice, s->compute));
+            s->cur ^= 1;
+        }                                                                          // (no frame: the tail just grew where it is)
+        s->held = keep;
+        SGZ_HIP(hipEventRecord(sl.ev[4], s->compute));
+        // 3. read back
+        if (frames) {
+            sl.rgbaBytes = size_t(frames) * P * 4; sl.linesBytes = pcmLinesFloats(*s, frames) * sizeof(float);
+            uint8_t *rgbaAt = rgba_out + size_t(framesDone) * P * 4;
+            float *linesAt = lines_out ? lines_out + pcmLinesFloats(*s, framesDone) : nullptr;
+            SGZ_HIP(hipStreamWaitEvent(s->back, sl.ev[4], 0));
+            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s->back));
+            SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_rgba, sl.d_rgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
+            if (lines_out) SGZ_HIP(hipMemcpyAsync(linesPinned ? linesAt : sl.h_lines, sl.d_lines, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
+            SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
+            sl.rgbaDst = rgbaPinned ? nullptr : rgbaAt;
+            sl.linesDst = (lines_out && !linesPinned) ? linesAt : nullptr;
+        }
+        sl.busy = true;
+        framesDone += frames; ++chunks; ++s->pieces; at += n;
+    }
+    // the end of the feed: both slots, the older piece first
+    for (uint64_t k = 0; k < 2; ++k)
+        if (sgz_status st = pcmDrain(s->slot[(s->pieces + k) & 1], timing); st != SGZ_OK) return st;
+    if (frames_out) *frames_out = framesDone;
+    if (timing) {
+        timing->frames = framesDone; timing->chunks = chunks;
+        timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrogram_render_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                      const uint32_t *channel_map, size_t nsamples, uint8_t *rgba_out, float *lines_out, sgz_pcm_timing *timing)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!cfg || !pcm || !rgba_out) return fail(SGZ_EINVAL, "null argument");
+    sgz_pcm_stream *s = nullptr;
+    // (no more device and pinned memory than the buffer needs)
+    const uint32_t frameBytes = std::max(1u, src_channels * sgz_pcm_sample_bytes(format));
+    const size_t chunk = std::min(std::min(kPcmDefaultChunk, kPcmDefaultSlotBytes / frameBytes), std::max<size_t>(nsamples, 1));
+    if (sgz_status st = sgz_pcm_stream_create(cfg, format, src_channels, channel_map, chunk, &s); st != SGZ_OK) return st;
+    uint64_t frames = sgz_pcm_stream_frames_for(s, nsamples);
+    sgz_status st = SGZ_SKIPPED_FRAME;
+    if (frames == 0) { if (timing) *timing = sgz_pcm_timing{}; }
+    else st = sgz_pcm_stream_feed(s, pcm, nsamples, rgba_out, lines_out, frames, &frames, timing);
+    const std::string keep = g_lastError;
+    sgz_pcm_stream_destroy(s);
+    g_lastError = keep;
+    if (timing && st == SGZ_OK) timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return st;
+}
+
+}  // extern "C"
