@@ -439,6 +439,35 @@ typedef struct sgz_line_peak {
     double peak_slope;           /* slopeMap[peak]                               */
 } sgz_line_peak;
 sgz_status sgz_track_peak_lines(const sgz_plan *plan, const float *results /*HOST float2 [P]*/, double mouse_fraction, sgz_line_peak *out);
+/* Both branches for a whole render: one peak per record, on the device.  One workgroup per record, asynchronous on `stream`; nothing is
+ * allocated, nothing is waited for.  The definitions are the single-frame calls above, byte for byte (NaN payloads included):
+ *  sgz_stage_track_peaks        d_bins: DEVICE float [records][N + 1], records = frames * pairs, as sgz_stage_bins writes them; d_out: DEVICE
+ *                               sgz_peak [records].  Record r == sgz_stage_track_peak(plan, d_bins + r * (N + 1), mouse_fraction, &out, stream)
+ *                               (SpectrumRendering.cpp:379-469 per record), with its refusals: Phase / Complex SGZ_EUNSUPPORTED, a non-finite
+ *                               mouse_fraction SGZ_EINVAL.  records == 0: SGZ_OK, nothing launched.
+ *  sgz_stage_track_peaks_lines  d_lines: DEVICE float2 [frames][pairs][graphs][P] as every render writes them; record (f, p) searches graph
+ *                               `graph`.  d_out: DEVICE sgz_line_peak [frames][pairs].  Record (f, p) == sgz_track_peak_lines(plan, <that
+ *                               record's P float2 on the host>, mouse_fraction, &out) (:300-377 per record): all six fields, the confinement
+ *                               for fewer than 17 axis points, the first largest, both boundary walks; a comparison with a NaN is false, so a
+ *                               NaN wins only where the host's loop starts on it and never stops a walk.  graph >= SGZ_NUM_GRAPHS or a
+ *                               non-finite mouse_fraction: SGZ_EINVAL.
+ * The boundary walks are cooperative (256 neighbour pairs per step): a silent or constant record, whose walk runs to the end of the axis,
+ * costs P / 256 steps, not P dependent loads. */
+sgz_status sgz_stage_track_peaks(sgz_plan *plan, const float *d_bins, size_t records, double mouse_fraction, sgz_peak *d_out, void *stream);
+sgz_status sgz_stage_track_peaks_lines(sgz_plan *plan, const float *d_lines, size_t frames, uint32_t graph, double mouse_fraction,
+                                       sgz_line_peak *d_out, void *stream);
+/* The offline render, with the line-results tracker applied to every frame on the device: d_track / track_out [frames][pairs] sgz_line_peak,
+ * equal to sgz_spectrogram_render_host(..., lines_out) followed by sgz_track_peak_lines per (frame, pair) on graph `graph`, byte for byte.
+ * d_rgba / rgba_out may be NULL (track only); an image asked for is that render's image.  Everything else as
+ * sgz_spectrogram_render_device / _host (SGZ_SKIPPED_FRAME and nothing written for fewer samples than a window; d_state carry-in / out).
+ * Every channel mode and RSNT (every render produces line results; in Phase the searched value is the magnitude half, as in the
+ * reference).  The line results stay on the device, in plan-owned scratch that is kept between calls and is PROPORTIONAL TO THE FRAME
+ * COUNT (frames * pairs * graphs * P * 8 bytes): the first call, and any call with more frames than every call before it, allocates it
+ * and therefore synchronises the device; calls that fit enqueue and return.  _host reads back the track (48 bytes per record) and the image if one was asked for. */
+sgz_status sgz_spectrogram_track_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t graph,
+                                        double mouse_fraction, uint8_t *d_rgba, float *d_state, sgz_line_peak *d_track, void *stream);
+sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t graph,
+                                      double mouse_fraction, uint8_t *rgba_out, sgz_line_peak *track_out, sgz_timing *timing);
 
 /* K_B in two steps, for the multi-GPU carry exchange (collective A2).  scan: the chunk scans of `frames` frames from a
  * ZERO carry-in; writes that zero-carry end state (what a rank publishes) to d_end_state [pairs][graphs][P][2] and keeps the chunk

@@ -190,6 +190,7 @@ EXPORTS = [
     "sgz_scope_dense_device",
     "sgz_pcm_sample_bytes", "sgz_pcm_to_planar_device", "sgz_stream_step", "sgz_pcm_stream_create", "sgz_pcm_stream_destroy",
     "sgz_pcm_stream_frames_for", "sgz_pcm_stream_feed", "sgz_pcm_stream_reset", "sgz_spectrogram_render_pcm",
+    "sgz_stage_track_peaks", "sgz_stage_track_peaks_lines", "sgz_spectrogram_track_device", "sgz_spectrogram_track_host",
 ]
 
 
@@ -268,6 +269,10 @@ def lib() -> C.CDLL:
     L.sgz_spectrum_track_peak.argtypes = [vp, u32, C.c_double, C.POINTER(Peak)]
     L.sgz_track_peak_lines.argtypes = [vp, vp, C.c_double, C.POINTER(LinePeak)]
     L.sgz_spectrum_track_peak_lines.argtypes = [vp, u32, u32, C.c_double, C.POINTER(LinePeak)]
+    L.sgz_stage_track_peaks.argtypes = [vp, vp, sz, C.c_double, vp, vp]
+    L.sgz_stage_track_peaks_lines.argtypes = [vp, vp, sz, u32, C.c_double, vp, vp]
+    L.sgz_spectrogram_track_device.argtypes = [vp, vp, sz, sz, u32, C.c_double, vp, vp, vp, vp]
+    L.sgz_spectrogram_track_host.argtypes = [vp, vp, u32, sz, u32, C.c_double, vp, vp, C.POINTER(Timing)]
     L.sgz_comm_unique_id.argtypes = [vp]
     L.sgz_comm_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.sgz_comm_destroy.argtypes = [vp]
@@ -690,6 +695,61 @@ class Plan:
         out = LinePeak()
         check(lib().sgz_track_peak_lines(self.h, _np_ptr(r), float(mouse_fraction), C.byref(out)))
         return out.asdict()
+
+    # the batched tracker: records come back as float64 rows in the field order of Peak (8) / LinePeak (6)
+    def track_peaks(self, bins, mouse_fraction: float, out=None, stream=None):
+        """sgz_stage_track_peaks: bins -- cuda float32 [..., N + 1] (sgz_stage_bins' records); returns cuda float64 [records, 8]"""
+        import torch
+        assert bins.is_cuda and bins.dtype == torch.float32 and bins.is_contiguous() and bins.shape[-1] == self.N + 1
+        records = bins.numel() // (self.N + 1)
+        if out is None:
+            out = torch.empty((records, len(Peak._fields_)), dtype=torch.float64, device=bins.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_track_peaks(self.h, bins.data_ptr(), records, float(mouse_fraction), out.data_ptr(), s))
+        return out
+
+    def track_peaks_lines(self, lines, graph: int, mouse_fraction: float, out=None, stream=None):
+        """sgz_stage_track_peaks_lines: lines -- cuda float32 [frames, pairs, graphs, P, 2]; returns cuda float64 [frames, pairs, 6]"""
+        import torch
+        assert lines.is_cuda and lines.dtype == torch.float32 and lines.is_contiguous()
+        assert tuple(lines.shape[1:]) == (self.C, NUM_GRAPHS, self.P, 2)
+        frames = lines.shape[0]
+        if out is None:
+            out = torch.empty((frames, self.C, len(LinePeak._fields_)), dtype=torch.float64, device=lines.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_track_peaks_lines(self.h, lines.data_ptr(), frames, graph, float(mouse_fraction), out.data_ptr(), s))
+        return out
+
+    def track_render(self, planar, graph: int, mouse_fraction: float, want_rgba: bool = True, state=None, stream=None):
+        """The render that returns a track.  planar a numpy array [2 C, S]: sgz_spectrogram_track_host -> (track float64 [F, C, 6], rgba uint8
+        [F, P, 4] or None, timing dict).  planar a cuda tensor: sgz_spectrogram_track_device, asynchronous -> (cuda track, cuda rgba or None).
+        Fewer samples than a window: None."""
+        if isinstance(planar, np.ndarray):
+            planar = np.ascontiguousarray(planar, np.float32)
+            nch, S = planar.shape
+            F = self.num_frames(S)
+            track = np.zeros((max(F, 1), self.C, len(LinePeak._fields_)), np.float64)            # (never a NULL pointer: F == 0 is the call's to refuse)
+            rgba = np.zeros((max(F, 1), self.P, 4), np.uint8) if want_rgba else None
+            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
+            t = Timing()
+            st = check(lib().sgz_spectrogram_track_host(self.h, ptrs, nch, S, graph, float(mouse_fraction), _np_ptr(rgba) if want_rgba else None,
+                                                        _np_ptr(track), C.byref(t)))
+            if st == SGZ_SKIPPED_FRAME:
+                return None
+            return track[:F], (rgba[:F] if want_rgba else None), {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+        import torch
+        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
+        S = planar.shape[1]
+        F = self.num_frames(S)
+        track = torch.empty((max(F, 1), self.C, len(LinePeak._fields_)), dtype=torch.float64, device=planar.device)      # (never a NULL
+        rgba = torch.empty((max(F, 1), self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None        # pointer)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = check(lib().sgz_spectrogram_track_device(self.h, planar.data_ptr(), planar.stride(0), S, graph, float(mouse_fraction),
+                                                      rgba.data_ptr() if want_rgba else None,
+                                                      state.data_ptr() if state is not None else None, track.data_ptr(), s))
+        if st == SGZ_SKIPPED_FRAME:
+            return None
+        return track[:F], (rgba[:F] if want_rgba else None)
 
     def colour_table(self, pair: int) -> np.ndarray:
         out = np.zeros((NUM_SPEC_COLOURS + 1, 3), np.float32)

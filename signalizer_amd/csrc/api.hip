@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -42,7 +43,7 @@ Plan::~Plan()
                     d_stateCopy, d_work0, d_work1, d_binsWork, d_halfBins, d_dcPixels, d_dcWork, d_phaseType, d_phaseNorm, d_phaseWork, d_shard, d_twReal1, d_twRealPost, d_tw2Full, d_windowHalf, d_winPhase, d_winPhaseT, d_ny, d_nyBest, d_chunkEnds, d_chunkReBase, d_chunkRec, d_weights12, d_resCoeff, d_resPow, d_resPowB, d_resPowBLo, d_resW1, d_resW2, d_resW1b, d_resTile, d_resGain, d_resState, d_resLocal};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines})
+    for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq})
         if (p) (void)hipFree(p);
     for (void *e : hostEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *e : shardEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
@@ -70,6 +71,7 @@ sgz_status uploadPlan(Plan &p, std::string &err)
     sgz_status st;
     if ((st = uploadVec(p.window, &p.d_window)) != SGZ_OK) return st;
     if ((st = uploadVec(p.slope, &p.d_slope)) != SGZ_OK) return st;
+    if ((st = uploadVec(p.mapped, &p.d_mappedFreq)) != SGZ_OK) return st;
     if ((st = uploadVec(p.colourTables, &p.d_colourTables)) != SGZ_OK) return st;
     if ((st = uploadVec(p.weights, &p.d_weights)) != SGZ_OK) return st;
     if ((st = uploadVec(p.weights11, &p.d_weights11)) != SGZ_OK) return st;
@@ -908,6 +910,37 @@ sgz_status sgz_render_queue_join(sgz_render_queue *q, void *stream)
     return SGZ_OK;
 }
 
+// What the host-buffer forms (sgz_spectrogram_render_host, sgz_spectrogram_track_host) share: the plan's own stream and timing events,
+// made on first use; the upload of the caller's channels into d_hostAudio (256-byte rows) between ev[0] and ev[1]; the stage times.
+static sgz_status hostStreamAndEvents(Plan &p, hipStream_t &s, hipEvent_t ev[4])
+{
+    if (!p.hostStream) {
+        hipStream_t ns = nullptr;
+        SGZ_HIP(hipStreamCreateWithFlags(&ns, hipStreamNonBlocking));
+        p.hostStream = ns;
+        for (void *&e : p.hostEv) { hipEvent_t ne = nullptr; SGZ_HIP(hipEventCreate(&ne)); e = ne; }
+    }
+    s = static_cast<hipStream_t>(p.hostStream);
+    for (int i = 0; i < 4; ++i) ev[i] = static_cast<hipEvent_t>(p.hostEv[i]);
+    return SGZ_OK;
+}
+static sgz_status uploadHostAudio(Plan &p, const float *const *planar, uint32_t num_channels, size_t nsamples, size_t stride, hipStream_t s,
+                                  hipEvent_t ev[4])
+{
+    SGZ_HIP(hipEventRecord(ev[0], s));
+    for (uint32_t c = 0; c < num_channels; ++c)
+        SGZ_HIP(hipMemcpyAsync(p.d_hostAudio + size_t(c) * stride, planar[c], nsamples * sizeof(float), hipMemcpyHostToDevice, s));
+    SGZ_HIP(hipEventRecord(ev[1], s));
+    return SGZ_OK;
+}
+static void fillHostTiming(sgz_timing &timing, hipEvent_t ev[4], long frames)
+{
+    float a = 0, b = 0, c = 0;
+    (void)hipEventElapsedTime(&a, ev[0], ev[1]); (void)hipEventElapsedTime(&b, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&c, ev[2], ev[3]);
+    timing.h2d_ms = a; timing.kernel_ms = b; timing.d2h_ms = c; timing.frames = uint64_t(frames);
+}
+
 // Host buffers in, host buffers out, on a plan the caller keeps: the constant block is built and uploaded once, the device buffers and
 // the stream live in the plan and only grow, so a second render of the same shape allocates nothing.
 sgz_status sgz_spectrogram_render_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples,
@@ -920,24 +953,15 @@ sgz_status sgz_spectrogram_render_host(sgz_plan *plan, const float *const *plana
     if (num_channels != 2 * p.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
     const long frames = planFrames(p, nsamples);
     if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
-    if (!p.hostStream) {
-        hipStream_t ns = nullptr;
-        SGZ_HIP(hipStreamCreateWithFlags(&ns, hipStreamNonBlocking));
-        p.hostStream = ns;
-        for (void *&e : p.hostEv) { hipEvent_t ne = nullptr; SGZ_HIP(hipEventCreate(&ne)); e = ne; }
-    }
-    hipStream_t s = static_cast<hipStream_t>(p.hostStream);
+    hipStream_t s = nullptr;
     hipEvent_t ev[4];
-    for (int i = 0; i < 4; ++i) ev[i] = static_cast<hipEvent_t>(p.hostEv[i]);
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
     const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
     const size_t linesN = size_t(frames) * p.C * SGZ_NUM_GRAPHS * p.P * 2;
     if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
     if ((st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, (size_t(frames) * p.P * 4 + 3) / 4)) != SGZ_OK) return st;
     if (lines_out && (st = ensureCap(&p.d_hostLines, &p.hostLinesCap, linesN)) != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[0], s));
-    for (uint32_t c = 0; c < num_channels; ++c)
-        SGZ_HIP(hipMemcpyAsync(p.d_hostAudio + size_t(c) * stride, planar[c], nsamples * sizeof(float), hipMemcpyHostToDevice, s));
-    SGZ_HIP(hipEventRecord(ev[1], s));
+    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
     uint8_t *d_rgba = reinterpret_cast<uint8_t *>(p.d_hostRgba);
     st = sgz_spectrogram_render_device(plan, p.d_hostAudio, stride, nsamples, d_rgba, lines_out ? p.d_hostLines : nullptr, nullptr, s);
     if (st != SGZ_OK) return st;
@@ -946,12 +970,62 @@ sgz_status sgz_spectrogram_render_host(sgz_plan *plan, const float *const *plana
     if (lines_out) SGZ_HIP(hipMemcpyAsync(lines_out, p.d_hostLines, linesN * sizeof(float), hipMemcpyDeviceToHost, s));
     SGZ_HIP(hipEventRecord(ev[3], s));
     SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) {
-        float a = 0, b = 0, c = 0;
-        (void)hipEventElapsedTime(&a, ev[0], ev[1]); (void)hipEventElapsedTime(&b, ev[1], ev[2]);
-        (void)hipEventElapsedTime(&c, ev[2], ev[3]);
-        timing->h2d_ms = a; timing->kernel_ms = b; timing->d2h_ms = c; timing->frames = uint64_t(frames);
-    }
+    if (timing) fillHostTiming(*timing, ev, frames);
+    return SGZ_OK;
+}
+
+// The offline render with the line-results tracker applied to every frame on the device (sgz.h): the render's chain as it is -- K_A's path
+// selection and K_B are sgz_spectrogram_render_device's, with line results asked for (every K_B form takes a null image) -- into plan
+// scratch, then trackLinePeaksKernel behind it on the same stream.  The line results never leave the device.
+sgz_status sgz_spectrogram_track_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t graph,
+                                        double mouse_fraction, uint8_t *d_rgba, float *d_state, sgz_line_peak *d_track, void *stream)
+{
+    if (!plan || !d_planar || !d_track) return fail(SGZ_EINVAL, "null argument");
+    if (graph >= SGZ_NUM_GRAPHS) return fail(SGZ_EINVAL, "graph");
+    if (!std::isfinite(mouse_fraction)) return fail(SGZ_EINVAL, "mouse_fraction");
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    if ((st = ensureCap(&p.d_trackLines, &p.trackLinesCap, size_t(frames) * p.C * SGZ_NUM_GRAPHS * p.P * 2)) != SGZ_OK) return st;
+    if ((st = sgz_spectrogram_render_device(plan, d_planar, channel_stride, nsamples, d_rgba, p.d_trackLines, d_state, stream)) != SGZ_OK) return st;
+    return runTrackPeaksLines(p, p.d_trackLines, size_t(frames), graph, mouse_fraction, d_track, reinterpret_cast<hipStream_t>(stream));
+}
+
+sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t graph,
+                                      double mouse_fraction, uint8_t *rgba_out, sgz_line_peak *track_out, sgz_timing *timing)
+{
+    if (!plan || !planar || !track_out) return fail(SGZ_EINVAL, "null argument");
+    if (graph >= SGZ_NUM_GRAPHS) return fail(SGZ_EINVAL, "graph");
+    if (!std::isfinite(mouse_fraction)) return fail(SGZ_EINVAL, "mouse_fraction");
+    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
+    for (uint32_t c = 0; c < num_channels; ++c)
+        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
+    const size_t records = size_t(frames) * p.C;
+    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
+    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, (size_t(frames) * p.P * 4 + 3) / 4)) != SGZ_OK) return st;
+    if ((st = ensureCap(&p.d_hostTrack, &p.hostTrackCap, records * (sizeof(sgz_line_peak) / sizeof(float)))) != SGZ_OK) return st;
+    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
+    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
+    sgz_line_peak *d_track = reinterpret_cast<sgz_line_peak *>(p.d_hostTrack);
+    st = sgz_spectrogram_track_device(plan, p.d_hostAudio, stride, nsamples, graph, mouse_fraction, d_rgba, nullptr, d_track, s);
+    if (st != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(frames) * p.P * 4, hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipMemcpyAsync(track_out, d_track, records * sizeof(sgz_line_peak), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, frames);
     return SGZ_OK;
 }
 

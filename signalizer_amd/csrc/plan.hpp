@@ -133,6 +133,7 @@ struct Plan {
 
     // device mirrors (owned)
     bool uploaded = false;
+    float *d_mappedFreq = nullptr;                        // `mapped` (mappedFrequencies), for the batched line tracker (tracker.hip)
     float *d_window = nullptr, *d_slope = nullptr, *d_colourTables = nullptr, *d_weights = nullptr, *d_weights11 = nullptr;
     float *d_tw1 = nullptr, *d_tw2 = nullptr, *d_twN = nullptr, *d_tw1odd = nullptr;
     float *d_work0 = nullptr, *d_work1 = nullptr, *d_binsWork = nullptr; size_t workSlab = 0;
@@ -152,6 +153,9 @@ struct Plan {
     // sgz_spectrogram_render_host: device copies of the caller's host buffers, the stream they move on, timing events
     float *d_hostAudio = nullptr, *d_hostRgba = nullptr, *d_hostLines = nullptr;
     size_t hostAudioCap = 0, hostRgbaCap = 0, hostLinesCap = 0;
+    // sgz_spectrogram_track_device / _host: the render's line results [frames][pairs][graphs][P] float2 (they stay on the device) and the
+    // host form's device copy of the track
+    float *d_trackLines = nullptr, *d_hostTrack = nullptr; size_t trackLinesCap = 0, hostTrackCap = 0;
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;

@@ -83,5 +83,9 @@ sgz_status runDecayEmitWithCarry(Plan &p, const float *d_mapped, long frames, co
                                  float *d_stateOut, hipStream_t stream);
 // frequency tracker (tracker.hip): peak search + parabolic fit on one (frame, pair)'s csf magnitudes; d_out: DEVICE sgz_peak
 sgz_status runTrackPeak(const Plan &p, const float *d_bins, double mouseFraction, sgz_peak *d_out, hipStream_t stream);
+// the batched forms: one workgroup per record, asynchronous on `stream`, nothing allocated; d_out: DEVICE [records] / [frames][pairs]
+sgz_status runTrackPeaks(const Plan &p, const float *d_bins, size_t records, double mouseFraction, sgz_peak *d_out, hipStream_t stream);
+sgz_status runTrackPeaksLines(const Plan &p, const float *d_lines, size_t frames, uint32_t graph, double mouseFraction, sgz_line_peak *d_out,
+                              hipStream_t stream);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 }  // namespace sgz
