@@ -36,6 +36,9 @@ extern "C" {
  * (5, later: interleaved PCM in -- SGZ_PCM_*, sgz_pcm_sample_bytes, sgz_pcm_to_planar_device, the sgz_pcm_stream handle, sgz_stream_step and
  *  sgz_spectrogram_render_pcm.  No existing entry point or struct changed and the suite pins 5; a binding that needs them looks the
  *  symbols up.)
+ * (5, later: the overview render -- sgz_overview_step, sgz_stage_overview, sgz_spectrogram_overview_device / _host and plan option
+ *  SGZ_OPT_OVERVIEW_SLAB.  No existing entry point or struct changed and the suite pins 5; a binding that needs them looks the symbols
+ *  up, and one that sets the option on an older library gets SGZ_EINVAL, "unknown plan option".)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -223,6 +226,9 @@ sgz_status sgz_plan_reset_resonator(sgz_plan *plan, void *stream);
                                       2 <= n <= 4096: as 1, with n frames per Nyquist workgroup instead of the automatic size (a render of fewer
                                       frames uses its frame count); larger values are refused with SGZ_EINVAL.  Other renders, the stage calls
                                       and the real-time handles are not affected. */
+#define SGZ_OPT_OVERVIEW_SLAB 10u     /* sgz_spectrogram_overview_device / _host, FFT plans: frames per slab of the render (0, the default: as many as
+                                      fit 64 MiB of line results, frames * pairs * graphs * P * 8 bytes).  Any value gives the same bytes; the
+                                      plan's scratch is bounded by the slab, not by the buffer.  RSNT plans render one slab whatever it says. */
 sgz_status sgz_plan_set_option(sgz_plan *plan, uint32_t option, uint32_t value);
 /* The pixels whose filter taps or arg-max run reach a csf entry the reference leaves complex -- Complex: csf[0] = Z[0]/2
  * (TransformDSP.inl:993); Left / Right / Merge / Side: csf[N/2 .. N-1] (:553-560), reached by windows that wrap below bin 0 or
@@ -468,6 +474,50 @@ sgz_status sgz_spectrogram_track_device(sgz_plan *plan, const float *d_planar, s
                                         double mouse_fraction, uint8_t *d_rgba, float *d_state, sgz_line_peak *d_track, void *stream);
 sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t graph,
                                       double mouse_fraction, uint8_t *rgba_out, sgz_line_peak *track_out, sgz_timing *timing);
+
+/* The overview render: an image with k frames per column, reduced and coloured on the device -- what a host draws as a file's
+ * spectrogram in a lane, a thumbnail or a zoomed-out view, without reading back one column per frame.  The reference has no counterpart
+ * (renderColourSpectrum draws one column per audio frame, Source/Spectrum/SpectrumRendering.cpp:696-721); the colouring is its own.
+ * Definition (exact, no tolerance): with L[f][p][g][i] the float2 line results every render writes and F frames,
+ *   columns = ceil(F / k); column c covers frames c k <= f < min((c + 1) k, F) (the last one may be partial);
+ *   V[c][p][i] = the greatest of L[f][p][0][i].x over the column's frames -- a peak hold of graph 0 (LineMain), first component, the value
+ *     the image is coloured from in every channel mode, Phase included.  "Greatest" is a total order, so that any split of the work
+ *     gives the same bits: NaNs take no part; the others compare by bits ^ (sign ? 0xFFFFFFFF : 0x80000000) as unsigned (IEEE order
+ *     with -0 below +0); a group of NaNs alone yields the quiet NaN 0x7FC00000;
+ *   pixel (c, i) = the additive blend of the pairs' colours at V[c][p][i], p = 0 .. pairs - 1 in order, from a black column buffer,
+ *     then the 8-bit conversion (SpectrumDSP.cpp:119-198, as K_B does it for a frame).
+ * For k == 1 the image is sgz_spectrogram_render_device's byte for byte and V is the line results' first components bit for bit.
+ *  sgz_overview_step   host arithmetic, the twin of sgz_stream_step: `held` frames of an open column plus `frames` new ones, t = held +
+ *                      frames: *columns = t / k, plus one if flush and t % k != 0; *held_out = flush ? 0 : t % k.  SGZ_EINVAL: k == 0,
+ *                      held >= k, a null result.
+ *  sgz_stage_overview  the reduction on given line results d_lines [frames][pairs][graphs][P] float2.  d_carry: DEVICE float [pairs][P], the
+ *                      open column's V so far -- read iff held > 0, written iff frames stay open afterwards (no flush, t % k != 0), NULL
+ *                      allowed when neither applies; a carried column continues exactly as if its frames had come in one call.  d_rgba
+ *                      [columns][P][4] and d_peaks float [columns][pairs][P] = V, columns as sgz_overview_step counts them; either may be
+ *                      NULL, not both.  slices: 0 = the library's choice, 1 .. 64 forced (few columns of many frames are reduced in that
+ *                      many slices per column into plan scratch, then folded) -- identical results.  Only the documented bytes are
+ *                      written.  SGZ_EINVAL, nothing launched or written: a null plan or d_lines, k == 0, held >= k, slices > 64, both
+ *                      outputs NULL, a needed d_carry that is NULL.  frames == 0 without a column to flush: SGZ_OK, nothing launched.
+ *                      Asynchronous on `stream`, nothing is waited for; plan scratch grows on demand (only growth synchronises).
+ *  sgz_spectrogram_overview_device / _host   the render: columns = ceil(F / k), the last column flushed; d_rgba / rgba_out [columns][P][4],
+ *                      d_peaks / peaks_out float [columns][pairs][P], either may be NULL, not both.  Everything else as
+ *                      sgz_spectrogram_render_device / _host: SGZ_SKIPPED_FRAME and nothing written for fewer samples than a window,
+ *                      d_state carry-in / out, the host form on the plan's own stream with kept device copies -- it reads back the
+ *                      columns and nothing else.  FFT plans render in slabs of frames (SGZ_OPT_OVERVIEW_SLAB; by default 64 MiB of
+ *                      line results) with the decay state carried from slab to slab (in a plan-owned buffer when d_state is NULL) and
+ *                      the open column carried across the cut: neither the read-back nor the plan's scratch grows with the frame
+ *                      count, and the bytes do not depend on the slab.  RSNT plans render ONE slab (their launches chain the frames
+ *                      within an fp32 bar, a cut would move the bits -- why sgz_pcm_stream refuses them): their line-result scratch is
+ *                      PROPORTIONAL TO THE FRAME COUNT (frames * pairs * graphs * P * 8 bytes), as the tracker's.  The first call,
+ *                      and any call that needs more scratch than every call before it, allocates and therefore synchronises the
+ *                      device; calls that fit enqueue and return. */
+sgz_status sgz_overview_step(uint32_t k, uint64_t held, uint64_t frames, int flush, uint64_t *columns, uint64_t *held_out);
+sgz_status sgz_stage_overview(sgz_plan *plan, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                              float *d_carry, uint8_t *d_rgba, float *d_peaks, void *stream);
+sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                           uint8_t *d_rgba, float *d_peaks, float *d_state, void *stream);
+sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                         uint8_t *rgba_out, float *peaks_out, sgz_timing *timing);
 
 /* K_B in two steps, for the multi-GPU carry exchange (collective A2).  scan: the chunk scans of `frames` frames from a
  * ZERO carry-in; writes that zero-carry end state (what a rank publishes) to d_end_state [pairs][graphs][P][2] and keeps the chunk

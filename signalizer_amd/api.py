@@ -191,6 +191,7 @@ EXPORTS = [
     "sgz_pcm_sample_bytes", "sgz_pcm_to_planar_device", "sgz_stream_step", "sgz_pcm_stream_create", "sgz_pcm_stream_destroy",
     "sgz_pcm_stream_frames_for", "sgz_pcm_stream_feed", "sgz_pcm_stream_reset", "sgz_spectrogram_render_pcm",
     "sgz_stage_track_peaks", "sgz_stage_track_peaks_lines", "sgz_spectrogram_track_device", "sgz_spectrogram_track_host",
+    "sgz_overview_step", "sgz_stage_overview", "sgz_spectrogram_overview_device", "sgz_spectrogram_overview_host",
 ]
 
 
@@ -273,6 +274,10 @@ def lib() -> C.CDLL:
     L.sgz_stage_track_peaks_lines.argtypes = [vp, vp, sz, u32, C.c_double, vp, vp]
     L.sgz_spectrogram_track_device.argtypes = [vp, vp, sz, sz, u32, C.c_double, vp, vp, vp, vp]
     L.sgz_spectrogram_track_host.argtypes = [vp, vp, u32, sz, u32, C.c_double, vp, vp, C.POINTER(Timing)]
+    L.sgz_overview_step.argtypes = [u32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.sgz_stage_overview.argtypes = [vp, vp, sz, u32, u32, C.c_int, u32, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_host.argtypes = [vp, vp, u32, sz, u32, vp, vp, C.POINTER(Timing)]
     L.sgz_comm_unique_id.argtypes = [vp]
     L.sgz_comm_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.sgz_comm_destroy.argtypes = [vp]
@@ -602,6 +607,14 @@ OPT_CHANNEL_SPLIT, OPT_FUSED_COLOUR, OPT_FETCH_WINDOW, OPT_MATRIX_RESONATOR, OPT
 OPT_RESONATOR_SHARD_BOUND = 7
 OPT_PIPELINED = 8
 OPT_IMAGE_ONLY_SPLIT = 9
+OPT_OVERVIEW_SLAB = 10
+
+
+def overview_step(k: int, held: int, frames: int, flush: bool):
+    """sgz_overview_step (host arithmetic, no GPU): (columns that become complete, frames of the column left open)"""
+    c, h = C.c_uint64(0), C.c_uint64(0)
+    check(lib().sgz_overview_step(k, held, frames, int(bool(flush)), C.byref(c), C.byref(h)))
+    return c.value, h.value
 
 
 class Plan:
@@ -750,6 +763,58 @@ class Plan:
         if st == SGZ_SKIPPED_FRAME:
             return None
         return track[:F], (rgba[:F] if want_rgba else None)
+
+    # the overview: k frames per image column, reduced (a peak hold of the main graph) and coloured on the device
+    def overview_columns(self, lines, k: int, held: int = 0, flush: bool = True, slices: int = 0, carry=None, want_rgba: bool = True,
+                         want_peaks: bool = False, stream=None):
+        """sgz_stage_overview: lines -- cuda float32 [frames, pairs, graphs, P, 2]; carry -- cuda float32 [pairs, P], the open column (read
+        when held > 0, written when frames stay open).  Returns (cuda rgba uint8 [columns, P, 4] or None, cuda peaks float32 [columns,
+        pairs, P] or None, frames of the column left open)."""
+        import torch
+        assert lines.is_cuda and lines.dtype == torch.float32 and lines.is_contiguous()
+        assert tuple(lines.shape[1:]) == (self.C, NUM_GRAPHS, self.P, 2)
+        assert carry is None or (carry.is_cuda and carry.dtype == torch.float32 and carry.is_contiguous() and carry.numel() == self.C * self.P)
+        frames = lines.shape[0]
+        columns, held_out = overview_step(k, held, frames, flush)
+        rgba = torch.empty((max(columns, 1), self.P, 4), dtype=torch.uint8, device=lines.device) if want_rgba else None      # (never a NULL
+        peaks = torch.empty((max(columns, 1), self.C, self.P), dtype=torch.float32, device=lines.device) if want_peaks else None   # pointer)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview(self.h, lines.data_ptr(), frames, k, held, int(bool(flush)), slices,
+                                       carry.data_ptr() if carry is not None else None, rgba.data_ptr() if want_rgba else None,
+                                       peaks.data_ptr() if want_peaks else None, s))
+        return (rgba[:columns] if want_rgba else None), (peaks[:columns] if want_peaks else None), held_out
+
+    def overview(self, planar, k: int, want_rgba: bool = True, want_peaks: bool = False, state=None, stream=None):
+        """The overview render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_host -> (rgba uint8 [columns, P, 4] or None, peaks
+        float32 [columns, C, P] or None, timing dict).  planar a cuda tensor: sgz_spectrogram_overview_device, asynchronous -> (cuda rgba
+        or None, cuda peaks or None).  columns = ceil(frames / k).  Fewer samples than a window: None."""
+        if isinstance(planar, np.ndarray):
+            planar = np.ascontiguousarray(planar, np.float32)
+            nch, S = planar.shape
+            columns = -(-self.num_frames(S) // k)
+            rgba = np.zeros((max(columns, 1), self.P, 4), np.uint8) if want_rgba else None
+            peaks = np.zeros((max(columns, 1), self.C, self.P), np.float32) if want_peaks else None
+            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
+            t = Timing()
+            st = check(lib().sgz_spectrogram_overview_host(self.h, ptrs, nch, S, k, _np_ptr(rgba) if want_rgba else None,
+                                                           _np_ptr(peaks) if want_peaks else None, C.byref(t)))
+            if st == SGZ_SKIPPED_FRAME:
+                return None
+            return ((rgba[:columns] if want_rgba else None), (peaks[:columns] if want_peaks else None),
+                    {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames})
+        import torch
+        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
+        S = planar.shape[1]
+        columns = -(-self.num_frames(S) // k)
+        rgba = torch.empty((max(columns, 1), self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None
+        peaks = torch.empty((max(columns, 1), self.C, self.P), dtype=torch.float32, device=planar.device) if want_peaks else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = check(lib().sgz_spectrogram_overview_device(self.h, planar.data_ptr(), planar.stride(0), S, k,
+                                                         rgba.data_ptr() if want_rgba else None, peaks.data_ptr() if want_peaks else None,
+                                                         state.data_ptr() if state is not None else None, s))
+        if st == SGZ_SKIPPED_FRAME:
+            return None
+        return (rgba[:columns] if want_rgba else None), (peaks[:columns] if want_peaks else None)
 
     def colour_table(self, pair: int) -> np.ndarray:
         out = np.zeros((NUM_SPEC_COLOURS + 1, 3), np.float32)

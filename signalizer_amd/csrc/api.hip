@@ -43,7 +43,8 @@ Plan::~Plan()
                     d_stateCopy, d_work0, d_work1, d_binsWork, d_halfBins, d_dcPixels, d_dcWork, d_phaseType, d_phaseNorm, d_phaseWork, d_shard, d_twReal1, d_twRealPost, d_tw2Full, d_windowHalf, d_winPhase, d_winPhaseT, d_ny, d_nyBest, d_chunkEnds, d_chunkReBase, d_chunkRec, d_weights12, d_resCoeff, d_resPow, d_resPowB, d_resPowBLo, d_resW1, d_resW2, d_resW1b, d_resTile, d_resGain, d_resState, d_resLocal};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq})
+    for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq, (void *)d_ovLines, (void *)d_ovCarry,
+                    (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks})
         if (p) (void)hipFree(p);
     for (void *e : hostEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *e : shardEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
@@ -641,6 +642,7 @@ sgz_status sgz_plan_set_option(sgz_plan *plan, uint32_t option, uint32_t value)
     case SGZ_OPT_IMAGE_ONLY_SPLIT:
         if (value > kMaxNyFrames) return fail(SGZ_EINVAL, "SGZ_OPT_IMAGE_ONLY_SPLIT: 0, 1 or 2 .. 4096 frames per Nyquist workgroup");
         p.optImageOnlySplit = value; return SGZ_OK;
+    case SGZ_OPT_OVERVIEW_SLAB: p.optOverviewSlab = value; return SGZ_OK;
     case SGZ_OPT_WIDE_GROUPS: return SGZ_OK;                   // retired (sgz.h): accepted, changes nothing
     default: return fail(SGZ_EINVAL, "unknown plan option");
     }
@@ -1023,6 +1025,84 @@ sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar
     SGZ_HIP(hipEventRecord(ev[2], s));
     if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(frames) * p.P * 4, hipMemcpyDeviceToHost, s));
     SGZ_HIP(hipMemcpyAsync(track_out, d_track, records * sizeof(sgz_line_peak), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, frames);
+    return SGZ_OK;
+}
+
+// The overview render (sgz.h; overview.hip): the render's chain as it is, a slab of frames at a time with line results into plan scratch
+// and the decay state carried from slab to slab, and the reduction behind every slab with the open column carried across the cut.  Carried
+// state makes the pieces equal the single render byte for byte (what sgz_pcm_stream relies on), so the columns do not depend on the slab.
+// RSNT renders as one slab: its launches chain their frames within an fp32 bar, a cut would move the bits.
+constexpr size_t kOverviewSlabBytes = size_t(64) << 20;
+sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                           uint8_t *d_rgba, float *d_peaks, float *d_state, void *stream)
+{
+    if (!plan || !d_planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!d_rgba && !d_peaks) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t perFrame = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;                                   // floats of line results
+    long slab = frames;
+    if (!isResonator(p)) slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kOverviewSlabBytes / (perFrame * sizeof(float)))));
+    if ((st = ensureCap(&p.d_ovLines, &p.ovLinesCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
+    if ((st = ensureCap(&p.d_ovCarry, &p.ovCarryCap, size_t(p.C) * p.P)) != SGZ_OK) return st;
+    float *state = d_state;
+    if (!state && slab < frames) {                               // the slabs continue a state of the plan's own, from rest
+        const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
+        if ((st = ensureCap(&p.d_ovState, &p.ovStateCap, stateN)) != SGZ_OK) return st;
+        SGZ_HIP(hipMemsetAsync(p.d_ovState, 0, stateN * sizeof(float), s));
+        state = p.d_ovState;
+    }
+    for (long f0 = 0; f0 < frames; f0 += slab) {
+        const long nf = std::min(slab, frames - f0);
+        const size_t ns = isResonator(p) ? nsamples : size_t(p.W) + size_t(nf - 1) * p.cfg.hop;
+        st = sgz_spectrogram_render_device(plan, d_planar + size_t(f0) * p.cfg.hop, channel_stride, ns, nullptr, p.d_ovLines, state, s);
+        if (st != SGZ_OK) return st;
+        const size_t column = size_t(f0) / k;                   // the column frame f0 belongs to: the carried one when f0 % k != 0
+        st = runOverviewColumns(p, p.d_ovLines, size_t(nf), k, uint32_t(size_t(f0) % k), f0 + nf == frames, 0, p.d_ovCarry,
+                                d_rgba ? d_rgba + column * p.P * 4 : nullptr, d_peaks ? d_peaks + column * p.C * p.P : nullptr, s);
+        if (st != SGZ_OK) return st;
+    }
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                         uint8_t *rgba_out, float *peaks_out, sgz_timing *timing)
+{
+    if (!plan || !planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
+    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
+    for (uint32_t c = 0; c < num_channels; ++c)
+        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
+    const size_t columns = (size_t(frames) + k - 1) / k;
+    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
+    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, columns * p.P)) != SGZ_OK) return st;
+    if (peaks_out && (st = ensureCap(&p.d_hostOvPeaks, &p.hostOvPeaksCap, columns * p.C * p.P)) != SGZ_OK) return st;
+    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
+    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
+    float *d_peaks = peaks_out ? p.d_hostOvPeaks : nullptr;
+    st = sgz_spectrogram_overview_device(plan, p.d_hostAudio, stride, nsamples, k, d_rgba, d_peaks, nullptr, s);
+    if (st != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, columns * p.P * 4, hipMemcpyDeviceToHost, s));
+    if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaks_out, d_peaks, columns * p.C * p.P * sizeof(float), hipMemcpyDeviceToHost, s));
     SGZ_HIP(hipEventRecord(ev[3], s));
     SGZ_HIP(hipStreamSynchronize(s));
     if (timing) fillHostTiming(*timing, ev, frames);

@@ -1,0 +1,245 @@
+// overview.hip -- the overview image: k frames of line results per image column, reduced and coloured on the device (sgz.h, "The overview
+// render").  gfx950 only.  The reference has no counterpart: renderColourSpectrum draws one column per audio frame
+// (Source/Spectrum/SpectrumRendering.cpp:696-721); the colouring is its own (decay_body.hpp blendColour / toRgba8, called, not copied).
+//   V[c][p][i] = the greatest of L[f][p][0][i].x over the column's frames (graph 0, first component: the value K_B colours from), under a
+//   total order -- NaNs take no part, the others compare by the key bits ^ (sign ? 0xFFFFFFFF : 0x80000000) as unsigned, i.e. IEEE order
+//   with -0 below +0 -- so that any split of the frames (slices, calls, slabs) gives the same bits.  A group of NaNs alone yields 0x7FC00000.
+// The kernels keep KEYS: key 0 is "no value yet" (it is the key of a NaN pattern and of nothing else: -inf's key is 0x007FFFFF), a maximum
+// of keys is associative and commutative, and a key turns back into the value's own bits.
+//   overviewColumnsKernel   one thread per (column, pixel): pairs outermost (the blend order), the column's frames inside, 8 loads in
+//                           flight before the compares; then the carry, the colour, one uchar4 store.
+//   overviewSliceKernel     few columns of many frames: slice s of a column's frames -> partial keys [slices][columns][pairs][P] in plan
+//   overviewEmitKernel      scratch; then the fold over the slices and the carry, the colour, the store -- a launch of its own behind it on
+//                           the stream (no hand-off between workgroups inside a launch).
+// Nothing is waited for; scratch grows on demand (only growth synchronises); everything runs on the caller's stream.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "runtime.hpp"
+#include "decay_body.hpp"
+
+#pragma clang fp contract(off)
+
+using namespace sgz;
+
+namespace {
+
+constexpr int kOvThreads = 256;
+constexpr int kOvUnroll = 8;             // frames (or slices) whose loads are issued before the first compare
+constexpr uint32_t kOvMaxSlices = 64;
+
+struct OverviewParams {
+    const float2 *lines;                 // [frames][C][G][P]
+    long frames;
+    long columns, closed;                // columns this call touches; the first `closed` of them are emitted, a last open one goes to carryOut
+    uint32_t k, held, C, P;
+    uint32_t blocks;                     // workgroups per column = ceil(P / 256)
+    uint32_t slices;
+    const float *carryIn;                // [C][P]: V of column 0's `held` earlier frames (read iff held > 0)
+    float *carryOut;                     // [C][P]: V of the open column
+    uchar4 *rgba;                        // [closed][P] or null
+    float *peaks;                        // [closed][C][P] or null
+    uint32_t *partial;                   // [slices][columns][C][P] keys
+    const float *colourTables;
+    DeviceScalars sc;
+};
+
+__device__ __forceinline__ uint32_t orderKey(uint32_t bits)
+{
+    if ((bits & 0x7fffffffu) > 0x7f800000u) return 0u;                          // a NaN takes no part
+    return bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ uint32_t keyBits(uint32_t key)
+{
+    if (key == 0u) return 0x7fc00000u;                                          // nothing but NaNs
+    return key ^ ((key >> 31) ? 0x80000000u : 0xffffffffu);
+}
+
+// frames [a, b) of this call that belong to column `col`
+__device__ __forceinline__ void columnFrames(const OverviewParams &prm, long col, long &a, long &b)
+{
+    a = col * long(prm.k) - long(prm.held);
+    b = a + long(prm.k);
+    a = a < 0 ? 0 : a;
+    b = b > prm.frames ? prm.frames : b;
+}
+
+// the greatest key of (pair, pixel) over frames [a, b): graph 0's row of every frame, independent loads first
+__device__ __forceinline__ uint32_t framesKey(const OverviewParams &prm, long a, long b, uint32_t pair, uint32_t pixel)
+{
+    const size_t perFrame = size_t(prm.C) * G * prm.P;
+    const float2 *row = prm.lines + size_t(pair) * G * prm.P + pixel;
+    uint32_t run = 0u;
+    for (long f = a; f < b; f += kOvUnroll) {
+        uint32_t bits[kOvUnroll];
+#pragma unroll
+        for (int j = 0; j < kOvUnroll; ++j) bits[j] = f + j < b ? __float_as_uint(row[size_t(f + j) * perFrame].x) : 0xffffffffu;
+#pragma unroll
+        for (int j = 0; j < kOvUnroll; ++j) run = max(run, orderKey(bits[j]));
+    }
+    return run;
+}
+
+// what a (column, pixel) does with its keys: the carry into column 0, then V to the peaks and the colour blend in pair order (a closed
+// column) or to the carry (the open one)
+template <typename KeyOf>
+__device__ __forceinline__ void emitColumn(const OverviewParams &prm, long col, uint32_t pixel, KeyOf keyOf)
+{
+    const bool closed = col < prm.closed;
+    float cb[3] = {0.f, 0.f, 0.f};
+    for (uint32_t pair = 0; pair < prm.C; ++pair) {
+        uint32_t key = keyOf(pair);
+        if (col == 0 && prm.held) key = max(key, orderKey(__float_as_uint(prm.carryIn[size_t(pair) * prm.P + pixel])));
+        const float v = __uint_as_float(keyBits(key));
+        if (!closed) { prm.carryOut[size_t(pair) * prm.P + pixel] = v; continue; }
+        if (prm.peaks) prm.peaks[(size_t(col) * prm.C + pair) * prm.P + pixel] = v;
+        if (prm.rgba) blendColour(cb, v, prm.colourTables + size_t(pair) * NC * 3, prm.sc);
+    }
+    if (closed && prm.rgba) prm.rgba[size_t(col) * prm.P + pixel] = toRgba8(cb);
+}
+
+__global__ void __launch_bounds__(kOvThreads)
+overviewColumnsKernel(const OverviewParams prm)
+{
+    const long col = long(blockIdx.x / prm.blocks);
+    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    if (pixel >= prm.P) return;
+    long a, b;
+    columnFrames(prm, col, a, b);
+    emitColumn(prm, col, pixel, [&](uint32_t pair) { return framesKey(prm, a, b, pair, pixel); });
+}
+
+// slice blockIdx.y of every column's frames (an empty slice -- more slices than frames -- leaves key 0)
+__global__ void __launch_bounds__(kOvThreads)
+overviewSliceKernel(const OverviewParams prm)
+{
+    const long col = long(blockIdx.x / prm.blocks);
+    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    if (pixel >= prm.P) return;
+    long a, b;
+    columnFrames(prm, col, a, b);
+    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
+    const long sa = a + long(blockIdx.y) * per, sb = sa + per < b ? sa + per : b;
+    for (uint32_t pair = 0; pair < prm.C; ++pair)
+        prm.partial[((size_t(blockIdx.y) * size_t(prm.columns) + size_t(col)) * prm.C + pair) * prm.P + pixel] = framesKey(prm, sa, sb, pair, pixel);
+}
+
+__global__ void __launch_bounds__(kOvThreads)
+overviewEmitKernel(const OverviewParams prm)
+{
+    const long col = long(blockIdx.x / prm.blocks);
+    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    if (pixel >= prm.P) return;
+    const size_t perSlice = size_t(prm.columns) * prm.C * prm.P;
+    emitColumn(prm, col, pixel, [&](uint32_t pair) {
+        const uint32_t *q = prm.partial + (size_t(col) * prm.C + pair) * prm.P + pixel;
+        uint32_t run = 0u;
+        for (uint32_t s = 0; s < prm.slices; s += kOvUnroll) {
+            uint32_t key[kOvUnroll];
+#pragma unroll
+            for (int j = 0; j < kOvUnroll; ++j) key[j] = s + j < prm.slices ? q[size_t(s + j) * perSlice] : 0u;
+#pragma unroll
+            for (int j = 0; j < kOvUnroll; ++j) run = max(run, key[j]);
+        }
+        return run;
+    });
+}
+
+// what every overview call refuses before anything else happens (message in g_lastError)
+sgz_status checkOverviewStep(uint32_t k, uint64_t held, uint64_t frames)
+{
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (held >= k) return fail(SGZ_EINVAL, "overview: held < k");
+    if (held + frames < frames) return fail(SGZ_EINVAL, "overview: frame count");
+    return SGZ_OK;
+}
+
+}  // namespace
+
+namespace sgz {
+
+// The slices of a call that leaves the choice to the library: the smallest count <= min(64, k, frames) with columns x ceil(P / 256) x slices
+// >= 2 workgroups per CU.
+uint32_t overviewAutoSlices(long columns, uint32_t blocks, uint32_t k, size_t frames, int cus)
+{
+    const uint64_t unit = uint64_t(columns) * blocks, need = 2 * uint64_t(cus);
+    if (unit >= need) return 1u;
+    const uint64_t most = std::min<uint64_t>(std::min<uint64_t>(kOvMaxSlices, k), std::max<size_t>(frames, 1));
+    return uint32_t(std::min<uint64_t>(most, (need + unit - 1) / unit));
+}
+
+// sgz_stage_overview behind its argument checks (the plan's tables are uploaded).  d_lines [frames][C][G][P] float2.
+sgz_status runOverviewColumns(Plan &p, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices, float *d_carry,
+                              uint8_t *d_rgba, float *d_peaks, hipStream_t stream)
+{
+    const uint64_t t = uint64_t(held) + frames;
+    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
+    const bool open = !flush && t % k != 0;
+    const uint64_t columns = closed + (open ? 1u : 0u);
+    if (frames == 0 && !(flush && held)) return SGZ_OK;          // nothing arrives and no column to flush
+    const uint32_t blocks = (p.P + kOvThreads - 1) / kOvThreads;
+    if (columns == 0 || blocks == 0) return SGZ_OK;
+    if (columns > 0x7fffffffull / blocks || frames > size_t(0x7fffffffffffffffll)) return fail(SGZ_EINVAL, "too many columns for one launch");
+    OverviewParams prm{};
+    prm.lines = reinterpret_cast<const float2 *>(d_lines);
+    prm.frames = long(frames); prm.columns = long(columns); prm.closed = long(closed);
+    prm.k = k; prm.held = held; prm.C = p.C; prm.P = p.P; prm.blocks = blocks;
+    prm.carryIn = d_carry; prm.carryOut = d_carry;
+    prm.rgba = reinterpret_cast<uchar4 *>(d_rgba); prm.peaks = d_peaks;
+    prm.colourTables = p.d_colourTables; prm.sc = p.scalars;
+    if (held && open && columns > 1) {
+        // column 0's threads read the carry while the open column's threads write it: they read a snapshot
+        const size_t carryN = size_t(p.C) * p.P;
+        if (sgz_status st = ensureCap(&p.d_ovCarryCopy, &p.ovCarryCopyCap, carryN); st != SGZ_OK) return st;
+        SGZ_HIP(hipMemcpyAsync(p.d_ovCarryCopy, d_carry, carryN * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        prm.carryIn = p.d_ovCarryCopy;
+    }
+    prm.slices = slices ? slices : overviewAutoSlices(long(columns), blocks, k, frames, numCUs());
+    const dim3 grid(unsigned(columns * blocks));
+    if (prm.slices <= 1) {
+        hipLaunchKernelGGL(overviewColumnsKernel, grid, dim3(kOvThreads), 0, stream, prm);
+        SGZ_HIP(hipGetLastError());
+        return SGZ_OK;
+    }
+    if (sgz_status st = ensureCap(&p.d_ovPartial, &p.ovPartialCap, size_t(prm.slices) * size_t(columns) * p.C * p.P); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<uint32_t *>(p.d_ovPartial);
+    hipLaunchKernelGGL(overviewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
+    SGZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(overviewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
+    SGZ_HIP(hipGetLastError());
+    return SGZ_OK;
+}
+
+}  // namespace sgz
+
+struct sgz_plan { Plan impl; };
+
+extern "C" sgz_status sgz_overview_step(uint32_t k, uint64_t held, uint64_t frames, int flush, uint64_t *columns, uint64_t *held_out)
+{
+    if (!columns || !held_out) return fail(SGZ_EINVAL, "sgz_overview_step: results non-null");
+    if (sgz_status st = checkOverviewStep(k, held, frames); st != SGZ_OK) return st;
+    const uint64_t t = held + frames;
+    *columns = t / k + ((flush && t % k) ? 1u : 0u);
+    *held_out = flush ? 0u : t % k;
+    return SGZ_OK;
+}
+
+extern "C" sgz_status sgz_stage_overview(sgz_plan *plan, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                                         float *d_carry, uint8_t *d_rgba, float *d_peaks, void *stream)
+{
+    if (!plan || !d_lines) return fail(SGZ_EINVAL, "null argument");
+    if (sgz_status st = checkOverviewStep(k, held, frames); st != SGZ_OK) return st;
+    if (slices > kOvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview: slices 0 (automatic) or 1 .. 64");
+    if (!d_rgba && !d_peaks) return fail(SGZ_EINVAL, "sgz_stage_overview: an image, the peaks or both");
+    const uint64_t t = uint64_t(held) + frames;
+    if (!d_carry && (held || (!flush && t % k))) return fail(SGZ_EINVAL, "sgz_stage_overview: d_carry is read (held > 0) or written (frames stay open)");
+    if (frames == 0 && !(flush && held)) return SGZ_OK;
+    Plan &p = plan->impl;
+    if (!p.uploaded) {                                           // the kernels read the plan's colour tables
+        std::string err;
+        const sgz_status st = uploadPlan(p, err);
+        if (st != SGZ_OK) return fail(st, err);
+    }
+    return runOverviewColumns(p, d_lines, frames, k, held, flush, slices, d_carry, d_rgba, d_peaks, reinterpret_cast<hipStream_t>(stream));
+}

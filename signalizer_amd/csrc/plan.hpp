@@ -130,6 +130,7 @@ struct Plan {
                                        //    kernels running beside it -- rocFFT's too --, NOTES.md round 6), 2: fp32 matrix cores (default since round 6)
     uint32_t optResonatorSlab = 0;      // RSNT: frames per slab of a long render (0: as many as fit 256 MiB of per-frame states)
     uint32_t optResonatorShardBound = 0; // RSNT, sharded render: most frames a rank's chunk may hold (0: 8 GiB worth of per-frame states)
+    uint32_t optOverviewSlab = 0;       // the overview render's frames per slab (0: as many as fit 64 MiB of line results)
 
     // device mirrors (owned)
     bool uploaded = false;
@@ -156,6 +157,11 @@ struct Plan {
     // sgz_spectrogram_track_device / _host: the render's line results [frames][pairs][graphs][P] float2 (they stay on the device) and the
     // host form's device copy of the track
     float *d_trackLines = nullptr, *d_hostTrack = nullptr; size_t trackLinesCap = 0, hostTrackCap = 0;
+    // the overview (overview.hip; sgz_spectrogram_overview_device / _host): a slab's line results [slab][pairs][graphs][P] float2, the open
+    // column's V [pairs][P] and its snapshot, the decay state between slabs when the caller carries none, the slices' partial keys
+    // [slices][columns][pairs][P], and the host form's device copy of the peaks
+    float *d_ovLines = nullptr, *d_ovCarry = nullptr, *d_ovCarryCopy = nullptr, *d_ovState = nullptr, *d_ovPartial = nullptr, *d_hostOvPeaks = nullptr;
+    size_t ovLinesCap = 0, ovCarryCap = 0, ovCarryCopyCap = 0, ovStateCap = 0, ovPartialCap = 0, hostOvPeaksCap = 0;
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;

@@ -87,5 +87,10 @@ sgz_status runTrackPeak(const Plan &p, const float *d_bins, double mouseFraction
 sgz_status runTrackPeaks(const Plan &p, const float *d_bins, size_t records, double mouseFraction, sgz_peak *d_out, hipStream_t stream);
 sgz_status runTrackPeaksLines(const Plan &p, const float *d_lines, size_t frames, uint32_t graph, double mouseFraction, sgz_line_peak *d_out,
                               hipStream_t stream);
+// the overview's reduction (overview.hip): k frames of line results per column -> image columns / peaks, the open column in d_carry; the
+// arguments are sgz_stage_overview's, checked by the caller; asynchronous on `stream`, plan scratch grows on demand
+sgz_status runOverviewColumns(Plan &p, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices, float *d_carry,
+                              uint8_t *d_rgba, float *d_peaks, hipStream_t stream);
+uint32_t overviewAutoSlices(long columns, uint32_t blocks, uint32_t k, size_t frames, int cus);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 }  // namespace sgz
