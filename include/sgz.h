@@ -39,6 +39,10 @@ extern "C" {
  * (5, later: the overview render -- sgz_overview_step, sgz_stage_overview, sgz_spectrogram_overview_device / _host and plan option
  *  SGZ_OPT_OVERVIEW_SLAB.  No existing entry point or struct changed and the suite pins 5; a binding that needs them looks the symbols
  *  up, and one that sets the option on an older library gets SGZ_EINVAL, "unknown plan option".)
+ * (5, later: the file lane -- the view of kept peaks (sgz_overview_view_columns, sgz_stage_overview_view, sgz_overview_view_host) and the
+ *  overview inside the PCM stream (sgz_pcm_stream_feed_overview, sgz_pcm_stream_columns_for, sgz_pcm_stream_open_frames,
+ *  sgz_pcm_stream_set_option, sgz_spectrogram_overview_pcm).  No struct changed and the suite pins 5; the one new refusal on an existing call, sgz_pcm_stream_feed
+ *  while an overview column is open, cannot be reached without the new calls.  A binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -364,10 +368,40 @@ uint64_t   sgz_pcm_stream_frames_for(const sgz_pcm_stream *s, size_t nsamples); 
 sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm /*HOST*/, size_t nsamples, uint8_t *rgba_out, float *lines_out /*or NULL*/,
                                uint64_t capacity_frames, uint64_t *frames_out, sgz_pcm_timing *timing /*or NULL*/);
 sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s);
+/* The overview inside the stream: the same pieces, three streams and two slots, but every piece's frames are reduced on the device to the
+ * overview's columns of k frames (below, "The overview render") and only those are read back: the image, the peaks V or both.  Let the
+ * stream be everything fed since create or reset.  The columns of all overview feeds, of which only the last flushes, concatenated, equal
+ * what sgz_spectrogram_overview_host returns for the stream's converted planar floats, byte for byte, image and peaks, however the
+ * stream is cut into feeds and whatever chunk_samples and SGZ_OPT_OVERVIEW_SLAB are.  A feed returns exactly the columns that closed; the
+ * frames of a column that stays open are held on the device (their V, [pairs][P]) with their count.  flush != 0 closes the open column
+ * early, the last frame of the feed included (the counts are those of sgz_overview_step chained over the feeds); the next frame opens a
+ * new column.  A flush with no open column and no new frames returns none.
+ *   rgba_out    HOST RGBA8 [capacity_columns][P][4]; peaks_out HOST float [capacity_columns][pairs][P]; either may be NULL, not both
+ *   columns_for    columns the next feed of nsamples yields at k and flush (0 as well where the feed would be refused for its k)
+ *   open_frames    frames of the open column
+ * Per slot the columns of a piece take ceil(max frames of a piece / k) + 1 columns of device (and, for pageable outputs, pinned) memory,
+ * made on first need and grown when a later k needs more; line results stay in the plan's slab scratch (SGZ_OPT_OVERVIEW_SLAB): memory
+ * is bounded by chunk_samples, window_size and the slab, never by the stream's length.  sgz_pcm_timing.frames counts the columns returned.
+ * Refusals consume nothing and leave the stream unchanged.  SGZ_EINVAL: a null stream, a null pcm with nsamples > 0, k == 0, both outputs
+ * NULL, capacity_columns below the need (*columns_out then holds the need), a k other than the open column's while frames are open.  While a
+ * column is open sgz_pcm_stream_feed is refused with SGZ_EINVAL (flush or reset first); reset drops the open column. */
+sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm /*HOST*/, size_t nsamples, uint32_t k, int flush, uint8_t *rgba_out /*or NULL*/,
+                                        float *peaks_out /*or NULL*/, uint64_t capacity_columns, uint64_t *columns_out, sgz_pcm_timing *timing /*or NULL*/);
+uint64_t   sgz_pcm_stream_columns_for(const sgz_pcm_stream *s, size_t nsamples, uint32_t k, int flush);
+uint64_t   sgz_pcm_stream_open_frames(const sgz_pcm_stream *s);
+/* sgz_plan_set_option on the stream's own plan (SGZ_OPT_OVERVIEW_SLAB bounds the line results an overview feed keeps on the device; the bytes
+ * do not depend on it).  Between feeds. */
+sgz_status sgz_pcm_stream_set_option(sgz_pcm_stream *s, uint32_t option, uint32_t value);
 /* One-shot: a stream with the default chunk_samples (the buffer's length if that is less), one feed of the whole buffer (rgba_out / lines_out hold
  * sgz_num_frames frames), destroyed.  Fewer samples than one window: SGZ_SKIPPED_FRAME, as sgz_spectrogram_render_host. */
 sgz_status sgz_spectrogram_render_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                       const uint32_t *channel_map, size_t nsamples, uint8_t *rgba_out, float *lines_out, sgz_pcm_timing *timing);
+/* One-shot overview: a stream with the default chunk_samples (the buffer's length if that is less), one flushed overview feed of the whole
+ * buffer (rgba_out / peaks_out hold ceil(sgz_num_frames / k) columns; either may be NULL, not both), destroyed.  Fewer samples than one
+ * window: SGZ_SKIPPED_FRAME. */
+sgz_status sgz_spectrogram_overview_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                        const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out, float *peaks_out,
+                                        sgz_pcm_timing *timing);
 
 /* Device memory for the display hand-off: `bytes` rounded up to whole 2 MiB blocks (*allocated), exported as a dma-buf
  * file descriptor (dmabuf_fd may be NULL: plain allocation) that the GL / Vulkan context of the display GPU -- an MI355X has no graphics
@@ -518,6 +552,33 @@ sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar
                                            uint8_t *d_rgba, float *d_peaks, float *d_state, void *stream);
 sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
                                          uint8_t *rgba_out, float *peaks_out, sgz_timing *timing);
+
+/* The view of kept peaks: any range of kept V at any width and in any colours, one small launch -- what a host calls per redraw of a file
+ * lane (zoom, pan, resize, another gradient) instead of rendering the file again.
+ * Definition (exact, no tolerance): given V [n][pairs][P] as any overview call writes its peaks, a source range x0 < x1 <= n, m = x1 - x0,
+ * and out_columns >= 1: cols = min(out_columns, m); output column b covers source columns x0 + ceil(b m / cols) <= j < x0 +
+ * ceil((b + 1) m / cols) (the rule of the dense scope columns; never empty -- zooming in past one source column per pixel is the texture
+ * sampler's job); V'[b][p][i] = the greatest of V[j][p][i] over the column under the overview's total order (NaNs take no part, a group
+ * of NaNs alone gives 0x7FC00000, -0 < +0); the pixel is the additive blend of the pairs' colours at V', then the 8-bit conversion, as
+ * above.  The peak hold is a maximum under a total order, so a coarser column is exactly the maximum of the finer ones it covers: the
+ * view of peaks kept at k has the bits of the direct overview at a multiple of k wherever the column boundaries coincide, and a view
+ * of a view those of the direct view where the boundaries nest.  With cols == m the call is a pure recolour.  The colour tables and
+ * scalars are the plan's; it only has to agree with the peaks in num_pairs and axis_points.
+ *  sgz_overview_view_columns  host arithmetic, no GPU: *columns = cols and, when bounds != NULL, the cols + 1 boundaries x0 + ceil(b m /
+ *                      cols), b = 0 .. cols.  SGZ_EINVAL: x0 >= x1, x1 > n, out_columns == 0, n >= 2^31, a null result.
+ *  sgz_stage_overview_view    DEVICE pointers, asynchronous on `stream`, nothing waited for.  d_rgba [cols][P][4], d_peaks_out float
+ *                      [cols][pairs][P] = V'; either may be NULL, not both.  slices as in sgz_stage_overview: 0 = the library's choice,
+ *                      1 .. 64 forced, identical bits.  Only the documented bytes are written.  The outputs must not overlap d_peaks.
+ *                      SGZ_EINVAL, nothing launched or written: a null plan or d_peaks, what sgz_overview_view_columns refuses,
+ *                      slices > 64, both outputs NULL, an output that overlaps source columns [x0, x1).
+ *  sgz_overview_view_host     HOST peaks, as the host overview and the stream return them: uploads only columns [x0, x1) into plan
+ *                      scratch on the plan's own stream, runs the stage call, reads back the cols columns and waits.  timing->frames
+ *                      counts the columns returned. */
+sgz_status sgz_overview_view_columns(uint64_t n, uint64_t x0, uint64_t x1, uint32_t out_columns, uint64_t *columns, uint64_t *bounds /*[cols + 1] or NULL*/);
+sgz_status sgz_stage_overview_view(sgz_plan *plan, const float *d_peaks, size_t n, size_t x0, size_t x1, uint32_t out_columns, uint32_t slices,
+                                   uint8_t *d_rgba, float *d_peaks_out, void *stream);
+sgz_status sgz_overview_view_host(sgz_plan *plan, const float *peaks, size_t n, size_t x0, size_t x1, uint32_t out_columns, uint8_t *rgba_out,
+                                  float *peaks_out, sgz_timing *timing);
 
 /* K_B in two steps, for the multi-GPU carry exchange (collective A2).  scan: the chunk scans of `frames` frames from a
  * ZERO carry-in; writes that zero-carry end state (what a rank publishes) to d_end_state [pairs][graphs][P][2] and keeps the chunk

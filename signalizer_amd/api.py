@@ -192,6 +192,9 @@ EXPORTS = [
     "sgz_pcm_stream_frames_for", "sgz_pcm_stream_feed", "sgz_pcm_stream_reset", "sgz_spectrogram_render_pcm",
     "sgz_stage_track_peaks", "sgz_stage_track_peaks_lines", "sgz_spectrogram_track_device", "sgz_spectrogram_track_host",
     "sgz_overview_step", "sgz_stage_overview", "sgz_spectrogram_overview_device", "sgz_spectrogram_overview_host",
+    "sgz_overview_view_columns", "sgz_stage_overview_view", "sgz_overview_view_host",
+    "sgz_pcm_stream_feed_overview", "sgz_pcm_stream_columns_for", "sgz_pcm_stream_open_frames", "sgz_spectrogram_overview_pcm",
+    "sgz_pcm_stream_set_option",
 ]
 
 
@@ -278,6 +281,9 @@ def lib() -> C.CDLL:
     L.sgz_stage_overview.argtypes = [vp, vp, sz, u32, u32, C.c_int, u32, vp, vp, vp, vp]
     L.sgz_spectrogram_overview_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, vp]
     L.sgz_spectrogram_overview_host.argtypes = [vp, vp, u32, sz, u32, vp, vp, C.POINTER(Timing)]
+    L.sgz_overview_view_columns.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, u32, C.POINTER(C.c_uint64), vp]
+    L.sgz_stage_overview_view.argtypes = [vp, vp, sz, sz, sz, u32, u32, vp, vp, vp]
+    L.sgz_overview_view_host.argtypes = [vp, vp, sz, sz, sz, u32, vp, vp, C.POINTER(Timing)]
     L.sgz_comm_unique_id.argtypes = [vp]
     L.sgz_comm_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.sgz_comm_destroy.argtypes = [vp]
@@ -398,6 +404,13 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_feed.argtypes = [vp, vp, sz, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
     L.sgz_pcm_stream_reset.argtypes = [vp]
     L.sgz_spectrogram_render_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, vp, vp, C.POINTER(PcmTiming)]
+    L.sgz_pcm_stream_feed_overview.argtypes = [vp, vp, sz, u32, C.c_int, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
+    L.sgz_pcm_stream_columns_for.argtypes = [vp, sz, u32, C.c_int]
+    L.sgz_pcm_stream_columns_for.restype = u64
+    L.sgz_pcm_stream_open_frames.argtypes = [vp]
+    L.sgz_pcm_stream_open_frames.restype = u64
+    L.sgz_pcm_stream_set_option.argtypes = [vp, u32, u32]
+    L.sgz_spectrogram_overview_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, C.POINTER(PcmTiming)]
     _lib = L
     return L
 
@@ -617,6 +630,18 @@ def overview_step(k: int, held: int, frames: int, flush: bool):
     return c.value, h.value
 
 
+def overview_view_columns(n: int, x0: int, x1: int, out_columns: int, want_bounds: bool = False):
+    """sgz_overview_view_columns (host arithmetic, no GPU): the view's column count min(out_columns, x1 - x0), or with want_bounds (count,
+    uint64 [count + 1] boundaries x0 + ceil(b m / count))"""
+    c = C.c_uint64(0)
+    check(lib().sgz_overview_view_columns(n, x0, x1, out_columns, C.byref(c), None))
+    if not want_bounds:
+        return int(c.value)
+    bounds = np.zeros(c.value + 1, np.uint64)
+    check(lib().sgz_overview_view_columns(n, x0, x1, out_columns, C.byref(c), _np_ptr(bounds)))
+    return int(c.value), bounds
+
+
 class Plan:
     """The Spectrum constant block (TransformConstant mirror). Host tables need no GPU."""
 
@@ -815,6 +840,32 @@ class Plan:
         if st == SGZ_SKIPPED_FRAME:
             return None
         return (rgba[:columns] if want_rgba else None), (peaks[:columns] if want_peaks else None)
+
+    def overview_view(self, peaks, out_columns: int, x0: int = 0, x1: int | None = None, slices: int = 0, want_rgba: bool = True,
+                      want_peaks: bool = False, stream=None):
+        """The view of kept peaks [n, C, P] over source columns [x0, x1) (default: to the end) at min(out_columns, x1 - x0) columns.  peaks a
+        cuda float32 tensor: sgz_stage_overview_view, asynchronous -> (cuda rgba uint8 [cols, P, 4] or None, cuda peaks float32 [cols, C, P]
+        or None).  peaks a numpy array: sgz_overview_view_host -> (rgba or None, peaks or None, timing dict)."""
+        n = int(peaks.shape[0])
+        x1 = n if x1 is None else x1
+        assert tuple(peaks.shape[1:]) == (self.C, self.P), tuple(peaks.shape)
+        cols = overview_view_columns(n, x0, x1, out_columns)
+        if isinstance(peaks, np.ndarray):
+            peaks = np.ascontiguousarray(peaks, np.float32)
+            rgba = np.zeros((cols, self.P, 4), np.uint8) if want_rgba else None
+            out = np.zeros((cols, self.C, self.P), np.float32) if want_peaks else None
+            t = Timing()
+            check(lib().sgz_overview_view_host(self.h, _np_ptr(peaks), n, x0, x1, out_columns, _np_ptr(rgba) if want_rgba else None,
+                                               _np_ptr(out) if want_peaks else None, C.byref(t)))
+            return rgba, out, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+        import torch
+        assert peaks.is_cuda and peaks.dtype == torch.float32 and peaks.is_contiguous()
+        rgba = torch.empty((cols, self.P, 4), dtype=torch.uint8, device=peaks.device) if want_rgba else None
+        out = torch.empty((cols, self.C, self.P), dtype=torch.float32, device=peaks.device) if want_peaks else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview_view(self.h, peaks.data_ptr(), n, x0, x1, out_columns, slices, rgba.data_ptr() if want_rgba else None,
+                                            out.data_ptr() if want_peaks else None, s))
+        return rgba, out
 
     def colour_table(self, pair: int) -> np.ndarray:
         out = np.zeros((NUM_SPEC_COLOURS + 1, 3), np.float32)
@@ -1057,6 +1108,61 @@ class PcmStream:
         check(st)
         assert f == F, (f, F)
         return rgba[:F], lines[:F] if want_lines else None, t.asdict()
+
+    def set_option(self, option: int, value: int) -> None:
+        """sgz_pcm_stream_set_option: a plan option (OPT_*) on the stream's own plan"""
+        check(lib().sgz_pcm_stream_set_option(self.h, option, value))
+
+    def columns_for(self, nsamples: int, k: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_columns_for: overview columns the next feed of nsamples yields at k"""
+        return int(lib().sgz_pcm_stream_columns_for(self.h, nsamples, k, int(bool(flush))))
+
+    def open_frames(self) -> int:
+        """sgz_pcm_stream_open_frames: frames of the overview column that is open"""
+        return int(lib().sgz_pcm_stream_open_frames(self.h))
+
+    def feed_overview_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, peaks, capacity_columns: int, timing: bool = True):
+        """the C call as it is: (status, columns_out, PcmTiming or None); rgba / peaks: numpy arrays, host torch tensors or None"""
+        t, c = PcmTiming() if timing else None, C.c_uint64(0)
+        st = lib().sgz_pcm_stream_feed_overview(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
+                                                _buf_ptr(rgba) if rgba is not None else None, _buf_ptr(peaks) if peaks is not None else None,
+                                                capacity_columns, C.byref(c), C.byref(t) if timing else None)
+        return st, int(c.value), t
+
+    def feed_overview(self, pcm, k: int, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_peaks: bool = False):
+        """Feeds nsamples (default: all of pcm; pcm None: none) into the overview at k frames per column and returns the columns that closed:
+        (rgba uint8 [columns, P, 4] or None, peaks float32 [columns, pairs, P] or None, timing dict)."""
+        if pcm is None:
+            n = 0
+        else:
+            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+            n = nbytes // self.frame_bytes if nsamples is None else nsamples
+        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
+        P = self.cfg.axis_points
+        rgba = np.zeros((max(cols, 1), P, 4), np.uint8) if want_rgba else None
+        peaks = np.zeros((max(cols, 1), self.cfg.num_pairs, P), np.float32) if want_peaks else None
+        st, c, t = self.feed_overview_into(pcm if n else None, n, k, flush, rgba, peaks, cols)
+        check(st)
+        assert c == cols, (c, cols)
+        return (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
+
+
+def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
+                 want_peaks: bool = False):
+    """One-shot overview of an interleaved PCM buffer (sgz_spectrogram_overview_pcm): (status, rgba or None, peaks or None, timing dict);
+    status is SGZ_SKIPPED_FRAME for fewer samples than one window."""
+    c = _as_config(cfg)
+    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
+    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
+    cols = -(-F // k) if k else 0
+    rgba = np.zeros((max(cols, 1), c.axis_points, 4), np.uint8) if want_rgba else None
+    peaks = np.zeros((max(cols, 1), c.num_pairs, c.axis_points), np.float32) if want_peaks else None
+    m, mp = _channel_map(channel_map)
+    t = PcmTiming()
+    st = check(lib().sgz_spectrogram_overview_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(rgba) if want_rgba else None,
+                                                  _np_ptr(peaks) if want_peaks else None, C.byref(t)))
+    return st, (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
 
 
 def render_spectrogram_pcm(cfg, pcm, fmt: int, src_channels: int, channel_map=None, nsamples: int | None = None, want_lines: bool = False):

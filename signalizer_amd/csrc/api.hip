@@ -44,7 +44,7 @@ Plan::~Plan()
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq, (void *)d_ovLines, (void *)d_ovCarry,
-                    (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks})
+                    (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks, (void *)d_ovViewIn})
         if (p) (void)hipFree(p);
     for (void *e : hostEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *e : shardEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
@@ -1036,23 +1036,18 @@ sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar
 // state makes the pieces equal the single render byte for byte (what sgz_pcm_stream relies on), so the columns do not depend on the slab.
 // RSNT renders as one slab: its launches chain their frames within an fp32 bar, a cut would move the bits.
 constexpr size_t kOverviewSlabBytes = size_t(64) << 20;
-sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
-                                           uint8_t *d_rgba, float *d_peaks, float *d_state, void *stream)
+}  // extern "C"
+// The slab loop by itself (runtime.hpp): `held` frames of an open column in front (their V in d_carry), the columns that close written from
+// the outputs' first element on.  The overview render enters with held = 0 and flush; sgz_pcm_stream enters once per piece.
+sgz_status sgz::runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
+                                 int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t s)
 {
-    if (!plan || !d_planar) return fail(SGZ_EINVAL, "null argument");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (!d_rgba && !d_peaks) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
-    sgz_status st = checkReady(plan);
-    if (st != SGZ_OK) return st;
     Plan &p = plan->impl;
-    const long frames = planFrames(p, nsamples);
-    if (frames <= 0) return SGZ_SKIPPED_FRAME;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    sgz_status st = SGZ_OK;
     const size_t perFrame = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;                                   // floats of line results
     long slab = frames;
     if (!isResonator(p)) slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kOverviewSlabBytes / (perFrame * sizeof(float)))));
     if ((st = ensureCap(&p.d_ovLines, &p.ovLinesCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
-    if ((st = ensureCap(&p.d_ovCarry, &p.ovCarryCap, size_t(p.C) * p.P)) != SGZ_OK) return st;
     float *state = d_state;
     if (!state && slab < frames) {                               // the slabs continue a state of the plan's own, from rest
         const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
@@ -1065,12 +1060,28 @@ sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar
         const size_t ns = isResonator(p) ? nsamples : size_t(p.W) + size_t(nf - 1) * p.cfg.hop;
         st = sgz_spectrogram_render_device(plan, d_planar + size_t(f0) * p.cfg.hop, channel_stride, ns, nullptr, p.d_ovLines, state, s);
         if (st != SGZ_OK) return st;
-        const size_t column = size_t(f0) / k;                   // the column frame f0 belongs to: the carried one when f0 % k != 0
-        st = runOverviewColumns(p, p.d_ovLines, size_t(nf), k, uint32_t(size_t(f0) % k), f0 + nf == frames, 0, p.d_ovCarry,
+        const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
+        const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
+        st = runOverviewColumns(p, p.d_ovLines, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, 0, d_carry,
                                 d_rgba ? d_rgba + column * p.P * 4 : nullptr, d_peaks ? d_peaks + column * p.C * p.P : nullptr, s);
         if (st != SGZ_OK) return st;
     }
     return SGZ_OK;
+}
+extern "C" {
+sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                           uint8_t *d_rgba, float *d_peaks, float *d_state, void *stream)
+{
+    if (!plan || !d_planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!d_rgba && !d_peaks) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    if ((st = ensureCap(&p.d_ovCarry, &p.ovCarryCap, size_t(p.C) * p.P)) != SGZ_OK) return st;
+    return runOverviewSlabs(plan, d_planar, channel_stride, nsamples, frames, k, 0, 1, p.d_ovCarry, d_state, d_rgba, d_peaks, reinterpret_cast<hipStream_t>(stream));
 }
 
 sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
@@ -1106,6 +1117,40 @@ sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *pla
     SGZ_HIP(hipEventRecord(ev[3], s));
     SGZ_HIP(hipStreamSynchronize(s));
     if (timing) fillHostTiming(*timing, ev, frames);
+    return SGZ_OK;
+}
+
+// The view of kept peaks from HOST peaks (sgz.h; overview.hip): only the range's columns are uploaded, into plan scratch, on the plan's own
+// stream; the stage call runs behind the upload and the `cols` columns are read back.
+sgz_status sgz_overview_view_host(sgz_plan *plan, const float *peaks, size_t n, size_t x0, size_t x1, uint32_t out_columns, uint8_t *rgba_out,
+                                  float *peaks_out, sgz_timing *timing)
+{
+    if (!plan || !peaks) return fail(SGZ_EINVAL, "null argument");
+    uint64_t cols = 0;
+    sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols);
+    if (st != SGZ_OK) return st;
+    if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "sgz_overview_view_host: an image, the peaks or both");
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t column = size_t(p.C) * p.P, m = x1 - x0;
+    if ((st = ensureCap(&p.d_ovViewIn, &p.ovViewInCap, m * column)) != SGZ_OK) return st;
+    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, size_t(cols) * p.P)) != SGZ_OK) return st;
+    if (peaks_out && (st = ensureCap(&p.d_hostOvPeaks, &p.hostOvPeaksCap, size_t(cols) * column)) != SGZ_OK) return st;
+    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
+    float *d_out = peaks_out ? p.d_hostOvPeaks : nullptr;
+    SGZ_HIP(hipEventRecord(ev[0], s));
+    SGZ_HIP(hipMemcpyAsync(p.d_ovViewIn, peaks + x0 * column, m * column * sizeof(float), hipMemcpyHostToDevice, s));
+    SGZ_HIP(hipEventRecord(ev[1], s));
+    if ((st = runOverviewView(p, p.d_ovViewIn, m, size_t(cols), 0, d_rgba, d_out, s)) != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(cols) * p.P * 4, hipMemcpyDeviceToHost, s));
+    if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaks_out, d_out, size_t(cols) * column * sizeof(float), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)
     return SGZ_OK;
 }
 

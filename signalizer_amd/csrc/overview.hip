@@ -11,6 +11,7 @@
 //   overviewSliceKernel     few columns of many frames: slice s of a column's frames -> partial keys [slices][columns][pairs][P] in plan
 //   overviewEmitKernel      scratch; then the fold over the slices and the carry, the colour, the store -- a launch of its own behind it on
 //                           the stream (no hand-off between workgroups inside a launch).
+// The view of kept peaks (overviewViewKernel, overviewViewSliceKernel, overviewViewEmitKernel; further down) is the same reduction on V itself.
 // Nothing is waited for; scratch grows on demand (only growth synchronises); everything runs on the caller's stream.
 #include <hip/hip_runtime.h>
 
@@ -146,6 +147,112 @@ overviewEmitKernel(const OverviewParams prm)
     });
 }
 
+// ---- the view of kept peaks (sgz.h, "The view of kept peaks") -------------------------------------------------------------------------------
+// V [n][pairs][P] as any overview call writes it; output column b is the greatest, under the same order, of source columns
+// ceil(b m / cols) <= j < ceil((b + 1) m / cols) of the range, m = x1 - x0 -- a maximum of maxima, hence the bits of the direct render
+// wherever the boundaries coincide.  The same three shapes as above, on [column][pair][P] floats instead of line results:
+//   overviewViewKernel        one thread per (output column, pixel), pairs outermost, the column's source columns inside
+//   overviewViewSliceKernel   few output columns over many source columns: slice s of every column -> partial keys in plan scratch
+//   overviewViewEmitKernel    the fold over the slices, the colour, the store
+struct ViewParams {
+    const float *src;                    // [m][C][P]: the range's first source column
+    long m, cols;
+    uint32_t C, P, blocks, slices;
+    uchar4 *rgba;                        // [cols][P] or null
+    float *peaks;                        // [cols][C][P] or null
+    uint32_t *partial;                   // [slices][cols][C][P] keys
+    const float *colourTables;
+    DeviceScalars sc;
+};
+
+// source columns [a, b) of output column `col`, relative to the range (m < 2^31 and col <= cols <= m: the products fit)
+__device__ __forceinline__ void viewColumns(const ViewParams &prm, long col, long &a, long &b)
+{
+    a = (col * prm.m + prm.cols - 1) / prm.cols;
+    b = ((col + 1) * prm.m + prm.cols - 1) / prm.cols;
+}
+
+// the greatest key of (pair, pixel) over source columns [a, b), independent loads first
+__device__ __forceinline__ uint32_t viewKey(const ViewParams &prm, long a, long b, uint32_t pair, uint32_t pixel)
+{
+    const size_t perColumn = size_t(prm.C) * prm.P;
+    const float *row = prm.src + size_t(pair) * prm.P + pixel;
+    uint32_t run = 0u;
+    for (long j = a; j < b; j += kOvUnroll) {
+        uint32_t bits[kOvUnroll];
+#pragma unroll
+        for (int u = 0; u < kOvUnroll; ++u) bits[u] = j + u < b ? __float_as_uint(row[size_t(j + u) * perColumn]) : 0xffffffffu;
+#pragma unroll
+        for (int u = 0; u < kOvUnroll; ++u) run = max(run, orderKey(bits[u]));
+    }
+    return run;
+}
+
+template <typename KeyOf>
+__device__ __forceinline__ void emitViewColumn(const ViewParams &prm, long col, uint32_t pixel, KeyOf keyOf)
+{
+    float cb[3] = {0.f, 0.f, 0.f};
+    for (uint32_t pair = 0; pair < prm.C; ++pair) {
+        const float v = __uint_as_float(keyBits(keyOf(pair)));
+        if (prm.peaks) prm.peaks[(size_t(col) * prm.C + pair) * prm.P + pixel] = v;
+        if (prm.rgba) blendColour(cb, v, prm.colourTables + size_t(pair) * NC * 3, prm.sc);
+    }
+    if (prm.rgba) prm.rgba[size_t(col) * prm.P + pixel] = toRgba8(cb);
+}
+
+__global__ void __launch_bounds__(kOvThreads)
+overviewViewKernel(const ViewParams prm)
+{
+    const long col = long(blockIdx.x / prm.blocks);
+    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    if (pixel >= prm.P) return;
+    long a, b;
+    viewColumns(prm, col, a, b);
+    emitViewColumn(prm, col, pixel, [&](uint32_t pair) { return viewKey(prm, a, b, pair, pixel); });
+}
+
+// slice blockIdx.y of every output column's source columns (an empty slice leaves key 0)
+__global__ void __launch_bounds__(kOvThreads)
+overviewViewSliceKernel(const ViewParams prm)
+{
+    const long col = long(blockIdx.x / prm.blocks);
+    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    if (pixel >= prm.P) return;
+    long a, b;
+    viewColumns(prm, col, a, b);
+    const long per = (b - a + long(prm.slices) - 1) / long(prm.slices);
+    const long sa = a + long(blockIdx.y) * per, sb = sa + per < b ? sa + per : b;
+    for (uint32_t pair = 0; pair < prm.C; ++pair)
+        prm.partial[((size_t(blockIdx.y) * size_t(prm.cols) + size_t(col)) * prm.C + pair) * prm.P + pixel] = viewKey(prm, sa, sb, pair, pixel);
+}
+
+__global__ void __launch_bounds__(kOvThreads)
+overviewViewEmitKernel(const ViewParams prm)
+{
+    const long col = long(blockIdx.x / prm.blocks);
+    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    if (pixel >= prm.P) return;
+    const size_t perSlice = size_t(prm.cols) * prm.C * prm.P;
+    emitViewColumn(prm, col, pixel, [&](uint32_t pair) {
+        const uint32_t *q = prm.partial + (size_t(col) * prm.C + pair) * prm.P + pixel;
+        uint32_t run = 0u;
+        for (uint32_t s = 0; s < prm.slices; s += kOvUnroll) {
+            uint32_t key[kOvUnroll];
+#pragma unroll
+            for (int j = 0; j < kOvUnroll; ++j) key[j] = s + j < prm.slices ? q[size_t(s + j) * perSlice] : 0u;
+#pragma unroll
+            for (int j = 0; j < kOvUnroll; ++j) run = max(run, key[j]);
+        }
+        return run;
+    });
+}
+
+bool bytesOverlap(const void *a, size_t aBytes, const void *b, size_t bBytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + bBytes && b0 < a0 + aBytes;
+}
+
 // what every overview call refuses before anything else happens (message in g_lastError)
 sgz_status checkOverviewStep(uint32_t k, uint64_t held, uint64_t frames)
 {
@@ -211,9 +318,82 @@ sgz_status runOverviewColumns(Plan &p, const float *d_lines, size_t frames, uint
     return SGZ_OK;
 }
 
+// what every view call refuses about its range (message in g_lastError); *cols = min(out_columns, x1 - x0)
+sgz_status checkViewRange(uint64_t n, uint64_t x0, uint64_t x1, uint32_t outColumns, uint64_t *cols)
+{
+    if (n >= (uint64_t(1) << 31)) return fail(SGZ_EINVAL, "overview view: fewer than 2^31 source columns");
+    if (x0 >= x1 || x1 > n) return fail(SGZ_EINVAL, "overview view: x0 < x1 <= n");
+    if (outColumns == 0) return fail(SGZ_EINVAL, "overview view: out_columns >= 1");
+    *cols = std::min<uint64_t>(outColumns, x1 - x0);
+    return SGZ_OK;
+}
+
+// sgz_stage_overview_view behind its argument checks (the plan's tables are uploaded).  d_src [m][C][P]: the range's first source column.
+sgz_status runOverviewView(Plan &p, const float *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba, float *d_peaksOut, hipStream_t stream)
+{
+    const uint32_t blocks = (p.P + kOvThreads - 1) / kOvThreads;
+    if (cols == 0 || blocks == 0) return SGZ_OK;
+    if (cols > 0x7fffffffull / blocks) return fail(SGZ_EINVAL, "too many columns for one launch");
+    ViewParams prm{};
+    prm.src = d_src; prm.m = long(m); prm.cols = long(cols);
+    prm.C = p.C; prm.P = p.P; prm.blocks = blocks;
+    prm.rgba = reinterpret_cast<uchar4 *>(d_rgba); prm.peaks = d_peaksOut;
+    prm.colourTables = p.d_colourTables; prm.sc = p.scalars;
+    const uint32_t most = uint32_t((m + cols - 1) / cols);       // source columns of the longest output column
+    // the overview's rule at four workgroups per CU, and no slice shorter than one batch of kOvUnroll loads
+    prm.slices = slices ? slices : std::min(overviewAutoSlices(long(cols), blocks, most, m, 2 * numCUs()), std::max(1u, most / uint32_t(kOvUnroll)));
+    const dim3 grid(unsigned(cols * blocks));
+    if (prm.slices <= 1) {
+        hipLaunchKernelGGL(overviewViewKernel, grid, dim3(kOvThreads), 0, stream, prm);
+        SGZ_HIP(hipGetLastError());
+        return SGZ_OK;
+    }
+    if (sgz_status st = ensureCap(&p.d_ovPartial, &p.ovPartialCap, size_t(prm.slices) * cols * p.C * p.P); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<uint32_t *>(p.d_ovPartial);
+    hipLaunchKernelGGL(overviewViewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
+    SGZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(overviewViewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
+    SGZ_HIP(hipGetLastError());
+    return SGZ_OK;
+}
+
 }  // namespace sgz
 
 struct sgz_plan { Plan impl; };
+
+extern "C" sgz_status sgz_overview_view_columns(uint64_t n, uint64_t x0, uint64_t x1, uint32_t out_columns, uint64_t *columns, uint64_t *bounds)
+{
+    if (!columns) return fail(SGZ_EINVAL, "sgz_overview_view_columns: result non-null");
+    uint64_t cols = 0;
+    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
+    *columns = cols;
+    const uint64_t m = x1 - x0;
+    if (bounds)
+        for (uint64_t b = 0; b <= cols; ++b) bounds[b] = x0 + (b * m + cols - 1) / cols;
+    return SGZ_OK;
+}
+
+extern "C" sgz_status sgz_stage_overview_view(sgz_plan *plan, const float *d_peaks, size_t n, size_t x0, size_t x1, uint32_t out_columns, uint32_t slices,
+                                              uint8_t *d_rgba, float *d_peaks_out, void *stream)
+{
+    if (!plan || !d_peaks) return fail(SGZ_EINVAL, "null argument");
+    uint64_t cols = 0;
+    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
+    if (slices > kOvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview_view: slices 0 (automatic) or 1 .. 64");
+    if (!d_rgba && !d_peaks_out) return fail(SGZ_EINVAL, "sgz_stage_overview_view: an image, the peaks or both");
+    Plan &p = plan->impl;
+    const size_t column = size_t(p.C) * p.P;                     // floats of a source column
+    const float *src = d_peaks + x0 * column;
+    const size_t srcBytes = (x1 - x0) * column * sizeof(float);
+    if (bytesOverlap(src, srcBytes, d_rgba, size_t(cols) * p.P * 4) || bytesOverlap(src, srcBytes, d_peaks_out, size_t(cols) * column * sizeof(float)))
+        return fail(SGZ_EINVAL, "sgz_stage_overview_view: an output overlaps the source columns it is made from");
+    if (!p.uploaded) {                                           // the kernels read the plan's colour tables
+        std::string err;
+        const sgz_status st = uploadPlan(p, err);
+        if (st != SGZ_OK) return fail(st, err);
+    }
+    return runOverviewView(p, src, x1 - x0, size_t(cols), slices, d_rgba, d_peaks_out, reinterpret_cast<hipStream_t>(stream));
+}
 
 extern "C" sgz_status sgz_overview_step(uint32_t k, uint64_t held, uint64_t frames, int flush, uint64_t *columns, uint64_t *held_out)
 {

@@ -202,6 +202,11 @@ struct PcmSlot {                        // what one piece in flight owns; a slot
     bool busy = false, rendered = false;
     // the host's part of the read-back, done when the slot is drained
     uint8_t *rgbaDst = nullptr; float *linesDst = nullptr; size_t rgbaBytes = 0, linesBytes = 0;
+    const uint8_t *rgbaFrom = nullptr; const float *linesFrom = nullptr;       // the pinned twins the drain copies from
+    // the overview's columns of one piece (sgz_pcm_stream_feed_overview): [ovCap][P][4] and V [ovCap][C][P] with their pinned twins, made on
+    // first need and grown when a later k needs more columns per piece
+    uint8_t *d_ovRgba = nullptr, *h_ovRgba = nullptr; float *d_ovPeaks = nullptr, *h_ovPeaks = nullptr;
+    size_t ovRgbaCap = 0, ovRgbaPinnedCap = 0, ovPeaksCap = 0, ovPeaksPinnedCap = 0;       // columns
 };
 }  // namespace
 
@@ -217,7 +222,12 @@ struct sgz_pcm_stream {
     float *d_state = nullptr;
     int cur = 0;
     uint64_t held = 0, pieces = 0;
+    // the overview inside the stream: the open column's V [pairs][P], its frame count and its k (meaningful while ovOpen > 0)
+    float *d_ovCarry = nullptr;
+    uint64_t ovOpen = 0; uint32_t ovK = 0;
 };
+
+struct sgz_plan { Plan impl; };
 
 static size_t pcmStateBytes(const sgz_pcm_stream &s) { return size_t(s.cfg.num_pairs) * SGZ_NUM_GRAPHS * s.cfg.axis_points * 2 * sizeof(float); }
 static size_t pcmLinesFloats(const sgz_pcm_stream &s, uint64_t frames) { return size_t(frames) * s.cfg.num_pairs * SGZ_NUM_GRAPHS * s.cfg.axis_points * 2; }
@@ -228,8 +238,8 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
     if (!sl.busy) return SGZ_OK;
     sl.busy = false;
     SGZ_HIP(hipEventSynchronize(sl.ev[sl.rendered ? 6 : 4]));
-    if (sl.rgbaDst) std::memcpy(sl.rgbaDst, sl.h_rgba, sl.rgbaBytes);
-    if (sl.linesDst) std::memcpy(sl.linesDst, sl.h_lines, sl.linesBytes);
+    if (sl.rgbaDst) std::memcpy(sl.rgbaDst, sl.rgbaFrom, sl.rgbaBytes);
+    if (sl.linesDst) std::memcpy(sl.linesDst, sl.linesFrom, sl.linesBytes);
     sl.rgbaDst = nullptr; sl.linesDst = nullptr;
     if (timing && sl.timed) {
         float ms = 0.f;
@@ -238,6 +248,18 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
         if (hipEventElapsedTime(&ms, sl.ev[3], sl.ev[4]) == hipSuccess) timing->render_ms += ms;
         if (sl.rendered && hipEventElapsedTime(&ms, sl.ev[5], sl.ev[6]) == hipSuccess) timing->d2h_ms += ms;
     }
+    return SGZ_OK;
+}
+
+// a device or pinned block of at least `need` columns of `bytes` each (the slot is idle: nothing in flight reads the old one)
+template <typename T>
+static sgz_status pcmGrow(T **buf, size_t *cap, size_t need, size_t bytes, bool pinned)
+{
+    if (*cap >= need) return SGZ_OK;
+    if (*buf) { (void)(pinned ? hipHostFree(*buf) : hipFree(*buf)); *buf = nullptr; *cap = 0; }
+    if (pinned) SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(buf), need * bytes, hipHostMallocDefault));
+    else SGZ_HIP(hipMalloc(reinterpret_cast<void **>(buf), need * bytes));
+    *cap = need;
     return SGZ_OK;
 }
 
@@ -263,11 +285,11 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
     if (!s) return;
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamSynchronize(q);
     for (PcmSlot &sl : s->slot) {
-        for (void *p : {sl.h_pcm, (void *)sl.h_rgba, (void *)sl.h_lines}) if (p) (void)hipHostFree(p);
-        for (void *p : {sl.d_pcm, (void *)sl.d_rgba, (void *)sl.d_lines}) if (p) (void)hipFree(p);
+        for (void *p : {sl.h_pcm, (void *)sl.h_rgba, (void *)sl.h_lines, (void *)sl.h_ovRgba, (void *)sl.h_ovPeaks}) if (p) (void)hipHostFree(p);
+        for (void *p : {sl.d_pcm, (void *)sl.d_rgba, (void *)sl.d_lines, (void *)sl.d_ovRgba, (void *)sl.d_ovPeaks}) if (p) (void)hipFree(p);
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
     if (s->plan) sgz_plan_destroy(s->plan);
     delete s;
@@ -321,6 +343,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     SGZ_HIP(hipMemsetAsync(s->d_state, 0, pcmStateBytes(*s), s->compute));          // (in order behind whatever the last feed left there: nothing)
     SGZ_HIP(hipStreamSynchronize(s->compute));
     s->held = 0;
+    s->ovOpen = 0;                                                                  // an open overview column is dropped
     return SGZ_OK;
 }
 
@@ -330,6 +353,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     const auto t0 = std::chrono::steady_clock::now();
     if (!s) return fail(SGZ_EINVAL, "null stream");
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null pcm");
+    if (s->ovOpen) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: an overview column is open -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
     const uint64_t need = sgz_pcm_stream_frames_for(s, nsamples);
     if (frames_out) *frames_out = need;
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
@@ -389,8 +413,8 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
             SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_rgba, sl.d_rgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
             if (lines_out) SGZ_HIP(hipMemcpyAsync(linesPinned ? linesAt : sl.h_lines, sl.d_lines, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
             SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
-            sl.rgbaDst = rgbaPinned ? nullptr : rgbaAt;
-            sl.linesDst = (lines_out && !linesPinned) ? linesAt : nullptr;
+            sl.rgbaDst = rgbaPinned ? nullptr : rgbaAt; sl.rgbaFrom = sl.h_rgba;
+            sl.linesDst = (lines_out && !linesPinned) ? linesAt : nullptr; sl.linesFrom = sl.h_lines;
         }
         sl.busy = true;
         framesDone += frames; ++chunks; ++s->pieces; at += n;
@@ -420,6 +444,159 @@ sgz_status sgz_spectrogram_render_pcm(const sgz_spectrum_config *cfg, const void
     sgz_status st = SGZ_SKIPPED_FRAME;
     if (frames == 0) { if (timing) *timing = sgz_pcm_timing{}; }
     else st = sgz_pcm_stream_feed(s, pcm, nsamples, rgba_out, lines_out, frames, &frames, timing);
+    const std::string keep = g_lastError;
+    sgz_pcm_stream_destroy(s);
+    g_lastError = keep;
+    if (timing && st == SGZ_OK) timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return st;
+}
+
+// ---- the overview inside the stream (sgz.h, "the overview inside sgz_pcm_stream") ----------------------------------------------------------
+// columns a feed of nsamples yields at k with the stream as it is; false: k == 0, or a k other than the open column's
+static bool pcmOverviewNeed(const sgz_pcm_stream *s, size_t nsamples, uint32_t k, int flush, uint64_t *columns)
+{
+    if (!s || k == 0 || (s->ovOpen && k != s->ovK)) return false;
+    const uint64_t t = s->ovOpen + sgz_pcm_stream_frames_for(s, nsamples);
+    *columns = t / k + ((flush && t % k) ? 1u : 0u);
+    return true;
+}
+
+uint64_t sgz_pcm_stream_columns_for(const sgz_pcm_stream *s, size_t nsamples, uint32_t k, int flush)
+{
+    uint64_t columns = 0;
+    return pcmOverviewNeed(s, nsamples, k, flush, &columns) ? columns : 0;
+}
+
+uint64_t sgz_pcm_stream_open_frames(const sgz_pcm_stream *s) { return s ? s->ovOpen : 0; }
+
+sgz_status sgz_pcm_stream_set_option(sgz_pcm_stream *s, uint32_t option, uint32_t value)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    return sgz_plan_set_option(s->plan, option, value);
+}
+
+sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush, uint8_t *rgba_out, float *peaks_out,
+                                        uint64_t capacity_columns, uint64_t *columns_out, sgz_pcm_timing *timing)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: null pcm");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
+    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: k differs from the open column's -- flush or reset first");
+    uint64_t need = 0;
+    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
+    if (columns_out) *columns_out = need;
+    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)");
+    if (timing) *timing = sgz_pcm_timing{};
+    const uint32_t W = s->cfg.window_size, hop = s->cfg.hop, P = s->cfg.axis_points, C = s->cfg.num_pairs;
+    const bool pcmPinned = nsamples && isPinnedHost(pcm);
+    const bool rgbaPinned = need && rgba_out && isPinnedHost(rgba_out), peaksPinned = need && peaks_out && isPinnedHost(peaks_out);
+    // the most columns one piece can close: floor((k - 1 + maxFrames) / k) = ceil(maxFrames / k), and one more from a flush
+    const size_t slotColumns = (s->maxFrames + k - 1) / k + 1;
+    if (!s->d_ovCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_ovCarry), size_t(C) * P * sizeof(float)));
+    for (PcmSlot &sl : s->slot) {                                 // (both slots are idle between feeds)
+        if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s->chunk * s->frameBytes, hipHostMallocDefault));
+        sgz_status st = SGZ_OK;
+        if (!need) continue;                                      // (no column closes: nothing is written or read back)
+        if (rgba_out && (st = pcmGrow(&sl.d_ovRgba, &sl.ovRgbaCap, slotColumns, size_t(P) * 4, false)) != SGZ_OK) return st;
+        if (rgba_out && !rgbaPinned && (st = pcmGrow(&sl.h_ovRgba, &sl.ovRgbaPinnedCap, slotColumns, size_t(P) * 4, true)) != SGZ_OK) return st;
+        if (peaks_out && (st = pcmGrow(&sl.d_ovPeaks, &sl.ovPeaksCap, slotColumns, size_t(C) * P * sizeof(float), false)) != SGZ_OK) return st;
+        if (peaks_out && !peaksPinned && (st = pcmGrow(&sl.h_ovPeaks, &sl.ovPeaksPinnedCap, slotColumns, size_t(C) * P * sizeof(float), true)) != SGZ_OK) return st;
+    }
+    const uint8_t *src = static_cast<const uint8_t *>(pcm);
+    uint64_t columnsDone = 0, chunks = 0;
+    // (a feed without samples still has one piece when it flushes an open column)
+    for (size_t at = 0; at < nsamples || (chunks == 0 && flush && s->ovOpen); ) {
+        const size_t n = std::min(s->chunk, nsamples - at);
+        const bool last = at + n == nsamples;
+        PcmSlot &sl = s->slot[s->pieces & 1];
+        if (sgz_status st = pcmDrain(sl, timing); st != SGZ_OK) return st;          // the one wait inside a feed: the piece before last
+        uint64_t frames = 0, keep = 0;
+        if (sgz_status st = streamStep(W, hop, s->held, n, &frames, &keep); st != SGZ_OK) return st;
+        sl.timed = timing != nullptr;
+        // 1. upload
+        if (n) {
+            const size_t bytes = n * s->frameBytes;
+            const void *from = src + at * s->frameBytes;
+            if (!pcmPinned) { std::memcpy(sl.h_pcm, from, bytes); from = sl.h_pcm; }
+            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[0], s->copy));
+            SGZ_HIP(hipMemcpyAsync(sl.d_pcm, from, bytes, hipMemcpyHostToDevice, s->copy));
+            SGZ_HIP(hipEventRecord(sl.ev[1], s->copy));
+            SGZ_HIP(hipStreamWaitEvent(s->compute, sl.ev[1], 0));
+        } else if (sl.timed) {
+            SGZ_HIP(hipEventRecord(sl.ev[0], s->copy));
+            SGZ_HIP(hipEventRecord(sl.ev[1], s->copy));
+        }
+        // 2. convert behind the held tail, render what became complete slab by slab into the columns, move the new tail
+        float *planar = s->d_planar[s->cur];
+        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[2], s->compute));
+        if (n)
+            if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s->format, s->srcChannels, n, s->map, s->numChannels, planar + s->held, s->stride, s->compute); st != SGZ_OK) return st;
+        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s->compute));
+        const uint64_t total = s->held + n;
+        const int pieceFlush = flush && last;
+        const uint64_t t = s->ovOpen + frames;
+        const uint64_t columns = t / k + ((pieceFlush && t % k) ? 1u : 0u);
+        uint8_t *d_rgba = rgba_out ? sl.d_ovRgba : nullptr;
+        float *d_peaks = peaks_out ? sl.d_ovPeaks : nullptr;
+        if (frames) {
+            const sgz_status st = runOverviewSlabs(s->plan, planar, s->stride, size_t(total), long(frames), k, uint32_t(s->ovOpen), pieceFlush, s->d_ovCarry,
+                                                   s->d_state, d_rgba, d_peaks, s->compute);
+            if (st != SGZ_OK) return st;
+            if (keep) SGZ_HIP(hipMemcpy2DAsync(s->d_planar[s->cur ^ 1], s->stride * sizeof(float), planar + (total - keep), s->stride * sizeof(float),
+                                               size_t(keep) * sizeof(float), s->numChannels, hipMemcpyDeviceToDevice, s->compute));
+            s->cur ^= 1;
+        } else if (columns) {                                                      // no frame arrives and the open column is flushed
+            const sgz_status st = runOverviewColumns(s->plan->impl, nullptr, 0, k, uint32_t(s->ovOpen), 1, 0, s->d_ovCarry, d_rgba, d_peaks, s->compute);
+            if (st != SGZ_OK) return st;
+        }
+        s->held = keep;
+        s->ovOpen = pieceFlush ? 0 : t % k;
+        s->ovK = k;
+        SGZ_HIP(hipEventRecord(sl.ev[4], s->compute));
+        // 3. read back the columns that closed
+        sl.rendered = columns > 0;
+        if (columns) {
+            sl.rgbaBytes = size_t(columns) * P * 4; sl.linesBytes = size_t(columns) * C * P * sizeof(float);
+            uint8_t *rgbaAt = rgba_out ? rgba_out + size_t(columnsDone) * P * 4 : nullptr;
+            float *peaksAt = peaks_out ? peaks_out + size_t(columnsDone) * C * P : nullptr;
+            SGZ_HIP(hipStreamWaitEvent(s->back, sl.ev[4], 0));
+            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s->back));
+            if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_ovRgba, sl.d_ovRgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
+            if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaksPinned ? peaksAt : sl.h_ovPeaks, sl.d_ovPeaks, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
+            SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
+            sl.rgbaDst = (rgba_out && !rgbaPinned) ? rgbaAt : nullptr; sl.rgbaFrom = sl.h_ovRgba;
+            sl.linesDst = (peaks_out && !peaksPinned) ? peaksAt : nullptr; sl.linesFrom = sl.h_ovPeaks;
+        }
+        sl.busy = true;
+        columnsDone += columns; ++chunks; ++s->pieces; at += n;
+    }
+    for (uint64_t i = 0; i < 2; ++i)
+        if (sgz_status st = pcmDrain(s->slot[(s->pieces + i) & 1], timing); st != SGZ_OK) return st;
+    if (columns_out) *columns_out = columnsDone;
+    if (timing) {
+        timing->frames = columnsDone; timing->chunks = chunks;
+        timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return SGZ_OK;
+}
+
+sgz_status sgz_spectrogram_overview_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                        const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out, float *peaks_out, sgz_pcm_timing *timing)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!cfg || !pcm) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
+    sgz_pcm_stream *s = nullptr;
+    const uint32_t frameBytes = std::max(1u, src_channels * sgz_pcm_sample_bytes(format));
+    const size_t chunk = std::min(std::min(kPcmDefaultChunk, kPcmDefaultSlotBytes / frameBytes), std::max<size_t>(nsamples, 1));
+    if (sgz_status st = sgz_pcm_stream_create(cfg, format, src_channels, channel_map, chunk, &s); st != SGZ_OK) return st;
+    uint64_t columns = sgz_pcm_stream_columns_for(s, nsamples, k, 1);
+    sgz_status st = SGZ_SKIPPED_FRAME;
+    if (columns == 0) { if (timing) *timing = sgz_pcm_timing{}; }
+    else st = sgz_pcm_stream_feed_overview(s, pcm, nsamples, k, 1, rgba_out, peaks_out, columns, &columns, timing);
     const std::string keep = g_lastError;
     sgz_pcm_stream_destroy(s);
     g_lastError = keep;

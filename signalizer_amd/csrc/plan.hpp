@@ -162,6 +162,7 @@ struct Plan {
     // [slices][columns][pairs][P], and the host form's device copy of the peaks
     float *d_ovLines = nullptr, *d_ovCarry = nullptr, *d_ovCarryCopy = nullptr, *d_ovState = nullptr, *d_ovPartial = nullptr, *d_hostOvPeaks = nullptr;
     size_t ovLinesCap = 0, ovCarryCap = 0, ovCarryCopyCap = 0, ovStateCap = 0, ovPartialCap = 0, hostOvPeaksCap = 0;
+    float *d_ovViewIn = nullptr; size_t ovViewInCap = 0;  // sgz_overview_view_host: the device copy of the range's source columns [m][pairs][P]
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;

@@ -92,5 +92,14 @@ sgz_status runTrackPeaksLines(const Plan &p, const float *d_lines, size_t frames
 sgz_status runOverviewColumns(Plan &p, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices, float *d_carry,
                               uint8_t *d_rgba, float *d_peaks, hipStream_t stream);
 uint32_t overviewAutoSlices(long columns, uint32_t blocks, uint32_t k, size_t frames, int cus);
+// the view of kept peaks (overview.hip): d_src [m][pairs][P], the range's first source column -> cols <= m output columns; the arguments are
+// sgz_stage_overview_view's, checked by the caller; asynchronous on `stream`, plan scratch grows on demand
+sgz_status checkViewRange(uint64_t n, uint64_t x0, uint64_t x1, uint32_t outColumns, uint64_t *cols);
+sgz_status runOverviewView(Plan &p, const float *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba, float *d_peaksOut, hipStream_t stream);
+// the overview render's slab loop (api.hip): `frames` frames from d_planar behind `held` frames of an open column whose V is in d_carry; the
+// columns that close go to d_rgba / d_peaks from their first element on, the open one stays in d_carry unless `flush`.  d_state: the decay
+// state in and out, or null (from rest; kept in plan scratch between slabs).  What sgz_spectrogram_overview_device and sgz_pcm_stream share.
+sgz_status runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
+                            int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t stream);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 }  // namespace sgz
