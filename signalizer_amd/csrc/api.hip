@@ -21,6 +21,9 @@
 namespace sgz {
 
 thread_local std::string g_lastError;
+#ifdef SGZ_SCHED_SWEEP
+int g_schedule[3] = {-1, -1, -1};      // tools/unit_trace_image.py, tools/image_sched_sweep.py: nyDelay, mateDelay, mateAdjacent of a one-round image-only launch (< 0: the build's default)
+#endif
 #ifdef SGZ_DEBUG
 uint32_t g_ablate = 0;      // tools/ablate.py
 #endif
@@ -373,6 +376,17 @@ sgz_status runStft(Plan &p, const float *d_planar, size_t chStride, long frames,
             rp.nyFrames = uint32_t(std::min<long>(want, frames));
         }
         p.lastNyFrames = rp.nyFrames;
+        // the one-round shape of that launch: more channel workgroups than CUs, fewer than slots, the chip to itself -- its own start-up
+        // schedule (spectrum_real.hip "one-round shape"; kernels.hpp for the defaults).  Everything else, an sgz_render_queue lane included,
+        // keeps the rules of the long launches.
+        if (rp.nyFrames && !rp.pipelined && tasks > long(rp.roundSize >> 1) && tasks < long(rp.roundSize)) {
+            rp.mateAdjacent = SGZ_MATE_ADJACENT;
+#ifdef SGZ_SCHED_SWEEP
+            if (g_schedule[0] >= 0) rp.nyDelay = uint32_t(g_schedule[0]);
+            if (g_schedule[1] >= 0) rp.mateDelay = uint32_t(g_schedule[1]);
+            if (g_schedule[2] >= 0) rp.mateAdjacent = uint32_t(g_schedule[2]);
+#endif
+        }
 #ifdef SGZ_DEBUG
         rp.phaseClock = d_phaseClock; rp.clkUnit = g_ablate >> 16;
 #endif
@@ -1303,6 +1317,12 @@ sgz_status sgz_stage_finish_pixel(const float *d_x, float *d_y, size_t n, void *
     return SGZ_OK;
 }
 
+#ifdef SGZ_SCHED_SWEEP
+/* -DSGZ_SCHED_SWEEP builds (every -DSGZ_DEBUG build is one; not in sgz.h): the start-up schedule of the next one-round image-only launches,
+ * delays in steps of ~1 k clocks, < 0: the build's default */
+void sgz_debug_set_schedule(int ny_delay, int mate_delay, int mate_adjacent) { g_schedule[0] = ny_delay; g_schedule[1] = mate_delay; g_schedule[2] = mate_adjacent; }
+#endif
+
 #ifdef SGZ_DEBUG
 /* debug hooks of a -DSGZ_DEBUG build only (not in sgz.h): phase ablation bits, and per-phase shader clocks of one workgroup of K_A;
  * d_clocks: DEVICE uint64[16 slots x 16 waves] */
@@ -1316,6 +1336,21 @@ sgz_status sgz_debug_phase_clocks(sgz_plan *plan, const float *d_planar, size_t 
     Plan &p = plan->impl;
     const long frames = planFrames(p, nsamples);
     return runStft(p, d_planar, channel_stride, frames, d_mapped, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream), d_clocks);
+}
+
+// the launch of an image-only render (sgz_stage_nyquist's, image_only = 1) with the debug stamps
+sgz_status sgz_debug_phase_clocks_image(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples,
+                                        unsigned long long *d_clocks, void *stream)
+{
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    if ((st = ensureCap(&p.d_mapped, &p.mappedCap, size_t(frames) * p.C * p.sides * p.P)) != SGZ_OK) return st;
+    st = runStft(p, d_planar, channel_stride, frames, p.d_mapped, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream), d_clocks, /*deferLate=*/true, /*imageOnly=*/true);
+    p.lateDeferred = nullptr; p.lateFrames = 0;
+    return st;
 }
 #endif
 

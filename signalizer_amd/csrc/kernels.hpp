@@ -89,7 +89,18 @@ struct RealParams {
     uint32_t nyFrames;
     uint32_t pipelined;       // 1: other launches run beside this one (sgz_render_queue): the second generation's delayed start and the wave priorities --
                               // tuned for a launch that has the chip to itself -- are left out (tools/pipeline_depth.py: 25.5 -> 22.0 us per render at depth 3)
+    // A ONE-ROUND image-only launch (nyFrames != 0, not pipelined, #CUs < channel workgroups < roundSize: runStft's shape test; spectrum_real.hip
+    // "one-round shape"); all zero everywhere else.  Speed assumptions only: no result depends on them.
+    uint32_t mateAdjacent;    // 1: workgroups b and b + #CUs, which share a CU, take neighbouring frames (real_common.hpp unitOfIndex)
+    uint32_t nyDelay;         // -DSGZ_SCHED_SWEEP builds only (measured and dropped, NOTES.md): steps of ~1 k clocks a Nyquist workgroup sleeps
+    uint32_t mateDelay;       // ... and the second channel workgroup of a CU sleeps, before its first request
 };
+#ifndef SGZ_MATE_ADJACENT
+#define SGZ_MATE_ADJACENT 1     // compile-time default, as SGZ_STAGGER is one (spectrum_real.hip)
+#endif
+#if defined(SGZ_DEBUG) && !defined(SGZ_SCHED_SWEEP)
+#define SGZ_SCHED_SWEEP         // the start-up delays and sgz_debug_set_schedule (tools/image_sched_sweep.py, tools/unit_trace_image.py)
+#endif
 constexpr int kLowBins = 24;
 constexpr uint32_t kMaxNyFrames = 4096;   // SGZ_OPT_IMAGE_ONLY_SPLIT's largest forced size (runStft also caps it at the launch's frame count)
 hipError_t launchStftReal(const RealParams &prm, uint32_t N, hipStream_t stream);

@@ -48,15 +48,28 @@ struct UnitId { int side, pair; uint32_t task, frame, self; };
 // (unit, nb: the workgroup's index and the launch's size -- or, for a workgroup that walks over several units, the index and the number
 // of workgroups a one-unit-per-workgroup launch would have had)
 // (P: RealParams, or the same block read in place from the kernel-argument segment -- WalkParams below)
+// mates (a one-round image-only launch, RealParams::mateAdjacent): the round holds more units than CUs, and workgroups b and b + #CUs --
+// positions i and i + c of their XCD's range, c = roundSize / 16 CUs per XCD -- share a CU from the first clock and run in phase.  They
+// take NEIGHBOURING frames, whose windows share twelve of sixteen rows, instead of frames c positions apart: of an XCD's n units, k = n - c
+// are second on their CU; mates take positions 2 j and 2 j + 1 (j < k), the unmated first workgroups the positions behind them.  A
+// permutation of positions inside the XCD's own contiguous range: every unit is still taken exactly once.
 template <bool MONO, typename P>
-__device__ __forceinline__ UnitId unitOfIndex(const P &prm, uint32_t unit, const uint32_t nb)
+__device__ __forceinline__ UnitId unitOfIndex(const P &prm, uint32_t unit, const uint32_t nb, const bool mates = false)
 {
     const uint32_t rs = prm.roundSize;
     if (nb >= 64u && rs >= 8u && (rs & 7u) == 0u) {
         const uint32_t base = (unit / rs) * rs;
         const uint32_t nbr = nb - base < rs ? nb - base : rs;
-        const uint32_t x = (unit - base) & 7u, i = (unit - base) >> 3;
+        const uint32_t x = (unit - base) & 7u;
+        uint32_t i = (unit - base) >> 3;
         const uint32_t per = nbr >> 3, extra = nbr & 7u;
+        if (mates) {
+            const uint32_t c = rs >> 4, n = per + (x < extra ? 1u : 0u);
+            if ((rs & 15u) == 0u && n > c && n <= 2u * c) {
+                const uint32_t k = n - c;
+                i = i < k ? 2u * i : i >= c ? 2u * (i - c) + 1u : i + k;
+            }
+        }
         unit = base + x * per + (x < extra ? x : extra) + i;
     }
     UnitId u;

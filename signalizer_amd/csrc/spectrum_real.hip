@@ -35,14 +35,15 @@
     do {                                                                                                               \
         if (prm.phaseClock && (tid & 63) == 0 && unit == long(prm.clkUnit)) prm.phaseClock[16 * (tid >> 6) + (slot)] = __builtin_readcyclecounter(); \
     } while (0)
-// clkUnit == 0xffff: instead, every workgroup leaves (start, end) in the 100 MHz wall clock all CUs share, HW_ID and XCC_ID behind
-// the 256 phase slots: the launch's schedule (tools/unit_trace.py)
+// clkUnit == 0xffff: instead, every workgroup leaves (start, end) in the 100 MHz wall clock all CUs share, HW_ID and XCC_ID (with its
+// index in the launch in the upper word) behind the 256 phase slots: the launch's schedule (tools/unit_trace.py; an image-only launch's
+// Nyquist workgroup j stamps the odd slot 2 j + 1, which no channel workgroup of side 0 uses: tools/unit_trace_image.py)
 #define RTRACE(which)                                                                                                  \
     do {                                                                                                               \
         if (prm.phaseClock && prm.clkUnit == 0xffffu && tid == 0) {                                                    \
             unsigned long long *t = prm.phaseClock + 256 + 4 * unit;                                                   \
             t[which] = __builtin_amdgcn_s_memrealtime();                                                               \
-            if (which == 0) { t[2] = __builtin_amdgcn_s_getreg(4 | (31 << 11)); t[3] = __builtin_amdgcn_s_getreg(20 | (31 << 11)); } \
+            if (which == 0) { t[2] = __builtin_amdgcn_s_getreg(4 | (31 << 11)); t[3] = __builtin_amdgcn_s_getreg(20 | (31 << 11)) | (static_cast<unsigned long long>(blockIdx.x) << 32); } \
         }                                                                                                              \
     } while (0)
 #else
@@ -187,6 +188,13 @@ __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, c
 {
     constexpr int LR = 5, R = 32, R1 = 1 << LR1, RR = R * R;
     static_assert(LR1 == 4, "the Nyquist workgroups mirror the two-columns-per-thread form (N = 32768)");
+    [[maybe_unused]] const long unit = 2 * long(light) + 1;                      // (debug stamps)
+    RTRACE(0);
+#ifdef SGZ_SCHED_SWEEP
+    // one-round shape (stftRealKernel, below), measured and dropped: the role starts late, so that the channel workgroups' first burst of
+    // requests has HBM and the CUs' fetch paths to itself; a fixed, bounded sleep -- nobody is waited for
+    for (uint32_t k = 0; k < prm.nyDelay; ++k) __builtin_amdgcn_s_sleep(16);      // (16 x 64 clocks per step)
+#endif
     const uint32_t F = prm.nyFrames, perPair = uint32_t(prm.frames) / F + (uint32_t(prm.frames) % F != 0u);     // (runStft: 1 <= F <= frames)
     const uint32_t pair = light / perPair, f0 = (light - pair * perPair) * F;
     const uint32_t f1 = f0 + F < uint32_t(prm.frames) ? f0 + F : uint32_t(prm.frames);
@@ -235,6 +243,7 @@ __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, c
             prm.ny[((size_t(f) * prm.C + pair) << 1) | 1u] = 2.f * (s[0].x - s[0].y);   // as the channel workgroup stores it (the transform runs on x w / 2)
         }
     }
+    RTRACE(1);
 }
 
 // MONO: SpectrumChannels Left / Right / Merge / Side -- ONE real signal per (frame, pair) (the reference transforms it as a complex frame
@@ -273,16 +282,33 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     const uint32_t totalUnits = WALK ? uint32_t(launchPrm.frames) * launchPrm.C * 2u : heavyUnits;
     uint32_t walkIndex = blockIdx.x;
     // (frame, pair, channel) or (frame, pair); real_common.hpp.  SIDE0: the (frame, pair) order of the mono modes, side 0, the same `self`
-    UnitId uid = unitOfIndex<MONO || SIDE0>(launchPrm, walkIndex, totalUnits);
+    UnitId uid = unitOfIndex<MONO || SIDE0>(launchPrm, walkIndex, totalUnits, SIDE0 && launchPrm.mateAdjacent != 0u);
     [[maybe_unused]] bool firstUnit = true;
-    // Wave priorities for a launch of two full dispatch generations and a partial third (cfg2: 696 workgroups on 256 CUs, two resident
-    // per CU).  tools/unit_trace.py: workgroups b and b + #CUs share a CU, the third generation starts in the slots the first frees
-    // and the launch ends when IT ends; its workgroups share their CU with second-generation ones that have ~10 us of slack.  Third
-    // generation at priority 3, first at 2, second at 1: -0.6 us of a 28.7 us launch at the sustained clock (tools/ab3.sh; every
-    // assignment with the last generation on top measures within 0.1 us of this one, 3 / 0 / 3 half the gain, 3 / 0 / 0 a loss).
-    // Longer launches are left alone.  (A speed assumption only.)  Both rules count the whole grid, an image-only launch's Nyquist workgroups
-    // (SIDE0) included: counting channel workgroups only measured 0.1 - 0.2 us slower at 480 and 500 frames, where the two differ (cfg2's 464
-    // workgroups take neither rule either way).
+    // ---- How a launch starts, by its shape.  A CU holds two of these workgroups, so a launch has `roundSize` = 2 #CUs slots per dispatch
+    // generation, and workgroups b and b + #CUs share a CU (tools/unit_trace.py, tools/unit_trace_image.py).  Every rule below is a speed
+    // assumption only and stands aside in a launch that shares the chip (sgz_render_queue, RealParams::pipelined: the delay and the
+    // priorities cost 3.5 us per render there, tools/pipeline_depth.py).
+    // LONG launches (the two-channel form: cfg2 is 696 workgroups = two full generations and a partial third):
+    //   * the second generation starts late (SGZ_STAGGER, below: launches with a FULL second generation);
+    //   * wave priorities, for launches of two full generations and a partial third: the third generation starts in the slots the first
+    //     frees and the launch ends when IT ends; its workgroups share their CU with second-generation ones that have ~10 us of slack.
+    //     Third generation at priority 3, first at 2, second at 1: -0.6 us of a 28.7 us launch at the sustained clock (tools/ab3.sh; every
+    //     assignment with the last generation on top measures within 0.1 us of this one, 3 / 0 / 3 half the gain, 3 / 0 / 0 a loss).
+    //     Longer launches are left alone.
+    //   Both count the whole grid, an image-only launch's Nyquist workgroups (SIDE0) included: counting channel workgroups only measured
+    //   0.1 - 0.2 us slower at 480 and 500 frames, where the two differ.
+    // The ONE-ROUND shape (an image-only launch with #CUs < channel workgroups < roundSize: cfg2 is 348 channel and 116 Nyquist workgroups
+    // on 512 slots; runStft's shape test, RealParams::mateAdjacent): one generation, three classes of CU -- 92 with two channel workgroups
+    // from the first clock, 116 with a channel and a Nyquist workgroup, 48 with one channel workgroup alone.  The trace (profiles/r07a,
+    // input from HBM): the doubled CUs end the launch -- their second workgroups end at 24.3 .. 29.0 us, the Nyquist workgroups at 18.1 ..
+    // 24.2, the CUs with one channel workgroup by 17.2 .. 21.8.  Neither long-launch rule applies (464 < 2 #CUs).  What it takes instead:
+    //   * MATES ON NEIGHBOURING FRAMES (real_common.hpp unitOfIndex): b and b + #CUs run in phase and ask, within a few hundred clocks of
+    //     each other and through one L1, for windows that now share twelve of sixteen rows instead of none (they were 32 frames apart).
+    //     cfg2: K_A 19.88 -> 19.21 us under rocprofv3 with the input from HBM (20.6 -> 19.6 us with its 2.8 KB copy on the sweep's box),
+    //     +-0 ... -0.1 us with the input cache-resident.
+    //   Measured and dropped (NOTES.md; -DSGZ_SCHED_SWEEP builds keep them for tools/image_sched_sweep.py): a late start of the Nyquist
+    //   workgroups (0 .. 8 k clocks: +-0.1 us) and of the second channel workgroup of a CU (1 .. 2 k: +-0.1 us; 4 k: +0.7 us, 6 k: +1.3 us with
+    //   the input cache-resident; the 10 k of the long-launch rule is half a workgroup's life here).
     if constexpr (LR1 == 4) {
         const uint32_t cus = launchPrm.roundSize >> 1;
         // The two workgroups that share a CU from the first clock of a launch (b and b + #CUs) would run IN PHASE -- both fetching, both in
@@ -297,8 +323,11 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
 #pragma unroll
             for (int k = 0; k < SGZ_STAGGER; ++k) __builtin_amdgcn_s_sleep(32);      // (32 x 64 clocks per step)
         }
-        // (both are for a launch that has the chip to itself: with other launches beside it -- sgz_render_queue -- the delay and the priorities
-        // cost 3.5 us per render, tools/pipeline_depth.py; RealParams::pipelined)
+#ifdef SGZ_SCHED_SWEEP
+        else if (SIDE0 && blockIdx.x >= cus) {      // one-round shape, measured and dropped: the second channel workgroup of a CU starts out of phase
+            for (uint32_t k = 0; k < launchPrm.mateDelay; ++k) __builtin_amdgcn_s_sleep(16);      // (16 x 64 clocks per step; 0 outside the shape window)
+        }
+#endif
 #ifndef SGZ_NO_PRIO
         if (cus && !launchPrm.pipelined && gridDim.x > 2u * cus && gridDim.x <= 3u * cus) {
 #else
