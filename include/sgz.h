@@ -43,6 +43,9 @@ extern "C" {
  *  overview inside the PCM stream (sgz_pcm_stream_feed_overview, sgz_pcm_stream_columns_for, sgz_pcm_stream_open_frames,
  *  sgz_pcm_stream_set_option, sgz_spectrogram_overview_pcm).  No struct changed and the suite pins 5; the one new refusal on an existing call, sgz_pcm_stream_feed
  *  while an overview column is open, cannot be reached without the new calls.  A binding that needs them looks the symbols up.)
+ * (5, later: the waveform lane -- sgz_stage_wave_columns, sgz_wave_columns_limits and, on the PCM stream, sgz_pcm_stream_set_waveform,
+ *  sgz_pcm_stream_waveform_for, sgz_pcm_stream_waveform_state, sgz_pcm_stream_flush_waveform.  No existing entry point or struct changed and
+ *  the suite pins 5; a stream that was never armed enqueues what it did before.  A binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -552,6 +555,60 @@ sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar
                                            uint8_t *d_rgba, float *d_peaks, float *d_state, void *stream);
 sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
                                          uint8_t *rgba_out, float *peaks_out, sgz_timing *timing);
+
+/* The waveform lane: a minimum and a maximum per screen column and channel of a file's samples -- what every editor draws beside the
+ * spectrogram lane -- reduced on the device from the planar floats the streamed render has there anyway.  The reference has no counterpart
+ * (its Oscilloscope draws a live ring, never a file; sgz_scope_dense_* is that ring's reduction).
+ * Definition (exact, no tolerance): let x[d][i] be the fp32 samples of channel d < channels, S their count so far and m >= 1 the samples per
+ * column.  Column c covers samples c m <= i < min((c + 1) m, S); only a flushed last column may be partial.  Wv[c][d] = (lo, hi): lo the
+ * least and hi the greatest of the column's non-NaN samples under the overview's total order (above: bits ^ (sign ? 0xFFFFFFFF :
+ * 0x80000000) compared as unsigned; NaNs take no part; -0 < +0); a column of NaNs alone gives lo = hi = 0x7FC00000.  The results are the
+ * samples' own bits: denormals, +-inf and -0 are kept.  Layout float2 [columns][channels].  Least and greatest under a total order are
+ * associative, so any cut of the stream (calls, pieces, feeds) or of a column (lanes, slices) gives the same bits; a coarser column is the
+ * fold of the finer ones it covers (lo of the los, hi of the his), which is how a host zooms kept columns out.  The counts are
+ * sgz_overview_step's with samples in the place of frames: (m, held, nsamples, flush) -> columns, held_out.
+ *  sgz_stage_wave_columns  DEVICE pointers.  d_planar [channels][channel_stride], the first nsamples of each row (any 4-byte-aligned address).
+ *                      held: samples of the open column that earlier calls took (< m).  d_carry: DEVICE float2 [channels], the open
+ *                      column's (lo, hi) so far -- read iff held > 0, written iff samples stay open afterwards (no flush, (held +
+ *                      nsamples) % m != 0), NULL allowed when neither applies; a carried column continues exactly as if its samples had
+ *                      come in one call.  d_wave: DEVICE float2 [columns][channels], columns as sgz_overview_step counts them (NULL
+ *                      allowed when none closes).  nsamples == 0 with held > 0 and flush: one column from the carry alone.  m up to
+ *                      the switch-over (1024; sgz_wave_columns_limits) runs one workgroup per (channel, tile of 4096 / m whole columns);
+ *                      longer columns are reduced in slices per column into scratch and folded by a second launch.  slices: 0 = the
+ *                      library's choice (m above the switch-over: the fewest slices that give two workgroups per CU), 1 .. 64 forced
+ *                      -- 2 and more take the sliced form whatever m is, 1 takes the form m implies -- identical bits.  Only the
+ *                      documented bytes are written.  Asynchronous on `stream`, nothing is waited for; scratch is allocated and freed in
+ *                      stream order.  SGZ_EINVAL, nothing launched or written: a null d_planar, channels == 0 or > 64, m == 0, held >= m,
+ *                      channel_stride < nsamples, slices > 64, a needed d_carry or d_wave that is NULL, d_planar not aligned to 4
+ *                      bytes, d_carry or d_wave not aligned to 8.  nsamples == 0 with nothing to flush: SGZ_OK, nothing launched.
+ *  sgz_wave_columns_limits  the switch-over and the tile's samples (either result may be NULL).
+ * The lane inside the sgz_pcm_stream handle -- above, "interleaved PCM in": while armed, every feed of either kind also reduces the new samples of
+ * each piece -- the stream's converted floats, exactly sgz_pcm_to_planar_device's -- on the compute stream behind the conversion, and
+ * reads the columns that closed back on the read-back stream into wave_out at a cursor.  The columns of all feeds and the final flush,
+ * concatenated, are Wv of the stream's converted floats bit for bit, however it is cut into feeds and pieces and whichever kind the feeds
+ * are; the image, lines, overview and peaks of an armed stream are those of an unarmed one byte for byte.
+ *  sgz_pcm_stream_set_waveform   between feeds.  m > 0 arms: wave_out HOST float2 [capacity_columns][channels] (channels = 2 num_pairs;
+ *                      pinned memory is written in place, pageable memory through a pinned twin per slot), the cursor restarts at 0.
+ *                      The same m with another buffer keeps the open column: how a caller with a small buffer drains.  m == 0 disarms
+ *                      and drops the open column.  SGZ_EINVAL: a null stream, a null wave_out with capacity_columns > 0, another m
+ *                      while samples are open.
+ *  sgz_pcm_stream_waveform_for   columns the next feed of nsamples closes (flush != 0: that feed followed by sgz_pcm_stream_flush_waveform);
+ *                      0 when disarmed.
+ *  sgz_pcm_stream_waveform_state columns written since the lane was armed (the cursor) and the open column's samples; either may be NULL.
+ *  sgz_pcm_stream_flush_waveform closes the open column: one launch on the carry, one column read back, waits.  Nothing open: SGZ_OK,
+ *                      nothing done.  SGZ_EINVAL: disarmed, no column left in the buffer.
+ * A feed that would close more columns than the buffer has left is refused with SGZ_EINVAL before anything is consumed.  reset drops the
+ * open column and restarts the cursor.  Per slot the columns of a piece take ceil(chunk_samples / m) + 1 columns of device (and, for a
+ * pageable buffer, pinned) memory, made on first need and grown when a later m needs more: memory is bounded by chunk_samples and m. */
+sgz_status sgz_stage_wave_columns(const float *d_planar, size_t channel_stride, uint32_t channels, size_t nsamples, uint32_t m, uint32_t held,
+                                  int flush, uint32_t slices, float *d_carry /*float2 [channels]*/, float *d_wave /*float2 [columns][channels]*/,
+                                  void *stream);
+void       sgz_wave_columns_limits(uint32_t *switch_over, uint32_t *tile_samples);
+sgz_status sgz_pcm_stream_set_waveform(sgz_pcm_stream *s, uint32_t m /*0 = off*/, float *wave_out /*HOST float2 [capacity][channels]*/,
+                                       uint64_t capacity_columns);
+uint64_t   sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
+sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
+sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s);
 
 /* The view of kept peaks: any range of kept V at any width and in any colours, one small launch -- what a host calls per redraw of a file
  * lane (zoom, pan, resize, another gradient) instead of rendering the file again.

@@ -195,6 +195,8 @@ EXPORTS = [
     "sgz_overview_view_columns", "sgz_stage_overview_view", "sgz_overview_view_host",
     "sgz_pcm_stream_feed_overview", "sgz_pcm_stream_columns_for", "sgz_pcm_stream_open_frames", "sgz_spectrogram_overview_pcm",
     "sgz_pcm_stream_set_option",
+    "sgz_stage_wave_columns", "sgz_wave_columns_limits", "sgz_pcm_stream_set_waveform", "sgz_pcm_stream_waveform_for",
+    "sgz_pcm_stream_waveform_state", "sgz_pcm_stream_flush_waveform",
 ]
 
 
@@ -410,6 +412,14 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_open_frames.argtypes = [vp]
     L.sgz_pcm_stream_open_frames.restype = u64
     L.sgz_pcm_stream_set_option.argtypes = [vp, u32, u32]
+    L.sgz_stage_wave_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
+    L.sgz_wave_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    L.sgz_wave_columns_limits.restype = None
+    L.sgz_pcm_stream_set_waveform.argtypes = [vp, u32, vp, u64]
+    L.sgz_pcm_stream_waveform_for.argtypes = [vp, sz, C.c_int]
+    L.sgz_pcm_stream_waveform_for.restype = u64
+    L.sgz_pcm_stream_waveform_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.sgz_pcm_stream_flush_waveform.argtypes = [vp]
     L.sgz_spectrogram_overview_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, C.POINTER(PcmTiming)]
     _lib = L
     return L
@@ -1145,6 +1155,48 @@ class PcmStream:
         check(st)
         assert c == cols, (c, cols)
         return (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
+
+
+    # the waveform lane: (lo, hi) per column of m samples and channel, beside whatever the feeds render
+    def set_waveform(self, m: int, out=None, capacity_columns: int | None = None) -> None:
+        """sgz_pcm_stream_set_waveform: out -- a float32 numpy array or host torch tensor [capacity, channels, 2] (kept alive here; pinned
+        memory is written in place); m == 0 disarms"""
+        if capacity_columns is None:
+            capacity_columns = 0 if out is None else int(out.shape[0])
+        check(lib().sgz_pcm_stream_set_waveform(self.h, m, _buf_ptr(out) if out is not None and m else None, capacity_columns if m else 0))
+        self._wave_out = out if m else None
+
+    def waveform_for(self, nsamples: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_waveform_for: waveform columns the next feed of nsamples closes"""
+        return int(lib().sgz_pcm_stream_waveform_for(self.h, nsamples, int(bool(flush))))
+
+    def waveform_state(self):
+        """sgz_pcm_stream_waveform_state: (columns written since the lane was armed, samples of the open column)"""
+        c, o = C.c_uint64(0), C.c_uint64(0)
+        check(lib().sgz_pcm_stream_waveform_state(self.h, C.byref(c), C.byref(o)))
+        return int(c.value), int(o.value)
+
+    def flush_waveform(self) -> None:
+        """sgz_pcm_stream_flush_waveform: closes the open column (one more column at the cursor); waits"""
+        check(lib().sgz_pcm_stream_flush_waveform(self.h))
+
+
+def wave_columns_limits():
+    """sgz_wave_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples)"""
+    s, t = C.c_uint32(0), C.c_uint32(0)
+    lib().sgz_wave_columns_limits(C.byref(s), C.byref(t))
+    return int(s.value), int(t.value)
+
+
+def stage_wave_columns(planar, channel_stride: int, channels: int, nsamples: int, m: int, held: int = 0, flush: bool = True, slices: int = 0,
+                       carry=None, wave=None, stream=None) -> int:
+    """sgz_stage_wave_columns as it is: planar / carry / wave -- cuda float32 tensors (their data pointers; any may be None where the call
+    allows NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    return lib().sgz_stage_wave_columns(ptr(planar), channel_stride, channels, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(wave),
+                                        C.c_void_p(s) if s else None)
 
 
 def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,

@@ -19,6 +19,7 @@
 
 #include "runtime.hpp"
 #include "decay_body.hpp"
+#include "order_key.hpp"       // orderKey / keyBits
 
 #pragma clang fp contract(off)
 
@@ -45,17 +46,6 @@ struct OverviewParams {
     const float *colourTables;
     DeviceScalars sc;
 };
-
-__device__ __forceinline__ uint32_t orderKey(uint32_t bits)
-{
-    if ((bits & 0x7fffffffu) > 0x7f800000u) return 0u;                          // a NaN takes no part
-    return bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ uint32_t keyBits(uint32_t key)
-{
-    if (key == 0u) return 0x7fc00000u;                                          // nothing but NaNs
-    return key ^ ((key >> 31) ? 0x80000000u : 0xffffffffu);
-}
 
 // frames [a, b) of this call that belong to column `col`
 __device__ __forceinline__ void columnFrames(const OverviewParams &prm, long col, long &a, long &b)

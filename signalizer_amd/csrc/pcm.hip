@@ -1,5 +1,6 @@
 // pcm.hip -- interleaved PCM in (include/sgz.h "interleaved PCM in"): the convert-and-de-interleave kernel, and the stream handle that
-// cuts a feed into pieces and runs upload / convert + render / read-back of neighbouring pieces side by side on three streams.
+// cuts a feed into pieces and runs upload / convert + render / read-back of neighbouring pieces side by side on three streams; armed, the
+// waveform lane (wave_columns.hip) reduces every piece's new samples behind the converter and its columns ride the same read-back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +10,7 @@
 
 #include "rt_common.hpp"       // isPinnedHost
 #include "runtime.hpp"
+#include "scope_ring.hpp"     // StreamScratch
 
 namespace sgz {
 
@@ -199,7 +201,7 @@ struct PcmSlot {                        // what one piece in flight owns; a slot
                                         // (the capitals order the streams; the others are recorded for a caller that asks for timing only: a
                                         // marker costs the stream it sits on microseconds, api.hip sgz_render_queue_submit)
     bool timed = false;
-    bool busy = false, rendered = false;
+    bool busy = false, rendered = false;            // rendered: the piece has a read-back (frames, overview or waveform columns), ev[6] is recorded
     // the host's part of the read-back, done when the slot is drained
     uint8_t *rgbaDst = nullptr; float *linesDst = nullptr; size_t rgbaBytes = 0, linesBytes = 0;
     const uint8_t *rgbaFrom = nullptr; const float *linesFrom = nullptr;       // the pinned twins the drain copies from
@@ -207,6 +209,10 @@ struct PcmSlot {                        // what one piece in flight owns; a slot
     // first need and grown when a later k needs more columns per piece
     uint8_t *d_ovRgba = nullptr, *h_ovRgba = nullptr; float *d_ovPeaks = nullptr, *h_ovPeaks = nullptr;
     size_t ovRgbaCap = 0, ovRgbaPinnedCap = 0, ovPeaksCap = 0, ovPeaksPinnedCap = 0;       // columns
+    // the waveform lane's columns of one piece (sgz_pcm_stream_set_waveform): float2 [waveCap][channels] with its pinned twin, made on first
+    // need and grown when a later m needs more columns per piece; waveDst: where the drain copies the twin's waveBytes to
+    float *d_wave = nullptr, *h_wave = nullptr, *waveDst = nullptr;
+    size_t waveCap = 0, wavePinnedCap = 0, waveBytes = 0;
 };
 }  // namespace
 
@@ -225,6 +231,14 @@ struct sgz_pcm_stream {
     // the overview inside the stream: the open column's V [pairs][P], its frame count and its k (meaningful while ovOpen > 0)
     float *d_ovCarry = nullptr;
     uint64_t ovOpen = 0; uint32_t ovK = 0;
+    // the waveform lane (m > 0: armed): the caller's columns and the cursor in them, the open column's sample count and its (lo, hi) per channel
+    // in d_wvCarry [2][channels] float2 -- a piece reads half wvCur and writes the other, so no launch reads what it writes
+    uint32_t wvM = 0;
+    float *wvOut = nullptr;
+    uint64_t wvCap = 0, wvCursor = 0, wvOpen = 0;
+    bool wvPinned = false;
+    float *d_wvCarry = nullptr;
+    int wvCur = 0;
 };
 
 struct sgz_plan { Plan impl; };
@@ -240,7 +254,8 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
     SGZ_HIP(hipEventSynchronize(sl.ev[sl.rendered ? 6 : 4]));
     if (sl.rgbaDst) std::memcpy(sl.rgbaDst, sl.rgbaFrom, sl.rgbaBytes);
     if (sl.linesDst) std::memcpy(sl.linesDst, sl.linesFrom, sl.linesBytes);
-    sl.rgbaDst = nullptr; sl.linesDst = nullptr;
+    if (sl.waveDst) std::memcpy(sl.waveDst, sl.h_wave, sl.waveBytes);
+    sl.rgbaDst = nullptr; sl.linesDst = nullptr; sl.waveDst = nullptr;
     if (timing && sl.timed) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, sl.ev[0], sl.ev[1]) == hipSuccess) timing->h2d_ms += ms;
@@ -260,6 +275,57 @@ static sgz_status pcmGrow(T **buf, size_t *cap, size_t need, size_t bytes, bool 
     if (pinned) SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(buf), need * bytes, hipHostMallocDefault));
     else SGZ_HIP(hipMalloc(reinterpret_cast<void **>(buf), need * bytes));
     *cap = need;
+    return SGZ_OK;
+}
+
+// ---- the waveform lane inside the stream (sgz.h, "The waveform lane") -----------------------------------------------------------------------
+static float *pcmWaveCarry(const sgz_pcm_stream &s, int half) { return s.d_wvCarry + size_t(half) * 2 * s.numChannels; }
+
+// what a feed checks for the lane before anything is consumed: the columns its samples close fit behind the cursor
+static sgz_status pcmWaveFits(const sgz_pcm_stream &s, size_t nsamples)
+{
+    if (s.wvM && (s.wvOpen + nsamples) / s.wvM > s.wvCap - s.wvCursor)
+        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed closes more waveform columns than the buffer has left (sgz_pcm_stream_waveform_for; re-arm with sgz_pcm_stream_set_waveform)");
+    return SGZ_OK;
+}
+
+// a slot's columns of a piece, ceil(chunk / m) + 1 of them (both slots are idle between feeds)
+static sgz_status pcmWaveBuffers(sgz_pcm_stream &s, PcmSlot &sl)
+{
+    if (!s.wvM) return SGZ_OK;
+    const size_t columns = (s.chunk + s.wvM - 1) / s.wvM + 1, bytes = size_t(s.numChannels) * 2 * sizeof(float);
+    if (sgz_status st = pcmGrow(&sl.d_wave, &sl.waveCap, columns, bytes, false); st != SGZ_OK) return st;
+    return s.wvPinned ? SGZ_OK : pcmGrow(&sl.h_wave, &sl.wavePinnedCap, columns, bytes, true);
+}
+
+// the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the columns they close, into the slot;
+// the open one into the carry
+static sgz_status pcmWavePiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
+{
+    *columns = 0;
+    if (!s.wvM || n == 0) return SGZ_OK;
+    const WaveColumnsShape sh = waveColumnsShape(s.numChannels, n, s.wvM, uint32_t(s.wvOpen), 0, 0);
+    StreamScratch scratch(s.compute);
+    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
+    const sgz_status st = runWaveColumns(sh, fresh, s.stride, s.numChannels, n, s.wvM, uint32_t(s.wvOpen), pcmWaveCarry(s, s.wvCur), pcmWaveCarry(s, s.wvCur ^ 1),
+                                         sl.d_wave, scratch.p, s.compute);
+    if (st != SGZ_OK) return st;
+    if (sh.open) s.wvCur ^= 1;
+    s.wvOpen = (s.wvOpen + n) % s.wvM;
+    *columns = sh.closed;
+    return SGZ_OK;
+}
+
+// the piece's columns to the caller's buffer at the cursor, on the read-back stream (behind ev[4]); pageable: to the twin, the drain copies
+static sgz_status pcmWaveReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
+{
+    if (!columns) return SGZ_OK;
+    const size_t column = size_t(s.numChannels) * 2;
+    float *at = s.wvOut + size_t(s.wvCursor) * column;
+    sl.waveBytes = size_t(columns) * column * sizeof(float);
+    SGZ_HIP(hipMemcpyAsync(s.wvPinned ? at : sl.h_wave, sl.d_wave, sl.waveBytes, hipMemcpyDeviceToHost, s.back));
+    sl.waveDst = s.wvPinned ? nullptr : at;
+    s.wvCursor += columns;
     return SGZ_OK;
 }
 
@@ -285,11 +351,11 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
     if (!s) return;
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamSynchronize(q);
     for (PcmSlot &sl : s->slot) {
-        for (void *p : {sl.h_pcm, (void *)sl.h_rgba, (void *)sl.h_lines, (void *)sl.h_ovRgba, (void *)sl.h_ovPeaks}) if (p) (void)hipHostFree(p);
-        for (void *p : {sl.d_pcm, (void *)sl.d_rgba, (void *)sl.d_lines, (void *)sl.d_ovRgba, (void *)sl.d_ovPeaks}) if (p) (void)hipFree(p);
+        for (void *p : {sl.h_pcm, (void *)sl.h_rgba, (void *)sl.h_lines, (void *)sl.h_ovRgba, (void *)sl.h_ovPeaks, (void *)sl.h_wave}) if (p) (void)hipHostFree(p);
+        for (void *p : {sl.d_pcm, (void *)sl.d_rgba, (void *)sl.d_lines, (void *)sl.d_ovRgba, (void *)sl.d_ovPeaks, (void *)sl.d_wave}) if (p) (void)hipFree(p);
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
     if (s->plan) sgz_plan_destroy(s->plan);
     delete s;
@@ -344,6 +410,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     SGZ_HIP(hipStreamSynchronize(s->compute));
     s->held = 0;
     s->ovOpen = 0;                                                                  // an open overview column is dropped
+    s->wvOpen = 0; s->wvCursor = 0;                                                 // and the waveform's; its columns start over
     return SGZ_OK;
 }
 
@@ -358,6 +425,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     if (frames_out) *frames_out = need;
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
     if (need && !rgba_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null rgba_out");
+    if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
     if (timing) *timing = sgz_pcm_timing{};
     const uint32_t W = s->cfg.window_size, hop = s->cfg.hop, P = s->cfg.axis_points;
     const bool pcmPinned = nsamples && isPinnedHost(pcm);
@@ -369,6 +437,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
         if (need && lines_out && !sl.d_lines) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&sl.d_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float)));
         if (need && lines_out && !linesPinned && !sl.h_lines)
             SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float), hipHostMallocDefault));
+        if (sgz_status st = pcmWaveBuffers(*s, sl); st != SGZ_OK) return st;
     }
     const uint8_t *src = static_cast<const uint8_t *>(pcm);
     uint64_t framesDone = 0, chunks = 0;
@@ -392,8 +461,10 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
         if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[2], s->compute));
         if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s->format, s->srcChannels, n, s->map, s->numChannels, planar + s->held, s->stride, s->compute); st != SGZ_OK) return st;
         if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s->compute));
+        uint64_t waveColumns = 0;
+        if (sgz_status st = pcmWavePiece(*s, sl, planar + s->held, n, &waveColumns); st != SGZ_OK) return st;
         const uint64_t total = s->held + n;
-        sl.rendered = frames > 0;
+        sl.rendered = frames > 0 || waveColumns > 0;               // (a piece may close waveform columns and complete no frame)
         if (frames) {
             const sgz_status st = sgz_spectrogram_render_device(s->plan, planar, s->stride, size_t(total), sl.d_rgba, lines_out ? sl.d_lines : nullptr, s->d_state, s->compute);
             if (st != SGZ_OK) return st;
@@ -404,17 +475,20 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
         s->held = keep;
         SGZ_HIP(hipEventRecord(sl.ev[4], s->compute));
         // 3. read back
-        if (frames) {
-            sl.rgbaBytes = size_t(frames) * P * 4; sl.linesBytes = pcmLinesFloats(*s, frames) * sizeof(float);
-            uint8_t *rgbaAt = rgba_out + size_t(framesDone) * P * 4;
-            float *linesAt = lines_out ? lines_out + pcmLinesFloats(*s, framesDone) : nullptr;
+        if (sl.rendered) {
             SGZ_HIP(hipStreamWaitEvent(s->back, sl.ev[4], 0));
             if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s->back));
-            SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_rgba, sl.d_rgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
-            if (lines_out) SGZ_HIP(hipMemcpyAsync(linesPinned ? linesAt : sl.h_lines, sl.d_lines, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
+            if (frames) {
+                sl.rgbaBytes = size_t(frames) * P * 4; sl.linesBytes = pcmLinesFloats(*s, frames) * sizeof(float);
+                uint8_t *rgbaAt = rgba_out + size_t(framesDone) * P * 4;
+                float *linesAt = lines_out ? lines_out + pcmLinesFloats(*s, framesDone) : nullptr;
+                SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_rgba, sl.d_rgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
+                if (lines_out) SGZ_HIP(hipMemcpyAsync(linesPinned ? linesAt : sl.h_lines, sl.d_lines, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
+                sl.rgbaDst = rgbaPinned ? nullptr : rgbaAt; sl.rgbaFrom = sl.h_rgba;
+                sl.linesDst = (lines_out && !linesPinned) ? linesAt : nullptr; sl.linesFrom = sl.h_lines;
+            }
+            if (sgz_status st = pcmWaveReadBack(*s, sl, waveColumns); st != SGZ_OK) return st;
             SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
-            sl.rgbaDst = rgbaPinned ? nullptr : rgbaAt; sl.rgbaFrom = sl.h_rgba;
-            sl.linesDst = (lines_out && !linesPinned) ? linesAt : nullptr; sl.linesFrom = sl.h_lines;
         }
         sl.busy = true;
         framesDone += frames; ++chunks; ++s->pieces; at += n;
@@ -488,6 +562,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
     if (columns_out) *columns_out = need;
     if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)");
+    if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
     if (timing) *timing = sgz_pcm_timing{};
     const uint32_t W = s->cfg.window_size, hop = s->cfg.hop, P = s->cfg.axis_points, C = s->cfg.num_pairs;
     const bool pcmPinned = nsamples && isPinnedHost(pcm);
@@ -497,7 +572,8 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (!s->d_ovCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_ovCarry), size_t(C) * P * sizeof(float)));
     for (PcmSlot &sl : s->slot) {                                 // (both slots are idle between feeds)
         if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s->chunk * s->frameBytes, hipHostMallocDefault));
-        sgz_status st = SGZ_OK;
+        sgz_status st = pcmWaveBuffers(*s, sl);
+        if (st != SGZ_OK) return st;
         if (!need) continue;                                      // (no column closes: nothing is written or read back)
         if (rgba_out && (st = pcmGrow(&sl.d_ovRgba, &sl.ovRgbaCap, slotColumns, size_t(P) * 4, false)) != SGZ_OK) return st;
         if (rgba_out && !rgbaPinned && (st = pcmGrow(&sl.h_ovRgba, &sl.ovRgbaPinnedCap, slotColumns, size_t(P) * 4, true)) != SGZ_OK) return st;
@@ -534,6 +610,8 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
         if (n)
             if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s->format, s->srcChannels, n, s->map, s->numChannels, planar + s->held, s->stride, s->compute); st != SGZ_OK) return st;
         if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s->compute));
+        uint64_t waveColumns = 0;
+        if (sgz_status st = pcmWavePiece(*s, sl, planar + s->held, n, &waveColumns); st != SGZ_OK) return st;
         const uint64_t total = s->held + n;
         const int pieceFlush = flush && last;
         const uint64_t t = s->ovOpen + frames;
@@ -556,18 +634,21 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
         s->ovK = k;
         SGZ_HIP(hipEventRecord(sl.ev[4], s->compute));
         // 3. read back the columns that closed
-        sl.rendered = columns > 0;
-        if (columns) {
-            sl.rgbaBytes = size_t(columns) * P * 4; sl.linesBytes = size_t(columns) * C * P * sizeof(float);
-            uint8_t *rgbaAt = rgba_out ? rgba_out + size_t(columnsDone) * P * 4 : nullptr;
-            float *peaksAt = peaks_out ? peaks_out + size_t(columnsDone) * C * P : nullptr;
+        sl.rendered = columns > 0 || waveColumns > 0;
+        if (sl.rendered) {
             SGZ_HIP(hipStreamWaitEvent(s->back, sl.ev[4], 0));
             if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s->back));
-            if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_ovRgba, sl.d_ovRgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
-            if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaksPinned ? peaksAt : sl.h_ovPeaks, sl.d_ovPeaks, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
+            if (columns) {
+                sl.rgbaBytes = size_t(columns) * P * 4; sl.linesBytes = size_t(columns) * C * P * sizeof(float);
+                uint8_t *rgbaAt = rgba_out ? rgba_out + size_t(columnsDone) * P * 4 : nullptr;
+                float *peaksAt = peaks_out ? peaks_out + size_t(columnsDone) * C * P : nullptr;
+                if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_ovRgba, sl.d_ovRgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
+                if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaksPinned ? peaksAt : sl.h_ovPeaks, sl.d_ovPeaks, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
+                sl.rgbaDst = (rgba_out && !rgbaPinned) ? rgbaAt : nullptr; sl.rgbaFrom = sl.h_ovRgba;
+                sl.linesDst = (peaks_out && !peaksPinned) ? peaksAt : nullptr; sl.linesFrom = sl.h_ovPeaks;
+            }
+            if (sgz_status st = pcmWaveReadBack(*s, sl, waveColumns); st != SGZ_OK) return st;
             SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
-            sl.rgbaDst = (rgba_out && !rgbaPinned) ? rgbaAt : nullptr; sl.rgbaFrom = sl.h_ovRgba;
-            sl.linesDst = (peaks_out && !peaksPinned) ? peaksAt : nullptr; sl.linesFrom = sl.h_ovPeaks;
         }
         sl.busy = true;
         columnsDone += columns; ++chunks; ++s->pieces; at += n;
@@ -602,6 +683,60 @@ sgz_status sgz_spectrogram_overview_pcm(const sgz_spectrum_config *cfg, const vo
     g_lastError = keep;
     if (timing && st == SGZ_OK) timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return st;
+}
+
+// ---- the waveform lane's calls ----------------------------------------------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_set_waveform(sgz_pcm_stream *s, uint32_t m, float *wave_out, uint64_t capacity_columns)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (m == 0) {                                                  // off: the open column is dropped
+        s->wvM = 0; s->wvOut = nullptr; s->wvCap = s->wvCursor = s->wvOpen = 0;
+        return SGZ_OK;
+    }
+    if (!wave_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: null wave_out");
+    if (reinterpret_cast<uintptr_t>(wave_out) % alignof(float)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: wave_out is not aligned to float");
+    if (s->wvOpen && m != s->wvM) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: m differs from the open column's -- flush it (sgz_pcm_stream_flush_waveform), disarm or reset first");
+    if (!s->d_wvCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_wvCarry), size_t(2) * s->numChannels * 2 * sizeof(float)));
+    s->wvM = m; s->wvOut = wave_out; s->wvCap = capacity_columns; s->wvCursor = 0;
+    s->wvPinned = capacity_columns && isPinnedHost(wave_out);
+    return SGZ_OK;
+}
+
+uint64_t sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush)
+{
+    if (!s || !s->wvM) return 0;
+    const uint64_t t = s->wvOpen + nsamples;
+    return t / s->wvM + ((flush && t % s->wvM) ? 1u : 0u);
+}
+
+sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (columns_written) *columns_written = s->wvCursor;
+    if (open_samples) *open_samples = s->wvOpen;
+    return SGZ_OK;
+}
+
+sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!s->wvM) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_waveform: the lane is off (sgz_pcm_stream_set_waveform)");
+    if (!s->wvOpen) return SGZ_OK;
+    if (s->wvCursor >= s->wvCap) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_waveform: no column left in the buffer (re-arm with sgz_pcm_stream_set_waveform)");
+    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
+    if (sgz_status st = pcmWaveBuffers(*s, sl); st != SGZ_OK) return st;
+    const WaveColumnsShape sh = waveColumnsShape(s->numChannels, 0, s->wvM, uint32_t(s->wvOpen), 1, 0);
+    const sgz_status st = runWaveColumns(sh, s->d_planar[s->cur], s->stride, s->numChannels, 0, s->wvM, uint32_t(s->wvOpen), pcmWaveCarry(*s, s->wvCur),
+                                         pcmWaveCarry(*s, s->wvCur ^ 1), sl.d_wave, nullptr, s->compute);
+    if (st != SGZ_OK) return st;
+    const size_t bytes = size_t(s->numChannels) * 2 * sizeof(float);
+    float *at = s->wvOut + size_t(s->wvCursor) * s->numChannels * 2;
+    SGZ_HIP(hipMemcpyAsync(s->wvPinned ? at : sl.h_wave, sl.d_wave, bytes, hipMemcpyDeviceToHost, s->compute));
+    SGZ_HIP(hipStreamSynchronize(s->compute));
+    if (!s->wvPinned) std::memcpy(at, sl.h_wave, bytes);
+    s->wvOpen = 0;
+    ++s->wvCursor;
+    return SGZ_OK;
 }
 
 }  // extern "C"

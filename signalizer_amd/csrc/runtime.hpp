@@ -101,5 +101,16 @@ sgz_status runOverviewView(Plan &p, const float *d_src, size_t m, size_t cols, u
 // state in and out, or null (from rest; kept in plan scratch between slabs).  What sgz_spectrogram_overview_device and sgz_pcm_stream share.
 sgz_status runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
                             int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t stream);
+// the waveform lane's reduction (wave_columns.hip): (lo, hi) per column of m samples and channel, the open column in a carry; what
+// sgz_stage_wave_columns and sgz_pcm_stream share.  The arguments are the stage call's, checked by the caller; asynchronous on `stream`
+struct WaveColumnsShape {
+    uint64_t columns, closed;            // columns the call touches; those it emits
+    bool open, launch;                   // a last column stays open (it goes to the carry); anything is launched at all
+    uint32_t slices;                     // 0: the tile form
+    size_t scratchBytes;                 // partial pairs of the sliced form
+};
+WaveColumnsShape waveColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
+sgz_status runWaveColumns(const WaveColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples, uint32_t m,
+                          uint32_t held, const float *carryIn, float *carryOut, float *d_wave, void *scratch, hipStream_t stream);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 }  // namespace sgz
