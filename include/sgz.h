@@ -46,6 +46,9 @@ extern "C" {
  * (5, later: the waveform lane -- sgz_stage_wave_columns, sgz_wave_columns_limits and, on the PCM stream, sgz_pcm_stream_set_waveform,
  *  sgz_pcm_stream_waveform_for, sgz_pcm_stream_waveform_state, sgz_pcm_stream_flush_waveform.  No existing entry point or struct changed and
  *  the suite pins 5; a stream that was never armed enqueues what it did before.  A binding that needs them looks the symbols up.)
+ * (5, later: the track lane -- sgz_track_peak_values, sgz_stage_track_peaks_values and, on the PCM stream, sgz_pcm_stream_set_track,
+ *  sgz_pcm_stream_track_for, sgz_pcm_stream_track_state.  No existing entry point or struct changed and the suite pins 5; a stream that was
+ *  never armed enqueues what it did before.  A binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -511,6 +514,19 @@ sgz_status sgz_spectrogram_track_device(sgz_plan *plan, const float *d_planar, s
                                         double mouse_fraction, uint8_t *d_rgba, float *d_state, sgz_line_peak *d_track, void *stream);
 sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t graph,
                                       double mouse_fraction, uint8_t *rgba_out, sgz_line_peak *track_out, sgz_timing *timing);
+/* The line-results search on value planes: float [P] per record instead of float2 -- the layout of V / V', the peaks every overview and view
+ * call below writes (d_peaks, peaks_out, d_peaks_out: [columns][pairs][P], records = columns * pairs).  A track drawn over a zoomed-out
+ * lane is not a fold of per-frame tracks: the track that belongs on an overview or view column is the tracker applied to that column.
+ * Definition (exact, no tolerance): record r == sgz_track_peak_lines(plan, L, mouse_fraction, &out) with L[i] = (values[r][i], anything),
+ * byte for byte in all six fields (the confinement below 17 axis points, the first largest, both boundary walks, the NaN rules, the
+ * deviance floor); the plan only has to agree in axis_points.
+ *  sgz_track_peak_values         host arithmetic on a HOST record, nothing launched.  SGZ_EINVAL: a null argument, a non-finite mouse_fraction.
+ *  sgz_stage_track_peaks_values  DEVICE pointers; one workgroup per record (trackLinePeaksKernel's body on the other layout), asynchronous on
+ *                                `stream`, nothing allocated, nothing waited for.  SGZ_EINVAL, nothing launched: a null argument, a non-finite
+ *                                mouse_fraction.  records == 0: SGZ_OK, nothing launched. */
+sgz_status sgz_track_peak_values(const sgz_plan *plan, const float *values /*HOST float [P]*/, double mouse_fraction, sgz_line_peak *out);
+sgz_status sgz_stage_track_peaks_values(sgz_plan *plan, const float *d_values /*DEVICE float [records][P]*/, size_t records, double mouse_fraction,
+                                        sgz_line_peak *d_out /*DEVICE [records]*/, void *stream);
 
 /* The overview render: an image with k frames per column, reduced and coloured on the device -- what a host draws as a file's
  * spectrogram in a lane, a thumbnail or a zoomed-out view, without reading back one column per frame.  The reference has no counterpart
@@ -609,6 +625,37 @@ sgz_status sgz_pcm_stream_set_waveform(sgz_pcm_stream *s, uint32_t m /*0 = off*/
 uint64_t   sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
 sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
 sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s);
+
+/* The track lane: the tracker's curve over a file -- the reference's drawFrequencyTracking readout (SpectrumRendering.cpp:300-377, the
+ * line-results branch) for every frame of a streamed file, in bounded memory.  sgz_spectrogram_track_device / _host want the whole file
+ * resident and keep line results proportional to the frame count; this lane searches each piece's line results where the stream has
+ * them anyway.
+ * While armed, every feed of either kind (sgz_pcm_stream_feed and sgz_pcm_stream_feed_overview, any k, any flush, mixed where the rules
+ * above allow) writes one sgz_line_peak per (frame, pair) for exactly the frames that became complete (sgz_stream_step), to track_out at a
+ * cursor.  The records of all feeds, concatenated, equal sgz_spectrogram_track_host(plan, <the stream's converted planar floats>, graph,
+ * mouse_fraction, ...) byte for byte, whatever the cuts into feeds and pieces, chunk_samples and SGZ_OPT_OVERVIEW_SLAB; the image, lines,
+ * overview columns, peaks and waveform columns of an armed stream are those of an unarmed one byte for byte.  The tracker runs on the
+ * compute stream behind the piece's render (in an overview feed: behind every slab's render, on the slab's line results) and the records
+ * ride the piece's read-back: pinned track_out is written in place, pageable memory through a pinned twin per slot.
+ *  sgz_pcm_stream_set_track    between feeds.  A non-NULL track_out arms: HOST sgz_line_peak [capacity_frames][pairs].  The lane has no open
+ *                      state (records exist only for complete frames), so every call restarts the cursor at 0 and may change graph,
+ *                      mouse_fraction or the buffer: how a caller with a small buffer drains.  NULL with capacity 0 disarms.
+ *                      SGZ_EINVAL, the stream unchanged: a null stream, graph >= SGZ_NUM_GRAPHS, a non-finite mouse_fraction, a null
+ *                      track_out with capacity_frames > 0, a track_out not aligned to 8 bytes.
+ *  sgz_pcm_stream_track_for    frames whose records the next feed of nsamples writes (sgz_pcm_stream_frames_for while armed); 0 when disarmed
+ *                      or for a null stream.
+ *  sgz_pcm_stream_track_state  frames written since the lane was armed or the stream reset (the cursor); frames_written may be NULL.
+ * A feed that would complete more frames than the buffer has left is refused with SGZ_EINVAL before anything is consumed.  reset restarts
+ * the cursor and keeps the lane armed.
+ * Memory: per slot maxFrames * pairs records of device (and, for a pageable buffer, pinned) memory, maxFrames = ceil(chunk_samples / hop),
+ * made on first need.  An armed sgz_pcm_stream_feed renders with line results even when lines_out is NULL -- they stay on the device --
+ * so each slot then holds maxFrames * pairs * graphs * P * 8 bytes of them, bounded by chunk_samples: the amount lines_out already costs.
+ * An armed sgz_pcm_stream_feed_overview searches the plan's slab scratch and adds no line-result memory.  A track-only pass over a file is
+ * therefore an overview feed with a large k and peaks_out only: one column of peaks per feed comes back beside the records. */
+sgz_status sgz_pcm_stream_set_track(sgz_pcm_stream *s, uint32_t graph, double mouse_fraction,
+                                    sgz_line_peak *track_out /*HOST [capacity_frames][pairs]; NULL with capacity 0 = off*/, uint64_t capacity_frames);
+uint64_t   sgz_pcm_stream_track_for(const sgz_pcm_stream *s, size_t nsamples);
+sgz_status sgz_pcm_stream_track_state(const sgz_pcm_stream *s, uint64_t *frames_written);
 
 /* The view of kept peaks: any range of kept V at any width and in any colours, one small launch -- what a host calls per redraw of a file
  * lane (zoom, pan, resize, another gradient) instead of rendering the file again.

@@ -197,6 +197,7 @@ EXPORTS = [
     "sgz_pcm_stream_set_option",
     "sgz_stage_wave_columns", "sgz_wave_columns_limits", "sgz_pcm_stream_set_waveform", "sgz_pcm_stream_waveform_for",
     "sgz_pcm_stream_waveform_state", "sgz_pcm_stream_flush_waveform",
+    "sgz_track_peak_values", "sgz_stage_track_peaks_values", "sgz_pcm_stream_set_track", "sgz_pcm_stream_track_for", "sgz_pcm_stream_track_state",
 ]
 
 
@@ -420,6 +421,12 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_waveform_for.restype = u64
     L.sgz_pcm_stream_waveform_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.sgz_pcm_stream_flush_waveform.argtypes = [vp]
+    L.sgz_track_peak_values.argtypes = [vp, vp, C.c_double, C.POINTER(LinePeak)]
+    L.sgz_stage_track_peaks_values.argtypes = [vp, vp, sz, C.c_double, vp, vp]
+    L.sgz_pcm_stream_set_track.argtypes = [vp, u32, C.c_double, vp, u64]
+    L.sgz_pcm_stream_track_for.argtypes = [vp, sz]
+    L.sgz_pcm_stream_track_for.restype = u64
+    L.sgz_pcm_stream_track_state.argtypes = [vp, C.POINTER(u64)]
     L.sgz_spectrogram_overview_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, C.POINTER(PcmTiming)]
     _lib = L
     return L
@@ -744,6 +751,15 @@ class Plan:
         check(lib().sgz_track_peak_lines(self.h, _np_ptr(r), float(mouse_fraction), C.byref(out)))
         return out.asdict()
 
+    def track_peak_values(self, values: np.ndarray, mouse_fraction: float) -> dict:
+        """sgz_track_peak_values: the same search on a host value plane float [P] -- one (column, pair) of the peaks any overview or view
+        call writes (no upload needed: host arithmetic)"""
+        v = np.ascontiguousarray(values, np.float32)
+        assert v.size == self.P
+        out = LinePeak()
+        check(lib().sgz_track_peak_values(self.h, _np_ptr(v), float(mouse_fraction), C.byref(out)))
+        return out.asdict()
+
     # the batched tracker: records come back as float64 rows in the field order of Peak (8) / LinePeak (6)
     def track_peaks(self, bins, mouse_fraction: float, out=None, stream=None):
         """sgz_stage_track_peaks: bins -- cuda float32 [..., N + 1] (sgz_stage_bins' records); returns cuda float64 [records, 8]"""
@@ -766,6 +782,18 @@ class Plan:
             out = torch.empty((frames, self.C, len(LinePeak._fields_)), dtype=torch.float64, device=lines.device)
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         check(lib().sgz_stage_track_peaks_lines(self.h, lines.data_ptr(), frames, graph, float(mouse_fraction), out.data_ptr(), s))
+        return out
+
+    def track_peaks_values(self, values, mouse_fraction: float, out=None, stream=None):
+        """sgz_stage_track_peaks_values: values -- cuda float32 [..., P], the peaks of any overview or view call ([columns, pairs, P]);
+        returns cuda float64 [*values.shape[:-1], 6]"""
+        import torch
+        assert values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and values.shape[-1] == self.P
+        records = values.numel() // self.P
+        if out is None:
+            out = torch.empty(tuple(values.shape[:-1]) + (len(LinePeak._fields_),), dtype=torch.float64, device=values.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_track_peaks_values(self.h, values.data_ptr(), records, float(mouse_fraction), out.data_ptr(), s))
         return out
 
     def track_render(self, planar, graph: int, mouse_fraction: float, want_rgba: bool = True, state=None, stream=None):
@@ -1179,6 +1207,26 @@ class PcmStream:
     def flush_waveform(self) -> None:
         """sgz_pcm_stream_flush_waveform: closes the open column (one more column at the cursor); waits"""
         check(lib().sgz_pcm_stream_flush_waveform(self.h))
+
+
+    # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
+    def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:
+        """sgz_pcm_stream_set_track: out -- a float64 numpy array or host torch tensor [capacity, pairs, 6] (kept alive here; pinned memory is
+        written in place); the cursor restarts at 0.  out None disarms"""
+        if capacity_frames is None:
+            capacity_frames = 0 if out is None else int(out.shape[0])
+        check(lib().sgz_pcm_stream_set_track(self.h, graph, float(mouse_fraction), _buf_ptr(out) if out is not None else None, capacity_frames))
+        self._track_out = out
+
+    def track_for(self, nsamples: int) -> int:
+        """sgz_pcm_stream_track_for: frames whose records the next feed of nsamples writes; 0 when disarmed"""
+        return int(lib().sgz_pcm_stream_track_for(self.h, nsamples))
+
+    def track_state(self) -> int:
+        """sgz_pcm_stream_track_state: frames written since the lane was armed or the stream reset (the cursor)"""
+        f = C.c_uint64(0)
+        check(lib().sgz_pcm_stream_track_state(self.h, C.byref(f)))
+        return int(f.value)
 
 
 def wave_columns_limits():

@@ -1052,9 +1052,10 @@ sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar
 constexpr size_t kOverviewSlabBytes = size_t(64) << 20;
 }  // extern "C"
 // The slab loop by itself (runtime.hpp): `held` frames of an open column in front (their V in d_carry), the columns that close written from
-// the outputs' first element on.  The overview render enters with held = 0 and flush; sgz_pcm_stream enters once per piece.
+// the outputs' first element on.  The overview render enters with held = 0 and flush; sgz_pcm_stream enters once per piece, with `track`
+// when its track lane is armed.
 sgz_status sgz::runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
-                                 int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t s)
+                                 int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t s, const SlabTrack *track)
 {
     Plan &p = plan->impl;
     sgz_status st = SGZ_OK;
@@ -1074,6 +1075,7 @@ sgz_status sgz::runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t c
         const size_t ns = isResonator(p) ? nsamples : size_t(p.W) + size_t(nf - 1) * p.cfg.hop;
         st = sgz_spectrogram_render_device(plan, d_planar + size_t(f0) * p.cfg.hop, channel_stride, ns, nullptr, p.d_ovLines, state, s);
         if (st != SGZ_OK) return st;
+        if (track && (st = runTrackPeaksLines(p, p.d_ovLines, size_t(nf), track->graph, track->mouseFraction, track->d_out + size_t(f0) * p.C, s)) != SGZ_OK) return st;
         const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
         const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
         st = runOverviewColumns(p, p.d_ovLines, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, 0, d_carry,

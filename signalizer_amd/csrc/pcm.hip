@@ -1,10 +1,12 @@
 // pcm.hip -- interleaved PCM in (include/sgz.h "interleaved PCM in"): the convert-and-de-interleave kernel, and the stream handle that
 // cuts a feed into pieces and runs upload / convert + render / read-back of neighbouring pieces side by side on three streams; armed, the
-// waveform lane (wave_columns.hip) reduces every piece's new samples behind the converter and its columns ride the same read-back.
+// waveform lane (wave_columns.hip) reduces every piece's new samples behind the converter and its columns ride the same read-back; armed, the
+// track lane (tracker.hip) searches every piece's line results behind its render and its records ride it too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -213,6 +215,10 @@ struct PcmSlot {                        // what one piece in flight owns; a slot
     // need and grown when a later m needs more columns per piece; waveDst: where the drain copies the twin's waveBytes to
     float *d_wave = nullptr, *h_wave = nullptr, *waveDst = nullptr;
     size_t waveCap = 0, wavePinnedCap = 0, waveBytes = 0;
+    // the track lane's records of one piece (sgz_pcm_stream_set_track): sgz_line_peak [maxFrames][pairs] with its pinned twin, made on first
+    // need; trackDst: where the drain copies the twin's trackBytes to
+    sgz_line_peak *d_track = nullptr, *h_track = nullptr, *trackDst = nullptr;
+    size_t trackCap = 0, trackPinnedCap = 0, trackBytes = 0;
 };
 }  // namespace
 
@@ -239,6 +245,12 @@ struct sgz_pcm_stream {
     bool wvPinned = false;
     float *d_wvCarry = nullptr;
     int wvCur = 0;
+    // the track lane (trArmed): the graph and mouse position searched, the caller's records [trCap][pairs] and the cursor in them, in frames
+    bool trArmed = false, trPinned = false;
+    uint32_t trGraph = 0;
+    double trFraction = 0;
+    sgz_line_peak *trOut = nullptr;
+    uint64_t trCap = 0, trCursor = 0;
 };
 
 struct sgz_plan { Plan impl; };
@@ -255,7 +267,8 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
     if (sl.rgbaDst) std::memcpy(sl.rgbaDst, sl.rgbaFrom, sl.rgbaBytes);
     if (sl.linesDst) std::memcpy(sl.linesDst, sl.linesFrom, sl.linesBytes);
     if (sl.waveDst) std::memcpy(sl.waveDst, sl.h_wave, sl.waveBytes);
-    sl.rgbaDst = nullptr; sl.linesDst = nullptr; sl.waveDst = nullptr;
+    if (sl.trackDst) std::memcpy(sl.trackDst, sl.h_track, sl.trackBytes);
+    sl.rgbaDst = nullptr; sl.linesDst = nullptr; sl.waveDst = nullptr; sl.trackDst = nullptr;
     if (timing && sl.timed) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, sl.ev[0], sl.ev[1]) == hipSuccess) timing->h2d_ms += ms;
@@ -329,6 +342,36 @@ static sgz_status pcmWaveReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t colum
     return SGZ_OK;
 }
 
+// ---- the track lane inside the stream (sgz.h, "The track lane") ----------------------------------------------------------------------------
+// what a feed checks for the lane before anything is consumed: the frames its samples complete fit behind the cursor
+static sgz_status pcmTrackFits(const sgz_pcm_stream &s, uint64_t frames)
+{
+    if (s.trArmed && frames > s.trCap - s.trCursor)
+        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed completes more frames than the track buffer has left (sgz_pcm_stream_track_for; re-arm with sgz_pcm_stream_set_track)");
+    return SGZ_OK;
+}
+
+// a slot's records of a piece, maxFrames * pairs of them (both slots are idle between feeds)
+static sgz_status pcmTrackBuffers(sgz_pcm_stream &s, PcmSlot &sl)
+{
+    if (!s.trArmed) return SGZ_OK;
+    const size_t bytes = size_t(s.cfg.num_pairs) * sizeof(sgz_line_peak);
+    if (sgz_status st = pcmGrow(&sl.d_track, &sl.trackCap, s.maxFrames, bytes, false); st != SGZ_OK) return st;
+    return s.trPinned ? SGZ_OK : pcmGrow(&sl.h_track, &sl.trackPinnedCap, s.maxFrames, bytes, true);
+}
+
+// the piece's records to the caller's buffer at the cursor, on the read-back stream (behind ev[4]); pageable: to the twin, the drain copies
+static sgz_status pcmTrackReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t frames)
+{
+    if (!s.trArmed || !frames) return SGZ_OK;
+    sgz_line_peak *at = s.trOut + size_t(s.trCursor) * s.cfg.num_pairs;
+    sl.trackBytes = size_t(frames) * s.cfg.num_pairs * sizeof(sgz_line_peak);
+    SGZ_HIP(hipMemcpyAsync(s.trPinned ? at : sl.h_track, sl.d_track, sl.trackBytes, hipMemcpyDeviceToHost, s.back));
+    sl.trackDst = s.trPinned ? nullptr : at;
+    s.trCursor += frames;
+    return SGZ_OK;
+}
+
 extern "C" {
 
 uint32_t sgz_pcm_sample_bytes(uint32_t format) { return pcmSampleBytes(format); }
@@ -351,8 +394,8 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
     if (!s) return;
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamSynchronize(q);
     for (PcmSlot &sl : s->slot) {
-        for (void *p : {sl.h_pcm, (void *)sl.h_rgba, (void *)sl.h_lines, (void *)sl.h_ovRgba, (void *)sl.h_ovPeaks, (void *)sl.h_wave}) if (p) (void)hipHostFree(p);
-        for (void *p : {sl.d_pcm, (void *)sl.d_rgba, (void *)sl.d_lines, (void *)sl.d_ovRgba, (void *)sl.d_ovPeaks, (void *)sl.d_wave}) if (p) (void)hipFree(p);
+        for (void *p : {sl.h_pcm, (void *)sl.h_rgba, (void *)sl.h_lines, (void *)sl.h_ovRgba, (void *)sl.h_ovPeaks, (void *)sl.h_wave, (void *)sl.h_track}) if (p) (void)hipHostFree(p);
+        for (void *p : {sl.d_pcm, (void *)sl.d_rgba, (void *)sl.d_lines, (void *)sl.d_ovRgba, (void *)sl.d_ovPeaks, (void *)sl.d_wave, (void *)sl.d_track}) if (p) (void)hipFree(p);
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
     for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry}) if (p) (void)hipFree(p);
@@ -411,6 +454,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     s->held = 0;
     s->ovOpen = 0;                                                                  // an open overview column is dropped
     s->wvOpen = 0; s->wvCursor = 0;                                                 // and the waveform's; its columns start over
+    s->trCursor = 0;                                                                // the track's records too; the lane stays armed
     return SGZ_OK;
 }
 
@@ -426,18 +470,21 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
     if (need && !rgba_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null rgba_out");
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
+    if (sgz_status st = pcmTrackFits(*s, need); st != SGZ_OK) return st;
     if (timing) *timing = sgz_pcm_timing{};
     const uint32_t W = s->cfg.window_size, hop = s->cfg.hop, P = s->cfg.axis_points;
+    const bool wantLines = lines_out || s->trArmed;             // the track lane searches the line results: rendered, never read back for it
     const bool pcmPinned = nsamples && isPinnedHost(pcm);
     const bool rgbaPinned = need && isPinnedHost(rgba_out), linesPinned = need && lines_out && isPinnedHost(lines_out);
     // (the pinned slots and the lines buffers are made on first need: a caller with pinned memory of its own never pays for them)
     for (PcmSlot &sl : s->slot) {
         if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s->chunk * s->frameBytes, hipHostMallocDefault));
         if (need && !rgbaPinned && !sl.h_rgba) SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_rgba), s->maxFrames * P * 4, hipHostMallocDefault));
-        if (need && lines_out && !sl.d_lines) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&sl.d_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float)));
+        if (need && wantLines && !sl.d_lines) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&sl.d_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float)));
         if (need && lines_out && !linesPinned && !sl.h_lines)
             SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float), hipHostMallocDefault));
         if (sgz_status st = pcmWaveBuffers(*s, sl); st != SGZ_OK) return st;
+        if (sgz_status st = pcmTrackBuffers(*s, sl); st != SGZ_OK) return st;
     }
     const uint8_t *src = static_cast<const uint8_t *>(pcm);
     uint64_t framesDone = 0, chunks = 0;
@@ -466,8 +513,9 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
         const uint64_t total = s->held + n;
         sl.rendered = frames > 0 || waveColumns > 0;               // (a piece may close waveform columns and complete no frame)
         if (frames) {
-            const sgz_status st = sgz_spectrogram_render_device(s->plan, planar, s->stride, size_t(total), sl.d_rgba, lines_out ? sl.d_lines : nullptr, s->d_state, s->compute);
+            sgz_status st = sgz_spectrogram_render_device(s->plan, planar, s->stride, size_t(total), sl.d_rgba, wantLines ? sl.d_lines : nullptr, s->d_state, s->compute);
             if (st != SGZ_OK) return st;
+            if (s->trArmed && (st = runTrackPeaksLines(s->plan->impl, sl.d_lines, size_t(frames), s->trGraph, s->trFraction, sl.d_track, s->compute)) != SGZ_OK) return st;
             if (keep) SGZ_HIP(hipMemcpy2DAsync(s->d_planar[s->cur ^ 1], s->stride * sizeof(float), planar + (total - keep), s->stride * sizeof(float),
                                                size_t(keep) * sizeof(float), s->numChannels, hipMemcpyDeviceToDevice, s->compute));
             s->cur ^= 1;
@@ -487,6 +535,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
                 sl.rgbaDst = rgbaPinned ? nullptr : rgbaAt; sl.rgbaFrom = sl.h_rgba;
                 sl.linesDst = (lines_out && !linesPinned) ? linesAt : nullptr; sl.linesFrom = sl.h_lines;
             }
+            if (sgz_status st = pcmTrackReadBack(*s, sl, frames); st != SGZ_OK) return st;
             if (sgz_status st = pcmWaveReadBack(*s, sl, waveColumns); st != SGZ_OK) return st;
             SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
         }
@@ -563,6 +612,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (columns_out) *columns_out = need;
     if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)");
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
+    if (sgz_status st = pcmTrackFits(*s, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
     if (timing) *timing = sgz_pcm_timing{};
     const uint32_t W = s->cfg.window_size, hop = s->cfg.hop, P = s->cfg.axis_points, C = s->cfg.num_pairs;
     const bool pcmPinned = nsamples && isPinnedHost(pcm);
@@ -574,6 +624,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
         if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s->chunk * s->frameBytes, hipHostMallocDefault));
         sgz_status st = pcmWaveBuffers(*s, sl);
         if (st != SGZ_OK) return st;
+        if ((st = pcmTrackBuffers(*s, sl)) != SGZ_OK) return st;
         if (!need) continue;                                      // (no column closes: nothing is written or read back)
         if (rgba_out && (st = pcmGrow(&sl.d_ovRgba, &sl.ovRgbaCap, slotColumns, size_t(P) * 4, false)) != SGZ_OK) return st;
         if (rgba_out && !rgbaPinned && (st = pcmGrow(&sl.h_ovRgba, &sl.ovRgbaPinnedCap, slotColumns, size_t(P) * 4, true)) != SGZ_OK) return st;
@@ -619,8 +670,9 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
         uint8_t *d_rgba = rgba_out ? sl.d_ovRgba : nullptr;
         float *d_peaks = peaks_out ? sl.d_ovPeaks : nullptr;
         if (frames) {
+            const SlabTrack track{s->trGraph, s->trFraction, sl.d_track};
             const sgz_status st = runOverviewSlabs(s->plan, planar, s->stride, size_t(total), long(frames), k, uint32_t(s->ovOpen), pieceFlush, s->d_ovCarry,
-                                                   s->d_state, d_rgba, d_peaks, s->compute);
+                                                   s->d_state, d_rgba, d_peaks, s->compute, s->trArmed ? &track : nullptr);
             if (st != SGZ_OK) return st;
             if (keep) SGZ_HIP(hipMemcpy2DAsync(s->d_planar[s->cur ^ 1], s->stride * sizeof(float), planar + (total - keep), s->stride * sizeof(float),
                                                size_t(keep) * sizeof(float), s->numChannels, hipMemcpyDeviceToDevice, s->compute));
@@ -634,7 +686,8 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
         s->ovK = k;
         SGZ_HIP(hipEventRecord(sl.ev[4], s->compute));
         // 3. read back the columns that closed
-        sl.rendered = columns > 0 || waveColumns > 0;
+        const uint64_t trackFrames = s->trArmed ? frames : 0;      // (a piece may complete frames and close no column)
+        sl.rendered = columns > 0 || waveColumns > 0 || trackFrames > 0;
         if (sl.rendered) {
             SGZ_HIP(hipStreamWaitEvent(s->back, sl.ev[4], 0));
             if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s->back));
@@ -647,6 +700,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
                 sl.rgbaDst = (rgba_out && !rgbaPinned) ? rgbaAt : nullptr; sl.rgbaFrom = sl.h_ovRgba;
                 sl.linesDst = (peaks_out && !peaksPinned) ? peaksAt : nullptr; sl.linesFrom = sl.h_ovPeaks;
             }
+            if (sgz_status st = pcmTrackReadBack(*s, sl, trackFrames); st != SGZ_OK) return st;
             if (sgz_status st = pcmWaveReadBack(*s, sl, waveColumns); st != SGZ_OK) return st;
             SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
         }
@@ -736,6 +790,32 @@ sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s)
     if (!s->wvPinned) std::memcpy(at, sl.h_wave, bytes);
     s->wvOpen = 0;
     ++s->wvCursor;
+    return SGZ_OK;
+}
+
+// ---- the track lane's calls -------------------------------------------------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_set_track(sgz_pcm_stream *s, uint32_t graph, double mouse_fraction, sgz_line_peak *track_out, uint64_t capacity_frames)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (graph >= SGZ_NUM_GRAPHS) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_track: graph");
+    if (!std::isfinite(mouse_fraction)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_track: mouse_fraction");
+    if (!track_out && capacity_frames) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_track: null track_out");
+    if (reinterpret_cast<uintptr_t>(track_out) % alignof(sgz_line_peak)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_track: track_out is not aligned to double");
+    s->trArmed = track_out != nullptr;                             // NULL with capacity 0: off
+    s->trGraph = graph; s->trFraction = mouse_fraction; s->trOut = track_out; s->trCap = capacity_frames; s->trCursor = 0;
+    s->trPinned = capacity_frames && isPinnedHost(track_out);
+    return SGZ_OK;
+}
+
+uint64_t sgz_pcm_stream_track_for(const sgz_pcm_stream *s, size_t nsamples)
+{
+    return s && s->trArmed ? sgz_pcm_stream_frames_for(s, nsamples) : 0;
+}
+
+sgz_status sgz_pcm_stream_track_state(const sgz_pcm_stream *s, uint64_t *frames_written)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (frames_written) *frames_written = s->trCursor;
     return SGZ_OK;
 }
 

@@ -87,6 +87,8 @@ sgz_status runTrackPeak(const Plan &p, const float *d_bins, double mouseFraction
 sgz_status runTrackPeaks(const Plan &p, const float *d_bins, size_t records, double mouseFraction, sgz_peak *d_out, hipStream_t stream);
 sgz_status runTrackPeaksLines(const Plan &p, const float *d_lines, size_t frames, uint32_t graph, double mouseFraction, sgz_line_peak *d_out,
                               hipStream_t stream);
+// ... and the line-results search over value planes d_values [records][P] float (the peaks of any overview or view call); d_out: DEVICE [records]
+sgz_status runTrackPeaksValues(const Plan &p, const float *d_values, size_t records, double mouseFraction, sgz_line_peak *d_out, hipStream_t stream);
 // the overview's reduction (overview.hip): k frames of line results per column -> image columns / peaks, the open column in d_carry; the
 // arguments are sgz_stage_overview's, checked by the caller; asynchronous on `stream`, plan scratch grows on demand
 sgz_status runOverviewColumns(Plan &p, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices, float *d_carry,
@@ -99,8 +101,12 @@ sgz_status runOverviewView(Plan &p, const float *d_src, size_t m, size_t cols, u
 // the overview render's slab loop (api.hip): `frames` frames from d_planar behind `held` frames of an open column whose V is in d_carry; the
 // columns that close go to d_rgba / d_peaks from their first element on, the open one stays in d_carry unless `flush`.  d_state: the decay
 // state in and out, or null (from rest; kept in plan scratch between slabs).  What sgz_spectrogram_overview_device and sgz_pcm_stream share.
+// track: null, or where the tracker's record of every (frame, pair) goes -- runTrackPeaksLines behind every slab's render on the slab's line
+// results, into d_out [frames][pairs] at the slab's frame offset (stream order alone keeps the next slab's render behind it)
+struct SlabTrack { uint32_t graph; double mouseFraction; sgz_line_peak *d_out; };
 sgz_status runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
-                            int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t stream);
+                            int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t stream,
+                            const SlabTrack *track = nullptr);
 // the waveform lane's reduction (wave_columns.hip): (lo, hi) per column of m samples and channel, the open column in a carry; what
 // sgz_stage_wave_columns and sgz_pcm_stream share.  The arguments are the stage call's, checked by the caller; asynchronous on `stream`
 struct WaveColumnsShape {
@@ -113,4 +119,5 @@ WaveColumnsShape waveColumnsShape(uint32_t channels, size_t nsamples, uint32_t m
 sgz_status runWaveColumns(const WaveColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples, uint32_t m,
                           uint32_t held, const float *carryIn, float *carryOut, float *d_wave, void *scratch, hipStream_t stream);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
+sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
 }  // namespace sgz

@@ -6,7 +6,8 @@
 // One workgroup: the range is at most a few thousand bins; the reduction key is (square, smaller index wins), i.e. max_element's.
 // The batched forms (one workgroup of 256 per record, nothing allocated, nothing waited for): trackPeaksKernel, the same search over
 // [records][N + 1] bins, and trackLinePeaksKernel, the line-results branch (:300-377, trackPeakLines below restated) over the line
-// results of a whole render.  Their boundary walks are cooperative: a wave tests 256 neighbour pairs per step and takes the first hit.
+// results of a whole render, with trackValuePeaksKernel, the same body (trackLineRecord) over [records][P] value planes -- the kept peaks
+// of an overview or a view.  Their boundary walks are cooperative: a wave tests 256 neighbour pairs per step and takes the first hit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -145,16 +146,15 @@ struct LineTrackParams {
     int floorApplies;
 };
 
-// trackPeakLines (below) per record of [records][graphs][P] float2 line results: record r searches graph `graph`
-__global__ void __launch_bounds__(kTrackThreads)
-trackLinePeaksKernel(const float *lines, uint32_t graph, const LineTrackParams prm, const float *mapped, const float *slopeMap, sgz_line_peak *out)
+// trackPeakLines (below) for one record, by one workgroup: `left(i)` reads the searched value of axis point i, wherever the record keeps it;
+// lane 0 of wave 0 writes *o.  What trackLinePeaksKernel and trackValuePeaksKernel share
+template <typename Left>
+__device__ __forceinline__ void trackLineRecord(Left left, const LineTrackParams &prm, const float *mapped, const float *slopeMap, sgz_line_peak *o)
 {
     __shared__ float sVal[kTrackThreads / 64];
     __shared__ long sIdx[kTrackThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long N = prm.points;
-    const float *results = lines + ((size_t(blockIdx.x) * SGZ_NUM_GRAPHS + graph) * size_t(N)) * 2;
-    auto left = [&](long i) { return results[2 * i]; };
     // the host loop "if (left(peak) < left(i)) peak = i" from left(start): the first largest; a NaN never wins, a NaN at the start stays
     // (every comparison with it is false) -- both fall out of the same comparisons here
     float best = left(prm.lowerBound < N ? prm.lowerBound : N - 1);
@@ -185,13 +185,28 @@ trackLinePeaksKernel(const float *lines, uint32_t graph, const LineTrackParams p
     double peakDeviance = double(mapped[hi] - mapped[lo]);
     if (prm.floorApplies) peakDeviance = peakDeviance < prm.devianceFloor ? prm.devianceFloor : peakDeviance;      // std::max   :355-358
     const float y = left(peak);
-    sgz_line_peak *o = out + blockIdx.x;
     o->peak_offset = double(peak);
     o->peak_frequency = double(mapped[peak]);
     o->peak_deviance = peakDeviance;
     o->peak_fraction_y = double(y);
     o->peak_dbs = prm.lowDb + double(y) * prm.dbRange;           // one multiply, one add (fp contract off: no fused form)
     o->peak_slope = double(slopeMap[peak]);
+}
+
+// per record of [records][graphs][P] float2 line results: record r searches graph `graph`, first components
+__global__ void __launch_bounds__(kTrackThreads)
+trackLinePeaksKernel(const float *lines, uint32_t graph, const LineTrackParams prm, const float *mapped, const float *slopeMap, sgz_line_peak *out)
+{
+    const float *results = lines + ((size_t(blockIdx.x) * SGZ_NUM_GRAPHS + graph) * size_t(prm.points)) * 2;
+    trackLineRecord([&](long i) { return results[2 * i]; }, prm, mapped, slopeMap, out + blockIdx.x);
+}
+
+// per record of [records][P] float values -- the planes V / V' every overview and view call writes: record r searches values[r]
+__global__ void __launch_bounds__(kTrackThreads)
+trackValuePeaksKernel(const float *values, const LineTrackParams prm, const float *mapped, const float *slopeMap, sgz_line_peak *out)
+{
+    const float *record = values + size_t(blockIdx.x) * size_t(prm.points);
+    trackLineRecord([&](long i) { return record[i]; }, prm, mapped, slopeMap, out + blockIdx.x);
 }
 
 // the line-results branch's search range (:305-312) from the clamped mouse position
@@ -249,26 +264,49 @@ sgz_status runTrackPeaks(const Plan &p, const float *d_bins, size_t records, dou
     return SGZ_OK;
 }
 
-// trackPeakLines for every (frame, pair) of d_lines [frames][pairs][graphs][P] float2 in one launch; d_out: DEVICE sgz_line_peak
-// [frames][pairs].  The entry points have checked graph < SGZ_NUM_GRAPHS and a finite mouseFraction and uploaded the plan's tables.
-sgz_status runTrackPeaksLines(const Plan &p, const float *d_lines, size_t frames, uint32_t graph, double mouseFraction, sgz_line_peak *d_out,
-                              hipStream_t stream)
+// what both line-results launches share: the clamp (:292), the search range and the plan's constants.  The entry points have checked a
+// finite mouseFraction and uploaded the plan's tables.
+static sgz_status lineTrackParams(const Plan &p, size_t records, double mouseFraction, LineTrackParams &prm)
 {
     mouseFraction = mouseFraction < 0 ? 0 : (mouseFraction > 1 ? 1 : mouseFraction);                      // :292
     const size_t N = p.P;
     if (N == 0) return fail(SGZ_EINVAL, "no axis points");
-    if (frames == 0) return SGZ_OK;
-    if (frames > 0x7fffffffu / p.C) return fail(SGZ_EINVAL, "too many (frame, pair) records for one launch");
+    if (records > 0x7fffffffu) return fail(SGZ_EINVAL, "too many records for one launch");
     if (!p.d_mappedFreq || !p.d_slope) return fail(SGZ_EINVAL, "plan tables not uploaded");
     const LineRange r = lineSearchRange(N, mouseFraction);
-    LineTrackParams prm{};
+    prm = LineTrackParams{};
     prm.points = long(N); prm.lowerBound = long(r.lowerBound); prm.higherBound = long(r.higherBound);
     prm.axisLast = long(size_t(p.cfg.axis_points) - 1);
     prm.lowDb = p.cfg.low_db; prm.dbRange = p.cfg.high_db - p.cfg.low_db;
     prm.floorApplies = p.cfg.algorithm == SGZ_ALGO_FFT && p.cfg.bin_interp != SGZ_INTERP_LANCZOS;
     prm.devianceFloor = 0.5 * double(p.N) / double(N);
+    return SGZ_OK;
+}
+
+// trackPeakLines for every (frame, pair) of d_lines [frames][pairs][graphs][P] float2 in one launch; d_out: DEVICE sgz_line_peak
+// [frames][pairs].  The entry points have checked graph < SGZ_NUM_GRAPHS and a finite mouseFraction and uploaded the plan's tables.
+sgz_status runTrackPeaksLines(const Plan &p, const float *d_lines, size_t frames, uint32_t graph, double mouseFraction, sgz_line_peak *d_out,
+                              hipStream_t stream)
+{
+    if (p.P == 0) return fail(SGZ_EINVAL, "no axis points");
+    if (frames == 0) return SGZ_OK;
+    if (frames > 0x7fffffffu / p.C) return fail(SGZ_EINVAL, "too many (frame, pair) records for one launch");
+    LineTrackParams prm{};
+    if (sgz_status st = lineTrackParams(p, frames * p.C, mouseFraction, prm); st != SGZ_OK) return st;
     hipLaunchKernelGGL(trackLinePeaksKernel, dim3(unsigned(frames * p.C)), dim3(kTrackThreads), 0, stream, d_lines, graph, prm, p.d_mappedFreq,
                        p.d_slope, d_out);
+    SGZ_HIP(hipGetLastError());
+    return SGZ_OK;
+}
+
+// the same for every record of d_values [records][P] float in one launch; d_out: DEVICE sgz_line_peak [records]
+sgz_status runTrackPeaksValues(const Plan &p, const float *d_values, size_t records, double mouseFraction, sgz_line_peak *d_out, hipStream_t stream)
+{
+    if (p.P == 0) return fail(SGZ_EINVAL, "no axis points");
+    if (records == 0) return SGZ_OK;
+    LineTrackParams prm{};
+    if (sgz_status st = lineTrackParams(p, records, mouseFraction, prm); st != SGZ_OK) return st;
+    hipLaunchKernelGGL(trackValuePeaksKernel, dim3(unsigned(records)), dim3(kTrackThreads), 0, stream, d_values, prm, p.d_mappedFreq, p.d_slope, d_out);
     SGZ_HIP(hipGetLastError());
     return SGZ_OK;
 }
@@ -278,13 +316,14 @@ sgz_status runTrackPeaksLines(const Plan &p, const float *d_lines, size_t frames
 namespace sgz {
 
 // The tracker's line-results branch (SpectrumRendering.cpp:300-377), host arithmetic on host-resident results (see sgz.h).
-sgz_status trackPeakLines(const Plan &p, const float *results, double mouseFraction, sgz_line_peak *out)
+// `stride`: floats from one axis point's searched value to the next -- 2 for float2 line results (the first component), 1 for a value plane.
+static sgz_status trackPeakStrided(const Plan &p, const float *results, size_t stride, double mouseFraction, sgz_line_peak *out)
 {
     if (!std::isfinite(mouseFraction)) return fail(SGZ_EINVAL, "mouse_fraction");
     mouseFraction = mouseFraction < 0 ? 0 : (mouseFraction > 1 ? 1 : mouseFraction);                      // :292
     const size_t N = p.P;                                                                                 // results.size()
     if (N == 0) return fail(SGZ_EINVAL, "no axis points");
-    auto left = [&](size_t i) { return results[2 * i]; };                                                 // UComplex::leftMagnitude
+    auto left = [&](size_t i) { return results[stride * i]; };                                            // UComplex::leftMagnitude
     const LineRange r = lineSearchRange(N, mouseFraction);
     const size_t lowerBound = r.lowerBound, higherBound = r.higherBound;
     // std::max_element over [lowerBound, higherBound): the first largest (an empty range -- fewer than 17 axis points -- yields its own
@@ -323,6 +362,16 @@ sgz_status trackPeakLines(const Plan &p, const float *results, double mouseFract
     return SGZ_OK;
 }
 
+sgz_status trackPeakLines(const Plan &p, const float *results, double mouseFraction, sgz_line_peak *out)
+{
+    return trackPeakStrided(p, results, 2, mouseFraction, out);
+}
+
+sgz_status trackPeakValues(const Plan &p, const float *values, double mouseFraction, sgz_line_peak *out)
+{
+    return trackPeakStrided(p, values, 1, mouseFraction, out);
+}
+
 }  // namespace sgz
 
 struct sgz_plan { Plan impl; };
@@ -331,6 +380,12 @@ extern "C" sgz_status sgz_track_peak_lines(const sgz_plan *plan, const float *re
 {
     if (!plan || !results || !out) return fail(SGZ_EINVAL, "null argument");
     return trackPeakLines(plan->impl, results, mouse_fraction, out);
+}
+
+extern "C" sgz_status sgz_track_peak_values(const sgz_plan *plan, const float *values, double mouse_fraction, sgz_line_peak *out)
+{
+    if (!plan || !values || !out) return fail(SGZ_EINVAL, "null argument");
+    return trackPeakValues(plan->impl, values, mouse_fraction, out);
 }
 
 extern "C" sgz_status sgz_stage_track_peak(sgz_plan *plan, const float *d_bins, double mouse_fraction, sgz_peak *out, void *stream)
@@ -371,4 +426,19 @@ extern "C" sgz_status sgz_stage_track_peaks_lines(sgz_plan *plan, const float *d
         if (st != SGZ_OK) return fail(st, err);
     }
     return runTrackPeaksLines(p, d_lines, frames, graph, mouse_fraction, d_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" sgz_status sgz_stage_track_peaks_values(sgz_plan *plan, const float *d_values, size_t records, double mouse_fraction, sgz_line_peak *d_out,
+                                                   void *stream)
+{
+    if (!plan || !d_values || !d_out) return fail(SGZ_EINVAL, "null argument");
+    if (!std::isfinite(mouse_fraction)) return fail(SGZ_EINVAL, "mouse_fraction");
+    if (records == 0) return SGZ_OK;
+    Plan &p = plan->impl;
+    if (!p.uploaded) {                                           // the kernel reads the plan's device tables
+        std::string err;
+        const sgz_status st = uploadPlan(p, err);
+        if (st != SGZ_OK) return fail(st, err);
+    }
+    return runTrackPeaksValues(p, d_values, records, mouse_fraction, d_out, reinterpret_cast<hipStream_t>(stream));
 }
