@@ -1,7 +1,9 @@
 // pcm.hip -- interleaved PCM in (include/sgz.h "interleaved PCM in"): the convert-and-de-interleave kernel, and the stream handle that
-// cuts a feed into pieces and runs upload / convert + render / read-back of neighbouring pieces side by side on three streams; armed, the
-// waveform lane (wave_columns.hip) reduces every piece's new samples behind the converter and its columns ride the same read-back; armed, the
-// track lane (tracker.hip) searches every piece's line results behind its render and its records ride it too.
+// cuts a feed into pieces and runs upload / convert + render / read-back of neighbouring pieces side by side on three streams.  Both kinds
+// of feed (frames, overview columns) go through ONE piece loop, pcmPieces, and differ in the Part they hand it: what to render from a piece
+// and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, waveform columns, track records --
+// is a PcmOut: device block, pinned twin, pending host copy.  Armed, the waveform lane (wave_columns.hip) reduces every piece's new samples
+// behind the converter and the track lane (tracker.hip) searches every piece's line results behind its render; both ride the same read-back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,13 +36,18 @@ constexpr uint32_t kPcmMaxTileSamples = 4096;
 
 struct PcmMap { uint32_t src[kPcmMaxChannels]; };
 
-template <uint32_t FORMAT> struct PcmBytes;
-template <> struct PcmBytes<SGZ_PCM_F32> { static constexpr uint32_t value = 4; };
-template <> struct PcmBytes<SGZ_PCM_U8> { static constexpr uint32_t value = 1; };
-template <> struct PcmBytes<SGZ_PCM_S16> { static constexpr uint32_t value = 2; };
-template <> struct PcmBytes<SGZ_PCM_S24> { static constexpr uint32_t value = 3; };
-template <> struct PcmBytes<SGZ_PCM_S32> { static constexpr uint32_t value = 4; };
-template <> struct PcmBytes<SGZ_PCM_F64> { static constexpr uint32_t value = 8; };
+// bytes of one sample of a format; 0: no such format
+static constexpr uint32_t pcmSampleBytes(uint32_t format)
+{
+    switch (format) {
+    case SGZ_PCM_F32: case SGZ_PCM_S32: return 4;
+    case SGZ_PCM_U8: return 1;
+    case SGZ_PCM_S16: return 2;
+    case SGZ_PCM_S24: return 3;
+    case SGZ_PCM_F64: return 8;
+    default: return 0;
+    }
+}
 
 // the sample at LDS byte offset `at` (a multiple of the sample's natural alignment) as the fp32 word sgz.h defines
 template <uint32_t FORMAT>
@@ -72,7 +79,7 @@ __global__ __launch_bounds__(kPcmThreads) void pcmToPlanarKernel(const uint8_t *
                                                                  uint32_t *__restrict__ planar, uint64_t channelStride)
 {
     extern __shared__ uint4 pcmTile[];                                     // [lead + tile bytes, rounded up to chunks] + one pad chunk
-    constexpr uint32_t kBytes = PcmBytes<FORMAT>::value;
+    constexpr uint32_t kBytes = pcmSampleBytes(FORMAT);
     const uint32_t frameBytes = srcChannels * kBytes;
     const uint64_t first = uint64_t(blockIdx.x) * tileSamples;             // the tile's first sample
     const uint32_t count = uint32_t(min(uint64_t(tileSamples), nsamples - first));
@@ -110,22 +117,8 @@ static uint32_t pcmTileSamples(uint32_t frameBytes)
     return std::min(kPcmMaxTileSamples, 64u * std::max(1u, kPcmTileBytes / (64u * frameBytes)));
 }
 
-static uint32_t pcmAlignment(uint32_t format)
-{
-    return format == SGZ_PCM_S16 ? 2u : (format == SGZ_PCM_S32 || format == SGZ_PCM_F32) ? 4u : format == SGZ_PCM_F64 ? 8u : 1u;
-}
-
-static uint32_t pcmSampleBytes(uint32_t format)
-{
-    switch (format) {
-    case SGZ_PCM_F32: case SGZ_PCM_S32: return 4;
-    case SGZ_PCM_U8: return 1;
-    case SGZ_PCM_S16: return 2;
-    case SGZ_PCM_S24: return 3;
-    case SGZ_PCM_F64: return 8;
-    default: return 0;
-    }
-}
+// the alignment d_pcm needs: the sample's own size, none for the packed three bytes of S24
+static uint32_t pcmAlignment(uint32_t format) { return pcmSampleBytes(format) == 3 ? 1u : pcmSampleBytes(format); }
 
 // everything the converter refuses that does not depend on the buffers (the stream handle checks it at create)
 static sgz_status checkPcmLayout(uint32_t format, uint32_t srcChannels, const uint32_t *channelMap, uint32_t numChannels, PcmMap &map)
@@ -194,31 +187,55 @@ constexpr size_t kPcmDefaultChunk = size_t(1) << 20;
 constexpr size_t kPcmDefaultSlotBytes = size_t(256) << 20;
 constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 
+// The outputs of a piece.  Image [maxFrames][P][4] and Lines [maxFrames][C][graphs][P][2] are the feed's; OvImage [columns][P][4] and OvPeaks
+// [columns][C][P] the overview feed's, ceil(maxFrames / k) + 1 columns of them; Wave float2 [ceil(chunk / m) + 1][channels] the waveform
+// lane's; Track sgz_line_peak [maxFrames][pairs] the track lane's.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kPcmOuts };
+
+// One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
+// performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
+// first need; a block grows when a later feed needs more (the slot is idle then: nothing in flight reads the old one).
+struct PcmOut {
+    void *dev = nullptr, *twin = nullptr;
+    size_t devCap = 0, twinCap = 0;
+    void *dst = nullptr; size_t bytes = 0;              // pending: `bytes` of the twin -> dst
+
+    template <typename T> T *as() const { return static_cast<T *>(dev); }
+    // a device block of at least n bytes; the twin as well when the destination is pageable
+    sgz_status reserve(size_t n, bool pageable)
+    {
+        if (devCap < n) {
+            if (dev) { (void)hipFree(dev); dev = nullptr; devCap = 0; }
+            SGZ_HIP(hipMalloc(&dev, n));
+            devCap = n;
+        }
+        if (pageable && twinCap < n) {
+            if (twin) { (void)hipHostFree(twin); twin = nullptr; twinCap = 0; }
+            SGZ_HIP(hipHostMalloc(&twin, n, hipHostMallocDefault));
+            twinCap = n;
+        }
+        return SGZ_OK;
+    }
+    // the block's first n bytes on their way to `to`: straight there when it is pinned, else to the twin, and the drain copies
+    sgz_status readBack(void *to, size_t n, bool pinned, hipStream_t stream)
+    {
+        SGZ_HIP(hipMemcpyAsync(pinned ? to : twin, dev, n, hipMemcpyDeviceToHost, stream));
+        dst = pinned ? nullptr : to; bytes = n;
+        return SGZ_OK;
+    }
+    void drain() { if (dst) std::memcpy(dst, twin, bytes); dst = nullptr; }
+    void release() { if (dev) (void)hipFree(dev); if (twin) (void)hipHostFree(twin); *this = PcmOut{}; }
+};
+
 struct PcmSlot {                        // what one piece in flight owns; a slot is reused by the piece after next
     void *h_pcm = nullptr;              // pinned [chunk][frameBytes], made when the first pageable feed arrives
     void *d_pcm = nullptr;
-    uint8_t *d_rgba = nullptr, *h_rgba = nullptr;       // [maxFrames][P][4]; the pinned twin when rgba_out is pageable
-    float *d_lines = nullptr, *h_lines = nullptr;       // [maxFrames][C][graphs][P][2], made when lines are first asked for
+    PcmOut out[kPcmOuts];
     hipEvent_t ev[7] = {};              // upload begin / END (copy stream); convert begin, convert end, render END (compute); read-back begin / END
                                         // (the capitals order the streams; the others are recorded for a caller that asks for timing only: a
                                         // marker costs the stream it sits on microseconds, api.hip sgz_render_queue_submit)
     bool timed = false;
-    bool busy = false, rendered = false;            // rendered: the piece has a read-back (frames, overview or waveform columns), ev[6] is recorded
-    // the host's part of the read-back, done when the slot is drained
-    uint8_t *rgbaDst = nullptr; float *linesDst = nullptr; size_t rgbaBytes = 0, linesBytes = 0;
-    const uint8_t *rgbaFrom = nullptr; const float *linesFrom = nullptr;       // the pinned twins the drain copies from
-    // the overview's columns of one piece (sgz_pcm_stream_feed_overview): [ovCap][P][4] and V [ovCap][C][P] with their pinned twins, made on
-    // first need and grown when a later k needs more columns per piece
-    uint8_t *d_ovRgba = nullptr, *h_ovRgba = nullptr; float *d_ovPeaks = nullptr, *h_ovPeaks = nullptr;
-    size_t ovRgbaCap = 0, ovRgbaPinnedCap = 0, ovPeaksCap = 0, ovPeaksPinnedCap = 0;       // columns
-    // the waveform lane's columns of one piece (sgz_pcm_stream_set_waveform): float2 [waveCap][channels] with its pinned twin, made on first
-    // need and grown when a later m needs more columns per piece; waveDst: where the drain copies the twin's waveBytes to
-    float *d_wave = nullptr, *h_wave = nullptr, *waveDst = nullptr;
-    size_t waveCap = 0, wavePinnedCap = 0, waveBytes = 0;
-    // the track lane's records of one piece (sgz_pcm_stream_set_track): sgz_line_peak [maxFrames][pairs] with its pinned twin, made on first
-    // need; trackDst: where the drain copies the twin's trackBytes to
-    sgz_line_peak *d_track = nullptr, *h_track = nullptr, *trackDst = nullptr;
-    size_t trackCap = 0, trackPinnedCap = 0, trackBytes = 0;
+    bool busy = false, rendered = false;            // rendered: the piece has a read-back (any output at all), ev[6] is recorded
 };
 }  // namespace
 
@@ -255,20 +272,21 @@ struct sgz_pcm_stream {
 
 struct sgz_plan { Plan impl; };
 
+using PcmClock = std::chrono::steady_clock;
+static double pcmMsSince(PcmClock::time_point t0) { return std::chrono::duration<double, std::milli>(PcmClock::now() - t0).count(); }
+
 static size_t pcmStateBytes(const sgz_pcm_stream &s) { return size_t(s.cfg.num_pairs) * SGZ_NUM_GRAPHS * s.cfg.axis_points * 2 * sizeof(float); }
 static size_t pcmLinesFloats(const sgz_pcm_stream &s, uint64_t frames) { return size_t(frames) * s.cfg.num_pairs * SGZ_NUM_GRAPHS * s.cfg.axis_points * 2; }
+static size_t pcmImageBytes(const sgz_pcm_stream &s, uint64_t columns) { return size_t(columns) * s.cfg.axis_points * 4; }
+static size_t pcmPeaksFloats(const sgz_pcm_stream &s, uint64_t columns) { return size_t(columns) * s.cfg.num_pairs * s.cfg.axis_points; }
 
-// waits for the piece that used the slot, hands its columns to the caller (pageable destinations) and adds its event intervals up
+// waits for the piece that used the slot, hands its outputs to the caller (pageable destinations) and adds its event intervals up
 static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
 {
     if (!sl.busy) return SGZ_OK;
     sl.busy = false;
     SGZ_HIP(hipEventSynchronize(sl.ev[sl.rendered ? 6 : 4]));
-    if (sl.rgbaDst) std::memcpy(sl.rgbaDst, sl.rgbaFrom, sl.rgbaBytes);
-    if (sl.linesDst) std::memcpy(sl.linesDst, sl.linesFrom, sl.linesBytes);
-    if (sl.waveDst) std::memcpy(sl.waveDst, sl.h_wave, sl.waveBytes);
-    if (sl.trackDst) std::memcpy(sl.trackDst, sl.h_track, sl.trackBytes);
-    sl.rgbaDst = nullptr; sl.linesDst = nullptr; sl.waveDst = nullptr; sl.trackDst = nullptr;
+    for (PcmOut &o : sl.out) o.drain();
     if (timing && sl.timed) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, sl.ev[0], sl.ev[1]) == hipSuccess) timing->h2d_ms += ms;
@@ -276,18 +294,6 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
         if (hipEventElapsedTime(&ms, sl.ev[3], sl.ev[4]) == hipSuccess) timing->render_ms += ms;
         if (sl.rendered && hipEventElapsedTime(&ms, sl.ev[5], sl.ev[6]) == hipSuccess) timing->d2h_ms += ms;
     }
-    return SGZ_OK;
-}
-
-// a device or pinned block of at least `need` columns of `bytes` each (the slot is idle: nothing in flight reads the old one)
-template <typename T>
-static sgz_status pcmGrow(T **buf, size_t *cap, size_t need, size_t bytes, bool pinned)
-{
-    if (*cap >= need) return SGZ_OK;
-    if (*buf) { (void)(pinned ? hipHostFree(*buf) : hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    if (pinned) SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(buf), need * bytes, hipHostMallocDefault));
-    else SGZ_HIP(hipMalloc(reinterpret_cast<void **>(buf), need * bytes));
-    *cap = need;
     return SGZ_OK;
 }
 
@@ -305,10 +311,7 @@ static sgz_status pcmWaveFits(const sgz_pcm_stream &s, size_t nsamples)
 // a slot's columns of a piece, ceil(chunk / m) + 1 of them (both slots are idle between feeds)
 static sgz_status pcmWaveBuffers(sgz_pcm_stream &s, PcmSlot &sl)
 {
-    if (!s.wvM) return SGZ_OK;
-    const size_t columns = (s.chunk + s.wvM - 1) / s.wvM + 1, bytes = size_t(s.numChannels) * 2 * sizeof(float);
-    if (sgz_status st = pcmGrow(&sl.d_wave, &sl.waveCap, columns, bytes, false); st != SGZ_OK) return st;
-    return s.wvPinned ? SGZ_OK : pcmGrow(&sl.h_wave, &sl.wavePinnedCap, columns, bytes, true);
+    return s.wvM ? sl.out[kOutWave].reserve(((s.chunk + s.wvM - 1) / s.wvM + 1) * s.numChannels * 2 * sizeof(float), !s.wvPinned) : SGZ_OK;
 }
 
 // the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the columns they close, into the slot;
@@ -321,7 +324,7 @@ static sgz_status pcmWavePiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fres
     StreamScratch scratch(s.compute);
     if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
     const sgz_status st = runWaveColumns(sh, fresh, s.stride, s.numChannels, n, s.wvM, uint32_t(s.wvOpen), pcmWaveCarry(s, s.wvCur), pcmWaveCarry(s, s.wvCur ^ 1),
-                                         sl.d_wave, scratch.p, s.compute);
+                                         sl.out[kOutWave].as<float>(), scratch.p, s.compute);
     if (st != SGZ_OK) return st;
     if (sh.open) s.wvCur ^= 1;
     s.wvOpen = (s.wvOpen + n) % s.wvM;
@@ -329,17 +332,14 @@ static sgz_status pcmWavePiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fres
     return SGZ_OK;
 }
 
-// the piece's columns to the caller's buffer at the cursor, on the read-back stream (behind ev[4]); pageable: to the twin, the drain copies
+// the piece's columns to the caller's buffer at the cursor, on the read-back stream
 static sgz_status pcmWaveReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
 {
     if (!columns) return SGZ_OK;
     const size_t column = size_t(s.numChannels) * 2;
-    float *at = s.wvOut + size_t(s.wvCursor) * column;
-    sl.waveBytes = size_t(columns) * column * sizeof(float);
-    SGZ_HIP(hipMemcpyAsync(s.wvPinned ? at : sl.h_wave, sl.d_wave, sl.waveBytes, hipMemcpyDeviceToHost, s.back));
-    sl.waveDst = s.wvPinned ? nullptr : at;
-    s.wvCursor += columns;
-    return SGZ_OK;
+    const sgz_status st = sl.out[kOutWave].readBack(s.wvOut + size_t(s.wvCursor) * column, size_t(columns) * column * sizeof(float), s.wvPinned, s.back);
+    if (st == SGZ_OK) s.wvCursor += columns;
+    return st;
 }
 
 // ---- the track lane inside the stream (sgz.h, "The track lane") ----------------------------------------------------------------------------
@@ -354,22 +354,212 @@ static sgz_status pcmTrackFits(const sgz_pcm_stream &s, uint64_t frames)
 // a slot's records of a piece, maxFrames * pairs of them (both slots are idle between feeds)
 static sgz_status pcmTrackBuffers(sgz_pcm_stream &s, PcmSlot &sl)
 {
-    if (!s.trArmed) return SGZ_OK;
-    const size_t bytes = size_t(s.cfg.num_pairs) * sizeof(sgz_line_peak);
-    if (sgz_status st = pcmGrow(&sl.d_track, &sl.trackCap, s.maxFrames, bytes, false); st != SGZ_OK) return st;
-    return s.trPinned ? SGZ_OK : pcmGrow(&sl.h_track, &sl.trackPinnedCap, s.maxFrames, bytes, true);
+    return s.trArmed ? sl.out[kOutTrack].reserve(s.maxFrames * s.cfg.num_pairs * sizeof(sgz_line_peak), !s.trPinned) : SGZ_OK;
 }
 
-// the piece's records to the caller's buffer at the cursor, on the read-back stream (behind ev[4]); pageable: to the twin, the drain copies
+// the records of the piece's `frames` frames to the caller's buffer at the cursor, on the read-back stream
 static sgz_status pcmTrackReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t frames)
 {
-    if (!s.trArmed || !frames) return SGZ_OK;
-    sgz_line_peak *at = s.trOut + size_t(s.trCursor) * s.cfg.num_pairs;
-    sl.trackBytes = size_t(frames) * s.cfg.num_pairs * sizeof(sgz_line_peak);
-    SGZ_HIP(hipMemcpyAsync(s.trPinned ? at : sl.h_track, sl.d_track, sl.trackBytes, hipMemcpyDeviceToHost, s.back));
-    sl.trackDst = s.trPinned ? nullptr : at;
-    s.trCursor += frames;
+    if (!frames) return SGZ_OK;
+    const size_t record = s.cfg.num_pairs;
+    const sgz_status st = sl.out[kOutTrack].readBack(s.trOut + size_t(s.trCursor) * record, size_t(frames) * record * sizeof(sgz_line_peak), s.trPinned, s.back);
+    if (st == SGZ_OK) s.trCursor += frames;
+    return st;
+}
+
+// ---- the piece loop ------------------------------------------------------------------------------------------------------------------------
+// What both feeds do once they have refused what they refuse.  The feed is cut into pieces of at most `chunk` samples; piece i uses slot i & 1:
+//   1. upload            copy stream: the samples to the slot (through its pinned block when the caller's are pageable)
+//   2. convert + render  compute stream, behind ev[1]: the converter behind the held tail, the waveform lane on the new samples, the Part's
+//                        render of what became complete (armed, the track lane's search with it), the new tail to the other planar buffer
+//   3. read back         read-back stream, behind ev[4]: the Part's rows, the track's records, the waveform's columns
+// The two kinds of feed differ in their Part alone: reserve(s, sl) makes its outputs in a slot before anything is consumed; render(s, sl,
+// planar, total, frames, last, &units) enqueues the render of a piece's frames and says how many rows -- `units`, what the feed counts and its
+// timing reports -- it leaves in the slot; readBack(s, sl, done, units) enqueues their copies behind the feed's `done` earlier rows.
+// emptyPiece: a feed without samples has one piece all the same (the overview's flush of an open column).
+template <typename Part>
+static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, bool emptyPiece, Part &part, uint64_t *unitsOut, sgz_pcm_timing *timing,
+                          PcmClock::time_point t0)
+{
+    if (timing) *timing = sgz_pcm_timing{};
+    const bool pcmPinned = nsamples && isPinnedHost(pcm);
+    // (the pinned blocks are made on first need: a caller with pinned memory of its own never pays for them)
+    for (PcmSlot &sl : s.slot) {
+        if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s.chunk * s.frameBytes, hipHostMallocDefault));
+        if (sgz_status st = part.reserve(s, sl); st != SGZ_OK) return st;
+        if (sgz_status st = pcmWaveBuffers(s, sl); st != SGZ_OK) return st;
+        if (sgz_status st = pcmTrackBuffers(s, sl); st != SGZ_OK) return st;
+    }
+    const uint8_t *src = static_cast<const uint8_t *>(pcm);
+    uint64_t done = 0, chunks = 0;
+    auto pieces = [&]() -> sgz_status {
+        for (size_t at = 0; at < nsamples || (emptyPiece && chunks == 0); ) {
+            const size_t n = std::min(s.chunk, nsamples - at);
+            PcmSlot &sl = s.slot[s.pieces & 1];
+            if (sgz_status st = pcmDrain(sl, timing); st != SGZ_OK) return st;      // the one wait inside a feed: the piece before last
+            uint64_t frames = 0, keep = 0;
+            if (sgz_status st = streamStep(s.cfg.window_size, s.cfg.hop, s.held, n, &frames, &keep); st != SGZ_OK) return st;
+            sl.timed = timing != nullptr;
+            // 1. upload (a piece without samples has none, and the compute stream nothing to wait for; timed, it still has its interval)
+            const void *from = n ? src + at * s.frameBytes : nullptr;
+            if (n && !pcmPinned) { std::memcpy(sl.h_pcm, from, n * s.frameBytes); from = sl.h_pcm; }
+            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[0], s.copy));
+            if (n) SGZ_HIP(hipMemcpyAsync(sl.d_pcm, from, n * s.frameBytes, hipMemcpyHostToDevice, s.copy));
+            if (n || sl.timed) SGZ_HIP(hipEventRecord(sl.ev[1], s.copy));
+            if (n) SGZ_HIP(hipStreamWaitEvent(s.compute, sl.ev[1], 0));
+            // 2. convert behind the held tail, render what became complete, move the new tail to the front of the other planar buffer
+            float *planar = s.d_planar[s.cur];
+            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[2], s.compute));
+            if (n)
+                if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s.format, s.srcChannels, n, s.map, s.numChannels, planar + s.held, s.stride, s.compute); st != SGZ_OK) return st;
+            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s.compute));
+            uint64_t waveColumns = 0, units = 0;
+            if (sgz_status st = pcmWavePiece(s, sl, planar + s.held, n, &waveColumns); st != SGZ_OK) return st;
+            const uint64_t total = s.held + n;
+            if (sgz_status st = part.render(s, sl, planar, size_t(total), frames, at + n == nsamples, &units); st != SGZ_OK) return st;
+            if (frames) {
+                if (keep) SGZ_HIP(hipMemcpy2DAsync(s.d_planar[s.cur ^ 1], s.stride * sizeof(float), planar + (total - keep), s.stride * sizeof(float),
+                                                   size_t(keep) * sizeof(float), s.numChannels, hipMemcpyDeviceToDevice, s.compute));
+                s.cur ^= 1;
+            }                                                                      // (no frame: the tail just grew where it is)
+            s.held = keep;
+            SGZ_HIP(hipEventRecord(sl.ev[4], s.compute));
+            // 3. read back (a piece may close waveform columns and complete no frame, or complete frames whose records are all it returns)
+            const uint64_t trackFrames = s.trArmed ? frames : 0;
+            sl.rendered = units > 0 || waveColumns > 0 || trackFrames > 0;
+            if (sl.rendered) {
+                SGZ_HIP(hipStreamWaitEvent(s.back, sl.ev[4], 0));
+                if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s.back));
+                if (units)
+                    if (sgz_status st = part.readBack(s, sl, done, units); st != SGZ_OK) return st;
+                if (sgz_status st = pcmTrackReadBack(s, sl, trackFrames); st != SGZ_OK) return st;
+                if (sgz_status st = pcmWaveReadBack(s, sl, waveColumns); st != SGZ_OK) return st;
+                SGZ_HIP(hipEventRecord(sl.ev[6], s.back));
+            }
+            sl.busy = true;
+            done += units; ++chunks; ++s.pieces; at += n;
+        }
+        // the end of the feed: both slots, the older piece first
+        for (uint64_t i = 0; i < 2; ++i)
+            if (sgz_status st = pcmDrain(s.slot[(s.pieces + i) & 1], timing); st != SGZ_OK) return st;
+        return SGZ_OK;
+    };
+    if (const sgz_status st = pieces(); st != SGZ_OK) {
+        // a failure among the pieces: nothing stays in flight, and both slots forget their pending host copies WITHOUT performing them -- those
+        // point into this call's output buffers, which the caller may free once it has the status (g_lastError stays the failure's)
+        for (hipStream_t q : {s.copy, s.compute, s.back}) (void)hipStreamSynchronize(q);
+        for (PcmSlot &sl : s.slot) { sl.busy = false; for (PcmOut &o : sl.out) o.dst = nullptr; }
+        return st;
+    }
+    if (unitsOut) *unitsOut = done;
+    if (timing) { timing->frames = done; timing->chunks = chunks; timing->wall_ms = pcmMsSince(t0); }
     return SGZ_OK;
+}
+
+// sgz_pcm_stream_feed's part: frames into the slot's image, and into its lines when the caller or the track lane wants them
+struct PcmFramesPart {
+    uint8_t *rgba; float *lines;
+    uint64_t need;                                                // the frames the whole feed yields
+    bool rgbaPinned, linesPinned;
+
+    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
+    {
+        if (!need) return SGZ_OK;
+        const sgz_status st = sl.out[kOutImage].reserve(pcmImageBytes(s, s.maxFrames), !rgbaPinned);
+        if (st != SGZ_OK || (!lines && !s.trArmed)) return st;    // (the track lane searches the line results: rendered, never read back for it)
+        return sl.out[kOutLines].reserve(pcmLinesFloats(s, s.maxFrames) * sizeof(float), lines && !linesPinned);
+    }
+    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t total, uint64_t frames, bool, uint64_t *units) const
+    {
+        *units = frames;
+        if (!frames) return SGZ_OK;
+        float *d_lines = (lines || s.trArmed) ? sl.out[kOutLines].as<float>() : nullptr;
+        const sgz_status st = sgz_spectrogram_render_device(s.plan, planar, s.stride, total, sl.out[kOutImage].as<uint8_t>(), d_lines, s.d_state, s.compute);
+        if (st != SGZ_OK || !s.trArmed) return st;
+        return runTrackPeaksLines(s.plan->impl, d_lines, size_t(frames), s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>(), s.compute);
+    }
+    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t frames) const
+    {
+        const sgz_status st = sl.out[kOutImage].readBack(rgba + pcmImageBytes(s, done), pcmImageBytes(s, frames), rgbaPinned, s.back);
+        if (st != SGZ_OK || !lines) return st;
+        return sl.out[kOutLines].readBack(lines + pcmLinesFloats(s, done), pcmLinesFloats(s, frames) * sizeof(float), linesPinned, s.back);
+    }
+};
+
+// sgz_pcm_stream_feed_overview's part: frames slab by slab into the columns they close, the open column in the stream's carry
+struct PcmColumnsPart {
+    uint8_t *rgba; float *peaks;
+    uint32_t k; int flush;
+    uint64_t need;                                                // the columns the whole feed yields
+    bool rgbaPinned, peaksPinned;
+
+    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
+    {
+        if (!s.d_ovCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovCarry), pcmPeaksFloats(s, 1) * sizeof(float)));
+        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
+        // the most columns one piece can close: floor((k - 1 + maxFrames) / k) = ceil(maxFrames / k), and one more from a flush
+        const size_t columns = (s.maxFrames + k - 1) / k + 1;
+        const sgz_status st = rgba ? sl.out[kOutOvImage].reserve(pcmImageBytes(s, columns), !rgbaPinned) : SGZ_OK;
+        if (st != SGZ_OK || !peaks) return st;
+        return sl.out[kOutOvPeaks].reserve(pcmPeaksFloats(s, columns) * sizeof(float), !peaksPinned);
+    }
+    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t total, uint64_t frames, bool last, uint64_t *units) const
+    {
+        const int pieceFlush = flush && last;
+        const uint64_t t = s.ovOpen + frames;
+        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
+        uint8_t *d_rgba = rgba ? sl.out[kOutOvImage].as<uint8_t>() : nullptr;
+        float *d_peaks = peaks ? sl.out[kOutOvPeaks].as<float>() : nullptr;
+        sgz_status st = SGZ_OK;
+        if (frames) {
+            const SlabTrack track{s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>()};
+            st = runOverviewSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovCarry, s.d_state, d_rgba, d_peaks,
+                                  s.compute, s.trArmed ? &track : nullptr);
+        } else if (*units) {                                       // no frame arrives and the open column is flushed
+            st = runOverviewColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovCarry, d_rgba, d_peaks, s.compute);
+        }
+        if (st != SGZ_OK) return st;
+        s.ovOpen = pieceFlush ? 0 : t % k;
+        s.ovK = k;
+        return SGZ_OK;
+    }
+    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
+    {
+        const sgz_status st = rgba ? sl.out[kOutOvImage].readBack(rgba + pcmImageBytes(s, done), pcmImageBytes(s, columns), rgbaPinned, s.back) : SGZ_OK;
+        if (st != SGZ_OK || !peaks) return st;
+        return sl.out[kOutOvPeaks].readBack(peaks + pcmPeaksFloats(s, done), pcmPeaksFloats(s, columns) * sizeof(float), peaksPinned, s.back);
+    }
+};
+
+// what the two one-shot calls share: a stream with no more device and pinned memory than the buffer needs, SGZ_SKIPPED_FRAME where nothing
+// comes out, the feed, and the wall time around all of it.  units(s): what the feed will yield; feed(s, units): the feed call
+template <typename Units, typename Feed>
+static sgz_status pcmOneShot(const sgz_spectrum_config *cfg, uint32_t format, uint32_t src_channels, const uint32_t *channel_map, size_t nsamples,
+                             sgz_pcm_timing *timing, Units units, Feed feed)
+{
+    const auto t0 = PcmClock::now();
+    sgz_pcm_stream *s = nullptr;
+    const uint32_t frameBytes = std::max(1u, src_channels * pcmSampleBytes(format));
+    const size_t chunk = std::min(std::min(kPcmDefaultChunk, kPcmDefaultSlotBytes / frameBytes), std::max<size_t>(nsamples, 1));
+    if (sgz_status st = sgz_pcm_stream_create(cfg, format, src_channels, channel_map, chunk, &s); st != SGZ_OK) return st;
+    const uint64_t yields = units(s);
+    sgz_status st = SGZ_SKIPPED_FRAME;
+    if (yields == 0) { if (timing) *timing = sgz_pcm_timing{}; }
+    else st = feed(s, yields);
+    const std::string keep = g_lastError;
+    sgz_pcm_stream_destroy(s);
+    g_lastError = keep;
+    if (timing && st == SGZ_OK) timing->wall_ms = pcmMsSince(t0);
+    return st;
+}
+
+// columns a feed of nsamples yields at k with the stream as it is; false: k == 0, or a k other than the open column's
+static bool pcmOverviewNeed(const sgz_pcm_stream *s, size_t nsamples, uint32_t k, int flush, uint64_t *columns)
+{
+    if (!s || k == 0 || (s->ovOpen && k != s->ovK)) return false;
+    const uint64_t t = s->ovOpen + sgz_pcm_stream_frames_for(s, nsamples);
+    *columns = t / k + ((flush && t % k) ? 1u : 0u);
+    return true;
 }
 
 extern "C" {
@@ -394,8 +584,9 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
     if (!s) return;
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamSynchronize(q);
     for (PcmSlot &sl : s->slot) {
-        for (void *p : {sl.h_pcm, (void *)sl.h_rgba, (void *)sl.h_lines, (void *)sl.h_ovRgba, (void *)sl.h_ovPeaks, (void *)sl.h_wave, (void *)sl.h_track}) if (p) (void)hipHostFree(p);
-        for (void *p : {sl.d_pcm, (void *)sl.d_rgba, (void *)sl.d_lines, (void *)sl.d_ovRgba, (void *)sl.d_ovPeaks, (void *)sl.d_wave, (void *)sl.d_track}) if (p) (void)hipFree(p);
+        if (sl.h_pcm) (void)hipHostFree(sl.h_pcm);
+        if (sl.d_pcm) (void)hipFree(sl.d_pcm);
+        for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
     for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry}) if (p) (void)hipFree(p);
@@ -429,7 +620,7 @@ sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format
     for (PcmSlot &sl : s->slot) {
         for (hipEvent_t &e : sl.ev) SGZ_PCM_TRY(hipEventCreate(&e));
         SGZ_PCM_TRY(hipMalloc(&sl.d_pcm, s->chunk * s->frameBytes));
-        SGZ_PCM_TRY(hipMalloc(reinterpret_cast<void **>(&sl.d_rgba), s->maxFrames * cfg->axis_points * 4));
+        if (sgz_status st = sl.out[kOutImage].reserve(pcmImageBytes(*s, s->maxFrames), false); st != SGZ_OK) return bail(st);
     }
     for (float *&p : s->d_planar) SGZ_PCM_TRY(hipMalloc(reinterpret_cast<void **>(&p), size_t(s->numChannels) * s->stride * sizeof(float)));
     SGZ_PCM_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_state), pcmStateBytes(*s)));
@@ -461,7 +652,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
 sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint8_t *rgba_out, float *lines_out,
                                uint64_t capacity_frames, uint64_t *frames_out, sgz_pcm_timing *timing)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = PcmClock::now();
     if (!s) return fail(SGZ_EINVAL, "null stream");
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null pcm");
     if (s->ovOpen) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: an overview column is open -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
@@ -471,119 +662,20 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     if (need && !rgba_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null rgba_out");
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTrackFits(*s, need); st != SGZ_OK) return st;
-    if (timing) *timing = sgz_pcm_timing{};
-    const uint32_t W = s->cfg.window_size, hop = s->cfg.hop, P = s->cfg.axis_points;
-    const bool wantLines = lines_out || s->trArmed;             // the track lane searches the line results: rendered, never read back for it
-    const bool pcmPinned = nsamples && isPinnedHost(pcm);
-    const bool rgbaPinned = need && isPinnedHost(rgba_out), linesPinned = need && lines_out && isPinnedHost(lines_out);
-    // (the pinned slots and the lines buffers are made on first need: a caller with pinned memory of its own never pays for them)
-    for (PcmSlot &sl : s->slot) {
-        if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s->chunk * s->frameBytes, hipHostMallocDefault));
-        if (need && !rgbaPinned && !sl.h_rgba) SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_rgba), s->maxFrames * P * 4, hipHostMallocDefault));
-        if (need && wantLines && !sl.d_lines) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&sl.d_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float)));
-        if (need && lines_out && !linesPinned && !sl.h_lines)
-            SGZ_HIP(hipHostMalloc(reinterpret_cast<void **>(&sl.h_lines), pcmLinesFloats(*s, s->maxFrames) * sizeof(float), hipHostMallocDefault));
-        if (sgz_status st = pcmWaveBuffers(*s, sl); st != SGZ_OK) return st;
-        if (sgz_status st = pcmTrackBuffers(*s, sl); st != SGZ_OK) return st;
-    }
-    const uint8_t *src = static_cast<const uint8_t *>(pcm);
-    uint64_t framesDone = 0, chunks = 0;
-    for (size_t at = 0; at < nsamples; ) {
-        const size_t n = std::min(s->chunk, nsamples - at);
-        PcmSlot &sl = s->slot[s->pieces & 1];
-        if (sgz_status st = pcmDrain(sl, timing); st != SGZ_OK) return st;          // the one wait inside a feed: the piece before last
-        uint64_t frames = 0, keep = 0;
-        if (sgz_status st = streamStep(W, hop, s->held, n, &frames, &keep); st != SGZ_OK) return st;
-        const size_t bytes = n * s->frameBytes;
-        const void *from = src + at * s->frameBytes;
-        if (!pcmPinned) { std::memcpy(sl.h_pcm, from, bytes); from = sl.h_pcm; }
-        // 1. upload
-        sl.timed = timing != nullptr;
-        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[0], s->copy));
-        SGZ_HIP(hipMemcpyAsync(sl.d_pcm, from, bytes, hipMemcpyHostToDevice, s->copy));
-        SGZ_HIP(hipEventRecord(sl.ev[1], s->copy));
-        // 2. convert behind the held tail, render what became complete, move the new tail to the front of the other planar buffer
-        float *planar = s->d_planar[s->cur];
-        SGZ_HIP(hipStreamWaitEvent(s->compute, sl.ev[1], 0));
-        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[2], s->compute));
-        if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s->format, s->srcChannels, n, s->map, s->numChannels, planar + s->held, s->stride, s->compute); st != SGZ_OK) return st;
-        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s->compute));
-        uint64_t waveColumns = 0;
-        if (sgz_status st = pcmWavePiece(*s, sl, planar + s->held, n, &waveColumns); st != SGZ_OK) return st;
-        const uint64_t total = s->held + n;
-        sl.rendered = frames > 0 || waveColumns > 0;               // (a piece may close waveform columns and complete no frame)
-        if (frames) {
-            sgz_status st = sgz_spectrogram_render_device(s->plan, planar, s->stride, size_t(total), sl.d_rgba, wantLines ? sl.d_lines : nullptr, s->d_state, s->compute);
-            if (st != SGZ_OK) return st;
-            if (s->trArmed && (st = runTrackPeaksLines(s->plan->impl, sl.d_lines, size_t(frames), s->trGraph, s->trFraction, sl.d_track, s->compute)) != SGZ_OK) return st;
-            if (keep) SGZ_HIP(hipMemcpy2DAsync(s->d_planar[s->cur ^ 1], s->stride * sizeof(float), planar + (total - keep), s->stride * sizeof(float),
-                                               size_t(keep) * sizeof(float), s->numChannels, hipMemcpyDeviceToDevice, s->compute));
-            s->cur ^= 1;
-        }                                                                          // (no frame: the tail just grew where it is)
-        s->held = keep;
-        SGZ_HIP(hipEventRecord(sl.ev[4], s->compute));
-        // 3. read back
-        if (sl.rendered) {
-            SGZ_HIP(hipStreamWaitEvent(s->back, sl.ev[4], 0));
-            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s->back));
-            if (frames) {
-                sl.rgbaBytes = size_t(frames) * P * 4; sl.linesBytes = pcmLinesFloats(*s, frames) * sizeof(float);
-                uint8_t *rgbaAt = rgba_out + size_t(framesDone) * P * 4;
-                float *linesAt = lines_out ? lines_out + pcmLinesFloats(*s, framesDone) : nullptr;
-                SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_rgba, sl.d_rgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
-                if (lines_out) SGZ_HIP(hipMemcpyAsync(linesPinned ? linesAt : sl.h_lines, sl.d_lines, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
-                sl.rgbaDst = rgbaPinned ? nullptr : rgbaAt; sl.rgbaFrom = sl.h_rgba;
-                sl.linesDst = (lines_out && !linesPinned) ? linesAt : nullptr; sl.linesFrom = sl.h_lines;
-            }
-            if (sgz_status st = pcmTrackReadBack(*s, sl, frames); st != SGZ_OK) return st;
-            if (sgz_status st = pcmWaveReadBack(*s, sl, waveColumns); st != SGZ_OK) return st;
-            SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
-        }
-        sl.busy = true;
-        framesDone += frames; ++chunks; ++s->pieces; at += n;
-    }
-    // the end of the feed: both slots, the older piece first
-    for (uint64_t k = 0; k < 2; ++k)
-        if (sgz_status st = pcmDrain(s->slot[(s->pieces + k) & 1], timing); st != SGZ_OK) return st;
-    if (frames_out) *frames_out = framesDone;
-    if (timing) {
-        timing->frames = framesDone; timing->chunks = chunks;
-        timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return SGZ_OK;
+    PcmFramesPart part{rgba_out, lines_out, need, need && isPinnedHost(rgba_out), need && lines_out && isPinnedHost(lines_out)};
+    return pcmFeed(*s, pcm, nsamples, false, part, frames_out, timing, t0);
 }
 
 sgz_status sgz_spectrogram_render_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                       const uint32_t *channel_map, size_t nsamples, uint8_t *rgba_out, float *lines_out, sgz_pcm_timing *timing)
 {
-    const auto t0 = std::chrono::steady_clock::now();
     if (!cfg || !pcm || !rgba_out) return fail(SGZ_EINVAL, "null argument");
-    sgz_pcm_stream *s = nullptr;
-    // (no more device and pinned memory than the buffer needs)
-    const uint32_t frameBytes = std::max(1u, src_channels * sgz_pcm_sample_bytes(format));
-    const size_t chunk = std::min(std::min(kPcmDefaultChunk, kPcmDefaultSlotBytes / frameBytes), std::max<size_t>(nsamples, 1));
-    if (sgz_status st = sgz_pcm_stream_create(cfg, format, src_channels, channel_map, chunk, &s); st != SGZ_OK) return st;
-    uint64_t frames = sgz_pcm_stream_frames_for(s, nsamples);
-    sgz_status st = SGZ_SKIPPED_FRAME;
-    if (frames == 0) { if (timing) *timing = sgz_pcm_timing{}; }
-    else st = sgz_pcm_stream_feed(s, pcm, nsamples, rgba_out, lines_out, frames, &frames, timing);
-    const std::string keep = g_lastError;
-    sgz_pcm_stream_destroy(s);
-    g_lastError = keep;
-    if (timing && st == SGZ_OK) timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return st;
+    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
+                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_frames_for(s, nsamples); },
+                      [&](sgz_pcm_stream *s, uint64_t frames) { return sgz_pcm_stream_feed(s, pcm, nsamples, rgba_out, lines_out, frames, &frames, timing); });
 }
 
 // ---- the overview inside the stream (sgz.h, "the overview inside sgz_pcm_stream") ----------------------------------------------------------
-// columns a feed of nsamples yields at k with the stream as it is; false: k == 0, or a k other than the open column's
-static bool pcmOverviewNeed(const sgz_pcm_stream *s, size_t nsamples, uint32_t k, int flush, uint64_t *columns)
-{
-    if (!s || k == 0 || (s->ovOpen && k != s->ovK)) return false;
-    const uint64_t t = s->ovOpen + sgz_pcm_stream_frames_for(s, nsamples);
-    *columns = t / k + ((flush && t % k) ? 1u : 0u);
-    return true;
-}
-
 uint64_t sgz_pcm_stream_columns_for(const sgz_pcm_stream *s, size_t nsamples, uint32_t k, int flush)
 {
     uint64_t columns = 0;
@@ -601,7 +693,7 @@ sgz_status sgz_pcm_stream_set_option(sgz_pcm_stream *s, uint32_t option, uint32_
 sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush, uint8_t *rgba_out, float *peaks_out,
                                         uint64_t capacity_columns, uint64_t *columns_out, sgz_pcm_timing *timing)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = PcmClock::now();
     if (!s) return fail(SGZ_EINVAL, "null stream");
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: null pcm");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
@@ -613,130 +705,20 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)");
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTrackFits(*s, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
-    if (timing) *timing = sgz_pcm_timing{};
-    const uint32_t W = s->cfg.window_size, hop = s->cfg.hop, P = s->cfg.axis_points, C = s->cfg.num_pairs;
-    const bool pcmPinned = nsamples && isPinnedHost(pcm);
-    const bool rgbaPinned = need && rgba_out && isPinnedHost(rgba_out), peaksPinned = need && peaks_out && isPinnedHost(peaks_out);
-    // the most columns one piece can close: floor((k - 1 + maxFrames) / k) = ceil(maxFrames / k), and one more from a flush
-    const size_t slotColumns = (s->maxFrames + k - 1) / k + 1;
-    if (!s->d_ovCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_ovCarry), size_t(C) * P * sizeof(float)));
-    for (PcmSlot &sl : s->slot) {                                 // (both slots are idle between feeds)
-        if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s->chunk * s->frameBytes, hipHostMallocDefault));
-        sgz_status st = pcmWaveBuffers(*s, sl);
-        if (st != SGZ_OK) return st;
-        if ((st = pcmTrackBuffers(*s, sl)) != SGZ_OK) return st;
-        if (!need) continue;                                      // (no column closes: nothing is written or read back)
-        if (rgba_out && (st = pcmGrow(&sl.d_ovRgba, &sl.ovRgbaCap, slotColumns, size_t(P) * 4, false)) != SGZ_OK) return st;
-        if (rgba_out && !rgbaPinned && (st = pcmGrow(&sl.h_ovRgba, &sl.ovRgbaPinnedCap, slotColumns, size_t(P) * 4, true)) != SGZ_OK) return st;
-        if (peaks_out && (st = pcmGrow(&sl.d_ovPeaks, &sl.ovPeaksCap, slotColumns, size_t(C) * P * sizeof(float), false)) != SGZ_OK) return st;
-        if (peaks_out && !peaksPinned && (st = pcmGrow(&sl.h_ovPeaks, &sl.ovPeaksPinnedCap, slotColumns, size_t(C) * P * sizeof(float), true)) != SGZ_OK) return st;
-    }
-    const uint8_t *src = static_cast<const uint8_t *>(pcm);
-    uint64_t columnsDone = 0, chunks = 0;
+    PcmColumnsPart part{rgba_out, peaks_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && peaks_out && isPinnedHost(peaks_out)};
     // (a feed without samples still has one piece when it flushes an open column)
-    for (size_t at = 0; at < nsamples || (chunks == 0 && flush && s->ovOpen); ) {
-        const size_t n = std::min(s->chunk, nsamples - at);
-        const bool last = at + n == nsamples;
-        PcmSlot &sl = s->slot[s->pieces & 1];
-        if (sgz_status st = pcmDrain(sl, timing); st != SGZ_OK) return st;          // the one wait inside a feed: the piece before last
-        uint64_t frames = 0, keep = 0;
-        if (sgz_status st = streamStep(W, hop, s->held, n, &frames, &keep); st != SGZ_OK) return st;
-        sl.timed = timing != nullptr;
-        // 1. upload
-        if (n) {
-            const size_t bytes = n * s->frameBytes;
-            const void *from = src + at * s->frameBytes;
-            if (!pcmPinned) { std::memcpy(sl.h_pcm, from, bytes); from = sl.h_pcm; }
-            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[0], s->copy));
-            SGZ_HIP(hipMemcpyAsync(sl.d_pcm, from, bytes, hipMemcpyHostToDevice, s->copy));
-            SGZ_HIP(hipEventRecord(sl.ev[1], s->copy));
-            SGZ_HIP(hipStreamWaitEvent(s->compute, sl.ev[1], 0));
-        } else if (sl.timed) {
-            SGZ_HIP(hipEventRecord(sl.ev[0], s->copy));
-            SGZ_HIP(hipEventRecord(sl.ev[1], s->copy));
-        }
-        // 2. convert behind the held tail, render what became complete slab by slab into the columns, move the new tail
-        float *planar = s->d_planar[s->cur];
-        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[2], s->compute));
-        if (n)
-            if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s->format, s->srcChannels, n, s->map, s->numChannels, planar + s->held, s->stride, s->compute); st != SGZ_OK) return st;
-        if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s->compute));
-        uint64_t waveColumns = 0;
-        if (sgz_status st = pcmWavePiece(*s, sl, planar + s->held, n, &waveColumns); st != SGZ_OK) return st;
-        const uint64_t total = s->held + n;
-        const int pieceFlush = flush && last;
-        const uint64_t t = s->ovOpen + frames;
-        const uint64_t columns = t / k + ((pieceFlush && t % k) ? 1u : 0u);
-        uint8_t *d_rgba = rgba_out ? sl.d_ovRgba : nullptr;
-        float *d_peaks = peaks_out ? sl.d_ovPeaks : nullptr;
-        if (frames) {
-            const SlabTrack track{s->trGraph, s->trFraction, sl.d_track};
-            const sgz_status st = runOverviewSlabs(s->plan, planar, s->stride, size_t(total), long(frames), k, uint32_t(s->ovOpen), pieceFlush, s->d_ovCarry,
-                                                   s->d_state, d_rgba, d_peaks, s->compute, s->trArmed ? &track : nullptr);
-            if (st != SGZ_OK) return st;
-            if (keep) SGZ_HIP(hipMemcpy2DAsync(s->d_planar[s->cur ^ 1], s->stride * sizeof(float), planar + (total - keep), s->stride * sizeof(float),
-                                               size_t(keep) * sizeof(float), s->numChannels, hipMemcpyDeviceToDevice, s->compute));
-            s->cur ^= 1;
-        } else if (columns) {                                                      // no frame arrives and the open column is flushed
-            const sgz_status st = runOverviewColumns(s->plan->impl, nullptr, 0, k, uint32_t(s->ovOpen), 1, 0, s->d_ovCarry, d_rgba, d_peaks, s->compute);
-            if (st != SGZ_OK) return st;
-        }
-        s->held = keep;
-        s->ovOpen = pieceFlush ? 0 : t % k;
-        s->ovK = k;
-        SGZ_HIP(hipEventRecord(sl.ev[4], s->compute));
-        // 3. read back the columns that closed
-        const uint64_t trackFrames = s->trArmed ? frames : 0;      // (a piece may complete frames and close no column)
-        sl.rendered = columns > 0 || waveColumns > 0 || trackFrames > 0;
-        if (sl.rendered) {
-            SGZ_HIP(hipStreamWaitEvent(s->back, sl.ev[4], 0));
-            if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s->back));
-            if (columns) {
-                sl.rgbaBytes = size_t(columns) * P * 4; sl.linesBytes = size_t(columns) * C * P * sizeof(float);
-                uint8_t *rgbaAt = rgba_out ? rgba_out + size_t(columnsDone) * P * 4 : nullptr;
-                float *peaksAt = peaks_out ? peaks_out + size_t(columnsDone) * C * P : nullptr;
-                if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgbaPinned ? rgbaAt : sl.h_ovRgba, sl.d_ovRgba, sl.rgbaBytes, hipMemcpyDeviceToHost, s->back));
-                if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaksPinned ? peaksAt : sl.h_ovPeaks, sl.d_ovPeaks, sl.linesBytes, hipMemcpyDeviceToHost, s->back));
-                sl.rgbaDst = (rgba_out && !rgbaPinned) ? rgbaAt : nullptr; sl.rgbaFrom = sl.h_ovRgba;
-                sl.linesDst = (peaks_out && !peaksPinned) ? peaksAt : nullptr; sl.linesFrom = sl.h_ovPeaks;
-            }
-            if (sgz_status st = pcmTrackReadBack(*s, sl, trackFrames); st != SGZ_OK) return st;
-            if (sgz_status st = pcmWaveReadBack(*s, sl, waveColumns); st != SGZ_OK) return st;
-            SGZ_HIP(hipEventRecord(sl.ev[6], s->back));
-        }
-        sl.busy = true;
-        columnsDone += columns; ++chunks; ++s->pieces; at += n;
-    }
-    for (uint64_t i = 0; i < 2; ++i)
-        if (sgz_status st = pcmDrain(s->slot[(s->pieces + i) & 1], timing); st != SGZ_OK) return st;
-    if (columns_out) *columns_out = columnsDone;
-    if (timing) {
-        timing->frames = columnsDone; timing->chunks = chunks;
-        timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return SGZ_OK;
+    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
 }
 
 sgz_status sgz_spectrogram_overview_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                         const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out, float *peaks_out, sgz_pcm_timing *timing)
 {
-    const auto t0 = std::chrono::steady_clock::now();
     if (!cfg || !pcm) return fail(SGZ_EINVAL, "null argument");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
-    sgz_pcm_stream *s = nullptr;
-    const uint32_t frameBytes = std::max(1u, src_channels * sgz_pcm_sample_bytes(format));
-    const size_t chunk = std::min(std::min(kPcmDefaultChunk, kPcmDefaultSlotBytes / frameBytes), std::max<size_t>(nsamples, 1));
-    if (sgz_status st = sgz_pcm_stream_create(cfg, format, src_channels, channel_map, chunk, &s); st != SGZ_OK) return st;
-    uint64_t columns = sgz_pcm_stream_columns_for(s, nsamples, k, 1);
-    sgz_status st = SGZ_SKIPPED_FRAME;
-    if (columns == 0) { if (timing) *timing = sgz_pcm_timing{}; }
-    else st = sgz_pcm_stream_feed_overview(s, pcm, nsamples, k, 1, rgba_out, peaks_out, columns, &columns, timing);
-    const std::string keep = g_lastError;
-    sgz_pcm_stream_destroy(s);
-    g_lastError = keep;
-    if (timing && st == SGZ_OK) timing->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return st;
+    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
+                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
+                      [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview(s, pcm, nsamples, k, 1, rgba_out, peaks_out, columns, &columns, timing); });
 }
 
 // ---- the waveform lane's calls ----------------------------------------------------------------------------------------------------------------
@@ -781,13 +763,14 @@ sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s)
     if (sgz_status st = pcmWaveBuffers(*s, sl); st != SGZ_OK) return st;
     const WaveColumnsShape sh = waveColumnsShape(s->numChannels, 0, s->wvM, uint32_t(s->wvOpen), 1, 0);
     const sgz_status st = runWaveColumns(sh, s->d_planar[s->cur], s->stride, s->numChannels, 0, s->wvM, uint32_t(s->wvOpen), pcmWaveCarry(*s, s->wvCur),
-                                         pcmWaveCarry(*s, s->wvCur ^ 1), sl.d_wave, nullptr, s->compute);
+                                         pcmWaveCarry(*s, s->wvCur ^ 1), sl.out[kOutWave].as<float>(), nullptr, s->compute);
     if (st != SGZ_OK) return st;
-    const size_t bytes = size_t(s->numChannels) * 2 * sizeof(float);
-    float *at = s->wvOut + size_t(s->wvCursor) * s->numChannels * 2;
-    SGZ_HIP(hipMemcpyAsync(s->wvPinned ? at : sl.h_wave, sl.d_wave, bytes, hipMemcpyDeviceToHost, s->compute));
-    SGZ_HIP(hipStreamSynchronize(s->compute));
-    if (!s->wvPinned) std::memcpy(at, sl.h_wave, bytes);
+    // the one column behind the launch on the compute stream itself, and waited for
+    const size_t column = size_t(s->numChannels) * 2;
+    PcmOut &out = sl.out[kOutWave];
+    if (sgz_status rb = out.readBack(s->wvOut + size_t(s->wvCursor) * column, column * sizeof(float), s->wvPinned, s->compute); rb != SGZ_OK) return rb;
+    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) { out.dst = nullptr; return hipFail(e, "hipStreamSynchronize(s->compute)"); }
+    out.drain();
     s->wvOpen = 0;
     ++s->wvCursor;
     return SGZ_OK;
