@@ -49,6 +49,10 @@ extern "C" {
  * (5, later: the track lane -- sgz_track_peak_values, sgz_stage_track_peaks_values and, on the PCM stream, sgz_pcm_stream_set_track,
  *  sgz_pcm_stream_track_for, sgz_pcm_stream_track_state.  No existing entry point or struct changed and the suite pins 5; a stream that was
  *  never armed enqueues what it did before.  A binding that needs them looks the symbols up.)
+ * (5, later: the level lane -- sgz_level_record, sgz_level_reading, sgz_stage_level_columns, sgz_level_columns_limits, the host helpers
+ *  sgz_level_fold and sgz_level_readout and, on the PCM stream, sgz_pcm_stream_set_level, sgz_pcm_stream_level_for,
+ *  sgz_pcm_stream_level_state, sgz_pcm_stream_flush_level.  No existing entry point or struct changed and the suite pins 5; a stream that
+ *  was never armed enqueues what it did before.  A binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -625,6 +629,100 @@ sgz_status sgz_pcm_stream_set_waveform(sgz_pcm_stream *s, uint32_t m /*0 = off*/
 uint64_t   sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
 sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
 sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s);
+
+/* The level lane: exact RMS, DC, "overs" and stereo correlation per screen column and channel pair of a file's samples -- the RMS body an
+ * editor draws inside the waveform lane's peak envelope, its DC line, its over marks and its correlation trace -- reduced on the device
+ * from the same planar floats.  The reference has no counterpart: its meters are live (the Vectorscope's drawStereoMeters reads one-pole
+ * filters, here sgz_vector_meters); nothing of them is reused or contradicted.
+ * A floating-point sum has no cut-independent bits; an integer sum has.  Every sample is quantised ONCE to a fixed-point integer and every
+ * quantity is a sum of integers.
+ * Definition (exact, no tolerance): let x[d][i] be the fp32 samples of channel d (the stream's converted floats, exactly what
+ * sgz_pcm_to_planar_device writes), pair p the channels (2p, 2p + 1) = (L, R), S the samples so far and m >= 1 the samples per column.
+ * Column c covers samples c m <= i < min((c + 1) m, S), counted exactly as the waveform lane counts them; only a flushed last column may
+ * be partial.  The quantiser (a NaN takes no part):
+ *     v = (int32) clamp(rintf(x * 2^23), -2^26, +2^26)
+ * -- the multiply is exact (a power of two), the rounding is to nearest, ties to even, the lane saturates at +-8.0 (+18 dBFS), +-inf
+ * saturate, and denormals quantise to 0 whether or not the device flushes them.  At this scale the quantiser is the identity on 8-, 16-
+ * and 24-bit integer PCM: for such files the lane is the file's level exactly.  One sgz_level_record per (column, pair), layout
+ * [columns][pairs], 80 bytes, little-endian; arrays of it on the DEVICE are aligned to 16 bytes:
+ *     sumsq[ch]  sum of v^2 of channel ch of the pair (0 = L, 1 = R), an unsigned 128-bit integer as (lo, hi)
+ *     cross      sum of v_L v_R over the sample frames where neither side is a NaN, 128-bit two's complement as (lo, hi)
+ *     sum[ch]    sum of v
+ *     count[ch]  the non-NaN samples
+ *     overs[ch]  the non-NaN samples with |v| >= 2^23 (at or over full scale)
+ * Bounds, with m <= 2^32 - 1: count fits 32 bits, |sum| < 2^58, sumsq and |cross| < 2^84.  A column of NaNs alone is the all-zero record.
+ * Integer sums are associative and commutative, so any cut of the stream (feeds, pieces, calls with a carry) or of a column (lanes,
+ * slices) gives the same bits, and a coarser column is the field-wise sum of the finer ones it covers: how a host zooms kept records out
+ * (sgz_level_fold).  The counts are sgz_overview_step's with samples in the place of frames: (m, held, nsamples, flush) -> columns,
+ * held_out.
+ *  sgz_stage_level_columns  DEVICE pointers.  d_planar [2 pairs][channel_stride], the first nsamples of each row (any 4-byte-aligned
+ *                      address).  held: samples of the open column that earlier calls took (< m).  d_carry: DEVICE sgz_level_record
+ *                      [pairs], the open column so far -- read iff held > 0, written iff samples stay open afterwards (no flush,
+ *                      (held + nsamples) % m != 0), NULL allowed when neither applies; a carried column continues exactly as if its
+ *                      samples had come in one call.  d_level: DEVICE sgz_level_record [columns][pairs], columns as sgz_overview_step
+ *                      counts them (NULL allowed when none closes).  nsamples == 0 with held > 0 and flush: one column from the carry
+ *                      alone.  m up to the switch-over (1024; sgz_level_columns_limits) runs one workgroup per (pair, tile of 4096 / m
+ *                      whole columns of both rows); longer columns are reduced in slices per column into scratch and folded by a
+ *                      second launch.  slices: 0 = the library's choice (m above the switch-over: the fewest slices that give two
+ *                      workgroups per CU), 1 .. 64 forced -- 2 and more take the sliced form whatever m is, 1 takes the form m
+ *                      implies -- identical bits.  Only the documented bytes are written.  Asynchronous on `stream`, nothing is waited
+ *                      for; scratch is allocated and freed in stream order.  SGZ_EINVAL, nothing launched or written: a null d_planar,
+ *                      pairs == 0 or > 32, m == 0, held >= m, channel_stride < nsamples, slices > 64, a needed d_carry or d_level that
+ *                      is NULL, d_planar not aligned to 4 bytes, d_carry or d_level not aligned to 16.  nsamples == 0 with nothing to
+ *                      flush: SGZ_OK, nothing launched.
+ *  sgz_level_columns_limits  the switch-over and the tile's samples per row (either result may be NULL).
+ * The lane inside the sgz_pcm_stream handle -- above, "interleaved PCM in": while armed, every feed of either kind also reduces the new samples of
+ * each piece -- the stream's converted floats, exactly sgz_pcm_to_planar_device's -- on the compute stream behind the conversion, and
+ * reads the records that closed back on the read-back stream into level_out at a cursor.  The records of all feeds and the final flush,
+ * concatenated, are the lane of the stream's converted floats bit for bit, however it is cut into feeds and pieces and whichever kind the
+ * feeds are; the image, lines, overview, peaks, waveform columns and track records of an armed stream are those of an unarmed one byte
+ * for byte.  The lane's m is its own: the waveform lane may be armed beside it with another.
+ *  sgz_pcm_stream_set_level   between feeds.  m > 0 arms: level_out HOST sgz_level_record [capacity_columns][pairs] (aligned to 8 bytes;
+ *                      pinned memory is written in place, pageable memory through a pinned twin per slot), the cursor restarts at 0.
+ *                      The same m with another buffer keeps the open column: how a caller with a small buffer drains.  m == 0 disarms
+ *                      and drops the open column.  SGZ_EINVAL: a null stream, a null level_out with capacity_columns > 0, a level_out
+ *                      that is not aligned, another m while samples are open.
+ *  sgz_pcm_stream_level_for   columns the next feed of nsamples closes (flush != 0: that feed followed by sgz_pcm_stream_flush_level);
+ *                      0 when disarmed.
+ *  sgz_pcm_stream_level_state columns written since the lane was armed (the cursor) and the open column's samples; either may be NULL.
+ *  sgz_pcm_stream_flush_level closes the open column: one launch on the carry, one column read back, waits.  Nothing open: SGZ_OK,
+ *                      nothing done.  SGZ_EINVAL: disarmed, no column left in the buffer.
+ * A feed that would close more columns than the buffer has left is refused with SGZ_EINVAL before anything is consumed.  reset drops the
+ * open column and restarts the cursor.  Per slot the records of a piece take ceil(chunk_samples / m) + 1 columns of device (and, for a
+ * pageable buffer, pinned) memory, made on first need and grown when a later m needs more: memory is bounded by chunk_samples and m.
+ * Host arithmetic on HOST records, nothing launched:
+ *  sgz_level_fold      the zoom: source columns [x0, x1) of in [n][pairs], w = x1 - x0, into cols = min(out_columns, w) columns of out
+ *                      [cols][pairs]; output column b is the field-wise sum of source columns x0 + ceil(b w / cols) <= j < x0 +
+ *                      ceil((b + 1) w / cols) -- the boundary rule of the view of kept peaks (sgz_overview_view_columns), so the lanes
+ *                      of a file zoom together.  128-bit fields add with carry.  out must not overlap in.  SGZ_EINVAL, nothing
+ *                      written: a null argument, pairs == 0, what sgz_overview_view_columns refuses, a folded count above 2^32 - 1.
+ *  sgz_level_readout   what a host draws from one record, in fp64: per channel mean square = sumsq / (count 2^46), rms = its square
+ *                      root, rms_db = 10 log10(mean square) (-inf for silence, NaN for count 0), dc = sum / (count 2^23) (NaN for
+ *                      count 0); correlation = cross / sqrt(sumsq_L sumsq_R), 0 when either is 0.  1.0 is full scale.  A 128-bit value
+ *                      becomes a double through its magnitude (a negative cross is negated first: hi 2^64 + lo of -5 would cancel to
+ *                      0).  SGZ_EINVAL: a null argument. */
+typedef struct sgz_level_record {
+    uint64_t sumsq[2][2];   /* [channel of the pair][lo, hi] */
+    uint64_t cross[2];      /* lo, hi */
+    int64_t  sum[2];
+    uint32_t count[2];
+    uint32_t overs[2];
+} sgz_level_record;         /* 80 bytes */
+typedef struct sgz_level_reading {
+    double rms[2], rms_db[2], dc[2];
+    double correlation;
+} sgz_level_reading;
+sgz_status sgz_stage_level_columns(const float *d_planar, size_t channel_stride, uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held,
+                                   int flush, uint32_t slices, sgz_level_record *d_carry /*[pairs]*/, sgz_level_record *d_level /*[columns][pairs]*/,
+                                   void *stream);
+void       sgz_level_columns_limits(uint32_t *switch_over, uint32_t *tile_samples);
+sgz_status sgz_pcm_stream_set_level(sgz_pcm_stream *s, uint32_t m /*0 = off*/, sgz_level_record *level_out /*HOST [capacity][pairs]*/,
+                                    uint64_t capacity_columns);
+uint64_t   sgz_pcm_stream_level_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
+sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
+sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s);
+sgz_status sgz_level_fold(const sgz_level_record *in, size_t n, uint32_t pairs, size_t x0, size_t x1, uint32_t out_columns, sgz_level_record *out);
+sgz_status sgz_level_readout(const sgz_level_record *rec, sgz_level_reading *out);
 
 /* The track lane: the tracker's curve over a file -- the reference's drawFrequencyTracking readout (SpectrumRendering.cpp:300-377, the
  * line-results branch) for every frame of a streamed file, in bounded memory.  sgz_spectrogram_track_device / _host want the whole file

@@ -110,6 +110,15 @@ class VectorMeters(C.Structure):
     _fields_ = [("balance", C.c_float * 2), ("stereo", C.c_float * 2)]
 
 
+class LevelReading(C.Structure):
+    _fields_ = [("rms", C.c_double * 2), ("rms_db", C.c_double * 2), ("dc", C.c_double * 2), ("correlation", C.c_double)]
+
+
+# sgz_level_record: one per (column, pair) of the level lane; 80 bytes, little-endian
+LEVEL_DTYPE = np.dtype([("sumsq", "<u8", (2, 2)), ("cross", "<u8", (2,)), ("sum", "<i8", (2,)), ("count", "<u4", (2,)), ("overs", "<u4", (2,))])
+assert LEVEL_DTYPE.itemsize == 80
+
+
 class LineGraphStyle(C.Structure):
     _fields_ = [("colour_one", (C.c_uint8 * 4) * NUM_GRAPHS), ("colour_two", (C.c_uint8 * 4) * NUM_GRAPHS), ("flood_alpha", C.c_float),
                 ("primitive_size", C.c_float), ("rendering_scale", C.c_double)]
@@ -198,6 +207,8 @@ EXPORTS = [
     "sgz_stage_wave_columns", "sgz_wave_columns_limits", "sgz_pcm_stream_set_waveform", "sgz_pcm_stream_waveform_for",
     "sgz_pcm_stream_waveform_state", "sgz_pcm_stream_flush_waveform",
     "sgz_track_peak_values", "sgz_stage_track_peaks_values", "sgz_pcm_stream_set_track", "sgz_pcm_stream_track_for", "sgz_pcm_stream_track_state",
+    "sgz_stage_level_columns", "sgz_level_columns_limits", "sgz_pcm_stream_set_level", "sgz_pcm_stream_level_for", "sgz_pcm_stream_level_state",
+    "sgz_pcm_stream_flush_level", "sgz_level_fold", "sgz_level_readout",
 ]
 
 
@@ -428,6 +439,16 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_track_for.restype = u64
     L.sgz_pcm_stream_track_state.argtypes = [vp, C.POINTER(u64)]
     L.sgz_spectrogram_overview_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, C.POINTER(PcmTiming)]
+    L.sgz_stage_level_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
+    L.sgz_level_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    L.sgz_level_columns_limits.restype = None
+    L.sgz_pcm_stream_set_level.argtypes = [vp, u32, vp, u64]
+    L.sgz_pcm_stream_level_for.argtypes = [vp, sz, C.c_int]
+    L.sgz_pcm_stream_level_for.restype = u64
+    L.sgz_pcm_stream_level_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.sgz_pcm_stream_flush_level.argtypes = [vp]
+    L.sgz_level_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
+    L.sgz_level_readout.argtypes = [vp, C.POINTER(LevelReading)]
     _lib = L
     return L
 
@@ -1209,6 +1230,30 @@ class PcmStream:
         check(lib().sgz_pcm_stream_flush_waveform(self.h))
 
 
+    # the level lane: one sgz_level_record per column of m samples and pair, beside whatever the feeds render
+    def set_level(self, m: int, out=None, capacity_columns: int | None = None) -> None:
+        """sgz_pcm_stream_set_level: out -- a LEVEL_DTYPE numpy array [capacity, pairs] or a host torch uint8 tensor [capacity, pairs, 80] (kept
+        alive here; pinned memory is written in place); m == 0 disarms"""
+        if capacity_columns is None:
+            capacity_columns = 0 if out is None else int(out.shape[0])
+        check(lib().sgz_pcm_stream_set_level(self.h, m, _buf_ptr(out) if out is not None and m else None, capacity_columns if m else 0))
+        self._level_out = out if m else None
+
+    def level_for(self, nsamples: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_level_for: level columns the next feed of nsamples closes"""
+        return int(lib().sgz_pcm_stream_level_for(self.h, nsamples, int(bool(flush))))
+
+    def level_state(self):
+        """sgz_pcm_stream_level_state: (columns written since the lane was armed, samples of the open column)"""
+        c, o = C.c_uint64(0), C.c_uint64(0)
+        check(lib().sgz_pcm_stream_level_state(self.h, C.byref(c), C.byref(o)))
+        return int(c.value), int(o.value)
+
+    def flush_level(self) -> None:
+        """sgz_pcm_stream_flush_level: closes the open column (one more record per pair at the cursor); waits"""
+        check(lib().sgz_pcm_stream_flush_level(self.h))
+
+
     # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
     def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:
         """sgz_pcm_stream_set_track: out -- a float64 numpy array or host torch tensor [capacity, pairs, 6] (kept alive here; pinned memory is
@@ -1245,6 +1290,42 @@ def stage_wave_columns(planar, channel_stride: int, channels: int, nsamples: int
     ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
     return lib().sgz_stage_wave_columns(ptr(planar), channel_stride, channels, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(wave),
                                         C.c_void_p(s) if s else None)
+
+
+def level_columns_limits():
+    """sgz_level_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples per row)"""
+    s, t = C.c_uint32(0), C.c_uint32(0)
+    lib().sgz_level_columns_limits(C.byref(s), C.byref(t))
+    return int(s.value), int(t.value)
+
+
+def stage_level_columns(planar, channel_stride: int, pairs: int, nsamples: int, m: int, held: int = 0, flush: bool = True, slices: int = 0,
+                        carry=None, level=None, stream=None) -> int:
+    """sgz_stage_level_columns as it is: planar / carry / level -- cuda tensors (their data pointers; any may be None where the call allows
+    NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    return lib().sgz_stage_level_columns(ptr(planar), channel_stride, pairs, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(level),
+                                         C.c_void_p(s) if s else None)
+
+
+def level_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_level_fold: LEVEL_DTYPE records [n, pairs], source columns [x0, x1) -> [min(out_columns, x1 - x0), pairs]"""
+    records = np.ascontiguousarray(records, LEVEL_DTYPE)
+    n, pairs = records.shape
+    x1 = n if x1 is None else x1
+    out = np.zeros((max(min(out_columns, x1 - x0), 1), pairs), LEVEL_DTYPE)
+    check(lib().sgz_level_fold(_np_ptr(records), n, pairs, x0, x1, out_columns, _np_ptr(out)))
+    return out[:min(out_columns, x1 - x0)]
+
+
+def level_readout(record) -> dict:
+    """sgz_level_readout of one LEVEL_DTYPE record: {rms, rms_db, dc: (L, R), correlation}"""
+    rec = np.ascontiguousarray(record, LEVEL_DTYPE).reshape(1)
+    r = LevelReading()
+    check(lib().sgz_level_readout(_np_ptr(rec), C.byref(r)))
+    return dict(rms=tuple(r.rms), rms_db=tuple(r.rms_db), dc=tuple(r.dc), correlation=r.correlation)
 
 
 def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,

@@ -2,8 +2,9 @@
 // cuts a feed into pieces and runs upload / convert + render / read-back of neighbouring pieces side by side on three streams.  Both kinds
 // of feed (frames, overview columns) go through ONE piece loop, pcmPieces, and differ in the Part they hand it: what to render from a piece
 // and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, waveform columns, track records --
-// is a PcmOut: device block, pinned twin, pending host copy.  Armed, the waveform lane (wave_columns.hip) reduces every piece's new samples
-// behind the converter and the track lane (tracker.hip) searches every piece's line results behind its render; both ride the same read-back.
+// is a PcmOut: device block, pinned twin, pending host copy.  Armed, the waveform lane (wave_columns.hip) and the level lane
+// (level_columns.hip) reduce every piece's new samples behind the converter and the track lane (tracker.hip) searches every piece's line
+// results behind its render; all three ride the same read-back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -189,8 +190,8 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 
 // The outputs of a piece.  Image [maxFrames][P][4] and Lines [maxFrames][C][graphs][P][2] are the feed's; OvImage [columns][P][4] and OvPeaks
 // [columns][C][P] the overview feed's, ceil(maxFrames / k) + 1 columns of them; Wave float2 [ceil(chunk / m) + 1][channels] the waveform
-// lane's; Track sgz_line_peak [maxFrames][pairs] the track lane's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kPcmOuts };
+// lane's; Track sgz_line_peak [maxFrames][pairs] the track lane's; Level sgz_level_record [ceil(chunk / m) + 1][pairs] the level lane's.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -268,6 +269,14 @@ struct sgz_pcm_stream {
     double trFraction = 0;
     sgz_line_peak *trOut = nullptr;
     uint64_t trCap = 0, trCursor = 0;
+    // the level lane (lvM > 0: armed), as the waveform lane with an m of its own: the caller's records and the cursor in them, the open column's
+    // sample count and its record per pair in d_lvCarry [2][pairs] -- a piece reads half lvCur and writes the other
+    uint32_t lvM = 0;
+    sgz_level_record *lvOut = nullptr;
+    uint64_t lvCap = 0, lvCursor = 0, lvOpen = 0;
+    bool lvPinned = false;
+    sgz_level_record *d_lvCarry = nullptr;
+    int lvCur = 0;
 };
 
 struct sgz_plan { Plan impl; };
@@ -342,6 +351,51 @@ static sgz_status pcmWaveReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t colum
     return st;
 }
 
+// ---- the level lane inside the stream (sgz.h, "The level lane") ----------------------------------------------------------------------------
+static sgz_level_record *pcmLevelCarry(const sgz_pcm_stream &s, int half) { return s.d_lvCarry + size_t(half) * s.cfg.num_pairs; }
+
+// what a feed checks for the lane before anything is consumed: the columns its samples close fit behind the cursor
+static sgz_status pcmLevelFits(const sgz_pcm_stream &s, size_t nsamples)
+{
+    if (s.lvM && (s.lvOpen + nsamples) / s.lvM > s.lvCap - s.lvCursor)
+        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed closes more level columns than the buffer has left (sgz_pcm_stream_level_for; re-arm with sgz_pcm_stream_set_level)");
+    return SGZ_OK;
+}
+
+// a slot's records of a piece, ceil(chunk / m) + 1 columns of them (both slots are idle between feeds)
+static sgz_status pcmLevelBuffers(sgz_pcm_stream &s, PcmSlot &sl)
+{
+    return s.lvM ? sl.out[kOutLevel].reserve(((s.chunk + s.lvM - 1) / s.lvM + 1) * s.cfg.num_pairs * sizeof(sgz_level_record), !s.lvPinned) : SGZ_OK;
+}
+
+// the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the records they close, into the slot;
+// the open one into the carry
+static sgz_status pcmLevelPiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
+{
+    *columns = 0;
+    if (!s.lvM || n == 0) return SGZ_OK;
+    const LevelColumnsShape sh = levelColumnsShape(s.cfg.num_pairs, n, s.lvM, uint32_t(s.lvOpen), 0, 0);
+    StreamScratch scratch(s.compute);
+    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
+    const sgz_status st = runLevelColumns(sh, fresh, s.stride, s.cfg.num_pairs, n, s.lvM, uint32_t(s.lvOpen), pcmLevelCarry(s, s.lvCur), pcmLevelCarry(s, s.lvCur ^ 1),
+                                          sl.out[kOutLevel].as<sgz_level_record>(), scratch.p, s.compute);
+    if (st != SGZ_OK) return st;
+    if (sh.open) s.lvCur ^= 1;
+    s.lvOpen = (s.lvOpen + n) % s.lvM;
+    *columns = sh.closed;
+    return SGZ_OK;
+}
+
+// the piece's records to the caller's buffer at the cursor, on the read-back stream
+static sgz_status pcmLevelReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
+{
+    if (!columns) return SGZ_OK;
+    const size_t column = s.cfg.num_pairs;
+    const sgz_status st = sl.out[kOutLevel].readBack(s.lvOut + size_t(s.lvCursor) * column, size_t(columns) * column * sizeof(sgz_level_record), s.lvPinned, s.back);
+    if (st == SGZ_OK) s.lvCursor += columns;
+    return st;
+}
+
 // ---- the track lane inside the stream (sgz.h, "The track lane") ----------------------------------------------------------------------------
 // what a feed checks for the lane before anything is consumed: the frames its samples complete fit behind the cursor
 static sgz_status pcmTrackFits(const sgz_pcm_stream &s, uint64_t frames)
@@ -370,9 +424,9 @@ static sgz_status pcmTrackReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t fram
 // ---- the piece loop ------------------------------------------------------------------------------------------------------------------------
 // What both feeds do once they have refused what they refuse.  The feed is cut into pieces of at most `chunk` samples; piece i uses slot i & 1:
 //   1. upload            copy stream: the samples to the slot (through its pinned block when the caller's are pageable)
-//   2. convert + render  compute stream, behind ev[1]: the converter behind the held tail, the waveform lane on the new samples, the Part's
+//   2. convert + render  compute stream, behind ev[1]: the converter behind the held tail, the waveform and level lanes on the new samples, the Part's
 //                        render of what became complete (armed, the track lane's search with it), the new tail to the other planar buffer
-//   3. read back         read-back stream, behind ev[4]: the Part's rows, the track's records, the waveform's columns
+//   3. read back         read-back stream, behind ev[4]: the Part's rows, the track's records, the waveform's columns, the level's records
 // The two kinds of feed differ in their Part alone: reserve(s, sl) makes its outputs in a slot before anything is consumed; render(s, sl,
 // planar, total, frames, last, &units) enqueues the render of a piece's frames and says how many rows -- `units`, what the feed counts and its
 // timing reports -- it leaves in the slot; readBack(s, sl, done, units) enqueues their copies behind the feed's `done` earlier rows.
@@ -389,6 +443,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
         if (sgz_status st = part.reserve(s, sl); st != SGZ_OK) return st;
         if (sgz_status st = pcmWaveBuffers(s, sl); st != SGZ_OK) return st;
         if (sgz_status st = pcmTrackBuffers(s, sl); st != SGZ_OK) return st;
+        if (sgz_status st = pcmLevelBuffers(s, sl); st != SGZ_OK) return st;
     }
     const uint8_t *src = static_cast<const uint8_t *>(pcm);
     uint64_t done = 0, chunks = 0;
@@ -413,8 +468,9 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             if (n)
                 if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s.format, s.srcChannels, n, s.map, s.numChannels, planar + s.held, s.stride, s.compute); st != SGZ_OK) return st;
             if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s.compute));
-            uint64_t waveColumns = 0, units = 0;
+            uint64_t waveColumns = 0, levelColumns = 0, units = 0;
             if (sgz_status st = pcmWavePiece(s, sl, planar + s.held, n, &waveColumns); st != SGZ_OK) return st;
+            if (sgz_status st = pcmLevelPiece(s, sl, planar + s.held, n, &levelColumns); st != SGZ_OK) return st;
             const uint64_t total = s.held + n;
             if (sgz_status st = part.render(s, sl, planar, size_t(total), frames, at + n == nsamples, &units); st != SGZ_OK) return st;
             if (frames) {
@@ -424,9 +480,9 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             }                                                                      // (no frame: the tail just grew where it is)
             s.held = keep;
             SGZ_HIP(hipEventRecord(sl.ev[4], s.compute));
-            // 3. read back (a piece may close waveform columns and complete no frame, or complete frames whose records are all it returns)
+            // 3. read back (a piece may close waveform or level columns and complete no frame, or complete frames whose records are all it returns)
             const uint64_t trackFrames = s.trArmed ? frames : 0;
-            sl.rendered = units > 0 || waveColumns > 0 || trackFrames > 0;
+            sl.rendered = units > 0 || waveColumns > 0 || trackFrames > 0 || levelColumns > 0;
             if (sl.rendered) {
                 SGZ_HIP(hipStreamWaitEvent(s.back, sl.ev[4], 0));
                 if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s.back));
@@ -434,6 +490,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
                     if (sgz_status st = part.readBack(s, sl, done, units); st != SGZ_OK) return st;
                 if (sgz_status st = pcmTrackReadBack(s, sl, trackFrames); st != SGZ_OK) return st;
                 if (sgz_status st = pcmWaveReadBack(s, sl, waveColumns); st != SGZ_OK) return st;
+                if (sgz_status st = pcmLevelReadBack(s, sl, levelColumns); st != SGZ_OK) return st;
                 SGZ_HIP(hipEventRecord(sl.ev[6], s.back));
             }
             sl.busy = true;
@@ -589,7 +646,7 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry, (void *)s->d_lvCarry}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
     if (s->plan) sgz_plan_destroy(s->plan);
     delete s;
@@ -646,6 +703,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     s->ovOpen = 0;                                                                  // an open overview column is dropped
     s->wvOpen = 0; s->wvCursor = 0;                                                 // and the waveform's; its columns start over
     s->trCursor = 0;                                                                // the track's records too; the lane stays armed
+    s->lvOpen = 0; s->lvCursor = 0;                                                 // the level lane as the waveform's
     return SGZ_OK;
 }
 
@@ -661,6 +719,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
     if (need && !rgba_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null rgba_out");
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
+    if (sgz_status st = pcmLevelFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTrackFits(*s, need); st != SGZ_OK) return st;
     PcmFramesPart part{rgba_out, lines_out, need, need && isPinnedHost(rgba_out), need && lines_out && isPinnedHost(lines_out)};
     return pcmFeed(*s, pcm, nsamples, false, part, frames_out, timing, t0);
@@ -704,6 +763,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (columns_out) *columns_out = need;
     if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)");
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
+    if (sgz_status st = pcmLevelFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTrackFits(*s, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
     PcmColumnsPart part{rgba_out, peaks_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && peaks_out && isPinnedHost(peaks_out)};
     // (a feed without samples still has one piece when it flushes an open column)
@@ -773,6 +833,61 @@ sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s)
     out.drain();
     s->wvOpen = 0;
     ++s->wvCursor;
+    return SGZ_OK;
+}
+
+// ---- the level lane's calls -------------------------------------------------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_set_level(sgz_pcm_stream *s, uint32_t m, sgz_level_record *level_out, uint64_t capacity_columns)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (m == 0) {                                                  // off: the open column is dropped
+        s->lvM = 0; s->lvOut = nullptr; s->lvCap = s->lvCursor = s->lvOpen = 0;
+        return SGZ_OK;
+    }
+    if (!level_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: null level_out");
+    if (reinterpret_cast<uintptr_t>(level_out) % alignof(sgz_level_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: level_out is not aligned to 8 bytes");
+    if (s->lvOpen && m != s->lvM) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: m differs from the open column's -- flush it (sgz_pcm_stream_flush_level), disarm or reset first");
+    if (!s->d_lvCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_lvCarry), size_t(2) * s->cfg.num_pairs * sizeof(sgz_level_record)));
+    s->lvM = m; s->lvOut = level_out; s->lvCap = capacity_columns; s->lvCursor = 0;
+    s->lvPinned = capacity_columns && isPinnedHost(level_out);
+    return SGZ_OK;
+}
+
+uint64_t sgz_pcm_stream_level_for(const sgz_pcm_stream *s, size_t nsamples, int flush)
+{
+    if (!s || !s->lvM) return 0;
+    const uint64_t t = s->lvOpen + nsamples;
+    return t / s->lvM + ((flush && t % s->lvM) ? 1u : 0u);
+}
+
+sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (columns_written) *columns_written = s->lvCursor;
+    if (open_samples) *open_samples = s->lvOpen;
+    return SGZ_OK;
+}
+
+sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!s->lvM) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_level: the lane is off (sgz_pcm_stream_set_level)");
+    if (!s->lvOpen) return SGZ_OK;
+    if (s->lvCursor >= s->lvCap) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_level: no column left in the buffer (re-arm with sgz_pcm_stream_set_level)");
+    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
+    if (sgz_status st = pcmLevelBuffers(*s, sl); st != SGZ_OK) return st;
+    const uint32_t pairs = s->cfg.num_pairs;
+    const LevelColumnsShape sh = levelColumnsShape(pairs, 0, s->lvM, uint32_t(s->lvOpen), 1, 0);
+    const sgz_status st = runLevelColumns(sh, s->d_planar[s->cur], s->stride, pairs, 0, s->lvM, uint32_t(s->lvOpen), pcmLevelCarry(*s, s->lvCur),
+                                          pcmLevelCarry(*s, s->lvCur ^ 1), sl.out[kOutLevel].as<sgz_level_record>(), nullptr, s->compute);
+    if (st != SGZ_OK) return st;
+    // the one column behind the launch on the compute stream itself, and waited for
+    PcmOut &out = sl.out[kOutLevel];
+    if (sgz_status rb = out.readBack(s->lvOut + size_t(s->lvCursor) * pairs, pairs * sizeof(sgz_level_record), s->lvPinned, s->compute); rb != SGZ_OK) return rb;
+    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) { out.dst = nullptr; return hipFail(e, "hipStreamSynchronize(s->compute)"); }
+    out.drain();
+    s->lvOpen = 0;
+    ++s->lvCursor;
     return SGZ_OK;
 }
 

@@ -118,6 +118,13 @@ struct WaveColumnsShape {
 WaveColumnsShape waveColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
 sgz_status runWaveColumns(const WaveColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples, uint32_t m,
                           uint32_t held, const float *carryIn, float *carryOut, float *d_wave, void *scratch, hipStream_t stream);
+// the level lane's reduction (level_columns.hip), the same two steps: the shape (scratchBytes: the partial records of the sliced form), then
+// sgz_stage_level_columns behind its argument checks with the carry in two places
+using LevelColumnsShape = WaveColumnsShape;
+LevelColumnsShape levelColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
+sgz_status runLevelColumns(const LevelColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
+                           uint32_t held, const sgz_level_record *carryIn, sgz_level_record *carryOut, sgz_level_record *d_level, void *scratch,
+                           hipStream_t stream);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
 }  // namespace sgz
