@@ -53,6 +53,10 @@ extern "C" {
  *  sgz_level_fold and sgz_level_readout and, on the PCM stream, sgz_pcm_stream_set_level, sgz_pcm_stream_level_for,
  *  sgz_pcm_stream_level_state, sgz_pcm_stream_flush_level.  No existing entry point or struct changed and the suite pins 5; a stream that
  *  was never armed enqueues what it did before.  A binding that needs them looks the symbols up.)
+ * (5, later: the true-peak lane -- sgz_truepeak_record, sgz_truepeak_carry, sgz_stage_truepeak_columns, sgz_truepeak_columns_limits, the
+ *  host helpers sgz_truepeak_taps, sgz_truepeak_fold and sgz_truepeak_readout and, on the PCM stream, sgz_pcm_stream_set_truepeak,
+ *  sgz_pcm_stream_truepeak_for, sgz_pcm_stream_truepeak_state, sgz_pcm_stream_flush_truepeak.  No existing entry point or struct changed and
+ *  the suite pins 5; a stream that was never armed enqueues what it did before.  A binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -723,6 +727,115 @@ sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns
 sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s);
 sgz_status sgz_level_fold(const sgz_level_record *in, size_t n, uint32_t pairs, size_t x0, size_t x1, uint32_t out_columns, sgz_level_record *out);
 sgz_status sgz_level_readout(const sgz_level_record *rec, sgz_level_reading *out);
+
+/* The true-peak lane: the peak of the 4x oversampled signal per screen column and channel of a file's samples -- the inter-sample peak a
+ * mastering tool shows beside the level: the level lane's `overs` see only samples at or over full scale, and a sine at fs/4 sampled at
+ * 45 degrees has sample peaks of 0.707 A and a true peak of A.  The reference has no counterpart: its meters are live one-pole filters
+ * (here sgz_vector_meters); nothing of them is reused or contradicted.  The filter is NOT ITU-R BS.1770's printed coefficient table; it is
+ * a filter of the same structure -- 4x oversampling, 48 taps, 12 per phase -- with the taps below.  Loudness weighting (K-filtering) is not
+ * part of the lane: an IIR recurrence in fp32 has no cut-independent bits.  A polyphase FIR on quantised integers has: it is a sum of
+ * integer products, exact in any order.
+ * Definition (exact, no tolerance): let x[d][i] be the fp32 samples of channel d (the stream's converted floats, exactly what
+ * sgz_pcm_to_planar_device writes), i counting the samples of the whole stream since the lane was armed or reset, S the samples so far
+ * and m >= 1 the samples per column.  The quantiser is the level lane's,
+ *     v = (int32) clamp(rintf(x * 2^23), -2^26, +2^26)
+ * but a NaN gives v = 0 here: it enters the filter as silence, and it is not counted in `count`.  v[k] = 0 for k < 0.  The taps: T = 12
+ * per phase, 4 phases, scale 2^20, c[q][j] = rint(2^20 L(j - 6 + q / 4)) with L(t) = sinc(t) sinc(t / 6) for |t| < 6 (Lanczos, a = 6).
+ * This table is normative (sgz_truepeak_taps copies it):
+ *     q = 0:  c[0][6] = 1048576, all other taps 0           (the delayed sample itself)
+ *     q = 1:  -1780  12162  -29613  59093  -116769  306657  941356  -175616  82260  -42310  19798  -6258
+ *     q = 2:  -5454  22259  -50264  98518  -200334  659945  659945  -200334  98518  -50264  22259  -5454
+ *     q = 3:  c[3][j] = c[1][11 - j]
+ * The sums of |c| per phase are 1048576, 1793672, 2073548 and 1793672, hence |y| <= 2^26 * 2073548 < 2^47: every partial sum is exact in
+ * int64 (and in fp64).  The output:
+ *     y[i][q] = sum over j = 0 .. 11 of c[q][j] v[i - j]
+ * The filter is causal: y[i][.] estimates the signal around sample i - 6 and belongs to the column of sample i, so a peak shows up to 6
+ * samples late -- which is what keeps the column counts those of every other lane.  Column c covers samples c m <= i < min((c + 1) m, S),
+ * counted by sgz_overview_step with samples in the place of frames; only a flushed last column may be partial.  A flush closes the open
+ * column as it stands: the 11 outputs of the filter's tail are not produced (a host that wants them feeds 11 zeros), and the history is
+ * kept across a flush, because the stream may go on.  One sgz_truepeak_record per (column, channel), layout [columns][channels], 16
+ * bytes, little-endian; arrays on the DEVICE are aligned to 16 bytes:
+ *     peak    the greatest |y[i][q]| over the column's samples i and q = 0 .. 3; 2^43 is full scale; 0 for an empty column
+ *     count   the column's non-NaN samples
+ *     overs   the column's samples i with |y[i][q]| >= 2^43 for some q
+ * Maximum and integer sum are associative and commutative, so any cut of the stream or of a column gives the same bytes, and a coarser
+ * column is the fold of the finer ones: max of peak, sums of count and overs (sgz_truepeak_fold).  What a cut of the stream carries is
+ * one 64-byte sgz_truepeak_carry per channel, aligned to 16: the open column so far, the last 11 quantised samples (oldest first), and a
+ * reserved word written as 0.
+ *  sgz_stage_truepeak_columns  DEVICE pointers; sgz_stage_level_columns' semantics in every point not named here.  d_planar [channels]
+ *                      [channel_stride], the first nsamples of each row (any 4-byte-aligned address).  held: samples of the open
+ *                      column that earlier calls took (< m).  continued == 0: the stream begins with this call, the history is zeros,
+ *                      held must be 0.  continued != 0: d_carry[].hist holds the 11 samples before this call's first, d_carry[].open
+ *                      is read iff held > 0.  d_carry: DEVICE sgz_truepeak_carry [channels], needed (not NULL) whenever continued != 0
+ *                      or nsamples > 0.  After a call with nsamples > 0 all 64 bytes of every channel's carry are written: hist is the
+ *                      last 11 of (the old history followed by the new samples) -- a call of fewer than 11 samples shifts it --,
+ *                      open is the open column where samples stay open (no flush, (held + nsamples) % m != 0) and all zero
+ *                      otherwise, reserved is 0.  The call reads a snapshot of the carry it was given, so no workgroup reads what
+ *                      another one of the same launch writes.  nsamples == 0 with held > 0 and flush: one column from the carry
+ *                      alone, the carry untouched.  d_peaks: DEVICE sgz_truepeak_record [columns][channels], columns as
+ *                      sgz_overview_step counts them (NULL allowed when none closes).  m up to the switch-over (1024;
+ *                      sgz_truepeak_columns_limits) runs one workgroup per (channel, tile of 4096 / m whole columns); longer columns
+ *                      are reduced in slices per column into scratch and folded by a second launch; every tile and slice fetches its
+ *                      own 11-sample halo.  slices: 0 = the library's choice, 1 .. 64 forced -- 2 and more take the sliced form
+ *                      whatever m is, 1 takes the form m implies -- identical bits.  Only the documented bytes are written.
+ *                      Asynchronous on `stream`, nothing is waited for; scratch is allocated and freed in stream order.  SGZ_EINVAL,
+ *                      nothing launched or written: a null d_planar, channels == 0 or > 64, m == 0, held >= m, continued == 0 with
+ *                      held > 0, channel_stride < nsamples, slices > 64, a needed d_carry or d_peaks that is NULL, d_planar not
+ *                      aligned to 4 bytes, d_carry or d_peaks not aligned to 16.  nsamples == 0 with nothing to flush: SGZ_OK,
+ *                      nothing launched.
+ *  sgz_truepeak_columns_limits  the switch-over and the tile's samples (either result may be NULL).
+ *  sgz_truepeak_taps   copies the table, c[q][j] at taps[q][j].
+ * The lane inside the sgz_pcm_stream handle -- above, "interleaved PCM in": while armed, every feed of either kind also runs the
+ * reduction on the new samples of each piece on the compute stream behind the conversion (and behind the other lanes' launches), and
+ * reads the records that closed back on the read-back stream into `out` at a cursor.  The records of all feeds and the final flush,
+ * concatenated, are the definition applied to the stream's converted floats, byte for byte, however the stream is cut into feeds and
+ * pieces and whichever kind the feeds are; everything else an armed stream returns equals an unarmed stream's, byte for byte.  The
+ * lane's m is its own.
+ *  sgz_pcm_stream_set_truepeak   between feeds.  m > 0 arms: out HOST sgz_truepeak_record [capacity_columns][channels] (aligned to 8
+ *                      bytes; pinned memory is written in place, pageable memory through a pinned twin per slot), the cursor
+ *                      restarts at 0 and the lane starts at the next sample with a zero history.  The same m with another buffer
+ *                      keeps the open column and the history: how a caller with a small buffer drains.  m == 0 disarms and drops
+ *                      both.  SGZ_EINVAL: a null stream, a null out with capacity_columns > 0, an out that is not aligned, another m
+ *                      while samples are open.
+ *  sgz_pcm_stream_truepeak_for   columns the next feed of nsamples closes (flush != 0: that feed followed by
+ *                      sgz_pcm_stream_flush_truepeak); 0 when disarmed.
+ *  sgz_pcm_stream_truepeak_state columns written since the lane was armed (the cursor) and the open column's samples; either may be
+ *                      NULL.
+ *  sgz_pcm_stream_flush_truepeak closes the open column: one launch on the carry, one column read back, waits; the history is kept.
+ *                      Nothing open: SGZ_OK, nothing done.  SGZ_EINVAL: disarmed, no column left in the buffer.
+ * A feed that would close more columns than the buffer has left is refused with SGZ_EINVAL before anything is consumed.  reset drops
+ * the open column, zeroes the history and restarts the cursor.  The carry is kept twice and alternated: a piece reads one and writes
+ * the other.  Memory per slot as the level lane's, 16 bytes a record.
+ * Host arithmetic on HOST records, nothing launched:
+ *  sgz_truepeak_fold   the zoom, with sgz_level_fold's boundary rule: output column b is the fold of source columns x0 + ceil(b w /
+ *                      cols) <= j < x0 + ceil((b + 1) w / cols), w = x1 - x0, cols = min(out_columns, w).  out must not overlap in.
+ *                      SGZ_EINVAL, nothing written: a null argument, channels == 0, what sgz_overview_view_columns refuses, a folded
+ *                      count or overs above 2^32 - 1.
+ *  sgz_truepeak_readout  *peak = rec->peak / 2^43 (1.0 is full scale) and *dbtp = 20 log10(peak), -inf for 0, in fp64; either result
+ *                      may be NULL.  SGZ_EINVAL: a null rec. */
+typedef struct sgz_truepeak_record {
+    uint64_t peak;    /* max over the column's samples i and q = 0..3 of |y[i][q]|; 2^43 is full scale; 0 for an empty column */
+    uint32_t count;   /* the column's non-NaN samples */
+    uint32_t overs;   /* the column's samples i with |y[i][q]| >= 2^43 for some q */
+} sgz_truepeak_record;         /* 16 bytes */
+typedef struct sgz_truepeak_carry {
+    sgz_truepeak_record open;      /* the open column so far */
+    int32_t             hist[11];  /* the last 11 quantised samples before the next one, oldest first */
+    uint32_t            reserved;  /* written as 0 */
+} sgz_truepeak_carry;          /* 64 bytes */
+sgz_status sgz_stage_truepeak_columns(const float *d_planar, size_t channel_stride, uint32_t channels, size_t nsamples, uint32_t m, uint32_t held,
+                                      int flush, uint32_t continued, uint32_t slices, sgz_truepeak_carry *d_carry /*[channels]*/,
+                                      sgz_truepeak_record *d_peaks /*[columns][channels]*/, void *stream);
+void       sgz_truepeak_columns_limits(uint32_t *switch_over, uint32_t *tile_samples);
+void       sgz_truepeak_taps(int32_t taps[4][12]);
+sgz_status sgz_truepeak_fold(const sgz_truepeak_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns,
+                             sgz_truepeak_record *out);
+sgz_status sgz_truepeak_readout(const sgz_truepeak_record *rec, double *peak /*1.0 = full scale*/, double *dbtp);
+sgz_status sgz_pcm_stream_set_truepeak(sgz_pcm_stream *s, uint32_t m /*0 = off*/, sgz_truepeak_record *out /*HOST [capacity][channels]*/,
+                                       uint64_t capacity_columns);
+uint64_t   sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
+sgz_status sgz_pcm_stream_truepeak_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
+sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s);
 
 /* The track lane: the tracker's curve over a file -- the reference's drawFrequencyTracking readout (SpectrumRendering.cpp:300-377, the
  * line-results branch) for every frame of a streamed file, in bounded memory.  sgz_spectrogram_track_device / _host want the whole file

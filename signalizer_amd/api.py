@@ -118,6 +118,11 @@ class LevelReading(C.Structure):
 LEVEL_DTYPE = np.dtype([("sumsq", "<u8", (2, 2)), ("cross", "<u8", (2,)), ("sum", "<i8", (2,)), ("count", "<u4", (2,)), ("overs", "<u4", (2,))])
 assert LEVEL_DTYPE.itemsize == 80
 
+# sgz_truepeak_record: one per (column, channel) of the true-peak lane, 16 bytes; sgz_truepeak_carry: one per channel, 64 bytes
+TRUEPEAK_DTYPE = np.dtype([("peak", "<u8"), ("count", "<u4"), ("overs", "<u4")])
+TRUEPEAK_CARRY_DTYPE = np.dtype([("open", TRUEPEAK_DTYPE), ("hist", "<i4", (11,)), ("reserved", "<u4")])
+assert TRUEPEAK_DTYPE.itemsize == 16 and TRUEPEAK_CARRY_DTYPE.itemsize == 64
+
 
 class LineGraphStyle(C.Structure):
     _fields_ = [("colour_one", (C.c_uint8 * 4) * NUM_GRAPHS), ("colour_two", (C.c_uint8 * 4) * NUM_GRAPHS), ("flood_alpha", C.c_float),
@@ -209,6 +214,8 @@ EXPORTS = [
     "sgz_track_peak_values", "sgz_stage_track_peaks_values", "sgz_pcm_stream_set_track", "sgz_pcm_stream_track_for", "sgz_pcm_stream_track_state",
     "sgz_stage_level_columns", "sgz_level_columns_limits", "sgz_pcm_stream_set_level", "sgz_pcm_stream_level_for", "sgz_pcm_stream_level_state",
     "sgz_pcm_stream_flush_level", "sgz_level_fold", "sgz_level_readout",
+    "sgz_stage_truepeak_columns", "sgz_truepeak_columns_limits", "sgz_truepeak_taps", "sgz_truepeak_fold", "sgz_truepeak_readout",
+    "sgz_pcm_stream_set_truepeak", "sgz_pcm_stream_truepeak_for", "sgz_pcm_stream_truepeak_state", "sgz_pcm_stream_flush_truepeak",
 ]
 
 
@@ -449,6 +456,18 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_flush_level.argtypes = [vp]
     L.sgz_level_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_level_readout.argtypes = [vp, C.POINTER(LevelReading)]
+    L.sgz_stage_truepeak_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, u32, vp, vp, vp]
+    L.sgz_truepeak_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    L.sgz_truepeak_columns_limits.restype = None
+    L.sgz_truepeak_taps.argtypes = [vp]
+    L.sgz_truepeak_taps.restype = None
+    L.sgz_truepeak_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
+    L.sgz_truepeak_readout.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sgz_pcm_stream_set_truepeak.argtypes = [vp, u32, vp, u64]
+    L.sgz_pcm_stream_truepeak_for.argtypes = [vp, sz, C.c_int]
+    L.sgz_pcm_stream_truepeak_for.restype = u64
+    L.sgz_pcm_stream_truepeak_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.sgz_pcm_stream_flush_truepeak.argtypes = [vp]
     _lib = L
     return L
 
@@ -1254,6 +1273,30 @@ class PcmStream:
         check(lib().sgz_pcm_stream_flush_level(self.h))
 
 
+    # the true-peak lane: one sgz_truepeak_record per column of m samples and channel, beside whatever the feeds render
+    def set_truepeak(self, m: int, out=None, capacity_columns: int | None = None) -> None:
+        """sgz_pcm_stream_set_truepeak: out -- a TRUEPEAK_DTYPE numpy array [capacity, channels] or a host torch uint8 tensor [capacity, channels,
+        16] (kept alive here; pinned memory is written in place); m == 0 disarms"""
+        if capacity_columns is None:
+            capacity_columns = 0 if out is None else int(out.shape[0])
+        check(lib().sgz_pcm_stream_set_truepeak(self.h, m, _buf_ptr(out) if out is not None and m else None, capacity_columns if m else 0))
+        self._truepeak_out = out if m else None
+
+    def truepeak_for(self, nsamples: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_truepeak_for: true-peak columns the next feed of nsamples closes"""
+        return int(lib().sgz_pcm_stream_truepeak_for(self.h, nsamples, int(bool(flush))))
+
+    def truepeak_state(self):
+        """sgz_pcm_stream_truepeak_state: (columns written since the lane was armed, samples of the open column)"""
+        c, o = C.c_uint64(0), C.c_uint64(0)
+        check(lib().sgz_pcm_stream_truepeak_state(self.h, C.byref(c), C.byref(o)))
+        return int(c.value), int(o.value)
+
+    def flush_truepeak(self) -> None:
+        """sgz_pcm_stream_flush_truepeak: closes the open column (one more record per channel at the cursor); waits"""
+        check(lib().sgz_pcm_stream_flush_truepeak(self.h))
+
+
     # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
     def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:
         """sgz_pcm_stream_set_track: out -- a float64 numpy array or host torch tensor [capacity, pairs, 6] (kept alive here; pinned memory is
@@ -1326,6 +1369,49 @@ def level_readout(record) -> dict:
     r = LevelReading()
     check(lib().sgz_level_readout(_np_ptr(rec), C.byref(r)))
     return dict(rms=tuple(r.rms), rms_db=tuple(r.rms_db), dc=tuple(r.dc), correlation=r.correlation)
+
+
+def truepeak_columns_limits():
+    """sgz_truepeak_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples)"""
+    s, t = C.c_uint32(0), C.c_uint32(0)
+    lib().sgz_truepeak_columns_limits(C.byref(s), C.byref(t))
+    return int(s.value), int(t.value)
+
+
+def truepeak_taps() -> np.ndarray:
+    """sgz_truepeak_taps: the filter's table, int32 [4 phases, 12 taps]"""
+    taps = np.zeros((4, 12), np.int32)
+    lib().sgz_truepeak_taps(_np_ptr(taps))
+    return taps
+
+
+def stage_truepeak_columns(planar, channel_stride: int, channels: int, nsamples: int, m: int, held: int = 0, flush: bool = True,
+                           continued: bool = False, slices: int = 0, carry=None, peaks=None, stream=None) -> int:
+    """sgz_stage_truepeak_columns as it is: planar / carry / peaks -- cuda tensors (their data pointers; any may be None where the call allows
+    NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    return lib().sgz_stage_truepeak_columns(ptr(planar), channel_stride, channels, nsamples, m, held, int(bool(flush)), int(bool(continued)), slices,
+                                            ptr(carry), ptr(peaks), C.c_void_p(s) if s else None)
+
+
+def truepeak_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_truepeak_fold: TRUEPEAK_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels]"""
+    records = np.ascontiguousarray(records, TRUEPEAK_DTYPE)
+    n, channels = records.shape
+    x1 = n if x1 is None else x1
+    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), TRUEPEAK_DTYPE)
+    check(lib().sgz_truepeak_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
+    return out[:min(out_columns, x1 - x0)]
+
+
+def truepeak_readout(record):
+    """sgz_truepeak_readout of one TRUEPEAK_DTYPE record: (peak with 1.0 = full scale, dBTP)"""
+    rec = np.ascontiguousarray(record, TRUEPEAK_DTYPE).reshape(1)
+    p, d = C.c_double(0), C.c_double(0)
+    check(lib().sgz_truepeak_readout(_np_ptr(rec), C.byref(p), C.byref(d)))
+    return p.value, d.value
 
 
 def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,

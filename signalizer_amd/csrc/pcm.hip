@@ -4,7 +4,8 @@
 // and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, waveform columns, track records --
 // is a PcmOut: device block, pinned twin, pending host copy.  Armed, the waveform lane (wave_columns.hip) and the level lane
 // (level_columns.hip) reduce every piece's new samples behind the converter and the track lane (tracker.hip) searches every piece's line
-// results behind its render; all three ride the same read-back.
+// results behind its render; the true-peak lane (truepeak_columns.hip) filters every piece's new samples behind them.  All ride the same
+// read-back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -190,8 +191,9 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 
 // The outputs of a piece.  Image [maxFrames][P][4] and Lines [maxFrames][C][graphs][P][2] are the feed's; OvImage [columns][P][4] and OvPeaks
 // [columns][C][P] the overview feed's, ceil(maxFrames / k) + 1 columns of them; Wave float2 [ceil(chunk / m) + 1][channels] the waveform
-// lane's; Track sgz_line_peak [maxFrames][pairs] the track lane's; Level sgz_level_record [ceil(chunk / m) + 1][pairs] the level lane's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kPcmOuts };
+// lane's; Track sgz_line_peak [maxFrames][pairs] the track lane's; Level sgz_level_record [ceil(chunk / m) + 1][pairs] the level lane's;
+// TruePeak sgz_truepeak_record [ceil(chunk / m) + 1][channels] the true-peak lane's.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -277,6 +279,15 @@ struct sgz_pcm_stream {
     bool lvPinned = false;
     sgz_level_record *d_lvCarry = nullptr;
     int lvCur = 0;
+    // the true-peak lane (tpM > 0: armed), as the level lane per channel; its carry d_tpCarry [2][channels] also holds the filter's history, so
+    // every piece with samples writes the other half and the halves alternate.  tpContinued: half tpCur holds the samples before the next one
+    // (false after arming or a reset: the history is zeros)
+    uint32_t tpM = 0;
+    sgz_truepeak_record *tpOut = nullptr;
+    uint64_t tpCap = 0, tpCursor = 0, tpOpen = 0;
+    bool tpPinned = false, tpContinued = false;
+    sgz_truepeak_carry *d_tpCarry = nullptr;
+    int tpCur = 0;
 };
 
 struct sgz_plan { Plan impl; };
@@ -396,6 +407,52 @@ static sgz_status pcmLevelReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t colu
     return st;
 }
 
+// ---- the true-peak lane inside the stream (sgz.h, "The true-peak lane") --------------------------------------------------------------------
+static sgz_truepeak_carry *pcmTruePeakCarry(const sgz_pcm_stream &s, int half) { return s.d_tpCarry + size_t(half) * s.numChannels; }
+
+// what a feed checks for the lane before anything is consumed: the columns its samples close fit behind the cursor
+static sgz_status pcmTruePeakFits(const sgz_pcm_stream &s, size_t nsamples)
+{
+    if (s.tpM && (s.tpOpen + nsamples) / s.tpM > s.tpCap - s.tpCursor)
+        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed closes more true-peak columns than the buffer has left (sgz_pcm_stream_truepeak_for; re-arm with sgz_pcm_stream_set_truepeak)");
+    return SGZ_OK;
+}
+
+// a slot's records of a piece, ceil(chunk / m) + 1 columns of them (both slots are idle between feeds)
+static sgz_status pcmTruePeakBuffers(sgz_pcm_stream &s, PcmSlot &sl)
+{
+    return s.tpM ? sl.out[kOutTruePeak].reserve(((s.chunk + s.tpM - 1) / s.tpM + 1) * s.numChannels * sizeof(sgz_truepeak_record), !s.tpPinned) : SGZ_OK;
+}
+
+// the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the records they close, into the slot;
+// the open one and the new history into the other half of the carry
+static sgz_status pcmTruePeakPiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
+{
+    *columns = 0;
+    if (!s.tpM || n == 0) return SGZ_OK;
+    const TruePeakColumnsShape sh = truePeakColumnsShape(s.numChannels, n, s.tpM, uint32_t(s.tpOpen), 0, 0);
+    StreamScratch scratch(s.compute);
+    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
+    const sgz_status st = runTruePeakColumns(sh, fresh, s.stride, s.numChannels, n, s.tpM, uint32_t(s.tpOpen), s.tpContinued ? 1u : 0u, pcmTruePeakCarry(s, s.tpCur),
+                                             pcmTruePeakCarry(s, s.tpCur ^ 1), sl.out[kOutTruePeak].as<sgz_truepeak_record>(), scratch.p, s.compute);
+    if (st != SGZ_OK) return st;
+    s.tpCur ^= 1;                                                                   // (the history moved, whether or not a column stays open)
+    s.tpContinued = true;
+    s.tpOpen = (s.tpOpen + n) % s.tpM;
+    *columns = sh.closed;
+    return SGZ_OK;
+}
+
+// the piece's records to the caller's buffer at the cursor, on the read-back stream
+static sgz_status pcmTruePeakReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
+{
+    if (!columns) return SGZ_OK;
+    const size_t column = s.numChannels;
+    const sgz_status st = sl.out[kOutTruePeak].readBack(s.tpOut + size_t(s.tpCursor) * column, size_t(columns) * column * sizeof(sgz_truepeak_record), s.tpPinned, s.back);
+    if (st == SGZ_OK) s.tpCursor += columns;
+    return st;
+}
+
 // ---- the track lane inside the stream (sgz.h, "The track lane") ----------------------------------------------------------------------------
 // what a feed checks for the lane before anything is consumed: the frames its samples complete fit behind the cursor
 static sgz_status pcmTrackFits(const sgz_pcm_stream &s, uint64_t frames)
@@ -444,6 +501,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
         if (sgz_status st = pcmWaveBuffers(s, sl); st != SGZ_OK) return st;
         if (sgz_status st = pcmTrackBuffers(s, sl); st != SGZ_OK) return st;
         if (sgz_status st = pcmLevelBuffers(s, sl); st != SGZ_OK) return st;
+        if (sgz_status st = pcmTruePeakBuffers(s, sl); st != SGZ_OK) return st;
     }
     const uint8_t *src = static_cast<const uint8_t *>(pcm);
     uint64_t done = 0, chunks = 0;
@@ -468,9 +526,10 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             if (n)
                 if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s.format, s.srcChannels, n, s.map, s.numChannels, planar + s.held, s.stride, s.compute); st != SGZ_OK) return st;
             if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s.compute));
-            uint64_t waveColumns = 0, levelColumns = 0, units = 0;
+            uint64_t waveColumns = 0, levelColumns = 0, truePeakColumns = 0, units = 0;
             if (sgz_status st = pcmWavePiece(s, sl, planar + s.held, n, &waveColumns); st != SGZ_OK) return st;
             if (sgz_status st = pcmLevelPiece(s, sl, planar + s.held, n, &levelColumns); st != SGZ_OK) return st;
+            if (sgz_status st = pcmTruePeakPiece(s, sl, planar + s.held, n, &truePeakColumns); st != SGZ_OK) return st;
             const uint64_t total = s.held + n;
             if (sgz_status st = part.render(s, sl, planar, size_t(total), frames, at + n == nsamples, &units); st != SGZ_OK) return st;
             if (frames) {
@@ -482,7 +541,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             SGZ_HIP(hipEventRecord(sl.ev[4], s.compute));
             // 3. read back (a piece may close waveform or level columns and complete no frame, or complete frames whose records are all it returns)
             const uint64_t trackFrames = s.trArmed ? frames : 0;
-            sl.rendered = units > 0 || waveColumns > 0 || trackFrames > 0 || levelColumns > 0;
+            sl.rendered = units > 0 || waveColumns > 0 || trackFrames > 0 || levelColumns > 0 || truePeakColumns > 0;
             if (sl.rendered) {
                 SGZ_HIP(hipStreamWaitEvent(s.back, sl.ev[4], 0));
                 if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s.back));
@@ -491,6 +550,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
                 if (sgz_status st = pcmTrackReadBack(s, sl, trackFrames); st != SGZ_OK) return st;
                 if (sgz_status st = pcmWaveReadBack(s, sl, waveColumns); st != SGZ_OK) return st;
                 if (sgz_status st = pcmLevelReadBack(s, sl, levelColumns); st != SGZ_OK) return st;
+                if (sgz_status st = pcmTruePeakReadBack(s, sl, truePeakColumns); st != SGZ_OK) return st;
                 SGZ_HIP(hipEventRecord(sl.ev[6], s.back));
             }
             sl.busy = true;
@@ -646,7 +706,7 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry, (void *)s->d_lvCarry}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry, (void *)s->d_lvCarry, (void *)s->d_tpCarry}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
     if (s->plan) sgz_plan_destroy(s->plan);
     delete s;
@@ -704,6 +764,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     s->wvOpen = 0; s->wvCursor = 0;                                                 // and the waveform's; its columns start over
     s->trCursor = 0;                                                                // the track's records too; the lane stays armed
     s->lvOpen = 0; s->lvCursor = 0;                                                 // the level lane as the waveform's
+    s->tpOpen = 0; s->tpCursor = 0; s->tpContinued = false;                         // the true-peak lane too, and its history is zeros again
     return SGZ_OK;
 }
 
@@ -720,6 +781,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     if (need && !rgba_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null rgba_out");
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmLevelFits(*s, nsamples); st != SGZ_OK) return st;
+    if (sgz_status st = pcmTruePeakFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTrackFits(*s, need); st != SGZ_OK) return st;
     PcmFramesPart part{rgba_out, lines_out, need, need && isPinnedHost(rgba_out), need && lines_out && isPinnedHost(lines_out)};
     return pcmFeed(*s, pcm, nsamples, false, part, frames_out, timing, t0);
@@ -764,6 +826,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)");
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmLevelFits(*s, nsamples); st != SGZ_OK) return st;
+    if (sgz_status st = pcmTruePeakFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTrackFits(*s, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
     PcmColumnsPart part{rgba_out, peaks_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && peaks_out && isPinnedHost(peaks_out)};
     // (a feed without samples still has one piece when it flushes an open column)
@@ -888,6 +951,63 @@ sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s)
     out.drain();
     s->lvOpen = 0;
     ++s->lvCursor;
+    return SGZ_OK;
+}
+
+// ---- the true-peak lane's calls ---------------------------------------------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_set_truepeak(sgz_pcm_stream *s, uint32_t m, sgz_truepeak_record *out, uint64_t capacity_columns)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (m == 0) {                                                  // off: the open column and the history are dropped
+        s->tpM = 0; s->tpOut = nullptr; s->tpCap = s->tpCursor = s->tpOpen = 0; s->tpContinued = false;
+        return SGZ_OK;
+    }
+    if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: null out");
+    if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_truepeak_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: out is not aligned to 8 bytes");
+    if (s->tpOpen && m != s->tpM) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: m differs from the open column's -- flush it (sgz_pcm_stream_flush_truepeak), disarm or reset first");
+    if (!s->d_tpCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_tpCarry), size_t(2) * s->numChannels * sizeof(sgz_truepeak_carry)));
+    if (m != s->tpM) s->tpContinued = false;                       // (arming: the lane starts at the next sample with a zero history; the same m keeps it)
+    s->tpM = m; s->tpOut = out; s->tpCap = capacity_columns; s->tpCursor = 0;
+    s->tpPinned = capacity_columns && isPinnedHost(out);
+    return SGZ_OK;
+}
+
+uint64_t sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush)
+{
+    if (!s || !s->tpM) return 0;
+    const uint64_t t = s->tpOpen + nsamples;
+    return t / s->tpM + ((flush && t % s->tpM) ? 1u : 0u);
+}
+
+sgz_status sgz_pcm_stream_truepeak_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (columns_written) *columns_written = s->tpCursor;
+    if (open_samples) *open_samples = s->tpOpen;
+    return SGZ_OK;
+}
+
+sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!s->tpM) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_truepeak: the lane is off (sgz_pcm_stream_set_truepeak)");
+    if (!s->tpOpen) return SGZ_OK;
+    if (s->tpCursor >= s->tpCap) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_truepeak: no column left in the buffer (re-arm with sgz_pcm_stream_set_truepeak)");
+    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
+    if (sgz_status st = pcmTruePeakBuffers(*s, sl); st != SGZ_OK) return st;
+    const uint32_t channels = s->numChannels;
+    // the emit launch alone, on the open column of the current half; the carry, and with it the history, stays where it is
+    const TruePeakColumnsShape sh = truePeakColumnsShape(channels, 0, s->tpM, uint32_t(s->tpOpen), 1, 0);
+    const sgz_status st = runTruePeakColumns(sh, s->d_planar[s->cur], s->stride, channels, 0, s->tpM, uint32_t(s->tpOpen), 1u, pcmTruePeakCarry(*s, s->tpCur),
+                                             pcmTruePeakCarry(*s, s->tpCur ^ 1), sl.out[kOutTruePeak].as<sgz_truepeak_record>(), nullptr, s->compute);
+    if (st != SGZ_OK) return st;
+    // the one column behind the launch on the compute stream itself, and waited for
+    PcmOut &out = sl.out[kOutTruePeak];
+    if (sgz_status rb = out.readBack(s->tpOut + size_t(s->tpCursor) * channels, channels * sizeof(sgz_truepeak_record), s->tpPinned, s->compute); rb != SGZ_OK) return rb;
+    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) { out.dst = nullptr; return hipFail(e, "hipStreamSynchronize(s->compute)"); }
+    out.drain();
+    s->tpOpen = 0;
+    ++s->tpCursor;
     return SGZ_OK;
 }
 

@@ -125,6 +125,13 @@ LevelColumnsShape levelColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m,
 sgz_status runLevelColumns(const LevelColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
                            uint32_t held, const sgz_level_record *carryIn, sgz_level_record *carryOut, sgz_level_record *d_level, void *scratch,
                            hipStream_t stream);
+// the true-peak lane's reduction (truepeak_columns.hip), the same two steps.  carryIn is read (the history when `continued`, the open column
+// when held > 0) and carryOut is written whole by every call with samples: two places, never the same memory then
+using TruePeakColumnsShape = WaveColumnsShape;
+TruePeakColumnsShape truePeakColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
+sgz_status runTruePeakColumns(const TruePeakColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples,
+                              uint32_t m, uint32_t held, uint32_t continued, const sgz_truepeak_carry *carryIn, sgz_truepeak_carry *carryOut,
+                              sgz_truepeak_record *d_peaks, void *scratch, hipStream_t stream);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
 }  // namespace sgz
