@@ -57,6 +57,10 @@ extern "C" {
  *  host helpers sgz_truepeak_taps, sgz_truepeak_fold and sgz_truepeak_readout and, on the PCM stream, sgz_pcm_stream_set_truepeak,
  *  sgz_pcm_stream_truepeak_for, sgz_pcm_stream_truepeak_state, sgz_pcm_stream_flush_truepeak.  No existing entry point or struct changed and
  *  the suite pins 5; a stream that was never armed enqueues what it did before.  A binding that needs them looks the symbols up.)
+ * (5, later: the loudness lane -- sgz_loudness_filter, sgz_loudness_record, sgz_stage_loudness_columns, sgz_loudness_columns_limits, the host
+ *  helpers sgz_loudness_filter_for_rate, sgz_loudness_taps, sgz_loudness_fold, sgz_loudness_readout and sgz_loudness_integrated and, on the
+ *  PCM stream, sgz_pcm_stream_set_loudness, sgz_pcm_stream_loudness_for, sgz_pcm_stream_loudness_state, sgz_pcm_stream_flush_loudness.  No
+ *  existing entry point or struct changed and the suite pins 5; a stream that was never armed enqueues what it did before.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -836,6 +840,109 @@ sgz_status sgz_pcm_stream_set_truepeak(sgz_pcm_stream *s, uint32_t m /*0 = off*/
 uint64_t   sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
 sgz_status sgz_pcm_stream_truepeak_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
 sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s);
+
+/* The loudness lane: K-weighted energy per screen column and channel of a file's samples -- what momentary, short-term and integrated
+ * loudness after ITU-R BS.1770 / EBU R 128 are read from.  The reference has no counterpart.  An IIR recurrence in fp32 has no
+ * cut-independent bits; this formulation has: the sample axis is cut into short segments on an absolute grid, the filter's state at the
+ * start of every segment is an exact integer FIR over the last W quantised samples (64-bit, order-free), and the fp64 recurrence runs only
+ * over the segment's L samples, in an order fixed here.  Every output then depends on nothing but the samples.
+ * Definition (exact, no tolerance).
+ *  Filter     sgz_loudness_filter: two biquads as doubles, b[2][3] and a[2][2] with a0 = 1, stage 0 the shelf and stage 1 the RLB
+ *             high-pass; W, the memory in samples, and L, the segment length: powers of two, 16 <= L <= W <= 65536.  The coefficients are
+ *             inputs; nothing is derived from a sample rate inside the definition.
+ *  Quantiser  the true-peak lane's: v = (int32) clamp(rintf(x * 2^23), -2^26, +2^26), a NaN gives v = 0 and is not counted; v[k] = 0 for
+ *             k < 0; i counts the samples since the lane was armed or reset.
+ *  Step       transposed direct form II in fp64; every *, + and - is one IEEE operation rounded to nearest even, in this order, with no
+ *             contraction:
+ *                 y = b00*x + s1;   s1 = (b01*x - a00*y) + s2;   s2 = b02*x - a01*y;
+ *                 z = b10*y + t1;   t1 = (b11*y - a10*z) + t2;   t2 = b12*y - a11*z;
+ *             state (s1, s2, t1, t2), output z.
+ *  Tap table  S = 32.  The step run from rest on x = 1, 0, 0, ..; h[c][k], c = 0 .. 3, k = 0 .. W - 1, is state component c after k + 1
+ *             steps; C[c][k] = (int32) rint(2^32 h[c][k]).  The filter is accepted only if every C fits int32 and
+ *             2^26 max_c sum_k |C[c][k]| < 2^62 (sgz_loudness_taps; SGZ_EINVAL otherwise).
+ *  Segment    segment j covers samples j L <= i < (j + 1) L.  Its start state is
+ *                 state_c = (double)(int64) (sum over k = 0 .. W - 1 of C[c][k] v[j L - 1 - k]) * 2^-32
+ *             -- an exact 64-bit integer in any order, one conversion rounded to nearest even, an exact scale.
+ *  Output     z[i] is the step's output when the segment is run from that state over x = (double) v[j L], .., (double) v[i];
+ *             q[i] = (int64) rint(z[i]), ties to even, clamped to +-(2^31 - 1).
+ *  Record     one sgz_loudness_record per (column, channel), 32 bytes, layout [columns][channels], little-endian, arrays on the DEVICE
+ *             aligned to 16: sumsq = the sum of q^2 over the column as an unsigned 128-bit integer (low word first), count = the column's
+ *             non-NaN samples, three reserved words written as 0.  Columns of m samples are counted exactly as the true-peak lane counts
+ *             them (sgz_overview_step with samples in the place of frames; only a flushed last column may be partial).  A flush does not
+ *             move the segment grid.
+ * Integer sums make a coarser column the field-wise sum of the finer ones (sgz_loudness_fold) and any cut of the stream or of a column
+ * gives the same bytes.  Readout: mean square = sumsq / count / 2^46 (1.0 = a full-scale square wave), loudness = -0.691 + 10 log10 of the
+ * sum over channels of G_c ms_c.  Measured against the unsegmented fp64 recurrence the definition differs by less than 1e-4 dB in any
+ * 100 ms block (tests/test_loudness_host.py).
+ * What a cut of the stream carries, per channel: the open column's record, the last W + L - 1 quantised samples and a zero word --
+ * 32 + 4 (W + L) bytes, [channels] of them, aligned to 16; the call re-runs the open segment from its start out of that history without
+ * counting those samples again.  The carry is opaque but for its size (sgz_loudness_columns_limits).
+ *  sgz_stage_loudness_columns  DEVICE pointers; sgz_stage_truepeak_columns' semantics and refusals in every point not named here.  filter:
+ *                      HOST; its tap table is built and uploaded at the filter's first use on a device (the one blocking step) and kept.
+ *                      first_index: the absolute index i of the call's first sample; only first_index % L matters.  continued == 0: the
+ *                      samples before this call are zeros, held must be 0.  d_carry: needed whenever continued != 0 or nsamples > 0; after
+ *                      a call with nsamples > 0 all of it is written (the open column or zeros, the history, the zero word).  The call
+ *                      reads a snapshot of the carry it was given.  nsamples == 0 with held > 0 and flush: one column from the carry
+ *                      alone, the carry untouched.  The launches: one workgroup per (tile of max(4096, L) samples on the segment grid,
+ *                      channel) stages the tile behind its W-sample halo in LDS, forms the segment starts with 32 x 32 -> 64-bit integer
+ *                      multiply-adds, runs one lane per segment and stores q as int32 to stream-ordered scratch; a second launch writes
+ *                      the history; the column sums follow in the level lane's structure (m up to the switch-over, 1024, in tiles; longer
+ *                      columns in slices and a folding launch).  slices: 0 = the library's choice, 1 .. 64 forced, identical bits.
+ *                      SGZ_EINVAL, nothing launched or written: what sgz_stage_truepeak_columns refuses, a null or refused filter,
+ *                      W > 16384 (the halo and a tile must fit the LDS; the host helpers take every W of the definition), nsamples
+ *                      above 2^40, first_index above 2^62.
+ *  sgz_loudness_columns_limits  the column sums' switch-over, the run tile's samples and the carry's bytes for `channels` channels (any
+ *                      result may be NULL); SGZ_EINVAL where the stage call would refuse the filter or the channel count.
+ * The lane inside the sgz_pcm_stream handle: as the true-peak lane, launched behind it.  sgz_pcm_stream_set_loudness(s, filter, m, out,
+ * capacity_columns) arms (m > 0; the filter is copied, a refused one is SGZ_EINVAL), keeps the open column and the history where the
+ * same m and the same filter come with another buffer (draining), refuses another m or another filter while samples are open, and disarms
+ * with m == 0 (filter may be NULL then).  _loudness_for, _loudness_state and _flush_loudness are the true-peak lane's; a flush keeps the
+ * history and the sample index, so the segment grid stays where it is.  reset drops the open column, zeroes the history and the index.
+ * The carry is kept twice and alternated.  Everything an armed stream returns besides the records equals an unarmed stream's.
+ * Host arithmetic, nothing launched:
+ *  sgz_loudness_filter_for_rate  48000: ITU-R BS.1770-4's printed coefficients.  Any other rate in 200 .. 819200: the bilinear transform
+ *                      of the analogue prototype (shelf 1681.974450955533 Hz, +3.999843853973347 dB, Q 0.7071752369554196; high-pass
+ *                      38.13547087602444 Hz, Q 0.5003270373238773).  W = the smallest power of two >= 0.08 rate (at least 256), L = W / 16.
+ *                      Not bit-normative (libm decides the last bits off 48000): a caller may pass any coefficients.
+ *  sgz_loudness_taps   the normative table, C[c][k] at taps[c * W + k] (4 W words), or SGZ_EINVAL with nothing written.
+ *  sgz_loudness_fold   the zoom, with sgz_level_fold's boundary rule; SGZ_EINVAL, nothing written: a null argument, channels == 0, what
+ *                      sgz_overview_view_columns refuses, a folded count above 2^32 - 1.
+ *  sgz_loudness_readout  reads ncols >= 1 consecutive columns [ncols][channels] together: *mean_square = sum_c G_c ms_c with ms_c the sum
+ *                      of the columns' sumsq over the sum of their counts over 2^46 (0 for a channel without samples), *lufs = -0.691 +
+ *                      10 log10 of it, -inf when it is 0.  weights: G_c [channels], NULL = all 1.  4 columns of 100 ms are momentary
+ *                      loudness, 30 short-term.  Either result may be NULL.
+ *  sgz_loudness_integrated  gated loudness of n columns meant to be 100 ms each: blocks of 4 columns with a step of 1; the absolute gate
+ *                      at -70, then the relative gate 10 below the loudness of the absolutely gated blocks; -inf when no block passes
+ *                      (or n < 4).  Only whole columns take part: the caller leaves a flushed partial last column out of n. */
+typedef struct sgz_loudness_filter {
+    double   b[2][3];   /* numerators: stage 0 the shelf, stage 1 the high-pass */
+    double   a[2][2];   /* denominators a1, a2 of each stage (a0 = 1) */
+    uint32_t W;         /* memory in samples, a power of two */
+    uint32_t L;         /* segment length, a power of two, 16 <= L <= W <= 65536 */
+} sgz_loudness_filter;         /* 88 bytes */
+typedef struct sgz_loudness_record {
+    uint64_t sumsq[2];     /* the sum of q^2 over the column, unsigned 128-bit, low word first */
+    uint32_t count;        /* the column's non-NaN samples */
+    uint32_t reserved[3];  /* written as 0 */
+} sgz_loudness_record;         /* 32 bytes */
+sgz_status sgz_stage_loudness_columns(const float *d_planar, size_t channel_stride, uint32_t channels, size_t nsamples,
+                                      const sgz_loudness_filter *filter, uint64_t first_index, uint32_t m, uint32_t held, int flush,
+                                      uint32_t continued, uint32_t slices, void *d_carry, sgz_loudness_record *d_records /*[columns][channels]*/,
+                                      void *stream);
+sgz_status sgz_loudness_columns_limits(const sgz_loudness_filter *filter, uint32_t channels, uint32_t *switch_over, uint32_t *tile_samples,
+                                       size_t *carry_bytes);
+sgz_status sgz_loudness_filter_for_rate(double rate, sgz_loudness_filter *f);
+sgz_status sgz_loudness_taps(const sgz_loudness_filter *f, int32_t *taps /*[4][W]*/);
+sgz_status sgz_loudness_fold(const sgz_loudness_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns,
+                             sgz_loudness_record *out);
+sgz_status sgz_loudness_readout(const sgz_loudness_record *recs, size_t ncols, uint32_t channels, const double *weights /*[channels] or NULL*/,
+                                double *lufs, double *mean_square);
+sgz_status sgz_loudness_integrated(const sgz_loudness_record *recs, size_t n, uint32_t channels, const double *weights, double *lufs);
+sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_filter *filter, uint32_t m /*0 = off*/,
+                                       sgz_loudness_record *out /*HOST [capacity][channels]*/, uint64_t capacity_columns);
+uint64_t   sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
+sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
+sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s);
 
 /* The track lane: the tracker's curve over a file -- the reference's drawFrequencyTracking readout (SpectrumRendering.cpp:300-377, the
  * line-results branch) for every frame of a streamed file, in bounded memory.  sgz_spectrogram_track_device / _host want the whole file

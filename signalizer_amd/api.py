@@ -123,6 +123,17 @@ TRUEPEAK_DTYPE = np.dtype([("peak", "<u8"), ("count", "<u4"), ("overs", "<u4")])
 TRUEPEAK_CARRY_DTYPE = np.dtype([("open", TRUEPEAK_DTYPE), ("hist", "<i4", (11,)), ("reserved", "<u4")])
 assert TRUEPEAK_DTYPE.itemsize == 16 and TRUEPEAK_CARRY_DTYPE.itemsize == 64
 
+# sgz_loudness_record: one per (column, channel) of the loudness lane, 32 bytes (sumsq: unsigned 128-bit, low word first)
+LOUDNESS_DTYPE = np.dtype([("sumsq", "<u8", (2,)), ("count", "<u4"), ("reserved", "<u4", (3,))])
+assert LOUDNESS_DTYPE.itemsize == 32
+
+
+class LoudnessFilter(C.Structure):
+    _fields_ = [("b", (C.c_double * 3) * 2), ("a", (C.c_double * 2) * 2), ("W", C.c_uint32), ("L", C.c_uint32)]
+
+
+assert C.sizeof(LoudnessFilter) == 88
+
 
 class LineGraphStyle(C.Structure):
     _fields_ = [("colour_one", (C.c_uint8 * 4) * NUM_GRAPHS), ("colour_two", (C.c_uint8 * 4) * NUM_GRAPHS), ("flood_alpha", C.c_float),
@@ -216,6 +227,9 @@ EXPORTS = [
     "sgz_pcm_stream_flush_level", "sgz_level_fold", "sgz_level_readout",
     "sgz_stage_truepeak_columns", "sgz_truepeak_columns_limits", "sgz_truepeak_taps", "sgz_truepeak_fold", "sgz_truepeak_readout",
     "sgz_pcm_stream_set_truepeak", "sgz_pcm_stream_truepeak_for", "sgz_pcm_stream_truepeak_state", "sgz_pcm_stream_flush_truepeak",
+    "sgz_stage_loudness_columns", "sgz_loudness_columns_limits", "sgz_loudness_filter_for_rate", "sgz_loudness_taps", "sgz_loudness_fold",
+    "sgz_loudness_readout", "sgz_loudness_integrated",
+    "sgz_pcm_stream_set_loudness", "sgz_pcm_stream_loudness_for", "sgz_pcm_stream_loudness_state", "sgz_pcm_stream_flush_loudness",
 ]
 
 
@@ -468,6 +482,19 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_truepeak_for.restype = u64
     L.sgz_pcm_stream_truepeak_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.sgz_pcm_stream_flush_truepeak.argtypes = [vp]
+    fp = C.POINTER(LoudnessFilter)
+    L.sgz_stage_loudness_columns.argtypes = [vp, sz, u32, sz, fp, u64, u32, u32, C.c_int, u32, u32, vp, vp, vp]
+    L.sgz_loudness_columns_limits.argtypes = [fp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(sz)]
+    L.sgz_loudness_filter_for_rate.argtypes = [C.c_double, fp]
+    L.sgz_loudness_taps.argtypes = [fp, vp]
+    L.sgz_loudness_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
+    L.sgz_loudness_readout.argtypes = [vp, sz, u32, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sgz_loudness_integrated.argtypes = [vp, sz, u32, vp, C.POINTER(C.c_double)]
+    L.sgz_pcm_stream_set_loudness.argtypes = [vp, fp, u32, vp, u64]
+    L.sgz_pcm_stream_loudness_for.argtypes = [vp, sz, C.c_int]
+    L.sgz_pcm_stream_loudness_for.restype = u64
+    L.sgz_pcm_stream_loudness_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.sgz_pcm_stream_flush_loudness.argtypes = [vp]
     _lib = L
     return L
 
@@ -1297,6 +1324,31 @@ class PcmStream:
         check(lib().sgz_pcm_stream_flush_truepeak(self.h))
 
 
+    # the loudness lane: one sgz_loudness_record per column of m samples and channel, beside whatever the feeds render
+    def set_loudness(self, filter, m: int, out=None, capacity_columns: int | None = None) -> None:
+        """sgz_pcm_stream_set_loudness: filter -- a LoudnessFilter (None allowed with m == 0); out -- a LOUDNESS_DTYPE numpy array [capacity,
+        channels] or a host torch uint8 tensor [capacity, channels, 32] (kept alive here; pinned memory is written in place); m == 0 disarms"""
+        if capacity_columns is None:
+            capacity_columns = 0 if out is None else int(out.shape[0])
+        check(lib().sgz_pcm_stream_set_loudness(self.h, C.byref(filter) if filter is not None else None, m,
+                                                _buf_ptr(out) if out is not None and m else None, capacity_columns if m else 0))
+        self._loudness_out = out if m else None
+
+    def loudness_for(self, nsamples: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_loudness_for: loudness columns the next feed of nsamples closes"""
+        return int(lib().sgz_pcm_stream_loudness_for(self.h, nsamples, int(bool(flush))))
+
+    def loudness_state(self):
+        """sgz_pcm_stream_loudness_state: (columns written since the lane was armed, samples of the open column)"""
+        c, o = C.c_uint64(0), C.c_uint64(0)
+        check(lib().sgz_pcm_stream_loudness_state(self.h, C.byref(c), C.byref(o)))
+        return int(c.value), int(o.value)
+
+    def flush_loudness(self) -> None:
+        """sgz_pcm_stream_flush_loudness: closes the open column (one more record per channel at the cursor); waits"""
+        check(lib().sgz_pcm_stream_flush_loudness(self.h))
+
+
     # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
     def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:
         """sgz_pcm_stream_set_track: out -- a float64 numpy array or host torch tensor [capacity, pairs, 6] (kept alive here; pinned memory is
@@ -1412,6 +1464,80 @@ def truepeak_readout(record):
     p, d = C.c_double(0), C.c_double(0)
     check(lib().sgz_truepeak_readout(_np_ptr(rec), C.byref(p), C.byref(d)))
     return p.value, d.value
+
+
+def loudness_filter_for_rate(rate: float) -> LoudnessFilter:
+    """sgz_loudness_filter_for_rate: BS.1770's K-weighting at `rate`, W = the smallest power of two >= 0.08 rate, L = W / 16"""
+    f = LoudnessFilter()
+    check(lib().sgz_loudness_filter_for_rate(float(rate), C.byref(f)))
+    return f
+
+
+def loudness_filter(b, a, W: int, L: int) -> LoudnessFilter:
+    """a LoudnessFilter of any coefficients: b [2][3], a [2][2] (a1, a2 of each stage)"""
+    f = LoudnessFilter()
+    for s in range(2):
+        for i in range(3):
+            f.b[s][i] = float(b[s][i])
+        for i in range(2):
+            f.a[s][i] = float(a[s][i])
+    f.W, f.L = W, L
+    return f
+
+
+def loudness_taps(f: LoudnessFilter):
+    """sgz_loudness_taps: (status, the normative table int32 [4, W] or None)"""
+    taps = np.full((4, max(int(f.W), 1)), 0x5A5A5A5A, np.int32)
+    st = lib().sgz_loudness_taps(C.byref(f), _np_ptr(taps))
+    return st, (taps if st == SGZ_OK else None)
+
+
+def loudness_columns_limits(f: LoudnessFilter, channels: int = 1):
+    """sgz_loudness_columns_limits: (the column sums' switch-over, the run tile's samples, the carry's bytes for `channels` channels)"""
+    s, t, b = C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+    check(lib().sgz_loudness_columns_limits(C.byref(f), channels, C.byref(s), C.byref(t), C.byref(b)))
+    return int(s.value), int(t.value), int(b.value)
+
+
+def stage_loudness_columns(planar, channel_stride: int, channels: int, nsamples: int, filter, first_index: int, m: int, held: int = 0,
+                           flush: bool = True, continued: bool = False, slices: int = 0, carry=None, records=None, stream=None) -> int:
+    """sgz_stage_loudness_columns as it is: planar / carry / records -- cuda tensors (their data pointers; any may be None where the call allows
+    NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    return lib().sgz_stage_loudness_columns(ptr(planar), channel_stride, channels, nsamples, C.byref(filter) if filter is not None else None, first_index,
+                                            m, held, int(bool(flush)), int(bool(continued)), slices, ptr(carry), ptr(records), C.c_void_p(s) if s else None)
+
+
+def loudness_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_loudness_fold: LOUDNESS_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels]"""
+    records = np.ascontiguousarray(records, LOUDNESS_DTYPE)
+    n, channels = records.shape
+    x1 = n if x1 is None else x1
+    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), LOUDNESS_DTYPE)
+    check(lib().sgz_loudness_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
+    return out[:min(out_columns, x1 - x0)]
+
+
+def loudness_readout(records: np.ndarray, weights=None):
+    """sgz_loudness_readout of LOUDNESS_DTYPE records [ncols, channels] read together: (LUFS, the weighted mean square)"""
+    records = np.ascontiguousarray(records, LOUDNESS_DTYPE)
+    ncols, channels = records.shape
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64)
+    l, z = C.c_double(0), C.c_double(0)
+    check(lib().sgz_loudness_readout(_np_ptr(records), ncols, channels, _np_ptr(w) if w is not None else None, C.byref(l), C.byref(z)))
+    return l.value, z.value
+
+
+def loudness_integrated(records: np.ndarray, weights=None) -> float:
+    """sgz_loudness_integrated of LOUDNESS_DTYPE records [n, channels] of 100 ms columns: the gated loudness in LUFS"""
+    records = np.ascontiguousarray(records, LOUDNESS_DTYPE)
+    n, channels = records.shape
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64)
+    l = C.c_double(0)
+    check(lib().sgz_loudness_integrated(_np_ptr(records), n, channels, _np_ptr(w) if w is not None else None, C.byref(l)))
+    return l.value
 
 
 def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,

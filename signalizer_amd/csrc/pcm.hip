@@ -4,14 +4,15 @@
 // and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, waveform columns, track records --
 // is a PcmOut: device block, pinned twin, pending host copy.  Armed, the waveform lane (wave_columns.hip) and the level lane
 // (level_columns.hip) reduce every piece's new samples behind the converter and the track lane (tracker.hip) searches every piece's line
-// results behind its render; the true-peak lane (truepeak_columns.hip) filters every piece's new samples behind them.  All ride the same
-// read-back.
+// results behind its render; the true-peak lane (truepeak_columns.hip) filters every piece's new samples behind them, and the loudness lane
+// (loudness_columns.hip) behind that one.  All ride the same read-back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <vector>
 #include <new>
 
 #include "rt_common.hpp"       // isPinnedHost
@@ -193,7 +194,8 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // [columns][C][P] the overview feed's, ceil(maxFrames / k) + 1 columns of them; Wave float2 [ceil(chunk / m) + 1][channels] the waveform
 // lane's; Track sgz_line_peak [maxFrames][pairs] the track lane's; Level sgz_level_record [ceil(chunk / m) + 1][pairs] the level lane's;
 // TruePeak sgz_truepeak_record [ceil(chunk / m) + 1][channels] the true-peak lane's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kPcmOuts };
+// Loudness sgz_loudness_record [ceil(chunk / m) + 1][channels] the loudness lane's.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -288,6 +290,19 @@ struct sgz_pcm_stream {
     bool tpPinned = false, tpContinued = false;
     sgz_truepeak_carry *d_tpCarry = nullptr;
     int tpCur = 0;
+    // the loudness lane (ldM > 0: armed), as the true-peak lane; its carry d_ldCarry holds two halves of loudnessCarryBytes(ldFilter) * channels
+    // bytes (ldCarryCap: what is allocated).  ldIndex: the lane's samples so far -- the absolute index of the next one, which a flush does not move
+    uint32_t ldM = 0;
+    sgz_loudness_filter ldFilter{};
+    sgz_loudness_record *ldOut = nullptr;
+    uint64_t ldCap = 0, ldCursor = 0, ldOpen = 0, ldIndex = 0;
+    bool ldPinned = false, ldContinued = false;
+    uint8_t *d_ldCarry = nullptr;
+    size_t ldCarryCap = 0;
+    // the lane's scratch (q of a piece's samples, partial records), kept: every piece's launches are on the compute stream, one behind the other
+    void *d_ldScratch = nullptr;
+    size_t ldScratchCap = 0;
+    int ldCur = 0;
 };
 
 struct sgz_plan { Plan impl; };
@@ -453,6 +468,58 @@ static sgz_status pcmTruePeakReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t c
     return st;
 }
 
+// ---- the loudness lane inside the stream (sgz.h, "The loudness lane") ------------------------------------------------------------------------
+static uint8_t *pcmLoudnessCarry(const sgz_pcm_stream &s, int half) { return s.d_ldCarry + size_t(half) * loudnessCarryBytes(s.ldFilter) * s.numChannels; }
+
+// what a feed checks for the lane before anything is consumed: the columns its samples close fit behind the cursor
+static sgz_status pcmLoudnessFits(const sgz_pcm_stream &s, size_t nsamples)
+{
+    if (s.ldM && (s.ldOpen + nsamples) / s.ldM > s.ldCap - s.ldCursor)
+        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed closes more loudness columns than the buffer has left (sgz_pcm_stream_loudness_for; re-arm with sgz_pcm_stream_set_loudness)");
+    return SGZ_OK;
+}
+
+// a slot's records of a piece, ceil(chunk / m) + 1 columns of them (both slots are idle between feeds)
+static sgz_status pcmLoudnessBuffers(sgz_pcm_stream &s, PcmSlot &sl)
+{
+    return s.ldM ? sl.out[kOutLoudness].reserve(((s.chunk + s.ldM - 1) / s.ldM + 1) * s.numChannels * sizeof(sgz_loudness_record), !s.ldPinned) : SGZ_OK;
+}
+
+// the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the records they close, into the slot;
+// the open one and the new history into the other half of the carry
+static sgz_status pcmLoudnessPiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
+{
+    *columns = 0;
+    if (!s.ldM || n == 0) return SGZ_OK;
+    const LoudnessColumnsShape sh = loudnessColumnsShape(s.numChannels, n, s.ldM, uint32_t(s.ldOpen), 0, 0);
+    if (sh.scratchBytes > s.ldScratchCap) {                                         // (the first piece of a feed is its largest: this happens once)
+        SGZ_HIP(hipStreamSynchronize(s.compute));
+        if (s.d_ldScratch) { (void)hipFree(s.d_ldScratch); s.d_ldScratch = nullptr; s.ldScratchCap = 0; }
+        SGZ_HIP(hipMalloc(&s.d_ldScratch, sh.scratchBytes));
+        s.ldScratchCap = sh.scratchBytes;
+    }
+    const sgz_status st = runLoudnessColumns(sh, s.ldFilter, fresh, s.stride, s.numChannels, n, s.ldIndex, s.ldM, uint32_t(s.ldOpen), s.ldContinued ? 1u : 0u,
+                                             pcmLoudnessCarry(s, s.ldCur), pcmLoudnessCarry(s, s.ldCur ^ 1), sl.out[kOutLoudness].as<sgz_loudness_record>(),
+                                             s.d_ldScratch, s.compute);
+    if (st != SGZ_OK) return st;
+    s.ldCur ^= 1;                                                                   // (the history moved, whether or not a column stays open)
+    s.ldContinued = true;
+    s.ldOpen = (s.ldOpen + n) % s.ldM;
+    s.ldIndex += n;
+    *columns = sh.closed;
+    return SGZ_OK;
+}
+
+// the piece's records to the caller's buffer at the cursor, on the read-back stream
+static sgz_status pcmLoudnessReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
+{
+    if (!columns) return SGZ_OK;
+    const size_t column = s.numChannels;
+    const sgz_status st = sl.out[kOutLoudness].readBack(s.ldOut + size_t(s.ldCursor) * column, size_t(columns) * column * sizeof(sgz_loudness_record), s.ldPinned, s.back);
+    if (st == SGZ_OK) s.ldCursor += columns;
+    return st;
+}
+
 // ---- the track lane inside the stream (sgz.h, "The track lane") ----------------------------------------------------------------------------
 // what a feed checks for the lane before anything is consumed: the frames its samples complete fit behind the cursor
 static sgz_status pcmTrackFits(const sgz_pcm_stream &s, uint64_t frames)
@@ -502,6 +569,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
         if (sgz_status st = pcmTrackBuffers(s, sl); st != SGZ_OK) return st;
         if (sgz_status st = pcmLevelBuffers(s, sl); st != SGZ_OK) return st;
         if (sgz_status st = pcmTruePeakBuffers(s, sl); st != SGZ_OK) return st;
+        if (sgz_status st = pcmLoudnessBuffers(s, sl); st != SGZ_OK) return st;
     }
     const uint8_t *src = static_cast<const uint8_t *>(pcm);
     uint64_t done = 0, chunks = 0;
@@ -526,10 +594,11 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             if (n)
                 if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s.format, s.srcChannels, n, s.map, s.numChannels, planar + s.held, s.stride, s.compute); st != SGZ_OK) return st;
             if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s.compute));
-            uint64_t waveColumns = 0, levelColumns = 0, truePeakColumns = 0, units = 0;
+            uint64_t waveColumns = 0, levelColumns = 0, truePeakColumns = 0, loudnessColumns = 0, units = 0;
             if (sgz_status st = pcmWavePiece(s, sl, planar + s.held, n, &waveColumns); st != SGZ_OK) return st;
             if (sgz_status st = pcmLevelPiece(s, sl, planar + s.held, n, &levelColumns); st != SGZ_OK) return st;
             if (sgz_status st = pcmTruePeakPiece(s, sl, planar + s.held, n, &truePeakColumns); st != SGZ_OK) return st;
+            if (sgz_status st = pcmLoudnessPiece(s, sl, planar + s.held, n, &loudnessColumns); st != SGZ_OK) return st;
             const uint64_t total = s.held + n;
             if (sgz_status st = part.render(s, sl, planar, size_t(total), frames, at + n == nsamples, &units); st != SGZ_OK) return st;
             if (frames) {
@@ -541,7 +610,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             SGZ_HIP(hipEventRecord(sl.ev[4], s.compute));
             // 3. read back (a piece may close waveform or level columns and complete no frame, or complete frames whose records are all it returns)
             const uint64_t trackFrames = s.trArmed ? frames : 0;
-            sl.rendered = units > 0 || waveColumns > 0 || trackFrames > 0 || levelColumns > 0 || truePeakColumns > 0;
+            sl.rendered = units > 0 || waveColumns > 0 || trackFrames > 0 || levelColumns > 0 || truePeakColumns > 0 || loudnessColumns > 0;
             if (sl.rendered) {
                 SGZ_HIP(hipStreamWaitEvent(s.back, sl.ev[4], 0));
                 if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s.back));
@@ -551,6 +620,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
                 if (sgz_status st = pcmWaveReadBack(s, sl, waveColumns); st != SGZ_OK) return st;
                 if (sgz_status st = pcmLevelReadBack(s, sl, levelColumns); st != SGZ_OK) return st;
                 if (sgz_status st = pcmTruePeakReadBack(s, sl, truePeakColumns); st != SGZ_OK) return st;
+                if (sgz_status st = pcmLoudnessReadBack(s, sl, loudnessColumns); st != SGZ_OK) return st;
                 SGZ_HIP(hipEventRecord(sl.ev[6], s.back));
             }
             sl.busy = true;
@@ -706,7 +776,7 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry, (void *)s->d_lvCarry, (void *)s->d_tpCarry}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry, (void *)s->d_lvCarry, (void *)s->d_tpCarry, (void *)s->d_ldCarry, s->d_ldScratch}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
     if (s->plan) sgz_plan_destroy(s->plan);
     delete s;
@@ -765,6 +835,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     s->trCursor = 0;                                                                // the track's records too; the lane stays armed
     s->lvOpen = 0; s->lvCursor = 0;                                                 // the level lane as the waveform's
     s->tpOpen = 0; s->tpCursor = 0; s->tpContinued = false;                         // the true-peak lane too, and its history is zeros again
+    s->ldOpen = 0; s->ldCursor = 0; s->ldIndex = 0; s->ldContinued = false;         // the loudness lane as that one; its samples count from 0 again
     return SGZ_OK;
 }
 
@@ -782,6 +853,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmLevelFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTruePeakFits(*s, nsamples); st != SGZ_OK) return st;
+    if (sgz_status st = pcmLoudnessFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTrackFits(*s, need); st != SGZ_OK) return st;
     PcmFramesPart part{rgba_out, lines_out, need, need && isPinnedHost(rgba_out), need && lines_out && isPinnedHost(lines_out)};
     return pcmFeed(*s, pcm, nsamples, false, part, frames_out, timing, t0);
@@ -827,6 +899,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmLevelFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTruePeakFits(*s, nsamples); st != SGZ_OK) return st;
+    if (sgz_status st = pcmLoudnessFits(*s, nsamples); st != SGZ_OK) return st;
     if (sgz_status st = pcmTrackFits(*s, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
     PcmColumnsPart part{rgba_out, peaks_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && peaks_out && isPinnedHost(peaks_out)};
     // (a feed without samples still has one piece when it flushes an open column)
@@ -1008,6 +1081,81 @@ sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s)
     out.drain();
     s->tpOpen = 0;
     ++s->tpCursor;
+    return SGZ_OK;
+}
+
+// ---- the loudness lane's calls ----------------------------------------------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_filter *filter, uint32_t m, sgz_loudness_record *out, uint64_t capacity_columns)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (m == 0) {                                                  // off: the open column, the history and the index are dropped
+        s->ldM = 0; s->ldOut = nullptr; s->ldCap = s->ldCursor = s->ldOpen = s->ldIndex = 0; s->ldContinued = false;
+        return SGZ_OK;
+    }
+    if (!filter) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: null filter");
+    if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: null out");
+    if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_loudness_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: out is not aligned to 8 bytes");
+    const bool same = s->ldM == m && std::memcmp(&s->ldFilter, filter, sizeof *filter) == 0;
+    if (s->ldOpen && !same) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: m or the filter differs from the open column's -- flush it (sgz_pcm_stream_flush_loudness), disarm or reset first");
+    if (!same) {
+        // (what the stage call refuses, and the tap table: a refused filter arms nothing)
+        size_t bytes = 0;
+        if (sgz_status st = sgz_loudness_columns_limits(filter, s->numChannels, nullptr, nullptr, &bytes); st != SGZ_OK) return st;
+        std::vector<int32_t> taps(size_t(4) * filter->W);
+        if (sgz_status st = sgz_loudness_taps(filter, taps.data()); st != SGZ_OK) return st;
+        if (s->ldCarryCap < 2 * bytes) {
+            // (both slots are idle between feeds, but a flush's launch may still read the old block: wait for it)
+            SGZ_HIP(hipStreamSynchronize(s->compute));
+            if (s->d_ldCarry) { (void)hipFree(s->d_ldCarry); s->d_ldCarry = nullptr; s->ldCarryCap = 0; }
+            SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_ldCarry), 2 * bytes));
+            s->ldCarryCap = 2 * bytes;
+        }
+        s->ldFilter = *filter;
+        s->ldContinued = false;                                    // (arming: the lane starts at the next sample, index 0, with a zero history)
+        s->ldIndex = 0; s->ldCur = 0;
+    }
+    s->ldM = m; s->ldOut = out; s->ldCap = capacity_columns; s->ldCursor = 0;
+    s->ldPinned = capacity_columns && isPinnedHost(out);
+    return SGZ_OK;
+}
+
+uint64_t sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, int flush)
+{
+    if (!s || !s->ldM) return 0;
+    const uint64_t t = s->ldOpen + nsamples;
+    return t / s->ldM + ((flush && t % s->ldM) ? 1u : 0u);
+}
+
+sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (columns_written) *columns_written = s->ldCursor;
+    if (open_samples) *open_samples = s->ldOpen;
+    return SGZ_OK;
+}
+
+sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!s->ldM) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_loudness: the lane is off (sgz_pcm_stream_set_loudness)");
+    if (!s->ldOpen) return SGZ_OK;
+    if (s->ldCursor >= s->ldCap) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_loudness: no column left in the buffer (re-arm with sgz_pcm_stream_set_loudness)");
+    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
+    if (sgz_status st = pcmLoudnessBuffers(*s, sl); st != SGZ_OK) return st;
+    const uint32_t channels = s->numChannels;
+    // the emit launch alone, on the open column of the current half; the carry, and with it the history and the segment grid, stays where it is
+    const LoudnessColumnsShape sh = loudnessColumnsShape(channels, 0, s->ldM, uint32_t(s->ldOpen), 1, 0);
+    const sgz_status st = runLoudnessColumns(sh, s->ldFilter, s->d_planar[s->cur], s->stride, channels, 0, s->ldIndex, s->ldM, uint32_t(s->ldOpen), 1u,
+                                             pcmLoudnessCarry(*s, s->ldCur), pcmLoudnessCarry(*s, s->ldCur ^ 1), sl.out[kOutLoudness].as<sgz_loudness_record>(),
+                                             nullptr, s->compute);
+    if (st != SGZ_OK) return st;
+    // the one column behind the launch on the compute stream itself, and waited for
+    PcmOut &out = sl.out[kOutLoudness];
+    if (sgz_status rb = out.readBack(s->ldOut + size_t(s->ldCursor) * channels, channels * sizeof(sgz_loudness_record), s->ldPinned, s->compute); rb != SGZ_OK) return rb;
+    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) { out.dst = nullptr; return hipFail(e, "hipStreamSynchronize(s->compute)"); }
+    out.drain();
+    s->ldOpen = 0;
+    ++s->ldCursor;
     return SGZ_OK;
 }
 

@@ -132,6 +132,15 @@ TruePeakColumnsShape truePeakColumnsShape(uint32_t channels, size_t nsamples, ui
 sgz_status runTruePeakColumns(const TruePeakColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples,
                               uint32_t m, uint32_t held, uint32_t continued, const sgz_truepeak_carry *carryIn, sgz_truepeak_carry *carryOut,
                               sgz_truepeak_record *d_peaks, void *scratch, hipStream_t stream);
+// the loudness lane's reduction (loudness_columns.hip), the same two steps.  The carry is loudnessCarryBytes(f) bytes per channel: the open
+// column's record, the last W + L - 1 quantised samples, a zero word.  firstIndex: the absolute index of the call's first sample (the segment
+// phase).  scratch: sh.scratchBytes bytes aligned to 16 (q of every sample, then the sliced form's partial records)
+using LoudnessColumnsShape = WaveColumnsShape;
+size_t loudnessCarryBytes(const sgz_loudness_filter &f);
+LoudnessColumnsShape loudnessColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
+sgz_status runLoudnessColumns(const LoudnessColumnsShape &sh, const sgz_loudness_filter &f, const float *d_planar, size_t channelStride,
+                              uint32_t channels, size_t nsamples, uint64_t firstIndex, uint32_t m, uint32_t held, uint32_t continued,
+                              const void *carryIn, void *carryOut, sgz_loudness_record *d_out, void *scratch, hipStream_t stream);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
 }  // namespace sgz
