@@ -22,7 +22,7 @@ namespace sgz {
 
 thread_local std::string g_lastError;
 #ifdef SGZ_SCHED_SWEEP
-int g_schedule[3] = {-1, -1, -1};      // tools/unit_trace_image.py, tools/image_sched_sweep.py: nyDelay, mateDelay, mateAdjacent of a one-round image-only launch (< 0: the build's default)
+int g_schedule[7] = {-1, -1, -1, -1, -1, -1, -1};      // tools/unit_trace_image.py, tools/image_sched_sweep.py: nyDelay, mateDelay, mateAdjacent, then prioFirst, prioMate, prioNy, prioScope of a one-round image-only launch (< 0: the build's default)
 #endif
 #ifdef SGZ_DEBUG
 uint32_t g_ablate = 0;      // tools/ablate.py
@@ -381,10 +381,23 @@ sgz_status runStft(Plan &p, const float *d_planar, size_t chStride, long frames,
         // keeps the rules of the long launches.
         if (rp.nyFrames && !rp.pipelined && tasks > long(rp.roundSize >> 1) && tasks < long(rp.roundSize)) {
             rp.mateAdjacent = SGZ_MATE_ADJACENT;
+            // The mates' wave priorities: only while a channel workgroup outlasts a Nyquist workgroup (three frames each at the most: up to
+            // 384 frames at 256 CUs) and the whole grid is one generation.  Measured (NOTES.md, profiles/r08a staircase): -0.5 ... -0.7 us
+            // at 257 ... 348 frames, +-0 at 400 (four frames per Nyquist workgroup: they end the launch), +0.2 us from 420; a second
+            // generation runs under the long launches' priorities, which these would undo.  Launches that get none run the kernel
+            // instantiation without the priority code (launchStftReal).
+            const long nyUnits = long(p.C) * ((frames + long(rp.nyFrames) - 1) / long(rp.nyFrames));
+            if (rp.nyFrames <= 3u && tasks + nyUnits <= long(rp.roundSize)) {
+                rp.prioFirst = SGZ_PRIO_FIRST; rp.prioMate = SGZ_PRIO_MATE; rp.prioNy = SGZ_PRIO_NY; rp.prioScope = SGZ_PRIO_SCOPE;
+            }
 #ifdef SGZ_SCHED_SWEEP
             if (g_schedule[0] >= 0) rp.nyDelay = uint32_t(g_schedule[0]);
             if (g_schedule[1] >= 0) rp.mateDelay = uint32_t(g_schedule[1]);
             if (g_schedule[2] >= 0) rp.mateAdjacent = uint32_t(g_schedule[2]);
+            if (g_schedule[3] >= 0) rp.prioFirst = uint32_t(g_schedule[3]) & 3u;
+            if (g_schedule[4] >= 0) rp.prioMate = uint32_t(g_schedule[4]) & 3u;
+            if (g_schedule[5] >= 0) rp.prioNy = uint32_t(g_schedule[5]) & 3u;
+            if (g_schedule[6] >= 0) rp.prioScope = uint32_t(g_schedule[6]) & 3u;
 #endif
         }
 #ifdef SGZ_DEBUG
@@ -1323,6 +1336,8 @@ sgz_status sgz_stage_finish_pixel(const float *d_x, float *d_y, size_t n, void *
 /* -DSGZ_SCHED_SWEEP builds (every -DSGZ_DEBUG build is one; not in sgz.h): the start-up schedule of the next one-round image-only launches,
  * delays in steps of ~1 k clocks, < 0: the build's default */
 void sgz_debug_set_schedule(int ny_delay, int mate_delay, int mate_adjacent) { g_schedule[0] = ny_delay; g_schedule[1] = mate_delay; g_schedule[2] = mate_adjacent; }
+/* ... and its wave priorities (0 .. 3: first-on-CU channel workgroup of a doubled CU, its mate, the Nyquist role) with their scope (RealParams::prioScope, 0 .. 3); < 0: the build's default.  sgz_debug_set_schedule leaves them alone. */
+void sgz_debug_set_priorities(int prio_first, int prio_mate, int prio_ny, int prio_scope) { g_schedule[3] = prio_first; g_schedule[4] = prio_mate; g_schedule[5] = prio_ny; g_schedule[6] = prio_scope; }
 #endif
 
 #ifdef SGZ_DEBUG

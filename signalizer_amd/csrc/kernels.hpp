@@ -94,12 +94,40 @@ struct RealParams {
     uint32_t mateAdjacent;    // 1: workgroups b and b + #CUs, which share a CU, take neighbouring frames (real_common.hpp unitOfIndex)
     uint32_t nyDelay;         // -DSGZ_SCHED_SWEEP builds only (measured and dropped, NOTES.md): steps of ~1 k clocks a Nyquist workgroup sleeps
     uint32_t mateDelay;       // ... and the second channel workgroup of a CU sleeps, before its first request
+    // Wave priorities (s_setprio, 0 .. 3) between the two channel workgroups of a doubled CU -- a shift nobody sleeps for: set behind a
+    // workgroup's sample and table requests; 0: the role's priority is left alone.  Compiled in where SGZ_IMAGE_PRIO is set (below).
+    // runStft hands them out in the part of the window where they pay (Nyquist workgroups of at most three frames, one generation); a
+    // product build takes the VALUES from SGZ_PRIO_* and only "zero or not" from these fields, a -DSGZ_SCHED_SWEEP build takes the fields.
+    uint32_t prioFirst;       // the first-on-CU channel workgroup of a doubled CU: b < #CUs and b + #CUs < channel workgroups
+    uint32_t prioMate;        // its mate: #CUs <= b < channel workgroups
+    uint32_t prioNy;          // the Nyquist role, from its top
+    uint32_t prioScope;       // where a channel workgroup holds it.  0: behind its requests, for the rest of its life; 1: the VALU-bound passes
+                              // only -- from behind pass 1's butterflies to the end of the recombination, priority 0 behind it; 2: from
+                              // behind pass 1's butterflies for the rest of its life; 3: behind its requests to the end of the recombination.
+                              // (The Nyquist role: its whole life.)
 };
 #ifndef SGZ_MATE_ADJACENT
 #define SGZ_MATE_ADJACENT 1     // compile-time default, as SGZ_STAGGER is one (spectrum_real.hip)
 #endif
 #if defined(SGZ_DEBUG) && !defined(SGZ_SCHED_SWEEP)
-#define SGZ_SCHED_SWEEP         // the start-up delays and sgz_debug_set_schedule (tools/image_sched_sweep.py, tools/unit_trace_image.py)
+#define SGZ_SCHED_SWEEP         // the start-up delays, the priorities at run time and sgz_debug_set_schedule (tools/image_sched_sweep.py, tools/unit_trace_image.py)
+#endif
+// compile-time defaults of the one-round priorities (first-on-CU, mate, Nyquist, scope), as SGZ_MATE_ADJACENT is one.  Kept (NOTES.md,
+// profiles/r08a): the mate at priority 1 through the VALU-bound passes, everybody else left alone.
+#ifndef SGZ_PRIO_FIRST
+#define SGZ_PRIO_FIRST 0
+#endif
+#ifndef SGZ_PRIO_MATE
+#define SGZ_PRIO_MATE 1
+#endif
+#ifndef SGZ_PRIO_NY
+#define SGZ_PRIO_NY 0
+#endif
+#ifndef SGZ_PRIO_SCOPE
+#define SGZ_PRIO_SCOPE 1
+#endif
+#if defined(SGZ_SCHED_SWEEP) || SGZ_PRIO_FIRST || SGZ_PRIO_MATE || SGZ_PRIO_NY
+#define SGZ_IMAGE_PRIO          // the kernel reads RealParams::prio*: a build whose defaults are all 0 carries none of that code
 #endif
 constexpr int kLowBins = 24;
 constexpr uint32_t kMaxNyFrames = 4096;   // SGZ_OPT_IMAGE_ONLY_SPLIT's largest forced size (runStft also caps it at the launch's frame count)

@@ -183,13 +183,23 @@ __device__ __forceinline__ void realMapSettle(const P &prm, float *lds, const in
 // Bit-exactness rests on the two roles compiling the shared arithmetic alike: the builds contract floating-point expressions across
 // statements (-ffp-contract=fast), and the window's product meets pass 1's first add as one fma in both -- a change to either role, or to
 // the compiler, may fuse differently.  sgz_stage_nyquist and tests/test_gpu_image_only_split.py compare the ny words of both launch forms.
-template <int LR1>
+// s_setprio takes an immediate: a workgroup-uniform run-time priority (RealParams::prio*; 0: left alone) costs one scalar branch where it
+// is 0 and two more where it is not
+[[maybe_unused]] __device__ __forceinline__ void setWavePriority(const uint32_t p)
+{
+    if (p != 0u) { if (p == 1u) __builtin_amdgcn_s_setprio(1); else if (p == 2u) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
+}
+
+template <int LR1, bool PRIO>
 __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, const uint32_t light, const int tid)
 {
     constexpr int LR = 5, R = 32, R1 = 1 << LR1, RR = R * R;
     static_assert(LR1 == 4, "the Nyquist workgroups mirror the two-columns-per-thread form (N = 32768)");
     [[maybe_unused]] const long unit = 2 * long(light) + 1;                      // (debug stamps)
     RTRACE(0);
+#ifdef SGZ_IMAGE_PRIO
+    if constexpr (PRIO) setWavePriority(prm.prioNy);                             // (one-round shape, stftRealKernel below)
+#endif
 #ifdef SGZ_SCHED_SWEEP
     // one-round shape (stftRealKernel, below), measured and dropped: the role starts late, so that the channel workgroups' first burst of
     // requests has HBM and the CUs' fetch paths to itself; a fixed, bounded sleep -- nobody is waited for
@@ -251,7 +261,10 @@ __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, c
 // csf[N/2] = X[N/2] / 2 (:547-552; the latter stays signed: the reference leaves it complex, and X[N/2] of a real signal is real).
 // MIX: 0 Separate (two channel workgroups), 1 mono Left / Right, 2 MidSide (two workgroups on mid and side), 3 mono Merge / Side,
 // 4 Separate for an image-only render (side 0's channel workgroups, then the Nyquist workgroups: nyquistUnit above)
-template <int LR1, bool WCOS, int MIX = 0>
+// PRIO (MIX = 4): the instantiation that carries the one-round shape's wave priorities (RealParams::prio*), launched only where runStft
+// hands some out.  Every other image-only launch runs the plain one, whose code is what it was without them: the two scalar branches
+// alone changed the compiler's schedule (122 registers for 128) and cost 0.2 ... 0.3 us per launch where no priority was set.
+template <int LR1, bool WCOS, int MIX = 0, bool PRIO = false>
 __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealParams launchPrm)
 {
     constexpr int LR = 5, R = 32, R1 = 1 << LR1, T = R1 * R, RR = R * R, M = R1 * RR, N = 2 * M, U = R / R1;
@@ -277,13 +290,17 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     const uint32_t heavyUnits = SIDE0 ? uint32_t(launchPrm.frames) * launchPrm.C : gridDim.x;
     if constexpr (SIDE0) {
         // (thread index opaque: nothing the role derives from it is shared with -- hoisted into -- the channel workgroups' code)
-        if (blockIdx.x >= heavyUnits) { nyquistUnit<LR1>(launchPrm, lds, blockIdx.x - heavyUnits, opaque(tid0)); return; }
+        if (blockIdx.x >= heavyUnits) { nyquistUnit<LR1, PRIO>(launchPrm, lds, blockIdx.x - heavyUnits, opaque(tid0)); return; }
     }
     const uint32_t totalUnits = WALK ? uint32_t(launchPrm.frames) * launchPrm.C * 2u : heavyUnits;
     uint32_t walkIndex = blockIdx.x;
     // (frame, pair, channel) or (frame, pair); real_common.hpp.  SIDE0: the (frame, pair) order of the mono modes, side 0, the same `self`
     UnitId uid = unitOfIndex<MONO || SIDE0>(launchPrm, walkIndex, totalUnits, SIDE0 && launchPrm.mateAdjacent != 0u);
     [[maybe_unused]] bool firstUnit = true;
+    // one-round shape (below): this workgroup's priority behind its first requests / behind pass 1's butterflies, and whether it ends with
+    // the recombination; 0: left alone.  (Settled here, in scalar registers: a parameter fetched where it is used is a scalar-cache round
+    // trip that all eight waves wait for in the middle of the transform.)
+    [[maybe_unused]] uint32_t prioEarly = 0u, prioLate = 0u, prioEnds = 0u;
     // ---- How a launch starts, by its shape.  A CU holds two of these workgroups, so a launch has `roundSize` = 2 #CUs slots per dispatch
     // generation, and workgroups b and b + #CUs share a CU (tools/unit_trace.py, tools/unit_trace_image.py).  Every rule below is a speed
     // assumption only and stands aside in a launch that shares the chip (sgz_render_queue, RealParams::pipelined: the delay and the
@@ -306,9 +323,20 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     //     each other and through one L1, for windows that now share twelve of sixteen rows instead of none (they were 32 frames apart).
     //     cfg2: K_A 19.88 -> 19.21 us under rocprofv3 with the input from HBM (20.6 -> 19.6 us with its 2.8 KB copy on the sweep's box),
     //     +-0 ... -0.1 us with the input cache-resident.
+    //   * THE MATE RUNS AT PRIORITY 1 THROUGH THE VALU-BOUND PASSES (RealParams::prioMate / prioScope, kernels.hpp SGZ_PRIO_*; runStft hands
+    //     them out only while the Nyquist workgroups are no longer than three frames and the grid is one generation).  Left alone, the
+    //     first-on-CU workgroup of a doubled CU wins its SIMDs' arbitration and ends 4.4 us ahead of its mate, which then finishes on a
+    //     half-empty CU and ends the launch.  With the mate favoured from behind pass 1's butterflies to the end of the recombination --
+    //     and NOT while either fetches, stores its magnitudes or maps -- the two end 0.6 us apart (profiles/r08a traces) and the doubled
+    //     CU's last workgroup ends 0.9 us earlier; the launch then ends on a channel + Nyquist CU and keeps about half of that.  cfg2
+    //     against the parent, 8 alternating rounds: step -0.49 us from HBM, -0.50 us with the input cache-resident, faster in every
+    //     round.  Nobody sleeps; which of 1 .. 3 the priority is makes no difference.  (The PRIO instantiation of this kernel.)
     //   Measured and dropped (NOTES.md; -DSGZ_SCHED_SWEEP builds keep them for tools/image_sched_sweep.py): a late start of the Nyquist
     //   workgroups (0 .. 8 k clocks: +-0.1 us) and of the second channel workgroup of a CU (1 .. 2 k: +-0.1 us; 4 k: +0.7 us, 6 k: +1.3 us with
-    //   the input cache-resident; the 10 k of the long-launch rule is half a workgroup's life here).
+    //   the input cache-resident; the 10 k of the long-launch rule is half a workgroup's life here).  Round 8, with the priorities: a
+    //   mate delay of 1 .. 2 k on top of them +-0.05 us; the FIRST workgroup favoured +-0 (whole life) or +0.2 us (passes only); the mate
+    //   favoured for its whole life +0.85 us, from pass 1 on for the rest of its life +0.07 us, from its requests to the recombination
+    //   -0.35 us (the passes alone: -0.55); the Nyquist role at priority 3: +2.1 us.
     if constexpr (LR1 == 4) {
         const uint32_t cus = launchPrm.roundSize >> 1;
         // The two workgroups that share a CU from the first clock of a launch (b and b + #CUs) would run IN PHASE -- both fetching, both in
@@ -336,6 +364,25 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
             const uint32_t generation = blockIdx.x / cus;
             if (generation == 0u) __builtin_amdgcn_s_setprio(2); else if (generation == 1u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(3);
         }
+#ifdef SGZ_IMAGE_PRIO
+        // one-round shape: the two channel workgroups of a doubled CU (b < #CUs with a mate b + #CUs, and that mate)
+        if constexpr (PRIO) {
+#ifdef SGZ_SCHED_SWEEP
+            const uint32_t rolePrio = blockIdx.x >= cus ? launchPrm.prioMate : blockIdx.x + cus < heavyUnits ? launchPrm.prioFirst : 0u;
+            const uint32_t scope = launchPrm.prioScope;                 // (kernels.hpp: bit 0 -- ends with the recombination; 1, 2 -- starts late)
+#else
+            // the build's defaults or nothing (runStft): compile-time values, so that a site that takes none of them is no code at all
+            // and the others are one scalar branch around one s_setprio
+            const uint32_t rolePrio = blockIdx.x >= cus ? (launchPrm.prioMate ? uint32_t(SGZ_PRIO_MATE) : 0u)
+                                                        : blockIdx.x + cus < heavyUnits ? (launchPrm.prioFirst ? uint32_t(SGZ_PRIO_FIRST) : 0u) : 0u;
+            constexpr uint32_t scope = SGZ_PRIO_SCOPE;
+#endif
+            prioEarly = (scope == 0u || scope == 3u) ? rolePrio : 0u;
+            prioLate = (scope == 1u || scope == 2u) ? rolePrio : 0u;
+            prioEnds = (scope & 1u) ? rolePrio : 0u;
+            prioEarly = __builtin_amdgcn_readfirstlane(prioEarly); prioLate = __builtin_amdgcn_readfirstlane(prioLate); prioEnds = __builtin_amdgcn_readfirstlane(prioEnds);
+        }
+#endif
     }
     constexpr bool PAIRED = U == 2;                          // thread -> columns 2 tid, 2 tid + 1 (otherwise tid + T u): see the sample loads
     constexpr int COLSTEP = PAIRED ? 1 : T, COLLANE = PAIRED ? 2 : 1;     // column of (tid, u) = COLLANE tid + COLSTEP u
@@ -456,6 +503,10 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
             requestTables(tid);
         }
         if constexpr (FRONT) __builtin_amdgcn_sched_barrier(0);
+#ifdef SGZ_IMAGE_PRIO
+        // BEHIND the requests: the first requests of both mates go out as they always did
+        if constexpr (PRIO) setWavePriority(prioEarly);
+#endif
         if (mixed) {
             // (l +- r) w 0.5 (prepareTransform, TransformDSP.inl:92-135): the right channel comes in batches of 8 pairs on top of the left
             const float *Y = X + prm.chStride;
@@ -529,6 +580,12 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     RCLK(13);
     // -------------------------------------------------------------------------- pass 1: radix R1 per column, times W_M^{c q1}
     pass1Columns<R, R1, U, LR1>(c);
+#ifdef SGZ_IMAGE_PRIO
+    // scopes 1 and 2 start HERE, behind pass 1's butterflies.  In front of pass 1 -- a block boundary between the window and the butterflies,
+    // where all 128 registers are live -- the branch made the kernel spill 42 registers; in front of exchange 1 it keeps a fifth of the gain,
+    // behind exchange 1 all of it with three times the spread (profiles/r08a/ab5_sites.txt).
+    if constexpr (PRIO) setWavePriority(prioLate);
+#endif
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         constexpr int NB = R1 / 4 - 1;
@@ -814,6 +871,9 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
         for (int m3 = 0; m3 < R / 2; ++m3) c[m3 < 8 ? m3 : m3 + 8] = nextRows[m3];
     }
     RCLK(6);
+#ifdef SGZ_IMAGE_PRIO
+    if constexpr (PRIO) { if (prioEnds != 0u) __builtin_amdgcn_s_setprio(0); }
+#endif
     // csf[N/2 - 1] *= 0.5 (quirk Q3, TransformDSP.inl:864): the left channel's bin M - 1 = the mirror of bin 1
     if (!MONO && side == 0 && q1 == 1 && ix == 0) magB[0] *= 0.5f;
     if constexpr (WALK) mapper.arrived(); else if constexpr (!EARLYTAB) mapper.prefetch(tb, tid);
@@ -982,7 +1042,7 @@ hipError_t launchStftReal(const RealParams &prm, uint32_t N, hipStream_t stream)
     const uint32_t maxSlots = std::max(prm.chunkSlots[0], prm.chunkSlots[1]);
     // magnitudes, then the map's tile / chunk maxima (the same floats hold column 0's scratch during the recombination), then (mono) the complex entries
     const size_t ldsBytes = (size_t(realXFloats(int(M))) + realExtraFloats(maxSlots, T, N >= 32768) + 64 + (mono ? 2 * kSpecBins : 0)) * 4;
-    static size_t granted[28][64] = {};
+    static size_t granted[29][64] = {};
     const bool wcos = prm.winPhase != nullptr;
     if (prm.binsIn) {
         if (mono) return hipErrorNotSupported;
@@ -1031,6 +1091,10 @@ hipError_t launchStftReal(const RealParams &prm, uint32_t N, hipStream_t stream)
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
+#ifdef SGZ_IMAGE_PRIO
+    if (side0 && (prm.prioFirst | prm.prioMate | prm.prioNy)) e = go(&stftRealKernel<4, true, 4, true>, 28, 512, 80 * 1024);
+    else
+#endif
     if (side0) e = go(&stftRealKernel<4, true, 4>, 27, 512, 80 * 1024);
     else if (N == 32768) e = wcos ? go(&stftRealKernel<4, true>, 0, 512, 80 * 1024) : go(&stftRealKernel<4, false>, 1, 512, 80 * 1024);
     else if (N == 16384) e = wcos ? go(&stftRealKernel<3, true>, 4, 256, 40 * 1024) : go(&stftRealKernel<3, false>, 5, 256, 40 * 1024);

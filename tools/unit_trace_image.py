@@ -2,8 +2,9 @@
 and its index in the launch, by class -- first channel workgroup on its CU, second channel workgroup on its CU (a "mate": index >= #CUs),
 Nyquist workgroup -- and per class of CU (two channel workgroups / channel + Nyquist / one channel workgroup alone).  The input rotates
 over copies of the audio past the Infinity Cache, as bench.py's does.
-usage: SGZ_LIB=tools/ab/lib_dbg.so unit_trace_image.py [frames] [nyDelay mateDelay mateAdjacent] [name]
-       (delays in steps of ~1 k clocks, -1: the build's default; name: <name>.npy / <name>.txt under $SGZ_OUT, default the working directory)"""
+usage: SGZ_LIB=tools/ab/lib_dbg.so unit_trace_image.py [frames] [nyDelay mateDelay mateAdjacent] [name] [prioFirst prioMate prioNy prioScope]
+       (delays in steps of ~1 k clocks, priorities 0 .. 3 and their scope as in kernels.hpp, -1: the build's default; name: <name>.npy /
+       <name>.txt under $SGZ_OUT, default the working directory)"""
 import ctypes as C
 import os
 import sys
@@ -16,6 +17,7 @@ from signalizer_amd import api, config, synth
 frames = int(sys.argv[1]) if len(sys.argv) > 1 else 348
 sched = [int(a) for a in sys.argv[2:5]] if len(sys.argv) > 4 else [-1, -1, -1]
 name = sys.argv[5] if len(sys.argv) > 5 else "unit_trace_image"
+prio = [int(a) for a in sys.argv[6:10]] if len(sys.argv) > 9 else [-1, -1, -1, -1]
 cfg = config.cfg2()
 S = cfg["window_size"] + cfg["hop"] * (frames - 1)
 x = torch.from_numpy(synth.gen(config.CFG2_SEED, 48000, S, 2)).cuda()
@@ -27,6 +29,7 @@ clk = torch.zeros(256 + 4 * 2 * F, dtype=torch.int64, device="cuda")
 L = api.lib()
 L.sgz_debug_set_ablate(0xffff << 16)
 L.sgz_debug_set_schedule(*sched)
+L.sgz_debug_set_priorities(*prio)
 L.sgz_debug_phase_clocks_image.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
 lines = []
 
@@ -57,7 +60,7 @@ mate = ~nyq & (index >= cus)
 first = ~nyq & ~mate
 frame = slot >> 1
 say(f"frames {F}  workgroups {len(t)} ({int(first.sum())} first-on-CU channel, {int(mate.sum())} second-on-CU channel, {int(nyq.sum())} Nyquist)  "
-    f"schedule (nyDelay, mateDelay, mateAdjacent) {sched}  distinct CUs {len(set(cuid.tolist()))}")
+    f"schedule (nyDelay, mateDelay, mateAdjacent) {sched}  priorities (first, mate, Nyquist, scope) {prio}  distinct CUs {len(set(cuid.tolist()))}")
 say(f"launch span (first start -> last end), the {len(spans)} launches: median {np.median(spans):.2f} min {min(spans):.2f} max {max(spans):.2f} us; below: the last one, {end.max():.2f} us")
 for label, m in (("first-on-CU channel", first), ("second-on-CU channel", mate), ("Nyquist", nyq)):
     if m.any():
@@ -73,13 +76,23 @@ for c in set(cuid.tolist()):
     on = np.where(cuid == c)[0]
     k = (int((first | mate)[on].sum()), int(nyq[on].sum()))
     kinds.setdefault(k, []).append(end[on].max())
+    if last in on:
+        last_kind = k
     chans = on[~nyq[on]]
     if len(chans) == 2 and {int(index[chans[0]]) + cus, int(index[chans[0]]) - cus} & {int(index[chans[1]])}:
         shared_cu += 1
 for k in sorted(kinds):
     e = np.array(kinds[k])
     say(f"CUs with {k[0]} channel + {k[1]} Nyquist workgroups: {len(e):3d}  last end on the CU: {e.min():5.2f} .. median {np.median(e):5.2f} .. {e.max():5.2f} us")
+say(f"the launch's last workgroup runs on a CU with {last_kind[0]} channel + {last_kind[1]} Nyquist workgroups")
 say(f"CUs whose two channel workgroups are b and b + {cus}: {shared_cu}")
+doubled = [c for c in set(cuid.tolist()) if int((first | mate)[cuid == c].sum()) == 2]
+if doubled:
+    ef = np.array([end[(cuid == c) & first].max() for c in doubled if ((cuid == c) & first).any() and ((cuid == c) & mate).any()])
+    em = np.array([end[(cuid == c) & mate].max() for c in doubled if ((cuid == c) & first).any() and ((cuid == c) & mate).any()])
+    if len(ef):
+        say(f"doubled CUs: first-on-CU workgroup ends {ef.min():5.2f} .. median {np.median(ef):5.2f} .. {ef.max():5.2f}, its mate {em.min():5.2f} .. median {np.median(em):5.2f} .. {em.max():5.2f}; "
+            f"mate end - first end: {(em - ef).min():5.2f} .. median {np.median(em - ef):5.2f} .. {(em - ef).max():5.2f} us")
 pairs = [(int(frame[a]), int(frame[b])) for a in np.where(first)[0] for b in np.where(mate & (cuid == cuid[a]))[0]]
 if pairs:
     gap = np.array([abs(p - q) for p, q in pairs])
