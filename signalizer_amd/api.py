@@ -448,11 +448,6 @@ def lib() -> C.CDLL:
     L.sgz_stage_wave_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
     L.sgz_wave_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.sgz_wave_columns_limits.restype = None
-    L.sgz_pcm_stream_set_waveform.argtypes = [vp, u32, vp, u64]
-    L.sgz_pcm_stream_waveform_for.argtypes = [vp, sz, C.c_int]
-    L.sgz_pcm_stream_waveform_for.restype = u64
-    L.sgz_pcm_stream_waveform_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
-    L.sgz_pcm_stream_flush_waveform.argtypes = [vp]
     L.sgz_track_peak_values.argtypes = [vp, vp, C.c_double, C.POINTER(LinePeak)]
     L.sgz_stage_track_peaks_values.argtypes = [vp, vp, sz, C.c_double, vp, vp]
     L.sgz_pcm_stream_set_track.argtypes = [vp, u32, C.c_double, vp, u64]
@@ -463,11 +458,6 @@ def lib() -> C.CDLL:
     L.sgz_stage_level_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
     L.sgz_level_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.sgz_level_columns_limits.restype = None
-    L.sgz_pcm_stream_set_level.argtypes = [vp, u32, vp, u64]
-    L.sgz_pcm_stream_level_for.argtypes = [vp, sz, C.c_int]
-    L.sgz_pcm_stream_level_for.restype = u64
-    L.sgz_pcm_stream_level_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
-    L.sgz_pcm_stream_flush_level.argtypes = [vp]
     L.sgz_level_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_level_readout.argtypes = [vp, C.POINTER(LevelReading)]
     L.sgz_stage_truepeak_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, u32, vp, vp, vp]
@@ -477,11 +467,6 @@ def lib() -> C.CDLL:
     L.sgz_truepeak_taps.restype = None
     L.sgz_truepeak_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_truepeak_readout.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.sgz_pcm_stream_set_truepeak.argtypes = [vp, u32, vp, u64]
-    L.sgz_pcm_stream_truepeak_for.argtypes = [vp, sz, C.c_int]
-    L.sgz_pcm_stream_truepeak_for.restype = u64
-    L.sgz_pcm_stream_truepeak_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
-    L.sgz_pcm_stream_flush_truepeak.argtypes = [vp]
     fp = C.POINTER(LoudnessFilter)
     L.sgz_stage_loudness_columns.argtypes = [vp, sz, u32, sz, fp, u64, u32, u32, C.c_int, u32, u32, vp, vp, vp]
     L.sgz_loudness_columns_limits.argtypes = [fp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(sz)]
@@ -490,11 +475,12 @@ def lib() -> C.CDLL:
     L.sgz_loudness_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_loudness_readout.argtypes = [vp, sz, u32, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgz_loudness_integrated.argtypes = [vp, sz, u32, vp, C.POINTER(C.c_double)]
-    L.sgz_pcm_stream_set_loudness.argtypes = [vp, fp, u32, vp, u64]
-    L.sgz_pcm_stream_loudness_for.argtypes = [vp, sz, C.c_int]
-    L.sgz_pcm_stream_loudness_for.restype = u64
-    L.sgz_pcm_stream_loudness_state.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
-    L.sgz_pcm_stream_flush_loudness.argtypes = [vp]
+    for lane in ("waveform", "level", "truepeak", "loudness"):         # the four column lanes of the PCM stream: one set of calls each
+        getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, fp, u32, vp, u64] if lane == "loudness" else [vp, u32, vp, u64]
+        getattr(L, f"sgz_pcm_stream_{lane}_for").argtypes = [vp, sz, C.c_int]
+        getattr(L, f"sgz_pcm_stream_{lane}_for").restype = u64
+        getattr(L, f"sgz_pcm_stream_{lane}_state").argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        getattr(L, f"sgz_pcm_stream_flush_{lane}").argtypes = [vp]
     _lib = L
     return L
 
@@ -1252,102 +1238,96 @@ class PcmStream:
         return (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
 
 
+    # the four column lanes (waveform, level, truepeak, loudness): one helper per kind of call, the lane's name picks the C call
+    def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
+        if capacity_columns is None:
+            capacity_columns = 0 if out is None else int(out.shape[0])
+        check(getattr(lib(), f"sgz_pcm_stream_set_{lane}")(self.h, *front, m, _buf_ptr(out) if out is not None and m else None,
+                                                           capacity_columns if m else 0))
+        setattr(self, f"_{lane}_out", out if m else None)                # (kept alive here: the stream writes to it)
+
+    def _lane_for(self, lane: str, nsamples: int, flush: bool) -> int:
+        return int(getattr(lib(), f"sgz_pcm_stream_{lane}_for")(self.h, nsamples, int(bool(flush))))
+
+    def _lane_state(self, lane: str):
+        c, o = C.c_uint64(0), C.c_uint64(0)
+        check(getattr(lib(), f"sgz_pcm_stream_{lane}_state")(self.h, C.byref(c), C.byref(o)))
+        return int(c.value), int(o.value)
+
+    def _lane_flush(self, lane: str) -> None:
+        check(getattr(lib(), f"sgz_pcm_stream_flush_{lane}")(self.h))
+
     # the waveform lane: (lo, hi) per column of m samples and channel, beside whatever the feeds render
     def set_waveform(self, m: int, out=None, capacity_columns: int | None = None) -> None:
         """sgz_pcm_stream_set_waveform: out -- a float32 numpy array or host torch tensor [capacity, channels, 2] (kept alive here; pinned
         memory is written in place); m == 0 disarms"""
-        if capacity_columns is None:
-            capacity_columns = 0 if out is None else int(out.shape[0])
-        check(lib().sgz_pcm_stream_set_waveform(self.h, m, _buf_ptr(out) if out is not None and m else None, capacity_columns if m else 0))
-        self._wave_out = out if m else None
+        self._lane_set("waveform", m, out, capacity_columns)
 
     def waveform_for(self, nsamples: int, flush: bool = False) -> int:
         """sgz_pcm_stream_waveform_for: waveform columns the next feed of nsamples closes"""
-        return int(lib().sgz_pcm_stream_waveform_for(self.h, nsamples, int(bool(flush))))
+        return self._lane_for("waveform", nsamples, flush)
 
     def waveform_state(self):
         """sgz_pcm_stream_waveform_state: (columns written since the lane was armed, samples of the open column)"""
-        c, o = C.c_uint64(0), C.c_uint64(0)
-        check(lib().sgz_pcm_stream_waveform_state(self.h, C.byref(c), C.byref(o)))
-        return int(c.value), int(o.value)
+        return self._lane_state("waveform")
 
     def flush_waveform(self) -> None:
         """sgz_pcm_stream_flush_waveform: closes the open column (one more column at the cursor); waits"""
-        check(lib().sgz_pcm_stream_flush_waveform(self.h))
-
+        self._lane_flush("waveform")
 
     # the level lane: one sgz_level_record per column of m samples and pair, beside whatever the feeds render
     def set_level(self, m: int, out=None, capacity_columns: int | None = None) -> None:
         """sgz_pcm_stream_set_level: out -- a LEVEL_DTYPE numpy array [capacity, pairs] or a host torch uint8 tensor [capacity, pairs, 80] (kept
         alive here; pinned memory is written in place); m == 0 disarms"""
-        if capacity_columns is None:
-            capacity_columns = 0 if out is None else int(out.shape[0])
-        check(lib().sgz_pcm_stream_set_level(self.h, m, _buf_ptr(out) if out is not None and m else None, capacity_columns if m else 0))
-        self._level_out = out if m else None
+        self._lane_set("level", m, out, capacity_columns)
 
     def level_for(self, nsamples: int, flush: bool = False) -> int:
         """sgz_pcm_stream_level_for: level columns the next feed of nsamples closes"""
-        return int(lib().sgz_pcm_stream_level_for(self.h, nsamples, int(bool(flush))))
+        return self._lane_for("level", nsamples, flush)
 
     def level_state(self):
         """sgz_pcm_stream_level_state: (columns written since the lane was armed, samples of the open column)"""
-        c, o = C.c_uint64(0), C.c_uint64(0)
-        check(lib().sgz_pcm_stream_level_state(self.h, C.byref(c), C.byref(o)))
-        return int(c.value), int(o.value)
+        return self._lane_state("level")
 
     def flush_level(self) -> None:
         """sgz_pcm_stream_flush_level: closes the open column (one more record per pair at the cursor); waits"""
-        check(lib().sgz_pcm_stream_flush_level(self.h))
-
+        self._lane_flush("level")
 
     # the true-peak lane: one sgz_truepeak_record per column of m samples and channel, beside whatever the feeds render
     def set_truepeak(self, m: int, out=None, capacity_columns: int | None = None) -> None:
         """sgz_pcm_stream_set_truepeak: out -- a TRUEPEAK_DTYPE numpy array [capacity, channels] or a host torch uint8 tensor [capacity, channels,
         16] (kept alive here; pinned memory is written in place); m == 0 disarms"""
-        if capacity_columns is None:
-            capacity_columns = 0 if out is None else int(out.shape[0])
-        check(lib().sgz_pcm_stream_set_truepeak(self.h, m, _buf_ptr(out) if out is not None and m else None, capacity_columns if m else 0))
-        self._truepeak_out = out if m else None
+        self._lane_set("truepeak", m, out, capacity_columns)
 
     def truepeak_for(self, nsamples: int, flush: bool = False) -> int:
         """sgz_pcm_stream_truepeak_for: true-peak columns the next feed of nsamples closes"""
-        return int(lib().sgz_pcm_stream_truepeak_for(self.h, nsamples, int(bool(flush))))
+        return self._lane_for("truepeak", nsamples, flush)
 
     def truepeak_state(self):
         """sgz_pcm_stream_truepeak_state: (columns written since the lane was armed, samples of the open column)"""
-        c, o = C.c_uint64(0), C.c_uint64(0)
-        check(lib().sgz_pcm_stream_truepeak_state(self.h, C.byref(c), C.byref(o)))
-        return int(c.value), int(o.value)
+        return self._lane_state("truepeak")
 
     def flush_truepeak(self) -> None:
         """sgz_pcm_stream_flush_truepeak: closes the open column (one more record per channel at the cursor); waits"""
-        check(lib().sgz_pcm_stream_flush_truepeak(self.h))
-
+        self._lane_flush("truepeak")
 
     # the loudness lane: one sgz_loudness_record per column of m samples and channel, beside whatever the feeds render
     def set_loudness(self, filter, m: int, out=None, capacity_columns: int | None = None) -> None:
         """sgz_pcm_stream_set_loudness: filter -- a LoudnessFilter (None allowed with m == 0); out -- a LOUDNESS_DTYPE numpy array [capacity,
         channels] or a host torch uint8 tensor [capacity, channels, 32] (kept alive here; pinned memory is written in place); m == 0 disarms"""
-        if capacity_columns is None:
-            capacity_columns = 0 if out is None else int(out.shape[0])
-        check(lib().sgz_pcm_stream_set_loudness(self.h, C.byref(filter) if filter is not None else None, m,
-                                                _buf_ptr(out) if out is not None and m else None, capacity_columns if m else 0))
-        self._loudness_out = out if m else None
+        self._lane_set("loudness", m, out, capacity_columns, C.byref(filter) if filter is not None else None)
 
     def loudness_for(self, nsamples: int, flush: bool = False) -> int:
         """sgz_pcm_stream_loudness_for: loudness columns the next feed of nsamples closes"""
-        return int(lib().sgz_pcm_stream_loudness_for(self.h, nsamples, int(bool(flush))))
+        return self._lane_for("loudness", nsamples, flush)
 
     def loudness_state(self):
         """sgz_pcm_stream_loudness_state: (columns written since the lane was armed, samples of the open column)"""
-        c, o = C.c_uint64(0), C.c_uint64(0)
-        check(lib().sgz_pcm_stream_loudness_state(self.h, C.byref(c), C.byref(o)))
-        return int(c.value), int(o.value)
+        return self._lane_state("loudness")
 
     def flush_loudness(self) -> None:
         """sgz_pcm_stream_flush_loudness: closes the open column (one more record per channel at the cursor); waits"""
-        check(lib().sgz_pcm_stream_flush_loudness(self.h))
-
+        self._lane_flush("loudness")
 
     # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
     def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:

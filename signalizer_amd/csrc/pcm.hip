@@ -1,11 +1,12 @@
 // pcm.hip -- interleaved PCM in (include/sgz.h "interleaved PCM in"): the convert-and-de-interleave kernel, and the stream handle that
 // cuts a feed into pieces and runs upload / convert + render / read-back of neighbouring pieces side by side on three streams.  Both kinds
 // of feed (frames, overview columns) go through ONE piece loop, pcmPieces, and differ in the Part they hand it: what to render from a piece
-// and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, waveform columns, track records --
-// is a PcmOut: device block, pinned twin, pending host copy.  Armed, the waveform lane (wave_columns.hip) and the level lane
-// (level_columns.hip) reduce every piece's new samples behind the converter and the track lane (tracker.hip) searches every piece's line
-// results behind its render; the true-peak lane (truepeak_columns.hip) filters every piece's new samples behind them, and the loudness lane
-// (loudness_columns.hip) behind that one.  All ride the same read-back.
+// and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, a lane's columns or records --
+// is a PcmOut: device block, pinned twin, pending host copy.  Every lane is a PcmSink: the caller's buffer, the cursor in it, and the PcmOut its
+// units pass through; the track lane (tracker.hip), which searches every piece's line results behind its render, is a sink of frames, and the
+// four column lanes -- waveform, level, true-peak, loudness (wave_columns.hip, level_columns.hip, truepeak_columns.hip, loudness_columns.hip),
+// which reduce every piece's new samples behind the converter in that order -- are ONE PcmLane type, a sink of columns with the open column's
+// carry, and differ in a hook that makes the one call of their reduction.  The feed walks the lanes; all ride the same read-back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -182,6 +183,9 @@ static sgz_status streamStep(uint32_t W, uint32_t hop, uint64_t held, uint64_t i
 using namespace sgz;
 
 // ---- the stream handle -----------------------------------------------------------------------------------------------------------------
+struct sgz_pcm_stream;
+struct PcmLane;
+
 namespace {
 // The default piece: 2^20 samples, less where a slot of that many frames would pass 256 MiB (64-channel F64: 2^19).  A kept stream fed cfg2's
 // 60 s of stereo S16 (tools/bench_pcm_render.py): 5.1 / 2.5 / 1.4 / 0.93 / 0.67 / 0.65 / 0.66 ms at 2^16 .. 2^22 -- a piece costs the host
@@ -242,7 +246,60 @@ struct PcmSlot {                        // what one piece in flight owns; a slot
     bool timed = false;
     bool busy = false, rendered = false;            // rendered: the piece has a read-back (any output at all), ev[6] is recorded
 };
+
+// What every lane has: the caller's buffer and the cursor in it, in units -- columns, or frames for the track lane -- of `unit` bytes, and the
+// PcmOut of a slot that a piece's units pass through.  most: the most units one piece yields, which is what a slot's block holds; 0: off
+struct PcmSink {
+    PcmOutKind kind = kPcmOuts;
+    size_t unit = 0;
+    uint64_t most = 0;
+    uint8_t *out = nullptr;
+    uint64_t cap = 0, cursor = 0;
+    bool pinned = false;
+
+    void arm(uint64_t mostUnits, void *to, uint64_t capacity)
+    {
+        most = mostUnits; out = static_cast<uint8_t *>(to); cap = capacity; cursor = 0;
+        pinned = capacity && isPinnedHost(to);
+    }
+    void disarm() { most = 0; out = nullptr; cap = cursor = 0; }
+    bool armed() const { return most != 0; }
+    // what a feed checks before anything is consumed: the n units it yields fit behind the cursor
+    bool fits(uint64_t n) const { return !armed() || n <= cap - cursor; }
+    // the slot's block of `most` units (both slots are idle between feeds)
+    sgz_status reserve(PcmSlot &sl) const { return most ? sl.out[kind].reserve(size_t(most) * unit, !pinned) : SGZ_OK; }
+    // the first n units of the slot's block to the caller's buffer at the cursor, on `stream`
+    sgz_status readBack(PcmSlot &sl, uint64_t n, hipStream_t stream)
+    {
+        if (!n) return SGZ_OK;
+        const sgz_status st = sl.out[kind].readBack(out + size_t(cursor) * unit, size_t(n) * unit, pinned, stream);
+        if (st == SGZ_OK) cursor += n;
+        return st;
+    }
+};
+
+// The sinks in the order a feed refuses them; the four column lanes come first and are the stream's lane[] in this order
+enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
+constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness};
+constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness};
+
+// A lane's hook: the one call of its reduction, run<Lane>Columns, on the compute stream.  (n samples at `in`, flush 0) is a piece's step: the
+// columns they close go to d_out, the open one to the other half of the carry; (0 samples, flush 1) is the flush's emit launch, which leaves the
+// carry where it is.  The hook keeps what is the lane's own: the carry's layout, its scratch, and whether a step moves to the other half
+using PcmLaneRun = sgz_status (*)(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed);
 }  // namespace
+
+// A column lane (m > 0: armed): a sink of columns of m samples.  open: the open column's sample count; its state is in half `cur` of d_carry
+// [2][...] -- a step reads that half and writes the other, so no launch reads what it writes
+struct PcmLane {
+    PcmSink sink;
+    const char *word = "", *call = "";                  // for messages: "true-peak", and the calls' suffix, "truepeak"
+    PcmLaneRun run = nullptr;
+    uint32_t m = 0;
+    uint64_t open = 0;
+    int cur = 0;
+    void *d_carry = nullptr;
+};
 
 struct sgz_pcm_stream {
     sgz_spectrum_config cfg{};
@@ -259,50 +316,25 @@ struct sgz_pcm_stream {
     // the overview inside the stream: the open column's V [pairs][P], its frame count and its k (meaningful while ovOpen > 0)
     float *d_ovCarry = nullptr;
     uint64_t ovOpen = 0; uint32_t ovK = 0;
-    // the waveform lane (m > 0: armed): the caller's columns and the cursor in them, the open column's sample count and its (lo, hi) per channel
-    // in d_wvCarry [2][channels] float2 -- a piece reads half wvCur and writes the other, so no launch reads what it writes
-    uint32_t wvM = 0;
-    float *wvOut = nullptr;
-    uint64_t wvCap = 0, wvCursor = 0, wvOpen = 0;
-    bool wvPinned = false;
-    float *d_wvCarry = nullptr;
-    int wvCur = 0;
-    // the track lane (trArmed): the graph and mouse position searched, the caller's records [trCap][pairs] and the cursor in them, in frames
-    bool trArmed = false, trPinned = false;
+    // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels])
+    // and loudness (two halves of loudnessCarryBytes(ldFilter) * channels bytes; ldCarryCap: what is allocated)
+    PcmLane lane[kPcmLanes];
+    // the track lane (track.most > 0: armed): a sink of frames, and the graph and mouse position searched
+    PcmSink track;
     uint32_t trGraph = 0;
     double trFraction = 0;
-    sgz_line_peak *trOut = nullptr;
-    uint64_t trCap = 0, trCursor = 0;
-    // the level lane (lvM > 0: armed), as the waveform lane with an m of its own: the caller's records and the cursor in them, the open column's
-    // sample count and its record per pair in d_lvCarry [2][pairs] -- a piece reads half lvCur and writes the other
-    uint32_t lvM = 0;
-    sgz_level_record *lvOut = nullptr;
-    uint64_t lvCap = 0, lvCursor = 0, lvOpen = 0;
-    bool lvPinned = false;
-    sgz_level_record *d_lvCarry = nullptr;
-    int lvCur = 0;
-    // the true-peak lane (tpM > 0: armed), as the level lane per channel; its carry d_tpCarry [2][channels] also holds the filter's history, so
-    // every piece with samples writes the other half and the halves alternate.  tpContinued: half tpCur holds the samples before the next one
-    // (false after arming or a reset: the history is zeros)
-    uint32_t tpM = 0;
-    sgz_truepeak_record *tpOut = nullptr;
-    uint64_t tpCap = 0, tpCursor = 0, tpOpen = 0;
-    bool tpPinned = false, tpContinued = false;
-    sgz_truepeak_carry *d_tpCarry = nullptr;
-    int tpCur = 0;
-    // the loudness lane (ldM > 0: armed), as the true-peak lane; its carry d_ldCarry holds two halves of loudnessCarryBytes(ldFilter) * channels
-    // bytes (ldCarryCap: what is allocated).  ldIndex: the lane's samples so far -- the absolute index of the next one, which a flush does not move
-    uint32_t ldM = 0;
+    // the true-peak and loudness carries also hold the filter's history, so every piece with samples writes the other half and the halves
+    // alternate.  Continued: half `cur` holds the samples before the next one (false after arming or a reset: the history is zeros)
+    bool tpContinued = false, ldContinued = false;
+    // ldIndex: the loudness lane's samples so far -- the absolute index of the next one, which a flush does not move
     sgz_loudness_filter ldFilter{};
-    sgz_loudness_record *ldOut = nullptr;
-    uint64_t ldCap = 0, ldCursor = 0, ldOpen = 0, ldIndex = 0;
-    bool ldPinned = false, ldContinued = false;
-    uint8_t *d_ldCarry = nullptr;
+    uint64_t ldIndex = 0;
     size_t ldCarryCap = 0;
     // the lane's scratch (q of a piece's samples, partial records), kept: every piece's launches are on the compute stream, one behind the other
     void *d_ldScratch = nullptr;
     size_t ldScratchCap = 0;
-    int ldCur = 0;
+
+    PcmSink &sink(int id) { return id < kPcmLanes ? lane[id].sink : track; }
 };
 
 struct sgz_plan { Plan impl; };
@@ -332,225 +364,156 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
     return SGZ_OK;
 }
 
-// ---- the waveform lane inside the stream (sgz.h, "The waveform lane") -----------------------------------------------------------------------
-static float *pcmWaveCarry(const sgz_pcm_stream &s, int half) { return s.d_wvCarry + size_t(half) * 2 * s.numChannels; }
-
-// what a feed checks for the lane before anything is consumed: the columns its samples close fit behind the cursor
-static sgz_status pcmWaveFits(const sgz_pcm_stream &s, size_t nsamples)
+// ---- the lanes inside the stream (sgz.h, "The waveform lane" ... "The loudness lane", "The track lane") -----------------------------------------
+// The four hooks.  The waveform and level carries hold the open column alone: a step moves to the other half only when a column stays open.
+static sgz_status pcmWaveRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
 {
-    if (s.wvM && (s.wvOpen + nsamples) / s.wvM > s.wvCap - s.wvCursor)
-        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed closes more waveform columns than the buffer has left (sgz_pcm_stream_waveform_for; re-arm with sgz_pcm_stream_set_waveform)");
-    return SGZ_OK;
-}
-
-// a slot's columns of a piece, ceil(chunk / m) + 1 of them (both slots are idle between feeds)
-static sgz_status pcmWaveBuffers(sgz_pcm_stream &s, PcmSlot &sl)
-{
-    return s.wvM ? sl.out[kOutWave].reserve(((s.chunk + s.wvM - 1) / s.wvM + 1) * s.numChannels * 2 * sizeof(float), !s.wvPinned) : SGZ_OK;
-}
-
-// the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the columns they close, into the slot;
-// the open one into the carry
-static sgz_status pcmWavePiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
-{
-    *columns = 0;
-    if (!s.wvM || n == 0) return SGZ_OK;
-    const WaveColumnsShape sh = waveColumnsShape(s.numChannels, n, s.wvM, uint32_t(s.wvOpen), 0, 0);
+    const uint32_t channels = s.numChannels, open = uint32_t(l.open);
+    const WaveColumnsShape sh = waveColumnsShape(channels, n, l.m, open, flush, 0);
     StreamScratch scratch(s.compute);
     if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    const sgz_status st = runWaveColumns(sh, fresh, s.stride, s.numChannels, n, s.wvM, uint32_t(s.wvOpen), pcmWaveCarry(s, s.wvCur), pcmWaveCarry(s, s.wvCur ^ 1),
-                                         sl.out[kOutWave].as<float>(), scratch.p, s.compute);
+    float *carry = static_cast<float *>(l.d_carry);
+    const size_t half = size_t(2) * channels;
+    const sgz_status st = runWaveColumns(sh, in, s.stride, channels, n, l.m, open, carry + l.cur * half, carry + (l.cur ^ 1) * half,
+                                         static_cast<float *>(d_out), scratch.p, s.compute);
     if (st != SGZ_OK) return st;
-    if (sh.open) s.wvCur ^= 1;
-    s.wvOpen = (s.wvOpen + n) % s.wvM;
-    *columns = sh.closed;
+    if (sh.open) l.cur ^= 1;
+    *closed = sh.closed;
     return SGZ_OK;
 }
 
-// the piece's columns to the caller's buffer at the cursor, on the read-back stream
-static sgz_status pcmWaveReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
+static sgz_status pcmLevelRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
 {
-    if (!columns) return SGZ_OK;
-    const size_t column = size_t(s.numChannels) * 2;
-    const sgz_status st = sl.out[kOutWave].readBack(s.wvOut + size_t(s.wvCursor) * column, size_t(columns) * column * sizeof(float), s.wvPinned, s.back);
-    if (st == SGZ_OK) s.wvCursor += columns;
-    return st;
-}
-
-// ---- the level lane inside the stream (sgz.h, "The level lane") ----------------------------------------------------------------------------
-static sgz_level_record *pcmLevelCarry(const sgz_pcm_stream &s, int half) { return s.d_lvCarry + size_t(half) * s.cfg.num_pairs; }
-
-// what a feed checks for the lane before anything is consumed: the columns its samples close fit behind the cursor
-static sgz_status pcmLevelFits(const sgz_pcm_stream &s, size_t nsamples)
-{
-    if (s.lvM && (s.lvOpen + nsamples) / s.lvM > s.lvCap - s.lvCursor)
-        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed closes more level columns than the buffer has left (sgz_pcm_stream_level_for; re-arm with sgz_pcm_stream_set_level)");
-    return SGZ_OK;
-}
-
-// a slot's records of a piece, ceil(chunk / m) + 1 columns of them (both slots are idle between feeds)
-static sgz_status pcmLevelBuffers(sgz_pcm_stream &s, PcmSlot &sl)
-{
-    return s.lvM ? sl.out[kOutLevel].reserve(((s.chunk + s.lvM - 1) / s.lvM + 1) * s.cfg.num_pairs * sizeof(sgz_level_record), !s.lvPinned) : SGZ_OK;
-}
-
-// the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the records they close, into the slot;
-// the open one into the carry
-static sgz_status pcmLevelPiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
-{
-    *columns = 0;
-    if (!s.lvM || n == 0) return SGZ_OK;
-    const LevelColumnsShape sh = levelColumnsShape(s.cfg.num_pairs, n, s.lvM, uint32_t(s.lvOpen), 0, 0);
+    const uint32_t pairs = s.cfg.num_pairs, open = uint32_t(l.open);
+    const LevelColumnsShape sh = levelColumnsShape(pairs, n, l.m, open, flush, 0);
     StreamScratch scratch(s.compute);
     if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    const sgz_status st = runLevelColumns(sh, fresh, s.stride, s.cfg.num_pairs, n, s.lvM, uint32_t(s.lvOpen), pcmLevelCarry(s, s.lvCur), pcmLevelCarry(s, s.lvCur ^ 1),
-                                          sl.out[kOutLevel].as<sgz_level_record>(), scratch.p, s.compute);
+    sgz_level_record *carry = static_cast<sgz_level_record *>(l.d_carry);
+    const sgz_status st = runLevelColumns(sh, in, s.stride, pairs, n, l.m, open, carry + size_t(l.cur) * pairs, carry + size_t(l.cur ^ 1) * pairs,
+                                          static_cast<sgz_level_record *>(d_out), scratch.p, s.compute);
     if (st != SGZ_OK) return st;
-    if (sh.open) s.lvCur ^= 1;
-    s.lvOpen = (s.lvOpen + n) % s.lvM;
-    *columns = sh.closed;
+    if (sh.open) l.cur ^= 1;
+    *closed = sh.closed;
     return SGZ_OK;
 }
 
-// the piece's records to the caller's buffer at the cursor, on the read-back stream
-static sgz_status pcmLevelReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
+// The true-peak and loudness carries hold the filter's history too: every step with samples moves to the other half, whether or not a column
+// stays open.  A flush emits the open column of the current half as continued and leaves the carry, and with it the history, where it is
+static sgz_status pcmTruePeakRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
 {
-    if (!columns) return SGZ_OK;
-    const size_t column = s.cfg.num_pairs;
-    const sgz_status st = sl.out[kOutLevel].readBack(s.lvOut + size_t(s.lvCursor) * column, size_t(columns) * column * sizeof(sgz_level_record), s.lvPinned, s.back);
-    if (st == SGZ_OK) s.lvCursor += columns;
-    return st;
-}
-
-// ---- the true-peak lane inside the stream (sgz.h, "The true-peak lane") --------------------------------------------------------------------
-static sgz_truepeak_carry *pcmTruePeakCarry(const sgz_pcm_stream &s, int half) { return s.d_tpCarry + size_t(half) * s.numChannels; }
-
-// what a feed checks for the lane before anything is consumed: the columns its samples close fit behind the cursor
-static sgz_status pcmTruePeakFits(const sgz_pcm_stream &s, size_t nsamples)
-{
-    if (s.tpM && (s.tpOpen + nsamples) / s.tpM > s.tpCap - s.tpCursor)
-        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed closes more true-peak columns than the buffer has left (sgz_pcm_stream_truepeak_for; re-arm with sgz_pcm_stream_set_truepeak)");
-    return SGZ_OK;
-}
-
-// a slot's records of a piece, ceil(chunk / m) + 1 columns of them (both slots are idle between feeds)
-static sgz_status pcmTruePeakBuffers(sgz_pcm_stream &s, PcmSlot &sl)
-{
-    return s.tpM ? sl.out[kOutTruePeak].reserve(((s.chunk + s.tpM - 1) / s.tpM + 1) * s.numChannels * sizeof(sgz_truepeak_record), !s.tpPinned) : SGZ_OK;
-}
-
-// the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the records they close, into the slot;
-// the open one and the new history into the other half of the carry
-static sgz_status pcmTruePeakPiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
-{
-    *columns = 0;
-    if (!s.tpM || n == 0) return SGZ_OK;
-    const TruePeakColumnsShape sh = truePeakColumnsShape(s.numChannels, n, s.tpM, uint32_t(s.tpOpen), 0, 0);
+    const uint32_t channels = s.numChannels, open = uint32_t(l.open);
+    const TruePeakColumnsShape sh = truePeakColumnsShape(channels, n, l.m, open, flush, 0);
     StreamScratch scratch(s.compute);
     if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    const sgz_status st = runTruePeakColumns(sh, fresh, s.stride, s.numChannels, n, s.tpM, uint32_t(s.tpOpen), s.tpContinued ? 1u : 0u, pcmTruePeakCarry(s, s.tpCur),
-                                             pcmTruePeakCarry(s, s.tpCur ^ 1), sl.out[kOutTruePeak].as<sgz_truepeak_record>(), scratch.p, s.compute);
+    sgz_truepeak_carry *carry = static_cast<sgz_truepeak_carry *>(l.d_carry);
+    const sgz_status st = runTruePeakColumns(sh, in, s.stride, channels, n, l.m, open, (flush || s.tpContinued) ? 1u : 0u, carry + size_t(l.cur) * channels,
+                                             carry + size_t(l.cur ^ 1) * channels, static_cast<sgz_truepeak_record *>(d_out), scratch.p, s.compute);
     if (st != SGZ_OK) return st;
-    s.tpCur ^= 1;                                                                   // (the history moved, whether or not a column stays open)
-    s.tpContinued = true;
-    s.tpOpen = (s.tpOpen + n) % s.tpM;
-    *columns = sh.closed;
+    if (!flush) { l.cur ^= 1; s.tpContinued = true; }
+    *closed = sh.closed;
     return SGZ_OK;
 }
 
-// the piece's records to the caller's buffer at the cursor, on the read-back stream
-static sgz_status pcmTruePeakReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
+static sgz_status pcmLoudnessRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
 {
-    if (!columns) return SGZ_OK;
-    const size_t column = s.numChannels;
-    const sgz_status st = sl.out[kOutTruePeak].readBack(s.tpOut + size_t(s.tpCursor) * column, size_t(columns) * column * sizeof(sgz_truepeak_record), s.tpPinned, s.back);
-    if (st == SGZ_OK) s.tpCursor += columns;
-    return st;
-}
-
-// ---- the loudness lane inside the stream (sgz.h, "The loudness lane") ------------------------------------------------------------------------
-static uint8_t *pcmLoudnessCarry(const sgz_pcm_stream &s, int half) { return s.d_ldCarry + size_t(half) * loudnessCarryBytes(s.ldFilter) * s.numChannels; }
-
-// what a feed checks for the lane before anything is consumed: the columns its samples close fit behind the cursor
-static sgz_status pcmLoudnessFits(const sgz_pcm_stream &s, size_t nsamples)
-{
-    if (s.ldM && (s.ldOpen + nsamples) / s.ldM > s.ldCap - s.ldCursor)
-        return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed closes more loudness columns than the buffer has left (sgz_pcm_stream_loudness_for; re-arm with sgz_pcm_stream_set_loudness)");
-    return SGZ_OK;
-}
-
-// a slot's records of a piece, ceil(chunk / m) + 1 columns of them (both slots are idle between feeds)
-static sgz_status pcmLoudnessBuffers(sgz_pcm_stream &s, PcmSlot &sl)
-{
-    return s.ldM ? sl.out[kOutLoudness].reserve(((s.chunk + s.ldM - 1) / s.ldM + 1) * s.numChannels * sizeof(sgz_loudness_record), !s.ldPinned) : SGZ_OK;
-}
-
-// the lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the records they close, into the slot;
-// the open one and the new history into the other half of the carry
-static sgz_status pcmLoudnessPiece(sgz_pcm_stream &s, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
-{
-    *columns = 0;
-    if (!s.ldM || n == 0) return SGZ_OK;
-    const LoudnessColumnsShape sh = loudnessColumnsShape(s.numChannels, n, s.ldM, uint32_t(s.ldOpen), 0, 0);
+    const uint32_t channels = s.numChannels, open = uint32_t(l.open);
+    const LoudnessColumnsShape sh = loudnessColumnsShape(channels, n, l.m, open, flush, 0);
     if (sh.scratchBytes > s.ldScratchCap) {                                         // (the first piece of a feed is its largest: this happens once)
         SGZ_HIP(hipStreamSynchronize(s.compute));
         if (s.d_ldScratch) { (void)hipFree(s.d_ldScratch); s.d_ldScratch = nullptr; s.ldScratchCap = 0; }
         SGZ_HIP(hipMalloc(&s.d_ldScratch, sh.scratchBytes));
         s.ldScratchCap = sh.scratchBytes;
     }
-    const sgz_status st = runLoudnessColumns(sh, s.ldFilter, fresh, s.stride, s.numChannels, n, s.ldIndex, s.ldM, uint32_t(s.ldOpen), s.ldContinued ? 1u : 0u,
-                                             pcmLoudnessCarry(s, s.ldCur), pcmLoudnessCarry(s, s.ldCur ^ 1), sl.out[kOutLoudness].as<sgz_loudness_record>(),
-                                             s.d_ldScratch, s.compute);
+    uint8_t *carry = static_cast<uint8_t *>(l.d_carry);
+    const size_t half = loudnessCarryBytes(s.ldFilter) * channels;
+    const sgz_status st = runLoudnessColumns(sh, s.ldFilter, in, s.stride, channels, n, s.ldIndex, l.m, open, (flush || s.ldContinued) ? 1u : 0u,
+                                             carry + l.cur * half, carry + (l.cur ^ 1) * half, static_cast<sgz_loudness_record *>(d_out),
+                                             flush ? nullptr : s.d_ldScratch, s.compute);
     if (st != SGZ_OK) return st;
-    s.ldCur ^= 1;                                                                   // (the history moved, whether or not a column stays open)
-    s.ldContinued = true;
-    s.ldOpen = (s.ldOpen + n) % s.ldM;
-    s.ldIndex += n;
-    *columns = sh.closed;
+    if (!flush) { l.cur ^= 1; s.ldContinued = true; s.ldIndex += n; }
+    *closed = sh.closed;
     return SGZ_OK;
 }
 
-// the piece's records to the caller's buffer at the cursor, on the read-back stream
-static sgz_status pcmLoudnessReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t columns)
+// what both feeds refuse for the lanes before anything is consumed, in the sinks' order: the columns the samples close and the frames they
+// complete fit behind every armed lane's cursor
+static sgz_status pcmLanesFit(const sgz_pcm_stream &s, size_t nsamples, uint64_t frames)
 {
-    if (!columns) return SGZ_OK;
-    const size_t column = s.numChannels;
-    const sgz_status st = sl.out[kOutLoudness].readBack(s.ldOut + size_t(s.ldCursor) * column, size_t(columns) * column * sizeof(sgz_loudness_record), s.ldPinned, s.back);
-    if (st == SGZ_OK) s.ldCursor += columns;
-    return st;
-}
-
-// ---- the track lane inside the stream (sgz.h, "The track lane") ----------------------------------------------------------------------------
-// what a feed checks for the lane before anything is consumed: the frames its samples complete fit behind the cursor
-static sgz_status pcmTrackFits(const sgz_pcm_stream &s, uint64_t frames)
-{
-    if (s.trArmed && frames > s.trCap - s.trCursor)
+    for (const PcmLane &l : s.lane)
+        if (l.m && !l.sink.fits((l.open + nsamples) / l.m))
+            return fail(SGZ_EINVAL, std::string("sgz_pcm_stream: the feed closes more ") + l.word + " columns than the buffer has left (sgz_pcm_stream_" + l.call +
+                                        "_for; re-arm with sgz_pcm_stream_set_" + l.call + ")");
+    if (!s.track.fits(frames))
         return fail(SGZ_EINVAL, "sgz_pcm_stream: the feed completes more frames than the track buffer has left (sgz_pcm_stream_track_for; re-arm with sgz_pcm_stream_set_track)");
     return SGZ_OK;
 }
 
-// a slot's records of a piece, maxFrames * pairs of them (both slots are idle between feeds)
-static sgz_status pcmTrackBuffers(sgz_pcm_stream &s, PcmSlot &sl)
+// a lane's part of a piece, on the compute stream: the n samples the converter just wrote at `fresh` -> the columns they close, into the slot
+static sgz_status pcmLanePiece(sgz_pcm_stream &s, PcmLane &l, PcmSlot &sl, const float *fresh, size_t n, uint64_t *columns)
 {
-    return s.trArmed ? sl.out[kOutTrack].reserve(s.maxFrames * s.cfg.num_pairs * sizeof(sgz_line_peak), !s.trPinned) : SGZ_OK;
+    *columns = 0;
+    if (!l.m || n == 0) return SGZ_OK;
+    if (sgz_status st = l.run(s, l, fresh, n, 0, sl.out[l.sink.kind].dev, columns); st != SGZ_OK) return st;
+    l.open = (l.open + n) % l.m;
+    return SGZ_OK;
 }
 
-// the records of the piece's `frames` frames to the caller's buffer at the cursor, on the read-back stream
-static sgz_status pcmTrackReadBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t frames)
+// the tail every sgz_pcm_stream_set_<lane> shares behind its own checks: m, the caller's columns, the cursor at 0; a slot holds the
+// ceil(chunk / m) + 1 columns a piece can close
+static void pcmLaneArm(sgz_pcm_stream &s, PcmLane &l, uint32_t m, void *out, uint64_t capacity)
 {
-    if (!frames) return SGZ_OK;
-    const size_t record = s.cfg.num_pairs;
-    const sgz_status st = sl.out[kOutTrack].readBack(s.trOut + size_t(s.trCursor) * record, size_t(frames) * record * sizeof(sgz_line_peak), s.trPinned, s.back);
-    if (st == SGZ_OK) s.trCursor += frames;
-    return st;
+    l.m = m;
+    l.sink.arm((s.chunk + m - 1) / m + 1, out, capacity);
+}
+static void pcmLaneDisarm(PcmLane &l) { l.m = 0; l.open = 0; l.sink.disarm(); }         // off: the open column is dropped
+
+static uint64_t pcmLaneFor(const sgz_pcm_stream *s, int id, size_t nsamples, int flush)
+{
+    if (!s || !s->lane[id].m) return 0;
+    const PcmLane &l = s->lane[id];
+    const uint64_t t = l.open + nsamples;
+    return t / l.m + ((flush && t % l.m) ? 1u : 0u);
+}
+
+static sgz_status pcmLaneState(const sgz_pcm_stream *s, int id, uint64_t *columns_written, uint64_t *open_samples)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (columns_written) *columns_written = s->lane[id].sink.cursor;
+    if (open_samples) *open_samples = s->lane[id].open;
+    return SGZ_OK;
+}
+
+// sgz_pcm_stream_flush_<lane>: the emit launch alone, the one column behind it on the compute stream itself, and waited for
+static sgz_status pcmLaneFlush(sgz_pcm_stream *s, int id)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    PcmLane &l = s->lane[id];
+    // (the message is put together only where it is needed: a flush with nothing open is a microsecond)
+    const auto refuse = [&l](const char *why) { return fail(SGZ_EINVAL, std::string("sgz_pcm_stream_flush_") + l.call + why + "sgz_pcm_stream_set_" + l.call + ")"); };
+    if (!l.m) return refuse(": the lane is off (");
+    if (!l.open) return SGZ_OK;
+    if (l.sink.cursor >= l.sink.cap) return refuse(": no column left in the buffer (re-arm with ");
+    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
+    if (sgz_status st = l.sink.reserve(sl); st != SGZ_OK) return st;
+    PcmOut &out = sl.out[l.sink.kind];
+    uint64_t closed = 0;
+    if (sgz_status st = l.run(*s, l, s->d_planar[s->cur], 0, 1, out.dev, &closed); st != SGZ_OK) return st;
+    if (sgz_status rb = l.sink.readBack(sl, 1, s->compute); rb != SGZ_OK) return rb;
+    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) {
+        out.dst = nullptr; --l.sink.cursor;                        // (nothing arrived: the column is not counted)
+        return hipFail(e, "hipStreamSynchronize(s->compute)");
+    }
+    out.drain();
+    l.open = 0;
+    return SGZ_OK;
 }
 
 // ---- the piece loop ------------------------------------------------------------------------------------------------------------------------
 // What both feeds do once they have refused what they refuse.  The feed is cut into pieces of at most `chunk` samples; piece i uses slot i & 1:
 //   1. upload            copy stream: the samples to the slot (through its pinned block when the caller's are pageable)
-//   2. convert + render  compute stream, behind ev[1]: the converter behind the held tail, the waveform and level lanes on the new samples, the Part's
+//   2. convert + render  compute stream, behind ev[1]: the converter behind the held tail, the column lanes on the new samples, the Part's
 //                        render of what became complete (armed, the track lane's search with it), the new tail to the other planar buffer
-//   3. read back         read-back stream, behind ev[4]: the Part's rows, the track's records, the waveform's columns, the level's records
+//   3. read back         read-back stream, behind ev[4]: the Part's rows, then every sink's units in kReadBackOrder
 // The two kinds of feed differ in their Part alone: reserve(s, sl) makes its outputs in a slot before anything is consumed; render(s, sl,
 // planar, total, frames, last, &units) enqueues the render of a piece's frames and says how many rows -- `units`, what the feed counts and its
 // timing reports -- it leaves in the slot; readBack(s, sl, done, units) enqueues their copies behind the feed's `done` earlier rows.
@@ -565,11 +528,8 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
     for (PcmSlot &sl : s.slot) {
         if (nsamples && !pcmPinned && !sl.h_pcm) SGZ_HIP(hipHostMalloc(&sl.h_pcm, s.chunk * s.frameBytes, hipHostMallocDefault));
         if (sgz_status st = part.reserve(s, sl); st != SGZ_OK) return st;
-        if (sgz_status st = pcmWaveBuffers(s, sl); st != SGZ_OK) return st;
-        if (sgz_status st = pcmTrackBuffers(s, sl); st != SGZ_OK) return st;
-        if (sgz_status st = pcmLevelBuffers(s, sl); st != SGZ_OK) return st;
-        if (sgz_status st = pcmTruePeakBuffers(s, sl); st != SGZ_OK) return st;
-        if (sgz_status st = pcmLoudnessBuffers(s, sl); st != SGZ_OK) return st;
+        for (PcmSinkId id : kReserveOrder)
+            if (sgz_status st = s.sink(id).reserve(sl); st != SGZ_OK) return st;
     }
     const uint8_t *src = static_cast<const uint8_t *>(pcm);
     uint64_t done = 0, chunks = 0;
@@ -594,11 +554,9 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             if (n)
                 if (sgz_status st = launchPcmToPlanar(sl.d_pcm, s.format, s.srcChannels, n, s.map, s.numChannels, planar + s.held, s.stride, s.compute); st != SGZ_OK) return st;
             if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[3], s.compute));
-            uint64_t waveColumns = 0, levelColumns = 0, truePeakColumns = 0, loudnessColumns = 0, units = 0;
-            if (sgz_status st = pcmWavePiece(s, sl, planar + s.held, n, &waveColumns); st != SGZ_OK) return st;
-            if (sgz_status st = pcmLevelPiece(s, sl, planar + s.held, n, &levelColumns); st != SGZ_OK) return st;
-            if (sgz_status st = pcmTruePeakPiece(s, sl, planar + s.held, n, &truePeakColumns); st != SGZ_OK) return st;
-            if (sgz_status st = pcmLoudnessPiece(s, sl, planar + s.held, n, &loudnessColumns); st != SGZ_OK) return st;
+            uint64_t yields[kPcmSinks] = {}, units = 0;                             // what the piece leaves for every sink, and for the Part
+            for (int id = 0; id < kPcmLanes; ++id)
+                if (sgz_status st = pcmLanePiece(s, s.lane[id], sl, planar + s.held, n, &yields[id]); st != SGZ_OK) return st;
             const uint64_t total = s.held + n;
             if (sgz_status st = part.render(s, sl, planar, size_t(total), frames, at + n == nsamples, &units); st != SGZ_OK) return st;
             if (frames) {
@@ -608,19 +566,16 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             }                                                                      // (no frame: the tail just grew where it is)
             s.held = keep;
             SGZ_HIP(hipEventRecord(sl.ev[4], s.compute));
-            // 3. read back (a piece may close waveform or level columns and complete no frame, or complete frames whose records are all it returns)
-            const uint64_t trackFrames = s.trArmed ? frames : 0;
-            sl.rendered = units > 0 || waveColumns > 0 || trackFrames > 0 || levelColumns > 0 || truePeakColumns > 0 || loudnessColumns > 0;
+            // 3. read back (a piece may close a lane's columns and complete no frame, or complete frames whose records are all it returns)
+            yields[kSinkTrack] = s.track.armed() ? frames : 0;
+            sl.rendered = units > 0 || std::any_of(yields, yields + kPcmSinks, [](uint64_t y) { return y > 0; });
             if (sl.rendered) {
                 SGZ_HIP(hipStreamWaitEvent(s.back, sl.ev[4], 0));
                 if (sl.timed) SGZ_HIP(hipEventRecord(sl.ev[5], s.back));
                 if (units)
                     if (sgz_status st = part.readBack(s, sl, done, units); st != SGZ_OK) return st;
-                if (sgz_status st = pcmTrackReadBack(s, sl, trackFrames); st != SGZ_OK) return st;
-                if (sgz_status st = pcmWaveReadBack(s, sl, waveColumns); st != SGZ_OK) return st;
-                if (sgz_status st = pcmLevelReadBack(s, sl, levelColumns); st != SGZ_OK) return st;
-                if (sgz_status st = pcmTruePeakReadBack(s, sl, truePeakColumns); st != SGZ_OK) return st;
-                if (sgz_status st = pcmLoudnessReadBack(s, sl, loudnessColumns); st != SGZ_OK) return st;
+                for (PcmSinkId id : kReadBackOrder)
+                    if (sgz_status st = s.sink(id).readBack(sl, yields[id], s.back); st != SGZ_OK) return st;
                 SGZ_HIP(hipEventRecord(sl.ev[6], s.back));
             }
             sl.busy = true;
@@ -653,16 +608,16 @@ struct PcmFramesPart {
     {
         if (!need) return SGZ_OK;
         const sgz_status st = sl.out[kOutImage].reserve(pcmImageBytes(s, s.maxFrames), !rgbaPinned);
-        if (st != SGZ_OK || (!lines && !s.trArmed)) return st;    // (the track lane searches the line results: rendered, never read back for it)
+        if (st != SGZ_OK || (!lines && !s.track.armed())) return st;    // (the track lane searches the line results: rendered, never read back for it)
         return sl.out[kOutLines].reserve(pcmLinesFloats(s, s.maxFrames) * sizeof(float), lines && !linesPinned);
     }
     sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t total, uint64_t frames, bool, uint64_t *units) const
     {
         *units = frames;
         if (!frames) return SGZ_OK;
-        float *d_lines = (lines || s.trArmed) ? sl.out[kOutLines].as<float>() : nullptr;
+        float *d_lines = (lines || s.track.armed()) ? sl.out[kOutLines].as<float>() : nullptr;
         const sgz_status st = sgz_spectrogram_render_device(s.plan, planar, s.stride, total, sl.out[kOutImage].as<uint8_t>(), d_lines, s.d_state, s.compute);
-        if (st != SGZ_OK || !s.trArmed) return st;
+        if (st != SGZ_OK || !s.track.armed()) return st;
         return runTrackPeaksLines(s.plan->impl, d_lines, size_t(frames), s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>(), s.compute);
     }
     sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t frames) const
@@ -701,7 +656,7 @@ struct PcmColumnsPart {
         if (frames) {
             const SlabTrack track{s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>()};
             st = runOverviewSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovCarry, s.d_state, d_rgba, d_peaks,
-                                  s.compute, s.trArmed ? &track : nullptr);
+                                  s.compute, s.track.armed() ? &track : nullptr);
         } else if (*units) {                                       // no frame arrives and the open column is flushed
             st = runOverviewColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovCarry, d_rgba, d_peaks, s.compute);
         }
@@ -776,7 +731,9 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_wvCarry, (void *)s->d_lvCarry, (void *)s->d_tpCarry, (void *)s->d_ldCarry, s->d_ldScratch}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry}) if (p) (void)hipFree(p);
+    for (PcmLane &l : s->lane) if (l.d_carry) (void)hipFree(l.d_carry);
+    if (s->d_ldScratch) (void)hipFree(s->d_ldScratch);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
     if (s->plan) sgz_plan_destroy(s->plan);
     delete s;
@@ -801,6 +758,19 @@ sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format
     s->chunk = chunk_samples ? chunk_samples : std::min(kPcmDefaultChunk, kPcmDefaultSlotBytes / s->frameBytes);
     s->stride = (size_t(cfg->window_size) - 1 + s->chunk + 63) & ~size_t(63);       // the held tail (< W) and a piece behind it; 256-byte rows
     s->maxFrames = (s->chunk - 1) / cfg->hop + 1;
+    // the lanes: the word for messages, the calls' suffix, the slot's output, the bytes of one column (a record per channel or pair), the hook
+    const struct { const char *word, *call; PcmOutKind kind; size_t unit; PcmLaneRun run; } lanes[kPcmLanes] = {
+        {"waveform", "waveform", kOutWave, s->numChannels * 2 * sizeof(float), pcmWaveRun},
+        {"level", "level", kOutLevel, cfg->num_pairs * sizeof(sgz_level_record), pcmLevelRun},
+        {"true-peak", "truepeak", kOutTruePeak, s->numChannels * sizeof(sgz_truepeak_record), pcmTruePeakRun},
+        {"loudness", "loudness", kOutLoudness, s->numChannels * sizeof(sgz_loudness_record), pcmLoudnessRun},
+    };
+    for (int id = 0; id < kPcmLanes; ++id) {
+        PcmLane &l = s->lane[id];
+        l.word = lanes[id].word; l.call = lanes[id].call; l.run = lanes[id].run;
+        l.sink.kind = lanes[id].kind; l.sink.unit = lanes[id].unit;
+    }
+    s->track.kind = kOutTrack; s->track.unit = cfg->num_pairs * sizeof(sgz_line_peak);
     if (sgz_status st = sgz_plan_upload(s->plan); st != SGZ_OK) return bail(st);
 #define SGZ_PCM_TRY(call) do { if (hipError_t e_ = (call); e_ != hipSuccess) return bail(hipFail(e_, #call)); } while (0)
     for (hipStream_t *q : {&s->copy, &s->compute, &s->back}) SGZ_PCM_TRY(hipStreamCreateWithFlags(q, hipStreamNonBlocking));
@@ -831,11 +801,10 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     SGZ_HIP(hipStreamSynchronize(s->compute));
     s->held = 0;
     s->ovOpen = 0;                                                                  // an open overview column is dropped
-    s->wvOpen = 0; s->wvCursor = 0;                                                 // and the waveform's; its columns start over
-    s->trCursor = 0;                                                                // the track's records too; the lane stays armed
-    s->lvOpen = 0; s->lvCursor = 0;                                                 // the level lane as the waveform's
-    s->tpOpen = 0; s->tpCursor = 0; s->tpContinued = false;                         // the true-peak lane too, and its history is zeros again
-    s->ldOpen = 0; s->ldCursor = 0; s->ldIndex = 0; s->ldContinued = false;         // the loudness lane as that one; its samples count from 0 again
+    for (int id = 0; id < kPcmSinks; ++id) s->sink(id).cursor = 0;                  // every lane's columns and the track's records start over; all stay armed
+    for (PcmLane &l : s->lane) l.open = 0;                                          // open columns are dropped
+    s->tpContinued = s->ldContinued = false;                                        // the true-peak and loudness histories are zeros again
+    s->ldIndex = 0;                                                                 // and the loudness lane's samples count from 0
     return SGZ_OK;
 }
 
@@ -850,11 +819,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     if (frames_out) *frames_out = need;
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
     if (need && !rgba_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null rgba_out");
-    if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
-    if (sgz_status st = pcmLevelFits(*s, nsamples); st != SGZ_OK) return st;
-    if (sgz_status st = pcmTruePeakFits(*s, nsamples); st != SGZ_OK) return st;
-    if (sgz_status st = pcmLoudnessFits(*s, nsamples); st != SGZ_OK) return st;
-    if (sgz_status st = pcmTrackFits(*s, need); st != SGZ_OK) return st;
+    if (sgz_status st = pcmLanesFit(*s, nsamples, need); st != SGZ_OK) return st;
     PcmFramesPart part{rgba_out, lines_out, need, need && isPinnedHost(rgba_out), need && lines_out && isPinnedHost(lines_out)};
     return pcmFeed(*s, pcm, nsamples, false, part, frames_out, timing, t0);
 }
@@ -896,11 +861,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
     if (columns_out) *columns_out = need;
     if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)");
-    if (sgz_status st = pcmWaveFits(*s, nsamples); st != SGZ_OK) return st;
-    if (sgz_status st = pcmLevelFits(*s, nsamples); st != SGZ_OK) return st;
-    if (sgz_status st = pcmTruePeakFits(*s, nsamples); st != SGZ_OK) return st;
-    if (sgz_status st = pcmLoudnessFits(*s, nsamples); st != SGZ_OK) return st;
-    if (sgz_status st = pcmTrackFits(*s, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
+    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
     PcmColumnsPart part{rgba_out, peaks_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && peaks_out && isPinnedHost(peaks_out)};
     // (a feed without samples still has one piece when it flushes an open column)
     return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
@@ -917,186 +878,58 @@ sgz_status sgz_spectrogram_overview_pcm(const sgz_spectrum_config *cfg, const vo
                       [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview(s, pcm, nsamples, k, 1, rgba_out, peaks_out, columns, &columns, timing); });
 }
 
-// ---- the waveform lane's calls ----------------------------------------------------------------------------------------------------------------
+// ---- the lanes' calls ---------------------------------------------------------------------------------------------------------------------------
+// Every sgz_pcm_stream_set_<lane> keeps its own argument checks, and what arming and disarming mean for its carry; the tail is pcmLaneArm
 sgz_status sgz_pcm_stream_set_waveform(sgz_pcm_stream *s, uint32_t m, float *wave_out, uint64_t capacity_columns)
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (m == 0) {                                                  // off: the open column is dropped
-        s->wvM = 0; s->wvOut = nullptr; s->wvCap = s->wvCursor = s->wvOpen = 0;
-        return SGZ_OK;
-    }
+    PcmLane &l = s->lane[kSinkWave];
+    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
     if (!wave_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: null wave_out");
     if (reinterpret_cast<uintptr_t>(wave_out) % alignof(float)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: wave_out is not aligned to float");
-    if (s->wvOpen && m != s->wvM) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: m differs from the open column's -- flush it (sgz_pcm_stream_flush_waveform), disarm or reset first");
-    if (!s->d_wvCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_wvCarry), size_t(2) * s->numChannels * 2 * sizeof(float)));
-    s->wvM = m; s->wvOut = wave_out; s->wvCap = capacity_columns; s->wvCursor = 0;
-    s->wvPinned = capacity_columns && isPinnedHost(wave_out);
+    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: m differs from the open column's -- flush it (sgz_pcm_stream_flush_waveform), disarm or reset first");
+    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * 2 * sizeof(float)));
+    pcmLaneArm(*s, l, m, wave_out, capacity_columns);
     return SGZ_OK;
 }
 
-uint64_t sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush)
-{
-    if (!s || !s->wvM) return 0;
-    const uint64_t t = s->wvOpen + nsamples;
-    return t / s->wvM + ((flush && t % s->wvM) ? 1u : 0u);
-}
-
-sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (columns_written) *columns_written = s->wvCursor;
-    if (open_samples) *open_samples = s->wvOpen;
-    return SGZ_OK;
-}
-
-sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!s->wvM) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_waveform: the lane is off (sgz_pcm_stream_set_waveform)");
-    if (!s->wvOpen) return SGZ_OK;
-    if (s->wvCursor >= s->wvCap) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_waveform: no column left in the buffer (re-arm with sgz_pcm_stream_set_waveform)");
-    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
-    if (sgz_status st = pcmWaveBuffers(*s, sl); st != SGZ_OK) return st;
-    const WaveColumnsShape sh = waveColumnsShape(s->numChannels, 0, s->wvM, uint32_t(s->wvOpen), 1, 0);
-    const sgz_status st = runWaveColumns(sh, s->d_planar[s->cur], s->stride, s->numChannels, 0, s->wvM, uint32_t(s->wvOpen), pcmWaveCarry(*s, s->wvCur),
-                                         pcmWaveCarry(*s, s->wvCur ^ 1), sl.out[kOutWave].as<float>(), nullptr, s->compute);
-    if (st != SGZ_OK) return st;
-    // the one column behind the launch on the compute stream itself, and waited for
-    const size_t column = size_t(s->numChannels) * 2;
-    PcmOut &out = sl.out[kOutWave];
-    if (sgz_status rb = out.readBack(s->wvOut + size_t(s->wvCursor) * column, column * sizeof(float), s->wvPinned, s->compute); rb != SGZ_OK) return rb;
-    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) { out.dst = nullptr; return hipFail(e, "hipStreamSynchronize(s->compute)"); }
-    out.drain();
-    s->wvOpen = 0;
-    ++s->wvCursor;
-    return SGZ_OK;
-}
-
-// ---- the level lane's calls -------------------------------------------------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_set_level(sgz_pcm_stream *s, uint32_t m, sgz_level_record *level_out, uint64_t capacity_columns)
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (m == 0) {                                                  // off: the open column is dropped
-        s->lvM = 0; s->lvOut = nullptr; s->lvCap = s->lvCursor = s->lvOpen = 0;
-        return SGZ_OK;
-    }
+    PcmLane &l = s->lane[kSinkLevel];
+    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
     if (!level_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: null level_out");
     if (reinterpret_cast<uintptr_t>(level_out) % alignof(sgz_level_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: level_out is not aligned to 8 bytes");
-    if (s->lvOpen && m != s->lvM) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: m differs from the open column's -- flush it (sgz_pcm_stream_flush_level), disarm or reset first");
-    if (!s->d_lvCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_lvCarry), size_t(2) * s->cfg.num_pairs * sizeof(sgz_level_record)));
-    s->lvM = m; s->lvOut = level_out; s->lvCap = capacity_columns; s->lvCursor = 0;
-    s->lvPinned = capacity_columns && isPinnedHost(level_out);
+    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: m differs from the open column's -- flush it (sgz_pcm_stream_flush_level), disarm or reset first");
+    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->cfg.num_pairs * sizeof(sgz_level_record)));
+    pcmLaneArm(*s, l, m, level_out, capacity_columns);
     return SGZ_OK;
 }
 
-uint64_t sgz_pcm_stream_level_for(const sgz_pcm_stream *s, size_t nsamples, int flush)
-{
-    if (!s || !s->lvM) return 0;
-    const uint64_t t = s->lvOpen + nsamples;
-    return t / s->lvM + ((flush && t % s->lvM) ? 1u : 0u);
-}
-
-sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (columns_written) *columns_written = s->lvCursor;
-    if (open_samples) *open_samples = s->lvOpen;
-    return SGZ_OK;
-}
-
-sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!s->lvM) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_level: the lane is off (sgz_pcm_stream_set_level)");
-    if (!s->lvOpen) return SGZ_OK;
-    if (s->lvCursor >= s->lvCap) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_level: no column left in the buffer (re-arm with sgz_pcm_stream_set_level)");
-    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
-    if (sgz_status st = pcmLevelBuffers(*s, sl); st != SGZ_OK) return st;
-    const uint32_t pairs = s->cfg.num_pairs;
-    const LevelColumnsShape sh = levelColumnsShape(pairs, 0, s->lvM, uint32_t(s->lvOpen), 1, 0);
-    const sgz_status st = runLevelColumns(sh, s->d_planar[s->cur], s->stride, pairs, 0, s->lvM, uint32_t(s->lvOpen), pcmLevelCarry(*s, s->lvCur),
-                                          pcmLevelCarry(*s, s->lvCur ^ 1), sl.out[kOutLevel].as<sgz_level_record>(), nullptr, s->compute);
-    if (st != SGZ_OK) return st;
-    // the one column behind the launch on the compute stream itself, and waited for
-    PcmOut &out = sl.out[kOutLevel];
-    if (sgz_status rb = out.readBack(s->lvOut + size_t(s->lvCursor) * pairs, pairs * sizeof(sgz_level_record), s->lvPinned, s->compute); rb != SGZ_OK) return rb;
-    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) { out.dst = nullptr; return hipFail(e, "hipStreamSynchronize(s->compute)"); }
-    out.drain();
-    s->lvOpen = 0;
-    ++s->lvCursor;
-    return SGZ_OK;
-}
-
-// ---- the true-peak lane's calls ---------------------------------------------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_set_truepeak(sgz_pcm_stream *s, uint32_t m, sgz_truepeak_record *out, uint64_t capacity_columns)
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (m == 0) {                                                  // off: the open column and the history are dropped
-        s->tpM = 0; s->tpOut = nullptr; s->tpCap = s->tpCursor = s->tpOpen = 0; s->tpContinued = false;
-        return SGZ_OK;
-    }
+    PcmLane &l = s->lane[kSinkTruePeak];
+    if (m == 0) { pcmLaneDisarm(l); s->tpContinued = false; return SGZ_OK; }                 // (the history is dropped too)
     if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: null out");
     if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_truepeak_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: out is not aligned to 8 bytes");
-    if (s->tpOpen && m != s->tpM) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: m differs from the open column's -- flush it (sgz_pcm_stream_flush_truepeak), disarm or reset first");
-    if (!s->d_tpCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_tpCarry), size_t(2) * s->numChannels * sizeof(sgz_truepeak_carry)));
-    if (m != s->tpM) s->tpContinued = false;                       // (arming: the lane starts at the next sample with a zero history; the same m keeps it)
-    s->tpM = m; s->tpOut = out; s->tpCap = capacity_columns; s->tpCursor = 0;
-    s->tpPinned = capacity_columns && isPinnedHost(out);
+    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: m differs from the open column's -- flush it (sgz_pcm_stream_flush_truepeak), disarm or reset first");
+    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * sizeof(sgz_truepeak_carry)));
+    if (m != l.m) s->tpContinued = false;                          // (arming: the lane starts at the next sample with a zero history; the same m keeps it)
+    pcmLaneArm(*s, l, m, out, capacity_columns);
     return SGZ_OK;
 }
 
-uint64_t sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush)
-{
-    if (!s || !s->tpM) return 0;
-    const uint64_t t = s->tpOpen + nsamples;
-    return t / s->tpM + ((flush && t % s->tpM) ? 1u : 0u);
-}
-
-sgz_status sgz_pcm_stream_truepeak_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (columns_written) *columns_written = s->tpCursor;
-    if (open_samples) *open_samples = s->tpOpen;
-    return SGZ_OK;
-}
-
-sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!s->tpM) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_truepeak: the lane is off (sgz_pcm_stream_set_truepeak)");
-    if (!s->tpOpen) return SGZ_OK;
-    if (s->tpCursor >= s->tpCap) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_truepeak: no column left in the buffer (re-arm with sgz_pcm_stream_set_truepeak)");
-    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
-    if (sgz_status st = pcmTruePeakBuffers(*s, sl); st != SGZ_OK) return st;
-    const uint32_t channels = s->numChannels;
-    // the emit launch alone, on the open column of the current half; the carry, and with it the history, stays where it is
-    const TruePeakColumnsShape sh = truePeakColumnsShape(channels, 0, s->tpM, uint32_t(s->tpOpen), 1, 0);
-    const sgz_status st = runTruePeakColumns(sh, s->d_planar[s->cur], s->stride, channels, 0, s->tpM, uint32_t(s->tpOpen), 1u, pcmTruePeakCarry(*s, s->tpCur),
-                                             pcmTruePeakCarry(*s, s->tpCur ^ 1), sl.out[kOutTruePeak].as<sgz_truepeak_record>(), nullptr, s->compute);
-    if (st != SGZ_OK) return st;
-    // the one column behind the launch on the compute stream itself, and waited for
-    PcmOut &out = sl.out[kOutTruePeak];
-    if (sgz_status rb = out.readBack(s->tpOut + size_t(s->tpCursor) * channels, channels * sizeof(sgz_truepeak_record), s->tpPinned, s->compute); rb != SGZ_OK) return rb;
-    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) { out.dst = nullptr; return hipFail(e, "hipStreamSynchronize(s->compute)"); }
-    out.drain();
-    s->tpOpen = 0;
-    ++s->tpCursor;
-    return SGZ_OK;
-}
-
-// ---- the loudness lane's calls ----------------------------------------------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_filter *filter, uint32_t m, sgz_loudness_record *out, uint64_t capacity_columns)
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (m == 0) {                                                  // off: the open column, the history and the index are dropped
-        s->ldM = 0; s->ldOut = nullptr; s->ldCap = s->ldCursor = s->ldOpen = s->ldIndex = 0; s->ldContinued = false;
-        return SGZ_OK;
-    }
+    PcmLane &l = s->lane[kSinkLoudness];
+    if (m == 0) { pcmLaneDisarm(l); s->ldIndex = 0; s->ldContinued = false; return SGZ_OK; }  // (the history and the index are dropped too)
     if (!filter) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: null filter");
     if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: null out");
     if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_loudness_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: out is not aligned to 8 bytes");
-    const bool same = s->ldM == m && std::memcmp(&s->ldFilter, filter, sizeof *filter) == 0;
-    if (s->ldOpen && !same) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: m or the filter differs from the open column's -- flush it (sgz_pcm_stream_flush_loudness), disarm or reset first");
+    const bool same = l.m == m && std::memcmp(&s->ldFilter, filter, sizeof *filter) == 0;
+    if (l.open && !same) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: m or the filter differs from the open column's -- flush it (sgz_pcm_stream_flush_loudness), disarm or reset first");
     if (!same) {
         // (what the stage call refuses, and the tap table: a refused filter arms nothing)
         size_t bytes = 0;
@@ -1106,58 +939,32 @@ sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_fil
         if (s->ldCarryCap < 2 * bytes) {
             // (both slots are idle between feeds, but a flush's launch may still read the old block: wait for it)
             SGZ_HIP(hipStreamSynchronize(s->compute));
-            if (s->d_ldCarry) { (void)hipFree(s->d_ldCarry); s->d_ldCarry = nullptr; s->ldCarryCap = 0; }
-            SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_ldCarry), 2 * bytes));
+            if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; s->ldCarryCap = 0; }
+            SGZ_HIP(hipMalloc(&l.d_carry, 2 * bytes));
             s->ldCarryCap = 2 * bytes;
         }
         s->ldFilter = *filter;
         s->ldContinued = false;                                    // (arming: the lane starts at the next sample, index 0, with a zero history)
-        s->ldIndex = 0; s->ldCur = 0;
+        s->ldIndex = 0; l.cur = 0;
     }
-    s->ldM = m; s->ldOut = out; s->ldCap = capacity_columns; s->ldCursor = 0;
-    s->ldPinned = capacity_columns && isPinnedHost(out);
+    pcmLaneArm(*s, l, m, out, capacity_columns);
     return SGZ_OK;
 }
 
-uint64_t sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, int flush)
-{
-    if (!s || !s->ldM) return 0;
-    const uint64_t t = s->ldOpen + nsamples;
-    return t / s->ldM + ((flush && t % s->ldM) ? 1u : 0u);
-}
+uint64_t sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkWave, nsamples, flush); }
+uint64_t sgz_pcm_stream_level_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLevel, nsamples, flush); }
+uint64_t sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkTruePeak, nsamples, flush); }
+uint64_t sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLoudness, nsamples, flush); }
 
-sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (columns_written) *columns_written = s->ldCursor;
-    if (open_samples) *open_samples = s->ldOpen;
-    return SGZ_OK;
-}
+sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkWave, columns_written, open_samples); }
+sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLevel, columns_written, open_samples); }
+sgz_status sgz_pcm_stream_truepeak_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkTruePeak, columns_written, open_samples); }
+sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLoudness, columns_written, open_samples); }
 
-sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!s->ldM) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_loudness: the lane is off (sgz_pcm_stream_set_loudness)");
-    if (!s->ldOpen) return SGZ_OK;
-    if (s->ldCursor >= s->ldCap) return fail(SGZ_EINVAL, "sgz_pcm_stream_flush_loudness: no column left in the buffer (re-arm with sgz_pcm_stream_set_loudness)");
-    PcmSlot &sl = s->slot[0];                                      // (both slots are idle between feeds)
-    if (sgz_status st = pcmLoudnessBuffers(*s, sl); st != SGZ_OK) return st;
-    const uint32_t channels = s->numChannels;
-    // the emit launch alone, on the open column of the current half; the carry, and with it the history and the segment grid, stays where it is
-    const LoudnessColumnsShape sh = loudnessColumnsShape(channels, 0, s->ldM, uint32_t(s->ldOpen), 1, 0);
-    const sgz_status st = runLoudnessColumns(sh, s->ldFilter, s->d_planar[s->cur], s->stride, channels, 0, s->ldIndex, s->ldM, uint32_t(s->ldOpen), 1u,
-                                             pcmLoudnessCarry(*s, s->ldCur), pcmLoudnessCarry(*s, s->ldCur ^ 1), sl.out[kOutLoudness].as<sgz_loudness_record>(),
-                                             nullptr, s->compute);
-    if (st != SGZ_OK) return st;
-    // the one column behind the launch on the compute stream itself, and waited for
-    PcmOut &out = sl.out[kOutLoudness];
-    if (sgz_status rb = out.readBack(s->ldOut + size_t(s->ldCursor) * channels, channels * sizeof(sgz_loudness_record), s->ldPinned, s->compute); rb != SGZ_OK) return rb;
-    if (const hipError_t e = hipStreamSynchronize(s->compute); e != hipSuccess) { out.dst = nullptr; return hipFail(e, "hipStreamSynchronize(s->compute)"); }
-    out.drain();
-    s->ldOpen = 0;
-    ++s->ldCursor;
-    return SGZ_OK;
-}
+sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkWave); }
+sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLevel); }
+sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkTruePeak); }
+sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLoudness); }
 
 // ---- the track lane's calls -------------------------------------------------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_set_track(sgz_pcm_stream *s, uint32_t graph, double mouse_fraction, sgz_line_peak *track_out, uint64_t capacity_frames)
@@ -1167,21 +974,20 @@ sgz_status sgz_pcm_stream_set_track(sgz_pcm_stream *s, uint32_t graph, double mo
     if (!std::isfinite(mouse_fraction)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_track: mouse_fraction");
     if (!track_out && capacity_frames) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_track: null track_out");
     if (reinterpret_cast<uintptr_t>(track_out) % alignof(sgz_line_peak)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_track: track_out is not aligned to double");
-    s->trArmed = track_out != nullptr;                             // NULL with capacity 0: off
-    s->trGraph = graph; s->trFraction = mouse_fraction; s->trOut = track_out; s->trCap = capacity_frames; s->trCursor = 0;
-    s->trPinned = capacity_frames && isPinnedHost(track_out);
+    s->trGraph = graph; s->trFraction = mouse_fraction;
+    s->track.arm(track_out ? s->maxFrames : 0, track_out, capacity_frames);                // NULL with capacity 0: off; a slot holds a piece's frames
     return SGZ_OK;
 }
 
 uint64_t sgz_pcm_stream_track_for(const sgz_pcm_stream *s, size_t nsamples)
 {
-    return s && s->trArmed ? sgz_pcm_stream_frames_for(s, nsamples) : 0;
+    return s && s->track.armed() ? sgz_pcm_stream_frames_for(s, nsamples) : 0;
 }
 
 sgz_status sgz_pcm_stream_track_state(const sgz_pcm_stream *s, uint64_t *frames_written)
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (frames_written) *frames_written = s->trCursor;
+    if (frames_written) *frames_written = s->track.cursor;
     return SGZ_OK;
 }
 
