@@ -61,6 +61,10 @@ extern "C" {
  *  helpers sgz_loudness_filter_for_rate, sgz_loudness_taps, sgz_loudness_fold, sgz_loudness_readout and sgz_loudness_integrated and, on the
  *  PCM stream, sgz_pcm_stream_set_loudness, sgz_pcm_stream_loudness_for, sgz_pcm_stream_loudness_state, sgz_pcm_stream_flush_loudness.  No
  *  existing entry point or struct changed and the suite pins 5; a stream that was never armed enqueues what it did before.)
+ * (5, later: the stereo-field lane -- SGZ_FIELD_SECTORS, sgz_field_record, sgz_field_reading, sgz_stage_field_columns,
+ *  sgz_field_columns_limits, the host helpers sgz_field_boundaries, sgz_field_fold and sgz_field_readout and, on the PCM stream,
+ *  sgz_pcm_stream_set_field, sgz_pcm_stream_field_for, sgz_pcm_stream_field_state, sgz_pcm_stream_flush_field.  No existing entry point or
+ *  struct changed and the suite pins 5; a stream that was never armed enqueues what it did before.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -943,6 +947,117 @@ sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_fil
 uint64_t   sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
 sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
 sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s);
+
+/* The stereo-field lane: a histogram over stereo direction per screen column and channel pair of a file's samples -- where the energy sits
+ * between left and right, how wide it is, and whether something lives out of phase: what the Vectorscope's polar plot shows of a live
+ * signal, kept per column of a file (the level lane's correlation is one number of it).  The reference has no counterpart: its polar plot
+ * is live (drawPolarPlot); nothing of it is reused or contradicted.  The lane takes its geometry from it: direction from (L + R, L - R),
+ * radius = max(|L|, |R|), left at negative angles.
+ * Definition (exact, no tolerance).  Samples, pairs, columns and counts are the level lane's: x[d][i] are the stream's converted fp32
+ * samples, pair p the channels (2p, 2p + 1) = (L, R), column c covers frames c m <= i < min((c + 1) m, S), only a flushed last column may
+ * be partial, and the counts are sgz_overview_step's with samples in the place of frames.  The quantiser is the level lane's, unchanged:
+ *     v = (int32) clamp(rintf(x * 2^23), -2^26, +2^26)
+ * A frame where either side is a NaN is SKIPPED; a frame with vL = vR = 0 is SILENT; every other frame has a direction and a radius.
+ * Direction: SGZ_FIELD_SECTORS = 32 sectors on the half circle of directions.  M = vL + vR and X = vR - vL are exact integers with
+ * |.| <= 2^27; if M < 0, negate both; theta = atan2(X, M) lies in [-pi/2, pi/2].  Sector b is centred at (b - 16) pi / 32: mono is the
+ * centre of sector 16, left-only of sector 8, right-only of sector 24, antiphase (theta = +-pi/2, the same line) of sector 0.  No
+ * transcendental takes part: the boundaries are the 32 integer directions (C_k, S_k) = (rint(cos g_k 2^30), rint(sin g_k 2^30)) with
+ * g_k = (k - 15.5) pi / 32, n = #{k : C_k X - S_k M >= 0} -- every product is below 2^57, exact in 64 bits -- and the sector is n mod 32.
+ * The rounded directions increase strictly in angle, so the true tests form a prefix and a binary search finds n.  This table is
+ * normative (sgz_field_boundaries copies it); it is symmetric, C_(31-k) = C_k and S_(31-k) = -S_k:
+ *     k =  0: (52686014, -1072448455)     k =  1: (157550647, -1062120190)    k =  2: (260897982, -1041563127)
+ *     k =  3: (361732726, -1010975242)    k =  4: (459083786, -970651112)     k =  5: (552013618, -920979082)
+ *     k =  6: (639627258, -862437520)     k =  7: (721080937, -795590213)     k =  8: (795590213, -721080937)
+ *     k =  9: (862437520, -639627258)     k = 10: (920979082, -552013618)     k = 11: (970651112, -459083786)
+ *     k = 12: (1010975242, -361732726)    k = 13: (1041563127, -260897982)    k = 14: (1062120190, -157550647)
+ *     k = 15: (1072448455, -52686014)     k = 16: (1072448455, 52686014)      k = 17: (1062120190, 157550647)
+ *     k = 18: (1041563127, 260897982)     k = 19: (1010975242, 361732726)     k = 20: (970651112, 459083786)
+ *     k = 21: (920979082, 552013618)      k = 22: (862437520, 639627258)      k = 23: (795590213, 721080937)
+ *     k = 24: (721080937, 795590213)      k = 25: (639627258, 862437520)      k = 26: (552013618, 920979082)
+ *     k = 27: (459083786, 970651112)      k = 28: (361732726, 1010975242)     k = 29: (260897982, 1041563127)
+ *     k = 30: (157550647, 1062120190)     k = 31: (52686014, 1072448455)
+ * Radius: r = max(|vL|, |vR|) <= 2^26, the reference's `length`.  One sgz_field_record per (column, pair), layout [columns][pairs], 528
+ * bytes, little-endian; arrays of it on the DEVICE are aligned to 16 bytes:
+ *     radius[b]  sum of r over the sector's frames, < 2^58 with m <= 2^32 - 1
+ *     count[b]   the sector's frames
+ *     peak[b]    max of r over the sector's frames, 0 when empty
+ *     silent     frames with vL = vR = 0
+ *     skipped    frames with a NaN on either side
+ *     reserved   written as 0
+ * A column of NaNs alone has only `skipped` set.  All fields are integer sums and maxima, associative and commutative, so any cut of the
+ * stream (feeds, pieces, calls with a carry) or of a column (lanes, slices) gives the same bytes, and a coarser column is the fold of the
+ * finer ones -- add, add, max, add, add (sgz_field_fold).
+ *  sgz_stage_field_columns  DEVICE pointers; sgz_stage_level_columns' arguments and semantics to the letter, with sgz_field_record in the
+ *                      place of sgz_level_record: d_planar [2 pairs][channel_stride] (any 4-byte-aligned address), held, the carry
+ *                      d_carry [pairs] (read iff held > 0, written iff samples stay open), d_field [columns][pairs], flush, nsamples ==
+ *                      0 with held > 0 and flush: one column from the carry alone.  m up to the switch-over (512;
+ *                      sgz_field_columns_limits) runs one workgroup per (pair, tile of 4096 / m whole columns of both rows); longer
+ *                      columns are reduced in slices per column into scratch and folded by a second launch.  slices: 0 = the library's
+ *                      choice, 1 .. 64 forced -- 2 and more take the sliced form whatever m is, 1 takes the form m implies -- identical
+ *                      bytes.  Only the documented bytes are written.  Asynchronous on `stream`, nothing is waited for; scratch is
+ *                      allocated and freed in stream order.  SGZ_EINVAL, nothing launched or written: a null d_planar, pairs == 0 or
+ *                      > 32, m == 0, held >= m, channel_stride < nsamples, slices > 64, a needed d_carry or d_field that is NULL,
+ *                      d_planar not aligned to 4 bytes, d_carry or d_field not aligned to 16.  nsamples == 0 with nothing to flush:
+ *                      SGZ_OK, nothing launched.  m = 1 is legal: it writes a 528-byte record per frame.
+ *  sgz_field_columns_limits  the switch-over and the tile's sample frames (either result may be NULL).
+ *  sgz_field_boundaries  copies the table, (C_k, S_k) at cs[k][0], cs[k][1].
+ * The lane inside the sgz_pcm_stream handle -- above, "interleaved PCM in": the level lane's contract word for word, with
+ * sgz_field_record in the place of sgz_level_record and one exception.  While armed, every feed of either kind also reduces the new
+ * samples of each piece on the compute stream behind the conversion (and behind the other lanes' launches) and reads the records that
+ * closed back on the read-back stream into field_out at a cursor.  The records of all feeds and the final flush, concatenated, are the
+ * lane of the stream's converted floats byte for byte, however it is cut into feeds and pieces and whichever kind the feeds are; the
+ * image, lines, overview, peaks and every other lane's records of an armed stream are those of an unarmed one byte for byte.  The lane's
+ * m is its own.  The exception: the stream refuses 0 < m < 64 with SGZ_EINVAL -- a 528-byte record per pair for fewer than 64 frames would
+ * read back more than the samples it describes (the stage call takes every m >= 1).
+ *  sgz_pcm_stream_set_field   between feeds.  m >= 64 arms: field_out HOST sgz_field_record [capacity_columns][pairs] (aligned to 8
+ *                      bytes; pinned memory is written in place, pageable memory through a pinned twin per slot), the cursor restarts
+ *                      at 0.  The same m with another buffer keeps the open column: how a caller with a small buffer drains.  m == 0
+ *                      disarms and drops the open column.  SGZ_EINVAL: a null stream, 0 < m < 64, a null field_out with
+ *                      capacity_columns > 0, a field_out that is not aligned, another m while samples are open.
+ *  sgz_pcm_stream_field_for   columns the next feed of nsamples closes (flush != 0: that feed followed by sgz_pcm_stream_flush_field);
+ *                      0 when disarmed.
+ *  sgz_pcm_stream_field_state columns written since the lane was armed (the cursor) and the open column's samples; either may be NULL.
+ *  sgz_pcm_stream_flush_field closes the open column: one launch on the carry, one column read back, waits.  Nothing open: SGZ_OK,
+ *                      nothing done.  SGZ_EINVAL: disarmed, no column left in the buffer.
+ * A feed that would close more columns than the buffer has left is refused with SGZ_EINVAL before anything is consumed.  reset drops the
+ * open column and restarts the cursor.  Memory per slot as the level lane's, 528 bytes a record.
+ * Host arithmetic on HOST records, nothing launched:
+ *  sgz_field_fold      the zoom, with sgz_level_fold's boundary rule: output column b is the fold of source columns x0 + ceil(b w /
+ *                      cols) <= j < x0 + ceil((b + 1) w / cols), w = x1 - x0, cols = min(out_columns, w): radius and count add, peak
+ *                      is the maximum, silent and skipped add, reserved is 0.  out must not overlap in.  SGZ_EINVAL, nothing written:
+ *                      a null argument, pairs == 0, what sgz_overview_view_columns refuses, a folded count, silent or skipped above
+ *                      2^32 - 1.
+ *  sgz_field_readout   what a host draws from one record, in fp64: share[b] = count[b] / sum of count (0 when that is 0); mean[b] =
+ *                      radius[b] / (count[b] 2^23), 0 when empty; peak[b] = peak[b] / 2^23 (1.0 is full scale).  With w_b =
+ *                      radius[b] and theta_b = (b - 16) pi / 32: direction = atan2(sum w_b sin 2 theta_b, sum w_b cos 2 theta_b) / 2
+ *                      in radians, negative = left; spread = 1 - hypot(the two sums) / sum w_b, 0 for a point source and towards 1 for
+ *                      a diffuse field; both NaN where sum w_b = 0.  silent_share = silent / (sum of count + silent), 0 when that is
+ *                      0.  SGZ_EINVAL: a null argument. */
+#define SGZ_FIELD_SECTORS 32
+typedef struct sgz_field_record {
+    uint64_t radius[SGZ_FIELD_SECTORS];   /* sum of r over the sector's frames, < 2^58 */
+    uint32_t count[SGZ_FIELD_SECTORS];    /* the sector's frames */
+    uint32_t peak[SGZ_FIELD_SECTORS];     /* max r over the sector's frames, 0 when empty */
+    uint32_t silent;                      /* frames with vL = vR = 0 */
+    uint32_t skipped;                     /* frames with a NaN on either side */
+    uint64_t reserved;                    /* written as 0 */
+} sgz_field_record;         /* 528 bytes */
+typedef struct sgz_field_reading {
+    double share[SGZ_FIELD_SECTORS], mean[SGZ_FIELD_SECTORS], peak[SGZ_FIELD_SECTORS];
+    double direction, spread, silent_share;
+} sgz_field_reading;
+sgz_status sgz_stage_field_columns(const float *d_planar, size_t channel_stride, uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held,
+                                   int flush, uint32_t slices, sgz_field_record *d_carry /*[pairs]*/, sgz_field_record *d_field /*[columns][pairs]*/,
+                                   void *stream);
+void       sgz_field_columns_limits(uint32_t *switch_over, uint32_t *tile_samples);
+void       sgz_field_boundaries(int32_t cs[32][2]);
+sgz_status sgz_pcm_stream_set_field(sgz_pcm_stream *s, uint32_t m /*0 = off*/, sgz_field_record *field_out /*HOST [capacity][pairs]*/,
+                                    uint64_t capacity_columns);
+uint64_t   sgz_pcm_stream_field_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
+sgz_status sgz_pcm_stream_field_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
+sgz_status sgz_pcm_stream_flush_field(sgz_pcm_stream *s);
+sgz_status sgz_field_fold(const sgz_field_record *in, size_t n, uint32_t pairs, size_t x0, size_t x1, uint32_t out_columns, sgz_field_record *out);
+sgz_status sgz_field_readout(const sgz_field_record *rec, sgz_field_reading *out);
 
 /* The track lane: the tracker's curve over a file -- the reference's drawFrequencyTracking readout (SpectrumRendering.cpp:300-377, the
  * line-results branch) for every frame of a streamed file, in bounded memory.  sgz_spectrogram_track_device / _host want the whole file

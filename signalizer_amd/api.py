@@ -128,6 +128,18 @@ LOUDNESS_DTYPE = np.dtype([("sumsq", "<u8", (2,)), ("count", "<u4"), ("reserved"
 assert LOUDNESS_DTYPE.itemsize == 32
 
 
+# sgz_field_record: one per (column, pair) of the stereo-field lane, 528 bytes: 32 sectors of stereo direction
+FIELD_SECTORS = 32
+FIELD_DTYPE = np.dtype([("radius", "<u8", (FIELD_SECTORS,)), ("count", "<u4", (FIELD_SECTORS,)), ("peak", "<u4", (FIELD_SECTORS,)),
+                        ("silent", "<u4"), ("skipped", "<u4"), ("reserved", "<u8")])
+assert FIELD_DTYPE.itemsize == 528
+
+
+class FieldReading(C.Structure):
+    _fields_ = [("share", C.c_double * FIELD_SECTORS), ("mean", C.c_double * FIELD_SECTORS), ("peak", C.c_double * FIELD_SECTORS),
+                ("direction", C.c_double), ("spread", C.c_double), ("silent_share", C.c_double)]
+
+
 class LoudnessFilter(C.Structure):
     _fields_ = [("b", (C.c_double * 3) * 2), ("a", (C.c_double * 2) * 2), ("W", C.c_uint32), ("L", C.c_uint32)]
 
@@ -230,6 +242,8 @@ EXPORTS = [
     "sgz_stage_loudness_columns", "sgz_loudness_columns_limits", "sgz_loudness_filter_for_rate", "sgz_loudness_taps", "sgz_loudness_fold",
     "sgz_loudness_readout", "sgz_loudness_integrated",
     "sgz_pcm_stream_set_loudness", "sgz_pcm_stream_loudness_for", "sgz_pcm_stream_loudness_state", "sgz_pcm_stream_flush_loudness",
+    "sgz_stage_field_columns", "sgz_field_columns_limits", "sgz_field_boundaries", "sgz_field_fold", "sgz_field_readout",
+    "sgz_pcm_stream_set_field", "sgz_pcm_stream_field_for", "sgz_pcm_stream_field_state", "sgz_pcm_stream_flush_field",
 ]
 
 
@@ -475,7 +489,14 @@ def lib() -> C.CDLL:
     L.sgz_loudness_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_loudness_readout.argtypes = [vp, sz, u32, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgz_loudness_integrated.argtypes = [vp, sz, u32, vp, C.POINTER(C.c_double)]
-    for lane in ("waveform", "level", "truepeak", "loudness"):         # the four column lanes of the PCM stream: one set of calls each
+    L.sgz_stage_field_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
+    L.sgz_field_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    L.sgz_field_columns_limits.restype = None
+    L.sgz_field_boundaries.argtypes = [vp]
+    L.sgz_field_boundaries.restype = None
+    L.sgz_field_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
+    L.sgz_field_readout.argtypes = [vp, C.POINTER(FieldReading)]
+    for lane in ("waveform", "level", "truepeak", "loudness", "field"):      # the five column lanes of the PCM stream: one set of calls each
         getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, fp, u32, vp, u64] if lane == "loudness" else [vp, u32, vp, u64]
         getattr(L, f"sgz_pcm_stream_{lane}_for").argtypes = [vp, sz, C.c_int]
         getattr(L, f"sgz_pcm_stream_{lane}_for").restype = u64
@@ -1238,7 +1259,7 @@ class PcmStream:
         return (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
 
 
-    # the four column lanes (waveform, level, truepeak, loudness): one helper per kind of call, the lane's name picks the C call
+    # the five column lanes (waveform, level, truepeak, loudness, field): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
         if capacity_columns is None:
             capacity_columns = 0 if out is None else int(out.shape[0])
@@ -1329,6 +1350,24 @@ class PcmStream:
         """sgz_pcm_stream_flush_loudness: closes the open column (one more record per channel at the cursor); waits"""
         self._lane_flush("loudness")
 
+    # the stereo-field lane: one sgz_field_record per column of m >= 64 samples and pair, beside whatever the feeds render
+    def set_field(self, m: int, out=None, capacity_columns: int | None = None) -> None:
+        """sgz_pcm_stream_set_field: out -- a FIELD_DTYPE numpy array [capacity, pairs] or a host torch uint8 tensor [capacity, pairs, 528] (kept
+        alive here; pinned memory is written in place); m == 0 disarms, 0 < m < 64 is refused"""
+        self._lane_set("field", m, out, capacity_columns)
+
+    def field_for(self, nsamples: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_field_for: stereo-field columns the next feed of nsamples closes"""
+        return self._lane_for("field", nsamples, flush)
+
+    def field_state(self):
+        """sgz_pcm_stream_field_state: (columns written since the lane was armed, samples of the open column)"""
+        return self._lane_state("field")
+
+    def flush_field(self) -> None:
+        """sgz_pcm_stream_flush_field: closes the open column (one more record per pair at the cursor); waits"""
+        self._lane_flush("field")
+
     # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
     def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:
         """sgz_pcm_stream_set_track: out -- a float64 numpy array or host torch tensor [capacity, pairs, 6] (kept alive here; pinned memory is
@@ -1401,6 +1440,50 @@ def level_readout(record) -> dict:
     r = LevelReading()
     check(lib().sgz_level_readout(_np_ptr(rec), C.byref(r)))
     return dict(rms=tuple(r.rms), rms_db=tuple(r.rms_db), dc=tuple(r.dc), correlation=r.correlation)
+
+
+def field_columns_limits():
+    """sgz_field_columns_limits: (the switch-over between the tile form and the sliced form, the tile's sample frames)"""
+    s, t = C.c_uint32(0), C.c_uint32(0)
+    lib().sgz_field_columns_limits(C.byref(s), C.byref(t))
+    return int(s.value), int(t.value)
+
+
+def field_boundaries() -> np.ndarray:
+    """sgz_field_boundaries: the normative table, int32 [32, 2]: (C_k, S_k)"""
+    cs = np.zeros((FIELD_SECTORS, 2), np.int32)
+    lib().sgz_field_boundaries(_np_ptr(cs))
+    return cs
+
+
+def stage_field_columns(planar, channel_stride: int, pairs: int, nsamples: int, m: int, held: int = 0, flush: bool = True, slices: int = 0,
+                        carry=None, field=None, stream=None) -> int:
+    """sgz_stage_field_columns as it is: planar / carry / field -- cuda tensors (their data pointers; any may be None where the call allows
+    NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    return lib().sgz_stage_field_columns(ptr(planar), channel_stride, pairs, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(field),
+                                         C.c_void_p(s) if s else None)
+
+
+def field_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_field_fold: FIELD_DTYPE records [n, pairs], source columns [x0, x1) -> [min(out_columns, x1 - x0), pairs]"""
+    records = np.ascontiguousarray(records, FIELD_DTYPE)
+    n, pairs = records.shape
+    x1 = n if x1 is None else x1
+    out = np.zeros((max(min(out_columns, x1 - x0), 1), pairs), FIELD_DTYPE)
+    check(lib().sgz_field_fold(_np_ptr(records), n, pairs, x0, x1, out_columns, _np_ptr(out)))
+    return out[:min(out_columns, x1 - x0)]
+
+
+def field_readout(record) -> dict:
+    """sgz_field_readout of one FIELD_DTYPE record: {share, mean, peak: float64 [32], direction, spread, silent_share}"""
+    rec = np.ascontiguousarray(record, FIELD_DTYPE).reshape(1)
+    r = FieldReading()
+    check(lib().sgz_field_readout(_np_ptr(rec), C.byref(r)))
+    return dict(share=np.array(r.share), mean=np.array(r.mean), peak=np.array(r.peak), direction=r.direction, spread=r.spread,
+                silent_share=r.silent_share)
 
 
 def truepeak_columns_limits():

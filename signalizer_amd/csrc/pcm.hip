@@ -4,7 +4,8 @@
 // and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, a lane's columns or records --
 // is a PcmOut: device block, pinned twin, pending host copy.  Every lane is a PcmSink: the caller's buffer, the cursor in it, and the PcmOut its
 // units pass through; the track lane (tracker.hip), which searches every piece's line results behind its render, is a sink of frames, and the
-// four column lanes -- waveform, level, true-peak, loudness (wave_columns.hip, level_columns.hip, truepeak_columns.hip, loudness_columns.hip),
+// five column lanes -- waveform, level, true-peak, loudness, stereo-field (wave_columns.hip, level_columns.hip, truepeak_columns.hip,
+// loudness_columns.hip, field_columns.hip),
 // which reduce every piece's new samples behind the converter in that order -- are ONE PcmLane type, a sink of columns with the open column's
 // carry, and differ in a hook that makes the one call of their reduction.  The feed walks the lanes; all ride the same read-back.
 #include <hip/hip_runtime.h>
@@ -199,7 +200,8 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // lane's; Track sgz_line_peak [maxFrames][pairs] the track lane's; Level sgz_level_record [ceil(chunk / m) + 1][pairs] the level lane's;
 // TruePeak sgz_truepeak_record [ceil(chunk / m) + 1][channels] the true-peak lane's.
 // Loudness sgz_loudness_record [ceil(chunk / m) + 1][channels] the loudness lane's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kPcmOuts };
+// Field sgz_field_record [ceil(chunk / m) + 1][pairs] the stereo-field lane's.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -278,10 +280,10 @@ struct PcmSink {
     }
 };
 
-// The sinks in the order a feed refuses them; the four column lanes come first and are the stream's lane[] in this order
-enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
-constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness};
-constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness};
+// The sinks in the order a feed refuses them; the five column lanes come first and are the stream's lane[] in this order
+enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
+constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField};
+constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField};
 
 // A lane's hook: the one call of its reduction, run<Lane>Columns, on the compute stream.  (n samples at `in`, flush 0) is a piece's step: the
 // columns they close go to d_out, the open one to the other half of the carry; (0 samples, flush 1) is the flush's emit launch, which leaves the
@@ -316,8 +318,8 @@ struct sgz_pcm_stream {
     // the overview inside the stream: the open column's V [pairs][P], its frame count and its k (meaningful while ovOpen > 0)
     float *d_ovCarry = nullptr;
     uint64_t ovOpen = 0; uint32_t ovK = 0;
-    // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels])
-    // and loudness (two halves of loudnessCarryBytes(ldFilter) * channels bytes; ldCarryCap: what is allocated)
+    // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels]),
+    // stereo-field (sgz_field_record [2][pairs]) and loudness (two halves of loudnessCarryBytes(ldFilter) * channels bytes; ldCarryCap: what is allocated)
     PcmLane lane[kPcmLanes];
     // the track lane (track.most > 0: armed): a sink of frames, and the graph and mouse position searched
     PcmSink track;
@@ -365,7 +367,7 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
 }
 
 // ---- the lanes inside the stream (sgz.h, "The waveform lane" ... "The loudness lane", "The track lane") -----------------------------------------
-// The four hooks.  The waveform and level carries hold the open column alone: a step moves to the other half only when a column stays open.
+// The five hooks.  The waveform, level and stereo-field carries hold the open column alone: a step moves to the other half only when a column stays open.
 static sgz_status pcmWaveRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
 {
     const uint32_t channels = s.numChannels, open = uint32_t(l.open);
@@ -391,6 +393,22 @@ static sgz_status pcmLevelRun(sgz_pcm_stream &s, PcmLane &l, const float *in, si
     sgz_level_record *carry = static_cast<sgz_level_record *>(l.d_carry);
     const sgz_status st = runLevelColumns(sh, in, s.stride, pairs, n, l.m, open, carry + size_t(l.cur) * pairs, carry + size_t(l.cur ^ 1) * pairs,
                                           static_cast<sgz_level_record *>(d_out), scratch.p, s.compute);
+    if (st != SGZ_OK) return st;
+    if (sh.open) l.cur ^= 1;
+    *closed = sh.closed;
+    return SGZ_OK;
+}
+
+// (the stereo-field carry is sgz_field_record [2][pairs]: no filter history, the level lane's flip rule)
+static sgz_status pcmFieldRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
+{
+    const uint32_t pairs = s.cfg.num_pairs, open = uint32_t(l.open);
+    const FieldColumnsShape sh = fieldColumnsShape(pairs, n, l.m, open, flush, 0);
+    StreamScratch scratch(s.compute);
+    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
+    sgz_field_record *carry = static_cast<sgz_field_record *>(l.d_carry);
+    const sgz_status st = runFieldColumns(sh, in, s.stride, pairs, n, l.m, open, carry + size_t(l.cur) * pairs, carry + size_t(l.cur ^ 1) * pairs,
+                                          static_cast<sgz_field_record *>(d_out), scratch.p, s.compute);
     if (st != SGZ_OK) return st;
     if (sh.open) l.cur ^= 1;
     *closed = sh.closed;
@@ -764,6 +782,7 @@ sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format
         {"level", "level", kOutLevel, cfg->num_pairs * sizeof(sgz_level_record), pcmLevelRun},
         {"true-peak", "truepeak", kOutTruePeak, s->numChannels * sizeof(sgz_truepeak_record), pcmTruePeakRun},
         {"loudness", "loudness", kOutLoudness, s->numChannels * sizeof(sgz_loudness_record), pcmLoudnessRun},
+        {"stereo-field", "field", kOutField, cfg->num_pairs * sizeof(sgz_field_record), pcmFieldRun},
     };
     for (int id = 0; id < kPcmLanes; ++id) {
         PcmLane &l = s->lane[id];
@@ -951,20 +970,37 @@ sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_fil
     return SGZ_OK;
 }
 
+sgz_status sgz_pcm_stream_set_field(sgz_pcm_stream *s, uint32_t m, sgz_field_record *field_out, uint64_t capacity_columns)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    PcmLane &l = s->lane[kSinkField];
+    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
+    if (m < 64) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_field: m >= 64 samples per column (a 528-byte record per pair for fewer would read back more than the samples)");
+    if (!field_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_field: null field_out");
+    if (reinterpret_cast<uintptr_t>(field_out) % alignof(sgz_field_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_field: field_out is not aligned to 8 bytes");
+    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_field: m differs from the open column's -- flush it (sgz_pcm_stream_flush_field), disarm or reset first");
+    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->cfg.num_pairs * sizeof(sgz_field_record)));
+    pcmLaneArm(*s, l, m, field_out, capacity_columns);
+    return SGZ_OK;
+}
+
 uint64_t sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkWave, nsamples, flush); }
 uint64_t sgz_pcm_stream_level_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLevel, nsamples, flush); }
 uint64_t sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkTruePeak, nsamples, flush); }
 uint64_t sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLoudness, nsamples, flush); }
+uint64_t sgz_pcm_stream_field_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkField, nsamples, flush); }
 
 sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkWave, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLevel, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_truepeak_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkTruePeak, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLoudness, columns_written, open_samples); }
+sgz_status sgz_pcm_stream_field_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkField, columns_written, open_samples); }
 
 sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkWave); }
 sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLevel); }
 sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkTruePeak); }
 sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLoudness); }
+sgz_status sgz_pcm_stream_flush_field(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkField); }
 
 // ---- the track lane's calls -------------------------------------------------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_set_track(sgz_pcm_stream *s, uint32_t graph, double mouse_fraction, sgz_line_peak *track_out, uint64_t capacity_frames)

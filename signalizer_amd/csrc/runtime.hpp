@@ -125,6 +125,12 @@ LevelColumnsShape levelColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m,
 sgz_status runLevelColumns(const LevelColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
                            uint32_t held, const sgz_level_record *carryIn, sgz_level_record *carryOut, sgz_level_record *d_level, void *scratch,
                            hipStream_t stream);
+// the stereo-field lane's reduction (field_columns.hip), the same two steps with the level lane's carry rules
+using FieldColumnsShape = WaveColumnsShape;
+FieldColumnsShape fieldColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
+sgz_status runFieldColumns(const FieldColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
+                           uint32_t held, const sgz_field_record *carryIn, sgz_field_record *carryOut, sgz_field_record *d_field, void *scratch,
+                           hipStream_t stream);
 // the true-peak lane's reduction (truepeak_columns.hip), the same two steps.  carryIn is read (the history when `continued`, the open column
 // when held > 0) and carryOut is written whole by every call with samples: two places, never the same memory then
 using TruePeakColumnsShape = WaveColumnsShape;
