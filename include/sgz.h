@@ -65,6 +65,10 @@ extern "C" {
  *  sgz_field_columns_limits, the host helpers sgz_field_boundaries, sgz_field_fold and sgz_field_readout and, on the PCM stream,
  *  sgz_pcm_stream_set_field, sgz_pcm_stream_field_for, sgz_pcm_stream_field_state, sgz_pcm_stream_flush_field.  No existing entry point or
  *  struct changed and the suite pins 5; a stream that was never armed enqueues what it did before.)
+ * (5, later: the band lane -- sgz_band_filter, sgz_band_record, sgz_stage_band_columns, sgz_band_columns_limits, the host helpers
+ *  sgz_band_filter_for_rate, sgz_band_taps, sgz_band_fold, sgz_band_readout and sgz_band_colours and, on the PCM stream,
+ *  sgz_pcm_stream_set_band, sgz_pcm_stream_band_for, sgz_pcm_stream_band_state, sgz_pcm_stream_flush_band.  No existing entry point or
+ *  struct changed and the suite pins 5; a stream that was never armed enqueues what it did before.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -1058,6 +1062,111 @@ sgz_status sgz_pcm_stream_field_state(const sgz_pcm_stream *s, uint64_t *columns
 sgz_status sgz_pcm_stream_flush_field(sgz_pcm_stream *s);
 sgz_status sgz_field_fold(const sgz_field_record *in, size_t n, uint32_t pairs, size_t x0, size_t x1, uint32_t out_columns, sgz_field_record *out);
 sgz_status sgz_field_readout(const sgz_field_record *rec, sgz_field_reading *out);
+
+/* The band lane: three-band energy per screen column and channel of a file's samples -- the frequency colouring the Oscilloscope draws a
+ * waveform with (StreamState::audioProcessing: a 3-band Linkwitz-Riley split, band energies, RGB), kept per column of a file beside the
+ * waveform lane's envelope.  The live handle restates the network in fp32 sample by sample (scopeIngestKernel phase F); an fp32 or fp64
+ * recurrence over a file has no cut-independent bits, so this lane takes the loudness lane's formulation with another filter: segments on
+ * an absolute grid, every segment's start state an exact integer FIR, the fp64 recurrence only inside a segment in an order fixed here.
+ * Definition (exact, no tolerance).
+ *  Filter     sgz_band_filter: four section types as doubles, c[4][5] = {b0, b1, b2, a1, a2} (a0 = 1) of lp1, hp1, lp2, hp2; W, the memory
+ *             in samples, and L, the segment length: powers of two, 16 <= L <= W <= 65536.  168 bytes.  The coefficients are inputs;
+ *             nothing is derived from a sample rate inside the definition.
+ *  Quantiser  and sample index: as the loudness lane, word for word -- v = (int32) clamp(rintf(x * 2^23), -2^26, +2^26), a NaN gives
+ *             v = 0 and is not counted; v[k] = 0 for k < 0; i counts the samples since the lane was armed or reset.
+ *  Section    transposed direct form II in fp64; every *, + and - is one IEEE operation rounded to nearest even, in this order, with no
+ *             contraction, on a section's coefficients c and its state (z0, z1):
+ *                 y = c0*x + z0;   z0 = (c1*x - c3*y) + z1;   z1 = c2*x - c4*y
+ *  Tree       eight sections in the order lp1a, lp1b, hp1a, hp1b, lp2a, lp2b, hp2a, hp2b (the a and b of a type share its coefficients):
+ *                 low = lp1b(lp1a(x));   rest = hp1b(hp1a(x));   mid = lp2b(lp2a(rest));   high = hp2b(hp2a(rest))
+ *             The state has 16 components, section s owning components 2 s and 2 s + 1: the live scope's order.
+ *  Tap table  S = 30 (the loudness lane's 32 would not hold the Oscilloscope's own filter: at 22050 Hz one state component of its
+ *             impulse response reaches 0.5475).  The tree run from rest on x = 1, 0, 0, ..; h[c][k], c = 0 .. 15, k = 0 .. W - 1, is state
+ *             component c after k + 1 steps; C[c][k] = (int32) rint(2^30 h[c][k]).  The filter is accepted only if every C fits int32
+ *             and 2^26 max_c sum_k |C[c][k]| < 2^62 (sgz_band_taps; SGZ_EINVAL otherwise).
+ *  Segment    segment j covers samples j L <= i < (j + 1) L.  Its start state is
+ *                 state_c = (double)(int64) (sum over k = 0 .. W - 1 of C[c][k] v[j L - 1 - k]) * 2^-30
+ *             -- an exact 64-bit integer in any order, one conversion rounded to nearest even, an exact scale.
+ *  Output     z_b[i], b = low, mid, high, are the tree's outputs when the segment is run from that state over x = (double) v[j L], ..,
+ *             (double) v[i]; q_b[i] = (int64) rint(z_b[i]), ties to even, clamped to +-(2^31 - 1).
+ *  Record     one sgz_band_record per (column, channel), 64 bytes, layout [columns][channels], little-endian, arrays on the DEVICE
+ *             aligned to 16: sumsq[b] = the sum of q_b^2 over the column as an unsigned 128-bit integer (low word first) for b = low,
+ *             mid, high; count = the column's non-NaN samples; three reserved words written as 0.  Columns, a flush and a partial last
+ *             column are the loudness lane's.  A flush does not move the segment grid.
+ * Integer sums make a coarser column the field-wise sum of the finer ones (sgz_band_fold) and any cut of the stream or of a column gives
+ * the same bytes.  Readout: mean square of a band = sumsq / count / 2^46 (1.0 = a full-scale square wave).  Measured against the
+ * unsegmented fp64 recurrence with the helper's filter at 48000, 44100 and 8000 Hz, q differs by at most 1.55 units of 2^-23 and a
+ * 1024-sample column's band energy by at most 8e-5 of the column's total (noise at 1e-4 rms, where rounding q to an integer dominates;
+ * 2e-7 or less on louder signals): DESIGN.md section 4; tests/test_band_host.py.
+ * What a cut of the stream carries, per channel: the open column's record, the last W + L - 1 quantised samples and a zero word --
+ * 64 + 4 (W + L) bytes, [channels] of them, aligned to 16; opaque but for its size (sgz_band_columns_limits).
+ *  sgz_stage_band_columns  DEVICE pointers; sgz_stage_loudness_columns' semantics and refusals in every point: filter HOST, its tap table
+ *                      built and uploaded at the filter's first use on a device (the one blocking step) and kept; first_index, of which
+ *                      only first_index % L matters; continued; d_carry read as a snapshot and written whole by a call with
+ *                      nsamples > 0; nsamples == 0 with held > 0 and flush: one column from the carry alone, the carry untouched.  The
+ *                      launches: one workgroup per (tile of max(4096, L) samples on the segment grid, channel) stages the tile behind
+ *                      its W-sample halo in LDS, forms the 16 start-state dot products of every segment with 32 x 32 -> 64-bit integer
+ *                      multiply-adds, runs the tree's three independent chains of every segment in fp64 and stores the three q as int32
+ *                      planes to stream-ordered scratch; a second launch writes the history; the column sums follow in the loudness
+ *                      lane's structure, one pass over a column reading all three planes (m up to the switch-over, 1024, in tiles;
+ *                      longer columns in slices and a folding launch).  slices: 0 = the library's choice, 1 .. 64 forced, identical
+ *                      bytes.  SGZ_EINVAL, nothing launched or written: what sgz_stage_loudness_columns refuses -- a null or refused
+ *                      filter, W > 16384 (the host helpers take every W of the definition), nsamples above 2^40, first_index above
+ *                      2^62 among it.
+ *  sgz_band_columns_limits  the column sums' switch-over, the run tile's samples and the carry's bytes for `channels` channels (any result
+ *                      may be NULL); SGZ_EINVAL where the stage call would refuse the filter or the channel count.
+ * The lane inside the sgz_pcm_stream handle: as the loudness lane to the letter -- arm, drain, refuse, disarm, flush and reset -- launched,
+ * refused, reserved and read back behind every other lane, with one exception: the stream refuses 0 < m < 64 with SGZ_EINVAL, as the
+ * stereo-field lane does (a 64-byte record per channel for fewer samples would read back more than the samples it describes; the stage
+ * call takes every m >= 1).  Everything an armed stream returns besides the records equals an unarmed stream's.
+ * Host arithmetic, nothing launched, strict fp:
+ *  sgz_band_filter_for_rate  the Oscilloscope's design (tuneCrossOver; 300 and 3000 Hz there): fn = (double)(float)(hz / rate), w0 = 2 pi
+ *                      fn, alpha = sin w0 / sqrt 2, a0 = 1 + alpha; low-pass b = ((1 - cos w0) / 2, 1 - cos w0, (1 - cos w0) / 2) / a0,
+ *                      high-pass b = ((1 + cos w0) / 2, -(1 + cos w0), (1 + cos w0) / 2) / a0, a1 = -2 cos w0 / a0, a2 = (1 - alpha) / a0;
+ *                      each coefficient rounded to float and widened, so the sections are the live scope's.  W = the smallest power of
+ *                      two >= 6 rate / low_hz (at least 256), L = W / 16: with 300 / 3000 at 8 .. 384 kHz, 20 / 200 and 2000 / 20000 every
+ *                      impulse response is below 2^-33 at W and every table is accepted.  SGZ_EINVAL: a null f, a rate that is not
+ *                      positive and finite, low_hz <= 0, high_hz <= low_hz, high_hz >= rate / 2, a W above 65536.  Not bit-normative
+ *                      (libm decides the last bits): a caller may pass any coefficients.
+ *  sgz_band_taps       the normative table, C[c][k] at taps[c * W + k] (16 W words), or SGZ_EINVAL with nothing written.
+ *  sgz_band_fold       the zoom, with sgz_loudness_fold's rules and refusals.
+ *  sgz_band_readout    reads ncols >= 1 consecutive columns [ncols][channels] of channel `channel` together: mean_square[b] = the sum
+ *                      of the columns' sumsq[b] over the sum of their counts over 2^46 (0 without samples), db[b] = 10 log10 of it, -inf
+ *                      when it is 0.  Either result may be NULL.  SGZ_EINVAL: a null recs, ncols == 0, channel >= channels.
+ *  sgz_band_colours    one RGBA8 per column of channel `channel`, the live scope's colour rule applied to the column's mean band
+ *                      energies: the column's three mean squares are rounded to float and take the place of the smoothed band states
+ *                      in accumulateColour's fp32 arithmetic, in its order -- red, green, blue = sum_b state[b] band_colours[b][rgb];
+ *                      255 / max(red, max(blue, green)) times each, truncated to a byte, alpha 255; then each byte a + (key - a) t with
+ *                      t = 1 - (float) frequency_colouring_blend, truncated.  A silent column is 255 / 0 * 0, a NaN, which converts to 0
+ *                      there: the column is (0, 0, 0, 255) before the lerp.  The scope's one-pole smoothing between columns is host arithmetic
+ *                      on the readout and not part of this.  SGZ_EINVAL: a null argument, channel >= channels. */
+typedef struct sgz_band_filter {
+    double   c[4][5];   /* {b0, b1, b2, a1, a2} of lp1, hp1, lp2, hp2 (a0 = 1) */
+    uint32_t W;         /* memory in samples, a power of two */
+    uint32_t L;         /* segment length, a power of two, 16 <= L <= W <= 65536 */
+} sgz_band_filter;         /* 168 bytes */
+typedef struct sgz_band_record {
+    uint64_t sumsq[3][2];  /* the sums of q^2 over the column of low, mid, high: unsigned 128-bit, low word first */
+    uint32_t count;        /* the column's non-NaN samples */
+    uint32_t reserved[3];  /* written as 0 */
+} sgz_band_record;         /* 64 bytes */
+sgz_status sgz_stage_band_columns(const float *d_planar, size_t channel_stride, uint32_t channels, size_t nsamples, const sgz_band_filter *filter,
+                                  uint64_t first_index, uint32_t m, uint32_t held, int flush, uint32_t continued, uint32_t slices, void *d_carry,
+                                  sgz_band_record *d_records /*[columns][channels]*/, void *stream);
+sgz_status sgz_band_columns_limits(const sgz_band_filter *filter, uint32_t channels, uint32_t *switch_over, uint32_t *tile_samples,
+                                   size_t *carry_bytes);
+sgz_status sgz_band_filter_for_rate(double rate, double low_hz, double high_hz, sgz_band_filter *f);
+sgz_status sgz_band_taps(const sgz_band_filter *f, int32_t *taps /*[16][W]*/);
+sgz_status sgz_band_fold(const sgz_band_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns, sgz_band_record *out);
+sgz_status sgz_band_readout(const sgz_band_record *recs, size_t ncols, uint32_t channels, uint32_t channel, double *mean_square /*[3]*/,
+                            double *db /*[3]*/);
+sgz_status sgz_band_colours(const sgz_band_record *recs, size_t ncols, uint32_t channels, uint32_t channel, const float band_colours[3][3],
+                            const uint8_t key_rgba8[4], double frequency_colouring_blend, uint8_t *out_rgba8 /*[ncols][4]*/);
+sgz_status sgz_pcm_stream_set_band(sgz_pcm_stream *s, const sgz_band_filter *filter, uint32_t m /*0 = off*/,
+                                   sgz_band_record *out /*HOST [capacity][channels]*/, uint64_t capacity_columns);
+uint64_t   sgz_pcm_stream_band_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
+sgz_status sgz_pcm_stream_band_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
+sgz_status sgz_pcm_stream_flush_band(sgz_pcm_stream *s);
 
 /* The track lane: the tracker's curve over a file -- the reference's drawFrequencyTracking readout (SpectrumRendering.cpp:300-377, the
  * line-results branch) for every frame of a streamed file, in bounded memory.  sgz_spectrogram_track_device / _host want the whole file

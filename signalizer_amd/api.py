@@ -146,6 +146,17 @@ class LoudnessFilter(C.Structure):
 
 assert C.sizeof(LoudnessFilter) == 88
 
+# sgz_band_record: one per (column, channel) of the band lane, 64 bytes (sumsq[band]: unsigned 128-bit, low word first; low, mid, high)
+BAND_DTYPE = np.dtype([("sumsq", "<u8", (3, 2)), ("count", "<u4"), ("reserved", "<u4", (3,))])
+assert BAND_DTYPE.itemsize == 64
+
+
+class BandFilter(C.Structure):
+    _fields_ = [("c", (C.c_double * 5) * 4), ("W", C.c_uint32), ("L", C.c_uint32)]
+
+
+assert C.sizeof(BandFilter) == 168
+
 
 class LineGraphStyle(C.Structure):
     _fields_ = [("colour_one", (C.c_uint8 * 4) * NUM_GRAPHS), ("colour_two", (C.c_uint8 * 4) * NUM_GRAPHS), ("flood_alpha", C.c_float),
@@ -244,6 +255,8 @@ EXPORTS = [
     "sgz_pcm_stream_set_loudness", "sgz_pcm_stream_loudness_for", "sgz_pcm_stream_loudness_state", "sgz_pcm_stream_flush_loudness",
     "sgz_stage_field_columns", "sgz_field_columns_limits", "sgz_field_boundaries", "sgz_field_fold", "sgz_field_readout",
     "sgz_pcm_stream_set_field", "sgz_pcm_stream_field_for", "sgz_pcm_stream_field_state", "sgz_pcm_stream_flush_field",
+    "sgz_stage_band_columns", "sgz_band_columns_limits", "sgz_band_filter_for_rate", "sgz_band_taps", "sgz_band_fold", "sgz_band_readout",
+    "sgz_band_colours", "sgz_pcm_stream_set_band", "sgz_pcm_stream_band_for", "sgz_pcm_stream_band_state", "sgz_pcm_stream_flush_band",
 ]
 
 
@@ -496,8 +509,16 @@ def lib() -> C.CDLL:
     L.sgz_field_boundaries.restype = None
     L.sgz_field_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_field_readout.argtypes = [vp, C.POINTER(FieldReading)]
-    for lane in ("waveform", "level", "truepeak", "loudness", "field"):      # the five column lanes of the PCM stream: one set of calls each
-        getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, fp, u32, vp, u64] if lane == "loudness" else [vp, u32, vp, u64]
+    bp = C.POINTER(BandFilter)
+    L.sgz_stage_band_columns.argtypes = [vp, sz, u32, sz, bp, u64, u32, u32, C.c_int, u32, u32, vp, vp, vp]
+    L.sgz_band_columns_limits.argtypes = [bp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(sz)]
+    L.sgz_band_filter_for_rate.argtypes = [C.c_double, C.c_double, C.c_double, bp]
+    L.sgz_band_taps.argtypes = [bp, vp]
+    L.sgz_band_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
+    L.sgz_band_readout.argtypes = [vp, sz, u32, u32, vp, vp]
+    L.sgz_band_colours.argtypes = [vp, sz, u32, u32, vp, vp, C.c_double, vp]
+    for lane in ("waveform", "level", "truepeak", "loudness", "field", "band"):      # the six column lanes of the PCM stream: one set of calls each
+        getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, {"loudness": fp, "band": bp}[lane], u32, vp, u64] if lane in ("loudness", "band") else [vp, u32, vp, u64]
         getattr(L, f"sgz_pcm_stream_{lane}_for").argtypes = [vp, sz, C.c_int]
         getattr(L, f"sgz_pcm_stream_{lane}_for").restype = u64
         getattr(L, f"sgz_pcm_stream_{lane}_state").argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
@@ -1259,7 +1280,7 @@ class PcmStream:
         return (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
 
 
-    # the five column lanes (waveform, level, truepeak, loudness, field): one helper per kind of call, the lane's name picks the C call
+    # the six column lanes (waveform, level, truepeak, loudness, field, band): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
         if capacity_columns is None:
             capacity_columns = 0 if out is None else int(out.shape[0])
@@ -1367,6 +1388,25 @@ class PcmStream:
     def flush_field(self) -> None:
         """sgz_pcm_stream_flush_field: closes the open column (one more record per pair at the cursor); waits"""
         self._lane_flush("field")
+
+    # the band lane: one sgz_band_record per column of m >= 64 samples and channel, beside whatever the feeds render
+    def set_band(self, filter, m: int, out=None, capacity_columns: int | None = None) -> None:
+        """sgz_pcm_stream_set_band: filter -- a BandFilter (None allowed with m == 0); out -- a BAND_DTYPE numpy array [capacity, channels] or a
+        host torch uint8 tensor [capacity, channels, 64] (kept alive here; pinned memory is written in place); m == 0 disarms, 0 < m < 64 is
+        refused"""
+        self._lane_set("band", m, out, capacity_columns, C.byref(filter) if filter is not None else None)
+
+    def band_for(self, nsamples: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_band_for: band columns the next feed of nsamples closes"""
+        return self._lane_for("band", nsamples, flush)
+
+    def band_state(self):
+        """sgz_pcm_stream_band_state: (columns written since the lane was armed, samples of the open column)"""
+        return self._lane_state("band")
+
+    def flush_band(self) -> None:
+        """sgz_pcm_stream_flush_band: closes the open column (one more record per channel at the cursor); waits"""
+        self._lane_flush("band")
 
     # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
     def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:
@@ -1601,6 +1641,79 @@ def loudness_integrated(records: np.ndarray, weights=None) -> float:
     l = C.c_double(0)
     check(lib().sgz_loudness_integrated(_np_ptr(records), n, channels, _np_ptr(w) if w is not None else None, C.byref(l)))
     return l.value
+
+
+def band_filter_for_rate(rate: float, low_hz: float = 300.0, high_hz: float = 3000.0) -> BandFilter:
+    """sgz_band_filter_for_rate: the Oscilloscope's crossover at `rate`, W = the smallest power of two >= 6 rate / low_hz, L = W / 16"""
+    f = BandFilter()
+    check(lib().sgz_band_filter_for_rate(float(rate), float(low_hz), float(high_hz), C.byref(f)))
+    return f
+
+
+def band_filter(c, W: int, L: int) -> BandFilter:
+    """a BandFilter of any coefficients: c [4][5] = {b0, b1, b2, a1, a2} of lp1, hp1, lp2, hp2"""
+    f = BandFilter()
+    for s in range(4):
+        for i in range(5):
+            f.c[s][i] = float(c[s][i])
+    f.W, f.L = W, L
+    return f
+
+
+def band_taps(f: BandFilter):
+    """sgz_band_taps: (status, the normative table int32 [16, W] or None)"""
+    taps = np.full((16, max(int(f.W), 1)), 0x5A5A5A5A, np.int32)
+    st = lib().sgz_band_taps(C.byref(f), _np_ptr(taps))
+    return st, (taps if st == SGZ_OK else None)
+
+
+def band_columns_limits(f: BandFilter, channels: int = 1):
+    """sgz_band_columns_limits: (the column sums' switch-over, the run tile's samples, the carry's bytes for `channels` channels)"""
+    s, t, b = C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+    check(lib().sgz_band_columns_limits(C.byref(f), channels, C.byref(s), C.byref(t), C.byref(b)))
+    return int(s.value), int(t.value), int(b.value)
+
+
+def stage_band_columns(planar, channel_stride: int, channels: int, nsamples: int, filter, first_index: int, m: int, held: int = 0,
+                       flush: bool = True, continued: bool = False, slices: int = 0, carry=None, records=None, stream=None) -> int:
+    """sgz_stage_band_columns as it is: planar / carry / records -- cuda tensors (their data pointers; any may be None where the call allows
+    NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    return lib().sgz_stage_band_columns(ptr(planar), channel_stride, channels, nsamples, C.byref(filter) if filter is not None else None, first_index,
+                                        m, held, int(bool(flush)), int(bool(continued)), slices, ptr(carry), ptr(records), C.c_void_p(s) if s else None)
+
+
+def band_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_band_fold: BAND_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels]"""
+    records = np.ascontiguousarray(records, BAND_DTYPE)
+    n, channels = records.shape
+    x1 = n if x1 is None else x1
+    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), BAND_DTYPE)
+    check(lib().sgz_band_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
+    return out[:min(out_columns, x1 - x0)]
+
+
+def band_readout(records: np.ndarray, channel: int = 0):
+    """sgz_band_readout of BAND_DTYPE records [ncols, channels] of one channel read together: (mean squares float64 [3], dB float64 [3])"""
+    records = np.ascontiguousarray(records, BAND_DTYPE)
+    ncols, channels = records.shape
+    ms, db = np.zeros(3, np.float64), np.zeros(3, np.float64)
+    check(lib().sgz_band_readout(_np_ptr(records), ncols, channels, channel, _np_ptr(ms), _np_ptr(db)))
+    return ms, db
+
+
+def band_colours(records: np.ndarray, channel: int, band_colours, key_rgba8, frequency_colouring_blend: float) -> np.ndarray:
+    """sgz_band_colours of BAND_DTYPE records [ncols, channels]: uint8 [ncols, 4], the Oscilloscope's colour of every column of `channel`;
+    band_colours float32 [3][3] (band, rgb), key_rgba8 the channel's key colour"""
+    records = np.ascontiguousarray(records, BAND_DTYPE)
+    ncols, channels = records.shape
+    bc = np.ascontiguousarray(band_colours, np.float32).reshape(3, 3)
+    key = np.ascontiguousarray(key_rgba8, np.uint8).reshape(4)
+    out = np.zeros((ncols, 4), np.uint8)
+    check(lib().sgz_band_colours(_np_ptr(records), ncols, channels, channel, _np_ptr(bc), _np_ptr(key), float(frequency_colouring_blend), _np_ptr(out)))
+    return out
 
 
 def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,

@@ -1,0 +1,780 @@
+// band_columns.hip -- the band lane's reduction: one sgz_band_record (the sums of the squared low, mid and high band samples, the count) per
+// column of m samples and channel of a linear planar stream, with a carried open column and a carried sample history (sgz.h, "The band
+// lane"); and the lane's host helpers: the Oscilloscope's crossover of a sample rate, the tap table, the fold of kept records, the readout of
+// a run of columns and the colours the Oscilloscope draws them with.  gfx950 only.  The reference's counterpart is live
+// (StreamState::audioProcessing; scope_stream.hip scopeIngestKernel phase F); this is the same network per column of a file.
+//   The loudness lane's formulation (loudness_columns.hip) with another filter: v = (int32) clamp(rintf(x 2^23), +-2^26), a NaN is v = 0 and
+//   is not counted.  The sample axis is cut into segments of L samples on an absolute grid.  The 16 state components of the crossover tree at
+//   a segment's start are exact integer FIRs over the last W quantised samples (taps at 2^30, 64-bit sums, any order), converted to fp64
+//   once; from there the fp64 recurrence of the eight sections runs over the segment's L samples in one fixed order with no contraction (the
+//   pragma below, for host and device alike).  q_b = rint(z_b) clamped to 32 bits for the three bands, the record sums q_b^2 in 128 bits.
+// Three steps, each a launch of its own behind the other (no hand-off between workgroups inside a launch):
+//   bandRunKernel       one workgroup per (tile of T = max(4096, L) samples on the segment grid, channel).  The tile goes to LDS quantised,
+//                       behind a W-sample halo, as the loudness lane's.  Segment-start dot products: the 256 lanes are T / L segments x P
+//                       lanes; the 16 components are taken four at a time (one 16-byte row C[g][k][0..3] and one sample per four
+//                       multiply-adds), a lane walks taps k = sub, sub + P, ..; the P partial sums are folded by wave shuffles (through LDS
+//                       where P > 64).  The runs: the tree is three independent chains -- lp1a lp1b (low); hp1a hp1b lp2a lp2b (mid); hp1a
+//                       hp1b hp2a hp2b (high) -- and a lane runs one chain of one segment; the two copies of hp1a hp1b perform the same
+//                       operations on the same values, so `rest` is the same bits in both.  A chain's state lives in LDS between rounds of
+//                       kBdStage / segments steps: a round leaves its q in three staging planes, which the workgroup then stores in rows to
+//                       stream-ordered scratch [3][channels][n].  A segment that began before the call is re-run from its start out of the
+//                       history; its earlier samples are not stored.
+//   bandHistoryKernel   the new carry but for an open column: the last W + L - 1 quantised samples of (the old history, the call).  (The
+//                       loudness lane's kernel is not reused: its record is 32 bytes and its parameter block its own.)
+//   the column sums     of the three q^2 and of the non-NaN samples in one pass over the planes, in the level lane's structure: m <=
+//                       kBdSwitch (1024) bandSumTileKernel; longer columns or slices >= 2 bandSumSliceKernel into partial records
+//                       [slices][columns][channels] + bandEmitKernel.  A flush without samples is the emit kernel alone, on the carry.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <mutex>
+#include <vector>
+
+#include "runtime.hpp"
+#include "scope_ring.hpp"      // StreamScratch
+
+// The definition's step is one IEEE operation per *, + and -: nothing in this file may be contracted into an FMA, on the host (the tap table,
+// the colours) or on the device (the segment runs).  hipcc contracts by default.
+#pragma clang fp contract(off)
+
+using namespace sgz;
+
+namespace {
+
+constexpr int kBdThreads = 256;
+constexpr uint32_t kBdTile = 4096;               // samples of a run tile (a segment longer than this is a tile of its own) and of a sum tile
+constexpr uint32_t kBdSwitch = 1024;             // the switch-over of the column sums: longer columns take the sliced form
+constexpr uint32_t kBdStage = 1024;              // samples of a tile that one round of the runs leaves in the staging planes
+constexpr uint32_t kBdMaxSlices = 64, kBdMaxChannels = 64;
+constexpr uint32_t kBdMaxW = 65536, kBdMinL = 16;
+constexpr uint32_t kBdDeviceMaxW = 16384;        // the halo and a tile fit the 160 KiB of LDS up to here
+constexpr uint32_t kBdBatch = 8;                 // loads a lane of the run kernel issues before it uses the first
+constexpr uint32_t kBdRun = 16;                  // samples of a lane in the sum tile
+constexpr uint32_t kBdComps = 16, kBdChainWords = 20;      // state components; doubles of a segment's three chains in LDS (4 + 8 + 8)
+constexpr double kBdTapScale = 1073741824.0;     // S = 30
+constexpr uint64_t kBdTapSumBound = uint64_t(1) << 36;     // 2^26 sum |C| < 2^62
+static_assert(sizeof(sgz_band_record) == 64 && sizeof(sgz_band_filter) == 168, "sgz.h documents 64 and 168 bytes");
+
+// ---- the definition's step and the tap table (host) -----------------------------------------------------------------------------------------
+struct BdCoef { double c[4][5]; };               // {b0, b1, b2, a1, a2} of lp1, hp1, lp2, hp2
+
+// one section, transposed direct form II (every operation on its own: see the pragma above)
+__host__ __device__ __forceinline__ double bdSection(const double *c, double &z0, double &z1, double x)
+{
+    const double y = c[0] * x + z0;
+    z0 = (c[1] * x - c[3] * y) + z1;
+    z1 = c[2] * x - c[4] * y;
+    return y;
+}
+
+// the tree on the definition's 16 components; bands = {low, mid, high}
+void bdTree(const BdCoef &f, double *z, double x, double *bands)
+{
+    const double low = bdSection(f.c[0], z[2], z[3], bdSection(f.c[0], z[0], z[1], x));
+    const double rest = bdSection(f.c[1], z[6], z[7], bdSection(f.c[1], z[4], z[5], x));
+    bands[0] = low;
+    bands[1] = bdSection(f.c[2], z[10], z[11], bdSection(f.c[2], z[8], z[9], rest));
+    bands[2] = bdSection(f.c[3], z[14], z[15], bdSection(f.c[3], z[12], z[13], rest));
+}
+
+BdCoef coefOf(const sgz_band_filter &f)
+{
+    BdCoef c;
+    for (int s = 0; s < 4; ++s)
+        for (int i = 0; i < 5; ++i) c.c[s][i] = f.c[s][i];
+    return c;
+}
+
+bool pow2(uint32_t v) { return v && !(v & (v - 1)); }
+
+bool shapeOk(const sgz_band_filter &f) { return pow2(f.W) && pow2(f.L) && f.L >= kBdMinL && f.L <= f.W && f.W <= kBdMaxW; }
+
+// C[c][k] at taps[c * W + k]; false where the filter is refused
+bool buildTaps(const sgz_band_filter &f, int32_t *taps)
+{
+    if (!shapeOk(f)) return false;
+    const BdCoef c = coefOf(f);
+    double z[kBdComps] = {}, bands[3];
+    uint64_t sum[kBdComps] = {};
+    for (uint32_t k = 0; k < f.W; ++k) {
+        bdTree(c, z, k == 0 ? 1.0 : 0.0, bands);
+        for (uint32_t q = 0; q < kBdComps; ++q) {
+            const double t = std::nearbyint(kBdTapScale * z[q]);           // (round to nearest even: the default mode; the scale is exact)
+            if (!(t >= -2147483648.0 && t <= 2147483647.0)) return false;  // (a NaN fails too)
+            const int32_t v = int32_t(t);
+            taps[size_t(q) * f.W + k] = v;
+            sum[q] += uint64_t(v < 0 ? -int64_t(v) : int64_t(v));
+        }
+    }
+    return *std::max_element(sum, sum + kBdComps) < kBdTapSumBound;
+}
+
+// ---- the table on the device: one per (device, filter), made at the filter's first use and kept ----------------------------------------------
+struct DeviceTaps { int dev; sgz_band_filter f; int4 *d; };
+std::mutex g_tapsMutex;
+std::vector<DeviceTaps> g_taps;
+
+// rows C[g][k][0..3] of 16 bytes, g = 0 .. 3 the four components 4 g .. 4 g + 3; the first use of a filter on a device uploads them (the one
+// blocking step of the stage call)
+sgz_status deviceTaps(const sgz_band_filter &f, const int4 **out)
+{
+    int dev = 0;
+    SGZ_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_tapsMutex);
+    for (const DeviceTaps &t : g_taps)
+        if (t.dev == dev && std::memcmp(&t.f, &f, sizeof f) == 0) { *out = t.d; return SGZ_OK; }
+    std::vector<int32_t> planes(size_t(kBdComps) * f.W), rows(size_t(kBdComps) * f.W);
+    if (!buildTaps(f, planes.data())) return fail(SGZ_EINVAL, "band: the filter is refused (sgz_band_taps)");
+    for (uint32_t g = 0; g < 4; ++g)
+        for (uint32_t k = 0; k < f.W; ++k)
+            for (uint32_t q = 0; q < 4; ++q) rows[(size_t(g) * f.W + k) * 4 + q] = planes[size_t(g * 4 + q) * f.W + k];
+    DeviceTaps t{dev, f, nullptr};
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&t.d), rows.size() * sizeof(int32_t)));
+    if (const hipError_t e = hipMemcpy(t.d, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice); e != hipSuccess) {
+        (void)hipFree(t.d);
+        return hipFail(e, "hipMemcpy(band taps)");
+    }
+    g_taps.push_back(t);
+    *out = t.d;
+    return SGZ_OK;
+}
+
+// ---- the kernels ------------------------------------------------------------------------------------------------------------------------------
+struct BandParams {
+    const float *planar;                 // [channels][stride]
+    size_t stride;
+    long n;
+    long columns, closed;                // columns this call touches; the first `closed` of them are emitted, a last open one goes to carryOut
+    uint32_t m, held, channels;
+    uint32_t continued;                  // the history in carryIn holds the samples before this call (else zeros)
+    uint32_t W, L, logL, hist;           // hist = W + L - 1
+    uint32_t tileWords;                  // LDS words of the halo and the tile, padding included
+    uint32_t tile, segs, logSegs, lanesPer;  // the run tile: T samples = segs segments, lanesPer = 256 / segs lanes per segment in the dot products
+    uint32_t stage, perRound, logRound, rounds;  // a round: perRound = stage / segs steps of every segment; rounds = L / perRound
+    uint32_t phase;                      // first_index % L: the call's first sample within its segment
+    uint32_t perTile, group, slices;     // the column sums, as the loudness lane's
+    BdCoef coef;
+    const int4 *taps;                    // [4][W]: C[g][k][0..3]
+    const uint8_t *carryIn;              // [channels][carryBytes]: the open column, then the history (oldest first), then a zero word
+    uint8_t *carryOut;
+    size_t carryBytes;
+    int32_t *q;                          // [3][channels][qStride]: q of the call's samples, low, mid, high
+    size_t qStride;
+    sgz_band_record *out;                // [closed][channels]
+    sgz_band_record *partial;            // [slices][columns][channels]
+};
+
+__device__ __forceinline__ const sgz_band_record *carryOpen(const uint8_t *carry, size_t bytes, uint32_t ch)
+{
+    return reinterpret_cast<const sgz_band_record *>(carry + size_t(ch) * bytes);
+}
+__device__ __forceinline__ const int32_t *carryHist(const uint8_t *carry, size_t bytes, uint32_t ch)
+{
+    return reinterpret_cast<const int32_t *>(carry + size_t(ch) * bytes + sizeof(sgz_band_record));
+}
+
+// the quantiser, 0 for a NaN (x 2^23 is exact or overflows to an infinity, which the clamp takes)
+__device__ __forceinline__ int32_t quantise(float x)
+{
+    const float r = __builtin_amdgcn_fmed3f(rintf(x * 0x1p23f), -0x1p26f, 0x1p26f);
+    return x != x ? 0 : int32_t(r);
+}
+
+// what the filter sees at sample r of the call, r >= -hist: the call's own sample, the carried history in front of it, zeros behind the call
+__device__ __forceinline__ int32_t filterInput(const BandParams &prm, uint32_t ch, long r)
+{
+    if (r >= prm.n) return 0;
+    if (r >= 0) return quantise(prm.planar[size_t(ch) * prm.stride + size_t(r)]);
+    return prm.continued ? carryHist(prm.carryIn, prm.carryBytes, ch)[long(prm.hist) + r] : 0;
+}
+
+// LDS word of the tile's sample index i (0 = the halo's first): a shift of lanesPer words per segment keeps the segments' lanes on different banks
+__device__ __forceinline__ uint32_t bdWord(const BandParams &prm, uint32_t i) { return i + (i >> prm.logL) * prm.lanesPer; }
+
+// component c of segment seg's start state into the chains' words: [0..3] lp1a lp1b; [4..11] hp1a hp1b lp2a lp2b; [12..19] hp1a hp1b hp2a hp2b
+__device__ __forceinline__ void putStart(double *chains, uint32_t seg, uint32_t c, double v)
+{
+    double *s = chains + size_t(seg) * kBdChainWords;
+    if (c < 4u) s[c] = v;
+    else if (c < 8u) { s[c] = v; s[c + 8u] = v; }
+    else if (c < 12u) s[c] = v;
+    else s[c + 4u] = v;
+}
+
+__global__ void __launch_bounds__(kBdThreads)
+bandRunKernel(const BandParams prm)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];
+    // [segs][20] the chains' states, the tile, and one block that is first -- only where a segment's lanes are more than a wave -- [256][4]
+    // partial dot products and then the three staging planes [3][stage + segs]
+    double *chains = reinterpret_cast<double *>(ldsRaw);
+    int32_t *tile = reinterpret_cast<int32_t *>(ldsRaw + size_t(prm.segs) * kBdChainWords * 8);
+    unsigned char *shared = ldsRaw + size_t(prm.segs) * kBdChainWords * 8 + size_t(prm.tileWords) * 4;
+    long long *part = reinterpret_cast<long long *>(shared);
+    int32_t *staged = reinterpret_cast<int32_t *>(shared);
+    const uint32_t tid = threadIdx.x, ch = blockIdx.y;
+    const long r0 = long(blockIdx.x) * long(prm.tile) - long(prm.phase);               // the tile's first sample, on the segment grid (>= -(L - 1))
+    // 1. the halo and the tile, quantised
+    const uint32_t words = prm.W + prm.tile;
+    for (uint32_t base = tid; base < words; base += kBdBatch * kBdThreads) {             // (kBdBatch loads of a lane in flight together)
+        int32_t v[kBdBatch];
+#pragma unroll
+        for (uint32_t j = 0; j < kBdBatch; ++j) {
+            const uint32_t i = base + j * kBdThreads;
+            v[j] = i < words ? filterInput(prm, ch, r0 - long(prm.W) + long(i)) : 0;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kBdBatch; ++j) {
+            const uint32_t i = base + j * kBdThreads;
+            if (i < words) tile[bdWord(prm, i)] = v[j];
+        }
+    }
+    __syncthreads();
+    // 2. the dot products, four components at a time: lane (seg, sub) takes taps sub, sub + lanesPer, .. of its segment
+    const uint32_t seg = tid / prm.lanesPer, sub = tid % prm.lanesPer;
+    const bool live = r0 + long(seg) * long(prm.L) < prm.n;                             // (a segment behind the call's last sample is not run)
+    const uint32_t before = prm.W + seg * prm.L - 1u;                                   // the sample in front of the segment's first
+    for (uint32_t g = 0; g < 4u; ++g) {
+        const int4 *taps = prm.taps + size_t(g) * prm.W;
+        long long acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+        if (live) {
+            // (a lane's taps, W / lanesPer of them, are a power of two >= 16: kBdBatch at a time, their loads in flight together)
+            for (uint32_t k = sub; k < prm.W; k += kBdBatch * prm.lanesPer) {
+                int4 c[kBdBatch];
+                int32_t v[kBdBatch];
+#pragma unroll
+                for (uint32_t j = 0; j < kBdBatch; ++j) {
+                    c[j] = taps[k + j * prm.lanesPer];
+                    v[j] = tile[bdWord(prm, before - (k + j * prm.lanesPer))];
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < kBdBatch; ++j) {
+                    acc0 += (long long)c[j].x * v[j]; acc1 += (long long)c[j].y * v[j];
+                    acc2 += (long long)c[j].z * v[j]; acc3 += (long long)c[j].w * v[j];
+                }
+            }
+        }
+        // the fold of a segment's lanes, integer adds in any order; then one rounding to nearest even and an exact scale
+        if (prm.lanesPer <= 64u) {                                                      // (inside a wave: every lane takes the same trips)
+            for (uint32_t o = prm.lanesPer >> 1; o > 0; o >>= 1) {
+                acc0 += __shfl_xor(acc0, int(o)); acc1 += __shfl_xor(acc1, int(o)); acc2 += __shfl_xor(acc2, int(o)); acc3 += __shfl_xor(acc3, int(o));
+            }
+            if (sub == 0) {
+                putStart(chains, seg, g * 4u + 0u, double(acc0) * 0x1p-30); putStart(chains, seg, g * 4u + 1u, double(acc1) * 0x1p-30);
+                putStart(chains, seg, g * 4u + 2u, double(acc2) * 0x1p-30); putStart(chains, seg, g * 4u + 3u, double(acc3) * 0x1p-30);
+            }
+        } else {                                                                        // (a segment of 2048 samples or more: its lanes are 2 or 4 waves)
+            part[tid * 4 + 0] = acc0; part[tid * 4 + 1] = acc1; part[tid * 4 + 2] = acc2; part[tid * 4 + 3] = acc3;
+            __syncthreads();
+            for (uint32_t e = tid; e < prm.segs * 4u; e += kBdThreads) {
+                const uint32_t s = e >> 2, c = e & 3u;
+                long long sum = 0;
+                for (uint32_t j = 0; j < prm.lanesPer; ++j) sum += part[(s * prm.lanesPer + j) * 4 + c];
+                putStart(chains, s, g * 4u + c, double(sum) * 0x1p-30);
+            }
+            __syncthreads();                                                            // (the next four components, then the staging planes, reuse `part`)
+        }
+    }
+    __syncthreads();
+    // 3. the runs, in rounds of perRound steps: job (chain, segment) loads its chain's state, runs the steps in the definition's order, leaves
+    // q in its staging plane and the state where it was; then the workgroup stores the round's q of the call's own samples in rows
+    // (a workgroup's wave w always lands on SIMD w of its CU: which waves take the first jobs rotates with the workgroup)
+    const uint32_t jobs = 3u * prm.segs, plane = prm.stage + prm.segs;                  // (a staging plane: one pad word per segment against bank conflicts)
+    const uint32_t firstJob = (tid + uint32_t(kBdThreads) - ((blockIdx.x + blockIdx.y) & 3u) * 64u) & uint32_t(kBdThreads - 1);
+    const size_t qPlane = size_t(prm.channels) * prm.qStride;
+    int32_t *q = prm.q + size_t(ch) * prm.qStride;
+    for (uint32_t rd = 0; rd < prm.rounds; ++rd) {
+        for (uint32_t job = firstJob; job < jobs; job += kBdThreads) {
+            const uint32_t chain = job >> prm.logSegs, s = job & (prm.segs - 1u);
+            const long left = prm.n - (r0 + long(s) * long(prm.L));
+            const uint32_t steps = left <= 0 ? 0u : left < long(prm.L) ? uint32_t(left) : prm.L;
+            const uint32_t j0 = rd * prm.perRound, j1 = j0 + prm.perRound < steps ? j0 + prm.perRound : steps;
+            if (j0 >= j1) continue;
+            double a[5], b[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                a[i] = chain == 0u ? prm.coef.c[0][i] : prm.coef.c[1][i];
+                b[i] = chain == 1u ? prm.coef.c[2][i] : prm.coef.c[3][i];
+            }
+            double *st = chains + size_t(s) * kBdChainWords + (chain == 0u ? 0u : chain == 1u ? 4u : 12u);
+            double z0 = st[0], z1 = st[1], z2 = st[2], z3 = st[3], z4 = 0.0, z5 = 0.0, z6 = 0.0, z7 = 0.0;
+            if (chain) { z4 = st[4]; z5 = st[5]; z6 = st[6]; z7 = st[7]; }
+            const int32_t *in = tile + bdWord(prm, prm.W + s * prm.L);                   // (a segment's words are consecutive: j < L)
+            int32_t *to = staged + chain * plane + s * (prm.perRound + 1u);
+            for (uint32_t j = j0; j < j1; ++j) {
+                double y = bdSection(a, z2, z3, bdSection(a, z0, z1, double(in[j])));
+                if (chain) y = bdSection(b, z6, z7, bdSection(b, z4, z5, y));
+                to[j - j0] = int32_t(__builtin_fmin(__builtin_fmax(__builtin_rint(y), -2147483647.0), 2147483647.0));
+            }
+            st[0] = z0; st[1] = z1; st[2] = z2; st[3] = z3;
+            if (chain) { st[4] = z4; st[5] = z5; st[6] = z6; st[7] = z7; }
+        }
+        __syncthreads();
+        for (uint32_t e = tid; e < prm.stage; e += kBdThreads) {
+            const uint32_t s = e >> prm.logRound, j = e & (prm.perRound - 1u);
+            const long r = r0 + long(s) * long(prm.L) + long(rd * prm.perRound + j);
+            if (r >= 0 && r < prm.n) {
+#pragma unroll
+                for (uint32_t b = 0; b < 3u; ++b) q[size_t(b) * qPlane + size_t(r)] = staged[b * plane + e + s];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// the carry of a call with samples but for an open column's record: the history, the zero word behind it, an all-zero open column (an open
+// column's record is stored by the sums' launch behind this one)
+__global__ void __launch_bounds__(kBdThreads)
+bandHistoryKernel(const BandParams prm)
+{
+    const uint32_t t = blockIdx.x * kBdThreads + threadIdx.x, ch = blockIdx.y;
+    uint8_t *mine = prm.carryOut + size_t(ch) * prm.carryBytes;
+    int32_t *hist = reinterpret_cast<int32_t *>(mine + sizeof(sgz_band_record));
+    if (t < prm.hist) hist[t] = filterInput(prm, ch, prm.n - long(prm.hist) + long(t));
+    if (t == prm.hist) hist[t] = 0;
+    if (t < sizeof(sgz_band_record) / 4) reinterpret_cast<uint32_t *>(mine)[t] = 0u;
+}
+
+// a column's, a lane's or a slice's part of a record: three 128-bit sums of q^2 and the count
+struct BdAcc {
+    uint64_t lo[3], hi[3];
+    uint32_t count;
+    __device__ __forceinline__ void addSquare(int b, int32_t q)
+    {
+        const uint64_t s = uint64_t(int64_t(q) * int64_t(q));
+        lo[b] += s;
+        hi[b] += lo[b] < s ? 1u : 0u;
+    }
+    __device__ __forceinline__ void add(int b, uint64_t l, uint64_t h)
+    {
+        lo[b] += l;
+        hi[b] += h + (lo[b] < l ? 1u : 0u);
+    }
+    __device__ __forceinline__ void add(const sgz_band_record &r)
+    {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) add(b, r.sumsq[b][0], r.sumsq[b][1]);
+        count += r.count;
+    }
+    __device__ __forceinline__ void foldLane(int o)
+    {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) add(b, __shfl_xor((unsigned long long)lo[b], o), __shfl_xor((unsigned long long)hi[b], o));
+        count += __shfl_xor(count, o);
+    }
+    __device__ __forceinline__ void store(sgz_band_record *to) const
+    {
+        sgz_band_record r;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) { r.sumsq[b][0] = lo[b]; r.sumsq[b][1] = hi[b]; }
+        r.count = count; r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
+        *to = r;
+    }
+};
+
+// samples [a, b) of this call that belong to column `col`
+__device__ __forceinline__ void columnSamples(const BandParams &prm, long col, long &a, long &b)
+{
+    a = col * long(prm.m) - long(prm.held);
+    b = a + long(prm.m);
+    a = a < 0 ? 0 : a;
+    b = b > prm.n ? prm.n : b;
+}
+
+__device__ __forceinline__ void takeSample(const BandParams &prm, uint32_t ch, long r, BdAcc &k)
+{
+    const size_t plane = size_t(prm.channels) * prm.qStride, at = size_t(ch) * prm.qStride + size_t(r);
+    k.addSquare(0, prm.q[at]);
+    k.addSquare(1, prm.q[plane + at]);
+    k.addSquare(2, prm.q[2 * plane + at]);
+    const float x = prm.planar[size_t(ch) * prm.stride + size_t(r)];
+    k.count += x != x ? 0u : 1u;
+}
+
+// the carry into column 0, then to the output (a closed column) or to the carry's open column
+__device__ __forceinline__ void emitColumn(const BandParams &prm, long col, uint32_t ch, BdAcc k)
+{
+    if (col == 0 && prm.held) k.add(*carryOpen(prm.carryIn, prm.carryBytes, ch));
+    k.store(col < prm.closed ? prm.out + size_t(col) * prm.channels + ch
+                             : reinterpret_cast<sgz_band_record *>(prm.carryOut + size_t(ch) * prm.carryBytes));
+}
+
+// workgroup (tile of perTile whole columns, channel): groups of prm.group lanes per column, the lanes of a group stride over its samples
+__global__ void __launch_bounds__(kBdThreads)
+bandSumTileKernel(const BandParams prm)
+{
+    const uint32_t tid = threadIdx.x, ch = blockIdx.y;
+    const long c0 = long(blockIdx.x) * long(prm.perTile);
+    const long c1 = c0 + long(prm.perTile) < prm.columns ? c0 + long(prm.perTile) : prm.columns;
+    const uint32_t G = prm.group, sub = tid & (G - 1u), grp = tid / G, groups = uint32_t(kBdThreads) / G;
+    const uint32_t cols = uint32_t(c1 - c0);
+    for (uint32_t base = 0; base < cols; base += groups) {                  // (the same trips in every lane: the cross-lane steps see whole waves)
+        const uint32_t lc = base + grp;
+        const bool mine = lc < cols;
+        BdAcc k{{0, 0, 0}, {0, 0, 0}, 0};
+        if (mine) {
+            long a, b;
+            columnSamples(prm, c0 + long(lc), a, b);
+            for (long r = a + long(sub); r < b; r += long(G)) takeSample(prm, ch, r, k);
+        }
+        for (uint32_t o = G >> 1; o > 0; o >>= 1) k.foldLane(int(o));
+        if (mine && sub == 0) emitColumn(prm, c0 + long(lc), ch, k);
+    }
+}
+
+// slice blockIdx.z of column blockIdx.x's samples of channel blockIdx.y (an empty slice leaves the zero record)
+__global__ void __launch_bounds__(kBdThreads)
+bandSumSliceKernel(const BandParams prm)
+{
+    __shared__ sgz_band_record waves[kBdThreads / 64];
+    const long col = long(blockIdx.x);
+    const uint32_t ch = blockIdx.y, s = blockIdx.z, tid = threadIdx.x;
+    long a, b;
+    columnSamples(prm, col, a, b);
+    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
+    const long sa = a + long(s) * per < b ? a + long(s) * per : b, sb = sa + per < b ? sa + per : b;
+    BdAcc k{{0, 0, 0}, {0, 0, 0}, 0};
+    for (long r = sa + long(tid); r < sb; r += long(kBdThreads)) takeSample(prm, ch, r, k);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) k.foldLane(o);
+    if ((tid & 63u) == 0) k.store(&waves[tid >> 6]);
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int v = 1; v < kBdThreads / 64; ++v) k.add(waves[v]);
+        k.store(prm.partial + (size_t(s) * size_t(prm.columns) + size_t(col)) * prm.channels + ch);
+    }
+}
+
+// one thread per (column, channel): the fold of the slices (none: a flush of the carry alone), the carry, the store
+__global__ void __launch_bounds__(kBdThreads)
+bandEmitKernel(const BandParams prm)
+{
+    const size_t at = size_t(blockIdx.x) * kBdThreads + threadIdx.x, perSlice = size_t(prm.columns) * prm.channels;
+    if (at >= perSlice) return;
+    const long col = long(at / prm.channels);
+    const uint32_t ch = uint32_t(at % prm.channels);
+    BdAcc k{{0, 0, 0}, {0, 0, 0}, 0};
+    for (uint32_t s = 0; s < prm.slices; ++s) k.add(prm.partial[size_t(s) * perSlice + at]);
+    emitColumn(prm, col, ch, k);
+}
+
+uint32_t pow2AtLeast(uint32_t v)
+{
+    uint32_t p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+
+uint32_t log2Of(uint32_t v)
+{
+    uint32_t l = 0;
+    while ((1u << l) < v) ++l;
+    return l;
+}
+
+uint32_t runTileOf(const sgz_band_filter &f) { return std::max(kBdTile, f.L); }
+size_t qStrideOf(size_t nsamples) { return (nsamples + 3) & ~size_t(3); }
+
+uint32_t runTileWords(const sgz_band_filter &f)
+{
+    const uint32_t tile = runTileOf(f), lanesPer = uint32_t(kBdThreads) / (tile / f.L);
+    return ((f.W + tile) + ((f.W + tile) / f.L + 1) * lanesPer + 3u) & ~3u;
+}
+
+// the chains' states, the halo and the tile, and the block the partial dot products and the staging planes share (at most 143 KiB of the
+// 160: W = 16384 with L = 16 or L = 16384)
+size_t runLdsBytes(const sgz_band_filter &f)
+{
+    const uint32_t tile = runTileOf(f), segs = tile / f.L, lanesPer = uint32_t(kBdThreads) / segs;
+    const size_t staged = size_t(3) * (kBdStage + segs) * 4, part = lanesPer > 64u ? size_t(kBdThreads) * 32 : 0;
+    return size_t(segs) * kBdChainWords * 8 + size_t(runTileWords(f)) * 4 + std::max(staged, part);
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: remember what has been granted
+sgz_status grantRunLds(size_t need)
+{
+    static size_t granted[64] = {};
+    static std::mutex mutex;
+    int dev = 0;
+    SGZ_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mutex);
+    if (dev >= 0 && dev < 64 && granted[dev] >= need) return SGZ_OK;
+    SGZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bandRunKernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(need)));
+    if (dev >= 0 && dev < 64) granted[dev] = need;
+    return SGZ_OK;
+}
+
+sgz_status filterForDevice(const sgz_band_filter *f, const char *who)
+{
+    if (!f) return fail(SGZ_EINVAL, std::string(who) + ": null filter");
+    if (!shapeOk(*f)) return fail(SGZ_EINVAL, std::string(who) + ": W and L are powers of two, 16 <= L <= W <= 65536");
+    if (f->W > kBdDeviceMaxW) return fail(SGZ_EINVAL, std::string(who) + ": the device takes W <= 16384");
+    return SGZ_OK;
+}
+
+}  // namespace
+
+namespace sgz {
+
+size_t bandCarryBytes(const sgz_band_filter &f) { return sizeof(sgz_band_record) + size_t(f.W + f.L) * sizeof(int32_t); }
+
+// The shape of a call whose arguments passed sgz_stage_band_columns' checks, as loudnessColumnsShape; scratchBytes: q [3][channels][n rounded
+// up to 4] and behind it the partial records of the sliced form.
+BandColumnsShape bandColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
+{
+    BandColumnsShape sh{};
+    const uint64_t t = uint64_t(held) + nsamples;
+    sh.closed = t / m + ((flush && t % m) ? 1u : 0u);
+    sh.open = !flush && t % m != 0;
+    sh.columns = sh.closed + (sh.open ? 1u : 0u);
+    sh.launch = sh.columns != 0 && !(nsamples == 0 && !(flush && held));
+    if (!sh.launch || nsamples == 0) return sh;
+    if (slices >= 2 || m > kBdSwitch) sh.slices = slices ? slices : overviewAutoSlices(long(sh.columns), channels, m, nsamples, numCUs());
+    sh.scratchBytes = size_t(3) * qStrideOf(nsamples) * channels * sizeof(int32_t) + size_t(sh.slices) * size_t(sh.columns) * channels * sizeof(sgz_band_record);
+    return sh;
+}
+
+// sgz_stage_band_columns behind its argument checks, with the carry in two places: carryIn is read (the history when `continued`, the open
+// column when held > 0), carryOut is written whole by every call with samples -- never the same memory then.  scratch: sh.scratchBytes bytes,
+// aligned to 16.
+sgz_status runBandColumns(const BandColumnsShape &sh, const sgz_band_filter &f, const float *d_planar, size_t channelStride, uint32_t channels,
+                          size_t nsamples, uint64_t firstIndex, uint32_t m, uint32_t held, uint32_t continued, const void *carryIn, void *carryOut,
+                          sgz_band_record *d_out, void *scratch, hipStream_t stream)
+{
+    if (!sh.launch) return SGZ_OK;
+    BandParams prm{};
+    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
+    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
+    prm.m = m; prm.held = held; prm.channels = channels; prm.continued = continued; prm.slices = sh.slices;
+    prm.W = f.W; prm.L = f.L; prm.logL = log2Of(f.L); prm.hist = f.W + f.L - 1;
+    prm.tile = runTileOf(f); prm.segs = prm.tile / f.L; prm.logSegs = log2Of(prm.segs); prm.lanesPer = uint32_t(kBdThreads) / prm.segs;
+    prm.stage = kBdStage; prm.perRound = kBdStage / prm.segs; prm.logRound = log2Of(prm.perRound); prm.rounds = f.L / prm.perRound;
+    prm.tileWords = runTileWords(f);
+    prm.phase = uint32_t(firstIndex % f.L);
+    prm.coef = coefOf(f);
+    prm.carryIn = static_cast<const uint8_t *>(carryIn); prm.carryOut = static_cast<uint8_t *>(carryOut);
+    prm.carryBytes = bandCarryBytes(f);
+    prm.q = static_cast<int32_t *>(scratch); prm.qStride = qStrideOf(nsamples);
+    prm.out = d_out;
+    prm.partial = reinterpret_cast<sgz_band_record *>(static_cast<uint8_t *>(scratch) + size_t(3) * prm.qStride * channels * sizeof(int32_t));
+    const uint64_t cells = sh.columns * channels;
+    if (sh.columns > 0x7fffffffull || (cells + kBdThreads - 1) / kBdThreads > 0x7fffffffull) return fail(SGZ_EINVAL, "band columns: too many columns for one launch");
+    if (nsamples != 0) {
+        if (sgz_status st = deviceTaps(f, &prm.taps); st != SGZ_OK) return st;
+        const uint64_t tiles = (uint64_t(nsamples) + prm.phase + prm.tile - 1) / prm.tile;
+        if (tiles > 0x7fffffffull) return fail(SGZ_EINVAL, "band columns: too many samples for one launch");
+        const size_t lds = runLdsBytes(f);
+        if (sgz_status st = grantRunLds(lds); st != SGZ_OK) return st;
+        hipLaunchKernelGGL(bandRunKernel, dim3(unsigned(tiles), channels), dim3(kBdThreads), lds, stream, prm);
+        SGZ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(bandHistoryKernel, dim3((prm.hist + 1 + kBdThreads - 1) / kBdThreads, channels), dim3(kBdThreads), 0, stream, prm);
+        SGZ_HIP(hipGetLastError());
+        if (sh.slices == 0) {
+            prm.perTile = kBdTile / m;
+            prm.group = std::min(pow2AtLeast((m + kBdRun - 1) / kBdRun), 64u);
+            const uint64_t sumTiles = (sh.columns + prm.perTile - 1) / prm.perTile;
+            hipLaunchKernelGGL(bandSumTileKernel, dim3(unsigned(sumTiles), channels), dim3(kBdThreads), 0, stream, prm);
+            SGZ_HIP(hipGetLastError());
+            return SGZ_OK;
+        }
+        hipLaunchKernelGGL(bandSumSliceKernel, dim3(unsigned(sh.columns), channels, sh.slices), dim3(kBdThreads), 0, stream, prm);
+        SGZ_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(bandEmitKernel, dim3(unsigned((cells + kBdThreads - 1) / kBdThreads)), dim3(kBdThreads), 0, stream, prm);
+    SGZ_HIP(hipGetLastError());
+    return SGZ_OK;
+}
+
+}  // namespace sgz
+
+extern "C" {
+
+sgz_status sgz_band_columns_limits(const sgz_band_filter *filter, uint32_t channels, uint32_t *switch_over, uint32_t *tile_samples, size_t *carry_bytes)
+{
+    if (sgz_status st = filterForDevice(filter, "sgz_band_columns_limits"); st != SGZ_OK) return st;
+    if (channels == 0 || channels > kBdMaxChannels) return fail(SGZ_EINVAL, "sgz_band_columns_limits: 1 .. 64 channels");
+    if (switch_over) *switch_over = kBdSwitch;
+    if (tile_samples) *tile_samples = runTileOf(*filter);
+    if (carry_bytes) *carry_bytes = bandCarryBytes(*filter) * channels;
+    return SGZ_OK;
+}
+
+sgz_status sgz_stage_band_columns(const float *d_planar, size_t channel_stride, uint32_t channels, size_t nsamples, const sgz_band_filter *filter,
+                                  uint64_t first_index, uint32_t m, uint32_t held, int flush, uint32_t continued, uint32_t slices, void *d_carry,
+                                  sgz_band_record *d_records, void *stream)
+{
+    if (!d_planar) return fail(SGZ_EINVAL, "sgz_stage_band_columns: null d_planar");
+    if (sgz_status st = filterForDevice(filter, "sgz_stage_band_columns"); st != SGZ_OK) return st;
+    if (channels == 0 || channels > kBdMaxChannels) return fail(SGZ_EINVAL, "sgz_stage_band_columns: 1 .. 64 channels");
+    if (m == 0) return fail(SGZ_EINVAL, "sgz_stage_band_columns: m >= 1 samples per column");
+    if (held >= m) return fail(SGZ_EINVAL, "sgz_stage_band_columns: held < m");
+    if (!continued && held) return fail(SGZ_EINVAL, "sgz_stage_band_columns: held > 0 needs continued != 0 (a stream that begins here has no open column)");
+    if (channel_stride < nsamples || nsamples > (size_t(1) << 40)) return fail(SGZ_EINVAL, "sgz_stage_band_columns: channel_stride < nsamples, or more than 2^40 samples");
+    if (first_index > (uint64_t(1) << 62)) return fail(SGZ_EINVAL, "sgz_stage_band_columns: first_index above 2^62");
+    if (slices > kBdMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_band_columns: slices 0 (automatic) or 1 .. 64");
+    if ((reinterpret_cast<uintptr_t>(d_planar) & 3u) || (reinterpret_cast<uintptr_t>(d_carry) & 15u) || (reinterpret_cast<uintptr_t>(d_records) & 15u))
+        return fail(SGZ_EINVAL, "sgz_stage_band_columns: d_planar aligned to 4 bytes, d_carry and d_records to 16");
+    const BandColumnsShape sh = bandColumnsShape(channels, nsamples, m, held, flush, slices);
+    if (!d_carry && (continued || nsamples)) return fail(SGZ_EINVAL, "sgz_stage_band_columns: d_carry is read (continued) or written (nsamples > 0)");
+    if (!d_records && sh.closed) return fail(SGZ_EINVAL, "sgz_stage_band_columns: d_records is written (a column closes)");
+    if (nsamples) {                                                  // (the table before anything is launched: a refused filter writes nothing)
+        const int4 *taps = nullptr;
+        if (sgz_status st = deviceTaps(*filter, &taps); st != SGZ_OK) return st;
+    }
+    if (!sh.launch) return SGZ_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    StreamScratch scratch(s), snapshot(s);
+    const void *carryIn = d_carry;
+    const size_t carryBytes = bandCarryBytes(*filter) * channels;
+    if (continued && nsamples) {
+        // the halos, the history and column 0 read the carry while other workgroups write the new one: they read a snapshot
+        SGZ_HIP(snapshot.get(carryBytes));
+        SGZ_HIP(hipMemcpyAsync(snapshot.p, d_carry, carryBytes, hipMemcpyDeviceToDevice, s));
+        carryIn = snapshot.p;
+    }
+    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
+    return runBandColumns(sh, *filter, d_planar, channel_stride, channels, nsamples, first_index, m, held, continued, carryIn, d_carry, d_records,
+                          scratch.p, s);
+}
+
+// ---- host arithmetic ---------------------------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// the Oscilloscope's second-order Butterworth section at the normalised frequency fn (cycles per sample), each coefficient rounded to float
+// as the live scope holds it
+void butterworthSection(double fn, bool highpass, double *c)
+{
+    const double w0 = 6.283185307179586476925286766559 * fn;
+    const double cw = std::cos(w0), alpha = std::sin(w0) / (2.0 * 0.70710678118654752440);
+    const double a0 = 1 + alpha;
+    const double b0 = highpass ? (1 + cw) / 2 : (1 - cw) / 2, b1 = highpass ? -(1 + cw) : 1 - cw;
+    c[0] = double(float(b0 / a0)); c[1] = double(float(b1 / a0)); c[2] = double(float(b0 / a0));
+    c[3] = double(float(-2 * cw / a0)); c[4] = double(float((1 - alpha) / a0));
+}
+
+unsigned __int128 sumOf(const sgz_band_record &v, int b) { return (static_cast<unsigned __int128>(v.sumsq[b][1]) << 64) | v.sumsq[b][0]; }
+
+// the mean squares (1.0 = full scale squared) of the three bands of `ncols` columns of one channel read together
+void bandMeanSquares(const sgz_band_record *recs, size_t ncols, uint32_t channels, uint32_t channel, double *ms)
+{
+    unsigned __int128 sum[3] = {0, 0, 0};
+    uint64_t count = 0;
+    for (size_t j = 0; j < ncols; ++j) {
+        const sgz_band_record &v = recs[j * channels + channel];
+        for (int b = 0; b < 3; ++b) sum[b] += sumOf(v, b);
+        count += v.count;
+    }
+    for (int b = 0; b < 3; ++b) ms[b] = count ? double(sum[b]) / double(count) * 0x1p-46 : 0.0;
+}
+
+// static_cast<uint8_t>(float) as the live scope's build performs it: truncation, 0 out of range and for a NaN
+uint8_t toU8(float v) { return (!(v > -1.0f) || !(v < 256.0f)) ? uint8_t(0) : uint8_t(v); }
+uint8_t lerpU8(uint8_t a, uint8_t b, float t) { return toU8(float(a) + (float(b) - float(a)) * t); }
+
+}  // namespace
+
+extern "C" {
+
+sgz_status sgz_band_filter_for_rate(double rate, double low_hz, double high_hz, sgz_band_filter *f)
+{
+    if (!f) return fail(SGZ_EINVAL, "sgz_band_filter_for_rate: null argument");
+    if (!(rate > 0.0) || !std::isfinite(rate)) return fail(SGZ_EINVAL, "sgz_band_filter_for_rate: rate > 0");
+    if (!(low_hz > 0.0) || !(high_hz > low_hz) || !(high_hz < rate / 2)) return fail(SGZ_EINVAL, "sgz_band_filter_for_rate: 0 < low_hz < high_hz < rate / 2");
+    const double need = std::ceil(6.0 * rate / low_hz);
+    if (!(need <= double(kBdMaxW))) return fail(SGZ_EINVAL, "sgz_band_filter_for_rate: 6 rate / low_hz above 65536 samples of memory");
+    sgz_band_filter r{};
+    const double f1 = double(float(low_hz / rate)), f2 = double(float(high_hz / rate));
+    butterworthSection(f1, false, r.c[0]); butterworthSection(f1, true, r.c[1]);
+    butterworthSection(f2, false, r.c[2]); butterworthSection(f2, true, r.c[3]);
+    r.W = std::max(pow2AtLeast(uint32_t(need)), 16u * kBdMinL);
+    r.L = r.W / 16;
+    *f = r;
+    return SGZ_OK;
+}
+
+sgz_status sgz_band_taps(const sgz_band_filter *f, int32_t *taps)
+{
+    if (!f || !taps) return fail(SGZ_EINVAL, "sgz_band_taps: null argument");
+    if (!shapeOk(*f)) return fail(SGZ_EINVAL, "sgz_band_taps: W and L are powers of two, 16 <= L <= W <= 65536");
+    std::vector<int32_t> t(size_t(kBdComps) * f->W);                // (a refusal writes nothing)
+    if (!buildTaps(*f, t.data())) return fail(SGZ_EINVAL, "sgz_band_taps: a tap outside int32, or 2^26 sum |C| >= 2^62");
+    std::memcpy(taps, t.data(), t.size() * sizeof(int32_t));
+    return SGZ_OK;
+}
+
+sgz_status sgz_band_fold(const sgz_band_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns, sgz_band_record *out)
+{
+    if (!in || !out) return fail(SGZ_EINVAL, "sgz_band_fold: null argument");
+    if (channels == 0) return fail(SGZ_EINVAL, "sgz_band_fold: channels >= 1");
+    uint64_t cols = 0;
+    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
+    const uint64_t w = x1 - x0;
+    auto bound = [&](uint64_t b) { return x0 + (b * w + cols - 1) / cols; };                   // (b w < 2^62: n < 2^31)
+    // the counts first: a refusal writes nothing
+    for (uint64_t b = 0; b < cols; ++b)
+        for (uint32_t c = 0; c < channels; ++c) {
+            uint64_t count = 0;
+            for (uint64_t j = bound(b); j < bound(b + 1); ++j) count += in[j * channels + c].count;
+            if (count > 0xffffffffull) return fail(SGZ_EINVAL, "sgz_band_fold: a folded column counts more than 2^32 - 1");
+        }
+    for (uint64_t b = 0; b < cols; ++b)
+        for (uint32_t c = 0; c < channels; ++c) {
+            unsigned __int128 sum[3] = {0, 0, 0};
+            uint32_t count = 0;
+            for (uint64_t j = bound(b); j < bound(b + 1); ++j) {
+                const sgz_band_record &v = in[j * channels + c];
+                for (int k = 0; k < 3; ++k) sum[k] += sumOf(v, k);
+                count += v.count;
+            }
+            sgz_band_record r{};
+            for (int k = 0; k < 3; ++k) { r.sumsq[k][0] = uint64_t(sum[k]); r.sumsq[k][1] = uint64_t(sum[k] >> 64); }
+            r.count = count;
+            out[b * channels + c] = r;
+        }
+    return SGZ_OK;
+}
+
+sgz_status sgz_band_readout(const sgz_band_record *recs, size_t ncols, uint32_t channels, uint32_t channel, double *mean_square, double *db)
+{
+    if (!recs) return fail(SGZ_EINVAL, "sgz_band_readout: null argument");
+    if (channels == 0 || ncols == 0 || channel >= channels) return fail(SGZ_EINVAL, "sgz_band_readout: channels >= 1, ncols >= 1 and channel < channels");
+    double ms[3];
+    bandMeanSquares(recs, ncols, channels, channel, ms);
+    for (int b = 0; b < 3; ++b) {
+        if (mean_square) mean_square[b] = ms[b];
+        if (db) db[b] = ms[b] > 0.0 ? 10.0 * std::log10(ms[b]) : -std::numeric_limits<double>::infinity();
+    }
+    return SGZ_OK;
+}
+
+sgz_status sgz_band_colours(const sgz_band_record *recs, size_t ncols, uint32_t channels, uint32_t channel, const float band_colours[3][3],
+                            const uint8_t key_rgba8[4], double frequency_colouring_blend, uint8_t *out_rgba8)
+{
+    if (!recs || !band_colours || !key_rgba8 || !out_rgba8) return fail(SGZ_EINVAL, "sgz_band_colours: null argument");
+    if (channels == 0 || channel >= channels) return fail(SGZ_EINVAL, "sgz_band_colours: channels >= 1 and channel < channels");
+    const float blend = 1 - float(frequency_colouring_blend);       // what the live scope hands to accumulateColour
+    for (size_t j = 0; j < ncols; ++j) {
+        double ms[3];
+        bandMeanSquares(recs + j * channels, 1, channels, channel, ms);
+        const float state[3] = {float(ms[0]), float(ms[1]), float(ms[2])};
+        // accumulateColour (OscilloscopeDSP.inl:472-497) in its order; a silent column is 255 / 0 * 0, a NaN, which the conversion makes 0
+        float red = 0, green = 0, blue = 0;
+        for (int i = 0; i < 3; ++i) {
+            red += state[i] * band_colours[i][0];
+            green += state[i] * band_colours[i][1];
+            blue += state[i] * band_colours[i][2];
+        }
+        const float invMax = 255.0f / std::fmax(red, std::fmax(blue, green));
+        const uint8_t ret[4] = {toU8(red * invMax), toU8(green * invMax), toU8(blue * invMax), 255};
+        for (int k = 0; k < 4; ++k) out_rgba8[j * 4 + k] = lerpU8(ret[k], key_rgba8[k], blend);
+    }
+    return SGZ_OK;
+}
+
+}  // extern "C"

@@ -4,8 +4,8 @@
 // and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, a lane's columns or records --
 // is a PcmOut: device block, pinned twin, pending host copy.  Every lane is a PcmSink: the caller's buffer, the cursor in it, and the PcmOut its
 // units pass through; the track lane (tracker.hip), which searches every piece's line results behind its render, is a sink of frames, and the
-// five column lanes -- waveform, level, true-peak, loudness, stereo-field (wave_columns.hip, level_columns.hip, truepeak_columns.hip,
-// loudness_columns.hip, field_columns.hip),
+// six column lanes -- waveform, level, true-peak, loudness, stereo-field, band (wave_columns.hip, level_columns.hip, truepeak_columns.hip,
+// loudness_columns.hip, field_columns.hip, band_columns.hip),
 // which reduce every piece's new samples behind the converter in that order -- are ONE PcmLane type, a sink of columns with the open column's
 // carry, and differ in a hook that makes the one call of their reduction.  The feed walks the lanes; all ride the same read-back.
 #include <hip/hip_runtime.h>
@@ -201,7 +201,8 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // TruePeak sgz_truepeak_record [ceil(chunk / m) + 1][channels] the true-peak lane's.
 // Loudness sgz_loudness_record [ceil(chunk / m) + 1][channels] the loudness lane's.
 // Field sgz_field_record [ceil(chunk / m) + 1][pairs] the stereo-field lane's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kPcmOuts };
+// Band sgz_band_record [ceil(chunk / m) + 1][channels] the band lane's.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -280,10 +281,10 @@ struct PcmSink {
     }
 };
 
-// The sinks in the order a feed refuses them; the five column lanes come first and are the stream's lane[] in this order
-enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
-constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField};
-constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField};
+// The sinks in the order a feed refuses them; the six column lanes come first and are the stream's lane[] in this order
+enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
+constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand};
+constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand};
 
 // A lane's hook: the one call of its reduction, run<Lane>Columns, on the compute stream.  (n samples at `in`, flush 0) is a piece's step: the
 // columns they close go to d_out, the open one to the other half of the carry; (0 samples, flush 1) is the flush's emit launch, which leaves the
@@ -335,6 +336,14 @@ struct sgz_pcm_stream {
     // the lane's scratch (q of a piece's samples, partial records), kept: every piece's launches are on the compute stream, one behind the other
     void *d_ldScratch = nullptr;
     size_t ldScratchCap = 0;
+    // the band lane's own, as the loudness lane's: the filter, the sample index, the carry (two halves of bandCarryBytes(bdFilter) * channels
+    // bytes) and the kept scratch
+    bool bdContinued = false;
+    sgz_band_filter bdFilter{};
+    uint64_t bdIndex = 0;
+    size_t bdCarryCap = 0;
+    void *d_bdScratch = nullptr;
+    size_t bdScratchCap = 0;
 
     PcmSink &sink(int id) { return id < kPcmLanes ? lane[id].sink : track; }
 };
@@ -367,7 +376,7 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
 }
 
 // ---- the lanes inside the stream (sgz.h, "The waveform lane" ... "The loudness lane", "The track lane") -----------------------------------------
-// The five hooks.  The waveform, level and stereo-field carries hold the open column alone: a step moves to the other half only when a column stays open.
+// The six hooks.  The waveform, level and stereo-field carries hold the open column alone: a step moves to the other half only when a column stays open.
 static sgz_status pcmWaveRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
 {
     const uint32_t channels = s.numChannels, open = uint32_t(l.open);
@@ -449,6 +458,28 @@ static sgz_status pcmLoudnessRun(sgz_pcm_stream &s, PcmLane &l, const float *in,
                                              flush ? nullptr : s.d_ldScratch, s.compute);
     if (st != SGZ_OK) return st;
     if (!flush) { l.cur ^= 1; s.ldContinued = true; s.ldIndex += n; }
+    *closed = sh.closed;
+    return SGZ_OK;
+}
+
+// (the band lane: the loudness lane's carry rules with its own filter, index and scratch)
+static sgz_status pcmBandRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
+{
+    const uint32_t channels = s.numChannels, open = uint32_t(l.open);
+    const BandColumnsShape sh = bandColumnsShape(channels, n, l.m, open, flush, 0);
+    if (sh.scratchBytes > s.bdScratchCap) {                                         // (the first piece of a feed is its largest: this happens once)
+        SGZ_HIP(hipStreamSynchronize(s.compute));
+        if (s.d_bdScratch) { (void)hipFree(s.d_bdScratch); s.d_bdScratch = nullptr; s.bdScratchCap = 0; }
+        SGZ_HIP(hipMalloc(&s.d_bdScratch, sh.scratchBytes));
+        s.bdScratchCap = sh.scratchBytes;
+    }
+    uint8_t *carry = static_cast<uint8_t *>(l.d_carry);
+    const size_t half = bandCarryBytes(s.bdFilter) * channels;
+    const sgz_status st = runBandColumns(sh, s.bdFilter, in, s.stride, channels, n, s.bdIndex, l.m, open, (flush || s.bdContinued) ? 1u : 0u,
+                                         carry + l.cur * half, carry + (l.cur ^ 1) * half, static_cast<sgz_band_record *>(d_out),
+                                         flush ? nullptr : s.d_bdScratch, s.compute);
+    if (st != SGZ_OK) return st;
+    if (!flush) { l.cur ^= 1; s.bdContinued = true; s.bdIndex += n; }
     *closed = sh.closed;
     return SGZ_OK;
 }
@@ -752,6 +783,7 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
     for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry}) if (p) (void)hipFree(p);
     for (PcmLane &l : s->lane) if (l.d_carry) (void)hipFree(l.d_carry);
     if (s->d_ldScratch) (void)hipFree(s->d_ldScratch);
+    if (s->d_bdScratch) (void)hipFree(s->d_bdScratch);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
     if (s->plan) sgz_plan_destroy(s->plan);
     delete s;
@@ -783,6 +815,7 @@ sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format
         {"true-peak", "truepeak", kOutTruePeak, s->numChannels * sizeof(sgz_truepeak_record), pcmTruePeakRun},
         {"loudness", "loudness", kOutLoudness, s->numChannels * sizeof(sgz_loudness_record), pcmLoudnessRun},
         {"stereo-field", "field", kOutField, cfg->num_pairs * sizeof(sgz_field_record), pcmFieldRun},
+        {"band", "band", kOutBand, s->numChannels * sizeof(sgz_band_record), pcmBandRun},
     };
     for (int id = 0; id < kPcmLanes; ++id) {
         PcmLane &l = s->lane[id];
@@ -824,6 +857,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     for (PcmLane &l : s->lane) l.open = 0;                                          // open columns are dropped
     s->tpContinued = s->ldContinued = false;                                        // the true-peak and loudness histories are zeros again
     s->ldIndex = 0;                                                                 // and the loudness lane's samples count from 0
+    s->bdContinued = false; s->bdIndex = 0;                                         // the band lane's likewise
     return SGZ_OK;
 }
 
@@ -984,23 +1018,58 @@ sgz_status sgz_pcm_stream_set_field(sgz_pcm_stream *s, uint32_t m, sgz_field_rec
     return SGZ_OK;
 }
 
+sgz_status sgz_pcm_stream_set_band(sgz_pcm_stream *s, const sgz_band_filter *filter, uint32_t m, sgz_band_record *out, uint64_t capacity_columns)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    PcmLane &l = s->lane[kSinkBand];
+    if (m == 0) { pcmLaneDisarm(l); s->bdIndex = 0; s->bdContinued = false; return SGZ_OK; }  // (the history and the index are dropped too)
+    if (m < 64) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: m >= 64 samples per column (a 64-byte record per channel for fewer would read back more than the samples)");
+    if (!filter) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: null filter");
+    if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: null out");
+    if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_band_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: out is not aligned to 8 bytes");
+    const bool same = l.m == m && std::memcmp(&s->bdFilter, filter, sizeof *filter) == 0;
+    if (l.open && !same) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: m or the filter differs from the open column's -- flush it (sgz_pcm_stream_flush_band), disarm or reset first");
+    if (!same) {
+        // (what the stage call refuses, and the tap table: a refused filter arms nothing)
+        size_t bytes = 0;
+        if (sgz_status st = sgz_band_columns_limits(filter, s->numChannels, nullptr, nullptr, &bytes); st != SGZ_OK) return st;
+        std::vector<int32_t> taps(size_t(16) * filter->W);
+        if (sgz_status st = sgz_band_taps(filter, taps.data()); st != SGZ_OK) return st;
+        if (s->bdCarryCap < 2 * bytes) {
+            // (both slots are idle between feeds, but a flush's launch may still read the old block: wait for it)
+            SGZ_HIP(hipStreamSynchronize(s->compute));
+            if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; s->bdCarryCap = 0; }
+            SGZ_HIP(hipMalloc(&l.d_carry, 2 * bytes));
+            s->bdCarryCap = 2 * bytes;
+        }
+        s->bdFilter = *filter;
+        s->bdContinued = false;                                    // (arming: the lane starts at the next sample, index 0, with a zero history)
+        s->bdIndex = 0; l.cur = 0;
+    }
+    pcmLaneArm(*s, l, m, out, capacity_columns);
+    return SGZ_OK;
+}
+
 uint64_t sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkWave, nsamples, flush); }
 uint64_t sgz_pcm_stream_level_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLevel, nsamples, flush); }
 uint64_t sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkTruePeak, nsamples, flush); }
 uint64_t sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLoudness, nsamples, flush); }
 uint64_t sgz_pcm_stream_field_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkField, nsamples, flush); }
+uint64_t sgz_pcm_stream_band_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkBand, nsamples, flush); }
 
 sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkWave, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLevel, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_truepeak_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkTruePeak, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLoudness, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_field_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkField, columns_written, open_samples); }
+sgz_status sgz_pcm_stream_band_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkBand, columns_written, open_samples); }
 
 sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkWave); }
 sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLevel); }
 sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkTruePeak); }
 sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLoudness); }
 sgz_status sgz_pcm_stream_flush_field(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkField); }
+sgz_status sgz_pcm_stream_flush_band(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkBand); }
 
 // ---- the track lane's calls -------------------------------------------------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_set_track(sgz_pcm_stream *s, uint32_t graph, double mouse_fraction, sgz_line_peak *track_out, uint64_t capacity_frames)

@@ -147,6 +147,15 @@ LoudnessColumnsShape loudnessColumnsShape(uint32_t channels, size_t nsamples, ui
 sgz_status runLoudnessColumns(const LoudnessColumnsShape &sh, const sgz_loudness_filter &f, const float *d_planar, size_t channelStride,
                               uint32_t channels, size_t nsamples, uint64_t firstIndex, uint32_t m, uint32_t held, uint32_t continued,
                               const void *carryIn, void *carryOut, sgz_loudness_record *d_out, void *scratch, hipStream_t stream);
+// the band lane's reduction (band_columns.hip), the loudness lane's two steps.  The carry is bandCarryBytes(f) bytes per channel: the open
+// column's record, the last W + L - 1 quantised samples, a zero word.  scratch: sh.scratchBytes bytes aligned to 16 (the three q planes of
+// every sample, then the sliced form's partial records)
+using BandColumnsShape = WaveColumnsShape;
+size_t bandCarryBytes(const sgz_band_filter &f);
+BandColumnsShape bandColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
+sgz_status runBandColumns(const BandColumnsShape &sh, const sgz_band_filter &f, const float *d_planar, size_t channelStride, uint32_t channels,
+                          size_t nsamples, uint64_t firstIndex, uint32_t m, uint32_t held, uint32_t continued, const void *carryIn, void *carryOut,
+                          sgz_band_record *d_out, void *scratch, hipStream_t stream);
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
 }  // namespace sgz
