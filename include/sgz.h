@@ -69,6 +69,11 @@ extern "C" {
  *  sgz_band_filter_for_rate, sgz_band_taps, sgz_band_fold, sgz_band_readout and sgz_band_colours and, on the PCM stream,
  *  sgz_pcm_stream_set_band, sgz_pcm_stream_band_for, sgz_pcm_stream_band_state, sgz_pcm_stream_flush_band.  No existing entry point or
  *  struct changed and the suite pins 5; a stream that was never armed enqueues what it did before.)
+ * (5, later: the mean overview -- sgz_overview_stat_record, sgz_stage_overview_stats, sgz_spectrogram_overview_stats_device / _host,
+ *  sgz_stage_overview_stats_view, sgz_overview_stats_view_host, the host helpers sgz_overview_stats_fold and sgz_overview_stats_readout and,
+ *  on the PCM stream, sgz_pcm_stream_feed_overview_stats and sgz_spectrogram_overview_stats_pcm.  No existing entry point or struct changed
+ *  and the suite pins 5; the one new refusal on an existing call, sgz_pcm_stream_feed_overview while a stats column is open, cannot be
+ *  reached without the new calls.  A binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -591,6 +596,87 @@ sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar
                                            uint8_t *d_rgba, float *d_peaks, float *d_state, void *stream);
 sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
                                          uint8_t *rgba_out, float *peaks_out, sgz_timing *timing);
+
+/* The mean overview: mean and range of k frames per image column -- the second reduction of the overview render, of the same line results
+ * over the same columns.  A peak hold shows transients; at a few hundred frames per column dense material saturates it, and a tone in one
+ * frame of 500 looks like a tone in all 500.  This is the "average" every analyser offers beside "peak", with the minimum and the maximum
+ * it draws the average between.  One pass over a file gives mean, least and greatest; the image is coloured from the mean.
+ * Definition (exact, no tolerance).  L[f][p][g][i], F and k as in the overview render; columns and their frames are counted exactly as
+ * there (sgz_overview_step).  Let x = L[f][p][0][i].x.
+ *   quantiser  a NaN takes no part in sum, count, lo or hi; it is counted in nans.  Otherwise t = (double)x * 2^20 (exact; +-inf stays
+ *              +-inf);  q = 2^31 - 1 if t >= 2^31 - 1;  q = -(2^31 - 1) if t <= -(2^31 - 1);  otherwise q = rint(t), ties to even.
+ *              Line results are values on the normalised dB axis: |x| < 2048 covers a clip of -1000 dB over a 1 dB range, at a
+ *              resolution of 1e-6 of the axis.
+ *   record     per (column, pair, pixel) one sgz_overview_stat_record: sum = the sum of q; count = the non-NaN frames; nans = the NaN
+ *              frames; hi the greatest and lo the least of the non-NaN x under the overview's total order (-0 below +0), both
+ *              0x7FC00000 when count == 0.  hi is therefore V of the peak-hold overview, bit for bit.  |sum| < 2^63 for every count
+ *              below 2^32.
+ *   mean       count == 0: the bits 0x7FC00000; otherwise (float)(((double)sum / (double)count) * 2^-20), every conversion and the
+ *              division rounded to nearest even, nothing contracted.
+ *   pixel      the additive blend of the pairs' colours at the mean, p = 0 .. pairs - 1 in order, from a black column buffer, then the
+ *              8-bit conversion -- the overview render's pixel with the mean in V's place; a NaN mean is coloured as a NaN V is.
+ *   fold       field-wise: sum, count and nans add, lo is the least of the los, hi the greatest of the his.  All are associative and
+ *              commutative: every cut (slices, calls, slabs, feeds, chunk sizes) gives the same bytes, and a coarser column is exactly
+ *              the fold of the finer ones it covers -- any zoom from one streamed pass, as for the kept peaks.
+ * For k == 1: hi == lo == x bit for bit for a non-NaN x, sum == q(x) and count == 1.  The image is in general NOT the frame render's byte
+ * for byte: the mean is the quantised value.
+ * The mean is a mean of displayed (dB-axis) values, hence the geometric mean of the magnitudes: it is defined on what every render writes
+ * and what the colour map takes.  A power-domain mean needs magnitudes from before the dB map, which no boundary of the library exposes:
+ * out of scope, as are percentiles and the median.
+ * The calls follow their peak-hold twins argument for argument: float *d_peaks becomes sgz_overview_stat_record *d_stats, and every call
+ * has one more optional output, the means float [columns][pairs][P] -- value planes as V is (sgz_stage_track_peaks_values takes them).
+ * Of image, records and means at least one must be non-NULL.  The carry is sgz_overview_stat_record [pairs][P].
+ *  sgz_stage_overview_stats   refusals, slices (0, 1 .. 64, identical bits), asynchrony and "only the documented bytes are written" as for
+ *                      sgz_stage_overview.
+ *  sgz_spectrogram_overview_stats_device / _host   as sgz_spectrogram_overview_device / _host: slabs with the decay state and the open
+ *                      column carried, bytes independent of SGZ_OPT_OVERVIEW_SLAB, RSNT plans in one slab; carry and partial scratch of
+ *                      their own in the plan.
+ *  sgz_stage_overview_stats_view / sgz_overview_stats_view_host   any range [x0, x1) of kept records [n][pairs][P] at any width, in the
+ *                      plan's colours, by the boundary rule of sgz_overview_view_columns: the image, the folded records and the means.
+ *                      Outputs that overlap the source range are refused.  The counts of a folded column are the caller's to keep below
+ *                      2^32 (they are not checked on the device; sgz_overview_stats_fold checks them).
+ *  sgz_overview_stats_fold    host, no GPU: columns [x0, x1) of in [n][width] (width = pairs * P records per column) into cols =
+ *                      min(out_columns, x1 - x0) columns of out by the same boundary rule.  SGZ_EINVAL, nothing written: a null argument,
+ *                      width == 0, what sgz_overview_view_columns refuses, a folded count or nans above 2^32 - 1.
+ *  sgz_overview_stats_readout host, no GPU: `count` records into the float planes mean, lo and hi by the definition; any of the three may
+ *                      be NULL, not all.
+ *  sgz_pcm_stream_feed_overview_stats / sgz_spectrogram_overview_stats_pcm   the overview inside sgz_pcm_stream with this reduction:
+ *                      the concatenated columns of all feeds equal sgz_spectrogram_overview_stats_host of the converted planar floats,
+ *                      byte for byte, however the stream is cut.  An open column is of one kind: a peak-hold feed while a stats column is
+ *                      open, and the reverse, is refused with SGZ_EINVAL, consumes nothing and says so in sgz_last_error.
+ *                      sgz_pcm_stream_columns_for and sgz_pcm_stream_open_frames serve both kinds; sgz_pcm_stream_reset drops the open
+ *                      column; sgz_pcm_stream_feed stays refused while any column is open.  An armed lane runs in a stats feed exactly as
+ *                      in a peak-hold feed (the track lane searches every slab's line results). */
+typedef struct sgz_overview_stat_record {
+    int64_t sum;        /* the sum of q over the column's non-NaN frames                              */
+    uint32_t count;     /* non-NaN frames                                                            */
+    uint32_t nans;      /* NaN frames                                                                */
+    float lo, hi;       /* the least / the greatest non-NaN value; both 0x7FC00000 when count == 0   */
+} sgz_overview_stat_record;                /* 24 bytes, 8-aligned */
+#ifdef __cplusplus
+static_assert(sizeof(sgz_overview_stat_record) == 24 && alignof(sgz_overview_stat_record) == 8, "sgz_overview_stat_record: 24 bytes, 8-aligned");
+static_assert(offsetof(sgz_overview_stat_record, sum) == 0 && offsetof(sgz_overview_stat_record, count) == 8 && offsetof(sgz_overview_stat_record, nans) == 12 &&
+              offsetof(sgz_overview_stat_record, lo) == 16 && offsetof(sgz_overview_stat_record, hi) == 20, "sgz_overview_stat_record: offsets");
+#endif
+sgz_status sgz_stage_overview_stats(sgz_plan *plan, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                                    sgz_overview_stat_record *d_carry, uint8_t *d_rgba, sgz_overview_stat_record *d_stats, float *d_means, void *stream);
+sgz_status sgz_spectrogram_overview_stats_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                                 uint8_t *d_rgba, sgz_overview_stat_record *d_stats, float *d_means, float *d_state, void *stream);
+sgz_status sgz_spectrogram_overview_stats_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                               uint8_t *rgba_out, sgz_overview_stat_record *stats_out, float *means_out, sgz_timing *timing);
+sgz_status sgz_stage_overview_stats_view(sgz_plan *plan, const sgz_overview_stat_record *d_stats, size_t n, size_t x0, size_t x1, uint32_t out_columns,
+                                         uint32_t slices, uint8_t *d_rgba, sgz_overview_stat_record *d_stats_out, float *d_means, void *stream);
+sgz_status sgz_overview_stats_view_host(sgz_plan *plan, const sgz_overview_stat_record *stats, size_t n, size_t x0, size_t x1, uint32_t out_columns,
+                                        uint8_t *rgba_out, sgz_overview_stat_record *stats_out, float *means_out, sgz_timing *timing);
+sgz_status sgz_overview_stats_fold(const sgz_overview_stat_record *in, size_t n, size_t width, size_t x0, size_t x1, uint32_t out_columns,
+                                   sgz_overview_stat_record *out);
+sgz_status sgz_overview_stats_readout(const sgz_overview_stat_record *in, size_t count, float *mean, float *lo, float *hi);
+sgz_status sgz_pcm_stream_feed_overview_stats(sgz_pcm_stream *s, const void *pcm /*HOST*/, size_t nsamples, uint32_t k, int flush, uint8_t *rgba_out /*or NULL*/,
+                                              sgz_overview_stat_record *stats_out /*or NULL*/, float *means_out /*or NULL*/, uint64_t capacity_columns,
+                                              uint64_t *columns_out, sgz_pcm_timing *timing);
+sgz_status sgz_spectrogram_overview_stats_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                              const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
+                                              sgz_overview_stat_record *stats_out, float *means_out, sgz_pcm_timing *timing);
 
 /* The waveform lane: a minimum and a maximum per screen column and channel of a file's samples -- what every editor draws beside the
  * spectrogram lane -- reduced on the device from the planar floats the streamed render has there anyway.  The reference has no counterpart

@@ -243,6 +243,9 @@ EXPORTS = [
     "sgz_overview_view_columns", "sgz_stage_overview_view", "sgz_overview_view_host",
     "sgz_pcm_stream_feed_overview", "sgz_pcm_stream_columns_for", "sgz_pcm_stream_open_frames", "sgz_spectrogram_overview_pcm",
     "sgz_pcm_stream_set_option",
+    "sgz_stage_overview_stats", "sgz_spectrogram_overview_stats_device", "sgz_spectrogram_overview_stats_host", "sgz_stage_overview_stats_view",
+    "sgz_overview_stats_view_host", "sgz_overview_stats_fold", "sgz_overview_stats_readout", "sgz_pcm_stream_feed_overview_stats",
+    "sgz_spectrogram_overview_stats_pcm",
     "sgz_stage_wave_columns", "sgz_wave_columns_limits", "sgz_pcm_stream_set_waveform", "sgz_pcm_stream_waveform_for",
     "sgz_pcm_stream_waveform_state", "sgz_pcm_stream_flush_waveform",
     "sgz_track_peak_values", "sgz_stage_track_peaks_values", "sgz_pcm_stream_set_track", "sgz_pcm_stream_track_for", "sgz_pcm_stream_track_state",
@@ -346,6 +349,13 @@ def lib() -> C.CDLL:
     L.sgz_overview_view_columns.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, u32, C.POINTER(C.c_uint64), vp]
     L.sgz_stage_overview_view.argtypes = [vp, vp, sz, sz, sz, u32, u32, vp, vp, vp]
     L.sgz_overview_view_host.argtypes = [vp, vp, sz, sz, sz, u32, vp, vp, C.POINTER(Timing)]
+    L.sgz_stage_overview_stats.argtypes = [vp, vp, sz, u32, u32, C.c_int, u32, vp, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_stats_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_stats_host.argtypes = [vp, vp, u32, sz, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.sgz_stage_overview_stats_view.argtypes = [vp, vp, sz, sz, sz, u32, u32, vp, vp, vp, vp]
+    L.sgz_overview_stats_view_host.argtypes = [vp, vp, sz, sz, sz, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.sgz_overview_stats_fold.argtypes = [vp, sz, sz, sz, sz, u32, vp]
+    L.sgz_overview_stats_readout.argtypes = [vp, sz, vp, vp, vp]
     L.sgz_comm_unique_id.argtypes = [vp]
     L.sgz_comm_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.sgz_comm_destroy.argtypes = [vp]
@@ -482,6 +492,8 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_track_for.restype = u64
     L.sgz_pcm_stream_track_state.argtypes = [vp, C.POINTER(u64)]
     L.sgz_spectrogram_overview_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, C.POINTER(PcmTiming)]
+    L.sgz_pcm_stream_feed_overview_stats.argtypes = [vp, vp, sz, u32, C.c_int, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
+    L.sgz_spectrogram_overview_stats_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, vp, C.POINTER(PcmTiming)]
     L.sgz_stage_level_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
     L.sgz_level_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.sgz_level_columns_limits.restype = None
@@ -754,6 +766,44 @@ def overview_view_columns(n: int, x0: int, x1: int, out_columns: int, want_bound
     return int(c.value), bounds
 
 
+# sgz_overview_stat_record (sgz.h, "The mean overview"): 24 bytes, 8-aligned.  On the device a record is three int64 words of a torch tensor
+# [..., 3]; stats_from_device turns such a tensor into a numpy array of this dtype
+OVERVIEW_STAT_DTYPE = np.dtype({"names": ["sum", "count", "nans", "lo", "hi"], "formats": ["<i8", "<u4", "<u4", "<f4", "<f4"],
+                                "offsets": [0, 8, 12, 16, 20], "itemsize": 24})
+
+
+def stats_from_device(t) -> np.ndarray:
+    """cuda int64 [..., 3] (records as the stats calls write them) -> numpy OVERVIEW_STAT_DTYPE [...]"""
+    h = np.ascontiguousarray(t.cpu().numpy())
+    return h.view(OVERVIEW_STAT_DTYPE).reshape(h.shape[:-1])
+
+
+def stats_to_device(records: np.ndarray, device):
+    """numpy OVERVIEW_STAT_DTYPE [...] -> cuda int64 [..., 3]"""
+    import torch
+    r = np.ascontiguousarray(records, OVERVIEW_STAT_DTYPE)
+    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 3).copy()).to(device)
+
+
+def overview_stats_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_overview_stats_fold (host, no GPU): OVERVIEW_STAT_DTYPE records [n, ...], source columns [x0, x1) -> [min(out_columns, x1 - x0), ...]"""
+    records = np.ascontiguousarray(records, OVERVIEW_STAT_DTYPE)
+    n = int(records.shape[0])
+    x1 = n if x1 is None else x1
+    width = int(np.prod(records.shape[1:], dtype=np.int64))
+    out = np.zeros((overview_view_columns(n, x0, x1, out_columns), *records.shape[1:]), OVERVIEW_STAT_DTYPE)
+    check(lib().sgz_overview_stats_fold(_np_ptr(records), n, width, x0, x1, out_columns, _np_ptr(out)))
+    return out
+
+
+def overview_stats_readout(records: np.ndarray):
+    """sgz_overview_stats_readout (host, no GPU): OVERVIEW_STAT_DTYPE records [...] -> (mean, lo, hi), float32 planes of the same shape"""
+    records = np.ascontiguousarray(records, OVERVIEW_STAT_DTYPE)
+    mean, lo, hi = (np.zeros(records.shape, np.float32) for _ in range(3))
+    check(lib().sgz_overview_stats_readout(_np_ptr(records), records.size, _np_ptr(mean), _np_ptr(lo), _np_ptr(hi)))
+    return mean, lo, hi
+
+
 class Plan:
     """The Spectrum constant block (TransformConstant mirror). Host tables need no GPU."""
 
@@ -999,6 +1049,95 @@ class Plan:
         check(lib().sgz_stage_overview_view(self.h, peaks.data_ptr(), n, x0, x1, out_columns, slices, rgba.data_ptr() if want_rgba else None,
                                             out.data_ptr() if want_peaks else None, s))
         return rgba, out
+
+    # the mean overview: the same columns, reduced to sum / count / nans / lo / hi records and coloured from the mean
+    def overview_stats_columns(self, lines, k: int, held: int = 0, flush: bool = True, slices: int = 0, carry=None, want_rgba: bool = True,
+                               want_stats: bool = False, want_means: bool = False, stream=None):
+        """sgz_stage_overview_stats: lines -- cuda float32 [frames, pairs, graphs, P, 2]; carry -- cuda int64 [pairs, P, 3], the open column's
+        records (read when held > 0, written when frames stay open).  Returns (cuda rgba uint8 [columns, P, 4] or None, cuda records int64
+        [columns, pairs, P, 3] or None -- see stats_from_device --, cuda means float32 [columns, pairs, P] or None, frames left open)."""
+        import torch
+        assert lines.is_cuda and lines.dtype == torch.float32 and lines.is_contiguous()
+        assert tuple(lines.shape[1:]) == (self.C, NUM_GRAPHS, self.P, 2)
+        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * self.P * 3)
+        frames = lines.shape[0]
+        columns, held_out = overview_step(k, held, frames, flush)
+        n = max(columns, 1)                                                                                     # (never a NULL pointer)
+        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=lines.device) if want_rgba else None
+        stats = torch.empty((n, self.C, self.P, 3), dtype=torch.int64, device=lines.device) if want_stats else None
+        means = torch.empty((n, self.C, self.P), dtype=torch.float32, device=lines.device) if want_means else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview_stats(self.h, lines.data_ptr(), frames, k, held, int(bool(flush)), slices,
+                                             carry.data_ptr() if carry is not None else None, rgba.data_ptr() if want_rgba else None,
+                                             stats.data_ptr() if want_stats else None, means.data_ptr() if want_means else None, s))
+        return (rgba[:columns] if want_rgba else None), (stats[:columns] if want_stats else None), (means[:columns] if want_means else None), held_out
+
+    def overview_stats(self, planar, k: int, want_rgba: bool = True, want_stats: bool = False, want_means: bool = False, state=None, stream=None):
+        """The mean overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_stats_host -> (rgba or None, records
+        OVERVIEW_STAT_DTYPE [columns, C, P] or None, means float32 [columns, C, P] or None, timing dict).  planar a cuda tensor:
+        sgz_spectrogram_overview_stats_device, asynchronous -> (cuda rgba, cuda records int64 [columns, C, P, 3], cuda means), None where not
+        wanted.  Fewer samples than a window: None."""
+        if isinstance(planar, np.ndarray):
+            planar = np.ascontiguousarray(planar, np.float32)
+            nch, S = planar.shape
+            columns = -(-self.num_frames(S) // k)
+            n = max(columns, 1)
+            rgba = np.zeros((n, self.P, 4), np.uint8) if want_rgba else None
+            stats = np.zeros((n, self.C, self.P), OVERVIEW_STAT_DTYPE) if want_stats else None
+            means = np.zeros((n, self.C, self.P), np.float32) if want_means else None
+            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
+            t = Timing()
+            st = check(lib().sgz_spectrogram_overview_stats_host(self.h, ptrs, nch, S, k, _np_ptr(rgba) if want_rgba else None,
+                                                                 _np_ptr(stats) if want_stats else None, _np_ptr(means) if want_means else None,
+                                                                 C.byref(t)))
+            if st == SGZ_SKIPPED_FRAME:
+                return None
+            return ((rgba[:columns] if want_rgba else None), (stats[:columns] if want_stats else None), (means[:columns] if want_means else None),
+                    {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames})
+        import torch
+        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
+        S = planar.shape[1]
+        columns = -(-self.num_frames(S) // k)
+        n = max(columns, 1)
+        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None
+        stats = torch.empty((n, self.C, self.P, 3), dtype=torch.int64, device=planar.device) if want_stats else None
+        means = torch.empty((n, self.C, self.P), dtype=torch.float32, device=planar.device) if want_means else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = check(lib().sgz_spectrogram_overview_stats_device(self.h, planar.data_ptr(), planar.stride(0), S, k,
+                                                               rgba.data_ptr() if want_rgba else None, stats.data_ptr() if want_stats else None,
+                                                               means.data_ptr() if want_means else None,
+                                                               state.data_ptr() if state is not None else None, s))
+        if st == SGZ_SKIPPED_FRAME:
+            return None
+        return (rgba[:columns] if want_rgba else None), (stats[:columns] if want_stats else None), (means[:columns] if want_means else None)
+
+    def overview_stats_view(self, stats, out_columns: int, x0: int = 0, x1: int | None = None, slices: int = 0, want_rgba: bool = True,
+                            want_stats: bool = False, want_means: bool = False, stream=None):
+        """The view of kept records over source columns [x0, x1) (default: to the end) at min(out_columns, x1 - x0) columns.  stats a cuda
+        int64 tensor [n, C, P, 3]: sgz_stage_overview_stats_view, asynchronous -> (cuda rgba, cuda records, cuda means), None where not
+        wanted.  stats a numpy OVERVIEW_STAT_DTYPE array [n, C, P]: sgz_overview_stats_view_host -> (rgba, records, means, timing dict)."""
+        n = int(stats.shape[0])
+        x1 = n if x1 is None else x1
+        cols = overview_view_columns(n, x0, x1, out_columns)
+        if isinstance(stats, np.ndarray):
+            stats = np.ascontiguousarray(stats, OVERVIEW_STAT_DTYPE)
+            assert tuple(stats.shape[1:]) == (self.C, self.P), tuple(stats.shape)
+            rgba = np.zeros((cols, self.P, 4), np.uint8) if want_rgba else None
+            out = np.zeros((cols, self.C, self.P), OVERVIEW_STAT_DTYPE) if want_stats else None
+            means = np.zeros((cols, self.C, self.P), np.float32) if want_means else None
+            t = Timing()
+            check(lib().sgz_overview_stats_view_host(self.h, _np_ptr(stats), n, x0, x1, out_columns, _np_ptr(rgba) if want_rgba else None,
+                                                     _np_ptr(out) if want_stats else None, _np_ptr(means) if want_means else None, C.byref(t)))
+            return rgba, out, means, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+        import torch
+        assert stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape[1:]) == (self.C, self.P, 3)
+        rgba = torch.empty((cols, self.P, 4), dtype=torch.uint8, device=stats.device) if want_rgba else None
+        out = torch.empty((cols, self.C, self.P, 3), dtype=torch.int64, device=stats.device) if want_stats else None
+        means = torch.empty((cols, self.C, self.P), dtype=torch.float32, device=stats.device) if want_means else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview_stats_view(self.h, stats.data_ptr(), n, x0, x1, out_columns, slices, rgba.data_ptr() if want_rgba else None,
+                                                  out.data_ptr() if want_stats else None, means.data_ptr() if want_means else None, s))
+        return rgba, out, means
 
     def colour_table(self, pair: int) -> np.ndarray:
         out = np.zeros((NUM_SPEC_COLOURS + 1, 3), np.float32)
@@ -1279,6 +1418,33 @@ class PcmStream:
         assert c == cols, (c, cols)
         return (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
 
+    def feed_overview_stats_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, stats, means, capacity_columns: int, timing: bool = True):
+        """the C call as it is: (status, columns_out, PcmTiming or None); rgba / stats / means: numpy arrays, host torch tensors or None"""
+        t, c = PcmTiming() if timing else None, C.c_uint64(0)
+        st = lib().sgz_pcm_stream_feed_overview_stats(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
+                                                      *[_buf_ptr(a) if a is not None else None for a in (rgba, stats, means)],
+                                                      capacity_columns, C.byref(c), C.byref(t) if timing else None)
+        return st, int(c.value), t
+
+    def feed_overview_stats(self, pcm, k: int, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_stats: bool = True,
+                            want_means: bool = False):
+        """Feeds nsamples (default: all of pcm; pcm None: none) into the mean overview at k frames per column and returns the columns that
+        closed: (rgba uint8 [columns, P, 4] or None, records OVERVIEW_STAT_DTYPE [columns, pairs, P] or None, means float32 [columns,
+        pairs, P] or None, timing dict)."""
+        if pcm is None:
+            n = 0
+        else:
+            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+            n = nbytes // self.frame_bytes if nsamples is None else nsamples
+        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
+        P, pairs = self.cfg.axis_points, self.cfg.num_pairs
+        rgba = np.zeros((max(cols, 1), P, 4), np.uint8) if want_rgba else None
+        stats = np.zeros((max(cols, 1), pairs, P), OVERVIEW_STAT_DTYPE) if want_stats else None
+        means = np.zeros((max(cols, 1), pairs, P), np.float32) if want_means else None
+        st, c, t = self.feed_overview_stats_into(pcm if n else None, n, k, flush, rgba, stats, means, cols)
+        check(st)
+        assert c == cols, (c, cols)
+        return (rgba[:cols] if want_rgba else None), (stats[:cols] if want_stats else None), (means[:cols] if want_means else None), t.asdict()
 
     # the six column lanes (waveform, level, truepeak, loudness, field, band): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
@@ -1732,6 +1898,27 @@ def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None
     st = check(lib().sgz_spectrogram_overview_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(rgba) if want_rgba else None,
                                                   _np_ptr(peaks) if want_peaks else None, C.byref(t)))
     return st, (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
+
+
+def overview_stats_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
+                       want_stats: bool = True, want_means: bool = False):
+    """One-shot mean overview of an interleaved PCM buffer (sgz_spectrogram_overview_stats_pcm): (status, rgba or None, records
+    OVERVIEW_STAT_DTYPE or None, means or None, timing dict); SGZ_SKIPPED_FRAME and empty outputs for fewer samples than a window"""
+    c = _as_config(cfg)
+    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
+    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
+    cols = -(-F // k) if k else 0
+    rgba = np.zeros((max(cols, 1), c.axis_points, 4), np.uint8) if want_rgba else None
+    stats = np.zeros((max(cols, 1), c.num_pairs, c.axis_points), OVERVIEW_STAT_DTYPE) if want_stats else None
+    means = np.zeros((max(cols, 1), c.num_pairs, c.axis_points), np.float32) if want_means else None
+    m, mp = _channel_map(channel_map)
+    t = PcmTiming()
+    st = check(lib().sgz_spectrogram_overview_stats_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(rgba) if want_rgba else None,
+                                                        _np_ptr(stats) if want_stats else None, _np_ptr(means) if want_means else None, C.byref(t)))
+    if st == SGZ_SKIPPED_FRAME:
+        cols = 0
+    return st, (rgba[:cols] if want_rgba else None), (stats[:cols] if want_stats else None), (means[:cols] if want_means else None), t.asdict()
 
 
 def render_spectrogram_pcm(cfg, pcm, fmt: int, src_channels: int, channel_map=None, nsamples: int | None = None, want_lines: bool = False):

@@ -47,7 +47,8 @@ Plan::~Plan()
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq, (void *)d_ovLines, (void *)d_ovCarry,
-                    (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks, (void *)d_ovViewIn})
+                    (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks, (void *)d_ovViewIn, (void *)d_ovsCarry,
+                    (void *)d_ovsCarryCopy, (void *)d_ovsPartial, (void *)d_hostOvStats, (void *)d_hostOvMeans, (void *)d_ovsViewIn})
         if (p) (void)hipFree(p);
     for (void *e : hostEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *e : shardEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
@@ -1064,11 +1065,14 @@ sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar
 // RSNT renders as one slab: its launches chain their frames within an fp32 bar, a cut would move the bits.
 constexpr size_t kOverviewSlabBytes = size_t(64) << 20;
 }  // extern "C"
-// The slab loop by itself (runtime.hpp): `held` frames of an open column in front (their V in d_carry), the columns that close written from
-// the outputs' first element on.  The overview render enters with held = 0 and flush; sgz_pcm_stream enters once per piece, with `track`
-// when its track lane is armed.
-sgz_status sgz::runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
-                                 int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t s, const SlabTrack *track)
+// The slab loop by itself (runtime.hpp): `held` frames of an open column in front (their reduction in the caller's carry), the columns that
+// close written from the outputs' first element on.  The overview render enters with held = 0 and flush; sgz_pcm_stream enters once per
+// piece, with `track` when its track lane is armed.  reduce(d_lines, frames, held, flush, column): the reduction of one slab's line results,
+// `column` the output column its first frame belongs to -- the peak hold (runOverviewSlabs) or the mean overview (runOverviewStatsSlabs).
+namespace {
+template <typename Reduce>
+sgz_status overviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
+                         int flush, float *d_state, hipStream_t s, const sgz::SlabTrack *track, Reduce reduce)
 {
     Plan &p = plan->impl;
     sgz_status st = SGZ_OK;
@@ -1091,11 +1095,32 @@ sgz_status sgz::runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t c
         if (track && (st = runTrackPeaksLines(p, p.d_ovLines, size_t(nf), track->graph, track->mouseFraction, track->d_out + size_t(f0) * p.C, s)) != SGZ_OK) return st;
         const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
         const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
-        st = runOverviewColumns(p, p.d_ovLines, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, 0, d_carry,
-                                d_rgba ? d_rgba + column * p.P * 4 : nullptr, d_peaks ? d_peaks + column * p.C * p.P : nullptr, s);
-        if (st != SGZ_OK) return st;
+        if ((st = reduce(p.d_ovLines, size_t(nf), uint32_t(t0 % k), flush && f0 + nf == frames, column)) != SGZ_OK) return st;
     }
     return SGZ_OK;
+}
+}  // namespace
+sgz_status sgz::runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
+                                 int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t s, const SlabTrack *track)
+{
+    Plan &p = plan->impl;
+    return overviewSlabs(plan, d_planar, channel_stride, nsamples, frames, k, held, flush, d_state, s, track,
+                         [&](const float *d_lines, size_t nf, uint32_t heldIn, int flushNow, size_t column) {
+                             return runOverviewColumns(p, d_lines, nf, k, heldIn, flushNow, 0, d_carry, d_rgba ? d_rgba + column * p.P * 4 : nullptr,
+                                                       d_peaks ? d_peaks + column * p.C * p.P : nullptr, s);
+                         });
+}
+sgz_status sgz::runOverviewStatsSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k,
+                                      uint32_t held, int flush, sgz_overview_stat_record *d_carry, float *d_state, uint8_t *d_rgba,
+                                      sgz_overview_stat_record *d_stats, float *d_means, hipStream_t s, const SlabTrack *track)
+{
+    Plan &p = plan->impl;
+    return overviewSlabs(plan, d_planar, channel_stride, nsamples, frames, k, held, flush, d_state, s, track,
+                         [&](const float *d_lines, size_t nf, uint32_t heldIn, int flushNow, size_t column) {
+                             return runOverviewStatsColumns(p, d_lines, nf, k, heldIn, flushNow, 0, d_carry, d_rgba ? d_rgba + column * p.P * 4 : nullptr,
+                                                            d_stats ? d_stats + column * p.C * p.P : nullptr,
+                                                            d_means ? d_means + column * p.C * p.P : nullptr, s);
+                         });
 }
 extern "C" {
 sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
@@ -1177,6 +1202,102 @@ sgz_status sgz_overview_view_host(sgz_plan *plan, const float *peaks, size_t n, 
     SGZ_HIP(hipEventRecord(ev[2], s));
     if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(cols) * p.P * 4, hipMemcpyDeviceToHost, s));
     if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaks_out, d_out, size_t(cols) * column * sizeof(float), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)
+    return SGZ_OK;
+}
+
+// The mean overview's render and host view (sgz.h, "The mean overview"; overview_stats.hip): the peak-hold calls above with records in the place
+// of peaks and the means as one more output.
+sgz_status sgz_spectrogram_overview_stats_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                                 uint8_t *d_rgba, sgz_overview_stat_record *d_stats, float *d_means, float *d_state, void *stream)
+{
+    if (!plan || !d_planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!d_rgba && !d_stats && !d_means) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    if ((st = ensureCap(&p.d_ovsCarry, &p.ovsCarryCap, size_t(p.C) * p.P * (sizeof(sgz_overview_stat_record) / sizeof(float)))) != SGZ_OK) return st;
+    return runOverviewStatsSlabs(plan, d_planar, channel_stride, nsamples, frames, k, 0, 1, reinterpret_cast<sgz_overview_stat_record *>(p.d_ovsCarry), d_state,
+                                 d_rgba, d_stats, d_means, reinterpret_cast<hipStream_t>(stream));
+}
+
+sgz_status sgz_spectrogram_overview_stats_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                               uint8_t *rgba_out, sgz_overview_stat_record *stats_out, float *means_out, sgz_timing *timing)
+{
+    if (!plan || !planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
+    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
+    for (uint32_t c = 0; c < num_channels; ++c)
+        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
+    const size_t columns = (size_t(frames) + k - 1) / k, records = columns * p.C * p.P;
+    constexpr size_t recordFloats = sizeof(sgz_overview_stat_record) / sizeof(float);
+    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
+    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, columns * p.P)) != SGZ_OK) return st;
+    if (stats_out && (st = ensureCap(&p.d_hostOvStats, &p.hostOvStatsCap, records * recordFloats)) != SGZ_OK) return st;
+    if (means_out && (st = ensureCap(&p.d_hostOvMeans, &p.hostOvMeansCap, records)) != SGZ_OK) return st;
+    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
+    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
+    sgz_overview_stat_record *d_stats = stats_out ? reinterpret_cast<sgz_overview_stat_record *>(p.d_hostOvStats) : nullptr;
+    float *d_means = means_out ? p.d_hostOvMeans : nullptr;
+    st = sgz_spectrogram_overview_stats_device(plan, p.d_hostAudio, stride, nsamples, k, d_rgba, d_stats, d_means, nullptr, s);
+    if (st != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, columns * p.P * 4, hipMemcpyDeviceToHost, s));
+    if (stats_out) SGZ_HIP(hipMemcpyAsync(stats_out, d_stats, records * sizeof(sgz_overview_stat_record), hipMemcpyDeviceToHost, s));
+    if (means_out) SGZ_HIP(hipMemcpyAsync(means_out, d_means, records * sizeof(float), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, frames);
+    return SGZ_OK;
+}
+
+// The view of kept records from HOST records: only the range's columns are uploaded, into plan scratch, on the plan's own stream.
+sgz_status sgz_overview_stats_view_host(sgz_plan *plan, const sgz_overview_stat_record *stats, size_t n, size_t x0, size_t x1, uint32_t out_columns,
+                                        uint8_t *rgba_out, sgz_overview_stat_record *stats_out, float *means_out, sgz_timing *timing)
+{
+    if (!plan || !stats) return fail(SGZ_EINVAL, "null argument");
+    uint64_t cols = 0;
+    sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols);
+    if (st != SGZ_OK) return st;
+    if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "sgz_overview_stats_view_host: an image, the records, the means or any of them");
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    constexpr size_t recordFloats = sizeof(sgz_overview_stat_record) / sizeof(float);
+    const size_t column = size_t(p.C) * p.P, m = x1 - x0;
+    if ((st = ensureCap(&p.d_ovsViewIn, &p.ovsViewInCap, m * column * recordFloats)) != SGZ_OK) return st;
+    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, size_t(cols) * p.P)) != SGZ_OK) return st;
+    if (stats_out && (st = ensureCap(&p.d_hostOvStats, &p.hostOvStatsCap, size_t(cols) * column * recordFloats)) != SGZ_OK) return st;
+    if (means_out && (st = ensureCap(&p.d_hostOvMeans, &p.hostOvMeansCap, size_t(cols) * column)) != SGZ_OK) return st;
+    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
+    sgz_overview_stat_record *d_in = reinterpret_cast<sgz_overview_stat_record *>(p.d_ovsViewIn);
+    sgz_overview_stat_record *d_out = stats_out ? reinterpret_cast<sgz_overview_stat_record *>(p.d_hostOvStats) : nullptr;
+    float *d_means = means_out ? p.d_hostOvMeans : nullptr;
+    SGZ_HIP(hipEventRecord(ev[0], s));
+    SGZ_HIP(hipMemcpyAsync(d_in, stats + x0 * column, m * column * sizeof(sgz_overview_stat_record), hipMemcpyHostToDevice, s));
+    SGZ_HIP(hipEventRecord(ev[1], s));
+    if ((st = runOverviewStatsView(p, d_in, m, size_t(cols), 0, d_rgba, d_out, d_means, s)) != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(cols) * p.P * 4, hipMemcpyDeviceToHost, s));
+    if (stats_out) SGZ_HIP(hipMemcpyAsync(stats_out, d_out, size_t(cols) * column * sizeof(sgz_overview_stat_record), hipMemcpyDeviceToHost, s));
+    if (means_out) SGZ_HIP(hipMemcpyAsync(means_out, d_means, size_t(cols) * column * sizeof(float), hipMemcpyDeviceToHost, s));
     SGZ_HIP(hipEventRecord(ev[3], s));
     SGZ_HIP(hipStreamSynchronize(s));
     if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)

@@ -12,18 +12,18 @@
 
 namespace sgz {
 
-__device__ __forceinline__ uint32_t orderKey(uint32_t bits)
+__host__ __device__ __forceinline__ uint32_t orderKey(uint32_t bits)
 {
     if ((bits & 0x7fffffffu) > 0x7f800000u) return 0u;                          // a NaN takes no part
     return bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
 }
-__device__ __forceinline__ uint32_t keyBits(uint32_t key)
+__host__ __device__ __forceinline__ uint32_t keyBits(uint32_t key)
 {
     if (key == 0u) return 0x7fc00000u;                                          // nothing but NaNs
     return key ^ ((key >> 31) ? 0x80000000u : 0xffffffffu);
 }
 
-__device__ __forceinline__ uint32_t orderKeyMin(uint32_t bits) { return orderKey(bits) - 1u; }
-__device__ __forceinline__ uint32_t keyBitsMin(uint32_t keyMin) { return keyBits(keyMin + 1u); }
+__host__ __device__ __forceinline__ uint32_t orderKeyMin(uint32_t bits) { return orderKey(bits) - 1u; }
+__host__ __device__ __forceinline__ uint32_t keyBitsMin(uint32_t keyMin) { return keyBits(keyMin + 1u); }
 
 }  // namespace sgz

@@ -237,11 +237,9 @@ overviewViewEmitKernel(const ViewParams prm)
     });
 }
 
-bool bytesOverlap(const void *a, size_t aBytes, const void *b, size_t bBytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a0 < b0 + bBytes && b0 < a0 + aBytes;
-}
+}  // namespace
+
+namespace sgz {
 
 // what every overview call refuses before anything else happens (message in g_lastError)
 sgz_status checkOverviewStep(uint32_t k, uint64_t held, uint64_t frames)
@@ -252,9 +250,11 @@ sgz_status checkOverviewStep(uint32_t k, uint64_t held, uint64_t frames)
     return SGZ_OK;
 }
 
-}  // namespace
-
-namespace sgz {
+bool bytesOverlap(const void *a, size_t aBytes, const void *b, size_t bBytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + bBytes && b0 < a0 + aBytes;
+}
 
 // The slices of a call that leaves the choice to the library: the smallest count <= min(64, k, frames) with columns x ceil(P / 256) x slices
 // >= 2 workgroups per CU.

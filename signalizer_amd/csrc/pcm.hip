@@ -202,7 +202,8 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // Loudness sgz_loudness_record [ceil(chunk / m) + 1][channels] the loudness lane's.
 // Field sgz_field_record [ceil(chunk / m) + 1][pairs] the stereo-field lane's.
 // Band sgz_band_record [ceil(chunk / m) + 1][channels] the band lane's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kPcmOuts };
+// OvStats sgz_overview_stat_record [columns][C][P] and OvMeans float [columns][C][P] the stats feed's, beside its OvImage.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -319,6 +320,9 @@ struct sgz_pcm_stream {
     // the overview inside the stream: the open column's V [pairs][P], its frame count and its k (meaningful while ovOpen > 0)
     float *d_ovCarry = nullptr;
     uint64_t ovOpen = 0; uint32_t ovK = 0;
+    // the open column is of one kind: ovStats -- it is the mean overview's, its records [pairs][P] in d_ovStatCarry (sgz.h, "The mean overview")
+    bool ovStats = false;
+    sgz_overview_stat_record *d_ovStatCarry = nullptr;
     // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels]),
     // stereo-field (sgz_field_record [2][pairs]) and loudness (two halves of loudnessCarryBytes(ldFilter) * channels bytes; ldCarryCap: what is allocated)
     PcmLane lane[kPcmLanes];
@@ -722,6 +726,56 @@ struct PcmColumnsPart {
     }
 };
 
+// sgz_pcm_stream_feed_overview_stats' part: PcmColumnsPart with the stats reduction behind every slab -- records and means in the place of peaks
+struct PcmStatsPart {
+    uint8_t *rgba; sgz_overview_stat_record *stats; float *means;
+    uint32_t k; int flush;
+    uint64_t need;                                                // the columns the whole feed yields
+    bool rgbaPinned, statsPinned, meansPinned;
+
+    static size_t records(const sgz_pcm_stream &s, uint64_t columns) { return pcmPeaksFloats(s, columns); }     // one per float of the peaks
+
+    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
+    {
+        if (!s.d_ovStatCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovStatCarry), records(s, 1) * sizeof(sgz_overview_stat_record)));
+        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
+        const size_t columns = (s.maxFrames + k - 1) / k + 1;     // the most one piece can close (PcmColumnsPart::reserve)
+        sgz_status st = rgba ? sl.out[kOutOvImage].reserve(pcmImageBytes(s, columns), !rgbaPinned) : SGZ_OK;
+        if (st == SGZ_OK && stats) st = sl.out[kOutOvStats].reserve(records(s, columns) * sizeof(sgz_overview_stat_record), !statsPinned);
+        if (st == SGZ_OK && means) st = sl.out[kOutOvMeans].reserve(records(s, columns) * sizeof(float), !meansPinned);
+        return st;
+    }
+    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t total, uint64_t frames, bool last, uint64_t *units) const
+    {
+        const int pieceFlush = flush && last;
+        const uint64_t t = s.ovOpen + frames;
+        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
+        uint8_t *d_rgba = rgba ? sl.out[kOutOvImage].as<uint8_t>() : nullptr;
+        sgz_overview_stat_record *d_stats = stats ? sl.out[kOutOvStats].as<sgz_overview_stat_record>() : nullptr;
+        float *d_means = means ? sl.out[kOutOvMeans].as<float>() : nullptr;
+        sgz_status st = SGZ_OK;
+        if (frames) {
+            const SlabTrack track{s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>()};
+            st = runOverviewStatsSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovStatCarry, s.d_state, d_rgba,
+                                       d_stats, d_means, s.compute, s.track.armed() ? &track : nullptr);
+        } else if (*units) {                                       // no frame arrives and the open column is flushed
+            st = runOverviewStatsColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovStatCarry, d_rgba, d_stats, d_means, s.compute);
+        }
+        if (st != SGZ_OK) return st;
+        s.ovOpen = pieceFlush ? 0 : t % k;
+        s.ovK = k;
+        s.ovStats = s.ovOpen != 0;
+        return SGZ_OK;
+    }
+    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
+    {
+        sgz_status st = rgba ? sl.out[kOutOvImage].readBack(rgba + pcmImageBytes(s, done), pcmImageBytes(s, columns), rgbaPinned, s.back) : SGZ_OK;
+        if (st == SGZ_OK && stats) st = sl.out[kOutOvStats].readBack(stats + records(s, done), records(s, columns) * sizeof(sgz_overview_stat_record), statsPinned, s.back);
+        if (st == SGZ_OK && means) st = sl.out[kOutOvMeans].readBack(means + records(s, done), records(s, columns) * sizeof(float), meansPinned, s.back);
+        return st;
+    }
+};
+
 // what the two one-shot calls share: a stream with no more device and pinned memory than the buffer needs, SGZ_SKIPPED_FRAME where nothing
 // comes out, the feed, and the wall time around all of it.  units(s): what the feed will yield; feed(s, units): the feed call
 template <typename Units, typename Feed>
@@ -780,7 +834,7 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry}) if (p) (void)hipFree(p);
     for (PcmLane &l : s->lane) if (l.d_carry) (void)hipFree(l.d_carry);
     if (s->d_ldScratch) (void)hipFree(s->d_ldScratch);
     if (s->d_bdScratch) (void)hipFree(s->d_bdScratch);
@@ -852,7 +906,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     SGZ_HIP(hipMemsetAsync(s->d_state, 0, pcmStateBytes(*s), s->compute));          // (in order behind whatever the last feed left there: nothing)
     SGZ_HIP(hipStreamSynchronize(s->compute));
     s->held = 0;
-    s->ovOpen = 0;                                                                  // an open overview column is dropped
+    s->ovOpen = 0; s->ovStats = false;                                              // an open overview column, of either kind, is dropped
     for (int id = 0; id < kPcmSinks; ++id) s->sink(id).cursor = 0;                  // every lane's columns and the track's records start over; all stay armed
     for (PcmLane &l : s->lane) l.open = 0;                                          // open columns are dropped
     s->tpContinued = s->ldContinued = false;                                        // the true-peak and loudness histories are zeros again
@@ -867,7 +921,8 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     const auto t0 = PcmClock::now();
     if (!s) return fail(SGZ_EINVAL, "null stream");
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null pcm");
-    if (s->ovOpen) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: an overview column is open -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
+    if (s->ovOpen) return fail(SGZ_EINVAL, s->ovStats ? "sgz_pcm_stream_feed: a mean overview's column is open -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first"
+                                                      : "sgz_pcm_stream_feed: an overview column is open -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
     const uint64_t need = sgz_pcm_stream_frames_for(s, nsamples);
     if (frames_out) *frames_out = need;
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
@@ -909,6 +964,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: null pcm");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
+    if (s->ovOpen && s->ovStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -929,6 +985,42 @@ sgz_status sgz_spectrogram_overview_pcm(const sgz_spectrum_config *cfg, const vo
     return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
                       [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
                       [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview(s, pcm, nsamples, k, 1, rgba_out, peaks_out, columns, &columns, timing); });
+}
+
+// ---- the mean overview inside the stream (sgz.h, "The mean overview") ----------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_feed_overview_stats(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush, uint8_t *rgba_out,
+                                              sgz_overview_stat_record *stats_out, float *means_out, uint64_t capacity_columns, uint64_t *columns_out,
+                                              sgz_pcm_timing *timing)
+{
+    const auto t0 = PcmClock::now();
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: null pcm");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
+    if (reinterpret_cast<uintptr_t>(stats_out) % alignof(sgz_overview_stat_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: stats_out is not aligned to 8 bytes");
+    if (s->ovOpen && !s->ovStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
+    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: k differs from the open column's -- flush or reset first");
+    uint64_t need = 0;
+    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
+    if (columns_out) *columns_out = need;
+    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: capacity_columns below what this feed yields (see *columns_out)");
+    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
+    PcmStatsPart part{rgba_out, stats_out, means_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && stats_out && isPinnedHost(stats_out),
+                      need && means_out && isPinnedHost(means_out)};
+    // (a feed without samples still has one piece when it flushes an open column)
+    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+}
+
+sgz_status sgz_spectrogram_overview_stats_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                              const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
+                                              sgz_overview_stat_record *stats_out, float *means_out, sgz_pcm_timing *timing)
+{
+    if (!cfg || !pcm) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
+    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
+                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
+                      [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_stats(s, pcm, nsamples, k, 1, rgba_out, stats_out, means_out, columns, &columns, timing); });
 }
 
 // ---- the lanes' calls ---------------------------------------------------------------------------------------------------------------------------

@@ -163,6 +163,11 @@ struct Plan {
     float *d_ovLines = nullptr, *d_ovCarry = nullptr, *d_ovCarryCopy = nullptr, *d_ovState = nullptr, *d_ovPartial = nullptr, *d_hostOvPeaks = nullptr;
     size_t ovLinesCap = 0, ovCarryCap = 0, ovCarryCopyCap = 0, ovStateCap = 0, ovPartialCap = 0, hostOvPeaksCap = 0;
     float *d_ovViewIn = nullptr; size_t ovViewInCap = 0;  // sgz_overview_view_host: the device copy of the range's source columns [m][pairs][P]
+    // the mean overview (overview_stats.hip; sgz_spectrogram_overview_stats_device / _host, the stats views), counted in floats as every
+    // ensureCap block, 6 per sgz_overview_stat_record: the open column's records [pairs][P], their snapshot, the partial records of the
+    // sliced forms, the host forms' device copies of records and means, and the host view's copy of the range's source columns
+    float *d_ovsCarry = nullptr, *d_ovsCarryCopy = nullptr, *d_ovsPartial = nullptr, *d_hostOvStats = nullptr, *d_hostOvMeans = nullptr, *d_ovsViewIn = nullptr;
+    size_t ovsCarryCap = 0, ovsCarryCopyCap = 0, ovsPartialCap = 0, hostOvStatsCap = 0, hostOvMeansCap = 0, ovsViewInCap = 0;
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;

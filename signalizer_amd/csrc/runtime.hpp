@@ -97,6 +97,8 @@ uint32_t overviewAutoSlices(long columns, uint32_t blocks, uint32_t k, size_t fr
 // the view of kept peaks (overview.hip): d_src [m][pairs][P], the range's first source column -> cols <= m output columns; the arguments are
 // sgz_stage_overview_view's, checked by the caller; asynchronous on `stream`, plan scratch grows on demand
 sgz_status checkViewRange(uint64_t n, uint64_t x0, uint64_t x1, uint32_t outColumns, uint64_t *cols);
+sgz_status checkOverviewStep(uint32_t k, uint64_t held, uint64_t frames);          // what every overview stage call refuses first: k == 0, held >= k
+bool bytesOverlap(const void *a, size_t aBytes, const void *b, size_t bBytes);       // two non-null byte ranges share a byte (the views' outputs against their source)
 sgz_status runOverviewView(Plan &p, const float *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba, float *d_peaksOut, hipStream_t stream);
 // the overview render's slab loop (api.hip): `frames` frames from d_planar behind `held` frames of an open column whose V is in d_carry; the
 // columns that close go to d_rgba / d_peaks from their first element on, the open one stays in d_carry unless `flush`.  d_state: the decay
@@ -107,6 +109,17 @@ struct SlabTrack { uint32_t graph; double mouseFraction; sgz_line_peak *d_out; }
 sgz_status runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
                             int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t stream,
                             const SlabTrack *track = nullptr);
+// the mean overview (overview_stats.hip): the twins of runOverviewColumns and runOverviewView on sgz_overview_stat_record, with the means as
+// one more output; the arguments are sgz_stage_overview_stats' / sgz_stage_overview_stats_view's, checked by the caller
+sgz_status runOverviewStatsColumns(Plan &p, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                                   sgz_overview_stat_record *d_carry, uint8_t *d_rgba, sgz_overview_stat_record *d_stats, float *d_means,
+                                   hipStream_t stream);
+sgz_status runOverviewStatsView(Plan &p, const sgz_overview_stat_record *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba,
+                                sgz_overview_stat_record *d_statsOut, float *d_means, hipStream_t stream);
+// ... and of runOverviewSlabs: the same slab loop with the stats reduction behind every slab
+sgz_status runOverviewStatsSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
+                                 int flush, sgz_overview_stat_record *d_carry, float *d_state, uint8_t *d_rgba, sgz_overview_stat_record *d_stats,
+                                 float *d_means, hipStream_t stream, const SlabTrack *track = nullptr);
 // the waveform lane's reduction (wave_columns.hip): (lo, hi) per column of m samples and channel, the open column in a carry; what
 // sgz_stage_wave_columns and sgz_pcm_stream share.  The arguments are the stage call's, checked by the caller; asynchronous on `stream`
 struct WaveColumnsShape {
