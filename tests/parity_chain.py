@@ -11,6 +11,11 @@ magnitude crosses a uint8 truncation.  Instead of a blanket "x % of bytes may di
      winner to <= TIE_REL;
   2. mapping given bins: bit-exact (tests/test_gpu_spectrum.py::test_mapping_bit_exact_given_bins, test_gpu_phase.py);
   3. colour given mapped pixels: render(x) == oracle_decay_colour(K_A(x)) byte for byte -- checked here on every case.
+
+Links 2 and 3 are exact *against the oracle*, which the same reader wrote as the kernels.  What both could have misread -- which bins a
+pixel shows, where the break falls, the decay, the dB scale, the gradient -- is held to a numpy restatement that shares no code with
+either, tests/fp64_map.py: the oracle in tests/test_map_fp64_host.py, every map form of the kernels in tests/test_gpu_map_fp64.py
+(every mode but Phase, which keeps the tie rule above and tests/test_gpu_phase.py).
 """
 import numpy as np
 
