@@ -3,14 +3,16 @@
 // lane"); and the lane's host helpers: the Oscilloscope's crossover of a sample rate, the tap table, the fold of kept records, the readout of
 // a run of columns and the colours the Oscilloscope draws them with.  gfx950 only.  The reference's counterpart is live
 // (StreamState::audioProcessing; scope_stream.hip scopeIngestKernel phase F); this is the same network per column of a file.
-//   The loudness lane's formulation (loudness_columns.hip) with another filter: v = (int32) clamp(rintf(x 2^23), +-2^26), a NaN is v = 0 and
-//   is not counted.  The sample axis is cut into segments of L samples on an absolute grid.  The 16 state components of the crossover tree at
+// What the column lanes share is column_lanes.hpp, and so is what this lane shares with the loudness lane alone (section 4 there: the tap
+// table on the device, the carry's layout and history kernel, the run tile's geometry, the column sums); this file is the crossover tree, its
+// tap table, the run kernel and the record's readouts.
+//   v = the quantiser's (quantiseSilent): a NaN is v = 0 and is not counted.  The sample axis is cut into segments of L samples on an absolute grid.  The 16 state components of the crossover tree at
 //   a segment's start are exact integer FIRs over the last W quantised samples (taps at 2^30, 64-bit sums, any order), converted to fp64
 //   once; from there the fp64 recurrence of the eight sections runs over the segment's L samples in one fixed order with no contraction (the
 //   pragma below, for host and device alike).  q_b = rint(z_b) clamped to 32 bits for the three bands, the record sums q_b^2 in 128 bits.
 // Three steps, each a launch of its own behind the other (no hand-off between workgroups inside a launch):
 //   bandRunKernel       one workgroup per (tile of T = max(4096, L) samples on the segment grid, channel).  The tile goes to LDS quantised,
-//                       behind a W-sample halo, as the loudness lane's.  Segment-start dot products: the 256 lanes are T / L segments x P
+//                       behind a W-sample halo.  Segment-start dot products: the 256 lanes are T / L segments x P
 //                       lanes; the 16 components are taken four at a time (one 16-byte row C[g][k][0..3] and one sample per four
 //                       multiply-adds), a lane walks taps k = sub, sub + P, ..; the P partial sums are folded by wave shuffles (through LDS
 //                       where P > 64).  The runs: the tree is three independent chains -- lp1a lp1b (low); hp1a hp1b lp2a lp2b (mid); hp1a
@@ -19,38 +21,35 @@
 //                       kBdStage / segments steps: a round leaves its q in three staging planes, which the workgroup then stores in rows to
 //                       stream-ordered scratch [3][channels][n].  A segment that began before the call is re-run from its start out of the
 //                       history; its earlier samples are not stored.
-//   bandHistoryKernel   the new carry but for an open column: the last W + L - 1 quantised samples of (the old history, the call).  (The
-//                       loudness lane's kernel is not reused: its record is 32 bytes and its parameter block its own.)
-//   the column sums     of the three q^2 and of the non-NaN samples in one pass over the planes, in the level lane's structure: m <=
-//                       kBdSwitch (1024) bandSumTileKernel; longer columns or slices >= 2 bandSumSliceKernel into partial records
-//                       [slices][columns][channels] + bandEmitKernel.  A flush without samples is the emit kernel alone, on the carry.
+//   historyKernel       the new carry but for an open column: the last W + L - 1 quantised samples of (the old history, the call).
+//   the column sums     of the three q^2 and of the non-NaN samples in one pass over the planes (BdAcc): m <= kBdSwitch (1024)
+//                       sumTileKernel; longer columns or slices >= 2 sumSliceKernel + sumEmitKernel.  A flush without samples is the emit
+//                       kernel alone, on the carry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <mutex>
 #include <vector>
 
 #include "runtime.hpp"
-#include "scope_ring.hpp"      // StreamScratch
 
 // The definition's step is one IEEE operation per *, + and -: nothing in this file may be contracted into an FMA, on the host (the tap table,
 // the colours) or on the device (the segment runs).  hipcc contracts by default.
 #pragma clang fp contract(off)
 
+#include "column_lanes.hpp"    // (behind the pragma: what is instantiated from it here is not contracted either)
+
 using namespace sgz;
 
 namespace {
 
-constexpr int kBdThreads = 256;
-constexpr uint32_t kBdTile = 4096;               // samples of a run tile (a segment longer than this is a tile of its own) and of a sum tile
+constexpr int kBdThreads = kTwinThreads;
+constexpr uint32_t kBdTile = kTwinTile;              // samples of a run tile (a segment longer than this is a tile of its own) and of a sum tile
 constexpr uint32_t kBdSwitch = 1024;             // the switch-over of the column sums: longer columns take the sliced form
 constexpr uint32_t kBdStage = 1024;              // samples of a tile that one round of the runs leaves in the staging planes
-constexpr uint32_t kBdMaxSlices = 64, kBdMaxChannels = 64;
-constexpr uint32_t kBdMaxW = 65536, kBdMinL = 16;
-constexpr uint32_t kBdDeviceMaxW = 16384;        // the halo and a tile fit the 160 KiB of LDS up to here
+constexpr uint32_t kBdMaxChannels = 64;
 constexpr uint32_t kBdBatch = 8;                 // loads a lane of the run kernel issues before it uses the first
 constexpr uint32_t kBdRun = 16;                  // samples of a lane in the sum tile
 constexpr uint32_t kBdComps = 16, kBdChainWords = 20;      // state components; doubles of a segment's three chains in LDS (4 + 8 + 8)
@@ -88,14 +87,10 @@ BdCoef coefOf(const sgz_band_filter &f)
     return c;
 }
 
-bool pow2(uint32_t v) { return v && !(v & (v - 1)); }
-
-bool shapeOk(const sgz_band_filter &f) { return pow2(f.W) && pow2(f.L) && f.L >= kBdMinL && f.L <= f.W && f.W <= kBdMaxW; }
-
 // C[c][k] at taps[c * W + k]; false where the filter is refused
 bool buildTaps(const sgz_band_filter &f, int32_t *taps)
 {
-    if (!shapeOk(f)) return false;
+    if (!filterShapeOk(f)) return false;
     const BdCoef c = coefOf(f);
     double z[kBdComps] = {}, bands[3];
     uint64_t sum[kBdComps] = {};
@@ -112,38 +107,11 @@ bool buildTaps(const sgz_band_filter &f, int32_t *taps)
     return *std::max_element(sum, sum + kBdComps) < kBdTapSumBound;
 }
 
-// ---- the table on the device: one per (device, filter), made at the filter's first use and kept ----------------------------------------------
-struct DeviceTaps { int dev; sgz_band_filter f; int4 *d; };
-std::mutex g_tapsMutex;
-std::vector<DeviceTaps> g_taps;
-
-// rows C[g][k][0..3] of 16 bytes, g = 0 .. 3 the four components 4 g .. 4 g + 3; the first use of a filter on a device uploads them (the one
-// blocking step of the stage call)
-sgz_status deviceTaps(const sgz_band_filter &f, const int4 **out)
-{
-    int dev = 0;
-    SGZ_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_tapsMutex);
-    for (const DeviceTaps &t : g_taps)
-        if (t.dev == dev && std::memcmp(&t.f, &f, sizeof f) == 0) { *out = t.d; return SGZ_OK; }
-    std::vector<int32_t> planes(size_t(kBdComps) * f.W), rows(size_t(kBdComps) * f.W);
-    if (!buildTaps(f, planes.data())) return fail(SGZ_EINVAL, "band: the filter is refused (sgz_band_taps)");
-    for (uint32_t g = 0; g < 4; ++g)
-        for (uint32_t k = 0; k < f.W; ++k)
-            for (uint32_t q = 0; q < 4; ++q) rows[(size_t(g) * f.W + k) * 4 + q] = planes[size_t(g * 4 + q) * f.W + k];
-    DeviceTaps t{dev, f, nullptr};
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&t.d), rows.size() * sizeof(int32_t)));
-    if (const hipError_t e = hipMemcpy(t.d, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice); e != hipSuccess) {
-        (void)hipFree(t.d);
-        return hipFail(e, "hipMemcpy(band taps)");
-    }
-    g_taps.push_back(t);
-    *out = t.d;
-    return SGZ_OK;
-}
+sgz_status tapsOnDevice(const sgz_band_filter &f, const int4 **out) { return deviceTaps(f, kBdComps, buildTaps, "band", out); }
 
 // ---- the kernels ------------------------------------------------------------------------------------------------------------------------------
 struct BandParams {
+    typedef sgz_band_record Record;
     const float *planar;                 // [channels][stride]
     size_t stride;
     long n;
@@ -155,7 +123,7 @@ struct BandParams {
     uint32_t tile, segs, logSegs, lanesPer;  // the run tile: T samples = segs segments, lanesPer = 256 / segs lanes per segment in the dot products
     uint32_t stage, perRound, logRound, rounds;  // a round: perRound = stage / segs steps of every segment; rounds = L / perRound
     uint32_t phase;                      // first_index % L: the call's first sample within its segment
-    uint32_t perTile, group, slices;     // the column sums, as the loudness lane's
+    uint32_t perTile, group, slices;     // the column sums (column_lanes.hpp sumTileKernel)
     BdCoef coef;
     const int4 *taps;                    // [4][W]: C[g][k][0..3]
     const uint8_t *carryIn;              // [channels][carryBytes]: the open column, then the history (oldest first), then a zero word
@@ -166,33 +134,6 @@ struct BandParams {
     sgz_band_record *out;                // [closed][channels]
     sgz_band_record *partial;            // [slices][columns][channels]
 };
-
-__device__ __forceinline__ const sgz_band_record *carryOpen(const uint8_t *carry, size_t bytes, uint32_t ch)
-{
-    return reinterpret_cast<const sgz_band_record *>(carry + size_t(ch) * bytes);
-}
-__device__ __forceinline__ const int32_t *carryHist(const uint8_t *carry, size_t bytes, uint32_t ch)
-{
-    return reinterpret_cast<const int32_t *>(carry + size_t(ch) * bytes + sizeof(sgz_band_record));
-}
-
-// the quantiser, 0 for a NaN (x 2^23 is exact or overflows to an infinity, which the clamp takes)
-__device__ __forceinline__ int32_t quantise(float x)
-{
-    const float r = __builtin_amdgcn_fmed3f(rintf(x * 0x1p23f), -0x1p26f, 0x1p26f);
-    return x != x ? 0 : int32_t(r);
-}
-
-// what the filter sees at sample r of the call, r >= -hist: the call's own sample, the carried history in front of it, zeros behind the call
-__device__ __forceinline__ int32_t filterInput(const BandParams &prm, uint32_t ch, long r)
-{
-    if (r >= prm.n) return 0;
-    if (r >= 0) return quantise(prm.planar[size_t(ch) * prm.stride + size_t(r)]);
-    return prm.continued ? carryHist(prm.carryIn, prm.carryBytes, ch)[long(prm.hist) + r] : 0;
-}
-
-// LDS word of the tile's sample index i (0 = the halo's first): a shift of lanesPer words per segment keeps the segments' lanes on different banks
-__device__ __forceinline__ uint32_t bdWord(const BandParams &prm, uint32_t i) { return i + (i >> prm.logL) * prm.lanesPer; }
 
 // component c of segment seg's start state into the chains' words: [0..3] lp1a lp1b; [4..11] hp1a hp1b lp2a lp2b; [12..19] hp1a hp1b hp2a hp2b
 __device__ __forceinline__ void putStart(double *chains, uint32_t seg, uint32_t c, double v)
@@ -229,7 +170,7 @@ bandRunKernel(const BandParams prm)
 #pragma unroll
         for (uint32_t j = 0; j < kBdBatch; ++j) {
             const uint32_t i = base + j * kBdThreads;
-            if (i < words) tile[bdWord(prm, i)] = v[j];
+            if (i < words) tile[segmentWord(prm, i)] = v[j];
         }
     }
     __syncthreads();
@@ -248,7 +189,7 @@ bandRunKernel(const BandParams prm)
 #pragma unroll
                 for (uint32_t j = 0; j < kBdBatch; ++j) {
                     c[j] = taps[k + j * prm.lanesPer];
-                    v[j] = tile[bdWord(prm, before - (k + j * prm.lanesPer))];
+                    v[j] = tile[segmentWord(prm, before - (k + j * prm.lanesPer))];
                 }
 #pragma unroll
                 for (uint32_t j = 0; j < kBdBatch; ++j) {
@@ -302,7 +243,7 @@ bandRunKernel(const BandParams prm)
             double *st = chains + size_t(s) * kBdChainWords + (chain == 0u ? 0u : chain == 1u ? 4u : 12u);
             double z0 = st[0], z1 = st[1], z2 = st[2], z3 = st[3], z4 = 0.0, z5 = 0.0, z6 = 0.0, z7 = 0.0;
             if (chain) { z4 = st[4]; z5 = st[5]; z6 = st[6]; z7 = st[7]; }
-            const int32_t *in = tile + bdWord(prm, prm.W + s * prm.L);                   // (a segment's words are consecutive: j < L)
+            const int32_t *in = tile + segmentWord(prm, prm.W + s * prm.L);                   // (a segment's words are consecutive: j < L)
             int32_t *to = staged + chain * plane + s * (prm.perRound + 1u);
             for (uint32_t j = j0; j < j1; ++j) {
                 double y = bdSection(a, z2, z3, bdSection(a, z0, z1, double(in[j])));
@@ -325,19 +266,6 @@ bandRunKernel(const BandParams prm)
     }
 }
 
-// the carry of a call with samples but for an open column's record: the history, the zero word behind it, an all-zero open column (an open
-// column's record is stored by the sums' launch behind this one)
-__global__ void __launch_bounds__(kBdThreads)
-bandHistoryKernel(const BandParams prm)
-{
-    const uint32_t t = blockIdx.x * kBdThreads + threadIdx.x, ch = blockIdx.y;
-    uint8_t *mine = prm.carryOut + size_t(ch) * prm.carryBytes;
-    int32_t *hist = reinterpret_cast<int32_t *>(mine + sizeof(sgz_band_record));
-    if (t < prm.hist) hist[t] = filterInput(prm, ch, prm.n - long(prm.hist) + long(t));
-    if (t == prm.hist) hist[t] = 0;
-    if (t < sizeof(sgz_band_record) / 4) reinterpret_cast<uint32_t *>(mine)[t] = 0u;
-}
-
 // a column's, a lane's or a slice's part of a record: three 128-bit sums of q^2 and the count
 struct BdAcc {
     uint64_t lo[3], hi[3];
@@ -347,6 +275,15 @@ struct BdAcc {
         const uint64_t s = uint64_t(int64_t(q) * int64_t(q));
         lo[b] += s;
         hi[b] += lo[b] < s ? 1u : 0u;
+    }
+    __device__ __forceinline__ void takeSample(const BandParams &prm, uint32_t ch, long r)
+    {
+        const size_t plane = size_t(prm.channels) * prm.qStride, at = size_t(ch) * prm.qStride + size_t(r);
+        addSquare(0, prm.q[at]);
+        addSquare(1, prm.q[plane + at]);
+        addSquare(2, prm.q[2 * plane + at]);
+        const float x = prm.planar[size_t(ch) * prm.stride + size_t(r)];
+        count += x != x ? 0u : 1u;
     }
     __device__ __forceinline__ void add(int b, uint64_t l, uint64_t h)
     {
@@ -375,116 +312,6 @@ struct BdAcc {
     }
 };
 
-// samples [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnSamples(const BandParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.m) - long(prm.held);
-    b = a + long(prm.m);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
-}
-
-__device__ __forceinline__ void takeSample(const BandParams &prm, uint32_t ch, long r, BdAcc &k)
-{
-    const size_t plane = size_t(prm.channels) * prm.qStride, at = size_t(ch) * prm.qStride + size_t(r);
-    k.addSquare(0, prm.q[at]);
-    k.addSquare(1, prm.q[plane + at]);
-    k.addSquare(2, prm.q[2 * plane + at]);
-    const float x = prm.planar[size_t(ch) * prm.stride + size_t(r)];
-    k.count += x != x ? 0u : 1u;
-}
-
-// the carry into column 0, then to the output (a closed column) or to the carry's open column
-__device__ __forceinline__ void emitColumn(const BandParams &prm, long col, uint32_t ch, BdAcc k)
-{
-    if (col == 0 && prm.held) k.add(*carryOpen(prm.carryIn, prm.carryBytes, ch));
-    k.store(col < prm.closed ? prm.out + size_t(col) * prm.channels + ch
-                             : reinterpret_cast<sgz_band_record *>(prm.carryOut + size_t(ch) * prm.carryBytes));
-}
-
-// workgroup (tile of perTile whole columns, channel): groups of prm.group lanes per column, the lanes of a group stride over its samples
-__global__ void __launch_bounds__(kBdThreads)
-bandSumTileKernel(const BandParams prm)
-{
-    const uint32_t tid = threadIdx.x, ch = blockIdx.y;
-    const long c0 = long(blockIdx.x) * long(prm.perTile);
-    const long c1 = c0 + long(prm.perTile) < prm.columns ? c0 + long(prm.perTile) : prm.columns;
-    const uint32_t G = prm.group, sub = tid & (G - 1u), grp = tid / G, groups = uint32_t(kBdThreads) / G;
-    const uint32_t cols = uint32_t(c1 - c0);
-    for (uint32_t base = 0; base < cols; base += groups) {                  // (the same trips in every lane: the cross-lane steps see whole waves)
-        const uint32_t lc = base + grp;
-        const bool mine = lc < cols;
-        BdAcc k{{0, 0, 0}, {0, 0, 0}, 0};
-        if (mine) {
-            long a, b;
-            columnSamples(prm, c0 + long(lc), a, b);
-            for (long r = a + long(sub); r < b; r += long(G)) takeSample(prm, ch, r, k);
-        }
-        for (uint32_t o = G >> 1; o > 0; o >>= 1) k.foldLane(int(o));
-        if (mine && sub == 0) emitColumn(prm, c0 + long(lc), ch, k);
-    }
-}
-
-// slice blockIdx.z of column blockIdx.x's samples of channel blockIdx.y (an empty slice leaves the zero record)
-__global__ void __launch_bounds__(kBdThreads)
-bandSumSliceKernel(const BandParams prm)
-{
-    __shared__ sgz_band_record waves[kBdThreads / 64];
-    const long col = long(blockIdx.x);
-    const uint32_t ch = blockIdx.y, s = blockIdx.z, tid = threadIdx.x;
-    long a, b;
-    columnSamples(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(s) * per < b ? a + long(s) * per : b, sb = sa + per < b ? sa + per : b;
-    BdAcc k{{0, 0, 0}, {0, 0, 0}, 0};
-    for (long r = sa + long(tid); r < sb; r += long(kBdThreads)) takeSample(prm, ch, r, k);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) k.foldLane(o);
-    if ((tid & 63u) == 0) k.store(&waves[tid >> 6]);
-    __syncthreads();
-    if (tid == 0) {
-#pragma unroll
-        for (int v = 1; v < kBdThreads / 64; ++v) k.add(waves[v]);
-        k.store(prm.partial + (size_t(s) * size_t(prm.columns) + size_t(col)) * prm.channels + ch);
-    }
-}
-
-// one thread per (column, channel): the fold of the slices (none: a flush of the carry alone), the carry, the store
-__global__ void __launch_bounds__(kBdThreads)
-bandEmitKernel(const BandParams prm)
-{
-    const size_t at = size_t(blockIdx.x) * kBdThreads + threadIdx.x, perSlice = size_t(prm.columns) * prm.channels;
-    if (at >= perSlice) return;
-    const long col = long(at / prm.channels);
-    const uint32_t ch = uint32_t(at % prm.channels);
-    BdAcc k{{0, 0, 0}, {0, 0, 0}, 0};
-    for (uint32_t s = 0; s < prm.slices; ++s) k.add(prm.partial[size_t(s) * perSlice + at]);
-    emitColumn(prm, col, ch, k);
-}
-
-uint32_t pow2AtLeast(uint32_t v)
-{
-    uint32_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-uint32_t log2Of(uint32_t v)
-{
-    uint32_t l = 0;
-    while ((1u << l) < v) ++l;
-    return l;
-}
-
-uint32_t runTileOf(const sgz_band_filter &f) { return std::max(kBdTile, f.L); }
-size_t qStrideOf(size_t nsamples) { return (nsamples + 3) & ~size_t(3); }
-
-uint32_t runTileWords(const sgz_band_filter &f)
-{
-    const uint32_t tile = runTileOf(f), lanesPer = uint32_t(kBdThreads) / (tile / f.L);
-    return ((f.W + tile) + ((f.W + tile) / f.L + 1) * lanesPer + 3u) & ~3u;
-}
-
 // the chains' states, the halo and the tile, and the block the partial dot products and the staging planes share (at most 143 KiB of the
 // 160: W = 16384 with L = 16 or L = 16384)
 size_t runLdsBytes(const sgz_band_filter &f)
@@ -494,54 +321,18 @@ size_t runLdsBytes(const sgz_band_filter &f)
     return size_t(segs) * kBdChainWords * 8 + size_t(runTileWords(f)) * 4 + std::max(staged, part);
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: remember what has been granted
-sgz_status grantRunLds(size_t need)
-{
-    static size_t granted[64] = {};
-    static std::mutex mutex;
-    int dev = 0;
-    SGZ_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mutex);
-    if (dev >= 0 && dev < 64 && granted[dev] >= need) return SGZ_OK;
-    SGZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bandRunKernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(need)));
-    if (dev >= 0 && dev < 64) granted[dev] = need;
-    return SGZ_OK;
-}
-
-sgz_status filterForDevice(const sgz_band_filter *f, const char *who)
-{
-    if (!f) return fail(SGZ_EINVAL, std::string(who) + ": null filter");
-    if (!shapeOk(*f)) return fail(SGZ_EINVAL, std::string(who) + ": W and L are powers of two, 16 <= L <= W <= 65536");
-    if (f->W > kBdDeviceMaxW) return fail(SGZ_EINVAL, std::string(who) + ": the device takes W <= 16384");
-    return SGZ_OK;
-}
-
 }  // namespace
 
 namespace sgz {
 
 size_t bandCarryBytes(const sgz_band_filter &f) { return sizeof(sgz_band_record) + size_t(f.W + f.L) * sizeof(int32_t); }
 
-// The shape of a call whose arguments passed sgz_stage_band_columns' checks, as loudnessColumnsShape; scratchBytes: q [3][channels][n rounded
-// up to 4] and behind it the partial records of the sliced form.
-BandColumnsShape bandColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
+ColumnsShape bandColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
 {
-    BandColumnsShape sh{};
-    const uint64_t t = uint64_t(held) + nsamples;
-    sh.closed = t / m + ((flush && t % m) ? 1u : 0u);
-    sh.open = !flush && t % m != 0;
-    sh.columns = sh.closed + (sh.open ? 1u : 0u);
-    sh.launch = sh.columns != 0 && !(nsamples == 0 && !(flush && held));
-    if (!sh.launch || nsamples == 0) return sh;
-    if (slices >= 2 || m > kBdSwitch) sh.slices = slices ? slices : overviewAutoSlices(long(sh.columns), channels, m, nsamples, numCUs());
-    sh.scratchBytes = size_t(3) * qStrideOf(nsamples) * channels * sizeof(int32_t) + size_t(sh.slices) * size_t(sh.columns) * channels * sizeof(sgz_band_record);
-    return sh;
+    return columnsShape(channels, nsamples, m, held, flush, slices, kBdSwitch, sizeof(sgz_band_record), size_t(3) * qStrideOf(nsamples) * channels * sizeof(int32_t));
 }
 
-// sgz_stage_band_columns behind its argument checks, with the carry in two places: carryIn is read (the history when `continued`, the open
-// column when held > 0), carryOut is written whole by every call with samples -- never the same memory then.  scratch: sh.scratchBytes bytes,
-// aligned to 16.
-sgz_status runBandColumns(const BandColumnsShape &sh, const sgz_band_filter &f, const float *d_planar, size_t channelStride, uint32_t channels,
+sgz_status runBandColumns(const ColumnsShape &sh, const sgz_band_filter &f, const float *d_planar, size_t channelStride, uint32_t channels,
                           size_t nsamples, uint64_t firstIndex, uint32_t m, uint32_t held, uint32_t continued, const void *carryIn, void *carryOut,
                           sgz_band_record *d_out, void *scratch, hipStream_t stream)
 {
@@ -562,29 +353,29 @@ sgz_status runBandColumns(const BandColumnsShape &sh, const sgz_band_filter &f, 
     prm.out = d_out;
     prm.partial = reinterpret_cast<sgz_band_record *>(static_cast<uint8_t *>(scratch) + size_t(3) * prm.qStride * channels * sizeof(int32_t));
     const uint64_t cells = sh.columns * channels;
-    if (sh.columns > 0x7fffffffull || (cells + kBdThreads - 1) / kBdThreads > 0x7fffffffull) return fail(SGZ_EINVAL, "band columns: too many columns for one launch");
+    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kBdThreads)), "band", "columns"); st != SGZ_OK) return st;
     if (nsamples != 0) {
-        if (sgz_status st = deviceTaps(f, &prm.taps); st != SGZ_OK) return st;
+        if (sgz_status st = tapsOnDevice(f, &prm.taps); st != SGZ_OK) return st;
         const uint64_t tiles = (uint64_t(nsamples) + prm.phase + prm.tile - 1) / prm.tile;
-        if (tiles > 0x7fffffffull) return fail(SGZ_EINVAL, "band columns: too many samples for one launch");
+        if (sgz_status st = fitsOneLaunch(tiles, "band", "samples"); st != SGZ_OK) return st;
         const size_t lds = runLdsBytes(f);
-        if (sgz_status st = grantRunLds(lds); st != SGZ_OK) return st;
+        if (sgz_status st = grantRunLds<bandRunKernel>(lds); st != SGZ_OK) return st;
         hipLaunchKernelGGL(bandRunKernel, dim3(unsigned(tiles), channels), dim3(kBdThreads), lds, stream, prm);
         SGZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(bandHistoryKernel, dim3((prm.hist + 1 + kBdThreads - 1) / kBdThreads, channels), dim3(kBdThreads), 0, stream, prm);
+        hipLaunchKernelGGL(historyKernel<BandParams>, dim3((prm.hist + 1 + kBdThreads - 1) / kBdThreads, channels), dim3(kBdThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
         if (sh.slices == 0) {
             prm.perTile = kBdTile / m;
             prm.group = std::min(pow2AtLeast((m + kBdRun - 1) / kBdRun), 64u);
             const uint64_t sumTiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-            hipLaunchKernelGGL(bandSumTileKernel, dim3(unsigned(sumTiles), channels), dim3(kBdThreads), 0, stream, prm);
+            hipLaunchKernelGGL((sumTileKernel<BandParams, BdAcc>), dim3(unsigned(sumTiles), channels), dim3(kBdThreads), 0, stream, prm);
             SGZ_HIP(hipGetLastError());
             return SGZ_OK;
         }
-        hipLaunchKernelGGL(bandSumSliceKernel, dim3(unsigned(sh.columns), channels, sh.slices), dim3(kBdThreads), 0, stream, prm);
+        hipLaunchKernelGGL((sumSliceKernel<BandParams, BdAcc>), dim3(unsigned(sh.columns), channels, sh.slices), dim3(kBdThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(bandEmitKernel, dim3(unsigned((cells + kBdThreads - 1) / kBdThreads)), dim3(kBdThreads), 0, stream, prm);
+    hipLaunchKernelGGL((sumEmitKernel<BandParams, BdAcc>), dim3(unsigned(emitBlocks(cells, kBdThreads))), dim3(kBdThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     return SGZ_OK;
 }
@@ -607,38 +398,23 @@ sgz_status sgz_stage_band_columns(const float *d_planar, size_t channel_stride, 
                                   uint64_t first_index, uint32_t m, uint32_t held, int flush, uint32_t continued, uint32_t slices, void *d_carry,
                                   sgz_band_record *d_records, void *stream)
 {
-    if (!d_planar) return fail(SGZ_EINVAL, "sgz_stage_band_columns: null d_planar");
-    if (sgz_status st = filterForDevice(filter, "sgz_stage_band_columns"); st != SGZ_OK) return st;
-    if (channels == 0 || channels > kBdMaxChannels) return fail(SGZ_EINVAL, "sgz_stage_band_columns: 1 .. 64 channels");
-    if (m == 0) return fail(SGZ_EINVAL, "sgz_stage_band_columns: m >= 1 samples per column");
-    if (held >= m) return fail(SGZ_EINVAL, "sgz_stage_band_columns: held < m");
-    if (!continued && held) return fail(SGZ_EINVAL, "sgz_stage_band_columns: held > 0 needs continued != 0 (a stream that begins here has no open column)");
-    if (channel_stride < nsamples || nsamples > (size_t(1) << 40)) return fail(SGZ_EINVAL, "sgz_stage_band_columns: channel_stride < nsamples, or more than 2^40 samples");
-    if (first_index > (uint64_t(1) << 62)) return fail(SGZ_EINVAL, "sgz_stage_band_columns: first_index above 2^62");
-    if (slices > kBdMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_band_columns: slices 0 (automatic) or 1 .. 64");
-    if ((reinterpret_cast<uintptr_t>(d_planar) & 3u) || (reinterpret_cast<uintptr_t>(d_carry) & 15u) || (reinterpret_cast<uintptr_t>(d_records) & 15u))
-        return fail(SGZ_EINVAL, "sgz_stage_band_columns: d_planar aligned to 4 bytes, d_carry and d_records to 16");
-    const BandColumnsShape sh = bandColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (!d_carry && (continued || nsamples)) return fail(SGZ_EINVAL, "sgz_stage_band_columns: d_carry is read (continued) or written (nsamples > 0)");
-    if (!d_records && sh.closed) return fail(SGZ_EINVAL, "sgz_stage_band_columns: d_records is written (a column closes)");
+    const StageFront front{"sgz_stage_band_columns", "channels", kBdMaxChannels, "d_records", 16, true, 40};
+    // (the filter's check stands behind d_planar's: checkStageArgs)
+    if (sgz_status st = checkStageArgs(front, filterForDevice(filter, front.who), d_planar, channel_stride, channels, nsamples, m, held, continued, first_index, slices,
+                                       d_carry, d_records); st != SGZ_OK) return st;
+    const ColumnsShape sh = bandColumnsShape(channels, nsamples, m, held, flush, slices);
+    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, continued, d_carry, d_records); st != SGZ_OK) return st;
     if (nsamples) {                                                  // (the table before anything is launched: a refused filter writes nothing)
         const int4 *taps = nullptr;
-        if (sgz_status st = deviceTaps(*filter, &taps); st != SGZ_OK) return st;
+        if (sgz_status st = tapsOnDevice(*filter, &taps); st != SGZ_OK) return st;
     }
     if (!sh.launch) return SGZ_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StreamScratch scratch(s), snapshot(s);
-    const void *carryIn = d_carry;
-    const size_t carryBytes = bandCarryBytes(*filter) * channels;
-    if (continued && nsamples) {
-        // the halos, the history and column 0 read the carry while other workgroups write the new one: they read a snapshot
-        SGZ_HIP(snapshot.get(carryBytes));
-        SGZ_HIP(hipMemcpyAsync(snapshot.p, d_carry, carryBytes, hipMemcpyDeviceToDevice, s));
-        carryIn = snapshot.p;
-    }
-    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
+    StageScratch mem(s);
+    const void *carryIn = nullptr;
+    if (sgz_status st = mem.get(front, sh, nsamples, held, continued, d_carry, bandCarryBytes(*filter) * channels, &carryIn); st != SGZ_OK) return st;
     return runBandColumns(sh, *filter, d_planar, channel_stride, channels, nsamples, first_index, m, held, continued, carryIn, d_carry, d_records,
-                          scratch.p, s);
+                          mem.scratch.p, s);
 }
 
 // ---- host arithmetic ---------------------------------------------------------------------------------------------------------------------------
@@ -687,12 +463,12 @@ sgz_status sgz_band_filter_for_rate(double rate, double low_hz, double high_hz, 
     if (!(rate > 0.0) || !std::isfinite(rate)) return fail(SGZ_EINVAL, "sgz_band_filter_for_rate: rate > 0");
     if (!(low_hz > 0.0) || !(high_hz > low_hz) || !(high_hz < rate / 2)) return fail(SGZ_EINVAL, "sgz_band_filter_for_rate: 0 < low_hz < high_hz < rate / 2");
     const double need = std::ceil(6.0 * rate / low_hz);
-    if (!(need <= double(kBdMaxW))) return fail(SGZ_EINVAL, "sgz_band_filter_for_rate: 6 rate / low_hz above 65536 samples of memory");
+    if (!(need <= double(kTwinMaxW))) return fail(SGZ_EINVAL, "sgz_band_filter_for_rate: 6 rate / low_hz above 65536 samples of memory");
     sgz_band_filter r{};
     const double f1 = double(float(low_hz / rate)), f2 = double(float(high_hz / rate));
     butterworthSection(f1, false, r.c[0]); butterworthSection(f1, true, r.c[1]);
     butterworthSection(f2, false, r.c[2]); butterworthSection(f2, true, r.c[3]);
-    r.W = std::max(pow2AtLeast(uint32_t(need)), 16u * kBdMinL);
+    r.W = std::max(pow2AtLeast(uint32_t(need)), 16u * kTwinMinL);
     r.L = r.W / 16;
     *f = r;
     return SGZ_OK;
@@ -701,7 +477,7 @@ sgz_status sgz_band_filter_for_rate(double rate, double low_hz, double high_hz, 
 sgz_status sgz_band_taps(const sgz_band_filter *f, int32_t *taps)
 {
     if (!f || !taps) return fail(SGZ_EINVAL, "sgz_band_taps: null argument");
-    if (!shapeOk(*f)) return fail(SGZ_EINVAL, "sgz_band_taps: W and L are powers of two, 16 <= L <= W <= 65536");
+    if (!filterShapeOk(*f)) return fail(SGZ_EINVAL, "sgz_band_taps: W and L are powers of two, 16 <= L <= W <= 65536");
     std::vector<int32_t> t(size_t(kBdComps) * f->W);                // (a refusal writes nothing)
     if (!buildTaps(*f, t.data())) return fail(SGZ_EINVAL, "sgz_band_taps: a tap outside int32, or 2^26 sum |C| >= 2^62");
     std::memcpy(taps, t.data(), t.size() * sizeof(int32_t));
@@ -710,34 +486,23 @@ sgz_status sgz_band_taps(const sgz_band_filter *f, int32_t *taps)
 
 sgz_status sgz_band_fold(const sgz_band_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns, sgz_band_record *out)
 {
-    if (!in || !out) return fail(SGZ_EINVAL, "sgz_band_fold: null argument");
-    if (channels == 0) return fail(SGZ_EINVAL, "sgz_band_fold: channels >= 1");
-    uint64_t cols = 0;
-    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
-    const uint64_t w = x1 - x0;
-    auto bound = [&](uint64_t b) { return x0 + (b * w + cols - 1) / cols; };                   // (b w < 2^62: n < 2^31)
-    // the counts first: a refusal writes nothing
-    for (uint64_t b = 0; b < cols; ++b)
-        for (uint32_t c = 0; c < channels; ++c) {
-            uint64_t count = 0;
-            for (uint64_t j = bound(b); j < bound(b + 1); ++j) count += in[j * channels + c].count;
-            if (count > 0xffffffffull) return fail(SGZ_EINVAL, "sgz_band_fold: a folded column counts more than 2^32 - 1");
-        }
-    for (uint64_t b = 0; b < cols; ++b)
-        for (uint32_t c = 0; c < channels; ++c) {
+    return foldColumns(
+        "sgz_band_fold", "channels", "", in, n, channels, x0, x1, out_columns, out,
+        [](const sgz_band_record *v, size_t count, size_t stride) {
+            uint64_t tally = 0;
+            for (size_t j = 0; j < count; ++j) tally += v[j * stride].count;
+            return tally <= 0xffffffffull;
+        },
+        [](const sgz_band_record *v, size_t count, size_t stride) {
             unsigned __int128 sum[3] = {0, 0, 0};
-            uint32_t count = 0;
-            for (uint64_t j = bound(b); j < bound(b + 1); ++j) {
-                const sgz_band_record &v = in[j * channels + c];
-                for (int k = 0; k < 3; ++k) sum[k] += sumOf(v, k);
-                count += v.count;
-            }
             sgz_band_record r{};
+            for (size_t j = 0; j < count; ++j) {
+                for (int k = 0; k < 3; ++k) sum[k] += sumOf(v[j * stride], k);
+                r.count += v[j * stride].count;
+            }
             for (int k = 0; k < 3; ++k) { r.sumsq[k][0] = uint64_t(sum[k]); r.sumsq[k][1] = uint64_t(sum[k] >> 64); }
-            r.count = count;
-            out[b * channels + c] = r;
-        }
-    return SGZ_OK;
+            return r;
+        });
 }
 
 sgz_status sgz_band_readout(const sgz_band_record *recs, size_t ncols, uint32_t channels, uint32_t channel, double *mean_square, double *db)

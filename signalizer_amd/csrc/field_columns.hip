@@ -3,7 +3,9 @@
 // pair of a linear planar stream, with a carried open column (sgz.h, "The stereo-field lane"); and the lane's host helpers: the boundary
 // table, the fold of kept records and the readout of one.  gfx950 only.  The reference's polar plot is live (drawPolarPlot); the lane takes
 // its geometry from it -- direction from (L + R, L - R), radius = max(|L|, |R|), left at negative angles -- and nothing else.
-//   v = the level lane's quantiser; a frame with a NaN on either side is skipped, one with vL = vR = 0 is silent; every other frame adds its
+// What the column lanes share -- the shape of a call, the bounds, the quantiser, the staging of a row, the stage call's front, the fold's
+// frame -- is column_lanes.hpp; this file is the histogram.
+//   v = the quantiser's (quantiseMarked); a frame with a NaN on either side is skipped, one with vL = vR = 0 is silent; every other frame adds its
 //   radius to the sector its direction falls in, found by exact 64-bit tests against the 32 integer boundary directions (kFdDirs).  All fields
 //   are integer sums and maxima, so any cut of the stream (calls with a carry) or of a column (lanes, slices) gives the same bytes.
 // A histogram is a scatter: lanes that add to one address serialise, and real music piles its frames into two or three sectors.  Nothing is
@@ -12,10 +14,8 @@
 // broadcast -- and each lane keeps count, sum and peak of its own sector in registers.  No table in LDS, no atomics, nothing to zero or to
 // fold inside a column, and the rate is the same whatever the signal: an all-mono file costs what noise costs (DESIGN.md section 4 has the
 // measurements, and what the broadcast costs: every word is looked at by 32 lanes).
-// Column c of a call covers its samples [c m - held, (c + 1) m - held) clipped to [0, n), as in level_columns.hip.
 //   m <= kFdSwitch (512)    fieldTileKernel: one workgroup per (pair, tile); a tile is kFdTile / m whole columns of both rows of the pair.  The
-//                           rows go to LDS quantised (level_columns.hip's stageRow: 16-byte loads between the first and the last 16-byte
-//                           boundary of each row), the frames are packed in place, and each of the workgroup's eight half-waves takes a column
+//                           rows go to LDS quantised (stageRow, plain: nothing strides these rows), the frames are packed in place, and each of the workgroup's eight half-waves takes a column
 //                           at a time.  The lanes of the half-wave store the record: lane b its sector's three fields.  A tile of the
 //                           shortest columns holds kFdTile of them (m = 1): there is no table per column to bound that number.
 //   else, or slices >= 2    fieldSliceKernel: workgroup (column, pair, slice) takes its part of the column through LDS a tile at a time, the
@@ -30,8 +30,7 @@
 #include <cstring>
 #include <limits>
 
-#include "runtime.hpp"
-#include "scope_ring.hpp"      // StreamScratch
+#include "column_lanes.hpp"
 
 using namespace sgz;
 
@@ -42,11 +41,11 @@ constexpr int kFdHalves = kFdThreads / 32;       // half-waves of a workgroup: 3
 constexpr uint32_t kFdTile = 4096;               // sample frames of a tile (two rows of quantised samples: 32 KiB of LDS)
 constexpr uint32_t kFdSwitch = 512;              // the switch-over: columns longer than this take the sliced form (a full tile of shorter ones
                                                  // has a column for every half-wave)
-constexpr uint32_t kFdMaxSlices = 64, kFdMaxPairs = 32;
+constexpr uint32_t kFdMaxPairs = 32;
 constexpr int kFdUnroll = 4;                     // 16-byte loads per row a lane issues before the first store to LDS
 constexpr uint32_t kFdRowWords = kFdTile + 4;    // a row of the tile and its lead: the row's own offset within 16 bytes
 constexpr int32_t kFdClamp = 1 << 26;            // the quantiser's range, and the greatest radius
-constexpr int32_t kFdNaN = std::numeric_limits<int32_t>::min();     // a NaN in LDS (no quantised sample: |v| <= 2^26)
+constexpr int32_t kFdNaN = kQuantNaN;            // a NaN in LDS
 // a frame in LDS: sector << 27 | radius with 1 <= radius <= 2^26, or one of two words whose radius field is above 2^26 in every sector
 constexpr uint32_t kFdSilent = 0xffffffffu, kFdSkipped = 0xfffffffeu;
 static_assert(SGZ_FIELD_SECTORS == 32, "a lane of a half-wave per sector, five bits of a packed frame");
@@ -100,14 +99,6 @@ struct FieldParams {
     sgz_field_record *partial;           // [slices][columns][pairs]
 };
 
-// the level lane's quantiser (level_columns.hip); kFdNaN for a NaN
-__device__ __forceinline__ int32_t quantise(uint32_t bits)
-{
-    const float x = __uint_as_float(bits);
-    const float r = __builtin_amdgcn_fmed3f(rintf(x * 0x1p23f), -0x1p26f, 0x1p26f);
-    return x != x ? kFdNaN : int32_t(r);
-}
-
 // A frame's word.  n = #{k : C_k X - S_k M >= 0} by binary search over the tests 0 .. 30 (they form a prefix), then test 31 where all of
 // those hold: n = 32 is sector 0 again, the antiphase line from its other end.  Every product is a v_mad_i64_i32, exact.
 __device__ __forceinline__ uint32_t packFrame(int32_t l, int32_t r, const int2 *dirs)
@@ -142,47 +133,6 @@ struct Sector {
     }
 };
 
-// samples [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnSamples(const FieldParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.m) - long(prm.held);
-    b = a + long(prm.m);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
-}
-
-// where the 16-byte part of `count` floats at g begins and ends: [0, head) and [tail, count) are scalar, `vecs` chunks lie between
-__device__ __forceinline__ void splitAligned(const float *g, size_t count, uint32_t &head, size_t &vecs, size_t &tail)
-{
-    const uint32_t lead = uint32_t(reinterpret_cast<uintptr_t>(g) >> 2) & 3u;
-    const uint32_t toBoundary = (4u - lead) & 3u;
-    head = count < toBoundary ? uint32_t(count) : toBoundary;
-    vecs = (count - head) >> 2;
-    tail = head + 4 * vecs;
-}
-
-// `count` (<= kFdTile) floats at g, quantised, into a row of the tile, `lead` words in: 16-byte chunks of memory are 16-byte chunks of LDS
-// (level_columns.hip's stageRow without its padding: nothing strides these rows)
-__device__ __forceinline__ void stageRow(const float *g, uint32_t count, uint32_t lead, int32_t *row)
-{
-    const uint32_t tid = threadIdx.x;
-    uint32_t head;
-    size_t vecs, tail;
-    splitAligned(g, count, head, vecs, tail);
-    if (tid < head) row[lead + tid] = quantise(__float_as_uint(g[tid]));
-    if (tid < count - uint32_t(tail)) row[lead + uint32_t(tail) + tid] = quantise(__float_as_uint(g[tail + tid]));
-    const uint4 *gv = reinterpret_cast<const uint4 *>(g + head);
-    uint4 v[kFdUnroll];
-#pragma unroll
-    for (int j = 0; j < kFdUnroll; ++j)
-        v[j] = tid + uint32_t(j) * kFdThreads < vecs ? gv[tid + uint32_t(j) * kFdThreads] : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int j = 0; j < kFdUnroll; ++j)                                     // (lead + head is a multiple of 4 wherever vecs > 0)
-        if (tid + uint32_t(j) * kFdThreads < vecs)
-            *reinterpret_cast<int4 *>(row + lead + head + 4u * (tid + uint32_t(j) * kFdThreads)) =
-                make_int4(quantise(v[j].x), quantise(v[j].y), quantise(v[j].z), quantise(v[j].w));
-}
-
 // The tile of one (pair, sample range) in LDS.  load: `count` frames at gL / gR -> a packed word per frame in row 0, frame j at words()[j]
 // (the workgroup's call; it ends behind a barrier).  Each row keeps its own offset within 16 bytes, so the rows of a pair need not share one
 struct Tile {
@@ -196,8 +146,8 @@ struct Tile {
         const uint32_t leadL = uint32_t(reinterpret_cast<uintptr_t>(gL) >> 2) & 3u, leadR = uint32_t(reinterpret_cast<uintptr_t>(gR) >> 2) & 3u;
         if (tid < 32) dirs[tid] = make_int2(kFdDirsDevice[tid][0], kFdDirsDevice[tid][1]);
         if (tid == 0) lead = leadL;
-        stageRow(gL, count, leadL, row[0]);
-        stageRow(gR, count, leadR, row[1]);
+        stageRow<false, kFdThreads, kFdUnroll>(gL, count, leadL, row[0]);      // (plain rows: nothing strides them)
+        stageRow<false, kFdThreads, kFdUnroll>(gR, count, leadR, row[1]);
         __syncthreads();
         for (uint32_t i = tid; i < count; i += kFdThreads)                  // (a lane packs the frames it reads: in place)
             row[0][leadL + i] = int32_t(packFrame(row[0][leadL + i], row[1][leadR + i], dirs));
@@ -264,11 +214,9 @@ fieldTileKernel(const FieldParams prm)
 {
     __shared__ __attribute__((aligned(16))) Tile tile;
     const uint32_t tid = threadIdx.x, p = blockIdx.y;
-    const long c0 = long(blockIdx.x) * long(prm.perTile);
-    const long c1 = c0 + long(prm.perTile) < prm.columns ? c0 + long(prm.perTile) : prm.columns;
-    long a = c0 * long(prm.m) - long(prm.held), b = c1 * long(prm.m) - long(prm.held);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
+    TileBounds t;
+    tileBounds(prm, t);
+    const long c0 = t.c0, c1 = t.c1, a = t.a, b = t.b;
     const float *gL = prm.planar + size_t(2 * p) * prm.stride + size_t(a);
     tile.load(gL, gL + prm.stride, uint32_t(b - a));                        // (b - a <= perTile * m <= kFdTile)
     const uint32_t lane = tid & 31u, half = tid >> 5, cols = uint32_t(c1 - c0);
@@ -298,10 +246,9 @@ fieldSliceKernel(const FieldParams prm)
     __shared__ uint32_t foldCount[kFdHalves][32], foldPeak[kFdHalves][32], foldMarks[kFdHalves][2];
     const long col = long(blockIdx.x);
     const uint32_t p = blockIdx.y, sl = blockIdx.z, tid = threadIdx.x, lane = tid & 31u, half = tid >> 5;
-    long a, b;
+    long a, b, sa, sb;
     columnSamples(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(sl) * per < b ? a + long(sl) * per : b, sb = sa + per < b ? sa + per : b;
+    sliceSamples(prm, a, b, sl, sa, sb);
     const float *rowL = prm.planar + size_t(2 * p) * prm.stride;
     Sector s{0, 0, 0};
     uint32_t silent = 0, skipped = 0;
@@ -360,25 +307,12 @@ fieldEmitKernel(const FieldParams prm)
 
 namespace sgz {
 
-// The shape of a call whose arguments passed sgz_stage_field_columns' checks, as levelColumnsShape: slices 0 = the tile form, else the sliced
-// form with that many (the caller's count, or for m > kFdSwitch the overview's rule); scratchBytes: the partial records of the sliced form.
-FieldColumnsShape fieldColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
+ColumnsShape fieldColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
 {
-    FieldColumnsShape sh{};
-    const uint64_t t = uint64_t(held) + nsamples;
-    sh.closed = t / m + ((flush && t % m) ? 1u : 0u);
-    sh.open = !flush && t % m != 0;
-    sh.columns = sh.closed + (sh.open ? 1u : 0u);
-    sh.launch = sh.columns != 0 && !(nsamples == 0 && !(flush && held));
-    if (!sh.launch || nsamples == 0) return sh;
-    if (slices >= 2 || m > kFdSwitch) sh.slices = slices ? slices : overviewAutoSlices(long(sh.columns), pairs, m, nsamples, numCUs());
-    sh.scratchBytes = size_t(sh.slices) * size_t(sh.columns) * pairs * sizeof(sgz_field_record);
-    return sh;
+    return columnsShape(pairs, nsamples, m, held, flush, slices, kFdSwitch, sizeof(sgz_field_record), 0);
 }
 
-// sgz_stage_field_columns behind its argument checks, with the carry in two places: carryIn is read by column 0 (held > 0), carryOut written by
-// the open column -- the same memory only where the call has one column.  scratch: sh.scratchBytes bytes.
-sgz_status runFieldColumns(const FieldColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
+sgz_status runFieldColumns(const ColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
                            uint32_t held, const sgz_field_record *carryIn, sgz_field_record *carryOut, sgz_field_record *d_field, void *scratch,
                            hipStream_t stream)
 {
@@ -393,17 +327,17 @@ sgz_status runFieldColumns(const FieldColumnsShape &sh, const float *d_planar, s
     if (nsamples != 0 && sh.slices == 0) {
         prm.perTile = kFdTile / m;
         const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (tiles > 0x7fffffffull) return fail(SGZ_EINVAL, "field columns: too many columns for one launch");
+        if (sgz_status st = fitsOneLaunch(tiles, "field", "columns"); st != SGZ_OK) return st;
         hipLaunchKernelGGL(fieldTileKernel, dim3(unsigned(tiles), pairs), dim3(kFdThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sh.columns > 0x7fffffffull || (lanes + kFdThreads - 1) / kFdThreads > 0x7fffffffull) return fail(SGZ_EINVAL, "field columns: too many columns for one launch");
+    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(lanes, kFdThreads)), "field", "columns"); st != SGZ_OK) return st;
     if (nsamples != 0) {
         hipLaunchKernelGGL(fieldSliceKernel, dim3(unsigned(sh.columns), pairs, sh.slices), dim3(kFdThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(fieldEmitKernel, dim3(unsigned((lanes + kFdThreads - 1) / kFdThreads)), dim3(kFdThreads), 0, stream, prm);
+    hipLaunchKernelGGL(fieldEmitKernel, dim3(unsigned(emitBlocks(lanes, kFdThreads))), dim3(kFdThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     return SGZ_OK;
 }
@@ -423,58 +357,37 @@ void sgz_field_boundaries(int32_t cs[32][2]) { std::memcpy(cs, kFdDirs, sizeof k
 sgz_status sgz_stage_field_columns(const float *d_planar, size_t channel_stride, uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held,
                                    int flush, uint32_t slices, sgz_field_record *d_carry, sgz_field_record *d_field, void *stream)
 {
-    if (!d_planar) return fail(SGZ_EINVAL, "sgz_stage_field_columns: null d_planar");
-    if (pairs == 0 || pairs > kFdMaxPairs) return fail(SGZ_EINVAL, "sgz_stage_field_columns: 1 .. 32 pairs");
-    if (m == 0) return fail(SGZ_EINVAL, "sgz_stage_field_columns: m >= 1 samples per column");
-    if (held >= m) return fail(SGZ_EINVAL, "sgz_stage_field_columns: held < m");
-    if (channel_stride < nsamples || nsamples > (size_t(1) << 62)) return fail(SGZ_EINVAL, "sgz_stage_field_columns: channel_stride < nsamples");
-    if (slices > kFdMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_field_columns: slices 0 (automatic) or 1 .. 64");
-    if ((reinterpret_cast<uintptr_t>(d_planar) & 3u) || (reinterpret_cast<uintptr_t>(d_carry) & 15u) || (reinterpret_cast<uintptr_t>(d_field) & 15u))
-        return fail(SGZ_EINVAL, "sgz_stage_field_columns: d_planar aligned to 4 bytes, d_carry and d_field to 16");
-    const FieldColumnsShape sh = fieldColumnsShape(pairs, nsamples, m, held, flush, slices);
-    if (!d_carry && (held || sh.open)) return fail(SGZ_EINVAL, "sgz_stage_field_columns: d_carry is read (held > 0) or written (samples stay open)");
-    if (!d_field && sh.closed) return fail(SGZ_EINVAL, "sgz_stage_field_columns: d_field is written (a column closes)");
+    const StageFront front{"sgz_stage_field_columns", "pairs", kFdMaxPairs, "d_field", 16, false, 62};
+    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, pairs, nsamples, m, held, 0, 0, slices, d_carry, d_field); st != SGZ_OK) return st;
+    const ColumnsShape sh = fieldColumnsShape(pairs, nsamples, m, held, flush, slices);
+    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, 0, d_carry, d_field); st != SGZ_OK) return st;
     if (!sh.launch) return SGZ_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StreamScratch scratch(s), snapshot(s);
-    const sgz_field_record *carryIn = d_carry;
-    if (held && sh.open && sh.columns > 1) {
-        // column 0 reads the carry while the open column writes it, in another workgroup: column 0 reads a snapshot
-        SGZ_HIP(snapshot.get(size_t(pairs) * sizeof(sgz_field_record)));
-        SGZ_HIP(hipMemcpyAsync(snapshot.p, d_carry, size_t(pairs) * sizeof(sgz_field_record), hipMemcpyDeviceToDevice, s));
-        carryIn = static_cast<const sgz_field_record *>(snapshot.p);
-    }
-    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    return runFieldColumns(sh, d_planar, channel_stride, pairs, nsamples, m, held, carryIn, d_carry, d_field, scratch.p, s);
+    StageScratch mem(s);
+    const void *carryIn = nullptr;
+    if (sgz_status st = mem.get(front, sh, nsamples, held, 0, d_carry, size_t(pairs) * sizeof(sgz_field_record), &carryIn); st != SGZ_OK) return st;
+    return runFieldColumns(sh, d_planar, channel_stride, pairs, nsamples, m, held, static_cast<const sgz_field_record *>(carryIn), d_carry, d_field, mem.scratch.p, s);
 }
 
 sgz_status sgz_field_fold(const sgz_field_record *in, size_t n, uint32_t pairs, size_t x0, size_t x1, uint32_t out_columns, sgz_field_record *out)
 {
-    if (!in || !out) return fail(SGZ_EINVAL, "sgz_field_fold: null argument");
-    if (pairs == 0) return fail(SGZ_EINVAL, "sgz_field_fold: pairs >= 1");
-    uint64_t cols = 0;
-    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
-    const uint64_t w = x1 - x0;
-    auto bound = [&](uint64_t b) { return x0 + (b * w + cols - 1) / cols; };                   // (b w < 2^62: n < 2^31)
-    // the 32-bit tallies first: a refusal writes nothing
-    for (uint64_t b = 0; b < cols; ++b)
-        for (uint32_t p = 0; p < pairs; ++p) {
+    return foldColumns(
+        "sgz_field_fold", "pairs", " frames", in, n, pairs, x0, x1, out_columns, out,
+        [](const sgz_field_record *in, size_t count, size_t stride) {
             uint64_t tally[SGZ_FIELD_SECTORS + 2] = {};
-            for (uint64_t j = bound(b); j < bound(b + 1); ++j) {
-                const sgz_field_record &v = in[j * pairs + p];
+            for (size_t j = 0; j < count; ++j) {
+                const sgz_field_record &v = in[j * stride];
                 for (int k = 0; k < SGZ_FIELD_SECTORS; ++k) tally[k] += v.count[k];
                 tally[SGZ_FIELD_SECTORS] += v.silent;
                 tally[SGZ_FIELD_SECTORS + 1] += v.skipped;
             }
-            for (uint64_t t : tally)
-                if (t > 0xffffffffull) return fail(SGZ_EINVAL, "sgz_field_fold: a folded column counts more than 2^32 - 1 frames");
-        }
-    for (uint64_t b = 0; b < cols; ++b)
-        for (uint32_t p = 0; p < pairs; ++p) {
+            return std::all_of(tally, tally + SGZ_FIELD_SECTORS + 2, [](uint64_t t) { return t <= 0xffffffffull; });
+        },
+        [](const sgz_field_record *in, size_t count, size_t stride) {
             sgz_field_record r;
             std::memset(&r, 0, sizeof r);
-            for (uint64_t j = bound(b); j < bound(b + 1); ++j) {
-                const sgz_field_record &v = in[j * pairs + p];
+            for (size_t j = 0; j < count; ++j) {
+                const sgz_field_record &v = in[j * stride];
                 for (int k = 0; k < SGZ_FIELD_SECTORS; ++k) {
                     r.radius[k] += v.radius[k];
                     r.count[k] += v.count[k];
@@ -483,9 +396,8 @@ sgz_status sgz_field_fold(const sgz_field_record *in, size_t n, uint32_t pairs, 
                 r.silent += v.silent;
                 r.skipped += v.skipped;
             }
-            out[b * pairs + p] = r;
-        }
-    return SGZ_OK;
+            return r;
+        });
 }
 
 sgz_status sgz_field_readout(const sgz_field_record *rec, sgz_field_reading *out)

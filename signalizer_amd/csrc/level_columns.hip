@@ -1,24 +1,21 @@
 // level_columns.hip -- the level lane's reduction: one sgz_level_record (sums of squares, cross term, sums, counts, overs) per column of m
 // samples and channel pair of a linear planar stream, with a carried open column (sgz.h, "The level lane"); and the lane's host helpers, the
 // fold of kept records and the readout of one.  gfx950 only.  The reference has no counterpart: its meters are live one-pole filters.
-//   v = (int32) clamp(rintf(x 2^23), -2^26, +2^26), a NaN takes no part; every field is a sum of integers, so any cut of the stream (calls
-//   with a carry) or of a column (lanes, slices) gives the same bits.
-// The kernels keep a NaN as v = 0 beside a count of 0: it then adds nothing to any sum.  Column c of a call covers its samples
-// [c m - held, (c + 1) m - held) clipped to [0, n): column 0 is the rest of the carried column (held > 0), the last one may stay open.
-//   m <= kLvSwitch (1024)   levelTileKernel: one workgroup per (pair, tile); a tile is kLvTile / m whole columns of the call (column 0
-//                           counts as one, whatever is left of it) of BOTH rows of the pair, so no column straddles two workgroups.  Each
-//                           row goes to LDS once, quantised on the way: 16-byte loads between the row's first and last 16-byte boundary, up
-//                           to three scalar loads on either side (the bases are only 4-byte aligned, and the two rows of a pair need not
-//                           share an alignment); LDS keeps each row at its own offset within 16 bytes, four words of padding behind every 64.
-//                           Then groups of G lanes (a power of two near m / 16) take a column each: the lanes stride the column in LDS with
-//                           64-bit accumulators (Narrow: a column holds at most 1024 samples; a lane's own sums of v, at most 16 of them,
-//                           in 32 bits), log2 G cross-lane steps, the group's first lane widens, folds the carry (column 0) and stores the
-//                           record -- or the carry (the open column).
+// What the column lanes share -- the shape of a call, the bounds, the quantiser, the staging of a row, the stage call's front, the fold's
+// frame -- is column_lanes.hpp; this file is the record's arithmetic.
+//   v = the quantiser's (quantiseMarked), a NaN takes no part; every field is a sum of integers, so any cut of the stream (calls with a
+//   carry) or of a column (lanes, slices) gives the same bits.
+// The kernels keep a NaN as v = 0 beside a count of 0: it then adds nothing to any sum.
+//   m <= kLvSwitch (1024)   levelTileKernel: one workgroup per (pair, tile) of BOTH rows of the pair.  Each row goes to LDS once, quantised
+//                           on the way (stageRow, padded; the two rows of a pair need not share an alignment, each keeps its own offset
+//                           within 16 bytes).  Then groups of G lanes (a power of two near m / 16) take a column each: the lanes stride the
+//                           column in LDS with 64-bit accumulators (Narrow: a column holds at most 1024 samples; a lane's own sums of v, at
+//                           most 16 of them, in 32 bits), log2 G cross-lane steps, the group's first lane widens, folds the carry (column
+//                           0) and stores the record -- or the carry (the open column).
 //   else, or slices >= 2    levelSliceKernel: workgroup (column, pair, slice) scans its part of the column from memory (16-byte loads where
 //                           both rows share an alignment, 4-byte loads otherwise) into 128-bit accumulators -> partial records
 //                           [slices][columns][pairs] in scratch; levelEmitKernel, a launch of its own behind it, folds the slices and the
-//                           carry and stores (no hand-off between workgroups inside a launch).  A flush without samples is the emit kernel
-//                           alone, on the carry.
+//                           carry and stores.  A flush without samples is the emit kernel alone, on the carry.
 // Every sample is read from memory once.  Nothing is waited for.
 #include <hip/hip_runtime.h>
 
@@ -27,8 +24,7 @@
 #include <cstring>
 #include <limits>
 
-#include "runtime.hpp"
-#include "scope_ring.hpp"      // StreamScratch
+#include "column_lanes.hpp"
 
 using namespace sgz;
 
@@ -40,13 +36,13 @@ typedef __int128 i128;
 constexpr int kLvThreads = 256;
 constexpr uint32_t kLvTile = 4096;              // samples per row of a tile (two rows: 32 KiB of LDS and the padding)
 constexpr uint32_t kLvSwitch = 1024;            // the switch-over: columns longer than this take the sliced form
-constexpr uint32_t kLvMaxSlices = 64, kLvMaxPairs = 32;
+constexpr uint32_t kLvMaxPairs = 32;
 constexpr int kLvUnroll = 4;                    // 16-byte loads per row a lane of the tile form issues before the first store to LDS
 constexpr int kLvScan = 2;                      // loads per row a lane of the sliced form has in flight (two rows: four)
 constexpr uint32_t kLvTileWords = kLvTile + 4 + 4 * ((kLvTile + 4) / 64 + 1);      // the lead, and four words of padding per 64 (tileWord)
 constexpr int32_t kLvFull = 1 << 23;            // |v| of full scale: an over
 constexpr int32_t kLvClamp = 1 << 26;           // the quantiser's range
-constexpr int32_t kLvNaN = std::numeric_limits<int32_t>::min();     // a NaN in LDS (no quantised sample: |v| <= 2^26)
+constexpr int32_t kLvNaN = kQuantNaN;           // a NaN in LDS
 static_assert(kLvTile == 4u * kLvThreads * kLvUnroll, "a lane moves kLvUnroll 16-byte chunks of a tile's row");
 static_assert(kLvSwitch <= kLvTile, "a short column fits a tile");
 // The 64-bit accumulators: a term v^2 or |v_L v_R| is at most 2^52, so fewer than 2048 terms stay below 2^63, the signed cross term's limit.
@@ -77,15 +73,6 @@ struct LevelParams {
     sgz_level_record *level;             // [closed][pairs]
     sgz_level_record *partial;           // [slices][columns][pairs]
 };
-
-// the quantiser; kLvNaN for a NaN.  (x 2^23 is exact or overflows to an infinity, which the clamp takes; a denormal times 2^23 is below 2^-102
-// and rounds to 0, as does the 0 a flushing device makes of it)
-__device__ __forceinline__ int32_t quantise(uint32_t bits)
-{
-    const float x = __uint_as_float(bits);
-    const float r = __builtin_amdgcn_fmed3f(rintf(x * 0x1p23f), -0x1p26f, 0x1p26f);     // (the median of three: the clamp in one instruction)
-    return x != x ? kLvNaN : int32_t(r);
-}
 
 // at most kLvNarrowTerms sample frames of a pair (the static_asserts above)
 struct Narrow {
@@ -169,55 +156,11 @@ struct Wide {
 };
 __device__ __forceinline__ Wide nothing() { return Wide{{0, 0}, 0, {0, 0}, {0, 0}, {0, 0}}; }
 
-// samples [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnSamples(const LevelParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.m) - long(prm.held);
-    b = a + long(prm.m);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
-}
-
 // what a (column, pair) does with its sums: the carry into column 0, then the record to the output (a closed column) or to the carry
 __device__ __forceinline__ void emitColumn(const LevelParams &prm, long col, uint32_t p, Wide w)
 {
     if (col == 0 && prm.held) w.add(prm.carryIn[p]);
     w.store(col < prm.closed ? prm.level + size_t(col) * prm.pairs + p : prm.carryOut + p);
-}
-
-// where the 16-byte part of `count` floats at g begins and ends: [0, head) and [tail, count) are scalar, `vecs` chunks lie between
-__device__ __forceinline__ void splitAligned(const float *g, size_t count, uint32_t &head, size_t &vecs, size_t &tail)
-{
-    const uint32_t lead = uint32_t(reinterpret_cast<uintptr_t>(g) >> 2) & 3u;
-    const uint32_t toBoundary = (4u - lead) & 3u;
-    head = count < toBoundary ? uint32_t(count) : toBoundary;
-    vecs = (count - head) >> 2;
-    tail = head + 4 * vecs;
-}
-
-// where word i of a tile's row lies in LDS: four words of padding behind every 64, so that columns a multiple of 32 words apart start on
-// different banks (16-byte chunks stay whole and aligned)
-__device__ __forceinline__ uint32_t tileWord(uint32_t i) { return i + ((i >> 6) << 2); }
-
-// `count` (<= kLvTile) floats at g, quantised, into a row of the tile, `lead` words in: 16-byte chunks of memory are 16-byte chunks of LDS
-__device__ __forceinline__ void stageRow(const float *g, uint32_t count, uint32_t lead, int32_t *row)
-{
-    const uint32_t tid = threadIdx.x;
-    uint32_t head;
-    size_t vecs, tail;
-    splitAligned(g, count, head, vecs, tail);
-    if (tid < head) row[tileWord(lead + tid)] = quantise(__float_as_uint(g[tid]));
-    if (tid < count - uint32_t(tail)) row[tileWord(lead + uint32_t(tail) + tid)] = quantise(__float_as_uint(g[tail + tid]));
-    const uint4 *gv = reinterpret_cast<const uint4 *>(g + head);
-    uint4 v[kLvUnroll];
-#pragma unroll
-    for (int j = 0; j < kLvUnroll; ++j)
-        v[j] = tid + uint32_t(j) * kLvThreads < vecs ? gv[tid + uint32_t(j) * kLvThreads] : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int j = 0; j < kLvUnroll; ++j)                                     // (lead + head is a multiple of 4 wherever vecs > 0)
-        if (tid + uint32_t(j) * kLvThreads < vecs)
-            *reinterpret_cast<int4 *>(row + tileWord(lead + head + 4u * (tid + uint32_t(j) * kLvThreads))) =
-                make_int4(quantise(v[j].x), quantise(v[j].y), quantise(v[j].z), quantise(v[j].w));
 }
 
 // the tile's two rows through LDS, then groups of prm.group lanes per column
@@ -226,16 +169,14 @@ levelTileKernel(const LevelParams prm)
 {
     __shared__ __attribute__((aligned(16))) int32_t tile[2][kLvTileWords];
     const uint32_t tid = threadIdx.x, p = blockIdx.y;
-    const long c0 = long(blockIdx.x) * long(prm.perTile);
-    const long c1 = c0 + long(prm.perTile) < prm.columns ? c0 + long(prm.perTile) : prm.columns;
-    long a = c0 * long(prm.m) - long(prm.held), b = c1 * long(prm.m) - long(prm.held);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
+    TileBounds t;
+    tileBounds(prm, t);
+    const long c0 = t.c0, c1 = t.c1, a = t.a, b = t.b;
     const uint32_t count = uint32_t(b - a);                                 // <= perTile * m <= kLvTile
     const float *gL = prm.planar + size_t(2 * p) * prm.stride + size_t(a), *gR = gL + prm.stride;
     const uint32_t leadL = uint32_t(reinterpret_cast<uintptr_t>(gL) >> 2) & 3u, leadR = uint32_t(reinterpret_cast<uintptr_t>(gR) >> 2) & 3u;
-    stageRow(gL, count, leadL, tile[0]);
-    stageRow(gR, count, leadR, tile[1]);
+    stageRow<true, kLvThreads, kLvUnroll>(gL, count, leadL, tile[0]);
+    stageRow<true, kLvThreads, kLvUnroll>(gR, count, leadR, tile[1]);
     __syncthreads();
     const uint32_t G = prm.group, sub = tid & (G - 1u), grp = tid / G, groups = uint32_t(kLvThreads) / G;
     const uint32_t cols = uint32_t(c1 - c0);
@@ -275,8 +216,8 @@ __device__ __forceinline__ Wide scanLanes(const float *rowL, const float *rowR, 
         size_t vecs, tail;
         splitAligned(gL, count, head, vecs, tail);
         Narrow k = noSamples();
-        if (lane < head) k.take(quantise(__float_as_uint(gL[lane])), quantise(__float_as_uint(gR[lane])));
-        if (lane < count - tail) k.take(quantise(__float_as_uint(gL[tail + lane])), quantise(__float_as_uint(gR[tail + lane])));
+        if (lane < head) k.take(quantiseMarked(__float_as_uint(gL[lane])), quantiseMarked(__float_as_uint(gR[lane])));
+        if (lane < count - tail) k.take(quantiseMarked(__float_as_uint(gL[tail + lane])), quantiseMarked(__float_as_uint(gR[tail + lane])));
         w.add(k);
         const uint4 *vL = reinterpret_cast<const uint4 *>(gL + head), *vR = reinterpret_cast<const uint4 *>(gR + head);
         for (size_t i = lane; i < vecs; i += size_t(lanes) * kLvScan) {
@@ -290,10 +231,10 @@ __device__ __forceinline__ Wide scanLanes(const float *rowL, const float *rowR, 
             k = noSamples();
 #pragma unroll
             for (int j = 0; j < kLvScan; ++j) {
-                k.take(quantise(l[j].x), quantise(r[j].x));
-                k.take(quantise(l[j].y), quantise(r[j].y));
-                k.take(quantise(l[j].z), quantise(r[j].z));
-                k.take(quantise(l[j].w), quantise(r[j].w));
+                k.take(quantiseMarked(l[j].x), quantiseMarked(r[j].x));
+                k.take(quantiseMarked(l[j].y), quantiseMarked(r[j].y));
+                k.take(quantiseMarked(l[j].z), quantiseMarked(r[j].z));
+                k.take(quantiseMarked(l[j].w), quantiseMarked(r[j].w));
             }
             w.add(k);
         }
@@ -310,7 +251,7 @@ __device__ __forceinline__ Wide scanLanes(const float *rowL, const float *rowR, 
         }
         Narrow k = noSamples();
 #pragma unroll
-        for (int j = 0; j < 4 * kLvScan; ++j) k.take(quantise(l[j]), quantise(r[j]));
+        for (int j = 0; j < 4 * kLvScan; ++j) k.take(quantiseMarked(l[j]), quantiseMarked(r[j]));
         w.add(k);
     }
     return w;
@@ -341,10 +282,9 @@ levelSliceKernel(const LevelParams prm)
     __shared__ sgz_level_record lds[kLvThreads / 64];
     const long col = long(blockIdx.x);
     const uint32_t p = blockIdx.y, s = blockIdx.z, tid = threadIdx.x;
-    long a, b;
+    long a, b, sa, sb;
     columnSamples(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(s) * per < b ? a + long(s) * per : b, sb = sa + per < b ? sa + per : b;
+    sliceSamples(prm, a, b, s, sa, sb);
     const float *rowL = prm.planar + size_t(2 * p) * prm.stride;
     Wide w = waveFold(scanLanes(rowL, rowL + prm.stride, sa, sb, tid, uint32_t(kLvThreads)));
     if ((tid & 63u) == 0) w.store(&lds[tid >> 6]);
@@ -367,13 +307,6 @@ levelEmitKernel(const LevelParams prm)
     emitColumn(prm, long(at / prm.pairs), uint32_t(at % prm.pairs), w);
 }
 
-uint32_t pow2AtLeast(uint32_t v)
-{
-    uint32_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 // ---- the host helpers' 128-bit arithmetic: two words with carry ---------------------------------------------------------------------------
 void addWords(uint64_t acc[2], const uint64_t v[2])
 {
@@ -389,26 +322,12 @@ double wordsToDouble(uint64_t lo, uint64_t hi) { return std::ldexp(double(hi), 6
 
 namespace sgz {
 
-// The shape of a call whose arguments passed sgz_stage_level_columns' checks.  slices: 0 = the tile form, else the sliced form with that many
-// (the caller's count, or for m > kLvSwitch the overview's rule: the smallest count <= min(64, m, n) with columns x pairs x slices >= 2
-// workgroups per CU); scratchBytes: the partial records of the sliced form.  launch: false -- nothing arrives and nothing is flushed.
-LevelColumnsShape levelColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
+ColumnsShape levelColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
 {
-    LevelColumnsShape sh{};
-    const uint64_t t = uint64_t(held) + nsamples;
-    sh.closed = t / m + ((flush && t % m) ? 1u : 0u);
-    sh.open = !flush && t % m != 0;
-    sh.columns = sh.closed + (sh.open ? 1u : 0u);
-    sh.launch = sh.columns != 0 && !(nsamples == 0 && !(flush && held));
-    if (!sh.launch || nsamples == 0) return sh;
-    if (slices >= 2 || m > kLvSwitch) sh.slices = slices ? slices : overviewAutoSlices(long(sh.columns), pairs, m, nsamples, numCUs());
-    sh.scratchBytes = size_t(sh.slices) * size_t(sh.columns) * pairs * sizeof(sgz_level_record);
-    return sh;
+    return columnsShape(pairs, nsamples, m, held, flush, slices, kLvSwitch, sizeof(sgz_level_record), 0);
 }
 
-// sgz_stage_level_columns behind its argument checks, with the carry in two places: carryIn is read by column 0 (held > 0), carryOut written by
-// the open column -- the same memory only where the call has one column.  scratch: sh.scratchBytes bytes.
-sgz_status runLevelColumns(const LevelColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
+sgz_status runLevelColumns(const ColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
                            uint32_t held, const sgz_level_record *carryIn, sgz_level_record *carryOut, sgz_level_record *d_level, void *scratch,
                            hipStream_t stream)
 {
@@ -424,17 +343,17 @@ sgz_status runLevelColumns(const LevelColumnsShape &sh, const float *d_planar, s
         prm.perTile = kLvTile / m;
         prm.group = pow2AtLeast((m + kLvPerLane - 1) / kLvPerLane);   // (1 .. 64: at most sixteen sample frames a lane)
         const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (tiles > 0x7fffffffull) return fail(SGZ_EINVAL, "level columns: too many columns for one launch");
+        if (sgz_status st = fitsOneLaunch(tiles, "level", "columns"); st != SGZ_OK) return st;
         hipLaunchKernelGGL(levelTileKernel, dim3(unsigned(tiles), pairs), dim3(kLvThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sh.columns > 0x7fffffffull || (cells + kLvThreads - 1) / kLvThreads > 0x7fffffffull) return fail(SGZ_EINVAL, "level columns: too many columns for one launch");
+    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kLvThreads)), "level", "columns"); st != SGZ_OK) return st;
     if (nsamples != 0) {
         hipLaunchKernelGGL(levelSliceKernel, dim3(unsigned(sh.columns), pairs, sh.slices), dim3(kLvThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(levelEmitKernel, dim3(unsigned((cells + kLvThreads - 1) / kLvThreads)), dim3(kLvThreads), 0, stream, prm);
+    hipLaunchKernelGGL(levelEmitKernel, dim3(unsigned(emitBlocks(cells, kLvThreads))), dim3(kLvThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     return SGZ_OK;
 }
@@ -452,53 +371,33 @@ void sgz_level_columns_limits(uint32_t *switch_over, uint32_t *tile_samples)
 sgz_status sgz_stage_level_columns(const float *d_planar, size_t channel_stride, uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held,
                                    int flush, uint32_t slices, sgz_level_record *d_carry, sgz_level_record *d_level, void *stream)
 {
-    if (!d_planar) return fail(SGZ_EINVAL, "sgz_stage_level_columns: null d_planar");
-    if (pairs == 0 || pairs > kLvMaxPairs) return fail(SGZ_EINVAL, "sgz_stage_level_columns: 1 .. 32 pairs");
-    if (m == 0) return fail(SGZ_EINVAL, "sgz_stage_level_columns: m >= 1 samples per column");
-    if (held >= m) return fail(SGZ_EINVAL, "sgz_stage_level_columns: held < m");
-    if (channel_stride < nsamples || nsamples > (size_t(1) << 62)) return fail(SGZ_EINVAL, "sgz_stage_level_columns: channel_stride < nsamples");
-    if (slices > kLvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_level_columns: slices 0 (automatic) or 1 .. 64");
-    if ((reinterpret_cast<uintptr_t>(d_planar) & 3u) || (reinterpret_cast<uintptr_t>(d_carry) & 15u) || (reinterpret_cast<uintptr_t>(d_level) & 15u))
-        return fail(SGZ_EINVAL, "sgz_stage_level_columns: d_planar aligned to 4 bytes, d_carry and d_level to 16");
-    const LevelColumnsShape sh = levelColumnsShape(pairs, nsamples, m, held, flush, slices);
-    if (!d_carry && (held || sh.open)) return fail(SGZ_EINVAL, "sgz_stage_level_columns: d_carry is read (held > 0) or written (samples stay open)");
-    if (!d_level && sh.closed) return fail(SGZ_EINVAL, "sgz_stage_level_columns: d_level is written (a column closes)");
+    const StageFront front{"sgz_stage_level_columns", "pairs", kLvMaxPairs, "d_level", 16, false, 62};
+    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, pairs, nsamples, m, held, 0, 0, slices, d_carry, d_level); st != SGZ_OK) return st;
+    const ColumnsShape sh = levelColumnsShape(pairs, nsamples, m, held, flush, slices);
+    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, 0, d_carry, d_level); st != SGZ_OK) return st;
     if (!sh.launch) return SGZ_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StreamScratch scratch(s), snapshot(s);
-    const sgz_level_record *carryIn = d_carry;
-    if (held && sh.open && sh.columns > 1) {
-        // column 0 reads the carry while the open column writes it, in another workgroup: column 0 reads a snapshot
-        SGZ_HIP(snapshot.get(size_t(pairs) * sizeof(sgz_level_record)));
-        SGZ_HIP(hipMemcpyAsync(snapshot.p, d_carry, size_t(pairs) * sizeof(sgz_level_record), hipMemcpyDeviceToDevice, s));
-        carryIn = static_cast<const sgz_level_record *>(snapshot.p);
-    }
-    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    return runLevelColumns(sh, d_planar, channel_stride, pairs, nsamples, m, held, carryIn, d_carry, d_level, scratch.p, s);
+    StageScratch mem(s);
+    const void *carryIn = nullptr;
+    if (sgz_status st = mem.get(front, sh, nsamples, held, 0, d_carry, size_t(pairs) * sizeof(sgz_level_record), &carryIn); st != SGZ_OK) return st;
+    return runLevelColumns(sh, d_planar, channel_stride, pairs, nsamples, m, held, static_cast<const sgz_level_record *>(carryIn), d_carry, d_level, mem.scratch.p, s);
 }
 
 sgz_status sgz_level_fold(const sgz_level_record *in, size_t n, uint32_t pairs, size_t x0, size_t x1, uint32_t out_columns, sgz_level_record *out)
 {
-    if (!in || !out) return fail(SGZ_EINVAL, "sgz_level_fold: null argument");
-    if (pairs == 0) return fail(SGZ_EINVAL, "sgz_level_fold: pairs >= 1");
-    uint64_t cols = 0;
-    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
-    const uint64_t w = x1 - x0;
-    auto bound = [&](uint64_t b) { return x0 + (b * w + cols - 1) / cols; };                   // (b w < 2^62: n < 2^31)
-    // the counts first: a refusal writes nothing
-    for (uint64_t b = 0; b < cols; ++b)
-        for (uint32_t p = 0; p < pairs; ++p)
-            for (int c = 0; c < 2; ++c) {
-                uint64_t count = 0;
-                for (uint64_t j = bound(b); j < bound(b + 1); ++j) count += in[j * pairs + p].count[c];
-                if (count > 0xffffffffull) return fail(SGZ_EINVAL, "sgz_level_fold: a folded column counts more than 2^32 - 1 samples");
-            }
-    for (uint64_t b = 0; b < cols; ++b)
-        for (uint32_t p = 0; p < pairs; ++p) {
+    return foldColumns(
+        "sgz_level_fold", "pairs", " samples", in, n, pairs, x0, x1, out_columns, out,
+        [](const sgz_level_record *v, size_t count, size_t stride) {
+            uint64_t tally[2] = {0, 0};
+            for (size_t j = 0; j < count; ++j)
+                for (int c = 0; c < 2; ++c) tally[c] += v[j * stride].count[c];
+            return tally[0] <= 0xffffffffull && tally[1] <= 0xffffffffull;
+        },
+        [](const sgz_level_record *in, size_t count, size_t stride) {
             sgz_level_record r;
             std::memset(&r, 0, sizeof r);
-            for (uint64_t j = bound(b); j < bound(b + 1); ++j) {
-                const sgz_level_record &v = in[j * pairs + p];
+            for (size_t j = 0; j < count; ++j) {
+                const sgz_level_record &v = in[j * stride];
                 addWords(r.sumsq[0], v.sumsq[0]);
                 addWords(r.sumsq[1], v.sumsq[1]);
                 addWords(r.cross, v.cross);                        // (two's complement adds as unsigned)
@@ -508,9 +407,8 @@ sgz_status sgz_level_fold(const sgz_level_record *in, size_t n, uint32_t pairs, 
                     r.overs[c] += v.overs[c];
                 }
             }
-            out[b * pairs + p] = r;
-        }
-    return SGZ_OK;
+            return r;
+        });
 }
 
 sgz_status sgz_level_readout(const sgz_level_record *rec, sgz_level_reading *out)

@@ -4,10 +4,10 @@
 // and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, a lane's columns or records --
 // is a PcmOut: device block, pinned twin, pending host copy.  Every lane is a PcmSink: the caller's buffer, the cursor in it, and the PcmOut its
 // units pass through; the track lane (tracker.hip), which searches every piece's line results behind its render, is a sink of frames, and the
-// six column lanes -- waveform, level, true-peak, loudness, stereo-field, band (wave_columns.hip, level_columns.hip, truepeak_columns.hip,
-// loudness_columns.hip, field_columns.hip, band_columns.hip),
+// six column lanes -- waveform, level, true-peak, loudness, stereo-field, band (<lane>_columns.hip; their entry points: column_lanes.hpp),
 // which reduce every piece's new samples behind the converter in that order -- are ONE PcmLane type, a sink of columns with the open column's
-// carry, and differ in a hook that makes the one call of their reduction.  The feed walks the lanes; all ride the same read-back.
+// carry, and differ in a hook that makes the one call of their reduction: one of two templates, for the two carry rules.  The feed walks the
+// lanes; all ride the same read-back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,8 +18,7 @@
 #include <new>
 
 #include "rt_common.hpp"       // isPinnedHost
-#include "runtime.hpp"
-#include "scope_ring.hpp"     // StreamScratch
+#include "column_lanes.hpp"    // the column lanes' entry points
 
 namespace sgz {
 
@@ -294,7 +293,10 @@ using PcmLaneRun = sgz_status (*)(sgz_pcm_stream &s, PcmLane &l, const float *in
 }  // namespace
 
 // A column lane (m > 0: armed): a sink of columns of m samples.  open: the open column's sample count; its state is in half `cur` of d_carry
-// [2][...] -- a step reads that half and writes the other, so no launch reads what it writes
+// [2][...] -- a step reads that half and writes the other, so no launch reads what it writes.  The true-peak, loudness and band carries hold
+// the filter's history too, so every piece with samples writes the other half and the halves alternate.  continued: half `cur` holds the
+// samples before the next one (false after arming or a reset: the history is zeros); index: the lane's samples so far -- the absolute index
+// of the next one, which a flush does not move (the loudness and band lanes' segment phase)
 struct PcmLane {
     PcmSink sink;
     const char *word = "", *call = "";                  // for messages: "true-peak", and the calls' suffix, "truepeak"
@@ -303,6 +305,13 @@ struct PcmLane {
     uint64_t open = 0;
     int cur = 0;
     void *d_carry = nullptr;
+    size_t carryCap = 0;                                // what is allocated, where the carry's size depends on a filter (loudness, band)
+    bool continued = false;
+    uint64_t index = 0;
+    // the loudness and band lanes' scratch (q of a piece's samples, partial records), kept: every piece's launches are on the compute
+    // stream, one behind the other
+    void *d_scratch = nullptr;
+    size_t scratchCap = 0;
 };
 
 struct sgz_pcm_stream {
@@ -324,30 +333,14 @@ struct sgz_pcm_stream {
     bool ovStats = false;
     sgz_overview_stat_record *d_ovStatCarry = nullptr;
     // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels]),
-    // stereo-field (sgz_field_record [2][pairs]) and loudness (two halves of loudnessCarryBytes(ldFilter) * channels bytes; ldCarryCap: what is allocated)
+    // stereo-field (sgz_field_record [2][pairs]), loudness and band (two halves of <lane>CarryBytes(filter) * channels bytes), and the two filters
     PcmLane lane[kPcmLanes];
+    sgz_loudness_filter ldFilter{};
+    sgz_band_filter bdFilter{};
     // the track lane (track.most > 0: armed): a sink of frames, and the graph and mouse position searched
     PcmSink track;
     uint32_t trGraph = 0;
     double trFraction = 0;
-    // the true-peak and loudness carries also hold the filter's history, so every piece with samples writes the other half and the halves
-    // alternate.  Continued: half `cur` holds the samples before the next one (false after arming or a reset: the history is zeros)
-    bool tpContinued = false, ldContinued = false;
-    // ldIndex: the loudness lane's samples so far -- the absolute index of the next one, which a flush does not move
-    sgz_loudness_filter ldFilter{};
-    uint64_t ldIndex = 0;
-    size_t ldCarryCap = 0;
-    // the lane's scratch (q of a piece's samples, partial records), kept: every piece's launches are on the compute stream, one behind the other
-    void *d_ldScratch = nullptr;
-    size_t ldScratchCap = 0;
-    // the band lane's own, as the loudness lane's: the filter, the sample index, the carry (two halves of bandCarryBytes(bdFilter) * channels
-    // bytes) and the kept scratch
-    bool bdContinued = false;
-    sgz_band_filter bdFilter{};
-    uint64_t bdIndex = 0;
-    size_t bdCarryCap = 0;
-    void *d_bdScratch = nullptr;
-    size_t bdScratchCap = 0;
 
     PcmSink &sink(int id) { return id < kPcmLanes ? lane[id].sink : track; }
 };
@@ -380,110 +373,88 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
 }
 
 // ---- the lanes inside the stream (sgz.h, "The waveform lane" ... "The loudness lane", "The track lane") -----------------------------------------
-// The six hooks.  The waveform, level and stereo-field carries hold the open column alone: a step moves to the other half only when a column stays open.
-static sgz_status pcmWaveRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
+// The hooks are two templates over what a lane's two steps are called, for the two carry rules.
+// The waveform, level and stereo-field carries hold the open column alone: a step moves to the other half only when a column stays open.
+// Record: the element of the carry and of the output, PerCell of them per channel (or, OfPairs, per pair); Shape, Run: the lane's two steps
+template <class Record, size_t PerCell, bool OfPairs, auto Shape, auto Run>
+static sgz_status pcmOpenColumnRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
 {
-    const uint32_t channels = s.numChannels, open = uint32_t(l.open);
-    const WaveColumnsShape sh = waveColumnsShape(channels, n, l.m, open, flush, 0);
+    const uint32_t cells = OfPairs ? s.cfg.num_pairs : s.numChannels, open = uint32_t(l.open);
+    const ColumnsShape sh = Shape(cells, n, l.m, open, flush, 0);
     StreamScratch scratch(s.compute);
     if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    float *carry = static_cast<float *>(l.d_carry);
-    const size_t half = size_t(2) * channels;
-    const sgz_status st = runWaveColumns(sh, in, s.stride, channels, n, l.m, open, carry + l.cur * half, carry + (l.cur ^ 1) * half,
-                                         static_cast<float *>(d_out), scratch.p, s.compute);
+    Record *carry = static_cast<Record *>(l.d_carry);
+    const size_t half = PerCell * cells;
+    const sgz_status st = Run(sh, in, s.stride, cells, n, l.m, open, carry + l.cur * half, carry + (l.cur ^ 1) * half, static_cast<Record *>(d_out),
+                              scratch.p, s.compute);
     if (st != SGZ_OK) return st;
     if (sh.open) l.cur ^= 1;
     *closed = sh.closed;
     return SGZ_OK;
 }
 
-static sgz_status pcmLevelRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
-{
-    const uint32_t pairs = s.cfg.num_pairs, open = uint32_t(l.open);
-    const LevelColumnsShape sh = levelColumnsShape(pairs, n, l.m, open, flush, 0);
-    StreamScratch scratch(s.compute);
-    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    sgz_level_record *carry = static_cast<sgz_level_record *>(l.d_carry);
-    const sgz_status st = runLevelColumns(sh, in, s.stride, pairs, n, l.m, open, carry + size_t(l.cur) * pairs, carry + size_t(l.cur ^ 1) * pairs,
-                                          static_cast<sgz_level_record *>(d_out), scratch.p, s.compute);
-    if (st != SGZ_OK) return st;
-    if (sh.open) l.cur ^= 1;
-    *closed = sh.closed;
-    return SGZ_OK;
-}
+// The true-peak, loudness and band carries hold the filter's history too: every step with samples moves to the other half, whether or not a
+// column stays open.  A flush emits the open column of the current half as continued and leaves the carry, and with it the history, where it
+// is.  Lane: shape, the lane's <lane>ColumnsShape; carryBytes(s), a channel's carry; keptScratch (else stream-ordered); run(...), the lane's
+// run<Lane>Columns with what it takes from the stream (the filter, the sample index)
+struct PcmTruePeak {
+    static constexpr bool keptScratch = false;
+    static constexpr auto shape = truePeakColumnsShape;
+    static size_t carryBytes(const sgz_pcm_stream &) { return sizeof(sgz_truepeak_carry); }
+    static sgz_status run(sgz_pcm_stream &s, PcmLane &l, const ColumnsShape &sh, const float *in, size_t n, uint32_t continued, const void *carryIn,
+                          void *carryOut, void *d_out, void *scratch)
+    {
+        return runTruePeakColumns(sh, in, s.stride, s.numChannels, n, l.m, uint32_t(l.open), continued, static_cast<const sgz_truepeak_carry *>(carryIn),
+                                  static_cast<sgz_truepeak_carry *>(carryOut), static_cast<sgz_truepeak_record *>(d_out), scratch, s.compute);
+    }
+};
+struct PcmLoudness {
+    static constexpr bool keptScratch = true;
+    static constexpr auto shape = loudnessColumnsShape;
+    static size_t carryBytes(const sgz_pcm_stream &s) { return loudnessCarryBytes(s.ldFilter); }
+    static sgz_status run(sgz_pcm_stream &s, PcmLane &l, const ColumnsShape &sh, const float *in, size_t n, uint32_t continued, const void *carryIn,
+                          void *carryOut, void *d_out, void *scratch)
+    {
+        return runLoudnessColumns(sh, s.ldFilter, in, s.stride, s.numChannels, n, l.index, l.m, uint32_t(l.open), continued, carryIn, carryOut,
+                                  static_cast<sgz_loudness_record *>(d_out), scratch, s.compute);
+    }
+};
+struct PcmBand {
+    static constexpr bool keptScratch = true;
+    static constexpr auto shape = bandColumnsShape;
+    static size_t carryBytes(const sgz_pcm_stream &s) { return bandCarryBytes(s.bdFilter); }
+    static sgz_status run(sgz_pcm_stream &s, PcmLane &l, const ColumnsShape &sh, const float *in, size_t n, uint32_t continued, const void *carryIn,
+                          void *carryOut, void *d_out, void *scratch)
+    {
+        return runBandColumns(sh, s.bdFilter, in, s.stride, s.numChannels, n, l.index, l.m, uint32_t(l.open), continued, carryIn, carryOut,
+                              static_cast<sgz_band_record *>(d_out), scratch, s.compute);
+    }
+};
 
-// (the stereo-field carry is sgz_field_record [2][pairs]: no filter history, the level lane's flip rule)
-static sgz_status pcmFieldRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
+template <class Lane>
+static sgz_status pcmHistoryRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
 {
-    const uint32_t pairs = s.cfg.num_pairs, open = uint32_t(l.open);
-    const FieldColumnsShape sh = fieldColumnsShape(pairs, n, l.m, open, flush, 0);
-    StreamScratch scratch(s.compute);
-    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    sgz_field_record *carry = static_cast<sgz_field_record *>(l.d_carry);
-    const sgz_status st = runFieldColumns(sh, in, s.stride, pairs, n, l.m, open, carry + size_t(l.cur) * pairs, carry + size_t(l.cur ^ 1) * pairs,
-                                          static_cast<sgz_field_record *>(d_out), scratch.p, s.compute);
-    if (st != SGZ_OK) return st;
-    if (sh.open) l.cur ^= 1;
-    *closed = sh.closed;
-    return SGZ_OK;
-}
-
-// The true-peak and loudness carries hold the filter's history too: every step with samples moves to the other half, whether or not a column
-// stays open.  A flush emits the open column of the current half as continued and leaves the carry, and with it the history, where it is
-static sgz_status pcmTruePeakRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
-{
-    const uint32_t channels = s.numChannels, open = uint32_t(l.open);
-    const TruePeakColumnsShape sh = truePeakColumnsShape(channels, n, l.m, open, flush, 0);
-    StreamScratch scratch(s.compute);
-    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    sgz_truepeak_carry *carry = static_cast<sgz_truepeak_carry *>(l.d_carry);
-    const sgz_status st = runTruePeakColumns(sh, in, s.stride, channels, n, l.m, open, (flush || s.tpContinued) ? 1u : 0u, carry + size_t(l.cur) * channels,
-                                             carry + size_t(l.cur ^ 1) * channels, static_cast<sgz_truepeak_record *>(d_out), scratch.p, s.compute);
-    if (st != SGZ_OK) return st;
-    if (!flush) { l.cur ^= 1; s.tpContinued = true; }
-    *closed = sh.closed;
-    return SGZ_OK;
-}
-
-static sgz_status pcmLoudnessRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
-{
-    const uint32_t channels = s.numChannels, open = uint32_t(l.open);
-    const LoudnessColumnsShape sh = loudnessColumnsShape(channels, n, l.m, open, flush, 0);
-    if (sh.scratchBytes > s.ldScratchCap) {                                         // (the first piece of a feed is its largest: this happens once)
-        SGZ_HIP(hipStreamSynchronize(s.compute));
-        if (s.d_ldScratch) { (void)hipFree(s.d_ldScratch); s.d_ldScratch = nullptr; s.ldScratchCap = 0; }
-        SGZ_HIP(hipMalloc(&s.d_ldScratch, sh.scratchBytes));
-        s.ldScratchCap = sh.scratchBytes;
+    const uint32_t channels = s.numChannels;
+    const ColumnsShape sh = Lane::shape(channels, n, l.m, uint32_t(l.open), flush, 0);
+    StreamScratch ordered(s.compute);
+    void *scratch = nullptr;
+    if constexpr (Lane::keptScratch) {
+        if (sh.scratchBytes > l.scratchCap) {                                       // (the first piece of a feed is its largest: this happens once)
+            SGZ_HIP(hipStreamSynchronize(s.compute));
+            if (l.d_scratch) { (void)hipFree(l.d_scratch); l.d_scratch = nullptr; l.scratchCap = 0; }
+            SGZ_HIP(hipMalloc(&l.d_scratch, sh.scratchBytes));
+            l.scratchCap = sh.scratchBytes;
+        }
+        scratch = flush ? nullptr : l.d_scratch;
+    } else {
+        if (sh.scratchBytes) SGZ_HIP(ordered.get(sh.scratchBytes));
+        scratch = ordered.p;
     }
     uint8_t *carry = static_cast<uint8_t *>(l.d_carry);
-    const size_t half = loudnessCarryBytes(s.ldFilter) * channels;
-    const sgz_status st = runLoudnessColumns(sh, s.ldFilter, in, s.stride, channels, n, s.ldIndex, l.m, open, (flush || s.ldContinued) ? 1u : 0u,
-                                             carry + l.cur * half, carry + (l.cur ^ 1) * half, static_cast<sgz_loudness_record *>(d_out),
-                                             flush ? nullptr : s.d_ldScratch, s.compute);
+    const size_t half = Lane::carryBytes(s) * channels;
+    const sgz_status st = Lane::run(s, l, sh, in, n, (flush || l.continued) ? 1u : 0u, carry + l.cur * half, carry + (l.cur ^ 1) * half, d_out, scratch);
     if (st != SGZ_OK) return st;
-    if (!flush) { l.cur ^= 1; s.ldContinued = true; s.ldIndex += n; }
-    *closed = sh.closed;
-    return SGZ_OK;
-}
-
-// (the band lane: the loudness lane's carry rules with its own filter, index and scratch)
-static sgz_status pcmBandRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
-{
-    const uint32_t channels = s.numChannels, open = uint32_t(l.open);
-    const BandColumnsShape sh = bandColumnsShape(channels, n, l.m, open, flush, 0);
-    if (sh.scratchBytes > s.bdScratchCap) {                                         // (the first piece of a feed is its largest: this happens once)
-        SGZ_HIP(hipStreamSynchronize(s.compute));
-        if (s.d_bdScratch) { (void)hipFree(s.d_bdScratch); s.d_bdScratch = nullptr; s.bdScratchCap = 0; }
-        SGZ_HIP(hipMalloc(&s.d_bdScratch, sh.scratchBytes));
-        s.bdScratchCap = sh.scratchBytes;
-    }
-    uint8_t *carry = static_cast<uint8_t *>(l.d_carry);
-    const size_t half = bandCarryBytes(s.bdFilter) * channels;
-    const sgz_status st = runBandColumns(sh, s.bdFilter, in, s.stride, channels, n, s.bdIndex, l.m, open, (flush || s.bdContinued) ? 1u : 0u,
-                                         carry + l.cur * half, carry + (l.cur ^ 1) * half, static_cast<sgz_band_record *>(d_out),
-                                         flush ? nullptr : s.d_bdScratch, s.compute);
-    if (st != SGZ_OK) return st;
-    if (!flush) { l.cur ^= 1; s.bdContinued = true; s.bdIndex += n; }
+    if (!flush) { l.cur ^= 1; l.continued = true; l.index += n; }
     *closed = sh.closed;
     return SGZ_OK;
 }
@@ -518,7 +489,7 @@ static void pcmLaneArm(sgz_pcm_stream &s, PcmLane &l, uint32_t m, void *out, uin
     l.m = m;
     l.sink.arm((s.chunk + m - 1) / m + 1, out, capacity);
 }
-static void pcmLaneDisarm(PcmLane &l) { l.m = 0; l.open = 0; l.sink.disarm(); }         // off: the open column is dropped
+static void pcmLaneDisarm(PcmLane &l) { l.m = 0; l.open = 0; l.continued = false; l.index = 0; l.sink.disarm(); }     // off: the open column, the history and the index are dropped
 
 static uint64_t pcmLaneFor(const sgz_pcm_stream *s, int id, size_t nsamples, int flush)
 {
@@ -835,9 +806,8 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
     for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry}) if (p) (void)hipFree(p);
-    for (PcmLane &l : s->lane) if (l.d_carry) (void)hipFree(l.d_carry);
-    if (s->d_ldScratch) (void)hipFree(s->d_ldScratch);
-    if (s->d_bdScratch) (void)hipFree(s->d_bdScratch);
+    for (PcmLane &l : s->lane)
+        for (void *p : {l.d_carry, l.d_scratch}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
     if (s->plan) sgz_plan_destroy(s->plan);
     delete s;
@@ -864,12 +834,12 @@ sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format
     s->maxFrames = (s->chunk - 1) / cfg->hop + 1;
     // the lanes: the word for messages, the calls' suffix, the slot's output, the bytes of one column (a record per channel or pair), the hook
     const struct { const char *word, *call; PcmOutKind kind; size_t unit; PcmLaneRun run; } lanes[kPcmLanes] = {
-        {"waveform", "waveform", kOutWave, s->numChannels * 2 * sizeof(float), pcmWaveRun},
-        {"level", "level", kOutLevel, cfg->num_pairs * sizeof(sgz_level_record), pcmLevelRun},
-        {"true-peak", "truepeak", kOutTruePeak, s->numChannels * sizeof(sgz_truepeak_record), pcmTruePeakRun},
-        {"loudness", "loudness", kOutLoudness, s->numChannels * sizeof(sgz_loudness_record), pcmLoudnessRun},
-        {"stereo-field", "field", kOutField, cfg->num_pairs * sizeof(sgz_field_record), pcmFieldRun},
-        {"band", "band", kOutBand, s->numChannels * sizeof(sgz_band_record), pcmBandRun},
+        {"waveform", "waveform", kOutWave, s->numChannels * 2 * sizeof(float), pcmOpenColumnRun<float, 2, false, waveColumnsShape, runWaveColumns>},
+        {"level", "level", kOutLevel, cfg->num_pairs * sizeof(sgz_level_record), pcmOpenColumnRun<sgz_level_record, 1, true, levelColumnsShape, runLevelColumns>},
+        {"true-peak", "truepeak", kOutTruePeak, s->numChannels * sizeof(sgz_truepeak_record), pcmHistoryRun<PcmTruePeak>},
+        {"loudness", "loudness", kOutLoudness, s->numChannels * sizeof(sgz_loudness_record), pcmHistoryRun<PcmLoudness>},
+        {"stereo-field", "field", kOutField, cfg->num_pairs * sizeof(sgz_field_record), pcmOpenColumnRun<sgz_field_record, 1, true, fieldColumnsShape, runFieldColumns>},
+        {"band", "band", kOutBand, s->numChannels * sizeof(sgz_band_record), pcmHistoryRun<PcmBand>},
     };
     for (int id = 0; id < kPcmLanes; ++id) {
         PcmLane &l = s->lane[id];
@@ -908,10 +878,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     s->held = 0;
     s->ovOpen = 0; s->ovStats = false;                                              // an open overview column, of either kind, is dropped
     for (int id = 0; id < kPcmSinks; ++id) s->sink(id).cursor = 0;                  // every lane's columns and the track's records start over; all stay armed
-    for (PcmLane &l : s->lane) l.open = 0;                                          // open columns are dropped
-    s->tpContinued = s->ldContinued = false;                                        // the true-peak and loudness histories are zeros again
-    s->ldIndex = 0;                                                                 // and the loudness lane's samples count from 0
-    s->bdContinued = false; s->bdIndex = 0;                                         // the band lane's likewise
+    for (PcmLane &l : s->lane) { l.open = 0; l.continued = false; l.index = 0; }    // open columns are dropped, the histories are zeros again and the samples count from 0
     return SGZ_OK;
 }
 
@@ -1055,12 +1022,12 @@ sgz_status sgz_pcm_stream_set_truepeak(sgz_pcm_stream *s, uint32_t m, sgz_truepe
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
     PcmLane &l = s->lane[kSinkTruePeak];
-    if (m == 0) { pcmLaneDisarm(l); s->tpContinued = false; return SGZ_OK; }                 // (the history is dropped too)
+    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
     if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: null out");
     if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_truepeak_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: out is not aligned to 8 bytes");
     if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: m differs from the open column's -- flush it (sgz_pcm_stream_flush_truepeak), disarm or reset first");
     if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * sizeof(sgz_truepeak_carry)));
-    if (m != l.m) s->tpContinued = false;                          // (arming: the lane starts at the next sample with a zero history; the same m keeps it)
+    if (m != l.m) l.continued = false;                          // (arming: the lane starts at the next sample with a zero history; the same m keeps it)
     pcmLaneArm(*s, l, m, out, capacity_columns);
     return SGZ_OK;
 }
@@ -1069,7 +1036,7 @@ sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_fil
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
     PcmLane &l = s->lane[kSinkLoudness];
-    if (m == 0) { pcmLaneDisarm(l); s->ldIndex = 0; s->ldContinued = false; return SGZ_OK; }  // (the history and the index are dropped too)
+    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
     if (!filter) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: null filter");
     if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: null out");
     if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_loudness_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: out is not aligned to 8 bytes");
@@ -1081,16 +1048,16 @@ sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_fil
         if (sgz_status st = sgz_loudness_columns_limits(filter, s->numChannels, nullptr, nullptr, &bytes); st != SGZ_OK) return st;
         std::vector<int32_t> taps(size_t(4) * filter->W);
         if (sgz_status st = sgz_loudness_taps(filter, taps.data()); st != SGZ_OK) return st;
-        if (s->ldCarryCap < 2 * bytes) {
+        if (l.carryCap < 2 * bytes) {
             // (both slots are idle between feeds, but a flush's launch may still read the old block: wait for it)
             SGZ_HIP(hipStreamSynchronize(s->compute));
-            if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; s->ldCarryCap = 0; }
+            if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; l.carryCap = 0; }
             SGZ_HIP(hipMalloc(&l.d_carry, 2 * bytes));
-            s->ldCarryCap = 2 * bytes;
+            l.carryCap = 2 * bytes;
         }
         s->ldFilter = *filter;
-        s->ldContinued = false;                                    // (arming: the lane starts at the next sample, index 0, with a zero history)
-        s->ldIndex = 0; l.cur = 0;
+        l.continued = false;                                       // (arming: the lane starts at the next sample, index 0, with a zero history)
+        l.index = 0; l.cur = 0;
     }
     pcmLaneArm(*s, l, m, out, capacity_columns);
     return SGZ_OK;
@@ -1114,7 +1081,7 @@ sgz_status sgz_pcm_stream_set_band(sgz_pcm_stream *s, const sgz_band_filter *fil
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
     PcmLane &l = s->lane[kSinkBand];
-    if (m == 0) { pcmLaneDisarm(l); s->bdIndex = 0; s->bdContinued = false; return SGZ_OK; }  // (the history and the index are dropped too)
+    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
     if (m < 64) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: m >= 64 samples per column (a 64-byte record per channel for fewer would read back more than the samples)");
     if (!filter) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: null filter");
     if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: null out");
@@ -1127,16 +1094,16 @@ sgz_status sgz_pcm_stream_set_band(sgz_pcm_stream *s, const sgz_band_filter *fil
         if (sgz_status st = sgz_band_columns_limits(filter, s->numChannels, nullptr, nullptr, &bytes); st != SGZ_OK) return st;
         std::vector<int32_t> taps(size_t(16) * filter->W);
         if (sgz_status st = sgz_band_taps(filter, taps.data()); st != SGZ_OK) return st;
-        if (s->bdCarryCap < 2 * bytes) {
+        if (l.carryCap < 2 * bytes) {
             // (both slots are idle between feeds, but a flush's launch may still read the old block: wait for it)
             SGZ_HIP(hipStreamSynchronize(s->compute));
-            if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; s->bdCarryCap = 0; }
+            if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; l.carryCap = 0; }
             SGZ_HIP(hipMalloc(&l.d_carry, 2 * bytes));
-            s->bdCarryCap = 2 * bytes;
+            l.carryCap = 2 * bytes;
         }
         s->bdFilter = *filter;
-        s->bdContinued = false;                                    // (arming: the lane starts at the next sample, index 0, with a zero history)
-        s->bdIndex = 0; l.cur = 0;
+        l.continued = false;                                       // (arming: the lane starts at the next sample, index 0, with a zero history)
+        l.index = 0; l.cur = 0;
     }
     pcmLaneArm(*s, l, m, out, capacity_columns);
     return SGZ_OK;

@@ -120,55 +120,7 @@ sgz_status runOverviewStatsView(Plan &p, const sgz_overview_stat_record *d_src, 
 sgz_status runOverviewStatsSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
                                  int flush, sgz_overview_stat_record *d_carry, float *d_state, uint8_t *d_rgba, sgz_overview_stat_record *d_stats,
                                  float *d_means, hipStream_t stream, const SlabTrack *track = nullptr);
-// the waveform lane's reduction (wave_columns.hip): (lo, hi) per column of m samples and channel, the open column in a carry; what
-// sgz_stage_wave_columns and sgz_pcm_stream share.  The arguments are the stage call's, checked by the caller; asynchronous on `stream`
-struct WaveColumnsShape {
-    uint64_t columns, closed;            // columns the call touches; those it emits
-    bool open, launch;                   // a last column stays open (it goes to the carry); anything is launched at all
-    uint32_t slices;                     // 0: the tile form
-    size_t scratchBytes;                 // partial pairs of the sliced form
-};
-WaveColumnsShape waveColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
-sgz_status runWaveColumns(const WaveColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples, uint32_t m,
-                          uint32_t held, const float *carryIn, float *carryOut, float *d_wave, void *scratch, hipStream_t stream);
-// the level lane's reduction (level_columns.hip), the same two steps: the shape (scratchBytes: the partial records of the sliced form), then
-// sgz_stage_level_columns behind its argument checks with the carry in two places
-using LevelColumnsShape = WaveColumnsShape;
-LevelColumnsShape levelColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
-sgz_status runLevelColumns(const LevelColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
-                           uint32_t held, const sgz_level_record *carryIn, sgz_level_record *carryOut, sgz_level_record *d_level, void *scratch,
-                           hipStream_t stream);
-// the stereo-field lane's reduction (field_columns.hip), the same two steps with the level lane's carry rules
-using FieldColumnsShape = WaveColumnsShape;
-FieldColumnsShape fieldColumnsShape(uint32_t pairs, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
-sgz_status runFieldColumns(const FieldColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t pairs, size_t nsamples, uint32_t m,
-                           uint32_t held, const sgz_field_record *carryIn, sgz_field_record *carryOut, sgz_field_record *d_field, void *scratch,
-                           hipStream_t stream);
-// the true-peak lane's reduction (truepeak_columns.hip), the same two steps.  carryIn is read (the history when `continued`, the open column
-// when held > 0) and carryOut is written whole by every call with samples: two places, never the same memory then
-using TruePeakColumnsShape = WaveColumnsShape;
-TruePeakColumnsShape truePeakColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
-sgz_status runTruePeakColumns(const TruePeakColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples,
-                              uint32_t m, uint32_t held, uint32_t continued, const sgz_truepeak_carry *carryIn, sgz_truepeak_carry *carryOut,
-                              sgz_truepeak_record *d_peaks, void *scratch, hipStream_t stream);
-// the loudness lane's reduction (loudness_columns.hip), the same two steps.  The carry is loudnessCarryBytes(f) bytes per channel: the open
-// column's record, the last W + L - 1 quantised samples, a zero word.  firstIndex: the absolute index of the call's first sample (the segment
-// phase).  scratch: sh.scratchBytes bytes aligned to 16 (q of every sample, then the sliced form's partial records)
-using LoudnessColumnsShape = WaveColumnsShape;
-size_t loudnessCarryBytes(const sgz_loudness_filter &f);
-LoudnessColumnsShape loudnessColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
-sgz_status runLoudnessColumns(const LoudnessColumnsShape &sh, const sgz_loudness_filter &f, const float *d_planar, size_t channelStride,
-                              uint32_t channels, size_t nsamples, uint64_t firstIndex, uint32_t m, uint32_t held, uint32_t continued,
-                              const void *carryIn, void *carryOut, sgz_loudness_record *d_out, void *scratch, hipStream_t stream);
-// the band lane's reduction (band_columns.hip), the loudness lane's two steps.  The carry is bandCarryBytes(f) bytes per channel: the open
-// column's record, the last W + L - 1 quantised samples, a zero word.  scratch: sh.scratchBytes bytes aligned to 16 (the three q planes of
-// every sample, then the sliced form's partial records)
-using BandColumnsShape = WaveColumnsShape;
-size_t bandCarryBytes(const sgz_band_filter &f);
-BandColumnsShape bandColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
-sgz_status runBandColumns(const BandColumnsShape &sh, const sgz_band_filter &f, const float *d_planar, size_t channelStride, uint32_t channels,
-                          size_t nsamples, uint64_t firstIndex, uint32_t m, uint32_t held, uint32_t continued, const void *carryIn, void *carryOut,
-                          sgz_band_record *d_out, void *scratch, hipStream_t stream);
+// the column lanes' reductions (wave, level, true-peak, loudness, stereo-field, band): column_lanes.hpp
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
 }  // namespace sgz

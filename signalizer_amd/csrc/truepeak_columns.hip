@@ -2,14 +2,15 @@
 // per column of m samples and channel of a linear planar stream, with a carried open column and a carried filter history (sgz.h, "The
 // true-peak lane"); and the lane's host helpers, the tap table, the fold of kept records and the readout of one.  gfx950 only.  The reference
 // has no counterpart: its meters are live one-pole filters.
-//   v = (int32) clamp(rintf(x 2^23), -2^26, +2^26), a NaN is v = 0 and is not counted;  y[i][q] = sum_j c[q][j] v[i - j], 12 taps per phase,
+// What the column lanes share -- the shape of a call, the bounds, the quantiser, the aligned split, the stage call's front with the carry's
+// snapshot, the fold's frame -- is column_lanes.hpp; this file is the filter and the halo it needs.
+//   v = the quantiser's (quantiseMarked), a NaN is v = 0 and is not counted;  y[i][q] = sum_j c[q][j] v[i - j], 12 taps per phase,
 //   4 phases, integer taps at 2^20: every y is an exact integer below 2^47, the record a maximum and two integer sums, so any cut of the
 //   stream (calls with a carry) or of a column (lanes, slices) gives the same bits.
 // The multiply-adds come in two forms with the same bits, chosen at build time by SGZ_TP_FP64: 32 x 32 -> 64-bit integer multiply-adds
 // (v_mad_i64_i32) and FMAs on integer-valued doubles, exact below 2^53 -- every operand is an integer, so fp contraction cannot change a bit
 // either way.  Which one is built and what both cost: DESIGN.md section 8, row b8.
-// Column c of a call covers its samples [c m - held, (c + 1) m - held) clipped to [0, n): column 0 is the rest of the carried column
-// (held > 0), the last one may stay open.  Sample k < 0 of a call is word 11 + k of the carried history (zeros when the stream begins here).
+// Sample k < 0 of a call is word 11 + k of the carried history (zeros when the stream begins here).
 //   m <= kTpSwitch (1024)   truePeakTileKernel: one workgroup per (channel, tile); a tile is kTpTile / m whole columns of the call (column 0
 //                           counts as one, whatever is left of it).  The tile goes to LDS once, quantised on the way (16-byte loads between
 //                           the row's first and last 16-byte boundary, scalar loads on either side, the base only 4-byte aligned), behind an
@@ -32,8 +33,7 @@
 #include <cstring>
 #include <limits>
 
-#include "runtime.hpp"
-#include "scope_ring.hpp"      // StreamScratch
+#include "column_lanes.hpp"
 
 using namespace sgz;
 
@@ -73,11 +73,11 @@ static_assert(sizeof(((sgz_truepeak_carry *)nullptr)->hist) == kTpHist * sizeof(
 constexpr int kTpThreads = 256;
 constexpr uint32_t kTpTile = 4096;              // samples of a tile
 constexpr uint32_t kTpSwitch = 1024;            // the switch-over: columns longer than this take the sliced form
-constexpr uint32_t kTpMaxSlices = 64, kTpMaxChannels = 64;
+constexpr uint32_t kTpMaxChannels = 64;
 constexpr uint32_t kTpRun = 16;                 // the most samples a lane walks in one run
 constexpr int kTpUnroll = 4;                    // 16-byte loads a lane issues before the first store to LDS
 constexpr uint32_t kTpBase = 12;                // where the tile's 16-byte grid begins in LDS: room for the halo in front, a multiple of 4
-constexpr int32_t kTpNaN = std::numeric_limits<int32_t>::min();     // a NaN in LDS (no quantised sample: |v| <= 2^26)
+constexpr int32_t kTpNaN = kQuantNaN;           // a NaN in LDS
 // where sample word i lies in LDS: one word of padding behind every 16, so that runs 16 words apart start on different banks
 __host__ __device__ constexpr uint32_t padWord(uint32_t i) { return i + (i >> 4); }
 constexpr uint32_t kTpTileWords = padWord(kTpBase + 3 + kTpTile) + 1;      // the halo, the lead (the base's offset within 16 bytes), the tile
@@ -102,20 +102,12 @@ struct TruePeakParams {
     sgz_truepeak_record *partial;        // [slices][columns][channels]
 };
 
-// the quantiser; kTpNaN for a NaN.  (x 2^23 is exact or overflows to an infinity, which the clamp takes; a denormal times 2^23 is below 2^-102
-// and rounds to 0, as does the 0 a flushing device makes of it)
-__device__ __forceinline__ int32_t quantise(uint32_t bits)
-{
-    const float x = __uint_as_float(bits);
-    const float r = __builtin_amdgcn_fmed3f(rintf(x * 0x1p23f), -0x1p26f, 0x1p26f);
-    return x != x ? kTpNaN : int32_t(r);
-}
 __device__ __forceinline__ int32_t silenceForNaN(int32_t v) { return v == kTpNaN ? 0 : v; }
 
 // what the filter sees at sample k of the call, k >= -11: the call's own sample, or the carried history in front of it
 __device__ __forceinline__ int32_t filterInput(const TruePeakParams &prm, uint32_t ch, long k)
 {
-    if (k >= 0) return silenceForNaN(quantise(__float_as_uint(prm.planar[size_t(ch) * prm.stride + size_t(k)])));
+    if (k >= 0) return silenceForNaN(quantiseMarked(__float_as_uint(prm.planar[size_t(ch) * prm.stride + size_t(k)])));
     return prm.continued ? prm.carryIn[ch].hist[kTpHist + k] : 0;
 }
 
@@ -244,15 +236,6 @@ __device__ __forceinline__ void walkRun(const int32_t *tile, uint32_t from, uint
     k.peak = run > k.peak ? run : k.peak;
 }
 
-// samples [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnSamples(const TruePeakParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.m) - long(prm.held);
-    b = a + long(prm.m);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
-}
-
 // what a (column, channel) does with its record: the carry into column 0, then to the output (a closed column) or to the carry's open column
 __device__ __forceinline__ void emitColumn(const TruePeakParams &prm, long col, uint32_t ch, Acc k)
 {
@@ -269,16 +252,6 @@ __device__ __forceinline__ void writeCarry(const TruePeakParams &prm, uint32_t c
     if (t == uint32_t(kTpHist) + 1 && prm.closed == prm.columns) nothing().store(&prm.carryOut[ch].open);
 }
 
-// where the 16-byte part of `count` floats at g begins and ends: [0, head) and [tail, count) are scalar, `vecs` chunks lie between
-__device__ __forceinline__ void splitAligned(const float *g, uint32_t count, uint32_t &head, uint32_t &vecs, uint32_t &tail)
-{
-    const uint32_t lead = uint32_t(reinterpret_cast<uintptr_t>(g) >> 2) & 3u;
-    const uint32_t toBoundary = (4u - lead) & 3u;
-    head = count < toBoundary ? count : toBoundary;
-    vecs = (count - head) >> 2;
-    tail = head + 4 * vecs;
-}
-
 // samples [a, a + count) of channel ch (count <= kTpTile), quantised, into the tile behind their 11-word halo; returns where sample a lies
 // (LDS sample word kTpBase + lead: the tile keeps the row's offset within 16 bytes, so a 16-byte chunk of memory is four words of one
 // 16-word block of LDS).  The caller puts a barrier behind it.
@@ -290,8 +263,8 @@ __device__ __forceinline__ uint32_t stageTile(const TruePeakParams &prm, uint32_
     uint32_t head, vecs, tail;
     splitAligned(g, count, head, vecs, tail);
     if (tid < uint32_t(kTpHist)) tile[padWord(first - uint32_t(kTpHist) + tid)] = filterInput(prm, ch, a - long(kTpHist) + long(tid));
-    if (tid < head) tile[padWord(first + tid)] = quantise(__float_as_uint(g[tid]));
-    if (tid < count - tail) tile[padWord(first + tail + tid)] = quantise(__float_as_uint(g[tail + tid]));
+    if (tid < head) tile[padWord(first + tid)] = quantiseMarked(__float_as_uint(g[tid]));
+    if (tid < count - tail) tile[padWord(first + tail + tid)] = quantiseMarked(__float_as_uint(g[tail + tid]));
     const uint4 *gv = reinterpret_cast<const uint4 *>(g + head);
     uint4 v[kTpUnroll];
 #pragma unroll
@@ -301,7 +274,7 @@ __device__ __forceinline__ uint32_t stageTile(const TruePeakParams &prm, uint32_
     for (int j = 0; j < kTpUnroll; ++j)                                     // (first + head is a multiple of 4 wherever vecs > 0: the four words share a block)
         if (tid + uint32_t(j) * kTpThreads < vecs) {
             int32_t *to = tile + padWord(first + head + 4u * (tid + uint32_t(j) * kTpThreads));
-            to[0] = quantise(v[j].x); to[1] = quantise(v[j].y); to[2] = quantise(v[j].z); to[3] = quantise(v[j].w);
+            to[0] = quantiseMarked(v[j].x); to[1] = quantiseMarked(v[j].y); to[2] = quantiseMarked(v[j].z); to[3] = quantiseMarked(v[j].w);
         }
     return first;
 }
@@ -312,11 +285,9 @@ truePeakTileKernel(const TruePeakParams prm)
 {
     __shared__ int32_t tile[kTpTileWords];
     const uint32_t tid = threadIdx.x, ch = blockIdx.y;
-    const long c0 = long(blockIdx.x) * long(prm.perTile);
-    const long c1 = c0 + long(prm.perTile) < prm.columns ? c0 + long(prm.perTile) : prm.columns;
-    long a = c0 * long(prm.m) - long(prm.held), b = c1 * long(prm.m) - long(prm.held);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
+    TileBounds t;
+    tileBounds(prm, t);
+    const long c0 = t.c0, c1 = t.c1, a = t.a, b = t.b;
     const uint32_t first = stageTile(prm, ch, a, uint32_t(b - a), tile);   // (b - a <= perTile * m <= kTpTile)
     if (c1 == prm.columns) writeCarry(prm, ch, tid);                        // (the last tile's workgroup; carryOut is not carryIn)
     __syncthreads();
@@ -346,10 +317,9 @@ truePeakSliceKernel(const TruePeakParams prm)
     __shared__ sgz_truepeak_record waves[kTpThreads / 64];
     const long col = long(blockIdx.x);
     const uint32_t ch = blockIdx.y, s = blockIdx.z, tid = threadIdx.x;
-    long a, b;
+    long a, b, sa, sb;
     columnSamples(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(s) * per < b ? a + long(s) * per : b, sb = sa + per < b ? sa + per : b;
+    sliceSamples(prm, a, b, s, sa, sb);
     Acc k = nothing();
     for (long at = sa; at < sb; at += long(kTpTile)) {                      // (the same trips in every lane: the barriers see the whole workgroup)
         const uint32_t count = uint32_t(sb - at < long(kTpTile) ? sb - at : long(kTpTile));
@@ -386,36 +356,16 @@ truePeakEmitKernel(const TruePeakParams prm)
         for (uint32_t t = 0; t < uint32_t(kTpHist) + 2; ++t) writeCarry(prm, ch, t);
 }
 
-uint32_t pow2AtLeast(uint32_t v)
-{
-    uint32_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 }  // namespace
 
 namespace sgz {
 
-// The shape of a call whose arguments passed sgz_stage_truepeak_columns' checks, as levelColumnsShape: slices 0 = the tile form, else the
-// sliced form with that many (the caller's count, or for m > kTpSwitch the overview's rule); scratchBytes: the partial records.
-TruePeakColumnsShape truePeakColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
+ColumnsShape truePeakColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
 {
-    TruePeakColumnsShape sh{};
-    const uint64_t t = uint64_t(held) + nsamples;
-    sh.closed = t / m + ((flush && t % m) ? 1u : 0u);
-    sh.open = !flush && t % m != 0;
-    sh.columns = sh.closed + (sh.open ? 1u : 0u);
-    sh.launch = sh.columns != 0 && !(nsamples == 0 && !(flush && held));
-    if (!sh.launch || nsamples == 0) return sh;
-    if (slices >= 2 || m > kTpSwitch) sh.slices = slices ? slices : overviewAutoSlices(long(sh.columns), channels, m, nsamples, numCUs());
-    sh.scratchBytes = size_t(sh.slices) * size_t(sh.columns) * channels * sizeof(sgz_truepeak_record);
-    return sh;
+    return columnsShape(channels, nsamples, m, held, flush, slices, kTpSwitch, sizeof(sgz_truepeak_record), 0);
 }
 
-// sgz_stage_truepeak_columns behind its argument checks, with the carry in two places: carryIn is read (the history when `continued`, the open
-// column when held > 0), carryOut is written whole by every call with samples -- never the same memory then.  scratch: sh.scratchBytes bytes.
-sgz_status runTruePeakColumns(const TruePeakColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples,
+sgz_status runTruePeakColumns(const ColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples,
                               uint32_t m, uint32_t held, uint32_t continued, const sgz_truepeak_carry *carryIn, sgz_truepeak_carry *carryOut,
                               sgz_truepeak_record *d_peaks, void *scratch, hipStream_t stream)
 {
@@ -432,17 +382,17 @@ sgz_status runTruePeakColumns(const TruePeakColumnsShape &sh, const float *d_pla
         prm.group = pow2AtLeast((m + kTpRun - 1) / kTpRun);           // (1 .. 64)
         prm.run = (m + prm.group - 1) / prm.group;                    // (<= kTpRun; group * run >= m)
         const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (tiles > 0x7fffffffull) return fail(SGZ_EINVAL, "true-peak columns: too many columns for one launch");
+        if (sgz_status st = fitsOneLaunch(tiles, "true-peak", "columns"); st != SGZ_OK) return st;
         hipLaunchKernelGGL(truePeakTileKernel, dim3(unsigned(tiles), channels), dim3(kTpThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sh.columns > 0x7fffffffull || (cells + kTpThreads - 1) / kTpThreads > 0x7fffffffull) return fail(SGZ_EINVAL, "true-peak columns: too many columns for one launch");
+    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kTpThreads)), "true-peak", "columns"); st != SGZ_OK) return st;
     if (nsamples != 0) {
         hipLaunchKernelGGL(truePeakSliceKernel, dim3(unsigned(sh.columns), channels, sh.slices), dim3(kTpThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(truePeakEmitKernel, dim3(unsigned((cells + kTpThreads - 1) / kTpThreads)), dim3(kTpThreads), 0, stream, prm);
+    hipLaunchKernelGGL(truePeakEmitKernel, dim3(unsigned(emitBlocks(cells, kTpThreads))), dim3(kTpThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     return SGZ_OK;
 }
@@ -466,63 +416,40 @@ sgz_status sgz_stage_truepeak_columns(const float *d_planar, size_t channel_stri
                                       int flush, uint32_t continued, uint32_t slices, sgz_truepeak_carry *d_carry, sgz_truepeak_record *d_peaks,
                                       void *stream)
 {
-    if (!d_planar) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: null d_planar");
-    if (channels == 0 || channels > kTpMaxChannels) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: 1 .. 64 channels");
-    if (m == 0) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: m >= 1 samples per column");
-    if (held >= m) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: held < m");
-    if (!continued && held) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: held > 0 needs continued != 0 (a stream that begins here has no open column)");
-    if (channel_stride < nsamples || nsamples > (size_t(1) << 62)) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: channel_stride < nsamples");
-    if (slices > kTpMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: slices 0 (automatic) or 1 .. 64");
-    if ((reinterpret_cast<uintptr_t>(d_planar) & 3u) || (reinterpret_cast<uintptr_t>(d_carry) & 15u) || (reinterpret_cast<uintptr_t>(d_peaks) & 15u))
-        return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: d_planar aligned to 4 bytes, d_carry and d_peaks to 16");
-    const TruePeakColumnsShape sh = truePeakColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (!d_carry && (continued || nsamples)) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: d_carry is read (continued) or written (nsamples > 0)");
-    if (!d_peaks && sh.closed) return fail(SGZ_EINVAL, "sgz_stage_truepeak_columns: d_peaks is written (a column closes)");
+    const StageFront front{"sgz_stage_truepeak_columns", "channels", kTpMaxChannels, "d_peaks", 16, true, 62};
+    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, channels, nsamples, m, held, continued, 0, slices, d_carry, d_peaks); st != SGZ_OK) return st;
+    const ColumnsShape sh = truePeakColumnsShape(channels, nsamples, m, held, flush, slices);
+    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, continued, d_carry, d_peaks); st != SGZ_OK) return st;
     if (!sh.launch) return SGZ_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StreamScratch scratch(s), snapshot(s);
-    const sgz_truepeak_carry *carryIn = d_carry;
-    if (continued && nsamples) {
-        // the halos and column 0 read the carry while another workgroup writes the new one: they read a snapshot
-        SGZ_HIP(snapshot.get(size_t(channels) * sizeof(sgz_truepeak_carry)));
-        SGZ_HIP(hipMemcpyAsync(snapshot.p, d_carry, size_t(channels) * sizeof(sgz_truepeak_carry), hipMemcpyDeviceToDevice, s));
-        carryIn = static_cast<const sgz_truepeak_carry *>(snapshot.p);
-    }
-    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    return runTruePeakColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, continued, carryIn, d_carry, d_peaks, scratch.p, s);
+    StageScratch mem(s);
+    const void *carryIn = nullptr;
+    if (sgz_status st = mem.get(front, sh, nsamples, held, continued, d_carry, size_t(channels) * sizeof(sgz_truepeak_carry), &carryIn); st != SGZ_OK) return st;
+    return runTruePeakColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, continued, static_cast<const sgz_truepeak_carry *>(carryIn), d_carry, d_peaks, mem.scratch.p, s);
 }
 
 sgz_status sgz_truepeak_fold(const sgz_truepeak_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns,
                              sgz_truepeak_record *out)
 {
-    if (!in || !out) return fail(SGZ_EINVAL, "sgz_truepeak_fold: null argument");
-    if (channels == 0) return fail(SGZ_EINVAL, "sgz_truepeak_fold: channels >= 1");
-    uint64_t cols = 0;
-    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
-    const uint64_t w = x1 - x0;
-    auto bound = [&](uint64_t b) { return x0 + (b * w + cols - 1) / cols; };                   // (b w < 2^62: n < 2^31)
-    // the sums first: a refusal writes nothing
-    for (uint64_t b = 0; b < cols; ++b)
-        for (uint32_t c = 0; c < channels; ++c) {
-            uint64_t count = 0, overs = 0;
-            for (uint64_t j = bound(b); j < bound(b + 1); ++j) {
-                count += in[j * channels + c].count;
-                overs += in[j * channels + c].overs;
+    return foldColumns(
+        "sgz_truepeak_fold", "channels", "", in, n, channels, x0, x1, out_columns, out,
+        [](const sgz_truepeak_record *v, size_t count, size_t stride) {
+            uint64_t tally = 0, overs = 0;
+            for (size_t j = 0; j < count; ++j) {
+                tally += v[j * stride].count;
+                overs += v[j * stride].overs;
             }
-            if (count > 0xffffffffull || overs > 0xffffffffull) return fail(SGZ_EINVAL, "sgz_truepeak_fold: a folded column counts more than 2^32 - 1");
-        }
-    for (uint64_t b = 0; b < cols; ++b)
-        for (uint32_t c = 0; c < channels; ++c) {
+            return tally <= 0xffffffffull && overs <= 0xffffffffull;
+        },
+        [](const sgz_truepeak_record *v, size_t count, size_t stride) {
             sgz_truepeak_record r{0, 0, 0};
-            for (uint64_t j = bound(b); j < bound(b + 1); ++j) {
-                const sgz_truepeak_record &v = in[j * channels + c];
-                r.peak = std::max(r.peak, v.peak);
-                r.count += v.count;
-                r.overs += v.overs;
+            for (size_t j = 0; j < count; ++j) {
+                r.peak = std::max(r.peak, v[j * stride].peak);
+                r.count += v[j * stride].count;
+                r.overs += v[j * stride].overs;
             }
-            out[b * channels + c] = r;
-        }
-    return SGZ_OK;
+            return r;
+        });
 }
 
 sgz_status sgz_truepeak_readout(const sgz_truepeak_record *rec, double *peak, double *dbtp)

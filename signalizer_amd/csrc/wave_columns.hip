@@ -1,17 +1,16 @@
 // wave_columns.hip -- the waveform lane's reduction: a minimum and a maximum per column of m samples and channel of a linear planar stream,
 // with a carried open column (sgz.h, "The waveform lane").  gfx950 only.  The reference has no counterpart: it draws a live ring, never a file.
+// What the column lanes share -- the shape of a call, the column, tile and slice bounds, the aligned split of a row, the stage call's front --
+// is column_lanes.hpp; this file is what the lane does with a sample.
 //   Wv[c][d] = (lo, hi): the least and the greatest of the column's non-NaN samples under the overview's total order (order_key.hpp) --
 //   each the sample's own bits; a column of NaNs alone gives 0x7FC00000 twice.  Least and greatest are associative and commutative, so
 //   any cut of the stream (calls with a carry) or of a column (lanes, slices) gives the same bits.
-// The kernels keep KEY PAIRS (minimum key, maximum key), identities (0xFFFFFFFF, 0).  Column c of a call covers its samples
-// [c m - held, (c + 1) m - held) clipped to [0, n): column 0 is the rest of the carried column (held > 0), the last one may stay open.
-//   m <= kWvSwitch (1024)   waveTileKernel: one workgroup per (channel, tile); a tile is kWvTile / m whole columns of the call (column 0
-//                           counts as one, whatever is left of it), so no column straddles two workgroups.  The tile goes to LDS once:
-//                           16-byte loads between the first and the last 16-byte boundary, up to three scalar loads on either side (the
-//                           base is only 4-byte aligned); LDS keeps the tile at the same offset within 16 bytes, four words of padding
-//                           behind every 64.  Then groups of G lanes (a power of two near m / 16: a lane per column up to m = 16, a wave
-//                           per column from m = 513) take a column each: the lanes stride the column in LDS, log2 G cross-lane steps,
-//                           the group's first lane folds the carry (column 0) and stores the pair -- or the carry (the open column).
+// The kernels keep KEY PAIRS (minimum key, maximum key), identities (0xFFFFFFFF, 0).
+//   m <= kWvSwitch (1024)   waveTileKernel: one workgroup per (channel, tile), so no column straddles two workgroups.  The tile goes to LDS
+//                           once, raw bits, at the same offset within 16 bytes as in memory, four words of padding behind every 64.  Then
+//                           groups of G lanes (a power of two near m / 16: a lane per column up to m = 16, a wave per column from m = 513)
+//                           take a column each: the lanes stride the column in LDS, log2 G cross-lane steps, the group's first lane folds
+//                           the carry (column 0) and stores the pair -- or the carry (the open column).
 //                           (Measured, DESIGN.md section 8: with G near m / 4 the cross-lane steps, which go through the LDS pipe, cost
 //                           a third of the rate at m = 64; a wave per column straight from memory at m >= 256 was slower than the tile.)
 //   else, or slices >= 2    waveSliceKernel: workgroup (column, channel, slice) scans its part of the column from memory (16-byte loads
@@ -23,9 +22,8 @@
 
 #include <algorithm>
 
-#include "runtime.hpp"
+#include "column_lanes.hpp"
 #include "order_key.hpp"
-#include "scope_ring.hpp"      // StreamScratch
 
 using namespace sgz;
 
@@ -34,7 +32,7 @@ namespace {
 constexpr int kWvThreads = 256;
 constexpr uint32_t kWvTile = 4096;              // samples of a tile (16 KiB of LDS)
 constexpr uint32_t kWvSwitch = 1024;            // the switch-over: columns longer than this take the sliced form
-constexpr uint32_t kWvMaxSlices = 64, kWvMaxChannels = 64;
+constexpr uint32_t kWvMaxChannels = 64;
 constexpr int kWvUnroll = 4;                    // 16-byte loads a lane issues before the first compare
 constexpr uint32_t kWvTileWords = kWvTile + 4 + 4 * ((kWvTile + 4) / 64 + 1);      // the lead, and four words of padding per 64 (tileWord)
 static_assert(kWvTile == 4u * kWvThreads * kWvUnroll, "a lane moves kWvUnroll 16-byte chunks of a tile");
@@ -70,15 +68,6 @@ struct KeyPair {
 };
 __device__ __forceinline__ KeyPair noKeys() { return KeyPair{0xffffffffu, 0u}; }
 
-// samples [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnSamples(const WaveParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.m) - long(prm.held);
-    b = a + long(prm.m);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
-}
-
 // what a (column, channel) does with its keys: the carry into column 0, then the pair to the output (a closed column) or to the carry
 __device__ __forceinline__ void emitColumn(const WaveParams &prm, long col, uint32_t d, KeyPair k)
 {
@@ -91,38 +80,22 @@ __device__ __forceinline__ void emitColumn(const WaveParams &prm, long col, uint
     else prm.carryOut[d] = v;
 }
 
-// where the 16-byte part of `count` floats at g begins and ends: [0, head) and [tail, count) are scalar, `vecs` chunks lie between
-__device__ __forceinline__ void splitAligned(const float *g, size_t count, uint32_t &head, size_t &vecs, size_t &tail)
-{
-    const uint32_t lead = uint32_t(reinterpret_cast<uintptr_t>(g) >> 2) & 3u;
-    const uint32_t toBoundary = (4u - lead) & 3u;
-    head = count < toBoundary ? uint32_t(count) : toBoundary;
-    vecs = (count - head) >> 2;
-    tail = head + 4 * vecs;
-}
-
-// where word i of a tile lies in LDS: four words of padding behind every 64, so that columns a multiple of 32 words apart start on different
-// banks (16-byte chunks stay whole and aligned)
-__device__ __forceinline__ uint32_t tileWord(uint32_t i) { return i + ((i >> 6) << 2); }
-
 // the tile through LDS, then groups of prm.group lanes per column
 __global__ void __launch_bounds__(kWvThreads)
 waveTileKernel(const WaveParams prm)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tile[kWvTileWords];
     const uint32_t tid = threadIdx.x, d = blockIdx.y;
-    const long c0 = long(blockIdx.x) * long(prm.perTile);
-    const long c1 = c0 + long(prm.perTile) < prm.columns ? c0 + long(prm.perTile) : prm.columns;
-    long a = c0 * long(prm.m) - long(prm.held), b = c1 * long(prm.m) - long(prm.held);
-    a = a < 0 ? 0 : a;
-    b = b > prm.n ? prm.n : b;
+    TileBounds t;
+    tileBounds(prm, t);
+    const long c0 = t.c0, c1 = t.c1, a = t.a, b = t.b;
     const uint32_t count = uint32_t(b - a);                                 // <= perTile * m <= kWvTile
     const float *g = prm.planar + size_t(d) * prm.stride + size_t(a);
     // the tile sits in LDS `lead` words in: 16-byte chunks of memory are 16-byte chunks of LDS
     const uint32_t lead = uint32_t(reinterpret_cast<uintptr_t>(g) >> 2) & 3u;
     uint32_t head;
     size_t vecs, tail;
-    splitAligned(g, count, head, vecs, tail);
+    splitAligned(g, size_t(count), head, vecs, tail);
     if (tid < head) tile[tileWord(lead + tid)] = __float_as_uint(g[tid]);
     if (tid < count - uint32_t(tail)) tile[tileWord(lead + uint32_t(tail) + tid)] = __float_as_uint(g[tail + tid]);
     const uint4 *gv = reinterpret_cast<const uint4 *>(g + head);
@@ -208,10 +181,9 @@ waveSliceKernel(const WaveParams prm)
     __shared__ uint2 lds[kWvThreads / 64];
     const long col = long(blockIdx.x);
     const uint32_t d = blockIdx.y, s = blockIdx.z;
-    long a, b;
+    long a, b, sa, sb;
     columnSamples(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(s) * per < b ? a + long(s) * per : b, sb = sa + per < b ? sa + per : b;
+    sliceSamples(prm, a, b, s, sa, sb);
     const KeyPair k = scanSamples(prm.planar + size_t(d) * prm.stride, sa, sb, lds);
     if (threadIdx.x == 0) prm.partial[(size_t(s) * size_t(prm.columns) + size_t(col)) * prm.channels + d] = make_uint2(k.lo, k.hi);
 }
@@ -234,37 +206,16 @@ waveEmitKernel(const WaveParams prm)
     emitColumn(prm, long(at / prm.channels), uint32_t(at % prm.channels), k);
 }
 
-uint32_t pow2AtLeast(uint32_t v)
-{
-    uint32_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 }  // namespace
 
 namespace sgz {
 
-// The shape of a call whose arguments passed sgz_stage_wave_columns' checks.  slices: 0 = the tile form, else the sliced form with that many
-// (the caller's count, or for m > kWvSwitch the overview's rule: the smallest count <= min(64, m, n) with columns x channels x slices >= 2
-// workgroups per CU); scratchBytes: the partial pairs of the sliced form.  launch: false -- nothing arrives and nothing is flushed.
-WaveColumnsShape waveColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
+ColumnsShape waveColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
 {
-    WaveColumnsShape sh{};
-    const uint64_t t = uint64_t(held) + nsamples;
-    sh.closed = t / m + ((flush && t % m) ? 1u : 0u);
-    sh.open = !flush && t % m != 0;
-    sh.columns = sh.closed + (sh.open ? 1u : 0u);
-    sh.launch = sh.columns != 0 && !(nsamples == 0 && !(flush && held));
-    if (!sh.launch || nsamples == 0) return sh;
-    if (slices >= 2 || m > kWvSwitch) sh.slices = slices ? slices : overviewAutoSlices(long(sh.columns), channels, m, nsamples, numCUs());
-    sh.scratchBytes = size_t(sh.slices) * size_t(sh.columns) * channels * sizeof(uint2);
-    return sh;
+    return columnsShape(channels, nsamples, m, held, flush, slices, kWvSwitch, sizeof(uint2), 0);
 }
 
-// sgz_stage_wave_columns behind its argument checks, with the carry in two places: carryIn is read by column 0 (held > 0), carryOut written by
-// the open column -- the same memory only where the call has one column.  scratch: sh.scratchBytes bytes.
-sgz_status runWaveColumns(const WaveColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples, uint32_t m,
+sgz_status runWaveColumns(const ColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples, uint32_t m,
                           uint32_t held, const float *carryIn, float *carryOut, float *d_wave, void *scratch, hipStream_t stream)
 {
     if (!sh.launch) return SGZ_OK;
@@ -279,17 +230,17 @@ sgz_status runWaveColumns(const WaveColumnsShape &sh, const float *d_planar, siz
         prm.perTile = kWvTile / m;
         prm.group = pow2AtLeast((m + 15u) / 16u);                 // (1 .. 64: sixteen samples a lane, or as near as a power of two gets)
         const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (tiles > 0x7fffffffull) return fail(SGZ_EINVAL, "wave columns: too many columns for one launch");
+        if (sgz_status st = fitsOneLaunch(tiles, "wave", "columns"); st != SGZ_OK) return st;
         hipLaunchKernelGGL(waveTileKernel, dim3(unsigned(tiles), channels), dim3(kWvThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sh.columns > 0x7fffffffull || (cells + kWvThreads - 1) / kWvThreads > 0x7fffffffull) return fail(SGZ_EINVAL, "wave columns: too many columns for one launch");
+    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kWvThreads)), "wave", "columns"); st != SGZ_OK) return st;
     if (nsamples != 0) {
         hipLaunchKernelGGL(waveSliceKernel, dim3(unsigned(sh.columns), channels, sh.slices), dim3(kWvThreads), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(waveEmitKernel, dim3(unsigned((cells + kWvThreads - 1) / kWvThreads)), dim3(kWvThreads), 0, stream, prm);
+    hipLaunchKernelGGL(waveEmitKernel, dim3(unsigned(emitBlocks(cells, kWvThreads))), dim3(kWvThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     return SGZ_OK;
 }
@@ -307,29 +258,16 @@ void sgz_wave_columns_limits(uint32_t *switch_over, uint32_t *tile_samples)
 sgz_status sgz_stage_wave_columns(const float *d_planar, size_t channel_stride, uint32_t channels, size_t nsamples, uint32_t m, uint32_t held,
                                   int flush, uint32_t slices, float *d_carry, float *d_wave, void *stream)
 {
-    if (!d_planar) return fail(SGZ_EINVAL, "sgz_stage_wave_columns: null d_planar");
-    if (channels == 0 || channels > kWvMaxChannels) return fail(SGZ_EINVAL, "sgz_stage_wave_columns: 1 .. 64 channels");
-    if (m == 0) return fail(SGZ_EINVAL, "sgz_stage_wave_columns: m >= 1 samples per column");
-    if (held >= m) return fail(SGZ_EINVAL, "sgz_stage_wave_columns: held < m");
-    if (channel_stride < nsamples || nsamples > (size_t(1) << 62)) return fail(SGZ_EINVAL, "sgz_stage_wave_columns: channel_stride < nsamples");
-    if (slices > kWvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_wave_columns: slices 0 (automatic) or 1 .. 64");
-    if ((reinterpret_cast<uintptr_t>(d_planar) & 3u) || (reinterpret_cast<uintptr_t>(d_carry) & 7u) || (reinterpret_cast<uintptr_t>(d_wave) & 7u))
-        return fail(SGZ_EINVAL, "sgz_stage_wave_columns: d_planar aligned to 4 bytes, d_carry and d_wave to 8");
-    const WaveColumnsShape sh = waveColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (!d_carry && (held || sh.open)) return fail(SGZ_EINVAL, "sgz_stage_wave_columns: d_carry is read (held > 0) or written (samples stay open)");
-    if (!d_wave && sh.closed) return fail(SGZ_EINVAL, "sgz_stage_wave_columns: d_wave is written (a column closes)");
+    const StageFront front{"sgz_stage_wave_columns", "channels", kWvMaxChannels, "d_wave", 8, false, 62};
+    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, channels, nsamples, m, held, 0, 0, slices, d_carry, d_wave); st != SGZ_OK) return st;
+    const ColumnsShape sh = waveColumnsShape(channels, nsamples, m, held, flush, slices);
+    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, 0, d_carry, d_wave); st != SGZ_OK) return st;
     if (!sh.launch) return SGZ_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StreamScratch scratch(s), snapshot(s);
-    const float *carryIn = d_carry;
-    if (held && sh.open && sh.columns > 1) {
-        // column 0 reads the carry while the open column writes it, in another workgroup: column 0 reads a snapshot
-        SGZ_HIP(snapshot.get(size_t(channels) * sizeof(float2)));
-        SGZ_HIP(hipMemcpyAsync(snapshot.p, d_carry, size_t(channels) * sizeof(float2), hipMemcpyDeviceToDevice, s));
-        carryIn = static_cast<const float *>(snapshot.p);
-    }
-    if (sh.scratchBytes) SGZ_HIP(scratch.get(sh.scratchBytes));
-    return runWaveColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, carryIn, d_carry, d_wave, scratch.p, s);
+    StageScratch mem(s);
+    const void *carryIn = nullptr;
+    if (sgz_status st = mem.get(front, sh, nsamples, held, 0, d_carry, size_t(channels) * sizeof(float2), &carryIn); st != SGZ_OK) return st;
+    return runWaveColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, static_cast<const float *>(carryIn), d_carry, d_wave, mem.scratch.p, s);
 }
 
 }  // extern "C"

@@ -297,7 +297,9 @@ def test_loudness_kernels_need_no_scratch_and_do_not_contract():
     lib = os.path.join(ROOT, "signalizer_amd", "libsgz.so")
     if not (os.path.exists(lib) and os.path.exists(f"{cr.LLVM}/llvm-readelf") and os.path.exists(f"{cr.LLVM}/llvm-objcopy")):
         pytest.skip("library or llvm tools not present")
-    names = ("loudnessRunKernel", "loudnessHistoryKernel", "loudnessSumTileKernel", "loudnessSumSliceKernel", "loudnessEmitKernel")
+    # (the history and sum kernels are column_lanes.hpp's templates, instantiated on this lane's kernel arguments)
+    mine = "<(anonymous namespace)::LoudnessParams"
+    names = ("loudnessRunKernel", "historyKernel" + mine, "sumTileKernel" + mine, "sumSliceKernel" + mine, "sumEmitKernel" + mine)
     rows = [r for r in cr.kernels(lib) if any(k in r["demangled"] for k in names)]
     assert len(rows) == 5, [r["demangled"] for r in rows]
     bad = [(r["demangled"], r.get("vgpr_spill_count"), r.get("sgpr_spill_count"), r.get("private_segment_fixed_size")) for r in rows
