@@ -370,10 +370,15 @@ sgz_status runStft(Plan &p, const float *d_planar, size_t chStride, long frames,
         // image-only renders (spectrum_real.hip nyquistUnit): side 0's channel workgroups and Nyquist workgroups of F frames each, F such
         // that both together fill one round of workgroup slots where the channel workgroups leave room (SGZ_OPT_IMAGE_ONLY_SPLIT >= 2: F itself)
         // (never more than the frame count: the kernel divides by it)
+        // The automatic F (profiles/r09a split_sweep.txt, since the Nyquist workgroups share rows between their frames): a Nyquist workgroup is a
+        // serial chain of ~3.5 us per frame whatever it fetches, so the smallest F that fits the round wins while it is at most 6 (348
+        // frames: 3; 400: 4; 420: 5); where the round would take a longer one, workgroups of three frames in a second generation do
+        // better than it by 4 ... 10 us (450 frames: 31.0 us per step against 34.9 at F = 8; 511: 32.7 against 42.1).
         if (imageOnly && rp.lateInNext && p.optImageOnlySplit && p.realSplit && p.cfg.channel_mode == SGZ_CH_SEPARATE && p.N == 32768 &&
             rp.winPhase && p.C == 1) {
             const long room = long(rp.roundSize) - tasks;
-            const long want = p.optImageOnlySplit >= 2 ? long(p.optImageOnlySplit) : room > 0 ? std::min<long>(8, std::max<long>(1, (tasks + room - 1) / room)) : 4;
+            const long fit = room > 0 ? std::max<long>(1, (tasks + room - 1) / room) : 0;
+            const long want = p.optImageOnlySplit >= 2 ? long(p.optImageOnlySplit) : room <= 0 ? 4 : fit <= 6 ? fit : 3;
             rp.nyFrames = uint32_t(std::min<long>(want, frames));
         }
         p.lastNyFrames = rp.nyFrames;

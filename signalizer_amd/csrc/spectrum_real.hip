@@ -190,7 +190,8 @@ __device__ __forceinline__ void realMapSettle(const P &prm, float *lds, const in
     if (p != 0u) { if (p == 1u) __builtin_amdgcn_s_setprio(1); else if (p == 2u) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
 }
 
-template <int LR1, bool PRIO>
+constexpr uint32_t kNyHopRows = 4;      // the hop, in rows of 2048 samples, at which the Nyquist role shares rows between its frames
+template <int LR1, bool PRIO, bool SHARE>
 __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, const uint32_t light, const int tid)
 {
     constexpr int LR = 5, R = 32, R1 = 1 << LR1, RR = R * R;
@@ -213,22 +214,16 @@ __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, c
     const float4 ph[2] = {ldg(prm.winPhase, lane16 * 2u), ldg(prm.winPhase + 1, lane16 * 2u)};     // columns 2 tid, 2 tid + 1
     const v2 p0 = v2{prm.winP0, prm.winP0};
     v2 *lds2 = reinterpret_cast<v2 *>(lds);                                     // [1024] column sums, then [32] pass-2 sums
-    for (uint32_t f = f0; f < f1; ++f) {
-        const float *X = X0 + size_t(f) * prm.hop;
-        // one column at a time (16 registers of samples, not the channel workgroup's 32: the tail of this role shares the kernel's
-        // register allocation with the channel workgroups, whose form is at the 128-register limit)
+    // one column's rows (a fresh copy: the window multiplies in place) -> its pass-1 sum in LDS
+    auto columnSum = [&](v2 (&c)[R1], const int u) {
+        const v2 pc = v2{ph[u].x, ph[u].y}, ps = v2{ph[u].z, ph[u].w};
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            v2 c[R1];
-#pragma unroll
-            for (int j = 0; j < R1; ++j) c[j] = ldgPinned<v2>(X, uint32_t(RR * j) * 8u + 8u * u, lane16);
-            const v2 pc = v2{ph[u].x, ph[u].y}, ps = v2{ph[u].z, ph[u].w};
-#pragma unroll
-            for (int j = 0; j < R1 / 2; ++j) windowPairCos(c[j], c[j + R1 / 2], j * (32 / R1), pc, ps, p0);
-            ditPacked<LR1, 0>(c);                                             // pass 1 (pass1Columns): Z1[column][q1 = 0] at register 0
-            lds2[2 * tid + u] = c[0];
-        }
-        __syncthreads();
+        for (int j = 0; j < R1 / 2; ++j) windowPairCos(c[j], c[j + R1 / 2], j * (32 / R1), pc, ps, p0);
+        ditPacked<LR1, 0>(c);                                                 // pass 1 (pass1Columns): Z1[column][q1 = 0] at register 0
+        lds2[2 * tid + u] = c[0];
+    };
+    // what follows a frame's 1024 column sums, each behind a barrier: 32 lanes' and then one thread's 32-point tree
+    auto tree2 = [&]() {
         if (tid < R) {                                                         // pass 2, c_lo = tid: c_hi = 0 .. 31 in natural order
             v2 s[R];
 #pragma unroll
@@ -236,7 +231,8 @@ __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, c
             ditPacked<LR, 0>(s);
             lds2[RR + tid] = s[0];
         }
-        __syncthreads();
+    };
+    auto tree3 = [&](const uint32_t f) {
         if (tid == 0) {                                                        // pass 3, q2 = 0: register r is c_lo = r
             v2 s[R];
 #pragma unroll
@@ -252,6 +248,80 @@ __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, c
             ditPacked<LR, 0, R, 2>(s);
             prm.ny[((size_t(f) * prm.C + pair) << 1) | 1u] = 2.f * (s[0].x - s[0].y);   // as the channel workgroup stores it (the transform runs on x w / 2)
         }
+    };
+    // SHARED ROWS.  Frame f + 1's row j is frame f's row j + HOPROWS where the hop is HOPROWS whole rows of 2 R^2 samples (cfg2: 8192 = 4
+    // rows), so the F frames of a workgroup read 16 + 4 (F - 1) distinct rows, not 16 F: the thread keeps its column pair's sixteen RAW
+    // rows (one 16-byte request per row, the channel workgroups' form) as a window that slides by HOPROWS rows per frame, and windows a
+    // fresh copy of one column at a time.  The next frame's new rows are requested in front of this frame's barriers and trees and
+    // arrive during them.  Only the loads differ from the loop below: the copy is the same sixteen values, and everything behind it is
+    // the same expressions in the same order.  Any other hop, and a workgroup of one frame, run the loop below.  (A loop of its own: in
+    // one loop with the other form the 64 raw registers were live through that form's 64 registers of requests, and spilled.)
+    // SHARE: only in the kernel instantiation that launchStftReal picks for such launches.  The plain instantiation's channel role sits at
+    // exactly 128 registers, and with this form beside it -- in every schedule of this role that was tried -- the compiler put that
+    // role's pass-2 table piece into scratch, with a full wait behind the request.
+    constexpr uint32_t HOPROWS = kNyHopRows;
+    if (SHARE && f1 - f0 > 1u && prm.hop == HOPROWS * 2u * uint32_t(RR)) {
+        typedef float v4 __attribute__((ext_vector_type(4)));
+        v4 raw[R1];                                                             // rows of the current frame: (column 2 tid, column 2 tid + 1)
+        {
+            const float *X = X0 + size_t(f0) * prm.hop;
+#pragma unroll
+            for (int j = 0; j < R1; ++j) raw[j] = ldgPinned<v4>(X, uint32_t(RR * j) * 8u, lane16);
+        }
+        for (uint32_t f = f0; f < f1; ++f) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                v2 c[R1];
+#pragma unroll
+                for (int j = 0; j < R1; ++j) c[j] = u ? v2{raw[j].z, raw[j].w} : v2{raw[j].x, raw[j].y};
+                columnSum(c, u);
+            }
+            if (f + 1u < f1) {                                                 // (frame f + 1 <= frames - 1: its rows are inside the signal)
+                const float *X = X0 + size_t(f + 1u) * prm.hop;
+#pragma unroll
+                for (int j = 0; j < R1 - int(HOPROWS); ++j) raw[j] = raw[j + int(HOPROWS)];
+#pragma unroll
+                for (int j = R1 - int(HOPROWS); j < R1; ++j) raw[j] = ldgPinned<v4>(X, uint32_t(RR * j) * 8u, lane16);
+            }
+            // The trees are wave 0's alone and want 64 registers and more beside the 64 raw ones: wave 0 parks its PARK carried rows (the
+            // requests above stay in flight) in LDS behind the sums for the length of the trees -- 12 KB of the ~70 the role never
+            // uses -- where the compiler otherwise spilled 16 registers of EVERY wave to scratch, through the CU's fetch path.
+            constexpr int PARK = R1 - int(HOPROWS);
+            v4 *park = reinterpret_cast<v4 *>(lds + 4 * RR) + (tid & 63);      // (byte 16384: behind the [1024 + 32] sums)
+            // (One scalar branch around both of wave 0's barriers: the other waves meet the same two barriers on their side.  Behind a
+            // vector condition, or in two branches with the barrier between them, the parked registers stay live.)
+            if (__builtin_amdgcn_readfirstlane(tid) < 64) {
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < PARK; ++j) park[64 * j] = raw[j];
+                tree2();
+                __syncthreads();
+                tree3(f);
+#pragma unroll
+                for (int j = 0; j < PARK; ++j) raw[j] = park[64 * j];
+            } else {
+                __syncthreads();
+                __syncthreads();
+            }
+        }
+        RTRACE(1);
+        return;
+    }
+    for (uint32_t f = f0; f < f1; ++f) {
+        const float *X = X0 + size_t(f) * prm.hop;
+        // one column at a time (16 registers of samples, not the channel workgroup's 32: the tail of this role shares the kernel's
+        // register allocation with the channel workgroups, whose form is at the 128-register limit)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            v2 c[R1];
+#pragma unroll
+            for (int j = 0; j < R1; ++j) c[j] = ldgPinned<v2>(X, uint32_t(RR * j) * 8u + 8u * u, lane16);
+            columnSum(c, u);
+        }
+        __syncthreads();
+        tree2();
+        __syncthreads();
+        tree3(f);
     }
     RTRACE(1);
 }
@@ -261,8 +331,8 @@ __device__ __forceinline__ void nyquistUnit(const RealParams &prm, float *lds, c
 // csf[N/2] = X[N/2] / 2 (:547-552; the latter stays signed: the reference leaves it complex, and X[N/2] of a real signal is real).
 // MIX: 0 Separate (two channel workgroups), 1 mono Left / Right, 2 MidSide (two workgroups on mid and side), 3 mono Merge / Side,
 // 4 Separate for an image-only render (side 0's channel workgroups, then the Nyquist workgroups: nyquistUnit above)
-// PRIO (MIX = 4): the instantiation that carries the one-round shape's wave priorities (RealParams::prio*), launched only where runStft
-// hands some out.  Every other image-only launch runs the plain one, whose code is what it was without them: the two scalar branches
+// PRIO (MIX = 4): the instantiation that carries the one-round shape's wave priorities (RealParams::prio*) and the Nyquist role's shared
+// rows (nyquistUnit), launched where runStft hands priorities out or the Nyquist workgroups can share rows (launchStftReal).  Every other image-only launch runs the plain one, whose code is what it was without them: the two scalar branches
 // alone changed the compiler's schedule (122 registers for 128) and cost 0.2 ... 0.3 us per launch where no priority was set.
 template <int LR1, bool WCOS, int MIX = 0, bool PRIO = false>
 __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealParams launchPrm)
@@ -290,7 +360,7 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     const uint32_t heavyUnits = SIDE0 ? uint32_t(launchPrm.frames) * launchPrm.C : gridDim.x;
     if constexpr (SIDE0) {
         // (thread index opaque: nothing the role derives from it is shared with -- hoisted into -- the channel workgroups' code)
-        if (blockIdx.x >= heavyUnits) { nyquistUnit<LR1, PRIO>(launchPrm, lds, blockIdx.x - heavyUnits, opaque(tid0)); return; }
+        if (blockIdx.x >= heavyUnits) { nyquistUnit<LR1, PRIO, PRIO>(launchPrm, lds, blockIdx.x - heavyUnits, opaque(tid0)); return; }
     }
     const uint32_t totalUnits = WALK ? uint32_t(launchPrm.frames) * launchPrm.C * 2u : heavyUnits;
     uint32_t walkIndex = blockIdx.x;
@@ -457,7 +527,7 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     const int ix = half ? R - 1 - l : l;                // c_lo in pass 2, q2 in pass 3
     const uint32_t lane8 = uint32_t(tid) * (PAIRED ? 16u : 8u);
     [[maybe_unused]] const long unit = MONO ? long(uid.task) : long(uid.self);   // (debug clocks)
-    const int side = uid.side, pair = uid.pair;
+    const int side = SIDE0 ? 0 : uid.side, pair = uid.pair;       // (SIDE0: a compile-time 0)
     const long task = uid.task, frame = uid.frame, self = uid.self;
 
     // map tables of this side (chunk_map.hpp)
@@ -1092,7 +1162,9 @@ hipError_t launchStftReal(const RealParams &prm, uint32_t N, hipStream_t stream)
         return hipGetLastError();
     }
 #ifdef SGZ_IMAGE_PRIO
-    if (side0 && (prm.prioFirst | prm.prioMate | prm.prioNy)) e = go(&stftRealKernel<4, true, 4, true>, 28, 512, 80 * 1024);
+    // (... or its Nyquist workgroups have rows to share: several frames each, a hop of kNyHopRows whole rows)
+    if (side0 && ((prm.prioFirst | prm.prioMate | prm.prioNy) || (prm.nyFrames > 1u && prm.frames > 1 && prm.hop == kNyHopRows * 2048u)))
+        e = go(&stftRealKernel<4, true, 4, true>, 28, 512, 80 * 1024);
     else
 #endif
     if (side0) e = go(&stftRealKernel<4, true, 4>, 27, 512, 80 * 1024);
