@@ -74,6 +74,10 @@ extern "C" {
  *  on the PCM stream, sgz_pcm_stream_feed_overview_stats and sgz_spectrogram_overview_stats_pcm.  No existing entry point or struct changed
  *  and the suite pins 5; the one new refusal on an existing call, sgz_pcm_stream_feed_overview while a stats column is open, cannot be
  *  reached without the new calls.  A binding that needs them looks the symbols up.)
+ * (5, later: the histogram lane -- SGZ_HIST_BUCKETS, sgz_hist_record, sgz_hist_reading, sgz_stage_hist_columns, sgz_hist_columns_limits, the
+ *  host helpers sgz_hist_edges, sgz_hist_fold, sgz_hist_percentile and sgz_hist_readout and, on the PCM stream, sgz_pcm_stream_set_hist,
+ *  sgz_pcm_stream_hist_for, sgz_pcm_stream_hist_state, sgz_pcm_stream_flush_hist.  No existing entry point or struct changed and the suite
+ *  pins 5; a stream that was never armed enqueues what it did before.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -1253,6 +1257,111 @@ sgz_status sgz_pcm_stream_set_band(sgz_pcm_stream *s, const sgz_band_filter *fil
 uint64_t   sgz_pcm_stream_band_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
 sgz_status sgz_pcm_stream_band_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
 sgz_status sgz_pcm_stream_flush_band(sgz_pcm_stream *s);
+
+/* The histogram lane: how a column's samples are DISTRIBUTED over level, per screen column and channel of a file's samples -- the other
+ * lanes keep extremes and sums.  It gives the percentiles of |x| (the median, the 10 % floor, the 95 % ceiling: the noise floor of a take,
+ * the dynamic range of a passage) exactly at the resolution of fixed integer buckets, and a bit meter: which bits of the word a file uses
+ * (a 16-bit file padded to 24, a stuck bit, a channel with only positive samples, true digital silence).  The reference has no
+ * counterpart; nothing of it is reused or contradicted.
+ * Definition (exact, no tolerance).  Samples, columns and counts are the level lane's: x[d][i] are the stream's converted fp32 samples of
+ * channel d -- the lane is per channel --, column c covers samples c m <= i < min((c + 1) m, S), only a flushed last column may be
+ * partial, and the counts are sgz_overview_step's with samples in the place of frames.  The quantiser is the level lane's, unchanged:
+ *     v = (int32) clamp(rintf(x * 2^23), -2^26, +2^26)
+ * (the identity on 8-, 16- and 24-bit PCM).  A NaN takes no part and is counted in `skipped`.
+ * Bucket of a sample: a = |v|, 0 <= a <= 2^26; SGZ_HIST_BUCKETS = 106.  a = 0 is bucket 0.  Otherwise e = floor(log2 a) = 0 .. 26,
+ * s = (a >> (e - 2)) & 3 for e >= 2 and (a << (2 - e)) & 3 for e < 2, and the bucket is 1 + 4 e + s: the integers with (4 + s) 2^(e-2) <=
+ * a < (5 + s) 2^(e-2), an octave in four linear parts, 1.2 to 1.9 dB wide.  Full scale, 2^23, is the lower edge of bucket 93; 2^26, the
+ * saturated value, alone is bucket 105; buckets 2, 3, 4, 6 and 8 hold no integer and stay 0; the reachable buckets tile 1 .. 2^26 without
+ * gaps.  Integer arithmetic throughout: a conversion of a to float rounds above 2^24 and misfiles the upper edges there.
+ * One sgz_hist_record per (column, channel), layout [columns][channels], 448 bytes = 112 little-endian 32-bit words; arrays of it on the
+ * DEVICE are aligned to 16 bytes:
+ *     bucket[b]  samples of bucket b                                      fold: add
+ *     count      the samples that are no NaN (= the sum of bucket[])            add
+ *     skipped    the NaNs                                                       add
+ *     negative   samples with v < 0                                             add
+ *     peak       max a, 0 when count = 0                                        max
+ *     bits_or    OR of (uint32_t) v over the samples counted, 0 when none       or
+ *     bits_and   AND of the same, 0xffffffff when none                          and
+ * Every fold is associative and commutative, so any cut of the stream (feeds, pieces, calls with a carry) or of a column (lanes, waves,
+ * slices) gives the same bytes, and a coarser column is the fold of the finer ones (sgz_hist_fold).  The identity is the record of zeros
+ * with bits_and = 0xffffffff -- NOT all-zero: it is what a column of NaNs alone has beside `skipped`.
+ *  sgz_stage_hist_columns  DEVICE pointers; sgz_stage_level_columns' arguments, semantics, carry rule and refusals to the letter, with
+ *                      1 .. 64 channels in the place of pairs and sgz_hist_record in the place of sgz_level_record: d_planar
+ *                      [channels][channel_stride] (any 4-byte-aligned address), held, the carry d_carry [channels] (the open column
+ *                      alone; read iff held > 0, written iff samples stay open), d_hist [columns][channels], flush, nsamples == 0 with
+ *                      held > 0 and flush: one column from the carry alone.  m up to the switch-over (1024; sgz_hist_columns_limits)
+ *                      runs one workgroup per (channel, tile of min(4096 / m, 64) whole columns), a table per column in LDS; longer
+ *                      columns are reduced in slices per column into scratch and folded by a second launch.  slices: 0 = the
+ *                      library's choice, 1 .. 64 forced -- 2 and more take the sliced form whatever m is, 1 takes the form m implies --
+ *                      identical bytes.  Only the documented bytes are written.  Asynchronous on `stream`, nothing is waited for;
+ *                      scratch is allocated and freed in stream order.  SGZ_EINVAL, nothing launched or written: a null d_planar,
+ *                      channels == 0 or > 64, m == 0, held >= m, channel_stride < nsamples, slices > 64, a needed d_carry or d_hist
+ *                      that is NULL, d_planar not aligned to 4 bytes, d_carry or d_hist not aligned to 16.  nsamples == 0 with nothing
+ *                      to flush: SGZ_OK, nothing launched.  m = 1 is legal: it writes a 448-byte record per sample.
+ *  sgz_hist_columns_limits  the switch-over and the tile's samples (either result may be NULL).
+ * The lane inside the sgz_pcm_stream handle -- above, "interleaved PCM in": the level lane's contract word for word, per channel, with
+ * sgz_hist_record in the place of sgz_level_record and one exception.  While armed, every feed of either kind also reduces the new samples
+ * of each piece on the compute stream behind the conversion (and behind the other lanes' launches) and reads the records that closed back
+ * on the read-back stream into hist_out at a cursor.  The records of all feeds and the final flush, concatenated, are the lane of the
+ * stream's converted floats byte for byte, however it is cut into feeds and pieces and whichever kind the feeds are; the image, lines,
+ * overview, peaks and every other lane's records of an armed stream are those of an unarmed one byte for byte.  The lane's m is its own.
+ * The exception: the stream refuses 0 < m < 128 with SGZ_EINVAL -- a 448-byte record per channel for fewer than 112 samples would read
+ * back more than the samples it describes (the stage call takes every m >= 1).
+ *  sgz_pcm_stream_set_hist    between feeds.  m >= 128 arms: hist_out HOST sgz_hist_record [capacity_columns][channels] (aligned to 4
+ *                      bytes; pinned memory is written in place, pageable memory through a pinned twin per slot), the cursor restarts
+ *                      at 0.  The same m with another buffer keeps the open column: how a caller with a small buffer drains.  m == 0
+ *                      disarms and drops the open column.  SGZ_EINVAL: a null stream, 0 < m < 128, a null hist_out with
+ *                      capacity_columns > 0, a hist_out that is not aligned, another m while samples are open.
+ *  sgz_pcm_stream_hist_for    columns the next feed of nsamples closes (flush != 0: that feed followed by sgz_pcm_stream_flush_hist);
+ *                      0 when disarmed.
+ *  sgz_pcm_stream_hist_state  columns written since the lane was armed (the cursor) and the open column's samples; either may be NULL.
+ *  sgz_pcm_stream_flush_hist  closes the open column: one launch on the carry, one column read back, waits.  Nothing open: SGZ_OK,
+ *                      nothing done.  SGZ_EINVAL: disarmed, no column left in the buffer.
+ * A feed that would close more columns than the buffer has left is refused with SGZ_EINVAL before anything is consumed.  reset drops the
+ * open column and restarts the cursor.  Memory per slot as the level lane's, 448 bytes a record and channel.
+ * Host arithmetic on HOST records, nothing launched:
+ *  sgz_hist_edges      the integers of every bucket: lo[b] = ceil((4 + s) 2^(e-2)), hi[b] = ceil((5 + s) 2^(e-2)) - 1 for b = 1 + 4 e + s,
+ *                      hi[105] = 2^26, bucket 0 is (0, 0); an empty bucket has lo > hi.  Either array may be NULL.
+ *  sgz_hist_fold       the zoom, with sgz_level_fold's boundary rule: output column b is the fold of source columns x0 + ceil(b w /
+ *                      cols) <= j < x0 + ceil((b + 1) w / cols), w = x1 - x0, cols = min(out_columns, w), every word by its rule, from
+ *                      the identity.  out must not overlap in.  SGZ_EINVAL, nothing written: a null argument, channels == 0, what
+ *                      sgz_overview_view_columns refuses, a folded count or skipped above 2^32 - 1.
+ *  sgz_hist_percentile the bucket that holds the q-quantile of |v|: r = the least integer >= q count (the product is one fp64
+ *                      multiply), clamped to [1, count]; *bucket = the least b with bucket[0] + .. + bucket[b] >= r; *lo, *hi = that
+ *                      bucket's edges / 2^23 as doubles (1.0 is full scale; bucket 0 gives 0, 0).  SGZ_EINVAL: a null argument, q
+ *                      outside [0, 1] or NaN, count == 0.
+ *  sgz_hist_readout    what a host draws from one record, in fp64: zero_share = bucket[0] / count and negative_share = negative /
+ *                      count (NaN for count 0); peak = peak / 2^23; peak_db = 20 log10(peak), -inf for a peak of 0, NaN for count 0;
+ *                      median_db = the 0.5 percentile's hi in dB, -inf for bucket 0, NaN for count 0; toggling = bits_or & ~bits_and,
+ *                      the bits that took both values; effective_bits = max(0, 24 - ctz(bits_or)) for bits_or != 0, else 0: 16-bit
+ *                      PCM reads 16, 24-bit PCM up to 24.  SGZ_EINVAL: a null argument. */
+#define SGZ_HIST_BUCKETS 106
+typedef struct sgz_hist_record {
+    uint32_t bucket[SGZ_HIST_BUCKETS];    /* samples per bucket */
+    uint32_t count;                       /* the samples that are no NaN */
+    uint32_t skipped;                     /* the NaNs */
+    uint32_t negative;                    /* samples with v < 0 */
+    uint32_t peak;                        /* max |v|, 0 when count = 0 */
+    uint32_t bits_or;                     /* OR of (uint32_t) v, 0 when count = 0 */
+    uint32_t bits_and;                    /* AND of (uint32_t) v, 0xffffffff when count = 0 */
+} sgz_hist_record;          /* 448 bytes */
+typedef struct sgz_hist_reading {
+    double zero_share, negative_share, peak, peak_db, median_db;
+    uint32_t toggling, effective_bits;
+} sgz_hist_reading;
+sgz_status sgz_stage_hist_columns(const float *d_planar, size_t channel_stride, uint32_t channels, size_t nsamples, uint32_t m, uint32_t held,
+                                  int flush, uint32_t slices, sgz_hist_record *d_carry /*[channels]*/, sgz_hist_record *d_hist /*[columns][channels]*/,
+                                  void *stream);
+void       sgz_hist_columns_limits(uint32_t *switch_over, uint32_t *tile_samples);
+void       sgz_hist_edges(uint32_t lo[SGZ_HIST_BUCKETS], uint32_t hi[SGZ_HIST_BUCKETS]);
+sgz_status sgz_hist_fold(const sgz_hist_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns, sgz_hist_record *out);
+sgz_status sgz_hist_percentile(const sgz_hist_record *rec, double q, uint32_t *bucket, double *lo, double *hi);
+sgz_status sgz_hist_readout(const sgz_hist_record *rec, sgz_hist_reading *out);
+sgz_status sgz_pcm_stream_set_hist(sgz_pcm_stream *s, uint32_t m /*0 = off*/, sgz_hist_record *hist_out /*HOST [capacity][channels]*/,
+                                   uint64_t capacity_columns);
+uint64_t   sgz_pcm_stream_hist_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
+sgz_status sgz_pcm_stream_hist_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
+sgz_status sgz_pcm_stream_flush_hist(sgz_pcm_stream *s);
 
 /* The track lane: the tracker's curve over a file -- the reference's drawFrequencyTracking readout (SpectrumRendering.cpp:300-377, the
  * line-results branch) for every frame of a streamed file, in bounded memory.  sgz_spectrogram_track_device / _host want the whole file

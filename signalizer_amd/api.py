@@ -140,6 +140,18 @@ class FieldReading(C.Structure):
                 ("direction", C.c_double), ("spread", C.c_double), ("silent_share", C.c_double)]
 
 
+# sgz_hist_record: one per (column, channel) of the histogram lane, 448 bytes = 112 words: 106 buckets of |v| and six fields
+HIST_BUCKETS = 106
+HIST_DTYPE = np.dtype([("bucket", "<u4", (HIST_BUCKETS,)), ("count", "<u4"), ("skipped", "<u4"), ("negative", "<u4"), ("peak", "<u4"),
+                       ("bits_or", "<u4"), ("bits_and", "<u4")])
+assert HIST_DTYPE.itemsize == 448
+
+
+class HistReading(C.Structure):
+    _fields_ = [("zero_share", C.c_double), ("negative_share", C.c_double), ("peak", C.c_double), ("peak_db", C.c_double),
+                ("median_db", C.c_double), ("toggling", C.c_uint32), ("effective_bits", C.c_uint32)]
+
+
 class LoudnessFilter(C.Structure):
     _fields_ = [("b", (C.c_double * 3) * 2), ("a", (C.c_double * 2) * 2), ("W", C.c_uint32), ("L", C.c_uint32)]
 
@@ -260,6 +272,8 @@ EXPORTS = [
     "sgz_pcm_stream_set_field", "sgz_pcm_stream_field_for", "sgz_pcm_stream_field_state", "sgz_pcm_stream_flush_field",
     "sgz_stage_band_columns", "sgz_band_columns_limits", "sgz_band_filter_for_rate", "sgz_band_taps", "sgz_band_fold", "sgz_band_readout",
     "sgz_band_colours", "sgz_pcm_stream_set_band", "sgz_pcm_stream_band_for", "sgz_pcm_stream_band_state", "sgz_pcm_stream_flush_band",
+    "sgz_stage_hist_columns", "sgz_hist_columns_limits", "sgz_hist_edges", "sgz_hist_fold", "sgz_hist_percentile", "sgz_hist_readout",
+    "sgz_pcm_stream_set_hist", "sgz_pcm_stream_hist_for", "sgz_pcm_stream_hist_state", "sgz_pcm_stream_flush_hist",
 ]
 
 
@@ -529,7 +543,15 @@ def lib() -> C.CDLL:
     L.sgz_band_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_band_readout.argtypes = [vp, sz, u32, u32, vp, vp]
     L.sgz_band_colours.argtypes = [vp, sz, u32, u32, vp, vp, C.c_double, vp]
-    for lane in ("waveform", "level", "truepeak", "loudness", "field", "band"):      # the six column lanes of the PCM stream: one set of calls each
+    L.sgz_stage_hist_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
+    L.sgz_hist_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    L.sgz_hist_columns_limits.restype = None
+    L.sgz_hist_edges.argtypes = [vp, vp]
+    L.sgz_hist_edges.restype = None
+    L.sgz_hist_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
+    L.sgz_hist_percentile.argtypes = [vp, C.c_double, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sgz_hist_readout.argtypes = [vp, C.POINTER(HistReading)]
+    for lane in ("waveform", "level", "truepeak", "loudness", "field", "band", "hist"):      # the seven column lanes of the PCM stream: one set of calls each
         getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, {"loudness": fp, "band": bp}[lane], u32, vp, u64] if lane in ("loudness", "band") else [vp, u32, vp, u64]
         getattr(L, f"sgz_pcm_stream_{lane}_for").argtypes = [vp, sz, C.c_int]
         getattr(L, f"sgz_pcm_stream_{lane}_for").restype = u64
@@ -1446,7 +1468,7 @@ class PcmStream:
         assert c == cols, (c, cols)
         return (rgba[:cols] if want_rgba else None), (stats[:cols] if want_stats else None), (means[:cols] if want_means else None), t.asdict()
 
-    # the six column lanes (waveform, level, truepeak, loudness, field, band): one helper per kind of call, the lane's name picks the C call
+    # the seven column lanes (waveform, level, truepeak, loudness, field, band, hist): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
         if capacity_columns is None:
             capacity_columns = 0 if out is None else int(out.shape[0])
@@ -1574,6 +1596,24 @@ class PcmStream:
         """sgz_pcm_stream_flush_band: closes the open column (one more record per channel at the cursor); waits"""
         self._lane_flush("band")
 
+    # the histogram lane: one sgz_hist_record per column of m >= 128 samples and channel, beside whatever the feeds render
+    def set_hist(self, m: int, out=None, capacity_columns: int | None = None) -> None:
+        """sgz_pcm_stream_set_hist: out -- a HIST_DTYPE numpy array [capacity, channels] or a host torch uint8 tensor [capacity, channels, 448]
+        (kept alive here; pinned memory is written in place); m == 0 disarms, 0 < m < 128 is refused"""
+        self._lane_set("hist", m, out, capacity_columns)
+
+    def hist_for(self, nsamples: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_hist_for: histogram columns the next feed of nsamples closes"""
+        return self._lane_for("hist", nsamples, flush)
+
+    def hist_state(self):
+        """sgz_pcm_stream_hist_state: (columns written since the lane was armed, samples of the open column)"""
+        return self._lane_state("hist")
+
+    def flush_hist(self) -> None:
+        """sgz_pcm_stream_flush_hist: closes the open column (one more record per channel at the cursor); waits"""
+        self._lane_flush("hist")
+
     # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
     def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:
         """sgz_pcm_stream_set_track: out -- a float64 numpy array or host torch tensor [capacity, pairs, 6] (kept alive here; pinned memory is
@@ -1690,6 +1730,57 @@ def field_readout(record) -> dict:
     check(lib().sgz_field_readout(_np_ptr(rec), C.byref(r)))
     return dict(share=np.array(r.share), mean=np.array(r.mean), peak=np.array(r.peak), direction=r.direction, spread=r.spread,
                 silent_share=r.silent_share)
+
+
+def hist_columns_limits():
+    """sgz_hist_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples)"""
+    s, t = C.c_uint32(0), C.c_uint32(0)
+    lib().sgz_hist_columns_limits(C.byref(s), C.byref(t))
+    return int(s.value), int(t.value)
+
+
+def hist_edges():
+    """sgz_hist_edges: (lo, hi), uint32 [106] each: the integers |v| of every bucket; lo > hi where a bucket holds none"""
+    lo, hi = np.zeros(HIST_BUCKETS, np.uint32), np.zeros(HIST_BUCKETS, np.uint32)
+    lib().sgz_hist_edges(_np_ptr(lo), _np_ptr(hi))
+    return lo, hi
+
+
+def stage_hist_columns(planar, channel_stride: int, channels: int, nsamples: int, m: int, held: int = 0, flush: bool = True, slices: int = 0,
+                       carry=None, hist=None, stream=None) -> int:
+    """sgz_stage_hist_columns as it is: planar / carry / hist -- cuda tensors (their data pointers; any may be None where the call allows
+    NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    return lib().sgz_stage_hist_columns(ptr(planar), channel_stride, channels, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(hist),
+                                        C.c_void_p(s) if s else None)
+
+
+def hist_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_hist_fold: HIST_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels]"""
+    records = np.ascontiguousarray(records, HIST_DTYPE)
+    n, channels = records.shape
+    x1 = n if x1 is None else x1
+    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), HIST_DTYPE)
+    check(lib().sgz_hist_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
+    return out[:min(out_columns, x1 - x0)]
+
+
+def hist_percentile(record, q: float):
+    """sgz_hist_percentile of one HIST_DTYPE record: (bucket, lo, hi) -- the bucket of the q-quantile of |v| and its edges, 1.0 = full scale"""
+    rec = np.ascontiguousarray(record, HIST_DTYPE).reshape(1)
+    b, lo, hi = C.c_uint32(0), C.c_double(0), C.c_double(0)
+    check(lib().sgz_hist_percentile(_np_ptr(rec), q, C.byref(b), C.byref(lo), C.byref(hi)))
+    return int(b.value), lo.value, hi.value
+
+
+def hist_readout(record) -> dict:
+    """sgz_hist_readout of one HIST_DTYPE record: {zero_share, negative_share, peak, peak_db, median_db, toggling, effective_bits}"""
+    rec = np.ascontiguousarray(record, HIST_DTYPE).reshape(1)
+    r = HistReading()
+    check(lib().sgz_hist_readout(_np_ptr(rec), C.byref(r)))
+    return {k: getattr(r, k) for k, _ in r._fields_}
 
 
 def truepeak_columns_limits():

@@ -1,11 +1,11 @@
-// column_lanes.hpp -- what the six column lanes (wave, level, true-peak, loudness, stereo-field, band: <lane>_columns.hip) have in common,
+// column_lanes.hpp -- what the seven column lanes (wave, level, true-peak, loudness, stereo-field, band, histogram: <lane>_columns.hip) have in common,
 // written once: the shape of a call, the column / tile / slice bounds, the aligned split and the staging of a row, the two quantisers, the
 // stage calls' front, the fold's frame, and the parts in which the loudness and the band lane are twins.  A lane's file holds what is its own:
 // its record, its accumulators, its kernels' bodies.  pcm.hip includes this for the lanes' entry points.
 // A lane's kernel-argument struct keeps its own type and layout; the helpers here are templates on it and read the grid's fields by name:
 //   n, columns, closed (long); m, held, perTile, slices (uint32_t)
 // Floating-point contraction: this header neither sets nor resets it.  loudness_columns.hip and band_columns.hip include it BEHIND their
-// `#pragma clang fp contract(off)`, so every template instantiated there was parsed without contraction; the other four files have no pragma,
+// `#pragma clang fp contract(off)`, so every template instantiated there was parsed without contraction; the other five files have no pragma,
 // and nothing here has a multiply feeding an add in floating point.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,7 +52,7 @@ inline ColumnsShape columnsShape(uint32_t cells, size_t nsamples, uint32_t m, ui
 
 // The lanes' two steps, what the stage calls and sgz_pcm_stream share: <lane>ColumnsShape is columnsShape with the lane's switch-over and
 // record, run<Lane>Columns the stage call behind its argument checks, asynchronous on `stream`, with the carry in two places and scratch of
-// sh.scratchBytes bytes (aligned to 16 for loudness and band).  Wave, level, field: carryIn is read by column 0 (held > 0), carryOut written
+// sh.scratchBytes bytes (aligned to 16 for loudness and band).  Wave, level, field, histogram: carryIn is read by column 0 (held > 0), carryOut written
 // by the open column -- the same memory only where the call has one column.  True-peak, loudness, band: carryIn is read (the history when
 // `continued`, the open column when held > 0) and carryOut is written whole by every call with samples -- never the same memory then.  The
 // loudness and band carries are <lane>CarryBytes(f) bytes per channel: the open column's record, the last W + L - 1 quantised samples, a
@@ -82,6 +82,10 @@ ColumnsShape bandColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, ui
 sgz_status runBandColumns(const ColumnsShape &sh, const sgz_band_filter &f, const float *d_planar, size_t channelStride, uint32_t channels,
                           size_t nsamples, uint64_t firstIndex, uint32_t m, uint32_t held, uint32_t continued, const void *carryIn, void *carryOut,
                           sgz_band_record *d_out, void *scratch, hipStream_t stream);
+ColumnsShape histColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
+sgz_status runHistColumns(const ColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples, uint32_t m,
+                          uint32_t held, const sgz_hist_record *carryIn, sgz_hist_record *carryOut, sgz_hist_record *d_hist, void *scratch,
+                          hipStream_t stream);
 
 // ---- 2. device helpers --------------------------------------------------------------------------------------------------------------------------
 // samples [a, b) of this call that belong to column `col`

@@ -4,7 +4,7 @@
 // and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, a lane's columns or records --
 // is a PcmOut: device block, pinned twin, pending host copy.  Every lane is a PcmSink: the caller's buffer, the cursor in it, and the PcmOut its
 // units pass through; the track lane (tracker.hip), which searches every piece's line results behind its render, is a sink of frames, and the
-// six column lanes -- waveform, level, true-peak, loudness, stereo-field, band (<lane>_columns.hip; their entry points: column_lanes.hpp),
+// seven column lanes -- waveform, level, true-peak, loudness, stereo-field, band, histogram (<lane>_columns.hip; their entry points: column_lanes.hpp),
 // which reduce every piece's new samples behind the converter in that order -- are ONE PcmLane type, a sink of columns with the open column's
 // carry, and differ in a hook that makes the one call of their reduction: one of two templates, for the two carry rules.  The feed walks the
 // lanes; all ride the same read-back.
@@ -201,8 +201,9 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // Loudness sgz_loudness_record [ceil(chunk / m) + 1][channels] the loudness lane's.
 // Field sgz_field_record [ceil(chunk / m) + 1][pairs] the stereo-field lane's.
 // Band sgz_band_record [ceil(chunk / m) + 1][channels] the band lane's.
+// Hist sgz_hist_record [ceil(chunk / m) + 1][channels] the histogram lane's.
 // OvStats sgz_overview_stat_record [columns][C][P] and OvMeans float [columns][C][P] the stats feed's, beside its OvImage.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kPcmOuts };
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -281,10 +282,10 @@ struct PcmSink {
     }
 };
 
-// The sinks in the order a feed refuses them; the six column lanes come first and are the stream's lane[] in this order
-enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
-constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand};
-constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand};
+// The sinks in the order a feed refuses them; the seven column lanes come first and are the stream's lane[] in this order
+enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
+constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist};
+constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist};
 
 // A lane's hook: the one call of its reduction, run<Lane>Columns, on the compute stream.  (n samples at `in`, flush 0) is a piece's step: the
 // columns they close go to d_out, the open one to the other half of the carry; (0 samples, flush 1) is the flush's emit launch, which leaves the
@@ -333,7 +334,8 @@ struct sgz_pcm_stream {
     bool ovStats = false;
     sgz_overview_stat_record *d_ovStatCarry = nullptr;
     // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels]),
-    // stereo-field (sgz_field_record [2][pairs]), loudness and band (two halves of <lane>CarryBytes(filter) * channels bytes), and the two filters
+    // stereo-field (sgz_field_record [2][pairs]), histogram (sgz_hist_record [2][channels]), loudness and band (two halves of
+    // <lane>CarryBytes(filter) * channels bytes), and the two filters
     PcmLane lane[kPcmLanes];
     sgz_loudness_filter ldFilter{};
     sgz_band_filter bdFilter{};
@@ -374,7 +376,7 @@ static sgz_status pcmDrain(PcmSlot &sl, sgz_pcm_timing *timing)
 
 // ---- the lanes inside the stream (sgz.h, "The waveform lane" ... "The loudness lane", "The track lane") -----------------------------------------
 // The hooks are two templates over what a lane's two steps are called, for the two carry rules.
-// The waveform, level and stereo-field carries hold the open column alone: a step moves to the other half only when a column stays open.
+// The waveform, level, stereo-field and histogram carries hold the open column alone: a step moves to the other half only when a column stays open.
 // Record: the element of the carry and of the output, PerCell of them per channel (or, OfPairs, per pair); Shape, Run: the lane's two steps
 template <class Record, size_t PerCell, bool OfPairs, auto Shape, auto Run>
 static sgz_status pcmOpenColumnRun(sgz_pcm_stream &s, PcmLane &l, const float *in, size_t n, int flush, void *d_out, uint64_t *closed)
@@ -840,6 +842,7 @@ sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format
         {"loudness", "loudness", kOutLoudness, s->numChannels * sizeof(sgz_loudness_record), pcmHistoryRun<PcmLoudness>},
         {"stereo-field", "field", kOutField, cfg->num_pairs * sizeof(sgz_field_record), pcmOpenColumnRun<sgz_field_record, 1, true, fieldColumnsShape, runFieldColumns>},
         {"band", "band", kOutBand, s->numChannels * sizeof(sgz_band_record), pcmHistoryRun<PcmBand>},
+        {"histogram", "hist", kOutHist, s->numChannels * sizeof(sgz_hist_record), pcmOpenColumnRun<sgz_hist_record, 1, false, histColumnsShape, runHistColumns>},
     };
     for (int id = 0; id < kPcmLanes; ++id) {
         PcmLane &l = s->lane[id];
@@ -1109,12 +1112,27 @@ sgz_status sgz_pcm_stream_set_band(sgz_pcm_stream *s, const sgz_band_filter *fil
     return SGZ_OK;
 }
 
+sgz_status sgz_pcm_stream_set_hist(sgz_pcm_stream *s, uint32_t m, sgz_hist_record *hist_out, uint64_t capacity_columns)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    PcmLane &l = s->lane[kSinkHist];
+    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
+    if (m < 128) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_hist: m >= 128 samples per column (a 448-byte record per channel for fewer than 112 samples would read back more than the samples)");
+    if (!hist_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_hist: null hist_out");
+    if (reinterpret_cast<uintptr_t>(hist_out) % alignof(sgz_hist_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_hist: hist_out is not aligned to 4 bytes");
+    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_hist: m differs from the open column's -- flush it (sgz_pcm_stream_flush_hist), disarm or reset first");
+    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * sizeof(sgz_hist_record)));
+    pcmLaneArm(*s, l, m, hist_out, capacity_columns);
+    return SGZ_OK;
+}
+
 uint64_t sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkWave, nsamples, flush); }
 uint64_t sgz_pcm_stream_level_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLevel, nsamples, flush); }
 uint64_t sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkTruePeak, nsamples, flush); }
 uint64_t sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLoudness, nsamples, flush); }
 uint64_t sgz_pcm_stream_field_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkField, nsamples, flush); }
 uint64_t sgz_pcm_stream_band_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkBand, nsamples, flush); }
+uint64_t sgz_pcm_stream_hist_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkHist, nsamples, flush); }
 
 sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkWave, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLevel, columns_written, open_samples); }
@@ -1122,6 +1140,7 @@ sgz_status sgz_pcm_stream_truepeak_state(const sgz_pcm_stream *s, uint64_t *colu
 sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLoudness, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_field_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkField, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_band_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkBand, columns_written, open_samples); }
+sgz_status sgz_pcm_stream_hist_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkHist, columns_written, open_samples); }
 
 sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkWave); }
 sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLevel); }
@@ -1129,6 +1148,7 @@ sgz_status sgz_pcm_stream_flush_truepeak(sgz_pcm_stream *s) { return pcmLaneFlus
 sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLoudness); }
 sgz_status sgz_pcm_stream_flush_field(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkField); }
 sgz_status sgz_pcm_stream_flush_band(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkBand); }
+sgz_status sgz_pcm_stream_flush_hist(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkHist); }
 
 // ---- the track lane's calls -------------------------------------------------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_set_track(sgz_pcm_stream *s, uint32_t graph, double mouse_fraction, sgz_line_peak *track_out, uint64_t capacity_frames)
