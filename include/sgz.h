@@ -78,6 +78,12 @@ extern "C" {
  *  host helpers sgz_hist_edges, sgz_hist_fold, sgz_hist_percentile and sgz_hist_readout and, on the PCM stream, sgz_pcm_stream_set_hist,
  *  sgz_pcm_stream_hist_for, sgz_pcm_stream_hist_state, sgz_pcm_stream_flush_hist.  No existing entry point or struct changed and the suite
  *  pins 5; a stream that was never armed enqueues what it did before.)
+ * (5, later: the power overview -- sgz_overview_power_record, sgz_stage_overview_power, sgz_spectrogram_overview_power_device / _host,
+ *  sgz_stage_overview_power_view, sgz_overview_power_view_host, the host helpers sgz_overview_power_quantise, sgz_overview_power_fold,
+ *  sgz_overview_power_readout and sgz_overview_power_levels and, on the PCM stream, sgz_pcm_stream_feed_overview_power and
+ *  sgz_spectrogram_overview_power_pcm.  No existing entry point or struct changed and the suite pins 5; the new refusals on existing calls,
+ *  a feed of another kind while a power column is open, cannot be reached without the new calls.  A binding that needs them looks the
+ *  symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -625,8 +631,8 @@ sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *pla
  * For k == 1: hi == lo == x bit for bit for a non-NaN x, sum == q(x) and count == 1.  The image is in general NOT the frame render's byte
  * for byte: the mean is the quantised value.
  * The mean is a mean of displayed (dB-axis) values, hence the geometric mean of the magnitudes: it is defined on what every render writes
- * and what the colour map takes.  A power-domain mean needs magnitudes from before the dB map, which no boundary of the library exposes:
- * out of scope, as are percentiles and the median.
+ * and what the colour map takes.  A power-domain mean needs magnitudes from before the dB map: that is the power overview below, which
+ * reduces K_A's mapped magnitudes.  Percentiles and the median are out of scope.
  * The calls follow their peak-hold twins argument for argument: float *d_peaks becomes sgz_overview_stat_record *d_stats, and every call
  * has one more optional output, the means float [columns][pairs][P] -- value planes as V is (sgz_stage_track_peaks_values takes them).
  * Of image, records and means at least one must be non-NULL.  The carry is sgz_overview_stat_record [pairs][P].
@@ -681,6 +687,98 @@ sgz_status sgz_pcm_stream_feed_overview_stats(sgz_pcm_stream *s, const void *pcm
 sgz_status sgz_spectrogram_overview_stats_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                               const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
                                               sgz_overview_stat_record *stats_out, float *means_out, sgz_pcm_timing *timing);
+
+/* The power overview: mean-square spectrum of k frames per image column -- the power-domain mean that every analyser calls "average": the
+ * long-term average spectrum of a file, and the spectrum of a selection.  The mean overview above averages displayed (dB-axis) values, a
+ * geometric mean of the magnitudes, which understates noise-like material by about 2.5 dB and lets one silent frame drag a column down by the
+ * whole dB range.  This lane reduces the mapped magnitudes themselves, at the one boundary inside the library where they exist: K_A writes
+ * them to device memory before K_B reads them.  It needs no decay state and no K_B launch.
+ * Definition (exact, no tolerance).  M[f][p][s][i] are the mapped magnitudes of frame f, pair p, side s < sides, pixel i < P: exactly what
+ * sgz_stage_mapped writes, bit for bit, on every path (on channel-split plans the completed values, not sgz_stage_mapped_dominant's).  sides is
+ * 2 for Separate / MidSide and 1 otherwise; width = pairs * sides * P records per column.  Columns and their frames are counted by
+ * sgz_overview_step, exactly as in the two other overviews.  Let x = M[f][p][s][i].
+ *   quantiser  a NaN takes no part in sum, count, lo or hi; it is counted in nans.  Otherwise t = (double)x * (double)x (exact: 48
+ *              significant bits);  u = t * 2^60 (exact; +inf stays +inf);  q = 2^64 - 2^11 (the largest double below 2^64) if u >= 2^64 -
+ *              2^11;  otherwise q = rint(u) as a uint64.  A tie cannot occur: x^2 2^60 = m^2 2^(2e + 60) has an even exponent.  Range and
+ *              resolution: values up to 4 (+12 dB over a full-scale sine), 2^-60 in power (-180 dB).
+ *   record     per (column, pair, side, pixel) one sgz_overview_power_record: sum[0], sum[1] = the low and the high word of the 128-bit sum
+ *              of q; count = the non-NaN frames; nans = the NaN frames; lo the least and hi the greatest non-NaN x under the overview's
+ *              total order (-0 below +0), both 0x7FC00000 when count == 0.  sum < 2^96 for every count below 2^32.
+ *   fold       field-wise: the 128-bit sums add, count and nans add, lo is the least of the los, hi the greatest of the his.  All are
+ *              associative and commutative: every cut (slices, calls, slabs, feeds, chunk sizes) gives the same bytes, a coarser column
+ *              is exactly the fold of the finer ones, and the whole file's average spectrum is the fold of all columns.
+ *   readout    count == 0: rms has the bits 0x7FC00000.  Otherwise S = (double)sum[1] * 2^64 + (double)sum[0] (the first term is exact;
+ *              the conversion of sum[0] and the addition round to nearest even);  ms = S / (double)count;  rms = (float)(sqrt(ms) *
+ *              2^-30).  Division and root are correctly rounded, nothing is contracted.  The mean square as a double is ms * 2^-60.
+ *   level      the value K_B writes as a line result for a frame of magnitude rms from a zero decay state: dbMap(slopeMap[i], rms), the
+ *              render's own dB map; 0x7FC00000 when count == 0.  Both sides use slopeMap[i].
+ *   pixel      the additive blend of the pairs' colours at the level of side 0, p = 0 .. pairs - 1 in order, from a black column buffer,
+ *              then the 8-bit conversion -- the overview's pixel with the level in V's place.
+ * For k == 1 and 2^-7 <= |x| < 4: rms == |x| bit for bit.  In general the image is NOT the frame render's: there is no decay, and the value
+ * is quantised.
+ * Argument order follows the mean overview's calls: d_power [columns][pairs][sides][P] records, d_levels the same shape in floats, the carry
+ * sgz_overview_power_record [pairs][sides][P].  Of image, records and levels at least one must be non-NULL.
+ *  sgz_stage_overview_power   d_mapped float [frames][pairs][sides][P], whatever floats they are.  Refusals (SGZ_EINVAL, nothing launched or
+ *                      written), slices (0, 1 .. 64, identical bytes), asynchrony, the carry snapshot and "only the documented bytes are
+ *                      written" as for sgz_stage_overview_stats.
+ *  sgz_spectrogram_overview_power_device / _host   slabs of frames (SGZ_OPT_OVERVIEW_SLAB, or by default the overview's frame count): per
+ *                      slab K_A into plan scratch with its late pixels completed (sgz_stage_mapped's call), then the reduction with the open
+ *                      column carried; the bytes do not depend on the slab.  No K_B, no decay state, no d_state argument.  SGZ_CH_PHASE
+ *                      (plane 1 is no magnitude) and RSNT plans: SGZ_EUNSUPPORTED before the device is touched.  Fewer samples than a
+ *                      window: SGZ_SKIPPED_FRAME, nothing written.
+ *  sgz_stage_overview_power_view / sgz_overview_power_view_host   any range [x0, x1) of kept records [n][pairs][sides][P] at any width, in
+ *                      the plan's colours, by the boundary rule of sgz_overview_view_columns: the image, the folded records and the levels.
+ *                      Outputs that overlap the source range are refused.  The counts of a folded column are the caller's to keep below
+ *                      2^32 (sgz_overview_power_fold checks them).
+ *  sgz_overview_power_quantise   host, no GPU: q of n floats by the definition (0 for a NaN, which has none).
+ *  sgz_overview_power_fold    host, no GPU: columns [x0, x1) of in [n][width] into cols = min(out_columns, x1 - x0) columns of out by the
+ *                      same boundary rule.  SGZ_EINVAL, nothing written: a null argument, width == 0, what sgz_overview_view_columns
+ *                      refuses, a folded count or nans above 2^32 - 1.
+ *  sgz_overview_power_readout host, no GPU: `count` records into the planes mean_square (ms * 2^-60; NaN when count == 0), rms, lo and hi;
+ *                      any of the four may be NULL, not all.
+ *  sgz_overview_power_levels  host, no GPU: the levels of in [columns][pairs][sides][P] by the plan's host slope table and scalars and
+ *                      std::log(float) -- the spectrum of a selection is sgz_overview_power_fold, then this. */
+typedef struct sgz_overview_power_record {
+    uint64_t sum[2];    /* low word, high word of the 128-bit sum of q over the column's non-NaN frames */
+    uint32_t count;     /* non-NaN frames                                                            */
+    uint32_t nans;      /* NaN frames                                                                */
+    float lo, hi;       /* the least / the greatest non-NaN value; both 0x7FC00000 when count == 0   */
+} sgz_overview_power_record;               /* 32 bytes, 8-aligned */
+#ifdef __cplusplus
+static_assert(sizeof(sgz_overview_power_record) == 32 && alignof(sgz_overview_power_record) == 8, "sgz_overview_power_record: 32 bytes, 8-aligned");
+static_assert(offsetof(sgz_overview_power_record, sum) == 0 && offsetof(sgz_overview_power_record, count) == 16 && offsetof(sgz_overview_power_record, nans) == 20 &&
+              offsetof(sgz_overview_power_record, lo) == 24 && offsetof(sgz_overview_power_record, hi) == 28, "sgz_overview_power_record: offsets");
+#endif
+sgz_status sgz_stage_overview_power(sgz_plan *plan, const float *d_mapped, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                                    sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels, void *stream);
+sgz_status sgz_spectrogram_overview_power_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                                 uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels, void *stream);
+sgz_status sgz_spectrogram_overview_power_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                               uint8_t *rgba_out, sgz_overview_power_record *power_out, float *levels_out, sgz_timing *timing);
+sgz_status sgz_stage_overview_power_view(sgz_plan *plan, const sgz_overview_power_record *d_power, size_t n, size_t x0, size_t x1, uint32_t out_columns,
+                                         uint32_t slices, uint8_t *d_rgba, sgz_overview_power_record *d_power_out, float *d_levels, void *stream);
+sgz_status sgz_overview_power_view_host(sgz_plan *plan, const sgz_overview_power_record *power, size_t n, size_t x0, size_t x1, uint32_t out_columns,
+                                        uint8_t *rgba_out, sgz_overview_power_record *power_out, float *levels_out, sgz_timing *timing);
+sgz_status sgz_overview_power_quantise(const float *x, size_t n, uint64_t *q);
+sgz_status sgz_overview_power_fold(const sgz_overview_power_record *in, size_t n, size_t width, size_t x0, size_t x1, uint32_t out_columns,
+                                   sgz_overview_power_record *out);
+sgz_status sgz_overview_power_readout(const sgz_overview_power_record *in, size_t count, double *mean_square, float *rms, float *lo, float *hi);
+sgz_status sgz_overview_power_levels(const sgz_plan *plan, const sgz_overview_power_record *in, size_t columns, float *levels);
+/*  sgz_pcm_stream_feed_overview_power / sgz_spectrogram_overview_power_pcm   the overview inside sgz_pcm_stream with this reduction: the
+ *                      concatenated columns of all feeds equal sgz_spectrogram_overview_power_host of the converted planar floats, byte for
+ *                      byte, however the stream is cut.  A power feed neither reads nor advances the stream's decay state: a plain feed
+ *                      behind it continues the state of the last feed that rendered.  An open column is of one of three kinds (peak hold,
+ *                      mean, power): a feed of another kind while a column is open is refused with SGZ_EINVAL, consumes nothing and names the
+ *                      flush call that closes it in sgz_last_error.  sgz_pcm_stream_columns_for, sgz_pcm_stream_open_frames and
+ *                      sgz_pcm_stream_reset serve all three kinds.  A power feed with the track lane armed is refused (SGZ_EINVAL): it has
+ *                      no line results to search.  The seven column lanes run in it as in any feed.  Phase and RSNT streams:
+ *                      SGZ_EUNSUPPORTED. */
+sgz_status sgz_pcm_stream_feed_overview_power(sgz_pcm_stream *s, const void *pcm /*HOST*/, size_t nsamples, uint32_t k, int flush, uint8_t *rgba_out /*or NULL*/,
+                                              sgz_overview_power_record *power_out /*or NULL*/, float *levels_out /*or NULL*/, uint64_t capacity_columns,
+                                              uint64_t *columns_out, sgz_pcm_timing *timing);
+sgz_status sgz_spectrogram_overview_power_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                              const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
+                                              sgz_overview_power_record *power_out, float *levels_out, sgz_pcm_timing *timing);
 
 /* The waveform lane: a minimum and a maximum per screen column and channel of a file's samples -- what every editor draws beside the
  * spectrogram lane -- reduced on the device from the planar floats the streamed render has there anyway.  The reference has no counterpart

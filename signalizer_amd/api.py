@@ -258,6 +258,9 @@ EXPORTS = [
     "sgz_stage_overview_stats", "sgz_spectrogram_overview_stats_device", "sgz_spectrogram_overview_stats_host", "sgz_stage_overview_stats_view",
     "sgz_overview_stats_view_host", "sgz_overview_stats_fold", "sgz_overview_stats_readout", "sgz_pcm_stream_feed_overview_stats",
     "sgz_spectrogram_overview_stats_pcm",
+    "sgz_stage_overview_power", "sgz_spectrogram_overview_power_device", "sgz_spectrogram_overview_power_host", "sgz_stage_overview_power_view",
+    "sgz_overview_power_view_host", "sgz_overview_power_quantise", "sgz_overview_power_fold", "sgz_overview_power_readout",
+    "sgz_overview_power_levels", "sgz_pcm_stream_feed_overview_power", "sgz_spectrogram_overview_power_pcm",
     "sgz_stage_wave_columns", "sgz_wave_columns_limits", "sgz_pcm_stream_set_waveform", "sgz_pcm_stream_waveform_for",
     "sgz_pcm_stream_waveform_state", "sgz_pcm_stream_flush_waveform",
     "sgz_track_peak_values", "sgz_stage_track_peaks_values", "sgz_pcm_stream_set_track", "sgz_pcm_stream_track_for", "sgz_pcm_stream_track_state",
@@ -370,6 +373,15 @@ def lib() -> C.CDLL:
     L.sgz_overview_stats_view_host.argtypes = [vp, vp, sz, sz, sz, u32, vp, vp, vp, C.POINTER(Timing)]
     L.sgz_overview_stats_fold.argtypes = [vp, sz, sz, sz, sz, u32, vp]
     L.sgz_overview_stats_readout.argtypes = [vp, sz, vp, vp, vp]
+    L.sgz_stage_overview_power.argtypes = [vp, vp, sz, u32, u32, C.c_int, u32, vp, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_power_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_power_host.argtypes = [vp, vp, u32, sz, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.sgz_stage_overview_power_view.argtypes = [vp, vp, sz, sz, sz, u32, u32, vp, vp, vp, vp]
+    L.sgz_overview_power_view_host.argtypes = [vp, vp, sz, sz, sz, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.sgz_overview_power_quantise.argtypes = [vp, sz, vp]
+    L.sgz_overview_power_fold.argtypes = [vp, sz, sz, sz, sz, u32, vp]
+    L.sgz_overview_power_readout.argtypes = [vp, sz, vp, vp, vp, vp]
+    L.sgz_overview_power_levels.argtypes = [vp, vp, sz, vp]
     L.sgz_comm_unique_id.argtypes = [vp]
     L.sgz_comm_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.sgz_comm_destroy.argtypes = [vp]
@@ -508,6 +520,8 @@ def lib() -> C.CDLL:
     L.sgz_spectrogram_overview_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, C.POINTER(PcmTiming)]
     L.sgz_pcm_stream_feed_overview_stats.argtypes = [vp, vp, sz, u32, C.c_int, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
     L.sgz_spectrogram_overview_stats_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, vp, C.POINTER(PcmTiming)]
+    L.sgz_pcm_stream_feed_overview_power.argtypes = [vp, vp, sz, u32, C.c_int, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
+    L.sgz_spectrogram_overview_power_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, vp, C.POINTER(PcmTiming)]
     L.sgz_stage_level_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
     L.sgz_level_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.sgz_level_columns_limits.restype = None
@@ -824,6 +838,54 @@ def overview_stats_readout(records: np.ndarray):
     mean, lo, hi = (np.zeros(records.shape, np.float32) for _ in range(3))
     check(lib().sgz_overview_stats_readout(_np_ptr(records), records.size, _np_ptr(mean), _np_ptr(lo), _np_ptr(hi)))
     return mean, lo, hi
+
+
+# sgz_overview_power_record (sgz.h, "The power overview"): 32 bytes, 8-aligned; sum = (low word, high word) of the 128-bit sum.  On the device
+# a record is four int64 words of a torch tensor [..., 4]; power_from_device turns such a tensor into a numpy array of this dtype
+OVERVIEW_POWER_DTYPE = np.dtype({"names": ["sum", "count", "nans", "lo", "hi"], "formats": [("<u8", (2,)), "<u4", "<u4", "<f4", "<f4"],
+                                 "offsets": [0, 16, 20, 24, 28], "itemsize": 32})
+
+
+def power_from_device(t) -> np.ndarray:
+    """cuda int64 [..., 4] (records as the power calls write them) -> numpy OVERVIEW_POWER_DTYPE [...]"""
+    h = np.ascontiguousarray(t.cpu().numpy())
+    return h.view(OVERVIEW_POWER_DTYPE).reshape(h.shape[:-1])
+
+
+def power_to_device(records: np.ndarray, device):
+    """numpy OVERVIEW_POWER_DTYPE [...] -> cuda int64 [..., 4]"""
+    import torch
+    r = np.ascontiguousarray(records, OVERVIEW_POWER_DTYPE)
+    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 4).copy()).to(device)
+
+
+def overview_power_quantise(x: np.ndarray) -> np.ndarray:
+    """sgz_overview_power_quantise (host, no GPU): float32 [...] -> uint64 [...], q of the power overview's definition (0 for a NaN)"""
+    x = np.ascontiguousarray(x, np.float32)
+    q = np.zeros(x.shape, np.uint64)
+    check(lib().sgz_overview_power_quantise(_np_ptr(x), x.size, _np_ptr(q)))
+    return q
+
+
+def overview_power_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_overview_power_fold (host, no GPU): OVERVIEW_POWER_DTYPE records [n, ...], source columns [x0, x1) -> [min(out_columns, x1 - x0), ...]"""
+    records = np.ascontiguousarray(records, OVERVIEW_POWER_DTYPE)
+    n = int(records.shape[0])
+    x1 = n if x1 is None else x1
+    width = int(np.prod(records.shape[1:], dtype=np.int64))
+    out = np.zeros((overview_view_columns(n, x0, x1, out_columns), *records.shape[1:]), OVERVIEW_POWER_DTYPE)
+    check(lib().sgz_overview_power_fold(_np_ptr(records), n, width, x0, x1, out_columns, _np_ptr(out)))
+    return out
+
+
+def overview_power_readout(records: np.ndarray):
+    """sgz_overview_power_readout (host, no GPU): OVERVIEW_POWER_DTYPE records [...] -> (mean_square float64, rms, lo, hi float32), planes of
+    the same shape"""
+    records = np.ascontiguousarray(records, OVERVIEW_POWER_DTYPE)
+    ms = np.zeros(records.shape, np.float64)
+    rms, lo, hi = (np.zeros(records.shape, np.float32) for _ in range(3))
+    check(lib().sgz_overview_power_readout(_np_ptr(records), records.size, _np_ptr(ms), _np_ptr(rms), _np_ptr(lo), _np_ptr(hi)))
+    return ms, rms, lo, hi
 
 
 class Plan:
@@ -1161,6 +1223,106 @@ class Plan:
                                                   out.data_ptr() if want_stats else None, means.data_ptr() if want_means else None, s))
         return rgba, out, means
 
+    # the power overview: the same columns over the mapped magnitudes, reduced to 128-bit sums of squares and coloured from the rms' level
+    def overview_power_columns(self, mapped, k: int, held: int = 0, flush: bool = True, slices: int = 0, carry=None, want_rgba: bool = True,
+                               want_power: bool = False, want_levels: bool = False, stream=None):
+        """sgz_stage_overview_power: mapped -- cuda float32 [frames, pairs, sides, P]; carry -- cuda int64 [pairs, sides, P, 4], the open column's
+        records (read when held > 0, written when frames stay open).  Returns (cuda rgba uint8 [columns, P, 4] or None, cuda records int64
+        [columns, pairs, sides, P, 4] or None -- see power_from_device --, cuda levels float32 [columns, pairs, sides, P] or None, frames left
+        open)."""
+        import torch
+        assert mapped.is_cuda and mapped.dtype == torch.float32 and mapped.is_contiguous()
+        assert tuple(mapped.shape[1:]) == (self.C, self.sides, self.P)
+        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * self.sides * self.P * 4)
+        frames = mapped.shape[0]
+        columns, held_out = overview_step(k, held, frames, flush)
+        n = max(columns, 1)                                                                                     # (never a NULL pointer)
+        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=mapped.device) if want_rgba else None
+        power = torch.empty((n, self.C, self.sides, self.P, 4), dtype=torch.int64, device=mapped.device) if want_power else None
+        levels = torch.empty((n, self.C, self.sides, self.P), dtype=torch.float32, device=mapped.device) if want_levels else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview_power(self.h, mapped.data_ptr(), frames, k, held, int(bool(flush)), slices,
+                                             carry.data_ptr() if carry is not None else None, rgba.data_ptr() if want_rgba else None,
+                                             power.data_ptr() if want_power else None, levels.data_ptr() if want_levels else None, s))
+        return (rgba[:columns] if want_rgba else None), (power[:columns] if want_power else None), (levels[:columns] if want_levels else None), held_out
+
+    def overview_power(self, planar, k: int, want_rgba: bool = True, want_power: bool = False, want_levels: bool = False, stream=None):
+        """The power overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_power_host -> (rgba or None, records
+        OVERVIEW_POWER_DTYPE [columns, C, sides, P] or None, levels float32 [columns, C, sides, P] or None, timing dict).  planar a cuda tensor:
+        sgz_spectrogram_overview_power_device, asynchronous -> (cuda rgba, cuda records int64 [columns, C, sides, P, 4], cuda levels), None
+        where not wanted.  Fewer samples than a window: None."""
+        if isinstance(planar, np.ndarray):
+            planar = np.ascontiguousarray(planar, np.float32)
+            nch, S = planar.shape
+            columns = -(-self.num_frames(S) // k)
+            n = max(columns, 1)
+            rgba = np.zeros((n, self.P, 4), np.uint8) if want_rgba else None
+            power = np.zeros((n, self.C, self.sides, self.P), OVERVIEW_POWER_DTYPE) if want_power else None
+            levels = np.zeros((n, self.C, self.sides, self.P), np.float32) if want_levels else None
+            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
+            t = Timing()
+            st = check(lib().sgz_spectrogram_overview_power_host(self.h, ptrs, nch, S, k, _np_ptr(rgba) if want_rgba else None,
+                                                                 _np_ptr(power) if want_power else None, _np_ptr(levels) if want_levels else None,
+                                                                 C.byref(t)))
+            if st == SGZ_SKIPPED_FRAME:
+                return None
+            return ((rgba[:columns] if want_rgba else None), (power[:columns] if want_power else None), (levels[:columns] if want_levels else None),
+                    {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames})
+        import torch
+        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
+        S = planar.shape[1]
+        columns = -(-self.num_frames(S) // k)
+        n = max(columns, 1)
+        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None
+        power = torch.empty((n, self.C, self.sides, self.P, 4), dtype=torch.int64, device=planar.device) if want_power else None
+        levels = torch.empty((n, self.C, self.sides, self.P), dtype=torch.float32, device=planar.device) if want_levels else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = check(lib().sgz_spectrogram_overview_power_device(self.h, planar.data_ptr(), planar.stride(0), S, k,
+                                                               rgba.data_ptr() if want_rgba else None, power.data_ptr() if want_power else None,
+                                                               levels.data_ptr() if want_levels else None, s))
+        if st == SGZ_SKIPPED_FRAME:
+            return None
+        return (rgba[:columns] if want_rgba else None), (power[:columns] if want_power else None), (levels[:columns] if want_levels else None)
+
+    def overview_power_view(self, power, out_columns: int, x0: int = 0, x1: int | None = None, slices: int = 0, want_rgba: bool = True,
+                            want_power: bool = False, want_levels: bool = False, stream=None):
+        """The view of kept power records over source columns [x0, x1) (default: to the end) at min(out_columns, x1 - x0) columns.  power a
+        cuda int64 tensor [n, C, sides, P, 4]: sgz_stage_overview_power_view, asynchronous -> (cuda rgba, cuda records, cuda levels), None where
+        not wanted.  power a numpy OVERVIEW_POWER_DTYPE array [n, C, sides, P]: sgz_overview_power_view_host -> (rgba, records, levels, timing
+        dict)."""
+        n = int(power.shape[0])
+        x1 = n if x1 is None else x1
+        cols = overview_view_columns(n, x0, x1, out_columns)
+        shape = (self.C, self.sides, self.P)
+        if isinstance(power, np.ndarray):
+            power = np.ascontiguousarray(power, OVERVIEW_POWER_DTYPE)
+            assert tuple(power.shape[1:]) == shape, tuple(power.shape)
+            rgba = np.zeros((cols, self.P, 4), np.uint8) if want_rgba else None
+            out = np.zeros((cols, *shape), OVERVIEW_POWER_DTYPE) if want_power else None
+            levels = np.zeros((cols, *shape), np.float32) if want_levels else None
+            t = Timing()
+            check(lib().sgz_overview_power_view_host(self.h, _np_ptr(power), n, x0, x1, out_columns, _np_ptr(rgba) if want_rgba else None,
+                                                     _np_ptr(out) if want_power else None, _np_ptr(levels) if want_levels else None, C.byref(t)))
+            return rgba, out, levels, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+        import torch
+        assert power.is_cuda and power.dtype == torch.int64 and power.is_contiguous() and tuple(power.shape[1:]) == (*shape, 4)
+        rgba = torch.empty((cols, self.P, 4), dtype=torch.uint8, device=power.device) if want_rgba else None
+        out = torch.empty((cols, *shape, 4), dtype=torch.int64, device=power.device) if want_power else None
+        levels = torch.empty((cols, *shape), dtype=torch.float32, device=power.device) if want_levels else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview_power_view(self.h, power.data_ptr(), n, x0, x1, out_columns, slices, rgba.data_ptr() if want_rgba else None,
+                                                  out.data_ptr() if want_power else None, levels.data_ptr() if want_levels else None, s))
+        return rgba, out, levels
+
+    def overview_power_levels(self, records: np.ndarray) -> np.ndarray:
+        """sgz_overview_power_levels (host, no GPU): OVERVIEW_POWER_DTYPE records [columns, C, sides, P] (or [C, sides, P]: one column) -> float32
+        levels of the same shape, by the plan's host tables -- the spectrum of a selection is overview_power_fold, then this"""
+        records = np.ascontiguousarray(records, OVERVIEW_POWER_DTYPE)
+        assert tuple(records.shape[-3:]) == (self.C, self.sides, self.P), tuple(records.shape)
+        levels = np.zeros(records.shape, np.float32)
+        check(lib().sgz_overview_power_levels(self.h, _np_ptr(records), records.size // (self.C * self.sides * self.P), _np_ptr(levels)))
+        return levels
+
     def colour_table(self, pair: int) -> np.ndarray:
         out = np.zeros((NUM_SPEC_COLOURS + 1, 3), np.float32)
         check(lib().sgz_plan_get_colour_table(self.h, pair, _np_ptr(out)))
@@ -1467,6 +1629,35 @@ class PcmStream:
         check(st)
         assert c == cols, (c, cols)
         return (rgba[:cols] if want_rgba else None), (stats[:cols] if want_stats else None), (means[:cols] if want_means else None), t.asdict()
+
+    def feed_overview_power_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, power, levels, capacity_columns: int, timing: bool = True):
+        """the C call as it is: (status, columns_out, PcmTiming or None); rgba / power / levels: numpy arrays, host torch tensors or None"""
+        t, c = PcmTiming() if timing else None, C.c_uint64(0)
+        st = lib().sgz_pcm_stream_feed_overview_power(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
+                                                      *[_buf_ptr(a) if a is not None else None for a in (rgba, power, levels)],
+                                                      capacity_columns, C.byref(c), C.byref(t) if timing else None)
+        return st, int(c.value), t
+
+    def feed_overview_power(self, pcm, k: int, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_power: bool = True,
+                            want_levels: bool = False):
+        """Feeds nsamples (default: all of pcm; pcm None: none) into the power overview at k frames per column and returns the columns that
+        closed: (rgba uint8 [columns, P, 4] or None, records OVERVIEW_POWER_DTYPE [columns, pairs, sides, P] or None, levels float32 [columns,
+        pairs, sides, P] or None, timing dict).  The stream's decay state is neither read nor advanced."""
+        if pcm is None:
+            n = 0
+        else:
+            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+            n = nbytes // self.frame_bytes if nsamples is None else nsamples
+        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
+        P, pairs = self.cfg.axis_points, self.cfg.num_pairs
+        sides = 2 if self.cfg.channel_mode in (4, 5, 6) else 1
+        rgba = np.zeros((max(cols, 1), P, 4), np.uint8) if want_rgba else None
+        power = np.zeros((max(cols, 1), pairs, sides, P), OVERVIEW_POWER_DTYPE) if want_power else None
+        levels = np.zeros((max(cols, 1), pairs, sides, P), np.float32) if want_levels else None
+        st, c, t = self.feed_overview_power_into(pcm if n else None, n, k, flush, rgba, power, levels, cols)
+        check(st)
+        assert c == cols, (c, cols)
+        return (rgba[:cols] if want_rgba else None), (power[:cols] if want_power else None), (levels[:cols] if want_levels else None), t.asdict()
 
     # the seven column lanes (waveform, level, truepeak, loudness, field, band, hist): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
@@ -2010,6 +2201,28 @@ def overview_stats_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_ma
     if st == SGZ_SKIPPED_FRAME:
         cols = 0
     return st, (rgba[:cols] if want_rgba else None), (stats[:cols] if want_stats else None), (means[:cols] if want_means else None), t.asdict()
+
+
+def overview_power_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
+                       want_power: bool = True, want_levels: bool = False):
+    """One-shot power overview of an interleaved PCM buffer (sgz_spectrogram_overview_power_pcm): (status, rgba or None, records
+    OVERVIEW_POWER_DTYPE or None, levels or None, timing dict); SGZ_SKIPPED_FRAME and empty outputs for fewer samples than a window"""
+    c = _as_config(cfg)
+    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
+    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
+    cols = -(-F // k) if k else 0
+    sides = 2 if c.channel_mode in (4, 5, 6) else 1
+    rgba = np.zeros((max(cols, 1), c.axis_points, 4), np.uint8) if want_rgba else None
+    power = np.zeros((max(cols, 1), c.num_pairs, sides, c.axis_points), OVERVIEW_POWER_DTYPE) if want_power else None
+    levels = np.zeros((max(cols, 1), c.num_pairs, sides, c.axis_points), np.float32) if want_levels else None
+    m, mp = _channel_map(channel_map)
+    t = PcmTiming()
+    st = check(lib().sgz_spectrogram_overview_power_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(rgba) if want_rgba else None,
+                                                        _np_ptr(power) if want_power else None, _np_ptr(levels) if want_levels else None, C.byref(t)))
+    if st == SGZ_SKIPPED_FRAME:
+        cols = 0
+    return st, (rgba[:cols] if want_rgba else None), (power[:cols] if want_power else None), (levels[:cols] if want_levels else None), t.asdict()
 
 
 def render_spectrogram_pcm(cfg, pcm, fmt: int, src_channels: int, channel_map=None, nsamples: int | None = None, want_lines: bool = False):

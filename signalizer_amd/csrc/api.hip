@@ -48,7 +48,8 @@ Plan::~Plan()
         if (p) (void)hipFree(p);
     for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq, (void *)d_ovLines, (void *)d_ovCarry,
                     (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks, (void *)d_ovViewIn, (void *)d_ovsCarry,
-                    (void *)d_ovsCarryCopy, (void *)d_ovsPartial, (void *)d_hostOvStats, (void *)d_hostOvMeans, (void *)d_ovsViewIn})
+                    (void *)d_ovsCarryCopy, (void *)d_ovsPartial, (void *)d_hostOvStats, (void *)d_hostOvMeans, (void *)d_ovsViewIn,
+                    (void *)d_ovpCarry, (void *)d_ovpCarryCopy, (void *)d_ovpPartial, (void *)d_hostOvPower, (void *)d_hostOvLevels, (void *)d_ovpViewIn})
         if (p) (void)hipFree(p);
     for (void *e : hostEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *e : shardEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
@@ -1303,6 +1304,134 @@ sgz_status sgz_overview_stats_view_host(sgz_plan *plan, const sgz_overview_stat_
     if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(cols) * p.P * 4, hipMemcpyDeviceToHost, s));
     if (stats_out) SGZ_HIP(hipMemcpyAsync(stats_out, d_out, size_t(cols) * column * sizeof(sgz_overview_stat_record), hipMemcpyDeviceToHost, s));
     if (means_out) SGZ_HIP(hipMemcpyAsync(means_out, d_means, size_t(cols) * column * sizeof(float), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)
+    return SGZ_OK;
+}
+
+// The power overview's render and host view (sgz.h, "The power overview"; overview_power.hip).  The slab loop has no K_B in it: per slab K_A
+// into p.d_mapped -- sgz_stage_mapped's call, late pixels completed, because nothing behind it would -- and the reduction with the open column
+// carried.  The slab is counted as the overview's (the same option, the same default), so that one setting cuts all three renders alike.
+}  // extern "C"
+sgz_status sgz::powerOverviewSupported(const Plan &p)
+{
+    if (isResonator(p)) return fail(SGZ_EUNSUPPORTED, "the power overview reduces transform magnitudes: RSNT plans are not supported");
+    if (p.cfg.channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the power overview reduces magnitudes: Phase mode's second plane is none");
+    return SGZ_OK;
+}
+sgz_status sgz::runOverviewPowerSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                      sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels,
+                                      hipStream_t s)
+{
+    Plan &p = plan->impl;
+    sgz_status st = SGZ_OK;
+    const size_t perFrameLines = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2, perFrame = size_t(p.C) * p.sides * p.P;
+    const long slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kOverviewSlabBytes / (perFrameLines * sizeof(float)))));
+    if ((st = ensureCap(&p.d_mapped, &p.mappedCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
+    for (long f0 = 0; f0 < frames; f0 += slab) {
+        const long nf = std::min(slab, frames - f0);
+        if ((st = runStft(p, d_planar + size_t(f0) * p.cfg.hop, channel_stride, nf, p.d_mapped, nullptr, nullptr, s)) != SGZ_OK) return st;
+        const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
+        const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
+        st = runOverviewPowerColumns(p, p.d_mapped, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, 0, d_carry,
+                                     d_rgba ? d_rgba + column * p.P * 4 : nullptr, d_power ? d_power + column * perFrame : nullptr,
+                                     d_levels ? d_levels + column * perFrame : nullptr, s);
+        if (st != SGZ_OK) return st;
+    }
+    return SGZ_OK;
+}
+extern "C" {
+sgz_status sgz_spectrogram_overview_power_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                                 uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels, void *stream)
+{
+    if (!plan || !d_planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!d_rgba && !d_power && !d_levels) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
+    sgz_status st = powerOverviewSupported(plan->impl);
+    if (st != SGZ_OK) return st;
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    if ((st = ensureCap(&p.d_ovpCarry, &p.ovpCarryCap, size_t(p.C) * p.sides * p.P * (sizeof(sgz_overview_power_record) / sizeof(float)))) != SGZ_OK) return st;
+    return runOverviewPowerSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, reinterpret_cast<sgz_overview_power_record *>(p.d_ovpCarry), d_rgba,
+                                 d_power, d_levels, reinterpret_cast<hipStream_t>(stream));
+}
+
+sgz_status sgz_spectrogram_overview_power_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                               uint8_t *rgba_out, sgz_overview_power_record *power_out, float *levels_out, sgz_timing *timing)
+{
+    if (!plan || !planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
+    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
+    for (uint32_t c = 0; c < num_channels; ++c)
+        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
+    sgz_status st = powerOverviewSupported(plan->impl);
+    if (st != SGZ_OK) return st;
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
+    const size_t columns = (size_t(frames) + k - 1) / k, records = columns * p.C * p.sides * p.P;
+    constexpr size_t recordFloats = sizeof(sgz_overview_power_record) / sizeof(float);
+    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
+    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, columns * p.P)) != SGZ_OK) return st;
+    if (power_out && (st = ensureCap(&p.d_hostOvPower, &p.hostOvPowerCap, records * recordFloats)) != SGZ_OK) return st;
+    if (levels_out && (st = ensureCap(&p.d_hostOvLevels, &p.hostOvLevelsCap, records)) != SGZ_OK) return st;
+    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
+    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
+    sgz_overview_power_record *d_power = power_out ? reinterpret_cast<sgz_overview_power_record *>(p.d_hostOvPower) : nullptr;
+    float *d_levels = levels_out ? p.d_hostOvLevels : nullptr;
+    st = sgz_spectrogram_overview_power_device(plan, p.d_hostAudio, stride, nsamples, k, d_rgba, d_power, d_levels, s);
+    if (st != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, columns * p.P * 4, hipMemcpyDeviceToHost, s));
+    if (power_out) SGZ_HIP(hipMemcpyAsync(power_out, d_power, records * sizeof(sgz_overview_power_record), hipMemcpyDeviceToHost, s));
+    if (levels_out) SGZ_HIP(hipMemcpyAsync(levels_out, d_levels, records * sizeof(float), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, frames);
+    return SGZ_OK;
+}
+
+// The view of kept power records from HOST records: only the range's columns are uploaded, into plan scratch, on the plan's own stream.
+sgz_status sgz_overview_power_view_host(sgz_plan *plan, const sgz_overview_power_record *power, size_t n, size_t x0, size_t x1, uint32_t out_columns,
+                                        uint8_t *rgba_out, sgz_overview_power_record *power_out, float *levels_out, sgz_timing *timing)
+{
+    if (!plan || !power) return fail(SGZ_EINVAL, "null argument");
+    uint64_t cols = 0;
+    sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols);
+    if (st != SGZ_OK) return st;
+    if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "sgz_overview_power_view_host: an image, the records, the levels or any of them");
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    constexpr size_t recordFloats = sizeof(sgz_overview_power_record) / sizeof(float);
+    const size_t column = size_t(p.C) * p.sides * p.P, m = x1 - x0;
+    if ((st = ensureCap(&p.d_ovpViewIn, &p.ovpViewInCap, m * column * recordFloats)) != SGZ_OK) return st;
+    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, size_t(cols) * p.P)) != SGZ_OK) return st;
+    if (power_out && (st = ensureCap(&p.d_hostOvPower, &p.hostOvPowerCap, size_t(cols) * column * recordFloats)) != SGZ_OK) return st;
+    if (levels_out && (st = ensureCap(&p.d_hostOvLevels, &p.hostOvLevelsCap, size_t(cols) * column)) != SGZ_OK) return st;
+    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
+    sgz_overview_power_record *d_in = reinterpret_cast<sgz_overview_power_record *>(p.d_ovpViewIn);
+    sgz_overview_power_record *d_out = power_out ? reinterpret_cast<sgz_overview_power_record *>(p.d_hostOvPower) : nullptr;
+    float *d_levels = levels_out ? p.d_hostOvLevels : nullptr;
+    SGZ_HIP(hipEventRecord(ev[0], s));
+    SGZ_HIP(hipMemcpyAsync(d_in, power + x0 * column, m * column * sizeof(sgz_overview_power_record), hipMemcpyHostToDevice, s));
+    SGZ_HIP(hipEventRecord(ev[1], s));
+    if ((st = runOverviewPowerView(p, d_in, m, size_t(cols), 0, d_rgba, d_out, d_levels, s)) != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(cols) * p.P * 4, hipMemcpyDeviceToHost, s));
+    if (power_out) SGZ_HIP(hipMemcpyAsync(power_out, d_out, size_t(cols) * column * sizeof(sgz_overview_power_record), hipMemcpyDeviceToHost, s));
+    if (levels_out) SGZ_HIP(hipMemcpyAsync(levels_out, d_levels, size_t(cols) * column * sizeof(float), hipMemcpyDeviceToHost, s));
     SGZ_HIP(hipEventRecord(ev[3], s));
     SGZ_HIP(hipStreamSynchronize(s));
     if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)

@@ -203,7 +203,8 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // Band sgz_band_record [ceil(chunk / m) + 1][channels] the band lane's.
 // Hist sgz_hist_record [ceil(chunk / m) + 1][channels] the histogram lane's.
 // OvStats sgz_overview_stat_record [columns][C][P] and OvMeans float [columns][C][P] the stats feed's, beside its OvImage.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kPcmOuts };
+// OvPower sgz_overview_power_record [columns][C][sides][P] and OvLevels float [columns][C][sides][P] the power feed's, beside its OvImage.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -315,6 +316,8 @@ struct PcmLane {
     size_t scratchCap = 0;
 };
 
+enum PcmOvKind { kOvPeaks, kOvStats, kOvPower };
+
 struct sgz_pcm_stream {
     sgz_spectrum_config cfg{};
     sgz_plan *plan = nullptr;
@@ -330,9 +333,11 @@ struct sgz_pcm_stream {
     // the overview inside the stream: the open column's V [pairs][P], its frame count and its k (meaningful while ovOpen > 0)
     float *d_ovCarry = nullptr;
     uint64_t ovOpen = 0; uint32_t ovK = 0;
-    // the open column is of one kind: ovStats -- it is the mean overview's, its records [pairs][P] in d_ovStatCarry (sgz.h, "The mean overview")
-    bool ovStats = false;
+    // the open column is of one kind (meaningful while ovOpen > 0): the peak hold's, the mean overview's -- its records [pairs][P] in
+    // d_ovStatCarry (sgz.h, "The mean overview") -- or the power overview's -- [pairs][sides][P] in d_ovPowerCarry ("The power overview")
+    PcmOvKind ovKind = kOvPeaks;
     sgz_overview_stat_record *d_ovStatCarry = nullptr;
+    sgz_overview_power_record *d_ovPowerCarry = nullptr;
     // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels]),
     // stereo-field (sgz_field_record [2][pairs]), histogram (sgz_hist_record [2][channels]), loudness and band (two halves of
     // <lane>CarryBytes(filter) * channels bytes), and the two filters
@@ -689,6 +694,7 @@ struct PcmColumnsPart {
         if (st != SGZ_OK) return st;
         s.ovOpen = pieceFlush ? 0 : t % k;
         s.ovK = k;
+        s.ovKind = kOvPeaks;
         return SGZ_OK;
     }
     sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
@@ -737,7 +743,7 @@ struct PcmStatsPart {
         if (st != SGZ_OK) return st;
         s.ovOpen = pieceFlush ? 0 : t % k;
         s.ovK = k;
-        s.ovStats = s.ovOpen != 0;
+        s.ovKind = kOvStats;
         return SGZ_OK;
     }
     sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
@@ -745,6 +751,56 @@ struct PcmStatsPart {
         sgz_status st = rgba ? sl.out[kOutOvImage].readBack(rgba + pcmImageBytes(s, done), pcmImageBytes(s, columns), rgbaPinned, s.back) : SGZ_OK;
         if (st == SGZ_OK && stats) st = sl.out[kOutOvStats].readBack(stats + records(s, done), records(s, columns) * sizeof(sgz_overview_stat_record), statsPinned, s.back);
         if (st == SGZ_OK && means) st = sl.out[kOutOvMeans].readBack(means + records(s, done), records(s, columns) * sizeof(float), meansPinned, s.back);
+        return st;
+    }
+};
+
+// sgz_pcm_stream_feed_overview_power's part: the columns of PcmColumnsPart from the power reduction -- K_A and the reduction slab by slab, no K_B:
+// the stream's decay state is neither read nor advanced, and there are no line results for a track lane to search (the feed refuses one)
+struct PcmPowerPart {
+    uint8_t *rgba; sgz_overview_power_record *power; float *levels;
+    uint32_t k; int flush;
+    uint64_t need;                                                // the columns the whole feed yields
+    bool rgbaPinned, powerPinned, levelsPinned;
+
+    static size_t records(const sgz_pcm_stream &s, uint64_t columns) { return pcmPeaksFloats(s, columns) * size_t(s.plan->impl.sides); }
+
+    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
+    {
+        if (!s.d_ovPowerCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovPowerCarry), records(s, 1) * sizeof(sgz_overview_power_record)));
+        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
+        const size_t columns = (s.maxFrames + k - 1) / k + 1;     // the most one piece can close (PcmColumnsPart::reserve)
+        sgz_status st = rgba ? sl.out[kOutOvImage].reserve(pcmImageBytes(s, columns), !rgbaPinned) : SGZ_OK;
+        if (st == SGZ_OK && power) st = sl.out[kOutOvPower].reserve(records(s, columns) * sizeof(sgz_overview_power_record), !powerPinned);
+        if (st == SGZ_OK && levels) st = sl.out[kOutOvLevels].reserve(records(s, columns) * sizeof(float), !levelsPinned);
+        return st;
+    }
+    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t, uint64_t frames, bool last, uint64_t *units) const
+    {
+        const int pieceFlush = flush && last;
+        const uint64_t t = s.ovOpen + frames;
+        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
+        uint8_t *d_rgba = rgba ? sl.out[kOutOvImage].as<uint8_t>() : nullptr;
+        sgz_overview_power_record *d_power = power ? sl.out[kOutOvPower].as<sgz_overview_power_record>() : nullptr;
+        float *d_levels = levels ? sl.out[kOutOvLevels].as<float>() : nullptr;
+        sgz_status st = SGZ_OK;
+        if (frames) {
+            st = runOverviewPowerSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovPowerCarry, d_rgba, d_power, d_levels,
+                                       s.compute);
+        } else if (*units) {                                       // no frame arrives and the open column is flushed
+            st = runOverviewPowerColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovPowerCarry, d_rgba, d_power, d_levels, s.compute);
+        }
+        if (st != SGZ_OK) return st;
+        s.ovOpen = pieceFlush ? 0 : t % k;
+        s.ovK = k;
+        s.ovKind = kOvPower;
+        return SGZ_OK;
+    }
+    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
+    {
+        sgz_status st = rgba ? sl.out[kOutOvImage].readBack(rgba + pcmImageBytes(s, done), pcmImageBytes(s, columns), rgbaPinned, s.back) : SGZ_OK;
+        if (st == SGZ_OK && power) st = sl.out[kOutOvPower].readBack(power + records(s, done), records(s, columns) * sizeof(sgz_overview_power_record), powerPinned, s.back);
+        if (st == SGZ_OK && levels) st = sl.out[kOutOvLevels].readBack(levels + records(s, done), records(s, columns) * sizeof(float), levelsPinned, s.back);
         return st;
     }
 };
@@ -807,7 +863,7 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry, (void *)s->d_ovPowerCarry}) if (p) (void)hipFree(p);
     for (PcmLane &l : s->lane)
         for (void *p : {l.d_carry, l.d_scratch}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
@@ -879,7 +935,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     SGZ_HIP(hipMemsetAsync(s->d_state, 0, pcmStateBytes(*s), s->compute));          // (in order behind whatever the last feed left there: nothing)
     SGZ_HIP(hipStreamSynchronize(s->compute));
     s->held = 0;
-    s->ovOpen = 0; s->ovStats = false;                                              // an open overview column, of either kind, is dropped
+    s->ovOpen = 0; s->ovKind = kOvPeaks;                                            // an open overview column, of any kind, is dropped
     for (int id = 0; id < kPcmSinks; ++id) s->sink(id).cursor = 0;                  // every lane's columns and the track's records start over; all stay armed
     for (PcmLane &l : s->lane) { l.open = 0; l.continued = false; l.index = 0; }    // open columns are dropped, the histories are zeros again and the samples count from 0
     return SGZ_OK;
@@ -891,8 +947,9 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     const auto t0 = PcmClock::now();
     if (!s) return fail(SGZ_EINVAL, "null stream");
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null pcm");
-    if (s->ovOpen) return fail(SGZ_EINVAL, s->ovStats ? "sgz_pcm_stream_feed: a mean overview's column is open -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first"
-                                                      : "sgz_pcm_stream_feed: an overview column is open -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
+    if (s->ovOpen) return fail(SGZ_EINVAL, s->ovKind == kOvPower ? "sgz_pcm_stream_feed: a power overview's column is open -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first"
+                                           : s->ovKind == kOvStats ? "sgz_pcm_stream_feed: a mean overview's column is open -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first"
+                                                                   : "sgz_pcm_stream_feed: an overview column is open -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
     const uint64_t need = sgz_pcm_stream_frames_for(s, nsamples);
     if (frames_out) *frames_out = need;
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
@@ -934,7 +991,8 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: null pcm");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
-    if (s->ovOpen && s->ovStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvPower) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a power overview's -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first");
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -968,7 +1026,8 @@ sgz_status sgz_pcm_stream_feed_overview_stats(sgz_pcm_stream *s, const void *pcm
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
     if (reinterpret_cast<uintptr_t>(stats_out) % alignof(sgz_overview_stat_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: stats_out is not aligned to 8 bytes");
-    if (s->ovOpen && !s->ovStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvPeaks) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvPower) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a power overview's -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first");
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -991,6 +1050,47 @@ sgz_status sgz_spectrogram_overview_stats_pcm(const sgz_spectrum_config *cfg, co
     return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
                       [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
                       [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_stats(s, pcm, nsamples, k, 1, rgba_out, stats_out, means_out, columns, &columns, timing); });
+}
+
+// ---- the power overview inside the stream (sgz.h, "The power overview") --------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_feed_overview_power(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush, uint8_t *rgba_out,
+                                              sgz_overview_power_record *power_out, float *levels_out, uint64_t capacity_columns, uint64_t *columns_out,
+                                              sgz_pcm_timing *timing)
+{
+    const auto t0 = PcmClock::now();
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: null pcm");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
+    if (reinterpret_cast<uintptr_t>(power_out) % alignof(sgz_overview_power_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: power_out is not aligned to 8 bytes");
+    if (sgz_status st = powerOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
+    if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the track lane is armed and a power feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
+    if (s->ovOpen && s->ovKind == kOvPeaks) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
+    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: k differs from the open column's -- flush or reset first");
+    uint64_t need = 0;
+    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
+    if (columns_out) *columns_out = need;
+    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: capacity_columns below what this feed yields (see *columns_out)");
+    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
+    PcmPowerPart part{rgba_out, power_out, levels_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && power_out && isPinnedHost(power_out),
+                      need && levels_out && isPinnedHost(levels_out)};
+    // (a feed without samples still has one piece when it flushes an open column)
+    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+}
+
+sgz_status sgz_spectrogram_overview_power_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                              const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
+                                              sgz_overview_power_record *power_out, float *levels_out, sgz_pcm_timing *timing)
+{
+    if (!cfg || !pcm) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
+    if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the power overview reduces transform magnitudes: RSNT plans are not supported");
+    if (cfg->channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the power overview reduces magnitudes: Phase mode's second plane is none");
+    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
+                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
+                      [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_power(s, pcm, nsamples, k, 1, rgba_out, power_out, levels_out, columns, &columns, timing); });
 }
 
 // ---- the lanes' calls ---------------------------------------------------------------------------------------------------------------------------

@@ -168,6 +168,11 @@ struct Plan {
     // sliced forms, the host forms' device copies of records and means, and the host view's copy of the range's source columns
     float *d_ovsCarry = nullptr, *d_ovsCarryCopy = nullptr, *d_ovsPartial = nullptr, *d_hostOvStats = nullptr, *d_hostOvMeans = nullptr, *d_ovsViewIn = nullptr;
     size_t ovsCarryCap = 0, ovsCarryCopyCap = 0, ovsPartialCap = 0, hostOvStatsCap = 0, hostOvMeansCap = 0, ovsViewInCap = 0;
+    // the power overview (overview_power.hip; sgz_spectrogram_overview_power_device / _host, the power views), 8 floats per
+    // sgz_overview_power_record: the open column's records [pairs][sides][P], their snapshot, the partial records of the sliced forms, the host
+    // forms' device copies of records and levels, and the host view's copy of the range's source columns
+    float *d_ovpCarry = nullptr, *d_ovpCarryCopy = nullptr, *d_ovpPartial = nullptr, *d_hostOvPower = nullptr, *d_hostOvLevels = nullptr, *d_ovpViewIn = nullptr;
+    size_t ovpCarryCap = 0, ovpCarryCopyCap = 0, ovpPartialCap = 0, hostOvPowerCap = 0, hostOvLevelsCap = 0, ovpViewInCap = 0;
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;

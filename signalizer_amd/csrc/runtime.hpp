@@ -120,6 +120,21 @@ sgz_status runOverviewStatsView(Plan &p, const sgz_overview_stat_record *d_src, 
 sgz_status runOverviewStatsSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
                                  int flush, sgz_overview_stat_record *d_carry, float *d_state, uint8_t *d_rgba, sgz_overview_stat_record *d_stats,
                                  float *d_means, hipStream_t stream, const SlabTrack *track = nullptr);
+// the power overview (overview_power.hip): the same twins on sgz_overview_power_record over the mapped magnitudes d_mapped
+// [frames][pairs][sides][P], with the levels as the third output; the arguments are sgz_stage_overview_power's / sgz_stage_overview_power_view's,
+// checked by the caller
+sgz_status runOverviewPowerColumns(Plan &p, const float *d_mapped, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                                   sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels,
+                                   hipStream_t stream);
+sgz_status runOverviewPowerView(Plan &p, const sgz_overview_power_record *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba,
+                                sgz_overview_power_record *d_powerOut, float *d_levels, hipStream_t stream);
+// ... and its slab loop (api.hip): per slab K_A into p.d_mapped with the late pixels completed, then the reduction with the open column carried
+// in d_carry; no K_B and no decay state.  What sgz_spectrogram_overview_power_device and sgz_pcm_stream share; the caller has refused Phase and
+// RSNT plans (powerOverviewSupported)
+sgz_status powerOverviewSupported(const Plan &p);
+sgz_status runOverviewPowerSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                 sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels,
+                                 hipStream_t stream);
 // the column lanes' reductions (wave, level, true-peak, loudness, stereo-field, band): column_lanes.hpp
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
