@@ -84,6 +84,12 @@ extern "C" {
  *  sgz_spectrogram_overview_power_pcm.  No existing entry point or struct changed and the suite pins 5; the new refusals on existing calls,
  *  a feed of another kind while a power column is open, cannot be reached without the new calls.  A binding that needs them looks the
  *  symbols up.)
+ * (5, later: the cross overview -- sgz_overview_cross_record, sgz_overview_cross_reading, sgz_plan_set_cross_edges, sgz_stage_overview_cross,
+ *  sgz_spectrogram_overview_cross_device / _host, the host helpers sgz_overview_cross_quantise, sgz_overview_cross_fold,
+ *  sgz_overview_cross_readout, sgz_overview_cross_unit and sgz_cross_edges_octave and, on the PCM stream, sgz_pcm_stream_set_cross_edges,
+ *  sgz_pcm_stream_feed_overview_cross and sgz_spectrogram_overview_cross_pcm.  No existing entry point or struct changed and the suite pins 5;
+ *  the new refusals on existing calls, a feed of another kind while a cross column is open, cannot be reached without the new calls.  A
+ *  binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -779,6 +785,109 @@ sgz_status sgz_pcm_stream_feed_overview_power(sgz_pcm_stream *s, const void *pcm
 sgz_status sgz_spectrogram_overview_power_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                               const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
                                               sgz_overview_power_record *power_out, float *levels_out, sgz_pcm_timing *timing);
+
+/* The cross overview: band power, coherence and phase per column -- how the two channels of a pair relate per frequency.  The level lane's
+ * correlation is one number per column over all frequencies; Phase mode's second plane is a per-frame cancellation value; and the coherence of
+ * a single frame is identically 1, so no pass over the other outputs can produce it.  The quantity needed is the averaged cross-spectrum: per
+ * column of k frames and per frequency band, the sums of |L|^2, |R|^2, Re(L conj R) and Im(L conj R).  One such record yields the band levels
+ * of L, R, Mid and Side (a 1/3-octave analyser of a file or of a selection), the magnitude-squared coherence, the inter-channel phase and the
+ * per-band correlation.  It reduces the complex bins at the one place where both channels' exist: what sgz_stage_bins writes on an
+ * SGZ_CH_PHASE plan.  There is no image (the reference has no colour rule for coherence) and no device-side view: the host fold is the zoom.
+ * Definition (exact, no tolerance).
+ *   plan       FFT algorithm, SGZ_CH_PHASE, N = 2^n (n >= 3).  Every other plan: SGZ_EUNSUPPORTED before the device is touched.  B[f][p][j],
+ *              j = 0 .. N, is what sgz_stage_bins writes for frame f and pair p, as float2 (re, im).
+ *   bins       1 <= k <= N/2 - 2 are admitted; DC, Nyquist and the Q3-halved entry N/2 - 1 are left out.  L = B[k], R = B[N - k].
+ *   bands      a band table is bands + 1 uint32 edges with 1 <= edges[0] <= ... <= edges[bands] <= N/2 - 1 and 1 <= bands <= 4096.  Band b
+ *              holds the bins edges[b] <= k < edges[b + 1]; an empty band is allowed.  sgz_plan_set_cross_edges sets it on the plan: a host
+ *              call that copies to the device and may synchronise.  A table that breaks the rule: SGZ_EINVAL, the old table stays.  Calls on
+ *              a plan without a table: SGZ_EINVAL.
+ *   quantiser  on one bin of one frame, floats lr, li, rr, ri; the scale is s = 2^(62 - 2n), so that 2^60 is the power of a full-scale sine on
+ *              a bin under a rectangular full window.  If any of the four floats is not finite the bin takes no part and is counted in
+ *              skipped.  Otherwise, in fp64 with nothing contracted (each product exact, each sum rounded once):
+ *              a = lr lr + li li;  b = rr rr + ri ri;  c = lr rr + li ri;  d = li rr - lr ri  -- L conj R, the phase positive where L leads;
+ *              u = x s (exact);  q = rint(clamp(u, +-(2^63 - 2^10))), ties to even, as an int64.  q_a and q_b are never negative.
+ *              Resolution: 2^-60 in power, -180 dB re a full-scale sine.  Range: 8 in power, +9 dB.
+ *   record     one sgz_overview_cross_record per (column, pair, band): ll, rr, re, im the 128-bit sums of q_a, q_b, q_c, q_d, low word then
+ *              high word, re and im in two's complement; count the bin-frames summed; skipped the bin-frames left out.  Columns and their
+ *              frames are counted by sgz_overview_step, as in the three other overviews.
+ *   fold       every field adds (the sums modulo 2^128): associative and commutative.  Slices, calls, slabs, feeds and chunk sizes all
+ *              give the same bytes; a coarser column is the fold of the finer ones; a band whose range is the union of adjacent finer
+ *              bands is the fold of their records.
+ *   readout    host only, fp64, into sgz_overview_cross_reading.  S -> double as in the power overview: hi 2^64 + lo; the signed sums
+ *              through their magnitude.  With A, B, C, D the doubles of ll, rr, re, im:  ll = A / count 2^-60, and likewise rr, re, im --
+ *              the mean per bin-frame in unit power;  mid = max(0, S_ll + S_rr + 2 S_re) / count 2^-62, the integer sum exact in 128 bits;
+ *              side the same with -2 S_re;  coherence = min(1, (C^2 + D^2) / (A B));  phase = atan2(D, C);  correlation = C / sqrt(A B).
+ *              count == 0: every plane is NaN.  A B == 0: coherence and correlation are NaN.
+ *   unit       sgz_overview_cross_unit returns (invSize N / 2)^2 in fp64 from the plan's host scalars: ll * unit is the mean of
+ *              |X invSize|^2, the amplitude scale the render's dB map sees.  A band level is mean * (edges[b + 1] - edges[b]) * unit.
+ *  sgz_stage_overview_cross   d_bins float2 [frames][pairs][N + 1], whatever floats they are; d_carry [pairs][bands], d_cross
+ *                      [columns][pairs][bands].  Refusals (SGZ_EINVAL, nothing launched or written), slices (0, 1 .. 64, identical bytes),
+ *                      asynchrony, the carry snapshot and "only the documented bytes are written" as for sgz_stage_overview_power.
+ *  sgz_spectrogram_overview_cross_device / _host   slabs of frames (SGZ_OPT_OVERVIEW_SLAB, or by default as many whole frames as keep the
+ *                      slab's bins within 256 MiB of plan scratch): per slab K_A's bins into that scratch (sgz_stage_bins' call), then the
+ *                      reduction with the open column carried; the bytes do not depend on the slab.  No K_B, no decay state.  Fewer samples
+ *                      than a window: SGZ_SKIPPED_FRAME, nothing written.
+ *  sgz_overview_cross_quantise   host, no GPU: `count` bins of a transform of size 2^n -> q [count][4] (a, b, c, d) and skipped [count]
+ *                      (1: the bin takes no part, its q are 0).
+ *  sgz_overview_cross_fold    host, no GPU: columns [x0, x1) of in [n][pairs][bands] into cols = min(out_columns, x1 - x0) columns of out
+ *                      by the boundary rule of sgz_overview_view_columns and, when coarse_edges is not NULL, into coarse_bands bands: every
+ *                      coarse edge must be one of the fine `edges`, else SGZ_EINVAL.  out [cols][pairs][coarse_bands or bands].  edges may
+ *                      be NULL when coarse_edges is.  SGZ_EINVAL, nothing written: a null argument, what sgz_overview_view_columns refuses,
+ *                      a folded count above 2^64 - 1.
+ *  sgz_overview_cross_readout host, no GPU: `count` records into `count` readings.
+ *  sgz_cross_edges_octave     host, no GPU, all in fp64: the centres f_j = 1000 2^(j / b) for every integer j with f_lo <= f_j <= f_hi,
+ *                      b = bands_per_octave in 1 .. 48;  edges[i] = clamp(ceil(f_j 2^(-1 / (2 b)) N / sample_rate), 1, N/2 - 1), the last
+ *                      edge from the last centre with 2^(+1 / (2 b)).  *bands = the centres found; SGZ_EINVAL when there is none or
+ *                      capacity < *bands + 1.  centres [*bands] may be NULL. */
+typedef struct sgz_overview_cross_record {
+    uint64_t ll[2], rr[2];  /* the 128-bit sums of q_a and q_b, low word then high word                  */
+    uint64_t re[2], im[2];  /* ... of q_c and q_d, two's complement                                      */
+    uint64_t count;         /* bin-frames summed                                                         */
+    uint64_t skipped;       /* bin-frames left out: one of their four floats was not finite              */
+} sgz_overview_cross_record;               /* 80 bytes, 8-aligned */
+typedef struct sgz_overview_cross_reading {
+    double ll, rr, mid, side, re, im;       /* means per bin-frame in unit power */
+    double coherence, phase, correlation;
+} sgz_overview_cross_reading;
+#ifdef __cplusplus
+static_assert(sizeof(sgz_overview_cross_record) == 80 && alignof(sgz_overview_cross_record) == 8, "sgz_overview_cross_record: 80 bytes, 8-aligned");
+static_assert(offsetof(sgz_overview_cross_record, ll) == 0 && offsetof(sgz_overview_cross_record, rr) == 16 && offsetof(sgz_overview_cross_record, re) == 32 &&
+              offsetof(sgz_overview_cross_record, im) == 48 && offsetof(sgz_overview_cross_record, count) == 64 && offsetof(sgz_overview_cross_record, skipped) == 72,
+              "sgz_overview_cross_record: offsets");
+static_assert(sizeof(sgz_overview_cross_reading) == 72, "sgz_overview_cross_reading: nine doubles");
+#endif
+sgz_status sgz_plan_set_cross_edges(sgz_plan *plan, const uint32_t *edges /*HOST [bands + 1]*/, uint32_t bands);
+sgz_status sgz_stage_overview_cross(sgz_plan *plan, const float *d_bins, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                                    sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, void *stream);
+sgz_status sgz_spectrogram_overview_cross_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                                 sgz_overview_cross_record *d_cross, void *stream);
+sgz_status sgz_spectrogram_overview_cross_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                               sgz_overview_cross_record *cross_out, sgz_timing *timing);
+sgz_status sgz_overview_cross_quantise(uint32_t n, const float *lr, const float *li, const float *rr, const float *ri, size_t count,
+                                       int64_t *q /*[count][4]*/, uint8_t *skipped /*[count]*/);
+sgz_status sgz_overview_cross_fold(const sgz_overview_cross_record *in, size_t n, size_t pairs, const uint32_t *edges /*or NULL*/, uint32_t bands,
+                                   size_t x0, size_t x1, uint32_t out_columns, const uint32_t *coarse_edges /*or NULL*/, uint32_t coarse_bands,
+                                   sgz_overview_cross_record *out);
+sgz_status sgz_overview_cross_readout(const sgz_overview_cross_record *in, size_t count, sgz_overview_cross_reading *out);
+sgz_status sgz_overview_cross_unit(const sgz_plan *plan, double *unit);
+sgz_status sgz_cross_edges_octave(double sample_rate, uint32_t N, uint32_t bands_per_octave, double f_lo, double f_hi, uint32_t *edges,
+                                  uint32_t capacity, uint32_t *bands, double *centres /*or NULL*/);
+/*  sgz_pcm_stream_set_cross_edges / sgz_pcm_stream_feed_overview_cross / sgz_spectrogram_overview_cross_pcm   the overview inside
+ *                      sgz_pcm_stream with this reduction: the concatenated columns of all feeds equal sgz_spectrogram_overview_cross_host of
+ *                      the converted planar floats, byte for byte, however the stream is cut.  The band table is set on the stream
+ *                      (SGZ_EINVAL while a cross column is open); a cross feed neither reads nor advances the stream's decay state.  An open
+ *                      column is of one of four kinds (peak hold, mean, power, cross): a feed of another kind while a column is open is
+ *                      refused with SGZ_EINVAL, consumes nothing and names the flush call that closes it in sgz_last_error.
+ *                      sgz_pcm_stream_columns_for, sgz_pcm_stream_open_frames and sgz_pcm_stream_reset serve all four kinds.  A cross feed
+ *                      with the track lane armed is refused (SGZ_EINVAL): it has no line results to search.  The seven column lanes run in
+ *                      it as in any feed.  Streams that are not SGZ_CH_PHASE FFT streams: SGZ_EUNSUPPORTED. */
+sgz_status sgz_pcm_stream_set_cross_edges(sgz_pcm_stream *s, const uint32_t *edges /*HOST [bands + 1]*/, uint32_t bands);
+sgz_status sgz_pcm_stream_feed_overview_cross(sgz_pcm_stream *s, const void *pcm /*HOST*/, size_t nsamples, uint32_t k, int flush,
+                                              sgz_overview_cross_record *cross_out, uint64_t capacity_columns, uint64_t *columns_out,
+                                              sgz_pcm_timing *timing);
+sgz_status sgz_spectrogram_overview_cross_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                              const uint32_t *channel_map, size_t nsamples, const uint32_t *edges, uint32_t bands, uint32_t k,
+                                              sgz_overview_cross_record *cross_out, sgz_pcm_timing *timing);
 
 /* The waveform lane: a minimum and a maximum per screen column and channel of a file's samples -- what every editor draws beside the
  * spectrogram lane -- reduced on the device from the planar floats the streamed render has there anyway.  The reference has no counterpart

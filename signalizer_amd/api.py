@@ -261,6 +261,9 @@ EXPORTS = [
     "sgz_stage_overview_power", "sgz_spectrogram_overview_power_device", "sgz_spectrogram_overview_power_host", "sgz_stage_overview_power_view",
     "sgz_overview_power_view_host", "sgz_overview_power_quantise", "sgz_overview_power_fold", "sgz_overview_power_readout",
     "sgz_overview_power_levels", "sgz_pcm_stream_feed_overview_power", "sgz_spectrogram_overview_power_pcm",
+    "sgz_plan_set_cross_edges", "sgz_stage_overview_cross", "sgz_spectrogram_overview_cross_device", "sgz_spectrogram_overview_cross_host",
+    "sgz_overview_cross_quantise", "sgz_overview_cross_fold", "sgz_overview_cross_readout", "sgz_overview_cross_unit", "sgz_cross_edges_octave",
+    "sgz_pcm_stream_set_cross_edges", "sgz_pcm_stream_feed_overview_cross", "sgz_spectrogram_overview_cross_pcm",
     "sgz_stage_wave_columns", "sgz_wave_columns_limits", "sgz_pcm_stream_set_waveform", "sgz_pcm_stream_waveform_for",
     "sgz_pcm_stream_waveform_state", "sgz_pcm_stream_flush_waveform",
     "sgz_track_peak_values", "sgz_stage_track_peaks_values", "sgz_pcm_stream_set_track", "sgz_pcm_stream_track_for", "sgz_pcm_stream_track_state",
@@ -382,6 +385,15 @@ def lib() -> C.CDLL:
     L.sgz_overview_power_fold.argtypes = [vp, sz, sz, sz, sz, u32, vp]
     L.sgz_overview_power_readout.argtypes = [vp, sz, vp, vp, vp, vp]
     L.sgz_overview_power_levels.argtypes = [vp, vp, sz, vp]
+    L.sgz_plan_set_cross_edges.argtypes = [vp, vp, u32]
+    L.sgz_stage_overview_cross.argtypes = [vp, vp, sz, u32, u32, C.c_int, u32, vp, vp, vp]
+    L.sgz_spectrogram_overview_cross_device.argtypes = [vp, vp, sz, sz, u32, vp, vp]
+    L.sgz_spectrogram_overview_cross_host.argtypes = [vp, vp, u32, sz, u32, vp, C.POINTER(Timing)]
+    L.sgz_overview_cross_quantise.argtypes = [u32, vp, vp, vp, vp, sz, vp, vp]
+    L.sgz_overview_cross_fold.argtypes = [vp, sz, sz, vp, u32, sz, sz, u32, vp, u32, vp]
+    L.sgz_overview_cross_readout.argtypes = [vp, sz, vp]
+    L.sgz_overview_cross_unit.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sgz_cross_edges_octave.argtypes = [C.c_double, u32, u32, C.c_double, C.c_double, vp, u32, C.POINTER(u32), vp]
     L.sgz_comm_unique_id.argtypes = [vp]
     L.sgz_comm_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.sgz_comm_destroy.argtypes = [vp]
@@ -522,6 +534,9 @@ def lib() -> C.CDLL:
     L.sgz_spectrogram_overview_stats_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, vp, C.POINTER(PcmTiming)]
     L.sgz_pcm_stream_feed_overview_power.argtypes = [vp, vp, sz, u32, C.c_int, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
     L.sgz_spectrogram_overview_power_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, vp, C.POINTER(PcmTiming)]
+    L.sgz_pcm_stream_set_cross_edges.argtypes = [vp, vp, u32]
+    L.sgz_pcm_stream_feed_overview_cross.argtypes = [vp, vp, sz, u32, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
+    L.sgz_spectrogram_overview_cross_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, vp, u32, u32, vp, C.POINTER(PcmTiming)]
     L.sgz_stage_level_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
     L.sgz_level_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.sgz_level_columns_limits.restype = None
@@ -886,6 +901,80 @@ def overview_power_readout(records: np.ndarray):
     rms, lo, hi = (np.zeros(records.shape, np.float32) for _ in range(3))
     check(lib().sgz_overview_power_readout(_np_ptr(records), records.size, _np_ptr(ms), _np_ptr(rms), _np_ptr(lo), _np_ptr(hi)))
     return ms, rms, lo, hi
+
+
+# sgz_overview_cross_record (sgz.h, "The cross overview"): 80 bytes, 8-aligned; every sum = (low word, high word) of a 128-bit integer, re and
+# im in two's complement.  On the device a record is ten int64 words of a torch tensor [..., 10]; cross_from_device turns such a tensor into a
+# numpy array of this dtype.  OVERVIEW_CROSS_READING_DTYPE: sgz_overview_cross_reading, nine doubles
+OVERVIEW_CROSS_DTYPE = np.dtype({"names": ["ll", "rr", "re", "im", "count", "skipped"],
+                                 "formats": [("<u8", (2,)), ("<u8", (2,)), ("<u8", (2,)), ("<u8", (2,)), "<u8", "<u8"],
+                                 "offsets": [0, 16, 32, 48, 64, 72], "itemsize": 80})
+OVERVIEW_CROSS_READING_DTYPE = np.dtype([(name, "<f8") for name in ("ll", "rr", "mid", "side", "re", "im", "coherence", "phase", "correlation")])
+
+
+def cross_from_device(t) -> np.ndarray:
+    """cuda int64 [..., 10] (records as the cross calls write them) -> numpy OVERVIEW_CROSS_DTYPE [...]"""
+    h = np.ascontiguousarray(t.cpu().numpy())
+    return h.view(OVERVIEW_CROSS_DTYPE).reshape(h.shape[:-1])
+
+
+def cross_to_device(records: np.ndarray, device):
+    """numpy OVERVIEW_CROSS_DTYPE [...] -> cuda int64 [..., 10]"""
+    import torch
+    r = np.ascontiguousarray(records, OVERVIEW_CROSS_DTYPE)
+    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 10).copy()).to(device)
+
+
+def _edges(edges) -> np.ndarray:
+    e = np.ascontiguousarray(edges, np.uint32)
+    assert e.ndim == 1 and e.size >= 2, e.shape
+    return e
+
+
+def overview_cross_quantise(n: int, lr, li, rr, ri):
+    """sgz_overview_cross_quantise (host, no GPU): the bins (lr + i li, rr + i ri), float32 [...], of a transform of size 2^n -> (q int64
+    [..., 4]: a, b, c, d of the cross overview's definition, skipped bool [...])"""
+    lr, li, rr, ri = (np.ascontiguousarray(a, np.float32) for a in (lr, li, rr, ri))
+    assert lr.shape == li.shape == rr.shape == ri.shape
+    q = np.zeros((*lr.shape, 4), np.int64)
+    skipped = np.zeros(lr.shape, np.uint8)
+    check(lib().sgz_overview_cross_quantise(n, _np_ptr(lr), _np_ptr(li), _np_ptr(rr), _np_ptr(ri), lr.size, _np_ptr(q), _np_ptr(skipped)))
+    return q, skipped.astype(bool)
+
+
+def overview_cross_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None, edges=None, coarse_edges=None) -> np.ndarray:
+    """sgz_overview_cross_fold (host, no GPU): OVERVIEW_CROSS_DTYPE records [n, pairs, bands], source columns [x0, x1) -> [min(out_columns,
+    x1 - x0), pairs, bands]; with coarse_edges (every one of them among the fine `edges`) also over bands -> [..., pairs, len(coarse_edges) - 1]"""
+    records = np.ascontiguousarray(records, OVERVIEW_CROSS_DTYPE)
+    assert records.ndim == 3, records.shape
+    n, pairs, bands = (int(v) for v in records.shape)
+    x1 = n if x1 is None else x1
+    e = _edges(edges) if edges is not None else None
+    assert e is None or e.size == bands + 1
+    ce = _edges(coarse_edges) if coarse_edges is not None else None
+    out = np.zeros((overview_view_columns(n, x0, x1, out_columns), pairs, bands if ce is None else ce.size - 1), OVERVIEW_CROSS_DTYPE)
+    check(lib().sgz_overview_cross_fold(_np_ptr(records), n, pairs, _np_ptr(e) if e is not None else None, bands, x0, x1, out_columns,
+                                        _np_ptr(ce) if ce is not None else None, ce.size - 1 if ce is not None else 0, _np_ptr(out)))
+    return out
+
+
+def overview_cross_readout(records: np.ndarray) -> np.ndarray:
+    """sgz_overview_cross_readout (host, no GPU): OVERVIEW_CROSS_DTYPE records [...] -> OVERVIEW_CROSS_READING_DTYPE [...]: the planes ll, rr,
+    mid, side, re, im (means per bin-frame in unit power), coherence, phase, correlation"""
+    records = np.ascontiguousarray(records, OVERVIEW_CROSS_DTYPE)
+    out = np.zeros(records.shape, OVERVIEW_CROSS_READING_DTYPE)
+    check(lib().sgz_overview_cross_readout(_np_ptr(records), records.size, _np_ptr(out)))
+    return out
+
+
+def cross_edges_octave(sample_rate: float, N: int, bands_per_octave: int, f_lo: float, f_hi: float, capacity: int = 4097):
+    """sgz_cross_edges_octave (host, no GPU): (edges uint32 [bands + 1], centres float64 [bands]) of the fractional-octave bands whose centres
+    1000 * 2^(j / bands_per_octave) lie in [f_lo, f_hi]"""
+    edges = np.zeros(capacity, np.uint32)
+    centres = np.zeros(max(capacity - 1, 1), np.float64)
+    bands = C.c_uint32(0)
+    check(lib().sgz_cross_edges_octave(sample_rate, N, bands_per_octave, f_lo, f_hi, _np_ptr(edges), capacity, C.byref(bands), _np_ptr(centres)))
+    return edges[:bands.value + 1].copy(), centres[:bands.value].copy()
 
 
 class Plan:
@@ -1323,6 +1412,62 @@ class Plan:
         check(lib().sgz_overview_power_levels(self.h, _np_ptr(records), records.size // (self.C * self.sides * self.P), _np_ptr(levels)))
         return levels
 
+    # the cross overview: the complex bins of an SGZ_CH_PHASE plan reduced to band sums of |L|^2, |R|^2 and L conj R per column
+    def set_cross_edges(self, edges) -> None:
+        """sgz_plan_set_cross_edges: the band table, uint32 [bands + 1]; band b holds the bins edges[b] <= k < edges[b + 1]"""
+        e = _edges(edges)
+        check(lib().sgz_plan_set_cross_edges(self.h, _np_ptr(e), e.size - 1))
+        self.cross_bands = int(e.size - 1)
+
+    def overview_cross_unit(self) -> float:
+        unit = C.c_double(0.0)
+        check(lib().sgz_overview_cross_unit(self.h, C.byref(unit)))
+        return unit.value
+
+    def overview_cross_columns(self, bins, k: int, held: int = 0, flush: bool = True, slices: int = 0, carry=None, stream=None):
+        """sgz_stage_overview_cross: bins -- cuda float32 [frames, pairs, N + 1, 2] (stage_bins of a Phase plan); carry -- cuda int64 [pairs,
+        bands, 10], the open column's records (read when held > 0, written when frames stay open).  Returns (cuda records int64 [columns,
+        pairs, bands, 10] -- see cross_from_device --, frames left open)."""
+        import torch
+        assert bins.is_cuda and bins.dtype == torch.float32 and bins.is_contiguous()
+        assert tuple(bins.shape[1:]) == (self.C, self.N + 1, 2), tuple(bins.shape)
+        B = self.cross_bands
+        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * B * 10)
+        frames = bins.shape[0]
+        columns, held_out = overview_step(k, held, frames, flush)
+        out = torch.empty((max(columns, 1), self.C, B, 10), dtype=torch.int64, device=bins.device)               # (never a NULL pointer)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview_cross(self.h, bins.data_ptr(), frames, k, held, int(bool(flush)), slices,
+                                             carry.data_ptr() if carry is not None else None, out.data_ptr(), s))
+        return out[:columns], held_out
+
+    def overview_cross(self, planar, k: int, stream=None):
+        """The cross overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_cross_host -> (records OVERVIEW_CROSS_DTYPE
+        [columns, C, bands], timing dict).  planar a cuda tensor: sgz_spectrogram_overview_cross_device, asynchronous -> cuda records int64
+        [columns, C, bands, 10].  Fewer samples than a window: None."""
+        B = self.cross_bands
+        if isinstance(planar, np.ndarray):
+            planar = np.ascontiguousarray(planar, np.float32)
+            nch, S = planar.shape
+            columns = -(-self.num_frames(S) // k)
+            out = np.zeros((max(columns, 1), self.C, B), OVERVIEW_CROSS_DTYPE)
+            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
+            t = Timing()
+            st = check(lib().sgz_spectrogram_overview_cross_host(self.h, ptrs, nch, S, k, _np_ptr(out), C.byref(t)))
+            if st == SGZ_SKIPPED_FRAME:
+                return None
+            return out[:columns], {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+        import torch
+        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
+        S = planar.shape[1]
+        columns = -(-self.num_frames(S) // k)
+        out = torch.empty((max(columns, 1), self.C, B, 10), dtype=torch.int64, device=planar.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = check(lib().sgz_spectrogram_overview_cross_device(self.h, planar.data_ptr(), planar.stride(0), S, k, out.data_ptr(), s))
+        if st == SGZ_SKIPPED_FRAME:
+            return None
+        return out[:columns]
+
     def colour_table(self, pair: int) -> np.ndarray:
         out = np.zeros((NUM_SPEC_COLOURS + 1, 3), np.float32)
         check(lib().sgz_plan_get_colour_table(self.h, pair, _np_ptr(out)))
@@ -1658,6 +1803,35 @@ class PcmStream:
         check(st)
         assert c == cols, (c, cols)
         return (rgba[:cols] if want_rgba else None), (power[:cols] if want_power else None), (levels[:cols] if want_levels else None), t.asdict()
+
+    def set_cross_edges(self, edges) -> None:
+        """sgz_pcm_stream_set_cross_edges: the band table of the stream's cross feeds, uint32 [bands + 1]"""
+        e = _edges(edges)
+        check(lib().sgz_pcm_stream_set_cross_edges(self.h, _np_ptr(e), e.size - 1))
+        self.cross_bands = int(e.size - 1)
+
+    def feed_overview_cross_into(self, pcm, nsamples: int, k: int, flush: bool, cross, capacity_columns: int, timing: bool = True):
+        """the C call as it is: (status, columns_out, PcmTiming or None); cross: a numpy array, a host torch tensor or None"""
+        t, c = PcmTiming() if timing else None, C.c_uint64(0)
+        st = lib().sgz_pcm_stream_feed_overview_cross(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
+                                                      _buf_ptr(cross) if cross is not None else None, capacity_columns, C.byref(c),
+                                                      C.byref(t) if timing else None)
+        return st, int(c.value), t
+
+    def feed_overview_cross(self, pcm, k: int, flush: bool = False, nsamples: int | None = None):
+        """Feeds nsamples (default: all of pcm; pcm None: none) into the cross overview at k frames per column and returns the columns that
+        closed: (records OVERVIEW_CROSS_DTYPE [columns, pairs, bands], timing dict).  The stream's decay state is neither read nor advanced."""
+        if pcm is None:
+            n = 0
+        else:
+            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+            n = nbytes // self.frame_bytes if nsamples is None else nsamples
+        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
+        cross = np.zeros((max(cols, 1), self.cfg.num_pairs, getattr(self, "cross_bands", 1)), OVERVIEW_CROSS_DTYPE)
+        st, c, t = self.feed_overview_cross_into(pcm if n else None, n, k, flush, cross, cols)
+        check(st)
+        assert c == cols, (c, cols)
+        return cross[:cols], t.asdict()
 
     # the seven column lanes (waveform, level, truepeak, loudness, field, band, hist): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
@@ -2223,6 +2397,25 @@ def overview_power_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_ma
     if st == SGZ_SKIPPED_FRAME:
         cols = 0
     return st, (rgba[:cols] if want_rgba else None), (power[:cols] if want_power else None), (levels[:cols] if want_levels else None), t.asdict()
+
+
+def overview_cross_pcm(cfg, pcm, fmt: int, src_channels: int, edges, k: int, channel_map=None, nsamples: int | None = None):
+    """One-shot cross overview of an interleaved PCM buffer (sgz_spectrogram_overview_cross_pcm): (status, records OVERVIEW_CROSS_DTYPE
+    [columns, pairs, bands], timing dict); SGZ_SKIPPED_FRAME and no records for fewer samples than a window"""
+    c = _as_config(cfg)
+    e = _edges(edges)
+    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
+    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
+    cols = -(-F // k) if k else 0
+    cross = np.zeros((max(cols, 1), c.num_pairs, e.size - 1), OVERVIEW_CROSS_DTYPE)
+    m, mp = _channel_map(channel_map)
+    t = PcmTiming()
+    st = check(lib().sgz_spectrogram_overview_cross_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, _np_ptr(e), e.size - 1, k,
+                                                        _np_ptr(cross), C.byref(t)))
+    if st == SGZ_SKIPPED_FRAME:
+        cols = 0
+    return st, cross[:cols], t.asdict()
 
 
 def render_spectrogram_pcm(cfg, pcm, fmt: int, src_channels: int, channel_map=None, nsamples: int | None = None, want_lines: bool = False):

@@ -49,7 +49,8 @@ Plan::~Plan()
     for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq, (void *)d_ovLines, (void *)d_ovCarry,
                     (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks, (void *)d_ovViewIn, (void *)d_ovsCarry,
                     (void *)d_ovsCarryCopy, (void *)d_ovsPartial, (void *)d_hostOvStats, (void *)d_hostOvMeans, (void *)d_ovsViewIn,
-                    (void *)d_ovpCarry, (void *)d_ovpCarryCopy, (void *)d_ovpPartial, (void *)d_hostOvPower, (void *)d_hostOvLevels, (void *)d_ovpViewIn})
+                    (void *)d_ovpCarry, (void *)d_ovpCarryCopy, (void *)d_ovpPartial, (void *)d_hostOvPower, (void *)d_hostOvLevels, (void *)d_ovpViewIn,
+                    (void *)d_crossTables, (void *)d_ovcCarry, (void *)d_ovcCarryCopy, (void *)d_ovcPartial, (void *)d_hostOvCross, (void *)d_ovcBins})
         if (p) (void)hipFree(p);
     for (void *e : hostEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *e : shardEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
@@ -1435,6 +1436,86 @@ sgz_status sgz_overview_power_view_host(sgz_plan *plan, const sgz_overview_power
     SGZ_HIP(hipEventRecord(ev[3], s));
     SGZ_HIP(hipStreamSynchronize(s));
     if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)
+    return SGZ_OK;
+}
+
+// The cross overview's render (sgz.h, "The cross overview"; overview_cross.hip).  Per slab K_A's complex bins into plan scratch -- runStft as
+// sgz_stage_bins calls it -- and the reduction with the open column carried.  No K_B, no decay state.  The slab is SGZ_OPT_OVERVIEW_SLAB's, or as
+// many whole frames as keep the slab's bins within 256 MiB.
+}  // extern "C"
+constexpr size_t kCrossSlabBytes = size_t(256) << 20;
+sgz_status sgz::runOverviewCrossSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                      sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t s)
+{
+    Plan &p = plan->impl;
+    sgz_status st = SGZ_OK;
+    const size_t perFrame = size_t(p.C) * (size_t(p.N) + 1) * 2, perColumn = size_t(p.C) * p.crossBands;     // floats of a frame's bins; records of a column
+    const long slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kCrossSlabBytes / (perFrame * sizeof(float)))));
+    if ((st = ensureCap(&p.d_ovcBins, &p.ovcBinsCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
+    for (long f0 = 0; f0 < frames; f0 += slab) {
+        const long nf = std::min(slab, frames - f0);
+        if ((st = runStft(p, d_planar + size_t(f0) * p.cfg.hop, channel_stride, nf, nullptr, p.d_ovcBins, nullptr, s)) != SGZ_OK) return st;
+        const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
+        const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
+        st = runOverviewCrossColumns(p, p.d_ovcBins, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, 0, d_carry,
+                                     d_cross ? d_cross + column * perColumn : nullptr, s);
+        if (st != SGZ_OK) return st;
+    }
+    return SGZ_OK;
+}
+static sgz_status crossOverviewReady(sgz_plan *plan)
+{
+    if (sgz_status st = crossOverviewSupported(plan->impl); st != SGZ_OK) return st;
+    if (!plan->impl.crossBands) return fail(SGZ_EINVAL, "overview cross: the plan has no band table (sgz_plan_set_cross_edges)");
+    return SGZ_OK;
+}
+extern "C" {
+sgz_status sgz_spectrogram_overview_cross_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                                 sgz_overview_cross_record *d_cross, void *stream)
+{
+    if (!plan || !d_planar || !d_cross) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    sgz_status st = crossOverviewReady(plan);
+    if (st != SGZ_OK) return st;
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    if ((st = ensureCap(&p.d_ovcCarry, &p.ovcCarryCap, size_t(p.C) * p.crossBands * (sizeof(sgz_overview_cross_record) / sizeof(float)))) != SGZ_OK) return st;
+    return runOverviewCrossSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, reinterpret_cast<sgz_overview_cross_record *>(p.d_ovcCarry), d_cross,
+                                 reinterpret_cast<hipStream_t>(stream));
+}
+
+sgz_status sgz_spectrogram_overview_cross_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                               sgz_overview_cross_record *cross_out, sgz_timing *timing)
+{
+    if (!plan || !planar || !cross_out) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
+    for (uint32_t c = 0; c < num_channels; ++c)
+        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
+    sgz_status st = crossOverviewReady(plan);
+    if (st != SGZ_OK) return st;
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
+    const size_t columns = (size_t(frames) + k - 1) / k, records = columns * p.C * p.crossBands;
+    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
+    if ((st = ensureCap(&p.d_hostOvCross, &p.hostOvCrossCap, records * (sizeof(sgz_overview_cross_record) / sizeof(float)))) != SGZ_OK) return st;
+    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
+    sgz_overview_cross_record *d_cross = reinterpret_cast<sgz_overview_cross_record *>(p.d_hostOvCross);
+    st = sgz_spectrogram_overview_cross_device(plan, p.d_hostAudio, stride, nsamples, k, d_cross, s);
+    if (st != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    SGZ_HIP(hipMemcpyAsync(cross_out, d_cross, records * sizeof(sgz_overview_cross_record), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, frames);
     return SGZ_OK;
 }
 

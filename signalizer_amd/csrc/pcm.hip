@@ -204,7 +204,8 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // Hist sgz_hist_record [ceil(chunk / m) + 1][channels] the histogram lane's.
 // OvStats sgz_overview_stat_record [columns][C][P] and OvMeans float [columns][C][P] the stats feed's, beside its OvImage.
 // OvPower sgz_overview_power_record [columns][C][sides][P] and OvLevels float [columns][C][sides][P] the power feed's, beside its OvImage.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kPcmOuts };
+// OvCross sgz_overview_cross_record [columns][C][bands] the cross feed's.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutOvCross, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -316,7 +317,7 @@ struct PcmLane {
     size_t scratchCap = 0;
 };
 
-enum PcmOvKind { kOvPeaks, kOvStats, kOvPower };
+enum PcmOvKind { kOvPeaks, kOvStats, kOvPower, kOvCross };
 
 struct sgz_pcm_stream {
     sgz_spectrum_config cfg{};
@@ -334,10 +335,12 @@ struct sgz_pcm_stream {
     float *d_ovCarry = nullptr;
     uint64_t ovOpen = 0; uint32_t ovK = 0;
     // the open column is of one kind (meaningful while ovOpen > 0): the peak hold's, the mean overview's -- its records [pairs][P] in
-    // d_ovStatCarry (sgz.h, "The mean overview") -- or the power overview's -- [pairs][sides][P] in d_ovPowerCarry ("The power overview")
+    // d_ovStatCarry (sgz.h, "The mean overview") --, the power overview's -- [pairs][sides][P] in d_ovPowerCarry ("The power overview") -- or the
+    // cross overview's -- [pairs][bands] in d_ovCrossCarry, by the band table of the stream's plan ("The cross overview")
     PcmOvKind ovKind = kOvPeaks;
     sgz_overview_stat_record *d_ovStatCarry = nullptr;
     sgz_overview_power_record *d_ovPowerCarry = nullptr;
+    sgz_overview_cross_record *d_ovCrossCarry = nullptr;
     // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels]),
     // stereo-field (sgz_field_record [2][pairs]), histogram (sgz_hist_record [2][channels]), loudness and band (two halves of
     // <lane>CarryBytes(filter) * channels bytes), and the two filters
@@ -805,6 +808,46 @@ struct PcmPowerPart {
     }
 };
 
+// sgz_pcm_stream_feed_overview_cross's part: K_A's complex bins and the cross reduction slab by slab, no K_B: the stream's decay state is neither
+// read nor advanced, and there are no line results for a track lane to search (the feed refuses one).  The carry was made with the band table
+struct PcmCrossPart {
+    sgz_overview_cross_record *cross;
+    uint32_t k; int flush;
+    uint64_t need;                                                // the columns the whole feed yields
+    bool crossPinned;
+
+    static size_t records(const sgz_pcm_stream &s, uint64_t columns) { return size_t(columns) * s.cfg.num_pairs * s.plan->impl.crossBands; }
+
+    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
+    {
+        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
+        const size_t columns = (s.maxFrames + k - 1) / k + 1;     // the most one piece can close (PcmColumnsPart::reserve)
+        return sl.out[kOutOvCross].reserve(records(s, columns) * sizeof(sgz_overview_cross_record), !crossPinned);
+    }
+    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t, uint64_t frames, bool last, uint64_t *units) const
+    {
+        const int pieceFlush = flush && last;
+        const uint64_t t = s.ovOpen + frames;
+        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
+        sgz_overview_cross_record *d_cross = need ? sl.out[kOutOvCross].as<sgz_overview_cross_record>() : nullptr;
+        sgz_status st = SGZ_OK;
+        if (frames) {
+            st = runOverviewCrossSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovCrossCarry, d_cross, s.compute);
+        } else if (*units) {                                       // no frame arrives and the open column is flushed
+            st = runOverviewCrossColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovCrossCarry, d_cross, s.compute);
+        }
+        if (st != SGZ_OK) return st;
+        s.ovOpen = pieceFlush ? 0 : t % k;
+        s.ovK = k;
+        s.ovKind = kOvCross;
+        return SGZ_OK;
+    }
+    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
+    {
+        return sl.out[kOutOvCross].readBack(cross + records(s, done), records(s, columns) * sizeof(sgz_overview_cross_record), crossPinned, s.back);
+    }
+};
+
 // what the two one-shot calls share: a stream with no more device and pinned memory than the buffer needs, SGZ_SKIPPED_FRAME where nothing
 // comes out, the feed, and the wall time around all of it.  units(s): what the feed will yield; feed(s, units): the feed call
 template <typename Units, typename Feed>
@@ -863,7 +906,7 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry, (void *)s->d_ovPowerCarry}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry, (void *)s->d_ovPowerCarry, (void *)s->d_ovCrossCarry}) if (p) (void)hipFree(p);
     for (PcmLane &l : s->lane)
         for (void *p : {l.d_carry, l.d_scratch}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
@@ -947,6 +990,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     const auto t0 = PcmClock::now();
     if (!s) return fail(SGZ_EINVAL, "null stream");
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null pcm");
+    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: a cross overview's column is open -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
     if (s->ovOpen) return fail(SGZ_EINVAL, s->ovKind == kOvPower ? "sgz_pcm_stream_feed: a power overview's column is open -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first"
                                            : s->ovKind == kOvStats ? "sgz_pcm_stream_feed: a mean overview's column is open -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first"
                                                                    : "sgz_pcm_stream_feed: an overview column is open -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
@@ -993,6 +1037,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
     if (s->ovOpen && s->ovKind == kOvStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
     if (s->ovOpen && s->ovKind == kOvPower) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a power overview's -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a cross overview's -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -1028,6 +1073,7 @@ sgz_status sgz_pcm_stream_feed_overview_stats(sgz_pcm_stream *s, const void *pcm
     if (reinterpret_cast<uintptr_t>(stats_out) % alignof(sgz_overview_stat_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: stats_out is not aligned to 8 bytes");
     if (s->ovOpen && s->ovKind == kOvPeaks) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
     if (s->ovOpen && s->ovKind == kOvPower) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a power overview's -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a cross overview's -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -1067,6 +1113,7 @@ sgz_status sgz_pcm_stream_feed_overview_power(sgz_pcm_stream *s, const void *pcm
     if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the track lane is armed and a power feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
     if (s->ovOpen && s->ovKind == kOvPeaks) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
     if (s->ovOpen && s->ovKind == kOvStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the open column is a cross overview's -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -1091,6 +1138,61 @@ sgz_status sgz_spectrogram_overview_power_pcm(const sgz_spectrum_config *cfg, co
     return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
                       [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
                       [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_power(s, pcm, nsamples, k, 1, rgba_out, power_out, levels_out, columns, &columns, timing); });
+}
+
+// ---- the cross overview inside the stream (sgz.h, "The cross overview") --------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_set_cross_edges(sgz_pcm_stream *s, const uint32_t *edges, uint32_t bands)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (sgz_status st = crossOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
+    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_cross_edges: a cross overview's column is open -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
+    if (sgz_status st = sgz_plan_set_cross_edges(s->plan, edges, bands); st != SGZ_OK) return st;
+    if (s->d_ovCrossCarry) { (void)hipFree(s->d_ovCrossCarry); s->d_ovCrossCarry = nullptr; }
+    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_ovCrossCarry), size_t(s->cfg.num_pairs) * bands * sizeof(sgz_overview_cross_record)));
+    return SGZ_OK;
+}
+
+sgz_status sgz_pcm_stream_feed_overview_cross(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush,
+                                              sgz_overview_cross_record *cross_out, uint64_t capacity_columns, uint64_t *columns_out,
+                                              sgz_pcm_timing *timing)
+{
+    const auto t0 = PcmClock::now();
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: null pcm");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (sgz_status st = crossOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
+    if (!s->plan->impl.crossBands || !s->d_ovCrossCarry) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the stream has no band table (sgz_pcm_stream_set_cross_edges)");
+    if (reinterpret_cast<uintptr_t>(cross_out) % alignof(sgz_overview_cross_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: cross_out is not aligned to 8 bytes");
+    if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the track lane is armed and a cross feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
+    if (s->ovOpen && s->ovKind == kOvPeaks) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
+    if (s->ovOpen && s->ovKind == kOvPower) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the open column is a power overview's -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first");
+    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: k differs from the open column's -- flush or reset first");
+    uint64_t need = 0;
+    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
+    if (columns_out) *columns_out = need;
+    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: capacity_columns below what this feed yields (see *columns_out)");
+    if (need && !cross_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: null cross_out");
+    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
+    PcmCrossPart part{cross_out, k, flush, need, need && isPinnedHost(cross_out)};
+    // (a feed without samples still has one piece when it flushes an open column)
+    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+}
+
+sgz_status sgz_spectrogram_overview_cross_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                              const uint32_t *channel_map, size_t nsamples, const uint32_t *edges, uint32_t bands, uint32_t k,
+                                              sgz_overview_cross_record *cross_out, sgz_pcm_timing *timing)
+{
+    if (!cfg || !pcm || !edges || !cross_out) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the cross overview reduces transform bins: RSNT plans are not supported");
+    if (cfg->channel_mode != SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the cross overview reduces the complex bins of both channels: only SGZ_CH_PHASE plans keep them");
+    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
+                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
+                      [&](sgz_pcm_stream *s, uint64_t columns) {
+                          if (sgz_status st = sgz_pcm_stream_set_cross_edges(s, edges, bands); st != SGZ_OK) return st;
+                          return sgz_pcm_stream_feed_overview_cross(s, pcm, nsamples, k, 1, cross_out, columns, &columns, timing);
+                      });
 }
 
 // ---- the lanes' calls ---------------------------------------------------------------------------------------------------------------------------

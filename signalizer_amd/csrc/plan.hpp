@@ -173,6 +173,14 @@ struct Plan {
     // forms' device copies of records and levels, and the host view's copy of the range's source columns
     float *d_ovpCarry = nullptr, *d_ovpCarryCopy = nullptr, *d_ovpPartial = nullptr, *d_hostOvPower = nullptr, *d_hostOvLevels = nullptr, *d_ovpViewIn = nullptr;
     size_t ovpCarryCap = 0, ovpCarryCopyCap = 0, ovpPartialCap = 0, hostOvPowerCap = 0, hostOvLevelsCap = 0, ovpViewInCap = 0;
+    // the cross overview (overview_cross.hip; sgz_plan_set_cross_edges, sgz_spectrogram_overview_cross_device / _host): the band table's edges
+    // [bands + 1] (empty: none set) and its device tables, 20 floats per sgz_overview_cross_record: the open column's records [pairs][bands], their
+    // snapshot, the partial records [slices][columns][pairs][pieces], the host form's device copy of the records, and a slab's complex bins
+    std::vector<uint32_t> crossEdges;
+    uint32_t crossBands = 0, crossTiles = 0, crossPieces = 0;
+    uint32_t *d_crossTables = nullptr;
+    float *d_ovcCarry = nullptr, *d_ovcCarryCopy = nullptr, *d_ovcPartial = nullptr, *d_hostOvCross = nullptr, *d_ovcBins = nullptr;
+    size_t ovcCarryCap = 0, ovcCarryCopyCap = 0, ovcPartialCap = 0, hostOvCrossCap = 0, ovcBinsCap = 0;
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;

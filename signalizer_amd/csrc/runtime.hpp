@@ -135,6 +135,16 @@ sgz_status powerOverviewSupported(const Plan &p);
 sgz_status runOverviewPowerSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
                                  sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels,
                                  hipStream_t stream);
+// the cross overview (overview_cross.hip): the reduction of the complex bins d_bins [frames][pairs][N + 1] float2 of an SGZ_CH_PHASE plan into
+// sgz_overview_cross_record [columns][pairs][bands] by the plan's band table; the arguments are sgz_stage_overview_cross', checked by the caller
+sgz_status crossOverviewSupported(const Plan &p);                 // FFT, SGZ_CH_PHASE, N = 2^n: everything else SGZ_EUNSUPPORTED
+sgz_status runOverviewCrossColumns(Plan &p, const float *d_bins, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                                   sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t stream);
+// ... and its slab loop (api.hip): per slab K_A's complex bins into plan scratch (sgz_stage_bins' call), then the reduction with the open
+// column carried in d_carry; no K_B and no decay state.  What sgz_spectrogram_overview_cross_device and sgz_pcm_stream share; the caller has
+// checked the plan (crossOverviewSupported) and its band table
+sgz_status runOverviewCrossSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                 sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t stream);
 // the column lanes' reductions (wave, level, true-peak, loudness, stereo-field, band): column_lanes.hpp
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
