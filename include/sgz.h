@@ -90,6 +90,11 @@ extern "C" {
  *  sgz_pcm_stream_feed_overview_cross and sgz_spectrogram_overview_cross_pcm.  No existing entry point or struct changed and the suite pins 5;
  *  the new refusals on existing calls, a feed of another kind while a cross column is open, cannot be reached without the new calls.  A
  *  binding that needs them looks the symbols up.)
+ * (5, later: the flux overview -- sgz_overview_flux_record, sgz_stage_overview_flux, sgz_spectrogram_overview_flux_device / _host, the host
+ *  helpers sgz_overview_flux_quantise, sgz_overview_flux_fold, sgz_overview_flux_readout and sgz_overview_flux_hz and, on the PCM stream,
+ *  sgz_pcm_stream_feed_overview_flux and sgz_spectrogram_overview_flux_pcm.  No existing entry point or struct changed and the suite pins 5;
+ *  the new refusals on existing calls, a feed of another kind while a flux column is open, cannot be reached without the new calls.  A
+ *  binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -888,6 +893,100 @@ sgz_status sgz_pcm_stream_feed_overview_cross(sgz_pcm_stream *s, const void *pcm
 sgz_status sgz_spectrogram_overview_cross_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                               const uint32_t *channel_map, size_t nsamples, const uint32_t *edges, uint32_t bands, uint32_t k,
                                               sgz_overview_cross_record *cross_out, sgz_pcm_timing *timing);
+
+/* The flux overview: onset strength, centroid and spread of k frames per column -- the two curves a file view draws on top of a spectrogram:
+ * a novelty curve with the strongest onset of each column, and a brightness line.  Every other lane and overview reduces one pixel, sample
+ * or band over time; this one reduces along the frequency axis and compares a frame with the frame before it, which no host can do from what
+ * the other overviews return (they fold frames first).  It reads the mapped magnitudes at the boundary the power overview reads them.
+ * Definition (exact, no tolerance).  M[f][p][s][i] are the mapped magnitudes of frame f, pair p, side s < sides, pixel i < P as in the power
+ * overview: what sgz_stage_mapped writes, bit for bit (completed values on channel-split plans).  sides is 2 for Separate / MidSide and 1
+ * otherwise; width = pairs * sides records per column.  Columns and their frames are counted by sgz_overview_step.
+ *   quantiser  a(x) = rint(min((double)|x| * 2^30, 2^34)) as a uint64.  The product is exact; ties go to even; +inf clamps.  A NaN gives 0
+ *              and marks its frame.  Resolution 2^-30 in amplitude; the clamp is at |x| = 16.
+ *   per frame and (pair, side)   A = sum_i a_i;  M1 = sum_i i a_i;  M2 = sum_i i^2 a_i;  F = sum_i max(0, a_i(f) - a_i(f - 1)) with integer
+ *              subtraction (the half-wave rectified L1 flux), F = 0 for a frame without a predecessor.  The predecessor is the previous
+ *              frame of the same (pair, side), whatever column it fell in.  With P <= 2^20: F < 2^54 and M2 < 2^94 per frame, and every
+ *              sum stays below 2^128 over 2^32 frames.
+ *   record     per (column, pair, side) one sgz_overview_flux_record: amp, mom1, mom2, flux = the low and the high word of the 128-bit sums
+ *              of A, M1, M2 and F over the column's frames; flux_max the greatest F of the column; flux_at the absolute index of the first
+ *              frame that attains it (UINT64_MAX when count == 0); count the frames; nans the frames with at least one NaN pixel.
+ *   fold       field-wise: sums and counts add; of (flux_max, flux_at) the greater flux_max wins, at equal flux_max the smaller flux_at.
+ *              All of it is associative and commutative: every cut (runs, slices, calls, slabs, feeds) gives the same bytes, and a coarser
+ *              column is exactly the fold of the finer ones.
+ *   readout    host, fp64, nothing contracted, in this order.  A 128-bit sum s becomes S(s) = (double)s[1] * 2^64 + (double)s[0] (the power
+ *              overview's rule).  mean amplitude = S(amp) / ((double)count * (double)P) * 2^-30;  centroid c = S(mom1) / S(amp), in pixels;
+ *              spread = sqrt(max(0, S(mom2) / S(amp) - c * c));  mean flux = S(flux) / (double)count * 2^-30;  relative flux = S(flux) /
+ *              S(amp).  NaN: the mean amplitude and the mean flux when count == 0; the centroid, the spread and the relative flux when amp
+ *              == 0 (which count == 0 implies).
+ * There is no image and no device-side view: the host fold is the zoom, as in the cross overview.
+ *  sgz_stage_overview_flux   d_mapped float [frames][pairs][sides][P], whatever floats they are; first_frame the absolute index of its frame
+ *                      0.  d_prev float [pairs][sides][P] holds the frame before d_mapped[0]: NULL -- the first frame has no predecessor;
+ *                      otherwise the call reads it and then overwrites it with its own last frame (frames > 0), so that calls chain through
+ *                      it as they chain through d_carry, one sgz_overview_flux_record [pairs][sides].  A call may read and write the same
+ *                      buffers (the carry-snapshot rule of the other stage calls); d_prev must not overlap d_mapped.  d_flux [columns][pairs]
+ *                      [sides] receives the columns that close.  Refusals (SGZ_EINVAL, nothing launched or written): what
+ *                      sgz_overview_step refuses, slices above 64, a NULL d_flux when a column closes, a NULL d_carry that would be read
+ *                      or written, d_mapped / d_prev not 4-byte or d_carry / d_flux not 8-byte aligned.  slices (0: automatic, 1 .. 64:
+ *                      identical bytes), asynchrony and "only the documented bytes are written" as for sgz_stage_overview_power.
+ *  sgz_spectrogram_overview_flux_device / _host   slabs of frames (SGZ_OPT_OVERVIEW_SLAB, or by default the overview's frame count): per
+ *                      slab K_A into plan scratch (sgz_stage_mapped's call), then the reduction, with the open column and the previous
+ *                      frame carried in plan scratch; the bytes do not depend on the slab.  Frames count from 0.  No K_B, no decay state.
+ *                      SGZ_CH_PHASE and RSNT plans: SGZ_EUNSUPPORTED before the device is touched.  Fewer samples than a window:
+ *                      SGZ_SKIPPED_FRAME, nothing written.
+ *  sgz_overview_flux_quantise   host, no GPU: a of n floats by the definition (0 for a NaN).
+ *  sgz_overview_flux_fold     host, no GPU: columns [x0, x1) of in [n][width] into cols = min(out_columns, x1 - x0) columns of out by the
+ *                      boundary rule of sgz_overview_view_columns.  SGZ_EINVAL, nothing written: a null argument, width == 0, what
+ *                      sgz_overview_view_columns refuses, a folded count or nans above 2^32 - 1.
+ *  sgz_overview_flux_readout  host, no GPU: `count` records of rows of `pixels` pixels into the five planes of the readout; any may be NULL,
+ *                      not all; pixels >= 1 where the mean amplitude is wanted.
+ *  sgz_overview_flux_hz       host, no GPU: n fractional pixels (a centroid) into Hz by linear interpolation of
+ *                      sgz_plan_get_mapped_frequencies in fp64: with i = floor(x), hz = f[i] + (x - i) * (f[i + 1] - f[i]); x <= 0 gives
+ *                      f[0], x >= P - 1 gives f[P - 1], a NaN stays a NaN. */
+typedef struct sgz_overview_flux_record {
+    uint64_t amp[2];    /* low word, high word of the 128-bit sum of A over the column's frames   */
+    uint64_t mom1[2];   /* ... of M1 = sum_i i a_i                                                */
+    uint64_t mom2[2];   /* ... of M2 = sum_i i^2 a_i                                              */
+    uint64_t flux[2];   /* ... of F                                                               */
+    uint64_t flux_max;  /* the greatest F of the column                                           */
+    uint64_t flux_at;   /* absolute index of the first frame that attains it; UINT64_MAX: none    */
+    uint32_t count;     /* frames                                                                 */
+    uint32_t nans;      /* frames with at least one NaN pixel                                     */
+} sgz_overview_flux_record;                /* 88 bytes, 8-aligned */
+#ifdef __cplusplus
+static_assert(sizeof(sgz_overview_flux_record) == 88 && alignof(sgz_overview_flux_record) == 8, "sgz_overview_flux_record: 88 bytes, 8-aligned");
+static_assert(offsetof(sgz_overview_flux_record, amp) == 0 && offsetof(sgz_overview_flux_record, mom1) == 16 && offsetof(sgz_overview_flux_record, mom2) == 32 &&
+              offsetof(sgz_overview_flux_record, flux) == 48 && offsetof(sgz_overview_flux_record, flux_max) == 64 && offsetof(sgz_overview_flux_record, flux_at) == 72 &&
+              offsetof(sgz_overview_flux_record, count) == 80 && offsetof(sgz_overview_flux_record, nans) == 84, "sgz_overview_flux_record: offsets");
+#endif
+sgz_status sgz_stage_overview_flux(sgz_plan *plan, const float *d_mapped, size_t frames, uint32_t k, uint32_t held, int flush, uint64_t first_frame,
+                                   uint32_t slices, float *d_prev /*or NULL*/, sgz_overview_flux_record *d_carry, sgz_overview_flux_record *d_flux, void *stream);
+sgz_status sgz_spectrogram_overview_flux_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                                sgz_overview_flux_record *d_flux, void *stream);
+sgz_status sgz_spectrogram_overview_flux_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                              sgz_overview_flux_record *flux_out, sgz_timing *timing);
+sgz_status sgz_overview_flux_quantise(const float *x, size_t n, uint64_t *a);
+sgz_status sgz_overview_flux_fold(const sgz_overview_flux_record *in, size_t n, size_t width, size_t x0, size_t x1, uint32_t out_columns,
+                                  sgz_overview_flux_record *out);
+sgz_status sgz_overview_flux_readout(const sgz_overview_flux_record *in, size_t count, uint32_t pixels, double *mean_amplitude, double *centroid,
+                                     double *spread, double *mean_flux, double *relative_flux);
+sgz_status sgz_overview_flux_hz(const sgz_plan *plan, const double *pixel, size_t n, double *hz);
+/*  sgz_pcm_stream_feed_overview_flux / sgz_spectrogram_overview_flux_pcm   the overview inside sgz_pcm_stream with this reduction: the
+ *                      concatenated columns of all feeds equal sgz_spectrogram_overview_flux_host of the converted planar floats, byte for
+ *                      byte, however the stream is cut.  The stream keeps the previous frame across feeds, and flux_at counts every frame
+ *                      the stream has completed since it was made or reset, whichever kind of feed consumed it.  After
+ *                      sgz_pcm_stream_reset, and after any feed of another kind that consumed frames, the next flux feed starts without a
+ *                      predecessor: its first frame has F = 0.  A flux feed neither reads nor advances the stream's decay state.  An open
+ *                      column is of one of five kinds (peak hold, mean, power, cross, flux): a feed of another kind while a column is open
+ *                      is refused with SGZ_EINVAL, consumes nothing and names the flush call that closes it in sgz_last_error.
+ *                      sgz_pcm_stream_columns_for, sgz_pcm_stream_open_frames and sgz_pcm_stream_reset serve all five kinds.  A flux feed
+ *                      with the track lane armed is refused (SGZ_EINVAL): it has no line results to search.  The seven column lanes run in
+ *                      it as in any feed.  Phase and RSNT streams: SGZ_EUNSUPPORTED. */
+sgz_status sgz_pcm_stream_feed_overview_flux(sgz_pcm_stream *s, const void *pcm /*HOST*/, size_t nsamples, uint32_t k, int flush,
+                                             sgz_overview_flux_record *flux_out, uint64_t capacity_columns, uint64_t *columns_out,
+                                             sgz_pcm_timing *timing);
+sgz_status sgz_spectrogram_overview_flux_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                             const uint32_t *channel_map, size_t nsamples, uint32_t k, sgz_overview_flux_record *flux_out,
+                                             sgz_pcm_timing *timing);
 
 /* The waveform lane: a minimum and a maximum per screen column and channel of a file's samples -- what every editor draws beside the
  * spectrogram lane -- reduced on the device from the planar floats the streamed render has there anyway.  The reference has no counterpart

@@ -264,6 +264,9 @@ EXPORTS = [
     "sgz_plan_set_cross_edges", "sgz_stage_overview_cross", "sgz_spectrogram_overview_cross_device", "sgz_spectrogram_overview_cross_host",
     "sgz_overview_cross_quantise", "sgz_overview_cross_fold", "sgz_overview_cross_readout", "sgz_overview_cross_unit", "sgz_cross_edges_octave",
     "sgz_pcm_stream_set_cross_edges", "sgz_pcm_stream_feed_overview_cross", "sgz_spectrogram_overview_cross_pcm",
+    "sgz_stage_overview_flux", "sgz_spectrogram_overview_flux_device", "sgz_spectrogram_overview_flux_host", "sgz_overview_flux_quantise",
+    "sgz_overview_flux_fold", "sgz_overview_flux_readout", "sgz_overview_flux_hz", "sgz_pcm_stream_feed_overview_flux",
+    "sgz_spectrogram_overview_flux_pcm",
     "sgz_stage_wave_columns", "sgz_wave_columns_limits", "sgz_pcm_stream_set_waveform", "sgz_pcm_stream_waveform_for",
     "sgz_pcm_stream_waveform_state", "sgz_pcm_stream_flush_waveform",
     "sgz_track_peak_values", "sgz_stage_track_peaks_values", "sgz_pcm_stream_set_track", "sgz_pcm_stream_track_for", "sgz_pcm_stream_track_state",
@@ -394,6 +397,13 @@ def lib() -> C.CDLL:
     L.sgz_overview_cross_readout.argtypes = [vp, sz, vp]
     L.sgz_overview_cross_unit.argtypes = [vp, C.POINTER(C.c_double)]
     L.sgz_cross_edges_octave.argtypes = [C.c_double, u32, u32, C.c_double, C.c_double, vp, u32, C.POINTER(u32), vp]
+    L.sgz_stage_overview_flux.argtypes = [vp, vp, sz, u32, u32, C.c_int, C.c_uint64, u32, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_flux_device.argtypes = [vp, vp, sz, sz, u32, vp, vp]
+    L.sgz_spectrogram_overview_flux_host.argtypes = [vp, vp, u32, sz, u32, vp, C.POINTER(Timing)]
+    L.sgz_overview_flux_quantise.argtypes = [vp, sz, vp]
+    L.sgz_overview_flux_fold.argtypes = [vp, sz, sz, sz, sz, u32, vp]
+    L.sgz_overview_flux_readout.argtypes = [vp, sz, u32, vp, vp, vp, vp, vp]
+    L.sgz_overview_flux_hz.argtypes = [vp, vp, sz, vp]
     L.sgz_comm_unique_id.argtypes = [vp]
     L.sgz_comm_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.sgz_comm_destroy.argtypes = [vp]
@@ -537,6 +547,8 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_set_cross_edges.argtypes = [vp, vp, u32]
     L.sgz_pcm_stream_feed_overview_cross.argtypes = [vp, vp, sz, u32, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
     L.sgz_spectrogram_overview_cross_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, vp, u32, u32, vp, C.POINTER(PcmTiming)]
+    L.sgz_pcm_stream_feed_overview_flux.argtypes = [vp, vp, sz, u32, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
+    L.sgz_spectrogram_overview_flux_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, C.POINTER(PcmTiming)]
     L.sgz_stage_level_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
     L.sgz_level_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.sgz_level_columns_limits.restype = None
@@ -923,6 +935,59 @@ def cross_to_device(records: np.ndarray, device):
     import torch
     r = np.ascontiguousarray(records, OVERVIEW_CROSS_DTYPE)
     return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 10).copy()).to(device)
+
+
+# sgz_overview_flux_record (sgz.h, "The flux overview"): 88 bytes, 8-aligned; every sum = (low word, high word) of a 128-bit integer.  On the
+# device a record is eleven int64 words of a torch tensor [..., 11]; flux_from_device turns such a tensor into a numpy array of this dtype
+OVERVIEW_FLUX_DTYPE = np.dtype({"names": ["amp", "mom1", "mom2", "flux", "flux_max", "flux_at", "count", "nans"],
+                                "formats": [("<u8", (2,)), ("<u8", (2,)), ("<u8", (2,)), ("<u8", (2,)), "<u8", "<u8", "<u4", "<u4"],
+                                "offsets": [0, 16, 32, 48, 64, 72, 80, 84], "itemsize": 88})
+
+
+def flux_from_device(t) -> np.ndarray:
+    """cuda int64 [..., 11] (records as the flux calls write them) -> numpy OVERVIEW_FLUX_DTYPE [...]"""
+    h = np.ascontiguousarray(t.cpu().numpy())
+    return h.view(OVERVIEW_FLUX_DTYPE).reshape(h.shape[:-1])
+
+
+def flux_to_device(records: np.ndarray, device):
+    """numpy OVERVIEW_FLUX_DTYPE [...] -> cuda int64 [..., 11]"""
+    import torch
+    r = np.ascontiguousarray(records, OVERVIEW_FLUX_DTYPE)
+    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 11).copy()).to(device)
+
+
+def overview_flux_quantise(x: np.ndarray) -> np.ndarray:
+    """sgz_overview_flux_quantise (host, no GPU): float32 [...] -> uint64 [...], a of the flux overview's definition (0 for a NaN)"""
+    x = np.ascontiguousarray(x, np.float32)
+    a = np.zeros(x.shape, np.uint64)
+    check(lib().sgz_overview_flux_quantise(_np_ptr(x), x.size, _np_ptr(a)))
+    return a
+
+
+def overview_flux_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_overview_flux_fold (host, no GPU): OVERVIEW_FLUX_DTYPE records [n, ...], source columns [x0, x1) -> [min(out_columns, x1 - x0), ...]"""
+    records = np.ascontiguousarray(records, OVERVIEW_FLUX_DTYPE)
+    n = int(records.shape[0])
+    x1 = n if x1 is None else x1
+    width = int(np.prod(records.shape[1:], dtype=np.int64))
+    out = np.zeros((overview_view_columns(n, x0, x1, out_columns), *records.shape[1:]), OVERVIEW_FLUX_DTYPE)
+    check(lib().sgz_overview_flux_fold(_np_ptr(records), n, width, x0, x1, out_columns, _np_ptr(out)))
+    return out
+
+
+def overview_flux_readout(records: np.ndarray, pixels: int):
+    """sgz_overview_flux_readout (host, no GPU): OVERVIEW_FLUX_DTYPE records [...] of rows of `pixels` pixels -> (mean amplitude, centroid in
+    pixels, spread in pixels, mean flux, relative flux), float64 planes of the same shape"""
+    records = np.ascontiguousarray(records, OVERVIEW_FLUX_DTYPE)
+    planes = [np.zeros(records.shape, np.float64) for _ in range(5)]
+    check(lib().sgz_overview_flux_readout(_np_ptr(records), records.size, pixels, *[_np_ptr(a) for a in planes]))
+    return tuple(planes)
+
+
+def overview_flux_hz(plan, pixel) -> np.ndarray:
+    """sgz_overview_flux_hz (host, no GPU): fractional pixels, float64 [...] -> Hz by linear interpolation of the plan's mapped frequencies"""
+    return plan.overview_flux_hz(pixel)
 
 
 def _edges(edges) -> np.ndarray:
@@ -1468,6 +1533,61 @@ class Plan:
             return None
         return out[:columns]
 
+    # the flux overview: the mapped magnitudes reduced along the axis to amplitude, two moments and the rectified difference against the frame before
+    def overview_flux_columns(self, mapped, k: int, held: int = 0, flush: bool = True, first_frame: int = 0, slices: int = 0, prev=None, carry=None,
+                              stream=None):
+        """sgz_stage_overview_flux: mapped -- cuda float32 [frames, pairs, sides, P]; prev -- cuda float32 [pairs, sides, P], the frame before
+        mapped[0] (None: the first frame has no predecessor), overwritten with mapped[-1]; carry -- cuda int64 [pairs, sides, 11], the open
+        column's records (read when held > 0, written when frames stay open).  Returns (cuda records int64 [columns, pairs, sides, 11] -- see
+        flux_from_device --, frames left open)."""
+        import torch
+        assert mapped.is_cuda and mapped.dtype == torch.float32 and mapped.is_contiguous()
+        assert tuple(mapped.shape[1:]) == (self.C, self.sides, self.P), tuple(mapped.shape)
+        assert prev is None or (prev.is_cuda and prev.dtype == torch.float32 and prev.is_contiguous() and prev.numel() == self.C * self.sides * self.P)
+        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * self.sides * 11)
+        frames = mapped.shape[0]
+        columns, held_out = overview_step(k, held, frames, flush)
+        out = torch.empty((max(columns, 1), self.C, self.sides, 11), dtype=torch.int64, device=mapped.device)       # (never a NULL pointer)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview_flux(self.h, mapped.data_ptr(), frames, k, held, int(bool(flush)), first_frame, slices,
+                                            prev.data_ptr() if prev is not None else None, carry.data_ptr() if carry is not None else None,
+                                            out.data_ptr(), s))
+        return out[:columns], held_out
+
+    def overview_flux(self, planar, k: int, stream=None):
+        """The flux overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_flux_host -> (records OVERVIEW_FLUX_DTYPE
+        [columns, C, sides], timing dict).  planar a cuda tensor: sgz_spectrogram_overview_flux_device, asynchronous -> cuda records int64
+        [columns, C, sides, 11].  Fewer samples than a window: None."""
+        if isinstance(planar, np.ndarray):
+            planar = np.ascontiguousarray(planar, np.float32)
+            nch, S = planar.shape
+            columns = -(-self.num_frames(S) // k)
+            out = np.zeros((max(columns, 1), self.C, self.sides), OVERVIEW_FLUX_DTYPE)
+            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
+            t = Timing()
+            st = check(lib().sgz_spectrogram_overview_flux_host(self.h, ptrs, nch, S, k, _np_ptr(out), C.byref(t)))
+            if st == SGZ_SKIPPED_FRAME:
+                return None
+            return out[:columns], {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+        import torch
+        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
+        S = planar.shape[1]
+        columns = -(-self.num_frames(S) // k)
+        out = torch.empty((max(columns, 1), self.C, self.sides, 11), dtype=torch.int64, device=planar.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = check(lib().sgz_spectrogram_overview_flux_device(self.h, planar.data_ptr(), planar.stride(0), S, k, out.data_ptr(), s))
+        if st == SGZ_SKIPPED_FRAME:
+            return None
+        return out[:columns]
+
+    def overview_flux_hz(self, pixel) -> np.ndarray:
+        """sgz_overview_flux_hz (host, no GPU): fractional pixels (a centroid), float64 [...] -> Hz, float64 [...], by linear interpolation of
+        the plan's mapped frequencies"""
+        x = np.ascontiguousarray(pixel, np.float64)
+        hz = np.zeros(x.shape, np.float64)
+        check(lib().sgz_overview_flux_hz(self.h, _np_ptr(x), x.size, _np_ptr(hz)))
+        return hz
+
     def colour_table(self, pair: int) -> np.ndarray:
         out = np.zeros((NUM_SPEC_COLOURS + 1, 3), np.float32)
         check(lib().sgz_plan_get_colour_table(self.h, pair, _np_ptr(out)))
@@ -1832,6 +1952,30 @@ class PcmStream:
         check(st)
         assert c == cols, (c, cols)
         return cross[:cols], t.asdict()
+
+    def feed_overview_flux_into(self, pcm, nsamples: int, k: int, flush: bool, flux, capacity_columns: int, timing: bool = True):
+        """the C call as it is: (status, columns_out, PcmTiming or None); flux: a numpy array, a host torch tensor or None"""
+        t, c = PcmTiming() if timing else None, C.c_uint64(0)
+        st = lib().sgz_pcm_stream_feed_overview_flux(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
+                                                     _buf_ptr(flux) if flux is not None else None, capacity_columns, C.byref(c),
+                                                     C.byref(t) if timing else None)
+        return st, int(c.value), t
+
+    def feed_overview_flux(self, pcm, k: int, flush: bool = False, nsamples: int | None = None):
+        """Feeds nsamples (default: all of pcm; pcm None: none) into the flux overview at k frames per column and returns the columns that
+        closed: (records OVERVIEW_FLUX_DTYPE [columns, pairs, sides], timing dict).  The stream's decay state is neither read nor advanced."""
+        if pcm is None:
+            n = 0
+        else:
+            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+            n = nbytes // self.frame_bytes if nsamples is None else nsamples
+        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
+        sides = 2 if self.cfg.channel_mode in (4, 5, 6) else 1
+        flux = np.zeros((max(cols, 1), self.cfg.num_pairs, sides), OVERVIEW_FLUX_DTYPE)
+        st, c, t = self.feed_overview_flux_into(pcm if n else None, n, k, flush, flux, cols)
+        check(st)
+        assert c == cols, (c, cols)
+        return flux[:cols], t.asdict()
 
     # the seven column lanes (waveform, level, truepeak, loudness, field, band, hist): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
@@ -2416,6 +2560,24 @@ def overview_cross_pcm(cfg, pcm, fmt: int, src_channels: int, edges, k: int, cha
     if st == SGZ_SKIPPED_FRAME:
         cols = 0
     return st, cross[:cols], t.asdict()
+
+
+def overview_flux_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None):
+    """One-shot flux overview of an interleaved PCM buffer (sgz_spectrogram_overview_flux_pcm): (status, records OVERVIEW_FLUX_DTYPE [columns,
+    pairs, sides], timing dict); SGZ_SKIPPED_FRAME and no records for fewer samples than a window"""
+    c = _as_config(cfg)
+    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
+    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
+    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
+    cols = -(-F // k) if k else 0
+    sides = 2 if c.channel_mode in (4, 5, 6) else 1
+    flux = np.zeros((max(cols, 1), c.num_pairs, sides), OVERVIEW_FLUX_DTYPE)
+    m, mp = _channel_map(channel_map)
+    t = PcmTiming()
+    st = check(lib().sgz_spectrogram_overview_flux_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(flux), C.byref(t)))
+    if st == SGZ_SKIPPED_FRAME:
+        cols = 0
+    return st, flux[:cols], t.asdict()
 
 
 def render_spectrogram_pcm(cfg, pcm, fmt: int, src_channels: int, channel_map=None, nsamples: int | None = None, want_lines: bool = False):

@@ -50,7 +50,8 @@ Plan::~Plan()
                     (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks, (void *)d_ovViewIn, (void *)d_ovsCarry,
                     (void *)d_ovsCarryCopy, (void *)d_ovsPartial, (void *)d_hostOvStats, (void *)d_hostOvMeans, (void *)d_ovsViewIn,
                     (void *)d_ovpCarry, (void *)d_ovpCarryCopy, (void *)d_ovpPartial, (void *)d_hostOvPower, (void *)d_hostOvLevels, (void *)d_ovpViewIn,
-                    (void *)d_crossTables, (void *)d_ovcCarry, (void *)d_ovcCarryCopy, (void *)d_ovcPartial, (void *)d_hostOvCross, (void *)d_ovcBins})
+                    (void *)d_crossTables, (void *)d_ovcCarry, (void *)d_ovcCarryCopy, (void *)d_ovcPartial, (void *)d_hostOvCross, (void *)d_ovcBins,
+                    (void *)d_ovfCarry, (void *)d_ovfCarryCopy, (void *)d_ovfPrev, (void *)d_ovfPrevCopy, (void *)d_ovfPartial, (void *)d_hostOvFlux})
         if (p) (void)hipFree(p);
     for (void *e : hostEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *e : shardEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
@@ -1513,6 +1514,89 @@ sgz_status sgz_spectrogram_overview_cross_host(sgz_plan *plan, const float *cons
     if (st != SGZ_OK) return st;
     SGZ_HIP(hipEventRecord(ev[2], s));
     SGZ_HIP(hipMemcpyAsync(cross_out, d_cross, records * sizeof(sgz_overview_cross_record), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, frames);
+    return SGZ_OK;
+}
+
+// The flux overview's render (sgz.h, "The flux overview"; overview_flux.hip).  The power overview's slab loop -- K_A into p.d_mapped with the late
+// pixels completed, counted by the same option and default -- with the flux reduction behind every slab: the open column in d_carry, the slab's
+// last frame in d_prev for the next slab's first.
+}  // extern "C"
+sgz_status sgz::fluxOverviewSupported(const Plan &p)
+{
+    if (isResonator(p)) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces transform magnitudes: RSNT plans are not supported");
+    if (p.cfg.channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces magnitudes: Phase mode's second plane is none");
+    return SGZ_OK;
+}
+sgz_status sgz::runOverviewFluxSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                     uint64_t firstFrame, float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry,
+                                     sgz_overview_flux_record *d_flux, hipStream_t s)
+{
+    Plan &p = plan->impl;
+    sgz_status st = SGZ_OK;
+    const size_t perFrameLines = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2, perFrame = size_t(p.C) * p.sides * p.P, perColumn = size_t(p.C) * p.sides;
+    const long slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kOverviewSlabBytes / (perFrameLines * sizeof(float)))));
+    if ((st = ensureCap(&p.d_mapped, &p.mappedCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
+    for (long f0 = 0; f0 < frames; f0 += slab) {
+        const long nf = std::min(slab, frames - f0);
+        if ((st = runStft(p, d_planar + size_t(f0) * p.cfg.hop, channel_stride, nf, p.d_mapped, nullptr, nullptr, s)) != SGZ_OK) return st;
+        const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
+        const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
+        st = runOverviewFluxColumns(p, p.d_mapped, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, firstFrame + uint64_t(f0), 0, d_prev,
+                                    prevValid || f0 > 0, d_carry, d_flux ? d_flux + column * perColumn : nullptr, s);
+        if (st != SGZ_OK) return st;
+    }
+    return SGZ_OK;
+}
+extern "C" {
+sgz_status sgz_spectrogram_overview_flux_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                                sgz_overview_flux_record *d_flux, void *stream)
+{
+    if (!plan || !d_planar || !d_flux) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (reinterpret_cast<uintptr_t>(d_flux) % alignof(sgz_overview_flux_record)) return fail(SGZ_EINVAL, "overview flux: d_flux is not aligned to 8 bytes");
+    sgz_status st = fluxOverviewSupported(plan->impl);
+    if (st != SGZ_OK) return st;
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    const size_t rows = size_t(p.C) * p.sides;
+    if ((st = ensureCap(&p.d_ovfCarry, &p.ovfCarryCap, rows * (sizeof(sgz_overview_flux_record) / sizeof(float)))) != SGZ_OK) return st;
+    if ((st = ensureCap(&p.d_ovfPrev, &p.ovfPrevCap, rows * p.P)) != SGZ_OK) return st;
+    return runOverviewFluxSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, 0, p.d_ovfPrev, false, reinterpret_cast<sgz_overview_flux_record *>(p.d_ovfCarry),
+                                d_flux, reinterpret_cast<hipStream_t>(stream));
+}
+
+sgz_status sgz_spectrogram_overview_flux_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                              sgz_overview_flux_record *flux_out, sgz_timing *timing)
+{
+    if (!plan || !planar || !flux_out) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
+    for (uint32_t c = 0; c < num_channels; ++c)
+        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
+    sgz_status st = fluxOverviewSupported(plan->impl);
+    if (st != SGZ_OK) return st;
+    if ((st = checkReady(plan)) != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
+    const size_t columns = (size_t(frames) + k - 1) / k, records = columns * p.C * p.sides;
+    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
+    if ((st = ensureCap(&p.d_hostOvFlux, &p.hostOvFluxCap, records * (sizeof(sgz_overview_flux_record) / sizeof(float)))) != SGZ_OK) return st;
+    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
+    sgz_overview_flux_record *d_flux = reinterpret_cast<sgz_overview_flux_record *>(p.d_hostOvFlux);
+    st = sgz_spectrogram_overview_flux_device(plan, p.d_hostAudio, stride, nsamples, k, d_flux, s);
+    if (st != SGZ_OK) return st;
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    SGZ_HIP(hipMemcpyAsync(flux_out, d_flux, records * sizeof(sgz_overview_flux_record), hipMemcpyDeviceToHost, s));
     SGZ_HIP(hipEventRecord(ev[3], s));
     SGZ_HIP(hipStreamSynchronize(s));
     if (timing) fillHostTiming(*timing, ev, frames);

@@ -14,6 +14,8 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <string>
+#include <type_traits>
 #include <vector>
 #include <new>
 
@@ -205,7 +207,8 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // OvStats sgz_overview_stat_record [columns][C][P] and OvMeans float [columns][C][P] the stats feed's, beside its OvImage.
 // OvPower sgz_overview_power_record [columns][C][sides][P] and OvLevels float [columns][C][sides][P] the power feed's, beside its OvImage.
 // OvCross sgz_overview_cross_record [columns][C][bands] the cross feed's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutOvCross, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kPcmOuts };
+// OvFlux sgz_overview_flux_record [columns][C][sides] the flux feed's.
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutOvCross, kOutOvFlux, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -317,7 +320,12 @@ struct PcmLane {
     size_t scratchCap = 0;
 };
 
-enum PcmOvKind { kOvPeaks, kOvStats, kOvPower, kOvCross };
+enum PcmOvKind { kOvPeaks, kOvStats, kOvPower, kOvCross, kOvFlux, kPcmOvKinds };
+// how a refusal names an open column's kind, and the feed that flushes it
+static const struct { const char *word, *call; } kPcmOvKindText[kPcmOvKinds] = {
+    {"peak-hold", "sgz_pcm_stream_feed_overview"},       {"mean", "sgz_pcm_stream_feed_overview_stats"}, {"power", "sgz_pcm_stream_feed_overview_power"},
+    {"cross", "sgz_pcm_stream_feed_overview_cross"},     {"flux", "sgz_pcm_stream_feed_overview_flux"},
+};
 
 struct sgz_pcm_stream {
     sgz_spectrum_config cfg{};
@@ -341,6 +349,13 @@ struct sgz_pcm_stream {
     sgz_overview_stat_record *d_ovStatCarry = nullptr;
     sgz_overview_power_record *d_ovPowerCarry = nullptr;
     sgz_overview_cross_record *d_ovCrossCarry = nullptr;
+    // ... or the flux overview's -- [pairs][sides] in d_ovFluxCarry ("The flux overview").  That overview also keeps, across feeds, the last frame's
+    // mapped magnitudes [pairs][sides][P] in d_ovFluxPrev -- fluxLinked: they are the frame in front of the next one, which no reset and no feed of
+    // another kind has consumed frames since -- and frameIndex, the frames the stream has completed since it was made or reset, in any kind of feed
+    sgz_overview_flux_record *d_ovFluxCarry = nullptr;
+    float *d_ovFluxPrev = nullptr;
+    bool fluxLinked = false;
+    uint64_t frameIndex = 0;
     // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels]),
     // stereo-field (sgz_field_record [2][pairs]), histogram (sgz_hist_record [2][channels]), loudness and band (two halves of
     // <lane>CarryBytes(filter) * channels bytes), and the two filters
@@ -358,6 +373,7 @@ struct sgz_pcm_stream {
 struct sgz_plan { Plan impl; };
 
 using PcmClock = std::chrono::steady_clock;
+struct PcmFluxPart;
 static double pcmMsSince(PcmClock::time_point t0) { return std::chrono::duration<double, std::milli>(PcmClock::now() - t0).count(); }
 
 static size_t pcmStateBytes(const sgz_pcm_stream &s) { return size_t(s.cfg.num_pairs) * SGZ_NUM_GRAPHS * s.cfg.axis_points * 2 * sizeof(float); }
@@ -593,6 +609,8 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
                 if (sgz_status st = pcmLanePiece(s, s.lane[id], sl, planar + s.held, n, &yields[id]); st != SGZ_OK) return st;
             const uint64_t total = s.held + n;
             if (sgz_status st = part.render(s, sl, planar, size_t(total), frames, at + n == nsamples, &units); st != SGZ_OK) return st;
+            s.frameIndex += frames;
+            if (frames) s.fluxLinked = std::is_same<Part, PcmFluxPart>::value;      // (the flux overview's previous frame is the stream's last only behind a flux piece)
             if (frames) {
                 if (keep) SGZ_HIP(hipMemcpy2DAsync(s.d_planar[s.cur ^ 1], s.stride * sizeof(float), planar + (total - keep), s.stride * sizeof(float),
                                                    size_t(keep) * sizeof(float), s.numChannels, hipMemcpyDeviceToDevice, s.compute));
@@ -848,6 +866,50 @@ struct PcmCrossPart {
     }
 };
 
+// sgz_pcm_stream_feed_overview_flux's part: K_A's mapped magnitudes and the flux reduction slab by slab, no K_B: the stream's decay state is neither
+// read nor advanced, and there are no line results for a track lane to search (the feed refuses one).  The previous frame and the frame index are
+// the stream's (pcmFeed moves both on behind every piece)
+struct PcmFluxPart {
+    sgz_overview_flux_record *flux;
+    uint32_t k; int flush;
+    uint64_t need;                                                // the columns the whole feed yields
+    bool fluxPinned;
+
+    static size_t records(const sgz_pcm_stream &s, uint64_t columns) { return size_t(columns) * s.cfg.num_pairs * size_t(s.plan->impl.sides); }
+
+    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
+    {
+        if (!s.d_ovFluxCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovFluxCarry), records(s, 1) * sizeof(sgz_overview_flux_record)));
+        if (!s.d_ovFluxPrev) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovFluxPrev), records(s, 1) * s.cfg.axis_points * sizeof(float)));
+        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
+        const size_t columns = (s.maxFrames + k - 1) / k + 1;     // the most one piece can close (PcmColumnsPart::reserve)
+        return sl.out[kOutOvFlux].reserve(records(s, columns) * sizeof(sgz_overview_flux_record), !fluxPinned);
+    }
+    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t, uint64_t frames, bool last, uint64_t *units) const
+    {
+        const int pieceFlush = flush && last;
+        const uint64_t t = s.ovOpen + frames;
+        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
+        sgz_overview_flux_record *d_flux = need ? sl.out[kOutOvFlux].as<sgz_overview_flux_record>() : nullptr;
+        sgz_status st = SGZ_OK;
+        if (frames) {
+            st = runOverviewFluxSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.frameIndex, s.d_ovFluxPrev, s.fluxLinked,
+                                      s.d_ovFluxCarry, d_flux, s.compute);
+        } else if (*units) {                                       // no frame arrives and the open column is flushed
+            st = runOverviewFluxColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, s.frameIndex, 0, nullptr, false, s.d_ovFluxCarry, d_flux, s.compute);
+        }
+        if (st != SGZ_OK) return st;
+        s.ovOpen = pieceFlush ? 0 : t % k;
+        s.ovK = k;
+        s.ovKind = kOvFlux;
+        return SGZ_OK;
+    }
+    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
+    {
+        return sl.out[kOutOvFlux].readBack(flux + records(s, done), records(s, columns) * sizeof(sgz_overview_flux_record), fluxPinned, s.back);
+    }
+};
+
 // what the two one-shot calls share: a stream with no more device and pinned memory than the buffer needs, SGZ_SKIPPED_FRAME where nothing
 // comes out, the feed, and the wall time around all of it.  units(s): what the feed will yield; feed(s, units): the feed call
 template <typename Units, typename Feed>
@@ -868,6 +930,18 @@ static sgz_status pcmOneShot(const sgz_spectrum_config *cfg, uint32_t format, ui
     g_lastError = keep;
     if (timing && st == SGZ_OK) timing->wall_ms = pcmMsSince(t0);
     return st;
+}
+
+// The refusal of a feed while a column of another kind is open, written once: `feed` the refusing call's name; own: the kind the call could
+// continue (kPcmOvKinds: none -- sgz_pcm_stream_feed, whose text names the column first).  SGZ_OK: nothing stands in the way
+static sgz_status pcmOpenColumnRefusal(const sgz_pcm_stream &s, const char *feed, int own)
+{
+    if (!s.ovOpen || s.ovKind == own) return SGZ_OK;
+    const auto &kind = kPcmOvKindText[s.ovKind];
+    const std::string tail = std::string(" -- flush it (") + kind.call + ") or reset the stream first";
+    if (own == kPcmOvKinds)
+        return fail(SGZ_EINVAL, std::string(feed) + (s.ovKind == kOvPeaks ? ": an overview column" : std::string(": a ") + kind.word + " overview's column") + " is open" + tail);
+    return fail(SGZ_EINVAL, std::string(feed) + ": the open column is a " + kind.word + " overview's" + tail);
 }
 
 // columns a feed of nsamples yields at k with the stream as it is; false: k == 0, or a k other than the open column's
@@ -906,7 +980,7 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry, (void *)s->d_ovPowerCarry, (void *)s->d_ovCrossCarry}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry, (void *)s->d_ovPowerCarry, (void *)s->d_ovCrossCarry, (void *)s->d_ovFluxCarry, (void *)s->d_ovFluxPrev}) if (p) (void)hipFree(p);
     for (PcmLane &l : s->lane)
         for (void *p : {l.d_carry, l.d_scratch}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
@@ -979,6 +1053,7 @@ sgz_status sgz_pcm_stream_reset(sgz_pcm_stream *s)
     SGZ_HIP(hipStreamSynchronize(s->compute));
     s->held = 0;
     s->ovOpen = 0; s->ovKind = kOvPeaks;                                            // an open overview column, of any kind, is dropped
+    s->fluxLinked = false; s->frameIndex = 0;                                       // ... and the flux overview's predecessor; the frames count from 0
     for (int id = 0; id < kPcmSinks; ++id) s->sink(id).cursor = 0;                  // every lane's columns and the track's records start over; all stay armed
     for (PcmLane &l : s->lane) { l.open = 0; l.continued = false; l.index = 0; }    // open columns are dropped, the histories are zeros again and the samples count from 0
     return SGZ_OK;
@@ -990,10 +1065,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     const auto t0 = PcmClock::now();
     if (!s) return fail(SGZ_EINVAL, "null stream");
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null pcm");
-    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: a cross overview's column is open -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
-    if (s->ovOpen) return fail(SGZ_EINVAL, s->ovKind == kOvPower ? "sgz_pcm_stream_feed: a power overview's column is open -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first"
-                                           : s->ovKind == kOvStats ? "sgz_pcm_stream_feed: a mean overview's column is open -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first"
-                                                                   : "sgz_pcm_stream_feed: an overview column is open -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
+    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed", kPcmOvKinds); st != SGZ_OK) return st;
     const uint64_t need = sgz_pcm_stream_frames_for(s, nsamples);
     if (frames_out) *frames_out = need;
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
@@ -1035,9 +1107,7 @@ sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: null pcm");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
-    if (s->ovOpen && s->ovKind == kOvStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
-    if (s->ovOpen && s->ovKind == kOvPower) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a power overview's -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first");
-    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: the open column is a cross overview's -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
+    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview", kOvPeaks); st != SGZ_OK) return st;
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -1071,9 +1141,7 @@ sgz_status sgz_pcm_stream_feed_overview_stats(sgz_pcm_stream *s, const void *pcm
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
     if (reinterpret_cast<uintptr_t>(stats_out) % alignof(sgz_overview_stat_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: stats_out is not aligned to 8 bytes");
-    if (s->ovOpen && s->ovKind == kOvPeaks) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
-    if (s->ovOpen && s->ovKind == kOvPower) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a power overview's -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first");
-    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: the open column is a cross overview's -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
+    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview_stats", kOvStats); st != SGZ_OK) return st;
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -1111,9 +1179,7 @@ sgz_status sgz_pcm_stream_feed_overview_power(sgz_pcm_stream *s, const void *pcm
     if (reinterpret_cast<uintptr_t>(power_out) % alignof(sgz_overview_power_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: power_out is not aligned to 8 bytes");
     if (sgz_status st = powerOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
     if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the track lane is armed and a power feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
-    if (s->ovOpen && s->ovKind == kOvPeaks) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
-    if (s->ovOpen && s->ovKind == kOvStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
-    if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the open column is a cross overview's -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
+    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview_power", kOvPower); st != SGZ_OK) return st;
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -1164,9 +1230,7 @@ sgz_status sgz_pcm_stream_feed_overview_cross(sgz_pcm_stream *s, const void *pcm
     if (!s->plan->impl.crossBands || !s->d_ovCrossCarry) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the stream has no band table (sgz_pcm_stream_set_cross_edges)");
     if (reinterpret_cast<uintptr_t>(cross_out) % alignof(sgz_overview_cross_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: cross_out is not aligned to 8 bytes");
     if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the track lane is armed and a cross feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
-    if (s->ovOpen && s->ovKind == kOvPeaks) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the open column is a peak-hold overview's -- flush it (sgz_pcm_stream_feed_overview) or reset the stream first");
-    if (s->ovOpen && s->ovKind == kOvStats) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the open column is a mean overview's -- flush it (sgz_pcm_stream_feed_overview_stats) or reset the stream first");
-    if (s->ovOpen && s->ovKind == kOvPower) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the open column is a power overview's -- flush it (sgz_pcm_stream_feed_overview_power) or reset the stream first");
+    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview_cross", kOvCross); st != SGZ_OK) return st;
     if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: k differs from the open column's -- flush or reset first");
     uint64_t need = 0;
     (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
@@ -1193,6 +1257,43 @@ sgz_status sgz_spectrogram_overview_cross_pcm(const sgz_spectrum_config *cfg, co
                           if (sgz_status st = sgz_pcm_stream_set_cross_edges(s, edges, bands); st != SGZ_OK) return st;
                           return sgz_pcm_stream_feed_overview_cross(s, pcm, nsamples, k, 1, cross_out, columns, &columns, timing);
                       });
+}
+
+// ---- the flux overview inside the stream (sgz.h, "The flux overview") ----------------------------------------------------------------------------
+sgz_status sgz_pcm_stream_feed_overview_flux(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush, sgz_overview_flux_record *flux_out,
+                                             uint64_t capacity_columns, uint64_t *columns_out, sgz_pcm_timing *timing)
+{
+    const auto t0 = PcmClock::now();
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: null pcm");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (reinterpret_cast<uintptr_t>(flux_out) % alignof(sgz_overview_flux_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: flux_out is not aligned to 8 bytes");
+    if (sgz_status st = fluxOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
+    if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: the track lane is armed and a flux feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
+    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview_flux", kOvFlux); st != SGZ_OK) return st;
+    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: k differs from the open column's -- flush or reset first");
+    uint64_t need = 0;
+    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
+    if (columns_out) *columns_out = need;
+    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: capacity_columns below what this feed yields (see *columns_out)");
+    if (need && !flux_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: null flux_out");
+    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
+    PcmFluxPart part{flux_out, k, flush, need, need && isPinnedHost(flux_out)};
+    // (a feed without samples still has one piece when it flushes an open column)
+    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+}
+
+sgz_status sgz_spectrogram_overview_flux_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                             const uint32_t *channel_map, size_t nsamples, uint32_t k, sgz_overview_flux_record *flux_out,
+                                             sgz_pcm_timing *timing)
+{
+    if (!cfg || !pcm || !flux_out) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces transform magnitudes: RSNT plans are not supported");
+    if (cfg->channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces magnitudes: Phase mode's second plane is none");
+    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
+                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
+                      [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_flux(s, pcm, nsamples, k, 1, flux_out, columns, &columns, timing); });
 }
 
 // ---- the lanes' calls ---------------------------------------------------------------------------------------------------------------------------

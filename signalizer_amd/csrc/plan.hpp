@@ -181,6 +181,11 @@ struct Plan {
     uint32_t *d_crossTables = nullptr;
     float *d_ovcCarry = nullptr, *d_ovcCarryCopy = nullptr, *d_ovcPartial = nullptr, *d_hostOvCross = nullptr, *d_ovcBins = nullptr;
     size_t ovcCarryCap = 0, ovcCarryCopyCap = 0, ovcPartialCap = 0, hostOvCrossCap = 0, ovcBinsCap = 0;
+    // the flux overview (overview_flux.hip; sgz_spectrogram_overview_flux_device / _host), 22 floats per sgz_overview_flux_record: the open
+    // column's records [pairs][sides] and their snapshot, the previous frame [pairs][sides][P] and its snapshot, the partial records of the sliced
+    // form, and the host form's device copy of the records
+    float *d_ovfCarry = nullptr, *d_ovfCarryCopy = nullptr, *d_ovfPrev = nullptr, *d_ovfPrevCopy = nullptr, *d_ovfPartial = nullptr, *d_hostOvFlux = nullptr;
+    size_t ovfCarryCap = 0, ovfCarryCopyCap = 0, ovfPrevCap = 0, ovfPrevCopyCap = 0, ovfPartialCap = 0, hostOvFluxCap = 0;
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;

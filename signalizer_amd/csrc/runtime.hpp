@@ -145,6 +145,18 @@ sgz_status runOverviewCrossColumns(Plan &p, const float *d_bins, size_t frames, 
 // checked the plan (crossOverviewSupported) and its band table
 sgz_status runOverviewCrossSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
                                  sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t stream);
+// the flux overview (overview_flux.hip): the reduction of the mapped magnitudes d_mapped [frames][pairs][sides][P] into sgz_overview_flux_record
+// [columns][pairs][sides]; the arguments are sgz_stage_overview_flux's, checked by the caller, but for d_prev [pairs][sides][P], which is read only
+// where prevValid (the frame before frame 0) and written with the call's last frame wherever it is non-null and frames arrive
+sgz_status fluxOverviewSupported(const Plan &p);                  // Phase and RSNT plans: SGZ_EUNSUPPORTED
+sgz_status runOverviewFluxColumns(Plan &p, const float *d_mapped, size_t frames, uint32_t k, uint32_t held, int flush, uint64_t firstFrame, uint32_t slices,
+                                  float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry, sgz_overview_flux_record *d_flux, hipStream_t stream);
+// ... and its slab loop (api.hip): per slab K_A into p.d_mapped with the late pixels completed, then the reduction with the open column carried in
+// d_carry and the previous frame in d_prev; no K_B and no decay state.  What sgz_spectrogram_overview_flux_device and sgz_pcm_stream share; the
+// caller has refused Phase and RSNT plans
+sgz_status runOverviewFluxSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                uint64_t firstFrame, float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry, sgz_overview_flux_record *d_flux,
+                                hipStream_t stream);
 // the column lanes' reductions (wave, level, true-peak, loudness, stereo-field, band): column_lanes.hpp
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
