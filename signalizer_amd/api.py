@@ -731,6 +731,11 @@ def image_resize_device(src, old_columns: int, src_pitch_bytes: int, old_axis_po
 UPDATE_PLANS, UPDATE_CLEAR_LINES, UPDATE_CLEAR_STATE, UPDATE_RESONATORS_AT_REST, UPDATE_TRANSLATE_IMAGE, UPDATE_RING_MOVED = 1, 2, 4, 8, 16, 32
 
 
+def _sides(cfg) -> int:
+    """value planes per pair: 2 for Phase (4; magnitude and cancellation planes), Separate and MidSide"""
+    return 2 if cfg.channel_mode in (4, 5, 6) else 1
+
+
 def _as_config(cfg) -> SpectrumConfig:
     return cfg if isinstance(cfg, SpectrumConfig) else config_from_dict(cfg)
 
@@ -829,6 +834,30 @@ def overview_view_columns(n: int, x0: int, x1: int, out_columns: int, want_bound
     return int(c.value), bounds
 
 
+def _records_from_device(t, dtype) -> np.ndarray:
+    """cuda int64 [..., words] (records as the overview calls write them) -> numpy `dtype` [...]"""
+    h = np.ascontiguousarray(t.cpu().numpy())
+    return h.view(dtype).reshape(h.shape[:-1])
+
+
+def _records_to_device(records: np.ndarray, dtype, words: int, device):
+    """numpy `dtype` [...] -> cuda int64 [..., words]"""
+    import torch
+    r = np.ascontiguousarray(records, dtype)
+    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, words).copy()).to(device)
+
+
+def _overview_fold(symbol: str, dtype, records: np.ndarray, out_columns: int, x0: int, x1: int | None) -> np.ndarray:
+    """the kinds' sgz_overview_<kind>_fold: `dtype` records [n, ...], source columns [x0, x1) -> [min(out_columns, x1 - x0), ...]"""
+    records = np.ascontiguousarray(records, dtype)
+    n = int(records.shape[0])
+    x1 = n if x1 is None else x1
+    width = int(np.prod(records.shape[1:], dtype=np.int64))
+    out = np.zeros((overview_view_columns(n, x0, x1, out_columns), *records.shape[1:]), dtype)
+    check(getattr(lib(), symbol)(_np_ptr(records), n, width, x0, x1, out_columns, _np_ptr(out)))
+    return out
+
+
 # sgz_overview_stat_record (sgz.h, "The mean overview"): 24 bytes, 8-aligned.  On the device a record is three int64 words of a torch tensor
 # [..., 3]; stats_from_device turns such a tensor into a numpy array of this dtype
 OVERVIEW_STAT_DTYPE = np.dtype({"names": ["sum", "count", "nans", "lo", "hi"], "formats": ["<i8", "<u4", "<u4", "<f4", "<f4"],
@@ -837,26 +866,17 @@ OVERVIEW_STAT_DTYPE = np.dtype({"names": ["sum", "count", "nans", "lo", "hi"], "
 
 def stats_from_device(t) -> np.ndarray:
     """cuda int64 [..., 3] (records as the stats calls write them) -> numpy OVERVIEW_STAT_DTYPE [...]"""
-    h = np.ascontiguousarray(t.cpu().numpy())
-    return h.view(OVERVIEW_STAT_DTYPE).reshape(h.shape[:-1])
+    return _records_from_device(t, OVERVIEW_STAT_DTYPE)
 
 
 def stats_to_device(records: np.ndarray, device):
     """numpy OVERVIEW_STAT_DTYPE [...] -> cuda int64 [..., 3]"""
-    import torch
-    r = np.ascontiguousarray(records, OVERVIEW_STAT_DTYPE)
-    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 3).copy()).to(device)
+    return _records_to_device(records, OVERVIEW_STAT_DTYPE, 3, device)
 
 
 def overview_stats_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_overview_stats_fold (host, no GPU): OVERVIEW_STAT_DTYPE records [n, ...], source columns [x0, x1) -> [min(out_columns, x1 - x0), ...]"""
-    records = np.ascontiguousarray(records, OVERVIEW_STAT_DTYPE)
-    n = int(records.shape[0])
-    x1 = n if x1 is None else x1
-    width = int(np.prod(records.shape[1:], dtype=np.int64))
-    out = np.zeros((overview_view_columns(n, x0, x1, out_columns), *records.shape[1:]), OVERVIEW_STAT_DTYPE)
-    check(lib().sgz_overview_stats_fold(_np_ptr(records), n, width, x0, x1, out_columns, _np_ptr(out)))
-    return out
+    return _overview_fold("sgz_overview_stats_fold", OVERVIEW_STAT_DTYPE, records, out_columns, x0, x1)
 
 
 def overview_stats_readout(records: np.ndarray):
@@ -875,15 +895,12 @@ OVERVIEW_POWER_DTYPE = np.dtype({"names": ["sum", "count", "nans", "lo", "hi"], 
 
 def power_from_device(t) -> np.ndarray:
     """cuda int64 [..., 4] (records as the power calls write them) -> numpy OVERVIEW_POWER_DTYPE [...]"""
-    h = np.ascontiguousarray(t.cpu().numpy())
-    return h.view(OVERVIEW_POWER_DTYPE).reshape(h.shape[:-1])
+    return _records_from_device(t, OVERVIEW_POWER_DTYPE)
 
 
 def power_to_device(records: np.ndarray, device):
     """numpy OVERVIEW_POWER_DTYPE [...] -> cuda int64 [..., 4]"""
-    import torch
-    r = np.ascontiguousarray(records, OVERVIEW_POWER_DTYPE)
-    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 4).copy()).to(device)
+    return _records_to_device(records, OVERVIEW_POWER_DTYPE, 4, device)
 
 
 def overview_power_quantise(x: np.ndarray) -> np.ndarray:
@@ -896,13 +913,7 @@ def overview_power_quantise(x: np.ndarray) -> np.ndarray:
 
 def overview_power_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_overview_power_fold (host, no GPU): OVERVIEW_POWER_DTYPE records [n, ...], source columns [x0, x1) -> [min(out_columns, x1 - x0), ...]"""
-    records = np.ascontiguousarray(records, OVERVIEW_POWER_DTYPE)
-    n = int(records.shape[0])
-    x1 = n if x1 is None else x1
-    width = int(np.prod(records.shape[1:], dtype=np.int64))
-    out = np.zeros((overview_view_columns(n, x0, x1, out_columns), *records.shape[1:]), OVERVIEW_POWER_DTYPE)
-    check(lib().sgz_overview_power_fold(_np_ptr(records), n, width, x0, x1, out_columns, _np_ptr(out)))
-    return out
+    return _overview_fold("sgz_overview_power_fold", OVERVIEW_POWER_DTYPE, records, out_columns, x0, x1)
 
 
 def overview_power_readout(records: np.ndarray):
@@ -926,15 +937,12 @@ OVERVIEW_CROSS_READING_DTYPE = np.dtype([(name, "<f8") for name in ("ll", "rr", 
 
 def cross_from_device(t) -> np.ndarray:
     """cuda int64 [..., 10] (records as the cross calls write them) -> numpy OVERVIEW_CROSS_DTYPE [...]"""
-    h = np.ascontiguousarray(t.cpu().numpy())
-    return h.view(OVERVIEW_CROSS_DTYPE).reshape(h.shape[:-1])
+    return _records_from_device(t, OVERVIEW_CROSS_DTYPE)
 
 
 def cross_to_device(records: np.ndarray, device):
     """numpy OVERVIEW_CROSS_DTYPE [...] -> cuda int64 [..., 10]"""
-    import torch
-    r = np.ascontiguousarray(records, OVERVIEW_CROSS_DTYPE)
-    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 10).copy()).to(device)
+    return _records_to_device(records, OVERVIEW_CROSS_DTYPE, 10, device)
 
 
 # sgz_overview_flux_record (sgz.h, "The flux overview"): 88 bytes, 8-aligned; every sum = (low word, high word) of a 128-bit integer.  On the
@@ -946,15 +954,12 @@ OVERVIEW_FLUX_DTYPE = np.dtype({"names": ["amp", "mom1", "mom2", "flux", "flux_m
 
 def flux_from_device(t) -> np.ndarray:
     """cuda int64 [..., 11] (records as the flux calls write them) -> numpy OVERVIEW_FLUX_DTYPE [...]"""
-    h = np.ascontiguousarray(t.cpu().numpy())
-    return h.view(OVERVIEW_FLUX_DTYPE).reshape(h.shape[:-1])
+    return _records_from_device(t, OVERVIEW_FLUX_DTYPE)
 
 
 def flux_to_device(records: np.ndarray, device):
     """numpy OVERVIEW_FLUX_DTYPE [...] -> cuda int64 [..., 11]"""
-    import torch
-    r = np.ascontiguousarray(records, OVERVIEW_FLUX_DTYPE)
-    return torch.from_numpy(r.view(np.int64).reshape(*r.shape, 11).copy()).to(device)
+    return _records_to_device(records, OVERVIEW_FLUX_DTYPE, 11, device)
 
 
 def overview_flux_quantise(x: np.ndarray) -> np.ndarray:
@@ -967,13 +972,7 @@ def overview_flux_quantise(x: np.ndarray) -> np.ndarray:
 
 def overview_flux_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_overview_flux_fold (host, no GPU): OVERVIEW_FLUX_DTYPE records [n, ...], source columns [x0, x1) -> [min(out_columns, x1 - x0), ...]"""
-    records = np.ascontiguousarray(records, OVERVIEW_FLUX_DTYPE)
-    n = int(records.shape[0])
-    x1 = n if x1 is None else x1
-    width = int(np.prod(records.shape[1:], dtype=np.int64))
-    out = np.zeros((overview_view_columns(n, x0, x1, out_columns), *records.shape[1:]), OVERVIEW_FLUX_DTYPE)
-    check(lib().sgz_overview_flux_fold(_np_ptr(records), n, width, x0, x1, out_columns, _np_ptr(out)))
-    return out
+    return _overview_fold("sgz_overview_flux_fold", OVERVIEW_FLUX_DTYPE, records, out_columns, x0, x1)
 
 
 def overview_flux_readout(records: np.ndarray, pixels: int):
@@ -1085,7 +1084,7 @@ class Plan:
 
     @property
     def sides(self) -> int:
-        return 2 if self.cfg.channel_mode in (4, 5, 6) else 1      # Phase (4): magnitude and cancellation planes
+        return _sides(self.cfg)
 
     @property
     def window_scale(self) -> float:
@@ -1842,87 +1841,64 @@ class PcmStream:
         """sgz_pcm_stream_open_frames: frames of the overview column that is open"""
         return int(lib().sgz_pcm_stream_open_frames(self.h))
 
-    def feed_overview_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, peaks, capacity_columns: int, timing: bool = True):
-        """the C call as it is: (status, columns_out, PcmTiming or None); rgba / peaks: numpy arrays, host torch tensors or None"""
+    # the five overview feeds: `call` is the C call's suffix behind sgz_pcm_stream_feed_overview
+    def _feed_overview_into(self, call: str, pcm, nsamples: int, k: int, flush: bool, outputs, capacity_columns: int, timing: bool):
         t, c = PcmTiming() if timing else None, C.c_uint64(0)
-        st = lib().sgz_pcm_stream_feed_overview(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
-                                                _buf_ptr(rgba) if rgba is not None else None, _buf_ptr(peaks) if peaks is not None else None,
-                                                capacity_columns, C.byref(c), C.byref(t) if timing else None)
+        st = getattr(lib(), "sgz_pcm_stream_feed_overview" + call)(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
+                                                                   *[_buf_ptr(a) if a is not None else None for a in outputs],
+                                                                   capacity_columns, C.byref(c), C.byref(t) if timing else None)
         return st, int(c.value), t
 
-    def feed_overview(self, pcm, k: int, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_peaks: bool = False):
-        """Feeds nsamples (default: all of pcm; pcm None: none) into the overview at k frames per column and returns the columns that closed:
-        (rgba uint8 [columns, P, 4] or None, peaks float32 [columns, pairs, P] or None, timing dict)."""
+    def _feed_overview(self, call: str, pcm, k: int, flush: bool, nsamples, outputs):
+        """outputs: (wanted, the shape of one column, dtype) each -> the columns that closed of every output, None where not wanted, and the
+        timing dict"""
         if pcm is None:
             n = 0
         else:
             nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
             n = nbytes // self.frame_bytes if nsamples is None else nsamples
         cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
-        P = self.cfg.axis_points
-        rgba = np.zeros((max(cols, 1), P, 4), np.uint8) if want_rgba else None
-        peaks = np.zeros((max(cols, 1), self.cfg.num_pairs, P), np.float32) if want_peaks else None
-        st, c, t = self.feed_overview_into(pcm if n else None, n, k, flush, rgba, peaks, cols)
+        arrays = [np.zeros((max(cols, 1), *shape), dtype) if want else None for want, shape, dtype in outputs]
+        st, c, t = self._feed_overview_into(call, pcm if n else None, n, k, flush, arrays, cols, True)
         check(st)
         assert c == cols, (c, cols)
-        return (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
+        return (*[a[:cols] if a is not None else None for a in arrays], t.asdict())
+
+    def feed_overview_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, peaks, capacity_columns: int, timing: bool = True):
+        """the C call as it is: (status, columns_out, PcmTiming or None); rgba / peaks: numpy arrays, host torch tensors or None"""
+        return self._feed_overview_into("", pcm, nsamples, k, flush, (rgba, peaks), capacity_columns, timing)
+
+    def feed_overview(self, pcm, k: int, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_peaks: bool = False):
+        """Feeds nsamples (default: all of pcm; pcm None: none) into the overview at k frames per column and returns the columns that closed:
+        (rgba uint8 [columns, P, 4] or None, peaks float32 [columns, pairs, P] or None, timing dict)."""
+        P, pairs = self.cfg.axis_points, self.cfg.num_pairs
+        return self._feed_overview("", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_peaks, (pairs, P), np.float32)])
 
     def feed_overview_stats_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, stats, means, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); rgba / stats / means: numpy arrays, host torch tensors or None"""
-        t, c = PcmTiming() if timing else None, C.c_uint64(0)
-        st = lib().sgz_pcm_stream_feed_overview_stats(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
-                                                      *[_buf_ptr(a) if a is not None else None for a in (rgba, stats, means)],
-                                                      capacity_columns, C.byref(c), C.byref(t) if timing else None)
-        return st, int(c.value), t
+        return self._feed_overview_into("_stats", pcm, nsamples, k, flush, (rgba, stats, means), capacity_columns, timing)
 
     def feed_overview_stats(self, pcm, k: int, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_stats: bool = True,
                             want_means: bool = False):
         """Feeds nsamples (default: all of pcm; pcm None: none) into the mean overview at k frames per column and returns the columns that
         closed: (rgba uint8 [columns, P, 4] or None, records OVERVIEW_STAT_DTYPE [columns, pairs, P] or None, means float32 [columns,
         pairs, P] or None, timing dict)."""
-        if pcm is None:
-            n = 0
-        else:
-            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
-            n = nbytes // self.frame_bytes if nsamples is None else nsamples
-        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
         P, pairs = self.cfg.axis_points, self.cfg.num_pairs
-        rgba = np.zeros((max(cols, 1), P, 4), np.uint8) if want_rgba else None
-        stats = np.zeros((max(cols, 1), pairs, P), OVERVIEW_STAT_DTYPE) if want_stats else None
-        means = np.zeros((max(cols, 1), pairs, P), np.float32) if want_means else None
-        st, c, t = self.feed_overview_stats_into(pcm if n else None, n, k, flush, rgba, stats, means, cols)
-        check(st)
-        assert c == cols, (c, cols)
-        return (rgba[:cols] if want_rgba else None), (stats[:cols] if want_stats else None), (means[:cols] if want_means else None), t.asdict()
+        return self._feed_overview("_stats", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_stats, (pairs, P), OVERVIEW_STAT_DTYPE),
+                                                                       (want_means, (pairs, P), np.float32)])
 
     def feed_overview_power_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, power, levels, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); rgba / power / levels: numpy arrays, host torch tensors or None"""
-        t, c = PcmTiming() if timing else None, C.c_uint64(0)
-        st = lib().sgz_pcm_stream_feed_overview_power(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
-                                                      *[_buf_ptr(a) if a is not None else None for a in (rgba, power, levels)],
-                                                      capacity_columns, C.byref(c), C.byref(t) if timing else None)
-        return st, int(c.value), t
+        return self._feed_overview_into("_power", pcm, nsamples, k, flush, (rgba, power, levels), capacity_columns, timing)
 
     def feed_overview_power(self, pcm, k: int, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_power: bool = True,
                             want_levels: bool = False):
         """Feeds nsamples (default: all of pcm; pcm None: none) into the power overview at k frames per column and returns the columns that
         closed: (rgba uint8 [columns, P, 4] or None, records OVERVIEW_POWER_DTYPE [columns, pairs, sides, P] or None, levels float32 [columns,
         pairs, sides, P] or None, timing dict).  The stream's decay state is neither read nor advanced."""
-        if pcm is None:
-            n = 0
-        else:
-            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
-            n = nbytes // self.frame_bytes if nsamples is None else nsamples
-        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
-        P, pairs = self.cfg.axis_points, self.cfg.num_pairs
-        sides = 2 if self.cfg.channel_mode in (4, 5, 6) else 1
-        rgba = np.zeros((max(cols, 1), P, 4), np.uint8) if want_rgba else None
-        power = np.zeros((max(cols, 1), pairs, sides, P), OVERVIEW_POWER_DTYPE) if want_power else None
-        levels = np.zeros((max(cols, 1), pairs, sides, P), np.float32) if want_levels else None
-        st, c, t = self.feed_overview_power_into(pcm if n else None, n, k, flush, rgba, power, levels, cols)
-        check(st)
-        assert c == cols, (c, cols)
-        return (rgba[:cols] if want_rgba else None), (power[:cols] if want_power else None), (levels[:cols] if want_levels else None), t.asdict()
+        P, plane = self.cfg.axis_points, (self.cfg.num_pairs, _sides(self.cfg), self.cfg.axis_points)
+        return self._feed_overview("_power", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_power, plane, OVERVIEW_POWER_DTYPE),
+                                                                       (want_levels, plane, np.float32)])
 
     def set_cross_edges(self, edges) -> None:
         """sgz_pcm_stream_set_cross_edges: the band table of the stream's cross feeds, uint32 [bands + 1]"""
@@ -1932,50 +1908,21 @@ class PcmStream:
 
     def feed_overview_cross_into(self, pcm, nsamples: int, k: int, flush: bool, cross, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); cross: a numpy array, a host torch tensor or None"""
-        t, c = PcmTiming() if timing else None, C.c_uint64(0)
-        st = lib().sgz_pcm_stream_feed_overview_cross(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
-                                                      _buf_ptr(cross) if cross is not None else None, capacity_columns, C.byref(c),
-                                                      C.byref(t) if timing else None)
-        return st, int(c.value), t
+        return self._feed_overview_into("_cross", pcm, nsamples, k, flush, (cross,), capacity_columns, timing)
 
     def feed_overview_cross(self, pcm, k: int, flush: bool = False, nsamples: int | None = None):
         """Feeds nsamples (default: all of pcm; pcm None: none) into the cross overview at k frames per column and returns the columns that
         closed: (records OVERVIEW_CROSS_DTYPE [columns, pairs, bands], timing dict).  The stream's decay state is neither read nor advanced."""
-        if pcm is None:
-            n = 0
-        else:
-            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
-            n = nbytes // self.frame_bytes if nsamples is None else nsamples
-        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
-        cross = np.zeros((max(cols, 1), self.cfg.num_pairs, getattr(self, "cross_bands", 1)), OVERVIEW_CROSS_DTYPE)
-        st, c, t = self.feed_overview_cross_into(pcm if n else None, n, k, flush, cross, cols)
-        check(st)
-        assert c == cols, (c, cols)
-        return cross[:cols], t.asdict()
+        return self._feed_overview("_cross", pcm, k, flush, nsamples, [(True, (self.cfg.num_pairs, getattr(self, "cross_bands", 1)), OVERVIEW_CROSS_DTYPE)])
 
     def feed_overview_flux_into(self, pcm, nsamples: int, k: int, flush: bool, flux, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); flux: a numpy array, a host torch tensor or None"""
-        t, c = PcmTiming() if timing else None, C.c_uint64(0)
-        st = lib().sgz_pcm_stream_feed_overview_flux(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
-                                                     _buf_ptr(flux) if flux is not None else None, capacity_columns, C.byref(c),
-                                                     C.byref(t) if timing else None)
-        return st, int(c.value), t
+        return self._feed_overview_into("_flux", pcm, nsamples, k, flush, (flux,), capacity_columns, timing)
 
     def feed_overview_flux(self, pcm, k: int, flush: bool = False, nsamples: int | None = None):
         """Feeds nsamples (default: all of pcm; pcm None: none) into the flux overview at k frames per column and returns the columns that
         closed: (records OVERVIEW_FLUX_DTYPE [columns, pairs, sides], timing dict).  The stream's decay state is neither read nor advanced."""
-        if pcm is None:
-            n = 0
-        else:
-            nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
-            n = nbytes // self.frame_bytes if nsamples is None else nsamples
-        cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
-        sides = 2 if self.cfg.channel_mode in (4, 5, 6) else 1
-        flux = np.zeros((max(cols, 1), self.cfg.num_pairs, sides), OVERVIEW_FLUX_DTYPE)
-        st, c, t = self.feed_overview_flux_into(pcm if n else None, n, k, flush, flux, cols)
-        check(st)
-        assert c == cols, (c, cols)
-        return flux[:cols], t.asdict()
+        return self._feed_overview("_flux", pcm, k, flush, nsamples, [(True, (self.cfg.num_pairs, _sides(self.cfg)), OVERVIEW_FLUX_DTYPE)])
 
     # the seven column lanes (waveform, level, truepeak, loudness, field, band, hist): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
@@ -2482,102 +2429,62 @@ def band_colours(records: np.ndarray, channel: int, band_colours, key_rgba8, fre
     return out
 
 
-def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
-                 want_peaks: bool = False):
-    """One-shot overview of an interleaved PCM buffer (sgz_spectrogram_overview_pcm): (status, rgba or None, peaks or None, timing dict);
-    status is SGZ_SKIPPED_FRAME for fewer samples than one window."""
+def _overview_pcm(call: str, cfg, pcm, fmt: int, src_channels: int, k: int, channel_map, nsamples, outputs, front=()):
+    """sgz_spectrogram_overview<call>_pcm.  outputs(c): (wanted, the shape of one column, dtype) each, from the config; front: what the C call
+    takes between nsamples and k -> (status, every output's columns or None where not wanted, timing dict)"""
     c = _as_config(cfg)
     nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
     n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
     F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
     cols = -(-F // k) if k else 0
-    rgba = np.zeros((max(cols, 1), c.axis_points, 4), np.uint8) if want_rgba else None
-    peaks = np.zeros((max(cols, 1), c.num_pairs, c.axis_points), np.float32) if want_peaks else None
+    arrays = [np.zeros((max(cols, 1), *shape), dtype) if want else None for want, shape, dtype in outputs(c)]     # (never an empty array: its pointer may be null)
     m, mp = _channel_map(channel_map)
     t = PcmTiming()
-    st = check(lib().sgz_spectrogram_overview_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(rgba) if want_rgba else None,
-                                                  _np_ptr(peaks) if want_peaks else None, C.byref(t)))
-    return st, (rgba[:cols] if want_rgba else None), (peaks[:cols] if want_peaks else None), t.asdict()
+    st = check(getattr(lib(), f"sgz_spectrogram_overview{call}_pcm")(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, *front, k,
+                                                                     *[_np_ptr(a) if a is not None else None for a in arrays], C.byref(t)))
+    if st == SGZ_SKIPPED_FRAME:
+        cols = 0
+    return (st, *[a[:cols] if a is not None else None for a in arrays], t.asdict())
+
+
+def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
+                 want_peaks: bool = False):
+    """One-shot overview of an interleaved PCM buffer (sgz_spectrogram_overview_pcm): (status, rgba or None, peaks or None, timing dict);
+    status is SGZ_SKIPPED_FRAME for fewer samples than one window."""
+    return _overview_pcm("", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
+                         lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_peaks, (c.num_pairs, c.axis_points), np.float32)])
 
 
 def overview_stats_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
                        want_stats: bool = True, want_means: bool = False):
     """One-shot mean overview of an interleaved PCM buffer (sgz_spectrogram_overview_stats_pcm): (status, rgba or None, records
     OVERVIEW_STAT_DTYPE or None, means or None, timing dict); SGZ_SKIPPED_FRAME and empty outputs for fewer samples than a window"""
-    c = _as_config(cfg)
-    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
-    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
-    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
-    cols = -(-F // k) if k else 0
-    rgba = np.zeros((max(cols, 1), c.axis_points, 4), np.uint8) if want_rgba else None
-    stats = np.zeros((max(cols, 1), c.num_pairs, c.axis_points), OVERVIEW_STAT_DTYPE) if want_stats else None
-    means = np.zeros((max(cols, 1), c.num_pairs, c.axis_points), np.float32) if want_means else None
-    m, mp = _channel_map(channel_map)
-    t = PcmTiming()
-    st = check(lib().sgz_spectrogram_overview_stats_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(rgba) if want_rgba else None,
-                                                        _np_ptr(stats) if want_stats else None, _np_ptr(means) if want_means else None, C.byref(t)))
-    if st == SGZ_SKIPPED_FRAME:
-        cols = 0
-    return st, (rgba[:cols] if want_rgba else None), (stats[:cols] if want_stats else None), (means[:cols] if want_means else None), t.asdict()
+    return _overview_pcm("_stats", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
+                         lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_stats, (c.num_pairs, c.axis_points), OVERVIEW_STAT_DTYPE),
+                                    (want_means, (c.num_pairs, c.axis_points), np.float32)])
 
 
 def overview_power_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
                        want_power: bool = True, want_levels: bool = False):
     """One-shot power overview of an interleaved PCM buffer (sgz_spectrogram_overview_power_pcm): (status, rgba or None, records
     OVERVIEW_POWER_DTYPE or None, levels or None, timing dict); SGZ_SKIPPED_FRAME and empty outputs for fewer samples than a window"""
-    c = _as_config(cfg)
-    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
-    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
-    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
-    cols = -(-F // k) if k else 0
-    sides = 2 if c.channel_mode in (4, 5, 6) else 1
-    rgba = np.zeros((max(cols, 1), c.axis_points, 4), np.uint8) if want_rgba else None
-    power = np.zeros((max(cols, 1), c.num_pairs, sides, c.axis_points), OVERVIEW_POWER_DTYPE) if want_power else None
-    levels = np.zeros((max(cols, 1), c.num_pairs, sides, c.axis_points), np.float32) if want_levels else None
-    m, mp = _channel_map(channel_map)
-    t = PcmTiming()
-    st = check(lib().sgz_spectrogram_overview_power_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(rgba) if want_rgba else None,
-                                                        _np_ptr(power) if want_power else None, _np_ptr(levels) if want_levels else None, C.byref(t)))
-    if st == SGZ_SKIPPED_FRAME:
-        cols = 0
-    return st, (rgba[:cols] if want_rgba else None), (power[:cols] if want_power else None), (levels[:cols] if want_levels else None), t.asdict()
+    return _overview_pcm("_power", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
+                         lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_power, (c.num_pairs, _sides(c), c.axis_points), OVERVIEW_POWER_DTYPE),
+                                    (want_levels, (c.num_pairs, _sides(c), c.axis_points), np.float32)])
 
 
 def overview_cross_pcm(cfg, pcm, fmt: int, src_channels: int, edges, k: int, channel_map=None, nsamples: int | None = None):
     """One-shot cross overview of an interleaved PCM buffer (sgz_spectrogram_overview_cross_pcm): (status, records OVERVIEW_CROSS_DTYPE
     [columns, pairs, bands], timing dict); SGZ_SKIPPED_FRAME and no records for fewer samples than a window"""
-    c = _as_config(cfg)
     e = _edges(edges)
-    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
-    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
-    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
-    cols = -(-F // k) if k else 0
-    cross = np.zeros((max(cols, 1), c.num_pairs, e.size - 1), OVERVIEW_CROSS_DTYPE)
-    m, mp = _channel_map(channel_map)
-    t = PcmTiming()
-    st = check(lib().sgz_spectrogram_overview_cross_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, _np_ptr(e), e.size - 1, k,
-                                                        _np_ptr(cross), C.byref(t)))
-    if st == SGZ_SKIPPED_FRAME:
-        cols = 0
-    return st, cross[:cols], t.asdict()
+    return _overview_pcm("_cross", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, lambda c: [(True, (c.num_pairs, e.size - 1), OVERVIEW_CROSS_DTYPE)],
+                         front=(_np_ptr(e), e.size - 1))
 
 
 def overview_flux_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None):
     """One-shot flux overview of an interleaved PCM buffer (sgz_spectrogram_overview_flux_pcm): (status, records OVERVIEW_FLUX_DTYPE [columns,
     pairs, sides], timing dict); SGZ_SKIPPED_FRAME and no records for fewer samples than a window"""
-    c = _as_config(cfg)
-    nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
-    n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
-    F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
-    cols = -(-F // k) if k else 0
-    sides = 2 if c.channel_mode in (4, 5, 6) else 1
-    flux = np.zeros((max(cols, 1), c.num_pairs, sides), OVERVIEW_FLUX_DTYPE)
-    m, mp = _channel_map(channel_map)
-    t = PcmTiming()
-    st = check(lib().sgz_spectrogram_overview_flux_pcm(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, k, _np_ptr(flux), C.byref(t)))
-    if st == SGZ_SKIPPED_FRAME:
-        cols = 0
-    return st, flux[:cols], t.asdict()
+    return _overview_pcm("_flux", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, lambda c: [(True, (c.num_pairs, _sides(c)), OVERVIEW_FLUX_DTYPE)])
 
 
 def render_spectrogram_pcm(cfg, pcm, fmt: int, src_channels: int, channel_map=None, nsamples: int | None = None, want_lines: bool = False):

@@ -46,13 +46,12 @@ Plan::~Plan()
                     d_stateCopy, d_work0, d_work1, d_binsWork, d_halfBins, d_dcPixels, d_dcWork, d_phaseType, d_phaseNorm, d_phaseWork, d_shard, d_twReal1, d_twRealPost, d_tw2Full, d_windowHalf, d_winPhase, d_winPhaseT, d_ny, d_nyBest, d_chunkEnds, d_chunkReBase, d_chunkRec, d_weights12, d_resCoeff, d_resPow, d_resPowB, d_resPowBLo, d_resW1, d_resW2, d_resW1b, d_resTile, d_resGain, d_resState, d_resLocal};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq, (void *)d_ovLines, (void *)d_ovCarry,
-                    (void *)d_ovCarryCopy, (void *)d_ovState, (void *)d_ovPartial, (void *)d_hostOvPeaks, (void *)d_ovViewIn, (void *)d_ovsCarry,
-                    (void *)d_ovsCarryCopy, (void *)d_ovsPartial, (void *)d_hostOvStats, (void *)d_hostOvMeans, (void *)d_ovsViewIn,
-                    (void *)d_ovpCarry, (void *)d_ovpCarryCopy, (void *)d_ovpPartial, (void *)d_hostOvPower, (void *)d_hostOvLevels, (void *)d_ovpViewIn,
-                    (void *)d_crossTables, (void *)d_ovcCarry, (void *)d_ovcCarryCopy, (void *)d_ovcPartial, (void *)d_hostOvCross, (void *)d_ovcBins,
-                    (void *)d_ovfCarry, (void *)d_ovfCarryCopy, (void *)d_ovfPrev, (void *)d_ovfPrevCopy, (void *)d_ovfPartial, (void *)d_hostOvFlux})
+    for (void *p : {(void *)d_hostAudio, (void *)d_hostRgba, (void *)d_hostLines, (void *)d_trackLines, (void *)d_hostTrack, (void *)d_mappedFreq, (void *)d_ovLines, (void *)d_ovState,
+                    (void *)d_crossTables, (void *)d_ovcBins, (void *)d_ovfPrev, (void *)d_ovfPrevCopy})
         if (p) (void)hipFree(p);
+    for (const OverviewScratch &o : ov)
+        for (void *p : {(void *)o.d_carry, (void *)o.d_carryCopy, (void *)o.d_partial, (void *)o.d_hostRecords, (void *)o.d_hostValues, (void *)o.d_viewIn})
+            if (p) (void)hipFree(p);
     for (void *e : hostEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *e : shardEv) if (e) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     if (shardStream) (void)hipStreamDestroy(static_cast<hipStream_t>(shardStream));
@@ -1067,69 +1066,250 @@ sgz_status sgz_spectrogram_track_host(sgz_plan *plan, const float *const *planar
     return SGZ_OK;
 }
 
-// The overview render (sgz.h; overview.hip): the render's chain as it is, a slab of frames at a time with line results into plan scratch
-// and the decay state carried from slab to slab, and the reduction behind every slab with the open column carried across the cut.  Carried
-// state makes the pieces equal the single render byte for byte (what sgz_pcm_stream relies on), so the columns do not depend on the slab.
-// RSNT renders as one slab: its launches chain their frames within an fp32 bar, a cut would move the bits.
-constexpr size_t kOverviewSlabBytes = size_t(64) << 20;
+// The overview renders (sgz.h; overview*.hip): a slab of frames at a time, the kind's reduction behind every slab with the open column carried across
+// the cut.  Carried state makes the pieces equal the single render byte for byte (what sgz_pcm_stream relies on), so the columns do not depend
+// on the slab.  The slab is SGZ_OPT_OVERVIEW_SLAB's, or as many frames as keep what a slab produces within the kind's budget: 64 MiB of line
+// results -- the power and flux overviews count theirs the same way, so that one setting cuts all the renders alike -- or 256 MiB of bins.
+constexpr size_t kOverviewSlabBytes = size_t(64) << 20, kCrossSlabBytes = size_t(256) << 20;
 }  // extern "C"
-// The slab loop by itself (runtime.hpp): `held` frames of an open column in front (their reduction in the caller's carry), the columns that
-// close written from the outputs' first element on.  The overview render enters with held = 0 and flush; sgz_pcm_stream enters once per
-// piece, with `track` when its track lane is armed.  reduce(d_lines, frames, held, flush, column): the reduction of one slab's line results,
-// `column` the output column its first frame belongs to -- the peak hold (runOverviewSlabs) or the mean overview (runOverviewStatsSlabs).
 namespace {
-template <typename Reduce>
-sgz_status overviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
-                         int flush, float *d_state, hipStream_t s, const sgz::SlabTrack *track, Reduce reduce)
+long slabFrames(const Plan &p, long frames, size_t budgetBytes, size_t perFrameFloats)
 {
-    Plan &p = plan->impl;
-    sgz_status st = SGZ_OK;
-    const size_t perFrame = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;                                   // floats of line results
-    long slab = frames;
-    if (!isResonator(p)) slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kOverviewSlabBytes / (perFrame * sizeof(float)))));
-    if ((st = ensureCap(&p.d_ovLines, &p.ovLinesCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
-    float *state = d_state;
-    if (!state && slab < frames) {                               // the slabs continue a state of the plan's own, from rest
-        const size_t stateN = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2;
-        if ((st = ensureCap(&p.d_ovState, &p.ovStateCap, stateN)) != SGZ_OK) return st;
-        SGZ_HIP(hipMemsetAsync(p.d_ovState, 0, stateN * sizeof(float), s));
-        state = p.d_ovState;
-    }
+    return std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, budgetBytes / (perFrameFloats * sizeof(float)))));
+}
+size_t lineFloats(const Plan &p) { return size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2; }         // a frame's line results, and the decay state
+
+// The slab loop (runtime.hpp): `frames` frames in slabs of `slab`, behind `held` frames of an open column whose reduction is in the caller's
+// carry; the columns that close are written from the outputs' first element on.  The renders enter with held = 0 and flush; sgz_pcm_stream
+// enters once per piece.  produce(f0, nf): the kind's work on the nf frames from f0 on.  reduce(nf, heldIn, flushNow, column, f0): the kind's
+// run...Columns on what produce left -- heldIn frames of the open column in front, `column` the output column frame f0 belongs to.
+template <typename Produce, typename Reduce>
+sgz_status overviewSlabs(long frames, long slab, uint32_t k, uint32_t held, int flush, Produce produce, Reduce reduce)
+{
     for (long f0 = 0; f0 < frames; f0 += slab) {
         const long nf = std::min(slab, frames - f0);
-        const size_t ns = isResonator(p) ? nsamples : size_t(p.W) + size_t(nf - 1) * p.cfg.hop;
-        st = sgz_spectrogram_render_device(plan, d_planar + size_t(f0) * p.cfg.hop, channel_stride, ns, nullptr, p.d_ovLines, state, s);
-        if (st != SGZ_OK) return st;
-        if (track && (st = runTrackPeaksLines(p, p.d_ovLines, size_t(nf), track->graph, track->mouseFraction, track->d_out + size_t(f0) * p.C, s)) != SGZ_OK) return st;
+        if (sgz_status st = produce(f0, nf); st != SGZ_OK) return st;
         const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
         const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
-        if ((st = reduce(p.d_ovLines, size_t(nf), uint32_t(t0 % k), flush && f0 + nf == frames, column)) != SGZ_OK) return st;
+        if (sgz_status st = reduce(size_t(nf), uint32_t(t0 % k), flush && f0 + nf == frames, column, f0); st != SGZ_OK) return st;
     }
     return SGZ_OK;
 }
+
+// The peak hold's and the mean overview's slabs: the render's chain as it is, with line results into plan scratch and the decay state carried
+// from slab to slab; `track`: sgz_pcm_stream's track lane searches every slab's line results.  RSNT renders as one slab: its launches chain
+// their frames within an fp32 bar, a cut would move the bits.
+template <typename Reduce>
+sgz_status overviewLineSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
+                             int flush, float *d_state, hipStream_t s, const sgz::SlabTrack *track, Reduce reduce)
+{
+    Plan &p = plan->impl;
+    sgz_status st = SGZ_OK;
+    const long slab = isResonator(p) ? frames : slabFrames(p, frames, kOverviewSlabBytes, lineFloats(p));
+    if ((st = ensureCap(&p.d_ovLines, &p.ovLinesCap, size_t(slab) * lineFloats(p))) != SGZ_OK) return st;
+    float *state = d_state;
+    if (!state && slab < frames) {                               // the slabs continue a state of the plan's own, from rest
+        if ((st = ensureCap(&p.d_ovState, &p.ovStateCap, lineFloats(p))) != SGZ_OK) return st;
+        SGZ_HIP(hipMemsetAsync(p.d_ovState, 0, lineFloats(p) * sizeof(float), s));
+        state = p.d_ovState;
+    }
+    return overviewSlabs(frames, slab, k, held, flush,
+                         [&](long f0, long nf) {
+                             const size_t ns = isResonator(p) ? nsamples : size_t(p.W) + size_t(nf - 1) * p.cfg.hop;
+                             sgz_status r = sgz_spectrogram_render_device(plan, d_planar + size_t(f0) * p.cfg.hop, channel_stride, ns, nullptr, p.d_ovLines, state, s);
+                             if (r != SGZ_OK || !track) return r;
+                             return runTrackPeaksLines(p, p.d_ovLines, size_t(nf), track->graph, track->mouseFraction, track->d_out + size_t(f0) * p.C, s);
+                         },
+                         [&](size_t nf, uint32_t heldIn, int flushNow, size_t column, long) { return reduce(p.d_ovLines, nf, heldIn, flushNow, column); });
+}
+
+// The power and flux overviews' slabs have no K_B in them: per slab K_A into p.d_mapped -- sgz_stage_mapped's call, late pixels completed,
+// because nothing behind it would -- and the reduction.  No decay state.
+template <typename Reduce>
+sgz_status overviewMappedSlabs(Plan &p, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush, hipStream_t s,
+                               Reduce reduce)
+{
+    const size_t perFrame = size_t(p.C) * p.sides * p.P;
+    const long slab = slabFrames(p, frames, kOverviewSlabBytes, lineFloats(p));
+    if (sgz_status st = ensureCap(&p.d_mapped, &p.mappedCap, size_t(slab) * perFrame); st != SGZ_OK) return st;
+    return overviewSlabs(frames, slab, k, held, flush,
+                         [&](long f0, long nf) { return runStft(p, d_planar + size_t(f0) * p.cfg.hop, channel_stride, nf, p.d_mapped, nullptr, nullptr, s); }, reduce);
+}
+template <typename T> T *at(T *base, size_t offset) { return base ? base + offset : nullptr; }     // an output the caller did not ask for stays null
 }  // namespace
 sgz_status sgz::runOverviewSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
                                  int flush, float *d_carry, float *d_state, uint8_t *d_rgba, float *d_peaks, hipStream_t s, const SlabTrack *track)
 {
     Plan &p = plan->impl;
-    return overviewSlabs(plan, d_planar, channel_stride, nsamples, frames, k, held, flush, d_state, s, track,
-                         [&](const float *d_lines, size_t nf, uint32_t heldIn, int flushNow, size_t column) {
-                             return runOverviewColumns(p, d_lines, nf, k, heldIn, flushNow, 0, d_carry, d_rgba ? d_rgba + column * p.P * 4 : nullptr,
-                                                       d_peaks ? d_peaks + column * p.C * p.P : nullptr, s);
-                         });
+    return overviewLineSlabs(plan, d_planar, channel_stride, nsamples, frames, k, held, flush, d_state, s, track,
+                             [&](const float *d_lines, size_t nf, uint32_t heldIn, int flushNow, size_t column) {
+                                 return runOverviewColumns(p, d_lines, nf, k, heldIn, flushNow, 0, d_carry, at(d_rgba, column * p.P * 4), at(d_peaks, column * p.C * p.P), s);
+                             });
 }
 sgz_status sgz::runOverviewStatsSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k,
                                       uint32_t held, int flush, sgz_overview_stat_record *d_carry, float *d_state, uint8_t *d_rgba,
                                       sgz_overview_stat_record *d_stats, float *d_means, hipStream_t s, const SlabTrack *track)
 {
     Plan &p = plan->impl;
-    return overviewSlabs(plan, d_planar, channel_stride, nsamples, frames, k, held, flush, d_state, s, track,
-                         [&](const float *d_lines, size_t nf, uint32_t heldIn, int flushNow, size_t column) {
-                             return runOverviewStatsColumns(p, d_lines, nf, k, heldIn, flushNow, 0, d_carry, d_rgba ? d_rgba + column * p.P * 4 : nullptr,
-                                                            d_stats ? d_stats + column * p.C * p.P : nullptr,
-                                                            d_means ? d_means + column * p.C * p.P : nullptr, s);
+    return overviewLineSlabs(plan, d_planar, channel_stride, nsamples, frames, k, held, flush, d_state, s, track,
+                             [&](const float *d_lines, size_t nf, uint32_t heldIn, int flushNow, size_t column) {
+                                 return runOverviewStatsColumns(p, d_lines, nf, k, heldIn, flushNow, 0, d_carry, at(d_rgba, column * p.P * 4),
+                                                                at(d_stats, column * p.C * p.P), at(d_means, column * p.C * p.P), s);
+                             });
+}
+sgz_status sgz::powerOverviewSupported(const Plan &p)
+{
+    if (isResonator(p)) return fail(SGZ_EUNSUPPORTED, "the power overview reduces transform magnitudes: RSNT plans are not supported");
+    if (p.cfg.channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the power overview reduces magnitudes: Phase mode's second plane is none");
+    return SGZ_OK;
+}
+sgz_status sgz::runOverviewPowerSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                      sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels,
+                                      hipStream_t s)
+{
+    Plan &p = plan->impl;
+    const size_t perColumn = size_t(p.C) * p.sides * p.P;
+    return overviewMappedSlabs(p, d_planar, channel_stride, frames, k, held, flush, s, [&](size_t nf, uint32_t heldIn, int flushNow, size_t column, long) {
+        return runOverviewPowerColumns(p, p.d_mapped, nf, k, heldIn, flushNow, 0, d_carry, at(d_rgba, column * p.P * 4), at(d_power, column * perColumn),
+                                       at(d_levels, column * perColumn), s);
+    });
+}
+// The cross overview's slabs: per slab K_A's complex bins into plan scratch -- runStft as sgz_stage_bins calls it -- and the reduction.  No K_B,
+// no decay state.
+sgz_status sgz::runOverviewCrossSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                      sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t s)
+{
+    Plan &p = plan->impl;
+    const size_t perFrame = size_t(p.C) * (size_t(p.N) + 1) * 2, perColumn = size_t(p.C) * p.crossBands;     // floats of a frame's bins; records of a column
+    const long slab = slabFrames(p, frames, kCrossSlabBytes, perFrame);
+    if (sgz_status st = ensureCap(&p.d_ovcBins, &p.ovcBinsCap, size_t(slab) * perFrame); st != SGZ_OK) return st;
+    return overviewSlabs(frames, slab, k, held, flush,
+                         [&](long f0, long nf) { return runStft(p, d_planar + size_t(f0) * p.cfg.hop, channel_stride, nf, nullptr, p.d_ovcBins, nullptr, s); },
+                         [&](size_t nf, uint32_t heldIn, int flushNow, size_t column, long) {
+                             return runOverviewCrossColumns(p, p.d_ovcBins, nf, k, heldIn, flushNow, 0, d_carry, at(d_cross, column * perColumn), s);
                          });
 }
+static sgz_status crossOverviewReady(sgz_plan *plan)
+{
+    if (sgz_status st = crossOverviewSupported(plan->impl); st != SGZ_OK) return st;
+    if (!plan->impl.crossBands) return fail(SGZ_EINVAL, "overview cross: the plan has no band table (sgz_plan_set_cross_edges)");
+    return SGZ_OK;
+}
+sgz_status sgz::fluxOverviewSupported(const Plan &p)
+{
+    if (isResonator(p)) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces transform magnitudes: RSNT plans are not supported");
+    if (p.cfg.channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces magnitudes: Phase mode's second plane is none");
+    return SGZ_OK;
+}
+// The flux overview's slabs: the open column in d_carry, a slab's last frame in d_prev for the next slab's first.
+sgz_status sgz::runOverviewFluxSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
+                                     uint64_t firstFrame, float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry,
+                                     sgz_overview_flux_record *d_flux, hipStream_t s)
+{
+    Plan &p = plan->impl;
+    const size_t perColumn = size_t(p.C) * p.sides;
+    return overviewMappedSlabs(p, d_planar, channel_stride, frames, k, held, flush, s, [&](size_t nf, uint32_t heldIn, int flushNow, size_t column, long f0) {
+        return runOverviewFluxColumns(p, p.d_mapped, nf, k, heldIn, flushNow, firstFrame + uint64_t(f0), 0, d_prev, prevValid || f0 > 0, d_carry,
+                                      at(d_flux, column * perColumn), s);
+    });
+}
+
+// ---- the host forms' staging, written once ---------------------------------------------------------------------------------------------------
+// One output of a host call: the caller's buffer (null: not asked for), the plan scratch block its device copy lives in, and its size as
+// elements per column and bytes per element.  The blocks are counted in floats, as every ensureCap block; every element here is whole floats.
+namespace {
+struct HostOut {
+    void *host; float **d_buf; size_t *cap; size_t perColumn, elemBytes;
+    template <typename T> T *dev() const { return host ? reinterpret_cast<T *>(*d_buf) : nullptr; }
+    size_t bytes(size_t columns) const { return columns * perColumn * elemBytes; }
+};
+HostOut rgbaOut(Plan &p, uint8_t *rgba) { return {rgba, &p.d_hostRgba, &p.hostRgbaCap, p.P, 4}; }
+template <typename Record> HostOut recordsOut(Plan &p, OverviewKind kind, Record *records, size_t perColumn)
+{
+    return {records, &p.ov[kind].d_hostRecords, &p.ov[kind].hostRecordsCap, perColumn, sizeof(Record)};
+}
+HostOut valuesOut(Plan &p, OverviewKind kind, float *values, size_t perColumn) { return {values, &p.ov[kind].d_hostValues, &p.ov[kind].hostValuesCap, perColumn, sizeof(float)}; }
+
+template <size_t N> sgz_status reserveHostOuts(const HostOut (&outs)[N], size_t columns)
+{
+    for (const HostOut &o : outs)
+        if (o.host)
+            if (sgz_status st = ensureCap(o.d_buf, o.cap, o.bytes(columns) / sizeof(float)); st != SGZ_OK) return st;
+    return SGZ_OK;
+}
+// behind the device call: ev[2], every output's `columns` columns to the caller, ev[3], the wait, the timing (`frames`: what it reports)
+template <size_t N> sgz_status readBackHostOuts(const HostOut (&outs)[N], size_t columns, hipStream_t s, hipEvent_t ev[4], sgz_timing *timing, long frames)
+{
+    SGZ_HIP(hipEventRecord(ev[2], s));
+    for (const HostOut &o : outs)
+        if (o.host) SGZ_HIP(hipMemcpyAsync(o.host, *o.d_buf, o.bytes(columns), hipMemcpyDeviceToHost, s));
+    SGZ_HIP(hipEventRecord(ev[3], s));
+    SGZ_HIP(hipStreamSynchronize(s));
+    if (timing) fillHostTiming(*timing, ev, frames);
+    return SGZ_OK;
+}
+// what every host render refuses behind its own first refusals and in front of its kind's support check
+sgz_status checkHostChannels(const Plan &p, const float *const *planar, uint32_t num_channels)
+{
+    if (num_channels != 2 * p.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
+    for (uint32_t c = 0; c < num_channels; ++c)
+        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
+    return SGZ_OK;
+}
+// A host render from checkReady on: the audio up on the plan's own stream, device(d_audio, stride, stream) -- the one call of the kind's device
+// form, on the outputs' device copies --, and the columns back.
+template <size_t N, typename Device>
+sgz_status overviewHostRender(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k, const HostOut (&outs)[N],
+                              sgz_timing *timing, Device device)
+{
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
+    const size_t columns = (size_t(frames) + k - 1) / k;
+    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
+    if ((st = reserveHostOuts(outs, columns)) != SGZ_OK) return st;
+    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
+    if ((st = device(p.d_hostAudio, stride, s)) != SGZ_OK) return st;
+    return readBackHostOuts(outs, columns, s, ev, timing, frames);
+}
+// A host view from checkReady on: only the range's columns [x0, x1) of `src` -- perColumn elements of sizeof(Record) each -- are uploaded, into
+// the kind's plan scratch, on the plan's own stream; run(d_in, m, stream), the stage call, runs behind the upload and the `cols` columns are
+// read back.
+template <typename Record, size_t N, typename Run>
+sgz_status overviewHostView(sgz_plan *plan, OverviewKind kind, const Record *src, size_t perColumn, size_t x0, size_t x1, size_t cols, const HostOut (&outs)[N],
+                            sgz_timing *timing, Run run)
+{
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4];
+    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
+    const size_t m = x1 - x0;
+    if ((st = ensureCap(&p.ov[kind].d_viewIn, &p.ov[kind].viewInCap, m * perColumn * (sizeof(Record) / sizeof(float)))) != SGZ_OK) return st;
+    if ((st = reserveHostOuts(outs, cols)) != SGZ_OK) return st;
+    Record *d_in = reinterpret_cast<Record *>(p.ov[kind].d_viewIn);
+    SGZ_HIP(hipEventRecord(ev[0], s));
+    SGZ_HIP(hipMemcpyAsync(d_in, src + x0 * perColumn, m * perColumn * sizeof(Record), hipMemcpyHostToDevice, s));
+    SGZ_HIP(hipEventRecord(ev[1], s));
+    if ((st = run(d_in, m, s)) != SGZ_OK) return st;
+    return readBackHostOuts(outs, cols, s, ev, timing, long(cols));         // (frames: the columns returned)
+}
+// a kind's carry in plan scratch, grown to `records` records
+template <typename Record> sgz_status planCarry(Plan &p, OverviewKind kind, size_t records, Record **d_carry)
+{
+    const sgz_status st = ensureCap(&p.ov[kind].d_carry, &p.ov[kind].carryCap, records * (sizeof(Record) / sizeof(float)));
+    *d_carry = reinterpret_cast<Record *>(p.ov[kind].d_carry);
+    return st;
+}
+}  // namespace
+
 extern "C" {
 sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
                                            uint8_t *d_rgba, float *d_peaks, float *d_state, void *stream)
@@ -1142,8 +1322,9 @@ sgz_status sgz_spectrogram_overview_device(sgz_plan *plan, const float *d_planar
     Plan &p = plan->impl;
     const long frames = planFrames(p, nsamples);
     if (frames <= 0) return SGZ_SKIPPED_FRAME;
-    if ((st = ensureCap(&p.d_ovCarry, &p.ovCarryCap, size_t(p.C) * p.P)) != SGZ_OK) return st;
-    return runOverviewSlabs(plan, d_planar, channel_stride, nsamples, frames, k, 0, 1, p.d_ovCarry, d_state, d_rgba, d_peaks, reinterpret_cast<hipStream_t>(stream));
+    float *d_carry = nullptr;
+    if ((st = planCarry(p, kOvPeaks, size_t(p.C) * p.P, &d_carry)) != SGZ_OK) return st;
+    return runOverviewSlabs(plan, d_planar, channel_stride, nsamples, frames, k, 0, 1, d_carry, d_state, d_rgba, d_peaks, reinterpret_cast<hipStream_t>(stream));
 }
 
 sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
@@ -1152,68 +1333,28 @@ sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *pla
     if (!plan || !planar) return fail(SGZ_EINVAL, "null argument");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
-    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
-    for (uint32_t c = 0; c < num_channels; ++c)
-        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
-    sgz_status st = checkReady(plan);
-    if (st != SGZ_OK) return st;
     Plan &p = plan->impl;
-    const long frames = planFrames(p, nsamples);
-    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4];
-    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
-    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
-    const size_t columns = (size_t(frames) + k - 1) / k;
-    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
-    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, columns * p.P)) != SGZ_OK) return st;
-    if (peaks_out && (st = ensureCap(&p.d_hostOvPeaks, &p.hostOvPeaksCap, columns * p.C * p.P)) != SGZ_OK) return st;
-    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
-    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
-    float *d_peaks = peaks_out ? p.d_hostOvPeaks : nullptr;
-    st = sgz_spectrogram_overview_device(plan, p.d_hostAudio, stride, nsamples, k, d_rgba, d_peaks, nullptr, s);
-    if (st != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[2], s));
-    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, columns * p.P * 4, hipMemcpyDeviceToHost, s));
-    if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaks_out, d_peaks, columns * p.C * p.P * sizeof(float), hipMemcpyDeviceToHost, s));
-    SGZ_HIP(hipEventRecord(ev[3], s));
-    SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) fillHostTiming(*timing, ev, frames);
-    return SGZ_OK;
+    if (sgz_status st = checkHostChannels(p, planar, num_channels); st != SGZ_OK) return st;
+    const HostOut outs[] = {rgbaOut(p, rgba_out), recordsOut(p, kOvPeaks, peaks_out, size_t(p.C) * p.P)};
+    return overviewHostRender(plan, planar, num_channels, nsamples, k, outs, timing, [&](const float *d_audio, size_t stride, hipStream_t s) {
+        return sgz_spectrogram_overview_device(plan, d_audio, stride, nsamples, k, outs[0].dev<uint8_t>(), outs[1].dev<float>(), nullptr, s);
+    });
 }
 
-// The view of kept peaks from HOST peaks (sgz.h; overview.hip): only the range's columns are uploaded, into plan scratch, on the plan's own
-// stream; the stage call runs behind the upload and the `cols` columns are read back.
+// The view of kept peaks from HOST peaks (sgz.h; overview.hip).
 sgz_status sgz_overview_view_host(sgz_plan *plan, const float *peaks, size_t n, size_t x0, size_t x1, uint32_t out_columns, uint8_t *rgba_out,
                                   float *peaks_out, sgz_timing *timing)
 {
     if (!plan || !peaks) return fail(SGZ_EINVAL, "null argument");
     uint64_t cols = 0;
-    sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols);
-    if (st != SGZ_OK) return st;
+    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
     if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "sgz_overview_view_host: an image, the peaks or both");
-    if ((st = checkReady(plan)) != SGZ_OK) return st;
     Plan &p = plan->impl;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4];
-    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
-    const size_t column = size_t(p.C) * p.P, m = x1 - x0;
-    if ((st = ensureCap(&p.d_ovViewIn, &p.ovViewInCap, m * column)) != SGZ_OK) return st;
-    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, size_t(cols) * p.P)) != SGZ_OK) return st;
-    if (peaks_out && (st = ensureCap(&p.d_hostOvPeaks, &p.hostOvPeaksCap, size_t(cols) * column)) != SGZ_OK) return st;
-    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
-    float *d_out = peaks_out ? p.d_hostOvPeaks : nullptr;
-    SGZ_HIP(hipEventRecord(ev[0], s));
-    SGZ_HIP(hipMemcpyAsync(p.d_ovViewIn, peaks + x0 * column, m * column * sizeof(float), hipMemcpyHostToDevice, s));
-    SGZ_HIP(hipEventRecord(ev[1], s));
-    if ((st = runOverviewView(p, p.d_ovViewIn, m, size_t(cols), 0, d_rgba, d_out, s)) != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[2], s));
-    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(cols) * p.P * 4, hipMemcpyDeviceToHost, s));
-    if (peaks_out) SGZ_HIP(hipMemcpyAsync(peaks_out, d_out, size_t(cols) * column * sizeof(float), hipMemcpyDeviceToHost, s));
-    SGZ_HIP(hipEventRecord(ev[3], s));
-    SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)
-    return SGZ_OK;
+    const size_t perColumn = size_t(p.C) * p.P;
+    const HostOut outs[] = {rgbaOut(p, rgba_out), recordsOut(p, kOvPeaks, peaks_out, perColumn)};
+    return overviewHostView(plan, kOvPeaks, peaks, perColumn, x0, x1, size_t(cols), outs, timing, [&](const float *d_in, size_t m, hipStream_t s) {
+        return runOverviewView(p, d_in, m, size_t(cols), 0, outs[0].dev<uint8_t>(), outs[1].dev<float>(), s);
+    });
 }
 
 // The mean overview's render and host view (sgz.h, "The mean overview"; overview_stats.hip): the peak-hold calls above with records in the place
@@ -1229,9 +1370,9 @@ sgz_status sgz_spectrogram_overview_stats_device(sgz_plan *plan, const float *d_
     Plan &p = plan->impl;
     const long frames = planFrames(p, nsamples);
     if (frames <= 0) return SGZ_SKIPPED_FRAME;
-    if ((st = ensureCap(&p.d_ovsCarry, &p.ovsCarryCap, size_t(p.C) * p.P * (sizeof(sgz_overview_stat_record) / sizeof(float)))) != SGZ_OK) return st;
-    return runOverviewStatsSlabs(plan, d_planar, channel_stride, nsamples, frames, k, 0, 1, reinterpret_cast<sgz_overview_stat_record *>(p.d_ovsCarry), d_state,
-                                 d_rgba, d_stats, d_means, reinterpret_cast<hipStream_t>(stream));
+    sgz_overview_stat_record *d_carry = nullptr;
+    if ((st = planCarry(p, kOvStats, size_t(p.C) * p.P, &d_carry)) != SGZ_OK) return st;
+    return runOverviewStatsSlabs(plan, d_planar, channel_stride, nsamples, frames, k, 0, 1, d_carry, d_state, d_rgba, d_stats, d_means, reinterpret_cast<hipStream_t>(stream));
 }
 
 sgz_status sgz_spectrogram_overview_stats_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
@@ -1240,110 +1381,32 @@ sgz_status sgz_spectrogram_overview_stats_host(sgz_plan *plan, const float *cons
     if (!plan || !planar) return fail(SGZ_EINVAL, "null argument");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
-    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
-    for (uint32_t c = 0; c < num_channels; ++c)
-        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
-    sgz_status st = checkReady(plan);
-    if (st != SGZ_OK) return st;
     Plan &p = plan->impl;
-    const long frames = planFrames(p, nsamples);
-    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4];
-    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
-    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
-    const size_t columns = (size_t(frames) + k - 1) / k, records = columns * p.C * p.P;
-    constexpr size_t recordFloats = sizeof(sgz_overview_stat_record) / sizeof(float);
-    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
-    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, columns * p.P)) != SGZ_OK) return st;
-    if (stats_out && (st = ensureCap(&p.d_hostOvStats, &p.hostOvStatsCap, records * recordFloats)) != SGZ_OK) return st;
-    if (means_out && (st = ensureCap(&p.d_hostOvMeans, &p.hostOvMeansCap, records)) != SGZ_OK) return st;
-    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
-    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
-    sgz_overview_stat_record *d_stats = stats_out ? reinterpret_cast<sgz_overview_stat_record *>(p.d_hostOvStats) : nullptr;
-    float *d_means = means_out ? p.d_hostOvMeans : nullptr;
-    st = sgz_spectrogram_overview_stats_device(plan, p.d_hostAudio, stride, nsamples, k, d_rgba, d_stats, d_means, nullptr, s);
-    if (st != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[2], s));
-    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, columns * p.P * 4, hipMemcpyDeviceToHost, s));
-    if (stats_out) SGZ_HIP(hipMemcpyAsync(stats_out, d_stats, records * sizeof(sgz_overview_stat_record), hipMemcpyDeviceToHost, s));
-    if (means_out) SGZ_HIP(hipMemcpyAsync(means_out, d_means, records * sizeof(float), hipMemcpyDeviceToHost, s));
-    SGZ_HIP(hipEventRecord(ev[3], s));
-    SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) fillHostTiming(*timing, ev, frames);
-    return SGZ_OK;
+    if (sgz_status st = checkHostChannels(p, planar, num_channels); st != SGZ_OK) return st;
+    const size_t perColumn = size_t(p.C) * p.P;
+    const HostOut outs[] = {rgbaOut(p, rgba_out), recordsOut(p, kOvStats, stats_out, perColumn), valuesOut(p, kOvStats, means_out, perColumn)};
+    return overviewHostRender(plan, planar, num_channels, nsamples, k, outs, timing, [&](const float *d_audio, size_t stride, hipStream_t s) {
+        return sgz_spectrogram_overview_stats_device(plan, d_audio, stride, nsamples, k, outs[0].dev<uint8_t>(), outs[1].dev<sgz_overview_stat_record>(),
+                                                     outs[2].dev<float>(), nullptr, s);
+    });
 }
 
-// The view of kept records from HOST records: only the range's columns are uploaded, into plan scratch, on the plan's own stream.
 sgz_status sgz_overview_stats_view_host(sgz_plan *plan, const sgz_overview_stat_record *stats, size_t n, size_t x0, size_t x1, uint32_t out_columns,
                                         uint8_t *rgba_out, sgz_overview_stat_record *stats_out, float *means_out, sgz_timing *timing)
 {
     if (!plan || !stats) return fail(SGZ_EINVAL, "null argument");
     uint64_t cols = 0;
-    sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols);
-    if (st != SGZ_OK) return st;
+    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
     if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "sgz_overview_stats_view_host: an image, the records, the means or any of them");
-    if ((st = checkReady(plan)) != SGZ_OK) return st;
     Plan &p = plan->impl;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4];
-    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
-    constexpr size_t recordFloats = sizeof(sgz_overview_stat_record) / sizeof(float);
-    const size_t column = size_t(p.C) * p.P, m = x1 - x0;
-    if ((st = ensureCap(&p.d_ovsViewIn, &p.ovsViewInCap, m * column * recordFloats)) != SGZ_OK) return st;
-    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, size_t(cols) * p.P)) != SGZ_OK) return st;
-    if (stats_out && (st = ensureCap(&p.d_hostOvStats, &p.hostOvStatsCap, size_t(cols) * column * recordFloats)) != SGZ_OK) return st;
-    if (means_out && (st = ensureCap(&p.d_hostOvMeans, &p.hostOvMeansCap, size_t(cols) * column)) != SGZ_OK) return st;
-    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
-    sgz_overview_stat_record *d_in = reinterpret_cast<sgz_overview_stat_record *>(p.d_ovsViewIn);
-    sgz_overview_stat_record *d_out = stats_out ? reinterpret_cast<sgz_overview_stat_record *>(p.d_hostOvStats) : nullptr;
-    float *d_means = means_out ? p.d_hostOvMeans : nullptr;
-    SGZ_HIP(hipEventRecord(ev[0], s));
-    SGZ_HIP(hipMemcpyAsync(d_in, stats + x0 * column, m * column * sizeof(sgz_overview_stat_record), hipMemcpyHostToDevice, s));
-    SGZ_HIP(hipEventRecord(ev[1], s));
-    if ((st = runOverviewStatsView(p, d_in, m, size_t(cols), 0, d_rgba, d_out, d_means, s)) != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[2], s));
-    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(cols) * p.P * 4, hipMemcpyDeviceToHost, s));
-    if (stats_out) SGZ_HIP(hipMemcpyAsync(stats_out, d_out, size_t(cols) * column * sizeof(sgz_overview_stat_record), hipMemcpyDeviceToHost, s));
-    if (means_out) SGZ_HIP(hipMemcpyAsync(means_out, d_means, size_t(cols) * column * sizeof(float), hipMemcpyDeviceToHost, s));
-    SGZ_HIP(hipEventRecord(ev[3], s));
-    SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)
-    return SGZ_OK;
+    const size_t perColumn = size_t(p.C) * p.P;
+    const HostOut outs[] = {rgbaOut(p, rgba_out), recordsOut(p, kOvStats, stats_out, perColumn), valuesOut(p, kOvStats, means_out, perColumn)};
+    return overviewHostView(plan, kOvStats, stats, perColumn, x0, x1, size_t(cols), outs, timing, [&](const sgz_overview_stat_record *d_in, size_t m, hipStream_t s) {
+        return runOverviewStatsView(p, d_in, m, size_t(cols), 0, outs[0].dev<uint8_t>(), outs[1].dev<sgz_overview_stat_record>(), outs[2].dev<float>(), s);
+    });
 }
 
-// The power overview's render and host view (sgz.h, "The power overview"; overview_power.hip).  The slab loop has no K_B in it: per slab K_A
-// into p.d_mapped -- sgz_stage_mapped's call, late pixels completed, because nothing behind it would -- and the reduction with the open column
-// carried.  The slab is counted as the overview's (the same option, the same default), so that one setting cuts all three renders alike.
-}  // extern "C"
-sgz_status sgz::powerOverviewSupported(const Plan &p)
-{
-    if (isResonator(p)) return fail(SGZ_EUNSUPPORTED, "the power overview reduces transform magnitudes: RSNT plans are not supported");
-    if (p.cfg.channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the power overview reduces magnitudes: Phase mode's second plane is none");
-    return SGZ_OK;
-}
-sgz_status sgz::runOverviewPowerSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
-                                      sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels,
-                                      hipStream_t s)
-{
-    Plan &p = plan->impl;
-    sgz_status st = SGZ_OK;
-    const size_t perFrameLines = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2, perFrame = size_t(p.C) * p.sides * p.P;
-    const long slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kOverviewSlabBytes / (perFrameLines * sizeof(float)))));
-    if ((st = ensureCap(&p.d_mapped, &p.mappedCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
-    for (long f0 = 0; f0 < frames; f0 += slab) {
-        const long nf = std::min(slab, frames - f0);
-        if ((st = runStft(p, d_planar + size_t(f0) * p.cfg.hop, channel_stride, nf, p.d_mapped, nullptr, nullptr, s)) != SGZ_OK) return st;
-        const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
-        const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
-        st = runOverviewPowerColumns(p, p.d_mapped, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, 0, d_carry,
-                                     d_rgba ? d_rgba + column * p.P * 4 : nullptr, d_power ? d_power + column * perFrame : nullptr,
-                                     d_levels ? d_levels + column * perFrame : nullptr, s);
-        if (st != SGZ_OK) return st;
-    }
-    return SGZ_OK;
-}
-extern "C" {
+// The power overview's render and host view (sgz.h, "The power overview"; overview_power.hip).
 sgz_status sgz_spectrogram_overview_power_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
                                                  uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels, void *stream)
 {
@@ -1356,9 +1419,9 @@ sgz_status sgz_spectrogram_overview_power_device(sgz_plan *plan, const float *d_
     Plan &p = plan->impl;
     const long frames = planFrames(p, nsamples);
     if (frames <= 0) return SGZ_SKIPPED_FRAME;
-    if ((st = ensureCap(&p.d_ovpCarry, &p.ovpCarryCap, size_t(p.C) * p.sides * p.P * (sizeof(sgz_overview_power_record) / sizeof(float)))) != SGZ_OK) return st;
-    return runOverviewPowerSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, reinterpret_cast<sgz_overview_power_record *>(p.d_ovpCarry), d_rgba,
-                                 d_power, d_levels, reinterpret_cast<hipStream_t>(stream));
+    sgz_overview_power_record *d_carry = nullptr;
+    if ((st = planCarry(p, kOvPower, size_t(p.C) * p.sides * p.P, &d_carry)) != SGZ_OK) return st;
+    return runOverviewPowerSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, d_carry, d_rgba, d_power, d_levels, reinterpret_cast<hipStream_t>(stream));
 }
 
 sgz_status sgz_spectrogram_overview_power_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
@@ -1367,110 +1430,33 @@ sgz_status sgz_spectrogram_overview_power_host(sgz_plan *plan, const float *cons
     if (!plan || !planar) return fail(SGZ_EINVAL, "null argument");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
     if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
-    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
-    for (uint32_t c = 0; c < num_channels; ++c)
-        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
-    sgz_status st = powerOverviewSupported(plan->impl);
-    if (st != SGZ_OK) return st;
-    if ((st = checkReady(plan)) != SGZ_OK) return st;
     Plan &p = plan->impl;
-    const long frames = planFrames(p, nsamples);
-    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4];
-    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
-    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
-    const size_t columns = (size_t(frames) + k - 1) / k, records = columns * p.C * p.sides * p.P;
-    constexpr size_t recordFloats = sizeof(sgz_overview_power_record) / sizeof(float);
-    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
-    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, columns * p.P)) != SGZ_OK) return st;
-    if (power_out && (st = ensureCap(&p.d_hostOvPower, &p.hostOvPowerCap, records * recordFloats)) != SGZ_OK) return st;
-    if (levels_out && (st = ensureCap(&p.d_hostOvLevels, &p.hostOvLevelsCap, records)) != SGZ_OK) return st;
-    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
-    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
-    sgz_overview_power_record *d_power = power_out ? reinterpret_cast<sgz_overview_power_record *>(p.d_hostOvPower) : nullptr;
-    float *d_levels = levels_out ? p.d_hostOvLevels : nullptr;
-    st = sgz_spectrogram_overview_power_device(plan, p.d_hostAudio, stride, nsamples, k, d_rgba, d_power, d_levels, s);
-    if (st != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[2], s));
-    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, columns * p.P * 4, hipMemcpyDeviceToHost, s));
-    if (power_out) SGZ_HIP(hipMemcpyAsync(power_out, d_power, records * sizeof(sgz_overview_power_record), hipMemcpyDeviceToHost, s));
-    if (levels_out) SGZ_HIP(hipMemcpyAsync(levels_out, d_levels, records * sizeof(float), hipMemcpyDeviceToHost, s));
-    SGZ_HIP(hipEventRecord(ev[3], s));
-    SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) fillHostTiming(*timing, ev, frames);
-    return SGZ_OK;
+    if (sgz_status st = checkHostChannels(p, planar, num_channels); st != SGZ_OK) return st;
+    if (sgz_status st = powerOverviewSupported(p); st != SGZ_OK) return st;
+    const size_t perColumn = size_t(p.C) * p.sides * p.P;
+    const HostOut outs[] = {rgbaOut(p, rgba_out), recordsOut(p, kOvPower, power_out, perColumn), valuesOut(p, kOvPower, levels_out, perColumn)};
+    return overviewHostRender(plan, planar, num_channels, nsamples, k, outs, timing, [&](const float *d_audio, size_t stride, hipStream_t s) {
+        return sgz_spectrogram_overview_power_device(plan, d_audio, stride, nsamples, k, outs[0].dev<uint8_t>(), outs[1].dev<sgz_overview_power_record>(),
+                                                     outs[2].dev<float>(), s);
+    });
 }
 
-// The view of kept power records from HOST records: only the range's columns are uploaded, into plan scratch, on the plan's own stream.
 sgz_status sgz_overview_power_view_host(sgz_plan *plan, const sgz_overview_power_record *power, size_t n, size_t x0, size_t x1, uint32_t out_columns,
                                         uint8_t *rgba_out, sgz_overview_power_record *power_out, float *levels_out, sgz_timing *timing)
 {
     if (!plan || !power) return fail(SGZ_EINVAL, "null argument");
     uint64_t cols = 0;
-    sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols);
-    if (st != SGZ_OK) return st;
+    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
     if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "sgz_overview_power_view_host: an image, the records, the levels or any of them");
-    if ((st = checkReady(plan)) != SGZ_OK) return st;
     Plan &p = plan->impl;
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4];
-    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
-    constexpr size_t recordFloats = sizeof(sgz_overview_power_record) / sizeof(float);
-    const size_t column = size_t(p.C) * p.sides * p.P, m = x1 - x0;
-    if ((st = ensureCap(&p.d_ovpViewIn, &p.ovpViewInCap, m * column * recordFloats)) != SGZ_OK) return st;
-    if (rgba_out && (st = ensureCap(&p.d_hostRgba, &p.hostRgbaCap, size_t(cols) * p.P)) != SGZ_OK) return st;
-    if (power_out && (st = ensureCap(&p.d_hostOvPower, &p.hostOvPowerCap, size_t(cols) * column * recordFloats)) != SGZ_OK) return st;
-    if (levels_out && (st = ensureCap(&p.d_hostOvLevels, &p.hostOvLevelsCap, size_t(cols) * column)) != SGZ_OK) return st;
-    uint8_t *d_rgba = rgba_out ? reinterpret_cast<uint8_t *>(p.d_hostRgba) : nullptr;
-    sgz_overview_power_record *d_in = reinterpret_cast<sgz_overview_power_record *>(p.d_ovpViewIn);
-    sgz_overview_power_record *d_out = power_out ? reinterpret_cast<sgz_overview_power_record *>(p.d_hostOvPower) : nullptr;
-    float *d_levels = levels_out ? p.d_hostOvLevels : nullptr;
-    SGZ_HIP(hipEventRecord(ev[0], s));
-    SGZ_HIP(hipMemcpyAsync(d_in, power + x0 * column, m * column * sizeof(sgz_overview_power_record), hipMemcpyHostToDevice, s));
-    SGZ_HIP(hipEventRecord(ev[1], s));
-    if ((st = runOverviewPowerView(p, d_in, m, size_t(cols), 0, d_rgba, d_out, d_levels, s)) != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[2], s));
-    if (rgba_out) SGZ_HIP(hipMemcpyAsync(rgba_out, d_rgba, size_t(cols) * p.P * 4, hipMemcpyDeviceToHost, s));
-    if (power_out) SGZ_HIP(hipMemcpyAsync(power_out, d_out, size_t(cols) * column * sizeof(sgz_overview_power_record), hipMemcpyDeviceToHost, s));
-    if (levels_out) SGZ_HIP(hipMemcpyAsync(levels_out, d_levels, size_t(cols) * column * sizeof(float), hipMemcpyDeviceToHost, s));
-    SGZ_HIP(hipEventRecord(ev[3], s));
-    SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) fillHostTiming(*timing, ev, long(cols));         // (frames: the columns returned)
-    return SGZ_OK;
+    const size_t perColumn = size_t(p.C) * p.sides * p.P;
+    const HostOut outs[] = {rgbaOut(p, rgba_out), recordsOut(p, kOvPower, power_out, perColumn), valuesOut(p, kOvPower, levels_out, perColumn)};
+    return overviewHostView(plan, kOvPower, power, perColumn, x0, x1, size_t(cols), outs, timing, [&](const sgz_overview_power_record *d_in, size_t m, hipStream_t s) {
+        return runOverviewPowerView(p, d_in, m, size_t(cols), 0, outs[0].dev<uint8_t>(), outs[1].dev<sgz_overview_power_record>(), outs[2].dev<float>(), s);
+    });
 }
 
-// The cross overview's render (sgz.h, "The cross overview"; overview_cross.hip).  Per slab K_A's complex bins into plan scratch -- runStft as
-// sgz_stage_bins calls it -- and the reduction with the open column carried.  No K_B, no decay state.  The slab is SGZ_OPT_OVERVIEW_SLAB's, or as
-// many whole frames as keep the slab's bins within 256 MiB.
-}  // extern "C"
-constexpr size_t kCrossSlabBytes = size_t(256) << 20;
-sgz_status sgz::runOverviewCrossSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
-                                      sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t s)
-{
-    Plan &p = plan->impl;
-    sgz_status st = SGZ_OK;
-    const size_t perFrame = size_t(p.C) * (size_t(p.N) + 1) * 2, perColumn = size_t(p.C) * p.crossBands;     // floats of a frame's bins; records of a column
-    const long slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kCrossSlabBytes / (perFrame * sizeof(float)))));
-    if ((st = ensureCap(&p.d_ovcBins, &p.ovcBinsCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
-    for (long f0 = 0; f0 < frames; f0 += slab) {
-        const long nf = std::min(slab, frames - f0);
-        if ((st = runStft(p, d_planar + size_t(f0) * p.cfg.hop, channel_stride, nf, nullptr, p.d_ovcBins, nullptr, s)) != SGZ_OK) return st;
-        const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
-        const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
-        st = runOverviewCrossColumns(p, p.d_ovcBins, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, 0, d_carry,
-                                     d_cross ? d_cross + column * perColumn : nullptr, s);
-        if (st != SGZ_OK) return st;
-    }
-    return SGZ_OK;
-}
-static sgz_status crossOverviewReady(sgz_plan *plan)
-{
-    if (sgz_status st = crossOverviewSupported(plan->impl); st != SGZ_OK) return st;
-    if (!plan->impl.crossBands) return fail(SGZ_EINVAL, "overview cross: the plan has no band table (sgz_plan_set_cross_edges)");
-    return SGZ_OK;
-}
-extern "C" {
+// The cross overview's render (sgz.h, "The cross overview"; overview_cross.hip).
 sgz_status sgz_spectrogram_overview_cross_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
                                                  sgz_overview_cross_record *d_cross, void *stream)
 {
@@ -1482,9 +1468,9 @@ sgz_status sgz_spectrogram_overview_cross_device(sgz_plan *plan, const float *d_
     Plan &p = plan->impl;
     const long frames = planFrames(p, nsamples);
     if (frames <= 0) return SGZ_SKIPPED_FRAME;
-    if ((st = ensureCap(&p.d_ovcCarry, &p.ovcCarryCap, size_t(p.C) * p.crossBands * (sizeof(sgz_overview_cross_record) / sizeof(float)))) != SGZ_OK) return st;
-    return runOverviewCrossSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, reinterpret_cast<sgz_overview_cross_record *>(p.d_ovcCarry), d_cross,
-                                 reinterpret_cast<hipStream_t>(stream));
+    sgz_overview_cross_record *d_carry = nullptr;
+    if ((st = planCarry(p, kOvCross, size_t(p.C) * p.crossBands, &d_carry)) != SGZ_OK) return st;
+    return runOverviewCrossSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, d_carry, d_cross, reinterpret_cast<hipStream_t>(stream));
 }
 
 sgz_status sgz_spectrogram_overview_cross_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
@@ -1492,65 +1478,16 @@ sgz_status sgz_spectrogram_overview_cross_host(sgz_plan *plan, const float *cons
 {
     if (!plan || !planar || !cross_out) return fail(SGZ_EINVAL, "null argument");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
-    for (uint32_t c = 0; c < num_channels; ++c)
-        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
-    sgz_status st = crossOverviewReady(plan);
-    if (st != SGZ_OK) return st;
-    if ((st = checkReady(plan)) != SGZ_OK) return st;
     Plan &p = plan->impl;
-    const long frames = planFrames(p, nsamples);
-    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4];
-    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
-    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
-    const size_t columns = (size_t(frames) + k - 1) / k, records = columns * p.C * p.crossBands;
-    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
-    if ((st = ensureCap(&p.d_hostOvCross, &p.hostOvCrossCap, records * (sizeof(sgz_overview_cross_record) / sizeof(float)))) != SGZ_OK) return st;
-    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
-    sgz_overview_cross_record *d_cross = reinterpret_cast<sgz_overview_cross_record *>(p.d_hostOvCross);
-    st = sgz_spectrogram_overview_cross_device(plan, p.d_hostAudio, stride, nsamples, k, d_cross, s);
-    if (st != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[2], s));
-    SGZ_HIP(hipMemcpyAsync(cross_out, d_cross, records * sizeof(sgz_overview_cross_record), hipMemcpyDeviceToHost, s));
-    SGZ_HIP(hipEventRecord(ev[3], s));
-    SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) fillHostTiming(*timing, ev, frames);
-    return SGZ_OK;
+    if (sgz_status st = checkHostChannels(p, planar, num_channels); st != SGZ_OK) return st;
+    if (sgz_status st = crossOverviewReady(plan); st != SGZ_OK) return st;
+    const HostOut outs[] = {recordsOut(p, kOvCross, cross_out, size_t(p.C) * p.crossBands)};
+    return overviewHostRender(plan, planar, num_channels, nsamples, k, outs, timing, [&](const float *d_audio, size_t stride, hipStream_t s) {
+        return sgz_spectrogram_overview_cross_device(plan, d_audio, stride, nsamples, k, outs[0].dev<sgz_overview_cross_record>(), s);
+    });
 }
 
-// The flux overview's render (sgz.h, "The flux overview"; overview_flux.hip).  The power overview's slab loop -- K_A into p.d_mapped with the late
-// pixels completed, counted by the same option and default -- with the flux reduction behind every slab: the open column in d_carry, the slab's
-// last frame in d_prev for the next slab's first.
-}  // extern "C"
-sgz_status sgz::fluxOverviewSupported(const Plan &p)
-{
-    if (isResonator(p)) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces transform magnitudes: RSNT plans are not supported");
-    if (p.cfg.channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces magnitudes: Phase mode's second plane is none");
-    return SGZ_OK;
-}
-sgz_status sgz::runOverviewFluxSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
-                                     uint64_t firstFrame, float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry,
-                                     sgz_overview_flux_record *d_flux, hipStream_t s)
-{
-    Plan &p = plan->impl;
-    sgz_status st = SGZ_OK;
-    const size_t perFrameLines = size_t(p.C) * SGZ_NUM_GRAPHS * p.P * 2, perFrame = size_t(p.C) * p.sides * p.P, perColumn = size_t(p.C) * p.sides;
-    const long slab = std::min<long>(frames, p.optOverviewSlab ? long(p.optOverviewSlab) : long(std::max<size_t>(1, kOverviewSlabBytes / (perFrameLines * sizeof(float)))));
-    if ((st = ensureCap(&p.d_mapped, &p.mappedCap, size_t(slab) * perFrame)) != SGZ_OK) return st;
-    for (long f0 = 0; f0 < frames; f0 += slab) {
-        const long nf = std::min(slab, frames - f0);
-        if ((st = runStft(p, d_planar + size_t(f0) * p.cfg.hop, channel_stride, nf, p.d_mapped, nullptr, nullptr, s)) != SGZ_OK) return st;
-        const size_t t0 = size_t(held) + size_t(f0);            // frames in front of this slab, the open column's included
-        const size_t column = t0 / k;                           // the column frame f0 belongs to: the carried one when t0 % k != 0
-        st = runOverviewFluxColumns(p, p.d_mapped, size_t(nf), k, uint32_t(t0 % k), flush && f0 + nf == frames, firstFrame + uint64_t(f0), 0, d_prev,
-                                    prevValid || f0 > 0, d_carry, d_flux ? d_flux + column * perColumn : nullptr, s);
-        if (st != SGZ_OK) return st;
-    }
-    return SGZ_OK;
-}
-extern "C" {
+// The flux overview's render (sgz.h, "The flux overview"; overview_flux.hip).
 sgz_status sgz_spectrogram_overview_flux_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
                                                 sgz_overview_flux_record *d_flux, void *stream)
 {
@@ -1564,10 +1501,10 @@ sgz_status sgz_spectrogram_overview_flux_device(sgz_plan *plan, const float *d_p
     const long frames = planFrames(p, nsamples);
     if (frames <= 0) return SGZ_SKIPPED_FRAME;
     const size_t rows = size_t(p.C) * p.sides;
-    if ((st = ensureCap(&p.d_ovfCarry, &p.ovfCarryCap, rows * (sizeof(sgz_overview_flux_record) / sizeof(float)))) != SGZ_OK) return st;
+    sgz_overview_flux_record *d_carry = nullptr;
+    if ((st = planCarry(p, kOvFlux, rows, &d_carry)) != SGZ_OK) return st;
     if ((st = ensureCap(&p.d_ovfPrev, &p.ovfPrevCap, rows * p.P)) != SGZ_OK) return st;
-    return runOverviewFluxSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, 0, p.d_ovfPrev, false, reinterpret_cast<sgz_overview_flux_record *>(p.d_ovfCarry),
-                                d_flux, reinterpret_cast<hipStream_t>(stream));
+    return runOverviewFluxSlabs(plan, d_planar, channel_stride, frames, k, 0, 1, 0, p.d_ovfPrev, false, d_carry, d_flux, reinterpret_cast<hipStream_t>(stream));
 }
 
 sgz_status sgz_spectrogram_overview_flux_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
@@ -1575,32 +1512,13 @@ sgz_status sgz_spectrogram_overview_flux_host(sgz_plan *plan, const float *const
 {
     if (!plan || !planar || !flux_out) return fail(SGZ_EINVAL, "null argument");
     if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (num_channels != 2 * plan->impl.C) return fail(SGZ_EINVAL, "num_channels must equal 2*num_pairs (SpectrumDSP.cpp:65-72)");
-    for (uint32_t c = 0; c < num_channels; ++c)
-        if (!planar[c]) return fail(SGZ_EINVAL, "null channel");
-    sgz_status st = fluxOverviewSupported(plan->impl);
-    if (st != SGZ_OK) return st;
-    if ((st = checkReady(plan)) != SGZ_OK) return st;
     Plan &p = plan->impl;
-    const long frames = planFrames(p, nsamples);
-    if (frames <= 0) { if (timing) *timing = sgz_timing{}; return SGZ_SKIPPED_FRAME; }
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4];
-    if ((st = hostStreamAndEvents(p, s, ev)) != SGZ_OK) return st;
-    const size_t stride = (nsamples + 63) & ~size_t(63);                    // 256-byte rows
-    const size_t columns = (size_t(frames) + k - 1) / k, records = columns * p.C * p.sides;
-    if ((st = ensureCap(&p.d_hostAudio, &p.hostAudioCap, size_t(num_channels) * stride)) != SGZ_OK) return st;
-    if ((st = ensureCap(&p.d_hostOvFlux, &p.hostOvFluxCap, records * (sizeof(sgz_overview_flux_record) / sizeof(float)))) != SGZ_OK) return st;
-    if ((st = uploadHostAudio(p, planar, num_channels, nsamples, stride, s, ev)) != SGZ_OK) return st;
-    sgz_overview_flux_record *d_flux = reinterpret_cast<sgz_overview_flux_record *>(p.d_hostOvFlux);
-    st = sgz_spectrogram_overview_flux_device(plan, p.d_hostAudio, stride, nsamples, k, d_flux, s);
-    if (st != SGZ_OK) return st;
-    SGZ_HIP(hipEventRecord(ev[2], s));
-    SGZ_HIP(hipMemcpyAsync(flux_out, d_flux, records * sizeof(sgz_overview_flux_record), hipMemcpyDeviceToHost, s));
-    SGZ_HIP(hipEventRecord(ev[3], s));
-    SGZ_HIP(hipStreamSynchronize(s));
-    if (timing) fillHostTiming(*timing, ev, frames);
-    return SGZ_OK;
+    if (sgz_status st = checkHostChannels(p, planar, num_channels); st != SGZ_OK) return st;
+    if (sgz_status st = fluxOverviewSupported(p); st != SGZ_OK) return st;
+    const HostOut outs[] = {recordsOut(p, kOvFlux, flux_out, size_t(p.C) * p.sides)};
+    return overviewHostRender(plan, planar, num_channels, nsamples, k, outs, timing, [&](const float *d_audio, size_t stride, hipStream_t s) {
+        return sgz_spectrogram_overview_flux_device(plan, d_audio, stride, nsamples, k, outs[0].dev<sgz_overview_flux_record>(), s);
+    });
 }
 
 // One-shot convenience: builds a plan for cfg, renders, destroys it.  Callers that render more than once keep the plan

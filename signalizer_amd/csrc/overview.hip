@@ -288,9 +288,9 @@ sgz_status runOverviewColumns(Plan &p, const float *d_lines, size_t frames, uint
     if (held && open && columns > 1) {
         // column 0's threads read the carry while the open column's threads write it: they read a snapshot
         const size_t carryN = size_t(p.C) * p.P;
-        if (sgz_status st = ensureCap(&p.d_ovCarryCopy, &p.ovCarryCopyCap, carryN); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.d_ovCarryCopy, d_carry, carryN * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = p.d_ovCarryCopy;
+        if (sgz_status st = ensureCap(&p.ov[kOvPeaks].d_carryCopy, &p.ov[kOvPeaks].carryCopyCap, carryN); st != SGZ_OK) return st;
+        SGZ_HIP(hipMemcpyAsync(p.ov[kOvPeaks].d_carryCopy, d_carry, carryN * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        prm.carryIn = p.ov[kOvPeaks].d_carryCopy;
     }
     prm.slices = slices ? slices : overviewAutoSlices(long(columns), blocks, k, frames, numCUs());
     const dim3 grid(unsigned(columns * blocks));
@@ -299,8 +299,8 @@ sgz_status runOverviewColumns(Plan &p, const float *d_lines, size_t frames, uint
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sgz_status st = ensureCap(&p.d_ovPartial, &p.ovPartialCap, size_t(prm.slices) * size_t(columns) * p.C * p.P); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<uint32_t *>(p.d_ovPartial);
+    if (sgz_status st = ensureCap(&p.ov[kOvPeaks].d_partial, &p.ov[kOvPeaks].partialCap, size_t(prm.slices) * size_t(columns) * p.C * p.P); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<uint32_t *>(p.ov[kOvPeaks].d_partial);
     hipLaunchKernelGGL(overviewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(overviewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
@@ -338,8 +338,8 @@ sgz_status runOverviewView(Plan &p, const float *d_src, size_t m, size_t cols, u
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sgz_status st = ensureCap(&p.d_ovPartial, &p.ovPartialCap, size_t(prm.slices) * cols * p.C * p.P); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<uint32_t *>(p.d_ovPartial);
+    if (sgz_status st = ensureCap(&p.ov[kOvPeaks].d_partial, &p.ov[kOvPeaks].partialCap, size_t(prm.slices) * cols * p.C * p.P); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<uint32_t *>(p.ov[kOvPeaks].d_partial);
     hipLaunchKernelGGL(overviewViewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(overviewViewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);

@@ -355,14 +355,14 @@ sgz_status runOverviewCrossColumns(Plan &p, const float *d_bins, size_t frames, 
     if (held && open && columns > 1) {
         // column 0's threads read the carry while the open column's threads write it: they read a snapshot
         const size_t carryN = size_t(p.C) * B;
-        if (sgz_status st = ensureCap(&p.d_ovcCarryCopy, &p.ovcCarryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.d_ovcCarryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = reinterpret_cast<const Record *>(p.d_ovcCarryCopy);
+        if (sgz_status st = ensureCap(&p.ov[kOvCross].d_carryCopy, &p.ov[kOvCross].carryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
+        SGZ_HIP(hipMemcpyAsync(p.ov[kOvCross].d_carryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
+        prm.carryIn = reinterpret_cast<const Record *>(p.ov[kOvCross].d_carryCopy);
     }
     prm.slices = slices ? slices : overviewAutoSlices(long(columns), std::max(1u, p.C * tiles), k, frames, numCUs());
     if (frames > 0 && prm.pieces > 0) {
-        if (sgz_status st = ensureCap(&p.d_ovcPartial, &p.ovcPartialCap, size_t(prm.slices) * size_t(columns) * p.C * prm.pieces * kRecordFloats); st != SGZ_OK) return st;
-        prm.partial = reinterpret_cast<Record *>(p.d_ovcPartial);
+        if (sgz_status st = ensureCap(&p.ov[kOvCross].d_partial, &p.ov[kOvCross].partialCap, size_t(prm.slices) * size_t(columns) * p.C * prm.pieces * kRecordFloats); st != SGZ_OK) return st;
+        prm.partial = reinterpret_cast<Record *>(p.ov[kOvCross].d_partial);
         hipLaunchKernelGGL(overviewCrossTileKernel, dim3(unsigned(units), prm.slices), dim3(kTile), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
     } else {

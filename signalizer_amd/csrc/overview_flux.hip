@@ -439,9 +439,9 @@ sgz_status runOverviewFluxColumns(Plan &p, const float *d_mapped, size_t frames,
     const uint64_t groups = (columns + prm.G - 1) / prm.G;
     if (held && open && columns > 1) {
         // column 0's workgroup reads the carry while the open column's writes it: it reads a snapshot
-        if (sgz_status st = ensureCap(&p.d_ovfCarryCopy, &p.ovfCarryCopyCap, size_t(R) * kRecordFloats); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.d_ovfCarryCopy, d_carry, size_t(R) * sizeof(Record), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = reinterpret_cast<const Record *>(p.d_ovfCarryCopy);
+        if (sgz_status st = ensureCap(&p.ov[kOvFlux].d_carryCopy, &p.ov[kOvFlux].carryCopyCap, size_t(R) * kRecordFloats); st != SGZ_OK) return st;
+        SGZ_HIP(hipMemcpyAsync(p.ov[kOvFlux].d_carryCopy, d_carry, size_t(R) * sizeof(Record), hipMemcpyDeviceToDevice, stream));
+        prm.carryIn = reinterpret_cast<const Record *>(p.ov[kOvFlux].d_carryCopy);
     }
     if (prm.prevIn && prm.prevOut && (prm.slices > 1 || groups > 1)) {
         // ... and so for the previous frame, where frame 0's workgroup is not the last frame's (in one workgroup a pixel is read and written by one thread)
@@ -454,8 +454,8 @@ sgz_status runOverviewFluxColumns(Plan &p, const float *d_mapped, size_t frames,
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sgz_status st = ensureCap(&p.d_ovfPartial, &p.ovfPartialCap, size_t(prm.slices) * size_t(columns) * R * kRecordFloats); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<Record *>(p.d_ovfPartial);
+    if (sgz_status st = ensureCap(&p.ov[kOvFlux].d_partial, &p.ov[kOvFlux].partialCap, size_t(prm.slices) * size_t(columns) * R * kRecordFloats); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<Record *>(p.ov[kOvFlux].d_partial);
     launchSlices(p.P, dim3(unsigned(columns * R), prm.slices), stream, prm);
     SGZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(overviewFluxEmitKernel, dim3(unsigned((columns * R + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, prm);

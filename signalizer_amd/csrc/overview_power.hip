@@ -404,9 +404,9 @@ sgz_status runOverviewPowerColumns(Plan &p, const float *d_mapped, size_t frames
     if (held && open && columns > 1) {
         // column 0's threads read the carry while the open column's threads write it: they read a snapshot
         const size_t carryN = size_t(p.C) * sp;
-        if (sgz_status st = ensureCap(&p.d_ovpCarryCopy, &p.ovpCarryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.d_ovpCarryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = reinterpret_cast<const Record *>(p.d_ovpCarryCopy);
+        if (sgz_status st = ensureCap(&p.ov[kOvPower].d_carryCopy, &p.ov[kOvPower].carryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
+        SGZ_HIP(hipMemcpyAsync(p.ov[kOvPower].d_carryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
+        prm.carryIn = reinterpret_cast<const Record *>(p.ov[kOvPower].d_carryCopy);
     }
     prm.slices = slices ? slices : overviewAutoSlices(long(columns), blocks, k, frames, numCUs());
     const dim3 grid(unsigned(columns * blocks));
@@ -415,8 +415,8 @@ sgz_status runOverviewPowerColumns(Plan &p, const float *d_mapped, size_t frames
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sgz_status st = ensureCap(&p.d_ovpPartial, &p.ovpPartialCap, size_t(prm.slices) * size_t(columns) * p.C * sp * kRecordFloats); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<Record *>(p.d_ovpPartial);
+    if (sgz_status st = ensureCap(&p.ov[kOvPower].d_partial, &p.ov[kOvPower].partialCap, size_t(prm.slices) * size_t(columns) * p.C * sp * kRecordFloats); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<Record *>(p.ov[kOvPower].d_partial);
     hipLaunchKernelGGL(overviewPowerSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(overviewPowerEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
@@ -444,8 +444,8 @@ sgz_status runOverviewPowerView(Plan &p, const sgz_overview_power_record *d_src,
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sgz_status st = ensureCap(&p.d_ovpPartial, &p.ovpPartialCap, size_t(prm.slices) * cols * p.C * sp * kRecordFloats); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<Record *>(p.d_ovpPartial);
+    if (sgz_status st = ensureCap(&p.ov[kOvPower].d_partial, &p.ov[kOvPower].partialCap, size_t(prm.slices) * cols * p.C * sp * kRecordFloats); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<Record *>(p.ov[kOvPower].d_partial);
     hipLaunchKernelGGL(overviewPowerViewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(overviewPowerViewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);

@@ -380,9 +380,9 @@ sgz_status runOverviewStatsColumns(Plan &p, const float *d_lines, size_t frames,
     if (held && open && columns > 1) {
         // column 0's threads read the carry while the open column's threads write it: they read a snapshot
         const size_t carryN = size_t(p.C) * p.P;
-        if (sgz_status st = ensureCap(&p.d_ovsCarryCopy, &p.ovsCarryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.d_ovsCarryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = reinterpret_cast<const Record *>(p.d_ovsCarryCopy);
+        if (sgz_status st = ensureCap(&p.ov[kOvStats].d_carryCopy, &p.ov[kOvStats].carryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
+        SGZ_HIP(hipMemcpyAsync(p.ov[kOvStats].d_carryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
+        prm.carryIn = reinterpret_cast<const Record *>(p.ov[kOvStats].d_carryCopy);
     }
     prm.slices = slices ? slices : overviewAutoSlices(long(columns), blocks, k, frames, numCUs());
     const dim3 grid(unsigned(columns * blocks));
@@ -391,8 +391,8 @@ sgz_status runOverviewStatsColumns(Plan &p, const float *d_lines, size_t frames,
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sgz_status st = ensureCap(&p.d_ovsPartial, &p.ovsPartialCap, size_t(prm.slices) * size_t(columns) * p.C * p.P * kRecordFloats); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<Record *>(p.d_ovsPartial);
+    if (sgz_status st = ensureCap(&p.ov[kOvStats].d_partial, &p.ov[kOvStats].partialCap, size_t(prm.slices) * size_t(columns) * p.C * p.P * kRecordFloats); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<Record *>(p.ov[kOvStats].d_partial);
     hipLaunchKernelGGL(overviewStatsSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(overviewStatsEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
@@ -419,8 +419,8 @@ sgz_status runOverviewStatsView(Plan &p, const sgz_overview_stat_record *d_src, 
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sgz_status st = ensureCap(&p.d_ovsPartial, &p.ovsPartialCap, size_t(prm.slices) * cols * p.C * p.P * kRecordFloats); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<Record *>(p.d_ovsPartial);
+    if (sgz_status st = ensureCap(&p.ov[kOvStats].d_partial, &p.ov[kOvStats].partialCap, size_t(prm.slices) * cols * p.C * p.P * kRecordFloats); st != SGZ_OK) return st;
+    prm.partial = reinterpret_cast<Record *>(p.ov[kOvStats].d_partial);
     hipLaunchKernelGGL(overviewStatsViewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
     SGZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(overviewStatsViewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);

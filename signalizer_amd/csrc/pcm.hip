@@ -320,9 +320,8 @@ struct PcmLane {
     size_t scratchCap = 0;
 };
 
-enum PcmOvKind { kOvPeaks, kOvStats, kOvPower, kOvCross, kOvFlux, kPcmOvKinds };
-// how a refusal names an open column's kind, and the feed that flushes it
-static const struct { const char *word, *call; } kPcmOvKindText[kPcmOvKinds] = {
+// how a refusal names an open column's kind (plan.hpp OverviewKind), and the feed that flushes it
+static const struct { const char *word, *call; } kPcmOvKindText[kOverviewKinds] = {
     {"peak-hold", "sgz_pcm_stream_feed_overview"},       {"mean", "sgz_pcm_stream_feed_overview_stats"}, {"power", "sgz_pcm_stream_feed_overview_power"},
     {"cross", "sgz_pcm_stream_feed_overview_cross"},     {"flux", "sgz_pcm_stream_feed_overview_flux"},
 };
@@ -339,20 +338,16 @@ struct sgz_pcm_stream {
     float *d_state = nullptr;
     int cur = 0;
     uint64_t held = 0, pieces = 0;
-    // the overview inside the stream: the open column's V [pairs][P], its frame count and its k (meaningful while ovOpen > 0)
-    float *d_ovCarry = nullptr;
+    // the overview inside the stream: the open column's frame count, its k and its kind (meaningful while ovOpen > 0), and every kind's carry,
+    // made on first use: the peak hold's V [pairs][P], the mean overview's records [pairs][P] (sgz.h, "The mean overview"), the power overview's
+    // [pairs][sides][P] ("The power overview"), the cross overview's [pairs][bands], by the band table of the stream's plan and made with it ("The
+    // cross overview"), the flux overview's [pairs][sides] ("The flux overview")
     uint64_t ovOpen = 0; uint32_t ovK = 0;
-    // the open column is of one kind (meaningful while ovOpen > 0): the peak hold's, the mean overview's -- its records [pairs][P] in
-    // d_ovStatCarry (sgz.h, "The mean overview") --, the power overview's -- [pairs][sides][P] in d_ovPowerCarry ("The power overview") -- or the
-    // cross overview's -- [pairs][bands] in d_ovCrossCarry, by the band table of the stream's plan ("The cross overview")
-    PcmOvKind ovKind = kOvPeaks;
-    sgz_overview_stat_record *d_ovStatCarry = nullptr;
-    sgz_overview_power_record *d_ovPowerCarry = nullptr;
-    sgz_overview_cross_record *d_ovCrossCarry = nullptr;
-    // ... or the flux overview's -- [pairs][sides] in d_ovFluxCarry ("The flux overview").  That overview also keeps, across feeds, the last frame's
-    // mapped magnitudes [pairs][sides][P] in d_ovFluxPrev -- fluxLinked: they are the frame in front of the next one, which no reset and no feed of
-    // another kind has consumed frames since -- and frameIndex, the frames the stream has completed since it was made or reset, in any kind of feed
-    sgz_overview_flux_record *d_ovFluxCarry = nullptr;
+    OverviewKind ovKind = kOvPeaks;
+    void *d_ovCarry[kOverviewKinds] = {};
+    // The flux overview also keeps, across feeds, the last frame's mapped magnitudes [pairs][sides][P] in d_ovFluxPrev -- fluxLinked: they are the
+    // frame in front of the next one, which no reset and no feed of another kind has consumed frames since -- and frameIndex, the frames the
+    // stream has completed since it was made or reset, in any kind of feed
     float *d_ovFluxPrev = nullptr;
     bool fluxLinked = false;
     uint64_t frameIndex = 0;
@@ -373,7 +368,6 @@ struct sgz_pcm_stream {
 struct sgz_plan { Plan impl; };
 
 using PcmClock = std::chrono::steady_clock;
-struct PcmFluxPart;
 static double pcmMsSince(PcmClock::time_point t0) { return std::chrono::duration<double, std::milli>(PcmClock::now() - t0).count(); }
 
 static size_t pcmStateBytes(const sgz_pcm_stream &s) { return size_t(s.cfg.num_pairs) * SGZ_NUM_GRAPHS * s.cfg.axis_points * 2 * sizeof(float); }
@@ -566,7 +560,8 @@ static sgz_status pcmLaneFlush(sgz_pcm_stream *s, int id)
 //   3. read back         read-back stream, behind ev[4]: the Part's rows, then every sink's units in kReadBackOrder
 // The two kinds of feed differ in their Part alone: reserve(s, sl) makes its outputs in a slot before anything is consumed; render(s, sl,
 // planar, total, frames, last, &units) enqueues the render of a piece's frames and says how many rows -- `units`, what the feed counts and its
-// timing reports -- it leaves in the slot; readBack(s, sl, done, units) enqueues their copies behind the feed's `done` earlier rows.
+// timing reports -- it leaves in the slot; readBack(s, sl, done, units) enqueues their copies behind the feed's `done` earlier rows;
+// fluxPiece(): its pieces leave the stream's last frame where the next flux feed finds it.
 // emptyPiece: a feed without samples has one piece all the same (the overview's flush of an open column).
 template <typename Part>
 static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, bool emptyPiece, Part &part, uint64_t *unitsOut, sgz_pcm_timing *timing,
@@ -610,7 +605,7 @@ static sgz_status pcmFeed(sgz_pcm_stream &s, const void *pcm, size_t nsamples, b
             const uint64_t total = s.held + n;
             if (sgz_status st = part.render(s, sl, planar, size_t(total), frames, at + n == nsamples, &units); st != SGZ_OK) return st;
             s.frameIndex += frames;
-            if (frames) s.fluxLinked = std::is_same<Part, PcmFluxPart>::value;      // (the flux overview's previous frame is the stream's last only behind a flux piece)
+            if (frames) s.fluxLinked = part.fluxPiece();                            // (the flux overview's previous frame is the stream's last only behind a flux piece)
             if (frames) {
                 if (keep) SGZ_HIP(hipMemcpy2DAsync(s.d_planar[s.cur ^ 1], s.stride * sizeof(float), planar + (total - keep), s.stride * sizeof(float),
                                                    size_t(keep) * sizeof(float), s.numChannels, hipMemcpyDeviceToDevice, s.compute));
@@ -656,6 +651,7 @@ struct PcmFramesPart {
     uint64_t need;                                                // the frames the whole feed yields
     bool rgbaPinned, linesPinned;
 
+    static bool fluxPiece() { return false; }
     sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
     {
         if (!need) return SGZ_OK;
@@ -680,235 +676,107 @@ struct PcmFramesPart {
     }
 };
 
-// sgz_pcm_stream_feed_overview's part: frames slab by slab into the columns they close, the open column in the stream's carry
-struct PcmColumnsPart {
-    uint8_t *rgba; float *peaks;
+// The overview feeds' part, of any kind: frames slab by slab into the columns they close, the open column in the stream's carry of the kind.
+// out[]: the outputs the call has, in the order the kind's hook takes them -- the slot's block, the bytes of one column, the caller's buffer
+// (null: not asked for).  firstUse[]: the device blocks the kind makes on its first feed (the cross carry is made with the band table).
+// run(s, sl, k, d_out, planar, total, frames, flush): frames > 0, the kind's slabs, on the compute stream; frames == 0, the Columns call that
+// flushes the open column alone.  d_out[i]: out[i]'s block in the slot, null where the caller asked for none or no column closes in this feed.
+// The power, cross and flux hooks have no K_B: the stream's decay state is neither read nor advanced, and there are no line results for a track
+// lane to search (their feeds refuse one)
+struct PcmOverviewPart {
+    using Run = sgz_status (*)(sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d_out[3], const float *planar, size_t total, uint64_t frames, int flush);
+    OverviewKind kind;
     uint32_t k; int flush;
-    uint64_t need;                                                // the columns the whole feed yields
-    bool rgbaPinned, peaksPinned;
+    Run run;
+    uint64_t need = 0;                                            // the columns the whole feed yields
+    struct Out { PcmOutKind slot; size_t unit; void *host; bool pinned; } out[3] = {};
+    int outs = 0;
+    struct { void **block; size_t bytes; } firstUse[2] = {};
 
+    void add(PcmOutKind slot, size_t unit, void *host) { out[outs++] = {slot, unit, host, false}; }
+    bool fluxPiece() const { return kind == kOvFlux; }
     sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
     {
-        if (!s.d_ovCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovCarry), pcmPeaksFloats(s, 1) * sizeof(float)));
+        for (const auto &f : firstUse)
+            if (f.block && !*f.block) SGZ_HIP(hipMalloc(f.block, f.bytes));
         if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
         // the most columns one piece can close: floor((k - 1 + maxFrames) / k) = ceil(maxFrames / k), and one more from a flush
         const size_t columns = (s.maxFrames + k - 1) / k + 1;
-        const sgz_status st = rgba ? sl.out[kOutOvImage].reserve(pcmImageBytes(s, columns), !rgbaPinned) : SGZ_OK;
-        if (st != SGZ_OK || !peaks) return st;
-        return sl.out[kOutOvPeaks].reserve(pcmPeaksFloats(s, columns) * sizeof(float), !peaksPinned);
+        for (int i = 0; i < outs; ++i)
+            if (out[i].host)
+                if (sgz_status st = sl.out[out[i].slot].reserve(columns * out[i].unit, !out[i].pinned); st != SGZ_OK) return st;
+        return SGZ_OK;
     }
     sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t total, uint64_t frames, bool last, uint64_t *units) const
     {
         const int pieceFlush = flush && last;
         const uint64_t t = s.ovOpen + frames;
         *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
-        uint8_t *d_rgba = rgba ? sl.out[kOutOvImage].as<uint8_t>() : nullptr;
-        float *d_peaks = peaks ? sl.out[kOutOvPeaks].as<float>() : nullptr;
-        sgz_status st = SGZ_OK;
-        if (frames) {
-            const SlabTrack track{s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>()};
-            st = runOverviewSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovCarry, s.d_state, d_rgba, d_peaks,
-                                  s.compute, s.track.armed() ? &track : nullptr);
-        } else if (*units) {                                       // no frame arrives and the open column is flushed
-            st = runOverviewColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovCarry, d_rgba, d_peaks, s.compute);
-        }
-        if (st != SGZ_OK) return st;
+        void *d_out[3] = {};
+        for (int i = 0; i < outs; ++i) d_out[i] = (out[i].host && need) ? sl.out[out[i].slot].dev : nullptr;
+        if (frames || *units)                                      // (no frame arrives: the open column is flushed, or nothing happens)
+            if (sgz_status st = run(s, sl, k, d_out, planar, total, frames, pieceFlush); st != SGZ_OK) return st;
         s.ovOpen = pieceFlush ? 0 : t % k;
         s.ovK = k;
-        s.ovKind = kOvPeaks;
+        s.ovKind = kind;
         return SGZ_OK;
     }
     sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
     {
-        const sgz_status st = rgba ? sl.out[kOutOvImage].readBack(rgba + pcmImageBytes(s, done), pcmImageBytes(s, columns), rgbaPinned, s.back) : SGZ_OK;
-        if (st != SGZ_OK || !peaks) return st;
-        return sl.out[kOutOvPeaks].readBack(peaks + pcmPeaksFloats(s, done), pcmPeaksFloats(s, columns) * sizeof(float), peaksPinned, s.back);
-    }
-};
-
-// sgz_pcm_stream_feed_overview_stats' part: PcmColumnsPart with the stats reduction behind every slab -- records and means in the place of peaks
-struct PcmStatsPart {
-    uint8_t *rgba; sgz_overview_stat_record *stats; float *means;
-    uint32_t k; int flush;
-    uint64_t need;                                                // the columns the whole feed yields
-    bool rgbaPinned, statsPinned, meansPinned;
-
-    static size_t records(const sgz_pcm_stream &s, uint64_t columns) { return pcmPeaksFloats(s, columns); }     // one per float of the peaks
-
-    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
-    {
-        if (!s.d_ovStatCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovStatCarry), records(s, 1) * sizeof(sgz_overview_stat_record)));
-        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
-        const size_t columns = (s.maxFrames + k - 1) / k + 1;     // the most one piece can close (PcmColumnsPart::reserve)
-        sgz_status st = rgba ? sl.out[kOutOvImage].reserve(pcmImageBytes(s, columns), !rgbaPinned) : SGZ_OK;
-        if (st == SGZ_OK && stats) st = sl.out[kOutOvStats].reserve(records(s, columns) * sizeof(sgz_overview_stat_record), !statsPinned);
-        if (st == SGZ_OK && means) st = sl.out[kOutOvMeans].reserve(records(s, columns) * sizeof(float), !meansPinned);
-        return st;
-    }
-    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t total, uint64_t frames, bool last, uint64_t *units) const
-    {
-        const int pieceFlush = flush && last;
-        const uint64_t t = s.ovOpen + frames;
-        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
-        uint8_t *d_rgba = rgba ? sl.out[kOutOvImage].as<uint8_t>() : nullptr;
-        sgz_overview_stat_record *d_stats = stats ? sl.out[kOutOvStats].as<sgz_overview_stat_record>() : nullptr;
-        float *d_means = means ? sl.out[kOutOvMeans].as<float>() : nullptr;
-        sgz_status st = SGZ_OK;
-        if (frames) {
-            const SlabTrack track{s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>()};
-            st = runOverviewStatsSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovStatCarry, s.d_state, d_rgba,
-                                       d_stats, d_means, s.compute, s.track.armed() ? &track : nullptr);
-        } else if (*units) {                                       // no frame arrives and the open column is flushed
-            st = runOverviewStatsColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovStatCarry, d_rgba, d_stats, d_means, s.compute);
-        }
-        if (st != SGZ_OK) return st;
-        s.ovOpen = pieceFlush ? 0 : t % k;
-        s.ovK = k;
-        s.ovKind = kOvStats;
+        for (int i = 0; i < outs; ++i)
+            if (out[i].host)
+                if (sgz_status st = sl.out[out[i].slot].readBack(static_cast<uint8_t *>(out[i].host) + done * out[i].unit, columns * out[i].unit, out[i].pinned, s.back); st != SGZ_OK) return st;
         return SGZ_OK;
     }
-    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
-    {
-        sgz_status st = rgba ? sl.out[kOutOvImage].readBack(rgba + pcmImageBytes(s, done), pcmImageBytes(s, columns), rgbaPinned, s.back) : SGZ_OK;
-        if (st == SGZ_OK && stats) st = sl.out[kOutOvStats].readBack(stats + records(s, done), records(s, columns) * sizeof(sgz_overview_stat_record), statsPinned, s.back);
-        if (st == SGZ_OK && means) st = sl.out[kOutOvMeans].readBack(means + records(s, done), records(s, columns) * sizeof(float), meansPinned, s.back);
-        return st;
-    }
 };
 
-// sgz_pcm_stream_feed_overview_power's part: the columns of PcmColumnsPart from the power reduction -- K_A and the reduction slab by slab, no K_B:
-// the stream's decay state is neither read nor advanced, and there are no line results for a track lane to search (the feed refuses one)
-struct PcmPowerPart {
-    uint8_t *rgba; sgz_overview_power_record *power; float *levels;
-    uint32_t k; int flush;
-    uint64_t need;                                                // the columns the whole feed yields
-    bool rgbaPinned, powerPinned, levelsPinned;
-
-    static size_t records(const sgz_pcm_stream &s, uint64_t columns) { return pcmPeaksFloats(s, columns) * size_t(s.plan->impl.sides); }
-
-    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
-    {
-        if (!s.d_ovPowerCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovPowerCarry), records(s, 1) * sizeof(sgz_overview_power_record)));
-        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
-        const size_t columns = (s.maxFrames + k - 1) / k + 1;     // the most one piece can close (PcmColumnsPart::reserve)
-        sgz_status st = rgba ? sl.out[kOutOvImage].reserve(pcmImageBytes(s, columns), !rgbaPinned) : SGZ_OK;
-        if (st == SGZ_OK && power) st = sl.out[kOutOvPower].reserve(records(s, columns) * sizeof(sgz_overview_power_record), !powerPinned);
-        if (st == SGZ_OK && levels) st = sl.out[kOutOvLevels].reserve(records(s, columns) * sizeof(float), !levelsPinned);
-        return st;
-    }
-    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t, uint64_t frames, bool last, uint64_t *units) const
-    {
-        const int pieceFlush = flush && last;
-        const uint64_t t = s.ovOpen + frames;
-        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
-        uint8_t *d_rgba = rgba ? sl.out[kOutOvImage].as<uint8_t>() : nullptr;
-        sgz_overview_power_record *d_power = power ? sl.out[kOutOvPower].as<sgz_overview_power_record>() : nullptr;
-        float *d_levels = levels ? sl.out[kOutOvLevels].as<float>() : nullptr;
-        sgz_status st = SGZ_OK;
-        if (frames) {
-            st = runOverviewPowerSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovPowerCarry, d_rgba, d_power, d_levels,
-                                       s.compute);
-        } else if (*units) {                                       // no frame arrives and the open column is flushed
-            st = runOverviewPowerColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovPowerCarry, d_rgba, d_power, d_levels, s.compute);
-        }
-        if (st != SGZ_OK) return st;
-        s.ovOpen = pieceFlush ? 0 : t % k;
-        s.ovK = k;
-        s.ovKind = kOvPower;
-        return SGZ_OK;
-    }
-    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
-    {
-        sgz_status st = rgba ? sl.out[kOutOvImage].readBack(rgba + pcmImageBytes(s, done), pcmImageBytes(s, columns), rgbaPinned, s.back) : SGZ_OK;
-        if (st == SGZ_OK && power) st = sl.out[kOutOvPower].readBack(power + records(s, done), records(s, columns) * sizeof(sgz_overview_power_record), powerPinned, s.back);
-        if (st == SGZ_OK && levels) st = sl.out[kOutOvLevels].readBack(levels + records(s, done), records(s, columns) * sizeof(float), levelsPinned, s.back);
-        return st;
-    }
-};
-
-// sgz_pcm_stream_feed_overview_cross's part: K_A's complex bins and the cross reduction slab by slab, no K_B: the stream's decay state is neither
-// read nor advanced, and there are no line results for a track lane to search (the feed refuses one).  The carry was made with the band table
-struct PcmCrossPart {
-    sgz_overview_cross_record *cross;
-    uint32_t k; int flush;
-    uint64_t need;                                                // the columns the whole feed yields
-    bool crossPinned;
-
-    static size_t records(const sgz_pcm_stream &s, uint64_t columns) { return size_t(columns) * s.cfg.num_pairs * s.plan->impl.crossBands; }
-
-    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
-    {
-        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
-        const size_t columns = (s.maxFrames + k - 1) / k + 1;     // the most one piece can close (PcmColumnsPart::reserve)
-        return sl.out[kOutOvCross].reserve(records(s, columns) * sizeof(sgz_overview_cross_record), !crossPinned);
-    }
-    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t, uint64_t frames, bool last, uint64_t *units) const
-    {
-        const int pieceFlush = flush && last;
-        const uint64_t t = s.ovOpen + frames;
-        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
-        sgz_overview_cross_record *d_cross = need ? sl.out[kOutOvCross].as<sgz_overview_cross_record>() : nullptr;
-        sgz_status st = SGZ_OK;
-        if (frames) {
-            st = runOverviewCrossSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.d_ovCrossCarry, d_cross, s.compute);
-        } else if (*units) {                                       // no frame arrives and the open column is flushed
-            st = runOverviewCrossColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, s.d_ovCrossCarry, d_cross, s.compute);
-        }
-        if (st != SGZ_OK) return st;
-        s.ovOpen = pieceFlush ? 0 : t % k;
-        s.ovK = k;
-        s.ovKind = kOvCross;
-        return SGZ_OK;
-    }
-    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
-    {
-        return sl.out[kOutOvCross].readBack(cross + records(s, done), records(s, columns) * sizeof(sgz_overview_cross_record), crossPinned, s.back);
-    }
-};
-
-// sgz_pcm_stream_feed_overview_flux's part: K_A's mapped magnitudes and the flux reduction slab by slab, no K_B: the stream's decay state is neither
-// read nor advanced, and there are no line results for a track lane to search (the feed refuses one).  The previous frame and the frame index are
-// the stream's (pcmFeed moves both on behind every piece)
-struct PcmFluxPart {
-    sgz_overview_flux_record *flux;
-    uint32_t k; int flush;
-    uint64_t need;                                                // the columns the whole feed yields
-    bool fluxPinned;
-
-    static size_t records(const sgz_pcm_stream &s, uint64_t columns) { return size_t(columns) * s.cfg.num_pairs * size_t(s.plan->impl.sides); }
-
-    sgz_status reserve(sgz_pcm_stream &s, PcmSlot &sl) const
-    {
-        if (!s.d_ovFluxCarry) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovFluxCarry), records(s, 1) * sizeof(sgz_overview_flux_record)));
-        if (!s.d_ovFluxPrev) SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s.d_ovFluxPrev), records(s, 1) * s.cfg.axis_points * sizeof(float)));
-        if (!need) return SGZ_OK;                                 // (no column closes: nothing is written or read back)
-        const size_t columns = (s.maxFrames + k - 1) / k + 1;     // the most one piece can close (PcmColumnsPart::reserve)
-        return sl.out[kOutOvFlux].reserve(records(s, columns) * sizeof(sgz_overview_flux_record), !fluxPinned);
-    }
-    sgz_status render(sgz_pcm_stream &s, PcmSlot &sl, const float *planar, size_t, uint64_t frames, bool last, uint64_t *units) const
-    {
-        const int pieceFlush = flush && last;
-        const uint64_t t = s.ovOpen + frames;
-        *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
-        sgz_overview_flux_record *d_flux = need ? sl.out[kOutOvFlux].as<sgz_overview_flux_record>() : nullptr;
-        sgz_status st = SGZ_OK;
-        if (frames) {
-            st = runOverviewFluxSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), pieceFlush, s.frameIndex, s.d_ovFluxPrev, s.fluxLinked,
-                                      s.d_ovFluxCarry, d_flux, s.compute);
-        } else if (*units) {                                       // no frame arrives and the open column is flushed
-            st = runOverviewFluxColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, s.frameIndex, 0, nullptr, false, s.d_ovFluxCarry, d_flux, s.compute);
-        }
-        if (st != SGZ_OK) return st;
-        s.ovOpen = pieceFlush ? 0 : t % k;
-        s.ovK = k;
-        s.ovKind = kOvFlux;
-        return SGZ_OK;
-    }
-    sgz_status readBack(sgz_pcm_stream &s, PcmSlot &sl, uint64_t done, uint64_t columns) const
-    {
-        return sl.out[kOutOvFlux].readBack(flux + records(s, done), records(s, columns) * sizeof(sgz_overview_flux_record), fluxPinned, s.back);
-    }
-};
+// the kinds' hooks.  The peak hold's and the mean overview's slabs render line results, which the track lane, armed, searches
+static sgz_status pcmPeaksRun(sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d[3], const float *planar, size_t total, uint64_t frames, int flush)
+{
+    float *carry = static_cast<float *>(s.d_ovCarry[kOvPeaks]);
+    uint8_t *d_rgba = static_cast<uint8_t *>(d[0]);
+    float *d_peaks = static_cast<float *>(d[1]);
+    if (!frames) return runOverviewColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, carry, d_rgba, d_peaks, s.compute);
+    const SlabTrack track{s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>()};
+    return runOverviewSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), flush, carry, s.d_state, d_rgba, d_peaks, s.compute,
+                            s.track.armed() ? &track : nullptr);
+}
+static sgz_status pcmStatsRun(sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d[3], const float *planar, size_t total, uint64_t frames, int flush)
+{
+    using Record = sgz_overview_stat_record;
+    Record *carry = static_cast<Record *>(s.d_ovCarry[kOvStats]), *d_stats = static_cast<Record *>(d[1]);
+    uint8_t *d_rgba = static_cast<uint8_t *>(d[0]);
+    float *d_means = static_cast<float *>(d[2]);
+    if (!frames) return runOverviewStatsColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, carry, d_rgba, d_stats, d_means, s.compute);
+    const SlabTrack track{s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>()};
+    return runOverviewStatsSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), flush, carry, s.d_state, d_rgba, d_stats, d_means,
+                                 s.compute, s.track.armed() ? &track : nullptr);
+}
+static sgz_status pcmPowerRun(sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[3], const float *planar, size_t, uint64_t frames, int flush)
+{
+    using Record = sgz_overview_power_record;
+    Record *carry = static_cast<Record *>(s.d_ovCarry[kOvPower]), *d_power = static_cast<Record *>(d[1]);
+    uint8_t *d_rgba = static_cast<uint8_t *>(d[0]);
+    float *d_levels = static_cast<float *>(d[2]);
+    if (!frames) return runOverviewPowerColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, carry, d_rgba, d_power, d_levels, s.compute);
+    return runOverviewPowerSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), flush, carry, d_rgba, d_power, d_levels, s.compute);
+}
+static sgz_status pcmCrossRun(sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[3], const float *planar, size_t, uint64_t frames, int flush)
+{
+    using Record = sgz_overview_cross_record;
+    Record *carry = static_cast<Record *>(s.d_ovCarry[kOvCross]), *d_cross = static_cast<Record *>(d[0]);
+    if (!frames) return runOverviewCrossColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, carry, d_cross, s.compute);
+    return runOverviewCrossSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), flush, carry, d_cross, s.compute);
+}
+// (the previous frame and the frame index are the stream's: pcmFeed moves both on behind every piece)
+static sgz_status pcmFluxRun(sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[3], const float *planar, size_t, uint64_t frames, int flush)
+{
+    using Record = sgz_overview_flux_record;
+    Record *carry = static_cast<Record *>(s.d_ovCarry[kOvFlux]), *d_flux = static_cast<Record *>(d[0]);
+    if (!frames) return runOverviewFluxColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, s.frameIndex, 0, nullptr, false, carry, d_flux, s.compute);
+    return runOverviewFluxSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), flush, s.frameIndex, s.d_ovFluxPrev, s.fluxLinked, carry, d_flux,
+                                s.compute);
+}
 
 // what the two one-shot calls share: a stream with no more device and pinned memory than the buffer needs, SGZ_SKIPPED_FRAME where nothing
 // comes out, the feed, and the wall time around all of it.  units(s): what the feed will yield; feed(s, units): the feed call
@@ -933,13 +801,13 @@ static sgz_status pcmOneShot(const sgz_spectrum_config *cfg, uint32_t format, ui
 }
 
 // The refusal of a feed while a column of another kind is open, written once: `feed` the refusing call's name; own: the kind the call could
-// continue (kPcmOvKinds: none -- sgz_pcm_stream_feed, whose text names the column first).  SGZ_OK: nothing stands in the way
+// continue (kOverviewKinds: none -- sgz_pcm_stream_feed, whose text names the column first).  SGZ_OK: nothing stands in the way
 static sgz_status pcmOpenColumnRefusal(const sgz_pcm_stream &s, const char *feed, int own)
 {
     if (!s.ovOpen || s.ovKind == own) return SGZ_OK;
     const auto &kind = kPcmOvKindText[s.ovKind];
     const std::string tail = std::string(" -- flush it (") + kind.call + ") or reset the stream first";
-    if (own == kPcmOvKinds)
+    if (own == kOverviewKinds)
         return fail(SGZ_EINVAL, std::string(feed) + (s.ovKind == kOvPeaks ? ": an overview column" : std::string(": a ") + kind.word + " overview's column") + " is open" + tail);
     return fail(SGZ_EINVAL, std::string(feed) + ": the open column is a " + kind.word + " overview's" + tail);
 }
@@ -951,6 +819,43 @@ static bool pcmOverviewNeed(const sgz_pcm_stream *s, size_t nsamples, uint32_t k
     const uint64_t t = s->ovOpen + sgz_pcm_stream_frames_for(s, nsamples);
     *columns = t / k + ((flush && t % k) ? 1u : 0u);
     return true;
+}
+
+// What the five overview feeds share, in the order every one of them refuses: the stream, the samples, k, then own() -- the call's checks of
+// its outputs and of the plan, which also fills part.out[] and part.firstUse[] --, a column of another kind, another k, the capacity, a missing
+// output the feed would write (text.nullOut; null: the call has refused a call without outputs before), the lanes.  The texts that name the call
+// are the call's own
+struct PcmOvTexts { const char *nullPcm, *kDiffers, *capacity, *nullOut; };
+template <typename Own>
+static sgz_status pcmOverviewFeed(sgz_pcm_stream *s, const void *pcm, size_t nsamples, const PcmOvTexts &text, PcmOverviewPart &part, uint64_t capacity_columns,
+                                  uint64_t *columns_out, sgz_pcm_timing *timing, Own own)
+{
+    const auto t0 = PcmClock::now();
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    if (!pcm && nsamples) return fail(SGZ_EINVAL, text.nullPcm);
+    if (part.k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (sgz_status st = own(); st != SGZ_OK) return st;
+    if (sgz_status st = pcmOpenColumnRefusal(*s, kPcmOvKindText[part.kind].call, part.kind); st != SGZ_OK) return st;
+    if (s->ovOpen && part.k != s->ovK) return fail(SGZ_EINVAL, text.kDiffers);
+    (void)pcmOverviewNeed(s, nsamples, part.k, part.flush, &part.need);
+    if (columns_out) *columns_out = part.need;
+    if (capacity_columns < part.need) return fail(SGZ_EINVAL, text.capacity);
+    if (text.nullOut && part.need && !part.out[0].host) return fail(SGZ_EINVAL, text.nullOut);
+    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
+    for (int i = 0; i < part.outs; ++i) part.out[i].pinned = part.need && part.out[i].host && isPinnedHost(part.out[i].host);
+    // (a feed without samples still has one piece when it flushes an open column)
+    return pcmFeed(*s, pcm, nsamples, part.flush && s->ovOpen, part, columns_out, timing, t0);
+}
+
+// ... and the five one-shots: the null arguments, k, own() -- the call's other refusals --, and the stream of pcmOneShot around feed(s, columns)
+template <typename Own, typename Feed>
+static sgz_status pcmOverviewOneShot(bool nullArgument, const sgz_spectrum_config *cfg, uint32_t format, uint32_t src_channels, const uint32_t *channel_map,
+                                     size_t nsamples, uint32_t k, sgz_pcm_timing *timing, Own own, Feed feed)
+{
+    if (nullArgument) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (sgz_status st = own(); st != SGZ_OK) return st;
+    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing, [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); }, feed);
 }
 
 extern "C" {
@@ -980,7 +885,8 @@ void sgz_pcm_stream_destroy(sgz_pcm_stream *s)
         for (PcmOut &o : sl.out) o.release();
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
     }
-    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovCarry, (void *)s->d_ovStatCarry, (void *)s->d_ovPowerCarry, (void *)s->d_ovCrossCarry, (void *)s->d_ovFluxCarry, (void *)s->d_ovFluxPrev}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->d_planar[0], (void *)s->d_planar[1], (void *)s->d_state, (void *)s->d_ovFluxPrev}) if (p) (void)hipFree(p);
+    for (void *p : s->d_ovCarry) if (p) (void)hipFree(p);
     for (PcmLane &l : s->lane)
         for (void *p : {l.d_carry, l.d_scratch}) if (p) (void)hipFree(p);
     for (hipStream_t q : {s->copy, s->compute, s->back}) if (q) (void)hipStreamDestroy(q);
@@ -1065,7 +971,7 @@ sgz_status sgz_pcm_stream_feed(sgz_pcm_stream *s, const void *pcm, size_t nsampl
     const auto t0 = PcmClock::now();
     if (!s) return fail(SGZ_EINVAL, "null stream");
     if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: null pcm");
-    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed", kPcmOvKinds); st != SGZ_OK) return st;
+    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed", kOverviewKinds); st != SGZ_OK) return st;
     const uint64_t need = sgz_pcm_stream_frames_for(s, nsamples);
     if (frames_out) *frames_out = need;
     if (capacity_frames < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed: capacity_frames below what this feed yields (see *frames_out)");
@@ -1102,32 +1008,24 @@ sgz_status sgz_pcm_stream_set_option(sgz_pcm_stream *s, uint32_t option, uint32_
 sgz_status sgz_pcm_stream_feed_overview(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush, uint8_t *rgba_out, float *peaks_out,
                                         uint64_t capacity_columns, uint64_t *columns_out, sgz_pcm_timing *timing)
 {
-    const auto t0 = PcmClock::now();
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: null pcm");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
-    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview", kOvPeaks); st != SGZ_OK) return st;
-    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: k differs from the open column's -- flush or reset first");
-    uint64_t need = 0;
-    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
-    if (columns_out) *columns_out = need;
-    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)");
-    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
-    PcmColumnsPart part{rgba_out, peaks_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && peaks_out && isPinnedHost(peaks_out)};
-    // (a feed without samples still has one piece when it flushes an open column)
-    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+    static const PcmOvTexts text = {"sgz_pcm_stream_feed_overview: null pcm", "sgz_pcm_stream_feed_overview: k differs from the open column's -- flush or reset first",
+                                    "sgz_pcm_stream_feed_overview: capacity_columns below what this feed yields (see *columns_out)", nullptr};
+    PcmOverviewPart part{kOvPeaks, k, flush, pcmPeaksRun};
+    return pcmOverviewFeed(s, pcm, nsamples, text, part, capacity_columns, columns_out, timing, [&]() -> sgz_status {
+        if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
+        part.add(kOutOvImage, pcmImageBytes(*s, 1), rgba_out);
+        part.add(kOutOvPeaks, pcmPeaksFloats(*s, 1) * sizeof(float), peaks_out);
+        part.firstUse[0] = {&s->d_ovCarry[kOvPeaks], pcmPeaksFloats(*s, 1) * sizeof(float)};
+        return SGZ_OK;
+    });
 }
 
 sgz_status sgz_spectrogram_overview_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                         const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out, float *peaks_out, sgz_pcm_timing *timing)
 {
-    if (!cfg || !pcm) return fail(SGZ_EINVAL, "null argument");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (!rgba_out && !peaks_out) return fail(SGZ_EINVAL, "overview: an image, the peaks or both");
-    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
-                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
-                      [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview(s, pcm, nsamples, k, 1, rgba_out, peaks_out, columns, &columns, timing); });
+    return pcmOverviewOneShot(!cfg || !pcm, cfg, format, src_channels, channel_map, nsamples, k, timing,
+                              [&] { return (!rgba_out && !peaks_out) ? fail(SGZ_EINVAL, "overview: an image, the peaks or both") : SGZ_OK; },
+                              [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview(s, pcm, nsamples, k, 1, rgba_out, peaks_out, columns, &columns, timing); });
 }
 
 // ---- the mean overview inside the stream (sgz.h, "The mean overview") ----------------------------------------------------------------------------
@@ -1135,35 +1033,28 @@ sgz_status sgz_pcm_stream_feed_overview_stats(sgz_pcm_stream *s, const void *pcm
                                               sgz_overview_stat_record *stats_out, float *means_out, uint64_t capacity_columns, uint64_t *columns_out,
                                               sgz_pcm_timing *timing)
 {
-    const auto t0 = PcmClock::now();
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: null pcm");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
-    if (reinterpret_cast<uintptr_t>(stats_out) % alignof(sgz_overview_stat_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: stats_out is not aligned to 8 bytes");
-    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview_stats", kOvStats); st != SGZ_OK) return st;
-    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: k differs from the open column's -- flush or reset first");
-    uint64_t need = 0;
-    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
-    if (columns_out) *columns_out = need;
-    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: capacity_columns below what this feed yields (see *columns_out)");
-    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
-    PcmStatsPart part{rgba_out, stats_out, means_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && stats_out && isPinnedHost(stats_out),
-                      need && means_out && isPinnedHost(means_out)};
-    // (a feed without samples still has one piece when it flushes an open column)
-    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+    static const PcmOvTexts text = {"sgz_pcm_stream_feed_overview_stats: null pcm", "sgz_pcm_stream_feed_overview_stats: k differs from the open column's -- flush or reset first",
+                                    "sgz_pcm_stream_feed_overview_stats: capacity_columns below what this feed yields (see *columns_out)", nullptr};
+    PcmOverviewPart part{kOvStats, k, flush, pcmStatsRun};
+    return pcmOverviewFeed(s, pcm, nsamples, text, part, capacity_columns, columns_out, timing, [&]() -> sgz_status {
+        if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
+        if (reinterpret_cast<uintptr_t>(stats_out) % alignof(sgz_overview_stat_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_stats: stats_out is not aligned to 8 bytes");
+        const size_t records = pcmPeaksFloats(*s, 1);                // one per float of the peaks
+        part.add(kOutOvImage, pcmImageBytes(*s, 1), rgba_out);
+        part.add(kOutOvStats, records * sizeof(sgz_overview_stat_record), stats_out);
+        part.add(kOutOvMeans, records * sizeof(float), means_out);
+        part.firstUse[0] = {&s->d_ovCarry[kOvStats], records * sizeof(sgz_overview_stat_record)};
+        return SGZ_OK;
+    });
 }
 
 sgz_status sgz_spectrogram_overview_stats_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                               const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
                                               sgz_overview_stat_record *stats_out, float *means_out, sgz_pcm_timing *timing)
 {
-    if (!cfg || !pcm) return fail(SGZ_EINVAL, "null argument");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (!rgba_out && !stats_out && !means_out) return fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them");
-    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
-                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
-                      [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_stats(s, pcm, nsamples, k, 1, rgba_out, stats_out, means_out, columns, &columns, timing); });
+    return pcmOverviewOneShot(!cfg || !pcm, cfg, format, src_channels, channel_map, nsamples, k, timing,
+                              [&] { return (!rgba_out && !stats_out && !means_out) ? fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them") : SGZ_OK; },
+                              [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_stats(s, pcm, nsamples, k, 1, rgba_out, stats_out, means_out, columns, &columns, timing); });
 }
 
 // ---- the power overview inside the stream (sgz.h, "The power overview") --------------------------------------------------------------------------
@@ -1171,39 +1062,35 @@ sgz_status sgz_pcm_stream_feed_overview_power(sgz_pcm_stream *s, const void *pcm
                                               sgz_overview_power_record *power_out, float *levels_out, uint64_t capacity_columns, uint64_t *columns_out,
                                               sgz_pcm_timing *timing)
 {
-    const auto t0 = PcmClock::now();
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: null pcm");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
-    if (reinterpret_cast<uintptr_t>(power_out) % alignof(sgz_overview_power_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: power_out is not aligned to 8 bytes");
-    if (sgz_status st = powerOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
-    if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the track lane is armed and a power feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
-    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview_power", kOvPower); st != SGZ_OK) return st;
-    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: k differs from the open column's -- flush or reset first");
-    uint64_t need = 0;
-    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
-    if (columns_out) *columns_out = need;
-    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: capacity_columns below what this feed yields (see *columns_out)");
-    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
-    PcmPowerPart part{rgba_out, power_out, levels_out, k, flush, need, need && rgba_out && isPinnedHost(rgba_out), need && power_out && isPinnedHost(power_out),
-                      need && levels_out && isPinnedHost(levels_out)};
-    // (a feed without samples still has one piece when it flushes an open column)
-    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+    static const PcmOvTexts text = {"sgz_pcm_stream_feed_overview_power: null pcm", "sgz_pcm_stream_feed_overview_power: k differs from the open column's -- flush or reset first",
+                                    "sgz_pcm_stream_feed_overview_power: capacity_columns below what this feed yields (see *columns_out)", nullptr};
+    PcmOverviewPart part{kOvPower, k, flush, pcmPowerRun};
+    return pcmOverviewFeed(s, pcm, nsamples, text, part, capacity_columns, columns_out, timing, [&]() -> sgz_status {
+        if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
+        if (reinterpret_cast<uintptr_t>(power_out) % alignof(sgz_overview_power_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: power_out is not aligned to 8 bytes");
+        if (sgz_status st = powerOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
+        if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_power: the track lane is armed and a power feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
+        const size_t records = pcmPeaksFloats(*s, 1) * size_t(s->plan->impl.sides);
+        part.add(kOutOvImage, pcmImageBytes(*s, 1), rgba_out);
+        part.add(kOutOvPower, records * sizeof(sgz_overview_power_record), power_out);
+        part.add(kOutOvLevels, records * sizeof(float), levels_out);
+        part.firstUse[0] = {&s->d_ovCarry[kOvPower], records * sizeof(sgz_overview_power_record)};
+        return SGZ_OK;
+    });
 }
 
 sgz_status sgz_spectrogram_overview_power_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                               const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
                                               sgz_overview_power_record *power_out, float *levels_out, sgz_pcm_timing *timing)
 {
-    if (!cfg || !pcm) return fail(SGZ_EINVAL, "null argument");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
-    if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the power overview reduces transform magnitudes: RSNT plans are not supported");
-    if (cfg->channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the power overview reduces magnitudes: Phase mode's second plane is none");
-    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
-                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
-                      [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_power(s, pcm, nsamples, k, 1, rgba_out, power_out, levels_out, columns, &columns, timing); });
+    return pcmOverviewOneShot(!cfg || !pcm, cfg, format, src_channels, channel_map, nsamples, k, timing,
+                              [&]() -> sgz_status {
+                                  if (!rgba_out && !power_out && !levels_out) return fail(SGZ_EINVAL, "overview power: an image, the records, the levels or any of them");
+                                  if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the power overview reduces transform magnitudes: RSNT plans are not supported");
+                                  if (cfg->channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the power overview reduces magnitudes: Phase mode's second plane is none");
+                                  return SGZ_OK;
+                              },
+                              [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_power(s, pcm, nsamples, k, 1, rgba_out, power_out, levels_out, columns, &columns, timing); });
 }
 
 // ---- the cross overview inside the stream (sgz.h, "The cross overview") --------------------------------------------------------------------------
@@ -1213,8 +1100,9 @@ sgz_status sgz_pcm_stream_set_cross_edges(sgz_pcm_stream *s, const uint32_t *edg
     if (sgz_status st = crossOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
     if (s->ovOpen && s->ovKind == kOvCross) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_cross_edges: a cross overview's column is open -- flush it (sgz_pcm_stream_feed_overview_cross) or reset the stream first");
     if (sgz_status st = sgz_plan_set_cross_edges(s->plan, edges, bands); st != SGZ_OK) return st;
-    if (s->d_ovCrossCarry) { (void)hipFree(s->d_ovCrossCarry); s->d_ovCrossCarry = nullptr; }
-    SGZ_HIP(hipMalloc(reinterpret_cast<void **>(&s->d_ovCrossCarry), size_t(s->cfg.num_pairs) * bands * sizeof(sgz_overview_cross_record)));
+    void *&carry = s->d_ovCarry[kOvCross];
+    if (carry) { (void)hipFree(carry); carry = nullptr; }
+    SGZ_HIP(hipMalloc(&carry, size_t(s->cfg.num_pairs) * bands * sizeof(sgz_overview_cross_record)));
     return SGZ_OK;
 }
 
@@ -1222,78 +1110,65 @@ sgz_status sgz_pcm_stream_feed_overview_cross(sgz_pcm_stream *s, const void *pcm
                                               sgz_overview_cross_record *cross_out, uint64_t capacity_columns, uint64_t *columns_out,
                                               sgz_pcm_timing *timing)
 {
-    const auto t0 = PcmClock::now();
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: null pcm");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (sgz_status st = crossOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
-    if (!s->plan->impl.crossBands || !s->d_ovCrossCarry) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the stream has no band table (sgz_pcm_stream_set_cross_edges)");
-    if (reinterpret_cast<uintptr_t>(cross_out) % alignof(sgz_overview_cross_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: cross_out is not aligned to 8 bytes");
-    if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the track lane is armed and a cross feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
-    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview_cross", kOvCross); st != SGZ_OK) return st;
-    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: k differs from the open column's -- flush or reset first");
-    uint64_t need = 0;
-    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
-    if (columns_out) *columns_out = need;
-    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: capacity_columns below what this feed yields (see *columns_out)");
-    if (need && !cross_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: null cross_out");
-    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
-    PcmCrossPart part{cross_out, k, flush, need, need && isPinnedHost(cross_out)};
-    // (a feed without samples still has one piece when it flushes an open column)
-    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+    static const PcmOvTexts text = {"sgz_pcm_stream_feed_overview_cross: null pcm", "sgz_pcm_stream_feed_overview_cross: k differs from the open column's -- flush or reset first",
+                                    "sgz_pcm_stream_feed_overview_cross: capacity_columns below what this feed yields (see *columns_out)", "sgz_pcm_stream_feed_overview_cross: null cross_out"};
+    PcmOverviewPart part{kOvCross, k, flush, pcmCrossRun};
+    return pcmOverviewFeed(s, pcm, nsamples, text, part, capacity_columns, columns_out, timing, [&]() -> sgz_status {
+        if (sgz_status st = crossOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
+        if (!s->plan->impl.crossBands || !s->d_ovCarry[kOvCross]) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the stream has no band table (sgz_pcm_stream_set_cross_edges)");
+        if (reinterpret_cast<uintptr_t>(cross_out) % alignof(sgz_overview_cross_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: cross_out is not aligned to 8 bytes");
+        if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_cross: the track lane is armed and a cross feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
+        part.add(kOutOvCross, size_t(s->cfg.num_pairs) * s->plan->impl.crossBands * sizeof(sgz_overview_cross_record), cross_out);
+        return SGZ_OK;
+    });
 }
 
 sgz_status sgz_spectrogram_overview_cross_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                               const uint32_t *channel_map, size_t nsamples, const uint32_t *edges, uint32_t bands, uint32_t k,
                                               sgz_overview_cross_record *cross_out, sgz_pcm_timing *timing)
 {
-    if (!cfg || !pcm || !edges || !cross_out) return fail(SGZ_EINVAL, "null argument");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the cross overview reduces transform bins: RSNT plans are not supported");
-    if (cfg->channel_mode != SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the cross overview reduces the complex bins of both channels: only SGZ_CH_PHASE plans keep them");
-    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
-                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
-                      [&](sgz_pcm_stream *s, uint64_t columns) {
-                          if (sgz_status st = sgz_pcm_stream_set_cross_edges(s, edges, bands); st != SGZ_OK) return st;
-                          return sgz_pcm_stream_feed_overview_cross(s, pcm, nsamples, k, 1, cross_out, columns, &columns, timing);
-                      });
+    return pcmOverviewOneShot(!cfg || !pcm || !edges || !cross_out, cfg, format, src_channels, channel_map, nsamples, k, timing,
+                              [&]() -> sgz_status {
+                                  if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the cross overview reduces transform bins: RSNT plans are not supported");
+                                  if (cfg->channel_mode != SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the cross overview reduces the complex bins of both channels: only SGZ_CH_PHASE plans keep them");
+                                  return SGZ_OK;
+                              },
+                              [&](sgz_pcm_stream *s, uint64_t columns) {
+                                  if (sgz_status st = sgz_pcm_stream_set_cross_edges(s, edges, bands); st != SGZ_OK) return st;
+                                  return sgz_pcm_stream_feed_overview_cross(s, pcm, nsamples, k, 1, cross_out, columns, &columns, timing);
+                              });
 }
 
 // ---- the flux overview inside the stream (sgz.h, "The flux overview") ----------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_feed_overview_flux(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush, sgz_overview_flux_record *flux_out,
                                              uint64_t capacity_columns, uint64_t *columns_out, sgz_pcm_timing *timing)
 {
-    const auto t0 = PcmClock::now();
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    if (!pcm && nsamples) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: null pcm");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (reinterpret_cast<uintptr_t>(flux_out) % alignof(sgz_overview_flux_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: flux_out is not aligned to 8 bytes");
-    if (sgz_status st = fluxOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
-    if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: the track lane is armed and a flux feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
-    if (sgz_status st = pcmOpenColumnRefusal(*s, "sgz_pcm_stream_feed_overview_flux", kOvFlux); st != SGZ_OK) return st;
-    if (s->ovOpen && k != s->ovK) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: k differs from the open column's -- flush or reset first");
-    uint64_t need = 0;
-    (void)pcmOverviewNeed(s, nsamples, k, flush, &need);
-    if (columns_out) *columns_out = need;
-    if (capacity_columns < need) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: capacity_columns below what this feed yields (see *columns_out)");
-    if (need && !flux_out) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: null flux_out");
-    if (sgz_status st = pcmLanesFit(*s, nsamples, sgz_pcm_stream_frames_for(s, nsamples)); st != SGZ_OK) return st;
-    PcmFluxPart part{flux_out, k, flush, need, need && isPinnedHost(flux_out)};
-    // (a feed without samples still has one piece when it flushes an open column)
-    return pcmFeed(*s, pcm, nsamples, flush && s->ovOpen, part, columns_out, timing, t0);
+    static const PcmOvTexts text = {"sgz_pcm_stream_feed_overview_flux: null pcm", "sgz_pcm_stream_feed_overview_flux: k differs from the open column's -- flush or reset first",
+                                    "sgz_pcm_stream_feed_overview_flux: capacity_columns below what this feed yields (see *columns_out)", "sgz_pcm_stream_feed_overview_flux: null flux_out"};
+    PcmOverviewPart part{kOvFlux, k, flush, pcmFluxRun};
+    return pcmOverviewFeed(s, pcm, nsamples, text, part, capacity_columns, columns_out, timing, [&]() -> sgz_status {
+        if (reinterpret_cast<uintptr_t>(flux_out) % alignof(sgz_overview_flux_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: flux_out is not aligned to 8 bytes");
+        if (sgz_status st = fluxOverviewSupported(s->plan->impl); st != SGZ_OK) return st;
+        if (s->track.armed()) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_flux: the track lane is armed and a flux feed has no line results to search -- disarm it (sgz_pcm_stream_set_track) first");
+        const size_t records = size_t(s->cfg.num_pairs) * size_t(s->plan->impl.sides);
+        part.add(kOutOvFlux, records * sizeof(sgz_overview_flux_record), flux_out);
+        part.firstUse[0] = {&s->d_ovCarry[kOvFlux], records * sizeof(sgz_overview_flux_record)};
+        part.firstUse[1] = {reinterpret_cast<void **>(&s->d_ovFluxPrev), records * s->cfg.axis_points * sizeof(float)};
+        return SGZ_OK;
+    });
 }
 
 sgz_status sgz_spectrogram_overview_flux_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                              const uint32_t *channel_map, size_t nsamples, uint32_t k, sgz_overview_flux_record *flux_out,
                                              sgz_pcm_timing *timing)
 {
-    if (!cfg || !pcm || !flux_out) return fail(SGZ_EINVAL, "null argument");
-    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
-    if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces transform magnitudes: RSNT plans are not supported");
-    if (cfg->channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces magnitudes: Phase mode's second plane is none");
-    return pcmOneShot(cfg, format, src_channels, channel_map, nsamples, timing,
-                      [&](sgz_pcm_stream *s) { return sgz_pcm_stream_columns_for(s, nsamples, k, 1); },
-                      [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_flux(s, pcm, nsamples, k, 1, flux_out, columns, &columns, timing); });
+    return pcmOverviewOneShot(!cfg || !pcm || !flux_out, cfg, format, src_channels, channel_map, nsamples, k, timing,
+                              [&]() -> sgz_status {
+                                  if (cfg->algorithm == SGZ_ALGO_RSNT) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces transform magnitudes: RSNT plans are not supported");
+                                  if (cfg->channel_mode == SGZ_CH_PHASE) return fail(SGZ_EUNSUPPORTED, "the flux overview reduces magnitudes: Phase mode's second plane is none");
+                                  return SGZ_OK;
+                              },
+                              [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_flux(s, pcm, nsamples, k, 1, flux_out, columns, &columns, timing); });
 }
 
 // ---- the lanes' calls ---------------------------------------------------------------------------------------------------------------------------

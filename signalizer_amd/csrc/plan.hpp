@@ -56,6 +56,18 @@ struct DeviceScalars {
     float ratios[SGZ_NUM_SPEC_COLOURS + 1];   // normalizedSpecRatios, Spectrum.cpp:226-246
 };
 
+// The overview kinds (sgz.h: the peak hold, "The mean overview", "The power overview", "The cross overview", "The flux overview"), in the order
+// sgz_pcm_stream names an open column's kind
+enum OverviewKind { kOvPeaks, kOvStats, kOvPower, kOvCross, kOvFlux, kOverviewKinds };
+// A kind's plan scratch: the open column of the render forms (peaks [pairs][P]; records [pairs][P], [pairs][sides][P], [pairs][bands],
+// [pairs][sides]) and the snapshot the reduction reads while it writes the carry, the partial results of the sliced forms
+// [slices][columns][...], the host forms' device copies of the records (the peak hold: the peaks) and of the values (means, levels), and the
+// host view's copy of the range's source columns
+struct OverviewScratch {
+    float *d_carry = nullptr, *d_carryCopy = nullptr, *d_partial = nullptr, *d_hostRecords = nullptr, *d_hostValues = nullptr, *d_viewIn = nullptr;
+    size_t carryCap = 0, carryCopyCap = 0, partialCap = 0, hostRecordsCap = 0, hostValuesCap = 0, viewInCap = 0;
+};
+
 struct Plan {
     sgz_spectrum_config cfg{};
     uint32_t N = 0, W = 0, P = 0, C = 0;
@@ -157,35 +169,18 @@ struct Plan {
     // sgz_spectrogram_track_device / _host: the render's line results [frames][pairs][graphs][P] float2 (they stay on the device) and the
     // host form's device copy of the track
     float *d_trackLines = nullptr, *d_hostTrack = nullptr; size_t trackLinesCap = 0, hostTrackCap = 0;
-    // the overview (overview.hip; sgz_spectrogram_overview_device / _host): a slab's line results [slab][pairs][graphs][P] float2, the open
-    // column's V [pairs][P] and its snapshot, the decay state between slabs when the caller carries none, the slices' partial keys
-    // [slices][columns][pairs][P], and the host form's device copy of the peaks
-    float *d_ovLines = nullptr, *d_ovCarry = nullptr, *d_ovCarryCopy = nullptr, *d_ovState = nullptr, *d_ovPartial = nullptr, *d_hostOvPeaks = nullptr;
-    size_t ovLinesCap = 0, ovCarryCap = 0, ovCarryCopyCap = 0, ovStateCap = 0, ovPartialCap = 0, hostOvPeaksCap = 0;
-    float *d_ovViewIn = nullptr; size_t ovViewInCap = 0;  // sgz_overview_view_host: the device copy of the range's source columns [m][pairs][P]
-    // the mean overview (overview_stats.hip; sgz_spectrogram_overview_stats_device / _host, the stats views), counted in floats as every
-    // ensureCap block, 6 per sgz_overview_stat_record: the open column's records [pairs][P], their snapshot, the partial records of the
-    // sliced forms, the host forms' device copies of records and means, and the host view's copy of the range's source columns
-    float *d_ovsCarry = nullptr, *d_ovsCarryCopy = nullptr, *d_ovsPartial = nullptr, *d_hostOvStats = nullptr, *d_hostOvMeans = nullptr, *d_ovsViewIn = nullptr;
-    size_t ovsCarryCap = 0, ovsCarryCopyCap = 0, ovsPartialCap = 0, hostOvStatsCap = 0, hostOvMeansCap = 0, ovsViewInCap = 0;
-    // the power overview (overview_power.hip; sgz_spectrogram_overview_power_device / _host, the power views), 8 floats per
-    // sgz_overview_power_record: the open column's records [pairs][sides][P], their snapshot, the partial records of the sliced forms, the host
-    // forms' device copies of records and levels, and the host view's copy of the range's source columns
-    float *d_ovpCarry = nullptr, *d_ovpCarryCopy = nullptr, *d_ovpPartial = nullptr, *d_hostOvPower = nullptr, *d_hostOvLevels = nullptr, *d_ovpViewIn = nullptr;
-    size_t ovpCarryCap = 0, ovpCarryCopyCap = 0, ovpPartialCap = 0, hostOvPowerCap = 0, hostOvLevelsCap = 0, ovpViewInCap = 0;
-    // the cross overview (overview_cross.hip; sgz_plan_set_cross_edges, sgz_spectrogram_overview_cross_device / _host): the band table's edges
-    // [bands + 1] (empty: none set) and its device tables, 20 floats per sgz_overview_cross_record: the open column's records [pairs][bands], their
-    // snapshot, the partial records [slices][columns][pairs][pieces], the host form's device copy of the records, and a slab's complex bins
+    // the overviews (overview*.hip; sgz_spectrogram_overview*_device / _host, the host views): ov[kind] is a kind's plan scratch, every block an
+    // allocation of its own -- two kinds may be in flight on two streams of one plan --, counted in floats as every ensureCap block
+    OverviewScratch ov[kOverviewKinds];
+    // what one kind alone has.  Peak hold and mean: a slab's line results [slab][pairs][graphs][P] float2 and the decay state between slabs when
+    // the caller carries none.  Cross (sgz_plan_set_cross_edges): the band table's edges [bands + 1] (empty: none set), its device tables, and a
+    // slab's complex bins.  Flux: the previous frame [pairs][sides][P] and its snapshot
+    float *d_ovLines = nullptr, *d_ovState = nullptr; size_t ovLinesCap = 0, ovStateCap = 0;
     std::vector<uint32_t> crossEdges;
     uint32_t crossBands = 0, crossTiles = 0, crossPieces = 0;
     uint32_t *d_crossTables = nullptr;
-    float *d_ovcCarry = nullptr, *d_ovcCarryCopy = nullptr, *d_ovcPartial = nullptr, *d_hostOvCross = nullptr, *d_ovcBins = nullptr;
-    size_t ovcCarryCap = 0, ovcCarryCopyCap = 0, ovcPartialCap = 0, hostOvCrossCap = 0, ovcBinsCap = 0;
-    // the flux overview (overview_flux.hip; sgz_spectrogram_overview_flux_device / _host), 22 floats per sgz_overview_flux_record: the open
-    // column's records [pairs][sides] and their snapshot, the previous frame [pairs][sides][P] and its snapshot, the partial records of the sliced
-    // form, and the host form's device copy of the records
-    float *d_ovfCarry = nullptr, *d_ovfCarryCopy = nullptr, *d_ovfPrev = nullptr, *d_ovfPrevCopy = nullptr, *d_ovfPartial = nullptr, *d_hostOvFlux = nullptr;
-    size_t ovfCarryCap = 0, ovfCarryCopyCap = 0, ovfPrevCap = 0, ovfPrevCopyCap = 0, ovfPartialCap = 0, hostOvFluxCap = 0;
+    float *d_ovcBins = nullptr; size_t ovcBinsCap = 0;
+    float *d_ovfPrev = nullptr, *d_ovfPrevCopy = nullptr; size_t ovfPrevCap = 0, ovfPrevCopyCap = 0;
     void *hostStream = nullptr;                           // hipStream_t / hipEvent_t (this header is also compiled as plain C++)
     void *hostEv[4] = {nullptr, nullptr, nullptr, nullptr};
     float *d_tw2Full = nullptr;

@@ -100,9 +100,12 @@ sgz_status checkViewRange(uint64_t n, uint64_t x0, uint64_t x1, uint32_t outColu
 sgz_status checkOverviewStep(uint32_t k, uint64_t held, uint64_t frames);          // what every overview stage call refuses first: k == 0, held >= k
 bool bytesOverlap(const void *a, size_t aBytes, const void *b, size_t bBytes);       // two non-null byte ranges share a byte (the views' outputs against their source)
 sgz_status runOverviewView(Plan &p, const float *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba, float *d_peaksOut, hipStream_t stream);
-// the overview render's slab loop (api.hip): `frames` frames from d_planar behind `held` frames of an open column whose V is in d_carry; the
-// columns that close go to d_rgba / d_peaks from their first element on, the open one stays in d_carry unless `flush`.  d_state: the decay
-// state in and out, or null (from rest; kept in plan scratch between slabs).  What sgz_spectrogram_overview_device and sgz_pcm_stream share.
+// The kinds' run...Slabs below are one slab loop (api.hip, overviewSlabs) with the kind's two steps: `frames` frames from d_planar behind `held`
+// frames of an open column whose reduction is in d_carry; the columns that close go to the outputs from their first element on, the open one
+// stays in d_carry unless `flush`.  What a kind's sgz_spectrogram_overview..._device and sgz_pcm_stream share; the caller has checked the plan
+// (powerOverviewSupported, crossOverviewSupported and the band table, fluxOverviewSupported).  The peak hold and the mean overview render
+// K_A and K_B per slab -- d_state: the decay state in and out, or null (from rest; kept in plan scratch between slabs) --, the others K_A
+// alone: mapped magnitudes with the late pixels completed (power, flux) or complex bins (cross), no decay state.
 // track: null, or where the tracker's record of every (frame, pair) goes -- runTrackPeaksLines behind every slab's render on the slab's line
 // results, into d_out [frames][pairs] at the slab's frame offset (stream order alone keeps the next slab's render behind it)
 struct SlabTrack { uint32_t graph; double mouseFraction; sgz_line_peak *d_out; };
@@ -116,7 +119,6 @@ sgz_status runOverviewStatsColumns(Plan &p, const float *d_lines, size_t frames,
                                    hipStream_t stream);
 sgz_status runOverviewStatsView(Plan &p, const sgz_overview_stat_record *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba,
                                 sgz_overview_stat_record *d_statsOut, float *d_means, hipStream_t stream);
-// ... and of runOverviewSlabs: the same slab loop with the stats reduction behind every slab
 sgz_status runOverviewStatsSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
                                  int flush, sgz_overview_stat_record *d_carry, float *d_state, uint8_t *d_rgba, sgz_overview_stat_record *d_stats,
                                  float *d_means, hipStream_t stream, const SlabTrack *track = nullptr);
@@ -128,10 +130,7 @@ sgz_status runOverviewPowerColumns(Plan &p, const float *d_mapped, size_t frames
                                    hipStream_t stream);
 sgz_status runOverviewPowerView(Plan &p, const sgz_overview_power_record *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba,
                                 sgz_overview_power_record *d_powerOut, float *d_levels, hipStream_t stream);
-// ... and its slab loop (api.hip): per slab K_A into p.d_mapped with the late pixels completed, then the reduction with the open column carried
-// in d_carry; no K_B and no decay state.  What sgz_spectrogram_overview_power_device and sgz_pcm_stream share; the caller has refused Phase and
-// RSNT plans (powerOverviewSupported)
-sgz_status powerOverviewSupported(const Plan &p);
+sgz_status powerOverviewSupported(const Plan &p);                 // Phase and RSNT plans: SGZ_EUNSUPPORTED
 sgz_status runOverviewPowerSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
                                  sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels,
                                  hipStream_t stream);
@@ -140,9 +139,6 @@ sgz_status runOverviewPowerSlabs(sgz_plan *plan, const float *d_planar, size_t c
 sgz_status crossOverviewSupported(const Plan &p);                 // FFT, SGZ_CH_PHASE, N = 2^n: everything else SGZ_EUNSUPPORTED
 sgz_status runOverviewCrossColumns(Plan &p, const float *d_bins, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
                                    sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t stream);
-// ... and its slab loop (api.hip): per slab K_A's complex bins into plan scratch (sgz_stage_bins' call), then the reduction with the open
-// column carried in d_carry; no K_B and no decay state.  What sgz_spectrogram_overview_cross_device and sgz_pcm_stream share; the caller has
-// checked the plan (crossOverviewSupported) and its band table
 sgz_status runOverviewCrossSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
                                  sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t stream);
 // the flux overview (overview_flux.hip): the reduction of the mapped magnitudes d_mapped [frames][pairs][sides][P] into sgz_overview_flux_record
@@ -151,9 +147,7 @@ sgz_status runOverviewCrossSlabs(sgz_plan *plan, const float *d_planar, size_t c
 sgz_status fluxOverviewSupported(const Plan &p);                  // Phase and RSNT plans: SGZ_EUNSUPPORTED
 sgz_status runOverviewFluxColumns(Plan &p, const float *d_mapped, size_t frames, uint32_t k, uint32_t held, int flush, uint64_t firstFrame, uint32_t slices,
                                   float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry, sgz_overview_flux_record *d_flux, hipStream_t stream);
-// ... and its slab loop (api.hip): per slab K_A into p.d_mapped with the late pixels completed, then the reduction with the open column carried in
-// d_carry and the previous frame in d_prev; no K_B and no decay state.  What sgz_spectrogram_overview_flux_device and sgz_pcm_stream share; the
-// caller has refused Phase and RSNT plans
+// (its slabs keep a slab's last frame in d_prev for the next slab's first; firstFrame: the index of frame 0 in the file)
 sgz_status runOverviewFluxSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
                                 uint64_t firstFrame, float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry, sgz_overview_flux_record *d_flux,
                                 hipStream_t stream);
