@@ -95,6 +95,11 @@ extern "C" {
  *  sgz_pcm_stream_feed_overview_flux and sgz_spectrogram_overview_flux_pcm.  No existing entry point or struct changed and the suite pins 5;
  *  the new refusals on existing calls, a feed of another kind while a flux column is open, cannot be reached without the new calls.  A
  *  binding that needs them looks the symbols up.)
+ * (5, later: the run lane -- SGZ_RUN_HOT / _QUIET / _FLAT, SGZ_RUN_NAN, sgz_run_params, sgz_run_of, sgz_run_record, sgz_run_carry,
+ *  sgz_run_reading, sgz_stage_run_columns, sgz_run_columns_limits, the host helpers sgz_run_params_default, sgz_run_fold and
+ *  sgz_run_readout and, on the PCM stream, sgz_pcm_stream_set_run, sgz_pcm_stream_run_for, sgz_pcm_stream_run_state,
+ *  sgz_pcm_stream_flush_run.  No existing entry point or struct changed and the suite pins 5; a stream that was never armed enqueues what
+ *  it did before.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -1668,6 +1673,138 @@ sgz_status sgz_pcm_stream_set_hist(sgz_pcm_stream *s, uint32_t m /*0 = off*/, sg
 uint64_t   sgz_pcm_stream_hist_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
 sgz_status sgz_pcm_stream_hist_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
 sgz_status sgz_pcm_stream_flush_hist(sgz_pcm_stream *s);
+
+/* The run lane: clipped, flat and silent RUNS per screen column and channel of a file's samples -- what a file-QC view needs after level
+ * and true peak.  Clipping is consecutive samples on a ceiling, not single samples over it (the level lane's `overs` counts single
+ * samples); clipping that was attenuated afterwards sits under every threshold and shows only as flat tops; a dropout or a mute is a run
+ * of identical or zero samples (the histogram lane says "23 % of this column is digital zero", not "one hole of 4410 samples starting
+ * here").  Every other column lane is a commutative fold; this one is ordered: associative, not commutative.  The reference has no
+ * counterpart; nothing of it is reused or contradicted.
+ * Definition (exact, no tolerance).  Per channel, x[i] are the stream's converted fp32 samples, exactly what sgz_pcm_to_planar_device
+ * writes, i counting the lane's samples since it was armed or reset, S the samples so far and m >= 1 the samples per column.  The
+ * quantiser is the level lane's,
+ *     v = (int32) clamp(rintf(x * 2^23), -2^26, +2^26)
+ * and a NaN is INVALID: it has no v.  The thresholds are a sgz_run_params { hot, quiet }, valid when 1 <= hot <= 2^26 and quiet < hot;
+ * sgz_run_params_default gives hot = 2^23 - 2^8 -- the positive full scale of 16-bit PCM, so a clipped 16-bit file trips it on both
+ * rails -- and quiet = 0.  Three predicates, indices SGZ_RUN_HOT = 0, SGZ_RUN_QUIET = 1, SGZ_RUN_FLAT = 2:
+ *     P_hot(i)   = valid(i) and |v[i]| >= hot
+ *     P_quiet(i) = valid(i) and |v[i]| <= quiet
+ *     P_flat(i)  = i >= 1 and valid(i) and valid(i - 1) and v[i] = v[i - 1]          (a flat run of length r is r + 1 equal samples)
+ * and two derived terms:
+ *     cross(i)   = i >= 1 and valid(i) and valid(i - 1) and (v[i] < 0) != (v[i - 1] < 0)       (zero counts as non-negative)
+ *     start_k(i) = P_k(i) and not (i >= 1 and P_k(i - 1))
+ * Column c covers samples c m <= i < min((c + 1) m, S), counted by sgz_overview_step with samples in the place of frames; only a flushed
+ * last column may be partial.  A flush does not move i and does not drop the history: the first sample after a flush still relates to the
+ * one before it.  One sgz_run_record per (column, channel), layout [columns][channels], 96 bytes = 24 little-endian 32-bit words; arrays
+ * of it on the DEVICE are aligned to 16 bytes.  For the column [a, b):
+ *     word 0          len          b - a, NaNs included
+ *     word 1          skipped      the invalid samples
+ *     word 2          crossings    the sum of cross(i)
+ *     word 3          reserved0    0
+ *     words 4 + 6 k.. of[k]        count, runs, longest, at, head, tail of predicate k:
+ *         count       the sum of P_k(i)
+ *         runs        the sum of start_k(i): the runs that BEGIN in the column
+ *         longest     the greatest r such that r consecutive samples inside the column all have P_k (runs are clipped to the column)
+ *         at          the least offset from a at which such a stretch of `longest` samples starts; 0 when longest = 0
+ *         head, tail  the consecutive samples with P_k at the column's start / end; both equal len when every sample has P_k
+ *     words 22, 23    reserved     0
+ * A column of no samples is the all-zero record, the identity.  The fold of A followed by B: len, skipped, crossings, count and runs
+ * add; head = (A.head == A.len) ? A.len + B.head : A.head; tail = (B.tail == B.len) ? B.len + A.tail : B.tail; longest is the greatest of
+ * three candidates, (A.longest at A.at), (A.tail + B.head at A.len - A.tail) and (B.longest at A.len + B.at), and `at` the least position
+ * among the candidates that attain it, 0 when longest is 0.  The fold is associative, so any cut of the stream (feeds, pieces, calls with
+ * a carry) or of a column (lanes, waves, tiles, slices) gives the same bytes as long as the parts are folded IN ORDER, and a coarser
+ * column is the fold of the finer ones in order (sgz_run_fold).  What a cut of the stream carries is one 112-byte sgz_run_carry per
+ * channel, aligned to 16: the open column so far, prev[0] = v[i - 1] and prev[1] = v[i - 2] (SGZ_RUN_NAN = INT32_MIN stands for an invalid
+ * sample or for none: "no sample before" and "a NaN before" are the same thing under the definition; v[i - 2] is needed because
+ * start_flat(i) asks for P_flat(i - 1)), and two reserved words written as 0.
+ *  sgz_stage_run_columns  DEVICE pointers; sgz_stage_truepeak_columns' arguments, semantics, carry rule, snapshot rule and refusals to the
+ *                      letter, with 1 .. 64 channels, a two-sample history in the place of eleven, and `params` in the place the
+ *                      loudness call has its filter: a NULL or invalid params is SGZ_EINVAL with nothing launched.  continued == 0: the
+ *                      stream begins with this call, the history is two marks, held must be 0 -- exactly a carry whose prev are marks.
+ *                      After a call with nsamples > 0 all 112 bytes of every channel's carry are written: prev is the last two of (the
+ *                      old history followed by the new samples), open is the open column where samples stay open and all zero
+ *                      otherwise, reserved is 0.  nsamples == 0 with held > 0 and flush: one column from the carry alone, the carry
+ *                      untouched.  d_runs: DEVICE sgz_run_record [columns][channels] (NULL allowed when none closes).  m up to the
+ *                      switch-over (1024; sgz_run_columns_limits) runs one workgroup per (channel, tile of 4096 / m whole columns)
+ *                      behind a two-sample halo; longer columns are reduced in slices per column into scratch, each slice fetching its
+ *                      own halo, and folded in order by a second launch.  slices: 0 = the library's choice, 1 .. 64 forced -- 2 and more
+ *                      take the sliced form whatever m is, 1 takes the form m implies -- identical bytes.  Only the documented bytes are
+ *                      written.  Asynchronous on `stream`, nothing is waited for; scratch is allocated and freed in stream order.
+ *  sgz_run_columns_limits  the switch-over and the tile's samples (either result may be NULL).
+ *  sgz_run_params_default  fills the defaults (NULL: nothing).
+ * The lane inside the sgz_pcm_stream handle -- above, "interleaved PCM in": the true-peak lane's contract word for word, with
+ * sgz_run_record in the place of sgz_truepeak_record, the thresholds handled as sgz_pcm_stream_set_loudness handles its filter, and one
+ * exception: the stream refuses 0 < m < 32 with SGZ_EINVAL -- 96 bytes per 32 samples keeps the records under the samples' size (the
+ * stage call takes every m >= 1).  The records of all feeds and the final flush, concatenated, are the definition applied to the stream's
+ * converted floats, byte for byte, however the stream is cut into feeds and pieces and whichever kind the feeds are; everything else an
+ * armed stream returns equals an unarmed stream's, byte for byte.  The lane's m is its own.
+ *  sgz_pcm_stream_set_run   between feeds.  m >= 32 arms: out HOST sgz_run_record [capacity_columns][channels] (aligned to 4 bytes; pinned
+ *                      memory is written in place, pageable memory through a pinned twin per slot), the cursor restarts at 0 and the
+ *                      lane starts at the next sample, i = 0, with a history of marks.  The same m and params with another buffer keep
+ *                      the open column and the history: how a caller with a small buffer drains.  m == 0 disarms and drops both (params
+ *                      may be NULL then).  SGZ_EINVAL: a null stream, 0 < m < 32, NULL or invalid params, a null out with
+ *                      capacity_columns > 0, an out that is not aligned, another m or other params while samples are open.
+ *  sgz_pcm_stream_run_for   columns the next feed of nsamples closes (flush != 0: that feed followed by sgz_pcm_stream_flush_run); 0 when
+ *                      disarmed.
+ *  sgz_pcm_stream_run_state columns written since the lane was armed (the cursor) and the open column's samples; either may be NULL.
+ *  sgz_pcm_stream_flush_run closes the open column: one launch on the carry, one column read back, waits; the history is kept.  Nothing
+ *                      open: SGZ_OK, nothing done.  SGZ_EINVAL: disarmed, no column left in the buffer.
+ * A feed that would close more columns than the buffer has left is refused with SGZ_EINVAL before anything is consumed.  reset drops the
+ * open column, sets the history to marks and restarts the cursor.  The carry is kept twice and alternated: a piece reads one and writes
+ * the other.  Memory per slot as the level lane's, 96 bytes a record and channel.
+ * Host arithmetic on HOST records, nothing launched:
+ *  sgz_run_fold        the zoom, with sgz_level_fold's boundary rule -- output column b is the fold of source columns x0 + ceil(b w /
+ *                      cols) <= j < x0 + ceil((b + 1) w / cols), w = x1 - x0, cols = min(out_columns, w) --, so the lanes of a file zoom
+ *                      together.  The fold above is applied in source order; `at` of an output column counts from the first sample of
+ *                      its first source column.  out must not overlap in.  SGZ_EINVAL, nothing written: a null argument, channels == 0,
+ *                      what sgz_overview_view_columns refuses, a folded len above 2^32 - 1.
+ *  sgz_run_readout     what a host draws from one record at `rate` samples per second, in fp64: share[k] = count / len (NaN for len
+ *                      == 0), longest_seconds[k] = longest / rate, at_seconds[k] = at / rate, crossing_hz = crossings rate / (2 len)
+ *                      (NaN for len == 0).  SGZ_EINVAL: a null argument, a rate that is not a positive finite number. */
+#define SGZ_RUN_HOT   0
+#define SGZ_RUN_QUIET 1
+#define SGZ_RUN_FLAT  2
+#define SGZ_RUN_NAN   (-2147483647 - 1)       /* INT32_MIN: an invalid sample, or none */
+typedef struct sgz_run_params {
+    uint32_t hot;      /* |v| >= hot is hot; 1 .. 2^26 */
+    uint32_t quiet;    /* |v| <= quiet is quiet; < hot */
+} sgz_run_params;
+typedef struct sgz_run_of {
+    uint32_t count;    /* samples with the predicate */
+    uint32_t runs;     /* runs that begin in the column */
+    uint32_t longest;  /* the longest stretch inside the column */
+    uint32_t at;       /* where the first such stretch starts, from the column's first sample; 0 when longest = 0 */
+    uint32_t head;     /* the stretch at the column's start */
+    uint32_t tail;     /* the stretch at the column's end */
+} sgz_run_of;               /* 24 bytes */
+typedef struct sgz_run_record {
+    uint32_t   len;          /* the column's samples, NaNs included */
+    uint32_t   skipped;      /* the invalid samples (NaNs) */
+    uint32_t   crossings;    /* sign changes between neighbouring valid samples */
+    uint32_t   reserved0;    /* 0 */
+    sgz_run_of of[3];        /* SGZ_RUN_HOT, SGZ_RUN_QUIET, SGZ_RUN_FLAT */
+    uint32_t   reserved[2];  /* 0 */
+} sgz_run_record;           /* 96 bytes */
+typedef struct sgz_run_carry {
+    sgz_run_record open;         /* the open column so far */
+    int32_t        prev[2];      /* v[i - 1], v[i - 2] of the next sample i; SGZ_RUN_NAN: invalid or none */
+    uint32_t       reserved[2];  /* written as 0 */
+} sgz_run_carry;            /* 112 bytes */
+typedef struct sgz_run_reading {
+    double share[3], longest_seconds[3], at_seconds[3], crossing_hz;
+} sgz_run_reading;
+sgz_status sgz_stage_run_columns(const float *d_planar, size_t channel_stride, uint32_t channels, size_t nsamples, const sgz_run_params *params,
+                                 uint32_t m, uint32_t held, int flush, uint32_t continued, uint32_t slices, sgz_run_carry *d_carry /*[channels]*/,
+                                 sgz_run_record *d_runs /*[columns][channels]*/, void *stream);
+void       sgz_run_columns_limits(uint32_t *switch_over, uint32_t *tile_samples);
+void       sgz_run_params_default(sgz_run_params *params);
+sgz_status sgz_run_fold(const sgz_run_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns, sgz_run_record *out);
+sgz_status sgz_run_readout(const sgz_run_record *rec, double rate, sgz_run_reading *out);
+sgz_status sgz_pcm_stream_set_run(sgz_pcm_stream *s, const sgz_run_params *params, uint32_t m /*0 = off*/,
+                                  sgz_run_record *out /*HOST [capacity][channels]*/, uint64_t capacity_columns);
+uint64_t   sgz_pcm_stream_run_for(const sgz_pcm_stream *s, size_t nsamples, int flush);
+sgz_status sgz_pcm_stream_run_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples);
+sgz_status sgz_pcm_stream_flush_run(sgz_pcm_stream *s);
 
 /* The track lane: the tracker's curve over a file -- the reference's drawFrequencyTracking readout (SpectrumRendering.cpp:300-377, the
  * line-results branch) for every frame of a streamed file, in bounded memory.  sgz_spectrogram_track_device / _host want the whole file

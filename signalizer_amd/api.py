@@ -152,6 +152,25 @@ class HistReading(C.Structure):
                 ("median_db", C.c_double), ("toggling", C.c_uint32), ("effective_bits", C.c_uint32)]
 
 
+# sgz_run_record: one per (column, channel) of the run lane, 96 bytes = 24 words: of[k] for the predicates hot, quiet, flat;
+# sgz_run_carry: one per channel, 112 bytes (RUN_NAN in prev: an invalid sample, or none)
+RUN_HOT, RUN_QUIET, RUN_FLAT = 0, 1, 2
+RUN_NAN = -2**31
+RUN_OF_DTYPE = np.dtype([("count", "<u4"), ("runs", "<u4"), ("longest", "<u4"), ("at", "<u4"), ("head", "<u4"), ("tail", "<u4")])
+RUN_DTYPE = np.dtype([("len", "<u4"), ("skipped", "<u4"), ("crossings", "<u4"), ("reserved0", "<u4"), ("of", RUN_OF_DTYPE, (3,)),
+                      ("reserved", "<u4", (2,))])
+RUN_CARRY_DTYPE = np.dtype([("open", RUN_DTYPE), ("prev", "<i4", (2,)), ("reserved", "<u4", (2,))])
+assert RUN_DTYPE.itemsize == 96 and RUN_CARRY_DTYPE.itemsize == 112
+
+
+class RunParams(C.Structure):
+    _fields_ = [("hot", C.c_uint32), ("quiet", C.c_uint32)]
+
+
+class RunReading(C.Structure):
+    _fields_ = [("share", C.c_double * 3), ("longest_seconds", C.c_double * 3), ("at_seconds", C.c_double * 3), ("crossing_hz", C.c_double)]
+
+
 class LoudnessFilter(C.Structure):
     _fields_ = [("b", (C.c_double * 3) * 2), ("a", (C.c_double * 2) * 2), ("W", C.c_uint32), ("L", C.c_uint32)]
 
@@ -283,6 +302,8 @@ EXPORTS = [
     "sgz_band_colours", "sgz_pcm_stream_set_band", "sgz_pcm_stream_band_for", "sgz_pcm_stream_band_state", "sgz_pcm_stream_flush_band",
     "sgz_stage_hist_columns", "sgz_hist_columns_limits", "sgz_hist_edges", "sgz_hist_fold", "sgz_hist_percentile", "sgz_hist_readout",
     "sgz_pcm_stream_set_hist", "sgz_pcm_stream_hist_for", "sgz_pcm_stream_hist_state", "sgz_pcm_stream_flush_hist",
+    "sgz_stage_run_columns", "sgz_run_columns_limits", "sgz_run_params_default", "sgz_run_fold", "sgz_run_readout",
+    "sgz_pcm_stream_set_run", "sgz_pcm_stream_run_for", "sgz_pcm_stream_run_state", "sgz_pcm_stream_flush_run",
 ]
 
 
@@ -592,8 +613,16 @@ def lib() -> C.CDLL:
     L.sgz_hist_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_hist_percentile.argtypes = [vp, C.c_double, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgz_hist_readout.argtypes = [vp, C.POINTER(HistReading)]
-    for lane in ("waveform", "level", "truepeak", "loudness", "field", "band", "hist"):      # the seven column lanes of the PCM stream: one set of calls each
-        getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, {"loudness": fp, "band": bp}[lane], u32, vp, u64] if lane in ("loudness", "band") else [vp, u32, vp, u64]
+    rp = C.POINTER(RunParams)
+    L.sgz_stage_run_columns.argtypes = [vp, sz, u32, sz, rp, u32, u32, C.c_int, u32, u32, vp, vp, vp]
+    L.sgz_run_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    L.sgz_run_columns_limits.restype = None
+    L.sgz_run_params_default.argtypes = [rp]
+    L.sgz_run_params_default.restype = None
+    L.sgz_run_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
+    L.sgz_run_readout.argtypes = [vp, C.c_double, C.POINTER(RunReading)]
+    for lane in ("waveform", "level", "truepeak", "loudness", "field", "band", "hist", "run"):      # the eight column lanes of the PCM stream: one set of calls each
+        getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, {"loudness": fp, "band": bp, "run": rp}[lane], u32, vp, u64] if lane in ("loudness", "band", "run") else [vp, u32, vp, u64]
         getattr(L, f"sgz_pcm_stream_{lane}_for").argtypes = [vp, sz, C.c_int]
         getattr(L, f"sgz_pcm_stream_{lane}_for").restype = u64
         getattr(L, f"sgz_pcm_stream_{lane}_state").argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
@@ -1924,7 +1953,7 @@ class PcmStream:
         closed: (records OVERVIEW_FLUX_DTYPE [columns, pairs, sides], timing dict).  The stream's decay state is neither read nor advanced."""
         return self._feed_overview("_flux", pcm, k, flush, nsamples, [(True, (self.cfg.num_pairs, _sides(self.cfg)), OVERVIEW_FLUX_DTYPE)])
 
-    # the seven column lanes (waveform, level, truepeak, loudness, field, band, hist): one helper per kind of call, the lane's name picks the C call
+    # the eight column lanes (waveform, level, truepeak, loudness, field, band, hist, run): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
         if capacity_columns is None:
             capacity_columns = 0 if out is None else int(out.shape[0])
@@ -2069,6 +2098,25 @@ class PcmStream:
     def flush_hist(self) -> None:
         """sgz_pcm_stream_flush_hist: closes the open column (one more record per channel at the cursor); waits"""
         self._lane_flush("hist")
+
+    # the run lane: one sgz_run_record per column of m >= 32 samples and channel, beside whatever the feeds render
+    def set_run(self, params, m: int, out=None, capacity_columns: int | None = None) -> None:
+        """sgz_pcm_stream_set_run: params -- a RunParams (None allowed with m == 0); out -- a RUN_DTYPE numpy array [capacity, channels] or a
+        host torch uint8 tensor [capacity, channels, 96] (kept alive here; pinned memory is written in place); m == 0 disarms, 0 < m < 32 is
+        refused"""
+        self._lane_set("run", m, out, capacity_columns, C.byref(params) if params is not None else None)
+
+    def run_for(self, nsamples: int, flush: bool = False) -> int:
+        """sgz_pcm_stream_run_for: run columns the next feed of nsamples closes"""
+        return self._lane_for("run", nsamples, flush)
+
+    def run_state(self):
+        """sgz_pcm_stream_run_state: (columns written since the lane was armed, samples of the open column)"""
+        return self._lane_state("run")
+
+    def flush_run(self) -> None:
+        """sgz_pcm_stream_flush_run: closes the open column (one more record per channel at the cursor); waits; the history is kept"""
+        self._lane_flush("run")
 
     # the track lane: one tracked peak per (frame, pair) that becomes complete, beside whatever the feeds render
     def set_track(self, graph: int = 0, mouse_fraction: float = 0.5, out=None, capacity_frames: int | None = None) -> None:
@@ -2237,6 +2285,50 @@ def hist_readout(record) -> dict:
     r = HistReading()
     check(lib().sgz_hist_readout(_np_ptr(rec), C.byref(r)))
     return {k: getattr(r, k) for k, _ in r._fields_}
+
+
+def run_params_default() -> RunParams:
+    """sgz_run_params_default: hot = 2^23 - 2^8 (the positive full scale of 16-bit PCM), quiet = 0"""
+    p = RunParams()
+    lib().sgz_run_params_default(C.byref(p))
+    return p
+
+
+def run_columns_limits():
+    """sgz_run_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples)"""
+    s, t = C.c_uint32(0), C.c_uint32(0)
+    lib().sgz_run_columns_limits(C.byref(s), C.byref(t))
+    return int(s.value), int(t.value)
+
+
+def stage_run_columns(planar, channel_stride: int, channels: int, nsamples: int, params, m: int, held: int = 0, flush: bool = True,
+                      continued: bool = False, slices: int = 0, carry=None, runs=None, stream=None) -> int:
+    """sgz_stage_run_columns as it is: params -- a RunParams or None; planar / carry / runs -- cuda tensors (their data pointers; any may be
+    None where the call allows NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    return lib().sgz_stage_run_columns(ptr(planar), channel_stride, channels, nsamples, C.byref(params) if params is not None else None, m, held,
+                                       int(bool(flush)), int(bool(continued)), slices, ptr(carry), ptr(runs), C.c_void_p(s) if s else None)
+
+
+def run_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_run_fold: RUN_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels], folded in order"""
+    records = np.ascontiguousarray(records, RUN_DTYPE)
+    n, channels = records.shape
+    x1 = n if x1 is None else x1
+    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), RUN_DTYPE)
+    check(lib().sgz_run_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
+    return out[:min(out_columns, x1 - x0)]
+
+
+def run_readout(record, rate: float) -> dict:
+    """sgz_run_readout of one RUN_DTYPE record at `rate` samples per second: {share, longest_seconds, at_seconds} -- three each, for hot,
+    quiet and flat -- and crossing_hz"""
+    rec = np.ascontiguousarray(record, RUN_DTYPE).reshape(1)
+    r = RunReading()
+    check(lib().sgz_run_readout(_np_ptr(rec), rate, C.byref(r)))
+    return dict(share=tuple(r.share), longest_seconds=tuple(r.longest_seconds), at_seconds=tuple(r.at_seconds), crossing_hz=r.crossing_hz)
 
 
 def truepeak_columns_limits():

@@ -1,11 +1,11 @@
-// column_lanes.hpp -- what the seven column lanes (wave, level, true-peak, loudness, stereo-field, band, histogram: <lane>_columns.hip) have in common,
+// column_lanes.hpp -- what the eight column lanes (wave, level, true-peak, loudness, stereo-field, band, histogram, run: <lane>_columns.hip) have in common,
 // written once: the shape of a call, the column / tile / slice bounds, the aligned split and the staging of a row, the two quantisers, the
 // stage calls' front, the fold's frame, and the parts in which the loudness and the band lane are twins.  A lane's file holds what is its own:
 // its record, its accumulators, its kernels' bodies.  pcm.hip includes this for the lanes' entry points.
 // A lane's kernel-argument struct keeps its own type and layout; the helpers here are templates on it and read the grid's fields by name:
 //   n, columns, closed (long); m, held, perTile, slices (uint32_t)
 // Floating-point contraction: this header neither sets nor resets it.  loudness_columns.hip and band_columns.hip include it BEHIND their
-// `#pragma clang fp contract(off)`, so every template instantiated there was parsed without contraction; the other five files have no pragma,
+// `#pragma clang fp contract(off)`, so every template instantiated there was parsed without contraction; the other six files have no pragma,
 // and nothing here has a multiply feeding an add in floating point.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -86,6 +86,12 @@ ColumnsShape histColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, ui
 sgz_status runHistColumns(const ColumnsShape &sh, const float *d_planar, size_t channelStride, uint32_t channels, size_t nsamples, uint32_t m,
                           uint32_t held, const sgz_hist_record *carryIn, sgz_hist_record *carryOut, sgz_hist_record *d_hist, void *scratch,
                           hipStream_t stream);
+// the run lane: the true-peak lane's carry rule (a history of two samples: sgz_run_carry), and its thresholds, checked by runParamsCheck
+sgz_status runParamsCheck(const sgz_run_params *p, const char *who);
+ColumnsShape runColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices);
+sgz_status runRunColumns(const ColumnsShape &sh, const sgz_run_params &p, const float *d_planar, size_t channelStride, uint32_t channels,
+                         size_t nsamples, uint32_t m, uint32_t held, uint32_t continued, const sgz_run_carry *carryIn, sgz_run_carry *carryOut,
+                         sgz_run_record *d_runs, void *scratch, hipStream_t stream);
 
 // ---- 2. device helpers --------------------------------------------------------------------------------------------------------------------------
 // samples [a, b) of this call that belong to column `col`

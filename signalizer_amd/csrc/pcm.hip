@@ -4,7 +4,7 @@
 // and which rows to read back.  Every output of a piece -- image, lines, overview image, overview peaks, a lane's columns or records --
 // is a PcmOut: device block, pinned twin, pending host copy.  Every lane is a PcmSink: the caller's buffer, the cursor in it, and the PcmOut its
 // units pass through; the track lane (tracker.hip), which searches every piece's line results behind its render, is a sink of frames, and the
-// seven column lanes -- waveform, level, true-peak, loudness, stereo-field, band, histogram (<lane>_columns.hip; their entry points: column_lanes.hpp),
+// eight column lanes -- waveform, level, true-peak, loudness, stereo-field, band, histogram, run (<lane>_columns.hip; their entry points: column_lanes.hpp),
 // which reduce every piece's new samples behind the converter in that order -- are ONE PcmLane type, a sink of columns with the open column's
 // carry, and differ in a hook that makes the one call of their reduction: one of two templates, for the two carry rules.  The feed walks the
 // lanes; all ride the same read-back.
@@ -204,11 +204,12 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // Field sgz_field_record [ceil(chunk / m) + 1][pairs] the stereo-field lane's.
 // Band sgz_band_record [ceil(chunk / m) + 1][channels] the band lane's.
 // Hist sgz_hist_record [ceil(chunk / m) + 1][channels] the histogram lane's.
+// Run sgz_run_record [ceil(chunk / m) + 1][channels] the run lane's.
 // OvStats sgz_overview_stat_record [columns][C][P] and OvMeans float [columns][C][P] the stats feed's, beside its OvImage.
 // OvPower sgz_overview_power_record [columns][C][sides][P] and OvLevels float [columns][C][sides][P] the power feed's, beside its OvImage.
 // OvCross sgz_overview_cross_record [columns][C][bands] the cross feed's.
 // OvFlux sgz_overview_flux_record [columns][C][sides] the flux feed's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutOvCross, kOutOvFlux, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kPcmOuts };
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutOvCross, kOutOvFlux, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kOutRun, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -287,10 +288,10 @@ struct PcmSink {
     }
 };
 
-// The sinks in the order a feed refuses them; the seven column lanes come first and are the stream's lane[] in this order
-enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
-constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist};
-constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist};
+// The sinks in the order a feed refuses them; the eight column lanes come first and are the stream's lane[] in this order
+enum PcmSinkId { kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist, kSinkRun, kSinkTrack, kPcmSinks, kPcmLanes = kSinkTrack };
+constexpr PcmSinkId kReserveOrder[kPcmSinks] = {kSinkWave, kSinkTrack, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist, kSinkRun};
+constexpr PcmSinkId kReadBackOrder[kPcmSinks] = {kSinkTrack, kSinkWave, kSinkLevel, kSinkTruePeak, kSinkLoudness, kSinkField, kSinkBand, kSinkHist, kSinkRun};
 
 // A lane's hook: the one call of its reduction, run<Lane>Columns, on the compute stream.  (n samples at `in`, flush 0) is a piece's step: the
 // columns they close go to d_out, the open one to the other half of the carry; (0 samples, flush 1) is the flush's emit launch, which leaves the
@@ -352,11 +353,12 @@ struct sgz_pcm_stream {
     bool fluxLinked = false;
     uint64_t frameIndex = 0;
     // the column lanes: waveform (carry float2 [2][channels]), level (sgz_level_record [2][pairs]), true-peak (sgz_truepeak_carry [2][channels]),
-    // stereo-field (sgz_field_record [2][pairs]), histogram (sgz_hist_record [2][channels]), loudness and band (two halves of
-    // <lane>CarryBytes(filter) * channels bytes), and the two filters
+    // stereo-field (sgz_field_record [2][pairs]), histogram (sgz_hist_record [2][channels]), run (sgz_run_carry [2][channels]), loudness and
+    // band (two halves of <lane>CarryBytes(filter) * channels bytes), and the two filters
     PcmLane lane[kPcmLanes];
     sgz_loudness_filter ldFilter{};
     sgz_band_filter bdFilter{};
+    sgz_run_params rnParams{};                          // the run lane's thresholds
     // the track lane (track.most > 0: armed): a sink of frames, and the graph and mouse position searched
     PcmSink track;
     uint32_t trGraph = 0;
@@ -426,6 +428,17 @@ struct PcmTruePeak {
     {
         return runTruePeakColumns(sh, in, s.stride, s.numChannels, n, l.m, uint32_t(l.open), continued, static_cast<const sgz_truepeak_carry *>(carryIn),
                                   static_cast<sgz_truepeak_carry *>(carryOut), static_cast<sgz_truepeak_record *>(d_out), scratch, s.compute);
+    }
+};
+struct PcmRun {
+    static constexpr bool keptScratch = false;
+    static constexpr auto shape = runColumnsShape;
+    static size_t carryBytes(const sgz_pcm_stream &) { return sizeof(sgz_run_carry); }
+    static sgz_status run(sgz_pcm_stream &s, PcmLane &l, const ColumnsShape &sh, const float *in, size_t n, uint32_t continued, const void *carryIn,
+                          void *carryOut, void *d_out, void *scratch)
+    {
+        return runRunColumns(sh, s.rnParams, in, s.stride, s.numChannels, n, l.m, uint32_t(l.open), continued, static_cast<const sgz_run_carry *>(carryIn),
+                             static_cast<sgz_run_carry *>(carryOut), static_cast<sgz_run_record *>(d_out), scratch, s.compute);
     }
 };
 struct PcmLoudness {
@@ -922,6 +935,7 @@ sgz_status sgz_pcm_stream_create(const sgz_spectrum_config *cfg, uint32_t format
         {"stereo-field", "field", kOutField, cfg->num_pairs * sizeof(sgz_field_record), pcmOpenColumnRun<sgz_field_record, 1, true, fieldColumnsShape, runFieldColumns>},
         {"band", "band", kOutBand, s->numChannels * sizeof(sgz_band_record), pcmHistoryRun<PcmBand>},
         {"histogram", "hist", kOutHist, s->numChannels * sizeof(sgz_hist_record), pcmOpenColumnRun<sgz_hist_record, 1, false, histColumnsShape, runHistColumns>},
+        {"run", "run", kOutRun, s->numChannels * sizeof(sgz_run_record), pcmHistoryRun<PcmRun>},
     };
     for (int id = 0; id < kPcmLanes; ++id) {
         PcmLane &l = s->lane[id];
@@ -1304,6 +1318,27 @@ sgz_status sgz_pcm_stream_set_hist(sgz_pcm_stream *s, uint32_t m, sgz_hist_recor
     return SGZ_OK;
 }
 
+sgz_status sgz_pcm_stream_set_run(sgz_pcm_stream *s, const sgz_run_params *params, uint32_t m, sgz_run_record *out, uint64_t capacity_columns)
+{
+    if (!s) return fail(SGZ_EINVAL, "null stream");
+    PcmLane &l = s->lane[kSinkRun];
+    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
+    if (m < 32) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_run: m >= 32 samples per column (a 96-byte record per channel for fewer would read back more than the samples)");
+    if (sgz_status st = runParamsCheck(params, "sgz_pcm_stream_set_run"); st != SGZ_OK) return st;
+    if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_run: null out");
+    if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_run_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_run: out is not aligned to 4 bytes");
+    const bool same = l.m == m && std::memcmp(&s->rnParams, params, sizeof *params) == 0;
+    if (l.open && !same) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_run: m or the params differ from the open column's -- flush it (sgz_pcm_stream_flush_run), disarm or reset first");
+    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * sizeof(sgz_run_carry)));
+    if (!same) {
+        s->rnParams = *params;
+        l.continued = false;                                       // (arming: the lane starts at the next sample, index 0, with a history of marks)
+        l.index = 0;
+    }
+    pcmLaneArm(*s, l, m, out, capacity_columns);
+    return SGZ_OK;
+}
+
 uint64_t sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkWave, nsamples, flush); }
 uint64_t sgz_pcm_stream_level_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkLevel, nsamples, flush); }
 uint64_t sgz_pcm_stream_truepeak_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkTruePeak, nsamples, flush); }
@@ -1311,6 +1346,7 @@ uint64_t sgz_pcm_stream_loudness_for(const sgz_pcm_stream *s, size_t nsamples, i
 uint64_t sgz_pcm_stream_field_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkField, nsamples, flush); }
 uint64_t sgz_pcm_stream_band_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkBand, nsamples, flush); }
 uint64_t sgz_pcm_stream_hist_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkHist, nsamples, flush); }
+uint64_t sgz_pcm_stream_run_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkRun, nsamples, flush); }
 
 sgz_status sgz_pcm_stream_waveform_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkWave, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_level_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkLevel, columns_written, open_samples); }
@@ -1319,6 +1355,7 @@ sgz_status sgz_pcm_stream_loudness_state(const sgz_pcm_stream *s, uint64_t *colu
 sgz_status sgz_pcm_stream_field_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkField, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_band_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkBand, columns_written, open_samples); }
 sgz_status sgz_pcm_stream_hist_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkHist, columns_written, open_samples); }
+sgz_status sgz_pcm_stream_run_state(const sgz_pcm_stream *s, uint64_t *columns_written, uint64_t *open_samples) { return pcmLaneState(s, kSinkRun, columns_written, open_samples); }
 
 sgz_status sgz_pcm_stream_flush_waveform(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkWave); }
 sgz_status sgz_pcm_stream_flush_level(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkLevel); }
@@ -1327,6 +1364,7 @@ sgz_status sgz_pcm_stream_flush_loudness(sgz_pcm_stream *s) { return pcmLaneFlus
 sgz_status sgz_pcm_stream_flush_field(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkField); }
 sgz_status sgz_pcm_stream_flush_band(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkBand); }
 sgz_status sgz_pcm_stream_flush_hist(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkHist); }
+sgz_status sgz_pcm_stream_flush_run(sgz_pcm_stream *s) { return pcmLaneFlush(s, kSinkRun); }
 
 // ---- the track lane's calls -------------------------------------------------------------------------------------------------------------------
 sgz_status sgz_pcm_stream_set_track(sgz_pcm_stream *s, uint32_t graph, double mouse_fraction, sgz_line_peak *track_out, uint64_t capacity_frames)
