@@ -188,9 +188,11 @@ __global__ void __launch_bounds__(1024) decayLocalCarryKernel(const DecayParams 
 
 // The whole of K_B as ONE launch for the commonest request: the colour column only (no line results, no state out), one pair, at
 // most kFusedChunks time chunks.  A workgroup of 1024 threads owns PX = 4 pixels for the whole time axis:
-//   1. threads (chunk, px) < 64 x 4 load their chunk's magnitudes (side 0), park them in LDS and scan the chunk from a zero carry;
+//   1. all threads load the frames x 4 magnitudes (side 0) into LDS; threads (chunk, px) < 64 x 4 scan their chunk from a zero carry and
+//      leave every frame's state where its magnitude was;
 //   2. 4 threads fold the chunk-end states with the same sequential multiplies as decayCarryKernel;
-//   3. ALL threads share the frames x 4 emissions (replay <= 8 steps from the LDS magnitudes on the folded carry-in, dB map, colour).
+//   3. all threads but the fold's wave share the frames x 4 emissions (the frame's zero-carry state from LDS against the folded carry-in
+//      decayed up to the frame, dB map, colour).
 // Nothing goes through HBM between the steps and there is one launch instead of two.
 // The fused kernels' fold publishes how many chunk carries are final; the emitting waves wait for the one they need.
 #define SGZ_PUBLISH(n) asm volatile("ds_write_b32 %0, %1" :: "v"(progressAddr), "v"(uint32_t(n)) : "memory")
@@ -258,10 +260,14 @@ __global__ void __launch_bounds__(1024) decayColourFusedKernel(const DecayParams
         }
     }
     __syncthreads();
-    // 1b. zero-carry scan of every chunk
+    // (a thread's scan and all of its emissions are for one pixel)
+    static_assert(64 % PX == 0 && 960 % PX == 0, "thread tid's items tid - 64 + 960 k are all of pixel tid % PX");
+    const uint32_t px = tid % PX;
+    const uint32_t pixel = pixelGroup() * PX + px;
+    // 1b. zero-carry scan of every chunk; the state of every frame goes back over its magnitude (only this thread touches its chunk's
+    //     entries), so that an emission reads one word where it used to replay the chunk up to its frame
     if (tid < kFusedChunks * PX) {
-        const uint32_t px = tid % PX, chunk = tid / PX;
-        const uint32_t pixel = pixelGroup() * PX + px;
+        const uint32_t chunk = tid / PX;
         const long f0 = long(chunk) * kMaxChunk;
         const int len = chunk < prm.numChunks ? int(min(long(kMaxChunk), prm.frames - f0)) : 0;
         float a = (pixel < prm.P && chunk == 0 && prm.stateIn) ? prm.stateIn[size_t(pixel) * 2] : 0.f;
@@ -271,6 +277,7 @@ __global__ void __launch_bounds__(1024) decayColourFusedKernel(const DecayParams
                 const float m = magS[chunk * kMaxChunk + t][px];
                 a = a * pole;                                   // states[i] *= pole, TransformDSP.inl:1336,:1370
                 if (m > a) a = m;                               // :1338-1341
+                magS[chunk * kMaxChunk + t][px] = a;
             }
         aggS[chunk][px] = a;
     }
@@ -309,21 +316,18 @@ __global__ void __launch_bounds__(1024) decayColourFusedKernel(const DecayParams
         }
     }
     if (tid < 64) return;                                       // the fold's wave is done
+    // 3. emissions, one item per (frame, pixel): the frame's zero-carry state from LDS (read in front of the wait: it does not depend on
+    //    the carry), the carry of the chunk before decayed t + 1 times (no memory operation in that loop: it compiles to eight multiplies
+    //    and selects), the larger of the two through the dB map and the gradient
+    if (pixel >= prm.P) return;
     for (uint32_t e = tid - 64; e < items; e += 960) {
-        const uint32_t px = e % PX, f = e / PX, chunk = f / kMaxChunk, t = f % kMaxChunk;
-        const uint32_t pixel = pixelGroup() * PX + px;
-        if (pixel >= prm.P) continue;
+        const uint32_t f = e / PX, chunk = f / kMaxChunk, t = f % kMaxChunk;
+        const float a = magS[f][px];
         awaitCarries(progressAddr, chunk);
-        float a = (chunk == 0 && prm.stateIn) ? prm.stateIn[size_t(pixel) * 2] : 0.f;
         float cr = chunk > 0 ? carryS[chunk - 1][px] : 0.f;    // exact state at the end of the previous chunk
 #pragma unroll
         for (int i = 0; i < kMaxChunk; ++i)
-            if (uint32_t(i) <= t) {
-                const float m = magS[chunk * kMaxChunk + i][px];
-                a = a * pole;
-                if (m > a) a = m;
-                cr = cr * pole;
-            }
+            if (uint32_t(i) <= t) cr = cr * pole;
         const float st = a > cr ? a : cr;
         float cb[3] = {0.f, 0.f, 0.f};                          // colourBuffer, SpectrumDSP.cpp:170-174
         blendColour(cb, dbMap(prm.slope[pixel], st, prm.sc, logTab), prm.colourTables, prm.sc);
