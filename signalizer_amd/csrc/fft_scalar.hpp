@@ -133,22 +133,28 @@ __device__ __forceinline__ void bflyPackedFusedTw(v2 &a, v2 &b, v2 ta, v2 tb)
     a = p; b = q;
 }
 
+// the butterflies of stage S on ONE block of 2^S logical elements y[k0 .. k0 + 2^S), y[i] = c[base + brev(i)] (k0, base: compile-time
+// values of a fully unrolled caller)
+template <int LR, int S, int NREG>
+__device__ __forceinline__ void ditBlockPacked(v2 (&c)[NREG], const int base, const int k0)
+{
+    constexpr int m = 1 << S, h = m / 2;
+#pragma unroll
+    for (int j = 0; j < h; ++j) {
+        const int ia = base + brev(k0 + j, LR), ib = base + brev(k0 + j + h, LR);
+        const int tw = j * (32 / m);                                    // W_32^tw, tw in [0, 16)
+        if (tw == 0) { const v2 a = c[ia], b = c[ib]; c[ia] = a + b; c[ib] = a - b; }
+        else if (tw == 8) bflyPackedRot(c[ia], c[ib]);
+        else if (tw < 8) bflyPackedLow(c[ia], c[ib], v2{cos32(tw), sin32(tw)});
+        else bflyPackedHigh(c[ia], c[ib], v2{cos32(tw - 8), sin32(tw - 8)});
+    }
+}
 template <int LR, int S, int BASE, int NREG>
 __device__ __forceinline__ void ditStagePacked(v2 (&c)[NREG])
 {
-    constexpr int n = 1 << LR, m = 1 << S, h = m / 2;
+    constexpr int n = 1 << LR, m = 1 << S;
 #pragma unroll
-    for (int k0 = 0; k0 < n; k0 += m) {
-#pragma unroll
-        for (int j = 0; j < h; ++j) {
-            const int ia = BASE + brev(k0 + j, LR), ib = BASE + brev(k0 + j + h, LR);
-            const int tw = j * (32 / m);                                // W_32^tw, tw in [0, 16)
-            if (tw == 0) { const v2 a = c[ia], b = c[ib]; c[ia] = a + b; c[ib] = a - b; }
-            else if (tw == 8) bflyPackedRot(c[ia], c[ib]);
-            else if (tw < 8) bflyPackedLow(c[ia], c[ib], v2{cos32(tw), sin32(tw)});
-            else bflyPackedHigh(c[ia], c[ib], v2{cos32(tw - 8), sin32(tw - 8)});
-        }
-    }
+    for (int k0 = 0; k0 < n; k0 += m) ditBlockPacked<LR, S>(c, BASE, k0);
 }
 // 2^LR-point transform of c[BASE .. BASE + 2^LR): x[j] in c[BASE + j] -> X[k] in c[BASE + brev(k, LR)] (difPacked's convention)
 template <int LR, int BASE, int NREG, int FIRST = 1>
@@ -159,6 +165,35 @@ __device__ __forceinline__ void ditPacked(v2 (&c)[NREG])
     if constexpr (LR >= 3) ditStagePacked<LR, 3, BASE>(c);
     if constexpr (LR >= 4) ditStagePacked<LR, 4, BASE>(c);
     if constexpr (LR >= 5) ditStagePacked<LR, 5, BASE>(c);
+}
+
+// ---- The same transform traversed BY ARRIVAL, for input that is still on its way from memory.  ditPacked reads its input through
+// brev(), so logical element i is row brev(i): stage 1 pairs rows (j, j + n/2), stage 2 the quads {0, n/2, n/4, 3n/4}, ... .  With the rows
+// requested in the order brev(0), brev(1), ... -- logical order -- every block of every stage is complete as soon as its LAST logical
+// element is in, and the depth-first order below runs each block at that moment: behind the last row pair only one stage-1 butterfly
+// and one block of each later stage remain (1 + 2 + 4 + 8 of a 16-point column's 32 butterflies).  Same blocks (ditBlockPacked), same
+// operands and constants as ditPacked; only the order among independent butterflies differs.
+// COLS columns at c[u STRIDE ..] whose rows arrive together (one request carries row j of every column); arrived(u, j) is called once
+// per column and row pair (j, j + n/2), j < n/2, in front of that pair's stage-1 butterfly: the caller's work on the raw rows.
+template <int LR, int S, int NREG>
+__device__ __forceinline__ void ditBlocksEndingAt(v2 (&c)[NREG], const int base, const int end)
+{
+    if constexpr (S <= LR) {
+        constexpr int m = 1 << S;
+        if (end % m == 0) { ditBlockPacked<LR, S>(c, base, end - m); ditBlocksEndingAt<LR, S + 1>(c, base, end); }
+    }
+}
+template <int LR, int COLS, int STRIDE, int NREG, typename F>
+__device__ __forceinline__ void ditPackedByArrival(v2 (&c)[NREG], F &&arrived)
+{
+#pragma unroll
+    for (int i = 0; i < (1 << LR); i += 2) {
+#pragma unroll
+        for (int u = 0; u < COLS; ++u) {
+            arrived(u, brev(i, LR));
+            ditBlocksEndingAt<LR, 1>(c, u * STRIDE, i + 2);
+        }
+    }
 }
 
 }  // namespace sgz

@@ -462,6 +462,13 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
 #else
     constexpr bool DIET = false;
 #endif
+    // STREAM (N = 32768, window evaluated in the kernel, one signal): the window and pass 1 run UNDER the samples' arrival.  The two window
+    // phases are requested in front of the samples and the sixteen rows in the order pass 1 consumes them -- 0, 8, 4, 12, 2, 10, ... :
+    // bit-reversed, which is ditPacked's logical order -- so that each window pair and each butterfly issues when its own rows are in
+    // (fft_scalar.hpp ditPackedByArrival) and behind the LAST row there remain one window pair and 15 of a column's 32 butterflies.  In
+    // request order all sixteen rows stood in front of one wait, and the window's and pass 1's ~216 packed operations per thread -- a
+    // seventh of a wave's vector work -- overlapped none of the arrival.  Same operations on the same operands: bit for bit.
+    constexpr bool STREAM = LR1 == 4 && PAIRED && FRONT && !DIET;
     [[maybe_unused]] float4 phase[U];
     [[maybe_unused]] float2 twA[U], twB[U];
     [[maybe_unused]] float4 tw2piece, tw2tail;                  // (T = 512: threads 0 .. 31 carry a second piece of the 544)
@@ -489,7 +496,10 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
         if constexpr (PAIRED) {
             typedef float v4 __attribute__((ext_vector_type(4)));
 #pragma unroll
-            for (int j = 0; j < R1; ++j) { const v4 xv = ldgPinned<v4>(X, uint32_t(RR * j) * 8u, lane8); c[j] = v2{xv.x, xv.y}; c[R1 + j] = v2{xv.z, xv.w}; }
+            for (int i = 0; i < R1; ++i) {
+                const int j = STREAM ? brev(i, LR1) : i;                      // (STREAM: in the order pass 1 consumes them)
+                const v4 xv = ldgPinned<v4>(X, uint32_t(RR * j) * 8u, lane8); c[j] = v2{xv.x, xv.y}; c[R1 + j] = v2{xv.z, xv.w};
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < R; ++i)
@@ -502,12 +512,18 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     // its own in the workgroup's dependent chain: table -> LDS copy (waited for before the first sample was requested), samples,
     // second column's phases, first column's twiddles, second column's twiddles.  (N = 16384: 256 threads x four columns at the
     // 128-register limit: requested where used, as before.)
+    // (STREAM: the window phases alone go IN FRONT of the samples -- 16 bytes per lane of a 16 KB table every workgroup shares; the load
+    // counter is waited for in order, and the first window pair needs them with the first two rows)
+    auto requestPhases = [&](const int tid) {
+#pragma unroll
+        for (int u = 0; u < (DIET ? 1 : U); ++u) phase[u] = ldg(prm.winPhase + COLSTEP * u, uint32_t(tid) * 16u * COLLANE);
+    };
     auto requestTables = [&](const int tid) {
         if constexpr (FRONT) {
             if constexpr (WALK) tw2piece = prm.tw2Full[tid < kTw2Floats / 4 ? tid : 0];     // (unconditional: a conditional one makes the registers loop-carried)
+            if constexpr (WCOS && !STREAM) requestPhases(tid);
 #pragma unroll
             for (int u = 0; u < (DIET ? 1 : U); ++u) {
-                if (WCOS) phase[u] = ldg(prm.winPhase + COLSTEP * u, uint32_t(tid) * 16u * COLLANE);
                 twA[u] = ldg(prm.tw1 + (COLSTEP * u), uint32_t(tid) * 8u * COLLANE);
                 twB[u] = ldg(prm.tw1 + (COLSTEP * u + 3 * RR), uint32_t(tid) * 8u * COLLANE);
             }
@@ -569,6 +585,7 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
             __builtin_amdgcn_sched_barrier(0);
             if (tid < kTw2Floats / 4) reinterpret_cast<float4 *>(lds + TAB)[tid] = tw2piece;
         } else {
+            if constexpr (STREAM) { requestPhases(tid); __builtin_amdgcn_sched_barrier(0); }
             requestSamples(X, tid, std::integral_constant<int, 0>{});
             requestTables(tid);
         }
@@ -598,8 +615,20 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
             // (even, odd) sample pairs with packed operations, and only for j < R1 / 2: j + R1 / 2 is half a turn further, its cosine the
             // negative -- w[j] = p0 + t, w[j + R1/2] = p0 - t with t = p1 cos(theta_j) (p1 is folded into the table).
             const v2 p0 = v2{prm.winP0, prm.winP0};
+            if constexpr (STREAM) {
+                // program order is arrival order: window pair (0, 8) and its stage-1 butterfly, pair (4, 12), its butterfly and the quad's
+                // stage 2, ... for both columns of each row; the compiler places the partial waits
+                ditPackedByArrival<LR1, U, R1>(c, [&](const int u, const int j) __attribute__((always_inline)) {
+#ifdef SGZ_DEBUG
+                    // (debug stamps: the first requested row pair is in / the last requested rows, and so all sixteen, are in)
+                    if (u == 0 && j == 0) { asm volatile("" : "+v"(c[0]), "+v"(c[R1 / 2])); RCLK(14); }
+                    if (u == 0 && j == R1 / 2 - 1) { asm volatile("" : "+v"(c[R1 / 2 - 1]), "+v"(c[R1 - 1])); RCLK(15); }
+#endif
+                    windowPairCos(c[u * R1 + j], c[u * R1 + j + R1 / 2], j * (32 / R1), v2{phase[u].x, phase[u].y}, v2{phase[u].z, phase[u].w}, p0);
+                });
+            }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
+            for (int u = 0; u < (STREAM ? 0 : U); ++u) {
                 const float4 ph = (DIET && u == 1) ? rotatePhaseForward(phase[0], kRotA1Cm1, kRotA1Sin)
                                   : FRONT ? phase[u] : ldg(prm.winPhase + COLSTEP * u, uint32_t(tid) * 16u * COLLANE);     // p1 x (cos even, cos odd, sin even, sin odd) of the column's first pair
                 const v2 pc = v2{ph.x, ph.y}, ps = v2{ph.z, ph.w};
@@ -649,7 +678,7 @@ __global__ void __launch_bounds__(1 << (LR1 + 5), 4) stftRealKernel(const RealPa
     __builtin_amdgcn_sched_barrier(0);
     RCLK(13);
     // -------------------------------------------------------------------------- pass 1: radix R1 per column, times W_M^{c q1}
-    pass1Columns<R, R1, U, LR1>(c);
+    if constexpr (!STREAM) pass1Columns<R, R1, U, LR1>(c);              // (STREAM: done with the window, above)
 #ifdef SGZ_IMAGE_PRIO
     // scopes 1 and 2 start HERE, behind pass 1's butterflies.  In front of pass 1 -- a block boundary between the window and the butterflies,
     // where all 128 registers are live -- the branch made the kernel spill 42 registers; in front of exchange 1 it keeps a fifth of the gain,

@@ -17,7 +17,9 @@ L = api.lib()
 L.sgz_debug_set_ablate((int(sys.argv[2]) if len(sys.argv) > 2 else 0) | ((int(sys.argv[3]) if len(sys.argv) > 3 else 0) << 16))
 L.sgz_debug_phase_clocks.argtypes = [C.c_void_p] * 2 + [C.c_size_t] * 2 + [C.c_void_p] * 3
 names = ["start", "pass1 done", "ex1 done", "pass2 done", "ex2 done", "pass3 done", "mirror done", "M in LDS", "binsOut", "end",
-         "map: pieces scanned", "map: interp done", "map: barrier", "windowed", "dif1 done"]
+         "map: pieces scanned", "map: interp done", "map: barrier", "windowed", "first row pair in", "all rows in"]
+# (N = 32768 streamed load: "first row pair in" / "all rows in" are stamped inside the window-and-pass-1 traversal and "windowed" stands
+# behind pass 1; the other forms leave the two slots 0)
 # SGZ_BUFFERS=n: the launches rotate over n copies of the audio (n x 23 MB at cfg2: 16 of them are past the Infinity Cache -- the input of the
 # launch that is reported then comes from HBM)
 xs = [x] + [x.clone() for _ in range(max(1, int(os.environ.get("SGZ_BUFFERS", "1"))) - 1)]
@@ -28,7 +30,7 @@ for rep in range(max(3, 2 * len(xs))):
 c = clk.cpu().numpy().reshape(16, 16)
 c = c[:int(os.environ.get('SGZ_WAVES', '16'))]      # (the channel-split kernel at N = 32768 has 8 waves)
 t0 = c[:, 0].min()
-order = [0, 13, 14, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 12, 9]
+order = [0, 14, 15, 13, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 12, 9]
 if cfg5 and os.environ.get("SGZ_REALCLK") != "1":   # halves kernel: the map slots are then written by mapSideKernel (a later launch): print the two kernels
     # separately.  (SGZ_REALCLK=1: the plan runs the channel-split kernel at N = 65536 -- the default since round 2 --, one kernel, the full list)
     order = [0, 7, 10, 11, 12, 9] if os.environ.get("SGZ_MAPCLK") == "1" else [13, 14, 1, 2, 3, 4, 5, 6, 8]
