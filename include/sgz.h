@@ -100,6 +100,11 @@ extern "C" {
  *  sgz_run_readout and, on the PCM stream, sgz_pcm_stream_set_run, sgz_pcm_stream_run_for, sgz_pcm_stream_run_state,
  *  sgz_pcm_stream_flush_run.  No existing entry point or struct changed and the suite pins 5; a stream that was never armed enqueues what
  *  it did before.)
+ * (5, later: the percentile overview -- SGZ_OVERVIEW_PCT_BUCKETS, SGZ_OVERVIEW_PCT_MAX_QUANTILES, sgz_overview_pct_record,
+ *  sgz_stage_overview_pct, sgz_spectrogram_overview_pct_device / _host, the host helpers sgz_overview_pct_bucket, sgz_overview_pct_fold and
+ *  sgz_overview_pct_readout and, on the PCM stream, sgz_pcm_stream_feed_overview_pct and sgz_spectrogram_overview_pct_pcm.  No existing
+ *  entry point or struct changed and the suite pins 5; the new refusals on existing calls, a feed of another kind while a percentile
+ *  column is open, cannot be reached without the new calls.  A binding that needs them looks the symbols up.)
  * a binding compares sgz_abi_version() with the header it was compiled against */
 #define SGZ_ABI_VERSION 5
 
@@ -648,7 +653,7 @@ sgz_status sgz_spectrogram_overview_host(sgz_plan *plan, const float *const *pla
  * for byte: the mean is the quantised value.
  * The mean is a mean of displayed (dB-axis) values, hence the geometric mean of the magnitudes: it is defined on what every render writes
  * and what the colour map takes.  A power-domain mean needs magnitudes from before the dB map: that is the power overview below, which
- * reduces K_A's mapped magnitudes.  Percentiles and the median are out of scope.
+ * reduces K_A's mapped magnitudes.  (Percentiles and the median were out of scope here: they are "The percentile overview" below.)
  * The calls follow their peak-hold twins argument for argument: float *d_peaks becomes sgz_overview_stat_record *d_stats, and every call
  * has one more optional output, the means float [columns][pairs][P] -- value planes as V is (sgz_stage_track_peaks_values takes them).
  * Of image, records and means at least one must be non-NULL.  The carry is sgz_overview_stat_record [pairs][P].
@@ -703,6 +708,90 @@ sgz_status sgz_pcm_stream_feed_overview_stats(sgz_pcm_stream *s, const void *pcm
 sgz_status sgz_spectrogram_overview_stats_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
                                               const uint32_t *channel_map, size_t nsamples, uint32_t k, uint8_t *rgba_out,
                                               sgz_overview_stat_record *stats_out, float *means_out, sgz_pcm_timing *timing);
+
+/* The percentile overview: how a pixel's level is distributed over the k frames of a column -- the noise floor per frequency (the 10 %
+ * level), the median spectrum, which is robust against the bursts that saturate a peak hold, and the "95 % ceiling".  No associative fold
+ * of bounded size gives an order statistic exactly; a histogram over fixed buckets is such a fold, exact at the bucket's resolution, and
+ * every cut gives the same bytes (the histogram lane's answer for samples, applied to the spectrum).
+ * Definition (exact, no tolerance).  L[f][p][g][i], F and k as in the overview render; columns and their frames are counted exactly as
+ * there (sgz_overview_step).  Let x = L[f][p][0][i].x, the mean overview's input.
+ *   bucket     of a non-NaN x, SGZ_OVERVIEW_PCT_BUCKETS = 66 of them: bucket 0 takes x < 0 (-inf and the clip value included), bucket 65
+ *              takes x >= 1 (+inf included), otherwise the bucket is 1 + floor(64 x).  64 x and the floor are exact in fp32: there is no
+ *              rounding to argue about.  -0 lies in bucket 1; a value exactly on an edge j/64 lies in the upper bucket.  A bucket is 1/64
+ *              of the displayed dB axis -- 1.875 dB at a 120 dB range -- and gets finer as the user narrows the range.
+ *   record     per (column, pair, pixel) one sgz_overview_pct_record: bucket[b] = the frames whose x lies in bucket b; nans = the NaN
+ *              frames; reserved = 0.  count is the sum of the buckets.
+ *   fold       every word adds.  The fold is associative and commutative: every cut (slices, calls, slabs, feeds, chunk sizes) gives
+ *              the same bytes, and a coarser column is exactly the fold of the finer ones it covers.
+ *   quantile   q in [0, 1] of a record.  count == 0: the bits 0x7FC00000.  Otherwise r = the least integer >= q count, clamped to
+ *              [1, count] (the product is one fp64 multiply: sgz_hist_percentile's rule); b = the least bucket whose cumulative count is
+ *              >= r; before = the cumulative count below b.  The value is -2^-6 for b == 0, 1.0f for b == 65, and otherwise
+ *              (float)(((double)(b - 1) + ((double)(r - before) - 0.5) / (double)bucket[b]) * 2^-6), every conversion and the division
+ *              rounded to nearest even, nothing contracted.
+ *              Consequence: for a record whose non-NaN values all lie in [0, 1) the value is within 1/64 of the exact order statistic
+ *              sorted(x)[r - 1] (both lie in bucket b).  For any input the value is monotone in q.
+ *   pixel      the additive blend of the pairs' colours at quantile 0's value (q[0]), p = 0 .. pairs - 1 in order, from a black column
+ *              buffer, then the 8-bit conversion -- the mean overview's pixel with that value in the mean's place.
+ * The calls mirror the mean overview's argument for argument: sgz_overview_stat_record becomes sgz_overview_pct_record, float *d_means
+ * becomes float *d_values [nq][columns][pairs][P] -- each plane a value plane that sgz_stage_track_peaks_values takes and
+ * sgz_overview_view_host colours --, and every call gains const double *q, uint32_t nq behind its last scalar argument: q is a HOST pointer
+ * to nq = 1 .. SGZ_OVERVIEW_PCT_MAX_QUANTILES quantiles, each in [0, 1] and not a NaN, else SGZ_EINVAL.  The quantiles travel by value in
+ * the launch arguments: the stage call stays asynchronous and q may be reused at once.  Of image, records and values at least one must be
+ * non-NULL.  DEVICE pointers to records (d_carry, d_records) are 16-byte aligned; anything else is refused with SGZ_EINVAL.  The carry is
+ * sgz_overview_pct_record [pairs][P].
+ *  sgz_stage_overview_pct   refusals, slices (0, 1 .. 64, identical bytes), asynchrony and "only the documented bytes are written" as for
+ *                      sgz_stage_overview_stats; `columns` of d_values' layout is the columns this call closes.  With slices == 0 the
+ *                      library chooses the form: slices only where one launch would leave compute units idle, none shorter than 64 frames
+ *                      (a partial record, written and read, costs 68 row loads), and never more than 64 MiB of partial records in plan
+ *                      scratch.  An explicit slices takes slices x columns x pairs x P x 272 bytes.
+ *  sgz_spectrogram_overview_pct_device / _host   as sgz_spectrogram_overview_stats_device / _host: slabs with the decay state and the open
+ *                      column carried, bytes independent of SGZ_OPT_OVERVIEW_SLAB, RSNT plans in one slab; carry and partial scratch of
+ *                      their own in the plan.  `columns` of the values' layout is ceil(F / k).
+ *  sgz_overview_pct_bucket   host, no GPU: the bucket of x.  SGZ_EINVAL, *b untouched: b NULL, x a NaN.
+ *  sgz_overview_pct_fold     host, no GPU: columns [x0, x1) of in [n][width] (width = pairs * P records per column) into cols =
+ *                      min(out_columns, x1 - x0) columns of out by the boundary rule of sgz_overview_view_columns.  SGZ_EINVAL, nothing
+ *                      written: a null argument, width == 0, what sgz_overview_view_columns refuses, a folded word above 2^32 - 1.  The
+ *                      fold plus the readout is the zoom: there is no device view of kept records.
+ *  sgz_overview_pct_readout  host, no GPU: `count` records into values [nq][count] by the definition.  SGZ_EINVAL, nothing written: a null
+ *                      argument, q or nq as above, a record whose buckets sum above 2^32 - 1.
+ *  sgz_pcm_stream_feed_overview_pct / sgz_spectrogram_overview_pct_pcm   the overview inside sgz_pcm_stream with this reduction, a sixth
+ *                      kind of open column: the concatenated columns of all feeds equal sgz_spectrogram_overview_pct_host of the converted
+ *                      planar floats, byte for byte, however the stream is cut.  In a feed value plane j starts at values_out + j x
+ *                      capacity_columns x pairs x P and receives the feed's columns from there; in the one-shot call at j x ceil(F / k) x
+ *                      pairs x P.  records_out is a host pointer and needs 4-byte alignment only.  A feed of another kind while a
+ *                      percentile column is open, and the reverse, is refused with SGZ_EINVAL, consumes nothing and says so in
+ *                      sgz_last_error.  An armed lane runs in a percentile feed exactly as in a stats feed. */
+#define SGZ_OVERVIEW_PCT_BUCKETS 66
+#define SGZ_OVERVIEW_PCT_MAX_QUANTILES 8
+typedef struct sgz_overview_pct_record {
+    uint32_t bucket[SGZ_OVERVIEW_PCT_BUCKETS];  /* frames per bucket; count = their sum */
+    uint32_t nans;                              /* NaN frames                           */
+    uint32_t reserved;                          /* 0                                    */
+} sgz_overview_pct_record;                 /* 272 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(sgz_overview_pct_record) == 272, "sgz_overview_pct_record: 272 bytes");
+static_assert(offsetof(sgz_overview_pct_record, bucket) == 0 && offsetof(sgz_overview_pct_record, nans) == 264 &&
+              offsetof(sgz_overview_pct_record, reserved) == 268, "sgz_overview_pct_record: offsets");
+#endif
+sgz_status sgz_stage_overview_pct(sgz_plan *plan, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
+                                  const double *q /*HOST*/, uint32_t nq, sgz_overview_pct_record *d_carry, uint8_t *d_rgba,
+                                  sgz_overview_pct_record *d_records, float *d_values, void *stream);
+sgz_status sgz_spectrogram_overview_pct_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                               const double *q /*HOST*/, uint32_t nq, uint8_t *d_rgba, sgz_overview_pct_record *d_records,
+                                               float *d_values, float *d_state, void *stream);
+sgz_status sgz_spectrogram_overview_pct_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                             const double *q, uint32_t nq, uint8_t *rgba_out, sgz_overview_pct_record *records_out,
+                                             float *values_out, sgz_timing *timing);
+sgz_status sgz_overview_pct_bucket(float x, uint32_t *b);
+sgz_status sgz_overview_pct_fold(const sgz_overview_pct_record *in, size_t n, size_t width, size_t x0, size_t x1, uint32_t out_columns,
+                                 sgz_overview_pct_record *out);
+sgz_status sgz_overview_pct_readout(const sgz_overview_pct_record *records, size_t count, const double *q, uint32_t nq, float *values);
+sgz_status sgz_pcm_stream_feed_overview_pct(sgz_pcm_stream *s, const void *pcm /*HOST*/, size_t nsamples, uint32_t k, int flush, const double *q,
+                                            uint32_t nq, uint8_t *rgba_out /*or NULL*/, sgz_overview_pct_record *records_out /*or NULL*/,
+                                            float *values_out /*or NULL*/, uint64_t capacity_columns, uint64_t *columns_out, sgz_pcm_timing *timing);
+sgz_status sgz_spectrogram_overview_pct_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                            const uint32_t *channel_map, size_t nsamples, uint32_t k, const double *q, uint32_t nq,
+                                            uint8_t *rgba_out, sgz_overview_pct_record *records_out, float *values_out, sgz_pcm_timing *timing);
 
 /* The power overview: mean-square spectrum of k frames per image column -- the power-domain mean that every analyser calls "average": the
  * long-term average spectrum of a file, and the spectrum of a selection.  The mean overview above averages displayed (dB-axis) values, a

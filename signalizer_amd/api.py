@@ -286,6 +286,8 @@ EXPORTS = [
     "sgz_stage_overview_flux", "sgz_spectrogram_overview_flux_device", "sgz_spectrogram_overview_flux_host", "sgz_overview_flux_quantise",
     "sgz_overview_flux_fold", "sgz_overview_flux_readout", "sgz_overview_flux_hz", "sgz_pcm_stream_feed_overview_flux",
     "sgz_spectrogram_overview_flux_pcm",
+    "sgz_stage_overview_pct", "sgz_spectrogram_overview_pct_device", "sgz_spectrogram_overview_pct_host", "sgz_overview_pct_bucket",
+    "sgz_overview_pct_fold", "sgz_overview_pct_readout", "sgz_pcm_stream_feed_overview_pct", "sgz_spectrogram_overview_pct_pcm",
     "sgz_stage_wave_columns", "sgz_wave_columns_limits", "sgz_pcm_stream_set_waveform", "sgz_pcm_stream_waveform_for",
     "sgz_pcm_stream_waveform_state", "sgz_pcm_stream_flush_waveform",
     "sgz_track_peak_values", "sgz_stage_track_peaks_values", "sgz_pcm_stream_set_track", "sgz_pcm_stream_track_for", "sgz_pcm_stream_track_state",
@@ -400,6 +402,12 @@ def lib() -> C.CDLL:
     L.sgz_overview_stats_view_host.argtypes = [vp, vp, sz, sz, sz, u32, vp, vp, vp, C.POINTER(Timing)]
     L.sgz_overview_stats_fold.argtypes = [vp, sz, sz, sz, sz, u32, vp]
     L.sgz_overview_stats_readout.argtypes = [vp, sz, vp, vp, vp]
+    L.sgz_stage_overview_pct.argtypes = [vp, vp, sz, u32, u32, C.c_int, u32, vp, u32, vp, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_pct_device.argtypes = [vp, vp, sz, sz, u32, vp, u32, vp, vp, vp, vp, vp]
+    L.sgz_spectrogram_overview_pct_host.argtypes = [vp, vp, u32, sz, u32, vp, u32, vp, vp, vp, C.POINTER(Timing)]
+    L.sgz_overview_pct_bucket.argtypes = [C.c_float, C.POINTER(u32)]
+    L.sgz_overview_pct_fold.argtypes = [vp, sz, sz, sz, sz, u32, vp]
+    L.sgz_overview_pct_readout.argtypes = [vp, sz, vp, u32, vp]
     L.sgz_stage_overview_power.argtypes = [vp, vp, sz, u32, u32, C.c_int, u32, vp, vp, vp, vp, vp]
     L.sgz_spectrogram_overview_power_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp, vp]
     L.sgz_spectrogram_overview_power_host.argtypes = [vp, vp, u32, sz, u32, vp, vp, vp, C.POINTER(Timing)]
@@ -563,6 +571,8 @@ def lib() -> C.CDLL:
     L.sgz_spectrogram_overview_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, C.POINTER(PcmTiming)]
     L.sgz_pcm_stream_feed_overview_stats.argtypes = [vp, vp, sz, u32, C.c_int, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
     L.sgz_spectrogram_overview_stats_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, vp, C.POINTER(PcmTiming)]
+    L.sgz_pcm_stream_feed_overview_pct.argtypes = [vp, vp, sz, u32, C.c_int, vp, u32, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
+    L.sgz_spectrogram_overview_pct_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, u32, vp, vp, vp, C.POINTER(PcmTiming)]
     L.sgz_pcm_stream_feed_overview_power.argtypes = [vp, vp, sz, u32, C.c_int, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
     L.sgz_spectrogram_overview_power_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, vp, vp, C.POINTER(PcmTiming)]
     L.sgz_pcm_stream_set_cross_edges.argtypes = [vp, vp, u32]
@@ -914,6 +924,50 @@ def overview_stats_readout(records: np.ndarray):
     mean, lo, hi = (np.zeros(records.shape, np.float32) for _ in range(3))
     check(lib().sgz_overview_stats_readout(_np_ptr(records), records.size, _np_ptr(mean), _np_ptr(lo), _np_ptr(hi)))
     return mean, lo, hi
+
+
+# sgz_overview_pct_record (sgz.h, "The percentile overview"): 272 bytes.  On the device a record is 34 int64 words of a torch tensor [..., 34]
+# (whose storage torch aligns well beyond the 16 bytes the calls ask for); pct_from_device turns such a tensor into a numpy array of this dtype
+OVERVIEW_PCT_BUCKETS, OVERVIEW_PCT_MAX_QUANTILES = 66, 8
+OVERVIEW_PCT_DTYPE = np.dtype({"names": ["bucket", "nans", "reserved"], "formats": [("<u4", (OVERVIEW_PCT_BUCKETS,)), "<u4", "<u4"],
+                               "offsets": [0, 264, 268], "itemsize": 272})
+
+
+def pct_from_device(t) -> np.ndarray:
+    """cuda int64 [..., 34] (records as the percentile calls write them) -> numpy OVERVIEW_PCT_DTYPE [...]"""
+    return _records_from_device(t, OVERVIEW_PCT_DTYPE)
+
+
+def pct_to_device(records: np.ndarray, device):
+    """numpy OVERVIEW_PCT_DTYPE [...] -> cuda int64 [..., 34]"""
+    return _records_to_device(records, OVERVIEW_PCT_DTYPE, 34, device)
+
+
+def _quantiles(q):
+    """the calls' (const double *q, uint32_t nq): a scalar or a sequence -> (float64 array kept alive by the caller, its pointer, nq)"""
+    a = np.ascontiguousarray(np.atleast_1d(np.asarray(q, np.float64)))
+    return a, _np_ptr(a), int(a.size)
+
+
+def overview_pct_bucket(x: float) -> int:
+    """sgz_overview_pct_bucket (host, no GPU): the bucket of a non-NaN value"""
+    b = C.c_uint32(0)
+    check(lib().sgz_overview_pct_bucket(C.c_float(x), C.byref(b)))
+    return int(b.value)
+
+
+def overview_pct_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
+    """sgz_overview_pct_fold (host, no GPU): OVERVIEW_PCT_DTYPE records [n, ...], source columns [x0, x1) -> [min(out_columns, x1 - x0), ...]"""
+    return _overview_fold("sgz_overview_pct_fold", OVERVIEW_PCT_DTYPE, records, out_columns, x0, x1)
+
+
+def overview_pct_readout(records: np.ndarray, q) -> np.ndarray:
+    """sgz_overview_pct_readout (host, no GPU): OVERVIEW_PCT_DTYPE records [...] and nq quantiles -> float32 values [nq, ...]"""
+    records = np.ascontiguousarray(records, OVERVIEW_PCT_DTYPE)
+    qa, qp, nq = _quantiles(q)
+    values = np.zeros((nq, *records.shape), np.float32)
+    check(lib().sgz_overview_pct_readout(_np_ptr(records), records.size, qp, nq, _np_ptr(values)))
+    return values
 
 
 # sgz_overview_power_record (sgz.h, "The power overview"): 32 bytes, 8-aligned; sum = (low word, high word) of the 128-bit sum.  On the device
@@ -1376,6 +1430,70 @@ class Plan:
         if st == SGZ_SKIPPED_FRAME:
             return None
         return (rgba[:columns] if want_rgba else None), (stats[:columns] if want_stats else None), (means[:columns] if want_means else None)
+
+    # the percentile overview: the same columns, reduced to 66-bucket records; nq quantile planes, the image coloured from quantile 0
+    def overview_pct_columns(self, lines, k: int, q=0.5, held: int = 0, flush: bool = True, slices: int = 0, carry=None, want_rgba: bool = True,
+                             want_records: bool = False, want_values: bool = False, stream=None):
+        """sgz_stage_overview_pct: lines -- cuda float32 [frames, pairs, graphs, P, 2]; q -- a quantile or up to 8 of them; carry -- cuda
+        int64 [pairs, P, 34], the open column's records (read when held > 0, written when frames stay open).  Returns (cuda rgba uint8
+        [columns, P, 4] or None, cuda records int64 [columns, pairs, P, 34] or None -- see pct_from_device --, cuda values float32
+        [nq, columns, pairs, P] or None, frames left open)."""
+        import torch
+        assert lines.is_cuda and lines.dtype == torch.float32 and lines.is_contiguous()
+        assert tuple(lines.shape[1:]) == (self.C, NUM_GRAPHS, self.P, 2)
+        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * self.P * 34)
+        qa, qp, nq = _quantiles(q)
+        frames = lines.shape[0]
+        columns, held_out = overview_step(k, held, frames, flush)
+        rgba = torch.empty((max(columns, 1), self.P, 4), dtype=torch.uint8, device=lines.device) if want_rgba else None       # (never a NULL pointer)
+        records = torch.empty((max(columns, 1), self.C, self.P, 34), dtype=torch.int64, device=lines.device) if want_records else None
+        values = torch.empty((max(nq, 1), max(columns, 1), self.C, self.P), dtype=torch.float32, device=lines.device) if want_values else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(lib().sgz_stage_overview_pct(self.h, lines.data_ptr(), frames, k, held, int(bool(flush)), slices, qp, nq,
+                                           carry.data_ptr() if carry is not None else None, rgba.data_ptr() if want_rgba else None,
+                                           records.data_ptr() if want_records else None, values.data_ptr() if want_values else None, s))
+        return ((rgba[:columns] if want_rgba else None), (records[:columns] if want_records else None),
+                (values[:, :columns] if want_values else None), held_out)
+
+    def overview_pct(self, planar, k: int, q=0.5, want_rgba: bool = True, want_records: bool = False, want_values: bool = False, state=None, stream=None):
+        """The percentile overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_pct_host -> (rgba or None, records
+        OVERVIEW_PCT_DTYPE [columns, C, P] or None, values float32 [nq, columns, C, P] or None, timing dict).  planar a cuda tensor:
+        sgz_spectrogram_overview_pct_device, asynchronous -> (cuda rgba, cuda records int64 [columns, C, P, 34], cuda values), None where
+        not wanted.  Fewer samples than a window: None."""
+        qa, qp, nq = _quantiles(q)
+        if isinstance(planar, np.ndarray):
+            planar = np.ascontiguousarray(planar, np.float32)
+            nch, S = planar.shape
+            columns = -(-self.num_frames(S) // k)
+            n = max(columns, 1)
+            rgba = np.zeros((n, self.P, 4), np.uint8) if want_rgba else None
+            records = np.zeros((n, self.C, self.P), OVERVIEW_PCT_DTYPE) if want_records else None
+            values = np.zeros((max(nq, 1), n, self.C, self.P), np.float32) if want_values else None
+            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
+            t = Timing()
+            st = check(lib().sgz_spectrogram_overview_pct_host(self.h, ptrs, nch, S, k, qp, nq, _np_ptr(rgba) if want_rgba else None,
+                                                               _np_ptr(records) if want_records else None, _np_ptr(values) if want_values else None,
+                                                               C.byref(t)))
+            if st == SGZ_SKIPPED_FRAME:
+                return None
+            return ((rgba[:columns] if want_rgba else None), (records[:columns] if want_records else None), (values[:, :columns] if want_values else None),
+                    {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames})
+        import torch
+        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
+        S = planar.shape[1]
+        columns = -(-self.num_frames(S) // k)
+        n = max(columns, 1)
+        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None
+        records = torch.empty((n, self.C, self.P, 34), dtype=torch.int64, device=planar.device) if want_records else None
+        values = torch.empty((max(nq, 1), n, self.C, self.P), dtype=torch.float32, device=planar.device) if want_values else None
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = check(lib().sgz_spectrogram_overview_pct_device(self.h, planar.data_ptr(), planar.stride(0), S, k, qp, nq,
+                                                             rgba.data_ptr() if want_rgba else None, records.data_ptr() if want_records else None,
+                                                             values.data_ptr() if want_values else None,
+                                                             state.data_ptr() if state is not None else None, s))
+        if st == SGZ_SKIPPED_FRAME:
+            return None
+        return (rgba[:columns] if want_rgba else None), (records[:columns] if want_records else None), (values[:, :columns] if want_values else None)
 
     def overview_stats_view(self, stats, out_columns: int, x0: int = 0, x1: int | None = None, slices: int = 0, want_rgba: bool = True,
                             want_stats: bool = False, want_means: bool = False, stream=None):
@@ -1870,28 +1988,29 @@ class PcmStream:
         """sgz_pcm_stream_open_frames: frames of the overview column that is open"""
         return int(lib().sgz_pcm_stream_open_frames(self.h))
 
-    # the five overview feeds: `call` is the C call's suffix behind sgz_pcm_stream_feed_overview
-    def _feed_overview_into(self, call: str, pcm, nsamples: int, k: int, flush: bool, outputs, capacity_columns: int, timing: bool):
+    # the six overview feeds: `call` is the C call's suffix behind sgz_pcm_stream_feed_overview; mid: what the C call takes between flush and
+    # its outputs
+    def _feed_overview_into(self, call: str, pcm, nsamples: int, k: int, flush: bool, outputs, capacity_columns: int, timing: bool, mid=()):
         t, c = PcmTiming() if timing else None, C.c_uint64(0)
         st = getattr(lib(), "sgz_pcm_stream_feed_overview" + call)(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
-                                                                   *[_buf_ptr(a) if a is not None else None for a in outputs],
+                                                                   *mid, *[_buf_ptr(a) if a is not None else None for a in outputs],
                                                                    capacity_columns, C.byref(c), C.byref(t) if timing else None)
         return st, int(c.value), t
 
-    def _feed_overview(self, call: str, pcm, k: int, flush: bool, nsamples, outputs):
-        """outputs: (wanted, the shape of one column, dtype) each -> the columns that closed of every output, None where not wanted, and the
-        timing dict"""
+    def _feed_overview(self, call: str, pcm, k: int, flush: bool, nsamples, outputs, mid=()):
+        """outputs: (wanted, the shape of one column, dtype) each, or with a fourth entry, the number of planes [planes, columns, ...] the
+        output has -> the columns that closed of every output, None where not wanted, and the timing dict"""
         if pcm is None:
             n = 0
         else:
             nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
             n = nbytes // self.frame_bytes if nsamples is None else nsamples
         cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
-        arrays = [np.zeros((max(cols, 1), *shape), dtype) if want else None for want, shape, dtype in outputs]
-        st, c, t = self._feed_overview_into(call, pcm if n else None, n, k, flush, arrays, cols, True)
+        arrays = [_overview_out(cols, *o) for o in outputs]
+        st, c, t = self._feed_overview_into(call, pcm if n else None, n, k, flush, arrays, cols, True, mid)
         check(st)
         assert c == cols, (c, cols)
-        return (*[a[:cols] if a is not None else None for a in arrays], t.asdict())
+        return (*[_overview_cut(a, cols, *o) for a, o in zip(arrays, outputs)], t.asdict())
 
     def feed_overview_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, peaks, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); rgba / peaks: numpy arrays, host torch tensors or None"""
@@ -1915,6 +2034,22 @@ class PcmStream:
         P, pairs = self.cfg.axis_points, self.cfg.num_pairs
         return self._feed_overview("_stats", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_stats, (pairs, P), OVERVIEW_STAT_DTYPE),
                                                                        (want_means, (pairs, P), np.float32)])
+
+    def feed_overview_pct_into(self, pcm, nsamples: int, k: int, flush: bool, q, rgba, records, values, capacity_columns: int, timing: bool = True):
+        """the C call as it is: (status, columns_out, PcmTiming or None); rgba / records / values: numpy arrays, host torch tensors or None;
+        values is [nq, capacity_columns, pairs, P]"""
+        qa, qp, nq = _quantiles(q)
+        return self._feed_overview_into("_pct", pcm, nsamples, k, flush, (rgba, records, values), capacity_columns, timing, (qp, nq))
+
+    def feed_overview_pct(self, pcm, k: int, q=0.5, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_records: bool = True,
+                          want_values: bool = False):
+        """Feeds nsamples (default: all of pcm; pcm None: none) into the percentile overview at k frames per column and returns the columns
+        that closed: (rgba uint8 [columns, P, 4] or None, records OVERVIEW_PCT_DTYPE [columns, pairs, P] or None, values float32 [nq,
+        columns, pairs, P] or None, timing dict)."""
+        P, pairs = self.cfg.axis_points, self.cfg.num_pairs
+        qa, qp, nq = _quantiles(q)
+        return self._feed_overview("_pct", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_records, (pairs, P), OVERVIEW_PCT_DTYPE),
+                                                                     (want_values, (pairs, P), np.float32, max(nq, 1))], (qp, nq))
 
     def feed_overview_power_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, power, levels, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); rgba / power / levels: numpy arrays, host torch tensors or None"""
@@ -2521,22 +2656,35 @@ def band_colours(records: np.ndarray, channel: int, band_colours, key_rgba8, fre
     return out
 
 
-def _overview_pcm(call: str, cfg, pcm, fmt: int, src_channels: int, k: int, channel_map, nsamples, outputs, front=()):
-    """sgz_spectrogram_overview<call>_pcm.  outputs(c): (wanted, the shape of one column, dtype) each, from the config; front: what the C call
-    takes between nsamples and k -> (status, every output's columns or None where not wanted, timing dict)"""
+def _overview_out(cols: int, want, shape, dtype, planes=None):
+    """an overview output's buffer: [columns, *shape], or [planes, columns, *shape]; never an empty array (its pointer may be null)"""
+    if not want:
+        return None
+    return np.zeros((max(cols, 1), *shape) if planes is None else (planes, max(cols, 1), *shape), dtype)
+
+
+def _overview_cut(a, cols: int, want, shape, dtype, planes=None):
+    return None if a is None else a[:cols] if planes is None else a[:, :cols]
+
+
+def _overview_pcm(call: str, cfg, pcm, fmt: int, src_channels: int, k: int, channel_map, nsamples, outputs, front=(), mid=()):
+    """sgz_spectrogram_overview<call>_pcm.  outputs(c): (wanted, the shape of one column, dtype[, planes]) each, from the config; front: what
+    the C call takes between nsamples and k, mid: between k and its outputs -> (status, every output's columns or None where not wanted,
+    timing dict)"""
     c = _as_config(cfg)
     nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
     n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
     F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
     cols = -(-F // k) if k else 0
-    arrays = [np.zeros((max(cols, 1), *shape), dtype) if want else None for want, shape, dtype in outputs(c)]     # (never an empty array: its pointer may be null)
+    outs = outputs(c)
+    arrays = [_overview_out(cols, *o) for o in outs]
     m, mp = _channel_map(channel_map)
     t = PcmTiming()
-    st = check(getattr(lib(), f"sgz_spectrogram_overview{call}_pcm")(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, *front, k,
+    st = check(getattr(lib(), f"sgz_spectrogram_overview{call}_pcm")(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, *front, k, *mid,
                                                                      *[_np_ptr(a) if a is not None else None for a in arrays], C.byref(t)))
     if st == SGZ_SKIPPED_FRAME:
         cols = 0
-    return (st, *[a[:cols] if a is not None else None for a in arrays], t.asdict())
+    return (st, *[_overview_cut(a, cols, *o) for a, o in zip(arrays, outs)], t.asdict())
 
 
 def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
@@ -2554,6 +2702,17 @@ def overview_stats_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_ma
     return _overview_pcm("_stats", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
                          lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_stats, (c.num_pairs, c.axis_points), OVERVIEW_STAT_DTYPE),
                                     (want_means, (c.num_pairs, c.axis_points), np.float32)])
+
+
+def overview_pct_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, q=0.5, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
+                     want_records: bool = True, want_values: bool = False):
+    """One-shot percentile overview of an interleaved PCM buffer (sgz_spectrogram_overview_pct_pcm): (status, rgba or None, records
+    OVERVIEW_PCT_DTYPE or None, values float32 [nq, columns, pairs, P] or None, timing dict); SGZ_SKIPPED_FRAME and empty outputs for fewer
+    samples than a window"""
+    qa, qp, nq = _quantiles(q)
+    return _overview_pcm("_pct", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
+                         lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_records, (c.num_pairs, c.axis_points), OVERVIEW_PCT_DTYPE),
+                                    (want_values, (c.num_pairs, c.axis_points), np.float32, max(nq, 1))], mid=(qp, nq))
 
 
 def overview_power_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,

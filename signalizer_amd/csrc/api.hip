@@ -1157,6 +1157,19 @@ sgz_status sgz::runOverviewStatsSlabs(sgz_plan *plan, const float *d_planar, siz
                                                                 at(d_stats, column * p.C * p.P), at(d_means, column * p.C * p.P), s);
                              });
 }
+sgz_status sgz::runOverviewPctSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k,
+                                    uint32_t held, int flush, const double *q, uint32_t nq, sgz_overview_pct_record *d_carry, float *d_state,
+                                    uint8_t *d_rgba, sgz_overview_pct_record *d_records, const PctPlanes &planes, hipStream_t s, const SlabTrack *track)
+{
+    Plan &p = plan->impl;
+    return overviewLineSlabs(plan, d_planar, channel_stride, nsamples, frames, k, held, flush, d_state, s, track,
+                             [&](const float *d_lines, size_t nf, uint32_t heldIn, int flushNow, size_t column) {
+                                 PctPlanes now{};
+                                 for (uint32_t j = 0; j < nq; ++j) now.p[j] = at(planes.p[j], column * p.C * p.P);
+                                 return runOverviewPctColumns(p, d_lines, nf, k, heldIn, flushNow, 0, q, nq, d_carry, at(d_rgba, column * p.P * 4),
+                                                              at(d_records, column * p.C * p.P), now, s);
+                             });
+}
 sgz_status sgz::powerOverviewSupported(const Plan &p)
 {
     if (isResonator(p)) return fail(SGZ_EUNSUPPORTED, "the power overview reduces transform magnitudes: RSNT plans are not supported");
@@ -1403,6 +1416,48 @@ sgz_status sgz_overview_stats_view_host(sgz_plan *plan, const sgz_overview_stat_
     const HostOut outs[] = {rgbaOut(p, rgba_out), recordsOut(p, kOvStats, stats_out, perColumn), valuesOut(p, kOvStats, means_out, perColumn)};
     return overviewHostView(plan, kOvStats, stats, perColumn, x0, x1, size_t(cols), outs, timing, [&](const sgz_overview_stat_record *d_in, size_t m, hipStream_t s) {
         return runOverviewStatsView(p, d_in, m, size_t(cols), 0, outs[0].dev<uint8_t>(), outs[1].dev<sgz_overview_stat_record>(), outs[2].dev<float>(), s);
+    });
+}
+
+// The percentile overview's render (sgz.h, "The percentile overview"; overview_pct.hip): the mean overview's calls with the quantiles in front
+// of the outputs and nq value planes [nq][columns][pairs][P] in the means' place.
+sgz_status sgz_spectrogram_overview_pct_device(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, uint32_t k,
+                                               const double *q, uint32_t nq, uint8_t *d_rgba, sgz_overview_pct_record *d_records, float *d_values,
+                                               float *d_state, void *stream)
+{
+    if (!plan || !d_planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!validPctQuantiles(q, nq)) return fail(SGZ_EINVAL, "overview pct: 1 .. 8 quantiles, each in [0, 1]");
+    if (!d_rgba && !d_records && !d_values) return fail(SGZ_EINVAL, "overview pct: an image, the records, the values or any of them");
+    if (reinterpret_cast<uintptr_t>(d_records) % 16) return fail(SGZ_EINVAL, "overview pct: d_records is aligned to 16 bytes");
+    sgz_status st = checkReady(plan);
+    if (st != SGZ_OK) return st;
+    Plan &p = plan->impl;
+    const long frames = planFrames(p, nsamples);
+    if (frames <= 0) return SGZ_SKIPPED_FRAME;
+    sgz_overview_pct_record *d_carry = nullptr;
+    if ((st = planCarry(p, kOvPct, size_t(p.C) * p.P, &d_carry)) != SGZ_OK) return st;
+    const size_t columns = (size_t(frames) + k - 1) / k;
+    return runOverviewPctSlabs(plan, d_planar, channel_stride, nsamples, frames, k, 0, 1, q, nq, d_carry, d_state, d_rgba, d_records,
+                               pctPlanes(d_values, 0, columns * p.C * p.P, nq), reinterpret_cast<hipStream_t>(stream));
+}
+
+sgz_status sgz_spectrogram_overview_pct_host(sgz_plan *plan, const float *const *planar, uint32_t num_channels, size_t nsamples, uint32_t k,
+                                             const double *q, uint32_t nq, uint8_t *rgba_out, sgz_overview_pct_record *records_out, float *values_out,
+                                             sgz_timing *timing)
+{
+    if (!plan || !planar) return fail(SGZ_EINVAL, "null argument");
+    if (k == 0) return fail(SGZ_EINVAL, "overview: k >= 1 frames per column");
+    if (!validPctQuantiles(q, nq)) return fail(SGZ_EINVAL, "overview pct: 1 .. 8 quantiles, each in [0, 1]");
+    if (!rgba_out && !records_out && !values_out) return fail(SGZ_EINVAL, "overview pct: an image, the records, the values or any of them");
+    Plan &p = plan->impl;
+    if (sgz_status st = checkHostChannels(p, planar, num_channels); st != SGZ_OK) return st;
+    const size_t perColumn = size_t(p.C) * p.P;
+    // (the planes lie `columns` columns apart: nq * perColumn values a column, copied back as one block)
+    const HostOut outs[] = {rgbaOut(p, rgba_out), recordsOut(p, kOvPct, records_out, perColumn), valuesOut(p, kOvPct, values_out, nq * perColumn)};
+    return overviewHostRender(plan, planar, num_channels, nsamples, k, outs, timing, [&](const float *d_audio, size_t stride, hipStream_t s) {
+        return sgz_spectrogram_overview_pct_device(plan, d_audio, stride, nsamples, k, q, nq, outs[0].dev<uint8_t>(), outs[1].dev<sgz_overview_pct_record>(),
+                                                   outs[2].dev<float>(), nullptr, s);
     });
 }
 

@@ -209,7 +209,11 @@ constexpr size_t kPcmMaxChunk = size_t(1) << 26;
 // OvPower sgz_overview_power_record [columns][C][sides][P] and OvLevels float [columns][C][sides][P] the power feed's, beside its OvImage.
 // OvCross sgz_overview_cross_record [columns][C][bands] the cross feed's.
 // OvFlux sgz_overview_flux_record [columns][C][sides] the flux feed's.
-enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutOvCross, kOutOvFlux, kOutWave, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kOutRun, kPcmOuts };
+// OvPct sgz_overview_pct_record [columns][C][P] and OvPctValues + j, float [columns][C][P], value plane j of the percentile feed's, beside its
+// OvImage: a plane is a block of its own, because its columns go to a part of the caller's buffer of their own.
+constexpr int kPcmPctPlanes = SGZ_OVERVIEW_PCT_MAX_QUANTILES;
+enum PcmOutKind { kOutImage, kOutLines, kOutOvImage, kOutOvPeaks, kOutOvStats, kOutOvMeans, kOutOvPower, kOutOvLevels, kOutOvCross, kOutOvFlux, kOutOvPct,
+                  kOutOvPctValues, kOutOvPctValuesEnd = kOutOvPctValues + kPcmPctPlanes, kOutWave = kOutOvPctValuesEnd, kOutTrack, kOutLevel, kOutTruePeak, kOutLoudness, kOutField, kOutBand, kOutHist, kOutRun, kPcmOuts };
 
 // One output of a slot: a device block, its pinned twin, and the host's part of a read-back -- the copy out of the twin that the drain
 // performs when the caller's memory is pageable.  Capacities in bytes.  The image's device block is made at create, every other block on
@@ -324,7 +328,7 @@ struct PcmLane {
 // how a refusal names an open column's kind (plan.hpp OverviewKind), and the feed that flushes it
 static const struct { const char *word, *call; } kPcmOvKindText[kOverviewKinds] = {
     {"peak-hold", "sgz_pcm_stream_feed_overview"},       {"mean", "sgz_pcm_stream_feed_overview_stats"}, {"power", "sgz_pcm_stream_feed_overview_power"},
-    {"cross", "sgz_pcm_stream_feed_overview_cross"},     {"flux", "sgz_pcm_stream_feed_overview_flux"},
+    {"cross", "sgz_pcm_stream_feed_overview_cross"},     {"flux", "sgz_pcm_stream_feed_overview_flux"}, {"percentile", "sgz_pcm_stream_feed_overview_pct"},
 };
 
 struct sgz_pcm_stream {
@@ -342,7 +346,8 @@ struct sgz_pcm_stream {
     // the overview inside the stream: the open column's frame count, its k and its kind (meaningful while ovOpen > 0), and every kind's carry,
     // made on first use: the peak hold's V [pairs][P], the mean overview's records [pairs][P] (sgz.h, "The mean overview"), the power overview's
     // [pairs][sides][P] ("The power overview"), the cross overview's [pairs][bands], by the band table of the stream's plan and made with it ("The
-    // cross overview"), the flux overview's [pairs][sides] ("The flux overview")
+    // cross overview"), the flux overview's [pairs][sides] ("The flux overview"), the percentile overview's records [pairs][P] ("The percentile
+    // overview")
     uint64_t ovOpen = 0; uint32_t ovK = 0;
     OverviewKind ovKind = kOvPeaks;
     void *d_ovCarry[kOverviewKinds] = {};
@@ -692,19 +697,21 @@ struct PcmFramesPart {
 // The overview feeds' part, of any kind: frames slab by slab into the columns they close, the open column in the stream's carry of the kind.
 // out[]: the outputs the call has, in the order the kind's hook takes them -- the slot's block, the bytes of one column, the caller's buffer
 // (null: not asked for).  firstUse[]: the device blocks the kind makes on its first feed (the cross carry is made with the band table).
-// run(s, sl, k, d_out, planar, total, frames, flush): frames > 0, the kind's slabs, on the compute stream; frames == 0, the Columns call that
+// run(part, s, sl, k, d_out, planar, total, frames, flush): frames > 0, the kind's slabs, on the compute stream; frames == 0, the Columns call that
 // flushes the open column alone.  d_out[i]: out[i]'s block in the slot, null where the caller asked for none or no column closes in this feed.
 // The power, cross and flux hooks have no K_B: the stream's decay state is neither read nor advanced, and there are no line results for a track
 // lane to search (their feeds refuse one)
 struct PcmOverviewPart {
-    using Run = sgz_status (*)(sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d_out[3], const float *planar, size_t total, uint64_t frames, int flush);
+    static constexpr int kMostOuts = 2 + kPcmPctPlanes;          // the percentile feed's: the image, the records, the value planes
+    using Run = sgz_status (*)(const PcmOverviewPart &part, sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d_out[kMostOuts], const float *planar, size_t total, uint64_t frames, int flush);
     OverviewKind kind;
     uint32_t k; int flush;
     Run run;
     uint64_t need = 0;                                            // the columns the whole feed yields
-    struct Out { PcmOutKind slot; size_t unit; void *host; bool pinned; } out[3] = {};
+    struct Out { PcmOutKind slot; size_t unit; void *host; bool pinned; } out[kMostOuts] = {};
     int outs = 0;
     struct { void **block; size_t bytes; } firstUse[2] = {};
+    const double *q = nullptr; uint32_t nq = 0;                   // the percentile feed's quantiles
 
     void add(PcmOutKind slot, size_t unit, void *host) { out[outs++] = {slot, unit, host, false}; }
     bool fluxPiece() const { return kind == kOvFlux; }
@@ -725,10 +732,10 @@ struct PcmOverviewPart {
         const int pieceFlush = flush && last;
         const uint64_t t = s.ovOpen + frames;
         *units = t / k + ((pieceFlush && t % k) ? 1u : 0u);
-        void *d_out[3] = {};
+        void *d_out[kMostOuts] = {};
         for (int i = 0; i < outs; ++i) d_out[i] = (out[i].host && need) ? sl.out[out[i].slot].dev : nullptr;
         if (frames || *units)                                      // (no frame arrives: the open column is flushed, or nothing happens)
-            if (sgz_status st = run(s, sl, k, d_out, planar, total, frames, pieceFlush); st != SGZ_OK) return st;
+            if (sgz_status st = run(*this, s, sl, k, d_out, planar, total, frames, pieceFlush); st != SGZ_OK) return st;
         s.ovOpen = pieceFlush ? 0 : t % k;
         s.ovK = k;
         s.ovKind = kind;
@@ -744,7 +751,7 @@ struct PcmOverviewPart {
 };
 
 // the kinds' hooks.  The peak hold's and the mean overview's slabs render line results, which the track lane, armed, searches
-static sgz_status pcmPeaksRun(sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d[3], const float *planar, size_t total, uint64_t frames, int flush)
+static sgz_status pcmPeaksRun(const PcmOverviewPart &, sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d[], const float *planar, size_t total, uint64_t frames, int flush)
 {
     float *carry = static_cast<float *>(s.d_ovCarry[kOvPeaks]);
     uint8_t *d_rgba = static_cast<uint8_t *>(d[0]);
@@ -754,7 +761,7 @@ static sgz_status pcmPeaksRun(sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *
     return runOverviewSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), flush, carry, s.d_state, d_rgba, d_peaks, s.compute,
                             s.track.armed() ? &track : nullptr);
 }
-static sgz_status pcmStatsRun(sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d[3], const float *planar, size_t total, uint64_t frames, int flush)
+static sgz_status pcmStatsRun(const PcmOverviewPart &, sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d[], const float *planar, size_t total, uint64_t frames, int flush)
 {
     using Record = sgz_overview_stat_record;
     Record *carry = static_cast<Record *>(s.d_ovCarry[kOvStats]), *d_stats = static_cast<Record *>(d[1]);
@@ -765,7 +772,7 @@ static sgz_status pcmStatsRun(sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *
     return runOverviewStatsSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), flush, carry, s.d_state, d_rgba, d_stats, d_means,
                                  s.compute, s.track.armed() ? &track : nullptr);
 }
-static sgz_status pcmPowerRun(sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[3], const float *planar, size_t, uint64_t frames, int flush)
+static sgz_status pcmPowerRun(const PcmOverviewPart &, sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[], const float *planar, size_t, uint64_t frames, int flush)
 {
     using Record = sgz_overview_power_record;
     Record *carry = static_cast<Record *>(s.d_ovCarry[kOvPower]), *d_power = static_cast<Record *>(d[1]);
@@ -774,15 +781,28 @@ static sgz_status pcmPowerRun(sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *co
     if (!frames) return runOverviewPowerColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, carry, d_rgba, d_power, d_levels, s.compute);
     return runOverviewPowerSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), flush, carry, d_rgba, d_power, d_levels, s.compute);
 }
-static sgz_status pcmCrossRun(sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[3], const float *planar, size_t, uint64_t frames, int flush)
+static sgz_status pcmCrossRun(const PcmOverviewPart &, sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[], const float *planar, size_t, uint64_t frames, int flush)
 {
     using Record = sgz_overview_cross_record;
     Record *carry = static_cast<Record *>(s.d_ovCarry[kOvCross]), *d_cross = static_cast<Record *>(d[0]);
     if (!frames) return runOverviewCrossColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, carry, d_cross, s.compute);
     return runOverviewCrossSlabs(s.plan, planar, s.stride, long(frames), k, uint32_t(s.ovOpen), flush, carry, d_cross, s.compute);
 }
+// (d[2 + j]: value plane j's block; the quantiles are the feed's)
+static sgz_status pcmPctRun(const PcmOverviewPart &part, sgz_pcm_stream &s, PcmSlot &sl, uint32_t k, void *const d[], const float *planar, size_t total, uint64_t frames, int flush)
+{
+    using Record = sgz_overview_pct_record;
+    Record *carry = static_cast<Record *>(s.d_ovCarry[kOvPct]), *d_records = static_cast<Record *>(d[1]);
+    uint8_t *d_rgba = static_cast<uint8_t *>(d[0]);
+    PctPlanes planes{};
+    for (uint32_t j = 0; j < part.nq; ++j) planes.p[j] = static_cast<float *>(d[2 + j]);
+    if (!frames) return runOverviewPctColumns(s.plan->impl, nullptr, 0, k, uint32_t(s.ovOpen), 1, 0, part.q, part.nq, carry, d_rgba, d_records, planes, s.compute);
+    const SlabTrack track{s.trGraph, s.trFraction, sl.out[kOutTrack].as<sgz_line_peak>()};
+    return runOverviewPctSlabs(s.plan, planar, s.stride, total, long(frames), k, uint32_t(s.ovOpen), flush, part.q, part.nq, carry, s.d_state, d_rgba, d_records,
+                               planes, s.compute, s.track.armed() ? &track : nullptr);
+}
 // (the previous frame and the frame index are the stream's: pcmFeed moves both on behind every piece)
-static sgz_status pcmFluxRun(sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[3], const float *planar, size_t, uint64_t frames, int flush)
+static sgz_status pcmFluxRun(const PcmOverviewPart &, sgz_pcm_stream &s, PcmSlot &, uint32_t k, void *const d[], const float *planar, size_t, uint64_t frames, int flush)
 {
     using Record = sgz_overview_flux_record;
     Record *carry = static_cast<Record *>(s.d_ovCarry[kOvFlux]), *d_flux = static_cast<Record *>(d[0]);
@@ -834,7 +854,7 @@ static bool pcmOverviewNeed(const sgz_pcm_stream *s, size_t nsamples, uint32_t k
     return true;
 }
 
-// What the five overview feeds share, in the order every one of them refuses: the stream, the samples, k, then own() -- the call's checks of
+// What the six overview feeds share, in the order every one of them refuses: the stream, the samples, k, then own() -- the call's checks of
 // its outputs and of the plan, which also fills part.out[] and part.firstUse[] --, a column of another kind, another k, the capacity, a missing
 // output the feed would write (text.nullOut; null: the call has refused a call without outputs before), the lanes.  The texts that name the call
 // are the call's own
@@ -860,7 +880,7 @@ static sgz_status pcmOverviewFeed(sgz_pcm_stream *s, const void *pcm, size_t nsa
     return pcmFeed(*s, pcm, nsamples, part.flush && s->ovOpen, part, columns_out, timing, t0);
 }
 
-// ... and the five one-shots: the null arguments, k, own() -- the call's other refusals --, and the stream of pcmOneShot around feed(s, columns)
+// ... and the six one-shots: the null arguments, k, own() -- the call's other refusals --, and the stream of pcmOneShot around feed(s, columns)
 template <typename Own, typename Feed>
 static sgz_status pcmOverviewOneShot(bool nullArgument, const sgz_spectrum_config *cfg, uint32_t format, uint32_t src_channels, const uint32_t *channel_map,
                                      size_t nsamples, uint32_t k, sgz_pcm_timing *timing, Own own, Feed feed)
@@ -1069,6 +1089,41 @@ sgz_status sgz_spectrogram_overview_stats_pcm(const sgz_spectrum_config *cfg, co
     return pcmOverviewOneShot(!cfg || !pcm, cfg, format, src_channels, channel_map, nsamples, k, timing,
                               [&] { return (!rgba_out && !stats_out && !means_out) ? fail(SGZ_EINVAL, "overview stats: an image, the records, the means or any of them") : SGZ_OK; },
                               [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_stats(s, pcm, nsamples, k, 1, rgba_out, stats_out, means_out, columns, &columns, timing); });
+}
+
+// ---- the percentile overview inside the stream (sgz.h, "The percentile overview") ----------------------------------------------------------------
+sgz_status sgz_pcm_stream_feed_overview_pct(sgz_pcm_stream *s, const void *pcm, size_t nsamples, uint32_t k, int flush, const double *q, uint32_t nq,
+                                            uint8_t *rgba_out, sgz_overview_pct_record *records_out, float *values_out, uint64_t capacity_columns,
+                                            uint64_t *columns_out, sgz_pcm_timing *timing)
+{
+    static const PcmOvTexts text = {"sgz_pcm_stream_feed_overview_pct: null pcm", "sgz_pcm_stream_feed_overview_pct: k differs from the open column's -- flush or reset first",
+                                    "sgz_pcm_stream_feed_overview_pct: capacity_columns below what this feed yields (see *columns_out)", nullptr};
+    PcmOverviewPart part{kOvPct, k, flush, pcmPctRun};
+    return pcmOverviewFeed(s, pcm, nsamples, text, part, capacity_columns, columns_out, timing, [&]() -> sgz_status {
+        if (!validPctQuantiles(q, nq)) return fail(SGZ_EINVAL, "overview pct: 1 .. 8 quantiles, each in [0, 1]");
+        if (!rgba_out && !records_out && !values_out) return fail(SGZ_EINVAL, "overview pct: an image, the records, the values or any of them");
+        if (reinterpret_cast<uintptr_t>(records_out) % alignof(sgz_overview_pct_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_feed_overview_pct: records_out is not aligned to 4 bytes");
+        const size_t records = pcmPeaksFloats(*s, 1);                // one per float of the peaks
+        part.q = q; part.nq = nq;
+        part.add(kOutOvImage, pcmImageBytes(*s, 1), rgba_out);
+        part.add(kOutOvPct, records * sizeof(sgz_overview_pct_record), records_out);
+        for (uint32_t j = 0; j < nq; ++j)                            // plane j of the caller's buffer: capacity_columns columns behind plane j - 1
+            part.add(PcmOutKind(kOutOvPctValues + j), records * sizeof(float), values_out ? values_out + size_t(j) * size_t(capacity_columns) * records : nullptr);
+        part.firstUse[0] = {&s->d_ovCarry[kOvPct], records * sizeof(sgz_overview_pct_record)};
+        return SGZ_OK;
+    });
+}
+
+sgz_status sgz_spectrogram_overview_pct_pcm(const sgz_spectrum_config *cfg, const void *pcm, uint32_t format, uint32_t src_channels,
+                                            const uint32_t *channel_map, size_t nsamples, uint32_t k, const double *q, uint32_t nq, uint8_t *rgba_out,
+                                            sgz_overview_pct_record *records_out, float *values_out, sgz_pcm_timing *timing)
+{
+    return pcmOverviewOneShot(!cfg || !pcm, cfg, format, src_channels, channel_map, nsamples, k, timing,
+                              [&]() -> sgz_status {
+                                  if (!validPctQuantiles(q, nq)) return fail(SGZ_EINVAL, "overview pct: 1 .. 8 quantiles, each in [0, 1]");
+                                  return (!rgba_out && !records_out && !values_out) ? fail(SGZ_EINVAL, "overview pct: an image, the records, the values or any of them") : SGZ_OK;
+                              },
+                              [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_pct(s, pcm, nsamples, k, 1, q, nq, rgba_out, records_out, values_out, columns, &columns, timing); });
 }
 
 // ---- the power overview inside the stream (sgz.h, "The power overview") --------------------------------------------------------------------------

@@ -56,9 +56,9 @@ struct DeviceScalars {
     float ratios[SGZ_NUM_SPEC_COLOURS + 1];   // normalizedSpecRatios, Spectrum.cpp:226-246
 };
 
-// The overview kinds (sgz.h: the peak hold, "The mean overview", "The power overview", "The cross overview", "The flux overview"), in the order
-// sgz_pcm_stream names an open column's kind
-enum OverviewKind { kOvPeaks, kOvStats, kOvPower, kOvCross, kOvFlux, kOverviewKinds };
+// The overview kinds (sgz.h: the peak hold, "The mean overview", "The power overview", "The cross overview", "The flux overview", "The
+// percentile overview"), in the order sgz_pcm_stream names an open column's kind
+enum OverviewKind { kOvPeaks, kOvStats, kOvPower, kOvCross, kOvFlux, kOvPct, kOverviewKinds };
 // A kind's plan scratch: the open column of the render forms (peaks [pairs][P]; records [pairs][P], [pairs][sides][P], [pairs][bands],
 // [pairs][sides]) and the snapshot the reduction reads while it writes the carry, the partial results of the sliced forms
 // [slices][columns][...], the host forms' device copies of the records (the peak hold: the peaks) and of the values (means, levels), and the

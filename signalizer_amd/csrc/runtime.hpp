@@ -151,6 +151,24 @@ sgz_status runOverviewFluxColumns(Plan &p, const float *d_mapped, size_t frames,
 sgz_status runOverviewFluxSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, long frames, uint32_t k, uint32_t held, int flush,
                                 uint64_t firstFrame, float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry, sgz_overview_flux_record *d_flux,
                                 hipStream_t stream);
+// the percentile overview (overview_pct.hip): the mean overview's twin on sgz_overview_pct_record, with nq value planes as the third output.
+// PctPlanes: where the call's first column of every plane goes (all null: no values) -- the planes of a render lie a whole render's columns
+// apart, those of a stream's slot in blocks of their own; the other arguments are sgz_stage_overview_pct's, checked by the caller
+struct PctPlanes { float *p[SGZ_OVERVIEW_PCT_MAX_QUANTILES]; };
+inline PctPlanes pctPlanes(float *d_values, size_t offset, size_t planeStride, uint32_t nq)
+{
+    PctPlanes planes{};
+    for (uint32_t j = 0; d_values && j < nq; ++j) planes.p[j] = d_values + size_t(j) * planeStride + offset;
+    return planes;
+}
+bool validPctQuantiles(const double *q, uint32_t nq);              // a host pointer to 1 .. 8 values in [0, 1]
+sgz_status runOverviewPctColumns(Plan &p, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices, const double *q,
+                                 uint32_t nq, sgz_overview_pct_record *d_carry, uint8_t *d_rgba, sgz_overview_pct_record *d_records,
+                                 const PctPlanes &planes, hipStream_t stream);
+// (planes: the render's first column of every plane; the slabs move on in each)
+sgz_status runOverviewPctSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
+                               int flush, const double *q, uint32_t nq, sgz_overview_pct_record *d_carry, float *d_state, uint8_t *d_rgba,
+                               sgz_overview_pct_record *d_records, const PctPlanes &planes, hipStream_t stream, const SlabTrack *track = nullptr);
 // the column lanes' reductions (wave, level, true-peak, loudness, stereo-field, band): column_lanes.hpp
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
