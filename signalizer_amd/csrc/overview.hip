@@ -12,6 +12,8 @@
 //   overviewEmitKernel      scratch; then the fold over the slices and the carry, the colour, the store -- a launch of its own behind it on
 //                           the stream (no hand-off between workgroups inside a launch).
 // The view of kept peaks (overviewViewKernel, overviewViewSliceKernel, overviewViewEmitKernel; further down) is the same reduction on V itself.
+// From overview_kinds.hpp: the step of a call, the column / view / slice bounds, a thread's cell, the frames' batched fold, and the launch
+// front of both forms (refusal, carry snapshot, slice choice, launches).  The kernel bodies, over keys, are this file's own (why: that header).
 // Nothing is waited for; scratch grows on demand (only growth synchronises); everything runs on the caller's stream.
 #include <hip/hip_runtime.h>
 
@@ -23,13 +25,13 @@
 
 #pragma clang fp contract(off)
 
+#include "overview_kinds.hpp"   // behind the pragma: its templates are parsed without contraction
+
 using namespace sgz;
 
 namespace {
 
 constexpr int kOvThreads = 256;
-constexpr int kOvUnroll = 8;             // frames (or slices) whose loads are issued before the first compare
-constexpr uint32_t kOvMaxSlices = 64;
 
 struct OverviewParams {
     const float2 *lines;                 // [frames][C][G][P]
@@ -47,27 +49,30 @@ struct OverviewParams {
     DeviceScalars sc;
 };
 
-// frames [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnFrames(const OverviewParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.k) - long(prm.held);
-    b = a + long(prm.k);
-    a = a < 0 ? 0 : a;
-    b = b > prm.frames ? prm.frames : b;
-}
+// the peak hold's part in the frames' fold (overview_kinds.hpp, foldFrames): the accumulator is the greatest key; a NaN's key is 0, so the
+// fill of the last batch moves nothing
+struct PeakKey {
+    using Acc = uint32_t;
+    static __device__ __forceinline__ void accFrame(Acc &run, uint32_t bits) { run = max(run, orderKey(bits)); }
+    static __device__ __forceinline__ void accUnfill(Acc &, uint32_t) {}
+};
 
-// the greatest key of (pair, pixel) over frames [a, b): graph 0's row of every frame, independent loads first
+// the greatest key of (pair, pixel) over frames [a, b): graph 0's row of every frame
 __device__ __forceinline__ uint32_t framesKey(const OverviewParams &prm, long a, long b, uint32_t pair, uint32_t pixel)
 {
-    const size_t perFrame = size_t(prm.C) * G * prm.P;
-    const float2 *row = prm.lines + size_t(pair) * G * prm.P + pixel;
+    return foldFrames<PeakKey>(linesRow(prm.lines, prm.C, prm.P, pair, pixel), a, b);
+}
+
+// the greatest of a (column, pair, pixel)'s partial keys, `perSlice` apart, independent loads first
+__device__ __forceinline__ uint32_t slicesKey(const uint32_t *q, size_t perSlice, uint32_t slices)
+{
     uint32_t run = 0u;
-    for (long f = a; f < b; f += kOvUnroll) {
-        uint32_t bits[kOvUnroll];
+    for (uint32_t s = 0; s < slices; s += kOvUnroll) {
+        uint32_t key[kOvUnroll];
 #pragma unroll
-        for (int j = 0; j < kOvUnroll; ++j) bits[j] = f + j < b ? __float_as_uint(row[size_t(f + j) * perFrame].x) : 0xffffffffu;
+        for (int j = 0; j < kOvUnroll; ++j) key[j] = s + j < slices ? q[size_t(s + j) * perSlice] : 0u;
 #pragma unroll
-        for (int j = 0; j < kOvUnroll; ++j) run = max(run, orderKey(bits[j]));
+        for (int j = 0; j < kOvUnroll; ++j) run = max(run, key[j]);
     }
     return run;
 }
@@ -93,8 +98,9 @@ __device__ __forceinline__ void emitColumn(const OverviewParams &prm, long col, 
 __global__ void __launch_bounds__(kOvThreads)
 overviewColumnsKernel(const OverviewParams prm)
 {
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    long col;
+    uint32_t pixel;
+    threadCell<kOvThreads>(prm, col, pixel);
     if (pixel >= prm.P) return;
     long a, b;
     columnFrames(prm, col, a, b);
@@ -105,13 +111,13 @@ overviewColumnsKernel(const OverviewParams prm)
 __global__ void __launch_bounds__(kOvThreads)
 overviewSliceKernel(const OverviewParams prm)
 {
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    long col;
+    uint32_t pixel;
+    threadCell<kOvThreads>(prm, col, pixel);
     if (pixel >= prm.P) return;
-    long a, b;
+    long a, b, sa, sb;
     columnFrames(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(blockIdx.y) * per, sb = sa + per < b ? sa + per : b;
+    sliceRange(prm, a, b, b > a ? b - a : 0, sa, sb);
     for (uint32_t pair = 0; pair < prm.C; ++pair)
         prm.partial[((size_t(blockIdx.y) * size_t(prm.columns) + size_t(col)) * prm.C + pair) * prm.P + pixel] = framesKey(prm, sa, sb, pair, pixel);
 }
@@ -119,21 +125,13 @@ overviewSliceKernel(const OverviewParams prm)
 __global__ void __launch_bounds__(kOvThreads)
 overviewEmitKernel(const OverviewParams prm)
 {
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    long col;
+    uint32_t pixel;
+    threadCell<kOvThreads>(prm, col, pixel);
     if (pixel >= prm.P) return;
     const size_t perSlice = size_t(prm.columns) * prm.C * prm.P;
     emitColumn(prm, col, pixel, [&](uint32_t pair) {
-        const uint32_t *q = prm.partial + (size_t(col) * prm.C + pair) * prm.P + pixel;
-        uint32_t run = 0u;
-        for (uint32_t s = 0; s < prm.slices; s += kOvUnroll) {
-            uint32_t key[kOvUnroll];
-#pragma unroll
-            for (int j = 0; j < kOvUnroll; ++j) key[j] = s + j < prm.slices ? q[size_t(s + j) * perSlice] : 0u;
-#pragma unroll
-            for (int j = 0; j < kOvUnroll; ++j) run = max(run, key[j]);
-        }
-        return run;
+        return slicesKey(prm.partial + (size_t(col) * prm.C + pair) * prm.P + pixel, perSlice, prm.slices);
     });
 }
 
@@ -154,13 +152,6 @@ struct ViewParams {
     const float *colourTables;
     DeviceScalars sc;
 };
-
-// source columns [a, b) of output column `col`, relative to the range (m < 2^31 and col <= cols <= m: the products fit)
-__device__ __forceinline__ void viewColumns(const ViewParams &prm, long col, long &a, long &b)
-{
-    a = (col * prm.m + prm.cols - 1) / prm.cols;
-    b = ((col + 1) * prm.m + prm.cols - 1) / prm.cols;
-}
 
 // the greatest key of (pair, pixel) over source columns [a, b), independent loads first
 __device__ __forceinline__ uint32_t viewKey(const ViewParams &prm, long a, long b, uint32_t pair, uint32_t pixel)
@@ -193,8 +184,9 @@ __device__ __forceinline__ void emitViewColumn(const ViewParams &prm, long col, 
 __global__ void __launch_bounds__(kOvThreads)
 overviewViewKernel(const ViewParams prm)
 {
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    long col;
+    uint32_t pixel;
+    threadCell<kOvThreads>(prm, col, pixel);
     if (pixel >= prm.P) return;
     long a, b;
     viewColumns(prm, col, a, b);
@@ -205,13 +197,13 @@ overviewViewKernel(const ViewParams prm)
 __global__ void __launch_bounds__(kOvThreads)
 overviewViewSliceKernel(const ViewParams prm)
 {
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    long col;
+    uint32_t pixel;
+    threadCell<kOvThreads>(prm, col, pixel);
     if (pixel >= prm.P) return;
-    long a, b;
+    long a, b, sa, sb;
     viewColumns(prm, col, a, b);
-    const long per = (b - a + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(blockIdx.y) * per, sb = sa + per < b ? sa + per : b;
+    sliceRange(prm, a, b, b - a, sa, sb);
     for (uint32_t pair = 0; pair < prm.C; ++pair)
         prm.partial[((size_t(blockIdx.y) * size_t(prm.cols) + size_t(col)) * prm.C + pair) * prm.P + pixel] = viewKey(prm, sa, sb, pair, pixel);
 }
@@ -219,28 +211,19 @@ overviewViewSliceKernel(const ViewParams prm)
 __global__ void __launch_bounds__(kOvThreads)
 overviewViewEmitKernel(const ViewParams prm)
 {
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t pixel = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
+    long col;
+    uint32_t pixel;
+    threadCell<kOvThreads>(prm, col, pixel);
     if (pixel >= prm.P) return;
     const size_t perSlice = size_t(prm.cols) * prm.C * prm.P;
     emitViewColumn(prm, col, pixel, [&](uint32_t pair) {
-        const uint32_t *q = prm.partial + (size_t(col) * prm.C + pair) * prm.P + pixel;
-        uint32_t run = 0u;
-        for (uint32_t s = 0; s < prm.slices; s += kOvUnroll) {
-            uint32_t key[kOvUnroll];
-#pragma unroll
-            for (int j = 0; j < kOvUnroll; ++j) key[j] = s + j < prm.slices ? q[size_t(s + j) * perSlice] : 0u;
-#pragma unroll
-            for (int j = 0; j < kOvUnroll; ++j) run = max(run, key[j]);
-        }
-        return run;
+        return slicesKey(prm.partial + (size_t(col) * prm.C + pair) * prm.P + pixel, perSlice, prm.slices);
     });
 }
 
 }  // namespace
 
 namespace sgz {
-
 // what every overview call refuses before anything else happens (message in g_lastError)
 sgz_status checkOverviewStep(uint32_t k, uint64_t held, uint64_t frames)
 {
@@ -270,42 +253,14 @@ uint32_t overviewAutoSlices(long columns, uint32_t blocks, uint32_t k, size_t fr
 sgz_status runOverviewColumns(Plan &p, const float *d_lines, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices, float *d_carry,
                               uint8_t *d_rgba, float *d_peaks, hipStream_t stream)
 {
-    const uint64_t t = uint64_t(held) + frames;
-    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
-    const bool open = !flush && t % k != 0;
-    const uint64_t columns = closed + (open ? 1u : 0u);
-    if (frames == 0 && !(flush && held)) return SGZ_OK;          // nothing arrives and no column to flush
-    const uint32_t blocks = (p.P + kOvThreads - 1) / kOvThreads;
-    if (columns == 0 || blocks == 0) return SGZ_OK;
-    if (columns > 0x7fffffffull / blocks || frames > size_t(0x7fffffffffffffffll)) return fail(SGZ_EINVAL, "too many columns for one launch");
     OverviewParams prm{};
     prm.lines = reinterpret_cast<const float2 *>(d_lines);
-    prm.frames = long(frames); prm.columns = long(columns); prm.closed = long(closed);
-    prm.k = k; prm.held = held; prm.C = p.C; prm.P = p.P; prm.blocks = blocks;
-    prm.carryIn = d_carry; prm.carryOut = d_carry;
+    prm.C = p.C; prm.P = p.P;
     prm.rgba = reinterpret_cast<uchar4 *>(d_rgba); prm.peaks = d_peaks;
     prm.colourTables = p.d_colourTables; prm.sc = p.scalars;
-    if (held && open && columns > 1) {
-        // column 0's threads read the carry while the open column's threads write it: they read a snapshot
-        const size_t carryN = size_t(p.C) * p.P;
-        if (sgz_status st = ensureCap(&p.ov[kOvPeaks].d_carryCopy, &p.ov[kOvPeaks].carryCopyCap, carryN); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.ov[kOvPeaks].d_carryCopy, d_carry, carryN * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = p.ov[kOvPeaks].d_carryCopy;
-    }
-    prm.slices = slices ? slices : overviewAutoSlices(long(columns), blocks, k, frames, numCUs());
-    const dim3 grid(unsigned(columns * blocks));
-    if (prm.slices <= 1) {
-        hipLaunchKernelGGL(overviewColumnsKernel, grid, dim3(kOvThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = ensureCap(&p.ov[kOvPeaks].d_partial, &p.ov[kOvPeaks].partialCap, size_t(prm.slices) * size_t(columns) * p.C * p.P); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<uint32_t *>(p.ov[kOvPeaks].d_partial);
-    hipLaunchKernelGGL(overviewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(overviewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchOverviewColumns(p, kOvPeaks, prm, frames, k, held, flush, slices, d_carry, p.P, kOvThreads,
+                                 [&](uint64_t columns, uint32_t blocks) { return overviewAutoSlices(long(columns), blocks, k, frames, numCUs()); },
+                                 overviewColumnsKernel, overviewSliceKernel, overviewEmitKernel, stream);
 }
 
 // what every view call refuses about its range (message in g_lastError); *cols = min(out_columns, x1 - x0)
@@ -321,32 +276,14 @@ sgz_status checkViewRange(uint64_t n, uint64_t x0, uint64_t x1, uint32_t outColu
 // sgz_stage_overview_view behind its argument checks (the plan's tables are uploaded).  d_src [m][C][P]: the range's first source column.
 sgz_status runOverviewView(Plan &p, const float *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba, float *d_peaksOut, hipStream_t stream)
 {
-    const uint32_t blocks = (p.P + kOvThreads - 1) / kOvThreads;
-    if (cols == 0 || blocks == 0) return SGZ_OK;
-    if (cols > 0x7fffffffull / blocks) return fail(SGZ_EINVAL, "too many columns for one launch");
     ViewParams prm{};
-    prm.src = d_src; prm.m = long(m); prm.cols = long(cols);
-    prm.C = p.C; prm.P = p.P; prm.blocks = blocks;
+    prm.src = d_src;
+    prm.C = p.C; prm.P = p.P;
     prm.rgba = reinterpret_cast<uchar4 *>(d_rgba); prm.peaks = d_peaksOut;
     prm.colourTables = p.d_colourTables; prm.sc = p.scalars;
-    const uint32_t most = uint32_t((m + cols - 1) / cols);       // source columns of the longest output column
-    // the overview's rule at four workgroups per CU, and no slice shorter than one batch of kOvUnroll loads
-    prm.slices = slices ? slices : std::min(overviewAutoSlices(long(cols), blocks, most, m, 2 * numCUs()), std::max(1u, most / uint32_t(kOvUnroll)));
-    const dim3 grid(unsigned(cols * blocks));
-    if (prm.slices <= 1) {
-        hipLaunchKernelGGL(overviewViewKernel, grid, dim3(kOvThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = ensureCap(&p.ov[kOvPeaks].d_partial, &p.ov[kOvPeaks].partialCap, size_t(prm.slices) * cols * p.C * p.P); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<uint32_t *>(p.ov[kOvPeaks].d_partial);
-    hipLaunchKernelGGL(overviewViewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(overviewViewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchOverviewView(p, kOvPeaks, prm, m, cols, slices, p.P, kOvThreads, overviewViewKernel, overviewViewSliceKernel,
+                              overviewViewEmitKernel, stream);
 }
-
 }  // namespace sgz
 
 struct sgz_plan { Plan impl; };
@@ -377,11 +314,7 @@ extern "C" sgz_status sgz_stage_overview_view(sgz_plan *plan, const float *d_pea
     const size_t srcBytes = (x1 - x0) * column * sizeof(float);
     if (bytesOverlap(src, srcBytes, d_rgba, size_t(cols) * p.P * 4) || bytesOverlap(src, srcBytes, d_peaks_out, size_t(cols) * column * sizeof(float)))
         return fail(SGZ_EINVAL, "sgz_stage_overview_view: an output overlaps the source columns it is made from");
-    if (!p.uploaded) {                                           // the kernels read the plan's colour tables
-        std::string err;
-        const sgz_status st = uploadPlan(p, err);
-        if (st != SGZ_OK) return fail(st, err);
-    }
+    if (sgz_status st = uploaded(p); st != SGZ_OK) return st;
     return runOverviewView(p, src, x1 - x0, size_t(cols), slices, d_rgba, d_peaks_out, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -389,9 +322,8 @@ extern "C" sgz_status sgz_overview_step(uint32_t k, uint64_t held, uint64_t fram
 {
     if (!columns || !held_out) return fail(SGZ_EINVAL, "sgz_overview_step: results non-null");
     if (sgz_status st = checkOverviewStep(k, held, frames); st != SGZ_OK) return st;
-    const uint64_t t = held + frames;
-    *columns = t / k + ((flush && t % k) ? 1u : 0u);
-    *held_out = flush ? 0u : t % k;
+    *columns = overviewStepShape(k, held, frames, flush).closed;
+    *held_out = flush ? 0u : (held + frames) % k;
     return SGZ_OK;
 }
 
@@ -402,14 +334,10 @@ extern "C" sgz_status sgz_stage_overview(sgz_plan *plan, const float *d_lines, s
     if (sgz_status st = checkOverviewStep(k, held, frames); st != SGZ_OK) return st;
     if (slices > kOvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview: slices 0 (automatic) or 1 .. 64");
     if (!d_rgba && !d_peaks) return fail(SGZ_EINVAL, "sgz_stage_overview: an image, the peaks or both");
-    const uint64_t t = uint64_t(held) + frames;
-    if (!d_carry && (held || (!flush && t % k))) return fail(SGZ_EINVAL, "sgz_stage_overview: d_carry is read (held > 0) or written (frames stay open)");
-    if (frames == 0 && !(flush && held)) return SGZ_OK;
+    const OverviewStep sh = overviewStepShape(k, held, frames, flush);
+    if (!d_carry && (held || sh.open)) return fail(SGZ_EINVAL, "sgz_stage_overview: d_carry is read (held > 0) or written (frames stay open)");
+    if (!sh.launch) return SGZ_OK;
     Plan &p = plan->impl;
-    if (!p.uploaded) {                                           // the kernels read the plan's colour tables
-        std::string err;
-        const sgz_status st = uploadPlan(p, err);
-        if (st != SGZ_OK) return fail(st, err);
-    }
+    if (sgz_status st = uploaded(p); st != SGZ_OK) return st;
     return runOverviewColumns(p, d_lines, frames, k, held, flush, slices, d_carry, d_rgba, d_peaks, reinterpret_cast<hipStream_t>(stream));
 }

@@ -16,6 +16,8 @@
 // The band table is the plan's (sgz_plan_set_cross_edges): host-built tables name every bin's band, every tile's bands and every band's tiles.
 // Empty bands take no slot: the tables count the non-empty ones, so that a tile's 256 bins meet at most 256 of them.
 // Nothing is waited for; scratch grows on demand (only growth synchronises); everything runs on the caller's stream.
+// From overview_kinds.hpp: the step of a call, the column and slice bounds, the carry snapshot.  The launches and the host fold (band edges) are
+// this file's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +30,8 @@
 
 #pragma clang fp contract(off)
 
+#include "overview_kinds.hpp"   // behind the pragma: its templates are parsed without contraction
+
 using namespace sgz;
 
 namespace {
@@ -38,12 +42,10 @@ typedef __int128 i128;
 
 constexpr int kTile = 256;               // bins of a tile and threads of a workgroup
 constexpr int kUnroll = 4;               // frames whose loads are issued before the first product
-constexpr uint32_t kMaxSlices = 64;
 constexpr uint32_t kNoBand = 0xffffffffu;
 constexpr int kSlotWords = 18;           // 4 sums x 4 limbs, count, skipped
 constexpr double kQMost = 9223372036854774784.0;        // 2^63 - 2^10, the largest double below 2^63
 constexpr double kTwo64 = 18446744073709551616.0;
-constexpr size_t kRecordFloats = sizeof(Record) / sizeof(float);     // plan scratch is counted in floats (ensureCap)
 
 // ---- the definition, for the host and the device -------------------------------------------------------------------------------------------
 __host__ __device__ inline bool finiteBits(uint32_t bits) { return (bits & 0x7f800000u) != 0x7f800000u; }
@@ -145,15 +147,6 @@ struct CrossParams {
     Record *out;                         // [columns][C][B]
 };
 
-// frames [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnFrames(const CrossParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.k) - long(prm.held);
-    b = a + long(prm.k);
-    a = a < 0 ? 0 : a;
-    b = b > prm.frames ? prm.frames : b;
-}
-
 __device__ __forceinline__ uint64_t waveSum(uint64_t v)
 {
 #pragma unroll
@@ -175,10 +168,9 @@ overviewCrossTileKernel(const CrossParams prm)
     const uint32_t rank = admitted ? prm.binRank[bin] : kNoBand;
     for (uint32_t i = threadIdx.x; i < nRanks * kSlotWords; i += kTile) slots[i] = 0ull;
 
-    long a, b;
+    long a, b, sa, sb;
     columnFrames(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(blockIdx.y) * per, sb = sa + per < b ? sa + per : b;
+    sliceRange(prm, a, b, b > a ? b - a : 0, sa, sb);
     Acc acc;
     if (rank != kNoBand) {
         const size_t perFrame = size_t(prm.C) * (size_t(prm.N) + 1);
@@ -333,35 +325,26 @@ sgz_status crossOverviewSupported(const Plan &p)
 sgz_status runOverviewCrossColumns(Plan &p, const float *d_bins, size_t frames, uint32_t k, uint32_t held, int flush, uint32_t slices,
                                    sgz_overview_cross_record *d_carry, sgz_overview_cross_record *d_cross, hipStream_t stream)
 {
-    const uint64_t t = uint64_t(held) + frames;
-    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
-    const bool open = !flush && t % k != 0;
-    const uint64_t columns = closed + (open ? 1u : 0u);
-    if (frames == 0 && !(flush && held)) return SGZ_OK;          // nothing arrives and no column to flush
-    if (columns == 0) return SGZ_OK;
+    const OverviewStep sh = overviewStepShape(k, held, frames, flush);
+    const uint64_t columns = sh.columns;
+    if (!sh.launch || columns == 0) return SGZ_OK;
     const uint32_t B = p.crossBands, tiles = p.crossTiles;
     const uint64_t units = columns * p.C * tiles, records = columns * p.C * B;
     if (units > 0x7fffffffull || records > 0x7fffffffull * kTile || frames > size_t(0x7fffffffffffffffll))
         return fail(SGZ_EINVAL, "too many columns for one launch");
     CrossParams prm{};
     prm.bins = reinterpret_cast<const float2 *>(d_bins);
-    prm.frames = long(frames); prm.columns = long(columns); prm.closed = long(closed);
+    prm.frames = long(frames); prm.columns = long(columns); prm.closed = long(sh.closed);
     prm.k = k; prm.held = held; prm.C = p.C; prm.N = p.N; prm.B = B; prm.tiles = tiles; prm.pieces = p.crossPieces;
     prm.scale = crossScale(p.N);
     const uint32_t half = p.N / 2;
     prm.binRank = p.d_crossTables; prm.tileRankLo = prm.binRank + half; prm.tileRanks = prm.tileRankLo + tiles; prm.tilePieceBase = prm.tileRanks + tiles;
     prm.bandRank = prm.tilePieceBase + tiles; prm.bandTileLo = prm.bandRank + B; prm.bandTiles = prm.bandTileLo + B;
-    prm.carryIn = d_carry; prm.carryOut = d_carry; prm.out = d_cross;
-    if (held && open && columns > 1) {
-        // column 0's threads read the carry while the open column's threads write it: they read a snapshot
-        const size_t carryN = size_t(p.C) * B;
-        if (sgz_status st = ensureCap(&p.ov[kOvCross].d_carryCopy, &p.ov[kOvCross].carryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.ov[kOvCross].d_carryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = reinterpret_cast<const Record *>(p.ov[kOvCross].d_carryCopy);
-    }
+    prm.carryOut = d_carry; prm.out = d_cross;
+    if (sgz_status st = snapshotCarry<Record>(p, kOvCross, sh, held, d_carry, size_t(p.C) * B, stream, &prm.carryIn); st != SGZ_OK) return st;
     prm.slices = slices ? slices : overviewAutoSlices(long(columns), std::max(1u, p.C * tiles), k, frames, numCUs());
     if (frames > 0 && prm.pieces > 0) {
-        if (sgz_status st = ensureCap(&p.ov[kOvCross].d_partial, &p.ov[kOvCross].partialCap, size_t(prm.slices) * size_t(columns) * p.C * prm.pieces * kRecordFloats); st != SGZ_OK) return st;
+        if (sgz_status st = ensureCap(&p.ov[kOvCross].d_partial, &p.ov[kOvCross].partialCap, size_t(prm.slices) * size_t(columns) * p.C * prm.pieces * kRecordFloats<Record>); st != SGZ_OK) return st;
         prm.partial = reinterpret_cast<Record *>(p.ov[kOvCross].d_partial);
         hipLaunchKernelGGL(overviewCrossTileKernel, dim3(unsigned(units), prm.slices), dim3(kTile), 0, stream, prm);
         SGZ_HIP(hipGetLastError());
@@ -403,13 +386,12 @@ extern "C" sgz_status sgz_stage_overview_cross(sgz_plan *plan, const float *d_bi
     if (!plan || !d_bins) return fail(SGZ_EINVAL, "null argument");
     if (sgz_status st = crossOverviewSupported(plan->impl); st != SGZ_OK) return st;
     if (sgz_status st = checkOverviewStep(k, held, frames); st != SGZ_OK) return st;
-    if (slices > kMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview_cross: slices 0 (automatic) or 1 .. 64");
+    if (slices > kOvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview_cross: slices 0 (automatic) or 1 .. 64");
     if (!plan->impl.crossBands) return fail(SGZ_EINVAL, "sgz_stage_overview_cross: the plan has no band table (sgz_plan_set_cross_edges)");
-    const uint64_t t = uint64_t(held) + frames;
-    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
-    if (!d_cross && closed && (frames || (flush && held))) return fail(SGZ_EINVAL, "sgz_stage_overview_cross: d_cross is written (a column closes)");
-    if (!d_carry && (held || (!flush && t % k))) return fail(SGZ_EINVAL, "sgz_stage_overview_cross: d_carry is read (held > 0) or written (frames stay open)");
-    if (frames == 0 && !(flush && held)) return SGZ_OK;
+    const OverviewStep sh = overviewStepShape(k, held, frames, flush);
+    if (!d_cross && sh.closed && sh.launch) return fail(SGZ_EINVAL, "sgz_stage_overview_cross: d_cross is written (a column closes)");
+    if (!d_carry && (held || sh.open)) return fail(SGZ_EINVAL, "sgz_stage_overview_cross: d_carry is read (held > 0) or written (frames stay open)");
+    if (!sh.launch) return SGZ_OK;
     return runOverviewCrossColumns(plan->impl, d_bins, frames, k, held, flush, slices, d_carry, d_cross, reinterpret_cast<hipStream_t>(stream));
 }
 

@@ -16,6 +16,8 @@
 //   overviewFluxSliceKernel     few columns of many frames: slice s of a column's frames -> partial records [slices][columns][rows] in plan scratch;
 //   overviewFluxEmitKernel      behind it on the stream, one thread per (column, row): the fold over the slices and the carry.
 // Nothing is waited for; scratch grows on demand (only growth synchronises); everything runs on the caller's stream.
+// From overview_kinds.hpp: the step of a call, the column bounds, the carry snapshot and the host fold's frame.  The launches and the slice
+// range (its start is clamped) are this file's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +28,8 @@
 #include "runtime.hpp"
 
 #pragma clang fp contract(off)
+
+#include "overview_kinds.hpp"   // behind the pragma: its templates are parsed without contraction
 
 using namespace sgz;
 
@@ -47,7 +51,6 @@ constexpr uint32_t kLdsPixels = 12288;               // P <= 12288: the previous
 constexpr uint32_t kRunFrames = 32;                  // a run of whole columns has at most this many frames (one column when k is above it)
 constexpr uint64_t kWantGroups = 512;                // ... and is shortened while the launch would have fewer workgroups than this
 constexpr uint32_t kSliceFrames = 8;                 // an automatic slice keeps at least this many frames: each slice pays one halo fetch
-constexpr uint32_t kMaxSlices = 64;
 constexpr double kQuantum = 1073741824.0;            // 2^30 steps per unit of amplitude
 constexpr double kQMost = 17179869184.0;             // 2^34: the clamp, at |x| = 16
 constexpr double kTwo64 = 18446744073709551616.0;
@@ -109,15 +112,6 @@ struct FluxParams {
     Record *partial;                     // [slices][columns][R]
     Record *flux;                        // [columns][R]
 };
-
-// frames [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnFrames(const FluxParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.k) - long(prm.held);
-    b = a + long(prm.k);
-    a = a < 0 ? 0 : a;
-    b = b > prm.frames ? prm.frames : b;
-}
 
 // what becomes of a (column, row)'s accumulator: the carry into column 0, then a closed column's record or the open one's carry
 __device__ __forceinline__ void emitColumn(const FluxParams &prm, long col, uint32_t r, Acc acc)
@@ -388,8 +382,6 @@ overviewFluxEmitKernel(const FluxParams prm)
     emitColumn(prm, long(j / prm.R), uint32_t(j % prm.R), acc);
 }
 
-constexpr size_t kRecordFloats = sizeof(Record) / sizeof(float);     // plan scratch is counted in floats (ensureCap)
-
 void launchColumns(uint32_t P, dim3 grid, hipStream_t stream, const FluxParams &prm)
 {
     if (P <= kPass) hipLaunchKernelGGL(overviewFluxColumnsKernel<1>, grid, dim3(kThreads), 0, stream, prm);
@@ -416,35 +408,28 @@ namespace sgz {
 sgz_status runOverviewFluxColumns(Plan &p, const float *d_mapped, size_t frames, uint32_t k, uint32_t held, int flush, uint64_t firstFrame, uint32_t slices,
                                   float *d_prev, bool prevValid, sgz_overview_flux_record *d_carry, sgz_overview_flux_record *d_flux, hipStream_t stream)
 {
-    const uint64_t t = uint64_t(held) + frames;
-    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
-    const bool open = !flush && t % k != 0;
-    const uint64_t columns = closed + (open ? 1u : 0u);
-    if (frames == 0 && !(flush && held)) return SGZ_OK;          // nothing arrives and no column to flush
+    const OverviewStep sh = overviewStepShape(k, held, frames, flush);
+    const uint64_t columns = sh.columns;
+    if (!sh.launch) return SGZ_OK;
     const uint32_t R = p.C * uint32_t(p.sides);
     if (columns == 0 || R == 0) return SGZ_OK;
     if (columns > 0x7fffffffull / R || frames > size_t(0x7fffffffffffffffll)) return fail(SGZ_EINVAL, "too many columns for one launch");
     FluxParams prm{};
     prm.mapped = reinterpret_cast<const uint32_t *>(d_mapped);
-    prm.frames = long(frames); prm.columns = long(columns); prm.closed = long(closed);
+    prm.frames = long(frames); prm.columns = long(columns); prm.closed = long(sh.closed);
     prm.k = k; prm.held = held; prm.P = p.P; prm.R = R;
     prm.firstFrame = firstFrame;
     prm.prevIn = prevValid ? reinterpret_cast<const uint32_t *>(d_prev) : nullptr;
     prm.prevOut = frames ? reinterpret_cast<uint32_t *>(d_prev) : nullptr;
-    prm.carryIn = d_carry; prm.carryOut = d_carry; prm.flux = d_flux;
+    prm.carryOut = d_carry; prm.flux = d_flux;
     // a slice pays a halo fetch, so there are none by default unless each keeps kSliceFrames frames
     prm.slices = slices ? slices : std::max(1u, overviewAutoSlices(long(columns), R, k / kSliceFrames, frames, int(kWantGroups / 2)));
     // runs of whole columns: kRunFrames frames at the most, fewer while that leaves fewer than kWantGroups workgroups
     prm.G = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(kRunFrames / k, columns * R / kWantGroups)));
     const uint64_t groups = (columns + prm.G - 1) / prm.G;
-    if (held && open && columns > 1) {
-        // column 0's workgroup reads the carry while the open column's writes it: it reads a snapshot
-        if (sgz_status st = ensureCap(&p.ov[kOvFlux].d_carryCopy, &p.ov[kOvFlux].carryCopyCap, size_t(R) * kRecordFloats); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.ov[kOvFlux].d_carryCopy, d_carry, size_t(R) * sizeof(Record), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = reinterpret_cast<const Record *>(p.ov[kOvFlux].d_carryCopy);
-    }
+    if (sgz_status st = snapshotCarry<Record>(p, kOvFlux, sh, held, d_carry, R, stream, &prm.carryIn); st != SGZ_OK) return st;
     if (prm.prevIn && prm.prevOut && (prm.slices > 1 || groups > 1)) {
-        // ... and so for the previous frame, where frame 0's workgroup is not the last frame's (in one workgroup a pixel is read and written by one thread)
+        // the same snapshot for the previous frame, where frame 0's workgroup is not the last frame's (in one workgroup a pixel is read and written by one thread)
         if (sgz_status st = ensureCap(&p.d_ovfPrevCopy, &p.ovfPrevCopyCap, size_t(R) * p.P); st != SGZ_OK) return st;
         SGZ_HIP(hipMemcpyAsync(p.d_ovfPrevCopy, d_prev, size_t(R) * p.P * sizeof(float), hipMemcpyDeviceToDevice, stream));
         prm.prevIn = reinterpret_cast<const uint32_t *>(p.d_ovfPrevCopy);
@@ -454,7 +439,7 @@ sgz_status runOverviewFluxColumns(Plan &p, const float *d_mapped, size_t frames,
         SGZ_HIP(hipGetLastError());
         return SGZ_OK;
     }
-    if (sgz_status st = ensureCap(&p.ov[kOvFlux].d_partial, &p.ov[kOvFlux].partialCap, size_t(prm.slices) * size_t(columns) * R * kRecordFloats); st != SGZ_OK) return st;
+    if (sgz_status st = ensureCap(&p.ov[kOvFlux].d_partial, &p.ov[kOvFlux].partialCap, size_t(prm.slices) * size_t(columns) * R * kRecordFloats<Record>); st != SGZ_OK) return st;
     prm.partial = reinterpret_cast<Record *>(p.ov[kOvFlux].d_partial);
     launchSlices(p.P, dim3(unsigned(columns * R), prm.slices), stream, prm);
     SGZ_HIP(hipGetLastError());
@@ -472,15 +457,14 @@ extern "C" sgz_status sgz_stage_overview_flux(sgz_plan *plan, const float *d_map
 {
     if (!plan || !d_mapped) return fail(SGZ_EINVAL, "null argument");
     if (sgz_status st = checkOverviewStep(k, held, frames); st != SGZ_OK) return st;
-    if (slices > kMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview_flux: slices 0 (automatic) or 1 .. 64");
-    const uint64_t t = uint64_t(held) + frames;
-    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
-    if (!d_flux && closed) return fail(SGZ_EINVAL, "sgz_stage_overview_flux: d_flux receives the columns that close");
-    if (!d_carry && (held || (!flush && t % k))) return fail(SGZ_EINVAL, "sgz_stage_overview_flux: d_carry is read (held > 0) or written (frames stay open)");
+    if (slices > kOvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview_flux: slices 0 (automatic) or 1 .. 64");
+    const OverviewStep sh = overviewStepShape(k, held, frames, flush);
+    if (!d_flux && sh.closed) return fail(SGZ_EINVAL, "sgz_stage_overview_flux: d_flux receives the columns that close");
+    if (!d_carry && (held || sh.open)) return fail(SGZ_EINVAL, "sgz_stage_overview_flux: d_carry is read (held > 0) or written (frames stay open)");
     if ((reinterpret_cast<uintptr_t>(d_mapped) & 3u) || (reinterpret_cast<uintptr_t>(d_prev) & 3u) || (reinterpret_cast<uintptr_t>(d_carry) & 7u) ||
         (reinterpret_cast<uintptr_t>(d_flux) & 7u))
         return fail(SGZ_EINVAL, "sgz_stage_overview_flux: d_mapped and d_prev aligned to 4 bytes, d_carry and d_flux to 8");
-    if (frames == 0 && !(flush && held)) return SGZ_OK;
+    if (!sh.launch) return SGZ_OK;
     return runOverviewFluxColumns(plan->impl, d_mapped, frames, k, held, flush, first_frame, slices, d_prev, d_prev != nullptr, d_carry, d_flux,
                                   reinterpret_cast<hipStream_t>(stream));
 }
@@ -496,31 +480,21 @@ extern "C" sgz_status sgz_overview_flux_quantise(const float *x, size_t n, uint6
 extern "C" sgz_status sgz_overview_flux_fold(const sgz_overview_flux_record *in, size_t n, size_t width, size_t x0, size_t x1, uint32_t out_columns,
                                              sgz_overview_flux_record *out)
 {
-    if (!in || !out) return fail(SGZ_EINVAL, "sgz_overview_flux_fold: null argument");
-    if (width == 0) return fail(SGZ_EINVAL, "sgz_overview_flux_fold: width >= 1 records per column");
-    uint64_t cols = 0;
-    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
-    const uint64_t m = x1 - x0;
-    // two passes: nothing is written when any column's count overflows
-    for (int pass = 0; pass < 2; ++pass)
-        for (uint64_t b = 0; b < cols; ++b) {
-            const uint64_t ja = x0 + (b * m + cols - 1) / cols, jb = x0 + ((b + 1) * m + cols - 1) / cols;
-            for (size_t i = 0; i < width; ++i) {
-                HostAcc h;
-                for (uint64_t j = ja; j < jb; ++j) {
-                    const Record &r = in[j * width + i];
-                    h.acc.amp += wide128(r.amp); h.acc.m1 += wide128(r.mom1); h.acc.m2 += wide128(r.mom2); h.acc.flux += wide128(r.flux);
-                    accPeak(h.acc, r.flux_max, r.flux_at);
-                    h.count += r.count; h.nans += r.nans;
-                }
-                if (h.count > 0xffffffffull || h.nans > 0xffffffffull)
-                    return fail(SGZ_EINVAL, "sgz_overview_flux_fold: a folded column counts more than 2^32 - 1 frames");
-                if (pass == 0) continue;
-                h.acc.count = uint32_t(h.count); h.acc.nans = uint32_t(h.nans);
-                accRecord(h.acc, out[b * width + i]);
-            }
-        }
-    return SGZ_OK;
+    return foldKeptColumns<HostAcc>(
+        {"sgz_overview_flux_fold: null argument", "sgz_overview_flux_fold: width >= 1 records per column",
+         "sgz_overview_flux_fold: a folded column counts more than 2^32 - 1 frames"},
+        in, n, width, x0, x1, out_columns, out,
+        [](HostAcc &h, const Record &r) {
+            h.acc.amp += wide128(r.amp); h.acc.m1 += wide128(r.mom1); h.acc.m2 += wide128(r.mom2); h.acc.flux += wide128(r.flux);
+            accPeak(h.acc, r.flux_max, r.flux_at);
+            h.count += r.count; h.nans += r.nans;
+        },
+        [](const HostAcc &h) { return h.count <= 0xffffffffull && h.nans <= 0xffffffffull; },
+        [](const HostAcc &h, Record &o) {
+            Acc acc = h.acc;
+            acc.count = uint32_t(h.count); acc.nans = uint32_t(h.nans);
+            accRecord(acc, o);
+        });
 }
 
 extern "C" sgz_status sgz_overview_flux_readout(const sgz_overview_flux_record *in, size_t count, uint32_t pixels, double *mean_amplitude, double *centroid,

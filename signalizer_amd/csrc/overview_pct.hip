@@ -18,6 +18,8 @@
 //                              the table), the quantiles, the colour, the stores -- a launch of its own behind it on the stream.
 // A wave's lanes exchange table columns only in the run transfers; a __syncthreads() stands on either side of each (one wave: no s_barrier
 // is left of it, the LDS counter wait is).  Nothing is waited for on the host; scratch grows on demand; everything runs on the caller's stream.
+// From overview_kinds.hpp: the step of a call, the column and slice bounds, a workgroup's cells, the launch front (with this kind's slice rule,
+// pctAutoSlices, and its 64-thread workgroup) and the host fold's frame.  The kernel bodies are this file's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +31,8 @@
 #include "decay_body.hpp"
 
 #pragma clang fp contract(off)
+
+#include "overview_kinds.hpp"   // behind the pragma: its templates are parsed without contraction
 
 using namespace sgz;
 
@@ -44,7 +48,6 @@ using Record = sgz_overview_pct_record;
 constexpr int kPctThreads = 64;                          // one wave
 constexpr int kPctUnroll = 4;                            // frames whose loads are issued before the first increment, where a column is emitted
 constexpr int kPctSliceUnroll = 8;                       // ... and in the slice kernel (in the columns kernel 8 spill twelve scalar registers to lanes)
-constexpr uint32_t kPctMaxSlices = 64;
 constexpr int kPctBuckets = SGZ_OVERVIEW_PCT_BUCKETS;
 constexpr int kPctNans = kPctBuckets;                    // the table's word 66; word 67 is `reserved` and stays 0
 constexpr int kPctWords = sizeof(Record) / 4;            // 68
@@ -119,15 +122,6 @@ __device__ __forceinline__ void tabZero(uint32_t *tab, uint32_t lane)
 __device__ __forceinline__ void tabAdd(uint32_t *tab, uint32_t at, uint32_t v)
 {
     (void)__hip_atomic_fetch_add(tab + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // result unused: ds_add_u32
-}
-
-// frames [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnFrames(const PctParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.k) - long(prm.held);
-    b = a + long(prm.k);
-    a = a < 0 ? 0 : a;
-    b = b > prm.frames ? prm.frames : b;
 }
 
 // frames [a, b) of (pair, pixel) into the lane's table: graph 0's row of every frame, independent loads first (a and b are the wave's)
@@ -248,8 +242,10 @@ __global__ void __launch_bounds__(kPctThreads)
 overviewPctColumnsKernel(const PctParams prm)
 {
     __shared__ uint32_t tab[kPctWords * kPctStride];
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t lane = threadIdx.x, first = (blockIdx.x % prm.blocks) * kPctThreads, pixel = first + lane;
+    long col;
+    uint32_t first;
+    blockCells<kPctThreads>(prm, col, first);
+    const uint32_t lane = threadIdx.x, pixel = first + lane;
     const uint32_t live = min(uint32_t(kPctThreads), prm.out.P - first);
     long a, b;
     columnFrames(prm, col, a, b);
@@ -276,13 +272,14 @@ __global__ void __launch_bounds__(kPctThreads)
 overviewPctSliceKernel(const PctParams prm)
 {
     __shared__ uint32_t tab[kPctWords * kPctStride];
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t lane = threadIdx.x, first = (blockIdx.x % prm.blocks) * kPctThreads, pixel = first + lane;
+    long col;
+    uint32_t first;
+    blockCells<kPctThreads>(prm, col, first);
+    const uint32_t lane = threadIdx.x, pixel = first + lane;
     const uint32_t live = min(uint32_t(kPctThreads), prm.out.P - first);
-    long a, b;
+    long a, b, sa, sb;
     columnFrames(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(blockIdx.y) * per, sb = sa + per < b ? sa + per : b;
+    sliceRange(prm, a, b, b > a ? b - a : 0, sa, sb);
     for (uint32_t pair = 0; pair < prm.out.C; ++pair) {
         tabZero(tab, lane);
         if (lane < live) tabCount<kPctSliceUnroll>(tab, lane, prm, sa, sb, pair, pixel);
@@ -296,8 +293,10 @@ __global__ void __launch_bounds__(kPctThreads)
 overviewPctEmitKernel(const PctParams prm)
 {
     __shared__ uint32_t tab[kPctWords * kPctStride];
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t lane = threadIdx.x, first = (blockIdx.x % prm.blocks) * kPctThreads, pixel = first + lane;
+    long col;
+    uint32_t first;
+    blockCells<kPctThreads>(prm, col, first);
+    const uint32_t lane = threadIdx.x, pixel = first + lane;
     const uint32_t live = min(uint32_t(kPctThreads), prm.out.P - first);
     const size_t perSlice = size_t(prm.columns) * prm.out.C * prm.out.P;
     long a, b;
@@ -315,16 +314,6 @@ overviewPctEmitKernel(const PctParams prm)
         __syncthreads();
     }
     emitPixel(prm, col, pixel, lane, live, cb);
-}
-
-constexpr size_t kRecordFloats = sizeof(Record) / sizeof(float);     // plan scratch is counted in floats (ensureCap)
-
-sgz_status uploaded(Plan &p)                                         // the kernels read the plan's colour tables
-{
-    if (p.uploaded) return SGZ_OK;
-    std::string err;
-    const sgz_status st = uploadPlan(p, err);
-    return st == SGZ_OK ? st : fail(st, err);
 }
 
 // The library's choice of form: slices only where the launch would leave CUs idle, no slice shorter than kPctSliceFrames frames, and no
@@ -355,45 +344,16 @@ sgz_status runOverviewPctColumns(Plan &p, const float *d_lines, size_t frames, u
                                  uint32_t nq, sgz_overview_pct_record *d_carry, uint8_t *d_rgba, sgz_overview_pct_record *d_records,
                                  const PctPlanes &planes, hipStream_t stream)
 {
-    const uint64_t t = uint64_t(held) + frames;
-    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
-    const bool open = !flush && t % k != 0;
-    const uint64_t columns = closed + (open ? 1u : 0u);
-    if (frames == 0 && !(flush && held)) return SGZ_OK;          // nothing arrives and no column to flush
-    const uint32_t blocks = (p.P + kPctThreads - 1) / kPctThreads;
-    if (columns == 0 || blocks == 0) return SGZ_OK;
-    if (columns > 0x7fffffffull / blocks || frames > size_t(0x7fffffffffffffffll)) return fail(SGZ_EINVAL, "too many columns for one launch");
     PctParams prm{};
     prm.lines = reinterpret_cast<const float2 *>(d_lines);
-    prm.frames = long(frames); prm.columns = long(columns); prm.closed = long(closed);
-    prm.k = k; prm.held = held; prm.blocks = blocks;
-    prm.carryIn = d_carry; prm.carryOut = d_carry;
     PctOut &o = prm.out;
     o.C = p.C; o.P = p.P; o.nq = nq;
     o.rgba = reinterpret_cast<uchar4 *>(d_rgba); o.records = d_records;
     for (uint32_t j = 0; j < nq; ++j) { o.values[j] = planes.p[j]; o.q[j] = q[j]; }
     o.colourTables = p.d_colourTables; o.sc = p.scalars;
-    if (held && open && columns > 1) {
-        // column 0's waves read the carry while the open column's waves write it: they read a snapshot
-        const size_t carryN = size_t(p.C) * p.P;
-        if (sgz_status st = ensureCap(&p.ov[kOvPct].d_carryCopy, &p.ov[kOvPct].carryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.ov[kOvPct].d_carryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = reinterpret_cast<const Record *>(p.ov[kOvPct].d_carryCopy);
-    }
-    prm.slices = slices ? slices : pctAutoSlices(p, columns, blocks, k, frames);
-    const dim3 grid(unsigned(columns * blocks));
-    if (prm.slices <= 1) {
-        hipLaunchKernelGGL(overviewPctColumnsKernel, grid, dim3(kPctThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = ensureCap(&p.ov[kOvPct].d_partial, &p.ov[kOvPct].partialCap, size_t(prm.slices) * size_t(columns) * p.C * p.P * kRecordFloats); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<Record *>(p.ov[kOvPct].d_partial);
-    hipLaunchKernelGGL(overviewPctSliceKernel, dim3(grid.x, prm.slices), dim3(kPctThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(overviewPctEmitKernel, grid, dim3(kPctThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchOverviewColumns(p, kOvPct, prm, frames, k, held, flush, slices, d_carry, p.P, kPctThreads,
+                                 [&](uint64_t columns, uint32_t blocks) { return pctAutoSlices(p, columns, blocks, k, frames); },
+                                 overviewPctColumnsKernel, overviewPctSliceKernel, overviewPctEmitKernel, stream);
 }
 
 }  // namespace sgz
@@ -406,19 +366,18 @@ extern "C" sgz_status sgz_stage_overview_pct(sgz_plan *plan, const float *d_line
 {
     if (!plan || !d_lines) return fail(SGZ_EINVAL, "null argument");
     if (sgz_status st = checkOverviewStep(k, held, frames); st != SGZ_OK) return st;
-    if (slices > kPctMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview_pct: slices 0 (automatic) or 1 .. 64");
+    if (slices > kOvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview_pct: slices 0 (automatic) or 1 .. 64");
     if (!validPctQuantiles(q, nq)) return fail(SGZ_EINVAL, "sgz_stage_overview_pct: 1 .. 8 quantiles, each in [0, 1]");
     if (!d_rgba && !d_records && !d_values) return fail(SGZ_EINVAL, "sgz_stage_overview_pct: an image, the records, the values or any of them");
     if (reinterpret_cast<uintptr_t>(d_carry) % 16 || reinterpret_cast<uintptr_t>(d_records) % 16)
         return fail(SGZ_EINVAL, "sgz_stage_overview_pct: d_carry and d_records are aligned to 16 bytes");
-    const uint64_t t = uint64_t(held) + frames;
-    if (!d_carry && (held || (!flush && t % k))) return fail(SGZ_EINVAL, "sgz_stage_overview_pct: d_carry is read (held > 0) or written (frames stay open)");
-    if (frames == 0 && !(flush && held)) return SGZ_OK;
+    const OverviewStep sh = overviewStepShape(k, held, frames, flush);
+    if (!d_carry && (held || sh.open)) return fail(SGZ_EINVAL, "sgz_stage_overview_pct: d_carry is read (held > 0) or written (frames stay open)");
+    if (!sh.launch) return SGZ_OK;
     Plan &p = plan->impl;
     if (sgz_status st = uploaded(p); st != SGZ_OK) return st;
-    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
     return runOverviewPctColumns(p, d_lines, frames, k, held, flush, slices, q, nq, d_carry, d_rgba, d_records,
-                                 pctPlanes(d_values, 0, size_t(closed) * p.C * p.P, nq), reinterpret_cast<hipStream_t>(stream));
+                                 pctPlanes(d_values, 0, size_t(sh.closed) * p.C * p.P, nq), reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- the host helpers (no GPU) ----------------------------------------------------------------------------------------------------------------
@@ -435,30 +394,21 @@ extern "C" sgz_status sgz_overview_pct_bucket(float x, uint32_t *b)
 extern "C" sgz_status sgz_overview_pct_fold(const sgz_overview_pct_record *in, size_t n, size_t width, size_t x0, size_t x1, uint32_t out_columns,
                                             sgz_overview_pct_record *out)
 {
-    if (!in || !out) return fail(SGZ_EINVAL, "sgz_overview_pct_fold: null argument");
-    if (width == 0) return fail(SGZ_EINVAL, "sgz_overview_pct_fold: width >= 1 records per column");
-    uint64_t cols = 0;
-    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
-    const uint64_t m = x1 - x0;
-    // two passes: nothing is written when any word overflows
-    for (int pass = 0; pass < 2; ++pass)
-        for (uint64_t b = 0; b < cols; ++b) {
-            const uint64_t ja = x0 + (b * m + cols - 1) / cols, jb = x0 + ((b + 1) * m + cols - 1) / cols;
-            for (size_t i = 0; i < width; ++i) {
-                uint64_t acc[kPctWords] = {};
-                for (uint64_t j = ja; j < jb; ++j) {
-                    const uint32_t *w = reinterpret_cast<const uint32_t *>(in + j * width + i);
-                    for (int x = 0; x <= kPctNans; ++x) acc[x] += w[x];
-                }
-                uint32_t *o = reinterpret_cast<uint32_t *>(out + b * width + i);
-                for (int x = 0; x <= kPctNans; ++x) {
-                    if (acc[x] > 0xffffffffull) return fail(SGZ_EINVAL, "sgz_overview_pct_fold: a folded word counts more than 2^32 - 1 frames");
-                    if (pass) o[x] = uint32_t(acc[x]);
-                }
-                if (pass) o[kPctWords - 1] = 0u;
-            }
-        }
-    return SGZ_OK;
+    struct Wide { uint64_t w[kPctWords] = {}; };                // every word wide enough to see it pass 2^32 - 1
+    return foldKeptColumns<Wide>(
+        {"sgz_overview_pct_fold: null argument", "sgz_overview_pct_fold: width >= 1 records per column",
+         "sgz_overview_pct_fold: a folded word counts more than 2^32 - 1 frames"},
+        in, n, width, x0, x1, out_columns, out,
+        [](Wide &acc, const Record &r) {
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(&r);
+            for (int x = 0; x <= kPctNans; ++x) acc.w[x] += w[x];
+        },
+        [](const Wide &acc) { return std::all_of(acc.w, acc.w + kPctNans + 1, [](uint64_t c) { return c <= 0xffffffffull; }); },
+        [](const Wide &acc, Record &r) {
+            uint32_t *o = reinterpret_cast<uint32_t *>(&r);
+            for (int x = 0; x <= kPctNans; ++x) o[x] = uint32_t(acc.w[x]);
+            o[kPctWords - 1] = 0u;
+        });
 }
 
 extern "C" sgz_status sgz_overview_pct_readout(const sgz_overview_pct_record *records, size_t count, const double *q, uint32_t nq, float *values)

@@ -7,7 +7,9 @@
 //   rms = (float)(sqrt(S / count) 2^-30), S = (double)sum[1] 2^64 + (double)sum[0];  level = dbMap(slopeMap[i], rms) of decay_body.hpp (called,
 //   not copied) -- K_B's line result for a frame of magnitude rms from a zero decay state;  the pixel is blendColour / toRgba8 at side 0's level.
 // The kernels keep an accumulator: the sum as unsigned __int128 (level_columns.hip's way), the counts, hi as a key (0: no value yet) and lo as
-// key - 1 (0xFFFFFFFF: no value yet; order_key.hpp), and turn it into a record where it leaves the registers.  The three shapes of
+// key - 1 (0xFFFFFFFF: no value yet; order_key.hpp), and turn it into a record where it leaves the registers.  This file holds the kind
+// (struct Power: the record, the accumulator's operations, a record's load and store, emitClosed) and the named entry points; the six kernel
+// bodies, the bounds, the batched folds, the launch front and the host fold's frame are overview_kinds.hpp's.  The three shapes of
 // overview_stats.hip, for its reasons, with a column's sides * P values in the place of its P:
 //   overviewPowerColumnsKernel   one thread per (column, side * P + pixel): pairs outermost (the blend order), the column's frames inside, 8 loads
 //                                in flight before the quantiser and the updates; then the carry, the readout, the level, the colour, the stores.
@@ -33,6 +35,8 @@
 
 #pragma clang fp contract(off)
 
+#include "overview_kinds.hpp"   // behind the pragma: its templates are parsed without contraction
+
 using namespace sgz;
 
 static_assert(sizeof(sgz_overview_power_record) == 32 && alignof(sgz_overview_power_record) == 8, "sgz_overview_power_record: 32 bytes, 8-aligned");
@@ -45,9 +49,6 @@ namespace {
 using Record = sgz_overview_power_record;
 typedef unsigned __int128 u128;
 
-constexpr int kOvThreads = 256;
-constexpr int kOvUnroll = 8;             // frames (or slices, or source columns) whose loads are issued before the first update
-constexpr uint32_t kOvMaxSlices = 64;
 constexpr double kQuantum = 1152921504606846976.0;      // 2^60 steps per unit of power
 constexpr double kQMost = 18446744073709549568.0;       // 2^64 - 2^11, the largest double below 2^64
 constexpr double kTwo64 = 18446744073709551616.0;
@@ -78,90 +79,8 @@ __host__ __device__ inline uint32_t powerRmsBits(uint64_t lo, uint64_t hi, uint3
 #ifdef __HIP_DEVICE_COMPILE__
     return __float_as_uint(float(__dsqrt_rn(ms) * kRmsScale));
 #else
-    const float rms = float(std::sqrt(ms) * kRmsScale);
-    uint32_t bits;
-    std::memcpy(&bits, &rms, sizeof bits);
-    return bits;
+    return hostBits(float(std::sqrt(ms) * kRmsScale));
 #endif
-}
-
-// ---- the accumulator ---------------------------------------------------------------------------------------------------------------------
-struct Acc {
-    u128 sum = 0;
-    uint32_t count = 0, nans = 0;
-    uint32_t hi = 0u;                    // the greatest orderKey; 0: no value yet
-    uint32_t lo = 0xffffffffu;           // the least orderKeyMin; 0xFFFFFFFF: no value yet
-};
-
-__device__ __forceinline__ void accFrame(Acc &a, uint32_t bits)
-{
-    const uint32_t key = orderKey(bits);                         // 0 for a NaN: it moves neither hi nor, as key - 1 = 0xFFFFFFFF, lo
-    const bool nan = key == 0u;
-    const uint64_t q = powerQuantise(__uint_as_float(bits));
-    a.sum += u128(nan ? 0ull : q);
-    a.count += nan ? 0u : 1u;
-    a.nans += nan ? 1u : 0u;
-    a.hi = max(a.hi, key);
-    a.lo = min(a.lo, key - 1u);
-}
-
-// field-wise: a record without values carries NaNs in lo and hi, whose keys are the two empty markers
-__device__ __forceinline__ void accFold(Acc &a, const Record &r)
-{
-    a.sum += (u128(r.sum[1]) << 64) | u128(r.sum[0]);
-    a.count += r.count;
-    a.nans += r.nans;
-    a.hi = max(a.hi, orderKey(__float_as_uint(r.hi)));
-    a.lo = min(a.lo, orderKeyMin(__float_as_uint(r.lo)));
-}
-
-__device__ __forceinline__ Record accRecord(const Acc &a)
-{
-    Record r;
-    r.sum[0] = uint64_t(a.sum); r.sum[1] = uint64_t(a.sum >> 64);
-    r.count = a.count; r.nans = a.nans;
-    r.lo = __uint_as_float(keyBitsMin(a.lo));
-    r.hi = __uint_as_float(keyBits(a.hi));
-    return r;
-}
-
-// a record as two 16-byte words, for loads that are issued together
-struct Words { uint4 w[2]; };
-__device__ __forceinline__ Words loadWords(const Record *p)
-{
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    return Words{{q[0], q[1]}};
-}
-__device__ __forceinline__ Record wordsRecord(const Words &x)
-{
-    Record r;
-    r.sum[0] = uint64_t(x.w[0].x) | (uint64_t(x.w[0].y) << 32);
-    r.sum[1] = uint64_t(x.w[0].z) | (uint64_t(x.w[0].w) << 32);
-    r.count = x.w[1].x; r.nans = x.w[1].y;
-    r.lo = __uint_as_float(x.w[1].z); r.hi = __uint_as_float(x.w[1].w);
-    return r;
-}
-__device__ __forceinline__ void storeRecord(Record *p, const Record &r)
-{
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(uint32_t(r.sum[0]), uint32_t(r.sum[0] >> 32), uint32_t(r.sum[1]), uint32_t(r.sum[1] >> 32));
-    q[1] = make_uint4(r.count, r.nans, __float_as_uint(r.lo), __float_as_uint(r.hi));
-}
-
-// the fold of `n` records `stride` apart, independent loads first
-__device__ __forceinline__ Acc foldRecords(const Record *first, size_t stride, long n)
-{
-    Acc acc;
-    for (long j = 0; j < n; j += kOvUnroll) {
-        Words x[kOvUnroll];
-#pragma unroll
-        for (int u = 0; u < kOvUnroll; ++u)
-            if (j + u < n) x[u] = loadWords(first + size_t(j + u) * stride);
-#pragma unroll
-        for (int u = 0; u < kOvUnroll; ++u)
-            if (j + u < n) accFold(acc, wordsRecord(x[u]));
-    }
-    return acc;
 }
 
 // ---- what every emitting kernel writes -----------------------------------------------------------------------------------------------------
@@ -175,29 +94,7 @@ struct PowerOut {
     DeviceScalars sc;
 };
 
-// a closed column of thread j = side * P + pixel: the records, the levels and -- side 0 -- the blend at the levels in pair order
-template <typename AccOf>
-__device__ __forceinline__ void emitClosed(const PowerOut &o, long col, uint32_t j, AccOf accOf)
-{
-    const uint32_t pixel = j < o.P ? j : j - o.P;
-    const bool image = o.rgba && j < o.P;
-    const bool level = o.levels || image;
-    const float slope = level ? o.slope[pixel] : 0.f;
-    float cb[3] = {0.f, 0.f, 0.f};
-    for (uint32_t pair = 0; pair < o.C; ++pair) {
-        const Acc acc = accOf(pair);
-        const size_t at = (size_t(col) * o.C + pair) * o.SP + j;
-        if (o.power) storeRecord(o.power + at, accRecord(acc));
-        if (!level) continue;
-        float lv = __uint_as_float(0x7fc00000u);
-        if (acc.count) lv = dbMap(slope, __uint_as_float(powerRmsBits(uint64_t(acc.sum), uint64_t(acc.sum >> 64), acc.count)), o.sc);
-        if (o.levels) o.levels[at] = lv;
-        if (image) blendColour(cb, lv, o.colourTables + size_t(pair) * NC * 3, o.sc);
-    }
-    if (image) o.rgba[size_t(col) * o.P + pixel] = toRgba8(cb);
-}
-
-// ---- the direct form: k frames of mapped magnitudes per column -------------------------------------------------------------------------------
+// the direct form: k frames of mapped magnitudes per column
 struct PowerParams {
     const float *mapped;                 // [frames][C][sides][P]
     long frames;
@@ -209,90 +106,7 @@ struct PowerParams {
     PowerOut out;
 };
 
-// frames [a, b) of this call that belong to column `col`
-__device__ __forceinline__ void columnFrames(const PowerParams &prm, long col, long &a, long &b)
-{
-    a = col * long(prm.k) - long(prm.held);
-    b = a + long(prm.k);
-    a = a < 0 ? 0 : a;
-    b = b > prm.frames ? prm.frames : b;
-}
-
-// the accumulator of (pair, j) over frames [a, b), independent loads first
-__device__ __forceinline__ Acc framesAcc(const PowerParams &prm, long a, long b, uint32_t pair, uint32_t j)
-{
-    const size_t perFrame = size_t(prm.out.C) * prm.out.SP;
-    const uint32_t *row = reinterpret_cast<const uint32_t *>(prm.mapped) + size_t(pair) * prm.out.SP + j;
-    Acc acc;
-    for (long f = a; f < b; f += kOvUnroll) {
-        uint32_t bits[kOvUnroll];
-#pragma unroll
-        for (int u = 0; u < kOvUnroll; ++u) bits[u] = f + u < b ? row[size_t(f + u) * perFrame] : 0xffffffffu;
-#pragma unroll
-        for (int u = 0; u < kOvUnroll; ++u) accFrame(acc, bits[u]);
-    }
-    // the last batch was filled up with NaNs, which moved nothing but their count
-    const long n = b > a ? b - a : 0;
-    acc.nans -= uint32_t((kOvUnroll - n % kOvUnroll) % kOvUnroll);
-    return acc;
-}
-
-// what a (column, j) does with its accumulators: the carry into column 0, then a closed column's outputs or the open one's carry
-template <typename AccOf>
-__device__ __forceinline__ void emitColumn(const PowerParams &prm, long col, uint32_t j, AccOf accOf)
-{
-    const auto withCarry = [&](uint32_t pair) {
-        Acc acc = accOf(pair);
-        if (col == 0 && prm.held) accFold(acc, wordsRecord(loadWords(prm.carryIn + size_t(pair) * prm.out.SP + j)));
-        return acc;
-    };
-    if (col < prm.closed) { emitClosed(prm.out, col, j, withCarry); return; }
-    for (uint32_t pair = 0; pair < prm.out.C; ++pair) storeRecord(prm.carryOut + size_t(pair) * prm.out.SP + j, accRecord(withCarry(pair)));
-}
-
-__global__ void __launch_bounds__(kOvThreads)
-overviewPowerColumnsKernel(const PowerParams prm)
-{
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t j = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
-    if (j >= prm.out.SP) return;
-    long a, b;
-    columnFrames(prm, col, a, b);
-    emitColumn(prm, col, j, [&](uint32_t pair) { return framesAcc(prm, a, b, pair, j); });
-}
-
-// slice blockIdx.y of every column's frames (an empty slice -- more slices than frames -- leaves an empty record)
-__global__ void __launch_bounds__(kOvThreads)
-overviewPowerSliceKernel(const PowerParams prm)
-{
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t j = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
-    if (j >= prm.out.SP) return;
-    long a, b;
-    columnFrames(prm, col, a, b);
-    const long n = b > a ? b - a : 0, per = (n + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(blockIdx.y) * per, sb = sa + per < b ? sa + per : b;
-    for (uint32_t pair = 0; pair < prm.out.C; ++pair)
-        storeRecord(prm.partial + ((size_t(blockIdx.y) * size_t(prm.columns) + size_t(col)) * prm.out.C + pair) * prm.out.SP + j,
-                    accRecord(framesAcc(prm, sa, sb, pair, j)));
-}
-
-__global__ void __launch_bounds__(kOvThreads)
-overviewPowerEmitKernel(const PowerParams prm)
-{
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t j = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
-    if (j >= prm.out.SP) return;
-    const size_t perSlice = size_t(prm.columns) * prm.out.C * prm.out.SP;
-    emitColumn(prm, col, j, [&](uint32_t pair) {
-        return foldRecords(prm.partial + (size_t(col) * prm.out.C + pair) * prm.out.SP + j, perSlice, long(prm.slices));
-    });
-}
-
-// ---- the view of kept records (sgz.h, "The power overview") --------------------------------------------------------------------------------
-// records [n][pairs][sides][P] as any power call writes them; output column b is the fold of source columns ceil(b m / cols) <= j < ceil((b + 1)
-// m / cols) of the range, m = x1 - x0 -- the boundary rule of the view of kept peaks, and a fold of folds, hence the bytes of the direct call
-// wherever the boundaries coincide.
+// the view of kept records (sgz.h, "The power overview"): records [n][pairs][sides][P] as any power call writes them
 struct PowerViewParams {
     const Record *src;                   // [m][C][sides][P]: the range's first source column
     long m, cols;
@@ -301,59 +115,118 @@ struct PowerViewParams {
     PowerOut out;
 };
 
-// source columns [a, b) of output column `col`, relative to the range (m < 2^31 and col <= cols <= m: the products fit)
-__device__ __forceinline__ void viewColumns(const PowerViewParams &prm, long col, long &a, long &b)
-{
-    a = (col * prm.m + prm.cols - 1) / prm.cols;
-    b = ((col + 1) * prm.m + prm.cols - 1) / prm.cols;
-}
+// the mapped magnitudes of thread j = side * P + pixel of a pair over the frames, as bits
+struct MappedRow {
+    const uint32_t *first;
+    size_t perFrame;
+    __device__ __forceinline__ uint32_t bits(long f) const { return first[size_t(f) * perFrame]; }
+};
 
-__device__ __forceinline__ Acc viewAcc(const PowerViewParams &prm, long a, long b, uint32_t pair, uint32_t j)
-{
-    const size_t perColumn = size_t(prm.out.C) * prm.out.SP;
-    return foldRecords(prm.src + size_t(a) * perColumn + size_t(pair) * prm.out.SP + j, perColumn, b > a ? b - a : 0);
-}
+// ---- the kind (overview_kinds.hpp, section 3) ------------------------------------------------------------------------------------------------
+struct Power {
+    using Record = ::Record;
+    using Params = PowerParams;
+    using ViewParams = PowerViewParams;
+    static constexpr int kThreads = 256;
 
-__global__ void __launch_bounds__(kOvThreads)
-overviewPowerViewKernel(const PowerViewParams prm)
-{
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t j = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
-    if (j >= prm.out.SP) return;
-    long a, b;
-    viewColumns(prm, col, a, b);
-    emitClosed(prm.out, col, j, [&](uint32_t pair) { return viewAcc(prm, a, b, pair, j); });
-}
+    struct Acc {
+        u128 sum = 0;
+        uint32_t count = 0, nans = 0;
+        uint32_t hi = 0u;                // the greatest orderKey; 0: no value yet
+        uint32_t lo = 0xffffffffu;       // the least orderKeyMin; 0xFFFFFFFF: no value yet
+    };
 
-// slice blockIdx.y of every output column's source columns (an empty slice leaves an empty record)
-__global__ void __launch_bounds__(kOvThreads)
-overviewPowerViewSliceKernel(const PowerViewParams prm)
-{
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t j = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
-    if (j >= prm.out.SP) return;
-    long a, b;
-    viewColumns(prm, col, a, b);
-    const long per = (b - a + long(prm.slices) - 1) / long(prm.slices);
-    const long sa = a + long(blockIdx.y) * per, sb = sa + per < b ? sa + per : b;
-    for (uint32_t pair = 0; pair < prm.out.C; ++pair)
-        storeRecord(prm.partial + ((size_t(blockIdx.y) * size_t(prm.cols) + size_t(col)) * prm.out.C + pair) * prm.out.SP + j,
-                    accRecord(viewAcc(prm, sa, sb, pair, j)));
-}
+    static __device__ __forceinline__ uint32_t cells(const PowerOut &o) { return o.SP; }
+    static __device__ __forceinline__ MappedRow row(const Params &prm, uint32_t pair, uint32_t j)
+    {
+        return MappedRow{reinterpret_cast<const uint32_t *>(prm.mapped) + size_t(pair) * prm.out.SP + j, size_t(prm.out.C) * prm.out.SP};
+    }
 
-__global__ void __launch_bounds__(kOvThreads)
-overviewPowerViewEmitKernel(const PowerViewParams prm)
-{
-    const long col = long(blockIdx.x / prm.blocks);
-    const uint32_t j = (blockIdx.x % prm.blocks) * kOvThreads + threadIdx.x;
-    if (j >= prm.out.SP) return;
-    const size_t perSlice = size_t(prm.cols) * prm.out.C * prm.out.SP;
-    emitClosed(prm.out, col, j, [&](uint32_t pair) {
-        return foldRecords(prm.partial + (size_t(col) * prm.out.C + pair) * prm.out.SP + j, perSlice, long(prm.slices));
-    });
-}
+    static __device__ __forceinline__ void accFrame(Acc &a, uint32_t bits)
+    {
+        const uint32_t key = orderKey(bits);                     // 0 for a NaN: it moves neither hi nor, as key - 1 = 0xFFFFFFFF, lo
+        const bool nan = key == 0u;
+        const uint64_t q = powerQuantise(__uint_as_float(bits));
+        a.sum += u128(nan ? 0ull : q);
+        a.count += nan ? 0u : 1u;
+        a.nans += nan ? 1u : 0u;
+        a.hi = max(a.hi, key);
+        a.lo = min(a.lo, key - 1u);
+    }
+    static __device__ __forceinline__ void accUnfill(Acc &a, uint32_t n) { a.nans -= n; }
 
-constexpr size_t kRecordFloats = sizeof(Record) / sizeof(float);     // plan scratch is counted in floats (ensureCap)
+    // field-wise: a record without values carries NaNs in lo and hi, whose keys are the two empty markers
+    static __device__ __forceinline__ void accFold(Acc &a, const Record &r)
+    {
+        a.sum += (u128(r.sum[1]) << 64) | u128(r.sum[0]);
+        a.count += r.count;
+        a.nans += r.nans;
+        a.hi = max(a.hi, orderKey(__float_as_uint(r.hi)));
+        a.lo = min(a.lo, orderKeyMin(__float_as_uint(r.lo)));
+    }
+
+    static __device__ __forceinline__ Record accRecord(const Acc &a)
+    {
+        Record r;
+        r.sum[0] = uint64_t(a.sum); r.sum[1] = uint64_t(a.sum >> 64);
+        r.count = a.count; r.nans = a.nans;
+        r.lo = __uint_as_float(keyBitsMin(a.lo));
+        r.hi = __uint_as_float(keyBits(a.hi));
+        return r;
+    }
+
+    // a record as two 16-byte words, for loads that are issued together
+    struct Words { uint4 w[2]; };
+    static __device__ __forceinline__ Words loadWords(const Record *p)
+    {
+        const uint4 *q = reinterpret_cast<const uint4 *>(p);
+        return Words{{q[0], q[1]}};
+    }
+    static __device__ __forceinline__ Record wordsRecord(const Words &x)
+    {
+        Record r;
+        r.sum[0] = uint64_t(x.w[0].x) | (uint64_t(x.w[0].y) << 32);
+        r.sum[1] = uint64_t(x.w[0].z) | (uint64_t(x.w[0].w) << 32);
+        r.count = x.w[1].x; r.nans = x.w[1].y;
+        r.lo = __uint_as_float(x.w[1].z); r.hi = __uint_as_float(x.w[1].w);
+        return r;
+    }
+    static __device__ __forceinline__ void storeRecord(Record *p, const Record &r)
+    {
+        uint4 *q = reinterpret_cast<uint4 *>(p);
+        q[0] = make_uint4(uint32_t(r.sum[0]), uint32_t(r.sum[0] >> 32), uint32_t(r.sum[1]), uint32_t(r.sum[1] >> 32));
+        q[1] = make_uint4(r.count, r.nans, __float_as_uint(r.lo), __float_as_uint(r.hi));
+    }
+
+    // a closed column of thread j = side * P + pixel: the records, the levels and -- side 0 -- the blend at the levels in pair order
+    template <typename AccOf>
+    static __device__ __forceinline__ void emitClosed(const PowerOut &o, long col, uint32_t j, AccOf accOf)
+    {
+        const uint32_t pixel = j < o.P ? j : j - o.P;
+        const bool image = o.rgba && j < o.P;
+        const bool level = o.levels || image;
+        const float slope = level ? o.slope[pixel] : 0.f;
+        float cb[3] = {0.f, 0.f, 0.f};
+        for (uint32_t pair = 0; pair < o.C; ++pair) {
+            const Acc acc = accOf(pair);
+            const size_t at = (size_t(col) * o.C + pair) * o.SP + j;
+            if (o.power) storeRecord(o.power + at, accRecord(acc));
+            if (!level) continue;
+            float lv = __uint_as_float(0x7fc00000u);
+            if (acc.count) lv = dbMap(slope, __uint_as_float(powerRmsBits(uint64_t(acc.sum), uint64_t(acc.sum >> 64), acc.count)), o.sc);
+            if (o.levels) o.levels[at] = lv;
+            if (image) blendColour(cb, lv, o.colourTables + size_t(pair) * NC * 3, o.sc);
+        }
+        if (image) o.rgba[size_t(col) * o.P + pixel] = toRgba8(cb);
+    }
+};
+
+__global__ void __launch_bounds__(Power::kThreads) overviewPowerColumnsKernel(const PowerParams prm) { overviewColumnsBody<Power>(prm); }
+__global__ void __launch_bounds__(Power::kThreads) overviewPowerSliceKernel(const PowerParams prm) { overviewSliceBody<Power>(prm); }
+__global__ void __launch_bounds__(Power::kThreads) overviewPowerEmitKernel(const PowerParams prm) { overviewEmitBody<Power>(prm); }
+__global__ void __launch_bounds__(Power::kThreads) overviewPowerViewKernel(const PowerViewParams prm) { overviewViewBody<Power>(prm); }
+__global__ void __launch_bounds__(Power::kThreads) overviewPowerViewSliceKernel(const PowerViewParams prm) { overviewViewSliceBody<Power>(prm); }
+__global__ void __launch_bounds__(Power::kThreads) overviewPowerViewEmitKernel(const PowerViewParams prm) { overviewViewEmitBody<Power>(prm); }
 
 PowerOut powerOut(const Plan &p, uint8_t *d_rgba, Record *d_power, float *d_levels)
 {
@@ -364,18 +237,8 @@ PowerOut powerOut(const Plan &p, uint8_t *d_rgba, Record *d_power, float *d_leve
     return o;
 }
 
-sgz_status uploaded(Plan &p)                                         // the kernels read the plan's slope map and colour tables
-{
-    if (p.uploaded) return SGZ_OK;
-    std::string err;
-    const sgz_status st = uploadPlan(p, err);
-    return st == SGZ_OK ? st : fail(st, err);
-}
-
 // host: the accumulator of sgz_overview_power_fold, with counts wide enough to see them pass 2^32 - 1
 struct HostAcc { u128 sum = 0; uint64_t count = 0, nans = 0; uint32_t hi = 0u, lo = 0xffffffffu; };
-uint32_t hostBits(float v) { uint32_t bits; std::memcpy(&bits, &v, sizeof bits); return bits; }
-float hostFloat(uint32_t bits) { float v; std::memcpy(&v, &bits, sizeof v); return v; }
 
 }  // namespace
 
@@ -386,71 +249,23 @@ sgz_status runOverviewPowerColumns(Plan &p, const float *d_mapped, size_t frames
                                    sgz_overview_power_record *d_carry, uint8_t *d_rgba, sgz_overview_power_record *d_power, float *d_levels,
                                    hipStream_t stream)
 {
-    const uint64_t t = uint64_t(held) + frames;
-    const uint64_t closed = t / k + ((flush && t % k) ? 1u : 0u);
-    const bool open = !flush && t % k != 0;
-    const uint64_t columns = closed + (open ? 1u : 0u);
-    if (frames == 0 && !(flush && held)) return SGZ_OK;          // nothing arrives and no column to flush
-    const uint32_t sp = uint32_t(p.sides) * p.P;
-    const uint32_t blocks = (sp + kOvThreads - 1) / kOvThreads;
-    if (columns == 0 || blocks == 0) return SGZ_OK;
-    if (columns > 0x7fffffffull / blocks || frames > size_t(0x7fffffffffffffffll)) return fail(SGZ_EINVAL, "too many columns for one launch");
     PowerParams prm{};
     prm.mapped = d_mapped;
-    prm.frames = long(frames); prm.columns = long(columns); prm.closed = long(closed);
-    prm.k = k; prm.held = held; prm.blocks = blocks;
-    prm.carryIn = d_carry; prm.carryOut = d_carry;
     prm.out = powerOut(p, d_rgba, d_power, d_levels);
-    if (held && open && columns > 1) {
-        // column 0's threads read the carry while the open column's threads write it: they read a snapshot
-        const size_t carryN = size_t(p.C) * sp;
-        if (sgz_status st = ensureCap(&p.ov[kOvPower].d_carryCopy, &p.ov[kOvPower].carryCopyCap, carryN * kRecordFloats); st != SGZ_OK) return st;
-        SGZ_HIP(hipMemcpyAsync(p.ov[kOvPower].d_carryCopy, d_carry, carryN * sizeof(Record), hipMemcpyDeviceToDevice, stream));
-        prm.carryIn = reinterpret_cast<const Record *>(p.ov[kOvPower].d_carryCopy);
-    }
-    prm.slices = slices ? slices : overviewAutoSlices(long(columns), blocks, k, frames, numCUs());
-    const dim3 grid(unsigned(columns * blocks));
-    if (prm.slices <= 1) {
-        hipLaunchKernelGGL(overviewPowerColumnsKernel, grid, dim3(kOvThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = ensureCap(&p.ov[kOvPower].d_partial, &p.ov[kOvPower].partialCap, size_t(prm.slices) * size_t(columns) * p.C * sp * kRecordFloats); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<Record *>(p.ov[kOvPower].d_partial);
-    hipLaunchKernelGGL(overviewPowerSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(overviewPowerEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchOverviewColumns(p, kOvPower, prm, frames, k, held, flush, slices, d_carry, prm.out.SP, Power::kThreads,
+                                 [&](uint64_t columns, uint32_t blocks) { return overviewAutoSlices(long(columns), blocks, k, frames, numCUs()); },
+                                 overviewPowerColumnsKernel, overviewPowerSliceKernel, overviewPowerEmitKernel, stream);
 }
 
 // sgz_stage_overview_power_view behind its argument checks (the plan's tables are uploaded).  d_src [m][C][sides][P]: the range's first source column.
 sgz_status runOverviewPowerView(Plan &p, const sgz_overview_power_record *d_src, size_t m, size_t cols, uint32_t slices, uint8_t *d_rgba,
                                 sgz_overview_power_record *d_powerOut, float *d_levels, hipStream_t stream)
 {
-    const uint32_t sp = uint32_t(p.sides) * p.P;
-    const uint32_t blocks = (sp + kOvThreads - 1) / kOvThreads;
-    if (cols == 0 || blocks == 0) return SGZ_OK;
-    if (cols > 0x7fffffffull / blocks) return fail(SGZ_EINVAL, "too many columns for one launch");
     PowerViewParams prm{};
-    prm.src = d_src; prm.m = long(m); prm.cols = long(cols); prm.blocks = blocks;
+    prm.src = d_src;
     prm.out = powerOut(p, d_rgba, d_powerOut, d_levels);
-    const uint32_t most = uint32_t((m + cols - 1) / cols);       // source columns of the longest output column
-    // the rule of the view of kept peaks (overview.hip runOverviewView)
-    prm.slices = slices ? slices : std::min(overviewAutoSlices(long(cols), blocks, most, m, 2 * numCUs()), std::max(1u, most / uint32_t(kOvUnroll)));
-    const dim3 grid(unsigned(cols * blocks));
-    if (prm.slices <= 1) {
-        hipLaunchKernelGGL(overviewPowerViewKernel, grid, dim3(kOvThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = ensureCap(&p.ov[kOvPower].d_partial, &p.ov[kOvPower].partialCap, size_t(prm.slices) * cols * p.C * sp * kRecordFloats); st != SGZ_OK) return st;
-    prm.partial = reinterpret_cast<Record *>(p.ov[kOvPower].d_partial);
-    hipLaunchKernelGGL(overviewPowerViewSliceKernel, dim3(grid.x, prm.slices), dim3(kOvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(overviewPowerViewEmitKernel, grid, dim3(kOvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchOverviewView(p, kOvPower, prm, m, cols, slices, prm.out.SP, Power::kThreads, overviewPowerViewKernel, overviewPowerViewSliceKernel,
+                              overviewPowerViewEmitKernel, stream);
 }
 
 }  // namespace sgz
@@ -465,9 +280,9 @@ extern "C" sgz_status sgz_stage_overview_power(sgz_plan *plan, const float *d_ma
     if (sgz_status st = checkOverviewStep(k, held, frames); st != SGZ_OK) return st;
     if (slices > kOvMaxSlices) return fail(SGZ_EINVAL, "sgz_stage_overview_power: slices 0 (automatic) or 1 .. 64");
     if (!d_rgba && !d_power && !d_levels) return fail(SGZ_EINVAL, "sgz_stage_overview_power: an image, the records, the levels or any of them");
-    const uint64_t t = uint64_t(held) + frames;
-    if (!d_carry && (held || (!flush && t % k))) return fail(SGZ_EINVAL, "sgz_stage_overview_power: d_carry is read (held > 0) or written (frames stay open)");
-    if (frames == 0 && !(flush && held)) return SGZ_OK;
+    const OverviewStep sh = overviewStepShape(k, held, frames, flush);
+    if (!d_carry && (held || sh.open)) return fail(SGZ_EINVAL, "sgz_stage_overview_power: d_carry is read (held > 0) or written (frames stay open)");
+    if (!sh.launch) return SGZ_OK;
     Plan &p = plan->impl;
     if (sgz_status st = uploaded(p); st != SGZ_OK) return st;
     return runOverviewPowerColumns(p, d_mapped, frames, k, held, flush, slices, d_carry, d_rgba, d_power, d_levels, reinterpret_cast<hipStream_t>(stream));
@@ -504,34 +319,22 @@ extern "C" sgz_status sgz_overview_power_quantise(const float *x, size_t n, uint
 extern "C" sgz_status sgz_overview_power_fold(const sgz_overview_power_record *in, size_t n, size_t width, size_t x0, size_t x1, uint32_t out_columns,
                                               sgz_overview_power_record *out)
 {
-    if (!in || !out) return fail(SGZ_EINVAL, "sgz_overview_power_fold: null argument");
-    if (width == 0) return fail(SGZ_EINVAL, "sgz_overview_power_fold: width >= 1 records per column");
-    uint64_t cols = 0;
-    if (sgz_status st = checkViewRange(n, x0, x1, out_columns, &cols); st != SGZ_OK) return st;
-    const uint64_t m = x1 - x0;
-    // two passes: nothing is written when any column's count overflows
-    for (int pass = 0; pass < 2; ++pass)
-        for (uint64_t b = 0; b < cols; ++b) {
-            const uint64_t ja = x0 + (b * m + cols - 1) / cols, jb = x0 + ((b + 1) * m + cols - 1) / cols;
-            for (size_t i = 0; i < width; ++i) {
-                HostAcc acc;
-                for (uint64_t j = ja; j < jb; ++j) {
-                    const Record &r = in[j * width + i];
-                    acc.sum += (u128(r.sum[1]) << 64) | u128(r.sum[0]);
-                    acc.count += r.count; acc.nans += r.nans;
-                    acc.hi = std::max(acc.hi, orderKey(hostBits(r.hi)));
-                    acc.lo = std::min(acc.lo, orderKeyMin(hostBits(r.lo)));
-                }
-                if (acc.count > 0xffffffffull || acc.nans > 0xffffffffull)
-                    return fail(SGZ_EINVAL, "sgz_overview_power_fold: a folded column counts more than 2^32 - 1 frames");
-                if (pass == 0) continue;
-                Record &o = out[b * width + i];
-                o.sum[0] = uint64_t(acc.sum); o.sum[1] = uint64_t(acc.sum >> 64);
-                o.count = uint32_t(acc.count); o.nans = uint32_t(acc.nans);
-                o.lo = hostFloat(keyBitsMin(acc.lo)); o.hi = hostFloat(keyBits(acc.hi));
-            }
-        }
-    return SGZ_OK;
+    return foldKeptColumns<HostAcc>(
+        {"sgz_overview_power_fold: null argument", "sgz_overview_power_fold: width >= 1 records per column",
+         "sgz_overview_power_fold: a folded column counts more than 2^32 - 1 frames"},
+        in, n, width, x0, x1, out_columns, out,
+        [](HostAcc &acc, const Record &r) {
+            acc.sum += (u128(r.sum[1]) << 64) | u128(r.sum[0]);
+            acc.count += r.count; acc.nans += r.nans;
+            acc.hi = std::max(acc.hi, orderKey(hostBits(r.hi)));
+            acc.lo = std::min(acc.lo, orderKeyMin(hostBits(r.lo)));
+        },
+        [](const HostAcc &acc) { return acc.count <= 0xffffffffull && acc.nans <= 0xffffffffull; },
+        [](const HostAcc &acc, Record &o) {
+            o.sum[0] = uint64_t(acc.sum); o.sum[1] = uint64_t(acc.sum >> 64);
+            o.count = uint32_t(acc.count); o.nans = uint32_t(acc.nans);
+            o.lo = hostFloat(keyBitsMin(acc.lo)); o.hi = hostFloat(keyBits(acc.hi));
+        });
 }
 
 extern "C" sgz_status sgz_overview_power_readout(const sgz_overview_power_record *in, size_t count, double *mean_square, float *rms, float *lo, float *hi)

@@ -169,6 +169,7 @@ sgz_status runOverviewPctColumns(Plan &p, const float *d_lines, size_t frames, u
 sgz_status runOverviewPctSlabs(sgz_plan *plan, const float *d_planar, size_t channel_stride, size_t nsamples, long frames, uint32_t k, uint32_t held,
                                int flush, const double *q, uint32_t nq, sgz_overview_pct_record *d_carry, float *d_state, uint8_t *d_rgba,
                                sgz_overview_pct_record *d_records, const PctPlanes &planes, hipStream_t stream, const SlabTrack *track = nullptr);
+// what the overview kinds' files share beside the declarations above (the step, the bounds, the kernel bodies, the launch front): overview_kinds.hpp
 // the column lanes' reductions (wave, level, true-peak, loudness, stereo-field, band): column_lanes.hpp
 sgz_status trackPeakLines(const Plan &p, const float *results /*host float2 [P]*/, double mouseFraction, sgz_line_peak *out);   // tracker.hip
 sgz_status trackPeakValues(const Plan &p, const float *values /*host float [P]*/, double mouseFraction, sgz_line_peak *out);
