@@ -325,6 +325,7 @@ def lib() -> C.CDLL:
         pass
     L = C.CDLL(path)
     vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
+    fp, bp, rp = C.POINTER(LoudnessFilter), C.POINTER(BandFilter), C.POINTER(RunParams)
     L.sgz_last_error.restype = C.c_char_p
     L.sgz_plan_create.argtypes = [C.POINTER(SpectrumConfig), C.POINTER(vp)]
     L.sgz_plan_destroy.argtypes = [vp]
@@ -559,9 +560,6 @@ def lib() -> C.CDLL:
     L.sgz_pcm_stream_open_frames.argtypes = [vp]
     L.sgz_pcm_stream_open_frames.restype = u64
     L.sgz_pcm_stream_set_option.argtypes = [vp, u32, u32]
-    L.sgz_stage_wave_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
-    L.sgz_wave_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
-    L.sgz_wave_columns_limits.restype = None
     L.sgz_track_peak_values.argtypes = [vp, vp, C.c_double, C.POINTER(LinePeak)]
     L.sgz_stage_track_peaks_values.argtypes = [vp, vp, sz, C.c_double, vp, vp]
     L.sgz_pcm_stream_set_track.argtypes = [vp, u32, C.c_double, vp, u64]
@@ -580,59 +578,43 @@ def lib() -> C.CDLL:
     L.sgz_spectrogram_overview_cross_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, vp, u32, u32, vp, C.POINTER(PcmTiming)]
     L.sgz_pcm_stream_feed_overview_flux.argtypes = [vp, vp, sz, u32, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(PcmTiming)]
     L.sgz_spectrogram_overview_flux_pcm.argtypes = [C.POINTER(SpectrumConfig), vp, u32, u32, vp, sz, u32, vp, C.POINTER(PcmTiming)]
-    L.sgz_stage_level_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
-    L.sgz_level_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
-    L.sgz_level_columns_limits.restype = None
-    L.sgz_level_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_level_readout.argtypes = [vp, C.POINTER(LevelReading)]
-    L.sgz_stage_truepeak_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, u32, vp, vp, vp]
-    L.sgz_truepeak_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
-    L.sgz_truepeak_columns_limits.restype = None
     L.sgz_truepeak_taps.argtypes = [vp]
     L.sgz_truepeak_taps.restype = None
-    L.sgz_truepeak_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_truepeak_readout.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    fp = C.POINTER(LoudnessFilter)
-    L.sgz_stage_loudness_columns.argtypes = [vp, sz, u32, sz, fp, u64, u32, u32, C.c_int, u32, u32, vp, vp, vp]
-    L.sgz_loudness_columns_limits.argtypes = [fp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(sz)]
     L.sgz_loudness_filter_for_rate.argtypes = [C.c_double, fp]
     L.sgz_loudness_taps.argtypes = [fp, vp]
-    L.sgz_loudness_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_loudness_readout.argtypes = [vp, sz, u32, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgz_loudness_integrated.argtypes = [vp, sz, u32, vp, C.POINTER(C.c_double)]
-    L.sgz_stage_field_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
-    L.sgz_field_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
-    L.sgz_field_columns_limits.restype = None
     L.sgz_field_boundaries.argtypes = [vp]
     L.sgz_field_boundaries.restype = None
-    L.sgz_field_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_field_readout.argtypes = [vp, C.POINTER(FieldReading)]
-    bp = C.POINTER(BandFilter)
-    L.sgz_stage_band_columns.argtypes = [vp, sz, u32, sz, bp, u64, u32, u32, C.c_int, u32, u32, vp, vp, vp]
-    L.sgz_band_columns_limits.argtypes = [bp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(sz)]
     L.sgz_band_filter_for_rate.argtypes = [C.c_double, C.c_double, C.c_double, bp]
     L.sgz_band_taps.argtypes = [bp, vp]
-    L.sgz_band_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_band_readout.argtypes = [vp, sz, u32, u32, vp, vp]
     L.sgz_band_colours.argtypes = [vp, sz, u32, u32, vp, vp, C.c_double, vp]
-    L.sgz_stage_hist_columns.argtypes = [vp, sz, u32, sz, u32, u32, C.c_int, u32, vp, vp, vp]
-    L.sgz_hist_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
-    L.sgz_hist_columns_limits.restype = None
     L.sgz_hist_edges.argtypes = [vp, vp]
     L.sgz_hist_edges.restype = None
-    L.sgz_hist_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_hist_percentile.argtypes = [vp, C.c_double, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgz_hist_readout.argtypes = [vp, C.POINTER(HistReading)]
-    rp = C.POINTER(RunParams)
-    L.sgz_stage_run_columns.argtypes = [vp, sz, u32, sz, rp, u32, u32, C.c_int, u32, u32, vp, vp, vp]
-    L.sgz_run_columns_limits.argtypes = [C.POINTER(u32), C.POINTER(u32)]
-    L.sgz_run_columns_limits.restype = None
     L.sgz_run_params_default.argtypes = [rp]
     L.sgz_run_params_default.restype = None
-    L.sgz_run_fold.argtypes = [vp, sz, u32, sz, sz, u32, vp]
     L.sgz_run_readout.argtypes = [vp, C.c_double, C.POINTER(RunReading)]
-    for lane in ("waveform", "level", "truepeak", "loudness", "field", "band", "hist", "run"):      # the eight column lanes of the PCM stream: one set of calls each
-        getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, {"loudness": fp, "band": bp, "run": rp}[lane], u32, vp, u64] if lane in ("loudness", "band", "run") else [vp, u32, vp, u64]
+    # the eight column lanes: what a lane's stage call takes between nsamples and m and its set call in front of m -- the filter or the
+    # thresholds by reference, and behind a filter the first index --, and whether the stage call takes `continued`
+    lanes = {"wave": ([], False), "level": ([], False), "truepeak": ([], True), "loudness": ([fp, u64], True), "field": ([], False),
+             "band": ([bp, u64], True), "hist": ([], False), "run": ([rp], True)}
+    for lane, (front, history) in lanes.items():
+        getattr(L, f"sgz_stage_{lane}_columns").argtypes = [vp, sz, u32, sz, *front, u32, u32, C.c_int, *([u32] if history else []), u32, vp, vp, vp]
+        limits = getattr(L, f"sgz_{lane}_columns_limits")
+        if len(front) == 2:                                             # (by the filter: a status, and the carry's bytes too)
+            limits.argtypes = [front[0], u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(sz)]
+        else:
+            limits.argtypes, limits.restype = [C.POINTER(u32), C.POINTER(u32)], None
+        if lane != "wave":
+            getattr(L, f"sgz_{lane}_fold").argtypes = [vp, sz, u32, sz, sz, u32, vp]
+        lane = "waveform" if lane == "wave" else lane                   # the PCM stream's calls: one set each
+        getattr(L, f"sgz_pcm_stream_set_{lane}").argtypes = [vp, *front[:1], u32, vp, u64]
         getattr(L, f"sgz_pcm_stream_{lane}_for").argtypes = [vp, sz, C.c_int]
         getattr(L, f"sgz_pcm_stream_{lane}_for").restype = u64
         getattr(L, f"sgz_pcm_stream_{lane}_state").argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
@@ -2273,50 +2255,63 @@ class PcmStream:
         return int(f.value)
 
 
+def _columns_limits(symbol: str):
+    s, t = C.c_uint32(0), C.c_uint32(0)
+    getattr(lib(), symbol)(C.byref(s), C.byref(t))
+    return int(s.value), int(t.value)
+
+
+def _by_ref(x):
+    return C.byref(x) if x is not None else None
+
+
+def _stage_columns(symbol: str, planar, channel_stride: int, cells: int, nsamples: int, front, m: int, held: int, flush, continued, slices: int, carry,
+                   out, stream) -> int:
+    """sgz_stage_<lane>_columns.  front: what the C call takes between nsamples and m; continued: None where the call has none"""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
+    history = () if continued is None else (int(bool(continued)),)
+    return getattr(lib(), symbol)(ptr(planar), channel_stride, cells, nsamples, *front, m, held, int(bool(flush)), *history, slices, ptr(carry), ptr(out),
+                                  C.c_void_p(s) if s else None)
+
+
+def _lane_fold(symbol: str, dtype, records: np.ndarray, out_columns: int, x0: int, x1: int | None) -> np.ndarray:
+    records = np.ascontiguousarray(records, dtype)
+    n, cells = records.shape
+    x1 = n if x1 is None else x1
+    out = np.zeros((max(min(out_columns, x1 - x0), 1), cells), dtype)
+    check(getattr(lib(), symbol)(_np_ptr(records), n, cells, x0, x1, out_columns, _np_ptr(out)))
+    return out[:min(out_columns, x1 - x0)]
+
+
 def wave_columns_limits():
     """sgz_wave_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples)"""
-    s, t = C.c_uint32(0), C.c_uint32(0)
-    lib().sgz_wave_columns_limits(C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return _columns_limits("sgz_wave_columns_limits")
 
 
 def stage_wave_columns(planar, channel_stride: int, channels: int, nsamples: int, m: int, held: int = 0, flush: bool = True, slices: int = 0,
                        carry=None, wave=None, stream=None) -> int:
     """sgz_stage_wave_columns as it is: planar / carry / wave -- cuda float32 tensors (their data pointers; any may be None where the call
     allows NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
-    return lib().sgz_stage_wave_columns(ptr(planar), channel_stride, channels, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(wave),
-                                        C.c_void_p(s) if s else None)
+    return _stage_columns("sgz_stage_wave_columns", planar, channel_stride, channels, nsamples, (), m, held, flush, None, slices, carry, wave, stream)
 
 
 def level_columns_limits():
     """sgz_level_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples per row)"""
-    s, t = C.c_uint32(0), C.c_uint32(0)
-    lib().sgz_level_columns_limits(C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return _columns_limits("sgz_level_columns_limits")
 
 
 def stage_level_columns(planar, channel_stride: int, pairs: int, nsamples: int, m: int, held: int = 0, flush: bool = True, slices: int = 0,
                         carry=None, level=None, stream=None) -> int:
     """sgz_stage_level_columns as it is: planar / carry / level -- cuda tensors (their data pointers; any may be None where the call allows
     NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
-    return lib().sgz_stage_level_columns(ptr(planar), channel_stride, pairs, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(level),
-                                         C.c_void_p(s) if s else None)
+    return _stage_columns("sgz_stage_level_columns", planar, channel_stride, pairs, nsamples, (), m, held, flush, None, slices, carry, level, stream)
 
 
 def level_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_level_fold: LEVEL_DTYPE records [n, pairs], source columns [x0, x1) -> [min(out_columns, x1 - x0), pairs]"""
-    records = np.ascontiguousarray(records, LEVEL_DTYPE)
-    n, pairs = records.shape
-    x1 = n if x1 is None else x1
-    out = np.zeros((max(min(out_columns, x1 - x0), 1), pairs), LEVEL_DTYPE)
-    check(lib().sgz_level_fold(_np_ptr(records), n, pairs, x0, x1, out_columns, _np_ptr(out)))
-    return out[:min(out_columns, x1 - x0)]
+    return _lane_fold("sgz_level_fold", LEVEL_DTYPE, records, out_columns, x0, x1)
 
 
 def level_readout(record) -> dict:
@@ -2329,9 +2324,7 @@ def level_readout(record) -> dict:
 
 def field_columns_limits():
     """sgz_field_columns_limits: (the switch-over between the tile form and the sliced form, the tile's sample frames)"""
-    s, t = C.c_uint32(0), C.c_uint32(0)
-    lib().sgz_field_columns_limits(C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return _columns_limits("sgz_field_columns_limits")
 
 
 def field_boundaries() -> np.ndarray:
@@ -2345,21 +2338,12 @@ def stage_field_columns(planar, channel_stride: int, pairs: int, nsamples: int, 
                         carry=None, field=None, stream=None) -> int:
     """sgz_stage_field_columns as it is: planar / carry / field -- cuda tensors (their data pointers; any may be None where the call allows
     NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
-    return lib().sgz_stage_field_columns(ptr(planar), channel_stride, pairs, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(field),
-                                         C.c_void_p(s) if s else None)
+    return _stage_columns("sgz_stage_field_columns", planar, channel_stride, pairs, nsamples, (), m, held, flush, None, slices, carry, field, stream)
 
 
 def field_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_field_fold: FIELD_DTYPE records [n, pairs], source columns [x0, x1) -> [min(out_columns, x1 - x0), pairs]"""
-    records = np.ascontiguousarray(records, FIELD_DTYPE)
-    n, pairs = records.shape
-    x1 = n if x1 is None else x1
-    out = np.zeros((max(min(out_columns, x1 - x0), 1), pairs), FIELD_DTYPE)
-    check(lib().sgz_field_fold(_np_ptr(records), n, pairs, x0, x1, out_columns, _np_ptr(out)))
-    return out[:min(out_columns, x1 - x0)]
+    return _lane_fold("sgz_field_fold", FIELD_DTYPE, records, out_columns, x0, x1)
 
 
 def field_readout(record) -> dict:
@@ -2373,9 +2357,7 @@ def field_readout(record) -> dict:
 
 def hist_columns_limits():
     """sgz_hist_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples)"""
-    s, t = C.c_uint32(0), C.c_uint32(0)
-    lib().sgz_hist_columns_limits(C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return _columns_limits("sgz_hist_columns_limits")
 
 
 def hist_edges():
@@ -2389,21 +2371,12 @@ def stage_hist_columns(planar, channel_stride: int, channels: int, nsamples: int
                        carry=None, hist=None, stream=None) -> int:
     """sgz_stage_hist_columns as it is: planar / carry / hist -- cuda tensors (their data pointers; any may be None where the call allows
     NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
-    return lib().sgz_stage_hist_columns(ptr(planar), channel_stride, channels, nsamples, m, held, int(bool(flush)), slices, ptr(carry), ptr(hist),
-                                        C.c_void_p(s) if s else None)
+    return _stage_columns("sgz_stage_hist_columns", planar, channel_stride, channels, nsamples, (), m, held, flush, None, slices, carry, hist, stream)
 
 
 def hist_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_hist_fold: HIST_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels]"""
-    records = np.ascontiguousarray(records, HIST_DTYPE)
-    n, channels = records.shape
-    x1 = n if x1 is None else x1
-    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), HIST_DTYPE)
-    check(lib().sgz_hist_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
-    return out[:min(out_columns, x1 - x0)]
+    return _lane_fold("sgz_hist_fold", HIST_DTYPE, records, out_columns, x0, x1)
 
 
 def hist_percentile(record, q: float):
@@ -2431,30 +2404,19 @@ def run_params_default() -> RunParams:
 
 def run_columns_limits():
     """sgz_run_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples)"""
-    s, t = C.c_uint32(0), C.c_uint32(0)
-    lib().sgz_run_columns_limits(C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return _columns_limits("sgz_run_columns_limits")
 
 
 def stage_run_columns(planar, channel_stride: int, channels: int, nsamples: int, params, m: int, held: int = 0, flush: bool = True,
                       continued: bool = False, slices: int = 0, carry=None, runs=None, stream=None) -> int:
     """sgz_stage_run_columns as it is: params -- a RunParams or None; planar / carry / runs -- cuda tensors (their data pointers; any may be
     None where the call allows NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
-    return lib().sgz_stage_run_columns(ptr(planar), channel_stride, channels, nsamples, C.byref(params) if params is not None else None, m, held,
-                                       int(bool(flush)), int(bool(continued)), slices, ptr(carry), ptr(runs), C.c_void_p(s) if s else None)
+    return _stage_columns("sgz_stage_run_columns", planar, channel_stride, channels, nsamples, (_by_ref(params),), m, held, flush, continued, slices, carry, runs, stream)
 
 
 def run_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_run_fold: RUN_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels], folded in order"""
-    records = np.ascontiguousarray(records, RUN_DTYPE)
-    n, channels = records.shape
-    x1 = n if x1 is None else x1
-    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), RUN_DTYPE)
-    check(lib().sgz_run_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
-    return out[:min(out_columns, x1 - x0)]
+    return _lane_fold("sgz_run_fold", RUN_DTYPE, records, out_columns, x0, x1)
 
 
 def run_readout(record, rate: float) -> dict:
@@ -2468,9 +2430,7 @@ def run_readout(record, rate: float) -> dict:
 
 def truepeak_columns_limits():
     """sgz_truepeak_columns_limits: (the switch-over between the tile form and the sliced form, the tile's samples)"""
-    s, t = C.c_uint32(0), C.c_uint32(0)
-    lib().sgz_truepeak_columns_limits(C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return _columns_limits("sgz_truepeak_columns_limits")
 
 
 def truepeak_taps() -> np.ndarray:
@@ -2484,21 +2444,12 @@ def stage_truepeak_columns(planar, channel_stride: int, channels: int, nsamples:
                            continued: bool = False, slices: int = 0, carry=None, peaks=None, stream=None) -> int:
     """sgz_stage_truepeak_columns as it is: planar / carry / peaks -- cuda tensors (their data pointers; any may be None where the call allows
     NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
-    return lib().sgz_stage_truepeak_columns(ptr(planar), channel_stride, channels, nsamples, m, held, int(bool(flush)), int(bool(continued)), slices,
-                                            ptr(carry), ptr(peaks), C.c_void_p(s) if s else None)
+    return _stage_columns("sgz_stage_truepeak_columns", planar, channel_stride, channels, nsamples, (), m, held, flush, continued, slices, carry, peaks, stream)
 
 
 def truepeak_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_truepeak_fold: TRUEPEAK_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels]"""
-    records = np.ascontiguousarray(records, TRUEPEAK_DTYPE)
-    n, channels = records.shape
-    x1 = n if x1 is None else x1
-    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), TRUEPEAK_DTYPE)
-    check(lib().sgz_truepeak_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
-    return out[:min(out_columns, x1 - x0)]
+    return _lane_fold("sgz_truepeak_fold", TRUEPEAK_DTYPE, records, out_columns, x0, x1)
 
 
 def truepeak_readout(record):
@@ -2546,21 +2497,13 @@ def stage_loudness_columns(planar, channel_stride: int, channels: int, nsamples:
                            flush: bool = True, continued: bool = False, slices: int = 0, carry=None, records=None, stream=None) -> int:
     """sgz_stage_loudness_columns as it is: planar / carry / records -- cuda tensors (their data pointers; any may be None where the call allows
     NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
-    return lib().sgz_stage_loudness_columns(ptr(planar), channel_stride, channels, nsamples, C.byref(filter) if filter is not None else None, first_index,
-                                            m, held, int(bool(flush)), int(bool(continued)), slices, ptr(carry), ptr(records), C.c_void_p(s) if s else None)
+    return _stage_columns("sgz_stage_loudness_columns", planar, channel_stride, channels, nsamples, (_by_ref(filter), first_index), m, held, flush, continued, slices,
+                          carry, records, stream)
 
 
 def loudness_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_loudness_fold: LOUDNESS_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels]"""
-    records = np.ascontiguousarray(records, LOUDNESS_DTYPE)
-    n, channels = records.shape
-    x1 = n if x1 is None else x1
-    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), LOUDNESS_DTYPE)
-    check(lib().sgz_loudness_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
-    return out[:min(out_columns, x1 - x0)]
+    return _lane_fold("sgz_loudness_fold", LOUDNESS_DTYPE, records, out_columns, x0, x1)
 
 
 def loudness_readout(records: np.ndarray, weights=None):
@@ -2618,21 +2561,13 @@ def stage_band_columns(planar, channel_stride: int, channels: int, nsamples: int
                        flush: bool = True, continued: bool = False, slices: int = 0, carry=None, records=None, stream=None) -> int:
     """sgz_stage_band_columns as it is: planar / carry / records -- cuda tensors (their data pointers; any may be None where the call allows
     NULL); returns the status.  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    ptr = lambda t: _buf_ptr(t) if t is not None else None                      # noqa: E731
-    return lib().sgz_stage_band_columns(ptr(planar), channel_stride, channels, nsamples, C.byref(filter) if filter is not None else None, first_index,
-                                        m, held, int(bool(flush)), int(bool(continued)), slices, ptr(carry), ptr(records), C.c_void_p(s) if s else None)
+    return _stage_columns("sgz_stage_band_columns", planar, channel_stride, channels, nsamples, (_by_ref(filter), first_index), m, held, flush, continued, slices,
+                          carry, records, stream)
 
 
 def band_fold(records: np.ndarray, out_columns: int, x0: int = 0, x1: int | None = None) -> np.ndarray:
     """sgz_band_fold: BAND_DTYPE records [n, channels], source columns [x0, x1) -> [min(out_columns, x1 - x0), channels]"""
-    records = np.ascontiguousarray(records, BAND_DTYPE)
-    n, channels = records.shape
-    x1 = n if x1 is None else x1
-    out = np.zeros((max(min(out_columns, x1 - x0), 1), channels), BAND_DTYPE)
-    check(lib().sgz_band_fold(_np_ptr(records), n, channels, x0, x1, out_columns, _np_ptr(out)))
-    return out[:min(out_columns, x1 - x0)]
+    return _lane_fold("sgz_band_fold", BAND_DTYPE, records, out_columns, x0, x1)
 
 
 def band_readout(records: np.ndarray, channel: int = 0):

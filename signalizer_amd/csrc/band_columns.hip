@@ -46,12 +46,10 @@ using namespace sgz;
 namespace {
 
 constexpr int kBdThreads = kTwinThreads;
-constexpr uint32_t kBdTile = kTwinTile;              // samples of a run tile (a segment longer than this is a tile of its own) and of a sum tile
 constexpr uint32_t kBdSwitch = 1024;             // the switch-over of the column sums: longer columns take the sliced form
 constexpr uint32_t kBdStage = 1024;              // samples of a tile that one round of the runs leaves in the staging planes
 constexpr uint32_t kBdMaxChannels = 64;
 constexpr uint32_t kBdBatch = 8;                 // loads a lane of the run kernel issues before it uses the first
-constexpr uint32_t kBdRun = 16;                  // samples of a lane in the sum tile
 constexpr uint32_t kBdComps = 16, kBdChainWords = 20;      // state components; doubles of a segment's three chains in LDS (4 + 8 + 8)
 constexpr double kBdTapScale = 1073741824.0;     // S = 30
 constexpr uint64_t kBdTapSumBound = uint64_t(1) << 36;     // 2^26 sum |C| < 2^62
@@ -325,7 +323,7 @@ size_t runLdsBytes(const sgz_band_filter &f)
 
 namespace sgz {
 
-size_t bandCarryBytes(const sgz_band_filter &f) { return sizeof(sgz_band_record) + size_t(f.W + f.L) * sizeof(int32_t); }
+size_t bandCarryBytes(const sgz_band_filter &f) { return twinCarryBytes<sgz_band_record>(f); }
 
 ColumnsShape bandColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
 {
@@ -338,46 +336,13 @@ sgz_status runBandColumns(const ColumnsShape &sh, const sgz_band_filter &f, cons
 {
     if (!sh.launch) return SGZ_OK;
     BandParams prm{};
-    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
-    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
-    prm.m = m; prm.held = held; prm.channels = channels; prm.continued = continued; prm.slices = sh.slices;
-    prm.W = f.W; prm.L = f.L; prm.logL = log2Of(f.L); prm.hist = f.W + f.L - 1;
-    prm.tile = runTileOf(f); prm.segs = prm.tile / f.L; prm.logSegs = log2Of(prm.segs); prm.lanesPer = uint32_t(kBdThreads) / prm.segs;
+    fillGrid(prm, sh, d_planar, channelStride, nsamples, m, held);
+    prm.channels = channels; prm.continued = continued;
+    fillTwin(prm, f, 3, channels, nsamples, firstIndex, carryIn, carryOut, d_out, scratch);
+    prm.logSegs = log2Of(prm.segs);
     prm.stage = kBdStage; prm.perRound = kBdStage / prm.segs; prm.logRound = log2Of(prm.perRound); prm.rounds = f.L / prm.perRound;
-    prm.tileWords = runTileWords(f);
-    prm.phase = uint32_t(firstIndex % f.L);
     prm.coef = coefOf(f);
-    prm.carryIn = static_cast<const uint8_t *>(carryIn); prm.carryOut = static_cast<uint8_t *>(carryOut);
-    prm.carryBytes = bandCarryBytes(f);
-    prm.q = static_cast<int32_t *>(scratch); prm.qStride = qStrideOf(nsamples);
-    prm.out = d_out;
-    prm.partial = reinterpret_cast<sgz_band_record *>(static_cast<uint8_t *>(scratch) + size_t(3) * prm.qStride * channels * sizeof(int32_t));
-    const uint64_t cells = sh.columns * channels;
-    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kBdThreads)), "band", "columns"); st != SGZ_OK) return st;
-    if (nsamples != 0) {
-        if (sgz_status st = tapsOnDevice(f, &prm.taps); st != SGZ_OK) return st;
-        const uint64_t tiles = (uint64_t(nsamples) + prm.phase + prm.tile - 1) / prm.tile;
-        if (sgz_status st = fitsOneLaunch(tiles, "band", "samples"); st != SGZ_OK) return st;
-        const size_t lds = runLdsBytes(f);
-        if (sgz_status st = grantRunLds<bandRunKernel>(lds); st != SGZ_OK) return st;
-        hipLaunchKernelGGL(bandRunKernel, dim3(unsigned(tiles), channels), dim3(kBdThreads), lds, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(historyKernel<BandParams>, dim3((prm.hist + 1 + kBdThreads - 1) / kBdThreads, channels), dim3(kBdThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        if (sh.slices == 0) {
-            prm.perTile = kBdTile / m;
-            prm.group = std::min(pow2AtLeast((m + kBdRun - 1) / kBdRun), 64u);
-            const uint64_t sumTiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-            hipLaunchKernelGGL((sumTileKernel<BandParams, BdAcc>), dim3(unsigned(sumTiles), channels), dim3(kBdThreads), 0, stream, prm);
-            SGZ_HIP(hipGetLastError());
-            return SGZ_OK;
-        }
-        hipLaunchKernelGGL((sumSliceKernel<BandParams, BdAcc>), dim3(unsigned(sh.columns), channels, sh.slices), dim3(kBdThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL((sumEmitKernel<BandParams, BdAcc>), dim3(unsigned(emitBlocks(cells, kBdThreads))), dim3(kBdThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchTwinLane<bandRunKernel, BdAcc>("band", prm, sh, f, channels, nsamples, m, runLdsBytes(f), tapsOnDevice, stream);
 }
 
 }  // namespace sgz
@@ -399,22 +364,16 @@ sgz_status sgz_stage_band_columns(const float *d_planar, size_t channel_stride, 
                                   sgz_band_record *d_records, void *stream)
 {
     const StageFront front{"sgz_stage_band_columns", "channels", kBdMaxChannels, "d_records", 16, true, 40};
-    // (the filter's check stands behind d_planar's: checkStageArgs)
-    if (sgz_status st = checkStageArgs(front, filterForDevice(filter, front.who), d_planar, channel_stride, channels, nsamples, m, held, continued, first_index, slices,
-                                       d_carry, d_records); st != SGZ_OK) return st;
-    const ColumnsShape sh = bandColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, continued, d_carry, d_records); st != SGZ_OK) return st;
-    if (nsamples) {                                                  // (the table before anything is launched: a refused filter writes nothing)
-        const int4 *taps = nullptr;
-        if (sgz_status st = tapsOnDevice(*filter, &taps); st != SGZ_OK) return st;
-    }
-    if (!sh.launch) return SGZ_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StageScratch mem(s);
-    const void *carryIn = nullptr;
-    if (sgz_status st = mem.get(front, sh, nsamples, held, continued, d_carry, bandCarryBytes(*filter) * channels, &carryIn); st != SGZ_OK) return st;
-    return runBandColumns(sh, *filter, d_planar, channel_stride, channels, nsamples, first_index, m, held, continued, carryIn, d_carry, d_records,
-                          mem.scratch.p, s);
+    // (the filter's check stands behind d_planar's: checkStageArgs.  The carry's size is read behind that check alone)
+    return stageColumns(front, filterForDevice(filter, front.who), d_planar, channel_stride, channels, nsamples, m, held, flush, continued, first_index, slices, d_carry,
+                        d_records, stream, bandColumnsShape, filter ? bandCarryBytes(*filter) * channels : 0,
+                        [&] {                                        // (the table before anything is launched: a refused filter writes nothing)
+                            const int4 *taps = nullptr;
+                            return nsamples ? tapsOnDevice(*filter, &taps) : SGZ_OK;
+                        },
+                        [&](const ColumnsShape &sh, const void *carryIn, void *scratch, hipStream_t s) {
+                            return runBandColumns(sh, *filter, d_planar, channel_stride, channels, nsamples, first_index, m, held, continued, carryIn, d_carry, d_records, scratch, s);
+                        });
 }
 
 // ---- host arithmetic ---------------------------------------------------------------------------------------------------------------------------

@@ -1,15 +1,18 @@
 // column_lanes.hpp -- what the eight column lanes (wave, level, true-peak, loudness, stereo-field, band, histogram, run: <lane>_columns.hip) have in common,
 // written once: the shape of a call, the column / tile / slice bounds, the aligned split and the staging of a row, the two quantisers, the
-// stage calls' front, the fold's frame, and the parts in which the loudness and the band lane are twins.  A lane's file holds what is its own:
-// its record, its accumulators, its kernels' bodies.  pcm.hip includes this for the lanes' entry points.
+// stage call from its argument checks to the lane's launches (stageColumns), the grid's fields of a kernel-argument struct (fillGrid), the
+// launch front of the six plain lanes (launchPlainLane), the fold's frame, and the parts in which the loudness and the band lane are twins:
+// their shared fields (fillTwin), their launch front (launchTwinLane), the history kernel and the column sums.  A lane's file holds what is
+// its own: its record, its accumulators, its kernels' bodies, the fields only it has.  pcm.hip includes this for the lanes' entry points.
 // A lane's kernel-argument struct keeps its own type and layout; the helpers here are templates on it and read the grid's fields by name:
-//   n, columns, closed (long); m, held, perTile, slices (uint32_t)
+//   planar, stride (size_t); n, columns, closed (long); m, held, perTile, slices (uint32_t)
 // Floating-point contraction: this header neither sets nor resets it.  loudness_columns.hip and band_columns.hip include it BEHIND their
 // `#pragma clang fp contract(off)`, so every template instantiated there was parsed without contraction; the other six files have no pragma,
 // and nothing here has a multiply feeding an add in floating point.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <limits>
 #include <mutex>
@@ -289,6 +292,62 @@ inline sgz_status fitsOneLaunch(uint64_t count, const char *lane, const char *wh
 // the emit launch: workgroups of `threads` over one lane per cell
 inline uint64_t emitBlocks(uint64_t cells, int threads) { return (cells + uint64_t(threads) - 1) / uint64_t(threads); }
 
+// the fields every lane's kernel-argument struct has under the same names
+template <class Params>
+void fillGrid(Params &prm, const ColumnsShape &sh, const float *d_planar, size_t channelStride, size_t nsamples, uint32_t m, uint32_t held)
+{
+    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
+    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
+    prm.m = m; prm.held = held; prm.slices = sh.slices;
+}
+
+// The launch front of the wave, level, field, true-peak, histogram and run lanes: the tile kernel alone -- setTile(prm) sets the tile form's
+// own fields, perTile among them --, or the slice kernel (samples arrive) and behind it the emit kernel, `emitLanes` threads per (column,
+// cell).  word: the lane's, for fitsOneLaunch
+template <class Params, class SetTile>
+sgz_status launchPlainLane(void (*tileKernel)(Params), void (*sliceKernel)(Params), void (*emitKernel)(Params), int threads, const char *word,
+                           Params &prm, const ColumnsShape &sh, uint32_t cells, size_t nsamples, uint32_t emitLanes, SetTile setTile, hipStream_t stream)
+{
+    if (nsamples != 0 && sh.slices == 0) {
+        setTile(prm);
+        const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
+        if (sgz_status st = fitsOneLaunch(tiles, word, "columns"); st != SGZ_OK) return st;
+        hipLaunchKernelGGL(tileKernel, dim3(unsigned(tiles), cells), dim3(threads), 0, stream, prm);
+        SGZ_HIP(hipGetLastError());
+        return SGZ_OK;
+    }
+    const uint64_t blocks = emitBlocks(sh.columns * cells * emitLanes, threads);
+    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, blocks), word, "columns"); st != SGZ_OK) return st;
+    if (nsamples != 0) {
+        hipLaunchKernelGGL(sliceKernel, dim3(unsigned(sh.columns), cells, sh.slices), dim3(threads), 0, stream, prm);
+        SGZ_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(emitKernel, dim3(unsigned(blocks)), dim3(threads), 0, stream, prm);
+    SGZ_HIP(hipGetLastError());
+    return SGZ_OK;
+}
+
+// The body of every sgz_stage_<lane>_columns, in the order that decides which refusal wins: the argument checks (filter: checkStageArgs), the
+// shape, the buffers, before() -- what must succeed before anything is launched: the twins' tap table --, then the stream-ordered memory and
+// run(sh, carryIn, scratch, stream), the lane's run<Lane>Columns.  carryBytes: of the whole carry (used behind the checks alone)
+inline sgz_status noStep() { return SGZ_OK; }
+template <class Shape, class Before, class Run>
+sgz_status stageColumns(const StageFront &front, sgz_status filter, const float *d_planar, size_t channelStride, uint32_t cells, size_t nsamples,
+                        uint32_t m, uint32_t held, int flush, uint32_t continued, uint64_t firstIndex, uint32_t slices, const void *d_carry,
+                        const void *d_out, void *stream, Shape shape, size_t carryBytes, Before before, Run run)
+{
+    if (sgz_status st = checkStageArgs(front, filter, d_planar, channelStride, cells, nsamples, m, held, continued, firstIndex, slices, d_carry, d_out); st != SGZ_OK) return st;
+    const ColumnsShape sh = shape(cells, nsamples, m, held, flush, slices);
+    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, continued, d_carry, d_out); st != SGZ_OK) return st;
+    if (sgz_status st = before(); st != SGZ_OK) return st;
+    if (!sh.launch) return SGZ_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    StageScratch mem(s);
+    const void *carryIn = nullptr;
+    if (sgz_status st = mem.get(front, sh, nsamples, held, continued, d_carry, carryBytes, &carryIn); st != SGZ_OK) return st;
+    return run(sh, carryIn, mem.scratch.p, s);
+}
+
 // The frame of every sgz_<lane>_fold: out[b][c] = the fold of source columns [bound(b), bound(b + 1)) of cell c.  fits(first, count, stride)
 // says whether the 32-bit tallies of records first[0], first[stride], .. hold their sum -- asked of every output first: a refusal writes
 // nothing --, sum(first, count, stride) is the folded record.  tooMany: what the refusal's message says behind "2^32 - 1"
@@ -321,6 +380,7 @@ sgz_status foldColumns(const char *who, const char *cellsWord, const char *tooMa
 // store(record *)
 constexpr int kTwinThreads = 256;
 constexpr uint32_t kTwinTile = 4096;             // samples of a run tile (a segment longer than this is a tile of its own) and of a sum tile
+constexpr uint32_t kTwinRun = 16;                // samples of a lane in the sum tile
 constexpr uint32_t kTwinMaxW = 65536, kTwinMinL = 16;
 constexpr uint32_t kTwinDeviceMaxW = 16384;      // the halo and a tile fit the 160 KiB of LDS up to here
 
@@ -369,6 +429,9 @@ sgz_status deviceTaps(const Filter &f, uint32_t comps, bool (*build)(const Filte
     *out = t.d;
     return SGZ_OK;
 }
+
+// a channel's carry (sgz::<lane>CarryBytes)
+template <class Record, class Filter> size_t twinCarryBytes(const Filter &f) { return sizeof(Record) + size_t(f.W + f.L) * sizeof(int32_t); }
 
 // the run tile: T = max(4096, L) samples; q rows of a call's samples; the LDS words of the halo and the tile, padding included
 template <class Filter> uint32_t runTileOf(const Filter &f) { return f.L > kTwinTile ? f.L : kTwinTile; }
@@ -505,6 +568,56 @@ sumEmitKernel(const Params prm)
     Acc k{};
     for (uint32_t s = 0; s < prm.slices; ++s) k.add(prm.partial[size_t(s) * perSlice + at]);
     emitSums(prm, col, ch, k);
+}
+
+// The fields the two lanes' kernel arguments share, beside the grid's.  scratch: `planes` q planes of [channels][qStride] words (one for
+// loudness, three for band), the partial records behind them
+template <class Params, class Filter>
+void fillTwin(Params &prm, const Filter &f, uint32_t planes, uint32_t channels, size_t nsamples, uint64_t firstIndex, const void *carryIn, void *carryOut,
+              typename Params::Record *d_out, void *scratch)
+{
+    prm.W = f.W; prm.L = f.L; prm.logL = log2Of(f.L); prm.hist = f.W + f.L - 1;
+    prm.tile = runTileOf(f); prm.segs = prm.tile / f.L; prm.lanesPer = uint32_t(kTwinThreads) / prm.segs;
+    prm.tileWords = runTileWords(f);
+    prm.phase = uint32_t(firstIndex % f.L);
+    prm.carryIn = static_cast<const uint8_t *>(carryIn); prm.carryOut = static_cast<uint8_t *>(carryOut);
+    prm.carryBytes = twinCarryBytes<typename Params::Record>(f);
+    prm.q = static_cast<int32_t *>(scratch); prm.qStride = qStrideOf(nsamples);
+    prm.out = d_out;
+    prm.partial = reinterpret_cast<typename Params::Record *>(static_cast<uint8_t *>(scratch) + size_t(planes) * prm.qStride * channels * sizeof(int32_t));
+}
+
+// The two lanes' launch front: RunKernel over the sample tiles (lds: its dynamic LDS; taps(f, &prm.taps): the lane's table on the device),
+// the history, then the column sums in the tile form or in slices; a flush without samples is the emit kernel alone
+template <auto RunKernel, class Acc, class Params, class Filter, class Taps>
+sgz_status launchTwinLane(const char *word, Params &prm, const ColumnsShape &sh, const Filter &f, uint32_t channels, size_t nsamples, uint32_t m,
+                          size_t lds, Taps taps, hipStream_t stream)
+{
+    const uint64_t blocks = emitBlocks(sh.columns * channels, kTwinThreads);
+    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, blocks), word, "columns"); st != SGZ_OK) return st;
+    if (nsamples != 0) {
+        if (sgz_status st = taps(f, &prm.taps); st != SGZ_OK) return st;
+        const uint64_t tiles = (uint64_t(nsamples) + prm.phase + prm.tile - 1) / prm.tile;
+        if (sgz_status st = fitsOneLaunch(tiles, word, "samples"); st != SGZ_OK) return st;
+        if (sgz_status st = grantRunLds<RunKernel>(lds); st != SGZ_OK) return st;
+        hipLaunchKernelGGL(RunKernel, dim3(unsigned(tiles), channels), dim3(kTwinThreads), lds, stream, prm);
+        SGZ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(historyKernel<Params>, dim3((prm.hist + 1 + kTwinThreads - 1) / kTwinThreads, channels), dim3(kTwinThreads), 0, stream, prm);
+        SGZ_HIP(hipGetLastError());
+        if (sh.slices == 0) {
+            prm.perTile = kTwinTile / m;
+            prm.group = std::min(pow2AtLeast((m + kTwinRun - 1) / kTwinRun), 64u);
+            const uint64_t sumTiles = (sh.columns + prm.perTile - 1) / prm.perTile;
+            hipLaunchKernelGGL((sumTileKernel<Params, Acc>), dim3(unsigned(sumTiles), channels), dim3(kTwinThreads), 0, stream, prm);
+            SGZ_HIP(hipGetLastError());
+            return SGZ_OK;
+        }
+        hipLaunchKernelGGL((sumSliceKernel<Params, Acc>), dim3(unsigned(sh.columns), channels, sh.slices), dim3(kTwinThreads), 0, stream, prm);
+        SGZ_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL((sumEmitKernel<Params, Acc>), dim3(unsigned(blocks)), dim3(kTwinThreads), 0, stream, prm);
+    SGZ_HIP(hipGetLastError());
+    return SGZ_OK;
 }
 
 }  // namespace sgz

@@ -318,28 +318,12 @@ sgz_status runFieldColumns(const ColumnsShape &sh, const float *d_planar, size_t
 {
     if (!sh.launch) return SGZ_OK;
     FieldParams prm{};
-    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
-    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
-    prm.m = m; prm.held = held; prm.pairs = pairs; prm.slices = sh.slices;
+    fillGrid(prm, sh, d_planar, channelStride, nsamples, m, held);
+    prm.pairs = pairs;
     prm.carryIn = carryIn; prm.carryOut = carryOut;
     prm.field = d_field; prm.partial = static_cast<sgz_field_record *>(scratch);
-    const uint64_t lanes = sh.columns * pairs * 32;
-    if (nsamples != 0 && sh.slices == 0) {
-        prm.perTile = kFdTile / m;
-        const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (sgz_status st = fitsOneLaunch(tiles, "field", "columns"); st != SGZ_OK) return st;
-        hipLaunchKernelGGL(fieldTileKernel, dim3(unsigned(tiles), pairs), dim3(kFdThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(lanes, kFdThreads)), "field", "columns"); st != SGZ_OK) return st;
-    if (nsamples != 0) {
-        hipLaunchKernelGGL(fieldSliceKernel, dim3(unsigned(sh.columns), pairs, sh.slices), dim3(kFdThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(fieldEmitKernel, dim3(unsigned(emitBlocks(lanes, kFdThreads))), dim3(kFdThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchPlainLane(fieldTileKernel, fieldSliceKernel, fieldEmitKernel, kFdThreads, "field", prm, sh, pairs, nsamples, 32,
+                           [m](FieldParams &p) { p.perTile = kFdTile / m; }, stream);
 }
 
 }  // namespace sgz
@@ -358,15 +342,10 @@ sgz_status sgz_stage_field_columns(const float *d_planar, size_t channel_stride,
                                    int flush, uint32_t slices, sgz_field_record *d_carry, sgz_field_record *d_field, void *stream)
 {
     const StageFront front{"sgz_stage_field_columns", "pairs", kFdMaxPairs, "d_field", 16, false, 62};
-    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, pairs, nsamples, m, held, 0, 0, slices, d_carry, d_field); st != SGZ_OK) return st;
-    const ColumnsShape sh = fieldColumnsShape(pairs, nsamples, m, held, flush, slices);
-    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, 0, d_carry, d_field); st != SGZ_OK) return st;
-    if (!sh.launch) return SGZ_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StageScratch mem(s);
-    const void *carryIn = nullptr;
-    if (sgz_status st = mem.get(front, sh, nsamples, held, 0, d_carry, size_t(pairs) * sizeof(sgz_field_record), &carryIn); st != SGZ_OK) return st;
-    return runFieldColumns(sh, d_planar, channel_stride, pairs, nsamples, m, held, static_cast<const sgz_field_record *>(carryIn), d_carry, d_field, mem.scratch.p, s);
+    return stageColumns(front, SGZ_OK, d_planar, channel_stride, pairs, nsamples, m, held, flush, 0, 0, slices, d_carry, d_field, stream, fieldColumnsShape,
+                        size_t(pairs) * sizeof(sgz_field_record), noStep, [&](const ColumnsShape &sh, const void *carryIn, void *scratch, hipStream_t s) {
+                            return runFieldColumns(sh, d_planar, channel_stride, pairs, nsamples, m, held, static_cast<const sgz_field_record *>(carryIn), d_carry, d_field, scratch, s);
+                        });
 }
 
 sgz_status sgz_field_fold(const sgz_field_record *in, size_t n, uint32_t pairs, size_t x0, size_t x1, uint32_t out_columns, sgz_field_record *out)

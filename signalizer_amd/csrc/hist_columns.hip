@@ -338,29 +338,14 @@ sgz_status runHistColumns(const ColumnsShape &sh, const float *d_planar, size_t 
 {
     if (!sh.launch) return SGZ_OK;
     HistParams prm{};
-    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
-    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
-    prm.m = m; prm.held = held; prm.channels = channels; prm.slices = sh.slices;
+    fillGrid(prm, sh, d_planar, channelStride, nsamples, m, held);
+    prm.channels = channels;
     prm.carryIn = carryIn; prm.carryOut = carryOut;
     prm.hist = d_hist; prm.partial = static_cast<sgz_hist_record *>(scratch);
-    const uint64_t lanes = sh.columns * channels * kHsWords;
-    if (nsamples != 0 && sh.slices == 0) {
-        prm.perTile = std::min(kHsTile / m, kHsTables);                    // (a tile of very short columns has fewer than kHsTile samples)
-        prm.group = pow2AtLeast((m + kHsPerLane - 1) / kHsPerLane);         // (1 .. 64: at most sixteen samples a lane)
-        const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (sgz_status st = fitsOneLaunch(tiles, "histogram", "columns"); st != SGZ_OK) return st;
-        hipLaunchKernelGGL(histTileKernel, dim3(unsigned(tiles), channels), dim3(kHsThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(lanes, kHsThreads)), "histogram", "columns"); st != SGZ_OK) return st;
-    if (nsamples != 0) {
-        hipLaunchKernelGGL(histSliceKernel, dim3(unsigned(sh.columns), channels, sh.slices), dim3(kHsThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(histEmitKernel, dim3(unsigned(emitBlocks(lanes, kHsThreads))), dim3(kHsThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchPlainLane(histTileKernel, histSliceKernel, histEmitKernel, kHsThreads, "histogram", prm, sh, channels, nsamples, kHsWords, [m](HistParams &p) {
+        p.perTile = std::min(kHsTile / m, kHsTables);                      // (a tile of very short columns has fewer than kHsTile samples)
+        p.group = pow2AtLeast((m + kHsPerLane - 1) / kHsPerLane);          // (1 .. 64: at most sixteen samples a lane)
+    }, stream);
 }
 
 }  // namespace sgz
@@ -377,15 +362,10 @@ sgz_status sgz_stage_hist_columns(const float *d_planar, size_t channel_stride, 
                                   int flush, uint32_t slices, sgz_hist_record *d_carry, sgz_hist_record *d_hist, void *stream)
 {
     const StageFront front{"sgz_stage_hist_columns", "channels", kHsMaxChannels, "d_hist", 16, false, 62};
-    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, channels, nsamples, m, held, 0, 0, slices, d_carry, d_hist); st != SGZ_OK) return st;
-    const ColumnsShape sh = histColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, 0, d_carry, d_hist); st != SGZ_OK) return st;
-    if (!sh.launch) return SGZ_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StageScratch mem(s);
-    const void *carryIn = nullptr;
-    if (sgz_status st = mem.get(front, sh, nsamples, held, 0, d_carry, size_t(channels) * sizeof(sgz_hist_record), &carryIn); st != SGZ_OK) return st;
-    return runHistColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, static_cast<const sgz_hist_record *>(carryIn), d_carry, d_hist, mem.scratch.p, s);
+    return stageColumns(front, SGZ_OK, d_planar, channel_stride, channels, nsamples, m, held, flush, 0, 0, slices, d_carry, d_hist, stream, histColumnsShape,
+                        size_t(channels) * sizeof(sgz_hist_record), noStep, [&](const ColumnsShape &sh, const void *carryIn, void *scratch, hipStream_t s) {
+                            return runHistColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, static_cast<const sgz_hist_record *>(carryIn), d_carry, d_hist, scratch, s);
+                        });
 }
 
 void sgz_hist_edges(uint32_t lo[SGZ_HIST_BUCKETS], uint32_t hi[SGZ_HIST_BUCKETS])

@@ -333,29 +333,14 @@ sgz_status runLevelColumns(const ColumnsShape &sh, const float *d_planar, size_t
 {
     if (!sh.launch) return SGZ_OK;
     LevelParams prm{};
-    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
-    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
-    prm.m = m; prm.held = held; prm.pairs = pairs; prm.slices = sh.slices;
+    fillGrid(prm, sh, d_planar, channelStride, nsamples, m, held);
+    prm.pairs = pairs;
     prm.carryIn = carryIn; prm.carryOut = carryOut;
     prm.level = d_level; prm.partial = static_cast<sgz_level_record *>(scratch);
-    const uint64_t cells = sh.columns * pairs;
-    if (nsamples != 0 && sh.slices == 0) {
-        prm.perTile = kLvTile / m;
-        prm.group = pow2AtLeast((m + kLvPerLane - 1) / kLvPerLane);   // (1 .. 64: at most sixteen sample frames a lane)
-        const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (sgz_status st = fitsOneLaunch(tiles, "level", "columns"); st != SGZ_OK) return st;
-        hipLaunchKernelGGL(levelTileKernel, dim3(unsigned(tiles), pairs), dim3(kLvThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kLvThreads)), "level", "columns"); st != SGZ_OK) return st;
-    if (nsamples != 0) {
-        hipLaunchKernelGGL(levelSliceKernel, dim3(unsigned(sh.columns), pairs, sh.slices), dim3(kLvThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(levelEmitKernel, dim3(unsigned(emitBlocks(cells, kLvThreads))), dim3(kLvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchPlainLane(levelTileKernel, levelSliceKernel, levelEmitKernel, kLvThreads, "level", prm, sh, pairs, nsamples, 1, [m](LevelParams &p) {
+        p.perTile = kLvTile / m;
+        p.group = pow2AtLeast((m + kLvPerLane - 1) / kLvPerLane);     // (1 .. 64: at most sixteen sample frames a lane)
+    }, stream);
 }
 
 }  // namespace sgz
@@ -372,15 +357,10 @@ sgz_status sgz_stage_level_columns(const float *d_planar, size_t channel_stride,
                                    int flush, uint32_t slices, sgz_level_record *d_carry, sgz_level_record *d_level, void *stream)
 {
     const StageFront front{"sgz_stage_level_columns", "pairs", kLvMaxPairs, "d_level", 16, false, 62};
-    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, pairs, nsamples, m, held, 0, 0, slices, d_carry, d_level); st != SGZ_OK) return st;
-    const ColumnsShape sh = levelColumnsShape(pairs, nsamples, m, held, flush, slices);
-    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, 0, d_carry, d_level); st != SGZ_OK) return st;
-    if (!sh.launch) return SGZ_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StageScratch mem(s);
-    const void *carryIn = nullptr;
-    if (sgz_status st = mem.get(front, sh, nsamples, held, 0, d_carry, size_t(pairs) * sizeof(sgz_level_record), &carryIn); st != SGZ_OK) return st;
-    return runLevelColumns(sh, d_planar, channel_stride, pairs, nsamples, m, held, static_cast<const sgz_level_record *>(carryIn), d_carry, d_level, mem.scratch.p, s);
+    return stageColumns(front, SGZ_OK, d_planar, channel_stride, pairs, nsamples, m, held, flush, 0, 0, slices, d_carry, d_level, stream, levelColumnsShape,
+                        size_t(pairs) * sizeof(sgz_level_record), noStep, [&](const ColumnsShape &sh, const void *carryIn, void *scratch, hipStream_t s) {
+                            return runLevelColumns(sh, d_planar, channel_stride, pairs, nsamples, m, held, static_cast<const sgz_level_record *>(carryIn), d_carry, d_level, scratch, s);
+                        });
 }
 
 sgz_status sgz_level_fold(const sgz_level_record *in, size_t n, uint32_t pairs, size_t x0, size_t x1, uint32_t out_columns, sgz_level_record *out)

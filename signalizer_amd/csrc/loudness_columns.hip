@@ -48,11 +48,9 @@ using namespace sgz;
 namespace {
 
 constexpr int kLdThreads = kTwinThreads;
-constexpr uint32_t kLdTile = kTwinTile;              // samples of a run tile (a segment longer than this is a tile of its own) and of a sum tile
 constexpr uint32_t kLdSwitch = 1024;             // the switch-over of the column sums: longer columns take the sliced form
 constexpr uint32_t kLdMaxChannels = 64;
 constexpr uint32_t kLdBatch = 8;                 // loads a lane of the run kernel issues before it uses the first
-constexpr uint32_t kLdRun = 16;                  // samples of a lane in the sum tile
 constexpr double kLdTapScale = 4294967296.0;     // S = 32
 constexpr uint64_t kLdTapSumBound = uint64_t(1) << 36;     // 2^26 sum |C| < 2^62
 static_assert(sizeof(sgz_loudness_record) == 32 && sizeof(sgz_loudness_filter) == 88, "sgz.h documents 32 and 88 bytes");
@@ -269,7 +267,7 @@ size_t runLdsBytes(const sgz_loudness_filter &f)
 
 namespace sgz {
 
-size_t loudnessCarryBytes(const sgz_loudness_filter &f) { return sizeof(sgz_loudness_record) + size_t(f.W + f.L) * sizeof(int32_t); }
+size_t loudnessCarryBytes(const sgz_loudness_filter &f) { return twinCarryBytes<sgz_loudness_record>(f); }
 
 ColumnsShape loudnessColumnsShape(uint32_t channels, size_t nsamples, uint32_t m, uint32_t held, int flush, uint32_t slices)
 {
@@ -282,45 +280,11 @@ sgz_status runLoudnessColumns(const ColumnsShape &sh, const sgz_loudness_filter 
 {
     if (!sh.launch) return SGZ_OK;
     LoudnessParams prm{};
-    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
-    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
-    prm.m = m; prm.held = held; prm.channels = channels; prm.continued = continued; prm.slices = sh.slices;
-    prm.W = f.W; prm.L = f.L; prm.logL = log2Of(f.L); prm.hist = f.W + f.L - 1;
-    prm.tile = runTileOf(f); prm.segs = prm.tile / f.L; prm.lanesPer = uint32_t(kLdThreads) / prm.segs;
-    prm.tileWords = runTileWords(f);
-    prm.phase = uint32_t(firstIndex % f.L);
+    fillGrid(prm, sh, d_planar, channelStride, nsamples, m, held);
+    prm.channels = channels; prm.continued = continued;
+    fillTwin(prm, f, 1, channels, nsamples, firstIndex, carryIn, carryOut, d_out, scratch);
     prm.coef = coefOf(f);
-    prm.carryIn = static_cast<const uint8_t *>(carryIn); prm.carryOut = static_cast<uint8_t *>(carryOut);
-    prm.carryBytes = loudnessCarryBytes(f);
-    prm.q = static_cast<int32_t *>(scratch); prm.qStride = qStrideOf(nsamples);
-    prm.out = d_out;
-    prm.partial = reinterpret_cast<sgz_loudness_record *>(static_cast<uint8_t *>(scratch) + prm.qStride * channels * sizeof(int32_t));
-    const uint64_t cells = sh.columns * channels;
-    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kLdThreads)), "loudness", "columns"); st != SGZ_OK) return st;
-    if (nsamples != 0) {
-        if (sgz_status st = tapsOnDevice(f, &prm.taps); st != SGZ_OK) return st;
-        const uint64_t tiles = (uint64_t(nsamples) + prm.phase + prm.tile - 1) / prm.tile;
-        if (sgz_status st = fitsOneLaunch(tiles, "loudness", "samples"); st != SGZ_OK) return st;
-        const size_t lds = runLdsBytes(f);
-        if (sgz_status st = grantRunLds<loudnessRunKernel>(lds); st != SGZ_OK) return st;
-        hipLaunchKernelGGL(loudnessRunKernel, dim3(unsigned(tiles), channels), dim3(kLdThreads), lds, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(historyKernel<LoudnessParams>, dim3((prm.hist + 1 + kLdThreads - 1) / kLdThreads, channels), dim3(kLdThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        if (sh.slices == 0) {
-            prm.perTile = kLdTile / m;
-            prm.group = std::min(pow2AtLeast((m + kLdRun - 1) / kLdRun), 64u);
-            const uint64_t sumTiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-            hipLaunchKernelGGL((sumTileKernel<LoudnessParams, LdAcc>), dim3(unsigned(sumTiles), channels), dim3(kLdThreads), 0, stream, prm);
-            SGZ_HIP(hipGetLastError());
-            return SGZ_OK;
-        }
-        hipLaunchKernelGGL((sumSliceKernel<LoudnessParams, LdAcc>), dim3(unsigned(sh.columns), channels, sh.slices), dim3(kLdThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL((sumEmitKernel<LoudnessParams, LdAcc>), dim3(unsigned(emitBlocks(cells, kLdThreads))), dim3(kLdThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchTwinLane<loudnessRunKernel, LdAcc>("loudness", prm, sh, f, channels, nsamples, m, runLdsBytes(f), tapsOnDevice, stream);
 }
 
 }  // namespace sgz
@@ -343,22 +307,16 @@ sgz_status sgz_stage_loudness_columns(const float *d_planar, size_t channel_stri
                                       sgz_loudness_record *d_records, void *stream)
 {
     const StageFront front{"sgz_stage_loudness_columns", "channels", kLdMaxChannels, "d_records", 16, true, 40};
-    // (the filter's check stands behind d_planar's: checkStageArgs)
-    if (sgz_status st = checkStageArgs(front, filterForDevice(filter, front.who), d_planar, channel_stride, channels, nsamples, m, held, continued, first_index, slices,
-                                       d_carry, d_records); st != SGZ_OK) return st;
-    const ColumnsShape sh = loudnessColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, continued, d_carry, d_records); st != SGZ_OK) return st;
-    if (nsamples) {                                                  // (the table before anything is launched: a refused filter writes nothing)
-        const int4 *taps = nullptr;
-        if (sgz_status st = tapsOnDevice(*filter, &taps); st != SGZ_OK) return st;
-    }
-    if (!sh.launch) return SGZ_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StageScratch mem(s);
-    const void *carryIn = nullptr;
-    if (sgz_status st = mem.get(front, sh, nsamples, held, continued, d_carry, loudnessCarryBytes(*filter) * channels, &carryIn); st != SGZ_OK) return st;
-    return runLoudnessColumns(sh, *filter, d_planar, channel_stride, channels, nsamples, first_index, m, held, continued, carryIn, d_carry, d_records,
-                              mem.scratch.p, s);
+    // (the filter's check stands behind d_planar's: checkStageArgs.  The carry's size is read behind that check alone)
+    return stageColumns(front, filterForDevice(filter, front.who), d_planar, channel_stride, channels, nsamples, m, held, flush, continued, first_index, slices, d_carry,
+                        d_records, stream, loudnessColumnsShape, filter ? loudnessCarryBytes(*filter) * channels : 0,
+                        [&] {                                        // (the table before anything is launched: a refused filter writes nothing)
+                            const int4 *taps = nullptr;
+                            return nsamples ? tapsOnDevice(*filter, &taps) : SGZ_OK;
+                        },
+                        [&](const ColumnsShape &sh, const void *carryIn, void *scratch, hipStream_t s) {
+                            return runLoudnessColumns(sh, *filter, d_planar, channel_stride, channels, nsamples, first_index, m, held, continued, carryIn, d_carry, d_records, scratch, s);
+                        });
 }
 
 // ---- host arithmetic ---------------------------------------------------------------------------------------------------------------------------

@@ -520,7 +520,7 @@ static sgz_status pcmLanePiece(sgz_pcm_stream &s, PcmLane &l, PcmSlot &sl, const
     return SGZ_OK;
 }
 
-// the tail every sgz_pcm_stream_set_<lane> shares behind its own checks: m, the caller's columns, the cursor at 0; a slot holds the
+// the tail of sgz_pcm_stream_set_<lane> (pcmLaneSet) behind its checks: m, the caller's columns, the cursor at 0; a slot holds the
 // ceil(chunk / m) + 1 columns a piece can close
 static void pcmLaneArm(sgz_pcm_stream &s, PcmLane &l, uint32_t m, void *out, uint64_t capacity)
 {
@@ -1240,158 +1240,120 @@ sgz_status sgz_spectrogram_overview_flux_pcm(const sgz_spectrum_config *cfg, con
                               [&](sgz_pcm_stream *s, uint64_t columns) { return sgz_pcm_stream_feed_overview_flux(s, pcm, nsamples, k, 1, flux_out, columns, &columns, timing); });
 }
 
+}  // extern "C"
+
 // ---- the lanes' calls ---------------------------------------------------------------------------------------------------------------------------
-// Every sgz_pcm_stream_set_<lane> keeps its own argument checks, and what arming and disarming mean for its carry; the tail is pcmLaneArm
-sgz_status sgz_pcm_stream_set_waveform(sgz_pcm_stream *s, uint32_t m, float *wave_out, uint64_t capacity_columns)
+namespace {
+
+// What sgz_pcm_stream_set_<lane> differs in.  leastM, leastWhy: "m >= leastM samples per column (leastWhy)" (1: any m); out, alignedTo: the
+// output argument's name and how its alignment is worded; cellBytes: of the carry per channel or pair (0: by the filter, made by the lane's own
+// `fresh`); history: the carry holds a history, which an arming unlike the last one begins anew; differs: what an open column refuses
+struct PcmLaneSetting {
+    PcmSinkId id;
+    uint32_t leastM;
+    const char *leastWhy, *out;
+    size_t align;
+    const char *alignedTo;
+    size_t cellBytes;
+    bool ofPairs, history;
+    const char *differs;
+};
+constexpr const char *kMDiffers = "m differs from";
+const PcmLaneSetting kSetWave{kSinkWave, 1, "", "wave_out", alignof(float), "float", 2 * sizeof(float), false, false, kMDiffers};
+const PcmLaneSetting kSetLevel{kSinkLevel, 1, "", "level_out", alignof(sgz_level_record), "8 bytes", sizeof(sgz_level_record), true, false, kMDiffers};
+const PcmLaneSetting kSetTruePeak{kSinkTruePeak, 1, "", "out", alignof(sgz_truepeak_record), "8 bytes", sizeof(sgz_truepeak_carry), false, true, kMDiffers};
+const PcmLaneSetting kSetLoudness{kSinkLoudness, 1, "", "out", alignof(sgz_loudness_record), "8 bytes", 0, false, true, "m or the filter differs from"};
+const PcmLaneSetting kSetField{kSinkField, 64, "a 528-byte record per pair for fewer would read back more than the samples", "field_out", alignof(sgz_field_record), "8 bytes", sizeof(sgz_field_record), true, false, kMDiffers};
+const PcmLaneSetting kSetBand{kSinkBand, 64, "a 64-byte record per channel for fewer would read back more than the samples", "out", alignof(sgz_band_record), "8 bytes", 0, false, true, "m or the filter differs from"};
+const PcmLaneSetting kSetHist{kSinkHist, 128, "a 448-byte record per channel for fewer than 112 samples would read back more than the samples", "hist_out", alignof(sgz_hist_record), "4 bytes", sizeof(sgz_hist_record), false, false, kMDiffers};
+const PcmLaneSetting kSetRun{kSinkRun, 32, "a 96-byte record per channel for fewer would read back more than the samples", "out", alignof(sgz_run_record), "4 bytes", sizeof(sgz_run_carry), false, true, "m or the params differ from"};
+
+// sgz_pcm_stream_set_<lane>, once.  keyCheck(who): the check of what the lane takes beside m (a filter, the thresholds), between the least m
+// and the output's checks; same(l): the lane is armed with this m (and filter, thresholds) already; fresh(l): what an arming unlike the last
+// one does of its own, behind every refusal (the key kept; the filter's carry).  The tail is pcmLaneArm
+template <class KeyCheck, class Same, class Fresh>
+sgz_status pcmLaneSet(sgz_pcm_stream *s, const PcmLaneSetting &d, uint32_t m, void *out, uint64_t capacity, KeyCheck keyCheck, Same same, Fresh fresh)
 {
     if (!s) return fail(SGZ_EINVAL, "null stream");
-    PcmLane &l = s->lane[kSinkWave];
+    PcmLane &l = s->lane[d.id];
     if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
-    if (!wave_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: null wave_out");
-    if (reinterpret_cast<uintptr_t>(wave_out) % alignof(float)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: wave_out is not aligned to float");
-    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_waveform: m differs from the open column's -- flush it (sgz_pcm_stream_flush_waveform), disarm or reset first");
-    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * 2 * sizeof(float)));
-    pcmLaneArm(*s, l, m, wave_out, capacity_columns);
+    const auto who = [&l] { return std::string("sgz_pcm_stream_set_") + l.call; };
+    if (m < d.leastM) return fail(SGZ_EINVAL, who() + ": m >= " + std::to_string(d.leastM) + " samples per column (" + d.leastWhy + ")");
+    if (sgz_status st = keyCheck(who); st != SGZ_OK) return st;
+    if (!out && capacity) return fail(SGZ_EINVAL, who() + ": null " + d.out);
+    if (reinterpret_cast<uintptr_t>(out) % d.align) return fail(SGZ_EINVAL, who() + ": " + d.out + " is not aligned to " + d.alignedTo);
+    const bool asBefore = same(l);
+    if (l.open && !asBefore)
+        return fail(SGZ_EINVAL, who() + ": " + d.differs + " the open column's -- flush it (sgz_pcm_stream_flush_" + l.call + "), disarm or reset first");
+    if (d.cellBytes && !l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * (d.ofPairs ? s->cfg.num_pairs : s->numChannels) * d.cellBytes));
+    if (!asBefore) {
+        if (sgz_status st = fresh(l); st != SGZ_OK) return st;
+        if (d.history) { l.continued = false; l.index = 0; }       // (the lane starts at the next sample, index 0, with an empty history; the same arming keeps it)
+    }
+    pcmLaneArm(*s, l, m, out, capacity);
     return SGZ_OK;
 }
 
-sgz_status sgz_pcm_stream_set_level(sgz_pcm_stream *s, uint32_t m, sgz_level_record *level_out, uint64_t capacity_columns)
+// ... the lanes that take m alone
+sgz_status pcmLaneSet(sgz_pcm_stream *s, const PcmLaneSetting &d, uint32_t m, void *out, uint64_t capacity)
 {
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    PcmLane &l = s->lane[kSinkLevel];
-    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
-    if (!level_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: null level_out");
-    if (reinterpret_cast<uintptr_t>(level_out) % alignof(sgz_level_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: level_out is not aligned to 8 bytes");
-    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_level: m differs from the open column's -- flush it (sgz_pcm_stream_flush_level), disarm or reset first");
-    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->cfg.num_pairs * sizeof(sgz_level_record)));
-    pcmLaneArm(*s, l, m, level_out, capacity_columns);
-    return SGZ_OK;
+    return pcmLaneSet(s, d, m, out, capacity, [](auto) { return SGZ_OK; }, [m](const PcmLane &l) { return l.m == m; }, [](PcmLane &) { return SGZ_OK; });
 }
 
-sgz_status sgz_pcm_stream_set_truepeak(sgz_pcm_stream *s, uint32_t m, sgz_truepeak_record *out, uint64_t capacity_columns)
+// ... and the loudness and the band lane.  kept: the stream's filter; limits, taps: the lane's sgz_<lane>_columns_limits and sgz_<lane>_taps;
+// rows: of the tap table (4 or 16)
+template <class Filter, class Limits, class Taps>
+sgz_status pcmTwinSet(sgz_pcm_stream *s, const PcmLaneSetting &d, Filter sgz_pcm_stream::*kept, const Filter *filter, Limits limits, Taps taps, uint32_t rows,
+                      uint32_t m, void *out, uint64_t capacity)
 {
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    PcmLane &l = s->lane[kSinkTruePeak];
-    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
-    if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: null out");
-    if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_truepeak_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: out is not aligned to 8 bytes");
-    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_truepeak: m differs from the open column's -- flush it (sgz_pcm_stream_flush_truepeak), disarm or reset first");
-    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * sizeof(sgz_truepeak_carry)));
-    if (m != l.m) l.continued = false;                          // (arming: the lane starts at the next sample with a zero history; the same m keeps it)
-    pcmLaneArm(*s, l, m, out, capacity_columns);
-    return SGZ_OK;
+    return pcmLaneSet(
+        s, d, m, out, capacity, [&](auto who) { return filter ? SGZ_OK : fail(SGZ_EINVAL, who() + ": null filter"); },
+        [&](const PcmLane &l) { return l.m == m && std::memcmp(&(s->*kept), filter, sizeof *filter) == 0; },
+        [&](PcmLane &l) {
+            // (what the stage call refuses, and the tap table: a refused filter arms nothing)
+            size_t bytes = 0;
+            if (sgz_status st = limits(filter, s->numChannels, nullptr, nullptr, &bytes); st != SGZ_OK) return st;
+            std::vector<int32_t> table(size_t(rows) * filter->W);
+            if (sgz_status st = taps(filter, table.data()); st != SGZ_OK) return st;
+            if (l.carryCap < 2 * bytes) {
+                // (both slots are idle between feeds, but a flush's launch may still read the old block: wait for it)
+                SGZ_HIP(hipStreamSynchronize(s->compute));
+                if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; l.carryCap = 0; }
+                SGZ_HIP(hipMalloc(&l.d_carry, 2 * bytes));
+                l.carryCap = 2 * bytes;
+            }
+            s->*kept = *filter;
+            l.cur = 0;
+            return SGZ_OK;
+        });
 }
+
+}  // namespace
+
+extern "C" {
+
+sgz_status sgz_pcm_stream_set_waveform(sgz_pcm_stream *s, uint32_t m, float *wave_out, uint64_t capacity_columns) { return pcmLaneSet(s, kSetWave, m, wave_out, capacity_columns); }
+sgz_status sgz_pcm_stream_set_level(sgz_pcm_stream *s, uint32_t m, sgz_level_record *level_out, uint64_t capacity_columns) { return pcmLaneSet(s, kSetLevel, m, level_out, capacity_columns); }
+sgz_status sgz_pcm_stream_set_truepeak(sgz_pcm_stream *s, uint32_t m, sgz_truepeak_record *out, uint64_t capacity_columns) { return pcmLaneSet(s, kSetTruePeak, m, out, capacity_columns); }
+sgz_status sgz_pcm_stream_set_field(sgz_pcm_stream *s, uint32_t m, sgz_field_record *field_out, uint64_t capacity_columns) { return pcmLaneSet(s, kSetField, m, field_out, capacity_columns); }
+sgz_status sgz_pcm_stream_set_hist(sgz_pcm_stream *s, uint32_t m, sgz_hist_record *hist_out, uint64_t capacity_columns) { return pcmLaneSet(s, kSetHist, m, hist_out, capacity_columns); }
 
 sgz_status sgz_pcm_stream_set_loudness(sgz_pcm_stream *s, const sgz_loudness_filter *filter, uint32_t m, sgz_loudness_record *out, uint64_t capacity_columns)
 {
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    PcmLane &l = s->lane[kSinkLoudness];
-    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
-    if (!filter) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: null filter");
-    if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: null out");
-    if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_loudness_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: out is not aligned to 8 bytes");
-    const bool same = l.m == m && std::memcmp(&s->ldFilter, filter, sizeof *filter) == 0;
-    if (l.open && !same) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_loudness: m or the filter differs from the open column's -- flush it (sgz_pcm_stream_flush_loudness), disarm or reset first");
-    if (!same) {
-        // (what the stage call refuses, and the tap table: a refused filter arms nothing)
-        size_t bytes = 0;
-        if (sgz_status st = sgz_loudness_columns_limits(filter, s->numChannels, nullptr, nullptr, &bytes); st != SGZ_OK) return st;
-        std::vector<int32_t> taps(size_t(4) * filter->W);
-        if (sgz_status st = sgz_loudness_taps(filter, taps.data()); st != SGZ_OK) return st;
-        if (l.carryCap < 2 * bytes) {
-            // (both slots are idle between feeds, but a flush's launch may still read the old block: wait for it)
-            SGZ_HIP(hipStreamSynchronize(s->compute));
-            if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; l.carryCap = 0; }
-            SGZ_HIP(hipMalloc(&l.d_carry, 2 * bytes));
-            l.carryCap = 2 * bytes;
-        }
-        s->ldFilter = *filter;
-        l.continued = false;                                       // (arming: the lane starts at the next sample, index 0, with a zero history)
-        l.index = 0; l.cur = 0;
-    }
-    pcmLaneArm(*s, l, m, out, capacity_columns);
-    return SGZ_OK;
-}
-
-sgz_status sgz_pcm_stream_set_field(sgz_pcm_stream *s, uint32_t m, sgz_field_record *field_out, uint64_t capacity_columns)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    PcmLane &l = s->lane[kSinkField];
-    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
-    if (m < 64) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_field: m >= 64 samples per column (a 528-byte record per pair for fewer would read back more than the samples)");
-    if (!field_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_field: null field_out");
-    if (reinterpret_cast<uintptr_t>(field_out) % alignof(sgz_field_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_field: field_out is not aligned to 8 bytes");
-    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_field: m differs from the open column's -- flush it (sgz_pcm_stream_flush_field), disarm or reset first");
-    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->cfg.num_pairs * sizeof(sgz_field_record)));
-    pcmLaneArm(*s, l, m, field_out, capacity_columns);
-    return SGZ_OK;
+    return pcmTwinSet(s, kSetLoudness, &sgz_pcm_stream::ldFilter, filter, sgz_loudness_columns_limits, sgz_loudness_taps, 4, m, out, capacity_columns);
 }
 
 sgz_status sgz_pcm_stream_set_band(sgz_pcm_stream *s, const sgz_band_filter *filter, uint32_t m, sgz_band_record *out, uint64_t capacity_columns)
 {
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    PcmLane &l = s->lane[kSinkBand];
-    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
-    if (m < 64) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: m >= 64 samples per column (a 64-byte record per channel for fewer would read back more than the samples)");
-    if (!filter) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: null filter");
-    if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: null out");
-    if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_band_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: out is not aligned to 8 bytes");
-    const bool same = l.m == m && std::memcmp(&s->bdFilter, filter, sizeof *filter) == 0;
-    if (l.open && !same) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_band: m or the filter differs from the open column's -- flush it (sgz_pcm_stream_flush_band), disarm or reset first");
-    if (!same) {
-        // (what the stage call refuses, and the tap table: a refused filter arms nothing)
-        size_t bytes = 0;
-        if (sgz_status st = sgz_band_columns_limits(filter, s->numChannels, nullptr, nullptr, &bytes); st != SGZ_OK) return st;
-        std::vector<int32_t> taps(size_t(16) * filter->W);
-        if (sgz_status st = sgz_band_taps(filter, taps.data()); st != SGZ_OK) return st;
-        if (l.carryCap < 2 * bytes) {
-            // (both slots are idle between feeds, but a flush's launch may still read the old block: wait for it)
-            SGZ_HIP(hipStreamSynchronize(s->compute));
-            if (l.d_carry) { (void)hipFree(l.d_carry); l.d_carry = nullptr; l.carryCap = 0; }
-            SGZ_HIP(hipMalloc(&l.d_carry, 2 * bytes));
-            l.carryCap = 2 * bytes;
-        }
-        s->bdFilter = *filter;
-        l.continued = false;                                       // (arming: the lane starts at the next sample, index 0, with a zero history)
-        l.index = 0; l.cur = 0;
-    }
-    pcmLaneArm(*s, l, m, out, capacity_columns);
-    return SGZ_OK;
-}
-
-sgz_status sgz_pcm_stream_set_hist(sgz_pcm_stream *s, uint32_t m, sgz_hist_record *hist_out, uint64_t capacity_columns)
-{
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    PcmLane &l = s->lane[kSinkHist];
-    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
-    if (m < 128) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_hist: m >= 128 samples per column (a 448-byte record per channel for fewer than 112 samples would read back more than the samples)");
-    if (!hist_out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_hist: null hist_out");
-    if (reinterpret_cast<uintptr_t>(hist_out) % alignof(sgz_hist_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_hist: hist_out is not aligned to 4 bytes");
-    if (l.open && m != l.m) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_hist: m differs from the open column's -- flush it (sgz_pcm_stream_flush_hist), disarm or reset first");
-    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * sizeof(sgz_hist_record)));
-    pcmLaneArm(*s, l, m, hist_out, capacity_columns);
-    return SGZ_OK;
+    return pcmTwinSet(s, kSetBand, &sgz_pcm_stream::bdFilter, filter, sgz_band_columns_limits, sgz_band_taps, 16, m, out, capacity_columns);
 }
 
 sgz_status sgz_pcm_stream_set_run(sgz_pcm_stream *s, const sgz_run_params *params, uint32_t m, sgz_run_record *out, uint64_t capacity_columns)
 {
-    if (!s) return fail(SGZ_EINVAL, "null stream");
-    PcmLane &l = s->lane[kSinkRun];
-    if (m == 0) { pcmLaneDisarm(l); return SGZ_OK; }
-    if (m < 32) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_run: m >= 32 samples per column (a 96-byte record per channel for fewer would read back more than the samples)");
-    if (sgz_status st = runParamsCheck(params, "sgz_pcm_stream_set_run"); st != SGZ_OK) return st;
-    if (!out && capacity_columns) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_run: null out");
-    if (reinterpret_cast<uintptr_t>(out) % alignof(sgz_run_record)) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_run: out is not aligned to 4 bytes");
-    const bool same = l.m == m && std::memcmp(&s->rnParams, params, sizeof *params) == 0;
-    if (l.open && !same) return fail(SGZ_EINVAL, "sgz_pcm_stream_set_run: m or the params differ from the open column's -- flush it (sgz_pcm_stream_flush_run), disarm or reset first");
-    if (!l.d_carry) SGZ_HIP(hipMalloc(&l.d_carry, size_t(2) * s->numChannels * sizeof(sgz_run_carry)));
-    if (!same) {
-        s->rnParams = *params;
-        l.continued = false;                                       // (arming: the lane starts at the next sample, index 0, with a history of marks)
-        l.index = 0;
-    }
-    pcmLaneArm(*s, l, m, out, capacity_columns);
-    return SGZ_OK;
+    return pcmLaneSet(
+        s, kSetRun, m, out, capacity_columns, [&](auto who) { return runParamsCheck(params, who().c_str()); },
+        [&](const PcmLane &l) { return l.m == m && std::memcmp(&s->rnParams, params, sizeof *params) == 0; },
+        [&](PcmLane &) { s->rnParams = *params; return SGZ_OK; });
 }
 
 uint64_t sgz_pcm_stream_waveform_for(const sgz_pcm_stream *s, size_t nsamples, int flush) { return pcmLaneFor(s, kSinkWave, nsamples, flush); }

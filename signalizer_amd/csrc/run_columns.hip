@@ -412,29 +412,13 @@ sgz_status runRunColumns(const ColumnsShape &sh, const sgz_run_params &p, const 
 {
     if (!sh.launch) return SGZ_OK;
     RunParams prm{};
-    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
-    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
-    prm.m = m; prm.held = held; prm.channels = channels; prm.continued = continued; prm.slices = sh.slices;
+    fillGrid(prm, sh, d_planar, channelStride, nsamples, m, held);
+    prm.channels = channels; prm.continued = continued;
     prm.hot = p.hot; prm.quiet = p.quiet;
     prm.carryIn = carryIn; prm.carryOut = carryOut;
     prm.runs = d_runs; prm.partial = static_cast<sgz_run_record *>(scratch);
-    const uint64_t cells = sh.columns * channels;
-    if (nsamples != 0 && sh.slices == 0) {
-        prm.perTile = kRnTile / m;
-        const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (sgz_status st = fitsOneLaunch(tiles, "run", "columns"); st != SGZ_OK) return st;
-        hipLaunchKernelGGL(runTileKernel, dim3(unsigned(tiles), channels), dim3(kRnThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kRnThreads)), "run", "columns"); st != SGZ_OK) return st;
-    if (nsamples != 0) {
-        hipLaunchKernelGGL(runSliceKernel, dim3(unsigned(sh.columns), channels, sh.slices), dim3(kRnThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(runEmitKernel, dim3(unsigned(emitBlocks(cells, kRnThreads))), dim3(kRnThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchPlainLane(runTileKernel, runSliceKernel, runEmitKernel, kRnThreads, "run", prm, sh, channels, nsamples, 1,
+                           [m](RunParams &t) { t.perTile = kRnTile / m; }, stream);
 }
 
 }  // namespace sgz
@@ -460,15 +444,11 @@ sgz_status sgz_stage_run_columns(const float *d_planar, size_t channel_stride, u
 {
     const StageFront front{"sgz_stage_run_columns", "channels", kRnMaxChannels, "d_runs", 16, true, 62};
     const sgz_status filter = d_planar ? checkParams(params, "sgz_stage_run_columns") : SGZ_OK;
-    if (sgz_status st = checkStageArgs(front, filter, d_planar, channel_stride, channels, nsamples, m, held, continued, 0, slices, d_carry, d_runs); st != SGZ_OK) return st;
-    const ColumnsShape sh = runColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, continued, d_carry, d_runs); st != SGZ_OK) return st;
-    if (!sh.launch) return SGZ_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StageScratch mem(s);
-    const void *carryIn = nullptr;
-    if (sgz_status st = mem.get(front, sh, nsamples, held, continued, d_carry, size_t(channels) * sizeof(sgz_run_carry), &carryIn); st != SGZ_OK) return st;
-    return runRunColumns(sh, *params, d_planar, channel_stride, channels, nsamples, m, held, continued, static_cast<const sgz_run_carry *>(carryIn), d_carry, d_runs, mem.scratch.p, s);
+    return stageColumns(front, filter, d_planar, channel_stride, channels, nsamples, m, held, flush, continued, 0, slices, d_carry, d_runs, stream, runColumnsShape,
+                        size_t(channels) * sizeof(sgz_run_carry), noStep, [&](const ColumnsShape &sh, const void *carryIn, void *scratch, hipStream_t s) {
+                            return runRunColumns(sh, *params, d_planar, channel_stride, channels, nsamples, m, held, continued, static_cast<const sgz_run_carry *>(carryIn), d_carry,
+                                                 d_runs, scratch, s);
+                        });
 }
 
 sgz_status sgz_run_fold(const sgz_run_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns, sgz_run_record *out)

@@ -371,30 +371,15 @@ sgz_status runTruePeakColumns(const ColumnsShape &sh, const float *d_planar, siz
 {
     if (!sh.launch) return SGZ_OK;
     TruePeakParams prm{};
-    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
-    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
-    prm.m = m; prm.held = held; prm.channels = channels; prm.continued = continued; prm.slices = sh.slices;
+    fillGrid(prm, sh, d_planar, channelStride, nsamples, m, held);
+    prm.channels = channels; prm.continued = continued;
     prm.carryIn = carryIn; prm.carryOut = carryOut;
     prm.peaks = d_peaks; prm.partial = static_cast<sgz_truepeak_record *>(scratch);
-    const uint64_t cells = sh.columns * channels;
-    if (nsamples != 0 && sh.slices == 0) {
-        prm.perTile = kTpTile / m;
-        prm.group = pow2AtLeast((m + kTpRun - 1) / kTpRun);           // (1 .. 64)
-        prm.run = (m + prm.group - 1) / prm.group;                    // (<= kTpRun; group * run >= m)
-        const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (sgz_status st = fitsOneLaunch(tiles, "true-peak", "columns"); st != SGZ_OK) return st;
-        hipLaunchKernelGGL(truePeakTileKernel, dim3(unsigned(tiles), channels), dim3(kTpThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kTpThreads)), "true-peak", "columns"); st != SGZ_OK) return st;
-    if (nsamples != 0) {
-        hipLaunchKernelGGL(truePeakSliceKernel, dim3(unsigned(sh.columns), channels, sh.slices), dim3(kTpThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(truePeakEmitKernel, dim3(unsigned(emitBlocks(cells, kTpThreads))), dim3(kTpThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchPlainLane(truePeakTileKernel, truePeakSliceKernel, truePeakEmitKernel, kTpThreads, "true-peak", prm, sh, channels, nsamples, 1, [m](TruePeakParams &p) {
+        p.perTile = kTpTile / m;
+        p.group = pow2AtLeast((m + kTpRun - 1) / kTpRun);             // (1 .. 64)
+        p.run = (m + p.group - 1) / p.group;                          // (<= kTpRun; group * run >= m)
+    }, stream);
 }
 
 }  // namespace sgz
@@ -417,15 +402,11 @@ sgz_status sgz_stage_truepeak_columns(const float *d_planar, size_t channel_stri
                                       void *stream)
 {
     const StageFront front{"sgz_stage_truepeak_columns", "channels", kTpMaxChannels, "d_peaks", 16, true, 62};
-    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, channels, nsamples, m, held, continued, 0, slices, d_carry, d_peaks); st != SGZ_OK) return st;
-    const ColumnsShape sh = truePeakColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, continued, d_carry, d_peaks); st != SGZ_OK) return st;
-    if (!sh.launch) return SGZ_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StageScratch mem(s);
-    const void *carryIn = nullptr;
-    if (sgz_status st = mem.get(front, sh, nsamples, held, continued, d_carry, size_t(channels) * sizeof(sgz_truepeak_carry), &carryIn); st != SGZ_OK) return st;
-    return runTruePeakColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, continued, static_cast<const sgz_truepeak_carry *>(carryIn), d_carry, d_peaks, mem.scratch.p, s);
+    return stageColumns(front, SGZ_OK, d_planar, channel_stride, channels, nsamples, m, held, flush, continued, 0, slices, d_carry, d_peaks, stream, truePeakColumnsShape,
+                        size_t(channels) * sizeof(sgz_truepeak_carry), noStep, [&](const ColumnsShape &sh, const void *carryIn, void *scratch, hipStream_t s) {
+                            return runTruePeakColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, continued, static_cast<const sgz_truepeak_carry *>(carryIn), d_carry,
+                                                      d_peaks, scratch, s);
+                        });
 }
 
 sgz_status sgz_truepeak_fold(const sgz_truepeak_record *in, size_t n, uint32_t channels, size_t x0, size_t x1, uint32_t out_columns,

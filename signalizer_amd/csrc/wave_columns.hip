@@ -220,29 +220,14 @@ sgz_status runWaveColumns(const ColumnsShape &sh, const float *d_planar, size_t 
 {
     if (!sh.launch) return SGZ_OK;
     WaveParams prm{};
-    prm.planar = d_planar; prm.stride = channelStride; prm.n = long(nsamples);
-    prm.columns = long(sh.columns); prm.closed = long(sh.closed);
-    prm.m = m; prm.held = held; prm.channels = channels; prm.slices = sh.slices;
+    fillGrid(prm, sh, d_planar, channelStride, nsamples, m, held);
+    prm.channels = channels;
     prm.carryIn = reinterpret_cast<const float2 *>(carryIn); prm.carryOut = reinterpret_cast<float2 *>(carryOut);
     prm.wave = reinterpret_cast<float2 *>(d_wave); prm.partial = static_cast<uint2 *>(scratch);
-    const uint64_t cells = sh.columns * channels;
-    if (nsamples != 0 && sh.slices == 0) {
-        prm.perTile = kWvTile / m;
-        prm.group = pow2AtLeast((m + 15u) / 16u);                 // (1 .. 64: sixteen samples a lane, or as near as a power of two gets)
-        const uint64_t tiles = (sh.columns + prm.perTile - 1) / prm.perTile;
-        if (sgz_status st = fitsOneLaunch(tiles, "wave", "columns"); st != SGZ_OK) return st;
-        hipLaunchKernelGGL(waveTileKernel, dim3(unsigned(tiles), channels), dim3(kWvThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-        return SGZ_OK;
-    }
-    if (sgz_status st = fitsOneLaunch(std::max(sh.columns, emitBlocks(cells, kWvThreads)), "wave", "columns"); st != SGZ_OK) return st;
-    if (nsamples != 0) {
-        hipLaunchKernelGGL(waveSliceKernel, dim3(unsigned(sh.columns), channels, sh.slices), dim3(kWvThreads), 0, stream, prm);
-        SGZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(waveEmitKernel, dim3(unsigned(emitBlocks(cells, kWvThreads))), dim3(kWvThreads), 0, stream, prm);
-    SGZ_HIP(hipGetLastError());
-    return SGZ_OK;
+    return launchPlainLane(waveTileKernel, waveSliceKernel, waveEmitKernel, kWvThreads, "wave", prm, sh, channels, nsamples, 1, [m](WaveParams &p) {
+        p.perTile = kWvTile / m;
+        p.group = pow2AtLeast((m + 15u) / 16u);                   // (1 .. 64: sixteen samples a lane, or as near as a power of two gets)
+    }, stream);
 }
 
 }  // namespace sgz
@@ -259,15 +244,10 @@ sgz_status sgz_stage_wave_columns(const float *d_planar, size_t channel_stride, 
                                   int flush, uint32_t slices, float *d_carry, float *d_wave, void *stream)
 {
     const StageFront front{"sgz_stage_wave_columns", "channels", kWvMaxChannels, "d_wave", 8, false, 62};
-    if (sgz_status st = checkStageArgs(front, SGZ_OK, d_planar, channel_stride, channels, nsamples, m, held, 0, 0, slices, d_carry, d_wave); st != SGZ_OK) return st;
-    const ColumnsShape sh = waveColumnsShape(channels, nsamples, m, held, flush, slices);
-    if (sgz_status st = checkStageBuffers(front, sh, nsamples, held, 0, d_carry, d_wave); st != SGZ_OK) return st;
-    if (!sh.launch) return SGZ_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StageScratch mem(s);
-    const void *carryIn = nullptr;
-    if (sgz_status st = mem.get(front, sh, nsamples, held, 0, d_carry, size_t(channels) * sizeof(float2), &carryIn); st != SGZ_OK) return st;
-    return runWaveColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, static_cast<const float *>(carryIn), d_carry, d_wave, mem.scratch.p, s);
+    return stageColumns(front, SGZ_OK, d_planar, channel_stride, channels, nsamples, m, held, flush, 0, 0, slices, d_carry, d_wave, stream, waveColumnsShape,
+                        size_t(channels) * sizeof(float2), noStep, [&](const ColumnsShape &sh, const void *carryIn, void *scratch, hipStream_t s) {
+                            return runWaveColumns(sh, d_planar, channel_stride, channels, nsamples, m, held, static_cast<const float *>(carryIn), d_carry, d_wave, scratch, s);
+                        });
 }
 
 }  // extern "C"

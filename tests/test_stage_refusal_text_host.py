@@ -1,6 +1,7 @@
-"""The text of every argument refusal of the six sgz_stage_<lane>_columns calls (csrc/column_lanes.hpp checkStageArgs / checkStageBuffers, which
-the six calls share): sgz_last_error() word for word, as the calls worded it when each had checks of its own.  Host only: the refusals come
-before the device is touched, on fake addresses that are never dereferenced."""
+"""The text of every argument refusal of the eight sgz_stage_<lane>_columns calls (csrc/column_lanes.hpp checkStageArgs / checkStageBuffers, which
+the eight calls share): sgz_last_error() word for word, as the calls worded it when each had checks of its own (the histogram and the run lane:
+as they worded it when each still wrote its stage call out).  Host only: the refusals come before the device is touched, on fake addresses
+that are never dereferenced."""
 import ctypes as C
 
 import pytest
@@ -8,16 +9,19 @@ import pytest
 from signalizer_amd import api
 
 E = api.SGZ_EINVAL
-LANES = ("wave", "level", "field", "truepeak", "loudness", "band")
+LANES = ("wave", "level", "field", "truepeak", "loudness", "band", "hist", "run")
 PLANAR, CARRY, OUT = 0x10000, 0x20000, 0x30000
 
 # the arguments of a call that passes every check (100 samples, m = 8, flush), then one change per case
-GOOD = dict(planar=PLANAR, stride=128, cells=1, n=100, filter="good", first=0, m=8, held=0, flush=1, continued=0, slices=0, carry=CARRY, out=OUT)
+GOOD = dict(planar=PLANAR, stride=128, cells=1, n=100, filter="good", params="good", first=0, m=8, held=0, flush=1, continued=0, slices=0, carry=CARRY, out=OUT)
 CASES = {
     "null d_planar": dict(planar=None),
     "null filter": dict(filter=None),
     "filter shape": dict(filter="W 64 L 48"),
     "filter too long": dict(filter="W 32768"),
+    "null params": dict(params=None),
+    "params hot 0": dict(params="hot 0"),
+    "params quiet not below hot": dict(params="quiet = hot"),
     "cells 0": dict(cells=0),
     "cells above the most": dict(cells=65),
     "m 0": dict(m=0),
@@ -37,6 +41,8 @@ CASES = {
     # ... and the first check wins where two arguments are wrong
     "null d_planar and null filter": dict(planar=None, filter=None),
     "null filter and cells 0": dict(filter=None, cells=0),
+    "null d_planar and null params": dict(planar=None, params=None),
+    "null params and cells 0": dict(params=None, cells=0),
 }
 
 
@@ -51,11 +57,24 @@ def _filter(lane, which):
     return C.byref(f)
 
 
+def _params(which):
+    if which is None:
+        return None
+    p = api.run_params_default()
+    if which == "hot 0":
+        p.hot = 0
+    elif which == "quiet = hot":
+        p.quiet = p.hot
+    return C.byref(p)
+
+
 def refusal(L, lane, case):
     """sgz_last_error() of the lane's stage call with the case's arguments; None where the lane has no such argument or refuses nothing"""
     a = dict(GOOD, **CASES[case])
-    filtered, history = lane in ("loudness", "band"), lane in ("truepeak", "loudness", "band")
+    filtered, history = lane in ("loudness", "band"), lane in ("truepeak", "loudness", "band", "run")
     if (("filter" in CASES[case] or "first" in CASES[case]) and not filtered) or (case == "held without continued" and not history):
+        return None
+    if "params" in CASES[case] and lane != "run":
         return None
     if lane in ("level", "field") and case == "cells above the most":
         a["cells"] = 33
@@ -64,7 +83,8 @@ def refusal(L, lane, case):
         st = call(a["planar"], a["stride"], a["cells"], a["n"], _filter(lane, a["filter"]), a["first"], a["m"], a["held"], a["flush"], a["continued"], a["slices"],
                   a["carry"], a["out"], None)
     elif history:
-        st = call(a["planar"], a["stride"], a["cells"], a["n"], a["m"], a["held"], a["flush"], a["continued"], a["slices"], a["carry"], a["out"], None)
+        front = (_params(a["params"]),) if lane == "run" else ()
+        st = call(a["planar"], a["stride"], a["cells"], a["n"], *front, a["m"], a["held"], a["flush"], a["continued"], a["slices"], a["carry"], a["out"], None)
     else:
         st = call(a["planar"], a["stride"], a["cells"], a["n"], a["m"], a["held"], a["flush"], a["slices"], a["carry"], a["out"], None)
     if st == api.SGZ_OK:
@@ -180,6 +200,43 @@ EXPECTED = {
     ("band", "null output, flushed carry"): "sgz_stage_band_columns: d_records is written (a column closes)",
     ("band", "null d_planar and null filter"): "sgz_stage_band_columns: null d_planar",
     ("band", "null filter and cells 0"): "sgz_stage_band_columns: null filter",
+    # the histogram and the run lane: recorded from the build in which each still wrote its stage call out
+    ("hist", "null d_planar"): "sgz_stage_hist_columns: null d_planar",
+    ("hist", "cells 0"): "sgz_stage_hist_columns: 1 .. 64 channels",
+    ("hist", "cells above the most"): "sgz_stage_hist_columns: 1 .. 64 channels",
+    ("hist", "m 0"): "sgz_stage_hist_columns: m >= 1 samples per column",
+    ("hist", "held not below m"): "sgz_stage_hist_columns: held < m",
+    ("hist", "stride below nsamples"): "sgz_stage_hist_columns: channel_stride < nsamples",
+    ("hist", "too many samples"): "sgz_stage_hist_columns: channel_stride < nsamples",
+    ("hist", "slices"): "sgz_stage_hist_columns: slices 0 (automatic) or 1 .. 64",
+    ("hist", "d_planar alignment"): "sgz_stage_hist_columns: d_planar aligned to 4 bytes, d_carry and d_hist to 16",
+    ("hist", "d_carry alignment"): "sgz_stage_hist_columns: d_planar aligned to 4 bytes, d_carry and d_hist to 16",
+    ("hist", "output alignment"): "sgz_stage_hist_columns: d_planar aligned to 4 bytes, d_carry and d_hist to 16",
+    ("hist", "null d_carry, written"): "sgz_stage_hist_columns: d_carry is read (held > 0) or written (samples stay open)",
+    ("hist", "null d_carry, read"): "sgz_stage_hist_columns: d_carry is read (held > 0) or written (samples stay open)",
+    ("hist", "null output"): "sgz_stage_hist_columns: d_hist is written (a column closes)",
+    ("hist", "null output, flushed carry"): "sgz_stage_hist_columns: d_hist is written (a column closes)",
+    ("run", "null d_planar"): "sgz_stage_run_columns: null d_planar",
+    ("run", "null params"): "sgz_stage_run_columns: null params",
+    ("run", "params hot 0"): "sgz_stage_run_columns: 1 <= hot <= 2^26 and quiet < hot",
+    ("run", "params quiet not below hot"): "sgz_stage_run_columns: 1 <= hot <= 2^26 and quiet < hot",
+    ("run", "cells 0"): "sgz_stage_run_columns: 1 .. 64 channels",
+    ("run", "cells above the most"): "sgz_stage_run_columns: 1 .. 64 channels",
+    ("run", "m 0"): "sgz_stage_run_columns: m >= 1 samples per column",
+    ("run", "held not below m"): "sgz_stage_run_columns: held < m",
+    ("run", "held without continued"): "sgz_stage_run_columns: held > 0 needs continued != 0 (a stream that begins here has no open column)",
+    ("run", "stride below nsamples"): "sgz_stage_run_columns: channel_stride < nsamples",
+    ("run", "too many samples"): "sgz_stage_run_columns: channel_stride < nsamples",
+    ("run", "slices"): "sgz_stage_run_columns: slices 0 (automatic) or 1 .. 64",
+    ("run", "d_planar alignment"): "sgz_stage_run_columns: d_planar aligned to 4 bytes, d_carry and d_runs to 16",
+    ("run", "d_carry alignment"): "sgz_stage_run_columns: d_planar aligned to 4 bytes, d_carry and d_runs to 16",
+    ("run", "output alignment"): "sgz_stage_run_columns: d_planar aligned to 4 bytes, d_carry and d_runs to 16",
+    ("run", "null d_carry, written"): "sgz_stage_run_columns: d_carry is read (continued) or written (nsamples > 0)",
+    ("run", "null d_carry, read"): "sgz_stage_run_columns: d_carry is read (continued) or written (nsamples > 0)",
+    ("run", "null output"): "sgz_stage_run_columns: d_runs is written (a column closes)",
+    ("run", "null output, flushed carry"): "sgz_stage_run_columns: d_runs is written (a column closes)",
+    ("run", "null d_planar and null params"): "sgz_stage_run_columns: null d_planar",
+    ("run", "null params and cells 0"): "sgz_stage_run_columns: null params",
 }
 
 
