@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -58,6 +59,9 @@ class LinePeak(C.Structure):
 
 class Timing(C.Structure):
     _fields_ = [("h2d_ms", C.c_double), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("frames", C.c_uint64)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PcmTiming(C.Structure):
@@ -1106,6 +1110,79 @@ def cross_edges_octave(sample_rate: float, N: int, bands_per_octave: int, f_lo: 
     return edges[:bands.value + 1].copy(), centres[:bands.value].copy()
 
 
+# The overview kinds: what each has of its own in sgz.h.  Plan's stage / render / view helpers, PcmStream.feed_overview* and the overview*_pcm
+# one-shots read it from here.  A shape names its extents -- "C" pairs, "sides", "P" axis points, "bands" of the cross table, "bins" N + 1 --
+# and _overview_shape puts a plan's or a config's numbers in.
+#   suffix        behind sgz_stage_overview, sgz_spectrogram_overview and sgz_pcm_stream_feed_overview
+#   source        what the stage call reduces: the shape of one frame of it
+#   cell          the shape of the carry and of one column of records
+#   dtype, words  the record on the host, and its int64 words [..., words] on the device (0: plain float32 there as well)
+#   outputs       in C order: (the want_* keyword that selects it, None where it is compulsory; column shape; dtype[; True: nq leading planes])
+#   state, view   the render's device form takes a decay state; the kind has the _view forms
+OverviewKind = namedtuple("OverviewKind", "suffix source cell dtype words outputs state view")
+_LINES, _MAPPED, _BINS = ("C", NUM_GRAPHS, "P", 2), ("C", "sides", "P"), ("C", "bins", 2)
+_RGBA = ("want_rgba", ("P", 4), np.uint8)
+OVERVIEW_KINDS = {
+    "peaks": OverviewKind("", _LINES, ("C", "P"), np.dtype(np.float32), 0,
+                          (_RGBA, ("want_peaks", ("C", "P"), np.float32)), True, True),
+    "stats": OverviewKind("_stats", _LINES, ("C", "P"), OVERVIEW_STAT_DTYPE, 3,
+                          (_RGBA, ("want_stats", ("C", "P"), OVERVIEW_STAT_DTYPE), ("want_means", ("C", "P"), np.float32)), True, True),
+    "pct": OverviewKind("_pct", _LINES, ("C", "P"), OVERVIEW_PCT_DTYPE, 34,
+                        (_RGBA, ("want_records", ("C", "P"), OVERVIEW_PCT_DTYPE), ("want_values", ("C", "P"), np.float32, True)), True, False),
+    "power": OverviewKind("_power", _MAPPED, ("C", "sides", "P"), OVERVIEW_POWER_DTYPE, 4,
+                          (_RGBA, ("want_power", ("C", "sides", "P"), OVERVIEW_POWER_DTYPE), ("want_levels", ("C", "sides", "P"), np.float32)),
+                          False, True),
+    "cross": OverviewKind("_cross", _BINS, ("C", "bands"), OVERVIEW_CROSS_DTYPE, 10, ((None, ("C", "bands"), OVERVIEW_CROSS_DTYPE),), False, False),
+    "flux": OverviewKind("_flux", _MAPPED, ("C", "sides"), OVERVIEW_FLUX_DTYPE, 11, ((None, ("C", "sides"), OVERVIEW_FLUX_DTYPE),), False, False),
+}
+
+
+def _overview_shape(shape, dims) -> tuple:
+    """a shape of the kind table at dims = (C, sides, P, bands[, bins])"""
+    at = dict(zip(("C", "sides", "P", "bands", "bins"), dims))
+    return tuple(at.get(d, d) for d in shape)
+
+
+def _overview_outputs(kind: OverviewKind, dims, wants=(), planes=None) -> list:
+    """the kind's outputs at dims, as (wanted, the shape of one column, dtype[, planes]) each.  wants: the flags of the outputs that have one,
+    in C order; planes: how many the output with leading planes has"""
+    wants = iter(wants)
+    return [(next(wants) if o[0] else True, _overview_shape(o[1], dims), o[2], *((planes,) if o[3:] else ())) for o in kind.outputs]
+
+
+def _overview_out(cols: int, want, shape, dtype, planes=None, device=None):
+    """an overview output's buffer: [columns, *shape], or [planes, columns, *shape]; never an empty array (its pointer may be null).  On the host
+    np.zeros; on `device` torch.empty, a record dtype as int64 with its words as the last axis"""
+    if not want:
+        return None
+    full = (max(cols, 1), *shape) if planes is None else (planes, max(cols, 1), *shape)
+    if device is None:
+        return np.zeros(full, dtype)
+    import torch
+    dtype = np.dtype(dtype)
+    if dtype.fields:
+        return torch.empty((*full, dtype.itemsize // 8), dtype=torch.int64, device=device)
+    return torch.empty(full, dtype=getattr(torch, dtype.name), device=device)
+
+
+def _overview_cut(a, cols: int, want, shape, dtype, planes=None):
+    return None if a is None else a[:cols] if planes is None else a[:, :cols]
+
+
+def _buf_ptrs(arrays) -> list:
+    return [_buf_ptr(a) if a is not None else None for a in arrays]
+
+
+def _channel_ptrs(planar: np.ndarray):
+    """the calls' `const float *const *channels`: the rows of a contiguous float32 [channels, S] array"""
+    return (C.c_void_p * planar.shape[0])(*[planar[i].ctypes.data for i in range(planar.shape[0])])
+
+
+def _stream(stream):
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream().cuda_stream
+
+
 class Plan:
     """The Spectrum constant block (TransformConstant mirror). Host tables need no GPU."""
 
@@ -1253,13 +1330,12 @@ class Plan:
             F = self.num_frames(S)
             track = np.zeros((max(F, 1), self.C, len(LinePeak._fields_)), np.float64)            # (never a NULL pointer: F == 0 is the call's to refuse)
             rgba = np.zeros((max(F, 1), self.P, 4), np.uint8) if want_rgba else None
-            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
             t = Timing()
-            st = check(lib().sgz_spectrogram_track_host(self.h, ptrs, nch, S, graph, float(mouse_fraction), _np_ptr(rgba) if want_rgba else None,
-                                                        _np_ptr(track), C.byref(t)))
+            st = check(lib().sgz_spectrogram_track_host(self.h, _channel_ptrs(planar), nch, S, graph, float(mouse_fraction),
+                                                        _np_ptr(rgba) if want_rgba else None, _np_ptr(track), C.byref(t)))
             if st == SGZ_SKIPPED_FRAME:
                 return None
-            return track[:F], (rgba[:F] if want_rgba else None), {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+            return track[:F], (rgba[:F] if want_rgba else None), t.asdict()
         import torch
         assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
         S = planar.shape[1]
@@ -1274,83 +1350,105 @@ class Plan:
             return None
         return track[:F], (rgba[:F] if want_rgba else None)
 
-    # the overview: k frames per image column, reduced (a peak hold of the main graph) and coloured on the device
+    # The overview: k frames per image column, reduced and coloured on the device.  What a kind has of its own is its entry of OVERVIEW_KINDS;
+    # the three helpers are every kind's stage call, render and view.  wants: the flags of the kind's optional outputs in C order; front / mid:
+    # what the C call takes between flush and slices / in front of the carry (stage) or the outputs (render); bands: of the cross table; planes:
+    # of pct's values
+    def _overview_stage(self, kind: str, x, k: int, held: int, flush: bool, slices: int, carry, wants=(), front=(), mid=(), bands: int = 0,
+                        planes=None, stream=None):
+        """sgz_stage_overview<suffix> -> (every output's columns, None where not wanted, frames of the column left open)"""
+        import torch
+        kind = OVERVIEW_KINDS[kind]
+        dims = (self.C, self.sides, self.P, bands, self.N + 1)
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert tuple(x.shape[1:]) == _overview_shape(kind.source, dims), tuple(x.shape)
+        assert carry is None or (carry.is_cuda and carry.dtype == (torch.int64 if kind.words else torch.float32) and carry.is_contiguous()
+                                 and carry.numel() == int(np.prod(_overview_shape(kind.cell, dims))) * max(kind.words, 1))
+        frames = x.shape[0]
+        columns, held_out = overview_step(k, held, frames, flush)
+        outputs = _overview_outputs(kind, dims, wants, planes)
+        arrays = [_overview_out(columns, *o, device=x.device) for o in outputs]
+        check(getattr(lib(), "sgz_stage_overview" + kind.suffix)(self.h, x.data_ptr(), frames, k, held, int(bool(flush)), *front, slices, *mid,
+                                                                 carry.data_ptr() if carry is not None else None, *_buf_ptrs(arrays),
+                                                                 _stream(stream)))
+        return (*[_overview_cut(a, columns, *o) for a, o in zip(arrays, outputs)], held_out)
+
+    def _overview_render(self, kind: str, planar, k: int, wants=(), mid=(), state=None, bands: int = 0, planes=None, stream=None):
+        """sgz_spectrogram_overview<suffix>_host for a numpy array -> (every output's columns, None where not wanted, timing dict);
+        sgz_spectrogram_overview<suffix>_device for a cuda tensor -> the outputs alone, a kind's single output bare.  A skipped frame: None"""
+        kind = OVERVIEW_KINDS[kind]
+        call = "sgz_spectrogram_overview" + kind.suffix
+        outputs = _overview_outputs(kind, (self.C, self.sides, self.P, bands), wants, planes)
+        host = isinstance(planar, np.ndarray)
+        if host:
+            planar = np.ascontiguousarray(planar, np.float32)
+            nch, S = planar.shape
+            columns = -(-self.num_frames(S) // k)
+            arrays = [_overview_out(columns, *o) for o in outputs]
+            t = Timing()
+            st = check(getattr(lib(), call + "_host")(self.h, _channel_ptrs(planar), nch, S, k, *mid, *_buf_ptrs(arrays), C.byref(t)))
+        else:
+            import torch
+            assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
+            S = planar.shape[1]
+            columns = -(-self.num_frames(S) // k)
+            arrays = [_overview_out(columns, *o, device=planar.device) for o in outputs]
+            tail = (state.data_ptr() if state is not None else None,) if kind.state else ()
+            st = check(getattr(lib(), call + "_device")(self.h, planar.data_ptr(), planar.stride(0), S, k, *mid, *_buf_ptrs(arrays), *tail,
+                                                        _stream(stream)))
+        if st == SGZ_SKIPPED_FRAME:
+            return None
+        cut = [_overview_cut(a, columns, *o) for a, o in zip(arrays, outputs)]
+        if host:
+            return (*cut, t.asdict())
+        return cut[0] if len(cut) == 1 else tuple(cut)
+
+    def _overview_view(self, kind: str, kept, out_columns: int, x0: int, x1, slices: int, wants, stream=None):
+        """sgz_overview<suffix>_view_host for kept numpy records [n, *cell] -> (every output, None where not wanted, timing dict);
+        sgz_stage_overview<suffix>_view for a cuda tensor of them -> the outputs alone"""
+        kind = OVERVIEW_KINDS[kind]
+        n = int(kept.shape[0])
+        x1 = n if x1 is None else x1
+        dims = (self.C, self.sides, self.P)
+        cell = _overview_shape(kind.cell, dims)
+        outputs = _overview_outputs(kind, dims, wants)
+        if isinstance(kept, np.ndarray):
+            kept = np.ascontiguousarray(kept, kind.dtype)
+            assert tuple(kept.shape[1:]) == cell, tuple(kept.shape)
+            cols = overview_view_columns(n, x0, x1, out_columns)
+            arrays = [_overview_out(cols, *o) for o in outputs]
+            t = Timing()
+            check(getattr(lib(), f"sgz_overview{kind.suffix}_view_host")(self.h, _np_ptr(kept), n, x0, x1, out_columns, *_buf_ptrs(arrays), C.byref(t)))
+            return (*[_overview_cut(a, cols, *o) for a, o in zip(arrays, outputs)], t.asdict())
+        import torch
+        assert kept.is_cuda and kept.dtype == (torch.int64 if kind.words else torch.float32) and kept.is_contiguous()
+        assert tuple(kept.shape[1:]) == ((*cell, kind.words) if kind.words else cell), tuple(kept.shape)
+        cols = overview_view_columns(n, x0, x1, out_columns)
+        arrays = [_overview_out(cols, *o, device=kept.device) for o in outputs]
+        check(getattr(lib(), f"sgz_stage_overview{kind.suffix}_view")(self.h, kept.data_ptr(), n, x0, x1, out_columns, slices, *_buf_ptrs(arrays),
+                                                                      _stream(stream)))
+        return tuple(_overview_cut(a, cols, *o) for a, o in zip(arrays, outputs))
+
+    # the peak hold of the main graph
     def overview_columns(self, lines, k: int, held: int = 0, flush: bool = True, slices: int = 0, carry=None, want_rgba: bool = True,
                          want_peaks: bool = False, stream=None):
         """sgz_stage_overview: lines -- cuda float32 [frames, pairs, graphs, P, 2]; carry -- cuda float32 [pairs, P], the open column (read
         when held > 0, written when frames stay open).  Returns (cuda rgba uint8 [columns, P, 4] or None, cuda peaks float32 [columns,
         pairs, P] or None, frames of the column left open)."""
-        import torch
-        assert lines.is_cuda and lines.dtype == torch.float32 and lines.is_contiguous()
-        assert tuple(lines.shape[1:]) == (self.C, NUM_GRAPHS, self.P, 2)
-        assert carry is None or (carry.is_cuda and carry.dtype == torch.float32 and carry.is_contiguous() and carry.numel() == self.C * self.P)
-        frames = lines.shape[0]
-        columns, held_out = overview_step(k, held, frames, flush)
-        rgba = torch.empty((max(columns, 1), self.P, 4), dtype=torch.uint8, device=lines.device) if want_rgba else None      # (never a NULL
-        peaks = torch.empty((max(columns, 1), self.C, self.P), dtype=torch.float32, device=lines.device) if want_peaks else None   # pointer)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview(self.h, lines.data_ptr(), frames, k, held, int(bool(flush)), slices,
-                                       carry.data_ptr() if carry is not None else None, rgba.data_ptr() if want_rgba else None,
-                                       peaks.data_ptr() if want_peaks else None, s))
-        return (rgba[:columns] if want_rgba else None), (peaks[:columns] if want_peaks else None), held_out
+        return self._overview_stage("peaks", lines, k, held, flush, slices, carry, (want_rgba, want_peaks), stream=stream)
 
     def overview(self, planar, k: int, want_rgba: bool = True, want_peaks: bool = False, state=None, stream=None):
         """The overview render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_host -> (rgba uint8 [columns, P, 4] or None, peaks
         float32 [columns, C, P] or None, timing dict).  planar a cuda tensor: sgz_spectrogram_overview_device, asynchronous -> (cuda rgba
         or None, cuda peaks or None).  columns = ceil(frames / k).  Fewer samples than a window: None."""
-        if isinstance(planar, np.ndarray):
-            planar = np.ascontiguousarray(planar, np.float32)
-            nch, S = planar.shape
-            columns = -(-self.num_frames(S) // k)
-            rgba = np.zeros((max(columns, 1), self.P, 4), np.uint8) if want_rgba else None
-            peaks = np.zeros((max(columns, 1), self.C, self.P), np.float32) if want_peaks else None
-            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
-            t = Timing()
-            st = check(lib().sgz_spectrogram_overview_host(self.h, ptrs, nch, S, k, _np_ptr(rgba) if want_rgba else None,
-                                                           _np_ptr(peaks) if want_peaks else None, C.byref(t)))
-            if st == SGZ_SKIPPED_FRAME:
-                return None
-            return ((rgba[:columns] if want_rgba else None), (peaks[:columns] if want_peaks else None),
-                    {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames})
-        import torch
-        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
-        S = planar.shape[1]
-        columns = -(-self.num_frames(S) // k)
-        rgba = torch.empty((max(columns, 1), self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None
-        peaks = torch.empty((max(columns, 1), self.C, self.P), dtype=torch.float32, device=planar.device) if want_peaks else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        st = check(lib().sgz_spectrogram_overview_device(self.h, planar.data_ptr(), planar.stride(0), S, k,
-                                                         rgba.data_ptr() if want_rgba else None, peaks.data_ptr() if want_peaks else None,
-                                                         state.data_ptr() if state is not None else None, s))
-        if st == SGZ_SKIPPED_FRAME:
-            return None
-        return (rgba[:columns] if want_rgba else None), (peaks[:columns] if want_peaks else None)
+        return self._overview_render("peaks", planar, k, (want_rgba, want_peaks), state=state, stream=stream)
 
     def overview_view(self, peaks, out_columns: int, x0: int = 0, x1: int | None = None, slices: int = 0, want_rgba: bool = True,
                       want_peaks: bool = False, stream=None):
         """The view of kept peaks [n, C, P] over source columns [x0, x1) (default: to the end) at min(out_columns, x1 - x0) columns.  peaks a
         cuda float32 tensor: sgz_stage_overview_view, asynchronous -> (cuda rgba uint8 [cols, P, 4] or None, cuda peaks float32 [cols, C, P]
         or None).  peaks a numpy array: sgz_overview_view_host -> (rgba or None, peaks or None, timing dict)."""
-        n = int(peaks.shape[0])
-        x1 = n if x1 is None else x1
-        assert tuple(peaks.shape[1:]) == (self.C, self.P), tuple(peaks.shape)
-        cols = overview_view_columns(n, x0, x1, out_columns)
-        if isinstance(peaks, np.ndarray):
-            peaks = np.ascontiguousarray(peaks, np.float32)
-            rgba = np.zeros((cols, self.P, 4), np.uint8) if want_rgba else None
-            out = np.zeros((cols, self.C, self.P), np.float32) if want_peaks else None
-            t = Timing()
-            check(lib().sgz_overview_view_host(self.h, _np_ptr(peaks), n, x0, x1, out_columns, _np_ptr(rgba) if want_rgba else None,
-                                               _np_ptr(out) if want_peaks else None, C.byref(t)))
-            return rgba, out, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
-        import torch
-        assert peaks.is_cuda and peaks.dtype == torch.float32 and peaks.is_contiguous()
-        rgba = torch.empty((cols, self.P, 4), dtype=torch.uint8, device=peaks.device) if want_rgba else None
-        out = torch.empty((cols, self.C, self.P), dtype=torch.float32, device=peaks.device) if want_peaks else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview_view(self.h, peaks.data_ptr(), n, x0, x1, out_columns, slices, rgba.data_ptr() if want_rgba else None,
-                                            out.data_ptr() if want_peaks else None, s))
-        return rgba, out
+        return self._overview_view("peaks", peaks, out_columns, x0, x1, slices, (want_rgba, want_peaks), stream)
 
     # the mean overview: the same columns, reduced to sum / count / nans / lo / hi records and coloured from the mean
     def overview_stats_columns(self, lines, k: int, held: int = 0, flush: bool = True, slices: int = 0, carry=None, want_rgba: bool = True,
@@ -1358,60 +1456,21 @@ class Plan:
         """sgz_stage_overview_stats: lines -- cuda float32 [frames, pairs, graphs, P, 2]; carry -- cuda int64 [pairs, P, 3], the open column's
         records (read when held > 0, written when frames stay open).  Returns (cuda rgba uint8 [columns, P, 4] or None, cuda records int64
         [columns, pairs, P, 3] or None -- see stats_from_device --, cuda means float32 [columns, pairs, P] or None, frames left open)."""
-        import torch
-        assert lines.is_cuda and lines.dtype == torch.float32 and lines.is_contiguous()
-        assert tuple(lines.shape[1:]) == (self.C, NUM_GRAPHS, self.P, 2)
-        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * self.P * 3)
-        frames = lines.shape[0]
-        columns, held_out = overview_step(k, held, frames, flush)
-        n = max(columns, 1)                                                                                     # (never a NULL pointer)
-        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=lines.device) if want_rgba else None
-        stats = torch.empty((n, self.C, self.P, 3), dtype=torch.int64, device=lines.device) if want_stats else None
-        means = torch.empty((n, self.C, self.P), dtype=torch.float32, device=lines.device) if want_means else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview_stats(self.h, lines.data_ptr(), frames, k, held, int(bool(flush)), slices,
-                                             carry.data_ptr() if carry is not None else None, rgba.data_ptr() if want_rgba else None,
-                                             stats.data_ptr() if want_stats else None, means.data_ptr() if want_means else None, s))
-        return (rgba[:columns] if want_rgba else None), (stats[:columns] if want_stats else None), (means[:columns] if want_means else None), held_out
+        return self._overview_stage("stats", lines, k, held, flush, slices, carry, (want_rgba, want_stats, want_means), stream=stream)
 
     def overview_stats(self, planar, k: int, want_rgba: bool = True, want_stats: bool = False, want_means: bool = False, state=None, stream=None):
         """The mean overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_stats_host -> (rgba or None, records
         OVERVIEW_STAT_DTYPE [columns, C, P] or None, means float32 [columns, C, P] or None, timing dict).  planar a cuda tensor:
         sgz_spectrogram_overview_stats_device, asynchronous -> (cuda rgba, cuda records int64 [columns, C, P, 3], cuda means), None where not
         wanted.  Fewer samples than a window: None."""
-        if isinstance(planar, np.ndarray):
-            planar = np.ascontiguousarray(planar, np.float32)
-            nch, S = planar.shape
-            columns = -(-self.num_frames(S) // k)
-            n = max(columns, 1)
-            rgba = np.zeros((n, self.P, 4), np.uint8) if want_rgba else None
-            stats = np.zeros((n, self.C, self.P), OVERVIEW_STAT_DTYPE) if want_stats else None
-            means = np.zeros((n, self.C, self.P), np.float32) if want_means else None
-            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
-            t = Timing()
-            st = check(lib().sgz_spectrogram_overview_stats_host(self.h, ptrs, nch, S, k, _np_ptr(rgba) if want_rgba else None,
-                                                                 _np_ptr(stats) if want_stats else None, _np_ptr(means) if want_means else None,
-                                                                 C.byref(t)))
-            if st == SGZ_SKIPPED_FRAME:
-                return None
-            return ((rgba[:columns] if want_rgba else None), (stats[:columns] if want_stats else None), (means[:columns] if want_means else None),
-                    {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames})
-        import torch
-        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
-        S = planar.shape[1]
-        columns = -(-self.num_frames(S) // k)
-        n = max(columns, 1)
-        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None
-        stats = torch.empty((n, self.C, self.P, 3), dtype=torch.int64, device=planar.device) if want_stats else None
-        means = torch.empty((n, self.C, self.P), dtype=torch.float32, device=planar.device) if want_means else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        st = check(lib().sgz_spectrogram_overview_stats_device(self.h, planar.data_ptr(), planar.stride(0), S, k,
-                                                               rgba.data_ptr() if want_rgba else None, stats.data_ptr() if want_stats else None,
-                                                               means.data_ptr() if want_means else None,
-                                                               state.data_ptr() if state is not None else None, s))
-        if st == SGZ_SKIPPED_FRAME:
-            return None
-        return (rgba[:columns] if want_rgba else None), (stats[:columns] if want_stats else None), (means[:columns] if want_means else None)
+        return self._overview_render("stats", planar, k, (want_rgba, want_stats, want_means), state=state, stream=stream)
+
+    def overview_stats_view(self, stats, out_columns: int, x0: int = 0, x1: int | None = None, slices: int = 0, want_rgba: bool = True,
+                            want_stats: bool = False, want_means: bool = False, stream=None):
+        """The view of kept records over source columns [x0, x1) (default: to the end) at min(out_columns, x1 - x0) columns.  stats a cuda
+        int64 tensor [n, C, P, 3]: sgz_stage_overview_stats_view, asynchronous -> (cuda rgba, cuda records, cuda means), None where not
+        wanted.  stats a numpy OVERVIEW_STAT_DTYPE array [n, C, P]: sgz_overview_stats_view_host -> (rgba, records, means, timing dict)."""
+        return self._overview_view("stats", stats, out_columns, x0, x1, slices, (want_rgba, want_stats, want_means), stream)
 
     # the percentile overview: the same columns, reduced to 66-bucket records; nq quantile planes, the image coloured from quantile 0
     def overview_pct_columns(self, lines, k: int, q=0.5, held: int = 0, flush: bool = True, slices: int = 0, carry=None, want_rgba: bool = True,
@@ -1420,22 +1479,9 @@ class Plan:
         int64 [pairs, P, 34], the open column's records (read when held > 0, written when frames stay open).  Returns (cuda rgba uint8
         [columns, P, 4] or None, cuda records int64 [columns, pairs, P, 34] or None -- see pct_from_device --, cuda values float32
         [nq, columns, pairs, P] or None, frames left open)."""
-        import torch
-        assert lines.is_cuda and lines.dtype == torch.float32 and lines.is_contiguous()
-        assert tuple(lines.shape[1:]) == (self.C, NUM_GRAPHS, self.P, 2)
-        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * self.P * 34)
         qa, qp, nq = _quantiles(q)
-        frames = lines.shape[0]
-        columns, held_out = overview_step(k, held, frames, flush)
-        rgba = torch.empty((max(columns, 1), self.P, 4), dtype=torch.uint8, device=lines.device) if want_rgba else None       # (never a NULL pointer)
-        records = torch.empty((max(columns, 1), self.C, self.P, 34), dtype=torch.int64, device=lines.device) if want_records else None
-        values = torch.empty((max(nq, 1), max(columns, 1), self.C, self.P), dtype=torch.float32, device=lines.device) if want_values else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview_pct(self.h, lines.data_ptr(), frames, k, held, int(bool(flush)), slices, qp, nq,
-                                           carry.data_ptr() if carry is not None else None, rgba.data_ptr() if want_rgba else None,
-                                           records.data_ptr() if want_records else None, values.data_ptr() if want_values else None, s))
-        return ((rgba[:columns] if want_rgba else None), (records[:columns] if want_records else None),
-                (values[:, :columns] if want_values else None), held_out)
+        return self._overview_stage("pct", lines, k, held, flush, slices, carry, (want_rgba, want_records, want_values), mid=(qp, nq),
+                                    planes=max(nq, 1), stream=stream)
 
     def overview_pct(self, planar, k: int, q=0.5, want_rgba: bool = True, want_records: bool = False, want_values: bool = False, state=None, stream=None):
         """The percentile overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_pct_host -> (rgba or None, records
@@ -1443,67 +1489,8 @@ class Plan:
         sgz_spectrogram_overview_pct_device, asynchronous -> (cuda rgba, cuda records int64 [columns, C, P, 34], cuda values), None where
         not wanted.  Fewer samples than a window: None."""
         qa, qp, nq = _quantiles(q)
-        if isinstance(planar, np.ndarray):
-            planar = np.ascontiguousarray(planar, np.float32)
-            nch, S = planar.shape
-            columns = -(-self.num_frames(S) // k)
-            n = max(columns, 1)
-            rgba = np.zeros((n, self.P, 4), np.uint8) if want_rgba else None
-            records = np.zeros((n, self.C, self.P), OVERVIEW_PCT_DTYPE) if want_records else None
-            values = np.zeros((max(nq, 1), n, self.C, self.P), np.float32) if want_values else None
-            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
-            t = Timing()
-            st = check(lib().sgz_spectrogram_overview_pct_host(self.h, ptrs, nch, S, k, qp, nq, _np_ptr(rgba) if want_rgba else None,
-                                                               _np_ptr(records) if want_records else None, _np_ptr(values) if want_values else None,
-                                                               C.byref(t)))
-            if st == SGZ_SKIPPED_FRAME:
-                return None
-            return ((rgba[:columns] if want_rgba else None), (records[:columns] if want_records else None), (values[:, :columns] if want_values else None),
-                    {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames})
-        import torch
-        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
-        S = planar.shape[1]
-        columns = -(-self.num_frames(S) // k)
-        n = max(columns, 1)
-        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None
-        records = torch.empty((n, self.C, self.P, 34), dtype=torch.int64, device=planar.device) if want_records else None
-        values = torch.empty((max(nq, 1), n, self.C, self.P), dtype=torch.float32, device=planar.device) if want_values else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        st = check(lib().sgz_spectrogram_overview_pct_device(self.h, planar.data_ptr(), planar.stride(0), S, k, qp, nq,
-                                                             rgba.data_ptr() if want_rgba else None, records.data_ptr() if want_records else None,
-                                                             values.data_ptr() if want_values else None,
-                                                             state.data_ptr() if state is not None else None, s))
-        if st == SGZ_SKIPPED_FRAME:
-            return None
-        return (rgba[:columns] if want_rgba else None), (records[:columns] if want_records else None), (values[:, :columns] if want_values else None)
-
-    def overview_stats_view(self, stats, out_columns: int, x0: int = 0, x1: int | None = None, slices: int = 0, want_rgba: bool = True,
-                            want_stats: bool = False, want_means: bool = False, stream=None):
-        """The view of kept records over source columns [x0, x1) (default: to the end) at min(out_columns, x1 - x0) columns.  stats a cuda
-        int64 tensor [n, C, P, 3]: sgz_stage_overview_stats_view, asynchronous -> (cuda rgba, cuda records, cuda means), None where not
-        wanted.  stats a numpy OVERVIEW_STAT_DTYPE array [n, C, P]: sgz_overview_stats_view_host -> (rgba, records, means, timing dict)."""
-        n = int(stats.shape[0])
-        x1 = n if x1 is None else x1
-        cols = overview_view_columns(n, x0, x1, out_columns)
-        if isinstance(stats, np.ndarray):
-            stats = np.ascontiguousarray(stats, OVERVIEW_STAT_DTYPE)
-            assert tuple(stats.shape[1:]) == (self.C, self.P), tuple(stats.shape)
-            rgba = np.zeros((cols, self.P, 4), np.uint8) if want_rgba else None
-            out = np.zeros((cols, self.C, self.P), OVERVIEW_STAT_DTYPE) if want_stats else None
-            means = np.zeros((cols, self.C, self.P), np.float32) if want_means else None
-            t = Timing()
-            check(lib().sgz_overview_stats_view_host(self.h, _np_ptr(stats), n, x0, x1, out_columns, _np_ptr(rgba) if want_rgba else None,
-                                                     _np_ptr(out) if want_stats else None, _np_ptr(means) if want_means else None, C.byref(t)))
-            return rgba, out, means, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
-        import torch
-        assert stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape[1:]) == (self.C, self.P, 3)
-        rgba = torch.empty((cols, self.P, 4), dtype=torch.uint8, device=stats.device) if want_rgba else None
-        out = torch.empty((cols, self.C, self.P, 3), dtype=torch.int64, device=stats.device) if want_stats else None
-        means = torch.empty((cols, self.C, self.P), dtype=torch.float32, device=stats.device) if want_means else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview_stats_view(self.h, stats.data_ptr(), n, x0, x1, out_columns, slices, rgba.data_ptr() if want_rgba else None,
-                                                  out.data_ptr() if want_stats else None, means.data_ptr() if want_means else None, s))
-        return rgba, out, means
+        return self._overview_render("pct", planar, k, (want_rgba, want_records, want_values), mid=(qp, nq), state=state, planes=max(nq, 1),
+                                     stream=stream)
 
     # the power overview: the same columns over the mapped magnitudes, reduced to 128-bit sums of squares and coloured from the rms' level
     def overview_power_columns(self, mapped, k: int, held: int = 0, flush: bool = True, slices: int = 0, carry=None, want_rgba: bool = True,
@@ -1512,59 +1499,14 @@ class Plan:
         records (read when held > 0, written when frames stay open).  Returns (cuda rgba uint8 [columns, P, 4] or None, cuda records int64
         [columns, pairs, sides, P, 4] or None -- see power_from_device --, cuda levels float32 [columns, pairs, sides, P] or None, frames left
         open)."""
-        import torch
-        assert mapped.is_cuda and mapped.dtype == torch.float32 and mapped.is_contiguous()
-        assert tuple(mapped.shape[1:]) == (self.C, self.sides, self.P)
-        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * self.sides * self.P * 4)
-        frames = mapped.shape[0]
-        columns, held_out = overview_step(k, held, frames, flush)
-        n = max(columns, 1)                                                                                     # (never a NULL pointer)
-        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=mapped.device) if want_rgba else None
-        power = torch.empty((n, self.C, self.sides, self.P, 4), dtype=torch.int64, device=mapped.device) if want_power else None
-        levels = torch.empty((n, self.C, self.sides, self.P), dtype=torch.float32, device=mapped.device) if want_levels else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview_power(self.h, mapped.data_ptr(), frames, k, held, int(bool(flush)), slices,
-                                             carry.data_ptr() if carry is not None else None, rgba.data_ptr() if want_rgba else None,
-                                             power.data_ptr() if want_power else None, levels.data_ptr() if want_levels else None, s))
-        return (rgba[:columns] if want_rgba else None), (power[:columns] if want_power else None), (levels[:columns] if want_levels else None), held_out
+        return self._overview_stage("power", mapped, k, held, flush, slices, carry, (want_rgba, want_power, want_levels), stream=stream)
 
     def overview_power(self, planar, k: int, want_rgba: bool = True, want_power: bool = False, want_levels: bool = False, stream=None):
         """The power overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_power_host -> (rgba or None, records
         OVERVIEW_POWER_DTYPE [columns, C, sides, P] or None, levels float32 [columns, C, sides, P] or None, timing dict).  planar a cuda tensor:
         sgz_spectrogram_overview_power_device, asynchronous -> (cuda rgba, cuda records int64 [columns, C, sides, P, 4], cuda levels), None
         where not wanted.  Fewer samples than a window: None."""
-        if isinstance(planar, np.ndarray):
-            planar = np.ascontiguousarray(planar, np.float32)
-            nch, S = planar.shape
-            columns = -(-self.num_frames(S) // k)
-            n = max(columns, 1)
-            rgba = np.zeros((n, self.P, 4), np.uint8) if want_rgba else None
-            power = np.zeros((n, self.C, self.sides, self.P), OVERVIEW_POWER_DTYPE) if want_power else None
-            levels = np.zeros((n, self.C, self.sides, self.P), np.float32) if want_levels else None
-            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
-            t = Timing()
-            st = check(lib().sgz_spectrogram_overview_power_host(self.h, ptrs, nch, S, k, _np_ptr(rgba) if want_rgba else None,
-                                                                 _np_ptr(power) if want_power else None, _np_ptr(levels) if want_levels else None,
-                                                                 C.byref(t)))
-            if st == SGZ_SKIPPED_FRAME:
-                return None
-            return ((rgba[:columns] if want_rgba else None), (power[:columns] if want_power else None), (levels[:columns] if want_levels else None),
-                    {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames})
-        import torch
-        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
-        S = planar.shape[1]
-        columns = -(-self.num_frames(S) // k)
-        n = max(columns, 1)
-        rgba = torch.empty((n, self.P, 4), dtype=torch.uint8, device=planar.device) if want_rgba else None
-        power = torch.empty((n, self.C, self.sides, self.P, 4), dtype=torch.int64, device=planar.device) if want_power else None
-        levels = torch.empty((n, self.C, self.sides, self.P), dtype=torch.float32, device=planar.device) if want_levels else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        st = check(lib().sgz_spectrogram_overview_power_device(self.h, planar.data_ptr(), planar.stride(0), S, k,
-                                                               rgba.data_ptr() if want_rgba else None, power.data_ptr() if want_power else None,
-                                                               levels.data_ptr() if want_levels else None, s))
-        if st == SGZ_SKIPPED_FRAME:
-            return None
-        return (rgba[:columns] if want_rgba else None), (power[:columns] if want_power else None), (levels[:columns] if want_levels else None)
+        return self._overview_render("power", planar, k, (want_rgba, want_power, want_levels), stream=stream)
 
     def overview_power_view(self, power, out_columns: int, x0: int = 0, x1: int | None = None, slices: int = 0, want_rgba: bool = True,
                             want_power: bool = False, want_levels: bool = False, stream=None):
@@ -1572,29 +1514,7 @@ class Plan:
         cuda int64 tensor [n, C, sides, P, 4]: sgz_stage_overview_power_view, asynchronous -> (cuda rgba, cuda records, cuda levels), None where
         not wanted.  power a numpy OVERVIEW_POWER_DTYPE array [n, C, sides, P]: sgz_overview_power_view_host -> (rgba, records, levels, timing
         dict)."""
-        n = int(power.shape[0])
-        x1 = n if x1 is None else x1
-        cols = overview_view_columns(n, x0, x1, out_columns)
-        shape = (self.C, self.sides, self.P)
-        if isinstance(power, np.ndarray):
-            power = np.ascontiguousarray(power, OVERVIEW_POWER_DTYPE)
-            assert tuple(power.shape[1:]) == shape, tuple(power.shape)
-            rgba = np.zeros((cols, self.P, 4), np.uint8) if want_rgba else None
-            out = np.zeros((cols, *shape), OVERVIEW_POWER_DTYPE) if want_power else None
-            levels = np.zeros((cols, *shape), np.float32) if want_levels else None
-            t = Timing()
-            check(lib().sgz_overview_power_view_host(self.h, _np_ptr(power), n, x0, x1, out_columns, _np_ptr(rgba) if want_rgba else None,
-                                                     _np_ptr(out) if want_power else None, _np_ptr(levels) if want_levels else None, C.byref(t)))
-            return rgba, out, levels, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
-        import torch
-        assert power.is_cuda and power.dtype == torch.int64 and power.is_contiguous() and tuple(power.shape[1:]) == (*shape, 4)
-        rgba = torch.empty((cols, self.P, 4), dtype=torch.uint8, device=power.device) if want_rgba else None
-        out = torch.empty((cols, *shape, 4), dtype=torch.int64, device=power.device) if want_power else None
-        levels = torch.empty((cols, *shape), dtype=torch.float32, device=power.device) if want_levels else None
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview_power_view(self.h, power.data_ptr(), n, x0, x1, out_columns, slices, rgba.data_ptr() if want_rgba else None,
-                                                  out.data_ptr() if want_power else None, levels.data_ptr() if want_levels else None, s))
-        return rgba, out, levels
+        return self._overview_view("power", power, out_columns, x0, x1, slices, (want_rgba, want_power, want_levels), stream)
 
     def overview_power_levels(self, records: np.ndarray) -> np.ndarray:
         """sgz_overview_power_levels (host, no GPU): OVERVIEW_POWER_DTYPE records [columns, C, sides, P] (or [C, sides, P]: one column) -> float32
@@ -1621,45 +1541,13 @@ class Plan:
         """sgz_stage_overview_cross: bins -- cuda float32 [frames, pairs, N + 1, 2] (stage_bins of a Phase plan); carry -- cuda int64 [pairs,
         bands, 10], the open column's records (read when held > 0, written when frames stay open).  Returns (cuda records int64 [columns,
         pairs, bands, 10] -- see cross_from_device --, frames left open)."""
-        import torch
-        assert bins.is_cuda and bins.dtype == torch.float32 and bins.is_contiguous()
-        assert tuple(bins.shape[1:]) == (self.C, self.N + 1, 2), tuple(bins.shape)
-        B = self.cross_bands
-        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * B * 10)
-        frames = bins.shape[0]
-        columns, held_out = overview_step(k, held, frames, flush)
-        out = torch.empty((max(columns, 1), self.C, B, 10), dtype=torch.int64, device=bins.device)               # (never a NULL pointer)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview_cross(self.h, bins.data_ptr(), frames, k, held, int(bool(flush)), slices,
-                                             carry.data_ptr() if carry is not None else None, out.data_ptr(), s))
-        return out[:columns], held_out
+        return self._overview_stage("cross", bins, k, held, flush, slices, carry, bands=self.cross_bands, stream=stream)
 
     def overview_cross(self, planar, k: int, stream=None):
         """The cross overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_cross_host -> (records OVERVIEW_CROSS_DTYPE
         [columns, C, bands], timing dict).  planar a cuda tensor: sgz_spectrogram_overview_cross_device, asynchronous -> cuda records int64
         [columns, C, bands, 10].  Fewer samples than a window: None."""
-        B = self.cross_bands
-        if isinstance(planar, np.ndarray):
-            planar = np.ascontiguousarray(planar, np.float32)
-            nch, S = planar.shape
-            columns = -(-self.num_frames(S) // k)
-            out = np.zeros((max(columns, 1), self.C, B), OVERVIEW_CROSS_DTYPE)
-            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
-            t = Timing()
-            st = check(lib().sgz_spectrogram_overview_cross_host(self.h, ptrs, nch, S, k, _np_ptr(out), C.byref(t)))
-            if st == SGZ_SKIPPED_FRAME:
-                return None
-            return out[:columns], {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
-        import torch
-        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
-        S = planar.shape[1]
-        columns = -(-self.num_frames(S) // k)
-        out = torch.empty((max(columns, 1), self.C, B, 10), dtype=torch.int64, device=planar.device)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        st = check(lib().sgz_spectrogram_overview_cross_device(self.h, planar.data_ptr(), planar.stride(0), S, k, out.data_ptr(), s))
-        if st == SGZ_SKIPPED_FRAME:
-            return None
-        return out[:columns]
+        return self._overview_render("cross", planar, k, bands=self.cross_bands, stream=stream)
 
     # the flux overview: the mapped magnitudes reduced along the axis to amplitude, two moments and the rectified difference against the frame before
     def overview_flux_columns(self, mapped, k: int, held: int = 0, flush: bool = True, first_frame: int = 0, slices: int = 0, prev=None, carry=None,
@@ -1669,44 +1557,15 @@ class Plan:
         column's records (read when held > 0, written when frames stay open).  Returns (cuda records int64 [columns, pairs, sides, 11] -- see
         flux_from_device --, frames left open)."""
         import torch
-        assert mapped.is_cuda and mapped.dtype == torch.float32 and mapped.is_contiguous()
-        assert tuple(mapped.shape[1:]) == (self.C, self.sides, self.P), tuple(mapped.shape)
         assert prev is None or (prev.is_cuda and prev.dtype == torch.float32 and prev.is_contiguous() and prev.numel() == self.C * self.sides * self.P)
-        assert carry is None or (carry.is_cuda and carry.dtype == torch.int64 and carry.is_contiguous() and carry.numel() == self.C * self.sides * 11)
-        frames = mapped.shape[0]
-        columns, held_out = overview_step(k, held, frames, flush)
-        out = torch.empty((max(columns, 1), self.C, self.sides, 11), dtype=torch.int64, device=mapped.device)       # (never a NULL pointer)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(lib().sgz_stage_overview_flux(self.h, mapped.data_ptr(), frames, k, held, int(bool(flush)), first_frame, slices,
-                                            prev.data_ptr() if prev is not None else None, carry.data_ptr() if carry is not None else None,
-                                            out.data_ptr(), s))
-        return out[:columns], held_out
+        return self._overview_stage("flux", mapped, k, held, flush, slices, carry, front=(first_frame,),
+                                    mid=(prev.data_ptr() if prev is not None else None,), stream=stream)
 
     def overview_flux(self, planar, k: int, stream=None):
         """The flux overview's render.  planar a numpy array [2 C, S]: sgz_spectrogram_overview_flux_host -> (records OVERVIEW_FLUX_DTYPE
         [columns, C, sides], timing dict).  planar a cuda tensor: sgz_spectrogram_overview_flux_device, asynchronous -> cuda records int64
         [columns, C, sides, 11].  Fewer samples than a window: None."""
-        if isinstance(planar, np.ndarray):
-            planar = np.ascontiguousarray(planar, np.float32)
-            nch, S = planar.shape
-            columns = -(-self.num_frames(S) // k)
-            out = np.zeros((max(columns, 1), self.C, self.sides), OVERVIEW_FLUX_DTYPE)
-            ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
-            t = Timing()
-            st = check(lib().sgz_spectrogram_overview_flux_host(self.h, ptrs, nch, S, k, _np_ptr(out), C.byref(t)))
-            if st == SGZ_SKIPPED_FRAME:
-                return None
-            return out[:columns], {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
-        import torch
-        assert planar.is_cuda and planar.dtype == torch.float32 and planar.stride(1) == 1
-        S = planar.shape[1]
-        columns = -(-self.num_frames(S) // k)
-        out = torch.empty((max(columns, 1), self.C, self.sides, 11), dtype=torch.int64, device=planar.device)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        st = check(lib().sgz_spectrogram_overview_flux_device(self.h, planar.data_ptr(), planar.stride(0), S, k, out.data_ptr(), s))
-        if st == SGZ_SKIPPED_FRAME:
-            return None
-        return out[:columns]
+        return self._overview_render("flux", planar, k, stream=stream)
 
     def overview_flux_hz(self, pixel) -> np.ndarray:
         """sgz_overview_flux_hz (host, no GPU): fractional pixels (a centroid), float64 [...] -> Hz, float64 [...], by linear interpolation of
@@ -1862,11 +1721,10 @@ def render_spectrogram(cfg: dict, planar: np.ndarray, want_lines: bool = False):
     F = S // c.hop if c.algorithm == 1 else lib().sgz_num_frames(S, c.window_size, c.hop)
     rgba = np.zeros((F, c.axis_points, 4), np.uint8)
     lines = np.zeros((F, c.num_pairs, NUM_GRAPHS, c.axis_points, 2), np.float32) if want_lines else None
-    ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
     t = Timing()
-    check(lib().sgz_spectrogram_render(C.byref(c), ptrs, nch, S, _np_ptr(rgba),
+    check(lib().sgz_spectrogram_render(C.byref(c), _channel_ptrs(planar), nch, S, _np_ptr(rgba),
                                        _np_ptr(lines) if want_lines else None, C.byref(t)))
-    return rgba, lines, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+    return rgba, lines, t.asdict()
 
 
 def render_spectrogram_host(plan, planar: np.ndarray, want_lines: bool = False):
@@ -1876,10 +1734,9 @@ def render_spectrogram_host(plan, planar: np.ndarray, want_lines: bool = False):
     F = plan.num_frames(S)
     rgba = np.zeros((F, plan.P, 4), np.uint8)
     lines = np.zeros((F, plan.cfg.num_pairs, NUM_GRAPHS, plan.P, 2), np.float32) if want_lines else None
-    ptrs = (C.c_void_p * nch)(*[planar[i].ctypes.data for i in range(nch)])
     t = Timing()
-    check(lib().sgz_spectrogram_render_host(plan.h, ptrs, nch, S, _np_ptr(rgba), _np_ptr(lines) if want_lines else None, C.byref(t)))
-    return rgba, lines, {"h2d_ms": t.h2d_ms, "kernel_ms": t.kernel_ms, "d2h_ms": t.d2h_ms, "frames": t.frames}
+    check(lib().sgz_spectrogram_render_host(plan.h, _channel_ptrs(planar), nch, S, _np_ptr(rgba), _np_ptr(lines) if want_lines else None, C.byref(t)))
+    return rgba, lines, t.asdict()
 
 
 def stream_step(window_size: int, hop: int, held: int, incoming: int):
@@ -1971,17 +1828,19 @@ class PcmStream:
         return int(lib().sgz_pcm_stream_open_frames(self.h))
 
     # the six overview feeds: `call` is the C call's suffix behind sgz_pcm_stream_feed_overview; mid: what the C call takes between flush and
-    # its outputs
+    # its outputs.  What the outputs are comes from the kind's entry of OVERVIEW_KINDS
     def _feed_overview_into(self, call: str, pcm, nsamples: int, k: int, flush: bool, outputs, capacity_columns: int, timing: bool, mid=()):
         t, c = PcmTiming() if timing else None, C.c_uint64(0)
         st = getattr(lib(), "sgz_pcm_stream_feed_overview" + call)(self.h, _buf_ptr(pcm) if pcm is not None else None, nsamples, k, int(bool(flush)),
-                                                                   *mid, *[_buf_ptr(a) if a is not None else None for a in outputs],
-                                                                   capacity_columns, C.byref(c), C.byref(t) if timing else None)
+                                                                   *mid, *_buf_ptrs(outputs), capacity_columns, C.byref(c),
+                                                                   C.byref(t) if timing else None)
         return st, int(c.value), t
 
-    def _feed_overview(self, call: str, pcm, k: int, flush: bool, nsamples, outputs, mid=()):
-        """outputs: (wanted, the shape of one column, dtype) each, or with a fourth entry, the number of planes [planes, columns, ...] the
-        output has -> the columns that closed of every output, None where not wanted, and the timing dict"""
+    def _feed_overview(self, kind: str, pcm, k: int, flush: bool, nsamples, wants=(), mid=(), planes=None):
+        """kind: of OVERVIEW_KINDS; wants: the flags of its optional outputs in C order; planes: of pct's values -> the columns that closed of
+        every output, None where not wanted, and the timing dict"""
+        kind, cfg = OVERVIEW_KINDS[kind], self.cfg
+        outputs = _overview_outputs(kind, (cfg.num_pairs, _sides(cfg), cfg.axis_points, getattr(self, "cross_bands", 1)), wants, planes)
         if pcm is None:
             n = 0
         else:
@@ -1989,7 +1848,7 @@ class PcmStream:
             n = nbytes // self.frame_bytes if nsamples is None else nsamples
         cols = self.columns_for(n, k, flush)                        # (0 as well for a k the call refuses)
         arrays = [_overview_out(cols, *o) for o in outputs]
-        st, c, t = self._feed_overview_into(call, pcm if n else None, n, k, flush, arrays, cols, True, mid)
+        st, c, t = self._feed_overview_into(kind.suffix, pcm if n else None, n, k, flush, arrays, cols, True, mid)
         check(st)
         assert c == cols, (c, cols)
         return (*[_overview_cut(a, cols, *o) for a, o in zip(arrays, outputs)], t.asdict())
@@ -2001,8 +1860,7 @@ class PcmStream:
     def feed_overview(self, pcm, k: int, flush: bool = False, nsamples: int | None = None, want_rgba: bool = True, want_peaks: bool = False):
         """Feeds nsamples (default: all of pcm; pcm None: none) into the overview at k frames per column and returns the columns that closed:
         (rgba uint8 [columns, P, 4] or None, peaks float32 [columns, pairs, P] or None, timing dict)."""
-        P, pairs = self.cfg.axis_points, self.cfg.num_pairs
-        return self._feed_overview("", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_peaks, (pairs, P), np.float32)])
+        return self._feed_overview("peaks", pcm, k, flush, nsamples, (want_rgba, want_peaks))
 
     def feed_overview_stats_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, stats, means, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); rgba / stats / means: numpy arrays, host torch tensors or None"""
@@ -2013,9 +1871,7 @@ class PcmStream:
         """Feeds nsamples (default: all of pcm; pcm None: none) into the mean overview at k frames per column and returns the columns that
         closed: (rgba uint8 [columns, P, 4] or None, records OVERVIEW_STAT_DTYPE [columns, pairs, P] or None, means float32 [columns,
         pairs, P] or None, timing dict)."""
-        P, pairs = self.cfg.axis_points, self.cfg.num_pairs
-        return self._feed_overview("_stats", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_stats, (pairs, P), OVERVIEW_STAT_DTYPE),
-                                                                       (want_means, (pairs, P), np.float32)])
+        return self._feed_overview("stats", pcm, k, flush, nsamples, (want_rgba, want_stats, want_means))
 
     def feed_overview_pct_into(self, pcm, nsamples: int, k: int, flush: bool, q, rgba, records, values, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); rgba / records / values: numpy arrays, host torch tensors or None;
@@ -2028,10 +1884,8 @@ class PcmStream:
         """Feeds nsamples (default: all of pcm; pcm None: none) into the percentile overview at k frames per column and returns the columns
         that closed: (rgba uint8 [columns, P, 4] or None, records OVERVIEW_PCT_DTYPE [columns, pairs, P] or None, values float32 [nq,
         columns, pairs, P] or None, timing dict)."""
-        P, pairs = self.cfg.axis_points, self.cfg.num_pairs
         qa, qp, nq = _quantiles(q)
-        return self._feed_overview("_pct", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_records, (pairs, P), OVERVIEW_PCT_DTYPE),
-                                                                     (want_values, (pairs, P), np.float32, max(nq, 1))], (qp, nq))
+        return self._feed_overview("pct", pcm, k, flush, nsamples, (want_rgba, want_records, want_values), (qp, nq), max(nq, 1))
 
     def feed_overview_power_into(self, pcm, nsamples: int, k: int, flush: bool, rgba, power, levels, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); rgba / power / levels: numpy arrays, host torch tensors or None"""
@@ -2042,9 +1896,7 @@ class PcmStream:
         """Feeds nsamples (default: all of pcm; pcm None: none) into the power overview at k frames per column and returns the columns that
         closed: (rgba uint8 [columns, P, 4] or None, records OVERVIEW_POWER_DTYPE [columns, pairs, sides, P] or None, levels float32 [columns,
         pairs, sides, P] or None, timing dict).  The stream's decay state is neither read nor advanced."""
-        P, plane = self.cfg.axis_points, (self.cfg.num_pairs, _sides(self.cfg), self.cfg.axis_points)
-        return self._feed_overview("_power", pcm, k, flush, nsamples, [(want_rgba, (P, 4), np.uint8), (want_power, plane, OVERVIEW_POWER_DTYPE),
-                                                                       (want_levels, plane, np.float32)])
+        return self._feed_overview("power", pcm, k, flush, nsamples, (want_rgba, want_power, want_levels))
 
     def set_cross_edges(self, edges) -> None:
         """sgz_pcm_stream_set_cross_edges: the band table of the stream's cross feeds, uint32 [bands + 1]"""
@@ -2059,7 +1911,7 @@ class PcmStream:
     def feed_overview_cross(self, pcm, k: int, flush: bool = False, nsamples: int | None = None):
         """Feeds nsamples (default: all of pcm; pcm None: none) into the cross overview at k frames per column and returns the columns that
         closed: (records OVERVIEW_CROSS_DTYPE [columns, pairs, bands], timing dict).  The stream's decay state is neither read nor advanced."""
-        return self._feed_overview("_cross", pcm, k, flush, nsamples, [(True, (self.cfg.num_pairs, getattr(self, "cross_bands", 1)), OVERVIEW_CROSS_DTYPE)])
+        return self._feed_overview("cross", pcm, k, flush, nsamples)
 
     def feed_overview_flux_into(self, pcm, nsamples: int, k: int, flush: bool, flux, capacity_columns: int, timing: bool = True):
         """the C call as it is: (status, columns_out, PcmTiming or None); flux: a numpy array, a host torch tensor or None"""
@@ -2068,7 +1920,7 @@ class PcmStream:
     def feed_overview_flux(self, pcm, k: int, flush: bool = False, nsamples: int | None = None):
         """Feeds nsamples (default: all of pcm; pcm None: none) into the flux overview at k frames per column and returns the columns that
         closed: (records OVERVIEW_FLUX_DTYPE [columns, pairs, sides], timing dict).  The stream's decay state is neither read nor advanced."""
-        return self._feed_overview("_flux", pcm, k, flush, nsamples, [(True, (self.cfg.num_pairs, _sides(self.cfg)), OVERVIEW_FLUX_DTYPE)])
+        return self._feed_overview("flux", pcm, k, flush, nsamples)
 
     # the eight column lanes (waveform, level, truepeak, loudness, field, band, hist, run): one helper per kind of call, the lane's name picks the C call
     def _lane_set(self, lane: str, m: int, out, capacity_columns, *front) -> None:
@@ -2591,32 +2443,22 @@ def band_colours(records: np.ndarray, channel: int, band_colours, key_rgba8, fre
     return out
 
 
-def _overview_out(cols: int, want, shape, dtype, planes=None):
-    """an overview output's buffer: [columns, *shape], or [planes, columns, *shape]; never an empty array (its pointer may be null)"""
-    if not want:
-        return None
-    return np.zeros((max(cols, 1), *shape) if planes is None else (planes, max(cols, 1), *shape), dtype)
-
-
-def _overview_cut(a, cols: int, want, shape, dtype, planes=None):
-    return None if a is None else a[:cols] if planes is None else a[:, :cols]
-
-
-def _overview_pcm(call: str, cfg, pcm, fmt: int, src_channels: int, k: int, channel_map, nsamples, outputs, front=(), mid=()):
-    """sgz_spectrogram_overview<call>_pcm.  outputs(c): (wanted, the shape of one column, dtype[, planes]) each, from the config; front: what
-    the C call takes between nsamples and k, mid: between k and its outputs -> (status, every output's columns or None where not wanted,
-    timing dict)"""
-    c = _as_config(cfg)
+def _overview_pcm(kind: str, cfg, pcm, fmt: int, src_channels: int, k: int, channel_map, nsamples, wants=(), front=(), mid=(), bands: int = 0,
+                  planes=None):
+    """sgz_spectrogram_overview<suffix>_pcm of a kind of OVERVIEW_KINDS.  wants: the flags of its optional outputs in C order; front: what the C
+    call takes between nsamples and k, mid: between k and its outputs; bands: of the cross table; planes: of pct's values -> (status, every
+    output's columns or None where not wanted, timing dict)"""
+    kind, c = OVERVIEW_KINDS[kind], _as_config(cfg)
     nbytes = pcm.numel() * pcm.element_size() if hasattr(pcm, "data_ptr") else pcm.nbytes
     n = nbytes // (src_channels * PCM_SAMPLE_BYTES[fmt]) if nsamples is None else nsamples
     F = max(0, int(lib().sgz_num_frames(n, c.window_size, c.hop)))
     cols = -(-F // k) if k else 0
-    outs = outputs(c)
+    outs = _overview_outputs(kind, (c.num_pairs, _sides(c), c.axis_points, bands), wants, planes)
     arrays = [_overview_out(cols, *o) for o in outs]
     m, mp = _channel_map(channel_map)
     t = PcmTiming()
-    st = check(getattr(lib(), f"sgz_spectrogram_overview{call}_pcm")(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, *front, k, *mid,
-                                                                     *[_np_ptr(a) if a is not None else None for a in arrays], C.byref(t)))
+    st = check(getattr(lib(), f"sgz_spectrogram_overview{kind.suffix}_pcm")(C.byref(c), _buf_ptr(pcm), fmt, src_channels, mp, n, *front, k, *mid,
+                                                                            *_buf_ptrs(arrays), C.byref(t)))
     if st == SGZ_SKIPPED_FRAME:
         cols = 0
     return (st, *[_overview_cut(a, cols, *o) for a, o in zip(arrays, outs)], t.asdict())
@@ -2626,17 +2468,14 @@ def overview_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None
                  want_peaks: bool = False):
     """One-shot overview of an interleaved PCM buffer (sgz_spectrogram_overview_pcm): (status, rgba or None, peaks or None, timing dict);
     status is SGZ_SKIPPED_FRAME for fewer samples than one window."""
-    return _overview_pcm("", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
-                         lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_peaks, (c.num_pairs, c.axis_points), np.float32)])
+    return _overview_pcm("peaks", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, (want_rgba, want_peaks))
 
 
 def overview_stats_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
                        want_stats: bool = True, want_means: bool = False):
     """One-shot mean overview of an interleaved PCM buffer (sgz_spectrogram_overview_stats_pcm): (status, rgba or None, records
     OVERVIEW_STAT_DTYPE or None, means or None, timing dict); SGZ_SKIPPED_FRAME and empty outputs for fewer samples than a window"""
-    return _overview_pcm("_stats", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
-                         lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_stats, (c.num_pairs, c.axis_points), OVERVIEW_STAT_DTYPE),
-                                    (want_means, (c.num_pairs, c.axis_points), np.float32)])
+    return _overview_pcm("stats", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, (want_rgba, want_stats, want_means))
 
 
 def overview_pct_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, q=0.5, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
@@ -2645,32 +2484,28 @@ def overview_pct_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, q=0.5, chann
     OVERVIEW_PCT_DTYPE or None, values float32 [nq, columns, pairs, P] or None, timing dict); SGZ_SKIPPED_FRAME and empty outputs for fewer
     samples than a window"""
     qa, qp, nq = _quantiles(q)
-    return _overview_pcm("_pct", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
-                         lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_records, (c.num_pairs, c.axis_points), OVERVIEW_PCT_DTYPE),
-                                    (want_values, (c.num_pairs, c.axis_points), np.float32, max(nq, 1))], mid=(qp, nq))
+    return _overview_pcm("pct", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, (want_rgba, want_records, want_values), mid=(qp, nq),
+                         planes=max(nq, 1))
 
 
 def overview_power_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None, want_rgba: bool = True,
                        want_power: bool = True, want_levels: bool = False):
     """One-shot power overview of an interleaved PCM buffer (sgz_spectrogram_overview_power_pcm): (status, rgba or None, records
     OVERVIEW_POWER_DTYPE or None, levels or None, timing dict); SGZ_SKIPPED_FRAME and empty outputs for fewer samples than a window"""
-    return _overview_pcm("_power", cfg, pcm, fmt, src_channels, k, channel_map, nsamples,
-                         lambda c: [(want_rgba, (c.axis_points, 4), np.uint8), (want_power, (c.num_pairs, _sides(c), c.axis_points), OVERVIEW_POWER_DTYPE),
-                                    (want_levels, (c.num_pairs, _sides(c), c.axis_points), np.float32)])
+    return _overview_pcm("power", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, (want_rgba, want_power, want_levels))
 
 
 def overview_cross_pcm(cfg, pcm, fmt: int, src_channels: int, edges, k: int, channel_map=None, nsamples: int | None = None):
     """One-shot cross overview of an interleaved PCM buffer (sgz_spectrogram_overview_cross_pcm): (status, records OVERVIEW_CROSS_DTYPE
     [columns, pairs, bands], timing dict); SGZ_SKIPPED_FRAME and no records for fewer samples than a window"""
     e = _edges(edges)
-    return _overview_pcm("_cross", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, lambda c: [(True, (c.num_pairs, e.size - 1), OVERVIEW_CROSS_DTYPE)],
-                         front=(_np_ptr(e), e.size - 1))
+    return _overview_pcm("cross", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, front=(_np_ptr(e), e.size - 1), bands=e.size - 1)
 
 
 def overview_flux_pcm(cfg, pcm, fmt: int, src_channels: int, k: int, channel_map=None, nsamples: int | None = None):
     """One-shot flux overview of an interleaved PCM buffer (sgz_spectrogram_overview_flux_pcm): (status, records OVERVIEW_FLUX_DTYPE [columns,
     pairs, sides], timing dict); SGZ_SKIPPED_FRAME and no records for fewer samples than a window"""
-    return _overview_pcm("_flux", cfg, pcm, fmt, src_channels, k, channel_map, nsamples, lambda c: [(True, (c.num_pairs, _sides(c)), OVERVIEW_FLUX_DTYPE)])
+    return _overview_pcm("flux", cfg, pcm, fmt, src_channels, k, channel_map, nsamples)
 
 
 def render_spectrogram_pcm(cfg, pcm, fmt: int, src_channels: int, channel_map=None, nsamples: int | None = None, want_lines: bool = False):
